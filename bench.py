@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — nnz/sec of FM mini-batch SGD training on MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C4|C5] [--batch-rows B] [--time-budget S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C4|C5] [--batch-rows B] [--time-budget S] [--dump-outputs DIR]
 
 A "step" is one mini-batch SGD step (forward + backward + update) over one batch of the
 synthetic workload, all inputs resident in HBM before the timed region.
@@ -123,7 +123,50 @@ def parse_args(argv=None):
     ap.add_argument("--log-dir", default=os.environ.get("FMHIP_BENCH_LOG_DIR", ""),
                     help="N > 1: every rank appends its progress to <log-dir>/rank<r>.progress (and to stderr); ranks spawned by "
                          "this file also have their stderr there")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed steps computed to DIR/<name>.npy (rank 0's model after the last timed step, and that "
+                         "step's loss scalars; see dump_outputs).  The warm-up and timed steps then start from the seeded initial "
+                         "parameters, so that the same arguments give the same inputs in every run")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 56 << 20           # --dump-outputs: the parameter rows written (ids, w, V in fp64) stay below this
+DUMP_SEED = 20251015            # ... and, for a model wider than that, the seed of the sampled rows
+
+
+def dump_ids(n1, k):
+    """The feature ids --dump-outputs writes: all of them when their rows fit DUMP_BYTES, else a fixed sample — the lowest ids
+    (the most frequent ones of the Zipf and relabelled Criteo-shaped data) and a seeded draw from the rest."""
+    cap = DUMP_BYTES // ((k + 2) * 8)
+    if n1 <= cap:
+        return np.arange(n1, dtype=np.int32)
+    half = cap // 2
+    rest = np.random.default_rng(DUMP_SEED).choice(n1 - half, cap - half, replace=False)
+    return np.concatenate([np.arange(half), half + np.sort(rest)]).astype(np.int32)
+
+
+def dump_outputs(out_dir, L, ffi, fm, st, wide):
+    """--dump-outputs: what a caller of the SGD step receives, read back after the last timed step — the model (`w0`, `w`
+    (n,), `v` (k, n), as FMModel holds them; n = every feature, or the sample of dump_ids, whose ids are in `ids`) and the
+    step's loss scalars (`step_stats`: sse, sum of residuals, rows, nonzeros, nonfinite predictions).  fp64; `w0` only when
+    the model is staged on the host (reading it back copies the whole table)."""
+    n1, k = fm.num_attribute + 1, fm.num_factor
+    ids = dump_ids(n1, k)
+    w, v = fm.rows(ids)
+    arrays = {"w": w, "v": np.ascontiguousarray(v),
+              "step_stats": np.array([st.sse, st.sum_e, st.rows, st.nnz, st.nonfinite], np.float64)}
+    if len(ids) < n1:
+        arrays["ids"] = ids.astype(np.float64)
+    if not wide:
+        w0 = C.c_double()
+        ffi.check(L.fmhip_model_get_params(fm.handle, C.byref(w0), None, None))
+        arrays["w0"] = np.array([w0.value])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -390,12 +433,21 @@ def run_rank(args, rank, world, local_rank, ctl, json_fd, torch, group=None):
     st = prof = cprof = replicas = None
     kernel_pass_steps = 0
 
+    def restart_from_seed():
+        """--dump-outputs: the initial parameters drawn again from the seed (on every rank), then the W warm-up steps once more,
+        so that what the timed steps start from does not depend on how many untimed steps the clock settle or the N > 1 sweep
+        took.  The draw runs on the device: a host upload would leave the GPU idle long enough to lose the settled clocks."""
+        _ffi.check(L.fmhip_model_init_normal(hm, cfg["seed"] + 1000, 0.0, 0.01))
+        steps_run(0, args.warmup)
+
     # ---- the timed region: exactly K steps between barriers, no event records inside; then the per-kernel pass, the
     # exchange's own timers and the replica check.  A function: at N > 1 it runs TWICE — once with the default plan BEFORE the
     # cut / mode sweep, so that a headline line exists whatever the sweep then does on a node nobody has seen (a mode that hangs
     # over real RCCL must not cost the record), and once with the plan the sweep chose.
     def measure():
         nonlocal elapsed, total_nnz, enqueue_s, st, prof, kernel_pass_steps, cprof, replicas, value, step_ms
+        if args.dump_outputs:
+            restart_from_seed()
         sync()
         barrier()
         t0 = time.perf_counter()
@@ -410,6 +462,9 @@ def run_rank(args, rank, world, local_rank, ctl, json_fd, torch, group=None):
         st = _ffi.Stats()
         _ffi.check(L.fmhip_step_stats(hm, C.byref(st)))
         log("timed region done: %d steps, %.4f ms/step" % (args.steps, elapsed / max(args.steps, 1) * 1e3))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, L, _ffi, fm, st, wide)
+            log("outputs of the timed steps written to %s" % args.dump_outputs)
 
         # ---- per-kernel times: a pass of the same steps right behind the timed region, every kernel of every step between a pair
         # of HIP events on the library's own stream (the records cost ~4 us each between the kernels, nothing inside them)

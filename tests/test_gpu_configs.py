@@ -851,6 +851,46 @@ def test_bench_fallback_exchange_over_torch_distributed():
     assert out["value"] > 0 and out["train"]["nonfinite"] == 0 and out["config"]["batch_rows_per_gpu"] == 100000
 
 
+def test_bench_dump_outputs_are_the_timed_steps_from_the_seeded_start(fmhip, tmp_path):
+    """`bench.py --dump-outputs DIR`: the model after the K timed steps and the last step's loss.  The W warm-up steps and the
+    timed ones start from the parameters drawn on the device from the config's seed however many steps the clock settle took —
+    so the oracle, run over the same W + K batch positions (three batches) from that draw, gives the same arrays.  The line
+    states exactly K steps."""
+    import json
+    from sparkfm_amd import synth
+    rows, batch, steps, warmup = 20000, 8000, 4, 2
+    out_dir = str(tmp_path / "dump")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C3", "--rows", str(rows), "--batch-rows", str(batch),
+           "--steps", str(steps), "--warmup", str(warmup), "--settle", "0.1", "--no-extra", "--no-pmc", "--no-cpu-baseline",
+           "--dump-outputs", out_dir]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    out = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.strip()][-1])
+    assert out["steps"] == steps and out["ms_per_step"] > 0
+    got = {n: np.load(os.path.join(out_dir, n + ".npy")) for n in ("w0", "w", "v", "step_stats")}
+    assert not os.path.exists(os.path.join(out_dir, "ids.npy"))                     # 100k x 32 fits: every row is written
+    assert sum(os.path.getsize(os.path.join(out_dir, f)) for f in os.listdir(out_dir)) <= 64 << 20
+    assert all(a.dtype == np.float64 for a in got.values())
+
+    cfg = synth.CONFIGS["C3"]
+    d = synth.make_config("C3", rows=rows)
+    n1, k = cfg["features"], cfg["k"]
+    fm0 = fmhip.FMModel(n1 - 1, k, seed=cfg["seed"] + 1000, device=0, init_on_device=True)
+    w0, w, v = fm0.w0, fm0.w.copy(), fm0.v.copy()
+    fm0.close()
+    val, y = d["val"].astype(np.float64), d["y"].astype(np.float64)
+    nb = (rows + batch - 1) // batch
+    for j in range(warmup + steps):
+        b = j % nb
+        w0, w, v, sse = oracle.sgd_step(w0, w, v, b * batch, min((b + 1) * batch, rows), d["row_ptr"], d["col"], val, y,
+                                        0.02, 0.0, 1e-4, 1e-4)
+    assert got["v"].shape == (k, n1) and got["w"].shape == (n1,)
+    assert np.linalg.norm(got["v"] - v) / np.linalg.norm(v) < 1e-5
+    assert np.linalg.norm(got["w"] - w) / np.linalg.norm(w) < 1e-5 and abs(got["w0"][0] - w0) < 1e-6
+    assert abs(got["step_stats"][0] - sse) <= 1e-5 * sse and got["step_stats"][2] == min((b + 1) * batch, rows) - b * batch
+
+
 def test_jni_shim_end_to_end_without_a_jvm(fmhip, tmp_path):
     """The JNI shim's model / dataset / training / scoring / communicator natives, driven by tests/jni_harness.c through an
     in-memory JNIEnv (copying arrays, poisoned on release) on the GPU: two SGD epochs, parameters, RMSE, predictions over a

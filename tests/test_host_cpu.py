@@ -381,6 +381,25 @@ def test_feature_order_utilities_are_host_arithmetic():
     assert np.array_equal(ident.relabel(np.array([5, 0, 2], np.int32)), [5, 0, 2])
 
 
+def test_bench_steps_and_dump_sample():
+    """bench.py's arguments: --steps is the count of timed steps (at least one: ms_per_step divides by it).  --dump-outputs
+    writes every parameter row of a model that fits its 64 MB, and otherwise the same sample of ids in every run — the lowest
+    ids and a seeded draw from the rest, sorted and distinct — within it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "0", "--dump-outputs", "out"])
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == "out" and bench.parse_args([]).dump_outputs == ""
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    assert np.array_equal(bench.dump_ids(100_000, 32), np.arange(100_000))            # C3: the whole model
+    for n1, k in ((1_000_000, 32), (1 << 25, 64)):                                     # C4, C5: a sample
+        ids = bench.dump_ids(n1, k)
+        assert np.array_equal(ids, bench.dump_ids(n1, k)) and ids.dtype == np.int32
+        assert (np.diff(ids) > 0).all() and ids[0] == 0 and ids[-1] < n1 and ids[len(ids) // 2 - 1] == len(ids) // 2 - 1
+        assert len(ids) * (k + 2) * 8 <= 60 << 20 and len(ids) > 100_000
+
+
 def test_bench_roofline_helpers():
     """bench.py's byte accounting and ceilings (pure arithmetic): ceilings stay between the Infinity-Cache and the L2
     gather rates, grow with the L2 hit rate, fall back to the HBM gather rate only when nothing is known about a table
