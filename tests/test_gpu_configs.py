@@ -184,7 +184,7 @@ def test_c5_criteo_shape_sgd(fmhip, c5, regs, flat, lazy):
     fm.close()
 
 
-@pytest.mark.parametrize("k", [16, 32])
+@pytest.mark.parametrize("k", [16, 32, 200, 256])
 def test_lazy_decay_long_run_and_refold(fmhip, k):
     """Lazy weight decay over many steps: 300 steps with strong decay on a wide model (the scale drops far
     enough to be folded back into the tables at least once) track the oracle's eager update; switching to a
@@ -770,7 +770,7 @@ def test_als_refuses_rows_with_a_repeated_feature(fmhip):
 
 @pytest.mark.parametrize("n1", [30000, 700])
 @pytest.mark.parametrize("k,regs", [(8, (0.01, 1e-3, 1e-3)), (32, (0.0, 1e-3, 2e-3)), (32, (0.0, 0.0, 0.0)), (64, (0.01, 0.0, 1e-3)),
-                                    (100, (0.0, 1e-3, 1e-3))])
+                                    (100, (0.0, 1e-3, 1e-3)), (200, (0.0, 1e-3, 2e-3)), (256, (0.01, 1e-3, 1e-3))])
 def test_where_the_update_runs_does_not_change_a_bit(fmhip, k, regs, n1):
     """Three places for the same update: a launch of its own (keys 10 = 11 = 0), inside the fixup launch beside the
     fixups (key 11, the default; taken when the update is the dense pass: n1 = 700) and inside the column walk's

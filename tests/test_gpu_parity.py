@@ -197,7 +197,7 @@ def test_row_blocked_transposes(fmhip, rb):
     L = _ffi.load()
     try:
         L.fmhip_tune(_ffi.TUNE_ROW_BLOCK, rb)
-        for k in (8, 32, 64):
+        for k in (8, 32, 64, 200):
             a = random_problem(700 + k, 900, 150, k, 0, 25, empty_rows=(2, 450))
             for r in range(900):                                    # feature 1 in (almost) every row: many pieces
                 s = slice(a["row_ptr"][r], a["row_ptr"][r + 1])
@@ -253,6 +253,13 @@ def hot_problem(seed, n_rows, n1, k, n_hot, dup_feature=None, zero_feature=None,
             idx.append(hot_ids[zero_feature]); x.append(0.0)
         perm = rng.permutation(len(idx))
         rows.append(np.asarray(idx, np.int32)[perm]); vals.append(np.asarray(x)[perm])
+    for f_ in hot_ids[n_hot - n_low:]:
+        # a feature drawn at <= 9 % can still reach 10 % of the rows by chance (seed 556: 406 of 4000), and then it belongs in
+        # page 0: take it out of the rows past the (n_rows - 1) // 10-th that hold it, so that it stays below the mark
+        has = [r for r in range(n_rows) if (rows[r] == f_).any()]
+        for r in has[(n_rows - 1) // 10:]:
+            keep = rows[r] != f_
+            rows[r], vals[r] = rows[r][keep], vals[r][keep]
     row_ptr = np.zeros(n_rows + 1, np.int64)
     row_ptr[1:] = np.cumsum([len(r) for r in rows])
     return dict(k=k, n1=n1, w0=0.25, w=rng.normal(0, 0.1, n1), v=rng.normal(0, 0.1, (k, n1)), row_ptr=row_ptr,
@@ -264,7 +271,8 @@ def hot_problem(seed, n_rows, n1, k, n_hot, dup_feature=None, zero_feature=None,
                                                       (8, 12, 0, 1, 3), (32, 48, None, None, 3), (32, 41, 20, 30, 2),
                                                       (64, 45, 3, None, 3), (16, 35, None, 1, 3), (100, 40, 25, None, 3), (32, 70, 50, None, 4),
                                                       (64, 64, None, None, 4), (32, 100, None, None, 8), (64, 128, 5, None, 8),
-                                                      (32, 90, 60, 70, 6)])
+                                                      (32, 90, 60, 70, 6), (200, 20, None, None, 3), (256, 40, 25, 30, 4),
+                                                      (129, 16, 0, 1, 2)])
 @pytest.mark.parametrize("flat", [0, 1])
 def test_dense_hot_block(fmhip, request, k, n_hot, dup, zero, pages, flat):
     """fmhip_tune(_ffi.TUNE_HOT_BLOCK, 1): the most frequent features (>= 10 % of the rows, none that occurs twice in a row or with a stored
@@ -335,7 +343,7 @@ def test_dense_hot_block(fmhip, request, k, n_hot, dup, zero, pages, flat):
     fm.close()
 
 
-@pytest.mark.parametrize("k,n_hot,n_low", [(32, 30, 27), (64, 12, 10), (16, 40, 39)])
+@pytest.mark.parametrize("k,n_hot,n_low", [(32, 30, 27), (64, 12, 10), (16, 40, 39), (256, 30, 27)])
 def test_dense_hot_block_with_a_thin_first_page(fmhip, k, n_hot, n_low):
     """Few features pass the 10 % mark of the two-sided page, many the 5 % mark of the gradient-side pages: page 0 is
     partly (or, with a single 10 % feature, not at all: then there is no hot block) filled, the others follow behind its
@@ -454,7 +462,7 @@ def test_dense_hot_block_chunked_backward(fmhip):
     fm.close()
 
 
-@pytest.mark.parametrize("k,hot", [(32, 1), (32, 0), (64, 1), (16, 1)])
+@pytest.mark.parametrize("k,hot", [(32, 1), (32, 0), (64, 1), (16, 1), (256, 1), (200, 0)])
 def test_band_affine_placement_of_the_backward(fmhip, request, k, hot):
     """fmhip_model_tune(m, _ffi.TUNE_XCD_PLACEMENT, 2): the whole-batch backward takes its ranges from per-XCD lists — the ranges of long columns
     that fall into an XCD's own row bands first (fmhip_dataset.hip: plan_bands) — and forms no wave sums.  Which slot walks a
@@ -576,7 +584,7 @@ def test_single_nonzero_rows_have_exactly_zero_interaction(fmhip):
     fm.close()
 
 
-@pytest.mark.parametrize("k,flat", [(16, 0), (32, 0), (32, 1), (64, 0), (100, 0)])
+@pytest.mark.parametrize("k,flat", [(16, 0), (32, 0), (32, 1), (64, 0), (100, 0), (127, 1), (200, 0), (200, 1), (256, 0), (256, 1)])
 def test_row_lengths_around_the_step_boundaries(fmhip, k, flat):
     """The forward walks a row 8 (k <= 64) or 16 entries per step; through a buffer view the row's last, partial step is a
     full step whose dead entries are id -1 with value 0, and the next step's entries are requested a step ahead; flat
@@ -643,7 +651,7 @@ def test_hot_columns_split_over_many_ranges(fmhip):
     fm.close()
 
 
-@pytest.mark.parametrize("k", [4, 16, 32, 64])
+@pytest.mark.parametrize("k", [4, 16, 32, 64, 129, 256])
 def test_column_lengths_around_the_range_and_wave_boundaries(fmhip, k):
     """Columns of every length 1..700 (ranges are 64 entries, a slot finishes a column that ends
     <= 16 entries behind its range, a wave sums 64/LPN ranges when they lie in one column): every
@@ -699,7 +707,7 @@ def test_sgd_epochs_track_the_oracle(fmhip, k, batch_rows):
     fm.close()
 
 
-@pytest.mark.parametrize("k", [16, 32, 64])
+@pytest.mark.parametrize("k", [16, 32, 64, 200, 256])
 def test_rows_only_apply_for_wide_models(fmhip, k):
     """Without weight decay a step may update just the rows its batch touched (a model far wider than a
     batch: the dense pass would rewrite every other row unchanged).  Same parameters, bit for bit, as
@@ -1114,6 +1122,18 @@ def test_random_shapes_property(fmhip, flat):
         L.fmhip_tune(_ffi.TUNE_FLAT_ADDRESS, 0)
 
 
+@pytest.mark.parametrize("flat", [0, 1])
+def test_random_shapes_property_of_wide_models(fmhip, flat):
+    """The same property over models of 65..256 factors (Kp = 128 and 256, packed rows and full ones), seeds of their own."""
+    from sparkfm_amd import _ffi
+    L = _ffi.load()
+    L.fmhip_tune(_ffi.TUNE_FLAT_ADDRESS, flat)
+    try:
+        _random_shapes(fmhip, L, seed=20261015, cases=16, ks=(65, 100, 128, 129, 200, 256))
+    finally:
+        L.fmhip_tune(_ffi.TUNE_FLAT_ADDRESS, 0)
+
+
 def _random_shapes(fmhip, L, seed=20261003, cases=40, skip_diverged=False, ks=(1, 2, 5, 8, 13, 16, 32, 40, 64)):
     rng = np.random.default_rng(seed)
     for case in range(cases):
@@ -1246,7 +1266,7 @@ def test_two_ranks_on_one_gpu(fmhip, tmp_path, overlap, k):
     assert float(r0["w0"]) == pytest.approx(w0, rel=1e-5, abs=1e-7)
 
 
-@pytest.mark.parametrize("k,flat", [(32, 0), (32, 1), (64, 0), (128, 0), (256, 0)])
+@pytest.mark.parametrize("k,flat", [(32, 0), (32, 1), (64, 0), (128, 0), (256, 0), (128, 1), (256, 1)])
 def test_the_residual_rides_in_the_p_row_exactly(fmhip, k, flat):
     """k == Kp leaves a P row no spare slot, so the forward writes the 32 bits of e into the low mantissa bits of the row's first
     floats and the backward reads them back from the row it gathers anyway (fm_device.h: no e gather).  e must arrive EXACTLY:

@@ -50,23 +50,38 @@ def run_case(cfg, tmp_path, timeout=600):
 def test_eight_ranks_dense_and_sharded(tmp_path, exchange, fractions):
     """803 feature rows over 8 ranks (n+1 is no multiple of 8: the top share reaches into the slack rows), 0 / 1 / 4 cuts, both
     dense modes; replicas bit-identical, same collectives on all 8 ranks, the oracle matched (the worker asserts all three)."""
-    s = run_case(case8(exchange=exchange, fractions=fractions), tmp_path)
-    assert s["world"] == 8 and s["steps"] == 4 and s["rows"] == 200          # the last global batch: rank 0's 200 rows, seven ranks contribute zeros
+    cfg = case8(exchange=exchange, fractions=fractions)
+    check_dense_or_sharded(run_case(cfg, tmp_path), cfg)
+
+
+def padded_factors(k):
+    """The model's padded row width Kp (sparkfm_amd/csrc/fm_forward.hip: padded_factors): 32, 64, 128 or 256 floats."""
+    kp = 32
+    while kp < k:
+        kp *= 2
+    return kp
+
+
+def check_dense_or_sharded(s, cfg):
+    """The eight-rank summary of a dense or sharded case: steps, rows, the oracle, and the collectives each mode issues."""
+    world, exchange, fractions = len(cfg["rows"]), cfg["exchange"], cfg["fractions"]
+    assert s["world"] == world and s["steps"] == 4 and s["rows"] == 200          # the last global batch: rank 0's 200 rows, seven ranks contribute zeros
     assert s["rel_err_v"] <= 1e-5 and s["rel_err_w"] <= 1e-5
     calls = np.array(s["calls"], np.int64).reshape(-1, 2)
     n_int = len([c for c in s["cuts"] if c > 0]) + 1
     assert len(s["cuts"]) == len(fractions)
-    steps = 2 * 4
+    steps = cfg["epochs"] * 4
     if exchange == "dense":
         sums = calls[calls[:, 0] == 0]
         assert len(sums) == steps * (1 + (1 if n_int == 1 else 3 * n_int))
     else:
-        assert all(c % 8 == 0 for c in s["cuts"])                               # equal shares: interval edges at multiples of the world
+        assert all(c % world == 0 for c in s["cuts"])                           # equal shares: interval edges at multiples of the world
         for kind in (4, 5):
             seg = calls[calls[:, 0] == kind][:, 1]
             assert len(seg) == steps * n_int
-            # per step the shares of one rank add up to ceil(803 / 8) = 101 rows of 32 floats: 808 > 803 rows — the slack rows
-            assert seg.reshape(steps, -1).sum(axis=1).tolist() == [101 * 32] * steps
+            # per step the shares of one rank add up to ceil(803 / 8) = 101 rows of Kp floats: 808 > 803 rows — the slack rows
+            share = -(-cfg["n1"] // world) * padded_factors(cfg["k"])
+            assert seg.reshape(steps, -1).sum(axis=1).tolist() == [share] * steps
 
 
 @pytest.mark.parametrize("fractions,shuffle,stepwise,k,reverse_ids", [([0.3], None, False, 32, False), ([0.05, 0.15, 0.3, 0.55], 11, False, 32, False),
