@@ -437,8 +437,9 @@ int fmhip_sgd_step(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, double eta
     WriteLock lock(m);
     TRY(check_train(m, d));
     TRY(check_batch(d, batch));
+    const Sgd sgd{eta, reg0, regw, regv};
     FusedPlan fp{};
-    const bool fused = plan_fused(m, d, batch, eta, reg0, regw, regv, &fp);
+    const bool fused = plan_fused(m, d, batch, sgd, &fp);
     TRY(step_compute(m, d, batch, nullptr, fused ? &fp : nullptr));
     if (stats) {
         memset(stats, 0, sizeof *stats);
@@ -446,7 +447,7 @@ int fmhip_sgd_step(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, double eta
         stats->nnz = d->batches[(size_t)batch].nnz_total;
         stats->steps = 1;
     }
-    return fused ? finish_fused(m, fp) : step_apply(m, eta, reg0, regw, regv, d, batch);
+    return fused ? finish_fused(m, fp) : step_apply(m, sgd, d, batch);
 }
 
 int fmhip_sgd_epoch(fmhip_model_t m, fmhip_dataset_t d, double eta, double reg0, double regw, double regv,
@@ -457,12 +458,13 @@ int fmhip_sgd_epoch(fmhip_model_t m, fmhip_dataset_t d, double eta, double reg0,
     if (order)
         for (int64_t j = 0; j < nb; ++j) TRY(check_batch(d, order[j]));
     HIP_TRY(hipMemsetAsync(m->acc.p, 0, 4 * sizeof(double), m->stream));
+    const Sgd sgd{eta, reg0, regw, regv};
     for (int64_t j = 0; j < nb; ++j) {
         const int64_t b = order ? order[j] : j;
         FusedPlan fp{};
-        const bool fused = plan_fused(m, d, b, eta, reg0, regw, regv, &fp);
+        const bool fused = plan_fused(m, d, b, sgd, &fp);
         TRY(step_compute(m, d, b, m->acc.p, fused ? &fp : nullptr));
-        TRY(fused ? finish_fused(m, fp) : step_apply(m, eta, reg0, regw, regv, d, b));
+        TRY(fused ? finish_fused(m, fp) : step_apply(m, sgd, d, b));
     }
     if (stats) {
         memset(stats, 0, sizeof *stats);
@@ -664,7 +666,7 @@ int fmhip_step_apply(fmhip_model_t m, double eta, double reg0, double regw, doub
     WriteLock lock(m);
     if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
     TRY(set_device(m->device));
-    return step_apply(m, eta, reg0, regw, regv);
+    return step_apply(m, Sgd{eta, reg0, regw, regv});
 }
 
 int fmhip_step_stats(fmhip_model_t m, fmhip_stats *stats) {

@@ -38,6 +38,7 @@
 #include <rocprim/device/device_select.hpp>
 
 #include <algorithm>
+#include <array>
 #include <cstring>
 #include <mutex>
 
@@ -390,16 +391,38 @@ struct Region {
     size_t n;
 };
 
+// the all-reduce regions of the feature interval [lo, hi) of a gradient (the packed one, or a compact one whose rows are
+// the interval's positions): its G_V rows of kp floats, its G_w and G_b entries.  The head interval's G_w region starts at
+// the statistics scalars in front of it (head_base)
+std::array<Region, 3> slice_regions(float *GV, float *Gw, float *Gb, float *head_base, int64_t lo, int64_t hi, size_t kp, bool head) {
+    const size_t n = (size_t)(hi - lo);
+    return {{{GV + (size_t)lo * kp, n * kp}, {head ? head_base : Gw + lo, n + (head ? (size_t)kGradHead : 0)}, {Gb + lo, n}}};
+}
+
+// Profiling spans of a step (pr NULL: not profiling): a collective (`coll`, the c0 / c1 events) or an interval's update (a0 / a1)
+// on stream `s`.  span_begin hands out the span's slot, -1 when the step's event set has none left; span_end closes it
+int span_begin(CommProf *pr, bool coll, hipStream_t s, int &slot) {
+    slot = -1;
+    if (!pr) return FMHIP_OK;
+    int &n = coll ? pr->n_coll : pr->n_apply;
+    if (n >= (coll ? kProfColl : kMaxCuts + 1)) return FMHIP_OK;
+    slot = n++;
+    HIP_TRY(hipEventRecord((coll ? pr->c0 : pr->a0)[slot], s));
+    return FMHIP_OK;
+}
+
+int span_end(CommProf *pr, bool coll, hipStream_t s, int slot) {
+    if (slot >= 0) HIP_TRY(hipEventRecord((coll ? pr->c1 : pr->a1)[slot], s));
+    return FMHIP_OK;
+}
+
 // The all-reduce of up to three regions of the packed gradient (one grouped call) on the comm stream, behind `after`
 // (an event of the compute stream); `done` is recorded behind it.
 int reduce_regions(fmhip_model_t m, fmhip_comm_t c, const Region *reg, int n_reg, hipEvent_t after, hipEvent_t done, CommProf *pr) {
     HIP_TRY(hipEventRecord(after, m->stream));
     HIP_TRY(hipStreamWaitEvent(c->cs, after, 0));
-    int pi = -1;
-    if (pr && pr->n_coll < kProfColl) {
-        pi = pr->n_coll++;
-        HIP_TRY(hipEventRecord(pr->c0[pi], c->cs));
-    }
+    int pi;
+    TRY(span_begin(pr, true, c->cs, pi));
     size_t bytes = 0;
     const bool group = n_reg > 1 && !c->ext;      // RCCL: the regions of an interval travel as one grouped call
     if (group) NCCL_TRY(rccl().GroupStart());
@@ -420,9 +443,48 @@ int reduce_regions(fmhip_model_t m, fmhip_comm_t c, const Region *reg, int n_reg
     } else {
         TRY(emu_delay(c, (double)bytes, c->cs));
     }
-    if (pi >= 0) HIP_TRY(hipEventRecord(pr->c1[pi], c->cs));
+    TRY(span_end(pr, true, c->cs, pi));
     HIP_TRY(hipEventRecord(done, c->cs));
     c->prof_bytes += c->profiling ? (int64_t)bytes : 0;
+    return FMHIP_OK;
+}
+
+// |B| first: every interval's update divides by the GLOBAL row count, so this rank's `rows` are written to the device float
+// `slot` and summed over the ranks on their own (4 bytes, hidden under the forward) instead of waiting for the head in the last
+// message.  on_comm_stream: on the collectives' stream, behind an event hop; else on the compute stream itself
+int exchange_row_count(fmhip_model_t m, fmhip_comm_t c, float *slot, float rows, bool on_comm_stream) {
+    hipLaunchKernelGGL(k_set_float, dim3(1), dim3(1), 0, m->stream, slot, rows);
+    HIP_TRY(hipGetLastError());
+    if (!on_comm_stream) return collective(c, slot, 1, FMHIP_COLL_SUM_F32, m->stream);
+    HIP_TRY(hipEventRecord(c->ev_rows, m->stream));
+    HIP_TRY(hipStreamWaitEvent(c->cs, c->ev_rows, 0));
+    return collective(c, slot, 1, FMHIP_COLL_SUM_F32, c->cs);
+}
+
+// the dense and pipelined modes' step on a rank that has run out of rows: it contributes zeros (row count 0 included)
+int zero_contribution(fmhip_model_t m) {
+    HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
+    m->grad_dirty = true;
+    m->last_nnz = m->last_rows = 0;
+    return FMHIP_OK;
+}
+
+// Update every interval as its slice arrives (identical on all ranks: replicas stay bit-identical).  The compute stream waits
+// for the slices of the intervals `first` down to 0 in turn (wait = false: the collectives ran on the compute stream itself).
+// Each group of apply_groups is updated behind the wait for its lowest interval: apply(lo, hi, last), last = the group that
+// ends at interval 0.  Intervals of less than an eighth of total_rows share the next one's launch (a launch costs more than they do)
+template <class Apply>
+int apply_as_arrived(fmhip_model_t m, fmhip_comm_t c, const std::vector<int64_t> &edges, int64_t total_rows, int first, bool wait,
+                     Apply apply) {
+    const std::vector<ApplyGroup> groups = apply_groups(edges, total_rows, first);
+    size_t g = 0;
+    for (int i = first; i >= 0; --i) {
+        if (wait) HIP_TRY(hipStreamWaitEvent(m->stream, c->ev_done[i], 0));
+        if (g < groups.size() && groups[g].at == i) {
+            TRY(apply(groups[g].lo, groups[g].hi, i == 0));
+            ++g;
+        }
+    }
     return FMHIP_OK;
 }
 
@@ -583,8 +645,7 @@ int plan_touched(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int64_t cap
 // the backward of the next interval; an interval gets the rows-only update (lazy weight decay: the tables' scale moves with
 // the last slice) as soon as its slice has arrived.  Nothing is sized on the device: no read-back, no host synchronisation.
 // Replicas stay bit-identical: same U, same sums, same update.
-int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, double eta, double reg0, double regw, double regv,
-                    int64_t position) {
+int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, const Sgd &sgd, int64_t position) {
     const bool live = batch >= 0;
     // (no plan at all is a state every rank shares — the plan is collective — so this returns on all of them alike; a model
     // of another width than the plan's can only be THIS rank's mistake: local_checks turns it into a zero contribution,
@@ -593,7 +654,7 @@ int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
         return fail(FMHIP_ERR_INVALID, "the touched-rows exchange is not planned: call fmhip_dp_plan (every rank)");
     const bool foreign = c->msg_kp != m->Kp;
     if (foreign && live) return fail(FMHIP_ERR_INVALID, "the touched-rows exchange was planned for rows of %d floats, this model has %d", c->msg_kp, m->Kp);
-    if (!lazy_decay_ok(m, eta, regw, regv))
+    if (!lazy_decay_ok(m, sgd))
         return fail(FMHIP_ERR_UNSUPPORTED, "the touched-rows exchange needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)");
     const bool packed_dirty = m->grad_dirty;      // this step neither writes nor cleans the model's packed gradient
     const int64_t t = position >= 0 ? position : c->t_cursor;
@@ -602,19 +663,10 @@ int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
     const auto &ts = c->tsteps[(size_t)t];
     const CompactLayout L(ts.n_u, c->msg_kp);
     const GradView view{c->cg, c->cg + L.gw, c->cg + L.gb, c->cg + L.gv, ts.cdst, ts.hot_pos};
-    const float my_rows = live ? (float)d->batches[(size_t)batch].rows : 0.f;
-    hipLaunchKernelGGL(k_set_float, dim3(1), dim3(1), 0, m->stream, c->rows_dev, my_rows);
-    HIP_TRY(hipGetLastError());
     // one interval (no cuts): nothing can overlap, so both collectives run on the compute stream itself — no event hops
     // between the streams, which cost a one-rank step ~40 us of idle time (profiles/r04_experiments.md)
     const bool serial = c->cuts.empty();
-    if (serial) {
-        TRY(collective(c, c->rows_dev, 1, FMHIP_COLL_SUM_F32, m->stream));
-    } else {
-        HIP_TRY(hipEventRecord(c->ev_rows, m->stream));
-        HIP_TRY(hipStreamWaitEvent(c->cs, c->ev_rows, 0));
-        TRY(collective(c, c->rows_dev, 1, FMHIP_COLL_SUM_F32, c->cs));
-    }
+    TRY(exchange_row_count(m, c, c->rows_dev, live ? (float)d->batches[(size_t)batch].rows : 0.f, !serial));
     if (live) {
         // the packed gradient is not written by this step: a pending memset of it (8.9 GB at C5's width) would be wasted
         m->grad_dirty = false;
@@ -629,17 +681,8 @@ int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
     }
     CommProf *pr = next_prof(c);
     // intervals of feature ids [edge[i], edge[i+1]) = rows [pe[i], pe[i+1]) of the compact buffer, from the top down
-    std::vector<int64_t> edge{0};
-    std::vector<int64_t> pe{0};
-    for (size_t i = 0; i < c->cuts.size(); ++i) {
-        const int64_t x = c->cuts[i];
-        if (x > edge.back() && x < m->n1) {
-            edge.push_back(x);
-            pe.push_back(ts.cut_pos[i]);
-        }
-    }
-    edge.push_back(m->n1);
-    pe.push_back(ts.n_u);
+    const CompactEdges ce = compact_edges(c->cuts, m->n1, ts.cut_pos, ts.n_u);
+    const std::vector<int64_t> &edge = ce.edge, &pe = ce.pe;
     const int n_int = (int)edge.size() - 1;
     for (int i = n_int - 1; i >= 0; --i) {
         const bool last = i == 0;
@@ -651,74 +694,47 @@ int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
             m->grad_dirty = packed_dirty;
             TRY(rc);
         }
-        const size_t plo = (size_t)pe[(size_t)i], phi = (size_t)pe[(size_t)i + 1];
         if (serial) {
-            int pi = -1;
-            if (pr && pr->n_coll < kProfColl) {
-                pi = pr->n_coll++;
-                HIP_TRY(hipEventRecord(pr->c0[pi], m->stream));
-            }
+            int pi;
+            TRY(span_begin(pr, true, m->stream, pi));
             TRY(collective(c, c->cg, L.total, FMHIP_COLL_SUM_F32, m->stream));
             TRY(emu_delay(c, (double)L.total * sizeof(float), m->stream, c->cg, L.total));
-            if (pi >= 0) HIP_TRY(hipEventRecord(pr->c1[pi], m->stream));
+            TRY(span_end(pr, true, m->stream, pi));
             if (c->profiling) c->prof_bytes += (int64_t)(L.total * sizeof(float));
         } else if (n_int == 1) {
             const Region whole[1] = {{c->cg, L.total}};
             TRY(reduce_regions(m, c, whole, 1, c->ev_ready[i], c->ev_done[i], pr));
         } else {
-            // the interval's G_V rows, G_w and G_b entries; the lowest interval's G_w region starts at the scalars in front of it
-            const Region reg[3] = {{view.GV + plo * (size_t)c->msg_kp, (phi - plo) * (size_t)c->msg_kp},
-                                   {last ? c->cg : view.Gw + plo, (phi - plo) + (last ? (size_t)kGradHead : 0)},
-                                   {view.Gb + plo, phi - plo}};
-            TRY(reduce_regions(m, c, reg, 3, c->ev_ready[i], c->ev_done[i], pr));
+            const auto reg = slice_regions(view.GV, view.Gw, view.Gb, c->cg, pe[(size_t)i], pe[(size_t)i + 1], (size_t)c->msg_kp, last);
+            TRY(reduce_regions(m, c, reg.data(), 3, c->ev_ready[i], c->ev_done[i], pr));
         }
     }
     m->bw_next_hi = -1;
     if (pr) HIP_TRY(hipEventRecord(pr->wait_a, m->stream));
-    int64_t pend_hi = -1;
-    for (int i = n_int - 1; i >= 0; --i) {
-        const int64_t plo = pe[(size_t)i], phi = pe[(size_t)i + 1];
-        if (pend_hi < 0) pend_hi = phi;
-        const bool last = i == 0;
-        if (!serial) HIP_TRY(hipStreamWaitEvent(m->stream, c->ev_done[i], 0));
+    TRY(apply_as_arrived(m, c, pe, ts.n_u, n_int - 1, !serial, [&](int64_t plo, int64_t phi, bool last) -> int {
         if (foreign) {
             // this rank only kept the peers' collectives company: the compact buffer must be clean for the next step, its
             // rows mean nothing to a model of another width
             if (last) HIP_TRY(hipMemsetAsync(c->cg, 0, L.total * sizeof(float), m->stream));
-            continue;
+            return FMHIP_OK;
         }
-        if (!last && (pend_hi - plo) * 8 < ts.n_u) continue;      // small slices share the next one's launch
         if (last)       // the step's global sums where fmhip_step_stats / fmhip_dp_epoch read them
             HIP_TRY(hipMemcpyAsync(m->scal(), c->cg, (size_t)kScalars * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
-        if (pr) HIP_TRY(hipEventRecord(pr->a0[pr->n_apply++], m->stream));
-        TRY(step_apply_rows(m, eta, reg0, regw, regv, ts.uni, (int32_t)(pend_hi - plo), c->rows_dev, &view, plo, last));
-        if (pr) HIP_TRY(hipEventRecord(pr->a1[pr->n_apply - 1], m->stream));
-        pend_hi = -1;
-    }
+        int ai;
+        TRY(span_begin(pr, false, m->stream, ai));
+        TRY(step_apply_rows(m, sgd, ts.uni, (int32_t)(phi - plo), c->rows_dev, &view, plo, last));
+        return span_end(pr, false, m->stream, ai);
+    }));
     if (pr) HIP_TRY(hipEventRecord(pr->wait_b, m->stream));
     m->grad_dirty = packed_dirty;
     c->t_cursor = (t + 1) % (int64_t)c->tsteps.size();
     return FMHIP_OK;
 }
 
-int dp_step_dense(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, double eta, double reg0, double regw, double regv) {
+int dp_step_dense(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, const Sgd &sgd) {
     const bool live = batch >= 0;
-    // |B| first: every interval's update divides by the GLOBAL row count, so it is exchanged on its own (4 bytes,
-    // hidden under the forward) instead of waiting for the head in the last message
-    const float my_rows = live ? (float)d->batches[(size_t)batch].rows : 0.f;
-    hipLaunchKernelGGL(k_set_float, dim3(1), dim3(1), 0, m->stream, c->rows_dev, my_rows);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_rows, m->stream));
-    HIP_TRY(hipStreamWaitEvent(c->cs, c->ev_rows, 0));
-    TRY(collective(c, c->rows_dev, 1, FMHIP_COLL_SUM_F32, c->cs));
-    if (live) {
-        TRY(step_forward(m, d, batch));
-    } else {
-        // out of rows: contribute zeros (row count 0 included)
-        HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
-        m->grad_dirty = true;
-        m->last_nnz = m->last_rows = 0;
-    }
+    TRY(exchange_row_count(m, c, c->rows_dev, live ? (float)d->batches[(size_t)batch].rows : 0.f, true));
+    TRY(live ? step_forward(m, d, batch) : zero_contribution(m));
     CommProf *pr = next_prof(c);
     // intervals [edge[i], edge[i+1]) from the top down; the lowest one carries the statistics scalars
     const std::vector<int64_t> edge = interval_edges(c->cuts, m->n1, 0);
@@ -731,29 +747,18 @@ int dp_step_dense(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_
             const Region whole[1] = {{m->grad, m->grad_floats()}};
             TRY(reduce_regions(m, c, whole, 1, c->ev_ready[i], c->ev_done[i], pr));
         } else {
-            // G_V rows, G_w and G_b of the interval; the lowest interval's G_w region starts at the scalars in front of it
-            const Region reg[3] = {{m->GV() + (size_t)lo * m->Kp, (size_t)(hi - lo) * m->Kp},
-                                   {last ? m->grad : m->Gw() + lo, (size_t)(hi - lo) + (last ? (size_t)kGradHead : 0)},
-                                   {m->Gb() + lo, (size_t)(hi - lo)}};
-            TRY(reduce_regions(m, c, reg, 3, c->ev_ready[i], c->ev_done[i], pr));
+            const auto reg = slice_regions(m->GV(), m->Gw(), m->Gb(), m->grad, lo, hi, (size_t)m->Kp, last);
+            TRY(reduce_regions(m, c, reg.data(), 3, c->ev_ready[i], c->ev_done[i], pr));
         }
     }
     m->bw_next_hi = -1;
     if (pr) HIP_TRY(hipEventRecord(pr->wait_a, m->stream));
-    // update every interval as its slice arrives (identical on all ranks: replicas stay bit-identical); intervals of
-    // less than an eighth of the rows wait for the next one and share its launch (a launch costs more than they do)
-    int64_t pend_hi = -1;
-    for (int i = n_int - 1; i >= 0; --i) {
-        const int64_t lo = edge[(size_t)i], hi = edge[(size_t)i + 1];
-        if (pend_hi < 0) pend_hi = hi;
-        const bool last = i == 0;
-        HIP_TRY(hipStreamWaitEvent(m->stream, c->ev_done[i], 0));
-        if (!last && (pend_hi - lo) * 8 < m->n1) continue;
-        if (pr) HIP_TRY(hipEventRecord(pr->a0[pr->n_apply++], m->stream));
-        TRY(step_apply_interval(m, eta, reg0, regw, regv, lo, pend_hi, c->rows_dev, last));
-        if (pr) HIP_TRY(hipEventRecord(pr->a1[pr->n_apply - 1], m->stream));
-        pend_hi = -1;
-    }
+    TRY(apply_as_arrived(m, c, edge, m->n1, n_int - 1, true, [&](int64_t lo, int64_t hi, bool last) -> int {
+        int ai;
+        TRY(span_begin(pr, false, m->stream, ai));
+        TRY(step_apply_interval(m, sgd, lo, hi, c->rows_dev, last));
+        return span_end(pr, false, m->stream, ai);
+    }));
     if (pr) HIP_TRY(hipEventRecord(pr->wait_b, m->stream));
     return FMHIP_OK;
 }
@@ -769,12 +774,11 @@ int dp_step_dense(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_
 // without the overlap.
 //   compute  A(t0) | B | bwd T-1 | .. bwd 0 | bwd T | wait, apply T-1 .. 0 | A(t1) | wait T apply T | B | bwd T-1 ...
 //   comm           |B|        | slice T-1 | .. slice 0    | slice T ............|       |B|   | slice T-1 ..
-int dp_run_pipelined(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const int64_t *batches, int64_t n, double eta, double reg0, double regw,
-                     double regv) {
+int dp_run_pipelined(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const int64_t *batches, int64_t n, const Sgd &sgd) {
     const std::vector<int64_t> edge = interval_edges(c->cuts, m->n1, 0);
     const int n_int = (int)edge.size() - 1, T = n_int - 1;
     if (n_int < 2 || m->Kp > 64) {      // nothing to pipeline: the dense step (the same collectives on every rank: cuts and width are agreed)
-        for (int64_t t = 0; t < n; ++t) TRY(dp_step_dense(m, d, batches[t], c, eta, reg0, regw, regv));
+        for (int64_t t = 0; t < n; ++t) TRY(dp_step_dense(m, d, batches[t], c, sgd));
         return FMHIP_OK;
     }
     bool any_live = false;
@@ -819,20 +823,10 @@ int dp_run_pipelined(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const i
             if (pr) HIP_TRY(hipEventRecord(pr->top_a, m->stream));
             HIP_TRY(hipStreamWaitEvent(m->stream, c->ev_done[T], 0));
             if (pr) { HIP_TRY(hipEventRecord(pr->top_b, m->stream)); pr->has_top = true; }
-            TRY(step_apply_interval(m, eta, reg0, regw, regv, edge[(size_t)T], edge[(size_t)T + 1], c->rows_dev + ((t - 1) & 1), true));
+            TRY(step_apply_interval(m, sgd, edge[(size_t)T], edge[(size_t)T + 1], c->rows_dev + ((t - 1) & 1), true));
         }
-        hipLaunchKernelGGL(k_set_float, dim3(1), dim3(1), 0, m->stream, rows_t, live ? (float)d->batches[(size_t)b].rows : 0.f);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev_rows, m->stream));
-        HIP_TRY(hipStreamWaitEvent(c->cs, c->ev_rows, 0));
-        TRY(collective(c, rows_t, 1, FMHIP_COLL_SUM_F32, c->cs));
-        if (live) {
-            TRY(step_forward_pass(m, d, b, 1));
-        } else {
-            HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
-            m->grad_dirty = true;
-            m->last_nnz = m->last_rows = 0;
-        }
+        TRY(exchange_row_count(m, c, rows_t, live ? (float)d->batches[(size_t)b].rows : 0.f, true));
+        TRY(live ? step_forward_pass(m, d, b, 1) : zero_contribution(m));
         // the order of the intervals: the second-coldest first (little work, many bytes: the wire starts early), down to feature
         // 0, the coldest last (it travels beside the next position's pass A).  Who walks a straddling range: whoever comes first
         for (int o = 0; o < n_int; ++o) {
@@ -841,32 +835,25 @@ int dp_run_pipelined(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const i
             const bool head = i == 0;                    // the lowest interval carries the statistics scalars
             const int own = i == T ? 0 : (i == T - 1 ? (kOwnLower | kOwnUpper) : kOwnLower);
             if (live) TRY(step_backward(m, d, b, lo, hi, head, nullptr, nullptr, own));
-            const Region reg[3] = {{m->GV() + (size_t)lo * m->Kp, (size_t)(hi - lo) * m->Kp},
-                                   {head ? m->grad : m->Gw() + lo, (size_t)(hi - lo) + (head ? (size_t)kGradHead : 0)},
-                                   {m->Gb() + lo, (size_t)(hi - lo)}};
-            TRY(reduce_regions(m, c, reg, 3, c->ev_ready[i], c->ev_done[i], pr));
+            const auto reg = slice_regions(m->GV(), m->Gw(), m->Gb(), m->grad, lo, hi, (size_t)m->Kp, head);
+            TRY(reduce_regions(m, c, reg.data(), 3, c->ev_ready[i], c->ev_done[i], pr));
         }
         m->bw_next_hi = -1;
         if (pr) HIP_TRY(hipEventRecord(pr->wait_a, m->stream));
-        // every interval but the top one is updated as its slice arrives (small ones share the next one's launch)
-        int64_t pend_hi = -1;
-        for (int i = T - 1; i >= 0; --i) {
-            const int64_t lo = edge[(size_t)i], hi = edge[(size_t)i + 1];
-            if (pend_hi < 0) pend_hi = hi;
-            HIP_TRY(hipStreamWaitEvent(m->stream, c->ev_done[i], 0));
-            if (i > 0 && (pend_hi - lo) * 8 < m->n1) continue;
-            if (pr) HIP_TRY(hipEventRecord(pr->a0[pr->n_apply++], m->stream));
-            TRY(step_apply_interval(m, eta, reg0, regw, regv, lo, pend_hi, rows_t, false));
-            if (pr) HIP_TRY(hipEventRecord(pr->a1[pr->n_apply - 1], m->stream));
-            pend_hi = -1;
-        }
+        // every interval but the top one is updated as its slice arrives; the step closes with the top one's update
+        TRY(apply_as_arrived(m, c, edge, m->n1, T - 1, true, [&](int64_t lo, int64_t hi, bool) -> int {
+            int ai;
+            TRY(span_begin(pr, false, m->stream, ai));
+            TRY(step_apply_interval(m, sgd, lo, hi, rows_t, false));
+            return span_end(pr, false, m->stream, ai);
+        }));
         if (pr) HIP_TRY(hipEventRecord(pr->wait_b, m->stream));
         if (t + 1 < n) {
             // ... and the next position's pass A beside the top slice (its rows are the only ones not final yet)
             if (batches[t + 1] >= 0) TRY(step_forward_pass(m, d, batches[t + 1], 0));
         } else {
             HIP_TRY(hipStreamWaitEvent(m->stream, c->ev_done[T], 0));
-            TRY(step_apply_interval(m, eta, reg0, regw, regv, edge[(size_t)T], edge[(size_t)T + 1], rows_t, true));
+            TRY(step_apply_interval(m, sgd, edge[(size_t)T], edge[(size_t)T + 1], rows_t, true));
         }
     }
     if (part_rc != FMHIP_OK) return fail(part_rc, "%s (this rank contributed zeros to the run)", part_err.c_str());
@@ -882,7 +869,7 @@ inline int64_t shard_top(fmhip_model_t m, int W) { return fmhip::host::shard_top
 // receives the summed rows of share r) grouped with the all-reduce of its G_w / G_b entries -> rank r updates ITS
 // rows of V and all of the interval's w, zeroes the other shares' gradient rows -> all-gather of the updated rows in
 // place into V.  One writer per V row: the replicas are identical whatever order the transport sums in.
-int dp_step_sharded(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, double eta, double reg0, double regw, double regv) {
+int dp_step_sharded(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, const Sgd &sgd) {
     const bool live = batch >= 0;
     const int W = c->emu_ranks > 0 ? c->emu_ranks : c->world;        // shares per interval
     const int R = c->emu_ranks > 0 ? 0 : c->rank;                    // ... and which one is this rank's
@@ -891,12 +878,7 @@ int dp_step_sharded(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
         return fail(FMHIP_ERR_UNSUPPORTED, "the sharded exchange needs %lld rows for %d equal shares of %lld: more ranks than the tables' "
                                            "slack allows (%d), or a caller-owned gradient buffer (fmhip_grad_bind) with n+1 not a multiple of world",
                     (long long)top, W, (long long)m->n1, fmhip_model::kSlackRows);
-    const float my_rows = live ? (float)d->batches[(size_t)batch].rows : 0.f;
-    hipLaunchKernelGGL(k_set_float, dim3(1), dim3(1), 0, m->stream, c->rows_dev, my_rows);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_rows, m->stream));
-    HIP_TRY(hipStreamWaitEvent(c->cs, c->ev_rows, 0));
-    TRY(collective(c, c->rows_dev, 1, FMHIP_COLL_SUM_F32, c->cs));
+    TRY(exchange_row_count(m, c, c->rows_dev, live ? (float)d->batches[(size_t)batch].rows : 0.f, true));
     if (live) {
         TRY(step_forward(m, d, batch));
     } else {
@@ -928,27 +910,20 @@ int dp_step_sharded(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
         //   shares' gradient rows zeroed (one launch) -> all-gather of the updated V rows
         HIP_TRY(hipEventRecord(c->ev_ready[i], m->stream));
         HIP_TRY(hipStreamWaitEvent(c->cs, c->ev_ready[i], 0));
-        int pi = -1;
-        if (pr && pr->n_coll < kProfColl) {
-            pi = pr->n_coll++;
-            HIP_TRY(hipEventRecord(pr->c0[pi], c->cs));
-        }
+        int pi;
+        TRY(span_begin(pr, true, c->cs, pi));
         if (!c->ext) NCCL_TRY(rccl().GroupStart());
         TRY(collective(c, m->GV() + at, count, FMHIP_COLL_REDUCE_SCATTER_F32, c->cs));
         TRY(collective(c, gw, n_gw, FMHIP_COLL_SUM_F32, c->cs));
         TRY(collective(c, m->Gb() + lo, n_gb, FMHIP_COLL_SUM_F32, c->cs));
         if (!c->ext) NCCL_TRY(rccl().GroupEnd());
         TRY(emu_delay(c, half * gv_bytes + head_bytes, c->cs, m->GV() + (size_t)lo * kp, (size_t)(hi_r - lo) * kp, 1));
-        if (pi >= 0) HIP_TRY(hipEventRecord(pr->c1[pi], c->cs));
-        TRY(step_apply_shard(m, eta, reg0, regw, regv, lo, hi, hi_r, vlo, vhi, c->rows_dev, last, c->cs));
-        pi = -1;
-        if (pr && pr->n_coll < kProfColl) {
-            pi = pr->n_coll++;
-            HIP_TRY(hipEventRecord(pr->c0[pi], c->cs));
-        }
+        TRY(span_end(pr, true, c->cs, pi));
+        TRY(step_apply_shard(m, sgd, lo, hi, hi_r, vlo, vhi, c->rows_dev, last, c->cs));
+        TRY(span_begin(pr, true, c->cs, pi));
         TRY(collective(c, m->V.p + at, count, FMHIP_COLL_ALLGATHER_F32, c->cs));
         TRY(emu_delay(c, half * gv_bytes, c->cs, m->V.p + (size_t)lo * kp, (size_t)(hi_r - lo) * kp, 1));
-        if (pi >= 0) HIP_TRY(hipEventRecord(pr->c1[pi], c->cs));
+        TRY(span_end(pr, true, c->cs, pi));
         if (c->profiling) c->prof_bytes += (int64_t)(gv_bytes + head_bytes);
     }
     HIP_TRY(hipEventRecord(c->ev_gathered, c->cs));
@@ -993,50 +968,32 @@ int local_checks(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t
     return FMHIP_OK;
 }
 
-int dp_step_mode(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, double eta, double reg0, double regw, double regv,
-                 int64_t position) {
+int dp_step_mode(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, const Sgd &sgd, int64_t position) {
     switch (c->exchange) {
-        case FMHIP_EXCHANGE_TOUCHED: return dp_step_touched(m, d, batch, c, eta, reg0, regw, regv, position);
-        case FMHIP_EXCHANGE_SHARDED: return dp_step_sharded(m, d, batch, c, eta, reg0, regw, regv);
-        case FMHIP_EXCHANGE_PIPELINED: return dp_run_pipelined(m, d, c, &batch, 1, eta, reg0, regw, regv);
-        default: return dp_step_dense(m, d, batch, c, eta, reg0, regw, regv);
+        case FMHIP_EXCHANGE_TOUCHED: return dp_step_touched(m, d, batch, c, sgd, position);
+        case FMHIP_EXCHANGE_SHARDED: return dp_step_sharded(m, d, batch, c, sgd);
+        case FMHIP_EXCHANGE_PIPELINED: return dp_run_pipelined(m, d, c, &batch, 1, sgd);
+        default: return dp_step_dense(m, d, batch, c, sgd);
     }
 }
 
 // position >= 0: the step's place in the lock-step schedule, named by every rank alike (fmhip_dp_step_at; the touched-rows
 // exchange picks that position's union); -1: the next one in order (fmhip_dp_step)
-int dp_step(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, double eta, double reg0, double regw, double regv,
-            int64_t position = -1) {
+int dp_step(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, const Sgd &sgd, int64_t position = -1) {
     const int pre = local_checks(m, d, batch, c, position < 0);
-    if (pre == FMHIP_OK) return dp_step_mode(m, d, batch, c, eta, reg0, regw, regv, position);
+    if (pre == FMHIP_OK) return dp_step_mode(m, d, batch, c, sgd, position);
     const std::string why = fmhip_last_error();
-    const int rc = dp_step_mode(m, d, -1, c, eta, reg0, regw, regv, position);     // keep in step with the peers: contribute zeros
+    const int rc = dp_step_mode(m, d, -1, c, sgd, position);     // keep in step with the peers: contribute zeros
     if (rc != FMHIP_OK) return rc;
     return fail(pre, "%s (this rank contributed zeros to the step)", why.c_str());
 }
 
 // `n` positions of the lock-step schedule in one call.  The pipelined mode overlaps consecutive steps; the other modes step one
-// by one.  A position whose batch fails a local check contributes zeros (as in dp_step) and the error is reported afterwards.
-int dp_run(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const int64_t *positions, int64_t n, double eta, double reg0, double regw, double regv) {
+// by one.  A position whose batch fails a check only THIS rank can see contributes zeros and the run goes on — stopping there
+// would leave the peers alone in the next position's collectives; the first such error is reported at the end.  A
+// failure of a step itself (HIP, the transport) is no local matter and ends the run at once.
+int dp_run(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const int64_t *positions, int64_t n, const Sgd &sgd) {
     const int64_t nb = (int64_t)d->batches.size();
-    if (c->exchange != FMHIP_EXCHANGE_PIPELINED) {
-        // a position whose batch fails a check only THIS rank can see contributes zeros and the run goes on — stopping here
-        // would leave the peers alone in the next position's collectives; the first such error is reported at
-        // the end.  A failure of the step itself (HIP, the transport) is no local matter and ends the run at once.
-        int pre = FMHIP_OK;
-        std::string why;
-        for (int64_t j = 0; j < n; ++j) {
-            int64_t b = positions[j] < nb ? positions[j] : -1;
-            const int rc = local_checks(m, d, b, c, false);
-            if (rc != FMHIP_OK) {
-                if (pre == FMHIP_OK) { pre = rc; why = fmhip_last_error(); }
-                b = -1;
-            }
-            TRY(dp_step_mode(m, d, b, c, eta, reg0, regw, regv, positions[j]));
-        }
-        if (pre != FMHIP_OK) return fail(pre, "%s (this rank contributed zeros to those steps)", why.c_str());
-        return FMHIP_OK;
-    }
     std::vector<int64_t> batches((size_t)n);
     int pre = FMHIP_OK;
     std::string why;
@@ -1048,7 +1005,9 @@ int dp_run(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const int64_t *po
             batches[(size_t)j] = -1;
         }
     }
-    TRY(dp_run_pipelined(m, d, c, batches.data(), n, eta, reg0, regw, regv));
+    if (c->exchange == FMHIP_EXCHANGE_PIPELINED) TRY(dp_run_pipelined(m, d, c, batches.data(), n, sgd));
+    else
+        for (int64_t j = 0; j < n; ++j) TRY(dp_step_mode(m, d, batches[(size_t)j], c, sgd, positions[j]));
     if (pre != FMHIP_OK) return fail(pre, "%s (this rank contributed zeros to those steps)", why.c_str());
     return FMHIP_OK;
 }
@@ -1369,7 +1328,7 @@ int fmhip_dp_step(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_
     TRY(check_comm(m, c));
     TRY(check_train(m, d));
     if (batch >= 0) TRY(check_batch(d, batch));
-    return dp_step(m, d, batch, c, eta, reg0, regw, regv);
+    return dp_step(m, d, batch, c, Sgd{eta, reg0, regw, regv});
 }
 
 int fmhip_dp_step_at(fmhip_model_t m, fmhip_dataset_t d, int64_t position, fmhip_comm_t c, double eta, double reg0, double regw,
@@ -1378,7 +1337,7 @@ int fmhip_dp_step_at(fmhip_model_t m, fmhip_dataset_t d, int64_t position, fmhip
     TRY(check_comm(m, c));
     TRY(check_train(m, d));
     if (position < 0) return fail(FMHIP_ERR_INVALID, "position must be >= 0");
-    return dp_step(m, d, position < (int64_t)d->batches.size() ? position : -1, c, eta, reg0, regw, regv, position);
+    return dp_step(m, d, position < (int64_t)d->batches.size() ? position : -1, c, Sgd{eta, reg0, regw, regv}, position);
 }
 
 int fmhip_dp_steps(fmhip_model_t m, fmhip_dataset_t d, const int64_t *positions, int64_t n, fmhip_comm_t c, double eta, double reg0, double regw,
@@ -1389,11 +1348,11 @@ int fmhip_dp_steps(fmhip_model_t m, fmhip_dataset_t d, const int64_t *positions,
     if (n < 0 || (n > 0 && !positions)) return fail(FMHIP_ERR_INVALID, "positions is NULL or n < 0");
     for (int64_t j = 0; j < n; ++j)
         if (positions[j] < 0) return fail(FMHIP_ERR_INVALID, "positions[%lld] = %lld: a position is >= 0", (long long)j, (long long)positions[j]);
-    return dp_run(m, d, c, positions, n, eta, reg0, regw, regv);
+    return dp_run(m, d, c, positions, n, Sgd{eta, reg0, regw, regv});
 }
 
-static int dp_epoch(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, double eta, double reg0, double regw, double regv,
-                    const int64_t *order, int64_t n_order, fmhip_stats *stats) {
+static int dp_epoch(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const Sgd &sgd, const int64_t *order, int64_t n_order,
+                    fmhip_stats *stats) {
     TRY(check_comm(m, c));
     TRY(check_train(m, d));
     const int64_t nb = (int64_t)d->batches.size();
@@ -1416,7 +1375,7 @@ static int dp_epoch(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, double e
     }
     int64_t agree[7] = {nb, 0, order ? n_order : -1, order ? -n_order : 1, order_bad, order_hash, -order_hash};
     for (int64_t j = 0; j < nb && !agree[1]; ++j) agree[1] = local_checks(m, d, j, c, false) != FMHIP_OK;
-    if (!agree[1] && c->exchange == FMHIP_EXCHANGE_TOUCHED && !lazy_decay_ok(m, eta, regw, regv)) {
+    if (!agree[1] && c->exchange == FMHIP_EXCHANGE_TOUCHED && !lazy_decay_ok(m, sgd)) {
         agree[1] = 1;
         (void)fail(FMHIP_ERR_UNSUPPORTED, "the touched-rows exchange needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)");
     }
@@ -1448,7 +1407,7 @@ static int dp_epoch(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, double e
     {
         std::vector<int64_t> pos((size_t)steps);
         for (int64_t j = 0; j < steps; ++j) pos[(size_t)j] = order ? order[j] : j;
-        TRY(dp_run(m, d, c, pos.data(), steps, eta, reg0, regw, regv));
+        TRY(dp_run(m, d, c, pos.data(), steps, sgd));
     }
     if (stats) {
         memset(stats, 0, sizeof *stats);
@@ -1462,14 +1421,14 @@ static int dp_epoch(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, double e
 int fmhip_dp_epoch(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, double eta, double reg0, double regw, double regv,
                    fmhip_stats *stats) {
     WriteLock lock(m);       // the step changes the model; the communicator is used by the thread that owns its model
-    return dp_epoch(m, d, c, eta, reg0, regw, regv, nullptr, 0, stats);
+    return dp_epoch(m, d, c, Sgd{eta, reg0, regw, regv}, nullptr, 0, stats);
 }
 
 int fmhip_dp_epoch_order(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, double eta, double reg0, double regw, double regv,
                          const int64_t *order, int64_t n_order, fmhip_stats *stats) {
     WriteLock lock(m);
-    if (!order || n_order < 0) return dp_epoch(m, d, c, eta, reg0, regw, regv, nullptr, 0, stats);
-    return dp_epoch(m, d, c, eta, reg0, regw, regv, order, n_order, stats);
+    if (!order || n_order < 0) return dp_epoch(m, d, c, Sgd{eta, reg0, regw, regv}, nullptr, 0, stats);
+    return dp_epoch(m, d, c, Sgd{eta, reg0, regw, regv}, order, n_order, stats);
 }
 
 int fmhip_dp_plan_info(fmhip_comm_t c, int64_t *steps, int64_t *max_batch_rows) {

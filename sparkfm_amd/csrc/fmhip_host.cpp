@@ -258,5 +258,31 @@ Share shard_share(int64_t lo, int64_t hi, bool top_interval, int64_t n1, int W, 
     return s;
 }
 
+CompactEdges compact_edges(const std::vector<int64_t> &cuts, int64_t n1, const int32_t *cut_pos, int32_t n_u) {
+    CompactEdges c{{0}, {0}};
+    for (size_t i = 0; i < cuts.size(); ++i) {
+        if (cuts[i] > c.edge.back() && cuts[i] < n1) {
+            c.edge.push_back(cuts[i]);
+            c.pe.push_back(cut_pos[i]);
+        }
+    }
+    c.edge.push_back(n1);
+    c.pe.push_back(n_u);
+    return c;
+}
+
+std::vector<ApplyGroup> apply_groups(const std::vector<int64_t> &edges, int64_t total_rows, int first_interval) {
+    std::vector<ApplyGroup> g;
+    int64_t pend_hi = -1;      // the top of the rows waiting for a launch (-1: none)
+    for (int i = first_interval; i >= 0; --i) {
+        const int64_t lo = edges[(size_t)i];
+        if (pend_hi < 0) pend_hi = edges[(size_t)i + 1];
+        if (i > 0 && (pend_hi - lo) * 8 < total_rows) continue;
+        g.push_back({i, lo, pend_hi});
+        pend_hi = -1;
+    }
+    return g;
+}
+
 }  // namespace host
 }  // namespace fmhip

@@ -1,6 +1,6 @@
 // fmhip_host.h — the library's PURE HOST ARITHMETIC: everything libfmhip.so computes on the host that needs no GPU and no
 // HIP header — row shards, feature relabelling, a batch's range / fixup metadata, the band-affine plan of the backward's ranges,
-// the ALS sweep's level schedule, the data-parallel plan's cuts, interval edges and equal shares.  fmhip_dataset.hip /
+// the ALS sweep's level schedule, the data-parallel plan's cuts, interval edges, equal shares and update groups.  fmhip_dataset.hip /
 // fmhip_comm.hip call these; tests/host_arith_harness.cpp compiles fmhip_host.cpp with g++ -fsanitize=address,undefined and
 // drives them over random shapes (the sanitizers cannot run on the GPU pool, the index arithmetic can run
 // here).  Not installed, not part of the ABI.
@@ -72,6 +72,15 @@ std::vector<int64_t> interval_edges(const std::vector<int64_t> &cuts, int64_t n1
 inline int64_t shard_top(int64_t n1, int W) { return (n1 + W - 1) / W * W; }
 struct Share { int64_t hi_r, chunk, vlo, vhi; };
 Share shard_share(int64_t lo, int64_t hi, bool top_interval, int64_t n1, int W, int R);
+// the touched-rows exchange's intervals: feature ids [edge[i], edge[i+1]) (edge == interval_edges(cuts, n1, 0)) are the rows
+// [pe[i], pe[i+1]) of the compact gradient; cut_pos[i]: where cuts[i] falls in the step's union of n_u rows
+struct CompactEdges { std::vector<int64_t> edge, pe; };
+CompactEdges compact_edges(const std::vector<int64_t> &cuts, int64_t n1, const int32_t *cut_pos, int32_t n_u);
+// The update launches of the intervals [edges[i], edges[i+1]) as their slices arrive, first_interval down to 0: an interval
+// of less than an eighth of total_rows waits and shares the next one's launch; interval 0 always launches.  -> one group per
+// launch, in that order: the rows [lo, hi) and the interval `at` whose arrival it waits for
+struct ApplyGroup { int at; int64_t lo, hi; };
+std::vector<ApplyGroup> apply_groups(const std::vector<int64_t> &edges, int64_t total_rows, int first_interval);
 
 }  // namespace host
 }  // namespace fmhip

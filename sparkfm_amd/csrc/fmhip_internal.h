@@ -275,11 +275,17 @@ int check_train(fmhip_model_t m, fmhip_dataset_t d);      // + the dataset must 
 int check_batch(fmhip_dataset_t d, int64_t batch);
 // the pieces of one mini-batch step, all asynchronous on m->stream (fmhip_api.hip)
 int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b);
+// the step size and the regularisation of one SGD step (the C entry points take them one by one)
+struct Sgd {
+    double eta, reg0, regw, regv;
+    double dv() const { return 1.0 - eta * regv; }     // the decay of one step (V, w): what lazy decay multiplies the tables' scale by
+    double dw() const { return 1.0 - eta * regw; }
+};
 // a step whose update happens inside the backward (mode 1: every finished gradient row, FMHIP_TUNE_FUSED_UPDATE) or
 // inside the fixup launch (mode 2, the merged finish: dense update beside the fixups, FMHIP_TUNE_MERGED_FINISH) — fmhip_api.hip
 struct FusedPlan {
     int mode = 0;
-    double eta = 0.0, reg0 = 0.0, regw = 0.0, regv = 0.0;
+    Sgd sgd{};
     double sv_out = 1.0, sw_out = 1.0;    // the tables' scales after the step
     FusedUpd upd{};
 };
@@ -294,26 +300,25 @@ int step_backward(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int64_t feat_lo
 // forward + backward + fixup of one batch into the packed gradient (fused: straight into the parameters)
 int step_compute(fmhip_model_t m, fmhip_dataset_t d, int64_t b, double *acc, const FusedPlan *fused = nullptr);
 // can this step's update run inside the fixup launch / the column walk?  (fills *p; false: a launch of its own, step_apply)
-bool plan_fused(fmhip_model_t m, fmhip_dataset_t d, int64_t b, double eta, double reg0, double regw, double regv, FusedPlan *p);
+bool plan_fused(fmhip_model_t m, fmhip_dataset_t d, int64_t b, const Sgd &s, FusedPlan *p);
 int finish_fused(fmhip_model_t m, const FusedPlan &p);      // what step_apply leaves behind, for a step planned fused
 int fold_scales(fmhip_model_t m);                           // lazily decayed tables back to scale 1
 int read_acc(fmhip_model_t m, fmhip_stats *st);             // the fp64 epoch accumulators (synchronises)
-int step_apply(fmhip_model_t m, double eta, double reg0, double regw, double regv, fmhip_dataset_t d = nullptr, int64_t b = -1);
-int step_apply_interval(fmhip_model_t m, double eta, double reg0, double regw, double regv, int64_t lo, int64_t hi,
-                        const float *rows, bool last);
+int step_apply(fmhip_model_t m, const Sgd &s, fmhip_dataset_t d = nullptr, int64_t b = -1);
+int step_apply_interval(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, const float *rows, bool last);
 // The sharded update of the feature interval [lo, hi) on stream `s` (one launch): V rows [vlo, vhi) (this rank's share) get
 // the dense update, every linear weight of the interval is stepped, the G_V rows of [lo, hi_r) outside the share are zeroed
 // (hi_r >= hi: the top interval's equal shares reach into the slack rows).  `last`: also steps w0 and closes the step.
-int step_apply_shard(fmhip_model_t m, double eta, double reg0, double regw, double regv, int64_t lo, int64_t hi, int64_t hi_r,
-                     int64_t vlo, int64_t vhi, const float *rows, bool last, hipStream_t s);
+int step_apply_shard(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, int64_t hi_r, int64_t vlo, int64_t vhi, const float *rows,
+                     bool last, hipStream_t stream);
 // the rows-only (lazy-decay) update of the feature rows listed on the device (ids < 0 are skipped), |B| from `rows`
 // (device float): the touched-rows exchange of the data-parallel step applies the union of all ranks' rows with it
 // view given: the gradient rows are read from (and zeroed in) its compact arrays, row j belonging to feature feat[j]
 // off / last: the rows [off, off + n_feat) of the list (and of a compact view) only — the touched-rows exchange updates a
 // feature interval as soon as its slice has arrived; the step's bookkeeping (w0, the tables' scale) moves with the LAST slice
-int step_apply_rows(fmhip_model_t m, double eta, double reg0, double regw, double regv, const int32_t *feat, int32_t n_feat,
-                    const float *rows, const GradView *view = nullptr, int64_t off = 0, bool last = true);
-bool lazy_decay_ok(fmhip_model_t m, double eta, double regw, double regv);
+int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t n_feat, const float *rows, const GradView *view = nullptr,
+                    int64_t off = 0, bool last = true);
+bool lazy_decay_ok(fmhip_model_t m, const Sgd &s);
 int read_scal(fmhip_model_t m, fmhip_stats *st);
 
 }  // namespace host

@@ -175,6 +175,32 @@ BwdArgs bwd_args(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
     return a;
 }
 
+// what every update launch shares: the tables, the packed gradient and its scalars, |B| (`rows`, on the device), the whole
+// feature range, the step's scalars at an unscaled step size, the tables' scales on entry.  Each update sets what is its own
+static ApplyArgs apply_args(fmhip_model_t m, const Sgd &s, const float *rows) {
+    ApplyArgs a{};
+    a.V = m->V.p;
+    a.w = m->w.p;
+    a.w0 = m->w0.p;
+    a.GV = m->GV();
+    a.Gw = m->Gw();
+    a.Gb = m->Gb();
+    a.scal = m->scal();
+    a.rows = rows;
+    a.n1 = m->n1;
+    a.row_lo = 0;
+    a.row_hi = m->n1;
+    a.pack_k = m->pack_k();
+    a.eta = (float)s.eta;
+    a.reg0 = (float)s.reg0;
+    a.regw = (float)s.regw;
+    a.regv = (float)s.regv;
+    a.eta_v = a.eta_w = a.eta;
+    a.sv_in = (float)m->sv;
+    a.sw_in = (float)m->sw;
+    return a;
+}
+
 // forward of one batch: P = e*q, e, per-block statistics partials
 int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
     const BatchMeta &bm = d->batches[(size_t)b];
@@ -275,7 +301,7 @@ int step_backward(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int64_t feat_lo
     BwdArgs ba = bwd_args(m, d, b);
     if (fused) {
         if (fused->mode == 1) ba.upd = fused->upd;
-        if (finish) { ba.red_w0 = m->w0.p; ba.red_eta = (float)fused->eta; ba.red_reg0 = (float)fused->reg0; }
+        if (finish) { ba.red_w0 = m->w0.p; ba.red_eta = (float)fused->sgd.eta; ba.red_reg0 = (float)fused->sgd.reg0; }
     }
     const bool whole = feat_lo <= 0 && feat_hi >= m->n1;
     // the block product rides in the first call whose interval reaches down to the highest hot id (callers that cut the
@@ -314,26 +340,8 @@ int step_backward(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int64_t feat_lo
             // merged finish: the fixup launch also updates the parameters (its own rows from registers, the rest in
             // extra workgroups beside it); the column walk above stored its gradient rows as usual
             ApplyArgs &f = ba.fin;
-            f.V = m->V.p;
-            f.w = m->w.p;
-            f.w0 = m->w0.p;
-            f.GV = m->GV();
-            f.Gw = m->Gw();
-            f.Gb = m->Gb();
-            f.scal = m->scal();
-            f.rows = m->scal() + 2;
-            f.n1 = m->n1;
-            f.row_lo = 0;
-            f.row_hi = m->n1;
+            f = apply_args(m, fused->sgd, m->scal() + 2);
             f.do_w0 = 0;                                   // the statistics block steps w0 (red_w0)
-            f.pack_k = m->pack_k();
-            f.eta = (float)fused->eta;
-            f.reg0 = (float)fused->reg0;
-            f.regw = (float)fused->regw;
-            f.regv = (float)fused->regv;
-            f.sv_in = (float)m->sv;
-            f.sw_in = (float)m->sw;
-            f.eta_v = f.eta_w = f.eta;
             f.invb_val = fused->upd.invb;
             f.use_invb_val = 1;
             int64_t blocks = (m->n1 * (m->Kp / 4) + 255) / 256;
@@ -404,25 +412,32 @@ int step_compute(fmhip_model_t m, fmhip_dataset_t d, int64_t b, double *acc, con
     return step_backward(m, d, b, 0, INT64_MAX, true, acc, fused);
 }
 
+// can weight decay ride in the tables' scale for this step?  (no decay at all: trivially)
+bool lazy_decay_ok(fmhip_model_t m, const Sgd &s) {
+    if (s.regw == 0.0 && s.regv == 0.0) return true;
+    const double dv = s.dv(), dw = s.dw();
+    return m->tv(kTuneLazy) && dv >= 0.5 && dw >= 0.5 && dv <= 1.0 && dw <= 1.0;
+}
+
+// does the rows-only update pay for batch `bm`?  (touching more than half of the rows, the dense, perfectly coalesced pass is as cheap)
+static bool few_rows(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm) {
+    const int64_t touched = (int64_t)bm.n_cols + d->hot_pages * kHotT;
+    return touched * 2 <= m->n1;
+}
+
 // Can this step apply its gradient rows inside the backward (no exchange, no separate update launch)?  It is the
 // rows-only update, so weight decay must be expressible through the tables' scale (lazy decay, fm_apply.hip).
-bool plan_fused(fmhip_model_t m, fmhip_dataset_t d, int64_t b, double eta, double reg0, double regw, double regv, FusedPlan *p) {
-    const double dv = 1.0 - eta * regv, dw = 1.0 - eta * regw;
-    const bool decay = regw != 0.0 || regv != 0.0;
-    const bool lazy_ok = !decay || (m->tv(kTuneLazy) && dv >= 0.5 && dw >= 0.5 && dv <= 1.0 && dw <= 1.0);
+bool plan_fused(fmhip_model_t m, fmhip_dataset_t d, int64_t b, const Sgd &s, FusedPlan *p) {
+    const bool lazy_ok = lazy_decay_ok(m, s);
     const BatchMeta &bm0 = d->batches[(size_t)b];
-    p->eta = eta;
-    p->reg0 = reg0;
-    p->regw = regw;
-    p->regv = regv;
+    p->sgd = s;
     {
         const float rows = (float)bm0.rows;
         p->upd.invb = rows > 0.f ? 1.0f / rows : 0.f;
     }
     // merged finish (FMHIP_TUNE_MERGED_FINISH): when the step's update is the DENSE pass (the batch touches most of the model, or decay
     // cannot ride in the scale) it runs inside the fixup launch, beside the fixups, instead of as a launch of its own
-    const int64_t touched = (int64_t)bm0.n_cols + d->hot_pages * kHotT;
-    const bool rows_only = lazy_ok && touched * 2 <= m->n1;
+    const bool rows_only = lazy_ok && few_rows(m, d, bm0);
     if (m->tv(kTuneMerged) && !m->tv(kTuneFused) && d->rb_rows == 0 && !rows_only && bm0.own_off >= 0 && d->dimension <= m->n) {
         p->mode = 2;
         p->sv_out = p->sw_out = 1.0;      // the dense pass folds the scale
@@ -431,13 +446,13 @@ bool plan_fused(fmhip_model_t m, fmhip_dataset_t d, int64_t b, double eta, doubl
     if (!m->tv(kTuneFused) || d->rb_rows != 0) return false;
     if (!lazy_ok) return false;
     p->mode = 1;
-    p->sv_out = m->sv * dv;
-    p->sw_out = m->sw * dw;
+    p->sv_out = m->sv * s.dv();
+    p->sw_out = m->sw * s.dw();
     p->upd.V = m->V.p;
     p->upd.w = m->w.p;
     p->upd.sv = (float)m->sv;
-    p->upd.eta_v = (float)(eta / p->sv_out);
-    p->upd.eta_w = (float)(eta / p->sw_out);
+    p->upd.eta_v = (float)(s.eta / p->sv_out);
+    p->upd.eta_w = (float)(s.eta / p->sw_out);
     return true;
 }
 
@@ -449,64 +464,8 @@ int fold_scales(fmhip_model_t m) {
     return FMHIP_OK;
 }
 
-// what step_apply leaves behind, for a step whose update already happened inside the backward
-int finish_fused(fmhip_model_t m, const FusedPlan &p) {
-    m->sv = p.sv_out;
-    m->sw = p.sw_out;
-    if (m->sv < 0x1p-24 || m->sw < 0x1p-24) TRY(fold_scales(m));
-    m->grad_dirty = false;        // nothing but the statistics head was written
-    m->host64_fresh = false;
-    ++m->prof_step;
-    return FMHIP_OK;
-}
-
-// `d`/`b` given: the gradient in the buffer is exactly batch b's (no exchange happened), so the update
-// may be restricted to the rows that batch touched — their decay, and everyone else's, rides in the
-// tables' scale (lazy weight decay, fm_apply.hip).  Otherwise the dense pass, which also folds a pending
-// scale back to 1.
-int step_apply(fmhip_model_t m, double eta, double reg0, double regw, double regv, fmhip_dataset_t d, int64_t b) {
-    ApplyArgs a{};
-    a.sv_in = (float)m->sv;
-    a.sw_in = (float)m->sw;
-    double sv_out = 1.0, sw_out = 1.0;
-    const double dv = 1.0 - eta * regv, dw = 1.0 - eta * regw;
-    const bool decay = regw != 0.0 || regv != 0.0;
-    if (d && b >= 0 && d->rb_rows == 0 && (!decay || (m->tv(kTuneLazy) && dv >= 0.5 && dw >= 0.5 && dv <= 1.0 && dw <= 1.0))) {
-        const BatchMeta &bm = d->batches[(size_t)b];
-        const int64_t touched = (int64_t)bm.n_cols + d->hot_pages * kHotT;
-        if (touched * 2 <= m->n1) {     // otherwise the dense, perfectly coalesced pass is as cheap
-            a.rows_only = 1;
-            a.feat = d->cfeat.p + bm.col_off;
-            a.n_feat = bm.n_cols;
-            a.hot_ids = d->d_hot_ids.p;
-            a.n_hot = d->hot_pages * kHotT;
-            sv_out = m->sv * dv;
-            sw_out = m->sw * dw;
-        }
-    }
-    a.eta_v = (float)(eta / sv_out);
-    a.eta_w = (float)(eta / sw_out);
-    a.V = m->V.p;
-    a.w = m->w.p;
-    a.w0 = m->w0.p;
-    a.GV = m->GV();
-    a.Gw = m->Gw();
-    a.Gb = m->Gb();
-    a.scal = m->scal();
-    a.rows = m->scal() + 2;
-    a.n1 = m->n1;
-    a.row_lo = 0;
-    a.row_hi = m->n1;
-    a.do_w0 = 1;
-    a.pack_k = m->pack_k();
-    a.eta = (float)eta;
-    a.reg0 = (float)reg0;
-    a.regw = (float)regw;
-    a.regv = (float)regv;
-    {
-        ProfScope ps(m, FMHIP_K_APPLY, m->last_nnz, m->last_rows);
-        HIP_TRY(launch_apply(m->Kp, a, m->stream));
-    }
+// the end of a step's update: the tables' new scales, the gradient clean, the fp64 copy stale, the next profiling step
+static int close_step(fmhip_model_t m, double sv_out, double sw_out) {
     m->sv = sv_out;
     m->sw = sw_out;
     // fp32 tables lose nothing to a small scale until their values approach the denormal range; fold long before
@@ -517,60 +476,55 @@ int step_apply(fmhip_model_t m, double eta, double reg0, double regw, double reg
     return FMHIP_OK;
 }
 
+// what step_apply leaves behind, for a step whose update already happened inside the backward (nothing but the statistics
+// head was written)
+int finish_fused(fmhip_model_t m, const FusedPlan &p) { return close_step(m, p.sv_out, p.sw_out); }
+
+// `d`/`b` given: the gradient in the buffer is exactly batch b's (no exchange happened), so the update
+// may be restricted to the rows that batch touched — their decay, and everyone else's, rides in the
+// tables' scale (lazy weight decay, fm_apply.hip).  Otherwise the dense pass, which also folds a pending
+// scale back to 1.
+int step_apply(fmhip_model_t m, const Sgd &s, fmhip_dataset_t d, int64_t b) {
+    ApplyArgs a = apply_args(m, s, m->scal() + 2);
+    double sv_out = 1.0, sw_out = 1.0;
+    if (d && b >= 0 && d->rb_rows == 0 && lazy_decay_ok(m, s) && few_rows(m, d, d->batches[(size_t)b])) {
+        const BatchMeta &bm = d->batches[(size_t)b];
+        a.rows_only = 1;
+        a.feat = d->cfeat.p + bm.col_off;
+        a.n_feat = bm.n_cols;
+        a.hot_ids = d->d_hot_ids.p;
+        a.n_hot = d->hot_pages * kHotT;
+        sv_out = m->sv * s.dv();
+        sw_out = m->sw * s.dw();
+    }
+    a.eta_v = (float)(s.eta / sv_out);
+    a.eta_w = (float)(s.eta / sw_out);
+    a.do_w0 = 1;
+    {
+        ProfScope ps(m, FMHIP_K_APPLY, m->last_nnz, m->last_rows);
+        HIP_TRY(launch_apply(m->Kp, a, m->stream));
+    }
+    return close_step(m, sv_out, sw_out);
+}
+
 // The dense update of the feature rows [lo, hi) only — the data-parallel step applies an interval as soon as its
 // slice of the gradient has been exchanged (fmhip_comm.hip).  `rows`: device float holding the global row count;
 // `last`: the final interval of the step (also steps w0 from the head's scalars and closes the step's bookkeeping).
-int step_apply_interval(fmhip_model_t m, double eta, double reg0, double regw, double regv, int64_t lo, int64_t hi,
-                        const float *rows, bool last) {
-    ApplyArgs a{};
-    a.sv_in = (float)m->sv;
-    a.sw_in = (float)m->sw;
-    a.eta_v = a.eta_w = (float)eta;
-    a.V = m->V.p;
-    a.w = m->w.p;
-    a.w0 = m->w0.p;
-    a.GV = m->GV();
-    a.Gw = m->Gw();
-    a.Gb = m->Gb();
-    a.scal = m->scal();
-    a.rows = rows;
-    a.n1 = m->n1;
+int step_apply_interval(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, const float *rows, bool last) {
+    ApplyArgs a = apply_args(m, s, rows);
     a.row_lo = lo;
     a.row_hi = hi;
     a.do_w0 = last ? 1 : 0;
-    a.pack_k = m->pack_k();
-    a.eta = (float)eta;
-    a.reg0 = (float)reg0;
-    a.regw = (float)regw;
-    a.regv = (float)regv;
     if (hi > lo || last) {
         ProfScope ps(m, FMHIP_K_APPLY, m->last_nnz, m->last_rows);
         HIP_TRY(launch_apply(m->Kp, a, m->stream));
     }
-    if (last) {
-        m->sv = m->sw = 1.0;      // every interval folded the pending scale
-        m->grad_dirty = false;
-        m->host64_fresh = false;
-        ++m->prof_step;
-    }
-    return FMHIP_OK;
+    return last ? close_step(m, 1.0, 1.0) : FMHIP_OK;      // every interval folded the pending scale
 }
 
-int step_apply_shard(fmhip_model_t m, double eta, double reg0, double regw, double regv, int64_t lo, int64_t hi, int64_t hi_r,
-                     int64_t vlo, int64_t vhi, const float *rows, bool last, hipStream_t s) {
-    ApplyArgs a{};
-    a.sv_in = (float)m->sv;
-    a.sw_in = (float)m->sw;
-    a.eta_v = a.eta_w = (float)eta;
-    a.V = m->V.p;
-    a.w = m->w.p;
-    a.w0 = m->w0.p;
-    a.GV = m->GV();
-    a.Gw = m->Gw();
-    a.Gb = m->Gb();
-    a.scal = m->scal();
-    a.rows = rows;
-    a.n1 = m->n1;
+int step_apply_shard(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, int64_t hi_r, int64_t vlo, int64_t vhi, const float *rows,
+                     bool last, hipStream_t stream) {
+    ApplyArgs a = apply_args(m, s, rows);
     hi = std::min(hi, m->n1);
     a.row_lo = std::min(std::max(vlo, lo), hi);
     a.row_hi = std::min(std::max(vhi, a.row_lo), hi);
@@ -578,73 +532,42 @@ int step_apply_shard(fmhip_model_t m, double eta, double reg0, double regw, doub
     a.w_hi = hi;
     a.z_hi = std::max(hi_r, hi);
     a.do_w0 = last ? 1 : 0;
-    a.pack_k = m->pack_k();
-    a.eta = (float)eta;
-    a.reg0 = (float)reg0;
-    a.regw = (float)regw;
-    a.regv = (float)regv;
-    HIP_TRY(launch_apply_shard(m->Kp, a, s));
+    HIP_TRY(launch_apply_shard(m->Kp, a, stream));
     if (last) {
-        m->sv = m->sw = 1.0;      // every share folded the pending scale; the all-gather spreads the folded rows
+        // every share folded the pending scale; the all-gather spreads the folded rows.  The gradient is left dirty: the
+        // caller's all-gathers still follow (dp_step_sharded clears it after the last one)
+        m->sv = m->sw = 1.0;
         m->host64_fresh = false;
         ++m->prof_step;
     }
     return FMHIP_OK;
 }
 
-// can weight decay ride in the tables' scale for this (eta, reg)?  (no decay at all: trivially)
-bool lazy_decay_ok(fmhip_model_t m, double eta, double regw, double regv) {
-    const double dv = 1.0 - eta * regv, dw = 1.0 - eta * regw;
-    if (regw == 0.0 && regv == 0.0) return true;
-    return m->tv(kTuneLazy) && dv >= 0.5 && dw >= 0.5 && dv <= 1.0 && dw <= 1.0;
-}
-
-int step_apply_rows(fmhip_model_t m, double eta, double reg0, double regw, double regv, const int32_t *feat, int32_t n_feat,
-                    const float *rows, const GradView *view, int64_t off, bool last) {
-    if (!lazy_decay_ok(m, eta, regw, regv))
+int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t n_feat, const float *rows, const GradView *view, int64_t off,
+                    bool last) {
+    if (!lazy_decay_ok(m, s))
         return fail(FMHIP_ERR_UNSUPPORTED, "a rows-only update needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)");
     // every slice of a step starts from the scale the step began with (m->sv / m->sw move with the LAST slice only)
-    const double sv_out = m->sv * (1.0 - eta * regv), sw_out = m->sw * (1.0 - eta * regw);
-    ApplyArgs a{};
-    a.sv_in = (float)m->sv;
-    a.sw_in = (float)m->sw;
+    const double sv_out = m->sv * s.dv(), sw_out = m->sw * s.dw();
+    ApplyArgs a = apply_args(m, s, rows);
     a.rows_only = 1;
     a.feat = feat + off;
     a.n_feat = n_feat;
-    a.hot_ids = nullptr;
-    a.n_hot = 0;
-    a.eta_v = (float)(eta / sv_out);
-    a.eta_w = (float)(eta / sw_out);
-    a.V = m->V.p;
-    a.w = m->w.p;
-    a.w0 = m->w0.p;
-    a.GV = (view ? view->GV : m->GV()) + (view ? (size_t)off * m->Kp : 0);
-    a.Gw = (view ? view->Gw : m->Gw()) + (view ? off : 0);
-    a.Gb = (view ? view->Gb : m->Gb()) + (view ? off : 0);
-    a.scal = view ? view->scal : m->scal();
-    a.g_compact = view ? 1 : 0;
-    a.rows = rows;
-    a.n1 = m->n1;
-    a.row_lo = 0;
-    a.row_hi = m->n1;
+    a.eta_v = (float)(s.eta / sv_out);
+    a.eta_w = (float)(s.eta / sw_out);
+    if (view) {
+        a.GV = view->GV + (size_t)off * m->Kp;
+        a.Gw = view->Gw + off;
+        a.Gb = view->Gb + off;
+        a.scal = view->scal;
+        a.g_compact = 1;
+    }
     a.do_w0 = last ? 1 : 0;
-    a.pack_k = m->pack_k();
-    a.eta = (float)eta;
-    a.reg0 = (float)reg0;
-    a.regw = (float)regw;
-    a.regv = (float)regv;
     if (n_feat > 0 || last) {
         ProfScope ps(m, FMHIP_K_APPLY, m->last_nnz, m->last_rows);
         HIP_TRY(launch_apply(m->Kp, a, m->stream));
     }
-    if (!last) return FMHIP_OK;
-    m->sv = sv_out;
-    m->sw = sw_out;
-    if (m->sv < 0x1p-24 || m->sw < 0x1p-24) TRY(fold_scales(m));
-    m->grad_dirty = false;
-    m->host64_fresh = false;
-    ++m->prof_step;
-    return FMHIP_OK;
+    return last ? close_step(m, sv_out, sw_out) : FMHIP_OK;
 }
 
 int read_scal(fmhip_model_t m, fmhip_stats *st) {

@@ -320,6 +320,118 @@ static void check_plan(Rng &r) {
     }
 }
 
+// ---- the data-parallel step's update groups and the touched-rows exchange's compact intervals -----------------------
+// the step's own loops as they were written inline in fmhip_comm.hip before apply_groups / compact_edges (dense, pipelined
+// and touched): each launch as {interval waited for, lo, hi}
+static std::vector<ApplyGroup> groups_dense(const std::vector<int64_t> &edge, int64_t n1) {
+    std::vector<ApplyGroup> out;
+    const int n_int = (int)edge.size() - 1;
+    int64_t pend_hi = -1;
+    for (int i = n_int - 1; i >= 0; --i) {
+        const int64_t lo = edge[(size_t)i], hi = edge[(size_t)i + 1];
+        if (pend_hi < 0) pend_hi = hi;
+        const bool last = i == 0;
+        if (!last && (pend_hi - lo) * 8 < n1) continue;
+        out.push_back({i, lo, pend_hi});
+        pend_hi = -1;
+    }
+    return out;
+}
+static std::vector<ApplyGroup> groups_pipelined(const std::vector<int64_t> &edge, int64_t n1) {
+    std::vector<ApplyGroup> out;
+    const int n_int = (int)edge.size() - 1, T = n_int - 1;
+    int64_t pend_hi = -1;
+    for (int i = T - 1; i >= 0; --i) {
+        const int64_t lo = edge[(size_t)i], hi = edge[(size_t)i + 1];
+        if (pend_hi < 0) pend_hi = hi;
+        if (i > 0 && (pend_hi - lo) * 8 < n1) continue;
+        out.push_back({i, lo, pend_hi});
+        pend_hi = -1;
+    }
+    return out;
+}
+static void edges_touched(const std::vector<int64_t> &cuts, int64_t n1, const int32_t *cut_pos, int32_t n_u, std::vector<int64_t> &edge,
+                          std::vector<int64_t> &pe) {
+    edge.assign(1, 0);
+    pe.assign(1, 0);
+    for (size_t i = 0; i < cuts.size(); ++i) {
+        const int64_t x = cuts[i];
+        if (x > edge.back() && x < n1) {
+            edge.push_back(x);
+            pe.push_back(cut_pos[i]);
+        }
+    }
+    edge.push_back(n1);
+    pe.push_back(n_u);
+}
+static std::vector<ApplyGroup> groups_touched(const std::vector<int64_t> &pe, int32_t n_u) {
+    std::vector<ApplyGroup> out;
+    const int n_int = (int)pe.size() - 1;
+    int64_t pend_hi = -1;
+    for (int i = n_int - 1; i >= 0; --i) {
+        const int64_t plo = pe[(size_t)i], phi = pe[(size_t)i + 1];
+        if (pend_hi < 0) pend_hi = phi;
+        const bool last = i == 0;
+        if (!last && (pend_hi - plo) * 8 < n_u) continue;
+        out.push_back({i, plo, pend_hi});
+        pend_hi = -1;
+    }
+    return out;
+}
+static bool same_groups(const std::vector<ApplyGroup> &a, const std::vector<ApplyGroup> &b) {
+    if (a.size() != b.size()) return false;
+    for (size_t i = 0; i < a.size(); ++i)
+        if (a[i].at != b[i].at || a[i].lo != b[i].lo || a[i].hi != b[i].hi) return false;
+    return true;
+}
+// the groups tile the rows [edges[0], edges[first + 1]) from the top down and the last one waits for interval 0
+static void check_tiling(const std::vector<ApplyGroup> &g, const std::vector<int64_t> &edges, int first) {
+    if (first < 0) { CHECK(g.empty()); return; }
+    CHECK(!g.empty() && g.back().at == 0 && g.back().lo == edges[0]);
+    int64_t top = edges[(size_t)first + 1];
+    int prev = first + 1;
+    for (const ApplyGroup &x : g) {
+        CHECK(x.at < prev && x.hi == top && x.lo == edges[(size_t)x.at] && x.lo <= x.hi);
+        top = x.lo;
+        prev = x.at;
+    }
+}
+
+static void check_groups(Rng &r) {
+    const int64_t n1 = uni(r, 1, uni(r, 0, 1) ? 64 : 200000);
+    // up to FMHIP_DP_MAX_CUTS cuts, ascending; some collapsed (0), some at or past n1, some equal, some clustered near the top
+    const int nc = (int)uni(r, 0, 7);
+    std::vector<int64_t> cuts((size_t)nc);
+    for (auto &x : cuts) {
+        const int64_t k = uni(r, 0, 5);
+        x = k == 0 ? 0 : k == 1 ? n1 + uni(r, 0, 2) : k == 2 ? std::max<int64_t>(n1 - uni(r, 1, 40), 0) : uni(r, 0, n1);
+    }
+    std::sort(cuts.begin(), cuts.end());
+    if (nc > 1 && uni(r, 0, 3) == 0) cuts[1] = cuts[0];
+    const std::vector<int64_t> edge = interval_edges(cuts, n1, 0);
+    const int n_int = (int)edge.size() - 1;
+    const std::vector<ApplyGroup> gd = apply_groups(edge, n1, n_int - 1);
+    CHECK(same_groups(gd, groups_dense(edge, n1)));
+    check_tiling(gd, edge, n_int - 1);
+    if (n_int >= 2) {
+        const std::vector<ApplyGroup> gp = apply_groups(edge, n1, n_int - 2);
+        CHECK(same_groups(gp, groups_pipelined(edge, n1)));
+        check_tiling(gp, edge, n_int - 2);
+    }
+    // the touched mode: the cuts' positions in a union of n_u rows (lower bounds: ascending, within [0, n_u])
+    const int32_t n_u = (int32_t)uni(r, 0, uni(r, 0, 1) ? 50 : 100000);
+    int32_t cut_pos[8] = {};
+    for (int i = 0; i < nc; ++i) cut_pos[i] = (int32_t)uni(r, 0, n_u);
+    std::sort(cut_pos, cut_pos + nc);
+    std::vector<int64_t> e_ref, pe_ref;
+    edges_touched(cuts, n1, cut_pos, n_u, e_ref, pe_ref);
+    const CompactEdges ce = compact_edges(cuts, n1, cut_pos, n_u);
+    CHECK(ce.edge == e_ref && ce.pe == pe_ref && ce.edge == edge);
+    const std::vector<ApplyGroup> gt = apply_groups(ce.pe, n_u, (int)ce.pe.size() - 2);
+    CHECK(same_groups(gt, groups_touched(ce.pe, n_u)));
+    check_tiling(gt, ce.pe, (int)ce.pe.size() - 2);
+}
+
 int main(int argc, char **argv) {
     g_seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
     const int cases = argc > 2 ? atoi(argv[2]) : 40;
@@ -330,6 +442,7 @@ int main(int argc, char **argv) {
         check_batch_meta_and_bands(r);
         check_pieces(r);
         check_plan(r);
+        for (int j = 0; j < 20; ++j) check_groups(r);
     }
     g_case = -1;
     // the multi-threaded paths: private tables per thread, and (tables too large for that) one table with atomic adds

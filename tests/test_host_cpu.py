@@ -580,7 +580,7 @@ def test_bench_roofline_says_what_bounds_the_step():
 def test_host_arithmetic_under_the_sanitizers(tmp_path):
     """the library's pure host arithmetic — row shards, feature relabelling (one thread, private tables per
     thread, one table with atomic adds), a batch's range / fixup metadata incl. row-blocked pieces, the band-affine plan of the
-    backward's ranges, the ALS level schedule, the data-parallel plan's cuts, interval edges and equal shares
+    backward's ranges, the ALS level schedule, the data-parallel plan's cuts, interval edges, equal shares, update groups and compact intervals
     (sparkfm_amd/csrc/fmhip_host.cpp: the very translation unit libfmhip.so links) — compiled with g++ -fsanitize=address,undefined
     and driven over seeded random shapes by tests/host_arith_harness.cpp, which checks every function against the contract the
     device code relies on (each range in exactly one ascending run of the band plan, no two columns of an ALS level sharing a
