@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — nnz/sec of FM mini-batch SGD training on MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C4|C5] [--batch-rows B] [--time-budget S] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C4|C5] [--batch-rows B] [--dump-outputs DIR] [--full [--time-budget S]]
 
 A "step" is one mini-batch SGD step (forward + backward + update) over one batch of the
 synthetic workload, all inputs resident in HBM before the timed region.
@@ -19,18 +19,23 @@ synthetic workload, all inputs resident in HBM before the timed region.
           ranks as THREADS of this process on GPU 0 (a rehearsal of the whole N-rank flow on a one-GPU box:
           a world of 8 fits neither RCCL, one rank per device, nor the test pool's 6 processes per card).
 
-The record cannot be lost (benchkit/emit.py): rank 0 writes the WHOLE JSON line as soon as the headline exists — metric,
-value, config, `roofline` (HIP-event kernel times; counter bytes from the committed profile until this run's own passes have
-finished), `exchange.*` at N > 1 — and re-writes it, enriched, after every further leg (`cpu_baseline`, the live rocprofv3
-counter passes, `sustained`, the twin and one-GPU legs, `extra.*`), each started only if `--time-budget` still covers its
-estimate.  THE LAST COMPLETE LINE IS THE RECORD; a run killed inside an optional leg has left a valid one behind.
+A plain run does only what the headline needs: it sets up, settles and warms up, times the K steps, writes --dump-outputs,
+and prints ONE JSON line (metric, value, ms_per_step, config, `exchange.*` at N > 1 with the cut / mode sweep that picks the
+plan the headline is timed with).  Everything else the bench measures or checks runs only with `--full`.
+
+The record cannot be lost (benchkit/emit.py): with `--full`, rank 0 writes the WHOLE JSON line as soon as the headline exists
+— metric, value, config, `roofline` (HIP-event kernel times; counter bytes from the committed profile until this run's own
+passes have finished), `exchange.*` at N > 1 — and re-writes it, enriched, after every further leg (`cpu_baseline`, the live
+rocprofv3 counter passes, `sustained`, the twin and one-GPU legs, `extra.*`), each started only if `--time-budget` still covers
+its estimate.  THE LAST COMPLETE LINE IS THE RECORD; a run killed inside an optional leg has left a valid one behind.
 
 The timed region carries no event records: clocks are settled first by >= `--settle` seconds of untimed steps, then W
-counted warm-up steps, then exactly K steps between barriers; the per-kernel HIP-event times (`roofline.avg_launch_ms`,
-`kernels`) come from a short pass of the SAME steps right after it (events recorded by the library on the stream its
-kernels run on).  `cpu_baseline` times the fp64 CPU oracle (a port — SparkFM itself needs a JVM, absent here) on a bounded
-sample of the same workload; `extra.hbm_resident` is a Criteo-width model (V = 8.6 GB, k=64: the only configuration whose
-tables do not live in L2 / Infinity Cache) with weight decay; its counter fraction is copied into `roofline.hbm_resident`.
+counted warm-up steps, then exactly K steps between barriers.  With `--full`, the per-kernel HIP-event times
+(`roofline.avg_launch_ms`, `kernels`) come from a short pass of the SAME steps right after it (events recorded by the library
+on the stream its kernels run on), and at N > 1 the exchange's own timers and the replica check follow.  `cpu_baseline` times
+the fp64 CPU oracle (a port — SparkFM itself runs on a JVM) on a bounded sample of the same workload;
+`extra.hbm_resident` is a Criteo-width model (V = 8.6 GB, k=64: the only configuration whose tables do not live in L2 /
+Infinity Cache) with weight decay; its counter fraction is copied into `roofline.hbm_resident`.
 
 Parts: this file = the argument parser and one rank's flow (setup, settle, measure, legs); benchkit/roofline.py (byte accounting,
 ceilings, the roofline block), benchkit/counters.py (rocprofv3 --pmc child passes), benchkit/record.py (the line's `config` and
@@ -71,17 +76,22 @@ def parse_args(argv=None):
     ap.add_argument("--rows", type=int, default=0, help="rows per GPU (default: the config's rows / N, capped at 5M — two global batches; 1.25M on one GPU)")
     ap.add_argument("--batch-rows", type=int, default=0, help="mini-batch rows per GPU (default 250000; data-parallel: 5M / N, the global batch is fixed)")
     ap.add_argument("--eta", type=float, default=0.02)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the per-kernel HIP-event pass and the roofline, at N > 1 the exchange's own "
+                         "timers and the replica check, the CPU baseline, the live rocprofv3 counter passes, `sustained` and the legs of "
+                         "other workloads (one-GPU and C3 twin at N > 1, extra.* at N = 1), each under --time-budget.  Without it the run "
+                         "prints the headline line alone")
     ap.add_argument("--time-budget", type=float, default=240.0,
-                    help="wall-clock seconds for the WHOLE run, counted from process start: the headline line is written as soon as it exists; "
-                         "every further leg starts only if the time left covers its estimate (skipped legs are named in `legs.skipped`)")
+                    help="--full: wall-clock seconds for the WHOLE run, counted from process start: the headline line is written as soon as it "
+                         "exists; every further leg starts only if the time left covers its estimate (skipped legs are named in `legs.skipped`)")
     ap.add_argument("--settle", type=float, default=0.4,
                     help="seconds of untimed steps BEFORE the counted warm-up (clock / power settle: a 5 ms warm-up does not)")
     ap.add_argument("--tune-budget", type=float, default=45.0,
                     help="N > 1: wall-clock seconds for the cut / exchange-mode sweep (candidates in order of likely merit; all ranks stop together)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the sustained / HBM-resident / ALS legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the sustained / HBM-resident / ALS legs")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not run the rocprofv3 --pmc child passes that measure the kernels' fabric-side traffic in this run "
+                    help="--full: do not run the rocprofv3 --pmc child passes that measure the kernels' fabric-side traffic in this run "
                          "(roofline.traffic then comes from the committed profile, profiles/pmc_traffic.json)")
     ap.add_argument("--exchange", default="rccl", choices=["rccl", "torch"],
                     help="rccl: the library's own communicator (fmhip_dp_step); torch: torch.distributed all-reduce "
@@ -119,7 +129,7 @@ def parse_args(argv=None):
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="A/B: fmhip_tune(KEY, VALUE) before anything is built (repeatable); KEY = a number or a name of "
                          "enum fmhip_tune_key without its prefix (include/fmhip_experimental.h), e.g. flat_address=1")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU work the cpu_baseline sample is sized for")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU work the cpu_baseline sample is sized for")
     ap.add_argument("--log-dir", default=os.environ.get("FMHIP_BENCH_LOG_DIR", ""),
                     help="N > 1: every rank appends its progress to <log-dir>/rank<r>.progress (and to stderr); ranks spawned by "
                          "this file also have their stderr there")
@@ -465,6 +475,10 @@ def run_rank(args, rank, world, local_rank, ctl, json_fd, torch, group=None):
         if args.dump_outputs and rank == 0:
             dump_outputs(args.dump_outputs, L, _ffi, fm, st, wide)
             log("outputs of the timed steps written to %s" % args.dump_outputs)
+        value = total_nnz / elapsed
+        step_ms = elapsed / args.steps * 1e3
+        if not args.full:
+            return
 
         # ---- per-kernel times: a pass of the same steps right behind the timed region, every kernel of every step between a pair
         # of HIP events on the library's own stream (the records cost ~4 us each between the kernels, nothing inside them)
@@ -503,9 +517,6 @@ def run_rank(args, rank, world, local_rank, ctl, json_fd, torch, group=None):
                         "note": "w0 and %d parameter rows spread over all feature intervals: plain and weighted fp64 sums, max == min over the ranks" % len(ids)}
             if not replicas["identical"]:
                 log("REPLICAS DIFFER after the timed steps: max %r, -min %r" % (hi_, lo_))
-
-        value = total_nnz / elapsed
-        step_ms = elapsed / args.steps * 1e3
 
     # ---- the record (rank 0 builds and re-writes it; the other ranks only take part in the collective legs)
     kp = 32
@@ -561,28 +572,36 @@ def run_rank(args, rank, world, local_rank, ctl, json_fd, torch, group=None):
     def exchange_block():
         out["exchange"] = record.exchange_block(x, value, cprof, replicas, tuning, tuning_note, **legs_dp)
 
-    def headline(stage):
-        """Rank 0 (re)builds the record from the latest measure() and writes it."""
+    def headline(stage, final=False):
+        """Rank 0 (re)builds the record from the latest measure() and writes it (a plain run: the roofline needs --full)."""
         if rank != 0:
             return
-        state["pmc"] = committed_pmc(config, k, batch_rows)
         out.update({
             "metric": "nnz_per_sec_fm_sgd_training", "value": value, "unit": "nnz/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": step_ms, "higher_is_better": True, "scaling": "strong" if world > 1 else "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": record.config_block(x),
-            "roofline": None,
-            "cpu_baseline": None,
             "train": {"last_batch_mse": st.sse / max(st.rows, 1), "nonfinite": st.nonfinite},
             "setup_s": {"generate": t_gen, "load_transpose_h2d": t_load},
             "host_enqueue_ms_per_step": enqueue_s / args.steps * 1e3,
         })
-        build_roofline()
+        if args.full:
+            state["pmc"] = committed_pmc(config, k, batch_rows)
+            out.update({"roofline": None, "cpu_baseline": None})
+            build_roofline()
         if use_dp:
             exchange_block()
-        emitter.emit(out, stage)
+        emitter.emit(out, stage, final=final)
         log("%s line written: %.2f G nnz/s" % (stage, value / 1e9))
+
+    def close_rank():
+        if use_dp:
+            ctl.barrier()
+            if comm is not None:
+                comm.close()
+        if progress_file:
+            progress_file.close()
 
     tuning = tuning_note = None
     sweeping = exchange == "rccl" and args.upper_fractions == "auto" and (world > 1 or args.emulate_allreduce or dp.exchange == "touched")
@@ -593,7 +612,10 @@ def run_rank(args, rank, world, local_rank, ctl, json_fd, torch, group=None):
         tuning, tuning_note = dp_legs.tune_sweep(x)
 
     measure()
-    headline("headline")
+    headline("headline", final=not args.full)
+    if not args.full:
+        close_rank()
+        return
 
     # ---- rank 0 alone, the other ranks wait at the next barrier: the CPU baseline, then this run's own counter passes
     if rank == 0:
@@ -710,12 +732,7 @@ def run_rank(args, rank, world, local_rank, ctl, json_fd, torch, group=None):
     if rank == 0:
         emitter.emit(out, "final", final=True)
         log("final line written (%d lines in all)" % emitter.lines)
-    if use_dp:
-        ctl.barrier()
-        if comm is not None:
-            comm.close()
-    if progress_file:
-        progress_file.close()
+    close_rank()
 
 
 if __name__ == "__main__":

@@ -564,14 +564,14 @@ def test_library_side_exchange_two_ranks_on_one_gpu_host_staged(fractions, world
 
 
 def test_bench_with_two_ranks_on_one_gpu():
-    """`python bench.py --gpus 2 --transport host`: the bench's whole N > 1 flow — self-launch of the ranks (before the
+    """`python bench.py --gpus 2 --transport host --full`: the bench's whole N > 1 flow — self-launch of the ranks (before the
     parent touches the GPU), gloo control plane, the library's communicator, the cut / exchange-mode tuning, the timed
     region with its barriers and max over ranks, the exchange's own profile pass, the legs without exchange, the C3 twin,
     the JSON assembly — with both ranks on the one GPU of the test box and every collective staged through the host
     (RCCL refuses two ranks on one device).  Timings mean nothing here; the flow and the line's keys are what is tested."""
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--transport", "host", "--steps", "4", "--warmup", "2",
-           "--rows", "200000", "--batch-rows", "100000", "--no-pmc", "--cpu-budget", "3", "--tune-budget", "12"]
+           "--rows", "200000", "--batch-rows", "100000", "--no-pmc", "--cpu-budget", "3", "--tune-budget", "12", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -851,6 +851,55 @@ def test_bench_fallback_exchange_over_torch_distributed():
     assert out["value"] > 0 and out["train"]["nonfinite"] == 0 and out["config"]["batch_rows_per_gpu"] == 100000
 
 
+def test_plain_bench_run_is_the_headline_alone():
+    """`python bench.py --gpus 1 --steps 20 --warmup 5`, as it is run for every change: set up, settle, warm up, the timed
+    steps, ONE JSON line — the headline and its config, final, with no leg, kernel pass or roofline (those take `--full`) — and
+    at most 30 s of the whole run's wall time outside the W + K steps."""
+    import json
+    import time
+    steps, warmup = 20, 5
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    t0 = time.time()
+    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    wall = time.time() - t0
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [json.loads(ln) for ln in r.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1, [ln["record"]["stage"] for ln in lines]
+    out = lines[0]
+    assert out["record"]["final"] is True and out["record"]["stage"] == "headline"
+    assert out["metric"] == "nnz_per_sec_fm_sgd_training" and out["unit"] == "nnz/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["steps"] == steps and out["warmup"] == warmup and out["n_gpus"] == 1
+    assert out["config"]["workload"].startswith("C3") and out["train"]["nonfinite"] == 0
+    assert out["value"] == pytest.approx(out["config"]["nnz_per_gpu"] / out["config"]["batches_per_gpu"] / (out["ms_per_step"] * 1e-3), rel=0.02)
+    for key in ("roofline", "kernels", "cpu_baseline", "sustained", "extra", "exchange"):
+        assert key not in out, key
+    assert not out["legs"]["seconds"] and not out["legs"]["skipped"]
+    assert wall - (steps + warmup) * out["ms_per_step"] * 1e-3 < 30.0, wall
+
+
+def test_plain_bench_run_with_two_ranks_on_one_gpu():
+    """The plain N > 1 flow (`--transport host`: both ranks on the one GPU, collectives staged through the host): the headline
+    with the default plan, the cut / mode sweep, the headline of the plan the sweep chose as the final line — and nothing after it."""
+    import json
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--transport", "host", "--steps", "4", "--warmup", "2",
+           "--rows", "200000", "--batch-rows", "100000", "--tune-budget", "6"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [json.loads(ln) for ln in r.stdout.decode().splitlines() if ln.strip()]
+    stages = [ln["record"]["stage"] for ln in lines]
+    assert len(lines) == 2 and stages[0].startswith("headline (default plan") and stages[1] == "headline", stages
+    assert [ln["record"]["final"] for ln in lines] == [False, True]
+    out = lines[-1]
+    assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["value"] > 0 and out["ms_per_step"] > 0
+    x = out["exchange"]
+    assert x["nranks"] == 2 and "passed" in x["selftest"] and {t["exchange"] for t in x["cut_tuning"]} == {"dense", "sharded", "pipelined"}
+    for key in ("roofline", "cpu_baseline", "sustained"):
+        assert key not in out, key
+    assert "replicas" not in x and "c3_on_every_gpu" not in x and "exposed_comm_ms" not in x
+
+
 def test_bench_dump_outputs_are_the_timed_steps_from_the_seeded_start(fmhip, tmp_path):
     """`bench.py --dump-outputs DIR`: the model after the K timed steps and the last step's loss.  The W warm-up steps and the
     timed ones start from the parameters drawn on the device from the config's seed however many steps the clock settle took —
@@ -1071,7 +1120,7 @@ def test_relabelling_on_the_gpu_is_the_host_numbering_bit_for_bit(fmhip):
 
 
 def test_bench_killed_inside_an_optional_leg_has_left_its_record():
-    """the bench line must not be losable.  `bench.py` writes the whole record as soon as the headline
+    """the bench line must not be losable.  `bench.py --full` writes the whole record as soon as the headline
     exists and re-writes it after every leg; here the HBM-resident leg is made to hang (FMHIP_BENCH_TEST_STALL), the process is
     killed once the line before it has appeared, and the last complete line on stdout is a valid record: the driver's
     keys, `roofline` with HIP-event kernel times and what bounds the step, `cpu_baseline` — everything but the legs that never ran."""
@@ -1079,7 +1128,7 @@ def test_bench_killed_inside_an_optional_leg_has_left_its_record():
     import signal
     import time
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--rows", "200000", "--batch-rows", "100000",
-           "--no-pmc", "--cpu-budget", "2", "--settle", "0.1"]
+           "--no-pmc", "--cpu-budget", "2", "--settle", "0.1", "--full"]
     env = dict({k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")},
                FMHIP_BENCH_TEST_STALL="hbm_resident")
     p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
@@ -1111,7 +1160,7 @@ def test_bench_killed_inside_an_optional_leg_has_left_its_record():
 def test_bench_under_the_drivers_launcher():
     """The driver starts an N > 1 bench as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py --gpus N --steps K --warmup W` (one rank per GPU, env:// rendezvous from RANK / LOCAL_RANK /
-    WORLD_SIZE / MASTER_*).  That launch path — not the bench's own spawn_ranks — with two ranks on the one GPU of the test box
+    WORLD_SIZE / MASTER_*).  That launch path — not the bench's own spawn_ranks — with `--full` and two ranks on the one GPU of the test box
     (`--transport host`: RCCL refuses two ranks on a device): the launcher's environment (OMP_NUM_THREADS=1 and all) reaches the
     ranks, the gloo control plane forms over env://, rank 0's JSON lines are the launcher's stdout and nothing else is, the
     first headline comes BEFORE the cut / mode sweep, the final line is complete."""
@@ -1125,7 +1174,7 @@ def test_bench_under_the_drivers_launcher():
             port = s.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
                os.path.join(ROOT, "bench.py"), "--gpus", "2", "--transport", "host", "--steps", "4", "--warmup", "2",
-               "--rows", "200000", "--batch-rows", "100000", "--no-pmc", "--cpu-budget", "2", "--tune-budget", "6"]
+               "--rows", "200000", "--batch-rows", "100000", "--no-pmc", "--cpu-budget", "2", "--tune-budget", "6", "--full"]
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
         if r.returncode == 0 or not any(m in r.stderr.decode().lower() for m in ("eaddrinuse", "address already in use")):
             break

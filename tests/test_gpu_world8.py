@@ -227,7 +227,7 @@ def test_two_threads_train_two_models_on_one_gpu():
 
 
 def test_bench_with_eight_thread_ranks():
-    """`python bench.py --gpus 8 --transport threads`: the bench's whole N = 8 flow on the one GPU of the test box — eight ranks
+    """`python bench.py --gpus 8 --transport threads --full`: the bench's whole N = 8 flow on the one GPU of the test box — eight ranks
     as threads of one process, the library's communicators over the thread transport, plan agreement, cut AND mode tuning over
     8 ranks, the timed region with its barriers and max over ranks, the exchange profile, the legs without exchange, the C3
     twin, rank 0's counter passes (rocprofv3 child processes over tools/pmc_leg.py c4) and CPU baseline while the other ranks
@@ -235,7 +235,7 @@ def test_bench_with_eight_thread_ranks():
     and its wall time are what is tested."""
     import time
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--transport", "threads", "--steps", "4", "--warmup", "2",
-           "--rows", "100000", "--batch-rows", "50000", "--cpu-budget", "3", "--tune-budget", "12"]
+           "--rows", "100000", "--batch-rows", "50000", "--cpu-budget", "3", "--tune-budget", "12", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     t0 = time.time()
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)

@@ -400,6 +400,14 @@ def test_bench_steps_and_dump_sample():
         assert len(ids) * (k + 2) * 8 <= 60 << 20 and len(ids) > 100_000
 
 
+def test_bench_full_is_opt_in():
+    """A plain bench.py run prints the headline alone; the legs, the kernel pass and the roofline run only with --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args([]).full is False
+    assert bench.parse_args(["--full", "--time-budget", "100"]).full is True
+
+
 def test_bench_roofline_helpers():
     """bench.py's byte accounting and ceilings (pure arithmetic): ceilings stay between the Infinity-Cache and the L2
     gather rates, grow with the L2 hit rate, fall back to the HBM gather rate only when nothing is known about a table

@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage: abrun.sh "<bench args>" lib1 lib2 ...   (lib = base or a variant name)
-args="$1"; shift
+# the kernel times come from bench.py's per-kernel pass, which runs with --full only
+args="--full $1"; shift
 for v in "$@"; do
   if [ $v = base ]; then unset FMHIP_LIB; else export FMHIP_LIB=sparkfm_amd/lib/libfmhip_$v.so; fi
   python bench.py --no-cpu-baseline --no-extra --no-pmc $args > gpurun_out/ab_$v.log 2>&1

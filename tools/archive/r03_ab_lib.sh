@@ -7,7 +7,7 @@ cfgs=${2:-C3 C5}
 for cfg in $cfgs; do
   for lib in base $name; do
     if [ $lib = base ]; then unset FMHIP_LIB; else export FMHIP_LIB=$PWD/sparkfm_amd/lib/libfmhip_$lib.so; fi
-    timeout -k 10 200 python3 bench.py --config $cfg --no-extra --no-cpu-baseline --no-pmc --steps 120 --warmup 12 \
+    timeout -k 10 200 python3 bench.py --full --config $cfg --no-extra --no-cpu-baseline --no-pmc --steps 120 --warmup 12 \
       > gpurun_out/r03_lib_${cfg}_$lib.json 2> gpurun_out/r03_lib_${cfg}_$lib.err || { echo "$cfg $lib FAILED"; tail -3 gpurun_out/r03_lib_${cfg}_$lib.err; exit 1; }
     python3 - <<PY
 import json

@@ -6,7 +6,7 @@ cfgs=${1:-C3 C5 C4 C2}
 pagelist=${2:-4 6 8}
 for cfg in $cfgs; do
   for pages in $pagelist; do
-    timeout -k 10 200 python3 bench.py --config $cfg --no-extra --no-cpu-baseline --no-pmc --hot-pages $pages --steps 120 --warmup 12 \
+    timeout -k 10 200 python3 bench.py --full --config $cfg --no-extra --no-cpu-baseline --no-pmc --hot-pages $pages --steps 120 --warmup 12 \
       > gpurun_out/r03_pages_${cfg}_$pages.json 2> gpurun_out/r03_pages_${cfg}_$pages.err
     python3 - <<PY
 import json

@@ -7,7 +7,7 @@ cfgs=${2:-C3 C2 C5 C4}
 for cfg in $cfgs; do
   for kv in $settings; do
     tag=${kv/=/_}
-    timeout -k 10 200 python3 bench.py --config $cfg --no-extra --no-cpu-baseline --no-pmc --tune $kv --steps 120 --warmup 12 \
+    timeout -k 10 200 python3 bench.py --full --config $cfg --no-extra --no-cpu-baseline --no-pmc --tune $kv --steps 120 --warmup 12 \
       > gpurun_out/r03_tune_${cfg}_$tag.json 2> gpurun_out/r03_tune_${cfg}_$tag.err || { echo "$cfg $kv FAILED"; tail -3 gpurun_out/r03_tune_${cfg}_$tag.err; exit 1; }
     python3 - <<PY
 import json

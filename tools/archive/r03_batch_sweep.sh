@@ -5,7 +5,7 @@ cfgs=${1:-C3}
 sizes=${2:-125000 250000 500000 1000000}
 for cfg in $cfgs; do
   for b in $sizes; do
-    timeout -k 10 200 python3 bench.py --config $cfg --no-extra --no-cpu-baseline --no-pmc --batch-rows $b --steps 96 --warmup 12 \
+    timeout -k 10 200 python3 bench.py --full --config $cfg --no-extra --no-cpu-baseline --no-pmc --batch-rows $b --steps 96 --warmup 12 \
       > gpurun_out/r03_batch_${cfg}_$b.json 2> gpurun_out/r03_batch_${cfg}_$b.err || { echo "$cfg $b FAILED"; tail -3 gpurun_out/r03_batch_${cfg}_$b.err; exit 1; }
     python3 - <<PY
 import json

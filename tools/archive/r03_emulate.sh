@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 specs=${1:-8:300}; shift || true
 for spec in $specs; do
   tag=${spec/:/_}
-  timeout -k 10 300 python3 bench.py --gpus 1 --force-dp --config C4 --emulate-allreduce $spec --no-cpu-baseline --steps 60 --warmup 8 "$@" \
+  timeout -k 10 300 python3 bench.py --full --gpus 1 --force-dp --config C4 --emulate-allreduce $spec --no-cpu-baseline --steps 60 --warmup 8 "$@" \
     > gpurun_out/r03_emulated_dp_c4_$tag.json 2> gpurun_out/r03_emulated_dp_c4_$tag.err
   python3 - <<PY
 import json

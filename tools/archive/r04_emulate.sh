@@ -8,7 +8,7 @@
 cd "$(dirname "$0")/../.."
 run() { # ranks:busbw wgs
   local tag=r04_emulated_dp_c4_${1/:/_}_wg$2
-  timeout -k 10 400 python bench.py --gpus 1 --force-dp --config C4 --rows 1250000 --batch-rows 625000 --emulate-allreduce $1 --emulate-load $2 --no-cpu-baseline --no-pmc --no-extra \
+  timeout -k 10 400 python bench.py --full --gpus 1 --force-dp --config C4 --rows 1250000 --batch-rows 625000 --emulate-allreduce $1 --emulate-load $2 --no-cpu-baseline --no-pmc --no-extra \
       > gpurun_out/$tag.json 2> gpurun_out/$tag.err
   local rc=$?
   echo "$tag rc=$rc"

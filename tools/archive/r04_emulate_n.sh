@@ -7,7 +7,7 @@
 cd "$(dirname "$0")/../.."
 run() { # ranks busbw batch_rows rows
   local tag=r04_emulated_dp_c4_$1_$2_b$3
-  timeout -k 10 500 python3 bench.py --gpus 1 --force-dp --config C4 --rows $4 --batch-rows $3 --emulate-allreduce $1:$2 --emulate-load 32 \
+  timeout -k 10 500 python3 bench.py --full --gpus 1 --force-dp --config C4 --rows $4 --batch-rows $3 --emulate-allreduce $1:$2 --emulate-load 32 \
       --no-cpu-baseline --no-pmc --no-extra > gpurun_out/$tag.json 2> gpurun_out/$tag.err
   local rc=$?
   echo "$tag rc=$rc"

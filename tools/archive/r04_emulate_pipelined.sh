@@ -6,7 +6,7 @@ cd "$(dirname "$0")/../.."
 mkdir -p gpurun_out
 for r in ${RATES:-8:300 8:450 8:200}; do
   tag=r04_emulated_dp_c4_${r/:/_}_wg64_modes3
-  timeout -k 10 500 python bench.py --gpus 1 --force-dp --config C4 --rows 1250000 --batch-rows 625000 --emulate-allreduce $r --emulate-load 64 \
+  timeout -k 10 500 python bench.py --full --gpus 1 --force-dp --config C4 --rows 1250000 --batch-rows 625000 --emulate-allreduce $r --emulate-load 64 \
       --no-cpu-baseline --no-pmc --no-extra > gpurun_out/$tag.json 2> gpurun_out/$tag.err
   rc=$?
   echo "$tag rc=$rc"

@@ -1,10 +1,12 @@
 #!/bin/bash
 # A/B of an environment switch on the GPU box: tools/r05_ab_env.sh VAR "<bench args>" ["<bench args>" ...]
-# runs bench.py (headline only) with VAR unset and VAR=1, twice each in alternation, and prints nnz/s, ms/step and kernel times.
+# runs bench.py (headline and per-kernel pass: --full, without its legs) with VAR unset and VAR=1, twice each in alternation, and
+# prints nnz/s, ms/step and kernel times.
 var=$1; shift
 mkdir -p gpurun_out/r05
 for args in "$@"; do
   tag=$(echo "$args" | tr -c 'A-Za-z0-9' '_')
+  args="$args --full"
   for rep in 1 2; do
     for on in 0 1; do
       if [ $on = 1 ]; then export $var=1; else unset $var; fi

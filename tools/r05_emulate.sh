@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out/r05
 tag=$1; r=$2; mode=$3; fr=$4; shift 4
-timeout -k 10 300 python3 bench.py --gpus 1 --force-dp --config C4 --rows 1250000 --batch-rows 625000 --emulate-allreduce $r --emulate-load 64 \
+timeout -k 10 300 python3 bench.py --full --gpus 1 --force-dp --config C4 --rows 1250000 --batch-rows 625000 --emulate-allreduce $r --emulate-load 64 \
     --dp-exchange $mode --upper-fractions $fr --steps 100 --warmup 10 --no-cpu-baseline --no-pmc --no-extra "$@" > gpurun_out/r05/emu_$tag.json 2> gpurun_out/r05/emu_$tag.err
 rc=$?
 if [ $rc -ne 0 ]; then echo "$tag rc=$rc"; tail -5 gpurun_out/r05/emu_$tag.err; fi
