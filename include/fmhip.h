@@ -41,11 +41,11 @@
  *  - threads.  Different handles are independent: any number of host threads may work on their own models / datasets /
  *    communicators at once, on one GPU or several (the reference's `local[*]` runs its tasks as threads of one JVM,
  *    S/driver.scala:14).  ONE model is guarded by a reader-writer lock inside the library: the scoring calls
- *    (fmhip_predict, fmhip_predict_rows, fmhip_rmse, fmhip_residual, fmhip_term_q) and the parameter reads
+ *    (fmhip_predict, fmhip_predict_rows, fmhip_rmse, fmhip_logloss, fmhip_residual, fmhip_term_q) and the parameter reads
  *    (fmhip_model_get_params*, fmhip_model_get_rows, fmhip_model_info) are RE-ENTRANT — each call works on a stream and in
  *    a workspace of its own, so executor threads score through one frozen model side by side (S/Model.scala:14) and each
  *    gets the bits a lone caller would get; every call that changes the model (set_params, init, training, the split and
- *    the data-parallel step, gradient binding; tuning and profiling in fmhip_experimental.h) takes the lock exclusively and so runs alone, after the
+ *    the data-parallel step, gradient binding, the loss; tuning and profiling in fmhip_experimental.h) takes the lock exclusively and so runs alone, after the
  *    readers before it and before those behind it.  A dataset is immutable once created and may be shared by any number of
  *    threads.  A communicator belongs to the thread that drives its model.  Destroying a
  *    handle while another thread still uses it is the caller's bug.
@@ -80,11 +80,13 @@ typedef struct fmhip_dataset *fmhip_dataset_t;
 typedef struct fmhip_comm *fmhip_comm_t;
 
 typedef struct fmhip_stats {
-    double sse;        /* sum over processed rows of e^2, e = yhat - y (S/fm/lib/ALS.scala:143) */
+    double sse;        /* sum over processed rows of e^2, e = yhat - y (S/fm/lib/ALS.scala:143); under the logistic loss
+                        * (training calls of such a model, and fmhip_logloss) e = sigma(yhat) - t, t = [y > 0]: sse/rows = Brier score */
     double sum_e;      /* sum of e */
     int64_t rows;      /* rows processed */
     int64_t nnz;       /* stored nonzeros processed */
-    int64_t nonfinite; /* rows whose prediction was NaN/Inf (never masked; cf. S/fm/lib/ALS.scala:190-192) */
+    int64_t nonfinite; /* rows whose prediction was NaN/Inf (never masked; cf. S/fm/lib/ALS.scala:190-192); under the logistic
+                        * loss the rows whose margin yhat was, though sigma(+-Inf) is finite */
     int64_t steps;     /* mini-batch steps taken */
 } fmhip_stats;
 
@@ -115,6 +117,17 @@ int fmhip_model_get_rows(fmhip_model_t m, int64_t n, const int32_t *ids, double 
 int fmhip_model_set_params_f32(fmhip_model_t m, float w0, const float *w, const float *v);
 int fmhip_model_get_params_f32(fmhip_model_t m, float *w0, float *w, float *v);
 int fmhip_synchronize(fmhip_model_t m);
+/* The loss the model TRAINS under (binary classification: SparkFM's Task.Classification, S/Task.scala, which the reference
+ * declares and never reads).  Squared: e = yhat - y.  Logistic: e = sigma(yhat) - t with t = [y > 0] (labels {0,1} or {-1,+1}),
+ * the gradient of the mean binary cross-entropy of sigma(yhat) — the same sum g_theta = sum e_r h_r(theta) below, with this e.
+ * It applies to every training call: fmhip_sgd_step / _epoch, fmhip_batch_grad, fmhip_step_compute / _forward / _backward / _apply,
+ * and every fmhip_dp_* mode (fmhip_dp_plan agrees it over the ranks and fails on every rank if they differ; a model whose loss
+ * changes after the plan contributes zeros and returns FMHIP_ERR_INVALID).  Their stats' sum_e and sse are over that e.  The scoring
+ * calls fmhip_predict(_rows) (the margin yhat), fmhip_rmse, fmhip_residual and fmhip_term_q do not depend on it; fmhip_als_epoch
+ * refuses a logistic model (FMHIP_ERR_UNSUPPORTED; ALS is derived for the squared loss).  A new model is squared; neither
+ * fmhip_model_set_params nor fmhip_model_init_normal resets it.  Any other value: FMHIP_ERR_INVALID. */
+enum fmhip_loss { FMHIP_LOSS_SQUARED = 0, FMHIP_LOSS_LOGISTIC = 1 };
+int fmhip_model_set_loss(fmhip_model_t m, int loss);
 
 /* ---- dataset: DataSet(rdd).cache() + transposeInput  S/DataSet.scala:42-62,31-38 */
 /* Copies the rows to the GPU, cuts them into mini-batches of `batch_rows` consecutive
@@ -164,6 +177,10 @@ int fmhip_predict_rows(fmhip_model_t m, int64_t n_rows, const int64_t *row_ptr, 
                        double *yhat /* n_rows */);
 /* Model.computeRMSE (S/Model.scala:13-19) */
 int fmhip_rmse(fmhip_model_t m, fmhip_dataset_t d, double *rmse, fmhip_stats *stats /* nullable */);
+/* Binary classification score, whatever the model's loss: the mean over rows of the log-loss
+ *   l = max(yhat, 0) - t*yhat + log1p(exp(-|yhat|)),  t = [y > 0]  (-log sigma(yhat) for t = 1, -log(1 - sigma(yhat)) for t = 0),
+ * summed in fp64.  stats: sum_e and sse over e = sigma(yhat) - t (sse/rows = Brier score); rows, nnz, nonfinite as for fmhip_rmse. */
+int fmhip_logloss(fmhip_model_t m, fmhip_dataset_t d, double *logloss, fmhip_stats *stats /* nullable */);
 /* ALS.precomputeTermE (S/fm/lib/ALS.scala:142-144): e_r = yhat_r - y_r */
 int fmhip_residual(fmhip_model_t m, fmhip_dataset_t d, double *e /* n_rows */);
 /* ALS.precomputeTermQ for every factor (S/fm/lib/ALS.scala:146-150): q[r*k + f] */
@@ -171,7 +188,8 @@ int fmhip_term_q(fmhip_model_t m, fmhip_dataset_t d, double *q /* n_rows*k */);
 
 /* ---- training (build-defined mini-batch SGD; SparkFM itself only ships ALS) ---- */
 /*   g_theta = sum_{r in batch} e_r * h_r(theta),  h from S/fm/lib/ALS.scala:56-58 (V), :40 (w), :21 (w0)
- *   theta  <- theta - eta * (g_theta / |batch| + reg_theta * theta)                                  */
+ *   theta  <- theta - eta * (g_theta / |batch| + reg_theta * theta)
+ * e_r = yhat_r - y_r, or sigma(yhat_r) - [y_r > 0] for a model set to FMHIP_LOSS_LOGISTIC (fmhip_model_set_loss)            */
 int fmhip_sgd_step(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, double eta, double reg0, double regw,
                    double regv, fmhip_stats *stats /* nullable: skips the host sync */);
 /* one pass over all batches; order[n_batches] = batch visiting order (NULL = ascending) */
@@ -195,7 +213,7 @@ int fmhip_als_epoch(fmhip_model_t m, fmhip_dataset_t d, double reg0, double regw
  * n1p = n+1 rounded up to 4, Kp = padded factors; fmhip_grad_layout returns Kp and the offset of
  * G_V.  G_V holds sum e*x*q; G_b holds sum e*x^2 (the -x^2*v term of h is applied in
  * fmhip_step_apply, so the packed buffer is a plain sum over rows and all-reduces with `sum`).
- * scalars = {sum e, sum e^2, rows, nonfinite}.  The head (everything before G_V) lies next to the
+ * scalars = {sum e, sum e^2, rows, nonfinite} (e: the model's loss).  The head (everything before G_V) lies next to the
  * G_V rows of the lowest feature ids — the interval a feature-chunked backward finishes last — so
  * the last collective of a step can cover head + interval in one message. */
 int fmhip_grad_floats(fmhip_model_t m, int64_t *n_floats);

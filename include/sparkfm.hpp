@@ -143,6 +143,11 @@ class FMModel {
         check(fmhip_rmse(upload(), dataset.handle(), &rmse, nullptr));
         return rmse;
     }
+    double computeLogLoss(DataSet &dataset) {    // mean log-loss of sigmoid(predict) against t = [y > 0], whatever the training loss
+        double logloss = 0.0;
+        check(fmhip_logloss(upload(), dataset.handle(), &logloss, nullptr));
+        return logloss;
+    }
 
     // the device replica: created on first use, refreshed from the host fields before every use (they are public and mutable)
     fmhip_model_t upload() {
@@ -166,13 +171,19 @@ class FMLearn {
 
 // One learn = one epoch of mini-batch SGD over the dataset's batches (ascending order) — fmhip_sgd_epoch.
 // theta <- theta - eta * (sum_{r in batch} e_r h_r(theta) / |batch| + reg * theta), e and h from S/fm/lib/ALS.scala:142-144, :56-58 / :40 / :21
+// loss = FMHIP_LOSS_LOGISTIC: e = sigmoid(yhat) - [y > 0], a binary classifier (fmhip_model_set_loss)
 class HipSGD : public FMLearn {
   public:
     double eta, reg0, regw, regv;
+    int loss;
     fmhip_stats last_stats{};
-    explicit HipSGD(double eta_ = 0.05, double reg0_ = 0.0, double regw_ = 0.0, double regv_ = 0.0) : eta(eta_), reg0(reg0_), regw(regw_), regv(regv_) {}
-    static HipSGD run(double eta = 0.05, double reg0 = 0.0, double regw = 0.0, double regv = 0.0) { return HipSGD(eta, reg0, regw, regv); }   // cf. ALS.run(), S/fm/lib/ALS.scala:202-208
+    explicit HipSGD(double eta_ = 0.05, double reg0_ = 0.0, double regw_ = 0.0, double regv_ = 0.0, int loss_ = FMHIP_LOSS_SQUARED)
+        : eta(eta_), reg0(reg0_), regw(regw_), regv(regv_), loss(loss_) {}
+    static HipSGD run(double eta = 0.05, double reg0 = 0.0, double regw = 0.0, double regv = 0.0, int loss = FMHIP_LOSS_SQUARED) {
+        return HipSGD(eta, reg0, regw, regv, loss);   // cf. ALS.run(), S/fm/lib/ALS.scala:202-208
+    }
     FMModel &learn(FMModel &fm, DataSet &dataset) override {
+        check(fmhip_model_set_loss(fm.upload(), loss));
         check(fmhip_sgd_epoch(fm.upload(), dataset.handle(), eta, reg0, regw, regv, nullptr, &last_stats));
         fm.download();
         return fm;

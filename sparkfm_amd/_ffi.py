@@ -18,10 +18,10 @@ SYMBOLS = (
     "fmhip_version", "fmhip_last_error", "fmhip_device_count",
     "fmhip_model_create", "fmhip_model_destroy", "fmhip_model_info", "fmhip_model_init_normal",
     "fmhip_model_set_params", "fmhip_model_get_params", "fmhip_model_get_rows", "fmhip_model_set_params_f32", "fmhip_model_get_params_f32",
-    "fmhip_synchronize",
+    "fmhip_synchronize", "fmhip_model_set_loss",
     "fmhip_dataset_create", "fmhip_dataset_create_f32", "fmhip_dataset_create_opts", "fmhip_rows_create", "fmhip_rows_create_f32",
     "fmhip_dataset_destroy", "fmhip_dataset_info", "fmhip_dataset_batch_info", "fmhip_dataset_get_transpose",
-    "fmhip_predict", "fmhip_predict_rows", "fmhip_rmse", "fmhip_residual", "fmhip_term_q",
+    "fmhip_predict", "fmhip_predict_rows", "fmhip_rmse", "fmhip_logloss", "fmhip_residual", "fmhip_term_q",
     "fmhip_sgd_step", "fmhip_sgd_epoch", "fmhip_batch_grad", "fmhip_als_epoch",
     "fmhip_grad_floats", "fmhip_grad_bind", "fmhip_grad_ptr", "fmhip_grad_layout", "fmhip_step_compute",
     "fmhip_step_forward", "fmhip_step_backward", "fmhip_step_apply", "fmhip_step_stats",
@@ -46,6 +46,16 @@ SYMBOLS_EXPERIMENTAL = (
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
 TUNE = {name[5:]: value for name, value in list(globals().items()) if name.startswith("TUNE_")}
 UNIQUE_ID_BYTES = 128
+# enum fmhip_loss (include/fmhip.h): the loss a model trains under (fmhip_model_set_loss)
+LOSS_SQUARED, LOSS_LOGISTIC = 0, 1
+LOSSES = {"squared": LOSS_SQUARED, "logistic": LOSS_LOGISTIC}
+
+
+def loss_code(loss):
+    """'squared' | 'logistic' -> enum fmhip_loss; anything else raises ValueError."""
+    if loss not in LOSSES:
+        raise ValueError("loss must be one of %s, not %r" % (sorted(LOSSES), loss))
+    return LOSSES[loss]
 
 
 class Stats(C.Structure):
@@ -132,6 +142,8 @@ def load():
     L.fmhip_dataset_get_transpose.argtypes = [vp, i64, vp, vp, vp, vp]
     L.fmhip_predict.argtypes = [vp, vp, vp]
     L.fmhip_rmse.argtypes = [vp, vp, P(dbl), P(Stats)]
+    L.fmhip_logloss.argtypes = [vp, vp, P(dbl), P(Stats)]
+    L.fmhip_model_set_loss.argtypes = [vp, C.c_int]
     L.fmhip_residual.argtypes = [vp, vp, vp]
     L.fmhip_term_q.argtypes = [vp, vp, vp]
     L.fmhip_sgd_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, P(Stats)]

@@ -278,10 +278,12 @@ __device__ __forceinline__ void apply_w0(const ApplyArgs &a, float invb) {
 // one block, fixed order: sums the forward's per-block partials into
 // scal = {sum e, sum e^2, rows, nonfinite} (fp32, part of the packed gradient) and acc (fp64, +=)
 // w0 (optional): also steps the bias, theta <- theta - eta*(sum e / rows + reg0*theta) — what k_apply does in the unfused path
+// WITH_L (the scoring pass of fmhip_logloss): the partials' fourth slot, the log-loss, is summed too into acc[4] (sh: 4 rows)
+template <bool WITH_L = false>
 __device__ __forceinline__ void reduce_blocks_body(const double *bsum, int32_t nblocks, int32_t n_rows, float *scal,
                                                    double *acc, double (*sh)[kBlock / 64], float *w0 = nullptr, float eta = 0.f,
                                                    float reg0 = 0.f) {
-    double s1 = 0.0, s2 = 0.0, bad = 0.0;
+    double s1 = 0.0, s2 = 0.0, bad = 0.0, ll = 0.0;
     const double4 *b4 = reinterpret_cast<const double4 *>(bsum);
     int i = threadIdx.x;
     for (; i + 3 * kBlock < nblocks; i += 4 * kBlock) {   // four loads in flight; added in index order
@@ -290,27 +292,36 @@ __device__ __forceinline__ void reduce_blocks_body(const double *bsum, int32_t n
         s1 += b1.x; s2 += b1.y; bad += b1.z;
         s1 += b2.x; s2 += b2.y; bad += b2.z;
         s1 += b3.x; s2 += b3.y; bad += b3.z;
+        if (WITH_L) { ll += b0.w; ll += b1.w; ll += b2.w; ll += b3.w; }
     }
     for (; i < nblocks; i += kBlock) {
         const double4 b = b4[i];
         s1 += b.x;
         s2 += b.y;
         bad += b.z;
+        if (WITH_L) ll += b.w;
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         s1 += __shfl_xor(s1, m, 64);
         s2 += __shfl_xor(s2, m, 64);
         bad += __shfl_xor(bad, m, 64);
+        if (WITH_L) ll += __shfl_xor(ll, m, 64);
     }
     const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[0][wv] = s1; sh[1][wv] = s2; sh[2][wv] = bad; }
+    if ((threadIdx.x & 63) == 0) {
+        sh[0][wv] = s1; sh[1][wv] = s2; sh[2][wv] = bad;
+        if (WITH_L) sh[3][wv] = ll;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        double t1 = 0.0, t2 = 0.0, tb = 0.0;
+        double t1 = 0.0, t2 = 0.0, tb = 0.0, tl = 0.0;
         for (int i = 0; i < kBlock / 64; ++i) { t1 += sh[0][i]; t2 += sh[1][i]; tb += sh[2][i]; }
+        if (WITH_L)
+            for (int i = 0; i < kBlock / 64; ++i) tl += sh[3][i];
         if (scal) { scal[0] = (float)t1; scal[1] = (float)t2; scal[2] = (float)n_rows; scal[3] = (float)tb; }
         if (acc) { acc[0] += t1; acc[1] += t2; acc[2] += (double)n_rows; acc[3] += tb; }
+        if (WITH_L && acc) acc[4] += tl;
         if (w0) {
             const float rows = (float)n_rows, invb = rows > 0.f ? 1.0f / rows : 0.f, b0 = *w0;
             *w0 = b0 - eta * fmaf(reg0, b0, (float)t1 * invb);

@@ -278,15 +278,18 @@ __device__ __forceinline__ void fwd_step(const float *V, __amdgpu_buffer_rsrc_t 
 // thread's share of the residual statistics.  q, s and lin are in units of the STORED tables; the scales
 // of a lazily decayed model (FwdArgs.sv / .sw; both 1 otherwise, and multiplying by 1 is exact) enter here:
 // the interaction is homogeneous of degree 2 in V, so a single-nonzero row still gives exactly 0 (quirk Q6).
+// Under the logistic loss (MODE | kFwdLogistic) the residual is e = sigma(yhat) - t, t = [y > 0], and a scoring pass
+// (kFwdResidual) also adds the row's log-loss to stl.  A template flag rather than a runtime branch on FwdArgs.loss: the branch,
+// never taken, cost the squared-loss kernels two registers and, at Kp = 32, a wave per SIMD.
 template <int LPN, int J, int MODE, bool PACKED>
 __device__ __forceinline__ void row_finish(const FwdArgs &a, int r, int l, float4 (&q)[J], float4 (&s)[J], float lin, float w0,
-                                           float &st1, float &st2, float &stbad) {
+                                           float &st1, float &st2, float &stbad, float &stl) {
     constexpr int KP = 4 * LPN * J;
     // Packed rows (k < Kp): slot k of every V row holds the feature's linear weight w_i, so q_k
     // accumulated sum w_i x_i — the linear term — and there was no separate w gather; slot k of the P row
     // carries e to the backward the same way.
     const int kl = PACKED ? (a.pack_k >> 2) & (LPN - 1) : 0, kj = PACKED ? (a.pack_k >> 2) / LPN : 0, kc = a.pack_k & 3;
-    if (MODE == kFwdPartA) {
+    if (fwd_mode(MODE) == kFwdPartA) {
         // pass A of a two-pass forward: the row's raw sums go out as they are — q (slot k of a packed row: the linear term so
         // far) into the P row, sum_f s_f and the lanes' linear terms, each summed over the slot, into part_sl
         float sp = 0.f, lp = lin;
@@ -320,12 +323,25 @@ __device__ __forceinline__ void row_finish(const FwdArgs &a, int r, int l, float
     for (int jj = 0; jj < J; ++jj) u += f4sqminus(q[jj], s[jj]);
     float tot = fmaf(0.5f * a.sv * a.sv, u, a.sw * lin);
     // pass B: q already holds pass A's share (the row started from it); its sum_f s_f and linear term enter once, through lane 0
-    if (MODE == kFwdPartB && l == 0) tot += fmaf(-0.5f * a.sv * a.sv, a.part_sl[2 * (size_t)r], a.sw * a.part_sl[2 * (size_t)r + 1]);
+    if (fwd_mode(MODE) == kFwdPartB && l == 0) tot += fmaf(-0.5f * a.sv * a.sv, a.part_sl[2 * (size_t)r], a.sw * a.part_sl[2 * (size_t)r + 1]);
 #pragma unroll
     for (int m = LPN >> 1; m >= 1; m >>= 1) tot += __shfl_xor(tot, m, LPN);
     const float yhat = w0 + (tot + lin_all);
-    const float e = yhat - a.y[a.row0 + r];
-    if (MODE == kFwdTrain || MODE == kFwdPartB) {
+    constexpr bool logistic = (MODE & kFwdLogistic) != 0;
+    float e, lrow = 0.f;
+    if constexpr (logistic) {
+        // sigma without overflow: z = exp(-|yhat|) <= 1.  1 - sigma(yhat) = sigma(-yhat) is formed directly, so a saturated
+        // margin on the right side gives a tiny e rather than a difference of two numbers near 1
+        const bool t = a.y[a.row0 + r] > 0.f;
+        const float z = expf(-fabsf(yhat)), inv = 1.f / (1.f + z);
+        const bool pos = yhat >= 0.f;
+        e = t ? -(pos ? z * inv : inv) : (pos ? inv : z * inv);
+        // l = max(yhat, 0) - t*yhat + log1p(exp(-|yhat|)); its first two terms are max(t ? -yhat : yhat, 0)
+        if constexpr (fwd_mode(MODE) == kFwdResidual) lrow = fmaxf(t ? -yhat : yhat, 0.f) + log1pf(z);
+    } else {
+        e = yhat - a.y[a.row0 + r];
+    }
+    if (fwd_mode(MODE) == kFwdTrain || fwd_mode(MODE) == kFwdPartB) {
         float4 *pr = reinterpret_cast<float4 *>(a.P + (size_t)r * KP) + l;
         const float es = e * a.sv;
 #pragma unroll
@@ -335,7 +351,7 @@ __device__ __forceinline__ void row_finish(const FwdArgs &a, int r, int l, float
             if (!PACKED && kEInP && jj == 0 && l < 8) o = embed_bits4(o, __float_as_uint(e) >> (4 * l));   // no spare slot: e rides in the LSBs (fm_device.h)
             p_store(pr + jj * LPN, o);
         }
-    } else if (MODE == kFwdQ) {
+    } else if (fwd_mode(MODE) == kFwdQ) {
         float4 *pr = reinterpret_cast<float4 *>(a.P + (size_t)r * KP) + l;
 #pragma unroll
         for (int jj = 0; jj < J; ++jj) pr[jj * LPN] = f4mul(q[jj], a.sv);
@@ -345,31 +361,39 @@ __device__ __forceinline__ void row_finish(const FwdArgs &a, int r, int l, float
         if (a.yhat) a.yhat[r] = yhat;
         st1 += e;
         st2 = fmaf(e, e, st2);
-        if (!isfinite(e)) stbad += 1.f;
+        if (!isfinite(logistic ? yhat : e)) stbad += 1.f;     // sigma(+-inf) is finite: the logistic loss counts the margin
+        if (logistic && fwd_mode(MODE) == kFwdResidual) stl += lrow;
     }
 }
 
-// block partial of the residual statistics (fixed order; the fixup launch / k_reduce_blocks finishes the sum)
-template <int NT>
-__device__ __forceinline__ void block_stats(double *bsum, float st1, float st2, float stbad) {
+// block partial of the residual statistics (fixed order; the fixup launch / k_reduce_blocks finishes the sum).  WITH_L (the
+// log-loss scoring pass, kFwdResidual | kFwdLogistic): the fourth slot carries the log-loss; every other mode leaves it 0.
+template <int NT, bool WITH_L>
+__device__ __forceinline__ void block_stats(double *bsum, float st1, float st2, float stbad, float stl) {
     if (!bsum) return;
-    __shared__ double sh[3][NT / 64];
-    double d1 = st1, d2 = st2, db = stbad;
+    __shared__ double sh[WITH_L ? 4 : 3][NT / 64];
+    double d1 = st1, d2 = st2, db = stbad, dl = WITH_L ? stl : 0.f;
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         d1 += __shfl_xor(d1, m, 64);
         d2 += __shfl_xor(d2, m, 64);
         db += __shfl_xor(db, m, 64);
+        if (WITH_L) dl += __shfl_xor(dl, m, 64);
     }
     const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[0][wv] = d1; sh[1][wv] = d2; sh[2][wv] = db; }
+    if ((threadIdx.x & 63) == 0) {
+        sh[0][wv] = d1; sh[1][wv] = d2; sh[2][wv] = db;
+        if (WITH_L) sh[WITH_L ? 3 : 0][wv] = dl;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        double t1 = 0.0, t2 = 0.0, tb = 0.0;
+        double t1 = 0.0, t2 = 0.0, tb = 0.0, tl = 0.0;
 #pragma unroll
         for (int i = 0; i < NT / 64; ++i) { t1 += sh[0][i]; t2 += sh[1][i]; tb += sh[2][i]; }
+        if (WITH_L)
+            for (int i = 0; i < NT / 64; ++i) tl += sh[WITH_L ? 3 : 0][i];
         double *o = bsum + (size_t)blockIdx.x * 4;
-        o[0] = t1; o[1] = t2; o[2] = tb; o[3] = 0.0;
+        o[0] = t1; o[1] = t2; o[2] = tb; o[3] = tl;
     }
 }
 
@@ -394,7 +418,7 @@ __global__ __launch_bounds__(kLdsBlock) void k_forward_lds(FwdArgs a) {
     const int slot = threadIdx.x / LPN;
     const float w0 = *a.w0;
     const __amdgpu_buffer_rsrc_t vr = make_rsrc(a.V, a.v_bytes);
-    float st1 = 0.f, st2 = 0.f, stbad = 0.f;
+    float st1 = 0.f, st2 = 0.f, stbad = 0.f, stl = 0.f;
     for (int ri = blockIdx.x * SLOTS + slot; ri < a.n_rows; ri += gridDim.x * SLOTS) {
         const int r = a.order ? a.order[ri] : ri;
         const int64_t p0 = a.row_ptr[a.row0 + r], p1 = a.row_ptr[a.row0 + r + 1];
@@ -442,9 +466,9 @@ __global__ __launch_bounds__(kLdsBlock) void k_forward_lds(FwdArgs a) {
                 }
             }
         }
-        row_finish<LPN, J, MODE, false>(a, r, l, q, s, lin, w0, st1, st2, stbad);
+        row_finish<LPN, J, MODE, false>(a, r, l, q, s, lin, w0, st1, st2, stbad, stl);
     }
-    block_stats<kLdsBlock>(a.bsum, st1, st2, stbad);
+    block_stats<kLdsBlock, MODE == (kFwdResidual | kFwdLogistic)>(a.bsum, st1, st2, stbad, stl);
 }
 
 // The linear weight of feature c: from the LDS tile when c < T, else from the table.  Written as one LDS read and one
@@ -485,7 +509,7 @@ __device__ __forceinline__ void forward_rows(const FwdArgs &a, const float *wt, 
     const __amdgpu_buffer_rsrc_t wr = make_rsrc(a.w, a.v_bytes / KPW);   // (n+1) floats, when V fits a buffer view
     const int32_t *colb = a.col + a.nz0;
     const float *valb = a.val + a.nz0;
-    float st1 = 0.f, st2 = 0.f, stbad = 0.f;   // this thread's share of {sum e, sum e^2, nonfinite}
+    float st1 = 0.f, st2 = 0.f, stbad = 0.f, stl = 0.f;   // this thread's share of {sum e, sum e^2, nonfinite, log-loss}
     if (BUF && FMHIP_FWD_AHEAD) {
         // Through a buffer view one loop serves full and partial steps — a dead entry is id -1 with value 0: its row offset
         // lies past the end of V (a multiple of the row size below 2^32), the gather fetches nothing and returns 0, and 0 * 0
@@ -498,12 +522,12 @@ __device__ __forceinline__ void forward_rows(const FwdArgs &a, const float *wt, 
             const int r = a.order ? a.order[ri] : ri;
             float4 xh = f4zero();
             if (HOT) xh = hot_load(a, r, l);
-            const uint32_t p0 = (uint32_t)((MODE == kFwdPartB ? a.row_split[a.row0 + r] : a.row_ptr[a.row0 + r]) - a.nz0),
-                           p1 = (uint32_t)((MODE == kFwdPartA ? a.row_split[a.row0 + r] : a.row_ptr[a.row0 + r + 1]) - a.nz0);
+            const uint32_t p0 = (uint32_t)((fwd_mode(MODE) == kFwdPartB ? a.row_split[a.row0 + r] : a.row_ptr[a.row0 + r]) - a.nz0),
+                           p1 = (uint32_t)((fwd_mode(MODE) == kFwdPartA ? a.row_split[a.row0 + r] : a.row_ptr[a.row0 + r + 1]) - a.nz0);
             float4 q[J], s[J];
 #pragma unroll
             for (int jj = 0; jj < J; ++jj) {
-                q[jj] = MODE == kFwdPartB ? reinterpret_cast<const float4 *>(a.P + (size_t)r * KPW)[jj * LPN + l] : f4zero();
+                q[jj] = fwd_mode(MODE) == kFwdPartB ? reinterpret_cast<const float4 *>(a.P + (size_t)r * KPW)[jj * LPN + l] : f4zero();
                 s[jj] = f4zero();
             }
             float lin = 0.f;
@@ -538,9 +562,9 @@ __device__ __forceinline__ void forward_rows(const FwdArgs &a, const float *wt, 
                 fwd_step<LPN, J, CH, false, BUF>(a.V, vr, slot_publish<LPN>(stage, c, x, l), c, x, LPN, l, q, s);
                 if (!PACKED) lin = fmaf(wv, x, lin);
             }
-            row_finish<LPN, J, MODE, PACKED>(a, r, l, q, s, lin, w0, st1, st2, stbad);
+            row_finish<LPN, J, MODE, PACKED>(a, r, l, q, s, lin, w0, st1, st2, stbad, stl);
         }
-        block_stats<kBlock>(a.bsum, st1, st2, stbad);
+        block_stats<kBlock, MODE == (kFwdResidual | kFwdLogistic)>(a.bsum, st1, st2, stbad, stl);
         return;
     }
     for (int ri = blockIdx.x * SLOTS + slot; ri < a.n_rows; ri += gridDim.x * SLOTS) {
@@ -548,12 +572,12 @@ __device__ __forceinline__ void forward_rows(const FwdArgs &a, const float *wt, 
         float4 xh = f4zero();
         if (HOT) xh = hot_load(a, r, l);
         // entry positions relative to the batch's first entry: 32-bit walk state (a batch holds < 2^31 entries)
-        const uint32_t p0 = (uint32_t)((MODE == kFwdPartB ? a.row_split[a.row0 + r] : a.row_ptr[a.row0 + r]) - a.nz0),
-                       p1 = (uint32_t)((MODE == kFwdPartA ? a.row_split[a.row0 + r] : a.row_ptr[a.row0 + r + 1]) - a.nz0);
+        const uint32_t p0 = (uint32_t)((fwd_mode(MODE) == kFwdPartB ? a.row_split[a.row0 + r] : a.row_ptr[a.row0 + r]) - a.nz0),
+                       p1 = (uint32_t)((fwd_mode(MODE) == kFwdPartA ? a.row_split[a.row0 + r] : a.row_ptr[a.row0 + r + 1]) - a.nz0);
         float4 q[J], s[J];
 #pragma unroll
         for (int jj = 0; jj < J; ++jj) {
-            q[jj] = MODE == kFwdPartB ? reinterpret_cast<const float4 *>(a.P + (size_t)r * KPW)[jj * LPN + l] : f4zero();
+            q[jj] = fwd_mode(MODE) == kFwdPartB ? reinterpret_cast<const float4 *>(a.P + (size_t)r * KPW)[jj * LPN + l] : f4zero();
             s[jj] = f4zero();
         }
         float lin = 0.f;
@@ -585,9 +609,9 @@ __device__ __forceinline__ void forward_rows(const FwdArgs &a, const float *wt, 
             fwd_step<LPN, J, CH, !BUF, BUF>(a.V, vr, slot_publish<LPN>(stage, c, x, l), c, x, (int)(p1 - base), l, q, s);
             if (!PACKED) lin = fmaf(wv, x, lin);
         }
-        row_finish<LPN, J, MODE, PACKED>(a, r, l, q, s, lin, w0, st1, st2, stbad);
+        row_finish<LPN, J, MODE, PACKED>(a, r, l, q, s, lin, w0, st1, st2, stbad, stl);
     }
-    block_stats<kBlock>(a.bsum, st1, st2, stbad);
+    block_stats<kBlock, MODE == (kFwdResidual | kFwdLogistic)>(a.bsum, st1, st2, stbad, stl);
 }
 
 // (Second launch bound, Kp = 32 with the hot-block prologue: left to itself the compiler takes 100 registers — four waves per
@@ -631,7 +655,7 @@ __global__ __launch_bounds__(kBlock, (LPN * J <= 8 ? FMHIP_FWD_WGS : 1)) void k_
 // entry's id and value from one address — a broadcast — and 16 B of the V row each); the body is lean enough for more waves, and
 // what pass B waits for is the chain of dependent loads per row (extent, entry, V row; the row's partial q from P), which more rows in
 // flight hide.  Same arithmetic per entry (acc_entry), same finish (row_finish); the linear term's few addends are summed by one lane.
-template <int LPN, int J, bool PACKED>
+template <int LPN, int J, int MODE, bool PACKED>
 __global__ __launch_bounds__(kBlock) void k_forward_pass_b(FwdArgs a) {
     constexpr int KP = 4 * LPN * J;
     constexpr int SLOTS = kBlock / LPN;
@@ -640,7 +664,7 @@ __global__ __launch_bounds__(kBlock) void k_forward_pass_b(FwdArgs a) {
     const float w0 = *a.w0;
     const int32_t *colb = a.col + a.nz0;
     const float *valb = a.val + a.nz0;
-    float st1 = 0.f, st2 = 0.f, stbad = 0.f;
+    float st1 = 0.f, st2 = 0.f, stbad = 0.f, stl = 0.f;
     for (int ri = blockIdx.x * SLOTS + slot; ri < a.n_rows; ri += gridDim.x * SLOTS) {
         const int r = a.order ? a.order[ri] : ri;
         const uint32_t p0 = (uint32_t)(a.row_split[a.row0 + r] - a.nz0), p1 = (uint32_t)(a.row_ptr[a.row0 + r + 1] - a.nz0);
@@ -659,15 +683,22 @@ __global__ __launch_bounds__(kBlock) void k_forward_pass_b(FwdArgs a) {
             for (int jj = 0; jj < J; ++jj) acc_entry(q[jj], s[jj], vp[jj * LPN], x);
             if (!PACKED && l == 0) lin = fmaf(a.w[c], x, lin);      // (row_finish sums the lanes' linear terms)
         }
-        row_finish<LPN, J, kFwdPartB, PACKED>(a, r, l, q, s, lin, w0, st1, st2, stbad);
+        row_finish<LPN, J, MODE, PACKED>(a, r, l, q, s, lin, w0, st1, st2, stbad, stl);
     }
-    block_stats<kBlock>(a.bsum, st1, st2, stbad);
+    block_stats<kBlock, false>(a.bsum, st1, st2, stbad, stl);
 }
 
 __global__ __launch_bounds__(kBlock) void k_reduce_blocks(const double *bsum, int32_t nblocks, int32_t n_rows, float *scal,
                                                          double *acc) {
     __shared__ double sh[3][kBlock / 64];
     reduce_blocks_body(bsum, nblocks, n_rows, scal, acc, sh);
+}
+
+// the same, with the fourth slot (fmhip_logloss: acc has 5 doubles)
+__global__ __launch_bounds__(kBlock) void k_reduce_blocks_logloss(const double *bsum, int32_t nblocks, int32_t n_rows, float *scal,
+                                                                 double *acc) {
+    __shared__ double sh[4][kBlock / 64];
+    reduce_blocks_body<true>(bsum, nblocks, n_rows, scal, acc, sh);
 }
 
 // dense V *= sv, w *= sw (lazily decayed tables back to scale 1)
@@ -707,10 +738,18 @@ FwdPlan fwd_plan(const FwdArgs &a) {
 
 template <int LPN, int J, int MODE>
 hipError_t fwd_launch(const FwdArgs &a, hipStream_t s, int *n_partials) {
+    // the log-loss scoring pass (fmhip_logloss) is no hot path: the plain kernel only, and no w-tile / V-tile instances of it
+    constexpr bool plain_only = MODE == (kFwdResidual | kFwdLogistic);
+    if (plain_only && a.variant != 0) {
+        FwdArgs b0 = a;
+        b0.variant = 0;
+        return fwd_launch<LPN, J, MODE>(b0, s, n_partials);
+    }
     const FwdPlan pl = fwd_plan<LPN, J>(a);
     if (n_partials) *n_partials = pl.blocks;
     const dim3 g((unsigned)pl.blocks), b(kBlock);
     const bool buf = a.v_bytes != 0;
+    if constexpr (!plain_only) {
     if (pl.var == 60) {
         const size_t lds_bytes = (size_t)a.wt_rows * sizeof(float);
 #define FMHIP_WT(HOT_, BUF_) hipLaunchKernelGGL((k_forward_wt<LPN, J, MODE, HOT_, BUF_>), g, b, lds_bytes, s, a)
@@ -725,6 +764,7 @@ hipError_t fwd_launch(const FwdArgs &a, hipStream_t s, int *n_partials) {
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((k_forward_lds<LPN, J, MODE>), g, dim3(kLdsBlock), lds_bytes, s, a);
         return hipGetLastError();
+    }
     }
 #define FMHIP_FW(PACKED_, HOT_)                                                                   \
     do {                                                                                          \
@@ -749,27 +789,27 @@ hipError_t fwd_launch_pass(const FwdArgs &a0, hipStream_t s, int *n_partials) {
         return hipErrorInvalidValue;
     } else {
         FwdArgs a = a0;
-        const bool hot_here = a.hot_T && (MODE == kFwdPartB) == (a.hot_in_b != 0);      // the pass that runs the prologue
+        const bool hot_here = a.hot_T && (fwd_mode(MODE) == kFwdPartB) == (a.hot_in_b != 0);      // the pass that runs the prologue
         if (!hot_here) a.hot_T = 0;
-        if (MODE == kFwdPartB) a.variant = 0;
+        if (fwd_mode(MODE) == kFwdPartB) a.variant = 0;
         if (a.variant == 20) a.variant = a.hot_T ? 60 : 0;
         const FwdPlan pl = fwd_plan<LPN, J>(a);
         if (n_partials) *n_partials = pl.blocks;
         const dim3 g((unsigned)pl.blocks), b(kBlock);
         const bool buf = a.v_bytes != 0;
-        if constexpr (MODE == kFwdPartB) {
+        if constexpr (fwd_mode(MODE) == kFwdPartB) {
             if (!a.hot_T) {
                 // rows in STORED order: the length-sorted order balances the slots of a wave over rows of 20..60 entries; pass
                 // B's rows hold a handful, and in stored order a wave's eight rows read their extents, partial sums, labels and
                 // P rows from neighbouring addresses and write e and P there (forward 378 -> 373.5 us per step at C4 / 625k rows)
                 a.order = nullptr;
                 // (the generic walk in this mode, A/B on one box: forward 409 -> 401 us per step, step 1.066 -> 1.058 ms)
-                if (a.pack_k >= 0) hipLaunchKernelGGL((k_forward_pass_b<LPN, J, true>), g, b, 0, s, a);
-                else hipLaunchKernelGGL((k_forward_pass_b<LPN, J, false>), g, b, 0, s, a);
+                if (a.pack_k >= 0) hipLaunchKernelGGL((k_forward_pass_b<LPN, J, MODE, true>), g, b, 0, s, a);
+                else hipLaunchKernelGGL((k_forward_pass_b<LPN, J, MODE, false>), g, b, 0, s, a);
                 return hipGetLastError();
             }
         }
-        if constexpr (MODE == kFwdPartA) {
+        if constexpr (fwd_mode(MODE) == kFwdPartA) {
             if (pl.var == 60) {
                 const size_t lds_bytes = (size_t)a.wt_rows * sizeof(float);
                 if (a.hot_T) {
@@ -792,7 +832,7 @@ hipError_t fwd_launch_pass(const FwdArgs &a0, hipStream_t s, int *n_partials) {
             }
             return hipGetLastError();
         }
-        if constexpr (MODE == kFwdPartA) {
+        if constexpr (fwd_mode(MODE) == kFwdPartA) {
             if (a.pack_k >= 0) {
                 if (buf) hipLaunchKernelGGL((k_forward<LPN, J, MODE, true, false, true>), g, b, 0, s, a);
                 else hipLaunchKernelGGL((k_forward<LPN, J, MODE, true, false, false>), g, b, 0, s, a);
@@ -809,10 +849,16 @@ hipError_t fwd_launch_pass(const FwdArgs &a0, hipStream_t s, int *n_partials) {
 template <int LPN, int J>
 hipError_t fwd_dispatch(FwdMode mode, const FwdArgs &a, hipStream_t s, int *n_partials) {
     switch (mode) {
-        case kFwdTrain: return fwd_launch<LPN, J, kFwdTrain>(a, s, n_partials);
-        case kFwdResidual: return fwd_launch<LPN, J, kFwdResidual>(a, s, n_partials);
+        // the loss picks the instance (kFwdLogistic); pass A and the q-mode form no residual
+        case kFwdTrain:
+            return a.loss == kLossLogistic ? fwd_launch<LPN, J, kFwdTrain | kFwdLogistic>(a, s, n_partials) : fwd_launch<LPN, J, kFwdTrain>(a, s, n_partials);
+        case kFwdResidual:
+            return a.loss == kLossLogistic ? fwd_launch<LPN, J, kFwdResidual | kFwdLogistic>(a, s, n_partials)
+                                           : fwd_launch<LPN, J, kFwdResidual>(a, s, n_partials);
         case kFwdPartA: return fwd_launch_pass<LPN, J, kFwdPartA>(a, s, n_partials);
-        case kFwdPartB: return fwd_launch_pass<LPN, J, kFwdPartB>(a, s, n_partials);
+        case kFwdPartB:
+            return a.loss == kLossLogistic ? fwd_launch_pass<LPN, J, kFwdPartB | kFwdLogistic>(a, s, n_partials)
+                                           : fwd_launch_pass<LPN, J, kFwdPartB>(a, s, n_partials);
         default: return fwd_launch<LPN, J, kFwdQ>(a, s, n_partials);
     }
 }
@@ -865,8 +911,9 @@ hipError_t launch_forward(int Kp, FwdMode mode, const FwdArgs &a, hipStream_t s,
 }
 
 hipError_t launch_reduce_blocks(const double *bsum, int32_t nblocks, int32_t n_rows, float *scal, double *acc,
-                                hipStream_t s) {
-    hipLaunchKernelGGL(k_reduce_blocks, dim3(1), dim3(kBlock), 0, s, bsum, nblocks, n_rows, scal, acc);
+                                hipStream_t s, bool with_logloss) {
+    if (with_logloss) hipLaunchKernelGGL(k_reduce_blocks_logloss, dim3(1), dim3(kBlock), 0, s, bsum, nblocks, n_rows, scal, acc);
+    else hipLaunchKernelGGL(k_reduce_blocks, dim3(1), dim3(kBlock), 0, s, bsum, nblocks, n_rows, scal, acc);
     return hipGetLastError();
 }
 

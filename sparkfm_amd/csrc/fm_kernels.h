@@ -43,6 +43,13 @@ int forward_blocks_wt(int Kp, int64_t n_rows, int occ_cap = 0);    // grid of th
 // features' terms once their rows are final and finishes the row).  A leaves the row's raw q in its P row and {sum_f s_f, linear
 // term} in part_sl; B starts from them.  Kp <= 64 only.
 enum FwdMode { kFwdTrain = 0, kFwdResidual = 1, kFwdQ = 2, kFwdPartA = 3, kFwdPartB = 4 };
+// The residual a row finish hands on (== enum fmhip_loss, include/fmhip.h): squared, e = yhat - y; logistic, e = sigma(yhat) - t
+// with t = [y > 0].  Everything after the forward only sees e.
+enum Loss { kLossSquared = 0, kLossLogistic = 1 };
+// The forward kernels take the loss as a flag on their MODE template parameter: kFwdTrain, kFwdResidual and kFwdPartB | kFwdLogistic
+// are the logistic instances (launch_forward picks them from FwdArgs.loss); MODE & kFwdModeMask is the FwdMode.
+constexpr int kFwdLogistic = 8, kFwdModeMask = 7;
+constexpr int fwd_mode(int mode) { return mode & kFwdModeMask; }
 
 struct FwdArgs {
     const int64_t *row_ptr;  // global CSR offsets (device), indexed row0 + r
@@ -63,7 +70,7 @@ struct FwdArgs {
     float *P;     // train: [rows][Kp] = e*q ; q-mode: [rows][Kp] = q
     float *e;     // [rows] e = yhat - y   (residual / train)
     float *yhat;  // optional [rows]
-    double *bsum; // optional [forward_blocks][4] per-block {sum e, sum e^2, nonfinite, 0}
+    double *bsum; // optional [forward_blocks][4] per-block {sum e, sum e^2, nonfinite, log-loss (kFwdResidual under kLossLogistic; else 0)}
     int32_t tile_rows; // LDS V-tile: rows of V (feature ids < tile_rows) staged in LDS; 0 = off
     int32_t wt_rows;   // LDS w-tile: linear weights of feature ids < wt_rows staged in LDS
     int32_t pack_k;    // >= 0: packed rows — slot pack_k of a V row is w_i, of a P row is e (k < Kp); -1: off
@@ -77,6 +84,7 @@ struct FwdArgs {
     // host-side launch choices (the model's tuning keys 0 and 6; the kernels never read them)
     int32_t variant;   // 60 = LDS w-tile kernel, 20 = LDS V-tile kernel, 0 = plain
     int32_t occ_cap;   // cap on the w-tile kernel's resident workgroups per CU (0 = all that fit)
+    int32_t loss;      // Loss: the residual the row finish forms (host side: launch_forward picks the kernel instance by it)
 };
 
 // Fused update (single-GPU step, nothing to exchange): a finished gradient row is applied to its parameter row on
@@ -212,8 +220,9 @@ hipError_t launch_fixup(int Kp, const BwdArgs &a, hipStream_t s);
 hipError_t launch_fixup2(int Kp, const BwdArgs &a, hipStream_t s);   // sums the pieces of multi-piece features
 hipError_t launch_apply(int Kp, const ApplyArgs &a, hipStream_t s);
 hipError_t launch_apply_shard(int Kp, const ApplyArgs &a, hipStream_t s);        // see ApplyArgs::w_lo
-// scal[0..3] = {sum e, sum e^2, n_rows, nonfinite} (optional); acc (optional, 4 doubles) += the same
+// scal[0..3] = {sum e, sum e^2, n_rows, nonfinite} (optional); acc (optional, 4 doubles) += the same;
+// with_logloss: acc holds 5 doubles and acc[4] += the sum of the partials' fourth slot (the log-loss)
 hipError_t launch_reduce_blocks(const double *bsum, int32_t nblocks, int32_t n_rows, float *scal, double *acc,
-                                hipStream_t s);
+                                hipStream_t s, bool with_logloss = false);
 
 }  // namespace fmhip

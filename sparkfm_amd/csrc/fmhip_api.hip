@@ -219,6 +219,17 @@ int fmhip_model_info(fmhip_model_t m, int64_t *num_attribute, int32_t *num_facto
     return FMHIP_OK;
 }
 
+static_assert((int)FMHIP_LOSS_SQUARED == (int)kLossSquared && (int)FMHIP_LOSS_LOGISTIC == (int)kLossLogistic, "fmhip.h and fm_kernels.h disagree on the losses");
+
+int fmhip_model_set_loss(fmhip_model_t m, int loss) {
+    if (loss != FMHIP_LOSS_SQUARED && loss != FMHIP_LOSS_LOGISTIC)
+        return fail(FMHIP_ERR_INVALID, "loss %d: FMHIP_LOSS_SQUARED (0) or FMHIP_LOSS_LOGISTIC (1)", loss);
+    WriteLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    m->loss = loss;
+    return FMHIP_OK;
+}
+
 int fmhip_model_init_normal(fmhip_model_t m, uint64_t seed, double mean, double stdev) {
     WriteLock lock(m);
     if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
@@ -327,8 +338,11 @@ struct ScoreLease {
 }  // namespace
 
 // One pass of FMModel.predict over a dataset's rows.  Re-entrant: the caller holds the model's lock SHARED, every call
-// works on a stream and in buffers of its own (ScoreCtx) and touches nothing of the model but its parameters.
-static int score_pass(fmhip_model_t m, fmhip_dataset_t d, double *yhat, double *e_out, double *q_out, fmhip_stats *st) {
+// works on a stream and in buffers of its own (ScoreCtx) and touches nothing of the model but its parameters.  The scoring
+// calls are the reference's formulas whatever the model's training loss; logloss (fmhip_logloss) scores under the logistic
+// loss instead: st's sums are over e = sigma(yhat) - t and *logloss = the sum of the rows' log-losses.
+static int score_pass(fmhip_model_t m, fmhip_dataset_t d, double *yhat, double *e_out, double *q_out, fmhip_stats *st,
+                      double *logloss = nullptr) {
     TRY(check_pair(m, d));
     ScoreLease lease(m);
     TRY(lease.take());
@@ -336,13 +350,13 @@ static int score_pass(fmhip_model_t m, fmhip_dataset_t d, double *yhat, double *
     const size_t rows_max = (size_t)std::max<int64_t>(d->max_rows, 1);
     TRY(cx.e.ensure(rows_max));
     TRY(cx.bsum.ensure((size_t)kMaxFwdBlocks * 4));
-    TRY(cx.acc.ensure(4));
+    TRY(cx.acc.ensure(5));
     if (yhat) TRY(cx.yhat.ensure(rows_max));
     if (q_out) TRY(cx.P.ensure(rows_max * m->Kp));
     // behind whatever the model's own stream still has queued (a training step returns before it has run)
     HIP_TRY(hipEventRecord(cx.ev, m->stream));
     HIP_TRY(hipStreamWaitEvent(cx.s, cx.ev, 0));
-    HIP_TRY(hipMemsetAsync(cx.acc.p, 0, 4 * sizeof(double), cx.s));
+    HIP_TRY(hipMemsetAsync(cx.acc.p, 0, 5 * sizeof(double), cx.s));
     std::vector<float> hbuf;
     for (size_t b = 0; b < d->batches.size(); ++b) {
         const BatchMeta &bm = d->batches[b];
@@ -351,9 +365,10 @@ static int score_pass(fmhip_model_t m, fmhip_dataset_t d, double *yhat, double *
         a.e = cx.e.p;
         a.bsum = cx.bsum.p;
         a.yhat = yhat ? cx.yhat.p : nullptr;
+        a.loss = logloss ? kLossLogistic : kLossSquared;
         int parts = 0;
         HIP_TRY(launch_forward(m->Kp, q_out ? kFwdQ : kFwdResidual, a, cx.s, &parts));
-        HIP_TRY(launch_reduce_blocks(cx.bsum.p, parts, (int32_t)bm.rows, nullptr, cx.acc.p, cx.s));
+        HIP_TRY(launch_reduce_blocks(cx.bsum.p, parts, (int32_t)bm.rows, nullptr, cx.acc.p, cx.s, logloss != nullptr));
         if (yhat || e_out) {
             hbuf.resize((size_t)bm.rows);
             if (yhat) {
@@ -377,7 +392,7 @@ static int score_pass(fmhip_model_t m, fmhip_dataset_t d, double *yhat, double *
     }
     if (st) {
         memset(st, 0, sizeof *st);
-        double h[4];
+        double h[5];
         HIP_TRY(hipMemcpyAsync(h, cx.acc.p, sizeof h, hipMemcpyDeviceToHost, cx.s));
         HIP_TRY(hipStreamSynchronize(cx.s));
         st->sum_e = h[0];
@@ -385,6 +400,7 @@ static int score_pass(fmhip_model_t m, fmhip_dataset_t d, double *yhat, double *
         st->rows = (int64_t)llround(h[2]);
         st->nonfinite = (int64_t)llround(h[3]);
         st->nnz = d->nnz;
+        if (logloss) *logloss = h[4];
     }
     return FMHIP_OK;
 }
@@ -426,6 +442,18 @@ int fmhip_rmse(fmhip_model_t m, fmhip_dataset_t d, double *rmse, fmhip_stats *st
     TRY(score_pass(m, d, nullptr, nullptr, nullptr, &st));
     // S/Model.scala:13-19: sqrt(sum (y - yhat)^2 / size); (y - yhat)^2 == e^2
     *rmse = st.rows > 0 ? std::sqrt(st.sse / (double)st.rows) : 0.0;
+    if (stats) *stats = st;
+    return FMHIP_OK;
+}
+
+int fmhip_logloss(fmhip_model_t m, fmhip_dataset_t d, double *logloss, fmhip_stats *stats) {
+    ReadLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    if (!logloss) return fail(FMHIP_ERR_INVALID, "logloss is NULL");
+    fmhip_stats st;
+    double sum_l = 0.0;
+    TRY(score_pass(m, d, nullptr, nullptr, nullptr, &st, &sum_l));
+    *logloss = st.rows > 0 ? sum_l / (double)st.rows : 0.0;
     if (stats) *stats = st;
     return FMHIP_OK;
 }
@@ -511,6 +539,9 @@ int fmhip_batch_grad(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, double *
 int fmhip_als_epoch(fmhip_model_t m, fmhip_dataset_t d, double reg0, double regw, double regv) {
     WriteLock lock(m);
     TRY(check_train(m, d));
+    if (m->loss != FMHIP_LOSS_SQUARED)
+        return fail(FMHIP_ERR_UNSUPPORTED, "ALS is derived for the squared loss: this model trains under the logistic loss "
+                                           "(fmhip_model_set_loss)");
     if (d->batches.size() > 1 || (d->nnz > 0 && !d->val64.p))
         return fail(FMHIP_ERR_UNSUPPORTED, "ALS walks the whole-dataset transpose: create the dataset with batch_rows <= 0 "
                                            "(single batch, at most 2^27 stored nonzeros) and without asking for the dense hot "

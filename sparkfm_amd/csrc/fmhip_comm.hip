@@ -298,6 +298,7 @@ struct fmhip_comm {
     // step passes or fails on every rank alike
     int64_t plan_max_rows = -1;
     int64_t plan_steps = 0;                   // ... and the largest batch count: the lock-step steps of an epoch
+    int plan_loss = -1;                       // ... and the models' loss (fmhip_model_set_loss; -1: no plan yet)
 };
 
 namespace {
@@ -940,6 +941,9 @@ int dp_step_sharded(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
 // collective: the caller runs the step with a zero contribution (as a rank that has run out of rows does) and
 // reports the error afterwards.
 int local_checks(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, bool in_schedule = true) {
+    if (c->plan_loss >= 0 && m->loss != c->plan_loss)
+        return fail(FMHIP_ERR_INVALID, "the plan was agreed for loss %d, this model now trains under loss %d (fmhip_model_set_loss): call "
+                                       "fmhip_dp_plan again (every rank)", c->plan_loss, m->loss);
     if (c->exchange == FMHIP_EXCHANGE_TOUCHED && !c->tsteps.empty() && c->msg_kp != m->Kp)
         return fail(FMHIP_ERR_INVALID, "the touched-rows exchange was planned for rows of %d floats, this model has %d: call fmhip_dp_plan "
                                        "with this model (every rank)", c->msg_kp, m->Kp);
@@ -1285,8 +1289,11 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     // What every rank must agree on before a step can be sized (one max-reduce): the largest mini-batch of any rank —
     // its global row count travels as one fp32 sum, exact below 2^24 —, whether some rank's transposes are row-blocked
     // (it cannot cut its backward: then nobody does, same collectives everywhere), the touched-rows table's width, and
-    // whether some rank cannot hold the sharded exchange's equal shares.  All ranks pass or fail together.
-    int64_t agree[5] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size()};
+    // whether some rank cannot hold the sharded exchange's equal shares, and the models' loss (it and its complement: a maximum
+    // of 1 for both = the ranks differ).  All ranks pass or fail together.
+    constexpr int kAgree = 7;
+    static_assert(kAgree <= kMaxCuts + 1, "the plan's agreement vector travels in the communicator's scratch (kMaxCuts + 1 int64)");
+    int64_t agree[kAgree] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size(), m->loss, 1 - m->loss};
     for (const auto &bm : d->batches) {
         agree[0] = std::max<int64_t>(agree[0], bm.rows);
         agree[2] = std::max<int64_t>(agree[2], (int64_t)bm.n_cols + d->hot_pages * kHotT);
@@ -1294,7 +1301,9 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     const int W = c->emu_ranks > 0 ? c->emu_ranks : c->world;
     if (c->exchange == FMHIP_EXCHANGE_SHARDED)
         agree[3] = shard_top(m, W) > m->n1p + (m->grad == m->grad_own.p ? (int64_t)fmhip_model::kSlackRows : 0);
-    TRY(control_i64(m, c, agree, 5, false));
+    TRY(control_i64(m, c, agree, kAgree, false));
+    if (agree[5] && agree[6])
+        return fail(FMHIP_ERR_INVALID, "the ranks' models train under different losses (fmhip_model_set_loss): set the same loss on every rank");
     if ((double)agree[0] * c->world >= 16777216.0)
         return fail(FMHIP_ERR_INVALID, "a global batch of %lld x %d rows exceeds 2^24 (the summed row count travels as one fp32 word): "
                                        "use smaller batches", (long long)agree[0], c->world);
@@ -1303,6 +1312,7 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
                                            "gradient buffer, fmhip_grad_bind, needs n+1 to be a multiple of world)", (long long)m->n1, W);
     c->plan_max_rows = agree[0];
     c->plan_steps = agree[4];
+    c->plan_loss = m->loss;
     const int64_t blocked = agree[1];
     if (c->exchange == FMHIP_EXCHANGE_TOUCHED && blocked)
         return fail(FMHIP_ERR_UNSUPPORTED, "the touched-rows exchange needs transposes without row blocks (some rank's dataset has them)");
@@ -1373,14 +1383,16 @@ static int dp_epoch(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const Sg
         }
         order_hash = (int64_t)(h >> 2);        // (62 bits: its negative exists)
     }
-    int64_t agree[7] = {nb, 0, order ? n_order : -1, order ? -n_order : 1, order_bad, order_hash, -order_hash};
+    constexpr int kAgree = 7;
+    static_assert(kAgree <= kMaxCuts + 1, "the epoch's agreement vector travels in the communicator's scratch (kMaxCuts + 1 int64)");
+    int64_t agree[kAgree] = {nb, 0, order ? n_order : -1, order ? -n_order : 1, order_bad, order_hash, -order_hash};
     for (int64_t j = 0; j < nb && !agree[1]; ++j) agree[1] = local_checks(m, d, j, c, false) != FMHIP_OK;
     if (!agree[1] && c->exchange == FMHIP_EXCHANGE_TOUCHED && !lazy_decay_ok(m, sgd)) {
         agree[1] = 1;
         (void)fail(FMHIP_ERR_UNSUPPORTED, "the touched-rows exchange needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)");
     }
     const std::string why = agree[1] ? fmhip_last_error() : "";
-    TRY(control_i64(m, c, agree, 7, false));
+    TRY(control_i64(m, c, agree, kAgree, false));
     if (agree[1])
         return fail(FMHIP_ERR_INVALID, "%s", why.empty() ? "another rank's dataset does not fit the communicator's plan: call fmhip_dp_plan "
                                                            "with the datasets of this epoch (every rank)" : why.c_str());

@@ -220,6 +220,7 @@ struct fmhip_model {
     // exactly 1 unless rows-only updates with decay are pending.  Tracked in fp64 on the host, so the
     // scale itself accumulates no fp32 rounding from step to step.
     double sv = 1.0, sw = 1.0;
+    int loss = FMHIP_LOSS_SQUARED;   // enum fmhip_loss: the residual every training path forms (fmhip_model_set_loss)
     int64_t bw_next_hi = -1;      // feature-chunked backward: the next interval must end here (-1: none pending)
     bool bw_up = false;           // ... ascending intervals instead (the next one must START here)
     // fp64 master copy of the parameters (reference layout): exact round trip of what the caller set,

@@ -120,6 +120,7 @@ FwdArgs fwd_args(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm) {
     a.xhot = d->hot_T ? d->xhot.p + (size_t)bm.row0 * kHotT : nullptr;
     a.hot_ids = d->d_hot_ids.p;
     a.bsum = m->bsum.p;
+    a.loss = m->loss;
     {
         // LDS V-tile size: as many hot rows as fit 128 KiB (+ their w), capped by the model
         int64_t t = (128 * 1024) / ((int64_t)m->Kp * 4);

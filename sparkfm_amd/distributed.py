@@ -50,6 +50,10 @@ class HipEngine:
         self.row_floats, self.gv_offset = int(rf.value), int(gv.value)
         self.n1 = fm.num_attribute + 1
 
+    def set_loss(self, loss):
+        """enum fmhip_loss: the loss the model's steps train under (fmhip_model_set_loss)."""
+        _ffi.check(self.L.fmhip_model_set_loss(self.fm.handle, loss))
+
     def forward(self, batch):
         _ffi.check(self.L.fmhip_step_forward(self.fm.handle, self.dataset.handle, batch))
 
@@ -119,8 +123,10 @@ class DataParallelSGD(FMLearn):
     """FMLearn whose `learn` runs one data-parallel epoch over this rank's row shard."""
 
     def __init__(self, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, group=None, engine_factory=HipEngine,
-                 always_reduce=False, overlap=True, cuts=None):
+                 always_reduce=False, overlap=True, cuts=None, loss="squared"):
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
+        self.loss = loss                     # "squared" | "logistic" (HipSGD): set through the engine before every step
+        self._loss = _ffi.loss_code(loss)
         self.group = group
         self.engine_factory = engine_factory
         self.always_reduce = always_reduce   # run the collective even in a 1-rank group (self-test)
@@ -178,6 +184,10 @@ class DataParallelSGD(FMLearn):
 
     def step(self, eng, j):
         import torch.distributed as dist
+        if hasattr(eng, "set_loss"):
+            eng.set_loss(self._loss)
+        elif self._loss != _ffi.LOSS_SQUARED:
+            raise ValueError("this engine trains the squared loss only")
         live = j < eng.n_batches
         if not (self._collective() and self.overlap and hasattr(eng, "backward")):
             if live:
@@ -463,9 +473,13 @@ class HipDataParallelSGD(FMLearn):
     (the fastest of the candidates timed against an emulated 8-GPU all-reduce at C4's width);
     () = no overlap: whole backward, one all-reduce."""
 
-    def __init__(self, comm, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, upper_fractions=(0.05, 0.15, 0.3, 0.55), exchange="dense"):
+    def __init__(self, comm, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, upper_fractions=(0.05, 0.15, 0.3, 0.55), exchange="dense",
+                 loss="squared"):
         self.comm = comm
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
+        # "squared" | "logistic" (HipSGD): set on the model before the plan (which agrees it over the ranks) and every step
+        self.loss = loss
+        self._loss = _ffi.loss_code(loss)
         self.upper_fractions = tuple(float(f) for f in upper_fractions)
         # "dense": the whole packed gradient all-reduced in overlapped slices, every rank updates every row; "sharded": the
         # slices reduce-scattered, every rank updates its 1/world share, the updated rows all-gathered; "touched": only the
@@ -484,9 +498,13 @@ class HipDataParallelSGD(FMLearn):
         self.exchange = exchange
         self._planned_for = None
 
+    def _set_loss(self, fm):
+        _ffi.check(_ffi.load().fmhip_model_set_loss(fm.handle, self._loss))
+
     def plan(self, fm, dataset):
-        """Collective: rank 0's data pick the cuts, every rank receives them."""
+        """Collective: rank 0's data pick the cuts, every rank receives them (and agrees the models' loss)."""
         import numpy as np
+        self._set_loss(fm)
         fr = np.ascontiguousarray(sorted(self.upper_fractions), np.float64)
         cuts = np.zeros(max(len(fr), 1), np.int64)
         _ffi.check(_ffi.load().fmhip_dp_plan(fm.handle, dataset.handle, self.comm.handle, len(fr), _ffi.ptr(fr), _ffi.ptr(cuts)))
@@ -508,6 +526,7 @@ class HipDataParallelSGD(FMLearn):
 
     def step(self, fm, dataset, batch):
         """One global step, the next of the schedule; batch < 0: this rank contributes zeros."""
+        self._set_loss(fm)
         if self._planned_for != id(dataset):
             self.plan(fm, dataset)
         _ffi.check(_ffi.load().fmhip_dp_step(fm.handle, dataset.handle, batch, self.comm.handle, self.eta, self.reg0,
@@ -517,6 +536,7 @@ class HipDataParallelSGD(FMLearn):
     def step_at(self, fm, dataset, position):
         """One global step at a position of the lock-step schedule that EVERY rank names alike (this rank's batch
         `position`, or zeros if it has fewer): the call of a permuted epoch."""
+        self._set_loss(fm)
         if self._planned_for != id(dataset):
             self.plan(fm, dataset)
         _ffi.check(_ffi.load().fmhip_dp_step_at(fm.handle, dataset.handle, position, self.comm.handle, self.eta, self.reg0,
@@ -528,6 +548,7 @@ class HipDataParallelSGD(FMLearn):
         fmhip_dp_steps): what the pipelined exchange needs to overlap each step's last slice with the next position's forward —
         in the other modes the same as step_at per position."""
         import numpy as np
+        self._set_loss(fm)
         if self._planned_for != id(dataset):
             self.plan(fm, dataset)
         pos = np.ascontiguousarray(positions, np.int64)
@@ -539,6 +560,7 @@ class HipDataParallelSGD(FMLearn):
         """One data-parallel epoch; `order`: a permutation of range(plan_steps()), the same on every rank
         (e.g. numpy's default_rng(shuffle_seed + epoch).permutation(steps)); None = ascending."""
         import numpy as np
+        self._set_loss(fm)
         if self._planned_for != id(dataset):
             self.plan(fm, dataset)
         st = _ffi.Stats()

@@ -24,10 +24,15 @@ class HipSGD(FMLearn):
         theta <- theta - eta * (sum_{r in batch} e_r h_r(theta) / |batch| + reg * theta)
     with e, h from S/fm/lib/ALS.scala:142-144 and :56-58/:40/:21.  The regularisers are the
     learner's own (the model's regv = 10 default is an ALS ridge term — quirk Q5).
+    `loss`: "squared" (e = yhat - y, regression) or "logistic" (e = sigmoid(yhat) - [y > 0]: a binary
+    classifier of labels {0,1} or {-1,+1}, the gradient of the mean log-loss; fmhip_model_set_loss).
+    `learn` and `step` set it on the model before they train.
     """
 
-    def __init__(self, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, shuffle_seed=None):
+    def __init__(self, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, shuffle_seed=None, loss="squared"):
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
+        self.loss = loss
+        self._loss = _ffi.loss_code(loss)
         self.shuffle_seed = shuffle_seed
         self._epoch = 0
         self.last_stats = None
@@ -47,6 +52,7 @@ class HipSGD(FMLearn):
         L = _ffi.load()
         order = self.batch_order(dataset.n_batches)
         st = _ffi.Stats()
+        _ffi.check(L.fmhip_model_set_loss(fm.handle, self._loss))
         _ffi.check(L.fmhip_sgd_epoch(fm.handle, dataset.handle, self.eta, self.reg0, self.regw, self.regv,
                                      _ffi.ptr(order), C.byref(st)))
         fm._device_updated()
@@ -57,6 +63,7 @@ class HipSGD(FMLearn):
     def step(self, fm, dataset, batch, want_stats=True):
         """A single mini-batch step (fmhip_sgd_step)."""
         st = _ffi.Stats()
+        _ffi.check(_ffi.load().fmhip_model_set_loss(fm.handle, self._loss))
         _ffi.check(_ffi.load().fmhip_sgd_step(fm.handle, dataset.handle, batch, self.eta, self.reg0, self.regw,
                                               self.regv, C.byref(st) if want_stats else None))
         fm._device_updated()

@@ -217,6 +217,14 @@ class FMModel(Model):
         _ffi.check(_ffi.load().fmhip_rmse(self.handle, dataset.handle, C.byref(r), None))
         return r.value
 
+    def computeLogLoss(self, dataset):
+        """Mean log-loss of sigmoid(predict) against the labels t = [y > 0], whatever loss the model was trained
+        under (fmhip_logloss; binary classification — the reference declares Task.Classification and scores it only by
+        sign, S/Model.scala:28-30)."""
+        r = C.c_double()
+        _ffi.check(_ffi.load().fmhip_logloss(self.handle, dataset.handle, C.byref(r), None))
+        return r.value
+
     def residual(self, dataset):
         """ALS.precomputeTermE (S/fm/lib/ALS.scala:142-144): e = predict - target."""
         out = np.empty(dataset.size)
