@@ -45,7 +45,7 @@
  *    (fmhip_model_get_params*, fmhip_model_get_rows, fmhip_model_info) are RE-ENTRANT — each call works on a stream and in
  *    a workspace of its own, so executor threads score through one frozen model side by side (S/Model.scala:14) and each
  *    gets the bits a lone caller would get; every call that changes the model (set_params, init, training, the split and
- *    the data-parallel step, gradient binding, the loss; tuning and profiling in fmhip_experimental.h) takes the lock exclusively and so runs alone, after the
+ *    the data-parallel step, gradient binding, the loss, the optimizer; tuning and profiling in fmhip_experimental.h) takes the lock exclusively and so runs alone, after the
  *    readers before it and before those behind it.  A dataset is immutable once created and may be shared by any number of
  *    threads.  A communicator belongs to the thread that drives its model.  Destroying a
  *    handle while another thread still uses it is the caller's bug.
@@ -128,6 +128,21 @@ int fmhip_synchronize(fmhip_model_t m);
  * fmhip_model_set_params nor fmhip_model_init_normal resets it.  Any other value: FMHIP_ERR_INVALID. */
 enum fmhip_loss { FMHIP_LOSS_SQUARED = 0, FMHIP_LOSS_LOGISTIC = 1 };
 int fmhip_model_set_loss(fmhip_model_t m, int loss);
+/* The update rule the model TRAINS under (the training section below).  SGD: one global step size.  AdaGrad (torch.optim.Adagrad
+ * with lr = eta, weight_decay = reg_theta, initial_accumulator_value = initial_accumulator, eps): every scalar parameter keeps
+ * its own fp32 accumulator n, started at `initial_accumulator`.  The accumulators are one more copy of the model on the device
+ * (8.6 GB at 2^25 features x 64 factors).  A new model is SGD.  Setting ADAGRAD on a model that is not already ADAGRAD with the
+ * same eps and initial_accumulator (bit-equal) folds a pending lazy decay into the tables, allocates the accumulators and fills
+ * them with initial_accumulator; the same settings again are a no-op that keeps the state (learners call this before every
+ * epoch).  Setting SGD frees them.  fmhip_model_set_params, fmhip_model_init_normal and fmhip_als_epoch leave them alone.
+ * Under AdaGrad every training call works as under SGD, except that: the update of the rows a batch touched only (models far
+ * wider than a batch) needs regw = regv = 0, else the whole model is updated each step; FMHIP_EXCHANGE_TOUCHED needs
+ * regw = regv = 0 too (refused on every rank otherwise); FMHIP_EXCHANGE_SHARDED is refused (FMHIP_ERR_UNSUPPORTED, at
+ * fmhip_dp_plan and at any step, on every rank).  fmhip_dp_plan agrees the optimizer, eps and initial_accumulator over the
+ * ranks as it agrees the loss; equal accumulator CONTENTS on every rank are the caller's job, as equal parameters are.
+ * eps not finite or <= 0, initial_accumulator not finite or < 0, an unknown optimizer: FMHIP_ERR_INVALID. */
+enum fmhip_optimizer { FMHIP_OPT_SGD = 0, FMHIP_OPT_ADAGRAD = 1 };
+int fmhip_model_set_optimizer(fmhip_model_t m, int optimizer, double eps, double initial_accumulator);
 
 /* ---- dataset: DataSet(rdd).cache() + transposeInput  S/DataSet.scala:42-62,31-38 */
 /* Copies the rows to the GPU, cuts them into mini-batches of `batch_rows` consecutive
@@ -189,7 +204,9 @@ int fmhip_term_q(fmhip_model_t m, fmhip_dataset_t d, double *q /* n_rows*k */);
 /* ---- training (build-defined mini-batch SGD; SparkFM itself only ships ALS) ---- */
 /*   g_theta = sum_{r in batch} e_r * h_r(theta),  h from S/fm/lib/ALS.scala:56-58 (V), :40 (w), :21 (w0)
  *   theta  <- theta - eta * (g_theta / |batch| + reg_theta * theta)
- * e_r = yhat_r - y_r, or sigma(yhat_r) - [y_r > 0] for a model set to FMHIP_LOSS_LOGISTIC (fmhip_model_set_loss)            */
+ * e_r = yhat_r - y_r, or sigma(yhat_r) - [y_r > 0] for a model set to FMHIP_LOSS_LOGISTIC (fmhip_model_set_loss).
+ * A model set to FMHIP_OPT_ADAGRAD (fmhip_model_set_optimizer) takes per-coordinate steps instead, each theta with its accumulator n:
+ *   g_hat  = g_theta / |batch| + reg_theta * theta,   n <- n + g_hat^2,   theta <- theta - eta * g_hat / (sqrt(n) + eps)      */
 int fmhip_sgd_step(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, double eta, double reg0, double regw,
                    double regv, fmhip_stats *stats /* nullable: skips the host sync */);
 /* one pass over all batches; order[n_batches] = batch visiting order (NULL = ascending) */

@@ -184,6 +184,14 @@ int fmhip_comm_emulate_ranks(fmhip_comm_t c, int ranks);
 int fmhip_comm_profile_begin(fmhip_comm_t c);
 int fmhip_comm_profile_end(fmhip_comm_t c, fmhip_comm_profile *p);
 
+/* ---- AdaGrad state (tests, checkpoint and resume) ------------------------------------------ */
+/* The accumulators of a model set to FMHIP_OPT_ADAGRAD (fmhip_model_set_optimizer) in the host layout of
+ * fmhip_model_get_params: n0 (w0's), nw[n+1], nv[f + i*k], fp64.  Both return FMHIP_ERR_INVALID on an SGD model; the setter
+ * also refuses negative or non-finite values.  A resumed run = fmhip_model_set_params + fmhip_model_set_optimizer (same eps and
+ * initial accumulator) + fmhip_model_set_optimizer_state: the next epoch is bit for bit the one the saved model would have taken. */
+int fmhip_model_get_optimizer_state(fmhip_model_t m, double *n0, double *nw, double *nv);
+int fmhip_model_set_optimizer_state(fmhip_model_t m, double n0, const double *nw, const double *nv);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,18 +172,26 @@ class FMLearn {
 // One learn = one epoch of mini-batch SGD over the dataset's batches (ascending order) — fmhip_sgd_epoch.
 // theta <- theta - eta * (sum_{r in batch} e_r h_r(theta) / |batch| + reg * theta), e and h from S/fm/lib/ALS.scala:142-144, :56-58 / :40 / :21
 // loss = FMHIP_LOSS_LOGISTIC: e = sigmoid(yhat) - [y > 0], a binary classifier (fmhip_model_set_loss)
+// optimizer = FMHIP_OPT_ADAGRAD: per-coordinate steps, g_hat = g/|batch| + reg*theta, n += g_hat^2, theta -= eta*g_hat/(sqrt(n) + adagrad_eps),
+// n started at adagrad_init (fmhip_model_set_optimizer; set before every epoch — the same settings keep the accumulators)
 class HipSGD : public FMLearn {
   public:
     double eta, reg0, regw, regv;
     int loss;
+    int optimizer;
+    double adagrad_eps, adagrad_init;
     fmhip_stats last_stats{};
-    explicit HipSGD(double eta_ = 0.05, double reg0_ = 0.0, double regw_ = 0.0, double regv_ = 0.0, int loss_ = FMHIP_LOSS_SQUARED)
-        : eta(eta_), reg0(reg0_), regw(regw_), regv(regv_), loss(loss_) {}
-    static HipSGD run(double eta = 0.05, double reg0 = 0.0, double regw = 0.0, double regv = 0.0, int loss = FMHIP_LOSS_SQUARED) {
-        return HipSGD(eta, reg0, regw, regv, loss);   // cf. ALS.run(), S/fm/lib/ALS.scala:202-208
+    explicit HipSGD(double eta_ = 0.05, double reg0_ = 0.0, double regw_ = 0.0, double regv_ = 0.0, int loss_ = FMHIP_LOSS_SQUARED,
+                    int optimizer_ = FMHIP_OPT_SGD, double adagrad_eps_ = 1e-10, double adagrad_init_ = 0.1)
+        : eta(eta_), reg0(reg0_), regw(regw_), regv(regv_), loss(loss_), optimizer(optimizer_), adagrad_eps(adagrad_eps_),
+          adagrad_init(adagrad_init_) {}
+    static HipSGD run(double eta = 0.05, double reg0 = 0.0, double regw = 0.0, double regv = 0.0, int loss = FMHIP_LOSS_SQUARED,
+                      int optimizer = FMHIP_OPT_SGD, double adagrad_eps = 1e-10, double adagrad_init = 0.1) {
+        return HipSGD(eta, reg0, regw, regv, loss, optimizer, adagrad_eps, adagrad_init);   // cf. ALS.run(), S/fm/lib/ALS.scala:202-208
     }
     FMModel &learn(FMModel &fm, DataSet &dataset) override {
         check(fmhip_model_set_loss(fm.upload(), loss));
+        check(fmhip_model_set_optimizer(fm.upload(), optimizer, adagrad_eps, adagrad_init));
         check(fmhip_sgd_epoch(fm.upload(), dataset.handle(), eta, reg0, regw, regv, nullptr, &last_stats));
         fm.download();
         return fm;

@@ -18,7 +18,7 @@ SYMBOLS = (
     "fmhip_version", "fmhip_last_error", "fmhip_device_count",
     "fmhip_model_create", "fmhip_model_destroy", "fmhip_model_info", "fmhip_model_init_normal",
     "fmhip_model_set_params", "fmhip_model_get_params", "fmhip_model_get_rows", "fmhip_model_set_params_f32", "fmhip_model_get_params_f32",
-    "fmhip_synchronize", "fmhip_model_set_loss",
+    "fmhip_synchronize", "fmhip_model_set_loss", "fmhip_model_set_optimizer",
     "fmhip_dataset_create", "fmhip_dataset_create_f32", "fmhip_dataset_create_opts", "fmhip_rows_create", "fmhip_rows_create_f32",
     "fmhip_dataset_destroy", "fmhip_dataset_info", "fmhip_dataset_batch_info", "fmhip_dataset_get_transpose",
     "fmhip_predict", "fmhip_predict_rows", "fmhip_rmse", "fmhip_logloss", "fmhip_residual", "fmhip_term_q",
@@ -40,6 +40,7 @@ SYMBOLS_EXPERIMENTAL = (
     "fmhip_dataset_partition_rows", "fmhip_step_forward_pass",
     "fmhip_comm_create_external", "fmhip_stream_wait", "fmhip_device_read", "fmhip_device_write",
     "fmhip_comm_profile_begin", "fmhip_comm_profile_end", "fmhip_comm_emulate", "fmhip_comm_emulate_load", "fmhip_comm_emulate_ranks",
+    "fmhip_model_get_optimizer_state", "fmhip_model_set_optimizer_state",
 )
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
@@ -56,6 +57,29 @@ def loss_code(loss):
     if loss not in LOSSES:
         raise ValueError("loss must be one of %s, not %r" % (sorted(LOSSES), loss))
     return LOSSES[loss]
+
+
+# enum fmhip_optimizer (include/fmhip.h): the update rule a model trains under (fmhip_model_set_optimizer)
+OPT_SGD, OPT_ADAGRAD = 0, 1
+OPTIMIZERS = {"sgd": OPT_SGD, "adagrad": OPT_ADAGRAD}
+
+
+def optimizer_code(optimizer):
+    """'sgd' | 'adagrad' -> enum fmhip_optimizer; anything else raises ValueError."""
+    if optimizer not in OPTIMIZERS:
+        raise ValueError("optimizer must be one of %s, not %r" % (sorted(OPTIMIZERS), optimizer))
+    return OPTIMIZERS[optimizer]
+
+
+def adagrad_settings(eps, init):
+    """(eps, initial accumulator) as floats; ValueError unless eps is finite and > 0 and init finite and >= 0 (as the C ABI)."""
+    import math
+    eps, init = float(eps), float(init)
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ValueError("adagrad_eps must be finite and > 0, not %r" % eps)
+    if not (math.isfinite(init) and init >= 0.0):
+        raise ValueError("adagrad_init must be finite and >= 0, not %r" % init)
+    return eps, init
 
 
 class Stats(C.Structure):
@@ -144,6 +168,9 @@ def load():
     L.fmhip_rmse.argtypes = [vp, vp, P(dbl), P(Stats)]
     L.fmhip_logloss.argtypes = [vp, vp, P(dbl), P(Stats)]
     L.fmhip_model_set_loss.argtypes = [vp, C.c_int]
+    L.fmhip_model_set_optimizer.argtypes = [vp, C.c_int, dbl, dbl]
+    L.fmhip_model_get_optimizer_state.argtypes = [vp, P(dbl), vp, vp]
+    L.fmhip_model_set_optimizer_state.argtypes = [vp, dbl, vp, vp]
     L.fmhip_residual.argtypes = [vp, vp, vp]
     L.fmhip_term_q.argtypes = [vp, vp, vp]
     L.fmhip_sgd_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, P(Stats)]

@@ -7,21 +7,23 @@ namespace {
 
 // (apply_piece / apply_w0 live in fm_device.h: k_fixup's merged finish uses them too)
 
-template <int KP>
+// ADA: the AdaGrad form (fm_device.h), its own instance — the SGD instances carry none of its registers
+template <int KP, bool ADA>
 __global__ __launch_bounds__(kBlock) void k_apply(ApplyArgs a) {
     constexpr int LPR = KP / 4;  // lanes per feature row (<= 64, divides the wave)
     const float invb = apply_invb(a);
     const int64_t total = (a.row_hi - a.row_lo) * LPR;
     for (int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * kBlock)
-        apply_piece<KP, false>(a, a.row_lo + idx / LPR, (int)(idx % LPR), invb);
-    if (a.do_w0) apply_w0(a, invb);
+        apply_piece<KP, false, ADA>(a, a.row_lo + idx / LPR, (int)(idx % LPR), invb);
+    if (a.do_w0) apply_w0<ADA>(a, invb);
 }
 
 // The same update restricted to the rows a batch touched (its distinct features + the dense hot
 // block's); every other row has a zero gradient and its decay rides in the tables' scale (see above).
 // Matters when the model is far wider than a batch (Criteo-like widths: 2^25 rows of V, 8.6 GB,
 // against ~2 M touched).
-template <int KP>
+// (ADA: the accumulator rows are indexed by the feature id i, like the parameter rows; the gradient by gr)
+template <int KP, bool ADA>
 __global__ __launch_bounds__(kBlock) void k_apply_rows(ApplyArgs a) {
     constexpr int LPR = KP / 4;
     const float invb = apply_invb(a);
@@ -29,9 +31,9 @@ __global__ __launch_bounds__(kBlock) void k_apply_rows(ApplyArgs a) {
     for (int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * kBlock) {
         const int64_t j = idx / LPR;
         const int32_t i = j < a.n_feat ? a.feat[j] : a.hot_ids[j - a.n_feat];
-        if (i >= 0) apply_piece<KP, true>(a, i, (int)(idx % LPR), invb, a.g_compact ? j : (int64_t)i);
+        if (i >= 0) apply_piece<KP, true, ADA>(a, i, (int)(idx % LPR), invb, a.g_compact ? j : (int64_t)i);
     }
-    if (a.do_w0) apply_w0(a, invb);
+    if (a.do_w0) apply_w0<ADA>(a, invb);
 }
 
 // Sharded update (fmhip_comm.hip, FMHIP_EXCHANGE_SHARDED): one launch per feature interval [w_lo, z_hi), queued on the
@@ -147,9 +149,13 @@ hipError_t launch_apply(int Kp, const ApplyArgs &a, hipStream_t s) {
     if (blocks > 8192) blocks = 8192;
     if (blocks < 1) blocks = 1;
     dim3 g((unsigned)blocks), b(kBlock);
-#define FMHIP_AP(KP_)                                                    \
-    if (rows_only) hipLaunchKernelGGL((k_apply_rows<KP_>), g, b, 0, s, a); \
-    else hipLaunchKernelGGL((k_apply<KP_>), g, b, 0, s, a)
+    const bool ada = a.NV != nullptr;
+#define FMHIP_AP(KP_)                                                                  \
+    if (ada) {                                                                         \
+        if (rows_only) hipLaunchKernelGGL((k_apply_rows<KP_, true>), g, b, 0, s, a);   \
+        else hipLaunchKernelGGL((k_apply<KP_, true>), g, b, 0, s, a);                  \
+    } else if (rows_only) hipLaunchKernelGGL((k_apply_rows<KP_, false>), g, b, 0, s, a); \
+    else hipLaunchKernelGGL((k_apply<KP_, false>), g, b, 0, s, a)
     switch (Kp) {
         case 32: FMHIP_AP(32); break;
         case 64: FMHIP_AP(64); break;

@@ -215,16 +215,60 @@ __device__ __forceinline__ uint32_t slot_bcast(uint32_t v, int src) { return (ui
 // (row_finish) and the next dense pass (below) folds it back in.  With no decay and sv = 1 both passes
 // perform the same operations on the same values (bit-identical; tested).
 //
-// one float4 of one feature row; ROWS = the rows-only (lazy) form
+// AdaGrad (ADA; torch.optim.Adagrad with lr = eta, weight_decay = reg): per scalar parameter theta with its accumulator n,
+//     g_hat = g/|B| + reg*theta  (the SGD form's fmaf),   n <- n + g_hat^2,   theta <- theta - eta*g_hat / (sqrt(n) + eps)
+// correctly rounded sqrtf and IEEE division; one writer per element, fixed order.  The tables are at scale 1 (no lazy
+// decay under AdaGrad), so the rows-only form is the dense one restricted to the listed rows — exact when reg = 0, where an
+// untouched row has g_hat = 0 and neither its accumulator nor its value moves (the host only takes it then).
+__device__ __forceinline__ void adagrad_step(float &th, float &n, float gh, float eta, float eps) {
+    n = fmaf(gh, gh, n);
+    th = th - eta * gh / (sqrtf(n) + eps);
+}
+
+// one float4 of one feature row; ROWS = the rows-only (lazy) form; ADA = the AdaGrad form
 // gr: the row of the gradient arrays that belongs to parameter row i (the packed gradient: gr == i; the compact
 // gradient of the touched-rows exchange: the position of feature i in the step's union)
-template <int KP, bool ROWS>
+template <int KP, bool ROWS, bool ADA = false>
 __device__ __forceinline__ void apply_piece(const ApplyArgs &a, int64_t i, int c, float invb, int64_t gr) {
     constexpr int LPR = KP / 4;
     float4 *V4 = reinterpret_cast<float4 *>(a.V) + i * LPR + c;
     float4 *G4 = reinterpret_cast<float4 *>(a.GV) + gr * LPR + c;
     const float b = a.Gb[gr];
     float4 g = *G4, u = *V4;
+    if constexpr (ADA) {
+        float4 *N4 = reinterpret_cast<float4 *>(a.NV) + i * LPR + c;   // same lanes, same float4 as the V row
+        float4 n = *N4;
+        const bool has_w = a.pack_k >= 0 && c == (a.pack_k >> 2);
+        float wt = 0.f, wn = 0.f, wg = 0.f;
+        if (has_w) {   // packed rows: component pack_k & 3 is the linear weight and its accumulator
+            wt = f4pick(u, a.pack_k & 3);
+            wn = f4pick(n, a.pack_k & 3);
+            wg = fmaf(a.regw, wt, f4pick(g, a.pack_k & 3) * invb);
+        }
+        adagrad_step(u.x, n.x, fmaf(a.regv, u.x, (g.x - u.x * b) * invb), a.eta, a.eps);
+        adagrad_step(u.y, n.y, fmaf(a.regv, u.y, (g.y - u.y * b) * invb), a.eta, a.eps);
+        adagrad_step(u.z, n.z, fmaf(a.regv, u.z, (g.z - u.z * b) * invb), a.eta, a.eps);
+        adagrad_step(u.w, n.w, fmaf(a.regv, u.w, (g.w - u.w * b) * invb), a.eta, a.eps);
+        if (has_w) {
+            adagrad_step(wt, wn, wg, a.eta, a.eps);
+            f4set(u, a.pack_k & 3, wt);
+            f4set(n, a.pack_k & 3, wn);
+        }
+        *V4 = u;
+        *N4 = n;
+        *G4 = f4zero();
+        if (c == 0) {
+            if (a.pack_k < 0) {   // (packed rows: the w table is not read, as under the fused update)
+                float wi = a.w[i], ni = a.Nw[i];
+                adagrad_step(wi, ni, fmaf(a.regw, wi, a.Gw[gr] * invb), a.eta, a.eps);
+                a.w[i] = wi;
+                a.Nw[i] = ni;
+            }
+            a.Gw[gr] = 0.f;
+            a.Gb[gr] = 0.f;
+        }
+        return;
+    }
     float4 v = f4mul(u, a.sv_in);                      // the parameter values (x 1 is exact)
     float wslot = 0.f;
     const bool has_w = a.pack_k >= 0 && c == (a.pack_k >> 2);
@@ -255,9 +299,9 @@ __device__ __forceinline__ void apply_piece(const ApplyArgs &a, int64_t i, int c
         a.Gb[gr] = 0.f;  // same wave already holds its copy of b (all lanes of a row share a wave)
     }
 }
-template <int KP, bool ROWS>
+template <int KP, bool ROWS, bool ADA = false>
 __device__ __forceinline__ void apply_piece(const ApplyArgs &a, int64_t i, int c, float invb) {
-    apply_piece<KP, ROWS>(a, i, c, invb, i);
+    apply_piece<KP, ROWS, ADA>(a, i, c, invb, i);
 }
 
 // 1/|B|: from the step's row count on the device, or given by the host
@@ -267,10 +311,18 @@ __device__ __forceinline__ float apply_invb(const ApplyArgs &a) {
     return rows > 0.f ? 1.0f / rows : 0.f;
 }
 
+template <bool ADA = false>
 __device__ __forceinline__ void apply_w0(const ApplyArgs &a, float invb) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const float w0 = *a.w0;
-        *a.w0 = w0 - a.eta * fmaf(a.reg0, w0, a.scal[0] * invb);
+        if constexpr (ADA) {
+            float t = w0, n = *a.N0;
+            adagrad_step(t, n, fmaf(a.reg0, w0, a.scal[0] * invb), a.eta, a.eps);
+            *a.w0 = t;
+            *a.N0 = n;
+        } else {
+            *a.w0 = w0 - a.eta * fmaf(a.reg0, w0, a.scal[0] * invb);
+        }
     }
 }
 

@@ -137,6 +137,11 @@ struct ApplyArgs {
     // k_apply_shard (sharded update of one feature interval): V rows [row_lo, row_hi) = this rank's share are updated,
     // the linear weights of [w_lo, w_hi) = the whole interval are stepped, the G_V rows of [w_lo, z_hi) outside the share zeroed
     int64_t w_lo, w_hi, z_hi;
+    // AdaGrad (NV != NULL: launch_apply picks the AdaGrad instances): the per-coordinate accumulators, shaped like the
+    // parameters — NV like V (packed rows: slot pack_k holds w_i's), Nw like w (unpacked rows only), N0 like w0.  The tables
+    // are at scale 1 under AdaGrad (sv_in = sw_in = 1; the host asserts it)
+    float *NV, *Nw, *N0;
+    float eps;
 };
 
 struct BwdArgs {

@@ -230,6 +230,92 @@ int fmhip_model_set_loss(fmhip_model_t m, int loss) {
     return FMHIP_OK;
 }
 
+static bool same_bits(double a, double b) { return memcmp(&a, &b, sizeof a) == 0; }
+
+int fmhip_model_set_optimizer(fmhip_model_t m, int optimizer, double eps, double initial_accumulator) {
+    if (optimizer != FMHIP_OPT_SGD && optimizer != FMHIP_OPT_ADAGRAD)
+        return fail(FMHIP_ERR_INVALID, "optimizer %d: FMHIP_OPT_SGD (0) or FMHIP_OPT_ADAGRAD (1)", optimizer);
+    if (optimizer == FMHIP_OPT_ADAGRAD && !(std::isfinite(eps) && eps > 0.0))
+        return fail(FMHIP_ERR_INVALID, "AdaGrad eps must be finite and > 0 (got %g)", eps);
+    if (optimizer == FMHIP_OPT_ADAGRAD && !(std::isfinite(initial_accumulator) && initial_accumulator >= 0.0))
+        return fail(FMHIP_ERR_INVALID, "AdaGrad initial_accumulator must be finite and >= 0 (got %g)", initial_accumulator);
+    WriteLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    TRY(set_device(m->device));
+    if (optimizer == FMHIP_OPT_SGD) {
+        if (m->opt != FMHIP_OPT_SGD) HIP_TRY(hipStreamSynchronize(m->stream));    // no queued update may still use them
+        m->NV.release();
+        m->Nw.release();
+        m->N0.release();
+        m->opt = FMHIP_OPT_SGD;
+        m->ada_eps = m->ada_init = 0.0;
+        return FMHIP_OK;
+    }
+    if (m->opt == FMHIP_OPT_ADAGRAD && same_bits(m->ada_eps, eps) && same_bits(m->ada_init, initial_accumulator)) return FMHIP_OK;
+    TRY(fold_scales(m));          // the AdaGrad kernels work on tables at scale 1
+    m->opt = FMHIP_OPT_SGD;       // (until the accumulators are in place)
+    TRY(m->NV.ensure((size_t)m->n1p * m->Kp));
+    if (m->pack_k() < 0) TRY(m->Nw.ensure((size_t)m->n1p));
+    TRY(m->N0.ensure(1));
+    const float init = (float)initial_accumulator;
+    uint32_t bits;
+    memcpy(&bits, &init, sizeof bits);
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->NV.p), (int)bits, m->NV.n, m->stream));
+    if (m->Nw.p) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->Nw.p), (int)bits, m->Nw.n, m->stream));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->N0.p), (int)bits, 1, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    m->opt = FMHIP_OPT_ADAGRAD;
+    m->ada_eps = eps;
+    m->ada_init = initial_accumulator;
+    return FMHIP_OK;
+}
+
+int fmhip_model_get_optimizer_state(fmhip_model_t m, double *n0, double *nw, double *nv) {
+    ReadLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    if (m->opt != FMHIP_OPT_ADAGRAD) return fail(FMHIP_ERR_INVALID, "the model has no optimizer state (fmhip_model_set_optimizer: FMHIP_OPT_ADAGRAD)");
+    TRY(set_device(m->device));
+    std::vector<float> hN((size_t)m->n1p * m->Kp), hw(m->Nw.p ? (size_t)m->n1p : 0);
+    float h0 = 0.f;
+    HIP_TRY(hipMemcpyAsync(hN.data(), m->NV.p, hN.size() * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+    if (m->Nw.p) HIP_TRY(hipMemcpyAsync(hw.data(), m->Nw.p, hw.size() * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipMemcpyAsync(&h0, m->N0.p, sizeof(float), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (n0) *n0 = h0;
+    for (int64_t i = 0; i < m->n1; ++i) {   // packed rows: w_i's accumulator rides in slot k, as w_i does
+        if (nw) nw[i] = m->pack_k() >= 0 ? hN[(size_t)i * m->Kp + m->k] : hw[(size_t)i];
+        if (nv)
+            for (int f = 0; f < m->k; ++f) nv[f + i * (int64_t)m->k] = hN[(size_t)i * m->Kp + f];
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_model_set_optimizer_state(fmhip_model_t m, double n0, const double *nw, const double *nv) {
+    WriteLock lock(m);
+    if (!m || !nw || !nv) return fail(FMHIP_ERR_INVALID, "NULL argument");
+    if (m->opt != FMHIP_OPT_ADAGRAD) return fail(FMHIP_ERR_INVALID, "the model has no optimizer state (fmhip_model_set_optimizer: FMHIP_OPT_ADAGRAD)");
+    auto ok = [](double x) { return std::isfinite(x) && x >= 0.0; };
+    if (!ok(n0)) return fail(FMHIP_ERR_INVALID, "accumulator of w0 is negative or not finite");
+    for (int64_t i = 0; i < m->n1; ++i)
+        if (!ok(nw[i])) return fail(FMHIP_ERR_INVALID, "accumulator nw[%lld] is negative or not finite", (long long)i);
+    for (int64_t j = 0; j < m->n1 * m->k; ++j)
+        if (!ok(nv[j])) return fail(FMHIP_ERR_INVALID, "accumulator nv[%lld] is negative or not finite", (long long)j);
+    TRY(set_device(m->device));
+    const float init = (float)m->ada_init;     // padding: what set_optimizer filled in
+    std::vector<float> hN((size_t)m->n1p * m->Kp, init), hw(m->Nw.p ? (size_t)m->n1p : 0, init);
+    for (int64_t i = 0; i < m->n1; ++i) {
+        for (int f = 0; f < m->k; ++f) hN[(size_t)i * m->Kp + f] = (float)nv[f + i * (int64_t)m->k];
+        if (m->pack_k() >= 0) hN[(size_t)i * m->Kp + m->k] = (float)nw[i];
+        else hw[(size_t)i] = (float)nw[i];
+    }
+    const float h0 = (float)n0;
+    HIP_TRY(hipMemcpyAsync(m->NV.p, hN.data(), hN.size() * sizeof(float), hipMemcpyHostToDevice, m->stream));
+    if (m->Nw.p) HIP_TRY(hipMemcpyAsync(m->Nw.p, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipMemcpyAsync(m->N0.p, &h0, sizeof(float), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return FMHIP_OK;
+}
+
 int fmhip_model_init_normal(fmhip_model_t m, uint64_t seed, double mean, double stdev) {
     WriteLock lock(m);
     if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");

@@ -299,6 +299,8 @@ struct fmhip_comm {
     int64_t plan_max_rows = -1;
     int64_t plan_steps = 0;                   // ... and the largest batch count: the lock-step steps of an epoch
     int plan_loss = -1;                       // ... and the models' loss (fmhip_model_set_loss; -1: no plan yet)
+    int plan_opt = -1;                        // ... and their optimizer with its settings (fmhip_model_set_optimizer; -1: no plan yet)
+    double plan_eps = 0.0, plan_init = 0.0;
 };
 
 namespace {
@@ -522,6 +524,16 @@ int control_i64(fmhip_model_t m, fmhip_comm_t c, int64_t *value, int count, bool
     return FMHIP_OK;
 }
 
+// The optimizer a step's collective-shaping checks go by: the one fmhip_dp_plan agreed over the ranks (a model changed since is
+// refused by local_checks and contributes zeros, but takes the same collectives as its peers), else the model's own
+int planned_opt(fmhip_model_t m, fmhip_comm_t c) { return c->plan_opt >= 0 ? c->plan_opt : m->opt; }
+
+const char *touched_decay_msg(int opt) {
+    return opt == FMHIP_OPT_ADAGRAD
+               ? "the touched-rows exchange under AdaGrad needs regw = regv = 0 (with decay every row moves: use the dense or pipelined exchange)"
+               : "the touched-rows exchange needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)";
+}
+
 // The plan of the touched-rows exchange (collective): for every position t < steps of the lock-step schedule, the union of the
 // rows the ranks' batches t touch, where this rank's columns lie in it, and where the plan's cuts fall in it.  Plan-time
 // work: one all-gather, one sort and one small read-back per position — what every STEP used to pay.
@@ -655,9 +667,9 @@ int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
         return fail(FMHIP_ERR_INVALID, "the touched-rows exchange is not planned: call fmhip_dp_plan (every rank)");
     const bool foreign = c->msg_kp != m->Kp;
     if (foreign && live) return fail(FMHIP_ERR_INVALID, "the touched-rows exchange was planned for rows of %d floats, this model has %d", c->msg_kp, m->Kp);
-    if (!lazy_decay_ok(m, sgd))
-        return fail(FMHIP_ERR_UNSUPPORTED, "the touched-rows exchange needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)");
-    const bool packed_dirty = m->grad_dirty;      // this step neither writes nor cleans the model's packed gradient
+    if (!lazy_decay_ok(m, sgd, planned_opt(m, c)))
+        return fail(FMHIP_ERR_UNSUPPORTED, "%s", touched_decay_msg(planned_opt(m, c)));
+    const bool packed_dirty = m->grad_dirty;     // this step neither writes nor cleans the model's packed gradient
     const int64_t t = position >= 0 ? position : c->t_cursor;
     if (t >= (int64_t)c->tsteps.size())
         return fail(FMHIP_ERR_INVALID, "position %lld outside the planned schedule of %zu steps", (long long)t, c->tsteps.size());
@@ -871,6 +883,10 @@ inline int64_t shard_top(fmhip_model_t m, int W) { return fmhip::host::shard_top
 // rows of V and all of the interval's w, zeroes the other shares' gradient rows -> all-gather of the updated rows in
 // place into V.  One writer per V row: the replicas are identical whatever order the transport sums in.
 int dp_step_sharded(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, const Sgd &sgd) {
+    // (the plan's optimizer, agreed by every rank — a rank whose model changed since must not be the only one to stop)
+    if (planned_opt(m, c) == FMHIP_OPT_ADAGRAD)
+        return fail(FMHIP_ERR_UNSUPPORTED, "the sharded exchange does not support AdaGrad (each rank's accumulators would hold its own share "
+                                           "only): use the dense, pipelined or touched exchange");
     const bool live = batch >= 0;
     const int W = c->emu_ranks > 0 ? c->emu_ranks : c->world;        // shares per interval
     const int R = c->emu_ranks > 0 ? 0 : c->rank;                    // ... and which one is this rank's
@@ -944,6 +960,11 @@ int local_checks(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t
     if (c->plan_loss >= 0 && m->loss != c->plan_loss)
         return fail(FMHIP_ERR_INVALID, "the plan was agreed for loss %d, this model now trains under loss %d (fmhip_model_set_loss): call "
                                        "fmhip_dp_plan again (every rank)", c->plan_loss, m->loss);
+    if (c->plan_opt >= 0 && (m->opt != c->plan_opt || memcmp(&m->ada_eps, &c->plan_eps, sizeof(double)) != 0 ||
+                             memcmp(&m->ada_init, &c->plan_init, sizeof(double)) != 0))
+        return fail(FMHIP_ERR_INVALID, "the plan was agreed for optimizer %d (eps %g, initial accumulator %g), this model now trains under "
+                                       "optimizer %d (eps %g, initial accumulator %g) (fmhip_model_set_optimizer): call fmhip_dp_plan again "
+                                       "(every rank)", c->plan_opt, c->plan_eps, c->plan_init, m->opt, m->ada_eps, m->ada_init);
     if (c->exchange == FMHIP_EXCHANGE_TOUCHED && !c->tsteps.empty() && c->msg_kp != m->Kp)
         return fail(FMHIP_ERR_INVALID, "the touched-rows exchange was planned for rows of %d floats, this model has %d: call fmhip_dp_plan "
                                        "with this model (every rank)", c->msg_kp, m->Kp);
@@ -1291,9 +1312,11 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     // (it cannot cut its backward: then nobody does, same collectives everywhere), the touched-rows table's width, and
     // whether some rank cannot hold the sharded exchange's equal shares, and the models' loss (it and its complement: a maximum
     // of 1 for both = the ranks differ).  All ranks pass or fail together.
-    constexpr int kAgree = 7;
+    // The last slot: whether some rank's model is not plain SGD — then (and only then: an SGD plan issues the collectives it
+    // always did) a second max-reduce agrees the optimizer and the bit patterns of its settings.
+    constexpr int kAgree = 8;
     static_assert(kAgree <= kMaxCuts + 1, "the plan's agreement vector travels in the communicator's scratch (kMaxCuts + 1 int64)");
-    int64_t agree[kAgree] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size(), m->loss, 1 - m->loss};
+    int64_t agree[kAgree] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size(), m->loss, 1 - m->loss, m->opt != FMHIP_OPT_SGD};
     for (const auto &bm : d->batches) {
         agree[0] = std::max<int64_t>(agree[0], bm.rows);
         agree[2] = std::max<int64_t>(agree[2], (int64_t)bm.n_cols + d->hot_pages * kHotT);
@@ -1302,6 +1325,22 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     if (c->exchange == FMHIP_EXCHANGE_SHARDED)
         agree[3] = shard_top(m, W) > m->n1p + (m->grad == m->grad_own.p ? (int64_t)fmhip_model::kSlackRows : 0);
     TRY(control_i64(m, c, agree, kAgree, false));
+    if (agree[7]) {
+        // each value and its negation (settings >= 0: their bit patterns are non-negative int64): equal on every rank iff max == -max(-x)
+        int64_t eb, ib;
+        memcpy(&eb, &m->ada_eps, sizeof eb);
+        memcpy(&ib, &m->ada_init, sizeof ib);
+        constexpr int kOpt = 7;
+        static_assert(kOpt <= kMaxCuts + 1, "the optimizer's agreement vector travels in the communicator's scratch (kMaxCuts + 1 int64)");
+        int64_t o[kOpt] = {m->opt, -m->opt, eb, -eb, ib, -ib, c->exchange == FMHIP_EXCHANGE_SHARDED && m->opt == FMHIP_OPT_ADAGRAD};
+        TRY(control_i64(m, c, o, kOpt, false));
+        if (o[0] != -o[1] || o[2] != -o[3] || o[4] != -o[5])
+            return fail(FMHIP_ERR_INVALID, "the ranks' models train under different optimizers or optimizer settings (fmhip_model_set_optimizer): "
+                                           "set the same optimizer, eps and initial accumulator on every rank");
+        if (o[6])
+            return fail(FMHIP_ERR_UNSUPPORTED, "the sharded exchange does not support AdaGrad (each rank's accumulators would hold its own share "
+                                               "only): use the dense, pipelined or touched exchange");
+    }
     if (agree[5] && agree[6])
         return fail(FMHIP_ERR_INVALID, "the ranks' models train under different losses (fmhip_model_set_loss): set the same loss on every rank");
     if ((double)agree[0] * c->world >= 16777216.0)
@@ -1313,6 +1352,9 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     c->plan_max_rows = agree[0];
     c->plan_steps = agree[4];
     c->plan_loss = m->loss;
+    c->plan_opt = m->opt;
+    c->plan_eps = m->ada_eps;
+    c->plan_init = m->ada_init;
     const int64_t blocked = agree[1];
     if (c->exchange == FMHIP_EXCHANGE_TOUCHED && blocked)
         return fail(FMHIP_ERR_UNSUPPORTED, "the touched-rows exchange needs transposes without row blocks (some rank's dataset has them)");
@@ -1387,9 +1429,13 @@ static int dp_epoch(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const Sg
     static_assert(kAgree <= kMaxCuts + 1, "the epoch's agreement vector travels in the communicator's scratch (kMaxCuts + 1 int64)");
     int64_t agree[kAgree] = {nb, 0, order ? n_order : -1, order ? -n_order : 1, order_bad, order_hash, -order_hash};
     for (int64_t j = 0; j < nb && !agree[1]; ++j) agree[1] = local_checks(m, d, j, c, false) != FMHIP_OK;
-    if (!agree[1] && c->exchange == FMHIP_EXCHANGE_TOUCHED && !lazy_decay_ok(m, sgd)) {
+    if (!agree[1] && c->exchange == FMHIP_EXCHANGE_TOUCHED && !lazy_decay_ok(m, sgd, planned_opt(m, c))) {
         agree[1] = 1;
-        (void)fail(FMHIP_ERR_UNSUPPORTED, "the touched-rows exchange needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)");
+        (void)fail(FMHIP_ERR_UNSUPPORTED, "%s", touched_decay_msg(planned_opt(m, c)));
+    }
+    if (!agree[1] && c->exchange == FMHIP_EXCHANGE_SHARDED && planned_opt(m, c) == FMHIP_OPT_ADAGRAD) {
+        agree[1] = 1;
+        (void)fail(FMHIP_ERR_UNSUPPORTED, "the sharded exchange does not support AdaGrad: use the dense, pipelined or touched exchange");
     }
     const std::string why = agree[1] ? fmhip_last_error() : "";
     TRY(control_i64(m, c, agree, kAgree, false));

@@ -221,6 +221,12 @@ struct fmhip_model {
     // scale itself accumulates no fp32 rounding from step to step.
     double sv = 1.0, sw = 1.0;
     int loss = FMHIP_LOSS_SQUARED;   // enum fmhip_loss: the residual every training path forms (fmhip_model_set_loss)
+    // enum fmhip_optimizer (fmhip_model_set_optimizer).  AdaGrad: per-coordinate accumulators shaped like the parameters —
+    // NV [n1p][Kp] like V (packed rows: slot pack_k holds w_i's), Nw [n1p] (unpacked rows only), N0 [1] — one more copy of
+    // the model (8.6 GB at 2^25 x 64); the tables stay at scale 1 (sv = sw = 1) while it is set
+    int opt = FMHIP_OPT_SGD;
+    double ada_eps = 0.0, ada_init = 0.0;
+    DevBuf<float> NV, Nw, N0;
     int64_t bw_next_hi = -1;      // feature-chunked backward: the next interval must end here (-1: none pending)
     bool bw_up = false;           // ... ascending intervals instead (the next one must START here)
     // fp64 master copy of the parameters (reference layout): exact round trip of what the caller set,
@@ -319,7 +325,9 @@ int step_apply_shard(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, int6
 // feature interval as soon as its slice has arrived; the step's bookkeeping (w0, the tables' scale) moves with the LAST slice
 int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t n_feat, const float *rows, const GradView *view = nullptr,
                     int64_t off = 0, bool last = true);
-bool lazy_decay_ok(fmhip_model_t m, const Sgd &s);
+// can the update of this step leave rows without a gradient alone (weight decay rides in the tables' scale, or there is
+// none)?  Under AdaGrad only without decay (`opt`: the optimizer to judge by; -1 = the model's own)
+bool lazy_decay_ok(fmhip_model_t m, const Sgd &s, int opt = -1);
 int read_scal(fmhip_model_t m, fmhip_stats *st);
 
 }  // namespace host

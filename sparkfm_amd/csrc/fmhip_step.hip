@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -199,6 +200,14 @@ static ApplyArgs apply_args(fmhip_model_t m, const Sgd &s, const float *rows) {
     a.eta_v = a.eta_w = a.eta;
     a.sv_in = (float)m->sv;
     a.sw_in = (float)m->sw;
+    if (m->opt == FMHIP_OPT_ADAGRAD) {
+        // set_optimizer folded the scale and AdaGrad never takes the lazy-decay path: the AdaGrad kernels assume scale 1
+        assert(m->sv == 1.0 && m->sw == 1.0);
+        a.NV = m->NV.p;
+        a.Nw = m->Nw.p;
+        a.N0 = m->N0.p;
+        a.eps = (float)m->ada_eps;
+    }
     return a;
 }
 
@@ -414,8 +423,10 @@ int step_compute(fmhip_model_t m, fmhip_dataset_t d, int64_t b, double *acc, con
 }
 
 // can weight decay ride in the tables' scale for this step?  (no decay at all: trivially)
-bool lazy_decay_ok(fmhip_model_t m, const Sgd &s) {
+// AdaGrad: only then — with decay every row moves (its accumulator too), which no scale can express: the dense pass
+bool lazy_decay_ok(fmhip_model_t m, const Sgd &s, int opt) {
     if (s.regw == 0.0 && s.regv == 0.0) return true;
+    if ((opt < 0 ? m->opt : opt) == FMHIP_OPT_ADAGRAD) return false;
     const double dv = s.dv(), dw = s.dw();
     return m->tv(kTuneLazy) && dv >= 0.5 && dw >= 0.5 && dv <= 1.0 && dw <= 1.0;
 }
@@ -428,7 +439,9 @@ static bool few_rows(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm) {
 
 // Can this step apply its gradient rows inside the backward (no exchange, no separate update launch)?  It is the
 // rows-only update, so weight decay must be expressible through the tables' scale (lazy decay, fm_apply.hip).
+// Both forms are SGD's: under AdaGrad the update is a launch of its own (k_apply / k_apply_rows).
 bool plan_fused(fmhip_model_t m, fmhip_dataset_t d, int64_t b, const Sgd &s, FusedPlan *p) {
+    if (m->opt != FMHIP_OPT_SGD) return false;
     const bool lazy_ok = lazy_decay_ok(m, s);
     const BatchMeta &bm0 = d->batches[(size_t)b];
     p->sgd = s;
@@ -546,10 +559,13 @@ int step_apply_shard(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, int6
 
 int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t n_feat, const float *rows, const GradView *view, int64_t off,
                     bool last) {
-    if (!lazy_decay_ok(m, s))
+    // (judged as SGD: the touched-rows exchange refuses AdaGrad with decay up front, by the plan's optimizer, on every rank alike —
+    // a rank whose optimizer changed since the plan must not stop halfway through the step's collectives)
+    if (!lazy_decay_ok(m, s, FMHIP_OPT_SGD))
         return fail(FMHIP_ERR_UNSUPPORTED, "a rows-only update needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)");
     // every slice of a step starts from the scale the step began with (m->sv / m->sw move with the LAST slice only)
-    const double sv_out = m->sv * s.dv(), sw_out = m->sw * s.dw();
+    const bool ada = m->opt == FMHIP_OPT_ADAGRAD;      // (its tables stay at scale 1)
+    const double sv_out = ada ? 1.0 : m->sv * s.dv(), sw_out = ada ? 1.0 : m->sw * s.dw();
     ApplyArgs a = apply_args(m, s, rows);
     a.rows_only = 1;
     a.feat = feat + off;

@@ -54,6 +54,10 @@ class HipEngine:
         """enum fmhip_loss: the loss the model's steps train under (fmhip_model_set_loss)."""
         _ffi.check(self.L.fmhip_model_set_loss(self.fm.handle, loss))
 
+    def set_optimizer(self, optimizer, eps, init):
+        """enum fmhip_optimizer and its settings: the update rule of the model's steps (fmhip_model_set_optimizer)."""
+        _ffi.check(self.L.fmhip_model_set_optimizer(self.fm.handle, optimizer, eps, init))
+
     def forward(self, batch):
         _ffi.check(self.L.fmhip_step_forward(self.fm.handle, self.dataset.handle, batch))
 
@@ -123,10 +127,13 @@ class DataParallelSGD(FMLearn):
     """FMLearn whose `learn` runs one data-parallel epoch over this rank's row shard."""
 
     def __init__(self, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, group=None, engine_factory=HipEngine,
-                 always_reduce=False, overlap=True, cuts=None, loss="squared"):
+                 always_reduce=False, overlap=True, cuts=None, loss="squared", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1):
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
         self.loss = loss                     # "squared" | "logistic" (HipSGD): set through the engine before every step
         self._loss = _ffi.loss_code(loss)
+        self.optimizer = optimizer           # "sgd" | "adagrad" (HipSGD): likewise; every rank's accumulators see the same summed gradient
+        self._opt = _ffi.optimizer_code(optimizer)
+        self.adagrad_eps, self.adagrad_init = _ffi.adagrad_settings(adagrad_eps, adagrad_init)
         self.group = group
         self.engine_factory = engine_factory
         self.always_reduce = always_reduce   # run the collective even in a 1-rank group (self-test)
@@ -188,6 +195,10 @@ class DataParallelSGD(FMLearn):
             eng.set_loss(self._loss)
         elif self._loss != _ffi.LOSS_SQUARED:
             raise ValueError("this engine trains the squared loss only")
+        if hasattr(eng, "set_optimizer"):
+            eng.set_optimizer(self._opt, self.adagrad_eps, self.adagrad_init)
+        elif self._opt != _ffi.OPT_SGD:
+            raise ValueError("this engine trains with plain SGD only")
         live = j < eng.n_batches
         if not (self._collective() and self.overlap and hasattr(eng, "backward")):
             if live:
@@ -474,12 +485,16 @@ class HipDataParallelSGD(FMLearn):
     () = no overlap: whole backward, one all-reduce."""
 
     def __init__(self, comm, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, upper_fractions=(0.05, 0.15, 0.3, 0.55), exchange="dense",
-                 loss="squared"):
+                 loss="squared", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1):
         self.comm = comm
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
         # "squared" | "logistic" (HipSGD): set on the model before the plan (which agrees it over the ranks) and every step
         self.loss = loss
         self._loss = _ffi.loss_code(loss)
+        # "sgd" | "adagrad" (HipSGD) and its settings: likewise (the sharded exchange refuses AdaGrad, the touched one with decay)
+        self.optimizer = optimizer
+        self._opt = _ffi.optimizer_code(optimizer)
+        self.adagrad_eps, self.adagrad_init = _ffi.adagrad_settings(adagrad_eps, adagrad_init)
         self.upper_fractions = tuple(float(f) for f in upper_fractions)
         # "dense": the whole packed gradient all-reduced in overlapped slices, every rank updates every row; "sharded": the
         # slices reduce-scattered, every rank updates its 1/world share, the updated rows all-gathered; "touched": only the
@@ -499,10 +514,12 @@ class HipDataParallelSGD(FMLearn):
         self._planned_for = None
 
     def _set_loss(self, fm):
+        """The model's loss and optimizer (the same AdaGrad settings again keep its accumulators)."""
         _ffi.check(_ffi.load().fmhip_model_set_loss(fm.handle, self._loss))
+        _ffi.check(_ffi.load().fmhip_model_set_optimizer(fm.handle, self._opt, self.adagrad_eps, self.adagrad_init))
 
     def plan(self, fm, dataset):
-        """Collective: rank 0's data pick the cuts, every rank receives them (and agrees the models' loss)."""
+        """Collective: rank 0's data pick the cuts, every rank receives them (and agrees the models' loss and optimizer)."""
         import numpy as np
         self._set_loss(fm)
         fr = np.ascontiguousarray(sorted(self.upper_fractions), np.float64)

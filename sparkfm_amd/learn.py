@@ -26,13 +26,20 @@ class HipSGD(FMLearn):
     learner's own (the model's regv = 10 default is an ALS ridge term — quirk Q5).
     `loss`: "squared" (e = yhat - y, regression) or "logistic" (e = sigmoid(yhat) - [y > 0]: a binary
     classifier of labels {0,1} or {-1,+1}, the gradient of the mean log-loss; fmhip_model_set_loss).
-    `learn` and `step` set it on the model before they train.
+    `optimizer`: "sgd" (the rule above) or "adagrad" (torch.optim.Adagrad with lr = eta, weight_decay = reg: every
+    parameter keeps an accumulator n, started at `adagrad_init`; g_hat = g/|batch| + reg*theta, n += g_hat^2,
+    theta -= eta*g_hat / (sqrt(n) + adagrad_eps); fmhip_model_set_optimizer).
+    `learn` and `step` set both on the model before they train (the same AdaGrad settings again keep its accumulators).
     """
 
-    def __init__(self, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, shuffle_seed=None, loss="squared"):
+    def __init__(self, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, shuffle_seed=None, loss="squared", optimizer="sgd",
+                 adagrad_eps=1e-10, adagrad_init=0.1):
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
         self.loss = loss
         self._loss = _ffi.loss_code(loss)
+        self.optimizer = optimizer
+        self._opt = _ffi.optimizer_code(optimizer)
+        self.adagrad_eps, self.adagrad_init = _ffi.adagrad_settings(adagrad_eps, adagrad_init)
         self.shuffle_seed = shuffle_seed
         self._epoch = 0
         self.last_stats = None
@@ -48,11 +55,16 @@ class HipSGD(FMLearn):
         rng = np.random.Generator(np.random.PCG64([self.shuffle_seed, self._epoch]))
         return rng.permutation(n_batches).astype(np.int64)
 
+    def _set_rule(self, fm):
+        L = _ffi.load()
+        _ffi.check(L.fmhip_model_set_loss(fm.handle, self._loss))
+        _ffi.check(L.fmhip_model_set_optimizer(fm.handle, self._opt, self.adagrad_eps, self.adagrad_init))
+
     def learn(self, fm, dataset):
         L = _ffi.load()
         order = self.batch_order(dataset.n_batches)
         st = _ffi.Stats()
-        _ffi.check(L.fmhip_model_set_loss(fm.handle, self._loss))
+        self._set_rule(fm)
         _ffi.check(L.fmhip_sgd_epoch(fm.handle, dataset.handle, self.eta, self.reg0, self.regw, self.regv,
                                      _ffi.ptr(order), C.byref(st)))
         fm._device_updated()
@@ -63,7 +75,7 @@ class HipSGD(FMLearn):
     def step(self, fm, dataset, batch, want_stats=True):
         """A single mini-batch step (fmhip_sgd_step)."""
         st = _ffi.Stats()
-        _ffi.check(_ffi.load().fmhip_model_set_loss(fm.handle, self._loss))
+        self._set_rule(fm)
         _ffi.check(_ffi.load().fmhip_sgd_step(fm.handle, dataset.handle, batch, self.eta, self.reg0, self.regw,
                                               self.regv, C.byref(st) if want_stats else None))
         fm._device_updated()
