@@ -12,7 +12,7 @@
 //     sparkfm::HipALS       S/fm/lib/ALS.scala:15-75,202-208 the reference's own learner in fp64 on the GPU
 //     sparkfm::FM           S/fm/FM.scala:25-33, S/fm/impl/FactorizationMachines.scala:30-51   the fit loop
 //
-// Nothing but include/fmhip.h (the product header) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
+// Nothing but include/fmhip.h (the product header) and include/fmhip_topk.h (top-K recommendation) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
 // here a non-zero status of the C ABI becomes sparkfm::Error carrying fmhip_last_error().  Parameters live on the host as in
 // the reference (public, mutable: `fm.w0`, `fm.w`, `fm.v` with v[f + i*k] = breeze's column-major DenseMatrix(k, n+1)); every
 // call that needs them on the device uploads them first, as jvm/HipSGD.scala does (the fit loop calls `learn` once per
@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "fmhip.h"
+#include "fmhip_topk.h"
 
 namespace sparkfm {
 
@@ -147,6 +148,33 @@ class FMModel {
         double logloss = 0.0;
         check(fmhip_logloss(upload(), dataset.handle(), &logloss, nullptr));
         return logloss;
+    }
+
+    // Per row of `contexts` the k rows of `candidates` the model ranks highest (fmhip_topk): the users x items ranking of
+    // S/driver.scala:100-112, a pair's score being predict (S/fm/FMModel.scala:34) of "the context's entries, then the
+    // candidate's".  idx[c * k + j]: candidate rows, best first, -1 past the last one; score (nullable) beside it.
+    // exclude (nullable): per context the candidate rows that must not be returned, ascending and distinct.
+    std::vector<int32_t> recommend(DataSet &contexts, DataSet &candidates, int32_t k, std::vector<double> *score = nullptr,
+                                   const std::vector<std::vector<int32_t>> *exclude = nullptr) {
+        if (k < 1 || k > FMHIP_TOPK_MAX) throw Error(FMHIP_ERR_INVALID, "k outside [1, FMHIP_TOPK_MAX]");
+        const size_t B = (size_t)contexts.size();
+        std::vector<int64_t> eptr;
+        std::vector<int32_t> eidx;
+        if (exclude) {
+            if (exclude->size() != B) throw Error(FMHIP_ERR_INVALID, "exclude must hold one list per context");
+            eptr.push_back(0);
+            for (const auto &e : *exclude) {
+                eidx.insert(eidx.end(), e.begin(), e.end());
+                eptr.push_back((int64_t)eidx.size());
+            }
+            if (eidx.empty()) eidx.push_back(0);       // (a non-NULL pointer beside eptr)
+        }
+        std::vector<int32_t> idx(B * (size_t)k);
+        if (B == 0) return idx;
+        if (score) score->assign(B * (size_t)k, 0.0);
+        check(fmhip_topk(upload(), contexts.handle(), candidates.handle(), k, exclude ? eptr.data() : nullptr,
+                         exclude ? eidx.data() : nullptr, idx.data(), score ? score->data() : nullptr));
+        return idx;
     }
 
     // the device replica: created on first use, refreshed from the host fields before every use (they are public and mutable)

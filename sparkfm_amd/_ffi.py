@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -42,6 +42,9 @@ SYMBOLS_EXPERIMENTAL = (
     "fmhip_comm_profile_begin", "fmhip_comm_profile_end", "fmhip_comm_emulate", "fmhip_comm_emulate_load", "fmhip_comm_emulate_ranks",
     "fmhip_model_get_optimizer_state", "fmhip_model_set_optimizer_state",
 )
+# ... and include/fmhip_topk.h — top-K recommendation over (contexts x candidates)
+SYMBOLS_TOPK = ("fmhip_topk", "fmhip_pair_scores")
+TOPK_MAX = 128      # FMHIP_TOPK_MAX
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -232,7 +235,9 @@ def load():
     L.fmhip_feature_counts_gpu.argtypes = [C.c_int, i64, vp, i64, vp]
     L.fmhip_rank_from_counts_gpu.argtypes = [C.c_int, i64, vp, vp, vp]
     L.fmhip_relabel_columns_gpu.argtypes = [C.c_int, i64, vp, i64, vp, vp]
-    for name in SYMBOLS + SYMBOLS_EXPERIMENTAL:
+    L.fmhip_topk.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+    L.fmhip_pair_scores.argtypes = [vp, vp, vp, i64, i64, vp]
+    for name in SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK:
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

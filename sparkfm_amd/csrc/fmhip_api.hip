@@ -3,9 +3,11 @@
 //   fmhip_dataset.hip   datasets (host passes, device transposes, layout queries, feature relabelling)
 //   fmhip_step.hip      the launch sequence of one mini-batch step
 //   fmhip_comm.hip      the data-parallel step (RCCL / caller's transport)
-//   fm_forward / fm_backward / fm_apply / als_kernels / csc_build .hip   the kernels
+//   fm_forward / fm_backward / fm_apply / als_kernels / csc_build / fm_topk .hip   the kernels
 #include "fmhip_internal.h"
+#include "../../include/fmhip_topk.h"
 #include "als_kernels.h"
+#include "fm_topk.h"
 
 #include <algorithm>
 #include <atomic>
@@ -541,6 +543,175 @@ int fmhip_logloss(fmhip_model_t m, fmhip_dataset_t d, double *logloss, fmhip_sta
     TRY(score_pass(m, d, nullptr, nullptr, nullptr, &st, &sum_l));
     *logloss = st.rows > 0 ? sum_l / (double)st.rows : 0.0;
     if (stats) *stats = st;
+    return FMHIP_OK;
+}
+
+// ---- top-K recommendation (include/fmhip_topk.h) ----------------------------------------------------------------------------
+// score(c, d) = (yhat(c) + (yhat(d) - w0)) + sum_f q_f(c) q_f(d): one kFwdQ forward per row set — it writes q into a [rows][Kp]
+// table and yhat beside it in one launch — then the product and the selection of fm_topk.hip.  Scoring calls: the caller holds
+// the model's lock shared, the work runs on a leased ScoreCtx's stream.  The tables live for the length of the call only.
+namespace {
+
+// the kFwdQ forward of one batch of `d`: q rows to Q[rows][Kp], predictions to yhat[rows]
+int forward_q(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm, ScoreCtx &cx, float *Q, float *yhat) {
+    FwdArgs a = fwd_args(m, d, bm);
+    a.P = Q;
+    a.e = cx.e.p;
+    a.bsum = cx.bsum.p;
+    a.yhat = yhat;
+    a.loss = kLossSquared;
+    HIP_TRY(launch_forward(m->Kp, kFwdQ, a, cx.s, nullptr));
+    return FMHIP_OK;
+}
+
+// what both calls share: the checks, the lease, the candidates' table Qd [M][Kp] and predictions yd [M]
+struct PairJob {
+    fmhip_model_t m;
+    fmhip_dataset_t ctx, cand;
+    DevBuf<float> Qd, yd;
+    ScoreLease lease;       // (declared after the buffers: its destructor drains the stream before they are freed)
+    int64_t B = 0, M = 0;
+    PairJob(fmhip_model_t m_, fmhip_dataset_t c_, fmhip_dataset_t d_) : m(m_), ctx(c_), cand(d_), lease(m_) {}
+    int begin() {
+        if (!m || !ctx || !cand) return fail(FMHIP_ERR_INVALID, "model, contexts or candidates is NULL");
+        TRY(check_pair(m, ctx));
+        TRY(check_pair(m, cand));
+        B = ctx->n_rows;
+        M = cand->n_rows;
+        if (M > 0x7fffffff) return fail(FMHIP_ERR_INVALID, "%lld candidates: the count must fit an int32", (long long)M);
+        TRY(lease.take());
+        ScoreCtx &cx = *lease.cx;
+        const size_t rows_max = (size_t)std::max<int64_t>(std::max(ctx->max_rows, cand->max_rows), 1);
+        TRY(cx.e.ensure(rows_max));
+        TRY(cx.bsum.ensure((size_t)kMaxFwdBlocks * 4));
+        TRY(cx.P.ensure((size_t)std::max<int64_t>(ctx->max_rows, 1) * m->Kp));
+        TRY(cx.yhat.ensure((size_t)std::max<int64_t>(ctx->max_rows, 1)));
+        // behind whatever the model's own stream still has queued (a training step returns before it has run)
+        HIP_TRY(hipEventRecord(cx.ev, m->stream));
+        HIP_TRY(hipStreamWaitEvent(cx.s, cx.ev, 0));
+        if (B == 0 || M == 0) return FMHIP_OK;
+        TRY(Qd.alloc((size_t)M * m->Kp));
+        TRY(yd.alloc((size_t)M));
+        for (const BatchMeta &bm : cand->batches) TRY(forward_q(m, cand, bm, cx, Qd.p + (size_t)bm.row0 * m->Kp, yd.p + bm.row0));
+        return FMHIP_OK;
+    }
+    TopkArgs args(int64_t first, int64_t rows) const {      // for rows [first, first + rows) of the context batch held in cx.P / cx.yhat
+        TopkArgs a{};
+        a.Qc = lease.cx->P.p + (size_t)first * m->Kp;
+        a.yc = lease.cx->yhat.p + first;
+        a.Qd = Qd.p;
+        a.yd = yd.p;
+        a.w0 = m->w0.p;
+        a.B = (int32_t)rows;
+        a.M = (int32_t)M;
+        return a;
+    }
+};
+
+}  // namespace
+
+int fmhip_topk(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candidates, int32_t k, const int64_t *excl_ptr,
+               const int32_t *excl, int32_t *idx, double *score) {
+    ReadLock lock(m);
+    if (!m || !contexts || !candidates) return fail(FMHIP_ERR_INVALID, "model, contexts or candidates is NULL");
+    if (!idx) return fail(FMHIP_ERR_INVALID, "idx is NULL");
+    if (k < 1 || k > FMHIP_TOPK_MAX) return fail(FMHIP_ERR_INVALID, "k = %d outside [1, %d]", (int)k, FMHIP_TOPK_MAX);
+    if ((excl_ptr == nullptr) != (excl == nullptr))
+        return fail(FMHIP_ERR_INVALID, "excl_ptr and excl must both be given or both be NULL");
+    const int64_t B = contexts->n_rows, M = candidates->n_rows;
+    if (excl_ptr) {
+        if (excl_ptr[0] < 0) return fail(FMHIP_ERR_INVALID, "excl_ptr[0] < 0");
+        for (int64_t c = 0; c < B; ++c)      // (the offsets first: nothing of excl is read through a bad one)
+            if (excl_ptr[c + 1] < excl_ptr[c]) return fail(FMHIP_ERR_INVALID, "excl_ptr decreases at context %lld", (long long)c);
+        for (int64_t c = 0; c < B; ++c) {
+            for (int64_t p = excl_ptr[c]; p < excl_ptr[c + 1]; ++p) {
+                if (excl[p] < 0 || excl[p] >= M)
+                    return fail(FMHIP_ERR_INVALID, "context %lld excludes candidate %d outside [0, %lld)", (long long)c, (int)excl[p], (long long)M);
+                if (p > excl_ptr[c] && excl[p] <= excl[p - 1])
+                    return fail(FMHIP_ERR_INVALID, "the exclusions of context %lld are not ascending and distinct", (long long)c);
+            }
+        }
+    }
+    DevBuf<int64_t> d_eptr;
+    DevBuf<int32_t> d_excl, d_idx;
+    DevBuf<float> d_score;
+    DevBuf<unsigned long long> part;
+    PairJob job(m, contexts, candidates);
+    TRY(job.begin());
+    if (B == 0) return FMHIP_OK;
+    if (M == 0) {
+        for (int64_t i = 0; i < B * k; ++i) idx[i] = -1;
+        if (score) for (int64_t i = 0; i < B * k; ++i) score[i] = -HUGE_VAL;
+        return FMHIP_OK;
+    }
+    ScoreCtx &cx = *job.lease.cx;
+    if (excl_ptr) {
+        TRY(d_eptr.alloc((size_t)B + 1));
+        TRY(d_excl.alloc((size_t)std::max<int64_t>(excl_ptr[B], 1)));
+        HIP_TRY(hipMemcpyAsync(d_eptr.p, excl_ptr, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, cx.s));
+        if (excl_ptr[B] > 0) HIP_TRY(hipMemcpyAsync(d_excl.p, excl, (size_t)excl_ptr[B] * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
+    }
+    const size_t rows_max = (size_t)contexts->max_rows;
+    TRY(d_idx.alloc(rows_max * k));
+    TRY(d_score.alloc(rows_max * k));
+    std::vector<int32_t> h_idx;
+    std::vector<float> h_score;
+    for (const BatchMeta &bm : contexts->batches) {       // a chunk of contexts = a batch of their dataset
+        TRY(forward_q(m, contexts, bm, cx, cx.P.p, cx.yhat.p));
+        TopkArgs a = job.args(0, bm.rows);
+        a.K = k;
+        const int splits = topk_splits(bm.rows, M, &a.split_len);
+        TRY(part.ensure((size_t)bm.rows * splits * k));
+        a.part = part.p;
+        a.excl_ptr = excl_ptr ? d_eptr.p + bm.row0 : nullptr;
+        a.excl = d_excl.p;
+        HIP_TRY(launch_pair_topk(m->Kp, a, cx.s));
+        HIP_TRY(launch_topk_merge(part.p, (int32_t)bm.rows, splits, k, d_idx.p, d_score.p, cx.s));
+        HIP_TRY(hipMemcpyAsync(idx + bm.row0 * k, d_idx.p, (size_t)bm.rows * k * sizeof(int32_t), hipMemcpyDeviceToHost, cx.s));
+        if (score) {
+            h_score.resize((size_t)bm.rows * k);
+            HIP_TRY(hipMemcpyAsync(h_score.data(), d_score.p, h_score.size() * sizeof(float), hipMemcpyDeviceToHost, cx.s));
+        }
+        HIP_TRY(hipStreamSynchronize(cx.s));
+        if (score)
+            for (size_t i = 0; i < h_score.size(); ++i) score[(size_t)bm.row0 * k + i] = (double)h_score[i];
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_pair_scores(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candidates, int64_t c0, int64_t c1, double *out) {
+    ReadLock lock(m);
+    if (!m || !contexts || !candidates) return fail(FMHIP_ERR_INVALID, "model, contexts or candidates is NULL");
+    if (c0 < 0 || c1 < c0 || c1 > contexts->n_rows)
+        return fail(FMHIP_ERR_INVALID, "contexts [%lld, %lld) outside [0, %lld]", (long long)c0, (long long)c1, (long long)contexts->n_rows);
+    const int64_t M = candidates->n_rows;
+    if (c1 > c0 && M > 0 && !out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    DevBuf<float> d_out;
+    PairJob job(m, contexts, candidates);
+    TRY(job.begin());
+    if (c1 == c0 || M == 0) return FMHIP_OK;
+    ScoreCtx &cx = *job.lease.cx;
+    // the scores travel in pieces of at most 2^25 floats (whole context rows)
+    const int64_t piece_rows = std::max<int64_t>(1, ((int64_t)1 << 25) / std::max<int64_t>(M, 1));
+    TRY(d_out.alloc((size_t)std::min(piece_rows, c1 - c0) * M));
+    std::vector<float> h_out;
+    for (const BatchMeta &bm : contexts->batches) {
+        const int64_t lo = std::max(c0, bm.row0), hi = std::min(c1, bm.row0 + bm.rows);
+        if (lo >= hi) continue;
+        TRY(forward_q(m, contexts, bm, cx, cx.P.p, cx.yhat.p));
+        for (int64_t r0 = lo; r0 < hi; r0 += piece_rows) {
+            const int64_t rows = std::min(piece_rows, hi - r0);
+            TopkArgs a = job.args(r0 - bm.row0, rows);
+            (void)topk_splits(rows, M, &a.split_len);
+            a.out = d_out.p;
+            HIP_TRY(launch_pair_scores(m->Kp, a, cx.s));
+            h_out.resize((size_t)rows * M);
+            HIP_TRY(hipMemcpyAsync(h_out.data(), d_out.p, h_out.size() * sizeof(float), hipMemcpyDeviceToHost, cx.s));
+            HIP_TRY(hipStreamSynchronize(cx.s));
+            double *o = out + (size_t)(r0 - c0) * M;
+            for (size_t i = 0; i < h_out.size(); ++i) o[i] = (double)h_out[i];
+        }
+    }
     return FMHIP_OK;
 }
 

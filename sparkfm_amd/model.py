@@ -237,6 +237,45 @@ class FMModel(Model):
         _ffi.check(_ffi.load().fmhip_term_q(self.handle, dataset.handle, _ffi.ptr(out)))
         return out
 
+    def recommend(self, contexts, candidates, k, exclude=None, scores=True):
+        """Per row of `contexts` the `k` rows of `candidates` the model ranks highest (fmhip_topk): the score of a pair is
+        FMModel.predict (S/fm/FMModel.scala:34) of the row "the context's entries, then the candidate's" — the users x items
+        ranking the reference's demo trains for (S/driver.scala:100-112) — without ever forming the joined rows or the full
+        score matrix.  -> (idx int32 [B, k], score float64 [B, k]) (score is None with scores=False); best first, equal scores by
+        ascending candidate row, NaN last; fewer than k candidates left: -1 / -inf.  `exclude`: None, or one integer array of
+        candidate rows per context that must not be returned (sorted and de-duplicated here)."""
+        B, k = contexts.size, int(k)
+        if not 1 <= k <= _ffi.TOPK_MAX:
+            raise ValueError("k must be in [1, %d], not %d" % (_ffi.TOPK_MAX, k))
+        eptr = eidx = None
+        if exclude is not None:
+            if len(exclude) != B:
+                raise ValueError("exclude must hold one array per context (%d), not %d" % (B, len(exclude)))
+            lists = [np.unique(np.asarray(e, np.int64).reshape(-1)) for e in exclude]
+            for e in lists:
+                if len(e) and (e[0] < 0 or e[-1] >= candidates.size):
+                    raise ValueError("exclude names a candidate row outside [0, %d)" % candidates.size)
+            eptr = np.zeros(B + 1, np.int64)
+            if B:
+                np.cumsum([len(e) for e in lists], out=eptr[1:])
+            eidx = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), np.int32)
+            if not len(eidx):
+                eidx = np.zeros(1, np.int32)        # (a non-NULL pointer beside eptr)
+        idx = np.empty((B, k), np.int32)
+        score = np.empty((B, k)) if scores else None
+        _ffi.check(_ffi.load().fmhip_topk(self.handle, contexts.handle, candidates.handle, k, _ffi.ptr(eptr), _ffi.ptr(eidx),
+                                          _ffi.ptr(idx), _ffi.ptr(score)))
+        return idx, score
+
+    def pairScores(self, contexts, candidates, c0=0, c1=None):
+        """The scores `recommend` ranks by, in full, for the contexts [c0, c1) (fmhip_pair_scores): [c1 - c0, candidates.size]."""
+        c0, c1 = int(c0), contexts.size if c1 is None else int(c1)
+        if not 0 <= c0 <= c1 <= contexts.size:
+            raise ValueError("contexts [%d, %d) outside [0, %d]" % (c0, c1, contexts.size))
+        out = np.empty((c1 - c0, candidates.size))
+        _ffi.check(_ffi.load().fmhip_pair_scores(self.handle, contexts.handle, candidates.handle, c0, c1, _ffi.ptr(out)))
+        return out
+
     def batchGradient(self, dataset, batch=0):
         """sum over the batch of e*h (h: S/fm/lib/ALS.scala:56-58,40,21) -> (gv (k,n1), gw, g0, stats)."""
         n1 = self.num_attribute + 1
