@@ -204,7 +204,8 @@ int fmhip_term_q(fmhip_model_t m, fmhip_dataset_t d, double *q /* n_rows*k */);
 /* ---- training (build-defined mini-batch SGD; SparkFM itself only ships ALS) ---- */
 /*   g_theta = sum_{r in batch} e_r * h_r(theta),  h from S/fm/lib/ALS.scala:56-58 (V), :40 (w), :21 (w0)
  *   theta  <- theta - eta * (g_theta / |batch| + reg_theta * theta)
- * e_r = yhat_r - y_r, or sigma(yhat_r) - [y_r > 0] for a model set to FMHIP_LOSS_LOGISTIC (fmhip_model_set_loss).
+ * e_r = yhat_r - y_r, or sigma(yhat_r) - [y_r > 0] for a model set to FMHIP_LOSS_LOGISTIC (fmhip_model_set_loss); a model set to
+ * FMHIP_PAIRING_ADJACENT (fmhip_pairing.h) trains on pairs of rows: e_2j = -e_2j+1 = the loss's residual of the pair's difference.
  * A model set to FMHIP_OPT_ADAGRAD (fmhip_model_set_optimizer) takes per-coordinate steps instead, each theta with its accumulator n:
  *   g_hat  = g_theta / |batch| + reg_theta * theta,   n <- n + g_hat^2,   theta <- theta - eta * g_hat / (sqrt(n) + eps)      */
 int fmhip_sgd_step(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, double eta, double reg0, double regw,

@@ -12,7 +12,7 @@
 //     sparkfm::HipALS       S/fm/lib/ALS.scala:15-75,202-208 the reference's own learner in fp64 on the GPU
 //     sparkfm::FM           S/fm/FM.scala:25-33, S/fm/impl/FactorizationMachines.scala:30-51   the fit loop
 //
-// Nothing but include/fmhip.h (the product header) and include/fmhip_topk.h (top-K recommendation) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
+// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation) and include/fmhip_pairing.h (pairwise ranking) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
 // here a non-zero status of the C ABI becomes sparkfm::Error carrying fmhip_last_error().  Parameters live on the host as in
 // the reference (public, mutable: `fm.w0`, `fm.w`, `fm.v` with v[f + i*k] = breeze's column-major DenseMatrix(k, n+1)); every
 // call that needs them on the device uploads them first, as jvm/HipSGD.scala does (the fit loop calls `learn` once per
@@ -30,6 +30,7 @@
 
 #include "fmhip.h"
 #include "fmhip_topk.h"
+#include "fmhip_pairing.h"
 
 namespace sparkfm {
 
@@ -149,6 +150,19 @@ class FMModel {
         check(fmhip_logloss(upload(), dataset.handle(), &logloss, nullptr));
         return logloss;
     }
+    // Pairwise ranking score of the pairs (rows 2j, 2j+1) of `dataset` (fmhip_pair_logloss): the mean of -log sigmoid(+-d) over the
+    // pairs' margins d = predict(row 2j) - predict(row 2j+1), the sign by which row carries the larger label ...
+    double computePairLogLoss(DataSet &dataset) {
+        double logloss = 0.0;
+        check(fmhip_pair_logloss(upload(), dataset.handle(), &logloss, nullptr, nullptr));
+        return logloss;
+    }
+    // ... and the share of the pairs the model orders as their labels do (a tie counts one half): the pairwise AUC
+    double computePairAccuracy(DataSet &dataset) {
+        double logloss = 0.0, concordance = 0.0;
+        check(fmhip_pair_logloss(upload(), dataset.handle(), &logloss, &concordance, nullptr));
+        return concordance;
+    }
 
     // Per row of `contexts` the k rows of `candidates` the model ranks highest (fmhip_topk): the users x items ranking of
     // S/driver.scala:100-112, a pair's score being predict (S/fm/FMModel.scala:34) of "the context's entries, then the
@@ -202,23 +216,27 @@ class FMLearn {
 // loss = FMHIP_LOSS_LOGISTIC: e = sigmoid(yhat) - [y > 0], a binary classifier (fmhip_model_set_loss)
 // optimizer = FMHIP_OPT_ADAGRAD: per-coordinate steps, g_hat = g/|batch| + reg*theta, n += g_hat^2, theta -= eta*g_hat/(sqrt(n) + adagrad_eps),
 // n started at adagrad_init (fmhip_model_set_optimizer; set before every epoch — the same settings keep the accumulators)
+// pairs = true: rows 2j and 2j+1 of a batch are one example, the loss applied to their difference (pairwise ranking: BPR under the
+// logistic loss with the preferred row first; fmhip_model_set_pairing) — the dataset needs an even row count and an even batch_rows
 class HipSGD : public FMLearn {
   public:
     double eta, reg0, regw, regv;
     int loss;
     int optimizer;
     double adagrad_eps, adagrad_init;
+    bool pairs;
     fmhip_stats last_stats{};
     explicit HipSGD(double eta_ = 0.05, double reg0_ = 0.0, double regw_ = 0.0, double regv_ = 0.0, int loss_ = FMHIP_LOSS_SQUARED,
-                    int optimizer_ = FMHIP_OPT_SGD, double adagrad_eps_ = 1e-10, double adagrad_init_ = 0.1)
+                    int optimizer_ = FMHIP_OPT_SGD, double adagrad_eps_ = 1e-10, double adagrad_init_ = 0.1, bool pairs_ = false)
         : eta(eta_), reg0(reg0_), regw(regw_), regv(regv_), loss(loss_), optimizer(optimizer_), adagrad_eps(adagrad_eps_),
-          adagrad_init(adagrad_init_) {}
+          adagrad_init(adagrad_init_), pairs(pairs_) {}
     static HipSGD run(double eta = 0.05, double reg0 = 0.0, double regw = 0.0, double regv = 0.0, int loss = FMHIP_LOSS_SQUARED,
-                      int optimizer = FMHIP_OPT_SGD, double adagrad_eps = 1e-10, double adagrad_init = 0.1) {
-        return HipSGD(eta, reg0, regw, regv, loss, optimizer, adagrad_eps, adagrad_init);   // cf. ALS.run(), S/fm/lib/ALS.scala:202-208
+                      int optimizer = FMHIP_OPT_SGD, double adagrad_eps = 1e-10, double adagrad_init = 0.1, bool pairs = false) {
+        return HipSGD(eta, reg0, regw, regv, loss, optimizer, adagrad_eps, adagrad_init, pairs);   // cf. ALS.run(), S/fm/lib/ALS.scala:202-208
     }
     FMModel &learn(FMModel &fm, DataSet &dataset) override {
         check(fmhip_model_set_loss(fm.upload(), loss));
+        check(fmhip_model_set_pairing(fm.upload(), pairs ? FMHIP_PAIRING_ADJACENT : FMHIP_PAIRING_NONE));
         check(fmhip_model_set_optimizer(fm.upload(), optimizer, adagrad_eps, adagrad_init));
         check(fmhip_sgd_epoch(fm.upload(), dataset.handle(), eta, reg0, regw, regv, nullptr, &last_stats));
         fm.download();

@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -45,6 +45,8 @@ SYMBOLS_EXPERIMENTAL = (
 # ... and include/fmhip_topk.h — top-K recommendation over (contexts x candidates)
 SYMBOLS_TOPK = ("fmhip_topk", "fmhip_pair_scores")
 TOPK_MAX = 128      # FMHIP_TOPK_MAX
+# ... and include/fmhip_pairing.h — pairwise ranking: training on pairs of adjacent rows, scoring held-out pairs
+SYMBOLS_PAIRING = ("fmhip_model_set_pairing", "fmhip_pair_logloss")
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -60,6 +62,17 @@ def loss_code(loss):
     if loss not in LOSSES:
         raise ValueError("loss must be one of %s, not %r" % (sorted(LOSSES), loss))
     return LOSSES[loss]
+
+
+# enum fmhip_pairing (include/fmhip_pairing.h): how a batch's rows form the examples a model trains on (fmhip_model_set_pairing)
+PAIRING_NONE, PAIRING_ADJACENT = 0, 1
+
+
+def pairing_code(pairs):
+    """False | True -> enum fmhip_pairing; anything but a bool raises ValueError."""
+    if not isinstance(pairs, bool):
+        raise ValueError("pairs must be True or False, not %r" % (pairs,))
+    return PAIRING_ADJACENT if pairs else PAIRING_NONE
 
 
 # enum fmhip_optimizer (include/fmhip.h): the update rule a model trains under (fmhip_model_set_optimizer)
@@ -171,6 +184,8 @@ def load():
     L.fmhip_rmse.argtypes = [vp, vp, P(dbl), P(Stats)]
     L.fmhip_logloss.argtypes = [vp, vp, P(dbl), P(Stats)]
     L.fmhip_model_set_loss.argtypes = [vp, C.c_int]
+    L.fmhip_model_set_pairing.argtypes = [vp, C.c_int]
+    L.fmhip_pair_logloss.argtypes = [vp, vp, P(dbl), P(dbl), P(Stats)]
     L.fmhip_model_set_optimizer.argtypes = [vp, C.c_int, dbl, dbl]
     L.fmhip_model_get_optimizer_state.argtypes = [vp, P(dbl), vp, vp]
     L.fmhip_model_set_optimizer_state.argtypes = [vp, dbl, vp, vp]
@@ -237,7 +252,7 @@ def load():
     L.fmhip_relabel_columns_gpu.argtypes = [C.c_int, i64, vp, i64, vp, vp]
     L.fmhip_topk.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.fmhip_pair_scores.argtypes = [vp, vp, vp, i64, i64, vp]
-    for name in SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK:
+    for name in SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING:
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

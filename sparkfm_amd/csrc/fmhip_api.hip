@@ -8,6 +8,7 @@
 #include "../../include/fmhip_topk.h"
 #include "als_kernels.h"
 #include "fm_topk.h"
+#include "fm_pairing.h"
 
 #include <algorithm>
 #include <atomic>
@@ -229,6 +230,15 @@ int fmhip_model_set_loss(fmhip_model_t m, int loss) {
     WriteLock lock(m);
     if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
     m->loss = loss;
+    return FMHIP_OK;
+}
+
+int fmhip_model_set_pairing(fmhip_model_t m, int pairing) {
+    if (pairing != FMHIP_PAIRING_NONE && pairing != FMHIP_PAIRING_ADJACENT)
+        return fail(FMHIP_ERR_INVALID, "pairing %d: FMHIP_PAIRING_NONE (0) or FMHIP_PAIRING_ADJACENT (1)", pairing);
+    WriteLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    m->pairing = pairing;
     return FMHIP_OK;
 }
 
@@ -546,6 +556,54 @@ int fmhip_logloss(fmhip_model_t m, fmhip_dataset_t d, double *logloss, fmhip_sta
     return FMHIP_OK;
 }
 
+// Pairwise ranking score of the pairs (2j, 2j+1) of `d`, whatever the model's loss or pairing: per batch one residual-mode forward
+// for the predictions, then k_pair_score's per-block partials and the block reduction of fmhip_logloss (fp64 sums).
+int fmhip_pair_logloss(fmhip_model_t m, fmhip_dataset_t d, double *logloss, double *concordance, fmhip_stats *stats) {
+    ReadLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    if (!logloss) return fail(FMHIP_ERR_INVALID, "logloss is NULL");
+    TRY(check_pair(m, d));
+    TRY(check_even_batches(d));
+    ScoreLease lease(m);
+    TRY(lease.take());
+    ScoreCtx &cx = *lease.cx;
+    const size_t rows_max = (size_t)std::max<int64_t>(d->max_rows, 2);
+    TRY(cx.yhat.ensure(rows_max));
+    TRY(cx.bsum.ensure((size_t)kMaxFwdBlocks * 4));
+    TRY(cx.acc.ensure(5));
+    // behind whatever the model's own stream still has queued (a training step returns before it has run)
+    HIP_TRY(hipEventRecord(cx.ev, m->stream));
+    HIP_TRY(hipStreamWaitEvent(cx.s, cx.ev, 0));
+    HIP_TRY(hipMemsetAsync(cx.acc.p, 0, 5 * sizeof(double), cx.s));
+    for (const BatchMeta &bm : d->batches) {
+        FwdArgs a = fwd_args(m, d, bm);
+        a.P = nullptr;
+        a.e = nullptr;
+        a.bsum = nullptr;
+        a.yhat = cx.yhat.p;
+        a.loss = kLossSquared;
+        HIP_TRY(launch_forward(m->Kp, kFwdResidual, a, cx.s, nullptr));
+        int parts = 0;
+        HIP_TRY(launch_pair_score(cx.yhat.p, d->y.p + bm.row0, (int32_t)(bm.rows / 2), cx.bsum.p, cx.s, &parts));
+        HIP_TRY(launch_reduce_blocks(cx.bsum.p, parts, (int32_t)bm.rows, nullptr, cx.acc.p, cx.s, true));
+    }
+    double h[5];       // {concordant pairs, sum e^2, rows, rows with a non-finite prediction, sum of the pairs' log-losses}
+    HIP_TRY(hipMemcpyAsync(h, cx.acc.p, sizeof h, hipMemcpyDeviceToHost, cx.s));
+    HIP_TRY(hipStreamSynchronize(cx.s));
+    const double pairs = (double)(d->n_rows / 2);
+    *logloss = pairs > 0 ? h[4] / pairs : 0.0;
+    if (concordance) *concordance = pairs > 0 ? h[0] / pairs : 0.0;
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        stats->sum_e = 0.0;        // e_2j = -e_2j+1
+        stats->sse = h[1];
+        stats->rows = (int64_t)llround(h[2]);
+        stats->nonfinite = (int64_t)llround(h[3]);
+        stats->nnz = d->nnz;
+    }
+    return FMHIP_OK;
+}
+
 // ---- top-K recommendation (include/fmhip_topk.h) ----------------------------------------------------------------------------
 // score(c, d) = (yhat(c) + (yhat(d) - w0)) + sum_f q_f(c) q_f(d): one kFwdQ forward per row set — it writes q into a [rows][Kp]
 // table and yhat beside it in one launch — then the product and the selection of fm_topk.hip.  Scoring calls: the caller holds
@@ -799,6 +857,9 @@ int fmhip_als_epoch(fmhip_model_t m, fmhip_dataset_t d, double reg0, double regw
     if (m->loss != FMHIP_LOSS_SQUARED)
         return fail(FMHIP_ERR_UNSUPPORTED, "ALS is derived for the squared loss: this model trains under the logistic loss "
                                            "(fmhip_model_set_loss)");
+    if (m->pairing != FMHIP_PAIRING_NONE)
+        return fail(FMHIP_ERR_UNSUPPORTED, "ALS is derived for the squared loss of single rows: this model trains on pairs of rows "
+                                           "(fmhip_model_set_pairing)");
     if (d->batches.size() > 1 || (d->nnz > 0 && !d->val64.p))
         return fail(FMHIP_ERR_UNSUPPORTED, "ALS walks the whole-dataset transpose: create the dataset with batch_rows <= 0 "
                                            "(single batch, at most 2^27 stored nonzeros) and without asking for the dense hot "

@@ -299,6 +299,7 @@ struct fmhip_comm {
     int64_t plan_max_rows = -1;
     int64_t plan_steps = 0;                   // ... and the largest batch count: the lock-step steps of an epoch
     int plan_loss = -1;                       // ... and the models' loss (fmhip_model_set_loss; -1: no plan yet)
+    int plan_pairing = -1;                    // ... and pairing (fmhip_model_set_pairing), agreed in the same word as the loss
     int plan_opt = -1;                        // ... and their optimizer with its settings (fmhip_model_set_optimizer; -1: no plan yet)
     double plan_eps = 0.0, plan_init = 0.0;
 };
@@ -960,6 +961,9 @@ int local_checks(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t
     if (c->plan_loss >= 0 && m->loss != c->plan_loss)
         return fail(FMHIP_ERR_INVALID, "the plan was agreed for loss %d, this model now trains under loss %d (fmhip_model_set_loss): call "
                                        "fmhip_dp_plan again (every rank)", c->plan_loss, m->loss);
+    if (c->plan_pairing >= 0 && m->pairing != c->plan_pairing)
+        return fail(FMHIP_ERR_INVALID, "the plan was agreed for pairing %d, this model now trains under pairing %d (fmhip_model_set_pairing): call "
+                                       "fmhip_dp_plan again (every rank)", c->plan_pairing, m->pairing);
     if (c->plan_opt >= 0 && (m->opt != c->plan_opt || memcmp(&m->ada_eps, &c->plan_eps, sizeof(double)) != 0 ||
                              memcmp(&m->ada_init, &c->plan_init, sizeof(double)) != 0))
         return fail(FMHIP_ERR_INVALID, "the plan was agreed for optimizer %d (eps %g, initial accumulator %g), this model now trains under "
@@ -1310,13 +1314,14 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     // What every rank must agree on before a step can be sized (one max-reduce): the largest mini-batch of any rank —
     // its global row count travels as one fp32 sum, exact below 2^24 —, whether some rank's transposes are row-blocked
     // (it cannot cut its backward: then nobody does, same collectives everywhere), the touched-rows table's width, and
-    // whether some rank cannot hold the sharded exchange's equal shares, and the models' loss (it and its complement: a maximum
-    // of 1 for both = the ranks differ).  All ranks pass or fail together.
+    // whether some rank cannot hold the sharded exchange's equal shares, and the models' loss and pairing in one word, loss + 2 * pairing
+    // in 0..3 (it and its complement to 3: the two maxima add up to 3 iff every rank holds the same word).  All ranks pass or fail together.
     // The last slot: whether some rank's model is not plain SGD — then (and only then: an SGD plan issues the collectives it
     // always did) a second max-reduce agrees the optimizer and the bit patterns of its settings.
     constexpr int kAgree = 8;
     static_assert(kAgree <= kMaxCuts + 1, "the plan's agreement vector travels in the communicator's scratch (kMaxCuts + 1 int64)");
-    int64_t agree[kAgree] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size(), m->loss, 1 - m->loss, m->opt != FMHIP_OPT_SGD};
+    const int64_t loss_word = m->loss + 2 * m->pairing;
+    int64_t agree[kAgree] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size(), loss_word, 3 - loss_word, m->opt != FMHIP_OPT_SGD};
     for (const auto &bm : d->batches) {
         agree[0] = std::max<int64_t>(agree[0], bm.rows);
         agree[2] = std::max<int64_t>(agree[2], (int64_t)bm.n_cols + d->hot_pages * kHotT);
@@ -1341,8 +1346,13 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
             return fail(FMHIP_ERR_UNSUPPORTED, "the sharded exchange does not support AdaGrad (each rank's accumulators would hold its own share "
                                                "only): use the dense, pipelined or touched exchange");
     }
-    if (agree[5] && agree[6])
-        return fail(FMHIP_ERR_INVALID, "the ranks' models train under different losses (fmhip_model_set_loss): set the same loss on every rank");
+    if (agree[5] + agree[6] != 3)
+        return fail(FMHIP_ERR_INVALID, "the ranks' models train under different losses (fmhip_model_set_loss) or pairings (fmhip_model_set_pairing): "
+                                       "set the same loss and the same pairing on every rank");
+    // (agreed above: every rank holds the same pairing, so every rank refuses here or none does)
+    if (m->pairing != FMHIP_PAIRING_NONE && c->exchange == FMHIP_EXCHANGE_PIPELINED)
+        return fail(FMHIP_ERR_UNSUPPORTED, "the pipelined exchange runs the two-pass forward, which does not form pair residuals "
+                                           "(fmhip_model_set_pairing): use the dense, sharded or touched exchange");
     if ((double)agree[0] * c->world >= 16777216.0)
         return fail(FMHIP_ERR_INVALID, "a global batch of %lld x %d rows exceeds 2^24 (the summed row count travels as one fp32 word): "
                                        "use smaller batches", (long long)agree[0], c->world);
@@ -1352,6 +1362,7 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     c->plan_max_rows = agree[0];
     c->plan_steps = agree[4];
     c->plan_loss = m->loss;
+    c->plan_pairing = m->pairing;
     c->plan_opt = m->opt;
     c->plan_eps = m->ada_eps;
     c->plan_init = m->ada_init;

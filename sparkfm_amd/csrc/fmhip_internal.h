@@ -4,6 +4,7 @@
 // Not installed, not part of the ABI.
 #pragma once
 #include "../../include/fmhip_experimental.h"   // (includes fmhip.h: the library implements both surfaces)
+#include "../../include/fmhip_pairing.h"        // (enum fmhip_pairing: the model carries the switch)
 #include "fm_kernels.h"
 #include "fmhip_host.h"   // the pure host arithmetic (shards, relabelling, batch metadata, band plan, ALS levels, the dp plan's cuts and shares)
 
@@ -221,6 +222,10 @@ struct fmhip_model {
     // scale itself accumulates no fp32 rounding from step to step.
     double sv = 1.0, sw = 1.0;
     int loss = FMHIP_LOSS_SQUARED;   // enum fmhip_loss: the residual every training path forms (fmhip_model_set_loss)
+    // enum fmhip_pairing (fmhip_model_set_pairing).  ADJACENT: rows 2j / 2j+1 of a batch are one example, the loss is applied to
+    // their difference (fm_pairing.h); the training forward then runs in two launches and keeps the rows' predictions in yhat
+    int pairing = FMHIP_PAIRING_NONE;
+    DevBuf<float> yhat;           // paired training forward: [max_rows] predictions between its two launches
     // enum fmhip_optimizer (fmhip_model_set_optimizer).  AdaGrad: per-coordinate accumulators shaped like the parameters —
     // NV [n1p][Kp] like V (packed rows: slot pack_k holds w_i's), Nw [n1p] (unpacked rows only), N0 [1] — one more copy of
     // the model (8.6 GB at 2^25 x 64); the tables stay at scale 1 (sv = sw = 1) while it is set
@@ -278,7 +283,8 @@ int partition_rows_locked(fmhip_dataset_t d, int64_t cut_feature);      // fmhip
 int ensure_workspace(fmhip_model_t m, fmhip_dataset_t d);
 FwdArgs fwd_args(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm);
 int check_pair(fmhip_model_t m, fmhip_dataset_t d);
-int check_train(fmhip_model_t m, fmhip_dataset_t d);      // + the dataset must have its transposes
+int check_train(fmhip_model_t m, fmhip_dataset_t d);      // + the dataset must have its transposes (and, for a paired model, even batches)
+int check_even_batches(fmhip_dataset_t d);                // pairs (rows 2j, 2j+1) must not straddle batches
 int check_batch(fmhip_dataset_t d, int64_t batch);
 // the pieces of one mini-batch step, all asynchronous on m->stream (fmhip_api.hip)
 int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b);

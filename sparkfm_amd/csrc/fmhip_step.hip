@@ -4,6 +4,7 @@
 // of its own, inside the fixup launch, inside the column walk) and the lazily decayed tables' bookkeeping.  Everything is
 // asynchronous on the model's stream; the arithmetic lives in fm_forward.hip / fm_backward.hip / fm_apply.hip.
 #include "fmhip_internal.h"
+#include "fm_pairing.h"
 
 #include <algorithm>
 #include <atomic>
@@ -71,6 +72,21 @@ int check_train(fmhip_model_t m, fmhip_dataset_t d) {
     TRY(check_pair(m, d));
     if (d->scoring_only)
         return fail(FMHIP_ERR_UNSUPPORTED, "dataset was created with fmhip_rows_create (scoring only): it has no transposes to train on");
+    if (m->pairing != FMHIP_PAIRING_NONE) TRY(check_even_batches(d));
+    return FMHIP_OK;
+}
+
+// Pairs are rows 2j / 2j+1 of a BATCH: every batch must start at an even row and hold an even number of rows.  Batches are
+// batch_rows consecutive rows each, so that is an even n_rows and — with more than one batch — an even batch_rows.
+int check_even_batches(fmhip_dataset_t d) {
+    if (d->n_rows & 1)
+        return fail(FMHIP_ERR_INVALID, "pairing: n_rows = %lld is odd — rows 2j and 2j+1 form a pair, the last row has no partner", (long long)d->n_rows);
+    for (size_t b = 0; b < d->batches.size(); ++b) {
+        const BatchMeta &bm = d->batches[b];
+        if ((bm.row0 | bm.rows) & 1)
+            return fail(FMHIP_ERR_INVALID, "pairing: batch_rows = %lld is odd — batch %zu would start at row %lld with %lld rows and cut a pair "
+                                           "(rows 2j and 2j+1) in two", (long long)d->batch_rows, b, (long long)bm.row0, (long long)bm.rows);
+    }
     return FMHIP_OK;
 }
 
@@ -83,6 +99,7 @@ int check_batch(fmhip_dataset_t d, int64_t batch) {
 int ensure_workspace(fmhip_model_t m, fmhip_dataset_t d) {
     TRY(m->P.ensure((size_t)std::max<int64_t>(d->max_rows, 1) * m->Kp));
     TRY(m->e.ensure((size_t)std::max<int64_t>(d->max_rows, 1)));
+    if (m->pairing != FMHIP_PAIRING_NONE) TRY(m->yhat.ensure((size_t)std::max<int64_t>(d->max_rows, 2)));
     TRY(m->part.ensure((size_t)std::max<int32_t>(d->max_ranges, 1) * 2 * (m->Kp + kPartPad)));
     TRY(m->pieces.ensure((size_t)std::max<int32_t>(d->max_pieces, 1) * (m->Kp + kPartPad)));
     TRY(m->bsum.ensure((size_t)kMaxFwdBlocks * 4));
@@ -219,7 +236,29 @@ int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
         HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
         m->grad_dirty = false;
     }
-    {
+    if (m->pairing == FMHIP_PAIRING_ADJACENT) {
+        // two launches: the q-mode forward — every existing kernel choice (hot pages, packed rows, row order, address mode) as it
+        // is, P = sv*q and the predictions beside it — then the pairs' finish (fm_pairing.hip): P rows times +-g, e, the statistics
+        // partials (its own block count: the backward's finish sums m->fwd_parts of them)
+        // (check_train has refused datasets whose batches would cut a pair)
+        ProfScope ps(m, FMHIP_K_FORWARD, bm.nnz_total, bm.rows);
+        FwdArgs a = fwd_args(m, d, bm);
+        a.e = nullptr;
+        a.bsum = nullptr;
+        a.yhat = m->yhat.p;
+        a.loss = kLossSquared;            // (the q-mode has one instance; its residual goes nowhere)
+        HIP_TRY(launch_forward(m->Kp, kFwdQ, a, m->stream, nullptr));
+        PairArgs pa{};
+        pa.P = m->P.p;
+        pa.yhat = m->yhat.p;
+        pa.y = d->y.p + bm.row0;
+        pa.e = m->e.p;
+        pa.bsum = m->bsum.p;
+        pa.n_pairs = (int32_t)(bm.rows / 2);
+        pa.pack_k = m->pack_k();
+        pa.loss = m->loss;
+        HIP_TRY(launch_pair_finish(m->Kp, pa, m->stream, &m->fwd_parts));
+    } else {
         ProfScope ps(m, FMHIP_K_FORWARD, bm.nnz_total, bm.rows);
         HIP_TRY(launch_forward(m->Kp, kFwdTrain, fwd_args(m, d, bm), m->stream, &m->fwd_parts));
     }
@@ -237,6 +276,9 @@ int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
 // step_forward.  A then B = the forward, up to the order of the fp32 sums (A's terms first).
 int step_forward_pass(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int pass) {
     const BatchMeta &bm = d->batches[(size_t)b];
+    if (m->pairing != FMHIP_PAIRING_NONE)
+        return fail(FMHIP_ERR_UNSUPPORTED, "the two-pass forward does not form pair residuals (fmhip_model_set_pairing): use fmhip_step_forward, "
+                                           "and the dense, sharded or touched exchange");
     if (d->split_cut < 0) return fail(FMHIP_ERR_INVALID, "the dataset's rows are not partitioned (fmhip_dataset_partition_rows)");
     if (m->Kp > 64) return fail(FMHIP_ERR_UNSUPPORTED, "the two-pass forward serves models of up to 64 padded factors (this one: %d)", m->Kp);
     TRY(ensure_workspace(m, d));

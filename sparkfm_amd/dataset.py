@@ -85,6 +85,25 @@ class DataSet(Features):
         return cls(np.asarray(ptr, np.int64), col, val, np.asarray(ys, np.float64), name=name, **kw)
 
     @classmethod
+    def from_pairs(cls, preferred, other, name="pairs", **kw):
+        """Preference pairs for pairwise ranking (``HipSGD(pairs=True)``, ``FMModel.computePairLogLoss``): pair j is row 2j =
+        ``preferred[j]`` with label 1 and row 2j+1 = ``other[j]`` with label 0.  Both row sets take the forms ``from_rows``
+        takes — (label, (indices, values)) items, whose labels are ignored — or bare (indices, values) items.  Pairs must not
+        straddle mini-batches: an odd ``batch_rows`` is raised to the next even number."""
+        def bare(rows):
+            return [it[1] if np.ndim(it[0]) == 0 else it for it in rows]
+        pref, oth = bare(preferred), bare(other)
+        if len(pref) != len(oth):
+            raise ValueError("preferred and other must be equally long (%d and %d rows)" % (len(pref), len(oth)))
+        rows = []
+        for p, o in zip(pref, oth):
+            rows.append((1.0, p))
+            rows.append((0.0, o))
+        if "batch_rows" in kw:
+            kw["batch_rows"] = int(kw["batch_rows"]) + (int(kw["batch_rows"]) & 1 if int(kw["batch_rows"]) > 0 else 0)
+        return cls.from_rows(rows, name=name, **kw)
+
+    @classmethod
     def from_arrays(cls, d, **kw):
         return cls(d["row_ptr"], d["col"], d["val"], d["y"], **kw)
 

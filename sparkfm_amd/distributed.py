@@ -54,6 +54,10 @@ class HipEngine:
         """enum fmhip_loss: the loss the model's steps train under (fmhip_model_set_loss)."""
         _ffi.check(self.L.fmhip_model_set_loss(self.fm.handle, loss))
 
+    def set_pairing(self, pairing):
+        """enum fmhip_pairing: whether the model's steps train on pairs of adjacent rows (fmhip_model_set_pairing)."""
+        _ffi.check(self.L.fmhip_model_set_pairing(self.fm.handle, pairing))
+
     def set_optimizer(self, optimizer, eps, init):
         """enum fmhip_optimizer and its settings: the update rule of the model's steps (fmhip_model_set_optimizer)."""
         _ffi.check(self.L.fmhip_model_set_optimizer(self.fm.handle, optimizer, eps, init))
@@ -127,8 +131,11 @@ class DataParallelSGD(FMLearn):
     """FMLearn whose `learn` runs one data-parallel epoch over this rank's row shard."""
 
     def __init__(self, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, group=None, engine_factory=HipEngine,
-                 always_reduce=False, overlap=True, cuts=None, loss="squared", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1):
+                 always_reduce=False, overlap=True, cuts=None, loss="squared", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1,
+                 pairs=False):
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
+        self.pairs = pairs                   # True: pairs of adjacent rows are the examples (HipSGD): likewise set before every step
+        self._pairing = _ffi.pairing_code(pairs)
         self.loss = loss                     # "squared" | "logistic" (HipSGD): set through the engine before every step
         self._loss = _ffi.loss_code(loss)
         self.optimizer = optimizer           # "sgd" | "adagrad" (HipSGD): likewise; every rank's accumulators see the same summed gradient
@@ -195,6 +202,10 @@ class DataParallelSGD(FMLearn):
             eng.set_loss(self._loss)
         elif self._loss != _ffi.LOSS_SQUARED:
             raise ValueError("this engine trains the squared loss only")
+        if hasattr(eng, "set_pairing"):
+            eng.set_pairing(self._pairing)
+        elif self._pairing != _ffi.PAIRING_NONE:
+            raise ValueError("this engine trains on single rows only")
         if hasattr(eng, "set_optimizer"):
             eng.set_optimizer(self._opt, self.adagrad_eps, self.adagrad_init)
         elif self._opt != _ffi.OPT_SGD:
@@ -485,8 +496,12 @@ class HipDataParallelSGD(FMLearn):
     () = no overlap: whole backward, one all-reduce."""
 
     def __init__(self, comm, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, upper_fractions=(0.05, 0.15, 0.3, 0.55), exchange="dense",
-                 loss="squared", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1):
+                 loss="squared", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1, pairs=False):
         self.comm = comm
+        # True: pairs of adjacent rows are the examples (HipSGD): set with the loss; every rank's shard needs even batches, and
+        # the pipelined exchange refuses it
+        self.pairs = pairs
+        self._pairing = _ffi.pairing_code(pairs)
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
         # "squared" | "logistic" (HipSGD): set on the model before the plan (which agrees it over the ranks) and every step
         self.loss = loss
@@ -514,8 +529,9 @@ class HipDataParallelSGD(FMLearn):
         self._planned_for = None
 
     def _set_loss(self, fm):
-        """The model's loss and optimizer (the same AdaGrad settings again keep its accumulators)."""
+        """The model's loss, pairing and optimizer (the same AdaGrad settings again keep its accumulators)."""
         _ffi.check(_ffi.load().fmhip_model_set_loss(fm.handle, self._loss))
+        _ffi.check(_ffi.load().fmhip_model_set_pairing(fm.handle, self._pairing))
         _ffi.check(_ffi.load().fmhip_model_set_optimizer(fm.handle, self._opt, self.adagrad_eps, self.adagrad_init))
 
     def plan(self, fm, dataset):

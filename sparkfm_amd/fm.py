@@ -9,7 +9,9 @@ log = logging.getLogger("sparkfm_amd")
 class Task:
     """S/Task.scala:3-6 (accepted and, as in the reference, never read).  The loss is the learner's: a binary
     classifier is ``FM(dataset, k).learnWith(HipSGD.run(loss="logistic"))`` (labels {0,1} or {-1,+1}), scored by
-    ``fm.computeLogLoss(test)`` and ``fm.computeAccuracy(test)``."""
+    ``fm.computeLogLoss(test)`` and ``fm.computeAccuracy(test)``; a ranking model is
+    ``FM(DataSet.from_pairs(preferred, other), k).learnWith(HipSGD.run(loss="logistic", pairs=True))``, scored by
+    ``fm.computePairLogLoss(test)`` and ``fm.computePairAccuracy(test)``."""
     Regression = "Regression"
     Classification = "Classification"
 

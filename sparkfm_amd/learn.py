@@ -29,17 +29,23 @@ class HipSGD(FMLearn):
     `optimizer`: "sgd" (the rule above) or "adagrad" (torch.optim.Adagrad with lr = eta, weight_decay = reg: every
     parameter keeps an accumulator n, started at `adagrad_init`; g_hat = g/|batch| + reg*theta, n += g_hat^2,
     theta -= eta*g_hat / (sqrt(n) + adagrad_eps); fmhip_model_set_optimizer).
-    `learn` and `step` set both on the model before they train (the same AdaGrad settings again keep its accumulators).
+    `pairs`: True trains on PAIRS of rows (pairwise ranking; fmhip_model_set_pairing): rows 2j and 2j+1 of a batch are one
+    example and the loss is applied to their difference — with loss="logistic" and the preferred row first (label 1 / 0,
+    ``DataSet.from_pairs``) this is BPR, -log sigmoid(yhat_preferred - yhat_other).  The dataset needs an even number of rows
+    and an even batch_rows.
+    `learn` and `step` set all three on the model before they train (the same AdaGrad settings again keep its accumulators).
     """
 
     def __init__(self, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, shuffle_seed=None, loss="squared", optimizer="sgd",
-                 adagrad_eps=1e-10, adagrad_init=0.1):
+                 adagrad_eps=1e-10, adagrad_init=0.1, pairs=False):
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
         self.loss = loss
         self._loss = _ffi.loss_code(loss)
         self.optimizer = optimizer
         self._opt = _ffi.optimizer_code(optimizer)
         self.adagrad_eps, self.adagrad_init = _ffi.adagrad_settings(adagrad_eps, adagrad_init)
+        self.pairs = pairs
+        self._pairing = _ffi.pairing_code(pairs)
         self.shuffle_seed = shuffle_seed
         self._epoch = 0
         self.last_stats = None
@@ -58,6 +64,7 @@ class HipSGD(FMLearn):
     def _set_rule(self, fm):
         L = _ffi.load()
         _ffi.check(L.fmhip_model_set_loss(fm.handle, self._loss))
+        _ffi.check(L.fmhip_model_set_pairing(fm.handle, self._pairing))
         _ffi.check(L.fmhip_model_set_optimizer(fm.handle, self._opt, self.adagrad_eps, self.adagrad_init))
 
     def learn(self, fm, dataset):

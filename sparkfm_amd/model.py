@@ -225,6 +225,22 @@ class FMModel(Model):
         _ffi.check(_ffi.load().fmhip_logloss(self.handle, dataset.handle, C.byref(r), None))
         return r.value
 
+    def _pair_score(self, dataset):
+        r, c = C.c_double(), C.c_double()
+        _ffi.check(_ffi.load().fmhip_pair_logloss(self.handle, dataset.handle, C.byref(r), C.byref(c), None))
+        return r.value, c.value
+
+    def computePairLogLoss(self, dataset):
+        """Mean pairwise log-loss over the pairs (rows 2j, 2j+1) of `dataset` (``DataSet.from_pairs``): -log sigmoid(d) of the
+        margin d = predict(row 2j) - predict(row 2j+1) when row 2j carries the larger label, -log sigmoid(-d) otherwise
+        (fmhip_pair_logloss); log 2 for a model that cannot tell the rows apart."""
+        return self._pair_score(dataset)[0]
+
+    def computePairAccuracy(self, dataset):
+        """Share of the pairs of `dataset` the model orders as their labels do (a tie counts one half): the pairwise AUC
+        (fmhip_pair_logloss's concordance)."""
+        return self._pair_score(dataset)[1]
+
     def residual(self, dataset):
         """ALS.precomputeTermE (S/fm/lib/ALS.scala:142-144): e = predict - target."""
         out = np.empty(dataset.size)
