@@ -98,6 +98,39 @@ def adagrad_settings(eps, init):
     return eps, init
 
 
+class TrainRule:
+    """How a model trains, as one value: loss, optimizer with its AdaGrad settings, pairing — the learners' five keywords,
+    validated here (ValueError); `set_on` puts it on a model through the three setters of the C ABI."""
+
+    def __init__(self, loss="squared", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1, pairs=False):
+        self.loss, self.optimizer, self.pairs = loss, optimizer, pairs
+        self.loss_code, self.opt_code = loss_code(loss), optimizer_code(optimizer)
+        self.adagrad_eps, self.adagrad_init = adagrad_settings(adagrad_eps, adagrad_init)
+        self.pairing_code = pairing_code(pairs)
+
+    def publish(self, learner):
+        """The keywords as the learner's public attributes (.loss, .optimizer, .adagrad_eps, .adagrad_init, .pairs) -> self."""
+        for name in ("loss", "optimizer", "adagrad_eps", "adagrad_init", "pairs"):
+            setattr(learner, name, getattr(self, name))
+        return self
+
+    def set_on(self, handle):
+        """fmhip_model_set_loss, _set_pairing, _set_optimizer (the same AdaGrad settings again keep the model's accumulators)."""
+        L = load()
+        check(L.fmhip_model_set_loss(handle, self.loss_code))
+        check(L.fmhip_model_set_pairing(handle, self.pairing_code))
+        check(L.fmhip_model_set_optimizer(handle, self.opt_code, self.adagrad_eps, self.adagrad_init))
+
+    def require_default(self):
+        """For a step engine that cannot set a rule: ValueError for every part that is not the default."""
+        if self.loss_code != LOSS_SQUARED:
+            raise ValueError("this engine trains the squared loss only")
+        if self.pairing_code != PAIRING_NONE:
+            raise ValueError("this engine trains on single rows only")
+        if self.opt_code != OPT_SGD:
+            raise ValueError("this engine trains with plain SGD only")
+
+
 class Stats(C.Structure):
     _fields_ = [("sse", C.c_double), ("sum_e", C.c_double), ("rows", C.c_int64), ("nnz", C.c_int64),
                 ("nonfinite", C.c_int64), ("steps", C.c_int64)]

@@ -229,7 +229,7 @@ int fmhip_model_set_loss(fmhip_model_t m, int loss) {
         return fail(FMHIP_ERR_INVALID, "loss %d: FMHIP_LOSS_SQUARED (0) or FMHIP_LOSS_LOGISTIC (1)", loss);
     WriteLock lock(m);
     if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
-    m->loss = loss;
+    m->rule.loss = loss;
     return FMHIP_OK;
 }
 
@@ -238,11 +238,9 @@ int fmhip_model_set_pairing(fmhip_model_t m, int pairing) {
         return fail(FMHIP_ERR_INVALID, "pairing %d: FMHIP_PAIRING_NONE (0) or FMHIP_PAIRING_ADJACENT (1)", pairing);
     WriteLock lock(m);
     if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
-    m->pairing = pairing;
+    m->rule.pairing = pairing;
     return FMHIP_OK;
 }
-
-static bool same_bits(double a, double b) { return memcmp(&a, &b, sizeof a) == 0; }
 
 int fmhip_model_set_optimizer(fmhip_model_t m, int optimizer, double eps, double initial_accumulator) {
     if (optimizer != FMHIP_OPT_SGD && optimizer != FMHIP_OPT_ADAGRAD)
@@ -255,17 +253,21 @@ int fmhip_model_set_optimizer(fmhip_model_t m, int optimizer, double eps, double
     if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
     TRY(set_device(m->device));
     if (optimizer == FMHIP_OPT_SGD) {
-        if (m->opt != FMHIP_OPT_SGD) HIP_TRY(hipStreamSynchronize(m->stream));    // no queued update may still use them
+        if (m->rule.adagrad()) HIP_TRY(hipStreamSynchronize(m->stream));    // no queued update may still use them
         m->NV.release();
         m->Nw.release();
         m->N0.release();
-        m->opt = FMHIP_OPT_SGD;
-        m->ada_eps = m->ada_init = 0.0;
+        m->rule.opt = FMHIP_OPT_SGD;
+        m->rule.ada_eps = m->rule.ada_init = 0.0;
         return FMHIP_OK;
     }
-    if (m->opt == FMHIP_OPT_ADAGRAD && same_bits(m->ada_eps, eps) && same_bits(m->ada_init, initial_accumulator)) return FMHIP_OK;
+    TrainRule want = m->rule;
+    want.opt = FMHIP_OPT_ADAGRAD;
+    want.ada_eps = eps;
+    want.ada_init = initial_accumulator;
+    if (m->rule == want) return FMHIP_OK;
     TRY(fold_scales(m));          // the AdaGrad kernels work on tables at scale 1
-    m->opt = FMHIP_OPT_SGD;       // (until the accumulators are in place)
+    m->rule.opt = FMHIP_OPT_SGD;  // (until the accumulators are in place)
     TRY(m->NV.ensure((size_t)m->n1p * m->Kp));
     if (m->pack_k() < 0) TRY(m->Nw.ensure((size_t)m->n1p));
     TRY(m->N0.ensure(1));
@@ -276,16 +278,14 @@ int fmhip_model_set_optimizer(fmhip_model_t m, int optimizer, double eps, double
     if (m->Nw.p) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->Nw.p), (int)bits, m->Nw.n, m->stream));
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->N0.p), (int)bits, 1, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
-    m->opt = FMHIP_OPT_ADAGRAD;
-    m->ada_eps = eps;
-    m->ada_init = initial_accumulator;
+    m->rule = want;
     return FMHIP_OK;
 }
 
 int fmhip_model_get_optimizer_state(fmhip_model_t m, double *n0, double *nw, double *nv) {
     ReadLock lock(m);
     if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
-    if (m->opt != FMHIP_OPT_ADAGRAD) return fail(FMHIP_ERR_INVALID, "the model has no optimizer state (fmhip_model_set_optimizer: FMHIP_OPT_ADAGRAD)");
+    if (!m->rule.adagrad()) return fail(FMHIP_ERR_INVALID, "the model has no optimizer state (fmhip_model_set_optimizer: FMHIP_OPT_ADAGRAD)");
     TRY(set_device(m->device));
     std::vector<float> hN((size_t)m->n1p * m->Kp), hw(m->Nw.p ? (size_t)m->n1p : 0);
     float h0 = 0.f;
@@ -305,7 +305,7 @@ int fmhip_model_get_optimizer_state(fmhip_model_t m, double *n0, double *nw, dou
 int fmhip_model_set_optimizer_state(fmhip_model_t m, double n0, const double *nw, const double *nv) {
     WriteLock lock(m);
     if (!m || !nw || !nv) return fail(FMHIP_ERR_INVALID, "NULL argument");
-    if (m->opt != FMHIP_OPT_ADAGRAD) return fail(FMHIP_ERR_INVALID, "the model has no optimizer state (fmhip_model_set_optimizer: FMHIP_OPT_ADAGRAD)");
+    if (!m->rule.adagrad()) return fail(FMHIP_ERR_INVALID, "the model has no optimizer state (fmhip_model_set_optimizer: FMHIP_OPT_ADAGRAD)");
     auto ok = [](double x) { return std::isfinite(x) && x >= 0.0; };
     if (!ok(n0)) return fail(FMHIP_ERR_INVALID, "accumulator of w0 is negative or not finite");
     for (int64_t i = 0; i < m->n1; ++i)
@@ -313,7 +313,7 @@ int fmhip_model_set_optimizer_state(fmhip_model_t m, double n0, const double *nw
     for (int64_t j = 0; j < m->n1 * m->k; ++j)
         if (!ok(nv[j])) return fail(FMHIP_ERR_INVALID, "accumulator nv[%lld] is negative or not finite", (long long)j);
     TRY(set_device(m->device));
-    const float init = (float)m->ada_init;     // padding: what set_optimizer filled in
+    const float init = (float)m->rule.ada_init;     // padding: what set_optimizer filled in
     std::vector<float> hN((size_t)m->n1p * m->Kp, init), hw(m->Nw.p ? (size_t)m->n1p : 0, init);
     for (int64_t i = 0; i < m->n1; ++i) {
         for (int f = 0; f < m->k; ++f) hN[(size_t)i * m->Kp + f] = (float)nv[f + i * (int64_t)m->k];
@@ -854,12 +854,7 @@ int fmhip_batch_grad(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, double *
 int fmhip_als_epoch(fmhip_model_t m, fmhip_dataset_t d, double reg0, double regw, double regv) {
     WriteLock lock(m);
     TRY(check_train(m, d));
-    if (m->loss != FMHIP_LOSS_SQUARED)
-        return fail(FMHIP_ERR_UNSUPPORTED, "ALS is derived for the squared loss: this model trains under the logistic loss "
-                                           "(fmhip_model_set_loss)");
-    if (m->pairing != FMHIP_PAIRING_NONE)
-        return fail(FMHIP_ERR_UNSUPPORTED, "ALS is derived for the squared loss of single rows: this model trains on pairs of rows "
-                                           "(fmhip_model_set_pairing)");
+    if (const char *why = refusal(Path::kAls, m->rule)) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
     if (d->batches.size() > 1 || (d->nnz > 0 && !d->val64.p))
         return fail(FMHIP_ERR_UNSUPPORTED, "ALS walks the whole-dataset transpose: create the dataset with batch_rows <= 0 "
                                            "(single batch, at most 2^27 stored nonzeros) and without asking for the dense hot "

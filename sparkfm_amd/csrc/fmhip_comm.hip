@@ -41,6 +41,7 @@
 #include <array>
 #include <cstring>
 #include <mutex>
+#include <optional>
 
 using namespace fmhip;
 using namespace fmhip::host;
@@ -298,10 +299,7 @@ struct fmhip_comm {
     // step passes or fails on every rank alike
     int64_t plan_max_rows = -1;
     int64_t plan_steps = 0;                   // ... and the largest batch count: the lock-step steps of an epoch
-    int plan_loss = -1;                       // ... and the models' loss (fmhip_model_set_loss; -1: no plan yet)
-    int plan_pairing = -1;                    // ... and pairing (fmhip_model_set_pairing), agreed in the same word as the loss
-    int plan_opt = -1;                        // ... and their optimizer with its settings (fmhip_model_set_optimizer; -1: no plan yet)
-    double plan_eps = 0.0, plan_init = 0.0;
+    std::optional<TrainRule> plan_rule;       // ... and the rule every rank's model trains under (empty: no plan yet)
 };
 
 namespace {
@@ -525,14 +523,20 @@ int control_i64(fmhip_model_t m, fmhip_comm_t c, int64_t *value, int count, bool
     return FMHIP_OK;
 }
 
-// The optimizer a step's collective-shaping checks go by: the one fmhip_dp_plan agreed over the ranks (a model changed since is
-// refused by local_checks and contributes zeros, but takes the same collectives as its peers), else the model's own
-int planned_opt(fmhip_model_t m, fmhip_comm_t c) { return c->plan_opt >= 0 ? c->plan_opt : m->opt; }
+// A value the ranks must hold alike, in two slots of a max-reduce: x and -x — afterwards max(x) == -max(-x) iff every rank put the same x
+void put_agree(int64_t *slot, int64_t x) { slot[0] = x, slot[1] = -x; }
+bool agreed(const int64_t *slot) { return slot[0] == -slot[1]; }
 
-const char *touched_decay_msg(int opt) {
-    return opt == FMHIP_OPT_ADAGRAD
-               ? "the touched-rows exchange under AdaGrad needs regw = regv = 0 (with decay every row moves: use the dense or pipelined exchange)"
-               : "the touched-rows exchange needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)";
+// The rule a step's collective-shaping checks go by: the one fmhip_dp_plan agreed over the ranks (a model changed since is
+// refused by local_checks and contributes zeros, but takes the same collectives as its peers), else the model's own
+const TrainRule &planned_rule(fmhip_model_t m, fmhip_comm_t c) { return c->plan_rule ? *c->plan_rule : m->rule; }
+
+// why the touched-rows exchange cannot take a step with this weight decay under the planned rule (nullptr: it can)
+const char *touched_refusal(fmhip_model_t m, fmhip_comm_t c, const Sgd &sgd) {
+    const TrainRule &r = planned_rule(m, c);
+    if (lazy_decay_ok(m, sgd, r)) return nullptr;
+    const char *why = refusal(Path::kTouchedDecay, r);
+    return why ? why : "the touched-rows exchange needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)";
 }
 
 // The plan of the touched-rows exchange (collective): for every position t < steps of the lock-step schedule, the union of the
@@ -668,8 +672,7 @@ int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
         return fail(FMHIP_ERR_INVALID, "the touched-rows exchange is not planned: call fmhip_dp_plan (every rank)");
     const bool foreign = c->msg_kp != m->Kp;
     if (foreign && live) return fail(FMHIP_ERR_INVALID, "the touched-rows exchange was planned for rows of %d floats, this model has %d", c->msg_kp, m->Kp);
-    if (!lazy_decay_ok(m, sgd, planned_opt(m, c)))
-        return fail(FMHIP_ERR_UNSUPPORTED, "%s", touched_decay_msg(planned_opt(m, c)));
+    if (const char *why = touched_refusal(m, c, sgd)) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
     const bool packed_dirty = m->grad_dirty;     // this step neither writes nor cleans the model's packed gradient
     const int64_t t = position >= 0 ? position : c->t_cursor;
     if (t >= (int64_t)c->tsteps.size())
@@ -885,9 +888,7 @@ inline int64_t shard_top(fmhip_model_t m, int W) { return fmhip::host::shard_top
 // place into V.  One writer per V row: the replicas are identical whatever order the transport sums in.
 int dp_step_sharded(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, const Sgd &sgd) {
     // (the plan's optimizer, agreed by every rank — a rank whose model changed since must not be the only one to stop)
-    if (planned_opt(m, c) == FMHIP_OPT_ADAGRAD)
-        return fail(FMHIP_ERR_UNSUPPORTED, "the sharded exchange does not support AdaGrad (each rank's accumulators would hold its own share "
-                                           "only): use the dense, pipelined or touched exchange");
+    if (const char *why = refusal(Path::kSharded, planned_rule(m, c))) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
     const bool live = batch >= 0;
     const int W = c->emu_ranks > 0 ? c->emu_ranks : c->world;        // shares per interval
     const int R = c->emu_ranks > 0 ? 0 : c->rank;                    // ... and which one is this rank's
@@ -958,17 +959,18 @@ int dp_step_sharded(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
 // collective: the caller runs the step with a zero contribution (as a rank that has run out of rows does) and
 // reports the error afterwards.
 int local_checks(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, bool in_schedule = true) {
-    if (c->plan_loss >= 0 && m->loss != c->plan_loss)
-        return fail(FMHIP_ERR_INVALID, "the plan was agreed for loss %d, this model now trains under loss %d (fmhip_model_set_loss): call "
-                                       "fmhip_dp_plan again (every rank)", c->plan_loss, m->loss);
-    if (c->plan_pairing >= 0 && m->pairing != c->plan_pairing)
-        return fail(FMHIP_ERR_INVALID, "the plan was agreed for pairing %d, this model now trains under pairing %d (fmhip_model_set_pairing): call "
-                                       "fmhip_dp_plan again (every rank)", c->plan_pairing, m->pairing);
-    if (c->plan_opt >= 0 && (m->opt != c->plan_opt || memcmp(&m->ada_eps, &c->plan_eps, sizeof(double)) != 0 ||
-                             memcmp(&m->ada_init, &c->plan_init, sizeof(double)) != 0))
+    if (c->plan_rule && !(m->rule == *c->plan_rule)) {
+        const TrainRule &p = *c->plan_rule, &r = m->rule;
+        auto changed = [](const char *what, int planned, int now) {
+            return fail(FMHIP_ERR_INVALID, "the plan was agreed for %s %d, this model now trains under %s %d (fmhip_model_set_%s): call "
+                                           "fmhip_dp_plan again (every rank)", what, planned, what, now, what);
+        };
+        if (r.loss != p.loss) return changed("loss", p.loss, r.loss);
+        if (r.pairing != p.pairing) return changed("pairing", p.pairing, r.pairing);
         return fail(FMHIP_ERR_INVALID, "the plan was agreed for optimizer %d (eps %g, initial accumulator %g), this model now trains under "
                                        "optimizer %d (eps %g, initial accumulator %g) (fmhip_model_set_optimizer): call fmhip_dp_plan again "
-                                       "(every rank)", c->plan_opt, c->plan_eps, c->plan_init, m->opt, m->ada_eps, m->ada_init);
+                                       "(every rank)", p.opt, p.ada_eps, p.ada_init, r.opt, r.ada_eps, r.ada_init);
+    }
     if (c->exchange == FMHIP_EXCHANGE_TOUCHED && !c->tsteps.empty() && c->msg_kp != m->Kp)
         return fail(FMHIP_ERR_INVALID, "the touched-rows exchange was planned for rows of %d floats, this model has %d: call fmhip_dp_plan "
                                        "with this model (every rank)", c->msg_kp, m->Kp);
@@ -1315,13 +1317,14 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     // its global row count travels as one fp32 sum, exact below 2^24 —, whether some rank's transposes are row-blocked
     // (it cannot cut its backward: then nobody does, same collectives everywhere), the touched-rows table's width, and
     // whether some rank cannot hold the sharded exchange's equal shares, and the models' loss and pairing in one word, loss + 2 * pairing
-    // in 0..3 (it and its complement to 3: the two maxima add up to 3 iff every rank holds the same word).  All ranks pass or fail together.
+    // (it and its negation, put_agree: every rank holds the same word iff agreed).  All ranks pass or fail together.
     // The last slot: whether some rank's model is not plain SGD — then (and only then: an SGD plan issues the collectives it
     // always did) a second max-reduce agrees the optimizer and the bit patterns of its settings.
     constexpr int kAgree = 8;
     static_assert(kAgree <= kMaxCuts + 1, "the plan's agreement vector travels in the communicator's scratch (kMaxCuts + 1 int64)");
-    const int64_t loss_word = m->loss + 2 * m->pairing;
-    int64_t agree[kAgree] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size(), loss_word, 3 - loss_word, m->opt != FMHIP_OPT_SGD};
+    const TrainRule &rule = m->rule;
+    int64_t agree[kAgree] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size(), 0, 0, rule.adagrad()};
+    put_agree(agree + 5, rule.loss + 2 * rule.pairing);
     for (const auto &bm : d->batches) {
         agree[0] = std::max<int64_t>(agree[0], bm.rows);
         agree[2] = std::max<int64_t>(agree[2], (int64_t)bm.n_cols + d->hot_pages * kHotT);
@@ -1331,28 +1334,29 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
         agree[3] = shard_top(m, W) > m->n1p + (m->grad == m->grad_own.p ? (int64_t)fmhip_model::kSlackRows : 0);
     TRY(control_i64(m, c, agree, kAgree, false));
     if (agree[7]) {
-        // each value and its negation (settings >= 0: their bit patterns are non-negative int64): equal on every rank iff max == -max(-x)
+        // the optimizer and the bit patterns of its settings (>= 0, so non-negative int64 whose negation exists)
         int64_t eb, ib;
-        memcpy(&eb, &m->ada_eps, sizeof eb);
-        memcpy(&ib, &m->ada_init, sizeof ib);
+        memcpy(&eb, &rule.ada_eps, sizeof eb);
+        memcpy(&ib, &rule.ada_init, sizeof ib);
         constexpr int kOpt = 7;
         static_assert(kOpt <= kMaxCuts + 1, "the optimizer's agreement vector travels in the communicator's scratch (kMaxCuts + 1 int64)");
-        int64_t o[kOpt] = {m->opt, -m->opt, eb, -eb, ib, -ib, c->exchange == FMHIP_EXCHANGE_SHARDED && m->opt == FMHIP_OPT_ADAGRAD};
+        int64_t o[kOpt] = {0, 0, 0, 0, 0, 0, c->exchange == FMHIP_EXCHANGE_SHARDED && refusal(Path::kSharded, rule)};
+        put_agree(o, rule.opt);
+        put_agree(o + 2, eb);
+        put_agree(o + 4, ib);
         TRY(control_i64(m, c, o, kOpt, false));
-        if (o[0] != -o[1] || o[2] != -o[3] || o[4] != -o[5])
+        if (!agreed(o) || !agreed(o + 2) || !agreed(o + 4))
             return fail(FMHIP_ERR_INVALID, "the ranks' models train under different optimizers or optimizer settings (fmhip_model_set_optimizer): "
                                            "set the same optimizer, eps and initial accumulator on every rank");
-        if (o[6])
-            return fail(FMHIP_ERR_UNSUPPORTED, "the sharded exchange does not support AdaGrad (each rank's accumulators would hold its own share "
-                                               "only): use the dense, pipelined or touched exchange");
+        // (agreed above: every rank holds the optimizer of the rank that raised the slot, so every rank refuses here or none does)
+        if (o[6]) return fail(FMHIP_ERR_UNSUPPORTED, "%s", refusal(Path::kSharded, rule));
     }
-    if (agree[5] + agree[6] != 3)
+    if (!agreed(agree + 5))
         return fail(FMHIP_ERR_INVALID, "the ranks' models train under different losses (fmhip_model_set_loss) or pairings (fmhip_model_set_pairing): "
                                        "set the same loss and the same pairing on every rank");
     // (agreed above: every rank holds the same pairing, so every rank refuses here or none does)
-    if (m->pairing != FMHIP_PAIRING_NONE && c->exchange == FMHIP_EXCHANGE_PIPELINED)
-        return fail(FMHIP_ERR_UNSUPPORTED, "the pipelined exchange runs the two-pass forward, which does not form pair residuals "
-                                           "(fmhip_model_set_pairing): use the dense, sharded or touched exchange");
+    if (const char *why = c->exchange == FMHIP_EXCHANGE_PIPELINED ? refusal(Path::kPipelined, rule) : nullptr)
+        return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
     if ((double)agree[0] * c->world >= 16777216.0)
         return fail(FMHIP_ERR_INVALID, "a global batch of %lld x %d rows exceeds 2^24 (the summed row count travels as one fp32 word): "
                                        "use smaller batches", (long long)agree[0], c->world);
@@ -1361,11 +1365,7 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
                                            "gradient buffer, fmhip_grad_bind, needs n+1 to be a multiple of world)", (long long)m->n1, W);
     c->plan_max_rows = agree[0];
     c->plan_steps = agree[4];
-    c->plan_loss = m->loss;
-    c->plan_pairing = m->pairing;
-    c->plan_opt = m->opt;
-    c->plan_eps = m->ada_eps;
-    c->plan_init = m->ada_init;
+    c->plan_rule = rule;
     const int64_t blocked = agree[1];
     if (c->exchange == FMHIP_EXCHANGE_TOUCHED && blocked)
         return fail(FMHIP_ERR_UNSUPPORTED, "the touched-rows exchange needs transposes without row blocks (some rank's dataset has them)");
@@ -1440,13 +1440,14 @@ static int dp_epoch(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const Sg
     static_assert(kAgree <= kMaxCuts + 1, "the epoch's agreement vector travels in the communicator's scratch (kMaxCuts + 1 int64)");
     int64_t agree[kAgree] = {nb, 0, order ? n_order : -1, order ? -n_order : 1, order_bad, order_hash, -order_hash};
     for (int64_t j = 0; j < nb && !agree[1]; ++j) agree[1] = local_checks(m, d, j, c, false) != FMHIP_OK;
-    if (!agree[1] && c->exchange == FMHIP_EXCHANGE_TOUCHED && !lazy_decay_ok(m, sgd, planned_opt(m, c))) {
-        agree[1] = 1;
-        (void)fail(FMHIP_ERR_UNSUPPORTED, "%s", touched_decay_msg(planned_opt(m, c)));
-    }
-    if (!agree[1] && c->exchange == FMHIP_EXCHANGE_SHARDED && planned_opt(m, c) == FMHIP_OPT_ADAGRAD) {
-        agree[1] = 1;
-        (void)fail(FMHIP_ERR_UNSUPPORTED, "the sharded exchange does not support AdaGrad: use the dense, pipelined or touched exchange");
+    if (!agree[1]) {
+        const char *why = c->exchange == FMHIP_EXCHANGE_TOUCHED   ? touched_refusal(m, c, sgd)
+                          : c->exchange == FMHIP_EXCHANGE_SHARDED ? refusal(Path::kSharded, planned_rule(m, c))
+                                                                  : nullptr;
+        if (why) {
+            agree[1] = 1;
+            (void)fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
+        }
     }
     const std::string why = agree[1] ? fmhip_last_error() : "";
     TRY(control_i64(m, c, agree, kAgree, false));

@@ -10,6 +10,7 @@
 
 #include <cstdarg>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -97,6 +98,57 @@ struct GradView {
     const int32_t *cdst;       // per compressed column of the batch: its row in GV / Gw / Gb
     const int32_t *hot_pos;    // per slot of the dense hot block: its row (-1 = unused slot)
 };
+
+// How a model trains, as ONE value: the residual every training path forms (enum fmhip_loss), whether rows 2j / 2j+1 of a
+// batch are one example with the loss applied to their difference (enum fmhip_pairing; fm_pairing.h — the training forward
+// then runs in two launches and keeps the rows' predictions in yhat), and the update rule with its settings (enum
+// fmhip_optimizer).  The three setters of the C ABI write it, fmhip_dp_plan agrees it over the ranks and keeps a copy, a
+// step compares the model's with the plan's; a path that cannot train under a rule says so through refusal().
+struct TrainRule {
+    int loss = FMHIP_LOSS_SQUARED;
+    int pairing = FMHIP_PAIRING_NONE;
+    int opt = FMHIP_OPT_SGD;
+    double ada_eps = 0.0, ada_init = 0.0;
+    bool adagrad() const { return opt == FMHIP_OPT_ADAGRAD; }
+    bool paired() const { return pairing != FMHIP_PAIRING_NONE; }
+    // the settings by bit pattern (what the ranks agree on is their bits, and -0.0 or a NaN must not compare by value)
+    bool same_optimizer(const TrainRule &o) const {
+        return opt == o.opt && memcmp(&ada_eps, &o.ada_eps, sizeof ada_eps) == 0 && memcmp(&ada_init, &o.ada_init, sizeof ada_init) == 0;
+    }
+    bool operator==(const TrainRule &o) const { return loss == o.loss && pairing == o.pairing && same_optimizer(o); }
+};
+
+// The training paths that refuse some rule, and the sentence each (path, rule) pair is refused with — nullptr: the path trains
+// under the rule.  The error code is FMHIP_ERR_UNSUPPORTED everywhere.  kTouchedDecay is the touched-rows exchange on a step WITH
+// weight decay (without, it takes every rule).  ALS is derived for the default loss and pairing only.
+enum class Path { kSharded, kTouchedDecay, kPipelined, kTwoPass, kAls };
+inline const char *refusal(Path p, const TrainRule &r) {
+    switch (p) {
+        case Path::kSharded:
+            return !r.adagrad() ? nullptr
+                                : "the sharded exchange does not support AdaGrad (each rank's accumulators would hold its own share "
+                                  "only): use the dense, pipelined or touched exchange";
+        case Path::kTouchedDecay:
+            return !r.adagrad() ? nullptr
+                                : "the touched-rows exchange under AdaGrad needs regw = regv = 0 (with decay every row moves: use the "
+                                  "dense or pipelined exchange)";
+        case Path::kPipelined:
+            return !r.paired() ? nullptr
+                               : "the pipelined exchange runs the two-pass forward, which does not form pair residuals "
+                                 "(fmhip_model_set_pairing): use the dense, sharded or touched exchange";
+        case Path::kTwoPass:
+            return !r.paired() ? nullptr
+                               : "the two-pass forward does not form pair residuals (fmhip_model_set_pairing): use fmhip_step_forward, "
+                                 "and the dense, sharded or touched exchange";
+        case Path::kAls:
+            if (r.loss != FMHIP_LOSS_SQUARED)
+                return "ALS is derived for the squared loss: this model trains under the logistic loss (fmhip_model_set_loss)";
+            return !r.paired() ? nullptr
+                               : "ALS is derived for the squared loss of single rows: this model trains on pairs of rows "
+                                 "(fmhip_model_set_pairing)";
+    }
+    return nullptr;
+}
 
 struct ProfRec {
     int kind;
@@ -221,16 +273,11 @@ struct fmhip_model {
     // exactly 1 unless rows-only updates with decay are pending.  Tracked in fp64 on the host, so the
     // scale itself accumulates no fp32 rounding from step to step.
     double sv = 1.0, sw = 1.0;
-    int loss = FMHIP_LOSS_SQUARED;   // enum fmhip_loss: the residual every training path forms (fmhip_model_set_loss)
-    // enum fmhip_pairing (fmhip_model_set_pairing).  ADJACENT: rows 2j / 2j+1 of a batch are one example, the loss is applied to
-    // their difference (fm_pairing.h); the training forward then runs in two launches and keeps the rows' predictions in yhat
-    int pairing = FMHIP_PAIRING_NONE;
+    fmhip::host::TrainRule rule;  // how the model trains (the three fmhip_model_set_* calls)
     DevBuf<float> yhat;           // paired training forward: [max_rows] predictions between its two launches
-    // enum fmhip_optimizer (fmhip_model_set_optimizer).  AdaGrad: per-coordinate accumulators shaped like the parameters —
-    // NV [n1p][Kp] like V (packed rows: slot pack_k holds w_i's), Nw [n1p] (unpacked rows only), N0 [1] — one more copy of
-    // the model (8.6 GB at 2^25 x 64); the tables stay at scale 1 (sv = sw = 1) while it is set
-    int opt = FMHIP_OPT_SGD;
-    double ada_eps = 0.0, ada_init = 0.0;
+    // AdaGrad: per-coordinate accumulators shaped like the parameters — NV [n1p][Kp] like V (packed rows: slot pack_k holds
+    // w_i's), Nw [n1p] (unpacked rows only), N0 [1] — one more copy of the model (8.6 GB at 2^25 x 64); the tables stay at
+    // scale 1 (sv = sw = 1) while it is set
     DevBuf<float> NV, Nw, N0;
     int64_t bw_next_hi = -1;      // feature-chunked backward: the next interval must end here (-1: none pending)
     bool bw_up = false;           // ... ascending intervals instead (the next one must START here)
@@ -332,8 +379,8 @@ int step_apply_shard(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, int6
 int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t n_feat, const float *rows, const GradView *view = nullptr,
                     int64_t off = 0, bool last = true);
 // can the update of this step leave rows without a gradient alone (weight decay rides in the tables' scale, or there is
-// none)?  Under AdaGrad only without decay (`opt`: the optimizer to judge by; -1 = the model's own)
-bool lazy_decay_ok(fmhip_model_t m, const Sgd &s, int opt = -1);
+// none)?  Under AdaGrad only without decay (`r`: the rule to judge by — the model's own, or the one a plan agreed)
+bool lazy_decay_ok(fmhip_model_t m, const Sgd &s, const TrainRule &r);
 int read_scal(fmhip_model_t m, fmhip_stats *st);
 
 }  // namespace host

@@ -72,7 +72,7 @@ int check_train(fmhip_model_t m, fmhip_dataset_t d) {
     TRY(check_pair(m, d));
     if (d->scoring_only)
         return fail(FMHIP_ERR_UNSUPPORTED, "dataset was created with fmhip_rows_create (scoring only): it has no transposes to train on");
-    if (m->pairing != FMHIP_PAIRING_NONE) TRY(check_even_batches(d));
+    if (m->rule.paired()) TRY(check_even_batches(d));
     return FMHIP_OK;
 }
 
@@ -99,7 +99,7 @@ int check_batch(fmhip_dataset_t d, int64_t batch) {
 int ensure_workspace(fmhip_model_t m, fmhip_dataset_t d) {
     TRY(m->P.ensure((size_t)std::max<int64_t>(d->max_rows, 1) * m->Kp));
     TRY(m->e.ensure((size_t)std::max<int64_t>(d->max_rows, 1)));
-    if (m->pairing != FMHIP_PAIRING_NONE) TRY(m->yhat.ensure((size_t)std::max<int64_t>(d->max_rows, 2)));
+    if (m->rule.paired()) TRY(m->yhat.ensure((size_t)std::max<int64_t>(d->max_rows, 2)));
     TRY(m->part.ensure((size_t)std::max<int32_t>(d->max_ranges, 1) * 2 * (m->Kp + kPartPad)));
     TRY(m->pieces.ensure((size_t)std::max<int32_t>(d->max_pieces, 1) * (m->Kp + kPartPad)));
     TRY(m->bsum.ensure((size_t)kMaxFwdBlocks * 4));
@@ -138,7 +138,7 @@ FwdArgs fwd_args(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm) {
     a.xhot = d->hot_T ? d->xhot.p + (size_t)bm.row0 * kHotT : nullptr;
     a.hot_ids = d->d_hot_ids.p;
     a.bsum = m->bsum.p;
-    a.loss = m->loss;
+    a.loss = m->rule.loss;
     {
         // LDS V-tile size: as many hot rows as fit 128 KiB (+ their w), capped by the model
         int64_t t = (128 * 1024) / ((int64_t)m->Kp * 4);
@@ -217,13 +217,13 @@ static ApplyArgs apply_args(fmhip_model_t m, const Sgd &s, const float *rows) {
     a.eta_v = a.eta_w = a.eta;
     a.sv_in = (float)m->sv;
     a.sw_in = (float)m->sw;
-    if (m->opt == FMHIP_OPT_ADAGRAD) {
+    if (m->rule.adagrad()) {
         // set_optimizer folded the scale and AdaGrad never takes the lazy-decay path: the AdaGrad kernels assume scale 1
         assert(m->sv == 1.0 && m->sw == 1.0);
         a.NV = m->NV.p;
         a.Nw = m->Nw.p;
         a.N0 = m->N0.p;
-        a.eps = (float)m->ada_eps;
+        a.eps = (float)m->rule.ada_eps;
     }
     return a;
 }
@@ -236,7 +236,7 @@ int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
         HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
         m->grad_dirty = false;
     }
-    if (m->pairing == FMHIP_PAIRING_ADJACENT) {
+    if (m->rule.paired()) {
         // two launches: the q-mode forward — every existing kernel choice (hot pages, packed rows, row order, address mode) as it
         // is, P = sv*q and the predictions beside it — then the pairs' finish (fm_pairing.hip): P rows times +-g, e, the statistics
         // partials (its own block count: the backward's finish sums m->fwd_parts of them)
@@ -256,7 +256,7 @@ int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
         pa.bsum = m->bsum.p;
         pa.n_pairs = (int32_t)(bm.rows / 2);
         pa.pack_k = m->pack_k();
-        pa.loss = m->loss;
+        pa.loss = m->rule.loss;
         HIP_TRY(launch_pair_finish(m->Kp, pa, m->stream, &m->fwd_parts));
     } else {
         ProfScope ps(m, FMHIP_K_FORWARD, bm.nnz_total, bm.rows);
@@ -276,9 +276,7 @@ int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
 // step_forward.  A then B = the forward, up to the order of the fp32 sums (A's terms first).
 int step_forward_pass(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int pass) {
     const BatchMeta &bm = d->batches[(size_t)b];
-    if (m->pairing != FMHIP_PAIRING_NONE)
-        return fail(FMHIP_ERR_UNSUPPORTED, "the two-pass forward does not form pair residuals (fmhip_model_set_pairing): use fmhip_step_forward, "
-                                           "and the dense, sharded or touched exchange");
+    if (const char *why = refusal(Path::kTwoPass, m->rule)) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
     if (d->split_cut < 0) return fail(FMHIP_ERR_INVALID, "the dataset's rows are not partitioned (fmhip_dataset_partition_rows)");
     if (m->Kp > 64) return fail(FMHIP_ERR_UNSUPPORTED, "the two-pass forward serves models of up to 64 padded factors (this one: %d)", m->Kp);
     TRY(ensure_workspace(m, d));
@@ -466,9 +464,9 @@ int step_compute(fmhip_model_t m, fmhip_dataset_t d, int64_t b, double *acc, con
 
 // can weight decay ride in the tables' scale for this step?  (no decay at all: trivially)
 // AdaGrad: only then — with decay every row moves (its accumulator too), which no scale can express: the dense pass
-bool lazy_decay_ok(fmhip_model_t m, const Sgd &s, int opt) {
+bool lazy_decay_ok(fmhip_model_t m, const Sgd &s, const TrainRule &r) {
     if (s.regw == 0.0 && s.regv == 0.0) return true;
-    if ((opt < 0 ? m->opt : opt) == FMHIP_OPT_ADAGRAD) return false;
+    if (r.adagrad()) return false;
     const double dv = s.dv(), dw = s.dw();
     return m->tv(kTuneLazy) && dv >= 0.5 && dw >= 0.5 && dv <= 1.0 && dw <= 1.0;
 }
@@ -483,8 +481,8 @@ static bool few_rows(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm) {
 // rows-only update, so weight decay must be expressible through the tables' scale (lazy decay, fm_apply.hip).
 // Both forms are SGD's: under AdaGrad the update is a launch of its own (k_apply / k_apply_rows).
 bool plan_fused(fmhip_model_t m, fmhip_dataset_t d, int64_t b, const Sgd &s, FusedPlan *p) {
-    if (m->opt != FMHIP_OPT_SGD) return false;
-    const bool lazy_ok = lazy_decay_ok(m, s);
+    if (m->rule.adagrad()) return false;
+    const bool lazy_ok = lazy_decay_ok(m, s, m->rule);
     const BatchMeta &bm0 = d->batches[(size_t)b];
     p->sgd = s;
     {
@@ -543,7 +541,7 @@ int finish_fused(fmhip_model_t m, const FusedPlan &p) { return close_step(m, p.s
 int step_apply(fmhip_model_t m, const Sgd &s, fmhip_dataset_t d, int64_t b) {
     ApplyArgs a = apply_args(m, s, m->scal() + 2);
     double sv_out = 1.0, sw_out = 1.0;
-    if (d && b >= 0 && d->rb_rows == 0 && lazy_decay_ok(m, s) && few_rows(m, d, d->batches[(size_t)b])) {
+    if (d && b >= 0 && d->rb_rows == 0 && lazy_decay_ok(m, s, m->rule) && few_rows(m, d, d->batches[(size_t)b])) {
         const BatchMeta &bm = d->batches[(size_t)b];
         a.rows_only = 1;
         a.feat = d->cfeat.p + bm.col_off;
@@ -603,10 +601,10 @@ int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t 
                     bool last) {
     // (judged as SGD: the touched-rows exchange refuses AdaGrad with decay up front, by the plan's optimizer, on every rank alike —
     // a rank whose optimizer changed since the plan must not stop halfway through the step's collectives)
-    if (!lazy_decay_ok(m, s, FMHIP_OPT_SGD))
+    if (!lazy_decay_ok(m, s, TrainRule{}))
         return fail(FMHIP_ERR_UNSUPPORTED, "a rows-only update needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)");
     // every slice of a step starts from the scale the step began with (m->sv / m->sw move with the LAST slice only)
-    const bool ada = m->opt == FMHIP_OPT_ADAGRAD;      // (its tables stay at scale 1)
+    const bool ada = m->rule.adagrad();      // (its tables stay at scale 1)
     const double sv_out = ada ? 1.0 : m->sv * s.dv(), sw_out = ada ? 1.0 : m->sw * s.dw();
     ApplyArgs a = apply_args(m, s, rows);
     a.rows_only = 1;

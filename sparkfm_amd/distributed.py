@@ -50,17 +50,9 @@ class HipEngine:
         self.row_floats, self.gv_offset = int(rf.value), int(gv.value)
         self.n1 = fm.num_attribute + 1
 
-    def set_loss(self, loss):
-        """enum fmhip_loss: the loss the model's steps train under (fmhip_model_set_loss)."""
-        _ffi.check(self.L.fmhip_model_set_loss(self.fm.handle, loss))
-
-    def set_pairing(self, pairing):
-        """enum fmhip_pairing: whether the model's steps train on pairs of adjacent rows (fmhip_model_set_pairing)."""
-        _ffi.check(self.L.fmhip_model_set_pairing(self.fm.handle, pairing))
-
-    def set_optimizer(self, optimizer, eps, init):
-        """enum fmhip_optimizer and its settings: the update rule of the model's steps (fmhip_model_set_optimizer)."""
-        _ffi.check(self.L.fmhip_model_set_optimizer(self.fm.handle, optimizer, eps, init))
+    def set_rule(self, rule):
+        """_ffi.TrainRule: the loss, pairing and optimizer the model's steps train under."""
+        rule.set_on(self.fm.handle)
 
     def forward(self, batch):
         _ffi.check(self.L.fmhip_step_forward(self.fm.handle, self.dataset.handle, batch))
@@ -134,13 +126,9 @@ class DataParallelSGD(FMLearn):
                  always_reduce=False, overlap=True, cuts=None, loss="squared", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1,
                  pairs=False):
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
-        self.pairs = pairs                   # True: pairs of adjacent rows are the examples (HipSGD): likewise set before every step
-        self._pairing = _ffi.pairing_code(pairs)
-        self.loss = loss                     # "squared" | "logistic" (HipSGD): set through the engine before every step
-        self._loss = _ffi.loss_code(loss)
-        self.optimizer = optimizer           # "sgd" | "adagrad" (HipSGD): likewise; every rank's accumulators see the same summed gradient
-        self._opt = _ffi.optimizer_code(optimizer)
-        self.adagrad_eps, self.adagrad_init = _ffi.adagrad_settings(adagrad_eps, adagrad_init)
+        # loss, optimizer, pairs as HipSGD's: set through the engine before every step (every rank's AdaGrad accumulators see the
+        # same summed gradient)
+        self.rule = _ffi.TrainRule(loss, optimizer, adagrad_eps, adagrad_init, pairs).publish(self)
         self.group = group
         self.engine_factory = engine_factory
         self.always_reduce = always_reduce   # run the collective even in a 1-rank group (self-test)
@@ -198,18 +186,10 @@ class DataParallelSGD(FMLearn):
 
     def step(self, eng, j):
         import torch.distributed as dist
-        if hasattr(eng, "set_loss"):
-            eng.set_loss(self._loss)
-        elif self._loss != _ffi.LOSS_SQUARED:
-            raise ValueError("this engine trains the squared loss only")
-        if hasattr(eng, "set_pairing"):
-            eng.set_pairing(self._pairing)
-        elif self._pairing != _ffi.PAIRING_NONE:
-            raise ValueError("this engine trains on single rows only")
-        if hasattr(eng, "set_optimizer"):
-            eng.set_optimizer(self._opt, self.adagrad_eps, self.adagrad_init)
-        elif self._opt != _ffi.OPT_SGD:
-            raise ValueError("this engine trains with plain SGD only")
+        if hasattr(eng, "set_rule"):
+            eng.set_rule(self.rule)
+        else:
+            self.rule.require_default()
         live = j < eng.n_batches
         if not (self._collective() and self.overlap and hasattr(eng, "backward")):
             if live:
@@ -498,18 +478,11 @@ class HipDataParallelSGD(FMLearn):
     def __init__(self, comm, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, upper_fractions=(0.05, 0.15, 0.3, 0.55), exchange="dense",
                  loss="squared", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1, pairs=False):
         self.comm = comm
-        # True: pairs of adjacent rows are the examples (HipSGD): set with the loss; every rank's shard needs even batches, and
-        # the pipelined exchange refuses it
-        self.pairs = pairs
-        self._pairing = _ffi.pairing_code(pairs)
+        # loss, optimizer, pairs as HipSGD's: set on the model before the plan (which agrees them over the ranks) and every step.
+        # Pairs need even batches in every rank's shard and are refused by the pipelined exchange; AdaGrad is refused by the
+        # sharded exchange, and by the touched one with decay
+        self.rule = _ffi.TrainRule(loss, optimizer, adagrad_eps, adagrad_init, pairs).publish(self)
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
-        # "squared" | "logistic" (HipSGD): set on the model before the plan (which agrees it over the ranks) and every step
-        self.loss = loss
-        self._loss = _ffi.loss_code(loss)
-        # "sgd" | "adagrad" (HipSGD) and its settings: likewise (the sharded exchange refuses AdaGrad, the touched one with decay)
-        self.optimizer = optimizer
-        self._opt = _ffi.optimizer_code(optimizer)
-        self.adagrad_eps, self.adagrad_init = _ffi.adagrad_settings(adagrad_eps, adagrad_init)
         self.upper_fractions = tuple(float(f) for f in upper_fractions)
         # "dense": the whole packed gradient all-reduced in overlapped slices, every rank updates every row; "sharded": the
         # slices reduce-scattered, every rank updates its 1/world share, the updated rows all-gathered; "touched": only the
@@ -528,16 +501,10 @@ class HipDataParallelSGD(FMLearn):
         self.exchange = exchange
         self._planned_for = None
 
-    def _set_loss(self, fm):
-        """The model's loss, pairing and optimizer (the same AdaGrad settings again keep its accumulators)."""
-        _ffi.check(_ffi.load().fmhip_model_set_loss(fm.handle, self._loss))
-        _ffi.check(_ffi.load().fmhip_model_set_pairing(fm.handle, self._pairing))
-        _ffi.check(_ffi.load().fmhip_model_set_optimizer(fm.handle, self._opt, self.adagrad_eps, self.adagrad_init))
-
     def plan(self, fm, dataset):
         """Collective: rank 0's data pick the cuts, every rank receives them (and agrees the models' loss and optimizer)."""
         import numpy as np
-        self._set_loss(fm)
+        self.rule.set_on(fm.handle)
         fr = np.ascontiguousarray(sorted(self.upper_fractions), np.float64)
         cuts = np.zeros(max(len(fr), 1), np.int64)
         _ffi.check(_ffi.load().fmhip_dp_plan(fm.handle, dataset.handle, self.comm.handle, len(fr), _ffi.ptr(fr), _ffi.ptr(cuts)))
@@ -559,7 +526,7 @@ class HipDataParallelSGD(FMLearn):
 
     def step(self, fm, dataset, batch):
         """One global step, the next of the schedule; batch < 0: this rank contributes zeros."""
-        self._set_loss(fm)
+        self.rule.set_on(fm.handle)
         if self._planned_for != id(dataset):
             self.plan(fm, dataset)
         _ffi.check(_ffi.load().fmhip_dp_step(fm.handle, dataset.handle, batch, self.comm.handle, self.eta, self.reg0,
@@ -569,7 +536,7 @@ class HipDataParallelSGD(FMLearn):
     def step_at(self, fm, dataset, position):
         """One global step at a position of the lock-step schedule that EVERY rank names alike (this rank's batch
         `position`, or zeros if it has fewer): the call of a permuted epoch."""
-        self._set_loss(fm)
+        self.rule.set_on(fm.handle)
         if self._planned_for != id(dataset):
             self.plan(fm, dataset)
         _ffi.check(_ffi.load().fmhip_dp_step_at(fm.handle, dataset.handle, position, self.comm.handle, self.eta, self.reg0,
@@ -581,7 +548,7 @@ class HipDataParallelSGD(FMLearn):
         fmhip_dp_steps): what the pipelined exchange needs to overlap each step's last slice with the next position's forward —
         in the other modes the same as step_at per position."""
         import numpy as np
-        self._set_loss(fm)
+        self.rule.set_on(fm.handle)
         if self._planned_for != id(dataset):
             self.plan(fm, dataset)
         pos = np.ascontiguousarray(positions, np.int64)
@@ -593,7 +560,7 @@ class HipDataParallelSGD(FMLearn):
         """One data-parallel epoch; `order`: a permutation of range(plan_steps()), the same on every rank
         (e.g. numpy's default_rng(shuffle_seed + epoch).permutation(steps)); None = ascending."""
         import numpy as np
-        self._set_loss(fm)
+        self.rule.set_on(fm.handle)
         if self._planned_for != id(dataset):
             self.plan(fm, dataset)
         st = _ffi.Stats()

@@ -39,13 +39,7 @@ class HipSGD(FMLearn):
     def __init__(self, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, shuffle_seed=None, loss="squared", optimizer="sgd",
                  adagrad_eps=1e-10, adagrad_init=0.1, pairs=False):
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
-        self.loss = loss
-        self._loss = _ffi.loss_code(loss)
-        self.optimizer = optimizer
-        self._opt = _ffi.optimizer_code(optimizer)
-        self.adagrad_eps, self.adagrad_init = _ffi.adagrad_settings(adagrad_eps, adagrad_init)
-        self.pairs = pairs
-        self._pairing = _ffi.pairing_code(pairs)
+        self.rule = _ffi.TrainRule(loss, optimizer, adagrad_eps, adagrad_init, pairs).publish(self)
         self.shuffle_seed = shuffle_seed
         self._epoch = 0
         self.last_stats = None
@@ -61,17 +55,11 @@ class HipSGD(FMLearn):
         rng = np.random.Generator(np.random.PCG64([self.shuffle_seed, self._epoch]))
         return rng.permutation(n_batches).astype(np.int64)
 
-    def _set_rule(self, fm):
-        L = _ffi.load()
-        _ffi.check(L.fmhip_model_set_loss(fm.handle, self._loss))
-        _ffi.check(L.fmhip_model_set_pairing(fm.handle, self._pairing))
-        _ffi.check(L.fmhip_model_set_optimizer(fm.handle, self._opt, self.adagrad_eps, self.adagrad_init))
-
     def learn(self, fm, dataset):
         L = _ffi.load()
         order = self.batch_order(dataset.n_batches)
         st = _ffi.Stats()
-        self._set_rule(fm)
+        self.rule.set_on(fm.handle)
         _ffi.check(L.fmhip_sgd_epoch(fm.handle, dataset.handle, self.eta, self.reg0, self.regw, self.regv,
                                      _ffi.ptr(order), C.byref(st)))
         fm._device_updated()
@@ -82,7 +70,7 @@ class HipSGD(FMLearn):
     def step(self, fm, dataset, batch, want_stats=True):
         """A single mini-batch step (fmhip_sgd_step)."""
         st = _ffi.Stats()
-        self._set_rule(fm)
+        self.rule.set_on(fm.handle)
         _ffi.check(_ffi.load().fmhip_sgd_step(fm.handle, dataset.handle, batch, self.eta, self.reg0, self.regw,
                                               self.regv, C.byref(st) if want_stats else None))
         fm._device_updated()

@@ -1,5 +1,5 @@
 """AdaGrad on every SGD training path (fmhip_model_set_optimizer, FMHIP_OPT_ADAGRAD): one step and epochs against the fp64
-reference of adagrad_ref.py (oracle.batch_grad + the rule in numpy), switches that must not change the result, the
+reference of train_ref.py (oracle.batch_grad + the rule in numpy), switches that must not change the result, the
 accumulators' lifecycle, the data-parallel exchanges with thread ranks, and the public learners.
 
 Every comparison against fp64 starts the accumulators above zero (initial_accumulator 0.1): with 0 the first step is
@@ -11,9 +11,10 @@ import subprocess
 import numpy as np
 import pytest
 
-import adagrad_ref as ref
+import train_ref as ref
 from helpers import random_problem
 from test_gpu_parity import TOL_G
+from train_ref import DP_FRACTIONS, DP_ROWS, dp_init, dp_shard, make, rel, same
 
 pytestmark = pytest.mark.gpu
 
@@ -52,24 +53,11 @@ def set_state(fm, n0, nw, nv):
     _ffi.check(L().fmhip_model_set_optimizer_state(fm.handle, n0, _ffi.ptr(np.ascontiguousarray(nw, np.float64)), _ffi.ptr(flat)))
 
 
-def make(fmhip, a, batch_rows=0, loss="squared"):
-    from sparkfm_amd import _ffi
-    ds = fmhip.DataSet(a["row_ptr"], a["col"], a["val"], a["y"], batch_rows=batch_rows).cache()
-    fm = fmhip.FMModel(a["n1"] - 1, a["k"])
-    fm.w0, fm.w, fm.v = a["w0"], a["w"], a["v"]
-    _ffi.check(L().fmhip_model_set_loss(fm.handle, _ffi.loss_code(loss)))
-    return ds, fm
-
-
 def problem(seed, n_rows, n1, k, lo, hi, loss):
     a = random_problem(seed, n_rows, n1, k, lo, hi)
     if loss == "logistic":
         a["y"] = (np.random.default_rng(seed + 1).random(n_rows) < 0.4).astype(np.float64)
     return a
-
-
-def rel(x, y):
-    return float(np.linalg.norm(np.asarray(x) - y) / max(np.linalg.norm(y), 1e-30))
 
 
 def rowtol(d_ref, floor_rel=1e-3):
@@ -119,7 +107,7 @@ def test_one_step_vs_reference(fmhip, k, loss, path):
     ds, fm = make(fmhip, a, batch_rows=0, loss=loss)
     set_opt(fm, init=init)
     s0 = ref.State(a["w0"], a["w"], a["v"], init)
-    s1 = ref.step(s0.copy(), a["row_ptr"], a["col"], a["val"], a["y"], 0, len(a["y"]), eta, *regs, EPS, loss)
+    s1 = ref.step(s0.copy(), a["row_ptr"], a["col"], a["val"], a["y"], 0, len(a["y"]), eta, *regs, ref.Rule(loss, False, EPS))
     fmhip.HipSGD(eta=eta, reg0=regs[0], regw=regs[1], regv=regs[2], loss=loss, optimizer="adagrad", adagrad_init=init).step(fm, ds, 0)
     check_step(fm, s0, s1, init, eta)
     if path == "rows":
@@ -146,7 +134,7 @@ def test_epochs_vs_reference(fmhip, k, loss, regs):
     for _ in range(2):
         orders.append(sgd.batch_order(ds.n_batches).tolist())
         sgd.learn(fm, ds)
-    s = ref.epochs(ref.State(a["w0"], a["w"], a["v"], 0.1), a, 200, orders, 0.05, *regs, EPS, loss)
+    s = ref.epochs(ref.State(a["w0"], a["w"], a["v"], 0.1), a, 200, orders, 0.05, *regs, ref.Rule(loss, False, EPS))
     n0, nw, nv = get_state(fm)
     assert rel(fm.v, s.v) <= 1e-5 and rel(fm.w, s.w) <= 1e-5, (rel(fm.v, s.v), rel(fm.w, s.w))
     assert rel(nv, s.nv) <= 1e-5 and rel(nw, s.nw) <= 1e-5, (rel(nv, s.nv), rel(nw, s.nw))
@@ -170,10 +158,6 @@ def train_bits(fmhip, a, regs, tune, init=0.0, epochs=2):
     ds.unpersist()
     fm.close()
     return out
-
-
-def same(x, y):
-    return all(np.array_equal(np.asarray(p), np.asarray(q)) for p, q in zip(x, y))
 
 
 @pytest.mark.parametrize("regs,n1", [((1e-3, 1e-3, 1e-3), 300), ((0.0, 0.0, 0.0), 4000)])
@@ -271,23 +255,6 @@ def test_resume_is_bitwise(fmhip, k, regs):
 
 # ---- 5. data-parallel, thread ranks on one GPU ------------------------------------------------------------------------
 
-DP_ROWS = {2: [900, 600], 8: [700, 300, 0, 500, 200, 500, 100, 500]}
-DP_FRACTIONS = {"dense": (0.3,), "sharded": (0.3,), "touched": (0.3,), "pipelined": (0.1, 0.3, 0.6)}
-
-
-def dp_shard(seed, rows, rank, all_rows, n1_data):
-    from sparkfm_amd import synth
-    if rows == 0:
-        return dict(row_ptr=np.zeros(1, np.int64), col=np.zeros(0, np.int32), val=np.zeros(0, np.float32), y=np.zeros(0, np.float32))
-    return synth.make_zipf(seed, rows, n1_data, 4, 24, zipf_s=1.05, row_begin=int(sum(all_rows[:rank])))
-
-
-def dp_init(n1, k):
-    from sparkfm_amd import synth
-    w0, w, v = synth.init_params(77, n1, k, stdev=0.05)
-    return 0.05, np.random.default_rng(78).normal(0, 0.05, n1), v
-
-
 def dp_run(world, exchange, shards, n1, k, br, epochs, regs, orders=None, init=0.1, setup=None):
     from sparkfm_amd import DataSet, FMModel
     from sparkfm_amd.distributed import HipDataParallelSGD, ThreadStagedComm, run_thread_ranks
@@ -333,7 +300,7 @@ def test_adagrad_data_parallel(fmhip, world, exchange, shuffle):
     for r in range(1, world):
         assert same((res[0]["w0"], res[0]["w"], res[0]["v"]) + res[0]["state"], (res[r]["w0"], res[r]["w"], res[r]["v"]) + res[r]["state"]), r
     w0, w, v = dp_init(n1, k)
-    s = ref.dp_epochs(ref.State(w0, w, v, 0.1), shards, br, orders or [None] * epochs, 0.05, *regs, EPS)
+    s = ref.dp_epochs(ref.State(w0, w, v, 0.1), shards, br, orders or [None] * epochs, 0.05, *regs, ref.Rule(eps=EPS))
     assert rel(res[0]["v"], s.v) <= 1e-5 and rel(res[0]["w"], s.w) <= 1e-5, (rel(res[0]["v"], s.v), rel(res[0]["w"], s.w))
     assert rel(res[0]["state"][2], s.nv) <= 1e-5 and rel(res[0]["state"][1], s.nw) <= 1e-5
     assert abs(res[0]["w0"] - s.w0) <= 1e-5 * abs(s.w0) + 1e-6
@@ -401,6 +368,65 @@ def test_adagrad_plan_agreement(fmhip, world):
     assert [o["sharded_step"] for o in res] == [-5] * world
     assert [o["replan"] for o in res] == [0] * world
     assert [o["epoch"] for o in res] == [-1] * world
+
+
+PLAN_THEN_CHANGE = {        # field -> (the rule every rank plans under, what rank 1 then sets, what its refusal names)
+    "loss": ({}, dict(loss=1), ["loss 0", "loss 1", "fmhip_model_set_loss"]),
+    "pairing": ({}, dict(pairing=1), ["pairing 0", "pairing 1", "fmhip_model_set_pairing"]),
+    "opt": ({}, dict(opt=("adagrad", EPS, 0.1)), ["optimizer 0", "optimizer 1", "fmhip_model_set_optimizer"]),
+    "ada_eps": (dict(opt=("adagrad", EPS, 0.1)), dict(opt=("adagrad", 1e-8, 0.1)), ["eps 1e-10", "eps 1e-08", "fmhip_model_set_optimizer"]),
+    "ada_init": (dict(opt=("adagrad", EPS, 0.1)), dict(opt=("adagrad", EPS, 0.5)),
+                 ["initial accumulator 0.1", "initial accumulator 0.5", "fmhip_model_set_optimizer"]),
+}
+
+
+@pytest.mark.parametrize("field", sorted(PLAN_THEN_CHANGE))
+def test_rule_changed_after_the_plan_is_that_ranks_failure(fmhip, field):
+    """Two ranks plan under one rule, then rank 1 alone changes one of its five fields and both take fmhip_dp_step_at(0):
+    rank 1 is refused (FMHIP_ERR_INVALID naming the field, the planned and the present value, the setter, and the way out) but
+    has taken the step's collectives with a zero contribution — rank 0's step completes, and both ranks issued the same
+    (kind, count) sequence."""
+    from sparkfm_amd import DataSet, FMModel, _ffi
+    from sparkfm_amd.distributed import ThreadStagedComm, run_thread_ranks
+    base, change, names = PLAN_THEN_CHANGE[field]
+    rows = [64, 64]
+    shards = [dp_shard(97, rows[r], r, rows, 100) for r in range(2)]
+
+    def rank_fn(r, group):
+        ds = DataSet.from_arrays(shards[r], batch_rows=32, device=0).cache()
+        fm = FMModel(100, 8, device=0)
+        fm.w0, fm.w, fm.v = dp_init(101, 8)
+        comm = ThreadStagedComm(fm, r, group)
+        lib = L()
+
+        def set_fields(loss=None, pairing=None, opt=None):
+            if loss is not None:
+                _ffi.check(lib.fmhip_model_set_loss(fm.handle, loss))
+            if pairing is not None:
+                _ffi.check(lib.fmhip_model_set_pairing(fm.handle, pairing))
+            if opt is not None:
+                set_opt(fm, *opt)
+
+        set_fields(**base)
+        fr = np.array([0.3])
+        _ffi.check(lib.fmhip_dp_plan(fm.handle, ds.handle, comm.handle, 1, _ffi.ptr(fr), None))
+        if r == 1:
+            set_fields(**change)
+        before = len(comm.calls)
+        rc = lib.fmhip_dp_step_at(fm.handle, ds.handle, 0, comm.handle, 0.05, 0.0, 0.0, 0.0)
+        out = dict(rc=rc, msg=lib.fmhip_last_error().decode() if rc else "", calls=comm.calls[before:])
+        group.barrier()
+        comm.close()
+        ds.unpersist()
+        fm.close(discard=True)
+        return out
+
+    res = run_thread_ranks(2, rank_fn, timeout=60.0)
+    assert res[0]["rc"] == 0, res[0]["msg"]
+    assert res[1]["rc"] == -1
+    for name in names + ["call fmhip_dp_plan again (every rank)", "contributed zeros"]:
+        assert name in res[1]["msg"], (name, res[1]["msg"])
+    assert res[0]["calls"] == res[1]["calls"] and len(res[0]["calls"]) >= 2
 
 
 # ---- 6. through the public flow ----------------------------------------------------------------------------------------

@@ -45,7 +45,7 @@ def _epoch(L, ffi, hm, hd, nb, eta, regs):
     return st.sse / max(st.rows, 1), st.nonfinite, st.rows, st.nnz
 
 
-def _same_bits_after_one_step(fmhip, L, ffi, make_model, ds, batch, ids, eta, regs):
+def _identical_after_one_step(fmhip, L, ffi, make_model, ds, batch, ids, eta, regs):
     """One step of `batch` from the same initial state, twice (two models): the parameters of `ids` agree bit for bit."""
     out = []
     for _ in range(2):
@@ -93,7 +93,7 @@ def test_c4_all_ten_million_rows(fmhip):
     fm._device_updated()
     fm.close(discard=True)
     ids = np.unique(np.concatenate([np.arange(0, 4096), np.random.default_rng(5).integers(0, n1, 20_000)])).astype(np.int32)
-    _same_bits_after_one_step(fmhip, L, ffi, make_model, ds, 7, ids, eta, regs)
+    _identical_after_one_step(fmhip, L, ffi, make_model, ds, 7, ids, eta, regs)
     ds.unpersist()
 
 
@@ -132,5 +132,5 @@ def test_c5_two_to_the_24_rows_at_the_real_width(fmhip):
     fm._device_updated()
     fm.close(discard=True)
     ids = np.unique(np.concatenate([feats[:20_000], np.random.default_rng(5).integers(0, n1, 20_000)])).astype(np.int32)
-    _same_bits_after_one_step(fmhip, L, ffi, make_model, ds, 33, ids, eta, regs)
+    _identical_after_one_step(fmhip, L, ffi, make_model, ds, 33, ids, eta, regs)
     ds.unpersist()

@@ -1,10 +1,7 @@
 """Binary classification: the logistic loss on every training path, and log-loss scoring (fmhip_model_set_loss, fmhip_logloss).
 
-Oracle without a logistic oracle: the logistic gradient is the squared-loss gradient at the pseudo-targets
-    y' = yhat - (sigmoid(yhat) - t),   t = [y > 0],   yhat = oracle.predict (fp64)
-because the squared residual there, yhat - y', is exactly the logistic residual.  So oracle.batch_grad / oracle.sgd_step with y'
-in place of y give the fp64 logistic gradient and step; a trajectory recomputes y' before every step.  Tolerances as in
-test_gpu_parity.py (TOL_Y, TOL_G, check_grad) and test_gpu_world8.py (rel-L2 1e-5 for the data-parallel runs)."""
+The fp64 reference is train_ref.py's: the unchanged squared-loss oracle at the pseudo-targets y' = yhat - (sigmoid(yhat) - [y > 0]).
+Tolerances as in test_gpu_parity.py (TOL_Y, TOL_G, check_grad) and test_gpu_world8.py (rel-L2 1e-5 for the data-parallel runs)."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +10,7 @@ import pytest
 import oracle
 from helpers import random_problem
 from test_gpu_parity import check_grad
+from train_ref import DP_FRACTIONS, DP_ROWS, Rule, State, dp_epochs, dp_init, dp_shard, epochs, make, pseudo_targets, rel, sigmoid
 
 pytestmark = pytest.mark.gpu
 
@@ -35,19 +33,6 @@ def set_loss(fm, loss):
     _ffi.check(L().fmhip_model_set_loss(fm.handle, _ffi.loss_code(loss)))
 
 
-def sigmoid(z):
-    z = np.asarray(z, np.float64)
-    ez = np.exp(-np.abs(z))
-    return np.where(z >= 0, 1.0 / (1.0 + ez), ez / (1.0 + ez))
-
-
-def pseudo_targets(w0, w, v, rp, col, val, y):
-    """-> (y', e = sigmoid(yhat) - t) at these parameters, over all rows."""
-    yh = oracle.predict(w0, w, v, rp, col, val)
-    e = sigmoid(yh) - (np.asarray(y) > 0)
-    return yh - e, e
-
-
 def logloss_np(yh, y):
     t = (np.asarray(y) > 0).astype(np.float64)
     return np.maximum(yh, 0.0) - t * yh + np.log1p(np.exp(-np.abs(yh)))
@@ -60,17 +45,10 @@ def binary_problem(seed, n_rows, n1, k, lo, hi, empty_rows=(), labels01=True):
     return a
 
 
-def make(fmhip, a, batch_rows=0, hot_block=None):
-    ds = fmhip.DataSet(a["row_ptr"], a["col"], a["val"], a["y"], batch_rows=batch_rows, hot_block=hot_block).cache()
-    fm = fmhip.FMModel(a["n1"] - 1, a["k"])
-    fm.w0, fm.w, fm.v = a["w0"], a["w"], a["v"]
-    return ds, fm
-
-
 def check_batches(fm, ds, a, batch_rows):
     """Every batch's logistic gradient (fmhip_batch_grad) against the pseudo-target oracle."""
     n = len(a["y"])
-    yp, e = pseudo_targets(a["w0"], a["w"], a["v"], a["row_ptr"], a["col"], a["val"], a["y"])
+    yp, e, _ = pseudo_targets(a["w0"], a["w"], a["v"], a["row_ptr"], a["col"], a["val"], a["y"], "logistic")
     for b in range(ds.n_batches):
         r0, r1 = b * batch_rows, min(n, (b + 1) * batch_rows)
         gv, gw, g0, st = fm.batchGradient(ds, b)
@@ -127,21 +105,6 @@ def test_logistic_gradient_with_hot_pages(fmhip, k):
     fm.close()
 
 
-def oracle_logistic_epochs(a, batch_rows, orders, eta, reg0, regw, regv):
-    w0, w, v = a["w0"], a["w"].copy(), a["v"].copy()
-    n = len(a["y"])
-    for order in orders:
-        for b in order:
-            r0, r1 = b * batch_rows, min(n, (b + 1) * batch_rows)
-            yp, _ = pseudo_targets(w0, w, v, a["row_ptr"], a["col"], a["val"], a["y"])
-            w0, w, v, _ = oracle.sgd_step(w0, w, v, r0, r1, a["row_ptr"], a["col"], a["val"], yp, eta, reg0, regw, regv)
-    return w0, w, v
-
-
-def rel(x, ref):
-    return float(np.linalg.norm(np.asarray(x) - ref) / max(np.linalg.norm(ref), 1e-12))
-
-
 @pytest.mark.parametrize("case", ["no_decay", "wide_lazy_decay"])
 def test_logistic_sgd_trajectory(fmhip, case):
     """Two shuffled epochs of fmhip_sgd_epoch (HipSGD(loss="logistic")) against the stepped pseudo-target oracle.  The wide case
@@ -159,7 +122,7 @@ def test_logistic_sgd_trajectory(fmhip, case):
         orders.append(sgd.batch_order(ds.n_batches).tolist())
         sgd.learn(fm, ds)
     assert sgd.last_stats["rows"] == len(a["y"])
-    ow0, ow, ov = oracle_logistic_epochs(a, br, orders, 0.1, *regs)
+    ow0, ow, ov = epochs(State(a["w0"], a["w"], a["v"]), a, br, orders, 0.1, *regs, Rule("logistic")).params()
     assert rel(fm.v, ov) <= 1e-4 and rel(fm.w, ow) <= 1e-4, (rel(fm.v, ov), rel(fm.w, ow))
     assert fm.w0 == pytest.approx(ow0, rel=1e-4, abs=1e-6)
     assert np.abs(fm.w - a["w"]).max() > 1e-3                # it moved
@@ -169,47 +132,6 @@ def test_logistic_sgd_trajectory(fmhip, case):
 
 # ---- data-parallel: thread ranks over ThreadStagedComm (every collective staged through the host) ----
 
-def dp_shard(seed, rows, rank, all_rows, n1_data, reverse_ids):
-    from sparkfm_amd import synth
-    if rows == 0:
-        return dict(row_ptr=np.zeros(1, np.int64), col=np.zeros(0, np.int32), val=np.zeros(0, np.float32), y=np.zeros(0, np.float32))
-    d = synth.make_zipf(seed, rows, n1_data, 4, 24, zipf_s=1.05, row_begin=int(sum(all_rows[:rank])))
-    if reverse_ids:
-        d = dict(d, col=(n1_data - 1 - d["col"]).astype(np.int32))
-    return dict(d, y=(d["y"] > np.median(d["y"])).astype(np.float32))
-
-
-def dp_init(n1, k):
-    from sparkfm_amd import synth
-    w0, w, v = synth.init_params(77, n1, k, stdev=0.05)
-    return 0.05, np.random.default_rng(78).normal(0, 0.05, n1), v
-
-
-def dp_oracle(shards, n1, k, batch_rows, epochs, eta, regw, regv):
-    w0, w, v = dp_init(n1, k)
-    steps = max((len(d["y"]) + batch_rows - 1) // batch_rows for d in shards)
-    for _ in range(epochs):
-        for j in range(steps):
-            rp, cols, vals, ys = [0], [], [], []
-            for d in shards:
-                n = len(d["y"])
-                lo, hi = min(n, j * batch_rows), min(n, (j + 1) * batch_rows)
-                if hi > lo:
-                    a0, b0 = int(d["row_ptr"][lo]), int(d["row_ptr"][hi])
-                    cols.append(d["col"][a0:b0])
-                    vals.append(d["val"][a0:b0].astype(np.float64))
-                    rp.extend((d["row_ptr"][lo + 1:hi + 1] - a0 + rp[-1]).tolist())
-                    ys.append(d["y"][lo:hi].astype(np.float64))
-            rp, col, val, y = np.array(rp, np.int64), np.concatenate(cols), np.concatenate(vals), np.concatenate(ys)
-            yp, _ = pseudo_targets(w0, w, v, rp, col, val, y)
-            w0, w, v, _ = oracle.sgd_step(w0, w, v, 0, len(y), rp, col, val, yp, eta, 0.0, regw, regv)
-    return w0, w, v
-
-
-DP_ROWS = {2: [900, 600], 8: [700, 300, 0, 500, 200, 500, 100, 500]}
-DP_FRACTIONS = {"dense": (0.3,), "sharded": (0.3,), "touched": (0.3,), "pipelined": (0.1, 0.3, 0.6)}
-
-
 @pytest.mark.parametrize("world,exchange,reverse_ids", [(w, x, False) for w in (2, 8) for x in ("dense", "sharded", "touched", "pipelined")]
                          + [(2, "pipelined", True)])
 def test_logistic_data_parallel(fmhip, world, exchange, reverse_ids):
@@ -218,9 +140,9 @@ def test_logistic_data_parallel(fmhip, world, exchange, reverse_ids):
     or above the top cut, so pass B also runs the hot prologue."""
     from sparkfm_amd import DataSet, FMModel
     from sparkfm_amd.distributed import HipDataParallelSGD, ThreadStagedComm, run_thread_ranks
-    rows, n1_data, n1, k, br, epochs = DP_ROWS[world], 800, 803, 32, 250, 2
+    rows, n1_data, n1, k, br, n_epochs = DP_ROWS[world], 800, 803, 32, 250, 2
     eta, regw, regv = 0.1, 1e-3, 1e-3
-    shards = [dp_shard(4321, rows[r], r, rows, n1_data, reverse_ids) for r in range(world)]
+    shards = [dp_shard(4321, rows[r], r, rows, n1_data, reverse_ids, binary=True) for r in range(world)]
 
     def rank_fn(r, group):
         ds = DataSet.from_arrays(shards[r], batch_rows=br, device=0).cache()
@@ -231,7 +153,7 @@ def test_logistic_data_parallel(fmhip, world, exchange, reverse_ids):
                                 loss="logistic")
         dp.plan(fm, ds)
         hot_top = reverse_ids and max(ds.layout()["hot_ids"]) >= max(dp.cuts)
-        for _ in range(epochs):
+        for _ in range(n_epochs):
             dp.learn(fm, ds)
         out = dict(w0=fm.w0, w=fm.w.copy(), v=fm.v.copy(), hot_top=hot_top)
         group.barrier()
@@ -245,7 +167,7 @@ def test_logistic_data_parallel(fmhip, world, exchange, reverse_ids):
         assert np.array_equal(res[0]["v"], res[r]["v"]) and np.array_equal(res[0]["w"], res[r]["w"]) and res[0]["w0"] == res[r]["w0"], r
     if reverse_ids:
         assert res[0]["hot_top"]
-    ow0, ow, ov = dp_oracle(shards, n1, k, br, epochs, eta, regw, regv)
+    ow0, ow, ov = dp_epochs(State(*dp_init(n1, k)), shards, br, [None] * n_epochs, eta, 0.0, regw, regv, Rule("logistic")).params()
     assert rel(res[0]["v"], ov) <= 1e-5 and rel(res[0]["w"], ow) <= 1e-5, (rel(res[0]["v"], ov), rel(res[0]["w"], ow))
     assert abs(res[0]["w0"] - ow0) <= 1e-5 * abs(ow0) + 1e-6
 
@@ -258,7 +180,7 @@ def test_data_parallel_plan_refuses_mixed_losses(fmhip, world):
     from sparkfm_amd import DataSet, FMModel, _ffi
     from sparkfm_amd.distributed import HipDataParallelSGD, ThreadStagedComm, run_thread_ranks
     rows = DP_ROWS[world]
-    shards = [dp_shard(99, rows[r], r, rows, 300, False) for r in range(world)]
+    shards = [dp_shard(99, rows[r], r, rows, 300, binary=True) for r in range(world)]
 
     def rank_fn(r, group):
         ds = DataSet.from_arrays(shards[r], batch_rows=250, device=0).cache()
@@ -379,7 +301,7 @@ def test_refusals_and_invariance(fmhip):
     _ffi.check(L().fmhip_model_init_normal(m.handle, 5, 0.0, 0.01))
     _ffi.check(L().fmhip_model_set_params(m.handle, a["w0"], _ffi.ptr(a["w"]), _ffi.ptr(np.asfortranarray(a["v"]).reshape(-1, order="F"))))
     _, _, g0, _ = m.batchGradient(ds, 0)
-    yp, e = pseudo_targets(a["w0"], a["w"], a["v"], a["row_ptr"], a["col"], a["val"], a["y"])
+    yp, e, _ = pseudo_targets(a["w0"], a["w"], a["v"], a["row_ptr"], a["col"], a["val"], a["y"], "logistic")
     assert g0 == pytest.approx(e[:150].sum(), rel=1e-5, abs=1e-4)      # still logistic
     m.close()
     ds.unpersist()

@@ -1,5 +1,5 @@
 """Pairwise ranking (fmhip_model_set_pairing, FMHIP_PAIRING_ADJACENT; fmhip_pair_logloss): the pair residual on every training
-path against the fp64 reference of pairing_ref.py (the unchanged oracle at the pseudo-targets y' = yhat - e), the scoring of
+path against the fp64 reference of train_ref.py (the unchanged oracle at the pseudo-targets y' = yhat - e), the scoring of
 held-out pairs against numpy, refusals, invariance, and a ranking model that learns.
 
 No tolerance here is new: the one-step gradient is check_grad of test_gpu_parity.py; trajectories take the bounds of
@@ -10,11 +10,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import adagrad_ref
 import oracle
-import pairing_ref as ref
+import train_ref as ref
 from helpers import random_problem
 from test_gpu_parity import check_grad
+from train_ref import DP_FRACTIONS, dp_init, dp_shard, make, rel, same
 
 pytestmark = pytest.mark.gpu
 
@@ -47,21 +47,6 @@ def problem(seed, n_rows, n1, k, lo, hi, loss, empty_rows=()):
     return a
 
 
-def make(fmhip, a, batch_rows=0, hot_block=None):
-    ds = fmhip.DataSet(a["row_ptr"], a["col"], a["val"], a["y"], batch_rows=batch_rows, hot_block=hot_block).cache()
-    fm = fmhip.FMModel(a["n1"] - 1, a["k"])
-    fm.w0, fm.w, fm.v = a["w0"], a["w"], a["v"]
-    return ds, fm
-
-
-def rel(x, y):
-    return float(np.linalg.norm(np.asarray(x) - y) / max(np.linalg.norm(y), 1e-30))
-
-
-def same(x, y):
-    return all(np.array_equal(np.asarray(p), np.asarray(q)) for p, q in zip(x, y))
-
-
 def params(fm):
     return fm.w0, fm.w.copy(), fm.v.copy()
 
@@ -71,7 +56,7 @@ def params(fm):
 def check_batches(fm, ds, a, batch_rows, loss):
     """Every batch's paired gradient against the oracle at the pseudo-targets; sum e exactly zero."""
     n = len(a["y"])
-    yp, e, _ = ref.pseudo_targets(a["w0"], a["w"], a["v"], a["row_ptr"], a["col"], a["val"], a["y"], loss)
+    yp, e, _ = ref.pseudo_targets(a["w0"], a["w"], a["v"], a["row_ptr"], a["col"], a["val"], a["y"], loss, True)
     assert ds.n_batches == (n + batch_rows - 1) // batch_rows > 1
     for b in range(ds.n_batches):
         r0, r1 = b * batch_rows, min(n, (b + 1) * batch_rows)
@@ -178,7 +163,7 @@ def test_pair_sgd_trajectory(fmhip, case):
         orders.append(sgd.batch_order(ds.n_batches).tolist())
         sgd.learn(fm, ds)
     assert sgd.last_stats["rows"] == len(a["y"]) and sgd.last_stats["sum_e"] == 0.0 and sgd.last_stats["sse"] > 0
-    ow0, ow, ov = ref.sgd_epochs(a, c["br"], orders, 0.1, *regs, c["loss"])
+    ow0, ow, ov = ref.epochs(ref.State(a["w0"], a["w"], a["v"]), a, c["br"], orders, 0.1, *regs, ref.Rule(c["loss"], True)).params()
     assert rel(fm.v, ov) <= 1e-4 and rel(fm.w, ow) <= 1e-4, (rel(fm.v, ov), rel(fm.w, ow))
     assert fm.w0 == pytest.approx(ow0, rel=1e-4, abs=1e-6)
     if regs[0] == 0.0:
@@ -205,7 +190,7 @@ def test_pair_adagrad_trajectory(fmhip, k, loss, regs):
         orders.append(sgd.batch_order(ds.n_batches).tolist())
         sgd.learn(fm, ds)
     assert sgd.last_stats["sum_e"] == 0.0
-    s = ref.adagrad_epochs(adagrad_ref.State(a["w0"], a["w"], a["v"], 0.1), a, 200, orders, 0.05, *regs, tga.EPS, loss)
+    s = ref.epochs(ref.State(a["w0"], a["w"], a["v"], 0.1), a, 200, orders, 0.05, *regs, ref.Rule(loss, True, tga.EPS))
     n0, nw, nv = tga.get_state(fm)
     assert rel(fm.v, s.v) <= 1e-5 and rel(fm.w, s.w) <= 1e-5, (rel(fm.v, s.v), rel(fm.w, s.w))
     assert rel(nv, s.nv) <= 1e-5 and rel(nw, s.nw) <= 1e-5, (rel(nv, s.nv), rel(nw, s.nw))
@@ -256,8 +241,7 @@ DP_ROWS = [900, 600]                # even shards, even batches of 250 rows (the
 
 
 def dp_shards():
-    from test_gpu_logistic import dp_shard
-    return [dp_shard(4321, DP_ROWS[r], r, DP_ROWS, 800, False) for r in range(2)]
+    return [dp_shard(4321, DP_ROWS[r], r, DP_ROWS, 800, binary=True) for r in range(2)]
 
 
 @pytest.mark.parametrize("exchange", ["dense", "sharded", "touched"])
@@ -267,7 +251,6 @@ def test_pair_data_parallel(fmhip, exchange):
     concatenation keeps the pairs)."""
     from sparkfm_amd import DataSet, FMModel
     from sparkfm_amd.distributed import HipDataParallelSGD, ThreadStagedComm, run_thread_ranks
-    from test_gpu_logistic import DP_FRACTIONS, dp_init
     n1, k, br, epochs = 803, 32, 250, 2
     eta, regw, regv = 0.1, 1e-3, 1e-3
     shards = dp_shards()
@@ -294,7 +277,7 @@ def test_pair_data_parallel(fmhip, exchange):
     # (fmhip_dp_epoch's stats are the last global batch's summed scalars: rank 0's fourth batch alone)
     assert res[0]["stats"]["sum_e"] == 0.0 and res[0]["stats"]["sse"] > 0 and res[0]["stats"]["rows"] == 150
     w0, w, v = dp_init(n1, k)
-    ow0, ow, ov = ref.dp_sgd_epochs(w0, w, v, shards, br, epochs, eta, 0.0, regw, regv, "logistic")
+    ow0, ow, ov = ref.dp_epochs(ref.State(w0, w, v), shards, br, [None] * epochs, eta, 0.0, regw, regv, ref.Rule("logistic", True)).params()
     assert rel(res[0]["v"], ov) <= 1e-5 and rel(res[0]["w"], ow) <= 1e-5, (rel(res[0]["v"], ov), rel(res[0]["w"], ow))
     assert res[0]["w0"] == np.float32(w0) and ow0 == pytest.approx(w0, rel=1e-12)
     assert np.abs(res[0]["w"] - w).max() > 1e-3
@@ -306,7 +289,6 @@ def test_data_parallel_plan_refusals(fmhip):
     in the loss's agreement word).  A pairing changed after the plan is that rank's own failure, found before the first collective."""
     from sparkfm_amd import DataSet, FMModel, _ffi
     from sparkfm_amd.distributed import HipDataParallelSGD, ThreadStagedComm, run_thread_ranks
-    from test_gpu_logistic import dp_init
     shards = dp_shards()
 
     def rank_fn(r, group):
@@ -380,7 +362,7 @@ def test_pair_logloss_vs_numpy(fmhip):
         assert rc == 0 and np.isfinite(r) and r == pytest.approx(ll, rel=1e-5), (scale, r, ll)
         slack = concordance_slack(yh, 1e-5 * (1 + np.abs(yh).max()))            # TOL_Y of test_gpu_parity.py on a margin
         assert slack <= 0.005 and abs(c - conc) <= slack + 1e-15, (scale, c, conc, slack)
-        e = ref.residuals(yh, a["y"], "logistic")
+        e = ref.residuals(yh, a["y"], "logistic", True)
         assert st.sum_e == 0.0 and st.sse == pytest.approx((e * e).sum(), rel=1e-5)
         assert st.rows == 1500 and st.nonfinite == 0 and st.nnz == int(a["row_ptr"][-1])
         assert (fm.computePairLogLoss(ds), fm.computePairAccuracy(ds)) == (r, c)
@@ -520,7 +502,7 @@ def test_invariance(fmhip):
     _ffi.check(L().fmhip_model_set_optimizer(m.handle, _ffi.OPT_ADAGRAD, 1e-10, 0.1))
     _ffi.check(L().fmhip_model_set_optimizer(m.handle, _ffi.OPT_SGD, 1e-10, 0.1))
     _, _, g0, st = m.batchGradient(ds, 0)
-    _, e, _ = ref.pseudo_targets(a["w0"], a["w"], a["v"], a["row_ptr"], a["col"], a["val"], a["y"], "logistic")
+    _, e, _ = ref.pseudo_targets(a["w0"], a["w"], a["v"], a["row_ptr"], a["col"], a["val"], a["y"], "logistic", True)
     assert g0 == 0.0 and st["sse"] == pytest.approx((e[:150] ** 2).sum(), rel=1e-5)
     m.close()
     # ADJACENT and back == never touched; paired twice == paired once more
@@ -582,7 +564,8 @@ def learn_reference(train, init, orders):
     """The fp64 reference on the same schedule -> (w0, w, v)."""
     c = LEARN
     a = dict(row_ptr=train.row_ptr, col=train.col, val=train.val, y=train.y, w0=init[0], w=init[1], v=init[2])
-    return ref.sgd_epochs(a, c["batch_rows"], orders, c["eta"], 0.0, c["regw"], c["regv"], "logistic")
+    return ref.epochs(ref.State(a["w0"], a["w"], a["v"]), a, c["batch_rows"], orders, c["eta"], 0.0, c["regw"], c["regv"],
+                      ref.Rule("logistic", True)).params()
 
 
 def test_pairwise_fm_learns_a_ranking(fmhip):

@@ -1,12 +1,12 @@
 """AdaGrad without a GPU: the C ABI's argument checks (fmhip_model_set_optimizer and the state I/O of fmhip_experimental.h),
-the Python learners' `optimizer=` validation, and the tests' own fp64 rule (adagrad_ref.py) pinned to torch.optim.Adagrad."""
+the Python learners' `optimizer=` validation, and the tests' own fp64 rule (train_ref.py) pinned to torch.optim.Adagrad."""
 import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
-from adagrad_ref import adagrad_rule
+from train_ref import adagrad_rule
 
 
 def L():
@@ -98,7 +98,7 @@ def test_data_parallel_engine_without_the_call_refuses_adagrad():
 
 
 def test_reference_rule_matches_torch_adagrad():
-    """adagrad_ref.adagrad_rule (what every GPU test compares against) against torch.optim.Adagrad in fp64 on a small dense
+    """train_ref.adagrad_rule (what every GPU test compares against) against torch.optim.Adagrad in fp64 on a small dense
     FM-like problem: three param groups (w0, w, V) each with its own weight_decay, the initial accumulator and eps of the
     library's defaults, several steps of a changing gradient."""
     torch = pytest.importorskip("torch")

@@ -1,5 +1,5 @@
 """The pairing switch's host surface (no GPU): argument checks of fmhip_model_set_pairing / fmhip_pair_logloss, the learners'
-`pairs=`, the header's enum against the binding's constants, DataSet.from_pairs, and the reference rule of pairing_ref.py
+`pairs=`, the header's enum against the binding's constants, DataSet.from_pairs, and the reference rule of train_ref.py
 against finite differences of the pair loss."""
 import ctypes as C
 import os
@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-import pairing_ref
+import train_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -111,35 +111,35 @@ def test_from_pairs_interleaves():
 
 @pytest.mark.parametrize("loss", ["squared", "logistic"])
 def test_reference_g_is_the_derivative_of_the_pair_loss(loss):
-    """pairing_ref.pair_g against a central difference of pairing_ref.pair_loss in d, at ordinary and at saturated margins, for
+    """train_ref.pair_g against a central difference of train_ref.pair_loss in d, at ordinary and at saturated margins, for
     targets of both signs and ties.  Bound of the difference quotient with step h: h^2/6 * max|loss'''| (<= 0.1 for the
     logistic loss, 0 for the squared one) + 2 eps * max|loss| / h."""
     d = np.array([-40.0, -12.5, -3.0, -0.7, -1e-3, 0.0, 1e-3, 0.4, 2.0, 9.0, 40.0])
     h = 1e-4
     for dy in (1.0, -1.0, 0.0, 2.0):
         dyv = np.full(len(d), dy)
-        lo, hi = pairing_ref.pair_loss(d - h, dyv, loss), pairing_ref.pair_loss(d + h, dyv, loss)
+        lo, hi = train_ref.pair_loss(d - h, dyv, loss), train_ref.pair_loss(d + h, dyv, loss)
         fd = (hi - lo) / (2 * h)
         tol = h * h / 6 * 0.1 + 2 * np.finfo(np.float64).eps * np.maximum(np.abs(lo), np.abs(hi)).max() / h
-        g = pairing_ref.pair_g(d, dyv, loss)
+        g = train_ref.pair_g(d, dyv, loss)
         assert np.abs(g - fd).max() <= tol, (dy, np.abs(g - fd).max(), tol)
     if loss == "logistic":
         # a margin saturated on the right side leaves a tiny residual, not a cancelled one
-        assert pairing_ref.pair_g(40.0, 1.0, loss) == pytest.approx(-np.exp(-40.0), rel=1e-12)
-        assert pairing_ref.pair_g(-40.0, -1.0, loss) == pytest.approx(np.exp(-40.0), rel=1e-12)
+        assert train_ref.pair_g(40.0, 1.0, loss) == pytest.approx(-np.exp(-40.0), rel=1e-12)
+        assert train_ref.pair_g(-40.0, -1.0, loss) == pytest.approx(np.exp(-40.0), rel=1e-12)
         # BPR: the preferred row first with the larger label -> -log sigmoid(yhat_preferred - yhat_other)
-        assert pairing_ref.pair_loss(0.3, 1.0, loss) == pytest.approx(-np.log(pairing_ref.sigmoid(0.3)), rel=1e-14)
-        assert pairing_ref.pair_loss(0.0, 1.0, loss) == pytest.approx(np.log(2.0), rel=1e-15)
+        assert train_ref.pair_loss(0.3, 1.0, loss) == pytest.approx(-np.log(train_ref.sigmoid(0.3)), rel=1e-14)
+        assert train_ref.pair_loss(0.0, 1.0, loss) == pytest.approx(np.log(2.0), rel=1e-15)
 
 
 def test_reference_residuals_and_scores():
     yh = np.array([0.5, -0.5, 0.0, 0.0, -2.0, 1.0, 3.0, 3.5])
     y = np.array([1.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 0.0])
     for loss in ("squared", "logistic"):
-        e = pairing_ref.residuals(yh, y, loss)
+        e = train_ref.residuals(yh, y, loss, True)
         assert np.array_equal(e[0::2], -e[1::2]) and e.sum() == 0.0
-    ll, conc = pairing_ref.pair_scores(yh, y)
+    ll, conc = train_ref.pair_scores(yh, y)
     # pairs: d = 1 (t), 0 (t: a tie), -3 (not t), -0.5 (not t: dy = 0)
-    sp = pairing_ref.softplus
+    sp = train_ref.softplus
     assert ll == pytest.approx((sp(-1.0) + sp(0.0) + sp(-3.0) + sp(-0.5)) / 4, rel=1e-15)
     assert conc == (1 + 0.5 + 1 + 1) / 4
