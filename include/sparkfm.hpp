@@ -12,7 +12,7 @@
 //     sparkfm::HipALS       S/fm/lib/ALS.scala:15-75,202-208 the reference's own learner in fp64 on the GPU
 //     sparkfm::FM           S/fm/FM.scala:25-33, S/fm/impl/FactorizationMachines.scala:30-51   the fit loop
 //
-// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation) and include/fmhip_pairing.h (pairwise ranking) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
+// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking) and include/fmhip_metrics.h (ROC AUC) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
 // here a non-zero status of the C ABI becomes sparkfm::Error carrying fmhip_last_error().  Parameters live on the host as in
 // the reference (public, mutable: `fm.w0`, `fm.w`, `fm.v` with v[f + i*k] = breeze's column-major DenseMatrix(k, n+1)); every
 // call that needs them on the device uploads them first, as jvm/HipSGD.scala does (the fit loop calls `learn` once per
@@ -31,6 +31,7 @@
 #include "fmhip.h"
 #include "fmhip_topk.h"
 #include "fmhip_pairing.h"
+#include "fmhip_metrics.h"
 
 namespace sparkfm {
 
@@ -162,6 +163,21 @@ class FMModel {
         double logloss = 0.0, concordance = 0.0;
         check(fmhip_pair_logloss(upload(), dataset.handle(), &logloss, &concordance, nullptr));
         return concordance;
+    }
+
+    // ROC AUC of predict against the labels t = [y > 0] (fmhip_auc), ranked on the device, exactly: the share of (positive,
+    // negative) pairs the model orders correctly, a tie counting one half; NaN when there is no such pair ...
+    double computeAUC(DataSet &dataset) { return aucDetails(dataset, nullptr).auc; }
+    // ... and GAUC: the AUC inside each group of rows (groups[r]: any id in [0, 2^31), one per row — a user's impressions),
+    // averaged by the groups' row counts over the groups that hold both classes
+    double computeGroupAUC(DataSet &dataset, const std::vector<int32_t> &groups) { return aucDetails(dataset, &groups).gauc; }
+    // every field of the result (the exact integer counts beside the two ratios)
+    fmhip_auc_result aucDetails(DataSet &dataset, const std::vector<int32_t> *groups = nullptr) {
+        if (groups && (int64_t)groups->size() != dataset.size()) throw Error(FMHIP_ERR_INVALID, "groups must hold one id per row");
+        fmhip_auc_result r{};
+        r.struct_size = (int32_t)sizeof r;
+        check(fmhip_auc(upload(), dataset.handle(), groups ? groups->data() : nullptr, &r, nullptr));
+        return r;
     }
 
     // Per row of `contexts` the k rows of `candidates` the model ranks highest (fmhip_topk): the users x items ranking of

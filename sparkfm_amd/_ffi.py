@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -47,6 +47,8 @@ SYMBOLS_TOPK = ("fmhip_topk", "fmhip_pair_scores")
 TOPK_MAX = 128      # FMHIP_TOPK_MAX
 # ... and include/fmhip_pairing.h — pairwise ranking: training on pairs of adjacent rows, scoring held-out pairs
 SYMBOLS_PAIRING = ("fmhip_model_set_pairing", "fmhip_pair_logloss")
+# ... and include/fmhip_metrics.h — ranking metrics: ROC AUC and per-group AUC, exact
+SYMBOLS_METRICS = ("fmhip_auc_scores", "fmhip_auc")
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -146,6 +148,37 @@ class Profile(C.Structure):
     def as_dict(self):
         return {KERNEL_NAMES[i]: dict(ms=self.ms[i], launches=self.launches[i], nnz=self.nnz[i], rows=self.rows[i], steps=self.steps[i])
                 for i in range(K_COUNT)}
+
+
+class AucResult(C.Structure):
+    """fmhip_auc_result (include/fmhip_metrics.h); struct_size is filled in on construction."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("u2", C.c_uint64), ("pairs", C.c_int64),
+                ("positives", C.c_int64), ("negatives", C.c_int64), ("groups", C.c_int64), ("groups_scored", C.c_int64),
+                ("auc", C.c_double), ("gauc", C.c_double)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(AucResult)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
+
+
+def group_ids(groups, n):
+    """None | n integers -> None | a contiguous int32 array (ValueError: wrong length, an id outside [0, 2^31))."""
+    if groups is None:
+        return None
+    import numpy as np
+    g = np.asarray(groups)
+    if g.shape != (n,):
+        raise ValueError("groups must hold one id per row (%d), not shape %r" % (n, g.shape))
+    if n and not np.issubdtype(g.dtype, np.integer):
+        raise ValueError("groups must be integers, not %s" % g.dtype)
+    if n and int(g.max()) >= 2 ** 31:
+        raise ValueError("group ids must be below 2^31")
+    if n and int(g.min()) < -2 ** 31:
+        raise ValueError("group ids must be >= 0")
+    return np.ascontiguousarray(g, np.int32)     # (a negative id is refused by the library, which names the row)
 
 
 class DatasetOpts(C.Structure):
@@ -285,7 +318,9 @@ def load():
     L.fmhip_relabel_columns_gpu.argtypes = [C.c_int, i64, vp, i64, vp, vp]
     L.fmhip_topk.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.fmhip_pair_scores.argtypes = [vp, vp, vp, i64, i64, vp]
-    for name in SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING:
+    L.fmhip_auc_scores.argtypes = [C.c_int, i64, vp, vp, vp, P(AucResult)]
+    L.fmhip_auc.argtypes = [vp, vp, vp, P(AucResult), P(Stats)]
+    for name in SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS:
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

@@ -23,6 +23,7 @@
 // The score of a pair is one fixed expression whatever tile, split or chunk it falls into: results are bit-identical run
 // to run and batch to batch.
 #include "fm_topk.h"
+#include "fm_score_key.h"
 
 #include <algorithm>
 
@@ -42,11 +43,7 @@ __device__ __forceinline__ float pair_score(float yc, float bd, float dot) {
     s += 0.f;
     return s != s ? __uint_as_float(0x7fc00000u) : s;
 }
-// order-preserving key: NaN -> 0, then -Inf < ... < -0 = +0 < ... < +Inf
-__device__ __forceinline__ uint32_t score_key(float s) {
-    const uint32_t u = __float_as_uint(s);
-    return s != s ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-}
+// order-preserving key, score_key (fm_score_key.h): NaN -> 0, then -Inf < ... < -0 = +0 < ... < +Inf (pair_score leaves no -0)
 __device__ __forceinline__ float key_score(uint32_t key) {
     return key == 0u ? __uint_as_float(0x7fc00000u) : __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
 }

@@ -3,12 +3,14 @@
 //   fmhip_dataset.hip   datasets (host passes, device transposes, layout queries, feature relabelling)
 //   fmhip_step.hip      the launch sequence of one mini-batch step
 //   fmhip_comm.hip      the data-parallel step (RCCL / caller's transport)
-//   fm_forward / fm_backward / fm_apply / als_kernels / csc_build / fm_topk .hip   the kernels
+//   fm_forward / fm_backward / fm_apply / als_kernels / csc_build / fm_topk / fm_pairing / fm_auc .hip   the kernels
 #include "fmhip_internal.h"
 #include "../../include/fmhip_topk.h"
+#include "../../include/fmhip_metrics.h"
 #include "als_kernels.h"
 #include "fm_topk.h"
 #include "fm_pairing.h"
+#include "fm_auc.h"
 
 #include <algorithm>
 #include <atomic>
@@ -601,6 +603,151 @@ int fmhip_pair_logloss(fmhip_model_t m, fmhip_dataset_t d, double *logloss, doub
         stats->nonfinite = (int64_t)llround(h[3]);
         stats->nnz = d->nnz;
     }
+    return FMHIP_OK;
+}
+
+// ---- ROC AUC and per-group AUC (include/fmhip_metrics.h) ---------------------------------------------------------------------
+// One 64-bit word per row (group, key of the prediction, label), sorted; the counts are read off the sorted words (fm_auc.hip).
+// fmhip_auc forms the words batch by batch behind the residual-mode forward, fmhip_auc_scores from the caller's arrays: the two
+// share every line after that.
+namespace {
+
+// the refusals that touch neither a handle nor a device
+int auc_check_out(fmhip_auc_result *out) {
+    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    if (out->struct_size != (int32_t)sizeof(fmhip_auc_result))
+        return fail(FMHIP_ERR_INVALID, "out->struct_size is %d, not sizeof(fmhip_auc_result) = %d", (int)out->struct_size,
+                    (int)sizeof(fmhip_auc_result));
+    return FMHIP_OK;
+}
+int auc_check_rows(int64_t n) {
+    if (n < 0) return fail(FMHIP_ERR_INVALID, "n = %lld is negative", (long long)n);
+    if (n > 0x7fffffffll) return fail(FMHIP_ERR_UNSUPPORTED, "%lld rows: the AUC calls take fewer than 2^31", (long long)n);
+    return FMHIP_OK;
+}
+// the ids must be >= 0; *end_bit: the bits of a word the sort has to look at (33 + what the largest id needs)
+int auc_check_groups(const int32_t *group, int64_t n, int *end_bit) {
+    int32_t top = 0;
+    if (group)
+        for (int64_t r = 0; r < n; ++r) {
+            if (group[r] < 0) return fail(FMHIP_ERR_INVALID, "group id %d of row %lld is negative", (int)group[r], (long long)r);
+            top = group[r] > top ? group[r] : top;
+        }
+    int bits = 0;
+    while (bits < 31 && ((int64_t)top >> bits) != 0) ++bits;
+    *end_bit = kAucGroupShift + bits;
+    return FMHIP_OK;
+}
+void auc_fill(fmhip_auc_result *out, const AucSums &a, int64_t n) {
+    const double nan = std::nan("");
+    out->reserved = 0;
+    out->u2 = a.u2;
+    out->pairs = (int64_t)a.pairs;
+    out->negatives = (int64_t)a.negatives;
+    out->positives = n - (int64_t)a.negatives;
+    out->groups = (int64_t)a.groups;
+    out->groups_scored = (int64_t)a.groups_scored;
+    out->auc = a.pairs ? (double)a.u2 / (2.0 * (double)a.pairs) : nan;
+    // one scored group: its AUC itself (the weighted mean of one number), so that gauc == auc bit for bit without groups
+    out->gauc = a.groups_scored == 0 ? nan : (a.groups_scored == 1 ? out->auc : a.gauc_num / (double)a.rows_scored);
+}
+struct OwnStream {
+    hipStream_t s = nullptr;
+    ~OwnStream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+}  // namespace
+
+int fmhip_auc_scores(int device, int64_t n, const float *score, const float *y, const int32_t *group, fmhip_auc_result *out) {
+    TRY(auc_check_out(out));
+    TRY(auc_check_rows(n));
+    if (n > 0 && (!score || !y)) return fail(FMHIP_ERR_INVALID, "score or y is NULL");
+    int end_bit = 0;
+    TRY(auc_check_groups(group, n, &end_bit));
+    AucSums sums{};
+    if (n == 0) {
+        auc_fill(out, sums, 0);
+        return FMHIP_OK;
+    }
+    TRY(set_device(device));
+    DevBuf<float> ds, dy;
+    DevBuf<int32_t> dg;
+    DevBuf<unsigned long long> words;
+    OwnStream st;            // (declared after the buffers: destroyed, and so drained, before they are freed)
+    TRY(ds.alloc((size_t)n));
+    TRY(dy.alloc((size_t)n));
+    if (group) TRY(dg.alloc((size_t)n));
+    TRY(words.alloc((size_t)n));
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    HIP_TRY(hipMemcpyAsync(ds.p, score, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st.s));
+    HIP_TRY(hipMemcpyAsync(dy.p, y, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st.s));
+    if (group) HIP_TRY(hipMemcpyAsync(dg.p, group, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st.s));
+    HIP_TRY(launch_auc_keys(ds.p, dy.p, dg.p, n, words.p, st.s));
+    HIP_TRY(auc_from_words(words.p, n, end_bit, st.s, &sums));
+    auc_fill(out, sums, n);
+    return FMHIP_OK;
+}
+
+int fmhip_auc(fmhip_model_t m, fmhip_dataset_t d, const int32_t *group, fmhip_auc_result *out, fmhip_stats *stats) {
+    TRY(auc_check_out(out));
+    ReadLock lock(m);
+    if (!m || !d) return fail(FMHIP_ERR_INVALID, "model or dataset is NULL");
+    const int64_t n = d->n_rows;
+    TRY(auc_check_rows(n));
+    TRY(check_pair(m, d));
+    int end_bit = 0;
+    TRY(auc_check_groups(group, n, &end_bit));
+    AucSums sums{};
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        stats->nnz = d->nnz;
+    }
+    if (n == 0) {
+        auc_fill(out, sums, 0);
+        return FMHIP_OK;
+    }
+    DevBuf<int32_t> dg;
+    DevBuf<unsigned long long> words;
+    ScoreLease lease(m);     // (declared after the buffers: its destructor drains the stream before they are freed)
+    TRY(lease.take());
+    ScoreCtx &cx = *lease.cx;
+    const size_t rows_max = (size_t)std::max<int64_t>(d->max_rows, 1);
+    TRY(cx.e.ensure(rows_max));
+    TRY(cx.yhat.ensure(rows_max));
+    TRY(cx.bsum.ensure((size_t)kMaxFwdBlocks * 4));
+    TRY(cx.acc.ensure(5));
+    TRY(words.alloc((size_t)n));
+    if (group) TRY(dg.alloc((size_t)n));
+    // behind whatever the model's own stream still has queued (a training step returns before it has run)
+    HIP_TRY(hipEventRecord(cx.ev, m->stream));
+    HIP_TRY(hipStreamWaitEvent(cx.s, cx.ev, 0));
+    HIP_TRY(hipMemsetAsync(cx.acc.p, 0, 5 * sizeof(double), cx.s));
+    if (group) HIP_TRY(hipMemcpyAsync(dg.p, group, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
+    for (const BatchMeta &bm : d->batches) {
+        FwdArgs a = fwd_args(m, d, bm);      // the forward of fmhip_rmse / fmhip_predict: the same predictions, the same statistics
+        a.P = nullptr;
+        a.e = cx.e.p;
+        a.bsum = cx.bsum.p;
+        a.yhat = cx.yhat.p;
+        a.loss = kLossSquared;
+        int parts = 0;
+        HIP_TRY(launch_forward(m->Kp, kFwdResidual, a, cx.s, &parts));
+        HIP_TRY(launch_reduce_blocks(cx.bsum.p, parts, (int32_t)bm.rows, nullptr, cx.acc.p, cx.s, false));
+        HIP_TRY(launch_auc_keys(cx.yhat.p, d->y.p + bm.row0, group ? dg.p + bm.row0 : nullptr, bm.rows, words.p + bm.row0, cx.s));
+    }
+    HIP_TRY(auc_from_words(words.p, n, end_bit, cx.s, &sums));
+    if (stats) {
+        double h[5];
+        HIP_TRY(hipMemcpyAsync(h, cx.acc.p, sizeof h, hipMemcpyDeviceToHost, cx.s));
+        HIP_TRY(hipStreamSynchronize(cx.s));
+        stats->sum_e = h[0];
+        stats->sse = h[1];
+        stats->rows = (int64_t)llround(h[2]);
+        stats->nonfinite = (int64_t)llround(h[3]);
+    }
+    auc_fill(out, sums, n);
     return FMHIP_OK;
 }
 

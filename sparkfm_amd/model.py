@@ -241,6 +241,30 @@ class FMModel(Model):
         (fmhip_pair_logloss's concordance)."""
         return self._pair_score(dataset)[1]
 
+    def aucDetails(self, dataset, groups=None, stats=False):
+        """Every field of fmhip_auc's result as a dict — u2, pairs, positives, negatives, groups, groups_scored, auc, gauc (and,
+        with stats=True, "stats": what computeRMSE's pass reports) — for the model's predictions on `dataset` against the labels
+        t = [y > 0].  `groups`: None (one group), or one integer id in [0, 2^31) per row — only pairs of rows that share an id
+        count.  Ranked on the device as the fp32 values `predict` returns, exactly: -0 ties with +0, NaN ranks below -inf."""
+        res, st = _ffi.AucResult(), _ffi.Stats()
+        g = _ffi.group_ids(groups, dataset.size)
+        _ffi.check(_ffi.load().fmhip_auc(self.handle, dataset.handle, _ffi.ptr(g), C.byref(res), C.byref(st) if stats else None))
+        out = res.as_dict()
+        if stats:
+            out["stats"] = st.as_dict()
+        return out
+
+    def computeAUC(self, dataset, groups=None):
+        """Area under the ROC curve of the model's predictions on `dataset` (fmhip_auc): the share of (positive, negative) pairs
+        the model orders correctly, a tie counting one half; with `groups`, over the pairs inside a group only.  nan when there
+        is no such pair."""
+        return self.aucDetails(dataset, groups)["auc"]
+
+    def computeGroupAUC(self, dataset, groups):
+        """GAUC: the AUC inside each group (a user's impressions) averaged by the groups' row counts, over the groups that hold
+        both classes; nan when there is none."""
+        return self.aucDetails(dataset, groups)["gauc"]
+
     def residual(self, dataset):
         """ALS.precomputeTermE (S/fm/lib/ALS.scala:142-144): e = predict - target."""
         out = np.empty(dataset.size)
