@@ -1,6 +1,6 @@
 // fmhip_internal.h — host-side state behind the opaque handles of include/fmhip.h / fmhip_experimental.h, shared by the
-// translation units of libfmhip.so (fmhip_api.hip: the C ABI of models, scoring and training; fmhip_dataset.hip:
-// datasets; fmhip_step.hip: the single-GPU step in pieces; fmhip_comm.hip: the data-parallel step).
+// translation units of libfmhip.so (fmhip_api.hip: the C ABI of models and training; fmhip_score.hip: of scoring;
+// fmhip_dataset.hip: datasets; fmhip_step.hip: the single-GPU step in pieces; fmhip_comm.hip: the data-parallel step).
 // Not installed, not part of the ABI.
 #pragma once
 #include "../../include/fmhip_experimental.h"   // (includes fmhip.h: the library implements both surfaces)
@@ -8,6 +8,7 @@
 #include "fm_kernels.h"
 #include "fmhip_host.h"   // the pure host arithmetic (shards, relabelling, batch metadata, band plan, ALS levels, the dp plan's cuts and shares)
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstring>
@@ -157,10 +158,10 @@ struct ProfRec {
     int64_t step;       // the step (fmhip_model::prof_step) the launch belongs to
 };
 
-// What ONE scoring call (predict / rmse / residual / term_q) works in: its own stream and workspace, so that any number of
-// host threads may score through one frozen model at once (the reference's `predict` runs on executor task threads over a
-// read-only model, S/Model.scala:14 under `local[*]`, S/driver.scala:14).  Pooled per model; a call takes a free one or
-// makes one (fmhip_api.hip: ScoreLease).
+// What ONE scoring call (every entry point of fmhip_score.hip that takes a model) works in: its own stream and workspace, so
+// that any number of host threads may score through one frozen model at once (the reference's `predict` runs on executor task
+// threads over a read-only model, S/Model.scala:14 under `local[*]`, S/driver.scala:14).  Pooled per model; a call takes a free
+// one or makes one (fmhip_score.hip: ScoreLease, inside ScorePass).
 struct ScoreCtx {
     hipStream_t s = nullptr;
     hipEvent_t ev = nullptr;        // orders the call behind what the model's own stream has queued (an asynchronous step)
@@ -329,11 +330,13 @@ int partition_rows_locked(fmhip_dataset_t d, int64_t cut_feature);      // fmhip
 // ---- fmhip_step.hip
 int ensure_workspace(fmhip_model_t m, fmhip_dataset_t d);
 FwdArgs fwd_args(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm);
+// ... of a forward that is not the training forward: outputs of the caller's (nullptr: not written), the residual of `loss`
+FwdArgs fwd_args_out(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm, float *P, float *e, double *bsum, float *yhat, int loss);
 int check_pair(fmhip_model_t m, fmhip_dataset_t d);
 int check_train(fmhip_model_t m, fmhip_dataset_t d);      // + the dataset must have its transposes (and, for a paired model, even batches)
 int check_even_batches(fmhip_dataset_t d);                // pairs (rows 2j, 2j+1) must not straddle batches
 int check_batch(fmhip_dataset_t d, int64_t batch);
-// the pieces of one mini-batch step, all asynchronous on m->stream (fmhip_api.hip)
+// the pieces of one mini-batch step, all asynchronous on m->stream
 int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b);
 // the step size and the regularisation of one SGD step (the C entry points take them one by one)
 struct Sgd {
@@ -382,6 +385,16 @@ int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t 
 // none)?  Under AdaGrad only without decay (`r`: the rule to judge by — the model's own, or the one a plan agreed)
 bool lazy_decay_ok(fmhip_model_t m, const Sgd &s, const TrainRule &r);
 int read_scal(fmhip_model_t m, fmhip_stats *st);
+// the four leading numbers of a statistics block {sum e, sum e^2, rows, rows with a non-finite prediction} (the packed gradient's
+// fp32 head, an fp64 accumulator) into *st; nnz, steps and what a fifth slot means are the caller's
+template <typename T>
+inline void fill_stats(fmhip_stats *st, const T *h) {
+    auto count = [](double x) { return (int64_t)llround(x); };
+    st->sum_e = h[0];
+    st->sse = h[1];
+    st->rows = count(h[2]);
+    st->nonfinite = count(h[3]);
+}
 
 }  // namespace host
 }  // namespace fmhip

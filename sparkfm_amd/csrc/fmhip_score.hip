@@ -1,0 +1,510 @@
+// fmhip_score.hip — the C ABI's scoring calls: predictions, residuals, q, RMSE / log-loss / pairwise log-loss (include/fmhip.h,
+// fmhip_pairing.h), ROC AUC (fmhip_metrics.h), top-K and pair scores (fmhip_topk.h).  They hold the model's lock SHARED and touch
+// nothing of it but its parameters: every call works on a stream and in a workspace of its own (ScoreCtx), so any number of host
+// threads score through one model at once.  ScorePass is what they all share; the kernels are fm_forward / fm_pairing / fm_auc /
+// fm_topk .hip.
+#include "fmhip_internal.h"
+#include "../../include/fmhip_topk.h"
+#include "../../include/fmhip_metrics.h"
+#include "fm_topk.h"
+#include "fm_pairing.h"
+#include "fm_auc.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <functional>
+#include <memory>
+#include <new>
+#include <vector>
+
+using namespace fmhip;
+using namespace fmhip::host;
+
+namespace {
+
+// What a call's forwards write into the workspace: per array the most rows one forward covers (-1: the call never asks for it),
+// and whether the call sums statistics (the accumulator: five fp64 slots).
+struct ScoreNeeds {
+    int64_t e, yhat, P;
+    bool stats;
+};
+
+// where one forward puts the q rows [rows][Kp], the residuals and the predictions (nullptr: not written)
+struct ScoreOut {
+    float *P, *e, *yhat;
+};
+
+// for a forward that writes no statistic partials itself: the launch behind it that does (into bsum, *parts of them)
+using PartialsBy = std::function<hipError_t(double *bsum, int *parts)>;
+
+// One scoring call's pass over the batches of its dataset(s): begin() once, forward() per batch, read() for the sums.  It works
+// in a ScoreCtx taken from the model's pool (or made), given back when the call returns.
+// DESTRUCTOR ORDER: a call declares the device buffers of its own BEFORE its ScorePass (in a struct: as earlier members) — locals
+// die in reverse, so ~ScorePass has drained the stream by the time those buffers are freed, on every return path.
+struct ScorePass {
+    fmhip_model_t m;
+    ScoreCtx *ctx = nullptr;
+    bool stats = false;
+    explicit ScorePass(fmhip_model_t m_) : m(m_) {}
+    ScoreCtx &cx() const { return *ctx; }
+    ~ScorePass() {
+        if (!ctx) return;
+        (void)hipStreamSynchronize(ctx->s);       // an early error return must not hand a busy workspace to the next call
+        std::lock_guard<std::mutex> g(m->pool_mu);
+        m->ctx_free.push_back(ctx);
+    }
+    int lease() {
+        {
+            std::lock_guard<std::mutex> g(m->pool_mu);
+            if (!m->ctx_free.empty()) {
+                ctx = m->ctx_free.back();
+                m->ctx_free.pop_back();
+                return FMHIP_OK;
+            }
+        }
+        std::unique_ptr<ScoreCtx> fresh(new (std::nothrow) ScoreCtx());
+        if (!fresh) return fail(FMHIP_ERR_NOMEM, "out of host memory");
+        HIP_TRY(hipStreamCreateWithFlags(&fresh->s, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&fresh->ev, hipEventDisableTiming));
+        std::lock_guard<std::mutex> g(m->pool_mu);
+        ctx = fresh.get();
+        m->ctx_all.push_back(std::move(fresh));
+        return FMHIP_OK;
+    }
+
+    // the lease; the workspace at the sizes asked for; the stream behind the model's own; the accumulator at zero
+    int begin(const ScoreNeeds &n) {
+        TRY(lease());
+        ScoreCtx &c = cx();
+        auto rows = [](int64_t r) { return (size_t)std::max<int64_t>(r, 1); };
+        if (n.e >= 0) TRY(c.e.ensure(rows(n.e)));
+        if (n.yhat >= 0) TRY(c.yhat.ensure(rows(n.yhat)));
+        if (n.P >= 0) TRY(c.P.ensure(rows(n.P) * m->Kp));
+        TRY(c.bsum.ensure((size_t)kMaxFwdBlocks * 4));
+        stats = n.stats;
+        if (stats) TRY(c.acc.ensure(5));
+        // behind whatever the model's own stream still has queued (a training step returns before it has run)
+        HIP_TRY(hipEventRecord(c.ev, m->stream));
+        HIP_TRY(hipStreamWaitEvent(c.s, c.ev, 0));
+        if (stats) HIP_TRY(hipMemsetAsync(c.acc.p, 0, 5 * sizeof(double), c.s));
+        return FMHIP_OK;
+    }
+
+    // The forward of batch `bm` of `d` in `mode` under `loss` into `o` and, when the call sums statistics, the block reduction of
+    // its partials into the accumulator (`fifth`: also slot 4, the sum of the rows' log-losses).  With `partials_by` the forward
+    // writes no partials: that launch runs between the two and supplies them.
+    int forward(fmhip_dataset_t d, const BatchMeta &bm, FwdMode mode, const ScoreOut &o, int loss, bool fifth = false,
+                const PartialsBy &partials_by = nullptr) {
+        ScoreCtx &c = cx();
+        const FwdArgs a = fwd_args_out(m, d, bm, o.P, o.e, partials_by ? nullptr : c.bsum.p, o.yhat, loss);
+        int parts = 0;
+        HIP_TRY(launch_forward(m->Kp, mode, a, c.s, stats && !partials_by ? &parts : nullptr));
+        if (partials_by) HIP_TRY(partials_by(c.bsum.p, &parts));
+        if (stats) HIP_TRY(launch_reduce_blocks(c.bsum.p, parts, (int32_t)bm.rows, nullptr, c.acc.p, c.s, fifth));
+        return FMHIP_OK;
+    }
+
+    // the accumulator's five sums (synchronises); st given: its four leading fields from slots 0..3, everything else zero
+    int read(fmhip_stats *st, double h[5]) {
+        HIP_TRY(hipMemcpyAsync(h, cx().acc.p, 5 * sizeof(double), hipMemcpyDeviceToHost, cx().s));
+        HIP_TRY(hipStreamSynchronize(cx().s));
+        if (st) {
+            memset(st, 0, sizeof *st);
+            fill_stats(st, h);
+        }
+        return FMHIP_OK;
+    }
+
+    // [rows][ld] floats on the device -> the leading `cols` of every row, widened, to out[rows][cols]: one copy on the pass's
+    // stream through the reusable host buffer `h`, one synchronisation
+    int copy_back(const float *dev, int64_t rows, int ld, int cols, std::vector<float> &h, double *out) {
+        h.resize((size_t)rows * ld);
+        HIP_TRY(hipMemcpyAsync(h.data(), dev, h.size() * sizeof(float), hipMemcpyDeviceToHost, cx().s));
+        HIP_TRY(hipStreamSynchronize(cx().s));
+        for (int64_t r = 0; r < rows; ++r)
+            for (int f = 0; f < cols; ++f) out[r * cols + f] = (double)h[(size_t)r * ld + f];
+        return FMHIP_OK;
+    }
+};
+
+// One pass of FMModel.predict over a dataset's rows.  The scoring calls are the reference's formulas whatever the model's
+// training loss; logloss (fmhip_logloss) scores under the logistic loss instead: st's sums are over e = sigma(yhat) - t and
+// *logloss = the sum of the rows' log-losses.
+int score_pass(fmhip_model_t m, fmhip_dataset_t d, double *yhat, double *e_out, double *q_out, fmhip_stats *st,
+               double *logloss = nullptr) {
+    TRY(check_pair(m, d));
+    ScorePass pass(m);
+    TRY(pass.begin({d->max_rows, yhat ? d->max_rows : -1, q_out ? d->max_rows : -1, true}));     // (P: only to hand q back)
+    ScoreCtx &cx = pass.cx();
+    const ScoreOut out{q_out ? cx.P.p : nullptr, cx.e.p, yhat ? cx.yhat.p : nullptr};
+    std::vector<float> hbuf;
+    for (const BatchMeta &bm : d->batches) {
+        TRY(pass.forward(d, bm, q_out ? kFwdQ : kFwdResidual, out, logloss ? kLossLogistic : kLossSquared, logloss != nullptr));
+        if (yhat) TRY(pass.copy_back(cx.yhat.p, bm.rows, 1, 1, hbuf, yhat + bm.row0));
+        if (e_out) TRY(pass.copy_back(cx.e.p, bm.rows, 1, 1, hbuf, e_out + bm.row0));
+        if (q_out) TRY(pass.copy_back(cx.P.p, bm.rows, m->Kp, m->k, hbuf, q_out + bm.row0 * m->k));
+    }
+    if (st) {
+        double h[5];
+        TRY(pass.read(st, h));
+        st->nnz = d->nnz;
+        if (logloss) *logloss = h[4];
+    }
+    return FMHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmhip_predict(fmhip_model_t m, fmhip_dataset_t d, double *yhat) {
+    ReadLock lock(m);
+    if (!yhat) return fail(FMHIP_ERR_INVALID, "yhat is NULL");
+    return score_pass(m, d, yhat, nullptr, nullptr, nullptr);
+}
+
+int fmhip_predict_rows(fmhip_model_t m, int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const double *val,
+                       double *yhat) {
+    ReadLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    if (n_rows > 0 && !yhat) return fail(FMHIP_ERR_INVALID, "yhat is NULL");
+    fmhip_dataset_t d = nullptr;
+    TRY(fmhip_rows_create(m->device, n_rows, row_ptr, col, val, nullptr, &d));      // scoring-only upload (fmhip_dataset.hip)
+    const int rc = n_rows > 0 ? score_pass(m, d, yhat, nullptr, nullptr, nullptr) : FMHIP_OK;
+    fmhip_dataset_destroy(d);
+    return rc;
+}
+
+int fmhip_residual(fmhip_model_t m, fmhip_dataset_t d, double *e) {
+    ReadLock lock(m);
+    if (!e) return fail(FMHIP_ERR_INVALID, "e is NULL");
+    return score_pass(m, d, nullptr, e, nullptr, nullptr);
+}
+
+int fmhip_term_q(fmhip_model_t m, fmhip_dataset_t d, double *q) {
+    ReadLock lock(m);
+    if (!q) return fail(FMHIP_ERR_INVALID, "q is NULL");
+    return score_pass(m, d, nullptr, nullptr, q, nullptr);
+}
+
+int fmhip_rmse(fmhip_model_t m, fmhip_dataset_t d, double *rmse, fmhip_stats *stats) {
+    ReadLock lock(m);
+    if (!rmse) return fail(FMHIP_ERR_INVALID, "rmse is NULL");
+    fmhip_stats st;
+    TRY(score_pass(m, d, nullptr, nullptr, nullptr, &st));
+    // S/Model.scala:13-19: sqrt(sum (y - yhat)^2 / size); (y - yhat)^2 == e^2
+    *rmse = st.rows > 0 ? std::sqrt(st.sse / (double)st.rows) : 0.0;
+    if (stats) *stats = st;
+    return FMHIP_OK;
+}
+
+int fmhip_logloss(fmhip_model_t m, fmhip_dataset_t d, double *logloss, fmhip_stats *stats) {
+    ReadLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    if (!logloss) return fail(FMHIP_ERR_INVALID, "logloss is NULL");
+    fmhip_stats st;
+    double sum_l = 0.0;
+    TRY(score_pass(m, d, nullptr, nullptr, nullptr, &st, &sum_l));
+    *logloss = st.rows > 0 ? sum_l / (double)st.rows : 0.0;
+    if (stats) *stats = st;
+    return FMHIP_OK;
+}
+
+// Pairwise ranking score of the pairs (2j, 2j+1) of `d`, whatever the model's loss or pairing: per batch one residual-mode forward
+// for the predictions only, then k_pair_score's per-block partials and the block reduction of fmhip_logloss (fp64 sums).
+int fmhip_pair_logloss(fmhip_model_t m, fmhip_dataset_t d, double *logloss, double *concordance, fmhip_stats *stats) {
+    ReadLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    if (!logloss) return fail(FMHIP_ERR_INVALID, "logloss is NULL");
+    TRY(check_pair(m, d));
+    TRY(check_even_batches(d));
+    ScorePass pass(m);
+    TRY(pass.begin({-1, std::max<int64_t>(d->max_rows, 2), -1, true}));
+    ScoreCtx &cx = pass.cx();
+    for (const BatchMeta &bm : d->batches)
+        TRY(pass.forward(d, bm, kFwdResidual, ScoreOut{nullptr, nullptr, cx.yhat.p}, kLossSquared, true, [&](double *bsum, int *parts) {
+            return launch_pair_score(cx.yhat.p, d->y.p + bm.row0, (int32_t)(bm.rows / 2), bsum, cx.s, parts);
+        }));
+    double h[5];       // {concordant pairs, sum e^2, rows, rows with a non-finite prediction, sum of the pairs' log-losses}
+    TRY(pass.read(stats, h));
+    const double pairs = (double)(d->n_rows / 2);
+    *logloss = pairs > 0 ? h[4] / pairs : 0.0;
+    if (concordance) *concordance = pairs > 0 ? h[0] / pairs : 0.0;
+    if (stats) {
+        stats->sum_e = 0.0;        // e_2j = -e_2j+1
+        stats->nnz = d->nnz;
+    }
+    return FMHIP_OK;
+}
+
+// ---- ROC AUC and per-group AUC (include/fmhip_metrics.h) ---------------------------------------------------------------------
+// One 64-bit word per row (group, key of the prediction, label), sorted; the counts are read off the sorted words (fm_auc.hip).
+// fmhip_auc forms the words batch by batch behind the residual-mode forward, fmhip_auc_scores from the caller's arrays: the two
+// share every line after that.
+namespace {
+
+// the refusals that touch neither a handle nor a device
+int auc_check_out(fmhip_auc_result *out) {
+    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    if (out->struct_size != (int32_t)sizeof(fmhip_auc_result))
+        return fail(FMHIP_ERR_INVALID, "out->struct_size is %d, not sizeof(fmhip_auc_result) = %d", (int)out->struct_size,
+                    (int)sizeof(fmhip_auc_result));
+    return FMHIP_OK;
+}
+int auc_check_rows(int64_t n) {
+    if (n < 0) return fail(FMHIP_ERR_INVALID, "n = %lld is negative", (long long)n);
+    if (n > 0x7fffffffll) return fail(FMHIP_ERR_UNSUPPORTED, "%lld rows: the AUC calls take fewer than 2^31", (long long)n);
+    return FMHIP_OK;
+}
+// the ids must be >= 0; *end_bit: the bits of a word the sort has to look at (33 + what the largest id needs)
+int auc_check_groups(const int32_t *group, int64_t n, int *end_bit) {
+    int32_t top = 0;
+    if (group)
+        for (int64_t r = 0; r < n; ++r) {
+            if (group[r] < 0) return fail(FMHIP_ERR_INVALID, "group id %d of row %lld is negative", (int)group[r], (long long)r);
+            top = group[r] > top ? group[r] : top;
+        }
+    int bits = 0;
+    while (bits < 31 && ((int64_t)top >> bits) != 0) ++bits;
+    *end_bit = kAucGroupShift + bits;
+    return FMHIP_OK;
+}
+void auc_fill(fmhip_auc_result *out, const AucSums &a, int64_t n) {
+    const double nan = std::nan("");
+    out->reserved = 0;
+    out->u2 = a.u2;
+    out->pairs = (int64_t)a.pairs;
+    out->negatives = (int64_t)a.negatives;
+    out->positives = n - (int64_t)a.negatives;
+    out->groups = (int64_t)a.groups;
+    out->groups_scored = (int64_t)a.groups_scored;
+    out->auc = a.pairs ? (double)a.u2 / (2.0 * (double)a.pairs) : nan;
+    // one scored group: its AUC itself (the weighted mean of one number), so that gauc == auc bit for bit without groups
+    out->gauc = a.groups_scored == 0 ? nan : (a.groups_scored == 1 ? out->auc : a.gauc_num / (double)a.rows_scored);
+}
+struct OwnStream {
+    hipStream_t s = nullptr;
+    ~OwnStream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+}  // namespace
+
+int fmhip_auc_scores(int device, int64_t n, const float *score, const float *y, const int32_t *group, fmhip_auc_result *out) {
+    TRY(auc_check_out(out));
+    TRY(auc_check_rows(n));
+    if (n > 0 && (!score || !y)) return fail(FMHIP_ERR_INVALID, "score or y is NULL");
+    int end_bit = 0;
+    TRY(auc_check_groups(group, n, &end_bit));
+    AucSums sums{};
+    if (n == 0) {
+        auc_fill(out, sums, 0);
+        return FMHIP_OK;
+    }
+    TRY(set_device(device));
+    DevBuf<float> ds, dy;
+    DevBuf<int32_t> dg;
+    DevBuf<unsigned long long> words;
+    OwnStream st;            // (declared after the buffers: destroyed, and so drained, before they are freed)
+    TRY(ds.alloc((size_t)n));
+    TRY(dy.alloc((size_t)n));
+    if (group) TRY(dg.alloc((size_t)n));
+    TRY(words.alloc((size_t)n));
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    HIP_TRY(hipMemcpyAsync(ds.p, score, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st.s));
+    HIP_TRY(hipMemcpyAsync(dy.p, y, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st.s));
+    if (group) HIP_TRY(hipMemcpyAsync(dg.p, group, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st.s));
+    HIP_TRY(launch_auc_keys(ds.p, dy.p, dg.p, n, words.p, st.s));
+    HIP_TRY(auc_from_words(words.p, n, end_bit, st.s, &sums));
+    auc_fill(out, sums, n);
+    return FMHIP_OK;
+}
+
+int fmhip_auc(fmhip_model_t m, fmhip_dataset_t d, const int32_t *group, fmhip_auc_result *out, fmhip_stats *stats) {
+    TRY(auc_check_out(out));
+    ReadLock lock(m);
+    if (!m || !d) return fail(FMHIP_ERR_INVALID, "model or dataset is NULL");
+    const int64_t n = d->n_rows;
+    TRY(auc_check_rows(n));
+    TRY(check_pair(m, d));
+    int end_bit = 0;
+    TRY(auc_check_groups(group, n, &end_bit));
+    AucSums sums{};
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        stats->nnz = d->nnz;
+    }
+    if (n == 0) {
+        auc_fill(out, sums, 0);
+        return FMHIP_OK;
+    }
+    DevBuf<int32_t> dg;
+    DevBuf<unsigned long long> words;
+    ScorePass pass(m);
+    TRY(words.alloc((size_t)n));
+    if (group) TRY(dg.alloc((size_t)n));
+    TRY(pass.begin({d->max_rows, d->max_rows, -1, true}));
+    ScoreCtx &cx = pass.cx();
+    if (group) HIP_TRY(hipMemcpyAsync(dg.p, group, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
+    for (const BatchMeta &bm : d->batches) {
+        // the forward of fmhip_rmse / fmhip_predict: the same predictions, the same statistics; then the rows' words
+        TRY(pass.forward(d, bm, kFwdResidual, ScoreOut{nullptr, cx.e.p, cx.yhat.p}, kLossSquared));
+        HIP_TRY(launch_auc_keys(cx.yhat.p, d->y.p + bm.row0, group ? dg.p + bm.row0 : nullptr, bm.rows, words.p + bm.row0, cx.s));
+    }
+    HIP_TRY(auc_from_words(words.p, n, end_bit, cx.s, &sums));
+    if (stats) {
+        double h[5];
+        TRY(pass.read(stats, h));
+        stats->nnz = d->nnz;
+    }
+    auc_fill(out, sums, n);
+    return FMHIP_OK;
+}
+
+// ---- top-K recommendation (include/fmhip_topk.h) ----------------------------------------------------------------------------
+// score(c, d) = (yhat(c) + (yhat(d) - w0)) + sum_f q_f(c) q_f(d): one kFwdQ forward per row set — it writes q into a [rows][Kp]
+// table and yhat beside it in one launch — then the product and the selection of fm_topk.hip.  The tables live for the length of
+// the call only.
+namespace {
+
+// what both calls share: the checks, the pass, the candidates' table Qd [M][Kp] and predictions yd [M]
+struct PairJob {
+    fmhip_model_t m;
+    fmhip_dataset_t ctx, cand;
+    DevBuf<float> Qd, yd;
+    ScorePass pass;
+    int64_t B = 0, M = 0;
+    PairJob(fmhip_model_t m_, fmhip_dataset_t c_, fmhip_dataset_t d_) : m(m_), ctx(c_), cand(d_), pass(m_) {}
+    // the kFwdQ forward of one batch of `d`: q rows to Q[rows][Kp], predictions to yhat[rows]
+    int forward_q(fmhip_dataset_t d, const BatchMeta &bm, float *Q, float *yhat) {
+        return pass.forward(d, bm, kFwdQ, ScoreOut{Q, pass.cx().e.p, yhat}, kLossSquared);
+    }
+    int forward_ctx(const BatchMeta &bm) { return forward_q(ctx, bm, pass.cx().P.p, pass.cx().yhat.p); }
+    int begin() {
+        if (!m || !ctx || !cand) return fail(FMHIP_ERR_INVALID, "model, contexts or candidates is NULL");
+        TRY(check_pair(m, ctx));
+        TRY(check_pair(m, cand));
+        B = ctx->n_rows;
+        M = cand->n_rows;
+        if (M > 0x7fffffff) return fail(FMHIP_ERR_INVALID, "%lld candidates: the count must fit an int32", (long long)M);
+        TRY(pass.begin({std::max(ctx->max_rows, cand->max_rows), ctx->max_rows, ctx->max_rows, false}));
+        if (B == 0 || M == 0) return FMHIP_OK;
+        TRY(Qd.alloc((size_t)M * m->Kp));
+        TRY(yd.alloc((size_t)M));
+        for (const BatchMeta &bm : cand->batches) TRY(forward_q(cand, bm, Qd.p + (size_t)bm.row0 * m->Kp, yd.p + bm.row0));
+        return FMHIP_OK;
+    }
+    TopkArgs args(int64_t first, int64_t rows) const {      // for rows [first, first + rows) of the context batch held in cx.P / cx.yhat
+        TopkArgs a{};
+        a.Qc = pass.cx().P.p + (size_t)first * m->Kp;
+        a.yc = pass.cx().yhat.p + first;
+        a.Qd = Qd.p;
+        a.yd = yd.p;
+        a.w0 = m->w0.p;
+        a.B = (int32_t)rows;
+        a.M = (int32_t)M;
+        return a;
+    }
+};
+
+}  // namespace
+
+int fmhip_topk(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candidates, int32_t k, const int64_t *excl_ptr,
+               const int32_t *excl, int32_t *idx, double *score) {
+    ReadLock lock(m);
+    if (!m || !contexts || !candidates) return fail(FMHIP_ERR_INVALID, "model, contexts or candidates is NULL");
+    if (!idx) return fail(FMHIP_ERR_INVALID, "idx is NULL");
+    if (k < 1 || k > FMHIP_TOPK_MAX) return fail(FMHIP_ERR_INVALID, "k = %d outside [1, %d]", (int)k, FMHIP_TOPK_MAX);
+    if ((excl_ptr == nullptr) != (excl == nullptr))
+        return fail(FMHIP_ERR_INVALID, "excl_ptr and excl must both be given or both be NULL");
+    const int64_t B = contexts->n_rows, M = candidates->n_rows;
+    if (excl_ptr) {
+        if (excl_ptr[0] < 0) return fail(FMHIP_ERR_INVALID, "excl_ptr[0] < 0");
+        for (int64_t c = 0; c < B; ++c)      // (the offsets first: nothing of excl is read through a bad one)
+            if (excl_ptr[c + 1] < excl_ptr[c]) return fail(FMHIP_ERR_INVALID, "excl_ptr decreases at context %lld", (long long)c);
+        for (int64_t c = 0; c < B; ++c) {
+            for (int64_t p = excl_ptr[c]; p < excl_ptr[c + 1]; ++p) {
+                if (excl[p] < 0 || excl[p] >= M)
+                    return fail(FMHIP_ERR_INVALID, "context %lld excludes candidate %d outside [0, %lld)", (long long)c, (int)excl[p], (long long)M);
+                if (p > excl_ptr[c] && excl[p] <= excl[p - 1])
+                    return fail(FMHIP_ERR_INVALID, "the exclusions of context %lld are not ascending and distinct", (long long)c);
+            }
+        }
+    }
+    DevBuf<int64_t> d_eptr;
+    DevBuf<int32_t> d_excl, d_idx;
+    DevBuf<float> d_score;
+    DevBuf<unsigned long long> part;
+    PairJob job(m, contexts, candidates);
+    TRY(job.begin());
+    if (B == 0) return FMHIP_OK;
+    if (M == 0) {
+        for (int64_t i = 0; i < B * k; ++i) idx[i] = -1;
+        if (score) for (int64_t i = 0; i < B * k; ++i) score[i] = -HUGE_VAL;
+        return FMHIP_OK;
+    }
+    ScoreCtx &cx = job.pass.cx();
+    if (excl_ptr) {
+        TRY(d_eptr.alloc((size_t)B + 1));
+        TRY(d_excl.alloc((size_t)std::max<int64_t>(excl_ptr[B], 1)));
+        HIP_TRY(hipMemcpyAsync(d_eptr.p, excl_ptr, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, cx.s));
+        if (excl_ptr[B] > 0) HIP_TRY(hipMemcpyAsync(d_excl.p, excl, (size_t)excl_ptr[B] * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
+    }
+    const size_t rows_max = (size_t)contexts->max_rows;
+    TRY(d_idx.alloc(rows_max * k));
+    TRY(d_score.alloc(rows_max * k));
+    std::vector<float> h_score;
+    for (const BatchMeta &bm : contexts->batches) {       // a chunk of contexts = a batch of their dataset
+        TRY(job.forward_ctx(bm));
+        TopkArgs a = job.args(0, bm.rows);
+        a.K = k;
+        const int splits = topk_splits(bm.rows, M, &a.split_len);
+        TRY(part.ensure((size_t)bm.rows * splits * k));
+        a.part = part.p;
+        a.excl_ptr = excl_ptr ? d_eptr.p + bm.row0 : nullptr;
+        a.excl = d_excl.p;
+        HIP_TRY(launch_pair_topk(m->Kp, a, cx.s));
+        HIP_TRY(launch_topk_merge(part.p, (int32_t)bm.rows, splits, k, d_idx.p, d_score.p, cx.s));
+        HIP_TRY(hipMemcpyAsync(idx + bm.row0 * k, d_idx.p, (size_t)bm.rows * k * sizeof(int32_t), hipMemcpyDeviceToHost, cx.s));
+        // one synchronisation for both copies
+        if (score) TRY(job.pass.copy_back(d_score.p, bm.rows * k, 1, 1, h_score, score + (size_t)bm.row0 * k));
+        else HIP_TRY(hipStreamSynchronize(cx.s));
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_pair_scores(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candidates, int64_t c0, int64_t c1, double *out) {
+    ReadLock lock(m);
+    if (!m || !contexts || !candidates) return fail(FMHIP_ERR_INVALID, "model, contexts or candidates is NULL");
+    if (c0 < 0 || c1 < c0 || c1 > contexts->n_rows)
+        return fail(FMHIP_ERR_INVALID, "contexts [%lld, %lld) outside [0, %lld]", (long long)c0, (long long)c1, (long long)contexts->n_rows);
+    const int64_t M = candidates->n_rows;
+    if (c1 > c0 && M > 0 && !out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    DevBuf<float> d_out;
+    PairJob job(m, contexts, candidates);
+    TRY(job.begin());
+    if (c1 == c0 || M == 0) return FMHIP_OK;
+    ScoreCtx &cx = job.pass.cx();
+    // the scores travel in pieces of at most 2^25 floats (whole context rows)
+    const int64_t piece_rows = std::max<int64_t>(1, ((int64_t)1 << 25) / std::max<int64_t>(M, 1));
+    TRY(d_out.alloc((size_t)std::min(piece_rows, c1 - c0) * M));
+    std::vector<float> h_out;
+    for (const BatchMeta &bm : contexts->batches) {
+        const int64_t lo = std::max(c0, bm.row0), hi = std::min(c1, bm.row0 + bm.rows);
+        if (lo >= hi) continue;
+        TRY(job.forward_ctx(bm));
+        for (int64_t r0 = lo; r0 < hi; r0 += piece_rows) {
+            const int64_t rows = std::min(piece_rows, hi - r0);
+            TopkArgs a = job.args(r0 - bm.row0, rows);
+            (void)topk_splits(rows, M, &a.split_len);
+            a.out = d_out.p;
+            HIP_TRY(launch_pair_scores(m->Kp, a, cx.s));
+            TRY(job.pass.copy_back(d_out.p, rows * M, 1, 1, h_out, out + (size_t)(r0 - c0) * M));
+        }
+    }
+    return FMHIP_OK;
+}
+
+}  // extern "C"

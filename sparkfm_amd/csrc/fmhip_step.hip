@@ -1,8 +1,9 @@
 // fmhip_step.hip — the launch sequence of one mini-batch step on one GPU, in pieces:
 //     step_forward -> step_backward (whole, or one feature interval at a time) -> [exchange, fmhip_comm.hip] -> step_apply*
-// plus the argument blocks of the kernels (fwd_args / bwd_args), the planning of where the update runs (plan_fused: a launch
-// of its own, inside the fixup launch, inside the column walk) and the lazily decayed tables' bookkeeping.  Everything is
-// asynchronous on the model's stream; the arithmetic lives in fm_forward.hip / fm_backward.hip / fm_apply.hip.
+// plus the argument blocks of the kernels (fwd_args / bwd_args; fwd_args_out: a forward with outputs of the caller's, as the
+// scoring calls of fmhip_score.hip launch it), the planning of where the update runs (plan_fused: a launch of its own, inside
+// the fixup launch, inside the column walk) and the lazily decayed tables' bookkeeping.  Everything here is asynchronous on the
+// model's stream; the arithmetic lives in fm_forward.hip / fm_backward.hip / fm_apply.hip.
 #include "fmhip_internal.h"
 #include "fm_pairing.h"
 
@@ -151,6 +152,16 @@ FwdArgs fwd_args(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm) {
     return a;
 }
 
+FwdArgs fwd_args_out(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm, float *P, float *e, double *bsum, float *yhat, int loss) {
+    FwdArgs a = fwd_args(m, d, bm);
+    a.P = P;
+    a.e = e;
+    a.bsum = bsum;
+    a.yhat = yhat;
+    a.loss = loss;
+    return a;
+}
+
 BwdArgs bwd_args(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
     const BatchMeta &bm = d->batches[(size_t)b];
     BwdArgs a{};
@@ -242,11 +253,8 @@ int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
         // partials (its own block count: the backward's finish sums m->fwd_parts of them)
         // (check_train has refused datasets whose batches would cut a pair)
         ProfScope ps(m, FMHIP_K_FORWARD, bm.nnz_total, bm.rows);
-        FwdArgs a = fwd_args(m, d, bm);
-        a.e = nullptr;
-        a.bsum = nullptr;
-        a.yhat = m->yhat.p;
-        a.loss = kLossSquared;            // (the q-mode has one instance; its residual goes nowhere)
+        // (the q-mode has one instance, the squared loss's; its residual goes nowhere)
+        const FwdArgs a = fwd_args_out(m, d, bm, m->P.p, nullptr, nullptr, m->yhat.p, kLossSquared);
         HIP_TRY(launch_forward(m->Kp, kFwdQ, a, m->stream, nullptr));
         PairArgs pa{};
         pa.P = m->P.p;
@@ -631,10 +639,7 @@ int read_scal(fmhip_model_t m, fmhip_stats *st) {
     float h[4];
     HIP_TRY(hipMemcpyAsync(h, m->scal(), sizeof h, hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
-    st->sum_e = h[0];
-    st->sse = h[1];
-    st->rows = (int64_t)llround(h[2]);
-    st->nonfinite = (int64_t)llround(h[3]);
+    fill_stats(st, h);
     return FMHIP_OK;
 }
 
@@ -642,10 +647,7 @@ int read_acc(fmhip_model_t m, fmhip_stats *st) {
     double h[4];
     HIP_TRY(hipMemcpyAsync(h, m->acc.p, sizeof h, hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
-    st->sum_e = h[0];
-    st->sse = h[1];
-    st->rows = (int64_t)llround(h[2]);
-    st->nonfinite = (int64_t)llround(h[3]);
+    fill_stats(st, h);
     return FMHIP_OK;
 }
 

@@ -1385,3 +1385,43 @@ def test_partitioned_rows_keep_the_als_learner_right(fmhip):
         np.testing.assert_allclose(got[2], v, rtol=1e-8, atol=1e-11)
         np.testing.assert_allclose(got[1], w, rtol=1e-8, atol=1e-11)
     np.testing.assert_allclose(out[1][2], out[0][2], rtol=1e-10, atol=1e-13)
+
+
+@pytest.mark.parametrize("k", [8, 65])
+def test_scoring_calls_share_one_pass(fmhip, k):
+    """What the scoring calls have in common because they run ONE pass (fmhip_score.hip): fmhip_auc's statistics are fmhip_rmse's,
+    bit for bit; fmhip_predict from four threads at once is the serial call; fmhip_residual is predict - y in fp32.  1,000 rows x
+    300 features in batches of 384, 384 and 232 rows, packed rows with 8-lane (k = 8) and 16-lane slots (k = 65); the model is
+    1,001 features wide, so that the SGD epoch's weight decay stays in the tables' scales (sv, sw != 1) when the calls read them."""
+    import ctypes as C
+    import threading
+    from sparkfm_amd import _ffi, synth
+    d = synth.make_zipf(7, 1000, 300, 4, 12, zipf_s=1.05)
+    ds = fmhip.DataSet.from_arrays(d, batch_rows=384).cache()
+    assert [ds.batch_info(b)["rows"] for b in range(ds.n_batches)] == [384, 384, 232]
+    fm = fmhip.FMModel(1000, k)
+    rng = np.random.Generator(np.random.PCG64(11 + k))
+    fm.w0, fm.w, fm.v = 0.1, rng.normal(0.0, 0.05, 1001), rng.normal(0.0, 0.05, (k, 1001))
+    fmhip.HipSGD(eta=0.05, regw=1e-3, regv=1e-3).learn(fm, ds)
+    L, r, st_rmse = _ffi.load(), C.c_double(), _ffi.Stats()
+    _ffi.check(L.fmhip_rmse(fm.handle, ds.handle, C.byref(r), C.byref(st_rmse)))
+    st_auc = fm.aucDetails(ds, stats=True)["stats"]
+    assert st_rmse.rows == 1000 and st_rmse.nonfinite == 0 and st_rmse.nnz == len(d["col"])
+    for name, _ in _ffi.Stats._fields_:
+        assert np.array(getattr(st_rmse, name)).tobytes() == np.array(st_auc[name]).tobytes(), name
+    serial = fm.predict(ds)
+    got = [None] * 4
+
+    def score(i):
+        got[i] = fm.predict(ds)
+    threads = [threading.Thread(target=score, args=(i,)) for i in range(4)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    for g in got:
+        assert g is not None and g.tobytes() == serial.tobytes()
+    e32 = serial.astype(np.float32) - ds.y.astype(np.float32)
+    assert e32.dtype == np.float32 and fm.residual(ds).tobytes() == e32.astype(np.float64).tobytes()
+    ds.unpersist()
+    fm.close()

@@ -3,23 +3,28 @@
 # GPU box: FMHIP_LIB=sparkfm_amd/lib/libfmhip_<name>.so python tools/ab_bench.py ...).
 #   tools/build_variant.sh <name> [git-rev, default HEAD; WORK = the working tree]
 #   EXTRA_FLAGS="-DFOO=1" adds compiler flags (experiment macros)
+# The revision's own sparkfm_amd/_build.py says which translation units it has and which flags they take.
 set -e
 name=$1; rev=${2:-HEAD}
 root=$(cd "$(dirname "$0")/.." && pwd)
 tmp=$(mktemp -d /tmp/fmhip_variant.XXXXXX)
-mkdir -p $tmp/sparkfm_amd/csrc $tmp/include
-for f in fm_forward.hip fm_backward.hip fm_apply.hip fm_device.h fm_kernels.h fm_constants.h als_kernels.hip als_kernels.h csc_build.hip csc_build.h fmhip_api.hip fmhip_dataset.hip fmhip_step.hip fmhip_comm.hip fmhip_internal.h fmhip_host.h fmhip_host.cpp; do
-  if [ "$rev" = WORK ]; then cp $root/sparkfm_amd/csrc/$f $tmp/sparkfm_amd/csrc/$f; else git -C $root show $rev:sparkfm_amd/csrc/$f > $tmp/sparkfm_amd/csrc/$f; fi
-done
-for h in fmhip.h fmhip_experimental.h; do
-  if [ "$rev" = WORK ]; then cp $root/include/$h $tmp/include/$h; else git -C $root show $rev:include/$h > $tmp/include/$h; fi
-done
-objs=""
-for f in fm_forward.hip fm_backward.hip fm_apply.hip als_kernels.hip csc_build.hip fmhip_api.hip fmhip_dataset.hip fmhip_step.hip fmhip_comm.hip fmhip_host.cpp; do
-  /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC ${EXTRA_FLAGS:+-DFMHIP_ABLATION_BUILD} $EXTRA_FLAGS -c $tmp/sparkfm_amd/csrc/$f -o $tmp/${f%.*}.o &
+trap 'rm -rf $tmp' EXIT
+if [ "$rev" = WORK ]; then
+  mkdir -p $tmp/sparkfm_amd
+  cp -r $root/include $tmp/include
+  cp -r $root/sparkfm_amd/csrc $root/sparkfm_amd/_build.py $tmp/sparkfm_amd/
+else
+  git -C $root archive $rev sparkfm_amd/_build.py sparkfm_amd/csrc include | tar -x -C $tmp
+fi
+query() { python3 -c "import sys; sys.path.insert(0, '$tmp/sparkfm_amd'); import _build; print(' '.join(_build.$1))"; }
+sources=$(query HIP_SOURCES); flags=$(query HIPCC_FLAGS)
+objs=""; pids=""
+for f in $sources; do
+  /opt/rocm/bin/hipcc $flags ${EXTRA_FLAGS:+-DFMHIP_ABLATION_BUILD} $EXTRA_FLAGS -c $tmp/sparkfm_amd/csrc/$f -o $tmp/${f%.*}.o &
+  pids="$pids $!"
   objs="$objs $tmp/${f%.*}.o"
 done
-wait
+for p in $pids; do wait $p; done
+mkdir -p $root/sparkfm_amd/lib
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $root/sparkfm_amd/lib/libfmhip_$name.so $objs -Wl,-rpath,/opt/rocm/lib -lpthread -ldl
-rm -rf $tmp
 echo $root/sparkfm_amd/lib/libfmhip_$name.so
