@@ -160,7 +160,8 @@ struct BwdArgs {
     // Band-affine placement (xlist != NULL): workgroup b — dispatched round-robin, so on XCD b % 8 — walks the ranges at
     // positions (b / 8) * SLOTS + slot of XCD b % 8's list, which is the concatenation of up to kXSegs runs of xlist
     // (xseg_off / xseg_len: one run per row band the XCD owns, then its share of the other ranges; a feature-interval
-    // launch passes the sub-runs that fall into its range window).  A range that lies inside one long column covers a
+    // launch passes the sub-runs that fall into its range window; a whole-batch launch ONE run per XCD, the list in the plan's
+    // walk order: the expensive cold ranges first, plan_bands).  A range that lies inside one long column covers a
     // narrow band of rows (a column's entries ascend by row): the plan gives XCD x the ranges of ITS row bands first, so
     // their P rows — 2 MB per band — stay in that XCD's L2 instead of coming from the Infinity Cache, the latency that
     // bounds the gather rate.  Wave sums are off in such a launch (no_wave_sum also tells k_fixup).

@@ -569,13 +569,17 @@ int dataset_create_impl(int device, int64_t n_rows, const int64_t *row_ptr, cons
                     delete d;
                     return fail(FMHIP_ERR_HIP, "range rows of batch %lld: %s", (long long)b, hipGetErrorString(he));
                 }
-                std::vector<int32_t> lists[kXcds];
+                std::vector<int32_t> lists[kXcds], walk[kXcds];
                 BatchMeta &bmw = d->batches[(size_t)b];
-                bmw.x_affine = plan_bands(hb, bm.cnnz, bm.rows, h_first, h_last, lists, bmw.xseg);
+                bmw.x_affine = plan_bands(hb, bm.cnnz, bm.rows, h_first, h_last, lists, bmw.xseg, walk_order_default(), &walk);
                 for (int x = 0; x < kXcds; ++x) {
                     bmw.xoff[x] = (int64_t)xlist_all.size();
                     bmw.xlen[x] = (int32_t)lists[x].size();
                     xlist_all.insert(xlist_all.end(), lists[x].begin(), lists[x].end());
+                }
+                for (int x = 0; x < kXcds; ++x) {                 // the walk order of the same lists (whole-batch launches)
+                    bmw.woff[x] = (int64_t)xlist_all.size();
+                    xlist_all.insert(xlist_all.end(), walk[x].begin(), walk[x].end());
                 }
             }
         }

@@ -144,13 +144,40 @@ void finish_batch_meta(HostBatch &hb, int32_t nnz, std::vector<int32_t> &cnt, st
     }
 }
 
+// cost of walking range rho (fmhip_host.h: kCostUnit per entry, kCloseCost per column that closes inside the range)
+int64_t range_cost(const HostBatch &hb, int32_t cnnz, int32_t rho) {
+    const int32_t n_ranges = (int32_t)hb.range_seg.size();
+    const int32_t beg = rho * kRangeLen, end = std::min(beg + kRangeLen, cnnz);
+    const int32_t nc = (int32_t)hb.cfeat.size();
+    const int32_t closes = (rho + 1 < n_ranges ? hb.range_seg[(size_t)rho + 1] : nc) - hb.range_seg[(size_t)rho];
+    return (int64_t)(end - beg) * kCostUnit + (int64_t)closes * kCloseCost;
+}
+
+int walk_order_default() {
+    if (const char *ev = getenv("FMHIP_BWD_ORDER")) {           // measurement knob: 0 = stream order, 1 = cold first
+        const int v = atoi(ev);
+        if (v == kWalkOrderStream || v == kWalkOrderColdFirst) return v;
+    }
+    return kWalkOrderColdFirst;
+}
+
 // Band-affine placement of one batch's ranges (BwdArgs::xlist).  first/last: the rows of the first and last entry of every
 // range.  A range that lies inside ONE column and spans at most a band and a half of rows is "affine" to the band of its
 // middle row; XCD x owns a run of consecutive bands (two at 250k-row batches) and its list starts with their ranges, band by band,
 // so that one band's slice of P (rows / 16 x 4 Kp bytes: 2 MB at 250k rows of Kp = 32) is what that XCD's L2 holds while
 // they are walked; every other range is "free" and fills the lists up to equal length.  Returns the affine count.
+//
+// kWalkOrderColdFirst also gives every free range a COST, entries + 2.65 x (columns that close inside it) — a stretch of cold
+// features, with a column close and a row store every entry or two, costs the walk up to 3.6 times a hot one per entry —
+// and deals the free blocks, the most expensive first, to the list with the least accumulated cost (a band-affine range
+// counts its entries).  walk[x] is then the order in which a WHOLE-BATCH launch walks list x: the free ranges in that
+// order, then the band runs.  The launch used to END with its most expensive work on all eight XCDs at once — the lists
+// closed with the coldest ranges of the stream — and a workgroup's wave slots are free only when its slowest wave is done;
+// now its last round is the cheapest work there is (C3: backward 120.9 -> 115.4 us, C2 129.9 -> 120.0, C5's width 161.7 ->
+// 146.1; profiles/bwd_dispatch.md).  lists / seg keep the interval form: the same ranges per XCD, every run ascending,
+// which is what a feature-interval launch searches.
 int32_t plan_bands(const HostBatch &hb, int32_t cnnz, int64_t rows, const std::vector<int32_t> &first, const std::vector<int32_t> &last,
-                   std::vector<int32_t> (&lists)[kXcds], int32_t (&seg)[kXcds][kXSegs + 1]) {
+                   std::vector<int32_t> (&lists)[kXcds], int32_t (&seg)[kXcds][kXSegs + 1], int order, std::vector<int32_t> (*walk)[kXcds]) {
     const int32_t n_ranges = (int32_t)hb.range_seg.size();
     // bands of about 16k rows (2 MB of P at Kp = 32, 4 MB at Kp = 64: C3 and C5's width measured the same with 16 and 32
     // bands of 250k rows), a multiple of the XCD count, at most 8 per XCD
@@ -193,6 +220,38 @@ int32_t plan_bands(const HostBatch &hb, int32_t cnnz, int64_t rows, const std::v
     // stretches of the stream alike; handing each XCD one contiguous eighth instead left the XCD with the coldest
     // features far behind the others (C4: backward 203 -> 268 us) — and the lists end within a block of each other.
     constexpr size_t kBlockRanges = 32;
+    if (order != kWalkOrderStream) {
+        // by cost: the blocks (still 32 consecutive ranges each) sorted by descending cost, ties in stream order
+        const size_t n_blocks = (free_ranges.size() + kBlockRanges - 1) / kBlockRanges;
+        std::vector<int64_t> bcost(n_blocks, 0);
+        for (size_t i = 0; i < free_ranges.size(); ++i) bcost[i / kBlockRanges] += range_cost(hb, cnnz, free_ranges[i]);
+        std::vector<int32_t> by_cost(n_blocks);
+        for (size_t i = 0; i < n_blocks; ++i) by_cost[i] = (int32_t)i;
+        std::stable_sort(by_cost.begin(), by_cost.end(), [&](int32_t p, int32_t q) { return bcost[(size_t)p] > bcost[(size_t)q]; });
+        int64_t acc[kXcds];
+        std::vector<int32_t> freew[kXcds];                        // the free part of every list in walk order
+        for (int x = 0; x < kXcds; ++x) acc[x] = (int64_t)lists[x].size() * kRangeLen * kCostUnit;   // band-affine ranges are full
+        for (int32_t bi : by_cost) {
+            int best = 0;
+            for (int x = 1; x < kXcds; ++x)
+                if (acc[x] < acc[best]) best = x;
+            const size_t lo = (size_t)bi * kBlockRanges, hi = std::min(lo + kBlockRanges, free_ranges.size());
+            freew[best].insert(freew[best].end(), free_ranges.begin() + (std::ptrdiff_t)lo, free_ranges.begin() + (std::ptrdiff_t)hi);
+            acc[best] += bcost[(size_t)bi];
+        }
+        for (int x = 0; x < kXcds; ++x) {
+            if (walk) {
+                std::vector<int32_t> &wl = (*walk)[x];
+                wl.clear();
+                wl.insert(wl.end(), freew[x].begin(), freew[x].end());
+                wl.insert(wl.end(), lists[x].begin(), lists[x].end());
+            }
+            std::sort(freew[x].begin(), freew[x].end());          // the interval form's last run ascends
+            lists[x].insert(lists[x].end(), freew[x].begin(), freew[x].end());
+            seg[x][kXSegs] = (int32_t)lists[x].size();
+        }
+        return affine;
+    }
     for (size_t next = 0; next < free_ranges.size(); next += kBlockRanges) {
         int best = 0;
         for (int x = 1; x < kXcds; ++x)
@@ -200,7 +259,10 @@ int32_t plan_bands(const HostBatch &hb, int32_t cnnz, int64_t rows, const std::v
         const size_t hi = std::min(next + kBlockRanges, free_ranges.size());
         lists[best].insert(lists[best].end(), free_ranges.begin() + (std::ptrdiff_t)next, free_ranges.begin() + (std::ptrdiff_t)hi);
     }
-    for (int x = 0; x < kXcds; ++x) seg[x][kXSegs] = (int32_t)lists[x].size();
+    for (int x = 0; x < kXcds; ++x) {
+        seg[x][kXSegs] = (int32_t)lists[x].size();
+        if (walk) (*walk)[x] = lists[x];                          // stream order: the interval form is the walk order
+    }
     return affine;
 }
 

@@ -54,9 +54,23 @@ struct HostBatch {
 void finish_batch_meta(HostBatch &hb, int32_t nnz, std::vector<int32_t> &cnt, std::vector<int32_t> &base);
 
 // Band-affine placement of one batch's ranges (BwdArgs::xlist).  first/last: the rows of the first and last entry of every
-// range.  -> the number of ranges placed by their band; lists[x] = XCD x's range ids, seg[x] = the runs of lists[x]
+// range.  -> the number of ranges placed by their band; lists[x] = XCD x's range ids, seg[x] = the runs of lists[x], each
+// ascending (the INTERVAL form: a feature-interval launch clips every run to its window by binary search).
+// order: how the free ranges (those no band claims) are dealt and in what order a whole-batch launch walks a list —
+//   kWalkOrderStream     in blocks of 32 in stream order (hot features first) to the shortest list; walked as the runs stand
+//   kWalkOrderColdFirst  in blocks of 32, the most expensive block first, to the list of least accumulated cost; a launch
+//                        walks the free ranges in that order and the band runs after them
+// walk (optional): walk[x] = list x in that WALK order (the same ranges as lists[x])
+enum { kWalkOrderStream = 0, kWalkOrderColdFirst = 1 };
+// cost of a range in units of 1 / kCostUnit entries: kCostUnit per entry + kCloseCost per column that closes inside it.  The
+// walk takes 15.6 ns per 1,000 entries inside hot columns and 57 ns where every entry closes one (profiles/r05_experiments.md
+// section 3): a close costs (57 - 15.6) / 15.6 = 2.65 entries
+constexpr int64_t kCostUnit = 20, kCloseCost = 53;
+int64_t range_cost(const HostBatch &hb, int32_t cnnz, int32_t rho);
+int walk_order_default();     // kWalkOrderColdFirst unless FMHIP_BWD_ORDER names another
 int32_t plan_bands(const HostBatch &hb, int32_t cnnz, int64_t rows, const std::vector<int32_t> &first, const std::vector<int32_t> &last,
-                   std::vector<int32_t> (&lists)[kXcds], int32_t (&seg)[kXcds][kXSegs + 1]);
+                   std::vector<int32_t> (&lists)[kXcds], int32_t (&seg)[kXcds][kXSegs + 1], int order = kWalkOrderStream,
+                   std::vector<int32_t> (*walk)[kXcds] = nullptr);
 
 // ---- ALS level schedule (S/fm/lib/ALS.scala:36-70 walks the features in id order) ------------------------------
 // level(c) = 1 + the largest level of an earlier column sharing a row with c.  crow: the transpose's row ids (bit 31 = a flag,

@@ -90,6 +90,7 @@ struct BatchMeta {
     int32_t xlen[fmhip::kXcds] = {};
     int32_t xseg[fmhip::kXcds][fmhip::kXSegs + 1] = {};   // list x = runs [xseg[x][s], xseg[x][s+1]) of ascending range ids (one per band, then the rest)
     int32_t x_affine = 0;   // ranges that were placed by their band (the rest fill the lists evenly)
+    int64_t woff[fmhip::kXcds] = {};   // list x once more in WALK order (plan_bands), xlen[x] ids from here: what a whole-batch launch reads
 };
 
 // Where a backward delivers its gradient rows when NOT into the model's packed buffer: the touched-rows exchange

@@ -378,11 +378,10 @@ int step_backward(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int64_t feat_lo
     }
     if (whole) {   // the common case needs no host-side searches
         if (banded)
-            for (int x = 0; x < kXcds; ++x)
-                for (int sg = 0; sg < kXSegs; ++sg) {
-                    ba.xseg_off[x][sg] = (int32_t)bm.xoff[x] + bm.xseg[x][sg];
-                    ba.xseg_len[x][sg] = bm.xseg[x][sg + 1] - bm.xseg[x][sg];
-                }
+            for (int x = 0; x < kXcds; ++x) {     // one run per XCD: its list in walk order (no window to clip the plan's runs to)
+                ba.xseg_off[x][0] = (int32_t)bm.woff[x];
+                ba.xseg_len[x][0] = bm.xlen[x];
+            }
         if (finish) {
             ba.red_bsum = m->bsum.p;
             ba.red_nblocks = m->fwd_parts;
