@@ -12,7 +12,7 @@
 //     sparkfm::HipALS       S/fm/lib/ALS.scala:15-75,202-208 the reference's own learner in fp64 on the GPU
 //     sparkfm::FM           S/fm/FM.scala:25-33, S/fm/impl/FactorizationMachines.scala:30-51   the fit loop
 //
-// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking) and include/fmhip_metrics.h (ROC AUC) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
+// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC) and include/fmhip_ranking.h (ranking evaluation) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
 // here a non-zero status of the C ABI becomes sparkfm::Error carrying fmhip_last_error().  Parameters live on the host as in
 // the reference (public, mutable: `fm.w0`, `fm.w`, `fm.v` with v[f + i*k] = breeze's column-major DenseMatrix(k, n+1)); every
 // call that needs them on the device uploads them first, as jvm/HipSGD.scala does (the fit loop calls `learn` once per
@@ -32,6 +32,7 @@
 #include "fmhip_topk.h"
 #include "fmhip_pairing.h"
 #include "fmhip_metrics.h"
+#include "fmhip_ranking.h"
 
 namespace sparkfm {
 
@@ -207,6 +208,49 @@ class FMModel {
         return idx;
     }
 
+    // Where the model ranks given candidates (fmhip_rank): relevant[c] = the candidate rows held out for context c, ascending and
+    // distinct; -> per context the 0-based position of each of them in the context's COMPLETE ranking (what recommend would
+    // return with k = candidates.size()), counted on the device.  exclude (nullable): per context the rows that are not in the
+    // ranking; score (nullable): the relevant rows' scores, in the order of the ranks.
+    std::vector<std::vector<int32_t>> rankOf(DataSet &contexts, DataSet &candidates, const std::vector<std::vector<int32_t>> &relevant,
+                                             const std::vector<std::vector<int32_t>> *exclude = nullptr,
+                                             std::vector<std::vector<double>> *score = nullptr) {
+        const size_t B = (size_t)contexts.size();
+        if (relevant.size() != B) throw Error(FMHIP_ERR_INVALID, "relevant must hold one list per context");
+        if (exclude && exclude->size() != B) throw Error(FMHIP_ERR_INVALID, "exclude must hold one list per context");
+        std::vector<int64_t> rptr, eptr;
+        std::vector<int32_t> ridx, eidx;
+        flatten(relevant, rptr, ridx);
+        if (exclude) flatten(*exclude, eptr, eidx);
+        std::vector<int32_t> rank(ridx.size());
+        std::vector<double> sc(score ? ridx.size() : 0);
+        check(fmhip_rank(upload(), contexts.handle(), candidates.handle(), rptr.data(), ridx.data(), exclude ? eptr.data() : nullptr,
+                         exclude ? eidx.data() : nullptr, rank.data(), score ? sc.data() : nullptr));
+        std::vector<std::vector<int32_t>> out(B);
+        if (score) score->assign(B, std::vector<double>());
+        for (size_t c = 0; c < B; ++c) {
+            out[c].assign(rank.begin() + rptr[c], rank.begin() + rptr[c + 1]);
+            if (score) (*score)[c].assign(sc.begin() + rptr[c], sc.begin() + rptr[c + 1]);
+        }
+        return out;
+    }
+    // HitRate@k, Recall@k, Precision@k, NDCG@k, MRR and MAP of those ranks (fmhip_rank_metrics, on the host), averaged over the
+    // contexts that have a relevant row
+    fmhip_rank_metrics_t computeRankingMetrics(DataSet &contexts, DataSet &candidates, const std::vector<std::vector<int32_t>> &relevant,
+                                               int32_t k = 10, const std::vector<std::vector<int32_t>> *exclude = nullptr) {
+        if (k < 1) throw Error(FMHIP_ERR_INVALID, "k must be >= 1");
+        return rankingMetrics(rankOf(contexts, candidates, relevant, exclude), k);
+    }
+    static fmhip_rank_metrics_t rankingMetrics(const std::vector<std::vector<int32_t>> &ranks, int32_t k) {
+        std::vector<int64_t> ptr;
+        std::vector<int32_t> flat;
+        flatten(ranks, ptr, flat);
+        fmhip_rank_metrics_t r{};
+        r.struct_size = (int32_t)sizeof r;
+        check(fmhip_rank_metrics((int64_t)ranks.size(), ptr.data(), flat.data(), k, &r));
+        return r;
+    }
+
     // the device replica: created on first use, refreshed from the host fields before every use (they are public and mutable)
     fmhip_model_t upload() {
         if (!h_) check(fmhip_model_create(device_, num_attribute, num_factor, nullptr, &h_));
@@ -216,6 +260,16 @@ class FMModel {
     void download() { check(fmhip_model_get_params(h_, &w0, w.data(), v.data())); }
 
   private:
+    // per-context lists -> offsets [n + 1] and the rows in one array (never empty: a non-NULL pointer)
+    static void flatten(const std::vector<std::vector<int32_t>> &lists, std::vector<int64_t> &ptr, std::vector<int32_t> &rows) {
+        ptr.assign(1, 0);
+        rows.clear();
+        for (const auto &e : lists) {
+            rows.insert(rows.end(), e.begin(), e.end());
+            ptr.push_back((int64_t)rows.size());
+        }
+        rows.reserve(1);
+    }
     int device_;
     fmhip_model_t h_ = nullptr;
 };

@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -49,6 +49,8 @@ TOPK_MAX = 128      # FMHIP_TOPK_MAX
 SYMBOLS_PAIRING = ("fmhip_model_set_pairing", "fmhip_pair_logloss")
 # ... and include/fmhip_metrics.h — ranking metrics: ROC AUC and per-group AUC, exact
 SYMBOLS_METRICS = ("fmhip_auc_scores", "fmhip_auc")
+# ... and include/fmhip_ranking.h — ranking evaluation: exact ranks of given candidate rows, HR / NDCG / MRR / MAP from them
+SYMBOLS_RANKING = ("fmhip_rank", "fmhip_rank_metrics")
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -162,6 +164,49 @@ class AucResult(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
+
+
+class RankMetrics(C.Structure):
+    """fmhip_rank_metrics_t (include/fmhip_ranking.h); struct_size is filled in on construction."""
+    _fields_ = [("struct_size", C.c_int32), ("k", C.c_int32), ("contexts", C.c_int64), ("skipped", C.c_int64), ("relevant", C.c_int64),
+                ("hit_rate", C.c_double), ("recall", C.c_double), ("precision", C.c_double), ("ndcg", C.c_double),
+                ("mrr", C.c_double), ("map", C.c_double)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(RankMetrics)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+def row_lists(lists, n_contexts, n_candidates, what):
+    """One integer array of candidate rows per context -> (ptr int64 [n_contexts + 1], rows int32): the lists sorted and
+    de-duplicated, one after the other; ValueError for a wrong count or a row outside [0, n_candidates).  `rows` is never empty
+    (a non-NULL pointer): its ptr[n_contexts] leading entries count.  All lists are handled in one pass (thousands of short
+    lists cost more in per-list numpy calls than the device takes to rank them)."""
+    import numpy as np
+    if len(lists) != n_contexts:
+        raise ValueError("%s must hold one array per context (%d), not %d" % (what, n_contexts, len(lists)))
+    lists = [np.asarray(e).reshape(-1) for e in lists]
+    lens = np.fromiter((len(e) for e in lists), np.int64, n_contexts)
+    ptr = np.zeros(n_contexts + 1, np.int64)
+    np.cumsum(lens, out=ptr[1:])
+    flat = np.concatenate(lists).astype(np.int64, copy=False) if ptr[-1] else np.zeros(0, np.int64)
+    if len(flat) and (flat.min() < 0 or flat.max() >= n_candidates):
+        raise ValueError("%s names a candidate row outside [0, %d)" % (what, n_candidates))
+    # lists that come ascending and distinct (every step inside a list goes up) are taken as they stand
+    up = flat[1:] > flat[:-1]
+    heads = ptr[1:-1]
+    up[heads[(heads > 0) & (heads < len(flat))] - 1] = True
+    if not up.all():
+        key = np.unique(np.repeat(np.arange(n_contexts, dtype=np.int64), lens) * int(n_candidates) + flat)      # (context, row)
+        np.cumsum(np.bincount(key // int(n_candidates), minlength=n_contexts), out=ptr[1:])
+        flat = key % int(n_candidates)
+    rows = np.ascontiguousarray(flat, np.int32)
+    if not len(rows):
+        rows = np.zeros(1, np.int32)
+    return ptr, rows
 
 
 def group_ids(groups, n):
@@ -320,7 +365,9 @@ def load():
     L.fmhip_pair_scores.argtypes = [vp, vp, vp, i64, i64, vp]
     L.fmhip_auc_scores.argtypes = [C.c_int, i64, vp, vp, vp, P(AucResult)]
     L.fmhip_auc.argtypes = [vp, vp, vp, P(AucResult), P(Stats)]
-    for name in SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS:
+    L.fmhip_rank.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.fmhip_rank_metrics.argtypes = [i64, vp, vp, i32, P(RankMetrics)]
+    for name in SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING:
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

@@ -4,6 +4,8 @@
 
 #include <stdlib.h>
 
+#include <math.h>
+
 #include <algorithm>
 #include <atomic>
 #include <numeric>
@@ -344,6 +346,54 @@ std::vector<ApplyGroup> apply_groups(const std::vector<int64_t> &edges, int64_t 
         pend_hi = -1;
     }
     return g;
+}
+
+// HitRate / Recall / Precision / NDCG at k, MRR and MAP of the ranks fmhip_rank returns (include/fmhip_ranking.h states each).
+// A context's ranks are sorted first: MAP needs them ascending, and equal neighbours are then the duplicates to refuse.
+int64_t rank_metrics(int64_t n_contexts, const int64_t *rel_ptr, const int32_t *rank, int32_t k, RankMetricSums *out) {
+    RankMetricSums s;
+    std::vector<int32_t> r;
+    for (int64_t c = 0; c < n_contexts; ++c) {
+        const int64_t n = rel_ptr[c + 1] - rel_ptr[c];
+        if (n == 0) {
+            ++s.skipped;
+            continue;
+        }
+        r.assign(rank + rel_ptr[c], rank + rel_ptr[c + 1]);
+        std::sort(r.begin(), r.end());
+        if (r[0] < 0) return c;
+        for (int64_t j = 1; j < n; ++j)
+            if (r[(size_t)j] == r[(size_t)j - 1]) return c;
+        ++s.contexts;
+        s.relevant += n;
+        int64_t hits = 0;
+        double dcg = 0.0, idcg = 0.0, ap = 0.0;
+        for (int64_t j = 0; j < n; ++j) {
+            if (r[(size_t)j] < k) {
+                ++hits;
+                dcg += 1.0 / log2((double)r[(size_t)j] + 2.0);
+            }
+            if (j < k) idcg += 1.0 / log2((double)j + 2.0);
+            ap += (double)(j + 1) / ((double)r[(size_t)j] + 1.0);
+        }
+        s.hit_rate += hits > 0 ? 1.0 : 0.0;
+        s.recall += (double)hits / (double)n;
+        s.precision += (double)hits / (double)k;
+        s.ndcg += dcg / idcg;
+        s.mrr += 1.0 / ((double)r[0] + 1.0);
+        s.map += ap / (double)n;
+    }
+    if (s.contexts > 0) {
+        const double n = (double)s.contexts;
+        s.hit_rate /= n;
+        s.recall /= n;
+        s.precision /= n;
+        s.ndcg /= n;
+        s.mrr /= n;
+        s.map /= n;
+    }
+    *out = s;
+    return -1;
 }
 
 }  // namespace host

@@ -96,5 +96,16 @@ CompactEdges compact_edges(const std::vector<int64_t> &cuts, int64_t n1, const i
 struct ApplyGroup { int at; int64_t lo, hi; };
 std::vector<ApplyGroup> apply_groups(const std::vector<int64_t> &edges, int64_t total_rows, int first_interval);
 
+// ---- ranking metrics of given ranks (fmhip_rank_metrics, include/fmhip_ranking.h) ------------------------------------
+// ranks[rel_ptr[c] .. rel_ptr[c+1]) are the 0-based ranks of context c's relevant rows; the metrics are cut at k >= 1 and
+// averaged (fp64 sums in context order) over the contexts that have a relevant row.  The caller has checked k, rel_ptr (not
+// NULL when n_contexts > 0, non-negative, non-decreasing) and rank (not NULL when there are ranks).
+struct RankMetricSums {
+    int64_t contexts = 0, skipped = 0, relevant = 0;
+    double hit_rate = 0, recall = 0, precision = 0, ndcg = 0, mrr = 0, map = 0;
+};
+// -> -1, or the first context that holds a negative rank or two equal ranks (out is then unreliable)
+int64_t rank_metrics(int64_t n_contexts, const int64_t *rel_ptr, const int32_t *rank, int32_t k, RankMetricSums *out);
+
 }  // namespace host
 }  // namespace fmhip

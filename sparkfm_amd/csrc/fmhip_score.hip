@@ -1,12 +1,14 @@
 // fmhip_score.hip — the C ABI's scoring calls: predictions, residuals, q, RMSE / log-loss / pairwise log-loss (include/fmhip.h,
-// fmhip_pairing.h), ROC AUC (fmhip_metrics.h), top-K and pair scores (fmhip_topk.h).  They hold the model's lock SHARED and touch
+// fmhip_pairing.h), ROC AUC (fmhip_metrics.h), top-K and pair scores (fmhip_topk.h), ranks of given rows (fmhip_ranking.h).  They hold the model's lock SHARED and touch
 // nothing of it but its parameters: every call works on a stream and in a workspace of its own (ScoreCtx), so any number of host
 // threads score through one model at once.  ScorePass is what they all share; the kernels are fm_forward / fm_pairing / fm_auc /
-// fm_topk .hip.
+// fm_topk / fm_rank .hip.
 #include "fmhip_internal.h"
 #include "../../include/fmhip_topk.h"
 #include "../../include/fmhip_metrics.h"
+#include "../../include/fmhip_ranking.h"
 #include "fm_topk.h"
+#include "fm_rank.h"
 #include "fm_pairing.h"
 #include "fm_auc.h"
 
@@ -409,6 +411,26 @@ struct PairJob {
     }
 };
 
+// the exclusion lists of fmhip_topk / fmhip_rank: both arrays or neither; offsets non-negative and non-decreasing; per context
+// the rows inside [0, M), ascending and distinct
+int check_exclusions(const int64_t *excl_ptr, const int32_t *excl, int64_t B, int64_t M) {
+    if ((excl_ptr == nullptr) != (excl == nullptr))
+        return fail(FMHIP_ERR_INVALID, "excl_ptr and excl must both be given or both be NULL");
+    if (!excl_ptr) return FMHIP_OK;
+    if (excl_ptr[0] < 0) return fail(FMHIP_ERR_INVALID, "excl_ptr[0] < 0");
+    for (int64_t c = 0; c < B; ++c)      // (the offsets first: nothing of excl is read through a bad one)
+        if (excl_ptr[c + 1] < excl_ptr[c]) return fail(FMHIP_ERR_INVALID, "excl_ptr decreases at context %lld", (long long)c);
+    for (int64_t c = 0; c < B; ++c) {
+        for (int64_t p = excl_ptr[c]; p < excl_ptr[c + 1]; ++p) {
+            if (excl[p] < 0 || excl[p] >= M)
+                return fail(FMHIP_ERR_INVALID, "context %lld excludes candidate %d outside [0, %lld)", (long long)c, (int)excl[p], (long long)M);
+            if (p > excl_ptr[c] && excl[p] <= excl[p - 1])
+                return fail(FMHIP_ERR_INVALID, "the exclusions of context %lld are not ascending and distinct", (long long)c);
+        }
+    }
+    return FMHIP_OK;
+}
+
 }  // namespace
 
 int fmhip_topk(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candidates, int32_t k, const int64_t *excl_ptr,
@@ -417,22 +439,8 @@ int fmhip_topk(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candid
     if (!m || !contexts || !candidates) return fail(FMHIP_ERR_INVALID, "model, contexts or candidates is NULL");
     if (!idx) return fail(FMHIP_ERR_INVALID, "idx is NULL");
     if (k < 1 || k > FMHIP_TOPK_MAX) return fail(FMHIP_ERR_INVALID, "k = %d outside [1, %d]", (int)k, FMHIP_TOPK_MAX);
-    if ((excl_ptr == nullptr) != (excl == nullptr))
-        return fail(FMHIP_ERR_INVALID, "excl_ptr and excl must both be given or both be NULL");
     const int64_t B = contexts->n_rows, M = candidates->n_rows;
-    if (excl_ptr) {
-        if (excl_ptr[0] < 0) return fail(FMHIP_ERR_INVALID, "excl_ptr[0] < 0");
-        for (int64_t c = 0; c < B; ++c)      // (the offsets first: nothing of excl is read through a bad one)
-            if (excl_ptr[c + 1] < excl_ptr[c]) return fail(FMHIP_ERR_INVALID, "excl_ptr decreases at context %lld", (long long)c);
-        for (int64_t c = 0; c < B; ++c) {
-            for (int64_t p = excl_ptr[c]; p < excl_ptr[c + 1]; ++p) {
-                if (excl[p] < 0 || excl[p] >= M)
-                    return fail(FMHIP_ERR_INVALID, "context %lld excludes candidate %d outside [0, %lld)", (long long)c, (int)excl[p], (long long)M);
-                if (p > excl_ptr[c] && excl[p] <= excl[p - 1])
-                    return fail(FMHIP_ERR_INVALID, "the exclusions of context %lld are not ascending and distinct", (long long)c);
-            }
-        }
-    }
+    TRY(check_exclusions(excl_ptr, excl, B, M));
     DevBuf<int64_t> d_eptr;
     DevBuf<int32_t> d_excl, d_idx;
     DevBuf<float> d_score;
@@ -504,6 +512,176 @@ int fmhip_pair_scores(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t
             TRY(job.pass.copy_back(d_out.p, rows * M, 1, 1, h_out, out + (size_t)(r0 - c0) * M));
         }
     }
+    return FMHIP_OK;
+}
+
+// ---- ranking evaluation (include/fmhip_ranking.h) ----------------------------------------------------------------------------
+// Per chunk of contexts (a batch of their dataset) the chunk's (context, relevant row) pairs are its QUERIES: their targets'
+// order words from k_pair_list, the order words of the chunk's (context, excluded row) pairs from the same kernel, the counting
+// sweep k_pair_rank over pieces of at most kRankPiece queries, k_rank_finish (fm_rank.hip).  Integers come back, and one score
+// per query if asked for.
+namespace {
+
+constexpr int64_t kRankPiece = (int64_t)1 << 20;      // queries per sweep: bounds part[nq][splits] at 2 GB
+
+int check_relevant(int64_t B, int64_t M, const int64_t *rel_ptr, const int32_t *rel, const int64_t *excl_ptr, const int32_t *excl,
+                   const int32_t *rank) {
+    if (B == 0) return FMHIP_OK;
+    if (!rel_ptr) return fail(FMHIP_ERR_INVALID, "rel_ptr is NULL");
+    if (rel_ptr[0] < 0) return fail(FMHIP_ERR_INVALID, "rel_ptr[0] < 0");
+    for (int64_t c = 0; c < B; ++c)
+        if (rel_ptr[c + 1] < rel_ptr[c]) return fail(FMHIP_ERR_INVALID, "rel_ptr decreases at context %lld", (long long)c);
+    if (rel_ptr[B] == 0) return FMHIP_OK;
+    if (!rel || !rank) return fail(FMHIP_ERR_INVALID, "rel or rank is NULL");
+    for (int64_t c = 0; c < B; ++c) {
+        int64_t e = excl_ptr ? excl_ptr[c] : 0;
+        const int64_t e_end = excl_ptr ? excl_ptr[c + 1] : 0;
+        for (int64_t p = rel_ptr[c]; p < rel_ptr[c + 1]; ++p) {
+            if (rel[p] < 0 || rel[p] >= M)
+                return fail(FMHIP_ERR_INVALID, "relevant row %d of context %lld outside [0, %lld)", (int)rel[p], (long long)c, (long long)M);
+            if (p > rel_ptr[c] && rel[p] <= rel[p - 1])
+                return fail(FMHIP_ERR_INVALID, "the relevant rows of context %lld are not ascending and distinct", (long long)c);
+            while (e < e_end && excl[e] < rel[p]) ++e;       // (both lists ascend: one merge pass)
+            if (e < e_end && excl[e] == rel[p])
+                return fail(FMHIP_ERR_INVALID, "candidate %d is both relevant and excluded for context %lld", (int)rel[p], (long long)c);
+        }
+    }
+    return FMHIP_OK;
+}
+
+}  // namespace
+
+int fmhip_rank(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candidates, const int64_t *rel_ptr, const int32_t *rel,
+               const int64_t *excl_ptr, const int32_t *excl, int32_t *rank, double *score) {
+    ReadLock lock(m);
+    if (!m || !contexts || !candidates) return fail(FMHIP_ERR_INVALID, "model, contexts or candidates is NULL");
+    const int64_t B = contexts->n_rows, M = candidates->n_rows;
+    TRY(check_exclusions(excl_ptr, excl, B, M));
+    TRY(check_relevant(B, M, rel_ptr, rel, excl_ptr, excl, rank));
+    DevBuf<int64_t> d_eptr;
+    DevBuf<int32_t> d_excl, d_rel, d_qctx, d_epc, d_part, d_rank;
+    DevBuf<unsigned long long> d_tk, d_ekey;
+    DevBuf<float> d_score;
+    PairJob job(m, contexts, candidates);
+    TRY(job.begin());
+    if (B == 0 || rel_ptr[B] == rel_ptr[0]) return FMHIP_OK;       // (M == 0 with relevant rows was refused above)
+    ScoreCtx &cx = job.pass.cx();
+    const int64_t r_lo = rel_ptr[0], r_hi = rel_ptr[B];
+    TRY(d_rel.alloc((size_t)(r_hi - r_lo)));
+    HIP_TRY(hipMemcpyAsync(d_rel.p, rel + r_lo, (size_t)(r_hi - r_lo) * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
+    const bool with_excl = excl_ptr && excl_ptr[B] > excl_ptr[0];
+    if (with_excl) {
+        TRY(d_eptr.alloc((size_t)B + 1));
+        TRY(d_excl.alloc((size_t)(excl_ptr[B] - excl_ptr[0])));
+        HIP_TRY(hipMemcpyAsync(d_eptr.p, excl_ptr, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, cx.s));
+        HIP_TRY(hipMemcpyAsync(d_excl.p, excl + excl_ptr[0], (size_t)(excl_ptr[B] - excl_ptr[0]) * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
+    }
+    std::vector<int32_t> h_qctx, h_epc;       // (rewritten only after the synchronisation that ends a piece)
+    std::vector<float> h_score;
+    for (const BatchMeta &bm : contexts->batches) {       // a chunk of contexts = a batch of their dataset
+        const int64_t p_lo = rel_ptr[bm.row0], p_hi = rel_ptr[bm.row0 + bm.rows];
+        if (p_lo == p_hi) continue;
+        TRY(job.forward_ctx(bm));
+        // the order words of the chunk's (context, excluded row) pairs, once for all of its queries
+        const int64_t e_lo = with_excl ? excl_ptr[bm.row0] : 0, n_excl = with_excl ? excl_ptr[bm.row0 + bm.rows] - e_lo : 0;
+        if (n_excl > 0x7fffffffll) return fail(FMHIP_ERR_UNSUPPORTED, "%lld exclusions in one batch of contexts: fewer than 2^31 are taken", (long long)n_excl);
+        PairListArgs la{};
+        la.Qc = cx.P.p;
+        la.yc = cx.yhat.p;
+        la.Qd = job.Qd.p;
+        la.yd = job.yd.p;
+        la.w0 = m->w0.p;
+        if (n_excl > 0) {
+            h_epc.resize((size_t)n_excl);
+            for (int64_t c = 0; c < bm.rows; ++c)
+                std::fill(h_epc.begin() + (excl_ptr[bm.row0 + c] - e_lo), h_epc.begin() + (excl_ptr[bm.row0 + c + 1] - e_lo), (int32_t)c);
+            TRY(d_epc.ensure((size_t)n_excl));
+            TRY(d_ekey.ensure((size_t)n_excl));
+            HIP_TRY(hipMemcpyAsync(d_epc.p, h_epc.data(), (size_t)n_excl * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
+            PairListArgs ea = la;
+            ea.pc = d_epc.p;
+            ea.pd = d_excl.p + (e_lo - excl_ptr[0]);
+            ea.n = n_excl;
+            ea.key = d_ekey.p;
+            HIP_TRY(launch_pair_list(m->Kp, ea, cx.s));
+        }
+        for (int64_t q_lo = p_lo; q_lo < p_hi; q_lo += kRankPiece) {
+            const int64_t nq = std::min(kRankPiece, p_hi - q_lo);
+            h_qctx.resize((size_t)nq);
+            {
+                int64_t c = std::upper_bound(rel_ptr + bm.row0, rel_ptr + bm.row0 + bm.rows + 1, q_lo) - rel_ptr - 1;
+                for (int64_t q = 0; q < nq; ++q) {
+                    while (rel_ptr[c + 1] <= q_lo + q) ++c;
+                    h_qctx[(size_t)q] = (int32_t)(c - bm.row0);
+                }
+            }
+            int32_t split_len = 0;
+            const int splits = topk_splits(nq, M, &split_len);
+            TRY(d_qctx.ensure((size_t)nq));
+            TRY(d_tk.ensure((size_t)nq));
+            TRY(d_score.ensure((size_t)nq));
+            TRY(d_rank.ensure((size_t)nq));
+            TRY(d_part.ensure((size_t)nq * splits));
+            HIP_TRY(hipMemcpyAsync(d_qctx.p, h_qctx.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
+            PairListArgs ta = la;
+            ta.pc = d_qctx.p;
+            ta.pd = d_rel.p + (q_lo - r_lo);
+            ta.n = nq;
+            ta.key = d_tk.p;
+            ta.score = d_score.p;
+            HIP_TRY(launch_pair_list(m->Kp, ta, cx.s));
+            RankArgs ra{};
+            ra.Qc = la.Qc;
+            ra.yc = la.yc;
+            ra.Qd = la.Qd;
+            ra.yd = la.yd;
+            ra.w0 = la.w0;
+            ra.qctx = d_qctx.p;
+            ra.tk = d_tk.p;
+            ra.nq = (int32_t)nq;
+            ra.M = (int32_t)M;
+            ra.split_len = split_len;
+            ra.splits = splits;
+            ra.part = d_part.p;
+            HIP_TRY(launch_pair_rank(m->Kp, ra, cx.s));
+            HIP_TRY(launch_rank_finish(d_part.p, (int32_t)nq, splits, d_tk.p, d_qctx.p, n_excl > 0 ? d_eptr.p + bm.row0 : nullptr, e_lo,
+                                       d_ekey.p, d_rank.p, cx.s));
+            HIP_TRY(hipMemcpyAsync(rank + q_lo, d_rank.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, cx.s));
+            // one synchronisation for both copies
+            if (score) TRY(job.pass.copy_back(d_score.p, nq, 1, 1, h_score, score + q_lo));
+            else HIP_TRY(hipStreamSynchronize(cx.s));
+        }
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_rank_metrics(int64_t n_contexts, const int64_t *rel_ptr, const int32_t *rank, int32_t k, fmhip_rank_metrics_t *out) {
+    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    if (out->struct_size != (int32_t)sizeof(fmhip_rank_metrics_t))
+        return fail(FMHIP_ERR_INVALID, "out->struct_size is %d, not sizeof(fmhip_rank_metrics_t) = %d", (int)out->struct_size,
+                    (int)sizeof(fmhip_rank_metrics_t));
+    if (k < 1) return fail(FMHIP_ERR_INVALID, "k = %d is below 1", (int)k);
+    if (n_contexts < 0) return fail(FMHIP_ERR_INVALID, "n_contexts = %lld is negative", (long long)n_contexts);
+    if (n_contexts > 0) {
+        if (!rel_ptr) return fail(FMHIP_ERR_INVALID, "rel_ptr is NULL");
+        if (rel_ptr[0] < 0) return fail(FMHIP_ERR_INVALID, "rel_ptr[0] < 0");
+        for (int64_t c = 0; c < n_contexts; ++c)
+            if (rel_ptr[c + 1] < rel_ptr[c]) return fail(FMHIP_ERR_INVALID, "rel_ptr decreases at context %lld", (long long)c);
+        if (rel_ptr[n_contexts] > rel_ptr[0] && !rank) return fail(FMHIP_ERR_INVALID, "rank is NULL");
+    }
+    RankMetricSums s;
+    const int64_t bad = rank_metrics(n_contexts, rel_ptr, rank, k, &s);
+    if (bad >= 0) return fail(FMHIP_ERR_INVALID, "context %lld holds a negative rank or the same rank twice", (long long)bad);
+    out->k = k;
+    out->contexts = s.contexts;
+    out->skipped = s.skipped;
+    out->relevant = s.relevant;
+    out->hit_rate = s.hit_rate;
+    out->recall = s.recall;
+    out->precision = s.precision;
+    out->ndcg = s.ndcg;
+    out->mrr = s.mrr;
+    out->map = s.map;
     return FMHIP_OK;
 }
 

@@ -289,18 +289,7 @@ class FMModel(Model):
             raise ValueError("k must be in [1, %d], not %d" % (_ffi.TOPK_MAX, k))
         eptr = eidx = None
         if exclude is not None:
-            if len(exclude) != B:
-                raise ValueError("exclude must hold one array per context (%d), not %d" % (B, len(exclude)))
-            lists = [np.unique(np.asarray(e, np.int64).reshape(-1)) for e in exclude]
-            for e in lists:
-                if len(e) and (e[0] < 0 or e[-1] >= candidates.size):
-                    raise ValueError("exclude names a candidate row outside [0, %d)" % candidates.size)
-            eptr = np.zeros(B + 1, np.int64)
-            if B:
-                np.cumsum([len(e) for e in lists], out=eptr[1:])
-            eidx = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), np.int32)
-            if not len(eidx):
-                eidx = np.zeros(1, np.int32)        # (a non-NULL pointer beside eptr)
+            eptr, eidx = _ffi.row_lists(exclude, B, candidates.size, "exclude")
         idx = np.empty((B, k), np.int32)
         score = np.empty((B, k)) if scores else None
         _ffi.check(_ffi.load().fmhip_topk(self.handle, contexts.handle, candidates.handle, k, _ffi.ptr(eptr), _ffi.ptr(eidx),
@@ -315,6 +304,45 @@ class FMModel(Model):
         out = np.empty((c1 - c0, candidates.size))
         _ffi.check(_ffi.load().fmhip_pair_scores(self.handle, contexts.handle, candidates.handle, c0, c1, _ffi.ptr(out)))
         return out
+
+    def rankOf(self, contexts, candidates, relevant, exclude=None, scores=False):
+        """Where the model ranks given candidates (fmhip_rank): `relevant` holds one integer array of candidate rows per context
+        (sorted and de-duplicated here, as `exclude`); -> one int32 array per context, the 0-based position of each of those rows,
+        ascending by row, in the context's COMPLETE ranking — what `recommend` would return with k = candidates.size: best
+        first, equal scores by ascending row, NaN last — counted on the device from the bits `pairScores` returns, without
+        forming the scores.  `exclude`: None, or per context the candidate rows that are not in the ranking (what the user
+        rated in training); a row both relevant and excluded for a context raises ValueError.  scores=True: -> (ranks, scores),
+        the score of every relevant row beside its rank."""
+        B, M = contexts.size, max(candidates.size, 1)
+        rptr, ridx = _ffi.row_lists(relevant, B, candidates.size, "relevant")
+        n = int(rptr[B])
+        eptr = eidx = None
+        if exclude is not None:
+            eptr, eidx = _ffi.row_lists(exclude, B, candidates.size, "exclude")
+            # (context, row) words of the exclusions ascend: one binary search per relevant row
+            ctx_of = lambda ptr: np.repeat(np.arange(B, dtype=np.int64), np.diff(ptr))       # noqa: E731
+            ekey, rkey = ctx_of(eptr) * M + eidx[:int(eptr[B])], ctx_of(rptr) * M + ridx[:n]
+            at = np.minimum(np.searchsorted(ekey, rkey), max(len(ekey) - 1, 0))
+            both = rkey[ekey[at] == rkey] if len(ekey) else rkey[:0]
+            if len(both):
+                raise ValueError("candidate row %d is both relevant and excluded for context %d" % (both[0] % M, both[0] // M))
+        rank = np.empty(max(n, 1), np.int32)
+        score = np.empty(max(n, 1)) if scores else None
+        _ffi.check(_ffi.load().fmhip_rank(self.handle, contexts.handle, candidates.handle, _ffi.ptr(rptr), _ffi.ptr(ridx),
+                                          _ffi.ptr(eptr), _ffi.ptr(eidx), _ffi.ptr(rank), _ffi.ptr(score)))
+        ranks = [rank[rptr[c]:rptr[c + 1]] for c in range(B)]
+        if not scores:
+            return ranks
+        return ranks, [score[rptr[c]:rptr[c + 1]] for c in range(B)]
+
+    def computeRankingMetrics(self, contexts, candidates, relevant, k=10, exclude=None):
+        """HitRate@k, Recall@k, Precision@k, NDCG@k, MRR and MAP of the relevant rows' ranks (`rankOf`, then fmhip_rank_metrics on
+        the host), averaged over the contexts that have a relevant row: a dict of k, contexts, skipped, relevant, hit_rate,
+        recall, precision, ndcg, mrr, map."""
+        from . import metrics
+        if int(k) < 1:
+            raise ValueError("k must be >= 1, not %d" % int(k))
+        return metrics.ranking_metrics(self.rankOf(contexts, candidates, relevant, exclude=exclude), k)
 
     def batchGradient(self, dataset, batch=0):
         """sum over the batch of e*h (h: S/fm/lib/ALS.scala:56-58,40,21) -> (gv (k,n1), gw, g0, stats)."""
