@@ -3,15 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fm_topk.h"
+
 namespace fmhip {
 
-// The score of n explicit (context row, candidate row) pairs: pc[p] a row of Qc / yc, pd[p] a row of Qd / yd.
+// The score of n explicit (context row, candidate row) pairs: pc[p] a row of t.Qc / t.yc, pd[p] a row of t.Qd / t.yd.
 //   key [n]    (order-preserving key of the score) << 32 | ~pd[p] — the order word of the top-K lists (fm_topk.hip)
 //   score [n]  nullable: the score itself, the bits of the pair-score kernel
 struct PairListArgs {
-    const float *Qc, *yc;
-    const float *Qd, *yd;
-    const float *w0;            // [1]
+    PairTables t;
     const int32_t *pc, *pd;     // [n]
     int64_t n;
     unsigned long long *key;
@@ -20,11 +20,9 @@ struct PairListArgs {
 hipError_t launch_pair_list(int Kp, const PairListArgs &a, hipStream_t s);
 
 // One (chunk's queries) x (all candidates) counting sweep.  A QUERY is one (context, relevant row) pair: qctx[q] is its
-// context's row in Qc / yc, tk[q] the order word of its target (launch_pair_list).
+// context's row in t.Qc / t.yc, tk[q] the order word of its target (launch_pair_list).
 struct RankArgs {
-    const float *Qc, *yc;       // contexts of the chunk: [B][Kp], [B]
-    const float *Qd, *yd;       // candidates: [M][Kp], [M]
-    const float *w0;            // [1]
+    PairTables t;
     const int32_t *qctx;        // [nq]
     const unsigned long long *tk;   // [nq]
     int32_t nq, M;

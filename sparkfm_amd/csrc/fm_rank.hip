@@ -8,43 +8,29 @@
 //     pair's dot product is the DIAGONAL of the 16 x 16 block — an element of the block depends on its own A row and B column
 //     only, so the bits are those k_pair_topk forms for the pair wherever it meets it.  It runs twice: over the queries'
 //     targets (their 64-bit order words tk) and over the chunk's (context, excluded row) pairs;
-//   - k_pair_rank is k_pair_topk's tile walk, restated (that file stays as it is: its two instantiations keep their
-//     registers): a workgroup of 4 waves owns 64 queries — the A operands gathered through the query -> context index — and one
-//     split of the candidates, streamed through LDS 64 rows at a time, the next tile prefetched into registers, the tile stored
-//     k-permuted so that one ds_read_b128 serves four steps, four independent accumulators per tile.  Per score the common
+//   - k_pair_rank walks the candidates as k_pair_topk does, by the same lines (PairTiles, fm_pair_tiles.h: the tile streamed
+//     through LDS, the prefetch, the k-permuted layout, the four accumulators): a workgroup of 4 waves owns 64 queries — the A
+//     operands gathered through the query -> context index — and one split of the candidates.  Per score the common
 //     path is one float compare against the query's target score, held in registers: strictly greater counts, strictly less
 //     does not.  Only an equal or NaN score makes its lane form the 64-bit order word and compare it with tk — the target itself
 //     (word == tk) is never counted and ties order by row exactly as top-K orders them.  Counts are per-lane int32, summed
 //     over the 16 lanes that share a query group at the end and written to part[nq][splits]: no atomics;
 //   - k_rank_finish: rank = sum of the splits' counts - #{excluded rows of the query's context whose word is above tk}.
 // Exclusions therefore cost one pair score per (context, excluded row) and one compare per (query, excluded row): nothing is
-// looked up inside the sweep.
+// looked up inside the sweep.  pair_score, key_score and order_word are fm_score_key.h's: one definition for this file and
+// fm_topk.hip.
 #include "fm_rank.h"
+#include "fm_pair_tiles.h"
 #include "fm_score_key.h"
-#include "fm_topk.h"
 
 namespace fmhip {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kPairThreads;
 constexpr int TC = kTopkTileC, TD = kTopkTileD;
-
-// the one expression a pair's score is (fm_topk.hip's, restated): -0 becomes +0 and every NaN the canonical one
-__device__ __forceinline__ float pair_score(float yc, float bd, float dot) {
-    float s = (yc + bd) + dot;
-    s += 0.f;
-    return s != s ? __uint_as_float(0x7fc00000u) : s;
-}
-// the score of a key (score_key's inverse; key 0 = NaN)
-__device__ __forceinline__ float key_score(uint32_t key) {
-    return key == 0u ? __uint_as_float(0x7fc00000u) : __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
-}
-// the order word of (score, candidate row): larger = better — higher score first, lower row first among equals, NaN below -Inf
-__device__ __forceinline__ u64 order_word(float score, uint32_t row) { return ((u64)score_key(score) << 32) | (u64)(0xffffffffu - row); }
 
 template <int KP>
 __global__ __launch_bounds__(kThreads) void k_pair_list(const PairListArgs a) {
@@ -53,7 +39,7 @@ __global__ __launch_bounds__(kThreads) void k_pair_list(const PairListArgs a) {
     const int64_t p = ((int64_t)blockIdx.x * (kThreads / 64) + wv) * 16 + c15;       // lane (g, c15) feeds slot 4s + g of pair p
     const bool ok = p < a.n;
     const int32_t c = ok ? a.pc[p] : 0, d = ok ? a.pd[p] : 0;
-    const float *qa = a.Qc + (size_t)c * KP + g, *qb = a.Qd + (size_t)d * KP + g;
+    const float *qa = a.t.Qc + (size_t)c * KP + g, *qb = a.t.Qd + (size_t)d * KP + g;
     f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < S; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ok ? qa[4 * s] : 0.f, ok ? qb[4 * s] : 0.f, acc, 0, 0, 0);
@@ -61,7 +47,7 @@ __global__ __launch_bounds__(kThreads) void k_pair_list(const PairListArgs a) {
     if (ok && (c15 >> 2) == g) {
         const int i = c15 & 3;
         const float dot = i == 0 ? acc[0] : i == 1 ? acc[1] : i == 2 ? acc[2] : acc[3];
-        const float s = pair_score(a.yc[c], a.yd[d] - *a.w0, dot);
+        const float s = pair_score(a.t.yc[c], a.t.yd[d] - *a.t.w0, dot);
         a.key[p] = order_word(s, (uint32_t)d);
         if (a.score) a.score[p] = s;
     }
@@ -69,22 +55,19 @@ __global__ __launch_bounds__(kThreads) void k_pair_list(const PairListArgs a) {
 
 template <int KP>
 __global__ __launch_bounds__(kThreads) void k_pair_rank(const RankArgs a) {
-    constexpr int S = KP / 4;        // MFMA steps; also the floats of one lane group's region of a tile row
-    constexpr int LD = KP + 4;       // floats per tile row (the pad spreads the 16 rows of a read over the banks)
+    constexpr int S = PairTiles<KP>::S;      // MFMA steps
+    constexpr PairTileLds lds = pair_tile_lds(KP);
     extern __shared__ __align__(16) unsigned char smem[];
-    float *tile = reinterpret_cast<float *>(smem);            // [TD][LD], slot 4s + g of a row at g * S + s
-    float *bd = tile + TD * LD;                               // [TD] yhat(d) - w0
     const int tid = threadIdx.x, l = tid & 63, wv = tid >> 6, g = l >> 4, c15 = l & 15;
     const int qw = blockIdx.x * TC + wv * 16;                 // the wave's first query
     const int split = blockIdx.y;
     const int64_t d_lo = (int64_t)split * a.split_len, d_hi = min((int64_t)a.M, d_lo + a.split_len);
-    const float w0 = *a.w0;
 
     // A operand of step s: Qc[context of query c15 of the wave][4s + g]; queries past the chunk's are zero rows
     float A[S];
     {
         const bool ok = qw + c15 < a.nq;
-        const float *q = a.Qc + (size_t)(ok ? a.qctx[qw + c15] : 0) * KP + g;
+        const float *q = a.t.Qc + (size_t)(ok ? a.qctx[qw + c15] : 0) * KP + g;
 #pragma unroll
         for (int s = 0; s < S; ++s) A[s] = ok ? q[4 * s] : 0.f;
     }
@@ -96,71 +79,23 @@ __global__ __launch_bounds__(kThreads) void k_pair_rank(const RankArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const bool v = qw + 4 * g + i < a.nq;
-        yc[i] = v ? a.yc[a.qctx[qw + 4 * g + i]] : 0.f;
+        yc[i] = v ? a.t.yc[a.qctx[qw + 4 * g + i]] : 0.f;
         tk[i] = v ? a.tk[qw + 4 * g + i] : 0ull;
         ts[i] = v ? key_score((uint32_t)(tk[i] >> 32)) : 0.f;
         cnt[i] = 0;
     }
 
-    // A thread moves UN units of a tile, a unit = 16 consecutive slots of a candidate row: four float4 in, regrouped by lane
-    // group, four float4 out.  The NEXT tile's units are fetched into registers before this tile's product starts.
-    constexpr int UNITS = TD * (KP / 16), UN = (UNITS + kThreads - 1) / kThreads;
-    float4 pre[UN][4];
-    float pre_y = 0.f;
-    auto fetch = [&](int64_t d0) {
-#pragma unroll
-        for (int n = 0; n < UN; ++n) {
-            const int u = tid + n * kThreads, row = u / (KP / 16), t = u % (KP / 16);
-            const bool ok = u < UNITS && d0 + row < d_hi;
-            const float4 *src = reinterpret_cast<const float4 *>(a.Qd + (size_t)(ok ? d0 + row : d_lo) * KP) + 4 * t;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pre[n][i] = ok ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (tid < TD) pre_y = d0 + tid < d_hi ? a.yd[d0 + tid] : w0;
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (int n = 0; n < UN; ++n) {
-            const int u = tid + n * kThreads, row = u / (KP / 16), t = u % (KP / 16);
-            if (u >= UNITS) continue;
-            float *dst = tile + row * LD + 4 * t;
-            *reinterpret_cast<float4 *>(dst + 0 * S) = make_float4(pre[n][0].x, pre[n][1].x, pre[n][2].x, pre[n][3].x);
-            *reinterpret_cast<float4 *>(dst + 1 * S) = make_float4(pre[n][0].y, pre[n][1].y, pre[n][2].y, pre[n][3].y);
-            *reinterpret_cast<float4 *>(dst + 2 * S) = make_float4(pre[n][0].z, pre[n][1].z, pre[n][2].z, pre[n][3].z);
-            *reinterpret_cast<float4 *>(dst + 3 * S) = make_float4(pre[n][0].w, pre[n][1].w, pre[n][2].w, pre[n][3].w);
-        }
-        if (tid < TD) bd[tid] = pre_y - w0;
-    };
-    if (d_lo < d_hi) fetch(d_lo);
+    PairTiles<KP> pt{reinterpret_cast<float *>(smem), reinterpret_cast<float *>(smem + lds.tile_bytes), a.t.Qd, a.t.yd, *a.t.w0, d_lo, d_hi,
+                     tid, g, c15};
+    if (d_lo < d_hi) pt.fetch(d_lo);
     for (int64_t d0 = d_lo; d0 < d_hi; d0 += TD) {
-        __syncthreads();                                       // the previous tile has been read by every wave
-        stash();
-        __syncthreads();
-        if (d0 + TD < d_hi) fetch(d0 + TD);
-
         f32x4 acc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const float *brow = tile + c15 * LD + g * S;
-#pragma unroll
-        for (int t = 0; t < S / 4; ++t) {
-            float4 b[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const float4 *>(brow + 16 * j * LD + 4 * t);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[4 * t + 0], b[j].x, acc[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[4 * t + 1], b[j].y, acc[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[4 * t + 2], b[j].z, acc[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[4 * t + 3], b[j].w, acc[j], 0, 0, 0);
-        }
+        pt.product(d0, A, acc);
 
         // lane (g, c15) holds, in acc[j][i], the pair (query 4g + i of the wave, candidate d0 + 16j + c15)
         float bdv[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bdv[j] = bd[16 * j + c15];
+        for (int j = 0; j < 4; ++j) bdv[j] = pt.bd[16 * j + c15];
         if (d0 + TD <= d_hi) {
             // the common path: one compare per score counts it (the raw sum orders like the canonical score), one more tells
             // whether any score of the lane is equal to its target or NaN; one branch per tile
@@ -231,7 +166,7 @@ hipError_t launch_list(const PairListArgs &a, hipStream_t s) {
 
 template <int KP>
 hipError_t launch_rank(const RankArgs &a, hipStream_t s) {
-    const size_t lds = (size_t)TD * (KP + 4) * sizeof(float) + TD * sizeof(float);
+    constexpr size_t lds = pair_tile_lds(KP).tile_bytes + pair_tile_lds(KP).bd_bytes;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_pair_rank<KP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_pair_rank<KP>), dim3((unsigned)((a.nq + TC - 1) / TC), (unsigned)a.splits), dim3(kThreads), lds, s, a);

@@ -9,12 +9,17 @@ constexpr int kTopkTileC = 64;        // contexts a workgroup keeps resident (16
 constexpr int kTopkTileD = 64;        // candidates per LDS tile
 constexpr int kTopkMaxSplits = 512;   // candidate splits a context's partial lists may come from (k_topk_merge: 8 heads per lane)
 
-// One (context chunk) x (all candidates) product.  Q tables are what the kFwdQ forward writes ([rows][Kp], packed slot and
-// padding zero, scales folded in), y the predictions it writes beside them.
-struct TopkArgs {
+// What every pair kernel reads.  Q tables are what the kFwdQ forward writes ([rows][Kp], packed slot and padding zero, scales
+// folded in), y the predictions it writes beside them.
+struct PairTables {
     const float *Qc, *yc;       // contexts of the chunk: [B][Kp], [B]
     const float *Qd, *yd;       // candidates: [M][Kp], [M]
     const float *w0;            // [1]
+};
+
+// One (context chunk) x (all candidates) product.
+struct TopkArgs {
+    PairTables t;
     int32_t B, M, K;
     int32_t split_len;          // candidates per split (a multiple of kTopkTileD); grid.y = ceil(M / split_len)
     const int64_t *excl_ptr;    // [B + 1] of the chunk's contexts (offsets into excl), NULL = no exclusions

@@ -7,11 +7,8 @@
 // k-ordered fmaf chain from 0, the numerics of every other kernel here) and selects while it goes, so the B x M scores never
 // reach memory:
 //   - a workgroup (4 waves) owns kTopkTileC = 64 contexts — each wave keeps the q rows of 16 of them in registers as the A
-//     operand of all Kp/4 steps — and one SPLIT of the candidates, which it streams through LDS kTopkTileD = 64 rows at a time;
-//   - the next tile's rows are fetched into registers before the current tile's product starts (their latency hides behind
-//     it) and stored to LDS after it;
-//   - the tile is stored k-permuted (slot 4s + g of a row at g * Kp/4 + s) so that lane group g reads the B operands of four
-//     consecutive steps with one ds_read_b128;
+//     operand of all Kp/4 steps — and one SPLIT of the candidates, which it streams through LDS kTopkTileD = 64 rows at a time:
+//     the tile walk (prefetch, k-permuted layout, MFMA steps) is PairTiles, fm_pair_tiles.h, shared with fm_rank.hip;
 //   - a wave forms four 16 x 16 blocks per tile (four independent accumulators: the MFMA's issue rate), adds the biases and
 //     offers a score to its context's running best-K list only if it is not below the list's K-th score: one float compare
 //     per score and one branch per tile on the common path, against thresholds held in registers.  What passes is inserted by the whole wave (the list
@@ -23,6 +20,7 @@
 // The score of a pair is one fixed expression whatever tile, split or chunk it falls into: results are bit-identical run
 // to run and batch to batch.
 #include "fm_topk.h"
+#include "fm_pair_tiles.h"
 #include "fm_score_key.h"
 
 #include <algorithm>
@@ -31,22 +29,11 @@ namespace fmhip {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kPairThreads;
 constexpr int TC = kTopkTileC, TD = kTopkTileD;
 
-// the one expression a pair's score is; -0 becomes +0 and every NaN the canonical one, so that key <-> score is a bijection
-__device__ __forceinline__ float pair_score(float yc, float bd, float dot) {
-    float s = (yc + bd) + dot;
-    s += 0.f;
-    return s != s ? __uint_as_float(0x7fc00000u) : s;
-}
-// order-preserving key, score_key (fm_score_key.h): NaN -> 0, then -Inf < ... < -0 = +0 < ... < +Inf (pair_score leaves no -0)
-__device__ __forceinline__ float key_score(uint32_t key) {
-    return key == 0u ? __uint_as_float(0x7fc00000u) : __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
-}
 // what a score must not be below to be worth offering to a list whose last entry is `last` (a list that is not full, or whose
 // K-th score is NaN, takes anything)
 __device__ __forceinline__ float list_threshold(u64 last) {
@@ -84,24 +71,21 @@ __device__ __forceinline__ void list_insert(u64 *L, int K, u64 c, int l) {
 
 template <int KP, bool SELECT>
 __global__ __launch_bounds__(kThreads) void k_pair_topk(const TopkArgs a) {
-    constexpr int S = KP / 4;        // MFMA steps; also the floats of one lane group's region of a tile row
-    constexpr int LD = KP + 4;       // floats per tile row (the pad spreads the 16 rows of a read over the banks)
+    constexpr int S = PairTiles<KP>::S;      // MFMA steps
+    constexpr PairTileLds lds = pair_tile_lds(KP);
     extern __shared__ __align__(16) unsigned char smem[];
-    float *tile = reinterpret_cast<float *>(smem);            // [TD][LD], slot 4s + g of a row at g * S + s
-    float *bd = tile + TD * LD;                               // [TD] yhat(d) - w0
-    u64 *lists = reinterpret_cast<u64 *>(bd + TD);            // SELECT: [TC][K]
+    u64 *lists = reinterpret_cast<u64 *>(smem + lds.tile_bytes + lds.bd_bytes);      // SELECT: [TC][K]
     const int tid = threadIdx.x, l = tid & 63, wv = tid >> 6, g = l >> 4, c15 = l & 15;
     const int K = a.K;
     const int cw = blockIdx.x * TC + wv * 16;                 // the wave's first context
     const int n_splits = gridDim.y, split = blockIdx.y;
     const int64_t d_lo = (int64_t)split * a.split_len, d_hi = min((int64_t)a.M, d_lo + a.split_len);
-    const float w0 = *a.w0;
 
     // A operand of step s: Qc[context c15 of the wave][4s + g]; rows past the chunk are zero
     float A[S];
     {
         const bool ok = cw + c15 < a.B;
-        const float *q = a.Qc + (size_t)(ok ? cw + c15 : 0) * KP + g;
+        const float *q = a.t.Qc + (size_t)(ok ? cw + c15 : 0) * KP + g;
 #pragma unroll
         for (int s = 0; s < S; ++s) A[s] = ok ? q[4 * s] : 0.f;
     }
@@ -111,75 +95,26 @@ __global__ __launch_bounds__(kThreads) void k_pair_topk(const TopkArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         vc[i] = cw + 4 * g + i < a.B;
-        yc[i] = vc[i] ? a.yc[cw + 4 * g + i] : 0.f;
+        yc[i] = vc[i] ? a.t.yc[cw + 4 * g + i] : 0.f;
         thr[i] = -__builtin_inff();
     }
     u64 *wl = lists + (size_t)(wv * 16) * K;                  // the wave's 16 lists
     if (SELECT)
         for (int t = l; t < 16 * K; t += 64) wl[t] = 0ull;
 
-    // A thread moves UN units of a tile, a unit = 16 consecutive slots of a candidate row: four float4 in, regrouped by lane
-    // group, four float4 out.  The NEXT tile's units are fetched into registers before this tile's product starts, so their
-    // latency hides behind it.
-    constexpr int UNITS = TD * (KP / 16), UN = (UNITS + kThreads - 1) / kThreads;
-    float4 pre[UN][4];
-    float pre_y = 0.f;
-    auto fetch = [&](int64_t d0) {
-#pragma unroll
-        for (int n = 0; n < UN; ++n) {
-            const int u = tid + n * kThreads, row = u / (KP / 16), t = u % (KP / 16);
-            const bool ok = u < UNITS && d0 + row < d_hi;
-            const float4 *src = reinterpret_cast<const float4 *>(a.Qd + (size_t)(ok ? d0 + row : d_lo) * KP) + 4 * t;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pre[n][i] = ok ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (tid < TD) pre_y = d0 + tid < d_hi ? a.yd[d0 + tid] : w0;
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (int n = 0; n < UN; ++n) {
-            const int u = tid + n * kThreads, row = u / (KP / 16), t = u % (KP / 16);
-            if (u >= UNITS) continue;
-            float *dst = tile + row * LD + 4 * t;
-            *reinterpret_cast<float4 *>(dst + 0 * S) = make_float4(pre[n][0].x, pre[n][1].x, pre[n][2].x, pre[n][3].x);
-            *reinterpret_cast<float4 *>(dst + 1 * S) = make_float4(pre[n][0].y, pre[n][1].y, pre[n][2].y, pre[n][3].y);
-            *reinterpret_cast<float4 *>(dst + 2 * S) = make_float4(pre[n][0].z, pre[n][1].z, pre[n][2].z, pre[n][3].z);
-            *reinterpret_cast<float4 *>(dst + 3 * S) = make_float4(pre[n][0].w, pre[n][1].w, pre[n][2].w, pre[n][3].w);
-        }
-        if (tid < TD) bd[tid] = pre_y - w0;
-    };
-    if (d_lo < d_hi) fetch(d_lo);
+    PairTiles<KP> pt{reinterpret_cast<float *>(smem), reinterpret_cast<float *>(smem + lds.tile_bytes), a.t.Qd, a.t.yd, *a.t.w0, d_lo, d_hi,
+                     tid, g, c15};
+    if (d_lo < d_hi) pt.fetch(d_lo);
     for (int64_t d0 = d_lo; d0 < d_hi; d0 += TD) {
-        __syncthreads();                                       // the previous tile has been read by every wave
-        stash();
-        __syncthreads();
-        if (d0 + TD < d_hi) fetch(d0 + TD);
-
         f32x4 acc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const float *brow = tile + c15 * LD + g * S;
-#pragma unroll
-        for (int t = 0; t < S / 4; ++t) {
-            float4 b[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const float4 *>(brow + 16 * j * LD + 4 * t);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[4 * t + 0], b[j].x, acc[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[4 * t + 1], b[j].y, acc[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[4 * t + 2], b[j].z, acc[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[4 * t + 3], b[j].w, acc[j], 0, 0, 0);
-        }
+        pt.product(d0, A, acc);
 
         // lane (g, c15) holds, in acc[j][i], the pair (context 4g + i of the wave, candidate d0 + 16j + c15)
         float bdv[4];
         bool vd[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            bdv[j] = bd[16 * j + c15];
+            bdv[j] = pt.bd[16 * j + c15];
             vd[j] = d0 + 16 * j + c15 < d_hi;
         }
         if constexpr (!SELECT) {
@@ -203,8 +138,7 @@ __global__ __launch_bounds__(kThreads) void k_pair_topk(const TopkArgs a) {
                     for (int i = 0; i < 4; ++i) {
                         u64 mask = __ballot(vd[j] && vc[i] && !((yc[i] + bdv[j]) + acc[j][i] < thr[i]));
                         if (mask == 0ull) continue;
-                        const u64 mine = ((u64)score_key(pair_score(yc[i], bdv[j], acc[j][i])) << 32) |
-                                         (u64)(0xffffffffu - (uint32_t)(d0 + 16 * j + c15));
+                        const u64 mine = order_word(pair_score(yc[i], bdv[j], acc[j][i]), (uint32_t)(d0 + 16 * j + c15));
                         while (mask) {
                             const int src = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)mask) - 1);
                             mask &= mask - 1;
@@ -272,7 +206,8 @@ __global__ __launch_bounds__(kThreads) void k_topk_merge(const u64 *part, int B,
 }
 
 size_t topk_lds_bytes(int Kp, int K, bool select) {
-    return (size_t)TD * (Kp + 4) * sizeof(float) + TD * sizeof(float) + (select ? (size_t)TC * K * sizeof(u64) : 0);
+    const PairTileLds lds = pair_tile_lds(Kp);
+    return lds.tile_bytes + lds.bd_bytes + (select ? (size_t)TC * K * sizeof(u64) : 0);
 }
 
 template <int KP, bool SELECT>

@@ -371,13 +371,26 @@ int fmhip_auc(fmhip_model_t m, fmhip_dataset_t d, const int32_t *group, fmhip_au
 // the call only.
 namespace {
 
-// what both calls share: the checks, the pass, the candidates' table Qd [M][Kp] and predictions yd [M]
+// ptr [n + 1], the offsets of n contexts' lists in a flat array: non-negative and non-decreasing
+int check_offsets(const char *name, const int64_t *ptr, int64_t n) {
+    if (ptr[0] < 0) return fail(FMHIP_ERR_INVALID, "%s[0] < 0", name);
+    for (int64_t c = 0; c < n; ++c)
+        if (ptr[c + 1] < ptr[c]) return fail(FMHIP_ERR_INVALID, "%s decreases at context %lld", name, (long long)c);
+    return FMHIP_OK;
+}
+
+// what the three calls share: the checks, the pass, the candidates' table Qd [M][Kp] and predictions yd [M], the tables every
+// pair kernel reads, the exclusion lists on the device, the way results travel back
 struct PairJob {
     fmhip_model_t m;
     fmhip_dataset_t ctx, cand;
     DevBuf<float> Qd, yd;
+    DevBuf<int64_t> d_eptr;
+    DevBuf<int32_t> d_excl;
     ScorePass pass;
     int64_t B = 0, M = 0;
+    PairTables t{};             // the context batch held in cx.P / cx.yhat, the candidates, w0
+    std::vector<float> h_score;
     PairJob(fmhip_model_t m_, fmhip_dataset_t c_, fmhip_dataset_t d_) : m(m_), ctx(c_), cand(d_), pass(m_) {}
     // the kFwdQ forward of one batch of `d`: q rows to Q[rows][Kp], predictions to yhat[rows]
     int forward_q(fmhip_dataset_t d, const BatchMeta &bm, float *Q, float *yhat) {
@@ -396,18 +409,34 @@ struct PairJob {
         TRY(Qd.alloc((size_t)M * m->Kp));
         TRY(yd.alloc((size_t)M));
         for (const BatchMeta &bm : cand->batches) TRY(forward_q(cand, bm, Qd.p + (size_t)bm.row0 * m->Kp, yd.p + bm.row0));
+        t = PairTables{pass.cx().P.p, pass.cx().yhat.p, Qd.p, yd.p, m->w0.p};
         return FMHIP_OK;
     }
-    TopkArgs args(int64_t first, int64_t rows) const {      // for rows [first, first + rows) of the context batch held in cx.P / cx.yhat
+    TopkArgs args(int64_t first, int64_t rows) const {      // for rows [first, first + rows) of the context batch
         TopkArgs a{};
-        a.Qc = pass.cx().P.p + (size_t)first * m->Kp;
-        a.yc = pass.cx().yhat.p + first;
-        a.Qd = Qd.p;
-        a.yd = yd.p;
-        a.w0 = m->w0.p;
+        a.t = t;
+        a.t.Qc += (size_t)first * m->Kp;
+        a.t.yc += first;
         a.B = (int32_t)rows;
         a.M = (int32_t)M;
         return a;
+    }
+    // The exclusion lists (checked: check_exclusions) to the device, as the caller holds them: d_eptr = excl_ptr [B + 1] and
+    // d_excl = excl [excl_ptr[B]], so an offset means on the device what it means to the caller — context c's rows are
+    // d_excl[d_eptr[c] .. d_eptr[c + 1]), whatever excl_ptr[0] is, for the kernels and for the host's pointer arithmetic alike.
+    int upload_exclusions(const int64_t *excl_ptr, const int32_t *excl) {
+        TRY(d_eptr.alloc((size_t)B + 1));
+        TRY(d_excl.alloc((size_t)std::max<int64_t>(excl_ptr[B], 1)));
+        HIP_TRY(hipMemcpyAsync(d_eptr.p, excl_ptr, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, pass.cx().s));
+        if (excl_ptr[B] > 0) HIP_TRY(hipMemcpyAsync(d_excl.p, excl, (size_t)excl_ptr[B] * sizeof(int32_t), hipMemcpyHostToDevice, pass.cx().s));
+        return FMHIP_OK;
+    }
+    // the end of a chunk: n integers back and, if asked for, n scores beside them, widened — one synchronisation for both copies
+    int results_back(const int32_t *d_ints, int32_t *ints, const float *d_score, double *score, int64_t n) {
+        HIP_TRY(hipMemcpyAsync(ints, d_ints, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, pass.cx().s));
+        if (score) return pass.copy_back(d_score, n, 1, 1, h_score, score);
+        HIP_TRY(hipStreamSynchronize(pass.cx().s));
+        return FMHIP_OK;
     }
 };
 
@@ -417,9 +446,7 @@ int check_exclusions(const int64_t *excl_ptr, const int32_t *excl, int64_t B, in
     if ((excl_ptr == nullptr) != (excl == nullptr))
         return fail(FMHIP_ERR_INVALID, "excl_ptr and excl must both be given or both be NULL");
     if (!excl_ptr) return FMHIP_OK;
-    if (excl_ptr[0] < 0) return fail(FMHIP_ERR_INVALID, "excl_ptr[0] < 0");
-    for (int64_t c = 0; c < B; ++c)      // (the offsets first: nothing of excl is read through a bad one)
-        if (excl_ptr[c + 1] < excl_ptr[c]) return fail(FMHIP_ERR_INVALID, "excl_ptr decreases at context %lld", (long long)c);
+    TRY(check_offsets("excl_ptr", excl_ptr, B));      // (the offsets first: nothing of excl is read through a bad one)
     for (int64_t c = 0; c < B; ++c) {
         for (int64_t p = excl_ptr[c]; p < excl_ptr[c + 1]; ++p) {
             if (excl[p] < 0 || excl[p] >= M)
@@ -441,8 +468,7 @@ int fmhip_topk(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candid
     if (k < 1 || k > FMHIP_TOPK_MAX) return fail(FMHIP_ERR_INVALID, "k = %d outside [1, %d]", (int)k, FMHIP_TOPK_MAX);
     const int64_t B = contexts->n_rows, M = candidates->n_rows;
     TRY(check_exclusions(excl_ptr, excl, B, M));
-    DevBuf<int64_t> d_eptr;
-    DevBuf<int32_t> d_excl, d_idx;
+    DevBuf<int32_t> d_idx;
     DevBuf<float> d_score;
     DevBuf<unsigned long long> part;
     PairJob job(m, contexts, candidates);
@@ -454,16 +480,10 @@ int fmhip_topk(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candid
         return FMHIP_OK;
     }
     ScoreCtx &cx = job.pass.cx();
-    if (excl_ptr) {
-        TRY(d_eptr.alloc((size_t)B + 1));
-        TRY(d_excl.alloc((size_t)std::max<int64_t>(excl_ptr[B], 1)));
-        HIP_TRY(hipMemcpyAsync(d_eptr.p, excl_ptr, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, cx.s));
-        if (excl_ptr[B] > 0) HIP_TRY(hipMemcpyAsync(d_excl.p, excl, (size_t)excl_ptr[B] * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
-    }
+    if (excl_ptr) TRY(job.upload_exclusions(excl_ptr, excl));
     const size_t rows_max = (size_t)contexts->max_rows;
     TRY(d_idx.alloc(rows_max * k));
     TRY(d_score.alloc(rows_max * k));
-    std::vector<float> h_score;
     for (const BatchMeta &bm : contexts->batches) {       // a chunk of contexts = a batch of their dataset
         TRY(job.forward_ctx(bm));
         TopkArgs a = job.args(0, bm.rows);
@@ -471,14 +491,11 @@ int fmhip_topk(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candid
         const int splits = topk_splits(bm.rows, M, &a.split_len);
         TRY(part.ensure((size_t)bm.rows * splits * k));
         a.part = part.p;
-        a.excl_ptr = excl_ptr ? d_eptr.p + bm.row0 : nullptr;
-        a.excl = d_excl.p;
+        a.excl_ptr = excl_ptr ? job.d_eptr.p + bm.row0 : nullptr;
+        a.excl = job.d_excl.p;
         HIP_TRY(launch_pair_topk(m->Kp, a, cx.s));
         HIP_TRY(launch_topk_merge(part.p, (int32_t)bm.rows, splits, k, d_idx.p, d_score.p, cx.s));
-        HIP_TRY(hipMemcpyAsync(idx + bm.row0 * k, d_idx.p, (size_t)bm.rows * k * sizeof(int32_t), hipMemcpyDeviceToHost, cx.s));
-        // one synchronisation for both copies
-        if (score) TRY(job.pass.copy_back(d_score.p, bm.rows * k, 1, 1, h_score, score + (size_t)bm.row0 * k));
-        else HIP_TRY(hipStreamSynchronize(cx.s));
+        TRY(job.results_back(d_idx.p, idx + bm.row0 * k, d_score.p, score ? score + (size_t)bm.row0 * k : nullptr, bm.rows * k));
     }
     return FMHIP_OK;
 }
@@ -528,9 +545,7 @@ int check_relevant(int64_t B, int64_t M, const int64_t *rel_ptr, const int32_t *
                    const int32_t *rank) {
     if (B == 0) return FMHIP_OK;
     if (!rel_ptr) return fail(FMHIP_ERR_INVALID, "rel_ptr is NULL");
-    if (rel_ptr[0] < 0) return fail(FMHIP_ERR_INVALID, "rel_ptr[0] < 0");
-    for (int64_t c = 0; c < B; ++c)
-        if (rel_ptr[c + 1] < rel_ptr[c]) return fail(FMHIP_ERR_INVALID, "rel_ptr decreases at context %lld", (long long)c);
+    TRY(check_offsets("rel_ptr", rel_ptr, B));
     if (rel_ptr[B] == 0) return FMHIP_OK;
     if (!rel || !rank) return fail(FMHIP_ERR_INVALID, "rel or rank is NULL");
     for (int64_t c = 0; c < B; ++c) {
@@ -558,8 +573,7 @@ int fmhip_rank(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candid
     const int64_t B = contexts->n_rows, M = candidates->n_rows;
     TRY(check_exclusions(excl_ptr, excl, B, M));
     TRY(check_relevant(B, M, rel_ptr, rel, excl_ptr, excl, rank));
-    DevBuf<int64_t> d_eptr;
-    DevBuf<int32_t> d_excl, d_rel, d_qctx, d_epc, d_part, d_rank;
+    DevBuf<int32_t> d_rel, d_qctx, d_epc, d_part, d_rank;
     DevBuf<unsigned long long> d_tk, d_ekey;
     DevBuf<float> d_score;
     PairJob job(m, contexts, candidates);
@@ -570,14 +584,8 @@ int fmhip_rank(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candid
     TRY(d_rel.alloc((size_t)(r_hi - r_lo)));
     HIP_TRY(hipMemcpyAsync(d_rel.p, rel + r_lo, (size_t)(r_hi - r_lo) * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
     const bool with_excl = excl_ptr && excl_ptr[B] > excl_ptr[0];
-    if (with_excl) {
-        TRY(d_eptr.alloc((size_t)B + 1));
-        TRY(d_excl.alloc((size_t)(excl_ptr[B] - excl_ptr[0])));
-        HIP_TRY(hipMemcpyAsync(d_eptr.p, excl_ptr, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, cx.s));
-        HIP_TRY(hipMemcpyAsync(d_excl.p, excl + excl_ptr[0], (size_t)(excl_ptr[B] - excl_ptr[0]) * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
-    }
+    if (with_excl) TRY(job.upload_exclusions(excl_ptr, excl));
     std::vector<int32_t> h_qctx, h_epc;       // (rewritten only after the synchronisation that ends a piece)
-    std::vector<float> h_score;
     for (const BatchMeta &bm : contexts->batches) {       // a chunk of contexts = a batch of their dataset
         const int64_t p_lo = rel_ptr[bm.row0], p_hi = rel_ptr[bm.row0 + bm.rows];
         if (p_lo == p_hi) continue;
@@ -586,11 +594,7 @@ int fmhip_rank(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candid
         const int64_t e_lo = with_excl ? excl_ptr[bm.row0] : 0, n_excl = with_excl ? excl_ptr[bm.row0 + bm.rows] - e_lo : 0;
         if (n_excl > 0x7fffffffll) return fail(FMHIP_ERR_UNSUPPORTED, "%lld exclusions in one batch of contexts: fewer than 2^31 are taken", (long long)n_excl);
         PairListArgs la{};
-        la.Qc = cx.P.p;
-        la.yc = cx.yhat.p;
-        la.Qd = job.Qd.p;
-        la.yd = job.yd.p;
-        la.w0 = m->w0.p;
+        la.t = job.t;
         if (n_excl > 0) {
             h_epc.resize((size_t)n_excl);
             for (int64_t c = 0; c < bm.rows; ++c)
@@ -600,7 +604,7 @@ int fmhip_rank(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candid
             HIP_TRY(hipMemcpyAsync(d_epc.p, h_epc.data(), (size_t)n_excl * sizeof(int32_t), hipMemcpyHostToDevice, cx.s));
             PairListArgs ea = la;
             ea.pc = d_epc.p;
-            ea.pd = d_excl.p + (e_lo - excl_ptr[0]);
+            ea.pd = job.d_excl.p + e_lo;
             ea.n = n_excl;
             ea.key = d_ekey.p;
             HIP_TRY(launch_pair_list(m->Kp, ea, cx.s));
@@ -631,11 +635,7 @@ int fmhip_rank(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candid
             ta.score = d_score.p;
             HIP_TRY(launch_pair_list(m->Kp, ta, cx.s));
             RankArgs ra{};
-            ra.Qc = la.Qc;
-            ra.yc = la.yc;
-            ra.Qd = la.Qd;
-            ra.yd = la.yd;
-            ra.w0 = la.w0;
+            ra.t = job.t;
             ra.qctx = d_qctx.p;
             ra.tk = d_tk.p;
             ra.nq = (int32_t)nq;
@@ -644,12 +644,9 @@ int fmhip_rank(fmhip_model_t m, fmhip_dataset_t contexts, fmhip_dataset_t candid
             ra.splits = splits;
             ra.part = d_part.p;
             HIP_TRY(launch_pair_rank(m->Kp, ra, cx.s));
-            HIP_TRY(launch_rank_finish(d_part.p, (int32_t)nq, splits, d_tk.p, d_qctx.p, n_excl > 0 ? d_eptr.p + bm.row0 : nullptr, e_lo,
+            HIP_TRY(launch_rank_finish(d_part.p, (int32_t)nq, splits, d_tk.p, d_qctx.p, n_excl > 0 ? job.d_eptr.p + bm.row0 : nullptr, e_lo,
                                        d_ekey.p, d_rank.p, cx.s));
-            HIP_TRY(hipMemcpyAsync(rank + q_lo, d_rank.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, cx.s));
-            // one synchronisation for both copies
-            if (score) TRY(job.pass.copy_back(d_score.p, nq, 1, 1, h_score, score + q_lo));
-            else HIP_TRY(hipStreamSynchronize(cx.s));
+            TRY(job.results_back(d_rank.p, rank + q_lo, d_score.p, score ? score + q_lo : nullptr, nq));
         }
     }
     return FMHIP_OK;
@@ -664,9 +661,7 @@ int fmhip_rank_metrics(int64_t n_contexts, const int64_t *rel_ptr, const int32_t
     if (n_contexts < 0) return fail(FMHIP_ERR_INVALID, "n_contexts = %lld is negative", (long long)n_contexts);
     if (n_contexts > 0) {
         if (!rel_ptr) return fail(FMHIP_ERR_INVALID, "rel_ptr is NULL");
-        if (rel_ptr[0] < 0) return fail(FMHIP_ERR_INVALID, "rel_ptr[0] < 0");
-        for (int64_t c = 0; c < n_contexts; ++c)
-            if (rel_ptr[c + 1] < rel_ptr[c]) return fail(FMHIP_ERR_INVALID, "rel_ptr decreases at context %lld", (long long)c);
+        TRY(check_offsets("rel_ptr", rel_ptr, n_contexts));
         if (rel_ptr[n_contexts] > rel_ptr[0] && !rank) return fail(FMHIP_ERR_INVALID, "rank is NULL");
     }
     RankMetricSums s;

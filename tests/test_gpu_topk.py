@@ -116,7 +116,7 @@ def run_topk(fmhip, seed, B, M, k, K, exclude=None, n1=600, rows=None, **kw):
 
 
 @pytest.mark.parametrize("K", [1, 10, 128])
-@pytest.mark.parametrize("k,B,M", [(8, 37, 1003), (64, 70, 5000), (200, 5, 300)])
+@pytest.mark.parametrize("k,B,M", [(8, 37, 1003), (64, 70, 5000), (200, 5, 300), (100, 19, 63)])
 def test_topk_is_a_valid_top_k(fmhip, K, k, B, M):
     run_topk(fmhip, 3 * K + k, B, M, k, K, empty_c=(1,), empty_d=(2, M - 1))
 

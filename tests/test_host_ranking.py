@@ -88,16 +88,20 @@ def test_ranking_header_is_plain_c(tmp_path):
 
 def test_rank_kernels_are_built_into_the_library():
     from sparkfm_amd import _build
-    assert "fm_rank.hip" in _build.HIP_SOURCES and {"fm_rank.h", "fm_topk.h", "fm_score_key.h"} <= set(_build.HIP_DEPS)
+    assert "fm_rank.hip" in _build.HIP_SOURCES and {"fm_rank.h", "fm_topk.h", "fm_pair_tiles.h", "fm_score_key.h"} <= set(_build.HIP_DEPS)
     assert any(d.endswith("fmhip_ranking.h") for d in _build.HIP_DEPS)
     csrc = os.path.join(ROOT, "sparkfm_amd", "csrc")
     text = open(os.path.join(csrc, "fm_rank.hip")).read()
-    src = re.sub(r"//[^\n]*", "", text)      # the code, not its comments
+    # the code, not its comments: the kernel file together with the tile walk it is built on
+    src = re.sub(r"//[^\n]*", "", text + open(os.path.join(csrc, "fm_pair_tiles.h")).read())
     assert "__builtin_amdgcn_mfma_f32_16x16x4f32" in src and "atomic" not in src.lower() and not re.search(r"\basm\b", src)
     for kernel in ("k_pair_list", "k_pair_rank", "k_rank_finish"):
         assert kernel in src, kernel
     # one key function, shared with top-K and the AUC kernels
     assert '#include "fm_score_key.h"' in text and not re.search(r"uint32_t\s+score_key\s*\(", text)
+    # one tile walk and one score expression, shared with top-K
+    assert '#include "fm_pair_tiles.h"' in text
+    assert not re.search(r"float\s+(pair_score|key_score)\s*\(|(void|auto)\s+(fetch|stash)\b", text)
 
 
 def test_rank_metrics_known_answer():

@@ -51,9 +51,15 @@ def test_topk_symbols_header_and_library():
 
 def test_topk_kernels_are_built_into_the_library():
     from sparkfm_amd import _build
-    assert "fm_topk.hip" in _build.HIP_SOURCES and "fm_topk.h" in _build.HIP_DEPS
-    src = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "sparkfm_amd", "csrc", "fm_topk.hip")).read())      # the code, not its comments
+    assert "fm_topk.hip" in _build.HIP_SOURCES and {"fm_topk.h", "fm_pair_tiles.h"} <= set(_build.HIP_DEPS)
+    csrc = os.path.join(ROOT, "sparkfm_amd", "csrc")
+    text = open(os.path.join(csrc, "fm_topk.hip")).read()
+    # the code, not its comments: the kernel file together with the tile walk it is built on
+    src = re.sub(r"//[^\n]*", "", text + open(os.path.join(csrc, "fm_pair_tiles.h")).read())
     assert "__builtin_amdgcn_mfma_f32_16x16x4f32" in src and "atomic" not in src.lower() and not re.search(r"\basm\b", src)
+    # one tile walk and one score expression, shared with the rank kernels
+    assert '#include "fm_pair_tiles.h"' in text
+    assert not re.search(r"float\s+(pair_score|key_score)\s*\(|(void|auto)\s+(fetch|stash)\b", text)
 
 
 def test_topk_header_is_plain_c(tmp_path):

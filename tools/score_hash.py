@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Prints hashes of what every READ call of the C ABI returns on fixed synthetic data — the scoring calls (predictions, residuals,
-q, RMSE / log-loss / pairwise log-loss, AUC, top-K, pair scores), the parameter and optimizer-state reads, the batch gradient —
+q, RMSE / log-loss / pairwise log-loss, AUC, top-K, pair scores, ranks), the parameter and optimizer-state reads, the batch gradient —
 one line per case: a SHA-256 prefix of each result array, %.17g of each scalar.  Run it with two builds of the library
 (FMHIP_LIB=sparkfm_amd/lib/libfmhip_<name>.so, tools/build_variant.sh): a change to the host side of those calls that moves no
 arithmetic leaves every line as it was.  The sibling of tools/grad_hash.py, which covers training.
@@ -69,6 +69,12 @@ def reads(fm, ds, cand, d, adagrad):
     idx, score = fm.recommend(ds, cand, TOP, exclude=exclude)
     out.append("topk %s %s" % (sha(idx), sha(score)))
     out.append("pair_scores %s" % sha(fm.pairScores(ds, cand, 300, 500)))
+    # two relevant rows per context, none of them among the context's exclusions
+    rel_rng = np.random.default_rng(6)       # (its own stream: the draws below stay what they were)
+    relevant = [np.setdiff1d(rel_rng.choice(CAND_ROWS, 6, replace=False), e)[:2] for e in exclude]
+    for tag, ex in (("rank_of", None), ("rank_of_excl", exclude)):
+        ranks, scores = fm.rankOf(ds, cand, relevant, exclude=ex, scores=True)
+        out.append("%s %s %s" % (tag, sha(*ranks), sha(*scores)))
     w0, w, v = C.c_double(), np.empty(n1), np.empty(n1 * k)
     _ffi.check(L.fmhip_model_get_params(hm, C.byref(w0), _ffi.ptr(w), _ffi.ptr(v)))
     out.append("get_params %.17g %s %s" % (w0.value, sha(w), sha(v)))
