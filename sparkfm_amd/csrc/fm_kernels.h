@@ -5,7 +5,7 @@
 
 #include <atomic>
 
-#include "fm_constants.h"   // kRangeLen, kXcds, kXSegs, kRowBands, kExtend
+#include "fm_constants.h"   // kRangeLen, kXcds, kXSegs, kRowBands, kExtend, kHotT, kHotPages
 
 namespace fmhip {
 
@@ -16,13 +16,6 @@ constexpr int kGradHead = 32;      // floats reserved for them at the front of t
 // runtime kernel-variant knobs (diagnostics / A-B benchmarking; fmhip_tune)
 enum { kTuneFwd = 0, kTuneBwd = 1, kTuneTile = 2, kTuneRowBlock = 3, kTuneXcd = 4, kTuneHot = 5, kTuneFwdOcc = 6, kTuneRowOrder = 7,
        kTuneFlat = 8, kTuneLazy = 9, kTuneFused = 10, kTuneMerged = 11, kTuneHotPages = 12, kTuneCount = 13 };
-constexpr int kHotT = 16;           // slots of one page of the dense hot block (fp32 per row: one 64-B half line)
-// Pages of the dense hot block.  Page 0 (the 16 most frequent features) is dense on BOTH sides: its entries leave the
-// CSR and the CSC streams.  Pages 1.. (the next most frequent ones that still pass the density test) are dense on the
-// GRADIENT side only: their entries stay in the CSR stream the forward walks (a longer dense prologue costs the forward
-// its occupancy — profiles/r02_experiments.md §18) but leave the CSC stream, where every entry costs the backward a P-row
-// gather; the MFMA block product below forms their gradient rows in the same pass over P as page 0's.
-constexpr int kHotPages = 8;
 // pages the gradient-side block product carries through ONE pass over P (its accumulators: pages x Kp/16 x 4 VGPRs: 64 at
 // 8 pages x Kp = 32 and at 4 pages x Kp = 64); a dataset with more pages than that takes several passes
 constexpr int hot_pages_max(int Kp) { return Kp <= 32 ? 8 : (Kp <= 64 ? 4 : 1); }

@@ -1,32 +1,25 @@
-// fmhip_dataset.hip — `DataSet(rdd).cache()` + `transposeInput` (S/DataSet.scala:42-62, 31-38) behind the C ABI: the host
-// passes of fmhip_dataset_create (validation, the dense hot block's choice and split, forward row order, fp32 re-pack), the
-// per-batch device transposes (csc_build.hip) with their column index, the dataset entry points of include/fmhip.h, and the
-// pure host arithmetic of the feature relabelling.  The step that consumes all this: fmhip_step.hip.
+// fmhip_dataset.hip — `DataSet(rdd).cache()` + `transposeInput` (S/DataSet.scala:42-62, 31-38) behind the C ABI:
+// fmhip_dataset_create as a sequence of phases — its pure host passes (validation, the dense hot block's choice and split, forward
+// row order, ALS row sort, own bitmaps) live in fmhip_host.cpp, what calls HIP (uploads, the per-batch device transposes of
+// csc_build.hip with their column index) here — and the dataset entry points of include/fmhip.h.  The step that consumes all
+// this: fmhip_step.hip.
 #include "fmhip_internal.h"
 #include "csc_build.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <cmath>
-#include <cstdarg>
 #include <cstdio>
-#include <cstring>
 #include <memory>
 #include <new>
-#include <numeric>
-#include <string>
-#include <thread>
 #include <type_traits>
 #include <vector>
 
 using namespace fmhip;
 using namespace fmhip::host;
 
-static_assert(FMHIP_HOT_PAGES == kHotPages && kHotPages * kHotT <= 128, "header and kernels disagree on the hot pages (128-bit slot masks)");
-typedef unsigned __int128 slotmask_t;      // one bit per slot of the dense hot block
+static_assert(FMHIP_HOT_PAGES == kHotPages, "header and kernels disagree on the hot pages");
 static_assert(FMHIP_RANGE_LEN == kRangeLen, "header and kernels disagree on the CSC range length");
 
 namespace fmhip {
@@ -85,12 +78,230 @@ __global__ __launch_bounds__(256) void k_fill_hot_pages(const int64_t *row_ptr, 
     }
 }
 
-hipError_t fill_hot_pages(const int64_t *row_ptr, const int32_t *col, const float *val, int64_t n_rows, const int32_t *hot_ids, int pages,
-                          float *xhot, int64_t page_floats) {
-    if (n_rows < 1 || pages < 2) return hipSuccess;
-    hipLaunchKernelGGL(k_fill_hot_pages, dim3((unsigned)((n_rows * 8 + 255) / 256)), dim3(256), 0, nullptr, row_ptr, col, val, n_rows, hot_ids, pages, xhot,
-                       page_floats);
-    return hipGetLastError();
+// ---- the phases of dataset_create_impl that call HIP -------------------------------------------------------------
+
+// the batch table: each batch's rows and its slices of the CSR stream (row_ptr; orig_row_ptr = the caller's) and of the transposes
+int batch_table(fmhip_dataset &d, const int64_t *row_ptr, const int64_t *orig_row_ptr, const HotSplit *sp) {
+    const int64_t nb = d.n_rows > 0 ? (d.n_rows + d.batch_rows - 1) / d.batch_rows : 0;
+    d.nnz_sparse = row_ptr[d.n_rows];
+    d.batches.resize((size_t)nb);
+    for (int64_t b = 0; b < nb; ++b) {
+        BatchMeta &bm = d.batches[(size_t)b];
+        bm.row0 = b * d.batch_rows;
+        bm.rows = std::min(d.batch_rows, d.n_rows - bm.row0);
+        bm.nnz0 = row_ptr[bm.row0];
+        bm.nnz_total = orig_row_ptr[bm.row0 + bm.rows] - orig_row_ptr[bm.row0];
+        bm.hot_mask = sp ? sp->hot_masks[(size_t)b] : 0u;
+        const int64_t bn = row_ptr[bm.row0 + bm.rows] - bm.nnz0, cn = bn - (sp ? sp->bwd_out[(size_t)b] : 0);
+        d.nnz_sparse_bwd += cn;
+        if (bn > (int64_t)0x7fffffff - 2 * kRangeLen || bm.rows > 0x7fffffff)
+            return fail(FMHIP_ERR_UNSUPPORTED, "batch %lld holds %lld nonzeros; the per-batch limit is 2^31", (long long)b, (long long)bn);
+        bm.nnz = (int32_t)bn;
+        bm.cnnz = (int32_t)cn;
+        d.max_rows = std::max(d.max_rows, bm.rows);
+    }
+    return FMHIP_OK;
+}
+
+// page 0 of the dense hot block from the host; pages 1.. zeroed and filled on the device from the uploaded CSR stream (a block has rows)
+int upload_hot_pages(fmhip_dataset &d, const float *xhot0) {
+    const size_t page_floats = (size_t)std::max<int64_t>(d.n_rows, 1) * kHotT;
+    hipError_t he = hipMemcpy(d.xhot.p, xhot0, page_floats * sizeof(float), hipMemcpyHostToDevice);
+    if (he == hipSuccess && d.hot_pages > 1) {
+        he = hipMemsetAsync(d.xhot.p + page_floats, 0, page_floats * (size_t)(d.hot_pages - 1) * sizeof(float), nullptr);
+        if (he == hipSuccess) {
+            hipLaunchKernelGGL(k_fill_hot_pages, dim3((unsigned)((d.n_rows * 8 + 255) / 256)), dim3(256), 0, nullptr, d.row_ptr.p, d.col.p, d.val.p, d.n_rows,
+                               d.d_hot_ids.p, d.hot_pages, d.xhot.p, (int64_t)page_floats);
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess) he = hipStreamSynchronize(nullptr);
+    }
+    if (he != hipSuccess) return fail(FMHIP_ERR_HIP, "filling the dense hot block's pages: %s", hipGetErrorString(he));
+    return FMHIP_OK;
+}
+
+// the fp64 ALS learner's copies: values and labels, and every row once more sorted by feature
+template <typename FT>
+int upload_als_copies(fmhip_dataset &d, const int64_t *row_ptr, const int32_t *col, const FT *val, const FT *y, int threads) {
+    const std::vector<double> val64 = converted<double>(val, d.nnz, 1), y64 = converted<double>(y, d.n_rows, 1);
+    const SortedRows sr = sort_rows_by_feature(d.n_rows, row_ptr, col, val, threads);
+    d.als_dup = sr.dup;
+    TRY(upload(d.val64, val64.data(), val64.size()));
+    TRY(upload(d.y64, y64.data(), y64.size()));
+    TRY(d.cval64.alloc((size_t)d.nnz));
+    TRY(upload(d.scol, sr.scol.data(), sr.scol.size()));
+    return upload(d.sval64, sr.sval.data(), sr.sval.size());
+}
+
+// what the per-batch transposes work in, allocated once for the largest batch
+struct TransposeScratch {
+    DevBuf<uint32_t> drop, idx_a, idx_b;
+    DevBuf<int32_t> keys_a, keys_b, rowid, starts, feats, count, rr_first, rr_last;
+    DevBuf<uint8_t> flags, tmp;
+    CscScratch sc;
+    std::vector<int32_t> cnt, base, h_first, h_last;   // finish_batch_meta's zeroed scratch; the range rows read back
+    int alloc(size_t max_nnz, int key_bits, int32_t dim, const std::vector<uint32_t> &drop_bits) {
+        if (!drop_bits.empty()) TRY(upload(drop, drop_bits.data(), drop_bits.size()));
+        size_t tmp_bytes = 0;
+        const hipError_t he = max_nnz ? csc_scratch_bytes(max_nnz, key_bits, &tmp_bytes) : hipSuccess;
+        if (he != hipSuccess) return fail(FMHIP_ERR_HIP, "rocPRIM scratch query failed: %s", hipGetErrorString(he));
+        TRY(keys_a.alloc(max_nnz)); TRY(keys_b.alloc(max_nnz)); TRY(idx_a.alloc(max_nnz)); TRY(idx_b.alloc(max_nnz));
+        TRY(rowid.alloc(max_nnz)); TRY(flags.alloc(max_nnz));
+        TRY(starts.alloc(max_nnz + 1)); TRY(feats.alloc(max_nnz + 1));   // (row-blocked streams repeat a feature once per block)
+        TRY(count.alloc(1)); TRY(tmp.alloc(tmp_bytes + 16));
+        sc.keys_a = keys_a.p; sc.keys_b = keys_b.p; sc.idx_a = idx_a.p; sc.idx_b = idx_b.p; sc.rowid = rowid.p;
+        sc.flags = flags.p; sc.starts = starts.p; sc.feats = feats.p; sc.count = count.p; sc.tmp = tmp.p; sc.tmp_bytes = tmp_bytes;
+        cnt.assign((size_t)dim + 2, 0);
+        base.assign((size_t)dim + 2, 0);
+        return FMHIP_OK;
+    }
+};
+
+// the column index (offsets, feature ids) of the batch just transposed, read back; the pseudo-column of the dropped entries cut off
+int read_columns(const TransposeScratch &ts, const BatchMeta &bm, int64_t b, int32_t drop_key, HostBatch &hb) {
+    int32_t nc = 0;
+    hipError_t he = hipMemcpy(&nc, ts.sc.count, sizeof nc, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) {
+        hb.cfeat.resize((size_t)nc);
+        hb.cptr.resize((size_t)nc + 1);
+        if (nc) {
+            he = hipMemcpy(hb.cfeat.data(), ts.sc.feats, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost);
+            if (he == hipSuccess) he = hipMemcpy(hb.cptr.data(), ts.sc.starts, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost);
+        }
+        hb.cptr[(size_t)nc] = bm.nnz;
+        if (he == hipSuccess && ts.drop.p && nc > 0 && hb.cfeat[(size_t)nc - 1] == drop_key) {
+            hb.cfeat.pop_back();               // the stream ends where the pseudo-column starts
+            hb.cptr.pop_back();
+        }
+        if (he == hipSuccess && hb.cptr.back() != bm.cnnz)
+            return fail(FMHIP_ERR_HIP, "batch %lld: the transpose holds %d entries, the host counted %d", (long long)b, hb.cptr.back(), bm.cnnz);
+    }
+    if (he != hipSuccess) return fail(FMHIP_ERR_HIP, "device transpose of batch %lld failed: %s", (long long)b, hipGetErrorString(he));
+    return FMHIP_OK;
+}
+
+// ALS level schedule of a single-batch dataset (fmhip_host.h, als_levels) from its transpose's row ids
+int als_schedule(fmhip_dataset &d, const BatchMeta &bm, const HostBatch &hb) {
+    std::vector<uint32_t> h_crow((size_t)bm.cnnz);
+    const hipError_t he = hipMemcpy(h_crow.data(), d.crow.p + bm.nnz0, h_crow.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return fail(FMHIP_ERR_HIP, "reading the transpose back for the ALS level schedule: %s", hipGetErrorString(he));
+    std::vector<int32_t> cols;
+    als_levels(hb.cptr, h_crow.data(), bm.rows, d.als_lev_ptr, cols);
+    TRY(upload(d.als_lev_cols, cols.data(), cols.size()));
+    d.h_als_lev_cols.swap(cols);
+    return FMHIP_OK;
+}
+
+// band-affine placement of batch b's ranges (fmhip_host.h, plan_bands): its lists, then the same lists in walk order, behind xlist_all
+int band_plan(fmhip_dataset &d, int64_t b, const HostBatch &hb, TransposeScratch &ts, std::vector<int32_t> &xlist_all) {
+    BatchMeta &bm = d.batches[(size_t)b];
+    const int32_t nr = (int32_t)hb.range_seg.size();
+    if ((size_t)nr > ts.rr_first.n) { TRY(ts.rr_first.alloc((size_t)nr)); TRY(ts.rr_last.alloc((size_t)nr)); }
+    ts.h_first.resize((size_t)nr);
+    ts.h_last.resize((size_t)nr);
+    hipError_t he = csc_range_rows(nullptr, d.crow.p + bm.nnz0, bm.cnnz, kRangeLen, nr, ts.rr_first.p, ts.rr_last.p);
+    if (he == hipSuccess) he = hipMemcpy(ts.h_first.data(), ts.rr_first.p, (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(ts.h_last.data(), ts.rr_last.p, (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return fail(FMHIP_ERR_HIP, "range rows of batch %lld: %s", (long long)b, hipGetErrorString(he));
+    std::vector<int32_t> lists[kXcds], walk[kXcds];
+    bm.x_affine = plan_bands(hb, bm.cnnz, bm.rows, ts.h_first, ts.h_last, lists, bm.xseg, walk_order_default(), &walk);
+    for (int x = 0; x < kXcds; ++x) {
+        bm.xoff[x] = (int64_t)xlist_all.size();
+        bm.xlen[x] = (int32_t)lists[x].size();
+        xlist_all.insert(xlist_all.end(), lists[x].begin(), lists[x].end());
+    }
+    for (int x = 0; x < kXcds; ++x) {                 // the walk order of the same lists (whole-batch launches)
+        bm.woff[x] = (int64_t)xlist_all.size();
+        xlist_all.insert(xlist_all.end(), walk[x].begin(), walk[x].end());
+    }
+    return FMHIP_OK;
+}
+
+// Phase 7: per-batch row -> column transposes, built on the device (csc_build.hip); only the small column index (offsets,
+// feature ids) comes back to the host, where each batch's metadata, the ALS levels and the band plan are made from it
+int build_transposes(fmhip_dataset &d, bool keep64, int64_t want_rb, const std::vector<uint32_t> &drop_bits, std::vector<HostBatch> &hbs) {
+    const int32_t dim = (int32_t)d.dimension;
+    int32_t max_nnz = 0;
+    for (const BatchMeta &bm : d.batches) max_nnz = std::max(max_nnz, bm.nnz);
+    // gradient-side hot pages: their entries are keyed dim + 1 and sort behind every real column
+    const bool drop = !drop_bits.empty();
+    const int32_t drop_key = dim + 1;
+    int key_bits = 1;
+    while (key_bits < 31 && ((int64_t)1 << key_bits) <= (int64_t)dim + (drop ? 1 : 0)) ++key_bits;
+    // optional row blocking of the transposes (FMHIP_TUNE_ROW_BLOCK): entries sorted by (row block,
+    // feature) so that a block's slice of P stays L2-resident while its columns are walked
+    int rb_bits = 0;
+    if (want_rb > 0) {
+        const int64_t blocks = (d.max_rows + want_rb - 1) / want_rb;
+        while (((int64_t)1 << rb_bits) < blocks) ++rb_bits;
+        if (key_bits + rb_bits > 31) rb_bits = 0;
+    }
+    d.rb_rows = rb_bits > 0 ? want_rb : 0;
+    const int32_t rb_div = d.rb_rows > 0 ? (int32_t)std::min<int64_t>(d.rb_rows, INT32_MAX) : INT32_MAX;
+    TransposeScratch ts;
+    TRY(ts.alloc((size_t)max_nnz, key_bits, dim, drop_bits));
+    std::vector<int32_t> xlist_all;
+    for (size_t b = 0; b < hbs.size(); ++b) {
+        const BatchMeta &bm = d.batches[b];
+        HostBatch &hb = hbs[b];
+        const hipError_t he = csc_build_batch(nullptr, ts.sc, d.row_ptr.p, d.col.p, d.val.p, keep64 ? d.val64.p : nullptr, bm.row0, bm.rows, bm.nnz0, bm.nnz,
+                                              key_bits, rb_div, rb_bits, d.crow.p, d.cval.p, keep64 ? d.cval64.p : nullptr, ts.drop.p, drop_key);
+        if (he != hipSuccess) return fail(FMHIP_ERR_HIP, "device transpose of batch %lld failed: %s", (long long)b, hipGetErrorString(he));
+        TRY(read_columns(ts, bm, (int64_t)b, drop_key, hb));
+        finish_batch_meta(hb, bm.cnnz, ts.cnt, ts.base);
+        if (keep64 && d.rb_rows == 0 && !hb.cfeat.empty() && bm.cnnz > 0) TRY(als_schedule(d, bm, hb));
+        // large batches of feature-sorted transposes only
+        if (d.rb_rows == 0 && hb.range_seg.size() >= 1024) TRY(band_plan(d, (int64_t)b, hb, ts, xlist_all));
+    }
+    TRY(upload(d.xlist, xlist_all.data(), xlist_all.size()));
+    d.h_xlist.swap(xlist_all);
+    return FMHIP_OK;
+}
+
+// Phase 8: the batches' column indexes packed end to end (BatchMeta holds the offsets), with the bitmap of the features whose
+// gradient rows the fixup launch assembles (cut columns + hot block), per batch: the merged finish skips them in its dense pass.
+// Kept for models of up to 2^24 features (2 MiB per batch).
+int pack_column_index(fmhip_dataset &d, std::vector<HostBatch> &hbs) {
+    const int64_t dim = d.dimension, nb = (int64_t)hbs.size();
+    std::vector<uint32_t> own;
+    if (d.rb_rows == 0 && dim < (1 << 24) && nb * (dim / 32 + 1) <= ((int64_t)1 << 26)) {
+        d.own_words = dim / 32 + 1;
+        own = own_bitmaps(hbs, d.hot_ids, (int32_t)dim);
+        for (int64_t b = 0; b < nb; ++b) d.batches[(size_t)b].own_off = b * d.own_words;
+    }
+    std::vector<int32_t> cfeat, cptr, range_seg, split_seg, split_short, cdst, mp_feat, mp_ptr;
+    auto append = [](std::vector<int32_t> &all, const std::vector<int32_t> &one, int32_t *n) {      // -> where `one` starts in `all`
+        if (n) *n = (int32_t)one.size();
+        all.insert(all.end(), one.begin(), one.end());
+        return (int64_t)(all.size() - one.size());
+    };
+    for (int64_t b = 0; b < nb; ++b) {
+        BatchMeta &bm = d.batches[(size_t)b];
+        HostBatch &hb = hbs[(size_t)b];
+        bm.n_feats = hb.n_feats;
+        bm.n_pieces = hb.n_pieces;
+        append(cdst, hb.cdst, nullptr);
+        append(mp_ptr, hb.mp_ptr, nullptr);
+        append(cptr, hb.cptr, nullptr);
+        bm.mp_off = append(mp_feat, hb.mp_feat, &bm.n_mp);
+        bm.col_off = append(cfeat, hb.cfeat, &bm.n_cols);
+        bm.range_off = append(range_seg, hb.range_seg, &bm.n_ranges);
+        bm.split_off = append(split_seg, hb.split_seg, &bm.n_split);
+        bm.split_short_off = append(split_short, hb.split_short, &bm.n_split_short);
+        d.max_pieces = std::max(d.max_pieces, bm.n_pieces);
+        d.max_ranges = std::max(d.max_ranges, bm.n_ranges);
+        HostBatch().cfeat.swap(hb.cfeat);
+    }
+    d.h_cfeat = cfeat;
+    d.h_cptr = cptr;
+    d.h_split = split_seg;
+    d.h_split_short = split_short;
+    TRY(upload(d.cfeat, cfeat.data(), cfeat.size())); TRY(upload(d.cptr, cptr.data(), cptr.size()));
+    TRY(upload(d.range_seg, range_seg.data(), range_seg.size()));
+    TRY(upload(d.split_seg, split_seg.data(), split_seg.size())); TRY(upload(d.split_short, split_short.data(), split_short.size()));
+    TRY(upload(d.cdst, cdst.data(), cdst.size()));
+    TRY(upload(d.mp_feat, mp_feat.data(), mp_feat.size())); TRY(upload(d.mp_ptr, mp_ptr.data(), mp_ptr.size()));
+    return upload(d.own_bits, own.data(), own.size());
 }
 
 // scoring = true: rows + labels only (FMModel.predict / Model.computeRMSE on held-out data,
@@ -109,40 +320,18 @@ int dataset_create_impl(int device, int64_t n_rows, const int64_t *row_ptr, cons
     if (n_rows < 0) return fail(FMHIP_ERR_INVALID, "n_rows < 0");
     if (!row_ptr) return fail(FMHIP_ERR_INVALID, "row_ptr is NULL");
     if (row_ptr[0] != 0) return fail(FMHIP_ERR_INVALID, "row_ptr[0] must be 0");
-    const int T = host_threads(n_rows);
     PhaseTimer pt;
-    {
-        std::vector<int64_t> bad((size_t)T, -1);
-        parallel_chunks(n_rows, T, [&](int t, int64_t lo, int64_t hi) {
-            for (int64_t r = lo; r < hi; ++r)
-                if (row_ptr[r + 1] < row_ptr[r]) { bad[(size_t)t] = r; break; }
-        });
-        for (int64_t r : bad)
-            if (r >= 0) return fail(FMHIP_ERR_INVALID, "row_ptr decreases at row %lld", (long long)r);
-    }
+    // ---- 1. validate (before the first HIP call)
+    const RowCheck chk = validate_rows(n_rows, row_ptr, col, host_threads(std::max(n_rows, row_ptr[n_rows])));
+    if (chk.bad_row >= 0) return fail(FMHIP_ERR_INVALID, "row_ptr decreases at row %lld", (long long)chk.bad_row);
     const int64_t nnz = row_ptr[n_rows];
     if (nnz > 0 && (!col || !val)) return fail(FMHIP_ERR_INVALID, "col/val is NULL");
     if (n_rows > 0 && !y && !scoring) return fail(FMHIP_ERR_INVALID, "y is NULL");
-    int32_t dim = 0;
-    {
-        const int Tn = host_threads(nnz);
-        std::vector<int64_t> bad((size_t)Tn, -1);
-        std::vector<int32_t> mx((size_t)Tn, 0);
-        parallel_chunks(nnz, Tn, [&](int t, int64_t lo, int64_t hi) {
-            int32_t m = 0;
-            for (int64_t p = lo; p < hi; ++p) {
-                if (col[p] < 0) { bad[(size_t)t] = p; break; }
-                m = std::max(m, col[p]);
-            }
-            mx[(size_t)t] = m;
-        });
-        for (int64_t p : bad)
-            if (p >= 0) return fail(FMHIP_ERR_INVALID, "negative feature index at entry %lld", (long long)p);
-        for (int32_t m : mx) dim = std::max(dim, m);
-    }
+    if (chk.bad_entry >= 0) return fail(FMHIP_ERR_INVALID, "negative feature index at entry %lld", (long long)chk.bad_entry);
+    const int32_t dim = chk.dim;
     pt.lap("validate");
     TRY(set_device(device));
-    fmhip_dataset *d = new (std::nothrow) fmhip_dataset();
+    std::unique_ptr<fmhip_dataset> d(new (std::nothrow) fmhip_dataset());
     if (!d) return fail(FMHIP_ERR_NOMEM, "out of host memory");
     d->device = device;
     d->n_rows = n_rows;
@@ -153,502 +342,74 @@ int dataset_create_impl(int device, int64_t n_rows, const int64_t *row_ptr, cons
     if (batch_rows <= 0 || batch_rows > n_rows) batch_rows = std::max<int64_t>(n_rows, 1);
     d->batch_rows = batch_rows;
     const int64_t nb = n_rows > 0 ? (n_rows + batch_rows - 1) / batch_rows : 0;
-    // ---- dense hot block (FMHIP_TUNE_HOT_BLOCK, FMHIP_TUNE_HOT_PAGES): features present in >= 10 % of the rows, the most frequent first, fill
-    // up to `max_pages` pages of kHotT slots; x_rh sits in xhot[page][r][slot].  Page 0's entries leave the sparse
-    // streams altogether; the entries of pages 1.. stay in the CSR stream (the forward walks them like any other entry)
-    // and leave only the transposes (fm_kernels.h, kHotPages).  A feature that occurs twice in a row, or is stored with
-    // an explicit zero, keeps the sparse path.  A single-batch dataset the ALS learner could walk (its whole transpose, at most
-    // kAlsMaxNnz nonzeros) is split only when the caller asks for the block by name (fmhip_dataset_opts::hot_block >= 1: such a
-    // dataset is for SGD, fmhip_als_epoch refuses it); larger single-batch datasets — full-batch SGD — are split like any other.
-    // Row-blocked ones keep page 0 only.
-    const int64_t *orig_row_ptr = row_ptr;
-    std::vector<int64_t> sp_ptr;
-    std::unique_ptr<int32_t[]> sp_col_buf;
-    std::unique_ptr<float[]> sp_val_buf, xhot_buf;
-    std::vector<slotmask_t> hot_masks;
-    std::vector<int64_t> bwd_out;          // per batch: entries of the gradient-side pages (in the CSR, not in the CSC)
-    std::vector<uint32_t> drop_bits;       // bitmap over feature ids: the gradient-side pages' features
+    const int T = host_threads(n_rows);
+    // ---- 2. dense hot block (FMHIP_TUNE_HOT_BLOCK, FMHIP_TUNE_HOT_PAGES; fmhip_host.h, choose_hot_block): x_rh sits in xhot[page][r][slot].
+    // A single-batch dataset the ALS learner could walk (its whole transpose, at most kAlsMaxNnz nonzeros) is split only when the
+    // caller asks for the block by name (fmhip_dataset_opts::hot_block >= 1: such a dataset is for SGD, fmhip_als_epoch refuses
+    // it); larger single-batch datasets — full-batch SGD — are split like any other.
+    HotSplit sp;
     bool split = false;
     if (want_hot && (nb > 1 || nnz > kAlsMaxNnz || hot_opt > 0) && nnz > 0 && !scoring) {
-        // Frequencies: exact for datasets of up to 8 M nonzeros; beyond that from every s-th row (the
-        // choice of hot features is a layout decision — any set that passes the checks below is valid —
-        // and a feature in >= 10 % of the rows cannot hide from a sample of millions of entries).
-        const int64_t stride = nnz > ((int64_t)8 << 20) ? std::max<int64_t>(1, nnz / ((int64_t)4 << 20)) : 1;
-        const int64_t sampled_rows = (n_rows + stride - 1) / stride;
-        std::vector<int32_t> cnt((size_t)dim + 1, 0);
-        {
-            // per-thread histograms while they stay small (<= 256 MB in all), merged in thread order
-            const int Ts = ((int64_t)(dim + 1) * T * 4 <= ((int64_t)256 << 20)) ? std::min<int>(T, (int)std::max<int64_t>(sampled_rows / 4096, 1)) : 1;
-            std::vector<std::vector<int32_t>> part((size_t)(Ts > 1 ? Ts : 0));
-            parallel_chunks(sampled_rows, Ts, [&](int t, int64_t lo, int64_t hi) {
-                int32_t *c = cnt.data();
-                if (Ts > 1) { part[(size_t)t].assign((size_t)dim + 1, 0); c = part[(size_t)t].data(); }
-                for (int64_t i = lo; i < hi; ++i) {
-                    const int64_t r = i * stride;
-                    for (int64_t p = row_ptr[r]; p < row_ptr[r + 1]; ++p) ++c[(size_t)col[p]];
-                }
-            });
-            if (Ts > 1)
-                parallel_chunks((int64_t)dim + 1, Ts, [&](int, int64_t lo, int64_t hi) {
-                    for (const auto &pc : part)
-                        for (int64_t f = lo; f < hi; ++f) cnt[(size_t)f] += pc[(size_t)f];
-                });
-        }
-        // candidates in descending order of frequency (ties: ascending id).  Page 0 is dense for the forward too, where a
-        // slot costs every row a multiply-add chain: it takes features present in >= 10 % of the rows.  A gradient-side slot
-        // costs a row 4 streamed bytes and saves, per entry, an 8-byte stream read, a P-row gather and an e gather (~2 line
-        // requests of the texture path, which is what bounds the column walk): those pages take features down to 2.5 %.
-        std::vector<int32_t> cand;
-        for (int32_t f = 0; f <= dim; ++f)
-            if ((int64_t)cnt[(size_t)f] * 40 >= sampled_rows) cand.push_back(f);
-        std::sort(cand.begin(), cand.end(), [&](int32_t x, int32_t y) { return cnt[(size_t)x] != cnt[(size_t)y] ? cnt[(size_t)x] > cnt[(size_t)y] : x < y; });
-        const size_t max_rest = (size_t)kHotT * (size_t)((want_rb > 0 ? 1 : max_hot_pages) - 1);
-        std::vector<int8_t> slot((size_t)dim + 1, -1);
-        sp_ptr.assign((size_t)n_rows + 1, 0);
-        // pass 1 (one sweep): the CSR length of every row if page 0 leaves the streams, and which candidates may not be
-        // dense — one that occurs twice in a row, or is stored with an explicit zero (its G row must have exactly one
-        // writer); if any is refused the sweep runs again without it (the ranking moves up)
-        size_t used = 0, p0 = 0;   // candidates being tried: the first p0 in page 0 (slots 0..), the next ones in slots kHotT..
-        auto slot_of = [&](size_t j) { return (int8_t)(j < p0 ? j : kHotT + (j - p0)); };
-        for (;;) {
-            p0 = 0;
-            while (p0 < cand.size() && p0 < (size_t)kHotT && (int64_t)cnt[(size_t)cand[p0]] * 10 >= sampled_rows) ++p0;
-            used = p0 < 2 ? 0 : p0 + std::min(cand.size() - p0, max_rest);
-            if (!used) break;
-            for (size_t j = 0; j < used; ++j) slot[(size_t)cand[j]] = slot_of(j);
-            std::vector<slotmask_t> badv((size_t)T, 0u);
-            parallel_chunks(n_rows, T, [&](int t, int64_t lo, int64_t hi) {
-                slotmask_t bad = 0;
-                for (int64_t r = lo; r < hi; ++r) {
-                    slotmask_t seen = 0;
-                    int64_t keep = 0;
-                    for (int64_t p = row_ptr[r]; p < row_ptr[r + 1]; ++p) {
-                        const int8_t h = slot[(size_t)col[p]];
-                        if (h < 0 || h >= kHotT) ++keep;
-                        if (h < 0) continue;
-                        if ((seen >> h & 1u) || (float)val[p] == 0.f) bad |= (slotmask_t)1 << h;
-                        seen |= (slotmask_t)1 << h;
-                    }
-                    sp_ptr[(size_t)r + 1] = keep;
-                }
-                badv[(size_t)t] = bad;
-            });
-            slotmask_t bad = 0;
-            for (slotmask_t x : badv) bad |= x;
-            if (!bad) break;
-            std::vector<int32_t> ok;
-            for (size_t j = 0; j < cand.size(); ++j) {
-                if (j < used) slot[(size_t)cand[j]] = -1;
-                if (j >= used || !(bad >> slot_of(j) & 1u)) ok.push_back(cand[j]);
-            }
-            cand.swap(ok);
-        }
-        std::vector<int32_t>().swap(cnt);
-        cand.resize(used);
-        if (used) {
-            // slots in ascending feature order inside every page (the sweep above does not depend on the numbering)
-            const int pages = 1 + (int)((used - p0 + kHotT - 1) / kHotT);
-            d->hot_ids.assign((size_t)(pages * kHotT), -1);
-            std::sort(cand.begin(), cand.begin() + (std::ptrdiff_t)p0);
-            for (size_t j = 0; j < p0; ++j) { d->hot_ids[j] = cand[j]; slot[(size_t)cand[j]] = (int8_t)j; }
-            for (size_t lo = p0; lo < used; lo += kHotT) {
-                const size_t hi = std::min(used, lo + kHotT);
-                std::sort(cand.begin() + (std::ptrdiff_t)lo, cand.begin() + (std::ptrdiff_t)hi);
-                for (size_t j = lo; j < hi; ++j) {
-                    const size_t h = kHotT + (j - p0);
-                    d->hot_ids[h] = cand[j];
-                    slot[(size_t)cand[j]] = (int8_t)h;
-                }
-            }
-            if (pages > 1) {
-                drop_bits.assign((size_t)(dim + 1) / 32 + 2, 0u);
-                for (size_t j = p0; j < used; ++j) drop_bits[(size_t)cand[j] >> 5] |= 1u << (cand[j] & 31);
-            }
-            hot_masks.assign((size_t)nb, 0u);
-            bwd_out.assign((size_t)nb, 0);
-            for (int64_t r = 0; r < n_rows; ++r) sp_ptr[(size_t)r + 1] += sp_ptr[(size_t)r];
-            // pass 2: fill (buffers left uninitialised: every element is written exactly once)
-            const size_t page_floats = (size_t)std::max<int64_t>(n_rows, 1) * kHotT;
-            sp_col_buf.reset(new int32_t[(size_t)std::max<int64_t>(sp_ptr[(size_t)n_rows], 1)]);
-            sp_val_buf.reset(new float[(size_t)std::max<int64_t>(sp_ptr[(size_t)n_rows], 1)]);
-            // page 0 is filled here (its entries leave the CSR stream); the gradient-side pages' entries STAY in the CSR stream,
-            // so their pages are filled on the device from the uploaded stream (k_fill_hot_pages): 64 MB per page and million
-            // rows that neither the host writes nor PCIe carries
-            xhot_buf.reset(new float[page_floats]);
-            int32_t *sp_col = sp_col_buf.get();
-            float *sp_val = sp_val_buf.get(), *xhot = xhot_buf.get();
-            std::vector<std::vector<slotmask_t>> tmask((size_t)T, std::vector<slotmask_t>((size_t)nb, 0u));
-            std::vector<std::vector<int64_t>> tout((size_t)T, std::vector<int64_t>((size_t)nb, 0));
-            parallel_chunks(n_rows, T, [&](int t, int64_t lo, int64_t hi) {
-                for (int64_t r = lo; r < hi; ++r) {
-                    slotmask_t seen = 0;
-                    int64_t o = sp_ptr[(size_t)r], outb = 0;
-                    {
-                        float *xr = xhot + (size_t)r * kHotT;
-                        for (int h = 0; h < kHotT; ++h) xr[h] = 0.f;
-                    }
-                    for (int64_t p = row_ptr[r]; p < row_ptr[r + 1]; ++p) {
-                        const int8_t h = slot[(size_t)col[p]];
-                        if (h >= 0) {
-                            seen |= (slotmask_t)1 << h;
-                            if (h < kHotT) xhot[(size_t)r * kHotT + h] = (float)val[p];
-                        }
-                        if (h < 0 || h >= kHotT) {
-                            sp_col[(size_t)o] = col[p];
-                            sp_val[(size_t)o] = (float)val[p];
-                            ++o;
-                            if (h >= 0) ++outb;
-                        }
-                    }
-                    tmask[(size_t)t][(size_t)(r / batch_rows)] |= seen;
-                    tout[(size_t)t][(size_t)(r / batch_rows)] += outb;
-                }
-            });
-            for (int t = 0; t < T; ++t)
-                for (int64_t b = 0; b < nb; ++b) {
-                    hot_masks[(size_t)b] |= tmask[(size_t)t][(size_t)b];
-                    bwd_out[(size_t)b] += tout[(size_t)t][(size_t)b];
-                }
+        HotBlock hb = choose_hot_block(n_rows, row_ptr, col, val, dim, max_hot_pages, want_rb > 0, T);
+        if (hb.pages) {
+            sp = split_hot_rows(n_rows, row_ptr, col, val, dim, batch_rows, hb, T);
             split = true;
             d->hot_T = kHotT;
-            d->hot_pages = pages;
-            for (int32_t f : d->hot_ids) d->hot_max_id = std::max(d->hot_max_id, (int64_t)f);
-            for (int h = 0; h < kHotT && h < (int)d->hot_ids.size(); ++h) d->hot0_max_id = std::max(d->hot0_max_id, d->hot_ids[(size_t)h]);
+            d->hot_pages = hb.pages;
+            d->hot_ids.swap(hb.hot_ids);
+            d->hot_max_id = *std::max_element(d->hot_ids.begin(), d->hot_ids.end());
+            d->hot0_max_id = *std::max_element(d->hot_ids.begin(), d->hot_ids.begin() + kHotT);
         }
     }
     pt.lap("hot block: choose + split");
-    if (split) {
-        row_ptr = sp_ptr.data();
-        col = sp_col_buf.get();
-    }
-    const int64_t nnz_s = split ? sp_ptr[(size_t)n_rows] : nnz;
-    d->nnz_sparse = nnz_s;
-    d->batches.resize((size_t)nb);
-    for (int64_t b = 0; b < nb; ++b) {
-        BatchMeta &bm = d->batches[(size_t)b];
-        bm.row0 = b * batch_rows;
-        bm.rows = std::min(batch_rows, n_rows - bm.row0);
-        bm.nnz0 = row_ptr[bm.row0];
-        bm.nnz_total = orig_row_ptr[bm.row0 + bm.rows] - orig_row_ptr[bm.row0];
-        bm.hot_mask = split ? hot_masks[(size_t)b] : 0u;
-        const int64_t bn = row_ptr[bm.row0 + bm.rows] - bm.nnz0;
-        d->nnz_sparse_bwd += bn - (split ? bwd_out[(size_t)b] : 0);
-        if (bn > (int64_t)0x7fffffff - 2 * kRangeLen || bm.rows > 0x7fffffff) {
-            delete d;
-            return fail(FMHIP_ERR_UNSUPPORTED, "batch %lld holds %lld nonzeros; the per-batch limit is 2^31", (long long)b,
-                        (long long)bn);
-        }
-        bm.nnz = (int32_t)bn;
-        bm.cnnz = (int32_t)(bn - (split ? bwd_out[(size_t)b] : 0));
-        d->max_rows = std::max(d->max_rows, bm.rows);
-    }
-    // forward walk order of each batch: rows by (sparse) length, longest first, ties in row order
+    // ---- 3. batch table, over the CSR stream as the device will hold it
+    const int64_t *sp_row_ptr = split ? sp.sp_ptr.data() : row_ptr;
+    const int32_t *sp_col = split ? sp.sp_col.get() : col;
+    TRY(batch_table(*d, sp_row_ptr, row_ptr, split ? &sp : nullptr));
+    const int64_t nnz_s = d->nnz_sparse;
+    // ---- 4. forward walk order of each batch: rows by (sparse) length, longest first, ties in row order
     {
-        std::vector<int32_t> order((size_t)n_rows);
-        const char *ow = getenv("FMHIP_ORDER_WINDOW");
-        const int64_t order_window = ow ? atoll(ow) : 0;   // experiment: sort inside windows of this many rows (0 = the whole batch)
-        parallel_chunks(nb, std::min<int>(T, (int)std::max<int64_t>(nb, 1)), [&](int, int64_t blo, int64_t bhi) {
-            std::vector<int64_t> start;
-            for (int64_t b = blo; b < bhi; ++b) {
-                const BatchMeta &bm = d->batches[(size_t)b];
-                const int64_t win = order_window > 0 ? order_window : std::max<int64_t>(bm.rows, 1);
-                for (int64_t w0 = 0; w0 < bm.rows; w0 += win) {
-                    const int64_t w1 = std::min(bm.rows, w0 + win);
-                    int64_t maxlen = 0;
-                    for (int64_t r = w0; r < w1; ++r) maxlen = std::max(maxlen, row_ptr[bm.row0 + r + 1] - row_ptr[bm.row0 + r]);
-                    start.assign((size_t)maxlen + 2, 0);
-                    for (int64_t r = w0; r < w1; ++r) ++start[(size_t)(maxlen - (row_ptr[bm.row0 + r + 1] - row_ptr[bm.row0 + r])) + 1];
-                    for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
-                    for (int64_t r = w0; r < w1; ++r) {
-                        const size_t key = (size_t)(maxlen - (row_ptr[bm.row0 + r + 1] - row_ptr[bm.row0 + r]));
-                        order[(size_t)(bm.row0 + w0 + start[key]++)] = (int32_t)r;
-                    }
-                    // windows alternate longest-first / shortest-first: a workgroup takes the same position of every window it visits
-                    if (order_window > 0 && ((w0 / win) & 1)) std::reverse(order.begin() + (bm.row0 + w0), order.begin() + (bm.row0 + w1));
-                }
-            }
-        });
-        const int rc0 = upload(d->row_order, order.data(), order.size());
-        if (rc0) {
-            delete d;
-            return rc0;
-        }
+        const char *ow = getenv("FMHIP_ORDER_WINDOW");   // experiment: sort inside windows of this many rows (0 = the whole batch)
+        const std::vector<int32_t> order = forward_row_order(n_rows, batch_rows, sp_row_ptr, ow ? atoll(ow) : 0, T);
+        TRY(upload(d->row_order, order.data(), order.size()));
     }
     pt.lap("row order + upload");
-    // fp32 copies of the streams (device arithmetic is fp32)
-    std::vector<float> valf, yf((size_t)n_rows, 0.f);
-    const float *val_up = nullptr;
-    if (split) {
-        val_up = sp_val_buf.get();
-    } else if (std::is_same<FT, float>::value) {
-        val_up = reinterpret_cast<const float *>(val);
-    } else {
-        valf.resize((size_t)nnz_s);
-        parallel_chunks(nnz_s, host_threads(nnz_s), [&](int, int64_t lo, int64_t hi) {
-            for (int64_t p = lo; p < hi; ++p) valf[(size_t)p] = (float)val[p];
-        });
-        val_up = valf.data();
-    }
-    if (y)
-        for (int64_t r = 0; r < n_rows; ++r) yf[(size_t)r] = (float)y[r];
-    const bool keep64 = !split && !scoring && nb == 1 && nnz <= kAlsMaxNnz;
-    int rc = FMHIP_OK;
-    if ((rc = upload(d->row_ptr, row_ptr, (size_t)n_rows + 1)) || (rc = upload(d->col, col, (size_t)nnz_s)) ||
-        (rc = upload(d->val, val_up, (size_t)nnz_s)) || (rc = upload(d->y, yf.data(), (size_t)n_rows)) ||
-        (!scoring && ((rc = d->crow.alloc((size_t)nnz_s)) || (rc = d->cval.alloc((size_t)nnz_s)))) ||
-        (split && ((rc = d->xhot.alloc((size_t)std::max<int64_t>(n_rows, 1) * kHotT * (size_t)d->hot_pages)) ||
-                   (rc = upload(d->d_hot_ids, d->hot_ids.data(), d->hot_ids.size()))))) {
-        delete d;
-        return rc;
-    }
-    if (split) {
-        const size_t page_floats = (size_t)std::max<int64_t>(n_rows, 1) * kHotT;
-        hipError_t he = hipMemcpy(d->xhot.p, xhot_buf.get(), page_floats * sizeof(float), hipMemcpyHostToDevice);
-        if (he == hipSuccess && d->hot_pages > 1) {
-            he = hipMemsetAsync(d->xhot.p + page_floats, 0, page_floats * (size_t)(d->hot_pages - 1) * sizeof(float), nullptr);
-            if (he == hipSuccess) he = fill_hot_pages(d->row_ptr.p, d->col.p, d->val.p, n_rows, d->d_hot_ids.p, d->hot_pages, d->xhot.p, (int64_t)page_floats);
-            if (he == hipSuccess) he = hipStreamSynchronize(nullptr);
+    // ---- 5. fp32 copies of the streams (device arithmetic is fp32) and H2D
+    {
+        std::vector<float> valf;
+        const float *val_up = split ? sp.sp_val.get() : reinterpret_cast<const float *>(val);   // (FT = float: the caller's array as it is)
+        if (!split && !std::is_same<FT, float>::value) {
+            valf = converted<float>(val, nnz_s, host_threads(nnz_s));
+            val_up = valf.data();
         }
-        if (he != hipSuccess) {
-            delete d;
-            return fail(FMHIP_ERR_HIP, "filling the dense hot block's pages: %s", hipGetErrorString(he));
+        const std::vector<float> yf = y ? converted<float>(y, n_rows, 1) : std::vector<float>((size_t)n_rows, 0.f);
+        TRY(upload(d->row_ptr, sp_row_ptr, (size_t)n_rows + 1)); TRY(upload(d->col, sp_col, (size_t)nnz_s));
+        TRY(upload(d->val, val_up, (size_t)nnz_s)); TRY(upload(d->y, yf.data(), (size_t)n_rows));
+        if (!scoring) { TRY(d->crow.alloc((size_t)nnz_s)); TRY(d->cval.alloc((size_t)nnz_s)); }
+        if (split) {
+            TRY(d->xhot.alloc((size_t)std::max<int64_t>(n_rows, 1) * kHotT * (size_t)d->hot_pages));
+            TRY(upload(d->d_hot_ids, d->hot_ids.data(), d->hot_ids.size()));
+            TRY(upload_hot_pages(*d, sp.xhot0.get()));
         }
     }
-    std::vector<float>().swap(valf);
-    xhot_buf.reset();
-    sp_val_buf.reset();
+    sp.xhot0.reset();
+    sp.sp_val.reset();
     pt.lap("fp32 re-pack + H2D");
     if (scoring) {
-        *out = d;
+        *out = d.release();
         return FMHIP_OK;
     }
-    if (keep64) {
-        std::vector<double> val64((size_t)nnz), y64((size_t)n_rows);
-        for (int64_t p = 0; p < nnz; ++p) val64[(size_t)p] = (double)val[p];
-        for (int64_t r = 0; r < n_rows; ++r) y64[(size_t)r] = (double)y[r];
-        // feature-sorted copy of every row (stable: equal ids keep their stored order)
-        std::vector<int32_t> scol((size_t)nnz);
-        std::vector<double> sval((size_t)nnz);
-        std::vector<char> dupv((size_t)T, 0);      // one byte per thread (vector<bool> packs bits: concurrent writes would race)
-        parallel_chunks(n_rows, T, [&](int t, int64_t lo, int64_t hi) {
-            std::vector<int32_t> idx;
-            bool dup = false;
-            for (int64_t r = lo; r < hi; ++r) {
-                const int64_t p0 = row_ptr[r], len = row_ptr[r + 1] - p0;
-                idx.resize((size_t)len);
-                for (int64_t j = 0; j < len; ++j) idx[(size_t)j] = (int32_t)j;
-                std::stable_sort(idx.begin(), idx.end(), [&](int32_t x, int32_t y2) { return col[p0 + x] < col[p0 + y2]; });
-                for (int64_t j = 0; j < len; ++j) {
-                    scol[(size_t)(p0 + j)] = col[p0 + idx[(size_t)j]];
-                    sval[(size_t)(p0 + j)] = val64[(size_t)(p0 + idx[(size_t)j])];
-                    if (j && scol[(size_t)(p0 + j)] == scol[(size_t)(p0 + j - 1)]) dup = true;
-                }
-            }
-            dupv[(size_t)t] = dup ? 1 : 0;
-        });
-        for (char b : dupv) d->als_dup = d->als_dup || b != 0;
-        if ((rc = upload(d->val64, val64.data(), val64.size())) || (rc = upload(d->y64, y64.data(), y64.size())) ||
-            (rc = d->cval64.alloc((size_t)nnz)) || (rc = upload(d->scol, scol.data(), scol.size())) ||
-            (rc = upload(d->sval64, sval.data(), sval.size()))) {
-            delete d;
-            return rc;
-        }
-    }
-    // per-batch row -> column transposes, built on the device (csc_build.hip); only the small
-    // column index (offsets, feature ids) comes back to the host
+    // ---- 6. fp64 ALS copies (single-batch datasets without a hot block)
+    const bool keep64 = !split && nb == 1 && nnz <= kAlsMaxNnz;
+    if (keep64) TRY(upload_als_copies(*d, row_ptr, col, val, y, T));
+    // ---- 7. device transposes and per-batch metadata
     std::vector<HostBatch> hbs((size_t)nb);
-    {
-        int32_t max_nnz = 0;
-        for (const BatchMeta &bm : d->batches) max_nnz = std::max(max_nnz, bm.nnz);
-        const size_t max_cols = (size_t)max_nnz;   // row-blocked streams repeat a feature once per block
-        // gradient-side hot pages: their entries are keyed dim + 1 and sort behind every real column
-        const bool drop = !drop_bits.empty();
-        const int32_t drop_key = dim + 1;
-        DevBuf<uint32_t> d_drop;
-        if (drop && (rc = upload(d_drop, drop_bits.data(), drop_bits.size()))) {
-            delete d;
-            return rc;
-        }
-        int key_bits = 1;
-        while (key_bits < 31 && ((int64_t)1 << key_bits) <= (int64_t)dim + (drop ? 1 : 0)) ++key_bits;
-        // optional row blocking of the transposes (FMHIP_TUNE_ROW_BLOCK): entries sorted by (row block,
-        // feature) so that a block's slice of P stays L2-resident while its columns are walked
-        int64_t rb_rows = want_rb;
-        int rb_bits = 0;
-        if (rb_rows > 0) {
-            const int64_t blocks = (d->max_rows + rb_rows - 1) / rb_rows;
-            while (((int64_t)1 << rb_bits) < blocks) ++rb_bits;
-            if (key_bits + rb_bits > 31) { rb_rows = 0; rb_bits = 0; }
-        }
-        d->rb_rows = rb_bits > 0 ? rb_rows : 0;
-        const int32_t rb_div = d->rb_rows > 0 ? (int32_t)std::min<int64_t>(d->rb_rows, INT32_MAX) : INT32_MAX;
-        std::vector<int32_t> cnt((size_t)dim + 2, 0), base((size_t)dim + 2, 0);
-        DevBuf<int32_t> keys_a, keys_b, rowid, starts, feats, count, rr_first, rr_last;
-        std::vector<int32_t> h_first, h_last, xlist_all;
-        DevBuf<uint32_t> idx_a, idx_b;
-        DevBuf<uint8_t> flags, tmp;
-        CscScratch sc;
-        size_t tmp_bytes = 0;
-        hipError_t he = max_nnz ? csc_scratch_bytes((size_t)max_nnz, key_bits, &tmp_bytes) : hipSuccess;
-        if (he != hipSuccess) {
-            delete d;
-            return fail(FMHIP_ERR_HIP, "rocPRIM scratch query failed: %s", hipGetErrorString(he));
-        }
-        if ((rc = keys_a.alloc((size_t)max_nnz)) || (rc = keys_b.alloc((size_t)max_nnz)) || (rc = idx_a.alloc((size_t)max_nnz)) ||
-            (rc = idx_b.alloc((size_t)max_nnz)) || (rc = rowid.alloc((size_t)max_nnz)) || (rc = flags.alloc((size_t)max_nnz)) ||
-            (rc = starts.alloc(max_cols + 1)) || (rc = feats.alloc(max_cols + 1)) || (rc = count.alloc(1)) ||
-            (rc = tmp.alloc(tmp_bytes + 16))) {
-            delete d;
-            return rc;
-        }
-        sc.keys_a = keys_a.p; sc.keys_b = keys_b.p; sc.idx_a = idx_a.p; sc.idx_b = idx_b.p; sc.rowid = rowid.p;
-        sc.flags = flags.p; sc.starts = starts.p; sc.feats = feats.p; sc.count = count.p; sc.tmp = tmp.p; sc.tmp_bytes = tmp_bytes;
-        for (int64_t b = 0; b < nb; ++b) {
-            const BatchMeta &bm = d->batches[(size_t)b];
-            HostBatch &hb = hbs[(size_t)b];
-            he = csc_build_batch(nullptr, sc, d->row_ptr.p, d->col.p, d->val.p, keep64 ? d->val64.p : nullptr, bm.row0, bm.rows,
-                                 bm.nnz0, bm.nnz, key_bits, rb_div, rb_bits, d->crow.p, d->cval.p, keep64 ? d->cval64.p : nullptr,
-                                 drop ? d_drop.p : nullptr, drop_key);
-            int32_t nc = 0;
-            if (he == hipSuccess) he = hipMemcpy(&nc, sc.count, sizeof nc, hipMemcpyDeviceToHost);
-            if (he == hipSuccess) {
-                hb.cfeat.resize((size_t)nc);
-                hb.cptr.resize((size_t)nc + 1);
-                if (nc) {
-                    he = hipMemcpy(hb.cfeat.data(), sc.feats, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost);
-                    if (he == hipSuccess) he = hipMemcpy(hb.cptr.data(), sc.starts, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost);
-                }
-                hb.cptr[(size_t)nc] = bm.nnz;
-                if (he == hipSuccess && drop && nc > 0 && hb.cfeat[(size_t)nc - 1] == drop_key) {
-                    // the pseudo-column of the dropped entries: the stream ends where it starts
-                    hb.cfeat.pop_back();
-                    hb.cptr.pop_back();
-                }
-                if (he == hipSuccess && hb.cptr.back() != bm.cnnz) {
-                    delete d;
-                    return fail(FMHIP_ERR_HIP, "batch %lld: the transpose holds %d entries, the host counted %d", (long long)b,
-                                hb.cptr.back(), bm.cnnz);
-                }
-            }
-            if (he != hipSuccess) {
-                delete d;
-                return fail(FMHIP_ERR_HIP, "device transpose of batch %lld failed: %s", (long long)b, hipGetErrorString(he));
-            }
-            finish_batch_meta(hb, bm.cnnz, cnt, base);
-            if (keep64 && nb == 1 && d->rb_rows == 0 && nc > 0 && bm.cnnz > 0) {
-                // ALS level schedule (S/fm/lib/ALS.scala:36-70 walks the features in id order; two columns without a common
-                // row touch disjoint residuals and q entries, so their closed-form steps commute EXACTLY): one pass over the
-                // transpose in id order, level(c) = 1 + max over c's rows of the level of the last column that touched the row
-                std::vector<uint32_t> h_crow((size_t)bm.cnnz);
-                he = hipMemcpy(h_crow.data(), d->crow.p + bm.nnz0, h_crow.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
-                if (he != hipSuccess) {
-                    delete d;
-                    return fail(FMHIP_ERR_HIP, "reading the transpose back for the ALS level schedule: %s", hipGetErrorString(he));
-                }
-                std::vector<int32_t> cols;
-                als_levels(hb.cptr, h_crow.data(), bm.rows, d->als_lev_ptr, cols);
-                if ((rc = upload(d->als_lev_cols, cols.data(), cols.size()))) {
-                    delete d;
-                    return rc;
-                }
-                d->h_als_lev_cols.swap(cols);
-            }
-            // band-affine placement of the ranges (large batches of feature-sorted transposes only)
-            if (d->rb_rows == 0 && hb.range_seg.size() >= 1024) {
-                const int32_t nr = (int32_t)hb.range_seg.size();
-                if ((size_t)nr > rr_first.n && ((rc = rr_first.alloc((size_t)nr)) || (rc = rr_last.alloc((size_t)nr)))) {
-                    delete d;
-                    return rc;
-                }
-                h_first.resize((size_t)nr);
-                h_last.resize((size_t)nr);
-                he = csc_range_rows(nullptr, d->crow.p + bm.nnz0, bm.cnnz, kRangeLen, nr, rr_first.p, rr_last.p);
-                if (he == hipSuccess) he = hipMemcpy(h_first.data(), rr_first.p, (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToHost);
-                if (he == hipSuccess) he = hipMemcpy(h_last.data(), rr_last.p, (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToHost);
-                if (he != hipSuccess) {
-                    delete d;
-                    return fail(FMHIP_ERR_HIP, "range rows of batch %lld: %s", (long long)b, hipGetErrorString(he));
-                }
-                std::vector<int32_t> lists[kXcds], walk[kXcds];
-                BatchMeta &bmw = d->batches[(size_t)b];
-                bmw.x_affine = plan_bands(hb, bm.cnnz, bm.rows, h_first, h_last, lists, bmw.xseg, walk_order_default(), &walk);
-                for (int x = 0; x < kXcds; ++x) {
-                    bmw.xoff[x] = (int64_t)xlist_all.size();
-                    bmw.xlen[x] = (int32_t)lists[x].size();
-                    xlist_all.insert(xlist_all.end(), lists[x].begin(), lists[x].end());
-                }
-                for (int x = 0; x < kXcds; ++x) {                 // the walk order of the same lists (whole-batch launches)
-                    bmw.woff[x] = (int64_t)xlist_all.size();
-                    xlist_all.insert(xlist_all.end(), walk[x].begin(), walk[x].end());
-                }
-            }
-        }
-        if ((rc = upload(d->xlist, xlist_all.data(), xlist_all.size()))) {
-            delete d;
-            return rc;
-        }
-        d->h_xlist.swap(xlist_all);
-    }
+    TRY(build_transposes(*d, keep64, want_rb, sp.drop_bits, hbs));
     pt.lap("device transposes + metadata");
-    // bitmap of the features whose gradient rows the fixup launch assembles (cut columns + hot block), per batch:
-    // the merged finish skips them in its dense pass.  Kept for models of up to 2^24 features (2 MiB per batch).
-    std::vector<uint32_t> own;
-    if (d->rb_rows == 0 && dim < (1 << 24) && nb * ((int64_t)dim / 32 + 1) <= ((int64_t)1 << 26)) {
-        d->own_words = (int64_t)dim / 32 + 1;
-        own.assign((size_t)(nb * d->own_words), 0u);
-        for (int64_t b = 0; b < nb; ++b) {
-            uint32_t *bits = own.data() + (size_t)(b * d->own_words);
-            const HostBatch &hb = hbs[(size_t)b];
-            for (const std::vector<int32_t> *lst : {&hb.split_seg, &hb.split_short})
-                for (int32_t c : *lst) { const int32_t f = hb.cfeat[(size_t)c]; bits[f >> 5] |= 1u << (f & 31); }
-            for (int32_t f : d->hot_ids)
-                if (f >= 0) bits[f >> 5] |= 1u << (f & 31);
-            d->batches[(size_t)b].own_off = b * d->own_words;
-        }
-    }
-    std::vector<int32_t> cfeat, cptr, range_seg, split_seg, split_short, cdst, mp_feat, mp_ptr;
-    for (int64_t b = 0; b < nb; ++b) {
-        BatchMeta &bm = d->batches[(size_t)b];
-        HostBatch &hb = hbs[(size_t)b];
-        bm.n_feats = hb.n_feats;
-        bm.n_mp = (int32_t)hb.mp_feat.size();
-        bm.mp_off = (int64_t)mp_feat.size();
-        bm.n_pieces = hb.n_pieces;
-        d->max_pieces = std::max(d->max_pieces, bm.n_pieces);
-        cdst.insert(cdst.end(), hb.cdst.begin(), hb.cdst.end());
-        mp_feat.insert(mp_feat.end(), hb.mp_feat.begin(), hb.mp_feat.end());
-        mp_ptr.insert(mp_ptr.end(), hb.mp_ptr.begin(), hb.mp_ptr.end());
-        bm.n_cols = (int32_t)hb.cfeat.size();
-        bm.col_off = (int64_t)cfeat.size();
-        bm.n_ranges = (int32_t)hb.range_seg.size();
-        bm.range_off = (int64_t)range_seg.size();
-        bm.n_split = (int32_t)hb.split_seg.size();
-        bm.split_off = (int64_t)split_seg.size();
-        bm.n_split_short = (int32_t)hb.split_short.size();
-        bm.split_short_off = (int64_t)split_short.size();
-        split_short.insert(split_short.end(), hb.split_short.begin(), hb.split_short.end());
-        d->max_ranges = std::max(d->max_ranges, bm.n_ranges);
-        cfeat.insert(cfeat.end(), hb.cfeat.begin(), hb.cfeat.end());
-        cptr.insert(cptr.end(), hb.cptr.begin(), hb.cptr.end());
-        range_seg.insert(range_seg.end(), hb.range_seg.begin(), hb.range_seg.end());
-        split_seg.insert(split_seg.end(), hb.split_seg.begin(), hb.split_seg.end());
-        HostBatch().cfeat.swap(hb.cfeat);
-    }
-    d->h_cfeat = cfeat;
-    d->h_cptr = cptr;
-    d->h_split = split_seg;
-    d->h_split_short = split_short;
-    if ((rc = upload(d->cfeat, cfeat.data(), cfeat.size())) || (rc = upload(d->cptr, cptr.data(), cptr.size())) ||
-        (rc = upload(d->range_seg, range_seg.data(), range_seg.size())) ||
-        (rc = upload(d->split_seg, split_seg.data(), split_seg.size())) ||
-        (rc = upload(d->split_short, split_short.data(), split_short.size())) || (rc = upload(d->cdst, cdst.data(), cdst.size())) ||
-        (rc = upload(d->mp_feat, mp_feat.data(), mp_feat.size())) || (rc = upload(d->mp_ptr, mp_ptr.data(), mp_ptr.size())) ||
-        (rc = upload(d->own_bits, own.data(), own.size()))) {
-        delete d;
-        return rc;
-    }
+    // ---- 8. pack and upload the column index
+    TRY(pack_column_index(*d, hbs));
     pt.lap("pack + upload column index");
-    *out = d;
+    *out = d.release();
     return FMHIP_OK;
 }
 
@@ -731,7 +492,7 @@ int fmhip_dataset_create_f32(int device, int64_t n_rows, const int64_t *row_ptr,
 int fmhip_dataset_destroy(fmhip_dataset_t d) {
     if (!d) return FMHIP_OK;
     (void)hipSetDevice(d->device);
-    delete d;
+    std::unique_ptr<fmhip_dataset>(d).reset();
     return FMHIP_OK;
 }
 

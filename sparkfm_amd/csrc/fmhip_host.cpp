@@ -95,6 +95,261 @@ int64_t relabel_columns(int64_t nnz, const int32_t *col, int64_t n1, const int32
     return bad.load();
 }
 
+// ---- dataset build ------------------------------------------------------------------------------------------------
+
+RowCheck validate_rows(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, int threads) {
+    RowCheck rc;
+    std::vector<int64_t> bad((size_t)threads, -1);          // every thread's first finding: the first of them is the first of all
+    std::vector<int32_t> mx((size_t)threads, 0);
+    auto first_bad = [&]() {
+        for (int64_t i : bad)
+            if (i >= 0) return i;
+        return (int64_t)-1;
+    };
+    parallel_chunks(n_rows, threads, [&](int t, int64_t lo, int64_t hi) {
+        for (int64_t r = lo; r < hi; ++r)
+            if (row_ptr[r + 1] < row_ptr[r]) { bad[(size_t)t] = r; break; }
+    });
+    if ((rc.bad_row = first_bad()) >= 0 || !col) return rc;
+    parallel_chunks(row_ptr[n_rows], threads, [&](int t, int64_t lo, int64_t hi) {
+        int32_t m = 0;
+        for (int64_t p = lo; p < hi; ++p) {
+            if (col[p] < 0) { bad[(size_t)t] = p; break; }
+            m = std::max(m, col[p]);
+        }
+        mx[(size_t)t] = m;
+    });
+    rc.bad_entry = first_bad();
+    rc.dim = *std::max_element(mx.begin(), mx.end());
+    return rc;
+}
+
+template <typename FT>
+HotBlock choose_hot_block(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const FT *val, int32_t dim, int max_pages, bool row_blocked,
+                          int threads, int64_t exact_nnz) {
+    const int T = threads;
+    const int64_t nnz = row_ptr[n_rows];
+    // Frequencies: exact for datasets of up to exact_nnz (8 M) nonzeros; beyond that from every s-th row (the
+    // choice of hot features is a layout decision — any set that passes the checks below is valid —
+    // and a feature in >= 10 % of the rows cannot hide from a sample of millions of entries).
+    const int64_t stride = nnz > exact_nnz ? std::max<int64_t>(1, nnz / std::max<int64_t>(exact_nnz / 2, 1)) : 1;
+    const int64_t sampled_rows = (n_rows + stride - 1) / stride;
+    std::vector<int32_t> cnt((size_t)dim + 1, 0);
+    {
+        // per-thread histograms while they stay small (<= 256 MB in all), merged in thread order; else one table, one thread
+        const int Ts = ((int64_t)(dim + 1) * T * 4 <= ((int64_t)256 << 20)) ? std::min<int>(T, (int)std::max<int64_t>(sampled_rows / 4096, 1)) : 1;
+        std::vector<std::vector<int32_t>> part((size_t)(Ts > 1 ? Ts : 0));
+        parallel_chunks(sampled_rows, Ts, [&](int t, int64_t lo, int64_t hi) {
+            int32_t *c = cnt.data();
+            if (Ts > 1) { part[(size_t)t].assign((size_t)dim + 1, 0); c = part[(size_t)t].data(); }
+            for (int64_t i = lo; i < hi; ++i) {
+                const int64_t r = i * stride;
+                for (int64_t p = row_ptr[r]; p < row_ptr[r + 1]; ++p) ++c[(size_t)col[p]];
+            }
+        });
+        if (Ts > 1)
+            parallel_chunks((int64_t)dim + 1, Ts, [&](int, int64_t lo, int64_t hi) {
+                for (const auto &pc : part)
+                    for (int64_t f = lo; f < hi; ++f) cnt[(size_t)f] += pc[(size_t)f];
+            });
+    }
+    // candidates in descending order of frequency (ties: ascending id).  Page 0 is dense for the forward too, where a
+    // slot costs every row a multiply-add chain: it takes features present in >= 10 % of the rows.  A gradient-side slot
+    // costs a row 4 streamed bytes and saves, per entry, an 8-byte stream read, a P-row gather and an e gather (~2 line
+    // requests of the texture path, which is what bounds the column walk): those pages take features down to 2.5 %.
+    std::vector<int32_t> cand;
+    for (int32_t f = 0; f <= dim; ++f)
+        if ((int64_t)cnt[(size_t)f] * 40 >= sampled_rows) cand.push_back(f);
+    std::sort(cand.begin(), cand.end(), [&](int32_t x, int32_t y) { return cnt[(size_t)x] != cnt[(size_t)y] ? cnt[(size_t)x] > cnt[(size_t)y] : x < y; });
+    const size_t max_rest = (size_t)kHotT * (size_t)((row_blocked ? 1 : max_pages) - 1);
+    HotBlock hb;
+    hb.slot.assign((size_t)dim + 1, -1);
+    hb.kept.assign((size_t)n_rows + 1, 0);
+    std::vector<int8_t> &slot = hb.slot;
+    // one sweep: the CSR length of every row if page 0 leaves the streams, and which candidates may not be
+    // dense — one that occurs twice in a row, or is stored with an explicit zero (its G row must have exactly one
+    // writer); if any is refused the sweep runs again without it (the ranking moves up)
+    size_t used = 0, p0 = 0;   // candidates being tried: the first p0 in page 0 (slots 0..), the next ones in slots kHotT..
+    auto slot_of = [&](size_t j) { return (int8_t)(j < p0 ? j : kHotT + (j - p0)); };
+    for (;;) {
+        p0 = 0;
+        while (p0 < cand.size() && p0 < (size_t)kHotT && (int64_t)cnt[(size_t)cand[p0]] * 10 >= sampled_rows) ++p0;
+        used = p0 < 2 ? 0 : p0 + std::min(cand.size() - p0, max_rest);
+        if (!used) break;
+        for (size_t j = 0; j < used; ++j) slot[(size_t)cand[j]] = slot_of(j);
+        std::vector<slotmask_t> badv((size_t)T, 0u);
+        parallel_chunks(n_rows, T, [&](int t, int64_t lo, int64_t hi) {
+            slotmask_t bad = 0;
+            for (int64_t r = lo; r < hi; ++r) {
+                slotmask_t seen = 0;
+                int64_t keep = 0;
+                for (int64_t p = row_ptr[r]; p < row_ptr[r + 1]; ++p) {
+                    const int8_t h = slot[(size_t)col[p]];
+                    if (h < 0 || h >= kHotT) ++keep;
+                    if (h < 0) continue;
+                    if ((seen >> h & 1u) || (float)val[p] == 0.f) bad |= (slotmask_t)1 << h;
+                    seen |= (slotmask_t)1 << h;
+                }
+                hb.kept[(size_t)r + 1] = keep;
+            }
+            badv[(size_t)t] = bad;
+        });
+        slotmask_t bad = 0;
+        for (slotmask_t x : badv) bad |= x;
+        if (!bad) break;
+        std::vector<int32_t> ok;
+        for (size_t j = 0; j < cand.size(); ++j) {
+            if (j < used) slot[(size_t)cand[j]] = -1;
+            if (j >= used || !(bad >> slot_of(j) & 1u)) ok.push_back(cand[j]);
+        }
+        cand.swap(ok);
+    }
+    if (!used) return hb;
+    // slots in ascending feature order inside every page (the sweep above does not depend on the numbering)
+    hb.p0 = p0;
+    hb.pages = 1 + (int)((used - p0 + kHotT - 1) / kHotT);
+    hb.hot_ids.assign((size_t)(hb.pages * kHotT), -1);
+    std::sort(cand.begin(), cand.begin() + (std::ptrdiff_t)p0);
+    for (size_t lo = p0; lo < used; lo += kHotT) std::sort(cand.begin() + (std::ptrdiff_t)lo, cand.begin() + (std::ptrdiff_t)std::min(used, lo + kHotT));
+    for (size_t j = 0; j < used; ++j) {
+        hb.hot_ids[(size_t)slot_of(j)] = cand[j];
+        slot[(size_t)cand[j]] = slot_of(j);
+    }
+    return hb;
+}
+template HotBlock choose_hot_block<float>(int64_t, const int64_t *, const int32_t *, const float *, int32_t, int, bool, int, int64_t);
+template HotBlock choose_hot_block<double>(int64_t, const int64_t *, const int32_t *, const double *, int32_t, int, bool, int, int64_t);
+
+template <typename FT>
+HotSplit split_hot_rows(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const FT *val, int32_t dim, int64_t batch_rows, HotBlock &hb,
+                        int threads) {
+    const int T = threads;
+    const int64_t nb = n_rows > 0 ? (n_rows + batch_rows - 1) / batch_rows : 0;
+    HotSplit s;
+    if (hb.pages > 1) {
+        s.drop_bits.assign((size_t)(dim + 1) / 32 + 2, 0u);
+        for (size_t h = kHotT; h < hb.hot_ids.size(); ++h)
+            if (hb.hot_ids[h] >= 0) s.drop_bits[(size_t)hb.hot_ids[h] >> 5] |= 1u << (hb.hot_ids[h] & 31);
+    }
+    s.hot_masks.assign((size_t)nb, 0u);
+    s.bwd_out.assign((size_t)nb, 0);
+    s.sp_ptr.swap(hb.kept);
+    for (int64_t r = 0; r < n_rows; ++r) s.sp_ptr[(size_t)r + 1] += s.sp_ptr[(size_t)r];
+    // fill (buffers left uninitialised: every element is written exactly once)
+    s.sp_col.reset(new int32_t[(size_t)std::max<int64_t>(s.sp_ptr[(size_t)n_rows], 1)]);
+    s.sp_val.reset(new float[(size_t)std::max<int64_t>(s.sp_ptr[(size_t)n_rows], 1)]);
+    // page 0 is filled here (its entries leave the CSR stream); the gradient-side pages' entries STAY in the CSR stream,
+    // so their pages are filled on the device from the uploaded stream (k_fill_hot_pages): 64 MB per page and million
+    // rows that neither the host writes nor PCIe carries
+    s.xhot0.reset(new float[(size_t)std::max<int64_t>(n_rows, 1) * kHotT]);
+    const int64_t *sp_ptr = s.sp_ptr.data();
+    const int8_t *slot = hb.slot.data();
+    int32_t *sp_col = s.sp_col.get();
+    float *sp_val = s.sp_val.get(), *xhot = s.xhot0.get();
+    std::vector<std::vector<slotmask_t>> tmask((size_t)T, std::vector<slotmask_t>((size_t)nb, 0u));
+    std::vector<std::vector<int64_t>> tout((size_t)T, std::vector<int64_t>((size_t)nb, 0));
+    parallel_chunks(n_rows, T, [&](int t, int64_t lo, int64_t hi) {
+        for (int64_t r = lo; r < hi; ++r) {
+            slotmask_t seen = 0;
+            int64_t o = sp_ptr[r], outb = 0;
+            float *xr = xhot + (size_t)r * kHotT;
+            for (int h = 0; h < kHotT; ++h) xr[h] = 0.f;
+            for (int64_t p = row_ptr[r]; p < row_ptr[r + 1]; ++p) {
+                const int8_t h = slot[(size_t)col[p]];
+                if (h >= 0) {
+                    seen |= (slotmask_t)1 << h;
+                    if (h < kHotT) xr[h] = (float)val[p];
+                }
+                if (h < 0 || h >= kHotT) {
+                    sp_col[(size_t)o] = col[p];
+                    sp_val[(size_t)o] = (float)val[p];
+                    ++o;
+                    if (h >= 0) ++outb;
+                }
+            }
+            tmask[(size_t)t][(size_t)(r / batch_rows)] |= seen;
+            tout[(size_t)t][(size_t)(r / batch_rows)] += outb;
+        }
+    });
+    for (int t = 0; t < T; ++t)
+        for (int64_t b = 0; b < nb; ++b) {
+            s.hot_masks[(size_t)b] |= tmask[(size_t)t][(size_t)b];
+            s.bwd_out[(size_t)b] += tout[(size_t)t][(size_t)b];
+        }
+    return s;
+}
+template HotSplit split_hot_rows<float>(int64_t, const int64_t *, const int32_t *, const float *, int32_t, int64_t, HotBlock &, int);
+template HotSplit split_hot_rows<double>(int64_t, const int64_t *, const int32_t *, const double *, int32_t, int64_t, HotBlock &, int);
+
+std::vector<int32_t> forward_row_order(int64_t n_rows, int64_t batch_rows, const int64_t *row_ptr, int64_t window, int threads) {
+    std::vector<int32_t> order((size_t)n_rows);
+    const int64_t nb = n_rows > 0 ? (n_rows + batch_rows - 1) / batch_rows : 0;
+    parallel_chunks(nb, std::min<int>(threads, (int)std::max<int64_t>(nb, 1)), [&](int, int64_t blo, int64_t bhi) {
+        std::vector<int64_t> start;
+        for (int64_t b = blo; b < bhi; ++b) {
+            const int64_t row0 = b * batch_rows, rows = std::min(batch_rows, n_rows - row0);
+            const int64_t win = window > 0 ? window : std::max<int64_t>(rows, 1);
+            for (int64_t w0 = 0; w0 < rows; w0 += win) {
+                const int64_t w1 = std::min(rows, w0 + win);
+                int64_t maxlen = 0;
+                for (int64_t r = w0; r < w1; ++r) maxlen = std::max(maxlen, row_ptr[row0 + r + 1] - row_ptr[row0 + r]);
+                start.assign((size_t)maxlen + 2, 0);
+                for (int64_t r = w0; r < w1; ++r) ++start[(size_t)(maxlen - (row_ptr[row0 + r + 1] - row_ptr[row0 + r])) + 1];
+                for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
+                for (int64_t r = w0; r < w1; ++r) {
+                    const size_t key = (size_t)(maxlen - (row_ptr[row0 + r + 1] - row_ptr[row0 + r]));
+                    order[(size_t)(row0 + w0 + start[key]++)] = (int32_t)r;
+                }
+                // windows alternate longest-first / shortest-first: a workgroup takes the same position of every window it visits
+                if (window > 0 && ((w0 / win) & 1)) std::reverse(order.begin() + (row0 + w0), order.begin() + (row0 + w1));
+            }
+        }
+    });
+    return order;
+}
+
+template <typename FT>
+SortedRows sort_rows_by_feature(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const FT *val, int threads) {
+    SortedRows s;
+    s.scol.resize((size_t)row_ptr[n_rows]);
+    s.sval.resize((size_t)row_ptr[n_rows]);
+    std::vector<char> dupv((size_t)threads, 0);      // one byte per thread (vector<bool> packs bits: concurrent writes would race)
+    parallel_chunks(n_rows, threads, [&](int t, int64_t lo, int64_t hi) {
+        std::vector<int32_t> idx;
+        bool dup = false;
+        for (int64_t r = lo; r < hi; ++r) {
+            const int64_t p0 = row_ptr[r], len = row_ptr[r + 1] - p0;
+            idx.resize((size_t)len);
+            std::iota(idx.begin(), idx.end(), 0);
+            std::stable_sort(idx.begin(), idx.end(), [&](int32_t x, int32_t y) { return col[p0 + x] < col[p0 + y]; });   // equal ids keep their stored order
+            for (int64_t j = 0; j < len; ++j) {
+                s.scol[(size_t)(p0 + j)] = col[p0 + idx[(size_t)j]];
+                s.sval[(size_t)(p0 + j)] = (double)val[p0 + idx[(size_t)j]];
+                if (j && s.scol[(size_t)(p0 + j)] == s.scol[(size_t)(p0 + j - 1)]) dup = true;
+            }
+        }
+        dupv[(size_t)t] = dup ? 1 : 0;
+    });
+    for (char b : dupv) s.dup = s.dup || b != 0;
+    return s;
+}
+template SortedRows sort_rows_by_feature<float>(int64_t, const int64_t *, const int32_t *, const float *, int);
+template SortedRows sort_rows_by_feature<double>(int64_t, const int64_t *, const int32_t *, const double *, int);
+
+std::vector<uint32_t> own_bitmaps(const std::vector<HostBatch> &hbs, const std::vector<int32_t> &hot_ids, int32_t dim) {
+    const size_t words = (size_t)dim / 32 + 1;
+    std::vector<uint32_t> own(hbs.size() * words, 0u);
+    for (size_t b = 0; b < hbs.size(); ++b) {
+        uint32_t *bits = own.data() + b * words;
+        const HostBatch &hb = hbs[b];
+        for (const std::vector<int32_t> *lst : {&hb.split_seg, &hb.split_short})
+            for (int32_t c : *lst) { const int32_t f = hb.cfeat[(size_t)c]; bits[f >> 5] |= 1u << (f & 31); }
+        for (int32_t f : hot_ids)
+            if (f >= 0) bits[f >> 5] |= 1u << (f & 31);
+    }
+    return own;
+}
+
 // Host-side metadata of one batch from its column offsets (the transposed stream itself is built
 // on the device, csc_build.hip): the column open at the start of every 64-entry range and the
 // columns whose sum is assembled by k_fixup.

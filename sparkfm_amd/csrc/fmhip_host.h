@@ -1,12 +1,14 @@
 // fmhip_host.h — the library's PURE HOST ARITHMETIC: everything libfmhip.so computes on the host that needs no GPU and no
-// HIP header — row shards, feature relabelling, a batch's range / fixup metadata, the band-affine plan of the backward's ranges,
-// the ALS sweep's level schedule, the data-parallel plan's cuts, interval edges, equal shares and update groups.  fmhip_dataset.hip /
+// HIP header — row shards, feature relabelling, the host passes of the dataset build (validation, the dense hot block's choice and
+// split, the forward row order, the ALS row sort, the own bitmaps), a batch's range / fixup metadata, the band-affine plan of the
+// backward's ranges, the ALS sweep's level schedule, the data-parallel plan's cuts, interval edges, equal shares and update groups.  fmhip_dataset.hip /
 // fmhip_comm.hip call these; tests/host_arith_harness.cpp compiles fmhip_host.cpp with g++ -fsanitize=address,undefined and
 // drives them over random shapes (the sanitizers cannot run on the GPU pool, the index arithmetic can run
 // here).  Not installed, not part of the ABI.
 #pragma once
 #include <stdint.h>
 
+#include <memory>
 #include <thread>
 #include <vector>
 
@@ -44,6 +46,50 @@ void rank_from_counts(int64_t n1, const int64_t *counts, int32_t *rank, int32_t 
 // out[i] = rank[col[i]]; -> -1, or the index of an id outside [0, n1)
 int64_t relabel_columns(int64_t nnz, const int32_t *col, int64_t n1, const int32_t *rank, int32_t *out);
 
+// ---- dataset build (fmhip_dataset_create; FT = float / double, the caller's value type) --------------------------
+// the first row where row_ptr decreases (then nothing else is looked at); the first negative entry of col (NULL: not swept); the largest id
+struct RowCheck { int64_t bad_row = -1, bad_entry = -1; int32_t dim = 0; };
+RowCheck validate_rows(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, int threads);
+// dst[i] = (D)src[i]
+template <typename D, typename S>
+std::vector<D> converted(const S *src, int64_t n, int threads) {
+    std::vector<D> dst((size_t)n);
+    parallel_chunks(n, threads, [&](int, int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; ++i) dst[(size_t)i] = (D)src[i];
+    });
+    return dst;
+}
+// The dense hot block's features: candidates by descending count (ties: ascending id), page 0 takes up to kHotT of those present in
+// >= 10 % of the rows (at least 2, or there is no block), the next (max_pages - 1) * kHotT down to 2.5 % fill pages 1.. (none if
+// row_blocked).  One stored twice in a row, or with a value that is 0 as fp32, is refused and the next candidate moves up.  Counts
+// are exact up to exact_nnz stored entries, from every s-th row beyond.  -> pages = 0: no block; else hot_ids[pages * kHotT]
+// (-1 = unused; live slots first and ascending inside a page), p0 = page 0's live slots, slot[dim + 1] = a feature's slot or -1,
+// kept[r + 1] = row r's entries outside page 0
+constexpr int64_t kHotExactNnz = (int64_t)8 << 20;
+struct HotBlock { int pages = 0; size_t p0 = 0; std::vector<int32_t> hot_ids; std::vector<int8_t> slot; std::vector<int64_t> kept; };
+template <typename FT>
+HotBlock choose_hot_block(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const FT *val, int32_t dim, int max_pages, bool row_blocked,
+                          int threads, int64_t exact_nnz = kHotExactNnz);
+// The rows without page 0's entries: sp_ptr (hb.kept summed in place and moved here) / sp_col / sp_val in stored order, values as
+// fp32; xhot0[n_rows][kHotT] = page 0 (0 = absent); per batch of batch_rows rows the slots seen and the kept entries of pages 1..;
+// drop_bits: bitmap of the ids of pages 1.. (empty if there are none).  The arrays are allocated uninitialised and written once.
+struct HotSplit {
+    std::vector<int64_t> sp_ptr, bwd_out;
+    std::unique_ptr<int32_t[]> sp_col;
+    std::unique_ptr<float[]> sp_val, xhot0;
+    std::vector<slotmask_t> hot_masks; std::vector<uint32_t> drop_bits;
+};
+template <typename FT>
+HotSplit split_hot_rows(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const FT *val, int32_t dim, int64_t batch_rows, HotBlock &hb,
+                        int threads);
+// forward walk order: per batch of batch_rows rows (window > 0: per window of that many of its rows) the local row ids by stored
+// length, longest first, ties in row order; with a window the odd windows are reversed
+std::vector<int32_t> forward_row_order(int64_t n_rows, int64_t batch_rows, const int64_t *row_ptr, int64_t window, int threads);
+// every row's entries stably sorted by feature id (the ALS learner's q pass); dup: some row stores an id twice
+struct SortedRows { std::vector<int32_t> scol; std::vector<double> sval; bool dup = false; };
+template <typename FT>
+SortedRows sort_rows_by_feature(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const FT *val, int threads);
+
 // ---- one batch's metadata from its column offsets --------------------------------------------------------------
 struct HostBatch {
     std::vector<int32_t> cfeat, cptr, range_seg, split_seg, split_short, cdst, mp_feat, mp_ptr;
@@ -52,6 +98,8 @@ struct HostBatch {
 // cfeat / cptr given: the column open at the start of every 64-entry range, the columns whose sum k_fixup assembles (short: up
 // to 8 ranges, else long), the destination of every column piece.  cnt / base: zeroed scratch of dimension + 1 entries (left zeroed)
 void finish_batch_meta(HostBatch &hb, int32_t nnz, std::vector<int32_t> &cnt, std::vector<int32_t> &base);
+// per batch, dim / 32 + 1 words: the features whose gradient rows the fixup launch assembles (cut columns + live hot_ids)
+std::vector<uint32_t> own_bitmaps(const std::vector<HostBatch> &hbs, const std::vector<int32_t> &hot_ids, int32_t dim);
 
 // Band-affine placement of one batch's ranges (BwdArgs::xlist).  first/last: the rows of the first and last entry of every
 // range.  -> the number of ranges placed by their band; lists[x] = XCD x's range ids, seg[x] = the runs of lists[x], each

@@ -215,7 +215,7 @@ struct fmhip_dataset {
     int32_t max_pieces = 0;
     // dense hot block: the entries of the most frequent features are held as dense [n_rows][kHotT] fp32 pages
     // (0 where the feature is absent).  Page 0 (up to kHotT features) is out of both sparse streams; pages 1.. are out
-    // of the CSC stream only (fm_kernels.h, kHotPages)
+    // of the CSC stream only (fm_constants.h, kHotPages)
     int32_t hot_T = 0;                 // 0 = no hot block
     int32_t hot_pages = 0;             // pages in use (0 = no hot block)
     int64_t hot_max_id = -1;           // the largest feature id held in any page

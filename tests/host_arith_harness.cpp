@@ -5,6 +5,11 @@
 // wrong ranges; a level schedule that puts two columns sharing a row side by side races in k_als_level) — while the sanitizers
 // watch the index arithmetic.  VERDICT r4 next #6; the sanitizers cannot run on the GPU pool.
 //
+// Covered: shard_bounds; feature_counts / rank_from_counts / relabel_columns; finish_batch_meta, plan_bands, als_levels; choose_cuts,
+// interval_edges, shard_share, compact_edges, apply_groups; and the host passes of the dataset build — validate_rows,
+// choose_hot_block, split_hot_rows, forward_row_order, sort_rows_by_feature (each for float and double values, with 1 and with
+// 4 threads, which must agree) and own_bitmaps.
+//
 //   host_arith_harness <seed> [cases]
 #include <stdint.h>
 #include <stdio.h>
@@ -432,6 +437,342 @@ static void check_groups(Rng &r) {
     check_tiling(gt, ce.pe, (int)ce.pe.size() - 2);
 }
 
+// ---- the dataset build: validation, the dense hot block's choice and split, forward row order, ALS row sort, own bitmaps ----
+template <typename FT>
+struct Rows {
+    int64_t n_rows = 0;
+    std::vector<int64_t> rp;
+    std::vector<int32_t> col;
+    std::vector<FT> val;
+};
+
+// Rows over n_feat ids of which n_cand (scattered over the id range) are frequent: the first n_page0 of them in 12-90 % of the
+// rows, the others in 3-6 %; every other id is rare.  Some rows are empty, the entries of a row are shuffled.  refuse_a (a
+// page-0 feature) / refuse_b (a later one), when >= 0: stored twice in some rows, or with a value that is 0 as fp32
+template <typename FT>
+static Rows<FT> make_rows(Rng &r, int64_t n_rows, int32_t n_feat, int n_cand, int n_page0, int refuse_a, int refuse_b) {
+    Rows<FT> d;
+    d.n_rows = n_rows;
+    d.rp.assign((size_t)n_rows + 1, 0);
+    std::vector<int32_t> ids((size_t)n_feat);
+    std::iota(ids.begin(), ids.end(), 0);
+    std::shuffle(ids.begin(), ids.end(), r);
+    n_cand = std::min<int>(n_cand, n_feat);
+    std::vector<int> freq((size_t)n_cand);                                     // in 1/1000 of the rows
+    for (int j = 0; j < n_cand; ++j) freq[(size_t)j] = j < n_page0 ? (int)uni(r, 120, 900) : (int)uni(r, 30, 60);
+    const bool dup_a = uni(r, 0, 1) != 0, dup_b = uni(r, 0, 1) != 0;
+    const FT zero = sizeof(FT) == 8 && uni(r, 0, 1) ? (FT)1e-60 : (FT)0;       // a double that is 0 only as fp32, or 0
+    std::vector<std::pair<int32_t, FT>> row;
+    for (int64_t i = 0; i < n_rows; ++i) {
+        row.clear();
+        if (n_feat > 0 && uni(r, 0, 19) != 0) {
+            for (int j = 0; j < n_cand; ++j) {
+                if (uni(r, 0, 999) >= freq[(size_t)j]) continue;
+                FT x = (FT)((double)uni(r, 1, 1000) / 500.0 - 1.001);
+                const bool refused = j == refuse_a || j == refuse_b, dup = j == refuse_a ? dup_a : dup_b;
+                if (refused && !dup && uni(r, 0, 3) == 0) x = zero;
+                row.push_back({ids[(size_t)j], x});
+                if (refused && dup && uni(r, 0, 3) == 0) row.push_back({ids[(size_t)j], (FT)0.5});
+            }
+            if (n_feat > n_cand)
+                for (int64_t e = uni(r, 0, 4); e > 0; --e) row.push_back({ids[(size_t)uni(r, n_cand, n_feat - 1)], (FT)((double)uni(r, 1, 100) / 50.0)});
+            std::shuffle(row.begin(), row.end(), r);
+        }
+        for (const auto &e : row) { d.col.push_back(e.first); d.val.push_back(e.second); }
+        d.rp[(size_t)i + 1] = (int64_t)d.col.size();
+    }
+    return d;
+}
+
+template <typename T>
+static bool same_array(const T *a, const T *b, size_t n) { return n == 0 || memcmp(a, b, n * sizeof(T)) == 0; }
+
+// one dataset through the host passes as fmhip_dataset_create chains them, each with 1 and with 4 threads (equal outputs), each
+// against what the device code relies on.  shape: the corner the case is built around (see the table in the body)
+template <typename FT>
+static void check_dataset_build(Rng &r, int shape) {
+    int64_t n_rows = uni(r, 2, 3000);
+    int32_t n_feat = (int32_t)uni(r, 2, 600);
+    int n_cand = (int)uni(r, 0, 40), n_page0 = (int)uni(r, 0, 20), max_pages = (int)uni(r, 1, kHotPages);
+    bool row_blocked = false;
+    int sample_stride = 0;                                                   // > 0: counts from every so-manieth row or so
+    switch (shape) {
+        case 0: n_rows = 0; break;
+        case 1: n_rows = 1; break;
+        case 2: n_feat = 0; n_cand = 0; break;                                 // zero nonzeros
+        case 3: n_feat = 1; n_cand = 1; n_page0 = 1; break;                    // dimension 0
+        case 4: n_rows = 2000; n_cand = 5; n_page0 = 1; break;                 // one feature at the 10 % mark: no block
+        case 5: n_cand = n_page0 = kHotT; break;
+        case 6: n_cand = n_page0 = kHotT + 1; max_pages = (int)uni(r, 1, 2); break;
+        case 7: n_rows = uni(r, 1000, 2000); n_cand = (int)uni(r, 128, 140); n_page0 = (int)uni(r, 2, 20); max_pages = kHotPages; break;
+        case 8: row_blocked = true; n_cand = 40; n_page0 = 10; max_pages = 4; break;
+        case 9: n_rows = uni(r, 2000, 4000); n_cand = 30; n_page0 = 12; sample_stride = (int)uni(r, 2, 16); break;
+        case 10: n_rows = uni(r, 17000, 20000); n_cand = 20; n_page0 = 6; sample_stride = (g_case / 12 & 1) * 2; break;   // a histogram per thread, of all rows / of every other row
+        default: break;
+    }
+    n_feat = std::max<int32_t>(n_feat, std::min<int32_t>(n_cand, 1));
+    n_page0 = std::min(n_page0, n_cand);
+    const int refuse_a = n_page0 > 2 && uni(r, 0, 2) ? (int)uni(r, 0, n_page0 - 1) : -1;
+    const int refuse_b = n_cand > n_page0 && uni(r, 0, 2) ? (int)uni(r, n_page0, n_cand - 1) : -1;
+    Rows<FT> d = make_rows<FT>(r, n_rows, n_feat, n_cand, n_page0, refuse_a, refuse_b);
+    const int64_t nnz = d.rp[(size_t)n_rows];
+    // the exact / sampled threshold as an argument: the stride is nnz / (threshold / 2)
+    const int64_t exact_nnz = sample_stride > 0 ? std::max<int64_t>(nnz * 2 / sample_stride - 1, 2) : kHotExactNnz;
+    const int64_t *rp = d.rp.data();
+    // (an empty vector's data() may be NULL: the library is handed NULL arrays for datasets without entries too)
+    const int32_t *col = d.col.data();
+    const FT *val = d.val.data();
+    const int kThreads[2] = {1, 4};
+
+    // ---- validate_rows: clean rows; the FIRST negative entry; the FIRST row where row_ptr decreases
+    int32_t dim = 0;
+    for (int32_t c : d.col) dim = std::max(dim, c);
+    for (int T : kThreads) {
+        const RowCheck ok = validate_rows(n_rows, rp, col, T);
+        CHECK(ok.bad_row == -1 && ok.bad_entry == -1 && ok.dim == dim);
+        if (nnz > 0) {
+            const int64_t a = uni(r, 0, nnz - 1), b = uni(r, 0, nnz - 1);
+            const int32_t ka = d.col[(size_t)a], kb = d.col[(size_t)b];
+            d.col[(size_t)a] = -1;
+            d.col[(size_t)b] = INT32_MIN;
+            const RowCheck bad = validate_rows(n_rows, rp, col, T);
+            CHECK(bad.bad_row == -1 && bad.bad_entry == std::min(a, b));
+            d.col[(size_t)a] = ka;
+            d.col[(size_t)b] = kb;
+        }
+        std::vector<int64_t> rp2 = d.rp;
+        int64_t first = -1;
+        for (int j = 0; j < 2 && n_rows > 0; ++j) {
+            const int64_t i = uni(r, 0, n_rows - 1);
+            if (rp2[(size_t)i] < 1 || rp2[(size_t)i + 1] < rp2[(size_t)i]) continue;
+            rp2[(size_t)i + 1] = rp2[(size_t)i] - 1;                               // (row i + 1 then starts lower too: still not a decrease)
+            first = first < 0 ? i : std::min(first, i);
+        }
+        if (first >= 0)
+            for (int64_t i = 0; i < n_rows; ++i)
+                if (rp2[(size_t)i + 1] < rp2[(size_t)i]) { first = i; break; }
+        CHECK(validate_rows(n_rows, rp2.data(), nullptr, T).bad_row == first);
+    }
+
+    // ---- choose_hot_block
+    HotBlock hb[2];
+    for (int t = 0; t < 2; ++t) hb[t] = choose_hot_block<FT>(n_rows, rp, col, val, dim, max_pages, row_blocked, kThreads[t], exact_nnz);
+    CHECK(hb[0].pages == hb[1].pages && hb[0].p0 == hb[1].p0 && hb[0].hot_ids == hb[1].hot_ids && hb[0].slot == hb[1].slot && hb[0].kept == hb[1].kept);
+    const HotBlock &h = hb[0];
+    // what the rows say: entries per feature, and the features that may not be dense (twice in a row, or a stored zero)
+    std::vector<int64_t> cnt((size_t)dim + 1, 0);
+    std::vector<char> refusable((size_t)dim + 1, 0);
+    {
+        std::vector<int64_t> last_row((size_t)dim + 1, -1);
+        for (int64_t i = 0; i < n_rows; ++i)
+            for (int64_t p = rp[i]; p < rp[i + 1]; ++p) {
+                const size_t f = (size_t)col[p];
+                ++cnt[f];
+                if (last_row[f] == i || (float)val[p] == 0.f) refusable[f] = 1;
+                last_row[f] = i;
+            }
+    }
+    CHECK(h.slot.size() == (size_t)dim + 1 || h.pages == 0);
+    if (h.pages == 0) {
+        CHECK(h.hot_ids.empty() && h.p0 == 0);
+    } else {
+        CHECK(h.pages >= 1 && h.pages <= (row_blocked ? 1 : max_pages) && h.pages <= kHotPages && h.hot_ids.size() == (size_t)h.pages * kHotT);
+        CHECK(h.p0 >= 2 && h.p0 <= (size_t)kHotT);
+        std::vector<int> slot_ref((size_t)dim + 1, -1);
+        for (int pg = 0; pg < h.pages; ++pg) {
+            int live = 0;
+            while (live < kHotT && h.hot_ids[(size_t)(pg * kHotT + live)] >= 0) ++live;
+            for (int s2 = 0; s2 < kHotT; ++s2) {
+                const int32_t f = h.hot_ids[(size_t)(pg * kHotT + s2)];
+                CHECK(s2 < live ? (f >= 0 && f <= dim) : f == -1);                 // live slots first
+                if (s2 > 0 && s2 < live) CHECK(h.hot_ids[(size_t)(pg * kHotT + s2 - 1)] < f);   // ascending (k_fill_hot_pages searches them)
+                if (s2 < live) { CHECK(!refusable[(size_t)f] && slot_ref[(size_t)f] == -1); slot_ref[(size_t)f] = pg * kHotT + s2; }
+            }
+            CHECK(pg == 0 ? (size_t)live == h.p0 : (live >= 1 && (live == kHotT || pg == h.pages - 1)));   // no empty page, only the last one partly filled
+        }
+        for (int32_t f = 0; f <= dim; ++f) CHECK((int)h.slot[(size_t)f] == slot_ref[(size_t)f]);
+        for (int64_t i = 0; i < n_rows; ++i) {
+            int64_t keep = 0;
+            for (int64_t p = rp[i]; p < rp[i + 1]; ++p) keep += h.slot[(size_t)col[p]] < 0 || h.slot[(size_t)col[p]] >= kHotT;
+            CHECK(h.kept[(size_t)i + 1] == keep);
+        }
+    }
+    if (nnz <= exact_nnz && nnz > 0) {
+        // exact counts: the candidates (>= 2.5 % of the rows) by descending count, ties by ascending id, WITHOUT the refusable
+        // ones — page 0 is the leading ones at >= 10 % (at most kHotT, at least 2 or there is no block), the other pages take
+        // the next ones while there is room: a refused feature's place goes to the next candidate, none is skipped
+        std::vector<int32_t> surv;
+        for (int32_t f = 0; f <= dim; ++f)
+            if (cnt[(size_t)f] * 40 >= n_rows && !refusable[(size_t)f]) surv.push_back(f);
+        std::sort(surv.begin(), surv.end(), [&](int32_t x, int32_t y) { return cnt[(size_t)x] != cnt[(size_t)y] ? cnt[(size_t)x] > cnt[(size_t)y] : x < y; });
+        size_t p0 = 0;
+        while (p0 < surv.size() && p0 < (size_t)kHotT && cnt[(size_t)surv[p0]] * 10 >= n_rows) ++p0;
+        const size_t rest = p0 < 2 ? 0 : std::min(surv.size() - p0, (size_t)kHotT * (size_t)((row_blocked ? 1 : max_pages) - 1));
+        if (p0 < 2) {
+            CHECK(h.pages == 0);
+        } else {
+            CHECK(h.p0 == p0 && h.pages == 1 + (int)((rest + kHotT - 1) / kHotT));
+            for (size_t j = 0; j < p0 + rest; ++j) {
+                const int sl = h.slot[(size_t)surv[j]];
+                CHECK(j < p0 ? (sl >= 0 && sl < kHotT) : (sl >= kHotT + (int)((j - p0) / kHotT * kHotT) && sl < kHotT + (int)(((j - p0) / kHotT + 1) * kHotT)));
+            }
+            size_t live = 0;
+            for (int32_t f : h.hot_ids) live += f >= 0;
+            CHECK(live == p0 + rest);
+        }
+    } else if (nnz == 0) {
+        CHECK(h.pages == 0);
+    }
+
+    // ---- split_hot_rows (only a chosen block is split); the stream the device will hold either way
+    const int64_t batch_rows = std::max<int64_t>(std::min(uni(r, 1, n_rows + 3), n_rows), 1);      // as the caller clamps it
+    const int64_t nb = n_rows > 0 ? (n_rows + batch_rows - 1) / batch_rows : 0;
+    const int64_t *walk_ptr = rp;
+    HotSplit sp[2];
+    if (h.pages > 0) {
+        for (int t = 0; t < 2; ++t) sp[t] = split_hot_rows<FT>(n_rows, rp, col, val, dim, batch_rows, hb[t], kThreads[t]);
+        const HotSplit &s = sp[0];
+        const int64_t kept = s.sp_ptr[(size_t)n_rows];
+        CHECK(s.sp_ptr == sp[1].sp_ptr && s.bwd_out == sp[1].bwd_out && s.drop_bits == sp[1].drop_bits && s.hot_masks.size() == sp[1].hot_masks.size());
+        CHECK(same_array(s.hot_masks.data(), sp[1].hot_masks.data(), s.hot_masks.size()));
+        CHECK(same_array(s.sp_col.get(), sp[1].sp_col.get(), (size_t)kept) && same_array(s.sp_val.get(), sp[1].sp_val.get(), (size_t)kept));
+        CHECK(same_array(s.xhot0.get(), sp[1].xhot0.get(), (size_t)n_rows * kHotT));
+        CHECK(s.sp_ptr.size() == (size_t)n_rows + 1 && s.sp_ptr[0] == 0 && s.hot_masks.size() == (size_t)nb && s.bwd_out.size() == (size_t)nb);
+        std::vector<slotmask_t> masks((size_t)nb, 0);
+        std::vector<int64_t> outb((size_t)nb, 0);
+        for (int64_t i = 0; i < n_rows; ++i) {
+            // the kept entries in stored order + the non-zero slots of page 0 = the row
+            int64_t o = s.sp_ptr[(size_t)i];
+            float x0[kHotT] = {};
+            for (int64_t p = rp[i]; p < rp[i + 1]; ++p) {
+                const int sl = h.slot[(size_t)col[p]];
+                if (sl >= 0) masks[(size_t)(i / batch_rows)] |= (slotmask_t)1 << sl;
+                if (sl >= 0 && sl < kHotT) { x0[sl] = (float)val[p]; continue; }
+                CHECK(o < s.sp_ptr[(size_t)i + 1] && s.sp_col[(size_t)o] == col[p] && s.sp_val[(size_t)o] == (float)val[p]);
+                ++o;
+                outb[(size_t)(i / batch_rows)] += sl >= kHotT;                    // pages 1..: stays in the CSR, leaves the transposes
+            }
+            CHECK(o == s.sp_ptr[(size_t)i + 1]);
+            CHECK(same_array(x0, s.xhot0.get() + (size_t)i * kHotT, (size_t)kHotT));
+        }
+        CHECK(same_array(masks.data(), s.hot_masks.data(), (size_t)nb) && outb == s.bwd_out);
+        CHECK(s.drop_bits.empty() == (h.pages == 1));
+        if (h.pages > 1) {
+            CHECK(s.drop_bits.size() >= (size_t)dim / 32 + 1);
+            for (size_t w = 0; w < s.drop_bits.size(); ++w)
+                for (int b = 0; b < 32; ++b) {
+                    const size_t f = w * 32 + (size_t)b;
+                    CHECK((s.drop_bits[w] >> b & 1u) == (f <= (size_t)dim && h.slot[f] >= kHotT ? 1u : 0u));
+                }
+        }
+        walk_ptr = s.sp_ptr.data();
+    }
+
+    // ---- forward_row_order over that stream: whole batches, and windows (odd ones reversed)
+    for (int64_t window : {(int64_t)0, uni(r, 1, 3), (int64_t)64}) {
+        const std::vector<int32_t> order = forward_row_order(n_rows, batch_rows, walk_ptr, window, 1);
+        CHECK(order == forward_row_order(n_rows, batch_rows, walk_ptr, window, 4) && order.size() == (size_t)n_rows);
+        std::vector<char> seen;
+        for (int64_t b = 0; b < nb; ++b) {
+            const int64_t row0 = b * batch_rows, rows = std::min(batch_rows, n_rows - row0), win = window > 0 ? window : rows;
+            seen.assign((size_t)rows, 0);
+            for (int64_t w0 = 0; w0 < rows; w0 += win) {
+                const int64_t w1 = std::min(rows, w0 + win);
+                const bool reversed = window > 0 && ((w0 / win) & 1);
+                for (int64_t i = w0; i < w1; ++i) {
+                    const int64_t lr = order[(size_t)(row0 + i)];
+                    CHECK(lr >= w0 && lr < w1 && !seen[(size_t)lr]);                    // a permutation of the window's local row ids
+                    seen[(size_t)lr] = 1;
+                    if (i == w0) continue;
+                    // longest first, ties in row order (a reversed window: the mirror image)
+                    const int64_t a = order[(size_t)(row0 + (reversed ? i : i - 1))], c = order[(size_t)(row0 + (reversed ? i - 1 : i))];
+                    const int64_t la = walk_ptr[row0 + a + 1] - walk_ptr[row0 + a], lc = walk_ptr[row0 + c + 1] - walk_ptr[row0 + c];
+                    CHECK(la > lc || (la == lc && a < c));
+                }
+            }
+        }
+    }
+
+    // ---- sort_rows_by_feature (the caller's rows): per row, by id, equal ids in stored order
+    const SortedRows sr = sort_rows_by_feature<FT>(n_rows, rp, col, val, 1), sr4 = sort_rows_by_feature<FT>(n_rows, rp, col, val, 4);
+    CHECK(sr.scol == sr4.scol && same_array(sr.sval.data(), sr4.sval.data(), sr.sval.size()) && sr.dup == sr4.dup);
+    CHECK(sr.scol.size() == (size_t)nnz && sr.sval.size() == (size_t)nnz);
+    bool dup = false;
+    std::vector<char> taken;
+    for (int64_t i = 0; i < n_rows; ++i) {
+        taken.assign((size_t)(rp[i + 1] - rp[i]), 0);
+        for (int64_t p = rp[i]; p < rp[i + 1]; ++p) {
+            if (p > rp[i]) CHECK(sr.scol[(size_t)p - 1] <= sr.scol[(size_t)p]);
+            dup = dup || (p > rp[i] && sr.scol[(size_t)p - 1] == sr.scol[(size_t)p]);
+            // stable: the entry is the FIRST stored one of its id not handed out yet
+            int64_t q = rp[i];
+            while (q < rp[i + 1] && (taken[(size_t)(q - rp[i])] || col[q] != sr.scol[(size_t)p])) ++q;
+            CHECK(q < rp[i + 1] && sr.sval[(size_t)p] == (double)val[q]);
+            taken[(size_t)(q - rp[i])] = 1;
+        }
+    }
+    CHECK(sr.dup == dup);
+}
+
+// The histogram rule's other branch: per-thread tables of dim + 1 counters would pass 256 MB in all (4 threads: ids beyond 2^24),
+// so ONE table is filled by one thread.  The same rows with and without a single entry of such an id choose the same block.
+static void check_hot_block_one_table(Rng &r) {
+    Rows<float> d = make_rows<float>(r, 9000, 300, 24, 8, 1, 20);
+    int32_t dim = 0;
+    for (int32_t c : d.col) dim = std::max(dim, c);
+    const HotBlock small = choose_hot_block<float>(d.n_rows, d.rp.data(), d.col.data(), d.val.data(), dim, 3, false, 4);
+    size_t at = (size_t)uni(r, 0, (int64_t)d.col.size() - 1);
+    while (small.slot[(size_t)d.col[at]] >= 0) at = (at + 1) % d.col.size();        // (not an entry of a chosen feature)
+    const int32_t big = (int32_t)(((int64_t)1 << 24) + uni(r, 0, 1000));
+    d.col[at] = big;
+    HotBlock hb[2];
+    for (int t = 0; t < 2; ++t) hb[t] = choose_hot_block<float>(d.n_rows, d.rp.data(), d.col.data(), d.val.data(), big, 3, false, t ? 4 : 1);
+    CHECK(small.pages >= 2 && hb[0].pages == small.pages && hb[0].p0 == small.p0 && hb[0].hot_ids == small.hot_ids && hb[0].kept == small.kept);
+    CHECK(hb[1].pages == small.pages && hb[1].p0 == small.p0 && hb[1].hot_ids == small.hot_ids && hb[1].kept == small.kept && hb[1].slot == hb[0].slot);
+    CHECK(hb[0].slot.size() == (size_t)big + 1 && hb[0].slot[(size_t)big] == -1);
+}
+
+// sort_rows_by_feature at its edges: equal ids at the very start of a row, in neighbouring rows (no duplicate), apart in a row
+static void check_row_sort_edges() {
+    const int64_t rp[] = {0, 2, 3, 4, 7};
+    const int32_t col[] = {3, 3, 3, 3, 2, 1, 2};
+    const double val[] = {1, 2, 3, 4, 5, 6, 7};
+    for (int T : {1, 4}) {
+        CHECK(sort_rows_by_feature<double>(1, rp, col, val, T).dup);                                   // {3, 3}
+        CHECK(!sort_rows_by_feature<double>(2, rp + 1, col, val, T).dup);                               // {3}, {3}
+        const SortedRows s = sort_rows_by_feature<double>(1, rp + 3, col, val, T);                      // {2, 1, 2}
+        CHECK(s.dup && s.scol[4] == 1 && s.scol[5] == 2 && s.scol[6] == 2 && s.sval[4] == 6 && s.sval[5] == 5 && s.sval[6] == 7);
+    }
+}
+
+// own_bitmaps: a batch's bits = the features of its cut columns (both fixup lists) + the live slots of the hot block
+static void check_own_bitmaps(Rng &r) {
+    const int32_t dim = (int32_t)uni(r, 0, 700);
+    std::vector<HostBatch> hbs((size_t)uni(r, 0, 4));
+    std::vector<int32_t> hot_ids((size_t)(uni(r, 0, 3) * kHotT), -1);
+    for (auto &f : hot_ids)
+        if (uni(r, 0, 2) == 0) f = (int32_t)uni(r, 0, dim);
+    std::vector<std::vector<char>> want(hbs.size(), std::vector<char>((size_t)dim + 1, 0));
+    for (size_t b = 0; b < hbs.size(); ++b) {
+        HostBatch &hb = hbs[b];
+        for (int32_t f = 0; f <= dim; ++f)
+            if (uni(r, 0, 3) == 0) hb.cfeat.push_back(f);
+        for (size_t c = 0; c < hb.cfeat.size(); ++c) {
+            const int64_t k = uni(r, 0, 5);
+            if (k == 0) hb.split_seg.push_back((int32_t)c);
+            if (k == 1) hb.split_short.push_back((int32_t)c);
+            if (k <= 1) want[b][(size_t)hb.cfeat[c]] = 1;
+        }
+        for (int32_t f : hot_ids)
+            if (f >= 0) want[b][(size_t)f] = 1;
+    }
+    const std::vector<uint32_t> own = own_bitmaps(hbs, hot_ids, dim);
+    const size_t words = (size_t)dim / 32 + 1;
+    CHECK(own.size() == hbs.size() * words);
+    for (size_t b = 0; b < hbs.size(); ++b)
+        for (size_t f = 0; f < words * 32; ++f) CHECK((own[b * words + f / 32] >> (f & 31) & 1u) == (f <= (size_t)dim && want[b][f] ? 1u : 0u));
+}
+
 int main(int argc, char **argv) {
     g_seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
     const int cases = argc > 2 ? atoi(argv[2]) : 40;
@@ -443,6 +784,9 @@ int main(int argc, char **argv) {
         check_pieces(r);
         check_plan(r);
         for (int j = 0; j < 20; ++j) check_groups(r);
+        check_dataset_build<float>(r, g_case % 12);
+        check_dataset_build<double>(r, (g_case + 6) % 12);
+        check_own_bitmaps(r);
     }
     g_case = -1;
     // the multi-threaded paths: private tables per thread, and (tables too large for that) one table with atomic adds
@@ -450,6 +794,8 @@ int main(int argc, char **argv) {
     check_relabel(r, false);
     check_relabel(r, true);
     unsetenv("FMHIP_HOST_THREADS");
+    check_hot_block_one_table(r);
+    check_row_sort_edges();
     printf("host_arith_harness: seed %llu, %d cases: checks ok\n", (unsigned long long)g_seed, cases);
     return 0;
 }

@@ -588,11 +588,14 @@ def test_bench_roofline_says_what_bounds_the_step():
 def test_host_arithmetic_under_the_sanitizers(tmp_path):
     """the library's pure host arithmetic — row shards, feature relabelling (one thread, private tables per
     thread, one table with atomic adds), a batch's range / fixup metadata incl. row-blocked pieces, the band-affine plan of the
-    backward's ranges, the ALS level schedule, the data-parallel plan's cuts, interval edges, equal shares, update groups and compact intervals
+    backward's ranges, the ALS level schedule, the data-parallel plan's cuts, interval edges, equal shares, update groups and compact intervals,
+    and the host passes of the dataset build (validate_rows, choose_hot_block, split_hot_rows, forward_row_order, sort_rows_by_feature:
+    float and double values, 1 and 4 threads with equal results; own_bitmaps)
     (sparkfm_amd/csrc/fmhip_host.cpp: the very translation unit libfmhip.so links) — compiled with g++ -fsanitize=address,undefined
     and driven over seeded random shapes by tests/host_arith_harness.cpp, which checks every function against the contract the
     device code relies on (each range in exactly one ascending run of the band plan, no two columns of an ALS level sharing a
-    row, shares that tile their interval ...).  The GPU pool cannot run sanitizers; this index arithmetic needs no GPU."""
+    row, shares that tile their interval, a hot block without a feature stored twice in a row whose pages ascend, a split that
+    loses no entry ...).  The GPU pool cannot run sanitizers; this index arithmetic needs no GPU."""
     import subprocess
     exe = str(tmp_path / "host_arith")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-pthread",

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""What `DataSet.cache()` costs and where: FMHIP_BUILD_TIMING=1 python3 tools/time_dataset_build.py [config] [rows] [batch_rows]"""
+"""What `DataSet.cache()` costs and where: FMHIP_BUILD_TIMING=1 python3 tools/time_dataset_build.py [config] [rows] [batch_rows]
+Two builds per process (the first one also pays for the device's start-up), each followed by the process's peak host RSS so far."""
 import os
+import resource
 import sys
 import time
 
@@ -15,5 +17,6 @@ d = synth.make_config(config, rows=rows)
 for rep in range(2):
     t = time.time()
     ds = DataSet.from_arrays(d, batch_rows=batch).cache()
-    print("%s: %d rows, %d nnz: cache() %.3f s" % (config, rows, d["row_ptr"][-1], time.time() - t), file=sys.stderr)
+    print("%s: %d rows, %d nnz: cache() %.3f s, peak RSS %.1f MiB" % (config, rows, d["row_ptr"][-1], time.time() - t,
+                                                                      resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0), file=sys.stderr)
     ds.unpersist()
