@@ -12,7 +12,7 @@
 //     sparkfm::HipALS       S/fm/lib/ALS.scala:15-75,202-208 the reference's own learner in fp64 on the GPU
 //     sparkfm::FM           S/fm/FM.scala:25-33, S/fm/impl/FactorizationMachines.scala:30-51   the fit loop
 //
-// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC) and include/fmhip_ranking.h (ranking evaluation) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
+// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC), include/fmhip_ranking.h (ranking evaluation) and include/fmhip_weights.h (per-row example weights) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
 // here a non-zero status of the C ABI becomes sparkfm::Error carrying fmhip_last_error().  Parameters live on the host as in
 // the reference (public, mutable: `fm.w0`, `fm.w`, `fm.v` with v[f + i*k] = breeze's column-major DenseMatrix(k, n+1)); every
 // call that needs them on the device uploads them first, as jvm/HipSGD.scala does (the fit loop calls `learn` once per
@@ -33,6 +33,7 @@
 #include "fmhip_pairing.h"
 #include "fmhip_metrics.h"
 #include "fmhip_ranking.h"
+#include "fmhip_weights.h"
 
 namespace sparkfm {
 
@@ -52,10 +53,13 @@ struct SparseVector {
 
 // S/DataSet.scala:42-62 — the rows live on the host until cache() uploads them (mini-batches of batch_rows rows; 0 = one batch,
 // what HipALS needs); unpersist() drops the device copy (S/fm/impl/FactorizationMachines.scala:36,48)
+// weights (optional; empty = an unweighted dataset): one example weight c_r >= 0 per row — every training path then forms
+// e_r <- c_r * e_r (include/fmhip_weights.h); their values are checked when cache() moves the rows to the device
 class DataSet {
   public:
-    explicit DataSet(const std::vector<std::pair<double, SparseVector>> &rows, int64_t batch_rows = 0, int device = 0)
-        : batch_rows_(batch_rows), device_(device) {
+    explicit DataSet(const std::vector<std::pair<double, SparseVector>> &rows, int64_t batch_rows = 0, int device = 0,
+                     std::vector<double> weights = {})
+        : weights_(std::move(weights)), batch_rows_(batch_rows), device_(device) {
         row_ptr_.push_back(0);
         for (const auto &r : rows) {
             if (r.second.index.size() != r.second.data.size()) throw Error(FMHIP_ERR_INVALID, "index / data length mismatch");
@@ -64,17 +68,27 @@ class DataSet {
             y_.push_back(r.first);
             row_ptr_.push_back((int64_t)col_.size());
         }
+        check_weights();
     }
-    DataSet(std::vector<int64_t> row_ptr, std::vector<int32_t> col, std::vector<double> val, std::vector<double> y, int64_t batch_rows = 0, int device = 0)
-        : row_ptr_(std::move(row_ptr)), col_(std::move(col)), val_(std::move(val)), y_(std::move(y)), batch_rows_(batch_rows), device_(device) {
+    DataSet(std::vector<int64_t> row_ptr, std::vector<int32_t> col, std::vector<double> val, std::vector<double> y, int64_t batch_rows = 0, int device = 0,
+            std::vector<double> weights = {})
+        : row_ptr_(std::move(row_ptr)), col_(std::move(col)), val_(std::move(val)), y_(std::move(y)), weights_(std::move(weights)),
+          batch_rows_(batch_rows), device_(device) {
         if (row_ptr_.size() != y_.size() + 1) throw Error(FMHIP_ERR_INVALID, "row_ptr must have one entry more than there are labels");
+        check_weights();
     }
     DataSet(const DataSet &) = delete;
     DataSet &operator=(const DataSet &) = delete;
     ~DataSet() { (void)fmhip_dataset_destroy(h_); }
 
     DataSet &cache() {      // dataset.cache() + transposeInput (S/DataSet.scala:48-62)
-        if (!h_) check(fmhip_dataset_create(device_, (int64_t)y_.size(), row_ptr_.data(), col_.data(), val_.data(), y_.data(), batch_rows_, &h_));
+        if (h_) return *this;
+        if (weights_.empty()) {
+            check(fmhip_dataset_create(device_, (int64_t)y_.size(), row_ptr_.data(), col_.data(), val_.data(), y_.data(), batch_rows_, &h_));
+        } else {
+            fmhip_dataset_opts opts{(int32_t)sizeof(fmhip_dataset_opts), -1, batch_rows_, -1};
+            check(fmhip_dataset_create_weighted(device_, (int64_t)y_.size(), row_ptr_.data(), col_.data(), val_.data(), y_.data(), weights_.data(), &opts, &h_));
+        }
         return *this;
     }
     DataSet &unpersist() {
@@ -94,13 +108,17 @@ class DataSet {
         return nb;
     }
     const std::vector<double> &labels() const { return y_; }
+    const std::vector<double> &weights() const { return weights_; }       // empty: unweighted
     fmhip_dataset_t handle() { return cache().h_; }
     int device() const { return device_; }
 
   private:
+    void check_weights() const {
+        if (!weights_.empty() && weights_.size() != y_.size()) throw Error(FMHIP_ERR_INVALID, "weights must hold one weight per row");
+    }
     std::vector<int64_t> row_ptr_;
     std::vector<int32_t> col_;
-    std::vector<double> val_, y_;
+    std::vector<double> val_, y_, weights_;
     int64_t batch_rows_;
     int device_;
     fmhip_dataset_t h_ = nullptr;
@@ -151,6 +169,14 @@ class FMModel {
         double logloss = 0.0;
         check(fmhip_logloss(upload(), dataset.handle(), &logloss, nullptr));
         return logloss;
+    }
+    // The weighted scores of predict over a WEIGHTED dataset (fmhip_weighted_scores): sum_w, rmse = sqrt(sum c (yhat - y)^2 / sum c),
+    // mae, logloss, rows, nonfinite; NaN ratios when the weights sum to 0.  computeRMSE / computeLogLoss ignore the weights.
+    fmhip_weighted_result weightedScores(DataSet &dataset) {
+        fmhip_weighted_result r{};
+        r.struct_size = (int32_t)sizeof r;
+        check(fmhip_weighted_scores(upload(), dataset.handle(), &r));
+        return r;
     }
     // Pairwise ranking score of the pairs (rows 2j, 2j+1) of `dataset` (fmhip_pair_logloss): the mean of -log sigmoid(+-d) over the
     // pairs' margins d = predict(row 2j) - predict(row 2j+1), the sign by which row carries the larger label ...

@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -51,6 +51,8 @@ SYMBOLS_PAIRING = ("fmhip_model_set_pairing", "fmhip_pair_logloss")
 SYMBOLS_METRICS = ("fmhip_auc_scores", "fmhip_auc")
 # ... and include/fmhip_ranking.h — ranking evaluation: exact ranks of given candidate rows, HR / NDCG / MRR / MAP from them
 SYMBOLS_RANKING = ("fmhip_rank", "fmhip_rank_metrics")
+# ... and include/fmhip_weights.h — per-row example weights: weighted datasets, weighted scores
+SYMBOLS_WEIGHTS = ("fmhip_dataset_create_weighted", "fmhip_rows_create_weighted", "fmhip_dataset_weights", "fmhip_weighted_scores")
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -178,6 +180,31 @@ class RankMetrics(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+class WeightedResult(C.Structure):
+    """fmhip_weighted_result (include/fmhip_weights.h); struct_size is filled in on construction."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("sum_w", C.c_double), ("rmse", C.c_double), ("mae", C.c_double),
+                ("logloss", C.c_double), ("rows", C.c_int64), ("nonfinite", C.c_int64)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(WeightedResult)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("struct_size", "reserved")}
+
+
+def row_weights(weights, n):
+    """None | n numbers -> None | a contiguous float64 array (ValueError: wrong length).  Their values — finite, >= 0 — are the
+    library's to check: it names the first offending row."""
+    if weights is None:
+        return None
+    import numpy as np
+    w = np.ascontiguousarray(weights, np.float64)
+    if w.shape != (n,):
+        raise ValueError("weights must hold one weight per row (%d), not shape %r" % (n, w.shape))
+    return w
 
 
 def row_lists(lists, n_contexts, n_candidates, what):
@@ -367,7 +394,11 @@ def load():
     L.fmhip_auc.argtypes = [vp, vp, vp, P(AucResult), P(Stats)]
     L.fmhip_rank.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.fmhip_rank_metrics.argtypes = [i64, vp, vp, i32, P(RankMetrics)]
-    for name in SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING:
+    L.fmhip_dataset_create_weighted.argtypes = [C.c_int, i64, vp, vp, vp, vp, vp, P(DatasetOpts), P(vp)]
+    L.fmhip_rows_create_weighted.argtypes = [C.c_int, i64, vp, vp, vp, vp, vp, P(vp)]
+    L.fmhip_dataset_weights.argtypes = [vp, P(C.c_int), P(dbl), vp]
+    L.fmhip_weighted_scores.argtypes = [vp, vp, P(WeightedResult)]
+    for name in SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS:
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

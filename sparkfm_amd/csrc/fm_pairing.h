@@ -22,6 +22,7 @@ struct PairArgs {
     int32_t n_pairs;
     int32_t pack_k;      // >= 0: packed rows (FwdArgs::pack_k)
     int32_t loss;        // Loss (fm_kernels.h)
+    const float *c;      // weighted dataset (fm_weights.h): [2 * n_pairs] the batch's row weights, pair j's = c[2j]; NULL: none
 };
 
 // grid of launch_pair_finish = the number of per-block statistic partials it writes (<= kMaxFwdBlocks)

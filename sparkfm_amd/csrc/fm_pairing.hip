@@ -7,49 +7,14 @@
 namespace fmhip {
 namespace {
 
-// sigma(d) - t, t in {0, 1}, without overflow — the form of row_finish (fm_forward.hip) applied to the pair's margin: z = exp(-|d|)
-// <= 1, and 1 - sigma(d) = sigma(-d) is formed directly, so a saturated margin on the right side gives a tiny residual rather
-// than a difference of two numbers near 1.  z is handed back for the log-loss, log1p(z) + max(t ? -d : d, 0).
-__device__ __forceinline__ float pair_sigma_residual(float d, bool t, float &z) {
-    z = expf(-fabsf(d));
-    const float inv = 1.f / (1.f + z);
-    const bool pos = d >= 0.f;
-    return t ? -(pos ? z * inv : inv) : (pos ? inv : z * inv);
-}
-
-// block partial of N sums (fixed order), to bsum[blockIdx.x][4] (the slots past N: 0)
-template <int N>
-__device__ __forceinline__ void pair_block_sums(double *bsum, double (&v)[N], const int (&slot)[N]) {
-    static_assert(N <= 4, "a partial has four slots");
-    __shared__ double sh[N][kBlock / 64];
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v[i] += __shfl_xor(v[i], m, 64);
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int i = 0; i < N; ++i) sh[i][wv] = v[i];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double o[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            double t = 0.0;
-#pragma unroll
-            for (int w = 0; w < kBlock / 64; ++w) t += sh[i][w];
-            o[slot[i]] = t;
-        }
-        *reinterpret_cast<double4 *>(bsum + (size_t)blockIdx.x * 4) = make_double4(o[0], o[1], o[2], o[3]);
-    }
-}
-
 // One slot of LPN lanes per pair: lane l holds floats 4*(l + jj*LPN) .. +3 of both rows (the forward's geometry), so a wave
 // moves 64/LPN pairs = 128/LPN whole rows per instruction, every row a contiguous 16-B-per-lane segment.  A pure stream over P
 // (read once, written once; no LDS but the statistics' few doubles); pairs grid-strided, so the result does not depend on the grid.
 // sum e is never formed: the partial's first slot is 0.0, which is what (+g) + (-g) summed pair by pair would have to be and what
 // a sum over rows in any other order is not.
-template <int LPN, int J, bool PACKED>
+// WEIGHTED (a weighted dataset, fm_weights.h): the pair's residual is c_2j * g — row 2j's weight; row 2j+1's is not read — so the
+// rows' residuals still sum to exactly zero.  The unweighted instances do not see the pointer.
+template <int LPN, int J, bool PACKED, bool WEIGHTED>
 __global__ __launch_bounds__(kBlock) void k_pair_finish(PairArgs a) {
     constexpr int KP = 4 * LPN * J;
     constexpr int SLOTS = kBlock / LPN;
@@ -66,7 +31,8 @@ __global__ __launch_bounds__(kBlock) void k_pair_finish(PairArgs a) {
         const float2 yh = reinterpret_cast<const float2 *>(a.yhat)[j], yy = reinterpret_cast<const float2 *>(a.y)[j];
         const float d = yh.x - yh.y, dy = yy.x - yy.y;
         float z;
-        const float g = logistic ? pair_sigma_residual(d, dy > 0.f, z) : d - dy;
+        float g = logistic ? pair_sigma_residual(d, dy > 0.f, z) : d - dy;
+        if (WEIGHTED) g = weighted_residual(a.c[2 * j], g);
         const float e0 = g, e1 = -g;
 #pragma unroll
         for (int jj = 0; jj < J; ++jj) {
@@ -131,8 +97,11 @@ hipError_t launch_pair_finish(int Kp, const PairArgs &a, hipStream_t s, int *n_p
     const dim3 g((unsigned)blocks), b(kBlock);
 #define FMHIP_PF(LPN_, J_)                                                                      \
     do {                                                                                        \
-        if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<LPN_, J_, true>), g, b, 0, s, a);  \
-        else hipLaunchKernelGGL((k_pair_finish<LPN_, J_, false>), g, b, 0, s, a);               \
+        if (a.c) {                                                                                      \
+            if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<LPN_, J_, true, true>), g, b, 0, s, a);  \
+            else hipLaunchKernelGGL((k_pair_finish<LPN_, J_, false, true>), g, b, 0, s, a);               \
+        } else if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<LPN_, J_, true, false>), g, b, 0, s, a); \
+        else hipLaunchKernelGGL((k_pair_finish<LPN_, J_, false, false>), g, b, 0, s, a);                \
     } while (0)
     switch (Kp) {
         case 32: FMHIP_PF(8, 1); break;

@@ -480,7 +480,7 @@ int fmhip_batch_grad(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, double *
 int fmhip_als_epoch(fmhip_model_t m, fmhip_dataset_t d, double reg0, double regw, double regv) {
     WriteLock lock(m);
     TRY(check_train(m, d));
-    if (const char *why = refusal(Path::kAls, m->rule)) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
+    if (const char *why = refusal(Path::kAls, m->rule, d->weighted)) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
     if (d->batches.size() > 1 || (d->nnz > 0 && !d->val64.p))
         return fail(FMHIP_ERR_UNSUPPORTED, "ALS walks the whole-dataset transpose: create the dataset with batch_rows <= 0 "
                                            "(single batch, at most 2^27 stored nonzeros) and without asking for the dense hot "

@@ -115,6 +115,7 @@ int need_rccl() {
     } while (0)
 
 constexpr int kMaxCuts = 7;      // == FMHIP_DP_MAX_CUTS
+constexpr int kCtrlWords = kMaxCuts + 2;      // int64 words of the communicator's scratch: the cuts' broadcast, the plan's agreement vector
 static_assert(kMaxCuts == FMHIP_DP_MAX_CUTS, "fmhip.h and fmhip_comm.hip disagree on the number of cuts");
 
 // Stand-in for a collective's duration on the comm stream (fmhip_comm_emulate): one wave spins on the
@@ -285,7 +286,7 @@ struct fmhip_comm {
     hipEvent_t ev_rows = nullptr;             // compute stream: this rank's row count is in place
     float *rows_dev = nullptr;                // device float: the step's global row count |B| (exchanged first)
     std::vector<int64_t> cuts;                // ascending feature ids in (0, n+1) cutting the backward into intervals (empty: one collective)
-    int64_t *scratch = nullptr;               // device int64[kMaxCuts + 1] for the small control collectives
+    int64_t *scratch = nullptr;               // device int64[kCtrlWords] for the small control collectives
     double emu_bytes_per_us = 0.0;            // > 0: every collective is followed by a delay of bytes / this (fmhip_comm_emulate)
     int emu_wgs = 0;                          // > 0: the delay is spent by this many workgroups streaming the payload (fmhip_comm_emulate_load)
     bool profiling = false;
@@ -971,6 +972,8 @@ int local_checks(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t
                                        "optimizer %d (eps %g, initial accumulator %g) (fmhip_model_set_optimizer): call fmhip_dp_plan again "
                                        "(every rank)", p.opt, p.ada_eps, p.ada_init, r.opt, r.ada_eps, r.ada_init);
     }
+    // a weighted dataset the plan has not seen (fmhip_dp_plan refuses the pipelined exchange on every rank when it sees one)
+    if (c->exchange == FMHIP_EXCHANGE_PIPELINED && d->weighted) return fail(FMHIP_ERR_UNSUPPORTED, "%s", refusal(Path::kPipelined, m->rule, true));
     if (c->exchange == FMHIP_EXCHANGE_TOUCHED && !c->tsteps.empty() && c->msg_kp != m->Kp)
         return fail(FMHIP_ERR_INVALID, "the touched-rows exchange was planned for rows of %d floats, this model has %d: call fmhip_dp_plan "
                                        "with this model (every rank)", c->msg_kp, m->Kp);
@@ -1062,7 +1065,7 @@ static int comm_resources(fmhip_comm *c) {
     for (int i = 0; i <= kMaxCuts && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&c->ev_done[i], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_rows, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_gathered, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->scratch), (kMaxCuts + 1) * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->scratch), kCtrlWords * sizeof(int64_t));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->rows_dev), 32 * sizeof(float));
     if (e != hipSuccess) return fail(FMHIP_ERR_HIP, "communicator resources: %s", hipGetErrorString(e));
     return FMHIP_OK;
@@ -1318,12 +1321,14 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     // (it cannot cut its backward: then nobody does, same collectives everywhere), the touched-rows table's width, and
     // whether some rank cannot hold the sharded exchange's equal shares, and the models' loss and pairing in one word, loss + 2 * pairing
     // (it and its negation, put_agree: every rank holds the same word iff agreed).  All ranks pass or fail together.
-    // The last slot: whether some rank's model is not plain SGD — then (and only then: an SGD plan issues the collectives it
+    // Slot 7: whether some rank's model is not plain SGD — then (and only then: an SGD plan issues the collectives it
     // always did) a second max-reduce agrees the optimizer and the bit patterns of its settings.
-    constexpr int kAgree = 8;
-    static_assert(kAgree <= kMaxCuts + 1, "the plan's agreement vector travels in the communicator's scratch (kMaxCuts + 1 int64)");
+    // The last slot: whether some rank's dataset carries example weights (fm_weights.h) — the ranks' datasets may differ in that,
+    // but a path that refuses weights (the pipelined exchange) must refuse on every rank or on none.
+    constexpr int kAgree = 9;
+    static_assert(kAgree <= kCtrlWords, "the plan's agreement vector travels in the communicator's scratch (kCtrlWords int64)");
     const TrainRule &rule = m->rule;
-    int64_t agree[kAgree] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size(), 0, 0, rule.adagrad()};
+    int64_t agree[kAgree] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size(), 0, 0, rule.adagrad(), d->weighted};
     put_agree(agree + 5, rule.loss + 2 * rule.pairing);
     for (const auto &bm : d->batches) {
         agree[0] = std::max<int64_t>(agree[0], bm.rows);
@@ -1355,7 +1360,8 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
         return fail(FMHIP_ERR_INVALID, "the ranks' models train under different losses (fmhip_model_set_loss) or pairings (fmhip_model_set_pairing): "
                                        "set the same loss and the same pairing on every rank");
     // (agreed above: every rank holds the same pairing, so every rank refuses here or none does)
-    if (const char *why = c->exchange == FMHIP_EXCHANGE_PIPELINED ? refusal(Path::kPipelined, rule) : nullptr)
+    // (... and agree[8] is the same on every rank)
+    if (const char *why = c->exchange == FMHIP_EXCHANGE_PIPELINED ? refusal(Path::kPipelined, rule, agree[8] != 0) : nullptr)
         return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
     if ((double)agree[0] * c->world >= 16777216.0)
         return fail(FMHIP_ERR_INVALID, "a global batch of %lld x %d rows exceeds 2^24 (the summed row count travels as one fp32 word): "

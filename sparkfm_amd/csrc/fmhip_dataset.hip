@@ -4,6 +4,7 @@
 // csc_build.hip with their column index) here — and the dataset entry points of include/fmhip.h.  The step that consumes all
 // this: fmhip_step.hip.
 #include "fmhip_internal.h"
+#include "../../include/fmhip_weights.h"
 #include "csc_build.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -311,7 +312,7 @@ int pack_column_index(fmhip_dataset &d, std::vector<HostBatch> &hbs) {
 template <typename FT>
 int dataset_create_impl(int device, int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const FT *val,
                         const FT *y, int64_t batch_rows, bool scoring, fmhip_dataset_t *out, int hot_opt = -1,
-                        int64_t rb_opt = -1) {
+                        int64_t rb_opt = -1, const double *weight = nullptr) {
     const bool want_hot = hot_opt < 0 ? tune_default(kTuneHot) > 0 : hot_opt > 0;
     const int max_hot_pages = std::max(1, std::min(kHotPages, hot_opt > 0 ? hot_opt : tune_default(kTuneHotPages)));
     const int64_t want_rb = rb_opt < 0 ? std::max(tune_default(kTuneRowBlock), 0) : rb_opt;
@@ -329,6 +330,10 @@ int dataset_create_impl(int device, int64_t n_rows, const int64_t *row_ptr, cons
     if (n_rows > 0 && !y && !scoring) return fail(FMHIP_ERR_INVALID, "y is NULL");
     if (chk.bad_entry >= 0) return fail(FMHIP_ERR_INVALID, "negative feature index at entry %lld", (long long)chk.bad_entry);
     const int32_t dim = chk.dim;
+    if (weight) {     // per-row example weights (include/fmhip_weights.h): finite and >= 0
+        const int64_t bad = validate_weights(n_rows, weight, host_threads(n_rows));
+        if (bad >= 0) return fail(FMHIP_ERR_INVALID, "weight[%lld] = %g: a row's weight must be finite (as fp32) and >= 0", (long long)bad, weight[bad]);
+    }
     pt.lap("validate");
     TRY(set_device(device));
     std::unique_ptr<fmhip_dataset> d(new (std::nothrow) fmhip_dataset());
@@ -385,6 +390,12 @@ int dataset_create_impl(int device, int64_t n_rows, const int64_t *row_ptr, cons
         const std::vector<float> yf = y ? converted<float>(y, n_rows, 1) : std::vector<float>((size_t)n_rows, 0.f);
         TRY(upload(d->row_ptr, sp_row_ptr, (size_t)n_rows + 1)); TRY(upload(d->col, sp_col, (size_t)nnz_s));
         TRY(upload(d->val, val_up, (size_t)nnz_s)); TRY(upload(d->y, yf.data(), (size_t)n_rows));
+        if (weight) {
+            const std::vector<float> cf = converted<float>(weight, n_rows, 1);
+            for (float c : cf) d->weight_sum += (double)c;
+            TRY(upload(d->c, cf.data(), (size_t)n_rows));
+            d->weighted = true;
+        }
         if (!scoring) { TRY(d->crow.alloc((size_t)nnz_s)); TRY(d->cval.alloc((size_t)nnz_s)); }
         if (split) {
             TRY(d->xhot.alloc((size_t)std::max<int64_t>(n_rows, 1) * kHotT * (size_t)d->hot_pages));
@@ -487,6 +498,37 @@ int fmhip_rows_create_f32(int device, int64_t n_rows, const int64_t *row_ptr, co
 int fmhip_dataset_create_f32(int device, int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const float *val,
                              const float *y, int64_t batch_rows, fmhip_dataset_t *out) {
     return dataset_create_impl<float>(device, n_rows, row_ptr, col, val, y, batch_rows, false, out);
+}
+
+// ---- per-row example weights (include/fmhip_weights.h)
+
+int fmhip_dataset_create_weighted(int device, int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const double *val,
+                                  const double *y, const double *weight, const fmhip_dataset_opts *opts, fmhip_dataset_t *out) {
+    if (opts && opts->struct_size != (int32_t)sizeof(fmhip_dataset_opts))
+        return fail(FMHIP_ERR_INVALID, "opts->struct_size is not sizeof(fmhip_dataset_opts)");
+    return dataset_create_impl<double>(device, n_rows, row_ptr, col, val, y, opts ? opts->batch_rows : 0, false, out, opts ? opts->hot_block : -1,
+                                       opts ? opts->row_block_rows : -1, weight);
+}
+
+int fmhip_rows_create_weighted(int device, int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const double *val,
+                               const double *y, const double *weight, fmhip_dataset_t *out) {
+    return dataset_create_impl<double>(device, n_rows, row_ptr, col, val, y, 0, true, out, -1, -1, weight);
+}
+
+int fmhip_dataset_weights(fmhip_dataset_t d, int *has, double *sum, double *out) {
+    if (!d) return fail(FMHIP_ERR_INVALID, "dataset is NULL");
+    if (has) *has = d->weighted ? 1 : 0;
+    if (sum) *sum = d->weighted ? d->weight_sum : (double)d->n_rows;
+    if (!out || d->n_rows == 0) return FMHIP_OK;
+    if (!d->weighted) {
+        std::fill(out, out + d->n_rows, 1.0);
+        return FMHIP_OK;
+    }
+    TRY(set_device(d->device));
+    std::vector<float> h((size_t)d->n_rows);
+    HIP_TRY(hipMemcpy(h.data(), d->c.p, h.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int64_t r = 0; r < d->n_rows; ++r) out[r] = (double)h[(size_t)r];
+    return FMHIP_OK;
 }
 
 int fmhip_dataset_destroy(fmhip_dataset_t d) {

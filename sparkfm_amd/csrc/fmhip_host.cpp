@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <numeric>
 
 namespace fmhip {
@@ -122,6 +123,18 @@ RowCheck validate_rows(int64_t n_rows, const int64_t *row_ptr, const int32_t *co
     rc.bad_entry = first_bad();
     rc.dim = *std::max_element(mx.begin(), mx.end());
     return rc;
+}
+
+int64_t validate_weights(int64_t n_rows, const double *weight, int threads) {
+    if (threads < 1) threads = 1;
+    std::vector<int64_t> bad((size_t)threads, -1);          // every thread's first finding: the first of them is the first of all
+    parallel_chunks(n_rows, threads, [&](int t, int64_t lo, int64_t hi) {
+        for (int64_t r = lo; r < hi; ++r)
+            if (!(weight[r] >= 0.0 && weight[r] <= (double)FLT_MAX)) { bad[(size_t)t] = r; break; }      // (a NaN fails both)
+    });
+    for (int64_t r : bad)
+        if (r >= 0) return r;
+    return -1;
 }
 
 template <typename FT>

@@ -1,6 +1,6 @@
 // fmhip_host.h — the library's PURE HOST ARITHMETIC: everything libfmhip.so computes on the host that needs no GPU and no
 // HIP header — row shards, feature relabelling, the host passes of the dataset build (validation, the dense hot block's choice and
-// split, the forward row order, the ALS row sort, the own bitmaps), a batch's range / fixup metadata, the band-affine plan of the
+// split, the forward row order, the ALS row sort, the own bitmaps, the example weights' check), a batch's range / fixup metadata, the band-affine plan of the
 // backward's ranges, the ALS sweep's level schedule, the data-parallel plan's cuts, interval edges, equal shares and update groups.  fmhip_dataset.hip /
 // fmhip_comm.hip call these; tests/host_arith_harness.cpp compiles fmhip_host.cpp with g++ -fsanitize=address,undefined and
 // drives them over random shapes (the sanitizers cannot run on the GPU pool, the index arithmetic can run
@@ -50,6 +50,9 @@ int64_t relabel_columns(int64_t nnz, const int32_t *col, int64_t n1, const int32
 // the first row where row_ptr decreases (then nothing else is looked at); the first negative entry of col (NULL: not swept); the largest id
 struct RowCheck { int64_t bad_row = -1, bad_entry = -1; int32_t dim = 0; };
 RowCheck validate_rows(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, int threads);
+// per-row example weights (include/fmhip_weights.h): every weight finite — as the fp32 it is stored as — and >= 0.  -> -1, or the
+// first row whose weight is not (NaN, +-inf, beyond FLT_MAX, negative; -0.0 passes: it is 0)
+int64_t validate_weights(int64_t n_rows, const double *weight, int threads);
 // dst[i] = (D)src[i]
 template <typename D, typename S>
 std::vector<D> converted(const S *src, int64_t n, int threads) {

@@ -123,8 +123,22 @@ struct TrainRule {
 // The training paths that refuse some rule, and the sentence each (path, rule) pair is refused with — nullptr: the path trains
 // under the rule.  The error code is FMHIP_ERR_UNSUPPORTED everywhere.  kTouchedDecay is the touched-rows exchange on a step WITH
 // weight decay (without, it takes every rule).  ALS is derived for the default loss and pairing only.
+// `weighted`: the dataset carries per-row example weights (include/fmhip_weights.h) — their residual is formed by a finish behind the
+// q-mode forward, which the two-pass forward (and so the pipelined exchange) does not have; ALS is derived for unweighted rows.
 enum class Path { kSharded, kTouchedDecay, kPipelined, kTwoPass, kAls };
-inline const char *refusal(Path p, const TrainRule &r) {
+inline const char *refusal(Path p, const TrainRule &r, bool weighted = false) {
+    if (weighted) switch (p) {
+        case Path::kPipelined:
+            return "the pipelined exchange runs the two-pass forward, which does not form weighted residuals (some rank's dataset "
+                   "carries example weights, fmhip_dataset_create_weighted): use the dense, sharded or touched exchange";
+        case Path::kTwoPass:
+            return "the two-pass forward does not form weighted residuals (the dataset carries example weights, "
+                   "fmhip_dataset_create_weighted): use fmhip_step_forward, and the dense, sharded or touched exchange";
+        case Path::kAls:
+            return "ALS is derived for the squared loss of unweighted rows: the dataset carries example weights "
+                   "(fmhip_dataset_create_weighted)";
+        default: break;
+    }
     switch (p) {
         case Path::kSharded:
             return !r.adagrad() ? nullptr
@@ -188,6 +202,11 @@ struct fmhip_dataset {
     DevBuf<int64_t> row_ptr;
     DevBuf<int32_t> col;
     DevBuf<float> val, y;
+    // per-row example weights (include/fmhip_weights.h; the rule: fm_weights.h): fp32 like y, finite and >= 0; weight_sum: their
+    // fp64 sum in row order, of the values as stored.  Not weighted: no array, and every path is the one it always was
+    DevBuf<float> c;
+    bool weighted = false;
+    double weight_sum = 0.0;
     DevBuf<uint32_t> crow;
     DevBuf<float> cval;
     DevBuf<int32_t> row_order;   // per batch: its rows' local ids sorted by stored length, longest first (forward walk order)
@@ -276,7 +295,7 @@ struct fmhip_model {
     // scale itself accumulates no fp32 rounding from step to step.
     double sv = 1.0, sw = 1.0;
     fmhip::host::TrainRule rule;  // how the model trains (the three fmhip_model_set_* calls)
-    DevBuf<float> yhat;           // paired training forward: [max_rows] predictions between its two launches
+    DevBuf<float> yhat;           // paired or weighted training forward: [max_rows] predictions between its two launches
     // AdaGrad: per-coordinate accumulators shaped like the parameters — NV [n1p][Kp] like V (packed rows: slot pack_k holds
     // w_i's), Nw [n1p] (unpacked rows only), N0 [1] — one more copy of the model (8.6 GB at 2^25 x 64); the tables stay at
     // scale 1 (sv = sw = 1) while it is set

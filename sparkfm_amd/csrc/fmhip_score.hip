@@ -11,6 +11,8 @@
 #include "fm_rank.h"
 #include "fm_pairing.h"
 #include "fm_auc.h"
+#include "fm_weights.h"
+#include "../../include/fmhip_weights.h"
 
 #include <algorithm>
 #include <cmath>
@@ -237,6 +239,47 @@ int fmhip_pair_logloss(fmhip_model_t m, fmhip_dataset_t d, double *logloss, doub
         stats->sum_e = 0.0;        // e_2j = -e_2j+1
         stats->nnz = d->nnz;
     }
+    return FMHIP_OK;
+}
+
+// Weighted scores over a weighted dataset (include/fmhip_weights.h): per batch the residual-mode forward of fmhip_rmse — its own
+// partials give the row count and the rows with a non-finite prediction — then k_weighted_score's partials over the predictions it
+// left, summed by the block reduction of fmhip_logloss into an accumulator of the call's own.
+int fmhip_weighted_scores(fmhip_model_t m, fmhip_dataset_t d, fmhip_weighted_result *out) {
+    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    if (out->struct_size != (int32_t)sizeof(fmhip_weighted_result))
+        return fail(FMHIP_ERR_INVALID, "out->struct_size is %d, not sizeof(fmhip_weighted_result) = %d", (int)out->struct_size,
+                    (int)sizeof(fmhip_weighted_result));
+    ReadLock lock(m);
+    TRY(check_pair(m, d));
+    if (!d->weighted)
+        return fail(FMHIP_ERR_INVALID, "the dataset carries no example weights (fmhip_dataset_create_weighted / fmhip_rows_create_weighted): "
+                                       "its unweighted scores are fmhip_rmse and fmhip_logloss");
+    DevBuf<double> wsum, wacc;       // (before the pass: freed after it has drained its stream)
+    ScorePass pass(m);
+    TRY(wsum.alloc((size_t)weighted_score_blocks(d->max_rows) * 4));
+    TRY(wacc.alloc(5));
+    TRY(pass.begin({d->max_rows, d->max_rows, -1, true}));
+    ScoreCtx &cx = pass.cx();
+    HIP_TRY(hipMemsetAsync(wacc.p, 0, 5 * sizeof(double), cx.s));
+    for (const BatchMeta &bm : d->batches) {
+        TRY(pass.forward(d, bm, kFwdResidual, ScoreOut{nullptr, cx.e.p, cx.yhat.p}, kLossSquared));
+        int parts = 0;
+        HIP_TRY(launch_weighted_score(cx.yhat.p, d->y.p + bm.row0, d->c.p + bm.row0, (int32_t)bm.rows, wsum.p, cx.s, &parts));
+        HIP_TRY(launch_reduce_blocks(wsum.p, parts, (int32_t)bm.rows, nullptr, wacc.p, cx.s, true));
+    }
+    double h[5], hw[5];       // hw: {sum c, sum c e^2, rows, sum c |e|, sum c l}
+    HIP_TRY(hipMemcpyAsync(hw, wacc.p, sizeof hw, hipMemcpyDeviceToHost, cx.s));
+    fmhip_stats st;
+    TRY(pass.read(&st, h));    // (synchronises the stream)
+    const double nan = std::nan("");
+    out->reserved = 0;
+    out->sum_w = hw[0];
+    out->rmse = hw[0] > 0.0 ? std::sqrt(hw[1] / hw[0]) : nan;
+    out->mae = hw[0] > 0.0 ? hw[3] / hw[0] : nan;
+    out->logloss = hw[0] > 0.0 ? hw[4] / hw[0] : nan;
+    out->rows = st.rows;
+    out->nonfinite = st.nonfinite;
     return FMHIP_OK;
 }
 

@@ -6,6 +6,7 @@
 // model's stream; the arithmetic lives in fm_forward.hip / fm_backward.hip / fm_apply.hip.
 #include "fmhip_internal.h"
 #include "fm_pairing.h"
+#include "fm_weights.h"
 
 #include <algorithm>
 #include <atomic>
@@ -100,7 +101,7 @@ int check_batch(fmhip_dataset_t d, int64_t batch) {
 int ensure_workspace(fmhip_model_t m, fmhip_dataset_t d) {
     TRY(m->P.ensure((size_t)std::max<int64_t>(d->max_rows, 1) * m->Kp));
     TRY(m->e.ensure((size_t)std::max<int64_t>(d->max_rows, 1)));
-    if (m->rule.paired()) TRY(m->yhat.ensure((size_t)std::max<int64_t>(d->max_rows, 2)));
+    if (m->rule.paired() || d->weighted) TRY(m->yhat.ensure((size_t)std::max<int64_t>(d->max_rows, 2)));
     TRY(m->part.ensure((size_t)std::max<int32_t>(d->max_ranges, 1) * 2 * (m->Kp + kPartPad)));
     TRY(m->pieces.ensure((size_t)std::max<int32_t>(d->max_pieces, 1) * (m->Kp + kPartPad)));
     TRY(m->bsum.ensure((size_t)kMaxFwdBlocks * 4));
@@ -247,25 +248,42 @@ int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
         HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
         m->grad_dirty = false;
     }
-    if (m->rule.paired()) {
+    if (m->rule.paired() || d->weighted) {
         // two launches: the q-mode forward — every existing kernel choice (hot pages, packed rows, row order, address mode) as it
         // is, P = sv*q and the predictions beside it — then the pairs' finish (fm_pairing.hip): P rows times +-g, e, the statistics
         // partials (its own block count: the backward's finish sums m->fwd_parts of them)
         // (check_train has refused datasets whose batches would cut a pair)
+        // A weighted dataset (fm_weights.h) trains the same way: its pairs through the same finish with the weights beside the
+        // labels, its single rows through a finish of their own (fm_weights.hip)
         ProfScope ps(m, FMHIP_K_FORWARD, bm.nnz_total, bm.rows);
         // (the q-mode has one instance, the squared loss's; its residual goes nowhere)
         const FwdArgs a = fwd_args_out(m, d, bm, m->P.p, nullptr, nullptr, m->yhat.p, kLossSquared);
         HIP_TRY(launch_forward(m->Kp, kFwdQ, a, m->stream, nullptr));
-        PairArgs pa{};
-        pa.P = m->P.p;
-        pa.yhat = m->yhat.p;
-        pa.y = d->y.p + bm.row0;
-        pa.e = m->e.p;
-        pa.bsum = m->bsum.p;
-        pa.n_pairs = (int32_t)(bm.rows / 2);
-        pa.pack_k = m->pack_k();
-        pa.loss = m->rule.loss;
-        HIP_TRY(launch_pair_finish(m->Kp, pa, m->stream, &m->fwd_parts));
+        if (m->rule.paired()) {
+            PairArgs pa{};
+            pa.P = m->P.p;
+            pa.yhat = m->yhat.p;
+            pa.y = d->y.p + bm.row0;
+            pa.e = m->e.p;
+            pa.bsum = m->bsum.p;
+            pa.n_pairs = (int32_t)(bm.rows / 2);
+            pa.pack_k = m->pack_k();
+            pa.loss = m->rule.loss;
+            pa.c = d->weighted ? d->c.p + bm.row0 : nullptr;
+            HIP_TRY(launch_pair_finish(m->Kp, pa, m->stream, &m->fwd_parts));
+        } else {
+            WeightArgs wa{};
+            wa.P = m->P.p;
+            wa.yhat = m->yhat.p;
+            wa.y = d->y.p + bm.row0;
+            wa.c = d->c.p + bm.row0;
+            wa.e = m->e.p;
+            wa.bsum = m->bsum.p;
+            wa.n_rows = (int32_t)bm.rows;
+            wa.pack_k = m->pack_k();
+            wa.loss = m->rule.loss;
+            HIP_TRY(launch_weight_finish(m->Kp, wa, m->stream, &m->fwd_parts));
+        }
     } else {
         ProfScope ps(m, FMHIP_K_FORWARD, bm.nnz_total, bm.rows);
         HIP_TRY(launch_forward(m->Kp, kFwdTrain, fwd_args(m, d, bm), m->stream, &m->fwd_parts));
@@ -284,7 +302,7 @@ int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
 // step_forward.  A then B = the forward, up to the order of the fp32 sums (A's terms first).
 int step_forward_pass(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int pass) {
     const BatchMeta &bm = d->batches[(size_t)b];
-    if (const char *why = refusal(Path::kTwoPass, m->rule)) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
+    if (const char *why = refusal(Path::kTwoPass, m->rule, d->weighted)) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
     if (d->split_cut < 0) return fail(FMHIP_ERR_INVALID, "the dataset's rows are not partitioned (fmhip_dataset_partition_rows)");
     if (m->Kp > 64) return fail(FMHIP_ERR_UNSUPPORTED, "the two-pass forward serves models of up to 64 padded factors (this one: %d)", m->Kp);
     TRY(ensure_workspace(m, d));

@@ -46,4 +46,6 @@ def _take_rows(ds, rows, name, kw):
     np.cumsum(lens, out=ptr[1:])
     # entry indices of the kept rows, row by row: start of the row + position inside it
     idx = np.repeat(ds.row_ptr[rows], lens) + (np.arange(int(ptr[-1]), dtype=np.int64) - np.repeat(ptr[:-1], lens))
+    if ds.weights is not None:      # a weighted dataset's splits carry the weights of the rows drawn
+        kw = dict(kw, weights=ds.weights[rows])
     return DataSet(ptr, ds.col[idx], ds.val[idx], ds.y[rows], name=name, **kw)

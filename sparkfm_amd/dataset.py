@@ -47,11 +47,14 @@ class DataSet(Features):
     """S/DataSet.scala:42-62.  ``rows`` of the reference = (label, SparseVector) pairs."""
 
     def __init__(self, row_ptr, col, val, y, name="dataset", batch_rows=0, device=0, scoring=False, hot_block=None,
-                 row_block_rows=None):
+                 row_block_rows=None, weights=None):
         super().__init__(row_ptr, col, val)
         self.y = np.ascontiguousarray(y, self.val.dtype)
         if len(self.y) != self.size:
             raise ValueError("y must have one label per row")
+        # per-row example weights c_r >= 0 (include/fmhip_weights.h): every training path then forms e_r <- c_r * e_r; None = an
+        # unweighted dataset, exactly as before.  Their values are checked by the library when the rows move to the device
+        self.weights = _ffi.row_weights(weights, self.size)
         self.name = name
         self.batch_rows = int(batch_rows)
         self.device = int(device)
@@ -70,6 +73,7 @@ class DataSet(Features):
 
     @classmethod
     def from_rows(cls, rows, name="dataset", **kw):
+        """rows = iterable of (label, (indices, values)); ``weights=``: one example weight per row."""
         ys, cols, vals, ptr = [], [], [], [0]
         for label, (idx, v) in rows:
             idx = np.asarray(idx, np.int32)
@@ -85,11 +89,12 @@ class DataSet(Features):
         return cls(np.asarray(ptr, np.int64), col, val, np.asarray(ys, np.float64), name=name, **kw)
 
     @classmethod
-    def from_pairs(cls, preferred, other, name="pairs", **kw):
+    def from_pairs(cls, preferred, other, name="pairs", weights=None, **kw):
         """Preference pairs for pairwise ranking (``HipSGD(pairs=True)``, ``FMModel.computePairLogLoss``): pair j is row 2j =
         ``preferred[j]`` with label 1 and row 2j+1 = ``other[j]`` with label 0.  Both row sets take the forms ``from_rows``
         takes — (label, (indices, values)) items, whose labels are ignored — or bare (indices, values) items.  Pairs must not
-        straddle mini-batches: an odd ``batch_rows`` is raised to the next even number."""
+        straddle mini-batches: an odd ``batch_rows`` is raised to the next even number.  ``weights``: one example weight per PAIR
+        (LambdaRank-style |delta NDCG|, confidence on implicit feedback), written to both of its rows — training reads row 2j's."""
         def bare(rows):
             return [it[1] if np.ndim(it[0]) == 0 else it for it in rows]
         pref, oth = bare(preferred), bare(other)
@@ -101,10 +106,14 @@ class DataSet(Features):
             rows.append((0.0, o))
         if "batch_rows" in kw:
             kw["batch_rows"] = int(kw["batch_rows"]) + (int(kw["batch_rows"]) & 1 if int(kw["batch_rows"]) > 0 else 0)
-        return cls.from_rows(rows, name=name, **kw)
+        if weights is not None:
+            weights = np.repeat(_ffi.row_weights(weights, len(pref)), 2)
+        return cls.from_rows(rows, name=name, weights=weights, **kw)
 
     @classmethod
     def from_arrays(cls, d, **kw):
+        if "weights" not in kw and d.get("weights") is not None:
+            kw = dict(kw, weights=d["weights"])
         return cls(d["row_ptr"], d["col"], d["val"], d["y"], **kw)
 
     # -- reference surface -----------------------------------------------------------
@@ -128,7 +137,18 @@ class DataSet(Features):
             L = _ffi.load()
             h = C.c_void_p()
             f32 = self.val.dtype == np.float32
-            if self.scoring:
+            if self.weights is not None:
+                # the weighted constructors take fp64 arrays (fmhip_weights.h); opts: as the unweighted branches below
+                val64, y64 = self.val.astype(np.float64, copy=False), self.y.astype(np.float64, copy=False)
+                args = (self.device, self.size, _ffi.ptr(self.row_ptr), _ffi.ptr(self.col), _ffi.ptr(val64), _ffi.ptr(y64), _ffi.ptr(self.weights))
+                if self.scoring:
+                    _ffi.check(L.fmhip_rows_create_weighted(*args, C.byref(h)))
+                else:
+                    hb = -1 if self.hot_block is None else (4 if self.hot_block is True else int(self.hot_block))
+                    opts = _ffi.DatasetOpts(C.sizeof(_ffi.DatasetOpts), hb,
+                                            self.batch_rows, -1 if self.row_block_rows is None else int(self.row_block_rows))
+                    _ffi.check(L.fmhip_dataset_create_weighted(*args, C.byref(opts), C.byref(h)))
+            elif self.scoring:
                 fn = L.fmhip_rows_create_f32 if f32 else L.fmhip_rows_create
                 _ffi.check(fn(self.device, self.size, _ffi.ptr(self.row_ptr), _ffi.ptr(self.col), _ffi.ptr(self.val),
                               _ffi.ptr(self.y), C.byref(h)))
@@ -168,6 +188,13 @@ class DataSet(Features):
         v = [C.c_int64() for _ in range(5)]
         _ffi.check(_ffi.load().fmhip_dataset_info(self.handle, *[C.byref(x) for x in v]))
         return dict(zip(("n_rows", "nnz", "dimension", "batch_rows", "n_batches"), (int(x.value) for x in v)))
+
+    def deviceWeights(self):
+        """The weights as the device holds them (fmhip_dataset_weights): dict of weighted (bool), sum, weights (float64 per row;
+        ones for an unweighted dataset)."""
+        has, s, out = C.c_int(), C.c_double(), np.empty(self.size)
+        _ffi.check(_ffi.load().fmhip_dataset_weights(self.handle, C.byref(has), C.byref(s), _ffi.ptr(out)))
+        return dict(weighted=bool(has.value), sum=s.value, weights=out)
 
     @property
     def n_batches(self):

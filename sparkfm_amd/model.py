@@ -225,6 +225,23 @@ class FMModel(Model):
         _ffi.check(_ffi.load().fmhip_logloss(self.handle, dataset.handle, C.byref(r), None))
         return r.value
 
+    def weightedScores(self, dataset):
+        """The weighted scores of the predictions over a weighted dataset (``DataSet(..., weights=)``; fmhip_weighted_scores): a
+        dict of sum_w, rmse = sqrt(sum c (yhat - y)^2 / sum c), mae, logloss (the weighted mean of computeLogLoss's row terms), rows,
+        nonfinite.  nan ratios when the weights sum to 0; an unweighted dataset is refused."""
+        res = _ffi.WeightedResult()
+        _ffi.check(_ffi.load().fmhip_weighted_scores(self.handle, dataset.handle, C.byref(res)))
+        return res.as_dict()
+
+    def computeWeightedRMSE(self, dataset):
+        """sqrt(sum c (predict - y)^2 / sum c) over a weighted dataset; computeRMSE ignores the weights."""
+        return self.weightedScores(dataset)["rmse"]
+
+    def computeWeightedLogLoss(self, dataset):
+        """Weighted mean log-loss over a weighted dataset — on a test set with down-sampled negatives weighted back up, the
+        log-loss of the traffic; computeLogLoss ignores the weights."""
+        return self.weightedScores(dataset)["logloss"]
+
     def _pair_score(self, dataset):
         r, c = C.c_double(), C.c_double()
         _ffi.check(_ffi.load().fmhip_pair_logloss(self.handle, dataset.handle, C.byref(r), C.byref(c), None))
