@@ -5,6 +5,7 @@
 // argument meaning, same call order and error behaviour as the reference —
 //
 //     sparkfm::DataSet      S/DataSet.scala:42-62            rows of (label, SparseVector), cache / unpersist, size, dimension
+//     sparkfm::Relation, sparkfm::RelationalData   S/fm/bs/* (a stub in the reference)   block-structure FM: blocks + mappings
 //     sparkfm::FMModel      S/fm/FMModel.scala:9-63          num_attribute, num_factor, public w0 / w / v, reg0 / regw / regv, predict
 //                           S/Model.scala:13-19              computeRMSE
 //     sparkfm::FMLearn      S/fm/FMLearn.scala:10-12         the plug-in point: learn(fm, dataset): FMModel
@@ -12,7 +13,7 @@
 //     sparkfm::HipALS       S/fm/lib/ALS.scala:15-75,202-208 the reference's own learner in fp64 on the GPU
 //     sparkfm::FM           S/fm/FM.scala:25-33, S/fm/impl/FactorizationMachines.scala:30-51   the fit loop
 //
-// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC), include/fmhip_ranking.h (ranking evaluation) and include/fmhip_weights.h (per-row example weights) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
+// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC), include/fmhip_ranking.h (ranking evaluation), include/fmhip_weights.h (per-row example weights) and include/fmhip_relational.h (relational data) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
 // here a non-zero status of the C ABI becomes sparkfm::Error carrying fmhip_last_error().  Parameters live on the host as in
 // the reference (public, mutable: `fm.w0`, `fm.w`, `fm.v` with v[f + i*k] = breeze's column-major DenseMatrix(k, n+1)); every
 // call that needs them on the device uploads them first, as jvm/HipSGD.scala does (the fit loop calls `learn` once per
@@ -20,6 +21,7 @@
 #ifndef SPARKFM_HPP
 #define SPARKFM_HPP
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <random>
@@ -34,6 +36,7 @@
 #include "fmhip_metrics.h"
 #include "fmhip_ranking.h"
 #include "fmhip_weights.h"
+#include "fmhip_relational.h"
 
 namespace sparkfm {
 
@@ -109,6 +112,8 @@ class DataSet {
     }
     const std::vector<double> &labels() const { return y_; }
     const std::vector<double> &weights() const { return weights_; }       // empty: unweighted
+    int64_t batch_rows() const { return batch_rows_; }
+    int64_t nnz() const { return (int64_t)col_.size(); }
     fmhip_dataset_t handle() { return cache().h_; }
     int device() const { return device_; }
 
@@ -122,6 +127,82 @@ class DataSet {
     int64_t batch_rows_;
     int device_;
     fmhip_dataset_t h_ = nullptr;
+};
+
+// Relational data (include/fmhip_relational.h; the reference's S/fm/bs/* is a stub): a Relation is a BLOCK of feature rows — a
+// one-batch DataSet with labels 0 — and a MAPPING, data row r using block row mapping[r]; a RelationalData is N labels, one or more
+// relations and an optional plain part (a DataSet of the same N rows, batched by the same batch_rows).  It stands for the flat
+// DataSet whose row r holds relation 0's entries of block row mapping_0[r], then relation 1's, ..., then the plain part's —
+// without building it.  Feature ids are global and the parts' feature sets must be disjoint (checked by the library).  Relations
+// and the plain part are BORROWED: they must outlive the RelationalData.
+class Relation {
+  public:
+    Relation(const std::vector<SparseVector> &rows, std::vector<int32_t> mapping, int device = 0)
+        : block_(labelled(rows), 0, device), mapping_(std::move(mapping)) {}
+    DataSet &block() { return block_; }
+    const std::vector<int32_t> &mapping() const { return mapping_; }
+
+  private:
+    static std::vector<std::pair<double, SparseVector>> labelled(const std::vector<SparseVector> &rows) {
+        std::vector<std::pair<double, SparseVector>> out;
+        for (const auto &r : rows) out.emplace_back(0.0, r);
+        return out;
+    }
+    DataSet block_;
+    std::vector<int32_t> mapping_;
+};
+
+class RelationalData {
+  public:
+    RelationalData(std::vector<double> y, std::vector<Relation *> relations, DataSet *plain = nullptr, int64_t batch_rows = 0, int device = 0)
+        : y_(std::move(y)), relations_(std::move(relations)), plain_(plain), batch_rows_(batch_rows), device_(device) {
+        if (relations_.empty()) throw Error(FMHIP_ERR_INVALID, "a RelationalData needs at least one Relation");
+        for (Relation *r : relations_)
+            if (!r || r->mapping().size() != y_.size()) throw Error(FMHIP_ERR_INVALID, "every mapping must hold one block row per data row");
+    }
+    RelationalData(const RelationalData &) = delete;
+    RelationalData &operator=(const RelationalData &) = delete;
+    ~RelationalData() { (void)fmhip_relational_destroy(h_); }
+
+    RelationalData &cache() {
+        if (h_) return *this;
+        std::vector<fmhip_dataset_t> blocks;
+        std::vector<const int32_t *> maps;
+        for (Relation *r : relations_) {
+            blocks.push_back(r->block().handle());
+            maps.push_back(r->mapping().data());
+        }
+        check(fmhip_relational_create(device_, (int64_t)y_.size(), y_.data(), (int32_t)blocks.size(), blocks.data(), maps.data(),
+                                      plain_ ? plain_->handle() : nullptr, batch_rows_, &h_));
+        return *this;
+    }
+    RelationalData &unpersist() {       // the relational handle only: the blocks stay cached with their Relation
+        check(fmhip_relational_destroy(h_));
+        h_ = nullptr;
+        return *this;
+    }
+    int64_t size() const { return (int64_t)y_.size(); }
+    int64_t dimension() {
+        int64_t d = plain_ ? plain_->dimension() : 0;
+        for (Relation *r : relations_) d = std::max<int64_t>(d, r->block().dimension());
+        return d;
+    }
+    int64_t n_batches() {
+        int64_t nb = 0;
+        check(fmhip_relational_info(cache().h_, nullptr, nullptr, nullptr, &nb, nullptr));
+        return nb;
+    }
+    const std::vector<double> &labels() const { return y_; }
+    fmhip_relational_t handle() { return cache().h_; }
+    int device() const { return device_; }
+
+  private:
+    std::vector<double> y_;
+    std::vector<Relation *> relations_;
+    DataSet *plain_;
+    int64_t batch_rows_;
+    int device_;
+    fmhip_relational_t h_ = nullptr;
 };
 
 // S/fm/FMModel.scala:9-63 — `new FMModel(num_attribute, num_factor)`: w0 = 0, w = 0, v ~ N(mean, stdev) (:17-22; the reference's
@@ -164,6 +245,22 @@ class FMModel {
         double rmse = 0.0;
         check(fmhip_rmse(upload(), dataset.handle(), &rmse, nullptr));
         return rmse;
+    }
+    // ... and of relational data (fmhip_relational_predict / _rmse / _logloss: every block's forward once per call)
+    std::vector<double> predict(RelationalData &dataset) {
+        std::vector<double> yhat((size_t)dataset.size());
+        check(fmhip_relational_predict(upload(), dataset.handle(), yhat.data()));
+        return yhat;
+    }
+    double computeRMSE(RelationalData &dataset) {
+        double rmse = 0.0;
+        check(fmhip_relational_rmse(upload(), dataset.handle(), &rmse, nullptr));
+        return rmse;
+    }
+    double computeLogLoss(RelationalData &dataset) {
+        double logloss = 0.0;
+        check(fmhip_relational_logloss(upload(), dataset.handle(), &logloss, nullptr));
+        return logloss;
     }
     double computeLogLoss(DataSet &dataset) {    // mean log-loss of sigmoid(predict) against t = [y > 0], whatever the training loss
         double logloss = 0.0;
@@ -305,6 +402,8 @@ class FMLearn {
   public:
     virtual ~FMLearn() = default;
     virtual FMModel &learn(FMModel &fm, DataSet &dataset) = 0;
+    // relational data: a learner that does not train on it says so
+    virtual FMModel &learn(FMModel &, RelationalData &) { throw Error(FMHIP_ERR_UNSUPPORTED, "this learner does not train on relational data"); }
 };
 
 // One learn = one epoch of mini-batch SGD over the dataset's batches (ascending order) — fmhip_sgd_epoch.
@@ -338,6 +437,15 @@ class HipSGD : public FMLearn {
         fm.download();
         return fm;
     }
+    // one epoch of relational steps (fmhip_relational_sgd_epoch): every block walked once per step; not with pairs
+    FMModel &learn(FMModel &fm, RelationalData &dataset) override {
+        check(fmhip_model_set_loss(fm.upload(), loss));
+        check(fmhip_model_set_pairing(fm.upload(), pairs ? FMHIP_PAIRING_ADJACENT : FMHIP_PAIRING_NONE));
+        check(fmhip_model_set_optimizer(fm.upload(), optimizer, adagrad_eps, adagrad_init));
+        check(fmhip_relational_sgd_epoch(fm.upload(), dataset.handle(), eta, reg0, regw, regv, nullptr, &last_stats));
+        fm.download();
+        return fm;
+    }
 };
 
 // The reference's own learner: one learn = one ALS.learn pass (S/fm/lib/ALS.scala:15-75) in fp64 on the GPU, with the MODEL's
@@ -345,6 +453,7 @@ class HipSGD : public FMLearn {
 class HipALS : public FMLearn {
   public:
     static HipALS run() { return HipALS(); }
+    using FMLearn::learn;
     FMModel &learn(FMModel &fm, DataSet &dataset) override {
         check(fmhip_als_epoch(fm.upload(), dataset.handle(), fm.reg0, fm.regw, fm.regv));
         fm.download();
@@ -359,10 +468,35 @@ class FM {
   public:
     std::vector<double> rmse_history;
     FM(DataSet &dataset, int32_t numFactor, int maxIteration = 100, uint64_t seed = 0) : dataset_(dataset), numFactor_(numFactor), maxIteration_(maxIteration), seed_(seed) {}
+    // S/fm/impl/FactorizationMachines.scala:24-28: appends and returns *this.  With relations learnWith fits
+    // RelationalData(labels, relations, plain = the dataset if it has nonzeros), batched as the dataset
+    FM &withRelation(Relation &relation) {
+        relations_.push_back(&relation);
+        return *this;
+    }
+    FM &withRelation(const std::vector<Relation *> &relations) {
+        relations_.insert(relations_.end(), relations.begin(), relations.end());
+        return *this;
+    }
     // init (optional): called on the fresh model before the first iteration — parity runs inject w0 / w / v here (quirk Q2)
+    // With relations the fit ends as the flat one does (:48): the relational handle and the dataset (the plain part) leave the
+    // device; the BLOCKS stay cached with their Relation, which other fits and held-out data may share (relation.block().unpersist())
     template <class Init>
     FMModel learnWith(FMLearn &fml, Init init) {
-        DataSet &ds = dataset_.cache();                                          // :36
+        if (relations_.empty()) return fit(dataset_, fml, init);
+        RelationalData rd(dataset_.labels(), relations_, dataset_.nnz() ? &dataset_ : nullptr, dataset_.batch_rows(), dataset_.device());
+        FMModel fm = fit(rd, fml, init);       // (its unpersist freed the handle that borrowed the dataset)
+        dataset_.unpersist();
+        return fm;
+    }
+    FMModel learnWith(FMLearn &fml) {
+        return learnWith(fml, [](FMModel &) {});
+    }
+
+  private:
+    template <class Data, class Init>
+    FMModel fit(Data &data, FMLearn &fml, Init init) {
+        Data &ds = data.cache();                                                 // :36
         FMModel fm(ds.dimension(), numFactor_, 0.0, 0.01, seed_, ds.device());   // :39
         init(fm);
         for (int i = 1; i <= maxIteration_; ++i) {                               // :42
@@ -372,12 +506,8 @@ class FM {
         ds.unpersist();                                                          // :48
         return fm;
     }
-    FMModel learnWith(FMLearn &fml) {
-        return learnWith(fml, [](FMModel &) {});
-    }
-
-  private:
     DataSet &dataset_;
+    std::vector<Relation *> relations_;
     int32_t numFactor_;
     int maxIteration_;
     uint64_t seed_;

@@ -5,6 +5,7 @@ The arithmetic runs in hand-written HIP kernels (csrc/) behind a plain C ABI
 (FM, FMModel, FMLearn, DataSet) over ctypes.  There is no CPU fallback.
 """
 from .dataset import DataSet, Features  # noqa: F401
+from .relational import Relation, RelationalData  # noqa: F401
 from .model import FMModel, Model  # noqa: F401
 from .learn import FMLearn, HipALS, HipSGD  # noqa: F401
 from .fm import FM, FactorizationMachines, Task  # noqa: F401
@@ -13,4 +14,4 @@ from .feature_order import FeatureOrder  # noqa: F401
 from . import fmutils as FMUtils  # noqa: F401
 
 __all__ = ["DataSet", "Features", "FMModel", "Model", "FMLearn", "HipSGD", "HipALS", "FM", "FactorizationMachines", "Task",
-           "DataCollection", "FMUtils", "FeatureOrder"]
+           "DataCollection", "FMUtils", "FeatureOrder", "Relation", "RelationalData"]

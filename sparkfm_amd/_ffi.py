@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -53,6 +53,11 @@ SYMBOLS_METRICS = ("fmhip_auc_scores", "fmhip_auc")
 SYMBOLS_RANKING = ("fmhip_rank", "fmhip_rank_metrics")
 # ... and include/fmhip_weights.h — per-row example weights: weighted datasets, weighted scores
 SYMBOLS_WEIGHTS = ("fmhip_dataset_create_weighted", "fmhip_rows_create_weighted", "fmhip_dataset_weights", "fmhip_weighted_scores")
+# ... and include/fmhip_relational.h — relational data: block-structure FM training and scoring
+SYMBOLS_RELATIONAL = ("fmhip_relational_create", "fmhip_relational_destroy", "fmhip_relational_info", "fmhip_relational_predict",
+                      "fmhip_relational_rmse", "fmhip_relational_logloss", "fmhip_relational_sgd_step", "fmhip_relational_sgd_epoch")
+RELATIONS_MAX = 8          # FMHIP_RELATIONS_MAX
+RELATIONAL_SUM_CUT = 256   # FMHIP_RELATIONAL_SUM_CUT: a block row referenced by more rows of a batch is summed in chunks of this many
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -398,7 +403,16 @@ def load():
     L.fmhip_rows_create_weighted.argtypes = [C.c_int, i64, vp, vp, vp, vp, vp, P(vp)]
     L.fmhip_dataset_weights.argtypes = [vp, P(C.c_int), P(dbl), vp]
     L.fmhip_weighted_scores.argtypes = [vp, vp, P(WeightedResult)]
-    for name in SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS:
+    L.fmhip_relational_create.argtypes = [C.c_int, i64, vp, i32, vp, vp, vp, i64, P(vp)]
+    L.fmhip_relational_destroy.argtypes = [vp]
+    L.fmhip_relational_info.argtypes = [vp, P(i64), P(i64), P(i64), P(i64), P(i32)]
+    L.fmhip_relational_predict.argtypes = [vp, vp, vp]
+    L.fmhip_relational_rmse.argtypes = [vp, vp, P(dbl), P(Stats)]
+    L.fmhip_relational_logloss.argtypes = [vp, vp, P(dbl), P(Stats)]
+    L.fmhip_relational_sgd_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, P(Stats)]
+    L.fmhip_relational_sgd_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, vp, P(Stats)]
+    for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
+                 + SYMBOLS_RELATIONAL):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

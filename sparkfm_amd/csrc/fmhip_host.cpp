@@ -664,5 +664,65 @@ int64_t rank_metrics(int64_t n_contexts, const int64_t *rel_ptr, const int32_t *
     return -1;
 }
 
+// ---- relational data (include/fmhip_relational.h) ---------------------------------------------------------------------
+
+int64_t relational_bad_mapping(int64_t n_rows, const int32_t *map, int64_t block_rows) {
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (map[r] < 0 || (int64_t)map[r] >= block_rows) return r;
+    return -1;
+}
+
+SharedFeature first_shared_feature(int n_parts, const int32_t *const *feat, const int64_t *n_feat, int64_t dimension) {
+    SharedFeature best;
+    std::vector<int32_t> owner((size_t)std::max<int64_t>(dimension, 0) + 1, -1);
+    for (int p = 0; p < n_parts; ++p)
+        for (int64_t i = 0; i < n_feat[p]; ++i) {
+            const int32_t f = feat[p][i];
+            if (f < 0 || (int64_t)f > dimension) continue;        // (an unused slot of a hot block's id list)
+            int32_t &o = owner[(size_t)f];
+            if (o < 0) o = p;
+            else if (o != p && (best.feature < 0 || f < best.feature || (f == best.feature && p < best.b))) best = SharedFeature{f, o, p};
+        }
+    return best;
+}
+
+void RelationInverse::append_batch(const int32_t *map, int64_t rows, int64_t block_rows, int32_t cut, std::vector<int32_t> &count) {
+    if (count.size() < (size_t)block_rows) count.assign((size_t)block_rows, 0);
+    Batch b;
+    b.row_off = (int64_t)trow.size();
+    b.t_off = (int64_t)tj.size();
+    b.tptr_off = (int64_t)tptr.size();
+    b.w_off = (int64_t)wt.size();
+    b.l_off = (int64_t)lt.size();
+    // counting sort of the batch's rows by block row: the counts, the touched block rows ascending, their offsets, the placement
+    for (int64_t r = 0; r < rows; ++r)
+        if (count[(size_t)map[r]]++ == 0) tj.push_back(map[r]);
+    std::sort(tj.begin() + b.t_off, tj.end());
+    b.n_touched = (int32_t)((int64_t)tj.size() - b.t_off);
+    int32_t at = 0;
+    for (int32_t t = 0; t < b.n_touched; ++t) {
+        int32_t &c = count[(size_t)tj[(size_t)(b.t_off + t)]];
+        const int32_t len = c;
+        tptr.push_back(at);
+        // the list's work: one item that writes the block row, or ceil(len / cut) chunks into partial rows + one second-pass item
+        if (len <= cut) {
+            wt.push_back(t); wbeg.push_back(at); wdst.push_back(tj[(size_t)(b.t_off + t)]);
+        } else {
+            lt.push_back(t); lfirst.push_back(b.n_part); lcount.push_back((len + cut - 1) / cut);
+            for (int32_t o = 0; o < len; o += cut) { wt.push_back(t); wbeg.push_back(at + o); wdst.push_back(-1 - b.n_part++); }
+        }
+        c = at;              // the count becomes the list's cursor
+        at += len;
+    }
+    tptr.push_back(at);
+    trow.resize((size_t)(b.row_off + rows));
+    for (int64_t r = 0; r < rows; ++r) trow[(size_t)(b.row_off + count[(size_t)map[r]]++)] = (int32_t)r;     // ascending inside a list
+    for (int32_t t = 0; t < b.n_touched; ++t) count[(size_t)tj[(size_t)(b.t_off + t)]] = 0;                 // the scratch is left zeroed
+    b.n_work = (int32_t)((int64_t)wt.size() - b.w_off);
+    b.n_long = (int32_t)((int64_t)lt.size() - b.l_off);
+    max_part = std::max(max_part, b.n_part);
+    batches.push_back(b);
+}
+
 }  // namespace host
 }  // namespace fmhip

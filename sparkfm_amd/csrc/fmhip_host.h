@@ -158,5 +158,30 @@ struct RankMetricSums {
 // -> -1, or the first context that holds a negative rank or two equal ranks (out is then unreliable)
 int64_t rank_metrics(int64_t n_contexts, const int64_t *rel_ptr, const int32_t *rank, int32_t k, RankMetricSums *out);
 
+// ---- relational data (fmhip_relational_create, include/fmhip_relational.h) ---------------------------------------------
+// -> -1, or the first row whose mapping entry lies outside [0, block_rows)
+int64_t relational_bad_mapping(int64_t n_rows, const int32_t *map, int64_t block_rows);
+// The parts' feature lists (any order, repeats inside a part allowed, ids outside [0, dimension] skipped) must be pairwise
+// disjoint.  -> feature = -1, or the LOWEST feature id two parts share with the two lowest parts (a < b) that hold it
+struct SharedFeature { int32_t feature = -1; int a = -1, b = -1; };
+SharedFeature first_shared_feature(int n_parts, const int32_t *const *feat, const int64_t *n_feat, int64_t dimension);
+// The inverse map of ONE relation, batch after batch (append_batch in batch order): per batch the block rows it touches,
+// ascending (tj), and for each the batch-local rows that point at it, ascending (trow [tptr[t], tptr[t+1])) — a counting sort.
+// Beside it the segmented sum's work list: a list of up to `cut` rows is ONE item whose sum is the block row's (wdst = the block
+// row); a longer one is cut into chunks of `cut` rows (wdst = -1 - its partial row) plus one second-pass entry (lt: the touched
+// index, lfirst / lcount: its partial rows).  Everything is O(rows + touched): nothing is sized by batches x block rows.
+// All offsets inside a batch's slices are relative to the slice (Batch: where the slices start).
+struct RelationInverse {
+    struct Batch {
+        int64_t row_off = 0, t_off = 0, tptr_off = 0, w_off = 0, l_off = 0;
+        int32_t n_touched = 0, n_work = 0, n_long = 0, n_part = 0;
+    };
+    std::vector<int32_t> trow, tj, tptr, wt, wbeg, wdst, lt, lfirst, lcount;
+    std::vector<Batch> batches;
+    int32_t max_part = 0;
+    // map: the batch's `rows` entries, all in [0, block_rows) (checked by the caller); count: scratch, zeroed or empty, left zeroed
+    void append_batch(const int32_t *map, int64_t rows, int64_t block_rows, int32_t cut, std::vector<int32_t> &count);
+};
+
 }  // namespace host
 }  // namespace fmhip

@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/fmhip_experimental.h"   // (includes fmhip.h: the library implements both surfaces)
 #include "../../include/fmhip_pairing.h"        // (enum fmhip_pairing: the model carries the switch)
+#include "../../include/fmhip_relational.h"     // (fmhip_relational_t: the handle's state is declared below)
 #include "fm_kernels.h"
 #include "fmhip_host.h"   // the pure host arithmetic (shards, relabelling, batch metadata, band plan, ALS levels, the dp plan's cuts and shares)
 
@@ -125,7 +126,8 @@ struct TrainRule {
 // weight decay (without, it takes every rule).  ALS is derived for the default loss and pairing only.
 // `weighted`: the dataset carries per-row example weights (include/fmhip_weights.h) — their residual is formed by a finish behind the
 // q-mode forward, which the two-pass forward (and so the pipelined exchange) does not have; ALS is derived for unweighted rows.
-enum class Path { kSharded, kTouchedDecay, kPipelined, kTwoPass, kAls };
+// kRelational: the relational step (include/fmhip_relational.h) — single rows, unweighted parts.
+enum class Path { kSharded, kTouchedDecay, kPipelined, kTwoPass, kAls, kRelational };
 inline const char *refusal(Path p, const TrainRule &r, bool weighted = false) {
     if (weighted) switch (p) {
         case Path::kPipelined:
@@ -137,6 +139,9 @@ inline const char *refusal(Path p, const TrainRule &r, bool weighted = false) {
         case Path::kAls:
             return "ALS is derived for the squared loss of unweighted rows: the dataset carries example weights "
                    "(fmhip_dataset_create_weighted)";
+        case Path::kRelational:
+            return "relational data does not take example weights yet (a block or the plain part was made by "
+                   "fmhip_dataset_create_weighted): one weight per data row would scale e_r before the segmented sum";
         default: break;
     }
     switch (p) {
@@ -162,6 +167,10 @@ inline const char *refusal(Path p, const TrainRule &r, bool weighted = false) {
             return !r.paired() ? nullptr
                                : "ALS is derived for the squared loss of single rows: this model trains on pairs of rows "
                                  "(fmhip_model_set_pairing)";
+        case Path::kRelational:
+            return !r.paired() ? nullptr
+                               : "the relational step forms single rows' residuals: this model trains on pairs of rows "
+                                 "(fmhip_model_set_pairing) — expand the data and train the pairs on the flat dataset";
     }
     return nullptr;
 }
@@ -259,6 +268,37 @@ struct fmhip_dataset {
     std::vector<int32_t> als_lev_ptr, h_als_lev_cols;
 };
 
+// A relational dataset (include/fmhip_relational.h): N labels, m relations (a borrowed block + a mapping + the inverse map of every
+// batch), an optional borrowed plain part.  The training workspace (per relation: the block's q rows and predictions, P_b / e_b, the
+// long lists' partial rows) lives here too: one training call per handle at a time; the scoring calls only read the handle.
+struct fmhip_relational {
+    template <typename T> using DevBuf = fmhip::host::DevBuf<T>;
+    struct Relation {
+        fmhip_dataset_t block = nullptr;
+        DevBuf<int32_t> map;                                            // [n_rows]
+        DevBuf<int32_t> trow, tj, tptr, wt, wbeg, wdst, lt, lfirst, lcount;      // fmhip::host::RelationInverse, on the device
+        std::vector<fmhip::host::RelationInverse::Batch> batches;      // where every batch's slices start
+        int32_t max_part = 0;
+        DevBuf<float> Q, yq, Pb, eb, part, part_e;                      // training workspace (allocated by the first step)
+    };
+    struct Batch { int64_t row0 = 0, rows = 0; };
+    int device = 0;
+    int64_t n_rows = 0, batch_rows = 0, dimension = 0, max_rows = 0;
+    int64_t block_nnz = 0;                                              // stored nonzeros of all blocks (what every step walks)
+    std::vector<std::unique_ptr<Relation>> rels;
+    fmhip_dataset_t plain = nullptr;
+    DevBuf<float> y;
+    std::vector<Batch> batches;
+    // A step is queued, not run, when its call returns, and the workspace above is the HANDLE's: `busy` is recorded behind every
+    // step on the stream it ran on, and a step on ANOTHER stream (another model) waits for it before it touches the workspace
+    hipEvent_t busy = nullptr;
+    hipStream_t busy_stream = nullptr;
+    bool busy_set = false;
+    ~fmhip_relational() {
+        if (busy) (void)hipEventDestroy(busy);
+    }
+};
+
 struct fmhip_model {
     template <typename T> using DevBuf = fmhip::host::DevBuf<T>;
     using ProfRec = fmhip::host::ProfRec;
@@ -349,6 +389,7 @@ struct ReadLock {
 int partition_rows_locked(fmhip_dataset_t d, int64_t cut_feature);      // fmhip_dataset_partition_rows with d->part_mu held by the caller
 // ---- fmhip_step.hip
 int ensure_workspace(fmhip_model_t m, fmhip_dataset_t d);
+int ensure_backward_workspace(fmhip_model_t m, fmhip_dataset_t d);     // ... the part a backward over `d` needs (partials, pieces, hot block)
 FwdArgs fwd_args(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm);
 // ... of a forward that is not the training forward: outputs of the caller's (nullptr: not written), the residual of `loss`
 FwdArgs fwd_args_out(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm, float *P, float *e, double *bsum, float *yhat, int loss);
@@ -378,8 +419,10 @@ struct FusedPlan {
 enum { kOwnLower = 1, kOwnUpper = 2 };
 // the training forward in two passes (pass 0 = A: features below the dataset's split cut; pass 1 = B: the others + the row's finish)
 int step_forward_pass(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int pass);
+// src (the relational step): the backward reads these P rows / residuals — a block's P_b / e_b — instead of the model's
+struct BwdSource { const float *P, *e; };
 int step_backward(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int64_t feat_lo, int64_t feat_hi, bool finish, double *acc,
-                  const FusedPlan *fused = nullptr, int own = kOwnLower);
+                  const FusedPlan *fused = nullptr, int own = kOwnLower, const BwdSource *src = nullptr);
 // forward + backward + fixup of one batch into the packed gradient (fused: straight into the parameters)
 int step_compute(fmhip_model_t m, fmhip_dataset_t d, int64_t b, double *acc, const FusedPlan *fused = nullptr);
 // can this step's update run inside the fixup launch / the column walk?  (fills *p; false: a launch of its own, step_apply)

@@ -12,6 +12,7 @@
 #include "fm_pairing.h"
 #include "fm_auc.h"
 #include "fm_weights.h"
+#include "fm_relational.h"
 #include "../../include/fmhip_weights.h"
 
 #include <algorithm>
@@ -720,6 +721,105 @@ int fmhip_rank_metrics(int64_t n_contexts, const int64_t *rel_ptr, const int32_t
     out->ndcg = s.ndcg;
     out->mrr = s.mrr;
     out->map = s.map;
+    return FMHIP_OK;
+}
+
+}  // extern "C"
+
+// ---- relational data (include/fmhip_relational.h) ----------------------------------------------------------------------------
+// Every block's q-mode pass ONCE (its q rows and predictions into buffers of the call's own), then per batch of data rows the plain
+// part's q-mode pass and k_rel_finish in residual mode, whose partials the block reduction of fmhip_logloss sums.
+namespace {
+
+struct RelScoreBufs {       // (declared before the pass: freed after it has drained its stream)
+    std::vector<std::unique_ptr<DevBuf<float>>> Q, yq;
+};
+
+int rel_score_pass(fmhip_model_t m, fmhip_relational_t R, double *yhat, fmhip_stats *st, double *logloss) {
+    if (!m || !R) return fail(FMHIP_ERR_INVALID, "model or relational dataset is NULL");
+    if (m->device != R->device) return fail(FMHIP_ERR_INVALID, "model on device %d, relational dataset on device %d", m->device, R->device);
+    if (R->dimension > m->n)
+        return fail(FMHIP_ERR_SHAPE, "relational dataset has feature index %lld but the model has num_attribute = %lld", (long long)R->dimension,
+                    (long long)m->n);
+    TRY(set_device(m->device));
+    RelScoreBufs bufs;
+    ScorePass pass(m);
+    TRY(pass.begin({R->max_rows, R->max_rows, R->plain ? R->max_rows : -1, true}));
+    ScoreCtx &cx = pass.cx();
+    RelFinishArgs fa{};
+    fa.m = (int32_t)R->rels.size();
+    for (int i = 0; i < fa.m; ++i) {
+        fmhip_dataset_t blk = R->rels[(size_t)i]->block;
+        bufs.Q.emplace_back(new DevBuf<float>());
+        bufs.yq.emplace_back(new DevBuf<float>());
+        TRY(bufs.Q.back()->alloc((size_t)blk->n_rows * m->Kp));
+        TRY(bufs.yq.back()->alloc((size_t)blk->n_rows));
+        const FwdArgs a = fwd_args_out(m, blk, blk->batches[0], bufs.Q.back()->p, nullptr, nullptr, bufs.yq.back()->p, kLossSquared);
+        HIP_TRY(launch_forward(m->Kp, kFwdQ, a, cx.s, nullptr));
+        fa.Q[i] = bufs.Q.back()->p;
+        fa.yq[i] = bufs.yq.back()->p;
+    }
+    fa.has_plain = R->plain ? 1 : 0;
+    fa.w0 = m->w0.p;
+    fa.P = R->plain ? cx.P.p : nullptr;
+    fa.yplain = cx.yhat.p;              // (read per row before the row's prediction is written over it)
+    fa.e = cx.e.p;
+    fa.yhat = cx.yhat.p;
+    fa.bsum = cx.bsum.p;
+    fa.pack_k = m->pack_k();
+    fa.loss = logloss ? kLossLogistic : kLossSquared;
+    std::vector<float> hbuf;
+    for (size_t b = 0; b < R->batches.size(); ++b) {
+        const fmhip_relational::Batch &B = R->batches[b];
+        if (R->plain) {
+            const FwdArgs a = fwd_args_out(m, R->plain, R->plain->batches[b], cx.P.p, nullptr, nullptr, cx.yhat.p, kLossSquared);
+            HIP_TRY(launch_forward(m->Kp, kFwdQ, a, cx.s, nullptr));
+        }
+        for (int i = 0; i < fa.m; ++i) fa.map[i] = R->rels[(size_t)i]->map.p + B.row0;
+        fa.y = R->y.p + B.row0;
+        fa.n_rows = (int32_t)B.rows;
+        int parts = 0;
+        HIP_TRY(launch_rel_finish(m->Kp, fa, true, cx.s, &parts));
+        HIP_TRY(launch_reduce_blocks(cx.bsum.p, parts, (int32_t)B.rows, nullptr, cx.acc.p, cx.s, logloss != nullptr));
+        if (yhat) TRY(pass.copy_back(cx.yhat.p, B.rows, 1, 1, hbuf, yhat + B.row0));
+    }
+    double h[5];
+    fmhip_stats s;
+    TRY(pass.read(&s, h));
+    s.nnz = R->block_nnz + (R->plain ? R->plain->nnz : 0);
+    if (st) *st = s;
+    if (logloss) *logloss = h[4];
+    return FMHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmhip_relational_predict(fmhip_model_t m, fmhip_relational_t r, double *yhat) {
+    ReadLock lock(m);
+    if (!yhat) return fail(FMHIP_ERR_INVALID, "yhat is NULL");
+    return rel_score_pass(m, r, yhat, nullptr, nullptr);
+}
+
+int fmhip_relational_rmse(fmhip_model_t m, fmhip_relational_t r, double *rmse, fmhip_stats *stats) {
+    ReadLock lock(m);
+    if (!rmse) return fail(FMHIP_ERR_INVALID, "rmse is NULL");
+    fmhip_stats st;
+    TRY(rel_score_pass(m, r, nullptr, &st, nullptr));
+    *rmse = st.rows > 0 ? std::sqrt(st.sse / (double)st.rows) : 0.0;
+    if (stats) *stats = st;
+    return FMHIP_OK;
+}
+
+int fmhip_relational_logloss(fmhip_model_t m, fmhip_relational_t r, double *logloss, fmhip_stats *stats) {
+    ReadLock lock(m);
+    if (!logloss) return fail(FMHIP_ERR_INVALID, "logloss is NULL");
+    fmhip_stats st;
+    double sum_l = 0.0;
+    TRY(rel_score_pass(m, r, nullptr, &st, &sum_l));
+    *logloss = st.rows > 0 ? sum_l / (double)st.rows : 0.0;
+    if (stats) *stats = st;
     return FMHIP_OK;
 }
 

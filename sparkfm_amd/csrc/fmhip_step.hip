@@ -102,9 +102,13 @@ int ensure_workspace(fmhip_model_t m, fmhip_dataset_t d) {
     TRY(m->P.ensure((size_t)std::max<int64_t>(d->max_rows, 1) * m->Kp));
     TRY(m->e.ensure((size_t)std::max<int64_t>(d->max_rows, 1)));
     if (m->rule.paired() || d->weighted) TRY(m->yhat.ensure((size_t)std::max<int64_t>(d->max_rows, 2)));
+    TRY(m->bsum.ensure((size_t)kMaxFwdBlocks * 4));
+    return ensure_backward_workspace(m, d);
+}
+
+int ensure_backward_workspace(fmhip_model_t m, fmhip_dataset_t d) {
     TRY(m->part.ensure((size_t)std::max<int32_t>(d->max_ranges, 1) * 2 * (m->Kp + kPartPad)));
     TRY(m->pieces.ensure((size_t)std::max<int32_t>(d->max_pieces, 1) * (m->Kp + kPartPad)));
-    TRY(m->bsum.ensure((size_t)kMaxFwdBlocks * 4));
     if (d->hot_T) TRY(m->hot_part.ensure((size_t)hot_blocks(m->Kp, d->max_rows) * d->hot_pages * kHotT * (m->Kp + kPartPad)));
     return FMHIP_OK;
 }
@@ -372,9 +376,10 @@ void hot_attach(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm, BwdArgs
 // pipelined data-parallel schedule (second-coldest interval first, then down to feature 0, the coldest last) says it per call.
 // What a range does never depends on which call walks it, so the gradient is the same bits in any order.
 int step_backward(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int64_t feat_lo, int64_t feat_hi, bool finish,
-                  double *acc, const FusedPlan *fused, int own) {
+                  double *acc, const FusedPlan *fused, int own, const BwdSource *src) {
     const BatchMeta &bm = d->batches[(size_t)b];
     BwdArgs ba = bwd_args(m, d, b);
+    if (src) { ba.P = src->P; ba.e = src->e; }
     if (fused) {
         if (fused->mode == 1) ba.upd = fused->upd;
         if (finish) { ba.red_w0 = m->w0.p; ba.red_eta = (float)fused->sgd.eta; ba.red_reg0 = (float)fused->sgd.reg0; }
@@ -386,6 +391,7 @@ int step_backward(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int64_t feat_lo
     if (d->rb_rows > 0 && !whole)      // refused before anything of the step's state (hot_pending) is consumed
         return fail(FMHIP_ERR_UNSUPPORTED, "feature-interval backward is not available on a row-blocked dataset");
     if (whole || finish || d->hot_max_id >= feat_lo) hot_attach(m, d, bm, ba);
+    if (src && ba.hot_blocks > 0) { ba.hot.P = src->P; ba.hot.e = src->e; }
     // band-affine placement (FMHIP_TUNE_XCD_PLACEMENT = 2): XCD x walks the ranges of its own row bands first (BwdArgs::xlist); the same
     // choice for every launch of a step — the partials of a cut column are written and read under one rule (no wave sums)
     const bool banded = m->tv(kTuneXcd) == 2 && bm.xoff[0] >= 0 && d->rb_rows == 0;

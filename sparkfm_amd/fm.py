@@ -2,6 +2,7 @@
 import logging
 
 from .model import FMModel
+from .relational import Relation, RelationalData
 
 log = logging.getLogger("sparkfm_amd")
 
@@ -27,16 +28,26 @@ class FactorizationMachines:
         self.timeout = timeout
         self.seed = seed
         self.rmse_history = []
+        self.relations = []
 
     def withRelation(self, relation):
-        # S/fm/bs/* is an unfinished stub in the reference (Relation.cache = null); out of scope.
-        raise NotImplementedError("relational (block-structure) FM is a non-functional stub in SparkFM")
+        """S/fm/impl/FactorizationMachines.scala:24-28: appends a Relation (or each of a list) and returns self.  The reference's
+        S/fm/bs/* is a stub; here the relations train as block-structure FM: `learnWith` fits
+        RelationalData(dataset.y, relations, plain = dataset if it has nonzeros), batched as `dataset`."""
+        for rel in ([relation] if isinstance(relation, Relation) else list(relation)):
+            if not isinstance(rel, Relation):
+                raise TypeError("withRelation takes a Relation or a list of them, not %s" % type(rel).__name__)
+            self.relations.append(rel)
+        return self
 
     def learnWith(self, fml, init=None):
         """S/fm/impl/FactorizationMachines.scala:30-51: cache; new FMModel(dimension, numFactor);
         maxIteration x { computeRMSE (logged); fm = fml.learn(fm, dataset) }; unpersist.
         `init` = (w0, w, v) injects parameters (the reference's own init is unseeded, quirk Q2)."""
-        ds = self.dataset.cache()                                     # :36
+        ds = self.dataset
+        if self.relations:
+            ds = RelationalData(ds.y, self.relations, plain=ds if ds.nnz else None, batch_rows=ds.batch_rows, name=ds.name, device=ds.device)
+        ds = ds.cache()                                               # :36
         fm = FMModel(ds.dimension, self.numFactor, seed=self.seed, device=ds.device)   # :39
         if init is not None:
             fm.w0, fm.w, fm.v = init
@@ -46,6 +57,10 @@ class FactorizationMachines:
             log.info("Iteration %d in progress... (%s RMSE = %.6f)", i, ds.name, rmse)
             fm = fml.learn(fm, ds)                                    # :45
         ds.unpersist()                                                # :48
+        if ds is not self.dataset and ds.plain is not None:
+            # the relational handle is gone: the plain part leaves the device as the flat fit's dataset does; the blocks stay cached
+            # with their Relation, which other fits and held-out data may share (relation.block.unpersist())
+            ds.plain.unpersist()
         return fm
 
 

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
+from .relational import RelationalData
 
 
 class FMLearn:
@@ -34,6 +35,7 @@ class HipSGD(FMLearn):
     ``DataSet.from_pairs``) this is BPR, -log sigmoid(yhat_preferred - yhat_other).  The dataset needs an even number of rows
     and an even batch_rows.
     `learn` and `step` set all three on the model before they train (the same AdaGrad settings again keep its accumulators).
+    Both also take a ``RelationalData`` (fmhip_relational_sgd_epoch / _step: every block walked once per step; not with pairs).
     """
 
     def __init__(self, eta=0.05, reg0=0.0, regw=0.0, regv=0.0, shuffle_seed=None, loss="squared", optimizer="sgd",
@@ -60,8 +62,12 @@ class HipSGD(FMLearn):
         order = self.batch_order(dataset.n_batches)
         st = _ffi.Stats()
         self.rule.set_on(fm.handle)
-        _ffi.check(L.fmhip_sgd_epoch(fm.handle, dataset.handle, self.eta, self.reg0, self.regw, self.regv,
-                                     _ffi.ptr(order), C.byref(st)))
+        if isinstance(dataset, RelationalData):
+            _ffi.check(L.fmhip_relational_sgd_epoch(fm.handle, dataset.rel_handle, self.eta, self.reg0, self.regw, self.regv,
+                                                    _ffi.ptr(order), C.byref(st)))
+        else:
+            _ffi.check(L.fmhip_sgd_epoch(fm.handle, dataset.handle, self.eta, self.reg0, self.regw, self.regv,
+                                         _ffi.ptr(order), C.byref(st)))
         fm._device_updated()
         self._epoch += 1
         self.last_stats = st.as_dict()
@@ -71,8 +77,10 @@ class HipSGD(FMLearn):
         """A single mini-batch step (fmhip_sgd_step)."""
         st = _ffi.Stats()
         self.rule.set_on(fm.handle)
-        _ffi.check(_ffi.load().fmhip_sgd_step(fm.handle, dataset.handle, batch, self.eta, self.reg0, self.regw,
-                                              self.regv, C.byref(st) if want_stats else None))
+        relational = isinstance(dataset, RelationalData)
+        fn = _ffi.load().fmhip_relational_sgd_step if relational else _ffi.load().fmhip_sgd_step
+        _ffi.check(fn(fm.handle, dataset.rel_handle if relational else dataset.handle, batch, self.eta, self.reg0, self.regw,
+                      self.regv, C.byref(st) if want_stats else None))
         fm._device_updated()
         return st.as_dict() if want_stats else None
 

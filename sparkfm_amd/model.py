@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _ffi
 from .dataset import DataSet
+from .relational import RelationalData
 
 
 class Model:
@@ -197,6 +198,10 @@ class FMModel(Model):
         """FMModel.predict (S/fm/FMModel.scala:34-55).  `features` is one sparse row
         ``(indices, values)`` -> float, or a DataSet -> array (the rdd.mapValues(predict) of
         S/Model.scala:14)."""
+        if isinstance(features, RelationalData):        # every block's forward once, then one combine per data row
+            out = np.empty(features.size)
+            _ffi.check(_ffi.load().fmhip_relational_predict(self.handle, features.rel_handle, _ffi.ptr(out)))
+            return out
         if isinstance(features, DataSet):
             out = np.empty(features.size)
             _ffi.check(_ffi.load().fmhip_predict(self.handle, features.handle, _ffi.ptr(out)))
@@ -214,6 +219,9 @@ class FMModel(Model):
     def computeRMSE(self, dataset):
         """Model.computeRMSE (S/Model.scala:13-19)."""
         r = C.c_double()
+        if isinstance(dataset, RelationalData):
+            _ffi.check(_ffi.load().fmhip_relational_rmse(self.handle, dataset.rel_handle, C.byref(r), None))
+            return r.value
         _ffi.check(_ffi.load().fmhip_rmse(self.handle, dataset.handle, C.byref(r), None))
         return r.value
 
@@ -222,6 +230,9 @@ class FMModel(Model):
         under (fmhip_logloss; binary classification — the reference declares Task.Classification and scores it only by
         sign, S/Model.scala:28-30)."""
         r = C.c_double()
+        if isinstance(dataset, RelationalData):
+            _ffi.check(_ffi.load().fmhip_relational_logloss(self.handle, dataset.rel_handle, C.byref(r), None))
+            return r.value
         _ffi.check(_ffi.load().fmhip_logloss(self.handle, dataset.handle, C.byref(r), None))
         return r.value
 
