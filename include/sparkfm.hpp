@@ -13,7 +13,7 @@
 //     sparkfm::HipALS       S/fm/lib/ALS.scala:15-75,202-208 the reference's own learner in fp64 on the GPU
 //     sparkfm::FM           S/fm/FM.scala:25-33, S/fm/impl/FactorizationMachines.scala:30-51   the fit loop
 //
-// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC), include/fmhip_ranking.h (ranking evaluation), include/fmhip_weights.h (per-row example weights) and include/fmhip_relational.h (relational data) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
+// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC), include/fmhip_ranking.h (ranking evaluation), include/fmhip_weights.h (per-row example weights), include/fmhip_relational.h (relational data) and include/fmhip_mcmc.h (the MCMC learner) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
 // here a non-zero status of the C ABI becomes sparkfm::Error carrying fmhip_last_error().  Parameters live on the host as in
 // the reference (public, mutable: `fm.w0`, `fm.w`, `fm.v` with v[f + i*k] = breeze's column-major DenseMatrix(k, n+1)); every
 // call that needs them on the device uploads them first, as jvm/HipSGD.scala does (the fit loop calls `learn` once per
@@ -37,6 +37,7 @@
 #include "fmhip_ranking.h"
 #include "fmhip_weights.h"
 #include "fmhip_relational.h"
+#include "fmhip_mcmc.h"
 
 namespace sparkfm {
 
@@ -459,6 +460,116 @@ class HipALS : public FMLearn {
         fm.download();
         return fm;
     }
+};
+
+// Bayesian FM by Gibbs sampling on the ALS column walk (include/fmhip_mcmc.h; libFM's MCMC learner, of which the reference's ALS.scala
+// is the cut-down copy): one learn = one Gibbs sweep in fp64.  Nothing to tune: the noise precision alpha and every group's
+// regulariser lambda and prior mean mu are sampled; the prediction is the average over the draws — of `test` (a one-batch DataSet
+// that must outlive the learner; nullptr: none), since the burn-in ended (the running average is reset once, after burn_in epochs).
+// opts (public: seed, sample, reg0, init_lambda, libFM's priors) are read when the handle is made — by the first learn for a
+// (model, dataset) pair; close() frees it, and must come before the dataset's device copy is dropped and used again.
+class HipMCMC : public FMLearn {
+  public:
+    struct State {
+        double alpha = 1.0;
+        std::vector<double> lambda, mu;             // k + 1 each: group 0 = w, 1 + f = factor f
+        int64_t iterations = 0;
+    };
+    fmhip_mcmc_opts opts;
+    int64_t burn_in;
+    fmhip_mcmc_stats last_stats{};
+    explicit HipMCMC(uint64_t seed = 0, DataSet *test = nullptr, int64_t burn_in_ = 0, bool sample = true) : burn_in(burn_in_), test_(test) {
+        check(fmhip_mcmc_opts_default(&opts));
+        opts.seed = seed;
+        opts.sample = sample ? 1 : 0;
+    }
+    static HipMCMC run(uint64_t seed = 0, DataSet *test = nullptr, int64_t burn_in = 0, bool sample = true) { return HipMCMC(seed, test, burn_in, sample); }
+    HipMCMC(const HipMCMC &) = delete;
+    HipMCMC &operator=(const HipMCMC &) = delete;
+    ~HipMCMC() override { (void)fmhip_mcmc_destroy(h_); }
+
+    using FMLearn::learn;
+    FMModel &learn(FMModel &fm, DataSet &dataset) override {
+        fmhip_model_t m = fm.upload();
+        fmhip_dataset_t d = dataset.handle();
+        if (h_ && (m != m_ || d != d_)) close();
+        if (!h_) {
+            check(fmhip_mcmc_create(m, d, test_ ? test_->handle() : nullptr, &opts, &h_));
+            m_ = m;
+            d_ = d;
+            k_ = fm.num_factor;
+            if (pending_) {
+                check(fmhip_mcmc_set_state(h_, pending_state_.alpha, pending_state_.lambda.data(), pending_state_.mu.data()));
+                pending_ = false;
+            }
+        }
+        check(fmhip_mcmc_epoch(h_, &last_stats));
+        fm.download();
+        if (burn_in > 0 && last_stats.iterations == burn_in) check(fmhip_mcmc_reset_average(h_));
+        return fm;
+    }
+    State state() {
+        State st;
+        st.lambda.resize((size_t)k_ + 1);
+        st.mu.resize((size_t)k_ + 1);
+        check(fmhip_mcmc_get_state(need(), &st.alpha, st.lambda.data(), st.mu.data(), &st.iterations));
+        return st;
+    }
+    // before the first learn the state is kept and set when the handle is made (lambda, mu: k + 1 values each)
+    void setState(double alpha, const std::vector<double> &lambda, const std::vector<double> &mu) {
+        if (!h_) {
+            pending_state_.alpha = alpha;
+            pending_state_.lambda = lambda;
+            pending_state_.mu = mu;
+            pending_ = true;
+            return;
+        }
+        if (lambda.size() != (size_t)k_ + 1 || mu.size() != (size_t)k_ + 1) throw Error(FMHIP_ERR_INVALID, "lambda and mu must hold k + 1 values each");
+        check(fmhip_mcmc_set_state(h_, alpha, lambda.data(), mu.data()));
+    }
+    void resetAverage() { check(fmhip_mcmc_reset_average(need())); }
+    std::vector<double> predictions() {             // the test rows' predictions averaged over the kept draws
+        std::vector<double> mean(test_rows());
+        check(fmhip_mcmc_predictions(need(), mean.data(), nullptr, nullptr));
+        return mean;
+    }
+    std::vector<double> lastPredictions() {         // ... under the last draw
+        std::vector<double> last(test_rows());
+        check(fmhip_mcmc_predictions(need(), nullptr, last.data(), nullptr));
+        return last;
+    }
+    int64_t draws() {
+        int64_t n = 0;
+        check(fmhip_mcmc_predictions(need(), nullptr, nullptr, &n));
+        return n;
+    }
+    double computeRMSE() {                          // of the averaged prediction against the test labels
+        const std::vector<double> mean = predictions();
+        double sse = 0.0;
+        for (size_t r = 0; r < mean.size(); ++r) sse += (mean[r] - test_->labels()[r]) * (mean[r] - test_->labels()[r]);
+        return mean.empty() ? 0.0 : std::sqrt(sse / (double)mean.size());
+    }
+    void close() {
+        check(fmhip_mcmc_destroy(h_));
+        h_ = nullptr;
+    }
+
+  private:
+    fmhip_mcmc_t need() const {
+        if (!h_) throw Error(FMHIP_ERR_INVALID, "HipMCMC has no handle yet: it is made by the first learn(fm, dataset)");
+        return h_;
+    }
+    size_t test_rows() const {
+        if (!test_) throw Error(FMHIP_ERR_INVALID, "HipMCMC was made without a test set");
+        return (size_t)test_->size();
+    }
+    DataSet *test_;
+    fmhip_mcmc_t h_ = nullptr;
+    fmhip_model_t m_ = nullptr;
+    fmhip_dataset_t d_ = nullptr;
+    int32_t k_ = 0;
+    bool pending_ = false;
+    State pending_state_;
 };
 
 // FM(dataset, numFactor, maxIteration).learnWith(learner) — S/fm/FM.scala:25-33 and the fit loop of

@@ -7,11 +7,11 @@ The arithmetic runs in hand-written HIP kernels (csrc/) behind a plain C ABI
 from .dataset import DataSet, Features  # noqa: F401
 from .relational import Relation, RelationalData  # noqa: F401
 from .model import FMModel, Model  # noqa: F401
-from .learn import FMLearn, HipALS, HipSGD  # noqa: F401
+from .learn import FMLearn, HipALS, HipMCMC, HipSGD  # noqa: F401
 from .fm import FM, FactorizationMachines, Task  # noqa: F401
 from .datacollection import DataCollection  # noqa: F401
 from .feature_order import FeatureOrder  # noqa: F401
 from . import fmutils as FMUtils  # noqa: F401
 
-__all__ = ["DataSet", "Features", "FMModel", "Model", "FMLearn", "HipSGD", "HipALS", "FM", "FactorizationMachines", "Task",
+__all__ = ["DataSet", "Features", "FMModel", "Model", "FMLearn", "HipSGD", "HipALS", "HipMCMC", "FM", "FactorizationMachines", "Task",
            "DataCollection", "FMUtils", "FeatureOrder", "Relation", "RelationalData"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -58,6 +58,9 @@ SYMBOLS_RELATIONAL = ("fmhip_relational_create", "fmhip_relational_destroy", "fm
                       "fmhip_relational_rmse", "fmhip_relational_logloss", "fmhip_relational_sgd_step", "fmhip_relational_sgd_epoch")
 RELATIONS_MAX = 8          # FMHIP_RELATIONS_MAX
 RELATIONAL_SUM_CUT = 256   # FMHIP_RELATIONAL_SUM_CUT: a block row referenced by more rows of a batch is summed in chunks of this many
+# ... and include/fmhip_mcmc.h — the MCMC learner: Bayesian FM by Gibbs sampling on the ALS column walk
+SYMBOLS_MCMC = ("fmhip_mcmc_opts_default", "fmhip_mcmc_create", "fmhip_mcmc_destroy", "fmhip_mcmc_epoch", "fmhip_mcmc_get_state",
+                "fmhip_mcmc_set_state", "fmhip_mcmc_reset_average", "fmhip_mcmc_predictions")
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -258,6 +261,21 @@ def group_ids(groups, n):
     return np.ascontiguousarray(g, np.int32)     # (a negative id is refused by the library, which names the row)
 
 
+class McmcOpts(C.Structure):
+    """fmhip_mcmc_opts (include/fmhip_mcmc.h)."""
+    _fields_ = [("seed", C.c_uint64), ("sample", C.c_int32), ("reg0", C.c_double), ("init_lambda", C.c_double),
+                ("alpha_0", C.c_double), ("beta_0", C.c_double), ("alpha_lambda", C.c_double), ("beta_lambda", C.c_double),
+                ("gamma_0", C.c_double), ("mu_0", C.c_double)]
+
+
+class McmcStats(C.Structure):
+    """fmhip_mcmc_stats (include/fmhip_mcmc.h)."""
+    _fields_ = [("alpha", C.c_double), ("train_rmse", C.c_double), ("iterations", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DatasetOpts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("hot_block", C.c_int32), ("batch_rows", C.c_int64), ("row_block_rows", C.c_int64)]
 
@@ -411,8 +429,16 @@ def load():
     L.fmhip_relational_logloss.argtypes = [vp, vp, P(dbl), P(Stats)]
     L.fmhip_relational_sgd_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, P(Stats)]
     L.fmhip_relational_sgd_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, vp, P(Stats)]
+    L.fmhip_mcmc_opts_default.argtypes = [P(McmcOpts)]
+    L.fmhip_mcmc_create.argtypes = [vp, vp, vp, P(McmcOpts), P(vp)]
+    L.fmhip_mcmc_destroy.argtypes = [vp]
+    L.fmhip_mcmc_epoch.argtypes = [vp, P(McmcStats)]
+    L.fmhip_mcmc_get_state.argtypes = [vp, P(dbl), vp, vp, P(i64)]
+    L.fmhip_mcmc_set_state.argtypes = [vp, dbl, vp, vp]
+    L.fmhip_mcmc_reset_average.argtypes = [vp]
+    L.fmhip_mcmc_predictions.argtypes = [vp, vp, vp, P(i64)]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
-                 + SYMBOLS_RELATIONAL):
+                 + SYMBOLS_RELATIONAL + SYMBOLS_MCMC):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

@@ -1,4 +1,5 @@
-// als_kernels.h — launcher of the fp64 ALS epoch (internal to libfmhip.so).
+// als_kernels.h — launchers of the fp64 ALS epoch and of the MCMC learner's epoch, which walks the same columns (internal to
+// libfmhip.so).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,6 +37,17 @@ struct AlsArgs {
     const int32_t *lev_cols;
 };
 
+// What the MCMC epoch's walks take beside AlsArgs (include/fmhip_mcmc.h; the ALS epoch's kernels take AlsArgs alone, as ever):
+// hyp = {alpha, lambda[k + 1], mu[k + 1]} of the groups g = 0 (w), 1 + f (factor f); z = this epoch's N(0,1) per (group, column
+// slot), [(k + 1) * n_cols], then the bias's; sample = 0: every step takes the conditional's mean and z does not enter it;
+// zi: set by the launcher of a long column's chip-wide step — that column's entry of z
+struct McmcDev {
+    const double *hyp;
+    const double *z;
+    int32_t sample;
+    int64_t zi;
+};
+
 constexpr int kAlsMaxParts = 512;       // workgroups of a chip-wide column step
 // Columns of at least this many entries take the chip-wide two-launch step, shorter ones the one-workgroup walk
 // (FMHIP_ALS_LONG in the environment overrides it: a test / measurement knob)
@@ -46,5 +58,19 @@ constexpr int kAlsLongColumn = 8192;
 // 16 columns on average (FMHIP_ALS_LEVELS=0 / 1 in the environment: never / always — a test and measurement knob).
 hipError_t launch_als_epoch(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
                             const int32_t *h_lev_cols, int n_levels, hipStream_t s);
+
+// ---- the MCMC epoch: the ALS column walk with the Gaussian conditional's draw in computeTheta's place --------------------
+constexpr int kMcmcSumParts = 64;       // workgroups (= partial sums the host adds in order) per reduced quantity
+// The launches in front of the epoch's one host sync: the epoch's noise into z (= m.z; m.sample only; counter (id, group, t, stream)
+// under `seed`), the residuals e = yhat - y, and the sums the hyper-parameter draws need — sums[2 * (q * kMcmcSumParts + c)], + 1:
+// quantity q = 0 {sum e^2, -}, q = 1 + g {sum theta, sum (theta - m.hyp's mu_g)^2} over group g's trained parameters
+hipError_t launch_mcmc_begin(const AlsArgs &a, const McmcDev &m, double *z, uint64_t seed, uint32_t t, double *sums, hipStream_t s);
+// ... and behind it, with the new m.hyp on the device: the bias draw, the residuals again, q, the sweeps — launch_als_epoch's
+// plan (the same environment knobs), every step a draw
+hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
+                              const int32_t *h_lev_cols, int n_levels, hipStream_t s);
+// The test rows' predictions under the parameters t.w0 / t.w / t.v into t.e (the last draw's), and sum[r] += t.e[r]: t holds the
+// test set's k, n_rows, row_ptr, col, val and, as y, n_rows zeros (k_als_residual's e = yhat - 0 is the prediction exactly)
+hipError_t launch_mcmc_accumulate(const AlsArgs &t, double *sum, hipStream_t s);
 
 }  // namespace fmhip

@@ -21,6 +21,7 @@
 // Every factor's q comes from one up-front pass over the feature-sorted rows (k_als_q_all), the per-row order of the
 // reference's transposed pass.
 #include "als_kernels.h"
+#include "mcmc_rng.h"
 
 #include <cstdlib>
 
@@ -36,6 +37,51 @@ __device__ __forceinline__ double compute_theta(double theta, double reg, double
 #pragma clang fp contract(off)
     const double theta_new = -(sum_e_h - theta * sum_h_sqr) / (reg + sum_h_sqr);
     return is_updatable(theta_new, theta) ? theta_new : theta;
+}
+
+// The closed-form step of one coordinate as a value: what the walks below call where ALS.scala calls computeTheta.
+//  * DrawAls  — computeTheta itself (the ALS epoch: the arithmetic it always had);
+//  * DrawMcmc — libFM's Gaussian conditional (include/fmhip_mcmc.h): precision lambda + alpha sum h^2, its mean, and (sample)
+//    the coordinate's own N(0,1) scaled by 1 / sqrt(precision).  With alpha = 1, mu = 0, sample off it rounds exactly as
+//    computeTheta does (1 * x and x - 0 are exact): ALS = MCMC without sampling, bit for bit.
+struct DrawAls {
+    double reg;
+    __device__ __forceinline__ double operator()(double theta, double sum_e_h, double sum_h_sqr, double) const {
+        return compute_theta(theta, reg, sum_e_h, sum_h_sqr);
+    }
+};
+
+struct DrawMcmc {
+    double alpha, lambda, mu;
+    bool sample;
+    __device__ __forceinline__ double operator()(double theta, double sum_e_h, double sum_h_sqr, double z) const {
+#pragma clang fp contract(off)
+        const double prec = lambda + alpha * sum_h_sqr;
+        const double mean = -(alpha * (sum_e_h - theta * sum_h_sqr) - mu * lambda) / prec;
+        const double theta_new = sample ? mean + z / sqrt(prec) : mean;      // (no `+ 0 * sigma` without sampling)
+        return is_updatable(theta_new, theta) ? theta_new : theta;
+    }
+};
+
+// Every walk below takes a parameter pack M that is EMPTY for the ALS epoch — its kernels keep the signatures, the kernel
+// arguments and the code they always had — and holds one McmcDev for the MCMC epoch; the overloads pick the step by it.
+// The draw of parameter group g (0: w, 1 + f: factor f); m.hyp = {alpha, lambda[k + 1], mu[k + 1]}
+__device__ __forceinline__ DrawAls group_draw(const AlsArgs &, int, double reg) { return DrawAls{reg}; }
+__device__ __forceinline__ DrawMcmc group_draw(const AlsArgs &a, int g, double, const McmcDev &m) {
+    return DrawMcmc{m.hyp[0], m.hyp[1 + g], m.hyp[2 + a.k + g], m.sample != 0};
+}
+
+// the noise of entry idx of m.z (k_mcmc_noise filled it before the epoch's first dependent launch); of a long column's own step
+__device__ __forceinline__ double noise_at(int64_t) { return 0.0; }
+__device__ __forceinline__ double noise_at(int64_t idx, const McmcDev &m) { return m.z[idx]; }
+__device__ __forceinline__ double noise_own() { return 0.0; }
+__device__ __forceinline__ double noise_own(const McmcDev &m) { return m.z[m.zi]; }
+
+// the bias step: computeTheta(w0, reg0, sum e, size) / the conditional with h = 1, lambda = reg0, mu = 0 (its noise sits behind
+// the coordinates')
+__device__ __forceinline__ double bias_step(const AlsArgs &a, double w0, double se) { return compute_theta(w0, a.reg0, se, (double)a.n_rows); }
+__device__ __forceinline__ double bias_step(const AlsArgs &a, double w0, double se, const McmcDev &m) {
+    return DrawMcmc{m.hyp[0], a.reg0, 0.0, m.sample != 0}(w0, se, (double)a.n_rows, m.z[(int64_t)(a.k + 1) * a.n_cols]);
 }
 
 // ALS.precomputeTermE (S/fm/lib/ALS.scala:142-144) with FMModel.predict's exact order of operations
@@ -65,6 +111,12 @@ __global__ __launch_bounds__(256) void k_als_residual(AlsArgs a) {
     }
 }
 
+// The MCMC learner's averaged prediction.  The test rows' predictions under the draw the epoch left are k_als_residual's own —
+// launched on the test rows with labels of zero, e = yhat - 0 is yhat exactly — written to `last`; this adds them to the running sum.
+__global__ __launch_bounds__(256) void k_mcmc_accumulate(const double *last, double *sum, int64_t n_rows) {
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * 256) sum[r] += last[r];
+}
+
 // fixed-order block sum of two doubles; result valid in every thread
 template <int kAlsBlock>
 __device__ __forceinline__ void block_sum2(double &x, double &y, double (*sh)[kAlsBlock / 64]) {
@@ -84,12 +136,63 @@ __device__ __forceinline__ void block_sum2(double &x, double &y, double (*sh)[kA
     y = ty;
 }
 
+// The N(0,1) of every coordinate the epoch will draw — z[g * n_cols + s] for column slot s of group g, then the bias's — in one
+// chip-wide launch before anything else: a draw depends on its counter only, so none of it sits on the sweep's dependent chain.
+__global__ __launch_bounds__(256) void k_mcmc_noise(AlsArgs a, double *z, uint64_t seed, uint32_t t) {
+    const int64_t total = (int64_t)(a.k + 1) * a.n_cols;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx <= total; idx += (int64_t)gridDim.x * 256) {
+        if (idx == total) {
+            z[idx] = rng::normal(seed, 0u, 0u, t, rng::kStreamW0);
+        } else {
+            const uint32_t g = (uint32_t)(idx / a.n_cols);
+            z[idx] = rng::normal(seed, (uint32_t)a.cfeat[idx % a.n_cols], g, t, rng::kStreamCoord);
+        }
+    }
+}
+
+// What the hyper-parameter draws need, in one launch of fixed-order reductions: quantity 0 = sum e^2 over the rows, quantity
+// 1 + g = {sum theta_i, sum (theta_i - mu_g)^2} over group g's trained parameters (the column slots with id < num_attribute;
+// mu_g: the mean the epoch starts from, m.hyp).  Every quantity is cut into P contiguous chunks, a workgroup each:
+// out[2 * (quantity * P + chunk)], + 1 — the host adds a quantity's P partials in order.  All groups at epoch start: nothing
+// writes w, or column f of V, before that group's own sweep (the argument that lets k_als_q_all run up front).
+constexpr int kSumsBlock = 256;
+__global__ __launch_bounds__(kSumsBlock) void k_mcmc_sums(AlsArgs a, McmcDev m, double *out, int P) {
+#pragma clang fp contract(off)
+    __shared__ double sh[2][kSumsBlock / 64];
+    const int quantity = (int)blockIdx.x / P, chunk = (int)blockIdx.x % P, tid = threadIdx.x;
+    double s0 = 0.0, s1 = 0.0;
+    if (quantity == 0) {
+        const int64_t lo = a.n_rows * chunk / P, hi = a.n_rows * (chunk + 1) / P;
+        for (int64_t r = lo + tid; r < hi; r += kSumsBlock) {
+            const double e = a.e[r];
+            s0 += e * e;
+        }
+    } else {
+        const int g = quantity - 1;
+        const double mu = m.hyp[2 + a.k + g];
+        const int64_t lo = (int64_t)a.n_cols * chunk / P, hi = (int64_t)a.n_cols * (chunk + 1) / P;
+        for (int64_t s = lo + tid; s < hi; s += kSumsBlock) {
+            const int64_t i = a.cfeat[s];
+            if (i >= a.num_attribute) continue;                    // quirk Q1: slot n is never trained
+            const double th = g == 0 ? a.w[i] : a.v[(g - 1) + i * a.k];
+            const double d = th - mu;
+            s0 += th;
+            s1 += d * d;
+        }
+    }
+    block_sum2<kSumsBlock>(s0, s1, sh);
+    if (tid == 0) {
+        out[2 * (int64_t)blockIdx.x] = s0;
+        out[2 * (int64_t)blockIdx.x + 1] = s1;
+    }
+}
+
 // drawGlobalBias :152-154 = computeTheta(w0, reg0, sum e, size) and `fm.w0 = w0` (:19-27) — once per epoch, one workgroup.
 // The residuals are NOT shifted here: as Spark evaluates :23-31 the lazy `error` RDD is materialised after `fm.w0 = w0`, so
 // its `fm.predict` already carries the new bias and the mapped term `w0 - fm.w0` is zero — the
 // launcher simply runs k_als_residual again with the new bias.
-template <int kAlsBlock>
-__global__ __launch_bounds__(kAlsBlock) void k_als_w0(AlsArgs a) {
+template <int kAlsBlock, class... M>
+__global__ __launch_bounds__(kAlsBlock) void k_als_w0(AlsArgs a, M... m) {
 #pragma clang fp contract(off)
     __shared__ double sh[2][kAlsBlock / 64];
     const int tid = threadIdx.x;
@@ -97,25 +200,27 @@ __global__ __launch_bounds__(kAlsBlock) void k_als_w0(AlsArgs a) {
     for (int64_t r = tid; r < a.n_rows; r += kAlsBlock) se += a.e[r];
     block_sum2<kAlsBlock>(se, dummy, sh);
     const double w0 = *a.w0;
-    const double w0n = compute_theta(w0, a.reg0, se, (double)a.n_rows);
+    const double w0n = bias_step(a, w0, se, m...);
     if (tid == 0) *a.w0 = w0n;
 }
 
 // The closed-form steps of the consecutive columns [s_lo, s_hi) by ONE workgroup, in order (S/fm/lib/ALS.scala:36-43
 // linear weights, :52-68 factor f): the run of SHORT columns between two long ones.  e and q in global memory.
-template <int kAlsBlock, bool FACTOR>   // threads: 256 for short columns (cheaper barriers), 1024 for longer ones
-__global__ __launch_bounds__(kAlsBlock) void k_als_cols_wg(AlsArgs a, double *q, int s_lo, int s_hi, int f) {
+template <int kAlsBlock, bool FACTOR, class... M>   // threads: 256 for short columns (cheaper barriers), 1024 for longer ones
+__global__ __launch_bounds__(kAlsBlock) void k_als_cols_wg(AlsArgs a, double *q, int s_lo, int s_hi, int f, M... m) {
 #pragma clang fp contract(off)
     __shared__ double sh[2][kAlsBlock / 64];
     const int tid = threadIdx.x;
     const int k = a.k;
-    const double reg = FACTOR ? a.regv : a.regw;
+    const int g = FACTOR ? 1 + f : 0;
+    const auto draw = group_draw(a, g, FACTOR ? a.regv : a.regw, m...);
     for (int s = s_lo; s < s_hi; ++s) {
         const int64_t i = a.cfeat[s];
         if (i >= a.num_attribute) continue;                       // `0 until num_attribute` (quirk Q1: slot n is never trained)
         const int c0 = a.cptr[s], c1 = a.cptr[s + 1];
         double *par = FACTOR ? a.v + f + i * k : a.w + i;
         const double th = *par;
+        const double zn = noise_at((int64_t)g * a.n_cols + s, m...);
         double shs = 0.0, seh = 0.0;
         for (int p = c0 + tid; p < c1; p += kAlsBlock) {
             const uint32_t r = a.crow[p] & 0x7fffffffu;
@@ -125,7 +230,7 @@ __global__ __launch_bounds__(kAlsBlock) void k_als_cols_wg(AlsArgs a, double *q,
             seh += a.e[r] * h;
         }
         block_sum2<kAlsBlock>(shs, seh, sh);
-        const double tn = compute_theta(th, reg, seh, shs);
+        const double tn = draw(th, seh, shs, zn);
         const double d = tn - th;
         const bool upd = is_updatable(tn, th);
         for (int p = c0 + tid; p < c1; p += kAlsBlock) {
@@ -173,8 +278,8 @@ __global__ __launch_bounds__(kColBlock) void k_als_col_sums(AlsArgs a, const dou
 
 // launch 2: every workgroup adds the G partials in the same fixed tree (the same bits everywhere), forms theta* and
 // updates its slice of e (and q); workgroup 0 stores the parameter
-template <bool FACTOR>
-__global__ __launch_bounds__(kColBlock) void k_als_col_update(AlsArgs a, double *q, int c0, int c1, int64_t i, int f) {
+template <bool FACTOR, class... M>
+__global__ __launch_bounds__(kColBlock) void k_als_col_update(AlsArgs a, double *q, int c0, int c1, int64_t i, int f, M... m) {
 #pragma clang fp contract(off)
     __shared__ double sh[2][kColBlock / 64];
     const int tid = threadIdx.x, G = (int)gridDim.x;
@@ -185,7 +290,7 @@ __global__ __launch_bounds__(kColBlock) void k_als_col_update(AlsArgs a, double 
     }
     block_sum2<kColBlock>(shs, seh, sh);
     const double th = a.part[2 * G];
-    const double tn = compute_theta(th, FACTOR ? a.regv : a.regw, seh, shs);
+    const double tn = group_draw(a, FACTOR ? 1 + f : 0, FACTOR ? a.regv : a.regw, m...)(th, seh, shs, noise_own(m...));
     const double d = tn - th;
     const bool upd = is_updatable(tn, th);
     const int per = (c1 - c0 + G - 1) / G;
@@ -275,9 +380,9 @@ __device__ __forceinline__ ColHead load_head(const AlsArgs &a, int c0, int lane)
 // The first two wave-iterations of the column (<= 128 entries: every column of config 1) stay in registers
 // between the sums and the update — e and q are read from LDS once; `head` arrives prefetched and leaves holding
 // the next column's.
-template <bool FACTOR, bool NEXT = true>
-__device__ __forceinline__ double column_step(const AlsArgs &a, double *e, double *q, int c0, int c1, double theta, double reg,
-                                              ColHead &head, int lane) {
+template <bool FACTOR, bool NEXT, class DRAW>
+__device__ __forceinline__ double column_step(const AlsArgs &a, double *e, double *q, int c0, int c1, double theta, const DRAW &draw,
+                                              double zn, ColHead &head, int lane) {
 #pragma clang fp contract(off)
     const int n = c1 - c0;
     const ColHead next = NEXT ? load_head(a, c1, lane) : head;      // in flight while this column is reduced
@@ -304,7 +409,7 @@ __device__ __forceinline__ double column_step(const AlsArgs &a, double *e, doubl
     }
     shs = wave_sum(shs);
     seh = wave_sum(seh);
-    const double tn = compute_theta(theta, reg, seh, shs);
+    const double tn = draw(theta, seh, shs, zn);
     const double d = tn - theta;
     const bool upd = is_updatable(tn, theta);
     if (v0) {
@@ -331,24 +436,29 @@ __device__ __forceinline__ double column_step(const AlsArgs &a, double *e, doubl
 // The column walk of one pass (linear weights, or factor f) by wave 0.  Everything a step needs from global memory
 // is requested a step (the column's entries, theta) or two (its feature id and end offset) ahead, so the chain of a
 // step is LDS + vector ALU only.  Valid because a pass touches every parameter exactly once.
-template <bool FACTOR>
-__device__ __forceinline__ void walk_columns(const AlsArgs &a, double *e, double *q, int f, int lane) {
+// (The MCMC walk's noise rides beside theta: drawn before the epoch's first dependent launch, read a step ahead.)
+template <bool FACTOR, class... M>
+__device__ __forceinline__ void walk_columns(const AlsArgs &a, double *e, double *q, int f, int lane, const M &...m) {
     const int k = a.k, nc = a.n_cols;
     if (nc < 1 || a.nnz < 1) return;
     double *par = FACTOR ? a.v + f : a.w;                          // parameter of feature i: par[i * stride]
     const int64_t stride = FACTOR ? k : 1;
-    const double reg = FACTOR ? a.regv : a.regw;
+    const int g = FACTOR ? 1 + f : 0;
+    const auto draw = group_draw(a, g, FACTOR ? a.regv : a.regw, m...);
+    const int64_t zrow = (int64_t)g * nc;
     int c0 = a.cptr[0], c1 = a.cptr[1];
     int64_t i_cur = a.cfeat[0], i_nx = a.cfeat[nc > 1 ? 1 : 0];
     int c_nx1 = a.cptr[nc > 1 ? 2 : 1];
     double th_cur = par[i_cur * stride];
+    double z_cur = noise_at(zrow, m...);
     ColHead head = load_head(a, c0, lane);
     for (int s = 0; s < nc; ++s) {
         const double th_nx = par[i_nx * stride];                   // step s+1's parameter
+        const double z_nx = noise_at(zrow + (s + 1 < nc ? s + 1 : nc - 1), m...);        // ... and its noise
         const int64_t i_nn = a.cfeat[s + 2 < nc ? s + 2 : nc - 1]; // step s+2's feature id and end offset (clamped, unconditional)
         const int c_nn1 = a.cptr[s + 3 < nc ? s + 3 : nc];
         if (i_cur < a.num_attribute) {                             // `0 until num_attribute`: slot n is never trained (quirk Q1)
-            const double tn = column_step<FACTOR>(a, e, q, c0, c1, th_cur, reg, head, lane);
+            const double tn = column_step<FACTOR, true>(a, e, q, c0, c1, th_cur, draw, z_cur, head, lane);
             if (lane == 0) par[i_cur * stride] = tn;               // :40 / :64
         } else {
             head = load_head(a, c1, lane);                         // skipped column: still hand the next column's head on
@@ -356,6 +466,7 @@ __device__ __forceinline__ void walk_columns(const AlsArgs &a, double *e, double
         c0 = c1; c1 = c_nx1; c_nx1 = c_nn1;
         i_cur = i_nx; i_nx = i_nn;
         th_cur = th_nx;
+        z_cur = z_nx;
     }
 }
 
@@ -366,8 +477,8 @@ __device__ __forceinline__ void walk_columns(const AlsArgs &a, double *e, double
 // of the one-wave LDS walk, on global memory — so a level-scheduled pass leaves the bits the sequential walk leaves.
 // One-hot fields (the reference's own MovieLens demo, S/driver.scala:73-113: a user field and an item field) are the
 // case this is for: all columns of a field form one level.
-template <bool FACTOR>
-__global__ __launch_bounds__(kLevelBlock) void k_als_level(AlsArgs a, double *q, const int32_t *cols, int n, int f, int long_col) {
+template <bool FACTOR, class... M>
+__global__ __launch_bounds__(kLevelBlock) void k_als_level(AlsArgs a, double *q, const int32_t *cols, int n, int f, int long_col, M... m) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
     const int j = (int)blockIdx.x * (kLevelBlock / 64) + (int)(threadIdx.x >> 6);
@@ -379,11 +490,14 @@ __global__ __launch_bounds__(kLevelBlock) void k_als_level(AlsArgs a, double *q,
     if (c1 - c0 >= long_col) return;                               // a long column of the level: the chip-wide step behind this launch
     double *par = FACTOR ? a.v + f + i * a.k : a.w + i;
     ColHead head = load_head(a, c0, lane);
-    const double tn = column_step<FACTOR, false>(a, a.e, q, c0, c1, *par, FACTOR ? a.regv : a.regw, head, lane);
+    const int g = FACTOR ? 1 + f : 0;
+    const double tn = column_step<FACTOR, false>(a, a.e, q, c0, c1, *par, group_draw(a, g, FACTOR ? a.regv : a.regw, m...),
+                                                 noise_at((int64_t)g * a.n_cols + s, m...), head, lane);
     if (lane == 0) *par = tn;                                      // :40 / :64
 }
 
-__global__ __launch_bounds__(kLdsSweepThreads) void k_als_sweep_lds(AlsArgs a, const double *qall) {
+template <class... M>
+__global__ __launch_bounds__(kLdsSweepThreads) void k_als_sweep_lds(AlsArgs a, const double *qall, M... m) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) double lds_eq[];
     double *e = lds_eq, *q = lds_eq + a.n_rows;
@@ -393,13 +507,13 @@ __global__ __launch_bounds__(kLdsSweepThreads) void k_als_sweep_lds(AlsArgs a, c
     __syncthreads();
     // (the global bias step ran before this launch: k_als_w0, then the residuals again with the new bias)
     // ---- linear weights (:36-43)
-    if (walker) walk_columns<false>(a, e, q, 0, lane);
+    if (walker) walk_columns<false>(a, e, q, 0, lane, m...);
     // ---- factors (:50-68): q of the factor comes in from the up-front pass, every thread copies its share
     for (int f = 0; f < a.k; ++f) {
         __syncthreads();
         for (int64_t r = tid; r < a.n_rows; r += kLdsSweepThreads) q[r] = qall[(int64_t)f * a.n_rows + r];
         __syncthreads();
-        if (walker) walk_columns<true>(a, e, q, f, lane);
+        if (walker) walk_columns<true>(a, e, q, f, lane, m...);
     }
 }
 
@@ -408,29 +522,37 @@ __global__ __launch_bounds__(kLdsSweepThreads) void k_als_sweep_lds(AlsArgs a, c
 namespace {
 
 // one chip-wide closed-form step of a long column (two launches; see k_als_col_sums)
-template <bool FACTOR>
-void long_column_step(const AlsArgs &a, double *q, int c0, int c1, int64_t i, int f, hipStream_t s) {
-    int G = (c1 - c0 + 2047) / 2048;
-    if (G > kAlsMaxParts) G = kAlsMaxParts;
-    hipLaunchKernelGGL((k_als_col_sums<FACTOR>), dim3((unsigned)G), dim3(kColBlock), 0, s, a, q, c0, c1, i, f);
-    hipLaunchKernelGGL((k_als_col_update<FACTOR>), dim3((unsigned)G), dim3(kColBlock), 0, s, a, q, c0, c1, i, f);
+inline McmcDev own_noise(McmcDev m, int64_t zi) {
+    m.zi = zi;
+    return m;
 }
 
-template <bool FACTOR>
-hipError_t sweep_pass(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, int f, int long_col, bool wide_wg, hipStream_t s) {
+// (slot: the column's index among the compressed columns — where its noise lies)
+template <bool FACTOR, class... M>
+void long_column_step(const AlsArgs &a, double *q, int c0, int c1, int64_t i, int f, int slot, hipStream_t s, const M &...m) {
+    int G = (c1 - c0 + 2047) / 2048;
+    if (G > kAlsMaxParts) G = kAlsMaxParts;
+    const int64_t zi = (int64_t)(FACTOR ? 1 + f : 0) * a.n_cols + slot;
+    (void)zi;
+    hipLaunchKernelGGL((k_als_col_sums<FACTOR>), dim3((unsigned)G), dim3(kColBlock), 0, s, a, q, c0, c1, i, f);
+    hipLaunchKernelGGL((k_als_col_update<FACTOR, M...>), dim3((unsigned)G), dim3(kColBlock), 0, s, a, q, c0, c1, i, f, own_noise(m, zi)...);
+}
+
+template <bool FACTOR, class... M>
+hipError_t sweep_pass(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, int f, int long_col, bool wide_wg, hipStream_t s, const M &...m) {
     double *q = a.q + (FACTOR ? (int64_t)f * a.n_rows : 0);
     int s0 = 0;
     while (s0 < a.n_cols) {
         const int len = h_cptr[s0 + 1] - h_cptr[s0];
         if (len >= long_col) {
-            if (h_cfeat[s0] < a.num_attribute) long_column_step<FACTOR>(a, q, h_cptr[s0], h_cptr[s0 + 1], (int64_t)h_cfeat[s0], f, s);
+            if (h_cfeat[s0] < a.num_attribute) long_column_step<FACTOR>(a, q, h_cptr[s0], h_cptr[s0 + 1], (int64_t)h_cfeat[s0], f, s0, s, m...);
             ++s0;
             continue;
         }
         int s1 = s0 + 1;
         while (s1 < a.n_cols && h_cptr[s1 + 1] - h_cptr[s1] < long_col) ++s1;
-        if (wide_wg) hipLaunchKernelGGL((k_als_cols_wg<1024, FACTOR>), dim3(1), dim3(1024), 0, s, a, q, s0, s1, f);
-        else hipLaunchKernelGGL((k_als_cols_wg<256, FACTOR>), dim3(1), dim3(256), 0, s, a, q, s0, s1, f);
+        if (wide_wg) hipLaunchKernelGGL((k_als_cols_wg<1024, FACTOR, M...>), dim3(1), dim3(1024), 0, s, a, q, s0, s1, f, m...);
+        else hipLaunchKernelGGL((k_als_cols_wg<256, FACTOR, M...>), dim3(1), dim3(256), 0, s, a, q, s0, s1, f, m...);
         s0 = s1;
     }
     return hipGetLastError();
@@ -439,36 +561,44 @@ hipError_t sweep_pass(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h
 }  // namespace
 
 namespace {
-template <bool FACTOR>
+template <bool FACTOR, class... M>
 hipError_t level_pass(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr, const int32_t *h_lev_cols,
-                      int n_levels, int f, int long_col, hipStream_t s) {
+                      int n_levels, int f, int long_col, hipStream_t s, const M &...m) {
     double *q = a.q + (FACTOR ? (int64_t)f * a.n_rows : 0);
     for (int l = 0; l < n_levels; ++l) {
         const int n = h_lev_ptr[l + 1] - h_lev_ptr[l];
         if (n < 1) continue;
-        hipLaunchKernelGGL((k_als_level<FACTOR>), dim3((unsigned)((n + kLevelBlock / 64 - 1) / (kLevelBlock / 64))), dim3(kLevelBlock), 0, s, a, q,
-                           a.lev_cols + h_lev_ptr[l], n, f, long_col);
+        hipLaunchKernelGGL((k_als_level<FACTOR, M...>), dim3((unsigned)((n + kLevelBlock / 64 - 1) / (kLevelBlock / 64))), dim3(kLevelBlock), 0, s, a, q,
+                           a.lev_cols + h_lev_ptr[l], n, f, long_col, m...);
         // the level's long columns share no row with its other columns either: their chip-wide steps follow, in any order
         for (int j = h_lev_ptr[l]; j < h_lev_ptr[l + 1]; ++j) {
             const int c = h_lev_cols[j];
             if (h_cptr[c + 1] - h_cptr[c] >= long_col && h_cfeat[c] < a.num_attribute)
-                long_column_step<FACTOR>(a, q, h_cptr[c], h_cptr[c + 1], (int64_t)h_cfeat[c], f, s);
+                long_column_step<FACTOR>(a, q, h_cptr[c], h_cptr[c + 1], (int64_t)h_cfeat[c], f, c, s, m...);
         }
     }
     return hipGetLastError();
 }
 }  // namespace
 
-hipError_t launch_als_epoch(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
-                            const int32_t *h_lev_cols, int n_levels, hipStream_t s) {
-    int64_t blocks = (a.n_rows + 255) / 256;
+namespace {
+
+unsigned row_blocks(int64_t n_rows) {
+    int64_t blocks = (n_rows + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
+    return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+// Everything of an epoch behind its first residual pass (which the caller has launched): the bias step, the residuals
+// again, every factor's q, the sweeps.  With an McmcDev every closed-form step is the Gaussian conditional's draw.
+template <class... M>
+hipError_t epoch_tail(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
+                      const int32_t *h_lev_cols, int n_levels, hipStream_t s, const M &...m) {
+    const unsigned blocks = row_blocks(a.n_rows);
     // precomputeTermE (:17) with the old bias feeds the bias step (:19-27); the residuals the sweeps start from are
     // evaluated after `fm.w0 = w0` (see k_als_w0)
-    hipLaunchKernelGGL(k_als_residual, dim3((unsigned)blocks), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_als_w0<1024>, dim3(1), dim3(1024), 0, s, a);
-    hipLaunchKernelGGL(k_als_residual, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_als_w0<1024, M...>), dim3(1), dim3(1024), 0, s, a, m...);
+    hipLaunchKernelGGL(k_als_residual, dim3(blocks), dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     int64_t qb = (a.n_rows * a.k + 255) / 256;
@@ -486,17 +616,17 @@ hipError_t launch_als_epoch(const AlsArgs &a, const int32_t *h_cfeat, const int3
         bool levels = have && (int64_t)n_levels * 16 <= a.n_cols;
         if (const char *ev = getenv("FMHIP_ALS_LEVELS")) levels = have && atoi(ev) != 0;
         if (levels) {
-            if ((e = level_pass<false>(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, 0, long_col, s)) != hipSuccess) return e;
+            if ((e = level_pass<false>(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, 0, long_col, s, m...)) != hipSuccess) return e;
             for (int f = 0; f < a.k; ++f)
-                if ((e = level_pass<true>(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, f, long_col, s)) != hipSuccess) return e;
+                if ((e = level_pass<true>(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, f, long_col, s, m...)) != hipSuccess) return e;
             return hipSuccess;
         }
     }
     if ((size_t)a.n_rows * 2 * sizeof(double) <= kAlsLdsBytes && !getenv("FMHIP_ALS_NO_LDS")) {
         // e and q fit the LDS of one CU: the one-wave column walk
-        e = hipFuncSetAttribute((const void *)k_als_sweep_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAlsLdsBytes);
+        e = hipFuncSetAttribute((const void *)k_als_sweep_lds<M...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAlsLdsBytes);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_als_sweep_lds, dim3(1), dim3(kLdsSweepThreads), (size_t)a.n_rows * 2 * sizeof(double), s, a, a.q);
+        hipLaunchKernelGGL(k_als_sweep_lds<M...>, dim3(1), dim3(kLdsSweepThreads), (size_t)a.n_rows * 2 * sizeof(double), s, a, a.q, m...);
         return hipGetLastError();
     }
     // e and q in global memory: one pass per parameter group following the column lengths — a run of short columns is one
@@ -508,10 +638,41 @@ hipError_t launch_als_epoch(const AlsArgs &a, const int32_t *h_cfeat, const int3
         if (len < long_col) { short_nnz += len; ++n_short; }
     }
     const bool wide_wg = n_short > 0 && short_nnz / n_short >= 512;
-    if ((e = sweep_pass<false>(a, h_cfeat, h_cptr, 0, long_col, wide_wg, s)) != hipSuccess) return e;
+    if ((e = sweep_pass<false>(a, h_cfeat, h_cptr, 0, long_col, wide_wg, s, m...)) != hipSuccess) return e;
     for (int f = 0; f < a.k; ++f)
-        if ((e = sweep_pass<true>(a, h_cfeat, h_cptr, f, long_col, wide_wg, s)) != hipSuccess) return e;
+        if ((e = sweep_pass<true>(a, h_cfeat, h_cptr, f, long_col, wide_wg, s, m...)) != hipSuccess) return e;
     return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t launch_als_epoch(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
+                            const int32_t *h_lev_cols, int n_levels, hipStream_t s) {
+    hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a);
+    return epoch_tail(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, s);
+}
+
+hipError_t launch_mcmc_begin(const AlsArgs &a, const McmcDev &m, double *z, uint64_t seed, uint32_t t, double *sums, hipStream_t s) {
+    if (m.sample) {
+        int64_t nb = ((int64_t)(a.k + 1) * a.n_cols + 1 + 255) / 256;
+        if (nb > 4096) nb = 4096;
+        hipLaunchKernelGGL(k_mcmc_noise, dim3((unsigned)nb), dim3(256), 0, s, a, z, seed, t);
+    }
+    hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_mcmc_sums, dim3((unsigned)((a.k + 2) * kMcmcSumParts)), dim3(kSumsBlock), 0, s, a, m, sums, kMcmcSumParts);
+    return hipGetLastError();
+}
+
+hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
+                              const int32_t *h_lev_cols, int n_levels, hipStream_t s) {
+    return epoch_tail(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, s, m);
+}
+
+hipError_t launch_mcmc_accumulate(const AlsArgs &t, double *sum, hipStream_t s) {
+    if (t.n_rows < 1) return hipSuccess;
+    hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(t.n_rows)), dim3(256), 0, s, t);
+    hipLaunchKernelGGL(k_mcmc_accumulate, dim3(row_blocks(t.n_rows)), dim3(256), 0, s, t.e, sum, t.n_rows);
+    return hipGetLastError();
 }
 
 }  // namespace fmhip

@@ -121,6 +121,90 @@ int get_params_impl(fmhip_model_t m, FT *w0, FT *w, FT *v) {
     return FMHIP_OK;
 }
 
+// ---- the column walk's epoch in pieces (fmhip_als_epoch below; fmhip_mcmc_epoch, fmhip_mcmc.hip) — the model's lock is the caller's
+
+// every reason the column walk refuses (m, d) — the model is untouched
+int als_check(fmhip_model_t m, fmhip_dataset_t d) {
+    TRY(check_train(m, d));
+    if (const char *why = refusal(Path::kAls, m->rule, d->weighted)) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
+    if (d->batches.size() > 1 || (d->nnz > 0 && !d->val64.p))
+        return fail(FMHIP_ERR_UNSUPPORTED, "ALS walks the whole-dataset transpose: create the dataset with batch_rows <= 0 "
+                                           "(single batch, at most 2^27 stored nonzeros) and without asking for the dense hot "
+                                           "block (fmhip_dataset_opts::hot_block <= 0)");
+    if (d->rb_rows > 0) return fail(FMHIP_ERR_UNSUPPORTED, "ALS needs a dataset without row blocks (FMHIP_TUNE_ROW_BLOCK = 0)");
+    if (d->als_dup)
+        return fail(FMHIP_ERR_UNSUPPORTED, "ALS: a row stores the same feature index twice; the column walk updates every row of a "
+                                           "column at once and needs the (row, feature) pairs to be distinct");
+    return FMHIP_OK;
+}
+
+// the fp64 masters onto the device and the walk's arguments (the workspace is the model's); *a is meaningful when d has rows
+int als_begin(fmhip_model_t m, fmhip_dataset_t d, double reg0, double regw, double regv, AlsArgs *out) {
+    TRY(als_check(m, d));
+    if (!m->host64_fresh) {   // parameters last changed by fp32 SGD: start from their fp64 widening
+        std::vector<double> w((size_t)m->n1), v((size_t)m->n1 * m->k);
+        double w0 = 0.0;
+        TRY(get_params_impl<double>(m, &w0, w.data(), v.data()));
+        m->h_w0 = w0;
+        m->h_w.swap(w);
+        m->h_v.swap(v);
+        m->host64_fresh = true;
+    }
+    const size_t n1 = (size_t)m->n1, nv = n1 * (size_t)m->k, nr = (size_t)std::max<int64_t>(d->n_rows, 1);
+    TRY(m->als_w0.ensure(1));
+    TRY(m->als_w.ensure(n1));
+    TRY(m->als_v.ensure(nv));
+    TRY(m->als_e.ensure(nr));
+    TRY(m->als_q.ensure(nr * (size_t)m->k));
+    TRY(m->als_part.ensure(2 * (size_t)kAlsMaxParts + 2));
+    HIP_TRY(hipMemcpyAsync(m->als_w0.p, &m->h_w0, sizeof(double), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipMemcpyAsync(m->als_w.p, m->h_w.data(), n1 * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipMemcpyAsync(m->als_v.p, m->h_v.data(), nv * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    AlsArgs a{};
+    if (d->n_rows > 0) {
+        const BatchMeta &bm = d->batches[0];
+        a.k = m->k;
+        a.num_attribute = m->n;
+        a.n_rows = d->n_rows;
+        a.nnz = d->nnz;
+        a.row_ptr = d->row_ptr.p;
+        a.col = d->col.p;
+        a.val = d->val64.p;
+        a.scol = d->scol.p;
+        a.sval = d->sval64.p;
+        a.y = d->y64.p;
+        a.n_cols = bm.n_cols;
+        a.cfeat = d->cfeat.p;
+        a.cptr = d->cptr.p;
+        a.crow = d->crow.p;
+        a.cval = d->cval64.p;
+        a.w0 = m->als_w0.p;
+        a.w = m->als_w.p;
+        a.v = m->als_v.p;
+        a.reg0 = reg0;
+        a.regw = regw;
+        a.regv = regv;
+        a.e = m->als_e.p;
+        a.q = m->als_q.p;
+        a.part = m->als_part.p;
+        a.lev_cols = d->als_lev_cols.p;
+    }
+    *out = a;
+    return FMHIP_OK;
+}
+
+// the device's fp64 parameters back into the masters and the fp32 device copy (synchronises)
+int als_end(fmhip_model_t m) {
+    const size_t n1 = (size_t)m->n1, nv = n1 * (size_t)m->k;
+    std::vector<double> w(n1), v(nv);
+    double w0 = 0.0;
+    HIP_TRY(hipMemcpyAsync(&w0, m->als_w0.p, sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipMemcpyAsync(w.data(), m->als_w.p, n1 * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipMemcpyAsync(v.data(), m->als_v.p, nv * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return set_params_impl<double>(m, w0, w.data(), v.data());   // refreshes the fp64 masters and the fp32 device copy
+}
+
 }  // namespace host
 }  // namespace fmhip
 
@@ -479,74 +563,14 @@ int fmhip_batch_grad(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, double *
 
 int fmhip_als_epoch(fmhip_model_t m, fmhip_dataset_t d, double reg0, double regw, double regv) {
     WriteLock lock(m);
-    TRY(check_train(m, d));
-    if (const char *why = refusal(Path::kAls, m->rule, d->weighted)) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
-    if (d->batches.size() > 1 || (d->nnz > 0 && !d->val64.p))
-        return fail(FMHIP_ERR_UNSUPPORTED, "ALS walks the whole-dataset transpose: create the dataset with batch_rows <= 0 "
-                                           "(single batch, at most 2^27 stored nonzeros) and without asking for the dense hot "
-                                           "block (fmhip_dataset_opts::hot_block <= 0)");
-    if (d->rb_rows > 0) return fail(FMHIP_ERR_UNSUPPORTED, "ALS needs a dataset without row blocks (FMHIP_TUNE_ROW_BLOCK = 0)");
-    if (d->als_dup)
-        return fail(FMHIP_ERR_UNSUPPORTED, "ALS: a row stores the same feature index twice; the column walk updates every row of a "
-                                           "column at once and needs the (row, feature) pairs to be distinct");
-    if (!m->host64_fresh) {   // parameters last changed by fp32 SGD: start from their fp64 widening
-        std::vector<double> w((size_t)m->n1), v((size_t)m->n1 * m->k);
-        double w0 = 0.0;
-        TRY(get_params_impl<double>(m, &w0, w.data(), v.data()));
-        m->h_w0 = w0;
-        m->h_w.swap(w);
-        m->h_v.swap(v);
-        m->host64_fresh = true;
-    }
-    const size_t n1 = (size_t)m->n1, nv = n1 * (size_t)m->k, nr = (size_t)std::max<int64_t>(d->n_rows, 1);
-    TRY(m->als_w0.ensure(1));
-    TRY(m->als_w.ensure(n1));
-    TRY(m->als_v.ensure(nv));
-    TRY(m->als_e.ensure(nr));
-    TRY(m->als_q.ensure(nr * (size_t)m->k));
-    TRY(m->als_part.ensure(2 * (size_t)kAlsMaxParts + 2));
-    HIP_TRY(hipMemcpyAsync(m->als_w0.p, &m->h_w0, sizeof(double), hipMemcpyHostToDevice, m->stream));
-    HIP_TRY(hipMemcpyAsync(m->als_w.p, m->h_w.data(), n1 * sizeof(double), hipMemcpyHostToDevice, m->stream));
-    HIP_TRY(hipMemcpyAsync(m->als_v.p, m->h_v.data(), nv * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    AlsArgs a{};
+    TRY(als_begin(m, d, reg0, regw, regv, &a));
     if (d->n_rows > 0) {
-        const BatchMeta &bm = d->batches[0];
-        AlsArgs a{};
-        a.k = m->k;
-        a.num_attribute = m->n;
-        a.n_rows = d->n_rows;
-        a.nnz = d->nnz;
-        a.row_ptr = d->row_ptr.p;
-        a.col = d->col.p;
-        a.val = d->val64.p;
-        a.scol = d->scol.p;
-        a.sval = d->sval64.p;
-        a.y = d->y64.p;
-        a.n_cols = bm.n_cols;
-        a.cfeat = d->cfeat.p;
-        a.cptr = d->cptr.p;
-        a.crow = d->crow.p;
-        a.cval = d->cval64.p;
-        a.w0 = m->als_w0.p;
-        a.w = m->als_w.p;
-        a.v = m->als_v.p;
-        a.reg0 = reg0;
-        a.regw = regw;
-        a.regv = regv;
-        a.e = m->als_e.p;
-        a.q = m->als_q.p;
-        a.part = m->als_part.p;
-        a.lev_cols = d->als_lev_cols.p;
         const int n_levels = d->als_lev_ptr.empty() ? 0 : (int)d->als_lev_ptr.size() - 1;
         HIP_TRY(launch_als_epoch(a, d->h_cfeat.data(), d->h_cptr.data(), n_levels ? d->als_lev_ptr.data() : nullptr, d->h_als_lev_cols.data(), n_levels,
                                  m->stream));
     }
-    std::vector<double> w(n1), v(nv);
-    double w0 = 0.0;
-    HIP_TRY(hipMemcpyAsync(&w0, m->als_w0.p, sizeof(double), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipMemcpyAsync(w.data(), m->als_w.p, n1 * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipMemcpyAsync(v.data(), m->als_v.p, nv * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    return set_params_impl<double>(m, w0, w.data(), v.data());   // refreshes the fp64 masters and the fp32 device copy
+    return als_end(m);
 }
 
 // ---- data-parallel split step

@@ -1,6 +1,7 @@
 // fmhip_host.cpp — the library's pure host arithmetic (fmhip_host.h): no HIP, no GPU.  Part of libfmhip.so, and compiled on
 // its own with g++ -fsanitize=address,undefined by the CPU suite (tests/host_arith_harness.cpp).
 #include "fmhip_host.h"
+#include "mcmc_rng.h"
 
 #include <stdlib.h>
 
@@ -9,6 +10,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
+#include <cmath>
 #include <numeric>
 
 namespace fmhip {
@@ -722,6 +724,59 @@ void RelationInverse::append_batch(const int32_t *map, int64_t rows, int64_t blo
     b.n_long = (int32_t)((int64_t)lt.size() - b.l_off);
     max_part = std::max(max_part, b.n_part);
     batches.push_back(b);
+}
+
+// ---- the MCMC learner's draws -------------------------------------------------------------------------------------------
+
+double mcmc_uniform(uint64_t seed, uint32_t index, uint32_t group, uint32_t t, uint32_t stream) { return rng::uniform(seed, index, group, t, stream); }
+double mcmc_normal(uint64_t seed, uint32_t index, uint32_t group, uint32_t t, uint32_t stream) { return rng::normal(seed, index, group, t, stream); }
+
+double mcmc_gamma(uint64_t seed, uint32_t group, uint32_t t, uint32_t stream, double shape, double rate, int *attempts) {
+    const bool boost = shape < 1.0;
+    const double a = boost ? shape + 1.0 : shape;
+    const double d = a - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
+    double out = a / rate;                  // (never reached: an attempt is accepted with probability > 0.95)
+    int j = 0;
+    for (; j < (1 << 20); ++j) {
+        const double x = rng::normal(seed, 2u * (uint32_t)j, group, t, stream), u = rng::uniform(seed, 2u * (uint32_t)j + 1u, group, t, stream);
+        double v = 1.0 + c * x;
+        v = v * v * v;
+        if (v <= 0.0) continue;
+        if (log(u) < x * x / 2.0 + d - d * v + d * log(v)) {
+            out = d * v / rate;
+            ++j;
+            break;
+        }
+    }
+    if (attempts) *attempts = j;
+    if (boost) out *= pow(rng::uniform(seed, 0xffffffffu, group, t, stream), 1.0 / shape);
+    return out;
+}
+
+const char *mcmc_bad_setting(const McmcPriors &p, double reg0, double init_lambda) {
+    auto pos = [](double x) { return std::isfinite(x) && x > 0.0; };
+    if (!pos(p.alpha_0)) return "alpha_0";
+    if (!pos(p.beta_0)) return "beta_0";
+    if (!pos(p.alpha_lambda)) return "alpha_lambda";
+    if (!pos(p.beta_lambda)) return "beta_lambda";
+    if (!pos(p.gamma_0)) return "gamma_0";
+    if (!std::isfinite(p.mu_0)) return "mu_0";
+    if (!(std::isfinite(reg0) && reg0 >= 0.0)) return "reg0";
+    if (!pos(init_lambda)) return "init_lambda";
+    return nullptr;
+}
+
+double mcmc_draw_alpha(uint64_t seed, uint32_t t, const McmcPriors &p, int64_t n_rows, double sse) {
+    return mcmc_gamma(seed, 0, t, rng::kStreamAlpha, (p.alpha_0 + (double)n_rows) / 2.0, (p.beta_0 + sse) / 2.0, nullptr);
+}
+
+void mcmc_draw_group(uint64_t seed, uint32_t t, uint32_t g, const McmcPriors &p, int64_t m, double sum_theta, double sum_dev2, double mu_old,
+                     double *lambda, double *mu) {
+    const double dm = mu_old - p.mu_0;
+    *lambda = mcmc_gamma(seed, g, t, rng::kStreamLambda, (p.alpha_lambda + (double)m + 1.0) / 2.0, (p.beta_lambda + sum_dev2 + p.gamma_0 * (dm * dm)) / 2.0,
+                         nullptr);
+    const double w = (double)m + p.gamma_0;
+    *mu = (sum_theta + p.gamma_0 * p.mu_0) / w + rng::normal(seed, 0, g, t, rng::kStreamMu) / sqrt(w * *lambda);
 }
 
 }  // namespace host

@@ -183,5 +183,26 @@ struct RelationInverse {
     void append_batch(const int32_t *map, int64_t rows, int64_t block_rows, int32_t cut, std::vector<int32_t> &count);
 };
 
+// ---- the MCMC learner's draws (fmhip_mcmc_epoch, include/fmhip_mcmc.h; the generator: mcmc_rng.h) ------------------------------
+// Counters are (index, group, t, stream); t = the epochs the handle has completed.
+double mcmc_uniform(uint64_t seed, uint32_t index, uint32_t group, uint32_t t, uint32_t stream);
+double mcmc_normal(uint64_t seed, uint32_t index, uint32_t group, uint32_t t, uint32_t stream);
+// Gamma(shape, rate) by Marsaglia-Tsang without the squeeze: attempt j takes the normal of index 2j and the uniform of index
+// 2j + 1 of (group, t, stream).  A shape below 1 draws shape + 1 and scales by uniform(index 2^32 - 1)^(1 / shape).
+// attempts (nullable): how many attempts the draw took.  shape, rate > 0 and finite (checked by the caller)
+double mcmc_gamma(uint64_t seed, uint32_t group, uint32_t t, uint32_t stream, double shape, double rate, int *attempts);
+// libFM's hyper-priors: alpha ~ Gamma(alpha_0 / 2, beta_0 / 2), lambda_g ~ Gamma(alpha_lambda / 2, beta_lambda / 2),
+// mu_g ~ N(mu_0, 1 / (gamma_0 lambda_g))
+struct McmcPriors { double alpha_0 = 1, beta_0 = 1, alpha_lambda = 1, beta_lambda = 1, gamma_0 = 1, mu_0 = 0; };
+// nullptr, or the name of the first setting that is not finite and > 0 (mu_0: finite; reg0: finite and >= 0)
+const char *mcmc_bad_setting(const McmcPriors &p, double reg0, double init_lambda);
+// alpha ~ Gamma((alpha_0 + N) / 2, rate (beta_0 + sse) / 2), sse = the sum of the squared residuals of the N rows
+double mcmc_draw_alpha(uint64_t seed, uint32_t t, const McmcPriors &p, int64_t n_rows, double sse);
+// group g's regulariser and mean from its m trained parameters: sum_theta = sum theta_i, sum_dev2 = sum (theta_i - mu_old)^2.
+// lambda ~ Gamma((alpha_lambda + m + 1) / 2, rate (beta_lambda + sum_dev2 + gamma_0 (mu_old - mu_0)^2) / 2), then with it
+// mu ~ N((sum_theta + gamma_0 mu_0) / (m + gamma_0), 1 / ((m + gamma_0) lambda)) = mean + z / sqrt((m + gamma_0) lambda)
+void mcmc_draw_group(uint64_t seed, uint32_t t, uint32_t g, const McmcPriors &p, int64_t m, double sum_theta, double sum_dev2, double mu_old,
+                     double *lambda, double *mu);
+
 }  // namespace host
 }  // namespace fmhip

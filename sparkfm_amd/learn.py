@@ -99,3 +99,154 @@ class HipALS(FMLearn):
         _ffi.check(_ffi.load().fmhip_als_epoch(fm.handle, dataset.handle, fm.reg0, fm.regw, fm.regv))
         fm._device_updated()
         return fm
+
+
+class HipMCMC(FMLearn):
+    """Bayesian FM by Gibbs sampling on the ALS column walk (include/fmhip_mcmc.h; libFM's MCMC learner, of which the reference's
+    ``ALS.scala`` is the cut-down copy): one ``learn`` = one Gibbs sweep in fp64.  No learning rate and no regularisers to tune:
+    the noise precision alpha and, per parameter group, the regulariser lambda and the prior mean mu are sampled; the prediction is
+    the average over the draws.
+
+        mcmc = HipMCMC.run(test=test, burn_in=15)
+        fm = FM(train, k, maxIteration=40).learnWith(mcmc)       # fm holds the LAST draw
+        mcmc.predictions(); mcmc.computeRMSE()                   # the averaged prediction of the 25 kept draws on `test`
+
+    `seed`: the key of the counter-based generator (the same seed gives the same bits, whatever walk the sweep takes).  `test`: a
+    DataSet (single batch, not scoring-only) whose predictions are averaged, or None.  `burn_in`: the running average is reset
+    once, after that many epochs.  `sample=False`: no draws at all — the conditional means under the state as set (with alpha = 1,
+    mu = 0, lambda = (regw, regv ...) that is ``HipALS``, bit for bit).  Priors (libFM's defaults): reg0 = 0, init_lambda = 1,
+    alpha_0 = beta_0 = alpha_lambda = beta_lambda = gamma_0 = 1, mu_0 = 0.  The handle is made on the first ``learn`` for a
+    (model, dataset) pair and remade when either changes; ``close()`` frees it.  Needs a single-batch DataSet like ``HipALS``."""
+
+    PRIORS = ("reg0", "init_lambda", "alpha_0", "beta_0", "alpha_lambda", "beta_lambda", "gamma_0", "mu_0")
+
+    def __init__(self, seed=0, test=None, burn_in=0, sample=True, **priors):
+        import math
+        import operator
+        self.seed = operator.index(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2^64), not %r" % (seed,))
+        self.burn_in = operator.index(burn_in)
+        if self.burn_in < 0:
+            raise ValueError("burn_in must be >= 0, not %d" % self.burn_in)
+        if not isinstance(sample, bool):
+            raise ValueError("sample must be True or False, not %r" % (sample,))
+        self.sample = sample
+        if isinstance(test, RelationalData):
+            test.handle             # raises: this call takes flat rows
+        if test is not None and getattr(test, "scoring", False):
+            raise ValueError("the test set must keep its fp64 rows: make it without scoring=True")
+        self.test = test
+        unknown = sorted(set(priors) - set(self.PRIORS))
+        if unknown:
+            raise TypeError("unknown prior %r (known: %s)" % (unknown[0], ", ".join(self.PRIORS)))
+        self.priors = dict(reg0=0.0, init_lambda=1.0, alpha_0=1.0, beta_0=1.0, alpha_lambda=1.0, beta_lambda=1.0, gamma_0=1.0, mu_0=0.0)
+        for name, value in priors.items():
+            value = float(value)
+            ok = math.isfinite(value) and (True if name == "mu_0" else value >= 0.0 if name == "reg0" else value > 0.0)
+            if not ok:
+                raise ValueError("%s must be finite and > 0 (mu_0: finite; reg0: finite and >= 0), not %r" % (name, value))
+            self.priors[name] = value
+        self._h = None
+        self._for = None            # the (model handle, dataset handle) values the MCMC handle was made for
+        self._pending_state = None
+        self.last_stats = None
+
+    @classmethod
+    def run(cls, seed=0, test=None, burn_in=0, sample=True, **priors):
+        return cls(seed=seed, test=test, burn_in=burn_in, sample=sample, **priors)
+
+    def _handle(self, fm, dataset):
+        L = _ffi.load()
+        mh, dh = fm.handle, dataset.handle
+        if self._h is not None and self._for != (mh.value, dh.value):
+            self.close()
+        if self._h is None:
+            opts = _ffi.McmcOpts(self.seed, 1 if self.sample else 0, *[self.priors[n] for n in self.PRIORS])
+            h = C.c_void_p()
+            _ffi.check(L.fmhip_mcmc_create(mh, dh, None if self.test is None else self.test.handle, C.byref(opts), C.byref(h)))
+            self._h, self._for, self._k = h, (mh.value, dh.value), fm.num_factor
+            self._keep = (fm, dataset)      # the handle borrows both
+            if self._pending_state is not None:
+                self.state = self._pending_state
+                self._pending_state = None
+        return self._h
+
+    def learn(self, fm, dataset):
+        if isinstance(dataset, RelationalData):
+            dataset.handle          # raises: this call takes flat rows
+        L = _ffi.load()
+        h = self._handle(fm, dataset)
+        st = _ffi.McmcStats()
+        _ffi.check(L.fmhip_mcmc_epoch(h, C.byref(st)))
+        fm._device_updated()
+        self.last_stats = st.as_dict()
+        if self.burn_in > 0 and st.iterations == self.burn_in:
+            _ffi.check(L.fmhip_mcmc_reset_average(h))
+        return fm
+
+    def _need(self):
+        if self._h is None:
+            raise RuntimeError("HipMCMC has no handle yet: it is made by the first learn(fm, dataset)")
+        return self._h
+
+    @property
+    def state(self):
+        """dict of alpha, lambda (k + 1: group 0 = w, 1 + f = factor f), mu (k + 1), iterations."""
+        h = self._need()
+        alpha, it = C.c_double(), C.c_int64()
+        lam, mu = np.empty(self._k + 1), np.empty(self._k + 1)
+        _ffi.check(_ffi.load().fmhip_mcmc_get_state(h, C.byref(alpha), _ffi.ptr(lam), _ffi.ptr(mu), C.byref(it)))
+        return dict(alpha=alpha.value, **{"lambda": lam, "mu": mu, "iterations": int(it.value)})
+
+    @state.setter
+    def state(self, value):
+        """(alpha, lambda, mu) or a dict with those keys; before the first learn it is kept and set when the handle is made."""
+        if isinstance(value, dict):
+            value = (value["alpha"], value["lambda"], value["mu"])
+        alpha, lam, mu = value
+        if self._h is None:
+            self._pending_state = (float(alpha), np.array(lam, np.float64), np.array(mu, np.float64))
+            return
+        lam, mu = np.ascontiguousarray(lam, np.float64), np.ascontiguousarray(mu, np.float64)
+        if lam.shape != (self._k + 1,) or mu.shape != (self._k + 1,):
+            raise ValueError("lambda and mu must hold k + 1 = %d values each" % (self._k + 1))
+        _ffi.check(_ffi.load().fmhip_mcmc_set_state(self._h, float(alpha), _ffi.ptr(lam), _ffi.ptr(mu)))
+
+    def reset_average(self):
+        _ffi.check(_ffi.load().fmhip_mcmc_reset_average(self._need()))
+
+    def _predictions(self):
+        if self.test is None:
+            raise RuntimeError("HipMCMC was made without a test set")
+        mean, last, draws = np.empty(self.test.size), np.empty(self.test.size), C.c_int64()
+        _ffi.check(_ffi.load().fmhip_mcmc_predictions(self._need(), _ffi.ptr(mean), _ffi.ptr(last), C.byref(draws)))
+        return mean, last, int(draws.value)
+
+    def predictions(self):
+        """The test rows' predictions averaged over the draws since the burn-in ended (or the last reset_average)."""
+        return self._predictions()[0]
+
+    def last_predictions(self):
+        """The test rows' predictions under the last draw (what ``fm.predict(test)`` gives in fp64)."""
+        return self._predictions()[1]
+
+    @property
+    def draws(self):
+        return self._predictions()[2]
+
+    def computeRMSE(self):
+        """RMSE of the averaged prediction against the test labels."""
+        mean = self.predictions()
+        return float(np.sqrt(np.mean((mean - self.test.y.astype(np.float64)) ** 2))) if len(mean) else 0.0
+
+    def close(self):
+        if self._h is not None:
+            _ffi.load().fmhip_mcmc_destroy(self._h)
+            self._h, self._for, self._keep = None, None, None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
