@@ -41,7 +41,8 @@
  *    pairs), and a test set without fp64 rows (fmhip_rows_create, multi-batch).  FMHIP_ERR_INVALID: a test set wider than the
  *    model, a prior that is not finite and > 0 (mu_0: finite; reg0: finite and >= 0).
  *  - determinism: bit-identical run to run for a given seed; the draws do not depend on the walk the sweep takes.
- * Not here: classification (the probit link), libFM's attribute groups, clipping to the label range, relational / weighted data.
+ * Classification (the probit link) and clipping to the label range: fmhip_mcmc_task.h, over this handle.
+ * Not here: libFM's attribute groups, relational / weighted data.
  */
 #ifndef FMHIP_MCMC_H
 #define FMHIP_MCMC_H

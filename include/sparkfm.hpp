@@ -13,7 +13,7 @@
 //     sparkfm::HipALS       S/fm/lib/ALS.scala:15-75,202-208 the reference's own learner in fp64 on the GPU
 //     sparkfm::FM           S/fm/FM.scala:25-33, S/fm/impl/FactorizationMachines.scala:30-51   the fit loop
 //
-// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC), include/fmhip_ranking.h (ranking evaluation), include/fmhip_weights.h (per-row example weights), include/fmhip_relational.h (relational data) and include/fmhip_mcmc.h (the MCMC learner) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
+// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC), include/fmhip_ranking.h (ranking evaluation), include/fmhip_weights.h (per-row example weights), include/fmhip_relational.h (relational data) include/fmhip_mcmc.h (the MCMC learner) and include/fmhip_mcmc_task.h (its tasks) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
 // here a non-zero status of the C ABI becomes sparkfm::Error carrying fmhip_last_error().  Parameters live on the host as in
 // the reference (public, mutable: `fm.w0`, `fm.w`, `fm.v` with v[f + i*k] = breeze's column-major DenseMatrix(k, n+1)); every
 // call that needs them on the device uploads them first, as jvm/HipSGD.scala does (the fit loop calls `learn` once per
@@ -38,6 +38,7 @@
 #include "fmhip_weights.h"
 #include "fmhip_relational.h"
 #include "fmhip_mcmc.h"
+#include "fmhip_mcmc_task.h"
 
 namespace sparkfm {
 
@@ -468,6 +469,10 @@ class HipALS : public FMLearn {
 // that must outlive the learner; nullptr: none), since the burn-in ended (the running average is reset once, after burn_in epochs).
 // opts (public: seed, sample, reg0, init_lambda, libFM's priors) are read when the handle is made — by the first learn for a
 // (model, dataset) pair; close() frees it, and must come before the dataset's device copy is dropped and used again.
+// task_opts (include/fmhip_mcmc_task.h; read with opts): task = FMHIP_MCMC_CLASSIFICATION trains on the probit link's latent targets
+// (latentTargets()), and predictions() / lastPredictions() are then probabilities Phi(yhat), scored by computeLogLoss() and
+// computeAccuracy() (computeRMSE() throws); the model holds the last draw, whose score is the probit score — not a logistic one.
+// Regression: clip + clip_lo / clip_hi clamp every draw's test prediction; clip_to_labels takes the train labels' min and max.
 class HipMCMC : public FMLearn {
   public:
     struct State {
@@ -476,14 +481,27 @@ class HipMCMC : public FMLearn {
         int64_t iterations = 0;
     };
     fmhip_mcmc_opts opts;
+    fmhip_mcmc_task_opts task_opts;
+    bool clip_to_labels = false;
     int64_t burn_in;
     fmhip_mcmc_stats last_stats{};
-    explicit HipMCMC(uint64_t seed = 0, DataSet *test = nullptr, int64_t burn_in_ = 0, bool sample = true) : burn_in(burn_in_), test_(test) {
+    explicit HipMCMC(uint64_t seed = 0, DataSet *test = nullptr, int64_t burn_in_ = 0, bool sample = true, int32_t task = FMHIP_MCMC_REGRESSION)
+        : burn_in(burn_in_), test_(test) {
         check(fmhip_mcmc_opts_default(&opts));
+        check(fmhip_mcmc_task_opts_default(&task_opts));
+        task_opts.task = task;
         opts.seed = seed;
         opts.sample = sample ? 1 : 0;
     }
-    static HipMCMC run(uint64_t seed = 0, DataSet *test = nullptr, int64_t burn_in = 0, bool sample = true) { return HipMCMC(seed, test, burn_in, sample); }
+    static HipMCMC run(uint64_t seed = 0, DataSet *test = nullptr, int64_t burn_in = 0, bool sample = true, int32_t task = FMHIP_MCMC_REGRESSION) {
+        return HipMCMC(seed, test, burn_in, sample, task);
+    }
+    void setClip(double lo, double hi) {            // regression: clamp every draw's test prediction to [lo, hi]
+        task_opts.clip = 1;
+        task_opts.clip_lo = lo;
+        task_opts.clip_hi = hi;
+        clip_to_labels = false;
+    }
     HipMCMC(const HipMCMC &) = delete;
     HipMCMC &operator=(const HipMCMC &) = delete;
     ~HipMCMC() override { (void)fmhip_mcmc_destroy(h_); }
@@ -494,7 +512,17 @@ class HipMCMC : public FMLearn {
         fmhip_dataset_t d = dataset.handle();
         if (h_ && (m != m_ || d != d_)) close();
         if (!h_) {
-            check(fmhip_mcmc_create(m, d, test_ ? test_->handle() : nullptr, &opts, &h_));
+            fmhip_mcmc_task_opts to = task_opts;
+            if (clip_to_labels) {
+                if (dataset.labels().empty()) throw Error(FMHIP_ERR_INVALID, "clip_to_labels needs a train set with rows");
+                const auto range = std::minmax_element(dataset.labels().begin(), dataset.labels().end());
+                to.clip = 1;
+                to.clip_lo = *range.first;
+                to.clip_hi = *range.second;
+            }
+            check(fmhip_mcmc_create_task(m, d, test_ ? test_->handle() : nullptr, &opts, &to, &h_));
+            n_train_ = dataset.size();
+            classification_ = to.task == FMHIP_MCMC_CLASSIFICATION;
             m_ = m;
             d_ = d;
             k_ = fm.num_factor;
@@ -543,7 +571,30 @@ class HipMCMC : public FMLearn {
         check(fmhip_mcmc_predictions(need(), nullptr, nullptr, &n));
         return n;
     }
-    double computeRMSE() {                          // of the averaged prediction against the test labels
+    std::vector<double> latentTargets() {           // the targets the last epoch trained on (regression, or no epoch yet: the labels)
+        std::vector<double> out((size_t)(h_ ? n_train_ : 0));
+        check(fmhip_mcmc_latent_targets(need(), out.data()));
+        return out;
+    }
+    double computeLogLoss() {                       // of the averaged probabilities against the test classes [y > 0]
+        const std::vector<double> p = probabilities("computeLogLoss");
+        double sum = 0.0;
+        for (size_t r = 0; r < p.size(); ++r) {
+            const double q = std::min(std::max(p[r], 1e-15), 1.0 - 1e-15);
+            sum -= test_->labels()[r] > 0 ? std::log(q) : std::log1p(-q);
+        }
+        return p.empty() ? 0.0 : sum / (double)p.size();
+    }
+    double computeAccuracy() {                      // the share of test rows whose averaged probability is on the label's side of 1/2
+        const std::vector<double> p = probabilities("computeAccuracy");
+        size_t hits = 0;
+        for (size_t r = 0; r < p.size(); ++r) hits += (p[r] > 0.5) == (test_->labels()[r] > 0);
+        return p.empty() ? 0.0 : (double)hits / (double)p.size();
+    }
+    double computeRMSE() {                          // of the averaged prediction against the test labels (regression)
+        need();
+        if (classification_)
+            throw Error(FMHIP_ERR_INVALID, "a classification run's predictions are probabilities: score them with computeLogLoss or computeAccuracy");
         const std::vector<double> mean = predictions();
         double sse = 0.0;
         for (size_t r = 0; r < mean.size(); ++r) sse += (mean[r] - test_->labels()[r]) * (mean[r] - test_->labels()[r]);
@@ -563,11 +614,18 @@ class HipMCMC : public FMLearn {
         if (!test_) throw Error(FMHIP_ERR_INVALID, "HipMCMC was made without a test set");
         return (size_t)test_->size();
     }
+    std::vector<double> probabilities(const char *what) {
+        need();
+        if (!classification_) throw Error(FMHIP_ERR_INVALID, std::string(what) + " scores a classification run's probabilities (see computeRMSE)");
+        return predictions();
+    }
     DataSet *test_;
     fmhip_mcmc_t h_ = nullptr;
     fmhip_model_t m_ = nullptr;
     fmhip_dataset_t d_ = nullptr;
     int32_t k_ = 0;
+    int64_t n_train_ = 0;
+    bool classification_ = false;
     bool pending_ = false;
     State pending_state_;
 };

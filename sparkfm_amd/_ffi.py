@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -61,6 +61,9 @@ RELATIONAL_SUM_CUT = 256   # FMHIP_RELATIONAL_SUM_CUT: a block row referenced by
 # ... and include/fmhip_mcmc.h — the MCMC learner: Bayesian FM by Gibbs sampling on the ALS column walk
 SYMBOLS_MCMC = ("fmhip_mcmc_opts_default", "fmhip_mcmc_create", "fmhip_mcmc_destroy", "fmhip_mcmc_epoch", "fmhip_mcmc_get_state",
                 "fmhip_mcmc_set_state", "fmhip_mcmc_reset_average", "fmhip_mcmc_predictions")
+# ... and include/fmhip_mcmc_task.h — its tasks: probit classification with truncated-normal targets, the regression clamp
+SYMBOLS_MCMC_TASK = ("fmhip_mcmc_task_opts_default", "fmhip_mcmc_create_task", "fmhip_mcmc_latent_targets")
+MCMC_REGRESSION, MCMC_CLASSIFICATION = 0, 1
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -268,6 +271,11 @@ class McmcOpts(C.Structure):
                 ("gamma_0", C.c_double), ("mu_0", C.c_double)]
 
 
+class McmcTaskOpts(C.Structure):
+    """fmhip_mcmc_task_opts (include/fmhip_mcmc_task.h)."""
+    _fields_ = [("task", C.c_int32), ("clip", C.c_int32), ("clip_lo", C.c_double), ("clip_hi", C.c_double)]
+
+
 class McmcStats(C.Structure):
     """fmhip_mcmc_stats (include/fmhip_mcmc.h)."""
     _fields_ = [("alpha", C.c_double), ("train_rmse", C.c_double), ("iterations", C.c_int64)]
@@ -437,8 +445,11 @@ def load():
     L.fmhip_mcmc_set_state.argtypes = [vp, dbl, vp, vp]
     L.fmhip_mcmc_reset_average.argtypes = [vp]
     L.fmhip_mcmc_predictions.argtypes = [vp, vp, vp, P(i64)]
+    L.fmhip_mcmc_task_opts_default.argtypes = [P(McmcTaskOpts)]
+    L.fmhip_mcmc_create_task.argtypes = [vp, vp, vp, P(McmcOpts), P(McmcTaskOpts), P(vp)]
+    L.fmhip_mcmc_latent_targets.argtypes = [vp, vp]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
-                 + SYMBOLS_RELATIONAL + SYMBOLS_MCMC):
+                 + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

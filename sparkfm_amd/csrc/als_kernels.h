@@ -48,6 +48,22 @@ struct McmcDev {
     int64_t zi;
 };
 
+// The probit link of a classification handle (include/fmhip_mcmc_task.h): k_mcmc_probit_targets stands where the epoch's first
+// residual pass stood and fills ystar — which AlsArgs.y points at for the whole epoch — from the labels' signs
+enum { kProbitStart = 0, kProbitSample = 1, kProbitMean = 2 };
+struct McmcProbit {
+    const double *labels;    // the dataset's own: the class is [y > 0]
+    double *ystar;           // [n_rows]
+    int32_t mode;            // kProbitStart: y* = +-1 (the handle's first epoch); kProbitSample: the truncated-normal draw; kProbitMean: its mean
+};
+
+// What a draw's test prediction becomes before it joins the running sum: itself, Phi of it, or itself clamped to [lo, hi]
+enum { kLinkNone = 0, kLinkProbit = 1, kLinkClamp = 2 };
+struct McmcLink {
+    int32_t kind = kLinkNone;
+    double lo = 0.0, hi = 0.0;
+};
+
 constexpr int kAlsMaxParts = 512;       // workgroups of a chip-wide column step
 // Columns of at least this many entries take the chip-wide two-launch step, shorter ones the one-workgroup walk
 // (FMHIP_ALS_LONG in the environment overrides it: a test / measurement knob)
@@ -64,13 +80,16 @@ constexpr int kMcmcSumParts = 64;       // workgroups (= partial sums the host a
 // The launches in front of the epoch's one host sync: the epoch's noise into z (= m.z; m.sample only; counter (id, group, t, stream)
 // under `seed`), the residuals e = yhat - y, and the sums the hyper-parameter draws need — sums[2 * (q * kMcmcSumParts + c)], + 1:
 // quantity q = 0 {sum e^2, -}, q = 1 + g {sum theta, sum (theta - m.hyp's mu_g)^2} over group g's trained parameters
-hipError_t launch_mcmc_begin(const AlsArgs &a, const McmcDev &m, double *z, uint64_t seed, uint32_t t, double *sums, hipStream_t s);
+// probit (nullable): the residual pass is k_mcmc_probit_targets' — a.y must be probit->ystar — with counter (row, attempt, t, 5)
+hipError_t launch_mcmc_begin(const AlsArgs &a, const McmcDev &m, double *z, uint64_t seed, uint32_t t, double *sums, hipStream_t s,
+                             const McmcProbit *probit = nullptr);
 // ... and behind it, with the new m.hyp on the device: the bias draw, the residuals again, q, the sweeps — launch_als_epoch's
 // plan (the same environment knobs), every step a draw
 hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
                               const int32_t *h_lev_cols, int n_levels, hipStream_t s);
 // The test rows' predictions under the parameters t.w0 / t.w / t.v into t.e (the last draw's), and sum[r] += t.e[r]: t holds the
-// test set's k, n_rows, row_ptr, col, val and, as y, n_rows zeros (k_als_residual's e = yhat - 0 is the prediction exactly)
-hipError_t launch_mcmc_accumulate(const AlsArgs &t, double *sum, hipStream_t s);
+// test set's k, n_rows, row_ptr, col, val and, as y, n_rows zeros (k_als_residual's e = yhat - 0 is the prediction exactly).
+// link: what the prediction becomes first, in t.e too (kLinkNone: the launch this always was)
+hipError_t launch_mcmc_accumulate(const AlsArgs &t, double *sum, hipStream_t s, const McmcLink &link = McmcLink{});
 
 }  // namespace fmhip

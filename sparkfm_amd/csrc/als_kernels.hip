@@ -84,30 +84,54 @@ __device__ __forceinline__ double bias_step(const AlsArgs &a, double w0, double 
     return DrawMcmc{m.hyp[0], a.reg0, 0.0, m.sample != 0}(w0, se, (double)a.n_rows, m.z[(int64_t)(a.k + 1) * a.n_cols]);
 }
 
-// ALS.precomputeTermE (S/fm/lib/ALS.scala:142-144) with FMModel.predict's exact order of operations
-// (S/fm/FMModel.scala:34-63): one thread per row, sequential sums in stored order.
+// FMModel.predict's exact order of operations (S/fm/FMModel.scala:34-63) for row r: sequential sums in stored order
+__device__ __forceinline__ double row_predict(const AlsArgs &a, int64_t r) {
+#pragma clang fp contract(off)
+    const int64_t p0 = a.row_ptr[r], p1 = a.row_ptr[r + 1];
+    double result = 0.0;
+    result += *a.w0;
+    if (p1 > p0) {
+        double lin = a.w[a.col[p0]] * a.val[p0];
+        for (int64_t p = p0 + 1; p < p1; ++p) lin += a.w[a.col[p]] * a.val[p];
+        result += lin;
+        for (int f = 0; f < a.k; ++f) {
+            double t = a.v[f + (int64_t)a.col[p0] * a.k] * a.val[p0];
+            double sum_f = t, sum_sqr_f = t * t;
+            for (int64_t p = p0 + 1; p < p1; ++p) {
+                t = a.v[f + (int64_t)a.col[p] * a.k] * a.val[p];
+                sum_f += t;
+                sum_sqr_f += t * t;
+            }
+            result += 0.5 * (sum_f * sum_f - sum_sqr_f);
+        }
+    }
+    return result;
+}
+
+// ALS.precomputeTermE (S/fm/lib/ALS.scala:142-144): one thread per row
 __global__ __launch_bounds__(256) void k_als_residual(AlsArgs a) {
 #pragma clang fp contract(off)
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < a.n_rows; r += (int64_t)gridDim.x * 256) a.e[r] = row_predict(a, r) - a.y[r];
+}
+
+// The probit link's latent targets (include/fmhip_mcmc_task.h), in the place of the epoch's first residual pass: per row the
+// forward, the target y* the whole epoch trains on — p.ystar, which a.y points at — and the residual e = yhat - y*.  The sign
+// s = +1 / -1 is that of the label's class [y > 0].  p.mode kProbitStart (the handle's first epoch): y* = s; kProbitSample:
+// y* = yhat + s z, z the row's own truncated normal (z > -s yhat; counter (row, attempt, t, kStreamTarget): no schedule enters it);
+// kProbitMean: z is that draw's expectation.  A wave waits for the lane with the most attempts — 64 at the most, by construction.
+__global__ __launch_bounds__(256) void k_mcmc_probit_targets(AlsArgs a, McmcProbit p, uint64_t seed, uint32_t t) {
+#pragma clang fp contract(off)
     for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < a.n_rows; r += (int64_t)gridDim.x * 256) {
-        const int64_t p0 = a.row_ptr[r], p1 = a.row_ptr[r + 1];
-        double result = 0.0;
-        result += *a.w0;
-        if (p1 > p0) {
-            double lin = a.w[a.col[p0]] * a.val[p0];
-            for (int64_t p = p0 + 1; p < p1; ++p) lin += a.w[a.col[p]] * a.val[p];
-            result += lin;
-            for (int f = 0; f < a.k; ++f) {
-                double t = a.v[f + (int64_t)a.col[p0] * a.k] * a.val[p0];
-                double sum_f = t, sum_sqr_f = t * t;
-                for (int64_t p = p0 + 1; p < p1; ++p) {
-                    t = a.v[f + (int64_t)a.col[p] * a.k] * a.val[p];
-                    sum_f += t;
-                    sum_sqr_f += t * t;
-                }
-                result += 0.5 * (sum_f * sum_f - sum_sqr_f);
-            }
+        const double yhat = row_predict(a, r);
+        const double s = p.labels[r] > 0.0 ? 1.0 : -1.0;
+        double target = s;
+        if (p.mode != kProbitStart) {
+            const double lo = -s * yhat;
+            const double z = p.mode == kProbitSample ? rng::truncated_normal(seed, (uint32_t)r, t, lo, nullptr) : rng::truncated_normal_mean(lo);
+            target = yhat + s * z;
         }
-        a.e[r] = result - a.y[r];
+        p.ystar[r] = target;
+        a.e[r] = yhat - target;
     }
 }
 
@@ -115,6 +139,24 @@ __global__ __launch_bounds__(256) void k_als_residual(AlsArgs a) {
 // launched on the test rows with labels of zero, e = yhat - 0 is yhat exactly — written to `last`; this adds them to the running sum.
 __global__ __launch_bounds__(256) void k_mcmc_accumulate(const double *last, double *sum, int64_t n_rows) {
     for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * 256) sum[r] += last[r];
+}
+
+// ... and what a draw's prediction becomes before it joins the sum and `last` under a task (include/fmhip_mcmc_task.h): the
+// probability Phi(yhat) of the probit link, or the score clamped to the range the caller gave
+struct LinkProbit {
+    __device__ __forceinline__ double operator()(double yhat) const { return rng::normal_cdf(yhat); }
+};
+struct LinkClamp {
+    double lo, hi;
+    __device__ __forceinline__ double operator()(double yhat) const { return yhat < lo ? lo : yhat > hi ? hi : yhat; }
+};
+template <class Link>
+__global__ __launch_bounds__(256) void k_mcmc_accumulate_link(double *last, double *sum, int64_t n_rows, Link link) {
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * 256) {
+        const double p = link(last[r]);
+        last[r] = p;
+        sum[r] += p;
+    }
 }
 
 // fixed-order block sum of two doubles; result valid in every thread
@@ -652,13 +694,17 @@ hipError_t launch_als_epoch(const AlsArgs &a, const int32_t *h_cfeat, const int3
     return epoch_tail(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, s);
 }
 
-hipError_t launch_mcmc_begin(const AlsArgs &a, const McmcDev &m, double *z, uint64_t seed, uint32_t t, double *sums, hipStream_t s) {
+hipError_t launch_mcmc_begin(const AlsArgs &a, const McmcDev &m, double *z, uint64_t seed, uint32_t t, double *sums, hipStream_t s,
+                             const McmcProbit *probit) {
     if (m.sample) {
         int64_t nb = ((int64_t)(a.k + 1) * a.n_cols + 1 + 255) / 256;
         if (nb > 4096) nb = 4096;
         hipLaunchKernelGGL(k_mcmc_noise, dim3((unsigned)nb), dim3(256), 0, s, a, z, seed, t);
     }
-    hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a);
+    if (probit)
+        hipLaunchKernelGGL(k_mcmc_probit_targets, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a, *probit, seed, t);
+    else
+        hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_mcmc_sums, dim3((unsigned)((a.k + 2) * kMcmcSumParts)), dim3(kSumsBlock), 0, s, a, m, sums, kMcmcSumParts);
     return hipGetLastError();
 }
@@ -668,10 +714,16 @@ hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcDev &m, const int32_t 
     return epoch_tail(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, s, m);
 }
 
-hipError_t launch_mcmc_accumulate(const AlsArgs &t, double *sum, hipStream_t s) {
+hipError_t launch_mcmc_accumulate(const AlsArgs &t, double *sum, hipStream_t s, const McmcLink &link) {
     if (t.n_rows < 1) return hipSuccess;
     hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(t.n_rows)), dim3(256), 0, s, t);
-    hipLaunchKernelGGL(k_mcmc_accumulate, dim3(row_blocks(t.n_rows)), dim3(256), 0, s, t.e, sum, t.n_rows);
+    const dim3 grid(row_blocks(t.n_rows)), block(256);
+    if (link.kind == kLinkProbit)
+        hipLaunchKernelGGL(k_mcmc_accumulate_link<LinkProbit>, grid, block, 0, s, t.e, sum, t.n_rows, LinkProbit{});
+    else if (link.kind == kLinkClamp)
+        hipLaunchKernelGGL(k_mcmc_accumulate_link<LinkClamp>, grid, block, 0, s, t.e, sum, t.n_rows, LinkClamp{link.lo, link.hi});
+    else
+        hipLaunchKernelGGL(k_mcmc_accumulate, grid, block, 0, s, t.e, sum, t.n_rows);
     return hipGetLastError();
 }
 

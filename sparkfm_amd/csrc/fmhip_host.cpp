@@ -779,5 +779,16 @@ void mcmc_draw_group(uint64_t seed, uint32_t t, uint32_t g, const McmcPriors &p,
     *mu = (sum_theta + p.gamma_0 * p.mu_0) / w + rng::normal(seed, 0, g, t, rng::kStreamMu) / sqrt(w * *lambda);
 }
 
+double mcmc_truncated_normal(uint64_t seed, uint32_t row, uint32_t t, double a, int *attempts) { return rng::truncated_normal(seed, row, t, a, attempts); }
+double mcmc_truncated_mean(double a) { return rng::truncated_normal_mean(a); }
+
+const char *mcmc_bad_task(int32_t task, int32_t clip, double clip_lo, double clip_hi) {
+    if (task != 0 && task != 1) return "unknown task (FMHIP_MCMC_REGRESSION = 0, FMHIP_MCMC_CLASSIFICATION = 1)";
+    if (!clip) return nullptr;
+    if (task == 1) return "clip goes with the regression task: a classification handle's predictions are probabilities";
+    if (!(std::isfinite(clip_lo) && std::isfinite(clip_hi) && clip_lo < clip_hi)) return "the clip range must be finite with clip_lo < clip_hi";
+    return nullptr;
+}
+
 }  // namespace host
 }  // namespace fmhip

@@ -203,6 +203,14 @@ double mcmc_draw_alpha(uint64_t seed, uint32_t t, const McmcPriors &p, int64_t n
 // mu ~ N((sum_theta + gamma_0 mu_0) / (m + gamma_0), 1 / ((m + gamma_0) lambda)) = mean + z / sqrt((m + gamma_0) lambda)
 void mcmc_draw_group(uint64_t seed, uint32_t t, uint32_t g, const McmcPriors &p, int64_t m, double sum_theta, double sum_dev2, double mu_old,
                      double *lambda, double *mu);
+// ---- ... and its tasks (include/fmhip_mcmc_task.h) ----
+// the probit link's latent draw of a row: z ~ N(0,1) given z > a, counter (row, attempt, t, stream 5); attempts: nullable
+double mcmc_truncated_normal(uint64_t seed, uint32_t row, uint32_t t, double a, int *attempts);
+// ... and its expectation E[z | z > a] (the epoch without sampling)
+double mcmc_truncated_mean(double a);
+// nullptr, or why (task, clip, [clip_lo, clip_hi]) is refused: an unknown task, a clip with the classification task, a clip
+// range that is not finite with lo < hi
+const char *mcmc_bad_task(int32_t task, int32_t clip, double clip_lo, double clip_hi);
 
 }  // namespace host
 }  // namespace fmhip

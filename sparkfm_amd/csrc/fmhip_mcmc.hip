@@ -5,10 +5,13 @@
 //     host: alpha, every lambda_g and mu_g (fmhip_host.cpp: mcmc_draw_alpha / mcmc_draw_group) -> hyp
 //     the bias draw, the residuals again, q, the sweeps: launch_als_epoch's plan with the draw in computeTheta's place
 //     k_als_residual over the test rows (labels of zero) + k_mcmc_accumulate -> the parameters back into the model
+// A classification handle (include/fmhip_mcmc_task.h) differs in three places: k_mcmc_probit_targets stands where the first
+// k_als_residual stood and fills the latent targets ystar, which the walk's y points at for the whole epoch; alpha is not drawn;
+// the test rows' accumulation takes Phi of the score (a regression handle with a clip: the clamp).
 // The kernels are in als_kernels.hip, the generator in mcmc_rng.h.
 #include "fmhip_internal.h"
 #include "als_kernels.h"
-#include "../../include/fmhip_mcmc.h"
+#include "../../include/fmhip_mcmc_task.h"
 
 #include <algorithm>
 #include <cmath>
@@ -22,6 +25,8 @@ struct fmhip_mcmc {
     fmhip_model_t m = nullptr;
     fmhip_dataset_t train = nullptr, test = nullptr;
     fmhip_mcmc_opts opts{};
+    int32_t task = FMHIP_MCMC_REGRESSION;
+    McmcLink link;                          // what a draw's test prediction becomes before it joins the sum
     McmcPriors priors;
     int32_t k = 0;
     int64_t n_trained = 0;                  // |T|: the column slots with id < num_attribute
@@ -29,6 +34,7 @@ struct fmhip_mcmc {
     std::vector<double> lambda, mu;         // [k + 1]
     int64_t iterations = 0, draws = 0;
     DevBuf<double> z, hyp, sums;            // the epoch's noise; {alpha, lambda, mu}; k_mcmc_sums' partials
+    DevBuf<double> ystar;                   // classification: the latent targets the last epoch trained on [train rows]
     DevBuf<double> test_sum, test_last, test_zero;     // [test rows]: the running sum, the last draw's predictions, zeros
     std::vector<double> h_sums, h_hyp;
 };
@@ -55,18 +61,9 @@ int check_test(fmhip_model_t m, fmhip_dataset_t test) {
     return FMHIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int fmhip_mcmc_opts_default(fmhip_mcmc_opts *opts) {
-    if (!opts) return fail(FMHIP_ERR_INVALID, "opts is NULL");
-    const McmcPriors p;
-    *opts = fmhip_mcmc_opts{0, 1, 0.0, 1.0, p.alpha_0, p.beta_0, p.alpha_lambda, p.beta_lambda, p.gamma_0, p.mu_0};
-    return FMHIP_OK;
-}
-
-int fmhip_mcmc_create(fmhip_model_t m, fmhip_dataset_t train, fmhip_dataset_t test, const fmhip_mcmc_opts *opts, fmhip_mcmc_t *out) {
+// fmhip_mcmc_create (task_opts NULL) and fmhip_mcmc_create_task
+int create(fmhip_model_t m, fmhip_dataset_t train, fmhip_dataset_t test, const fmhip_mcmc_opts *opts, const fmhip_mcmc_task_opts *task_opts,
+           fmhip_mcmc_t *out) {
     if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
     *out = nullptr;
     fmhip_mcmc_opts o;
@@ -75,6 +72,9 @@ int fmhip_mcmc_create(fmhip_model_t m, fmhip_dataset_t train, fmhip_dataset_t te
     const McmcPriors pri{o.alpha_0, o.beta_0, o.alpha_lambda, o.beta_lambda, o.gamma_0, o.mu_0};
     if (const char *bad = mcmc_bad_setting(pri, o.reg0, o.init_lambda))
         return fail(FMHIP_ERR_INVALID, "%s must be finite and > 0 (mu_0: finite; reg0: finite and >= 0)", bad);
+    fmhip_mcmc_task_opts to{FMHIP_MCMC_REGRESSION, 0, 0.0, 0.0};
+    if (task_opts) to = *task_opts;
+    if (const char *bad = mcmc_bad_task(to.task, to.clip, to.clip_lo, to.clip_hi)) return fail(FMHIP_ERR_INVALID, "%s", bad);
     if (!m || !train) return fail(FMHIP_ERR_INVALID, "model or train set is NULL");
     ReadLock lock(m);
     TRY(als_check(m, train));
@@ -87,6 +87,9 @@ int fmhip_mcmc_create(fmhip_model_t m, fmhip_dataset_t train, fmhip_dataset_t te
     s->test = test;
     s->opts = o;
     s->priors = pri;
+    s->task = to.task;
+    if (to.task == FMHIP_MCMC_CLASSIFICATION) s->link.kind = kLinkProbit;
+    else if (to.clip) s->link = McmcLink{kLinkClamp, to.clip_lo, to.clip_hi};
     s->k = m->k;
     const size_t k1 = (size_t)m->k + 1;
     s->lambda.assign(k1, o.init_lambda);
@@ -100,6 +103,7 @@ int fmhip_mcmc_create(fmhip_model_t m, fmhip_dataset_t train, fmhip_dataset_t te
     TRY(s->hyp.alloc(s->h_hyp.size()));
     TRY(s->sums.alloc(s->h_sums.size()));
     HIP_TRY(hipMemset(s->z.p, 0, nz * sizeof(double)));
+    if (s->task == FMHIP_MCMC_CLASSIFICATION) TRY(s->ystar.alloc((size_t)std::max<int64_t>(train->n_rows, 1)));
     if (test) {
         const size_t nt = (size_t)std::max<int64_t>(test->n_rows, 1);
         TRY(s->test_sum.alloc(nt));
@@ -111,6 +115,32 @@ int fmhip_mcmc_create(fmhip_model_t m, fmhip_dataset_t train, fmhip_dataset_t te
     }
     *out = guard.release();
     return FMHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmhip_mcmc_opts_default(fmhip_mcmc_opts *opts) {
+    if (!opts) return fail(FMHIP_ERR_INVALID, "opts is NULL");
+    const McmcPriors p;
+    *opts = fmhip_mcmc_opts{0, 1, 0.0, 1.0, p.alpha_0, p.beta_0, p.alpha_lambda, p.beta_lambda, p.gamma_0, p.mu_0};
+    return FMHIP_OK;
+}
+
+int fmhip_mcmc_task_opts_default(fmhip_mcmc_task_opts *task_opts) {
+    if (!task_opts) return fail(FMHIP_ERR_INVALID, "task_opts is NULL");
+    *task_opts = fmhip_mcmc_task_opts{FMHIP_MCMC_REGRESSION, 0, 0.0, 0.0};
+    return FMHIP_OK;
+}
+
+int fmhip_mcmc_create(fmhip_model_t m, fmhip_dataset_t train, fmhip_dataset_t test, const fmhip_mcmc_opts *opts, fmhip_mcmc_t *out) {
+    return create(m, train, test, opts, nullptr, out);
+}
+
+int fmhip_mcmc_create_task(fmhip_model_t m, fmhip_dataset_t train, fmhip_dataset_t test, const fmhip_mcmc_opts *opts,
+                           const fmhip_mcmc_task_opts *task_opts, fmhip_mcmc_t *out) {
+    return create(m, train, test, opts, task_opts, out);
 }
 
 int fmhip_mcmc_destroy(fmhip_mcmc_t s) {
@@ -129,17 +159,20 @@ int fmhip_mcmc_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats) {
     AlsArgs a{};
     TRY(als_begin(m, d, s->opts.reg0, 0.0, 0.0, &a));       // (what the handle was created for may have changed: checked again)
     const int k1 = s->k + 1, P = kMcmcSumParts;
+    const bool probit = s->task == FMHIP_MCMC_CLASSIFICATION;
     const uint32_t t = (uint32_t)s->iterations;
     double sse = 0.0;
     if (d->n_rows > 0) {
         const McmcDev dev{s->hyp.p, s->z.p, s->opts.sample ? 1 : 0, 0};
         TRY(upload_state(s));                                // the means the sums are taken around
-        HIP_TRY(launch_mcmc_begin(a, dev, s->z.p, s->opts.seed, t, s->sums.p, m->stream));
+        const McmcProbit targets{d->y64.p, s->ystar.p, s->iterations == 0 ? kProbitStart : dev.sample ? kProbitSample : kProbitMean};
+        if (probit) a.y = s->ystar.p;                        // the whole epoch trains on the latent targets
+        HIP_TRY(launch_mcmc_begin(a, dev, s->z.p, s->opts.seed, t, s->sums.p, m->stream, probit ? &targets : nullptr));
         HIP_TRY(hipMemcpyAsync(s->h_sums.data(), s->sums.p, s->h_sums.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
         HIP_TRY(hipStreamSynchronize(m->stream));
         for (int c = 0; c < P; ++c) sse += s->h_sums[2 * (size_t)c];
         if (dev.sample) {
-            s->alpha = mcmc_draw_alpha(s->opts.seed, t, s->priors, d->n_rows, sse);
+            if (!probit) s->alpha = mcmc_draw_alpha(s->opts.seed, t, s->priors, d->n_rows, sse);   // (the probit link: alpha stays what the state holds)
             for (int g = 0; g < k1; ++g) {
                 double sum_theta = 0.0, sum_dev2 = 0.0;
                 for (int c = 0; c < P; ++c) {
@@ -167,7 +200,7 @@ int fmhip_mcmc_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats) {
         ta.v = m->als_v.p;
         ta.y = s->test_zero.p;
         ta.e = s->test_last.p;
-        HIP_TRY(launch_mcmc_accumulate(ta, s->test_sum.p, m->stream));
+        HIP_TRY(launch_mcmc_accumulate(ta, s->test_sum.p, m->stream, s->link));
     }
     TRY(als_end(m));
     ++s->iterations;
@@ -227,6 +260,16 @@ int fmhip_mcmc_predictions(fmhip_mcmc_t s, double *mean, double *last, int64_t *
     if (mean)
         for (size_t r = 0; r < n; ++r) mean[r] = s->draws > 0 ? mean[r] / (double)s->draws : 0.0;
     if (draws) *draws = s->draws;
+    return FMHIP_OK;
+}
+
+int fmhip_mcmc_latent_targets(fmhip_mcmc_t s, double *out) {
+    if (!s || !out) return fail(FMHIP_ERR_INVALID, "the MCMC handle or out is NULL");
+    ReadLock lock(s->m);
+    TRY(set_device(s->m->device));
+    const size_t n = (size_t)s->train->n_rows;
+    const bool drawn = s->task == FMHIP_MCMC_CLASSIFICATION && s->iterations > 0;
+    if (n) HIP_TRY(hipMemcpy(out, drawn ? s->ystar.p : s->train->y64.p, n * sizeof(double), hipMemcpyDeviceToHost));
     return FMHIP_OK;
 }
 

@@ -1,6 +1,7 @@
 // mcmc_rng.h — the counter-based random numbers of the MCMC learner (include/fmhip_mcmc.h), shared by the host arithmetic
 // (fmhip_host.cpp) and the noise kernel (als_kernels.hip): Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random
-// numbers: as easy as 1, 2, 3", SC 2011) and the two variates derived from one block of it.  Integer arithmetic only up
+// numbers: as easy as 1, 2, 3", SC 2011), the two variates derived from one block of it, and the probit link's truncated
+// normal (include/fmhip_mcmc_task.h), a bounded rejection loop over blocks of a stream of its own.  Integer arithmetic only up
 // to u53; log / cos / sqrt are the caller's libm (host) or the device's (kernel), so host and device normals agree to a
 // few ulp, not bit for bit.  No HIP header: g++ compiles it for the sanitizer harnesses.
 #pragma once
@@ -17,7 +18,7 @@ namespace fmhip {
 namespace rng {
 
 // the streams of a counter (index, group, t, stream): what a draw is for
-enum { kStreamCoord = 0, kStreamW0 = 1, kStreamAlpha = 2, kStreamLambda = 3, kStreamMu = 4 };
+enum { kStreamCoord = 0, kStreamW0 = 1, kStreamAlpha = 2, kStreamLambda = 3, kStreamMu = 4, kStreamTarget = 5 };
 
 struct Block { uint32_t x[4]; };
 
@@ -57,6 +58,52 @@ FMHIP_RNG_FN double normal(uint64_t seed, uint32_t index, uint32_t group, uint32
     const Block b = block_of(seed, index, group, t, stream);
     return sqrt(-2.0 * log(u53(b.x[0], b.x[1]))) * cos(6.283185307179586 * u53(b.x[2], b.x[3]));
 }
+
+// ---- the probit link's latent target (include/fmhip_mcmc_task.h) ----------------------------------------------------------------
+constexpr int kTruncMaxAttempts = 64;
+
+// z ~ N(0,1) conditioned on z > a, by rejection: attempt j = 0, 1, ... takes the block of counter (row, j, t, kStreamTarget),
+// u1 = u53(x0, x1), u2 = u53(x2, x3).  a <= 0: the block's normal, accepted if z > a (at least every second attempt is);
+// a > 0: Robert's exponential proposal (C. P. Robert, "Simulation of truncated normal variables", 1995), z = a - ln(u1) / l with
+// l = (a + sqrt(a^2 + 4)) / 2, accepted if u2 <= exp(-(z - l)^2 / 2) (at least 0.76 of the attempts are).  The last attempt's
+// proposal is taken unconditionally (a <= 0: as |z|, which is > a), so the loop is bounded whatever a holds — a NaN included.
+// *attempts (nullable): how many blocks the draw took.  No fused multiply-add.
+FMHIP_RNG_FN double truncated_normal(uint64_t seed, uint32_t row, uint32_t t, double a, int *attempts) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double l = (a + sqrt(a * a + 4.0)) / 2.0;
+    double z = 0.0;
+    int j = 0;
+    for (; j < kTruncMaxAttempts; ++j) {
+        const Block b = block_of(seed, row, (uint32_t)j, t, kStreamTarget);
+        const double u1 = u53(b.x[0], b.x[1]), u2 = u53(b.x[2], b.x[3]);
+        if (a <= 0.0) {
+            z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+            if (z > a) break;
+            if (j == kTruncMaxAttempts - 1) z = fabs(z);
+        } else {
+            z = a - log(u1) / l;
+            const double d = z - l;
+            if (u2 <= exp(-0.5 * (d * d))) break;
+        }
+    }
+    if (attempts) *attempts = j < kTruncMaxAttempts ? j + 1 : kTruncMaxAttempts;
+    return z;
+}
+
+// E[z | z > a] for z ~ N(0,1): phi(a) / Q(a), Q(a) = erfc(a / sqrt 2) / 2.  Past a = 30 both terms head for the subnormals and the
+// asymptote a + 1 / a takes over (it is 2 / a^3 above the quotient there: 3e-6 relative)
+FMHIP_RNG_FN double truncated_normal_mean(double a) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    if (a > 30.0) return a + 1.0 / a;
+    return exp(-0.5 * (a * a)) * 0.3989422804014327 / (0.5 * erfc(a / 1.4142135623730951));
+}
+
+// Phi(x) = erfc(-x / sqrt 2) / 2: the probability a probit score stands for
+FMHIP_RNG_FN double normal_cdf(double x) { return 0.5 * erfc(-x / 1.4142135623730951); }
 
 }  // namespace rng
 }  // namespace fmhip

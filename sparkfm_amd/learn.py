@@ -116,13 +116,39 @@ class HipMCMC(FMLearn):
     once, after that many epochs.  `sample=False`: no draws at all — the conditional means under the state as set (with alpha = 1,
     mu = 0, lambda = (regw, regv ...) that is ``HipALS``, bit for bit).  Priors (libFM's defaults): reg0 = 0, init_lambda = 1,
     alpha_0 = beta_0 = alpha_lambda = beta_lambda = gamma_0 = 1, mu_0 = 0.  The handle is made on the first ``learn`` for a
-    (model, dataset) pair and remade when either changes; ``close()`` frees it.  Needs a single-batch DataSet like ``HipALS``."""
+    (model, dataset) pair and remade when either changes; ``close()`` frees it.  Needs a single-batch DataSet like ``HipALS``.
+
+    `task` (include/fmhip_mcmc_task.h): "regression", or "classification" — binary labels [y > 0] by the probit link: every epoch
+    trains on latent targets drawn from truncated normals (``latent_targets()``), alpha stays 1, and ``predictions()`` /
+    ``last_predictions()`` are PROBABILITIES Phi(yhat), scored by ``computeLogLoss()``, ``computeAccuracy()`` and ``computeAUC()``
+    (``computeRMSE()`` raises).  Afterwards `fm` is the last draw and ``fm.predict`` its probit score: the probability is Phi(yhat),
+    not the logistic sigmoid, so ``FMModel.computeAUC`` and ``computeAccuracy`` apply to it and ``FMModel.computeLogLoss`` does not.
+    `clip` (regression only): None, (lo, hi), or "labels" — the train labels' min and max, taken when the handle is made: every
+    draw's test prediction is clamped to that range before it is averaged (libFM's way; off unless asked for)."""
 
     PRIORS = ("reg0", "init_lambda", "alpha_0", "beta_0", "alpha_lambda", "beta_lambda", "gamma_0", "mu_0")
 
-    def __init__(self, seed=0, test=None, burn_in=0, sample=True, **priors):
+    TASKS = {"regression": _ffi.MCMC_REGRESSION, "classification": _ffi.MCMC_CLASSIFICATION}
+
+    def __init__(self, seed=0, test=None, burn_in=0, sample=True, task="regression", clip=None, **priors):
         import math
         import operator
+        if not isinstance(task, str) or task not in self.TASKS:
+            raise ValueError("task must be 'regression' or 'classification', not %r" % (task,))
+        self.task = task
+        if clip is not None and task == "classification":
+            raise ValueError("clip goes with task='regression': a classification run's predictions are probabilities")
+        if clip is not None and not (isinstance(clip, str) and clip == "labels"):
+            try:
+                if isinstance(clip, str):
+                    raise TypeError
+                lo, hi = clip
+                clip = (float(lo), float(hi))
+            except (TypeError, ValueError):
+                raise ValueError("clip must be None, (lo, hi) or 'labels', not %r" % (clip,)) from None
+            if not (math.isfinite(clip[0]) and math.isfinite(clip[1]) and clip[0] < clip[1]):
+                raise ValueError("the clip range must be finite with lo < hi, not %r" % (clip,))
+        self.clip = clip
         self.seed = operator.index(seed)
         if not 0 <= self.seed < 2 ** 64:
             raise ValueError("seed must be in [0, 2^64), not %r" % (seed,))
@@ -153,8 +179,8 @@ class HipMCMC(FMLearn):
         self.last_stats = None
 
     @classmethod
-    def run(cls, seed=0, test=None, burn_in=0, sample=True, **priors):
-        return cls(seed=seed, test=test, burn_in=burn_in, sample=sample, **priors)
+    def run(cls, seed=0, test=None, burn_in=0, sample=True, task="regression", clip=None, **priors):
+        return cls(seed=seed, test=test, burn_in=burn_in, sample=sample, task=task, clip=clip, **priors)
 
     def _handle(self, fm, dataset):
         L = _ffi.load()
@@ -164,8 +190,15 @@ class HipMCMC(FMLearn):
         if self._h is None:
             opts = _ffi.McmcOpts(self.seed, 1 if self.sample else 0, *[self.priors[n] for n in self.PRIORS])
             h = C.c_void_p()
-            _ffi.check(L.fmhip_mcmc_create(mh, dh, None if self.test is None else self.test.handle, C.byref(opts), C.byref(h)))
-            self._h, self._for, self._k = h, (mh.value, dh.value), fm.num_factor
+            clip = self.clip
+            if clip == "labels":
+                y = np.asarray(dataset.y, np.float64)
+                if not len(y):
+                    raise ValueError("clip='labels' needs a train set with rows")
+                clip = (float(y.min()), float(y.max()))
+            task = _ffi.McmcTaskOpts(self.TASKS[self.task], 0 if clip is None else 1, *(clip or (0.0, 0.0)))
+            _ffi.check(L.fmhip_mcmc_create_task(mh, dh, None if self.test is None else self.test.handle, C.byref(opts), C.byref(task), C.byref(h)))
+            self._h, self._for, self._k, self._n_train = h, (mh.value, dh.value), fm.num_factor, dataset.size
             self._keep = (fm, dataset)      # the handle borrows both
             if self._pending_state is not None:
                 self.state = self._pending_state
@@ -235,8 +268,39 @@ class HipMCMC(FMLearn):
     def draws(self):
         return self._predictions()[2]
 
+    def latent_targets(self):
+        """The targets the last epoch trained on, one per train row: a classification run's y* (the label's sign times a truncated
+        normal around the row's score; +-1 in the first epoch); the labels on a regression run and before the first epoch."""
+        out = np.empty(self._n_train if self._h is not None else 0)
+        _ffi.check(_ffi.load().fmhip_mcmc_latent_targets(self._need(), _ffi.ptr(out)))
+        return out
+
+    def _classes(self, what):
+        if self.task != "classification":
+            raise ValueError("%s scores a classification run's probabilities: this run's task is %r (see computeRMSE)" % (what, self.task))
+        return self.predictions(), np.asarray(self.test.y) > 0
+
+    def computeLogLoss(self):
+        """Mean log-loss of the averaged probabilities against the test classes [y > 0] (probabilities kept 1e-15 away from 0 and 1)."""
+        p, t = self._classes("computeLogLoss")
+        p = np.clip(p, 1e-15, 1.0 - 1e-15)
+        return float(-np.mean(np.where(t, np.log(p), np.log1p(-p)))) if len(p) else 0.0
+
+    def computeAccuracy(self):
+        """Share of the test rows whose averaged probability is on the label's side of 1/2."""
+        p, t = self._classes("computeAccuracy")
+        return float(np.mean((p > 0.5) == t)) if len(p) else 0.0
+
+    def computeAUC(self):
+        """ROC AUC of the averaged probabilities against the test classes (``sparkfm_amd.metrics.auc``)."""
+        from . import metrics
+        p, t = self._classes("computeAUC")
+        return metrics.auc(p, t.astype(np.float32), device=self.test.device)["auc"]
+
     def computeRMSE(self):
-        """RMSE of the averaged prediction against the test labels."""
+        """RMSE of the averaged prediction against the test labels (regression)."""
+        if self.task == "classification":
+            raise ValueError("a classification run's predictions are probabilities: score them with computeLogLoss, computeAccuracy or computeAUC")
         mean = self.predictions()
         return float(np.sqrt(np.mean((mean - self.test.y.astype(np.float64)) ** 2))) if len(mean) else 0.0
 

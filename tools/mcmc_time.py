@@ -5,7 +5,11 @@ LDS walk), a long-column shape of bench.als_long (the chip-wide two-launch step)
 rows (the level schedule).  Both calls are synchronous (they end with the parameters back on the host), so an epoch is the wall time
 of its call.
 
-    python tools/mcmc_time.py [--reps 9] [--shapes c1,long,fields] [--parent-lib PATH] [--out FILE]
+    python tools/mcmc_time.py [--reps 9] [--shapes c1,long,fields] [--task regression|classification|both] [--parent-lib PATH] [--out FILE]
+
+--task classification / both: the classification epoch (fmhip_mcmc_create_task, the probit link: labels cut at their median, a
+truncated-normal draw per row in front of the sweeps) is timed too, as a third series alternating with the other two on a model of
+its own.
 
 --parent-lib: another build of libfmhip.so (the parent commit's) — its fmhip_als_epoch is timed in the same process, alternating
 parent / this / parent-again / this-again on four models of their own, so that "this against the parent" can be read beside "the
@@ -40,6 +44,8 @@ def bind(path):
         L.fmhip_mcmc_create.argtypes = [vp, vp, vp, vp, P(vp)]
         L.fmhip_mcmc_epoch.argtypes = [vp, vp]
         L.fmhip_mcmc_destroy.argtypes = [vp]
+    if hasattr(L, "fmhip_mcmc_create_task"):
+        L.fmhip_mcmc_create_task.argtypes = [vp, vp, vp, vp, vp, P(vp)]
     return L
 
 
@@ -52,11 +58,15 @@ def ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-class Run:
-    """One model + its own dataset handle in library L."""
+class TaskOpts(C.Structure):
+    _fields_ = [("task", C.c_int32), ("clip", C.c_int32), ("clip_lo", C.c_double), ("clip_hi", C.c_double)]
 
-    def __init__(self, L, d, n, k, init):
-        self.L, self.m, self.d, self.s = L, C.c_void_p(), C.c_void_p(), None
+
+class Run:
+    """One model + its own dataset handle in library L; classification: the MCMC handle is made with the probit task."""
+
+    def __init__(self, L, d, n, k, init, classification=False):
+        self.L, self.m, self.d, self.s, self.classification = L, C.c_void_p(), C.c_void_p(), None, classification
         ok(L, L.fmhip_dataset_create(0, len(d["row_ptr"]) - 1, ptr(d["row_ptr"]), ptr(d["col"]), ptr(d["val"]), ptr(d["y"]), 0, C.byref(self.d)))
         ok(L, L.fmhip_model_create(0, n, k, None, C.byref(self.m)))
         ok(L, L.fmhip_model_set_params(self.m, init[0], ptr(init[1]), ptr(init[2])))
@@ -69,7 +79,10 @@ class Run:
     def mcmc(self):
         if self.s is None:
             self.s = C.c_void_p()
-            ok(self.L, self.L.fmhip_mcmc_create(self.m, self.d, None, None, C.byref(self.s)))
+            if self.classification:
+                ok(self.L, self.L.fmhip_mcmc_create_task(self.m, self.d, None, None, C.byref(TaskOpts(1, 0, 0.0, 0.0)), C.byref(self.s)))
+            else:
+                ok(self.L, self.L.fmhip_mcmc_create(self.m, self.d, None, None, C.byref(self.s)))
         t = time.perf_counter()
         ok(self.L, self.L.fmhip_mcmc_epoch(self.s, None))
         return (time.perf_counter() - t) * 1e3
@@ -111,6 +124,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--shapes", default="c1,long,fields")
+    ap.add_argument("--task", default="regression", choices=["regression", "classification", "both"])
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -129,13 +143,24 @@ def main():
         rec = {"workload": what}
         # ---- MCMC beside ALS, this library, alternating (one warm-up epoch each: allocations)
         a, b = Run(this, d, n, k, init), Run(this, d, n, k, init)
+        c = None
+        if args.task != "regression":
+            cut = dict(d, y=np.ascontiguousarray(d["y"] > np.median(d["y"]), np.float64))
+            c = Run(this, cut, n, k, init, classification=True)
+            c.mcmc()                                                       # (epoch 0 trains on +-1: every timed epoch draws)
         a.als(), b.mcmc()
-        als, mcmc = [], []
+        als, mcmc, probit = [], [], []
         for _ in range(args.reps):
             als.append(a.als())
             mcmc.append(b.mcmc())
+            if c is not None:
+                probit.append(c.mcmc())
         rec["als_epoch"], rec["mcmc_epoch"] = summary(als), summary(mcmc)
         rec["mcmc_over_als"] = rec["mcmc_epoch"]["median_ms"] / rec["als_epoch"]["median_ms"]
+        if c is not None:
+            rec["mcmc_classification_epoch"] = summary(probit)
+            rec["classification_over_regression"] = rec["mcmc_classification_epoch"]["median_ms"] / rec["mcmc_epoch"]["median_ms"]
+            c.close()
         b.close()
         # ---- the ALS epoch of this library against the parent's, and the parent's against itself
         if parent is not None:
@@ -160,7 +185,9 @@ def main():
         if a is not None:
             a.close()
         doc["shapes"][name] = rec
-        print("# %s: ALS %.3f ms, MCMC %.3f ms" % (name, rec["als_epoch"]["median_ms"], rec["mcmc_epoch"]["median_ms"]), file=sys.stderr, flush=True)
+        print("# %s: ALS %.3f ms, MCMC %.3f ms%s" % (name, rec["als_epoch"]["median_ms"], rec["mcmc_epoch"]["median_ms"],
+                                                   ", classification %.3f ms" % rec["mcmc_classification_epoch"]["median_ms"] if c is not None else ""),
+              file=sys.stderr, flush=True)
     text = json.dumps(doc, indent=1)
     print(text)
     if args.out:
