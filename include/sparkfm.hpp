@@ -39,6 +39,7 @@
 #include "fmhip_relational.h"
 #include "fmhip_mcmc.h"
 #include "fmhip_mcmc_task.h"
+#include "fmhip_mcmc_groups.h"
 
 namespace sparkfm {
 
@@ -473,11 +474,14 @@ class HipALS : public FMLearn {
 // (latentTargets()), and predictions() / lastPredictions() are then probabilities Phi(yhat), scored by computeLogLoss() and
 // computeAccuracy() (computeRMSE() throws); the model holds the last draw, whose score is the probit score — not a logistic one.
 // Regression: clip + clip_lo / clip_hi clamp every draw's test prediction; clip_to_labels takes the train labels' min and max.
+// setGroups (include/fmhip_mcmc_groups.h; before the first learn): one attribute-group id per feature — at least the model's
+// num_attribute of them — and lambda and mu are sampled per (parameter group, attribute group): State's lambda and mu then hold
+// (k + 1) * G values, [g * G + a], and groupCounts() the trained features of every group.
 class HipMCMC : public FMLearn {
   public:
     struct State {
         double alpha = 1.0;
-        std::vector<double> lambda, mu;             // k + 1 each: group 0 = w, 1 + f = factor f
+        std::vector<double> lambda, mu;             // k + 1 each: group 0 = w, 1 + f = factor f; with groups (k + 1) * G each, [g * G + a]
         int64_t iterations = 0;
     };
     fmhip_mcmc_opts opts;
@@ -502,6 +506,19 @@ class HipMCMC : public FMLearn {
         task_opts.clip_hi = hi;
         clip_to_labels = false;
     }
+    void setGroups(const std::vector<int32_t> &groups, int32_t n_groups = 0) {      // n_groups 0: the largest id + 1
+        if (h_) throw Error(FMHIP_ERR_INVALID, "the attribute groups are set before the first learn");
+        int32_t most = 0;
+        for (size_t i = 0; i < groups.size(); ++i) {
+            if (groups[i] < 0) throw Error(FMHIP_ERR_INVALID, "feature " + std::to_string(i) + " has a negative group id");
+            most = std::max(most, groups[i]);
+        }
+        if (n_groups != 0 && n_groups <= most) throw Error(FMHIP_ERR_INVALID, "n_groups is below the largest group id + 1");
+        groups_ = groups;
+        n_groups_ = n_groups != 0 ? n_groups : most + 1;
+        grouped_ = true;
+    }
+    int32_t numGroups() const { return n_groups_; }
     HipMCMC(const HipMCMC &) = delete;
     HipMCMC &operator=(const HipMCMC &) = delete;
     ~HipMCMC() override { (void)fmhip_mcmc_destroy(h_); }
@@ -520,15 +537,26 @@ class HipMCMC : public FMLearn {
                 to.clip_lo = *range.first;
                 to.clip_hi = *range.second;
             }
+            if (grouped_ && (int64_t)groups_.size() < fm.num_attribute)
+                throw Error(FMHIP_ERR_INVALID, "groups holds " + std::to_string(groups_.size()) + " ids but the model has num_attribute = " +
+                                                   std::to_string(fm.num_attribute));
             check(fmhip_mcmc_create_task(m, d, test_ ? test_->handle() : nullptr, &opts, &to, &h_));
+            if (grouped_) {
+                const int rc = fmhip_mcmc_set_groups(h_, groups_.data(), fm.num_attribute, n_groups_);
+                if (rc != FMHIP_OK) {
+                    (void)fmhip_mcmc_destroy(h_);
+                    h_ = nullptr;
+                    check(rc);
+                }
+            }
             n_train_ = dataset.size();
             classification_ = to.task == FMHIP_MCMC_CLASSIFICATION;
             m_ = m;
             d_ = d;
             k_ = fm.num_factor;
             if (pending_) {
-                check(fmhip_mcmc_set_state(h_, pending_state_.alpha, pending_state_.lambda.data(), pending_state_.mu.data()));
                 pending_ = false;
+                setState(pending_state_.alpha, pending_state_.lambda, pending_state_.mu);
             }
         }
         check(fmhip_mcmc_epoch(h_, &last_stats));
@@ -538,10 +566,15 @@ class HipMCMC : public FMLearn {
     }
     State state() {
         State st;
-        st.lambda.resize((size_t)k_ + 1);
-        st.mu.resize((size_t)k_ + 1);
-        check(fmhip_mcmc_get_state(need(), &st.alpha, st.lambda.data(), st.mu.data(), &st.iterations));
+        st.lambda.resize(state_size());
+        st.mu.resize(state_size());
+        check((grouped_ ? fmhip_mcmc_get_group_state : fmhip_mcmc_get_state)(need(), &st.alpha, st.lambda.data(), st.mu.data(), &st.iterations));
         return st;
+    }
+    std::vector<int64_t> groupCounts() {            // m_a: the trained features of attribute group a (one entry without groups)
+        std::vector<int64_t> counts((size_t)n_groups_);
+        check(fmhip_mcmc_group_info(need(), nullptr, counts.data()));
+        return counts;
     }
     // before the first learn the state is kept and set when the handle is made (lambda, mu: k + 1 values each)
     void setState(double alpha, const std::vector<double> &lambda, const std::vector<double> &mu) {
@@ -552,8 +585,9 @@ class HipMCMC : public FMLearn {
             pending_ = true;
             return;
         }
-        if (lambda.size() != (size_t)k_ + 1 || mu.size() != (size_t)k_ + 1) throw Error(FMHIP_ERR_INVALID, "lambda and mu must hold k + 1 values each");
-        check(fmhip_mcmc_set_state(h_, alpha, lambda.data(), mu.data()));
+        if (lambda.size() != state_size() || mu.size() != state_size())
+            throw Error(FMHIP_ERR_INVALID, "lambda and mu must hold k + 1 values each ((k + 1) * G with attribute groups)");
+        check((grouped_ ? fmhip_mcmc_set_group_state : fmhip_mcmc_set_state)(h_, alpha, lambda.data(), mu.data()));
     }
     void resetAverage() { check(fmhip_mcmc_reset_average(need())); }
     std::vector<double> predictions() {             // the test rows' predictions averaged over the kept draws
@@ -619,7 +653,11 @@ class HipMCMC : public FMLearn {
         if (!classification_) throw Error(FMHIP_ERR_INVALID, std::string(what) + " scores a classification run's probabilities (see computeRMSE)");
         return predictions();
     }
+    size_t state_size() const { return ((size_t)k_ + 1) * (size_t)n_groups_; }
     DataSet *test_;
+    std::vector<int32_t> groups_;
+    int32_t n_groups_ = 1;
+    bool grouped_ = false;
     fmhip_mcmc_t h_ = nullptr;
     fmhip_model_t m_ = nullptr;
     fmhip_dataset_t d_ = nullptr;

@@ -6,6 +6,7 @@ The arithmetic runs in hand-written HIP kernels (csrc/) behind a plain C ABI
 """
 from .dataset import DataSet, Features  # noqa: F401
 from .relational import Relation, RelationalData  # noqa: F401
+from .metadata import Metadata  # noqa: F401
 from .model import FMModel, Model  # noqa: F401
 from .learn import FMLearn, HipALS, HipMCMC, HipSGD  # noqa: F401
 from .fm import FM, FactorizationMachines, Task  # noqa: F401
@@ -14,4 +15,4 @@ from .feature_order import FeatureOrder  # noqa: F401
 from . import fmutils as FMUtils  # noqa: F401
 
 __all__ = ["DataSet", "Features", "FMModel", "Model", "FMLearn", "HipSGD", "HipALS", "HipMCMC", "FM", "FactorizationMachines", "Task",
-           "DataCollection", "FMUtils", "FeatureOrder", "Relation", "RelationalData"]
+           "DataCollection", "FMUtils", "FeatureOrder", "Relation", "RelationalData", "Metadata"]

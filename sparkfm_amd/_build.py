@@ -20,7 +20,8 @@ HIP_DEPS = ["fm_kernels.h", "fm_weights.h", "fm_relational.h", "fm_topk.h", "fm_
             os.path.join("..", "..", "include", "fmhip_topk.h"), os.path.join("..", "..", "include", "fmhip_pairing.h"),
             os.path.join("..", "..", "include", "fmhip_metrics.h"), os.path.join("..", "..", "include", "fmhip_ranking.h"),
             os.path.join("..", "..", "include", "fmhip_weights.h"), os.path.join("..", "..", "include", "fmhip_relational.h"),
-            os.path.join("..", "..", "include", "fmhip_mcmc.h"), os.path.join("..", "..", "include", "fmhip_mcmc_task.h")]
+            os.path.join("..", "..", "include", "fmhip_mcmc.h"), os.path.join("..", "..", "include", "fmhip_mcmc_task.h"),
+            os.path.join("..", "..", "include", "fmhip_mcmc_groups.h")]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result"]
 
 

@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -64,6 +64,9 @@ SYMBOLS_MCMC = ("fmhip_mcmc_opts_default", "fmhip_mcmc_create", "fmhip_mcmc_dest
 # ... and include/fmhip_mcmc_task.h — its tasks: probit classification with truncated-normal targets, the regression clamp
 SYMBOLS_MCMC_TASK = ("fmhip_mcmc_task_opts_default", "fmhip_mcmc_create_task", "fmhip_mcmc_latent_targets")
 MCMC_REGRESSION, MCMC_CLASSIFICATION = 0, 1
+# ... and include/fmhip_mcmc_groups.h — its attribute groups: a lambda and a mu per feature group
+SYMBOLS_MCMC_GROUPS = ("fmhip_mcmc_set_groups", "fmhip_mcmc_group_info", "fmhip_mcmc_get_group_state", "fmhip_mcmc_set_group_state")
+MCMC_MAX_GROUPS = 4096     # FMHIP_MCMC_MAX_GROUPS
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -448,8 +451,12 @@ def load():
     L.fmhip_mcmc_task_opts_default.argtypes = [P(McmcTaskOpts)]
     L.fmhip_mcmc_create_task.argtypes = [vp, vp, vp, P(McmcOpts), P(McmcTaskOpts), P(vp)]
     L.fmhip_mcmc_latent_targets.argtypes = [vp, vp]
+    L.fmhip_mcmc_set_groups.argtypes = [vp, vp, i64, C.c_int32]
+    L.fmhip_mcmc_group_info.argtypes = [vp, P(C.c_int32), vp]
+    L.fmhip_mcmc_get_group_state.argtypes = [vp, P(dbl), vp, vp, P(i64)]
+    L.fmhip_mcmc_set_group_state.argtypes = [vp, dbl, vp, vp]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
-                 + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK):
+                 + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

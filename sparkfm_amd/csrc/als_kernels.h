@@ -48,6 +48,26 @@ struct McmcDev {
     int64_t zi;
 };
 
+// ... and what a handle with attribute groups (include/fmhip_mcmc_groups.h, G = n_groups > 1) takes in McmcDev's place — a type of
+// its own, so that the instantiations the ALS epoch and an ungrouped handle run keep their arguments and their code:
+// hyp = {alpha, lambda[(k + 1) * G], mu[(k + 1) * G]}, [g * G + a]; group[i] = feature i's attribute group, num_attribute + 1
+// entries (the walks read a column's id a step ahead of the test that skips quirk Q1's slot)
+struct McmcGroupDev {
+    const double *hyp;
+    const double *z;
+    int32_t sample;
+    int64_t zi;
+    const int32_t *group;
+    int32_t n_groups;
+};
+
+// The plan of the grouped hyper-parameter sums on the device (fmhip_host.h: McmcGroupPlan)
+struct McmcGroupSums {
+    const int32_t *order, *chunk_ptr, *chunk_group;
+    int32_t n_chunks;
+    double *out;             // [n_chunks * (k + 1) * 2]: chunk c's {sum theta, sum (theta - mu_ga)^2} of parameter group g at 2 * (c * (k + 1) + g)
+};
+
 // The probit link of a classification handle (include/fmhip_mcmc_task.h): k_mcmc_probit_targets stands where the epoch's first
 // residual pass stood and fills ystar — which AlsArgs.y points at for the whole epoch — from the labels' signs
 enum { kProbitStart = 0, kProbitSample = 1, kProbitMean = 2 };
@@ -87,6 +107,13 @@ hipError_t launch_mcmc_begin(const AlsArgs &a, const McmcDev &m, double *z, uint
 // plan (the same environment knobs), every step a draw
 hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
                               const int32_t *h_lev_cols, int n_levels, hipStream_t s);
+// The same two for a handle with attribute groups.  Begin: sums[] holds quantity 0 only (kMcmcSumParts pairs); the groups' sums are
+// k_mcmc_group_sums' — a workgroup per chunk of the plan, every partial reduced in a fixed order, no atomics — which the host adds
+// in chunk order.  Sweeps: every step looks its lambda and mu up by the column's group.
+hipError_t launch_mcmc_group_begin(const AlsArgs &a, const McmcGroupDev &m, const McmcGroupSums &plan, double *z, uint64_t seed, uint32_t t, double *sums,
+                                   hipStream_t s, const McmcProbit *probit = nullptr);
+hipError_t launch_mcmc_group_sweeps(const AlsArgs &a, const McmcGroupDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
+                                    const int32_t *h_lev_cols, int n_levels, hipStream_t s);
 // The test rows' predictions under the parameters t.w0 / t.w / t.v into t.e (the last draw's), and sum[r] += t.e[r]: t holds the
 // test set's k, n_rows, row_ptr, col, val and, as y, n_rows zeros (k_als_residual's e = yhat - 0 is the prediction exactly).
 // link: what the prediction becomes first, in t.e too (kLinkNone: the launch this always was)

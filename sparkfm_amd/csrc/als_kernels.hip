@@ -49,6 +49,7 @@ struct DrawAls {
     __device__ __forceinline__ double operator()(double theta, double sum_e_h, double sum_h_sqr, double) const {
         return compute_theta(theta, reg, sum_e_h, sum_h_sqr);
     }
+    __device__ __forceinline__ const DrawAls &at(int64_t) const { return *this; }      // the step of feature i: the same for every feature
 };
 
 struct DrawMcmc {
@@ -61,6 +62,20 @@ struct DrawMcmc {
         const double theta_new = sample ? mean + z / sqrt(prec) : mean;      // (no `+ 0 * sigma` without sampling)
         return is_updatable(theta_new, theta) ? theta_new : theta;
     }
+    __device__ __forceinline__ const DrawMcmc &at(int64_t) const { return *this; }
+};
+
+// ... with attribute groups (include/fmhip_mcmc_groups.h): the step is per column — feature i takes the lambda and the mu of its
+// group.  lambda / mu: parameter group g's rows of the state, G values each.
+struct DrawMcmcGroups {
+    double alpha;
+    const double *lambda, *mu;
+    const int32_t *group;
+    bool sample;
+    __device__ __forceinline__ DrawMcmc at(int64_t i) const {
+        const int32_t a = group[i];
+        return DrawMcmc{alpha, lambda[a], mu[a], sample};
+    }
 };
 
 // Every walk below takes a parameter pack M that is EMPTY for the ALS epoch — its kernels keep the signatures, the kernel
@@ -71,17 +86,27 @@ __device__ __forceinline__ DrawMcmc group_draw(const AlsArgs &a, int g, double, 
     return DrawMcmc{m.hyp[0], m.hyp[1 + g], m.hyp[2 + a.k + g], m.sample != 0};
 }
 
+__device__ __forceinline__ DrawMcmcGroups group_draw(const AlsArgs &a, int g, double, const McmcGroupDev &m) {
+    const int64_t G = m.n_groups;
+    return DrawMcmcGroups{m.hyp[0], m.hyp + 1 + g * G, m.hyp + 1 + (a.k + 1 + g) * G, m.group, m.sample != 0};
+}
+
 // the noise of entry idx of m.z (k_mcmc_noise filled it before the epoch's first dependent launch); of a long column's own step
 __device__ __forceinline__ double noise_at(int64_t) { return 0.0; }
 __device__ __forceinline__ double noise_at(int64_t idx, const McmcDev &m) { return m.z[idx]; }
+__device__ __forceinline__ double noise_at(int64_t idx, const McmcGroupDev &m) { return m.z[idx]; }
 __device__ __forceinline__ double noise_own() { return 0.0; }
 __device__ __forceinline__ double noise_own(const McmcDev &m) { return m.z[m.zi]; }
+__device__ __forceinline__ double noise_own(const McmcGroupDev &m) { return m.z[m.zi]; }
 
 // the bias step: computeTheta(w0, reg0, sum e, size) / the conditional with h = 1, lambda = reg0, mu = 0 (its noise sits behind
 // the coordinates')
 __device__ __forceinline__ double bias_step(const AlsArgs &a, double w0, double se) { return compute_theta(w0, a.reg0, se, (double)a.n_rows); }
 __device__ __forceinline__ double bias_step(const AlsArgs &a, double w0, double se, const McmcDev &m) {
     return DrawMcmc{m.hyp[0], a.reg0, 0.0, m.sample != 0}(w0, se, (double)a.n_rows, m.z[(int64_t)(a.k + 1) * a.n_cols]);
+}
+__device__ __forceinline__ double bias_step(const AlsArgs &a, double w0, double se, const McmcGroupDev &m) {
+    return bias_step(a, w0, se, McmcDev{m.hyp, m.z, m.sample, m.zi});      // (the bias has no group: alpha is hyp[0] in both layouts)
 }
 
 // FMModel.predict's exact order of operations (S/fm/FMModel.scala:34-63) for row r: sequential sums in stored order
@@ -229,6 +254,55 @@ __global__ __launch_bounds__(kSumsBlock) void k_mcmc_sums(AlsArgs a, McmcDev m, 
     }
 }
 
+// The same sums per (parameter group g, attribute group a) of a handle with groups (include/fmhip_mcmc_groups.h): (k + 1) * G
+// pairs.  A workgroup per (g, a) would be tens of thousands of tiny workgroups, each striding V by k; here a workgroup takes one
+// CHUNK of the host's plan — at most kMcmcGroupChunk trained slots of ONE attribute group, in the plan's stable order — and
+// produces the chunk's partial pair of all k + 1 parameter groups.  The block is cut into S = 256 / L sub-groups of L = the power
+// of two >= k + 1 (at most 256) lanes: lane j of a sub-group owns parameter group g = j (w at j = 0, then the feature's V row,
+// read contiguously by the sub-group's lanes), sub-group u adds the chunk's slots u, u + S, u + 2S ... in that order, and lane j of
+// sub-group 0 adds the S sub-sums in order through LDS.  k + 1 = 257 takes a second pass.  No atomics; the order of every
+// addition is fixed by (chunk, k) alone, so neither the CU count nor the launch schedule enters the result.
+constexpr int kGroupSumsBlock = 256;
+__global__ __launch_bounds__(kGroupSumsBlock) void k_mcmc_group_sums(AlsArgs a, McmcGroupDev m, McmcGroupSums plan) {
+#pragma clang fp contract(off)
+    __shared__ double sh[2][kGroupSumsBlock];
+    const int chunk = (int)blockIdx.x, tid = threadIdx.x, k1 = a.k + 1;
+    if (chunk >= plan.n_chunks) return;
+    int L = 1;
+    while (L < k1 && L < kGroupSumsBlock) L <<= 1;
+    const int S = kGroupSumsBlock / L, u = tid / L, j = tid % L;
+    const int lo = plan.chunk_ptr[chunk], hi = plan.chunk_ptr[chunk + 1];
+    const int64_t G = m.n_groups;
+    const int32_t ag = plan.chunk_group[chunk];
+    for (int g0 = 0; g0 < k1; g0 += L) {
+        const int g = g0 + j;
+        double s0 = 0.0, s1 = 0.0;
+        if (g < k1) {
+            const double mu = m.hyp[1 + (k1 + g) * G + ag];
+            for (int p = lo + u; p < hi; p += S) {
+                const int64_t i = a.cfeat[plan.order[p]];          // trained by the plan's construction: i < num_attribute
+                const double th = g == 0 ? a.w[i] : a.v[(g - 1) + i * a.k];
+                const double d = th - mu;
+                s0 += th;
+                s1 += d * d;
+            }
+        }
+        __syncthreads();                                           // sh may still be read from the previous pass
+        sh[0][tid] = s0;
+        sh[1][tid] = s1;
+        __syncthreads();
+        if (u == 0 && g < k1) {
+            double t0 = 0.0, t1 = 0.0;
+            for (int x = 0; x < S; ++x) {
+                t0 += sh[0][x * L + j];
+                t1 += sh[1][x * L + j];
+            }
+            plan.out[2 * ((int64_t)chunk * k1 + g)] = t0;
+            plan.out[2 * ((int64_t)chunk * k1 + g) + 1] = t1;
+        }
+    }
+}
+
 // drawGlobalBias :152-154 = computeTheta(w0, reg0, sum e, size) and `fm.w0 = w0` (:19-27) — once per epoch, one workgroup.
 // The residuals are NOT shifted here: as Spark evaluates :23-31 the lazy `error` RDD is materialised after `fm.w0 = w0`, so
 // its `fm.predict` already carries the new bias and the mapped term `w0 - fm.w0` is zero — the
@@ -263,6 +337,7 @@ __global__ __launch_bounds__(kAlsBlock) void k_als_cols_wg(AlsArgs a, double *q,
         double *par = FACTOR ? a.v + f + i * k : a.w + i;
         const double th = *par;
         const double zn = noise_at((int64_t)g * a.n_cols + s, m...);
+        const auto &step = draw.at(i);                            // (with attribute groups: requested before the column is reduced)
         double shs = 0.0, seh = 0.0;
         for (int p = c0 + tid; p < c1; p += kAlsBlock) {
             const uint32_t r = a.crow[p] & 0x7fffffffu;
@@ -272,7 +347,7 @@ __global__ __launch_bounds__(kAlsBlock) void k_als_cols_wg(AlsArgs a, double *q,
             seh += a.e[r] * h;
         }
         block_sum2<kAlsBlock>(shs, seh, sh);
-        const double tn = draw(th, seh, shs, zn);
+        const double tn = step(th, seh, shs, zn);
         const double d = tn - th;
         const bool upd = is_updatable(tn, th);
         for (int p = c0 + tid; p < c1; p += kAlsBlock) {
@@ -332,7 +407,7 @@ __global__ __launch_bounds__(kColBlock) void k_als_col_update(AlsArgs a, double 
     }
     block_sum2<kColBlock>(shs, seh, sh);
     const double th = a.part[2 * G];
-    const double tn = group_draw(a, FACTOR ? 1 + f : 0, FACTOR ? a.regv : a.regw, m...)(th, seh, shs, noise_own(m...));
+    const double tn = group_draw(a, FACTOR ? 1 + f : 0, FACTOR ? a.regv : a.regw, m...).at(i)(th, seh, shs, noise_own(m...));
     const double d = tn - th;
     const bool upd = is_updatable(tn, th);
     const int per = (c1 - c0 + G - 1) / G;
@@ -493,14 +568,16 @@ __device__ __forceinline__ void walk_columns(const AlsArgs &a, double *e, double
     int c_nx1 = a.cptr[nc > 1 ? 2 : 1];
     double th_cur = par[i_cur * stride];
     double z_cur = noise_at(zrow, m...);
+    auto step_cur = draw.at(i_cur);                                // (with attribute groups: the column's own lambda and mu, looked up a step ahead)
     ColHead head = load_head(a, c0, lane);
     for (int s = 0; s < nc; ++s) {
         const double th_nx = par[i_nx * stride];                   // step s+1's parameter
         const double z_nx = noise_at(zrow + (s + 1 < nc ? s + 1 : nc - 1), m...);        // ... and its noise
+        const auto step_nx = draw.at(i_nx);
         const int64_t i_nn = a.cfeat[s + 2 < nc ? s + 2 : nc - 1]; // step s+2's feature id and end offset (clamped, unconditional)
         const int c_nn1 = a.cptr[s + 3 < nc ? s + 3 : nc];
         if (i_cur < a.num_attribute) {                             // `0 until num_attribute`: slot n is never trained (quirk Q1)
-            const double tn = column_step<FACTOR, true>(a, e, q, c0, c1, th_cur, draw, z_cur, head, lane);
+            const double tn = column_step<FACTOR, true>(a, e, q, c0, c1, th_cur, step_cur, z_cur, head, lane);
             if (lane == 0) par[i_cur * stride] = tn;               // :40 / :64
         } else {
             head = load_head(a, c1, lane);                         // skipped column: still hand the next column's head on
@@ -509,6 +586,7 @@ __device__ __forceinline__ void walk_columns(const AlsArgs &a, double *e, double
         i_cur = i_nx; i_nx = i_nn;
         th_cur = th_nx;
         z_cur = z_nx;
+        step_cur = step_nx;
     }
 }
 
@@ -533,7 +611,7 @@ __global__ __launch_bounds__(kLevelBlock) void k_als_level(AlsArgs a, double *q,
     double *par = FACTOR ? a.v + f + i * a.k : a.w + i;
     ColHead head = load_head(a, c0, lane);
     const int g = FACTOR ? 1 + f : 0;
-    const double tn = column_step<FACTOR, false>(a, a.e, q, c0, c1, *par, group_draw(a, g, FACTOR ? a.regv : a.regw, m...),
+    const double tn = column_step<FACTOR, false>(a, a.e, q, c0, c1, *par, group_draw(a, g, FACTOR ? a.regv : a.regw, m...).at(i),
                                                  noise_at((int64_t)g * a.n_cols + s, m...), head, lane);
     if (lane == 0) *par = tn;                                      // :40 / :64
 }
@@ -564,7 +642,8 @@ __global__ __launch_bounds__(kLdsSweepThreads) void k_als_sweep_lds(AlsArgs a, c
 namespace {
 
 // one chip-wide closed-form step of a long column (two launches; see k_als_col_sums)
-inline McmcDev own_noise(McmcDev m, int64_t zi) {
+template <class Dev>
+inline Dev own_noise(Dev m, int64_t zi) {
     m.zi = zi;
     return m;
 }
@@ -711,6 +790,30 @@ hipError_t launch_mcmc_begin(const AlsArgs &a, const McmcDev &m, double *z, uint
 
 hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
                               const int32_t *h_lev_cols, int n_levels, hipStream_t s) {
+    return epoch_tail(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, s, m);
+}
+
+hipError_t launch_mcmc_group_begin(const AlsArgs &a, const McmcGroupDev &m, const McmcGroupSums &plan, double *z, uint64_t seed, uint32_t t, double *sums,
+                                   hipStream_t s, const McmcProbit *probit) {
+    const McmcDev flat{m.hyp, m.z, m.sample, m.zi};
+    if (m.sample) {
+        int64_t nb = ((int64_t)(a.k + 1) * a.n_cols + 1 + 255) / 256;
+        if (nb > 4096) nb = 4096;
+        hipLaunchKernelGGL(k_mcmc_noise, dim3((unsigned)nb), dim3(256), 0, s, a, z, seed, t);
+    }
+    if (probit)
+        hipLaunchKernelGGL(k_mcmc_probit_targets, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a, *probit, seed, t);
+    else
+        hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a);
+    // quantity 0 (sum e^2) stays where it is: k_mcmc_sums' first kMcmcSumParts workgroups, which read nothing of the state
+    hipLaunchKernelGGL(k_mcmc_sums, dim3((unsigned)kMcmcSumParts), dim3(kSumsBlock), 0, s, a, flat, sums, kMcmcSumParts);
+    if (m.sample && plan.n_chunks > 0)
+        hipLaunchKernelGGL(k_mcmc_group_sums, dim3((unsigned)plan.n_chunks), dim3(kGroupSumsBlock), 0, s, a, m, plan);
+    return hipGetLastError();
+}
+
+hipError_t launch_mcmc_group_sweeps(const AlsArgs &a, const McmcGroupDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
+                                    const int32_t *h_lev_cols, int n_levels, hipStream_t s) {
     return epoch_tail(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, s, m);
 }
 

@@ -779,6 +779,36 @@ void mcmc_draw_group(uint64_t seed, uint32_t t, uint32_t g, const McmcPriors &p,
     *mu = (sum_theta + p.gamma_0 * p.mu_0) / w + rng::normal(seed, 0, g, t, rng::kStreamMu) / sqrt(w * *lambda);
 }
 
+int64_t mcmc_bad_group(const int32_t *group, int64_t n, int32_t n_groups) {
+    for (int64_t i = 0; i < n; ++i)
+        if (group[i] < 0 || group[i] >= n_groups) return i;
+    return -1;
+}
+
+void mcmc_group_plan(const int32_t *cfeat, int64_t n_cols, int64_t num_attribute, const int32_t *group, int32_t n_groups, int chunk_slots,
+                     McmcGroupPlan *plan) {
+    const size_t G = (size_t)n_groups;
+    plan->counts.assign(G, 0);
+    for (int64_t s = 0; s < n_cols; ++s)
+        if (cfeat[s] < num_attribute) ++plan->counts[(size_t)group[cfeat[s]]];
+    // a counting sort: stable, so a group's slots stay ascending
+    std::vector<int64_t> at(G + 1, 0);
+    for (size_t a = 0; a < G; ++a) at[a + 1] = at[a] + plan->counts[a];
+    plan->order.assign((size_t)at[G], 0);
+    plan->chunk_ptr.assign(1, 0);
+    plan->chunk_group.clear();
+    plan->group_chunks.assign(G + 1, 0);
+    for (size_t a = 0; a < G; ++a) {
+        for (int64_t lo = at[a]; lo < at[a + 1]; lo += chunk_slots) {
+            plan->chunk_group.push_back((int32_t)a);
+            plan->chunk_ptr.push_back((int32_t)std::min<int64_t>(lo + chunk_slots, at[a + 1]));
+        }
+        plan->group_chunks[a + 1] = (int32_t)plan->chunk_group.size();
+    }
+    for (int64_t s = 0; s < n_cols; ++s)
+        if (cfeat[s] < num_attribute) plan->order[(size_t)at[(size_t)group[cfeat[s]]]++] = (int32_t)s;
+}
+
 double mcmc_truncated_normal(uint64_t seed, uint32_t row, uint32_t t, double a, int *attempts) { return rng::truncated_normal(seed, row, t, a, attempts); }
 double mcmc_truncated_mean(double a) { return rng::truncated_normal_mean(a); }
 

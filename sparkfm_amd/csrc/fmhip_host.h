@@ -203,6 +203,22 @@ double mcmc_draw_alpha(uint64_t seed, uint32_t t, const McmcPriors &p, int64_t n
 // mu ~ N((sum_theta + gamma_0 mu_0) / (m + gamma_0), 1 / ((m + gamma_0) lambda)) = mean + z / sqrt((m + gamma_0) lambda)
 void mcmc_draw_group(uint64_t seed, uint32_t t, uint32_t g, const McmcPriors &p, int64_t m, double sum_theta, double sum_dev2, double mu_old,
                      double *lambda, double *mu);
+// ---- ... its attribute groups (include/fmhip_mcmc_groups.h) ----
+constexpr int kMcmcMaxGroups = 4096;        // FMHIP_MCMC_MAX_GROUPS
+constexpr int kMcmcGroupChunk = 512;        // column slots per chunk of k_mcmc_group_sums (a workgroup each)
+// -1, or the first feature i < n whose id group[i] lies outside [0, n_groups)
+int64_t mcmc_bad_group(const int32_t *group, int64_t n, int32_t n_groups);
+// The plan of the grouped hyper-parameter sums: the TRAINED column slots (cfeat[s] < num_attribute) in a stable order by group —
+// slots of one group keep their ascending order — cut into chunks of at most chunk_slots slots that never straddle a group.
+//   order[chunk_ptr[c] .. chunk_ptr[c + 1]): the slots of chunk c, all of group chunk_group[c]; chunks sit in group order and
+//   group a's are [group_chunks[a], group_chunks[a + 1]) (none for a group without a trained slot); counts[a] = m_a.
+// group: num_attribute ids, each in [0, n_groups) (checked by the caller: mcmc_bad_group)
+struct McmcGroupPlan {
+    std::vector<int32_t> order, chunk_ptr, chunk_group, group_chunks;
+    std::vector<int64_t> counts;
+};
+void mcmc_group_plan(const int32_t *cfeat, int64_t n_cols, int64_t num_attribute, const int32_t *group, int32_t n_groups, int chunk_slots,
+                     McmcGroupPlan *plan);
 // ---- ... and its tasks (include/fmhip_mcmc_task.h) ----
 // the probit link's latent draw of a row: z ~ N(0,1) given z > a, counter (row, attempt, t, stream 5); attempts: nullable
 double mcmc_truncated_normal(uint64_t seed, uint32_t row, uint32_t t, double a, int *attempts);

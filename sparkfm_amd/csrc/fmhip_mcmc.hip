@@ -8,13 +8,17 @@
 // A classification handle (include/fmhip_mcmc_task.h) differs in three places: k_mcmc_probit_targets stands where the first
 // k_als_residual stood and fills the latent targets ystar, which the walk's y points at for the whole epoch; alpha is not drawn;
 // the test rows' accumulation takes Phi of the score (a regression handle with a clip: the clamp).
+// A handle with attribute groups (include/fmhip_mcmc_groups.h, G > 1) keeps lambda and mu as [(k + 1) x G], takes the groups' sums
+// from k_mcmc_group_sums over the plan fmhip_mcmc_set_groups made (fmhip_host.cpp: mcmc_group_plan) — added here in chunk order,
+// inside the same single sync — and walks with McmcGroupDev.  G = 1, set or not, is the sequence above, launch for launch.
 // The kernels are in als_kernels.hip, the generator in mcmc_rng.h.
 #include "fmhip_internal.h"
 #include "als_kernels.h"
-#include "../../include/fmhip_mcmc_task.h"
+#include "../../include/fmhip_mcmc_groups.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <new>
 #include <vector>
 
@@ -31,7 +35,13 @@ struct fmhip_mcmc {
     int32_t k = 0;
     int64_t n_trained = 0;                  // |T|: the column slots with id < num_attribute
     double alpha = 1.0;
-    std::vector<double> lambda, mu;         // [k + 1]
+    std::vector<double> lambda, mu;         // [(k + 1) * G], row-major: [g * G + a]
+    int32_t G = 1;                          // attribute groups (include/fmhip_mcmc_groups.h); 1: none, the epoch fmhip_mcmc.h describes
+    McmcGroupPlan plan;                     // G > 1: the chunks of the grouped sums
+    int64_t plan_cols = 0;                  // ... and the column slots they were made over
+    DevBuf<int32_t> d_group, d_order, d_chunk_ptr, d_chunk_group;      // group: [num_attribute + 1]
+    DevBuf<double> gsums;                   // k_mcmc_group_sums' partials [n_chunks * (k + 1) * 2]
+    std::vector<double> h_gsums;
     int64_t iterations = 0, draws = 0;
     DevBuf<double> z, hyp, sums;            // the epoch's noise; {alpha, lambda, mu}; k_mcmc_sums' partials
     DevBuf<double> ystar;                   // classification: the latent targets the last epoch trained on [train rows]
@@ -42,7 +52,7 @@ struct fmhip_mcmc {
 namespace {
 
 int upload_state(fmhip_mcmc_t s) {
-    const size_t k1 = (size_t)s->k + 1;
+    const size_t k1 = ((size_t)s->k + 1) * (size_t)s->G;
     s->h_hyp[0] = s->alpha;
     std::copy(s->lambda.begin(), s->lambda.end(), s->h_hyp.begin() + 1);
     std::copy(s->mu.begin(), s->mu.end(), s->h_hyp.begin() + 1 + (ptrdiff_t)k1);
@@ -117,6 +127,43 @@ int create(fmhip_model_t m, fmhip_dataset_t train, fmhip_dataset_t test, const f
     return FMHIP_OK;
 }
 
+// dst frees what it held and owns src's buffer
+template <class T>
+void take(DevBuf<T> &dst, DevBuf<T> &src) {
+    dst.release();
+    dst.p = src.p;
+    dst.n = src.n;
+    src.p = nullptr;
+    src.n = 0;
+}
+
+// lambda, mu: (k + 1) * G values each (the caller holds the model's lock)
+int get_state(fmhip_mcmc_t s, double *alpha, double *lambda, double *mu, int64_t *iterations) {
+    if (alpha) *alpha = s->alpha;
+    if (lambda) std::copy(s->lambda.begin(), s->lambda.end(), lambda);
+    if (mu) std::copy(s->mu.begin(), s->mu.end(), mu);
+    if (iterations) *iterations = s->iterations;
+    return FMHIP_OK;
+}
+
+int set_state(fmhip_mcmc_t s, double alpha, const double *lambda, const double *mu) {
+    if (!(std::isfinite(alpha) && alpha > 0.0)) return fail(FMHIP_ERR_INVALID, "alpha must be finite and > 0");
+    const int G = s->G;
+    for (int g = 0; g <= s->k; ++g)
+        for (int a = 0; a < G; ++a) {
+            const size_t at = (size_t)g * G + a;
+            char name[32];
+            if (G > 1) snprintf(name, sizeof name, "[%d][%d]", g, a);
+            else snprintf(name, sizeof name, "[%d]", g);
+            if (!(std::isfinite(lambda[at]) && lambda[at] > 0.0)) return fail(FMHIP_ERR_INVALID, "lambda%s must be finite and > 0", name);
+            if (!std::isfinite(mu[at])) return fail(FMHIP_ERR_INVALID, "mu%s must be finite", name);
+        }
+    s->alpha = alpha;
+    s->lambda.assign(lambda, lambda + s->lambda.size());
+    s->mu.assign(mu, mu + s->mu.size());
+    return FMHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -162,7 +209,41 @@ int fmhip_mcmc_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats) {
     const bool probit = s->task == FMHIP_MCMC_CLASSIFICATION;
     const uint32_t t = (uint32_t)s->iterations;
     double sse = 0.0;
-    if (d->n_rows > 0) {
+    if (d->n_rows > 0 && s->G > 1) {
+        const int G = s->G, n_chunks = (int)s->plan.chunk_group.size();
+        if (a.n_cols != s->plan_cols)
+            return fail(FMHIP_ERR_INVALID, "the train set's columns changed under the MCMC handle (%d, the groups were set over %lld)", a.n_cols,
+                        (long long)s->plan_cols);
+        const McmcGroupDev dev{s->hyp.p, s->z.p, s->opts.sample ? 1 : 0, 0, s->d_group.p, G};
+        const McmcGroupSums sums{s->d_order.p, s->d_chunk_ptr.p, s->d_chunk_group.p, n_chunks, s->gsums.p};
+        TRY(upload_state(s));                                // the means the sums are taken around
+        const McmcProbit targets{d->y64.p, s->ystar.p, s->iterations == 0 ? kProbitStart : dev.sample ? kProbitSample : kProbitMean};
+        if (probit) a.y = s->ystar.p;
+        HIP_TRY(launch_mcmc_group_begin(a, dev, sums, s->z.p, s->opts.seed, t, s->sums.p, m->stream, probit ? &targets : nullptr));
+        HIP_TRY(hipMemcpyAsync(s->h_sums.data(), s->sums.p, 2 * (size_t)P * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        if (dev.sample && n_chunks > 0)
+            HIP_TRY(hipMemcpyAsync(s->h_gsums.data(), s->gsums.p, s->h_gsums.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));            // still the epoch's one host sync
+        for (int c = 0; c < P; ++c) sse += s->h_sums[2 * (size_t)c];
+        if (dev.sample) {
+            if (!probit) s->alpha = mcmc_draw_alpha(s->opts.seed, t, s->priors, d->n_rows, sse);
+            for (int g = 0; g < k1; ++g)
+                for (int ag = 0; ag < G; ++ag) {
+                    double sum_theta = 0.0, sum_dev2 = 0.0;      // a (g, a)'s partials in chunk order; none: a draw from the prior
+                    for (int c = s->plan.group_chunks[(size_t)ag]; c < s->plan.group_chunks[(size_t)ag + 1]; ++c) {
+                        sum_theta += s->h_gsums[2 * ((size_t)c * k1 + g)];
+                        sum_dev2 += s->h_gsums[2 * ((size_t)c * k1 + g) + 1];
+                    }
+                    const size_t at = (size_t)g * G + ag;
+                    mcmc_draw_group(s->opts.seed, t, (uint32_t)g + ((uint32_t)ag << 16), s->priors, s->plan.counts[(size_t)ag], sum_theta, sum_dev2, s->mu[at],
+                                    &s->lambda[at], &s->mu[at]);
+                }
+            TRY(upload_state(s));
+        }
+        const int n_levels = d->als_lev_ptr.empty() ? 0 : (int)d->als_lev_ptr.size() - 1;
+        HIP_TRY(launch_mcmc_group_sweeps(a, dev, d->h_cfeat.data(), d->h_cptr.data(), n_levels ? d->als_lev_ptr.data() : nullptr, d->h_als_lev_cols.data(),
+                                         n_levels, m->stream));
+    } else if (d->n_rows > 0) {
         const McmcDev dev{s->hyp.p, s->z.p, s->opts.sample ? 1 : 0, 0};
         TRY(upload_state(s));                                // the means the sums are taken around
         const McmcProbit targets{d->y64.p, s->ystar.p, s->iterations == 0 ? kProbitStart : dev.sample ? kProbitSample : kProbitMean};
@@ -216,25 +297,97 @@ int fmhip_mcmc_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats) {
 int fmhip_mcmc_get_state(fmhip_mcmc_t s, double *alpha, double *lambda, double *mu, int64_t *iterations) {
     if (!s) return fail(FMHIP_ERR_INVALID, "the MCMC handle is NULL");
     ReadLock lock(s->m);
-    if (alpha) *alpha = s->alpha;
-    if (lambda) std::copy(s->lambda.begin(), s->lambda.end(), lambda);
-    if (mu) std::copy(s->mu.begin(), s->mu.end(), mu);
-    if (iterations) *iterations = s->iterations;
-    return FMHIP_OK;
+    if (s->G > 1 && (lambda || mu))
+        return fail(FMHIP_ERR_INVALID, "this handle has %d attribute groups: its lambda and mu are (k + 1) x %d — read them with fmhip_mcmc_get_group_state",
+                    s->G, s->G);
+    return get_state(s, alpha, lambda, mu, iterations);
 }
 
 int fmhip_mcmc_set_state(fmhip_mcmc_t s, double alpha, const double *lambda, const double *mu) {
     if (!s || !lambda || !mu) return fail(FMHIP_ERR_INVALID, "NULL argument");
-    if (!(std::isfinite(alpha) && alpha > 0.0)) return fail(FMHIP_ERR_INVALID, "alpha must be finite and > 0");
-    for (int g = 0; g <= s->k; ++g) {
-        if (!(std::isfinite(lambda[g]) && lambda[g] > 0.0)) return fail(FMHIP_ERR_INVALID, "lambda[%d] must be finite and > 0", g);
-        if (!std::isfinite(mu[g])) return fail(FMHIP_ERR_INVALID, "mu[%d] must be finite", g);
-    }
     WriteLock lock(s->m);
-    s->alpha = alpha;
-    s->lambda.assign(lambda, lambda + s->k + 1);
-    s->mu.assign(mu, mu + s->k + 1);
+    if (s->G > 1)
+        return fail(FMHIP_ERR_INVALID, "this handle has %d attribute groups: its lambda and mu are (k + 1) x %d — set them with fmhip_mcmc_set_group_state",
+                    s->G, s->G);
+    return set_state(s, alpha, lambda, mu);
+}
+
+int fmhip_mcmc_set_groups(fmhip_mcmc_t s, const int32_t *group, int64_t n, int32_t n_groups) {
+    if (!group) return fail(FMHIP_ERR_INVALID, "the group table is NULL");
+    if (n_groups < 1) return fail(FMHIP_ERR_INVALID, "n_groups = %d: a handle has at least one attribute group", n_groups);
+    if (n_groups > FMHIP_MCMC_MAX_GROUPS)
+        return fail(FMHIP_ERR_UNSUPPORTED, "n_groups = %d is above FMHIP_MCMC_MAX_GROUPS = %d", n_groups, FMHIP_MCMC_MAX_GROUPS);
+    if (!s) return fail(FMHIP_ERR_INVALID, "the MCMC handle is NULL");
+    fmhip_model_t m = s->m;
+    WriteLock lock(m);
+    if (s->iterations > 0)
+        return fail(FMHIP_ERR_INVALID, "the attribute groups are set before the handle's first epoch: this one has completed %lld", (long long)s->iterations);
+    if (n != m->n) return fail(FMHIP_ERR_INVALID, "the group table holds n = %lld ids but the model has num_attribute = %lld", (long long)n, (long long)m->n);
+    const int64_t bad = mcmc_bad_group(group, n, n_groups);
+    if (bad >= 0)
+        return fail(FMHIP_ERR_INVALID, "feature %lld has group id %d, outside [0, %d)", (long long)bad, group[bad], n_groups);
+    // everything that can fail comes first, into buffers of its own: a refusal leaves the handle as it was
+    const size_t k1 = (size_t)s->k + 1, size = k1 * (size_t)n_groups;
+    McmcGroupPlan plan;
+    DevBuf<int32_t> d_group, d_order, d_chunk_ptr, d_chunk_group;
+    DevBuf<double> hyp, gsums;
+    if (n_groups > 1) {
+        TRY(set_device(m->device));
+        const int64_t n_cols = s->train->n_rows > 0 ? s->train->batches[0].n_cols : 0;
+        mcmc_group_plan(s->train->h_cfeat.data(), n_cols, m->n, group, n_groups, kMcmcGroupChunk, &plan);
+        std::vector<int32_t> padded(group, group + n);
+        padded.push_back(0);                                 // quirk Q1's slot: read a step ahead by the walks, never used
+        const size_t n_chunks = plan.chunk_group.size();
+        TRY(d_group.alloc(padded.size()));
+        TRY(d_order.alloc(std::max<size_t>(plan.order.size(), 1)));
+        TRY(d_chunk_ptr.alloc(n_chunks + 1));
+        TRY(d_chunk_group.alloc(std::max<size_t>(n_chunks, 1)));
+        TRY(gsums.alloc(std::max<size_t>(2 * k1 * n_chunks, 1)));
+        TRY(hyp.alloc(1 + 2 * size));
+        HIP_TRY(hipMemcpy(d_group.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (!plan.order.empty()) HIP_TRY(hipMemcpy(d_order.p, plan.order.data(), plan.order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_chunk_ptr.p, plan.chunk_ptr.data(), (n_chunks + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (n_chunks) HIP_TRY(hipMemcpy(d_chunk_group.p, plan.chunk_group.data(), n_chunks * sizeof(int32_t), hipMemcpyHostToDevice));
+    } else {
+        plan.counts.assign(1, s->n_trained);                 // G = 1: the handle fmhip_mcmc.h describes (its hyp is large enough as it is)
+    }
+    s->G = n_groups;
+    s->plan = std::move(plan);
+    s->plan_cols = s->train->n_rows > 0 ? s->train->batches[0].n_cols : 0;
+    take(s->d_group, d_group);
+    take(s->d_order, d_order);
+    take(s->d_chunk_ptr, d_chunk_ptr);
+    take(s->d_chunk_group, d_chunk_group);
+    take(s->gsums, gsums);
+    if (hyp.p) take(s->hyp, hyp);
+    s->h_gsums.assign(2 * k1 * s->plan.chunk_group.size(), 0.0);
+    s->h_hyp.assign(1 + 2 * size, 0.0);
+    s->lambda.assign(size, s->opts.init_lambda);
+    s->mu.assign(size, 0.0);
     return FMHIP_OK;
+}
+
+int fmhip_mcmc_group_info(fmhip_mcmc_t s, int32_t *n_groups, int64_t *counts) {
+    if (!s) return fail(FMHIP_ERR_INVALID, "the MCMC handle is NULL");
+    ReadLock lock(s->m);
+    if (n_groups) *n_groups = s->G;
+    if (counts) {
+        if (s->G > 1) std::copy(s->plan.counts.begin(), s->plan.counts.end(), counts);
+        else counts[0] = s->n_trained;
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_mcmc_get_group_state(fmhip_mcmc_t s, double *alpha, double *lambda, double *mu, int64_t *iterations) {
+    if (!s) return fail(FMHIP_ERR_INVALID, "the MCMC handle is NULL");
+    ReadLock lock(s->m);
+    return get_state(s, alpha, lambda, mu, iterations);
+}
+
+int fmhip_mcmc_set_group_state(fmhip_mcmc_t s, double alpha, const double *lambda, const double *mu) {
+    if (!s || !lambda || !mu) return fail(FMHIP_ERR_INVALID, "NULL argument");
+    WriteLock lock(s->m);
+    return set_state(s, alpha, lambda, mu);
 }
 
 int fmhip_mcmc_reset_average(fmhip_mcmc_t s) {

@@ -124,15 +124,35 @@ class HipMCMC(FMLearn):
     (``computeRMSE()`` raises).  Afterwards `fm` is the last draw and ``fm.predict`` its probit score: the probability is Phi(yhat),
     not the logistic sigmoid, so ``FMModel.computeAUC`` and ``computeAccuracy`` apply to it and ``FMModel.computeLogLoss`` does not.
     `clip` (regression only): None, (lo, hi), or "labels" — the train labels' min and max, taken when the handle is made: every
-    draw's test prediction is clamped to that range before it is averaged (libFM's way; off unless asked for)."""
+    draw's test prediction is clamped to that range before it is averaged (libFM's way; off unless asked for).
+
+    `groups` (include/fmhip_mcmc_groups.h): None, a ``Metadata`` or an int array with one attribute-group id per feature (at least
+    the model's num_attribute entries; what lies behind is not read).  lambda and mu are then sampled per (parameter group, attribute
+    group) — users, items and context fields each get their own scale, as in libFM — ``state`` holds ``lambda`` and ``mu`` of
+    shape (k + 1, G), and ``group_counts`` the trained features of every group."""
 
     PRIORS = ("reg0", "init_lambda", "alpha_0", "beta_0", "alpha_lambda", "beta_lambda", "gamma_0", "mu_0")
 
     TASKS = {"regression": _ffi.MCMC_REGRESSION, "classification": _ffi.MCMC_CLASSIFICATION}
 
-    def __init__(self, seed=0, test=None, burn_in=0, sample=True, task="regression", clip=None, **priors):
+    def __init__(self, seed=0, test=None, burn_in=0, sample=True, task="regression", clip=None, groups=None, **priors):
         import math
         import operator
+        self.groups, self.n_groups = None, 1
+        if groups is not None:
+            from .metadata import Metadata
+            if isinstance(groups, Metadata):
+                table, n_groups = groups.attrGroup, groups.numAttrGroups
+            else:
+                table = np.asarray(groups)
+                if table.ndim != 1 or (len(table) and not np.issubdtype(table.dtype, np.integer)):
+                    raise TypeError("groups must be a Metadata or a 1-d integer array (one group id per feature)")
+                if len(table) and table.min() < 0:
+                    raise ValueError("feature %d has group id %d: ids are >= 0" % (int(np.argmin(table)), int(table.min())))
+                n_groups = int(table.max()) + 1 if len(table) else 1
+            if n_groups > _ffi.MCMC_MAX_GROUPS:
+                raise ValueError("%d attribute groups: at most %d (FMHIP_MCMC_MAX_GROUPS)" % (n_groups, _ffi.MCMC_MAX_GROUPS))
+            self.groups, self.n_groups = np.ascontiguousarray(table, np.int32), int(n_groups)
         if not isinstance(task, str) or task not in self.TASKS:
             raise ValueError("task must be 'regression' or 'classification', not %r" % (task,))
         self.task = task
@@ -179,8 +199,8 @@ class HipMCMC(FMLearn):
         self.last_stats = None
 
     @classmethod
-    def run(cls, seed=0, test=None, burn_in=0, sample=True, task="regression", clip=None, **priors):
-        return cls(seed=seed, test=test, burn_in=burn_in, sample=sample, task=task, clip=clip, **priors)
+    def run(cls, seed=0, test=None, burn_in=0, sample=True, task="regression", clip=None, groups=None, **priors):
+        return cls(seed=seed, test=test, burn_in=burn_in, sample=sample, task=task, clip=clip, groups=groups, **priors)
 
     def _handle(self, fm, dataset):
         L = _ffi.load()
@@ -188,6 +208,9 @@ class HipMCMC(FMLearn):
         if self._h is not None and self._for != (mh.value, dh.value):
             self.close()
         if self._h is None:
+            n = fm.num_attribute
+            if self.groups is not None and len(self.groups) < n:
+                raise ValueError("groups holds %d ids but the model has num_attribute = %d" % (len(self.groups), n))
             opts = _ffi.McmcOpts(self.seed, 1 if self.sample else 0, *[self.priors[n] for n in self.PRIORS])
             h = C.c_void_p()
             clip = self.clip
@@ -200,6 +223,12 @@ class HipMCMC(FMLearn):
             _ffi.check(L.fmhip_mcmc_create_task(mh, dh, None if self.test is None else self.test.handle, C.byref(opts), C.byref(task), C.byref(h)))
             self._h, self._for, self._k, self._n_train = h, (mh.value, dh.value), fm.num_factor, dataset.size
             self._keep = (fm, dataset)      # the handle borrows both
+            if self.groups is not None:
+                table = np.ascontiguousarray(self.groups[:n])
+                rc = L.fmhip_mcmc_set_groups(h, _ffi.ptr(table), n, self.n_groups)
+                if rc != 0:
+                    self.close()
+                    _ffi.check(rc)
             if self._pending_state is not None:
                 self.state = self._pending_state
                 self._pending_state = None
@@ -225,11 +254,13 @@ class HipMCMC(FMLearn):
 
     @property
     def state(self):
-        """dict of alpha, lambda (k + 1: group 0 = w, 1 + f = factor f), mu (k + 1), iterations."""
+        """dict of alpha, lambda (k + 1: group 0 = w, 1 + f = factor f), mu (k + 1), iterations; with `groups` lambda and mu are
+        (k + 1, G): a row per parameter group, a column per attribute group."""
         h = self._need()
         alpha, it = C.c_double(), C.c_int64()
-        lam, mu = np.empty(self._k + 1), np.empty(self._k + 1)
-        _ffi.check(_ffi.load().fmhip_mcmc_get_state(h, C.byref(alpha), _ffi.ptr(lam), _ffi.ptr(mu), C.byref(it)))
+        lam, mu = np.empty(self._state_shape()), np.empty(self._state_shape())
+        get = _ffi.load().fmhip_mcmc_get_state if self.groups is None else _ffi.load().fmhip_mcmc_get_group_state
+        _ffi.check(get(h, C.byref(alpha), _ffi.ptr(lam), _ffi.ptr(mu), C.byref(it)))
         return dict(alpha=alpha.value, **{"lambda": lam, "mu": mu, "iterations": int(it.value)})
 
     @state.setter
@@ -242,9 +273,22 @@ class HipMCMC(FMLearn):
             self._pending_state = (float(alpha), np.array(lam, np.float64), np.array(mu, np.float64))
             return
         lam, mu = np.ascontiguousarray(lam, np.float64), np.ascontiguousarray(mu, np.float64)
-        if lam.shape != (self._k + 1,) or mu.shape != (self._k + 1,):
-            raise ValueError("lambda and mu must hold k + 1 = %d values each" % (self._k + 1))
-        _ffi.check(_ffi.load().fmhip_mcmc_set_state(self._h, float(alpha), _ffi.ptr(lam), _ffi.ptr(mu)))
+        if lam.shape != self._state_shape() or mu.shape != self._state_shape():
+            raise ValueError("lambda and mu must have shape %r (k + 1%s)" % (self._state_shape(), "" if self.groups is None else ", G"))
+        put = _ffi.load().fmhip_mcmc_set_state if self.groups is None else _ffi.load().fmhip_mcmc_set_group_state
+        _ffi.check(put(self._h, float(alpha), _ffi.ptr(lam), _ffi.ptr(mu)))
+
+    def _state_shape(self):
+        return (self._k + 1,) if self.groups is None else (self._k + 1, self.n_groups)
+
+    @property
+    def group_counts(self):
+        """int64 [G]: m_a, the trained features of attribute group a (quirk Q1's last slot never counts); [m] without groups."""
+        g = C.c_int32()
+        _ffi.check(_ffi.load().fmhip_mcmc_group_info(self._need(), C.byref(g), None))
+        counts = np.empty(g.value, np.int64)
+        _ffi.check(_ffi.load().fmhip_mcmc_group_info(self._h, None, _ffi.ptr(counts)))
+        return counts
 
     def reset_average(self):
         _ffi.check(_ffi.load().fmhip_mcmc_reset_average(self._need()))

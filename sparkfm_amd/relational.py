@@ -187,3 +187,15 @@ class RelationalData:
             col[dst], val[dst] = blk.col[src], blk.val[src]
             at += ln
         return DataSet(row_ptr, col, val, self.y, name=self.name + ".flat", batch_rows=self.batch_rows, device=self.device)
+
+    def meta(self):
+        """The ``Metadata`` of the ``expand()``ed layout — a block is a group: the features relation 0's block uses are group 0,
+        relation 1's group 1, ..., the plain part's the last; a feature id no part uses joins group 0.  What
+        ``HipMCMC.run(groups=relational.meta())`` over ``relational.expand()`` takes."""
+        from .metadata import Metadata
+        parts = self._parts()
+        groups = np.zeros(self.dimension, np.int32)
+        for p, part in enumerate(parts):
+            ids = np.unique(part.col)
+            groups[ids[ids < self.dimension]] = p
+        return Metadata(self.dimension).update(groups, numAttrGroups=len(parts))
