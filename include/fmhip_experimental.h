@@ -192,6 +192,16 @@ int fmhip_comm_profile_end(fmhip_comm_t c, fmhip_comm_profile *p);
 int fmhip_model_get_optimizer_state(fmhip_model_t m, double *n0, double *nw, double *nv);
 int fmhip_model_set_optimizer_state(fmhip_model_t m, double n0, const double *nw, const double *nv);
 
+/* ---- the BPR trainer's device-built inverse map (tests) -------------------------------------- */
+/* What the device built for batch `batch` of the candidates relation after the last resample (include/fmhip_bpr.h), read back:
+ * the touched block rows tj, the list starts tptr, the rows trow, the segmented sum's work list wt / wbeg / wdst and its long lists
+ * lt / lfirst / lcount, counts[4] = {touched rows, work items, long lists, partial rows}.  The caller's arrays hold the worst case
+ * of a batch of `rows` rows: trow, tj, wt, wbeg, wdst `rows` entries, tptr rows + 1, lt, lfirst, lcount
+ * rows / FMHIP_RELATIONAL_SUM_CUT + 1; only the leading entries that count are written.  Synchronises. */
+struct fmhip_bpr;
+int fmhip_bpr_debug_inverse(struct fmhip_bpr *h, int64_t batch, int32_t *trow, int32_t *tptr, int32_t *tj, int32_t *wt, int32_t *wbeg,
+                            int32_t *wdst, int32_t *lt, int32_t *lfirst, int32_t *lcount, int32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

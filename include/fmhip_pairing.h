@@ -6,7 +6,8 @@
  * meaningful labels to fit row by row, only preferences ("this user took item A, not item B"); its objective is pairwise,
  * -log sigma(yhat_preferred - yhat_other).  That objective needs no new data path: it only changes how the residual e is formed,
  * from the margin of TWO rows instead of one.  Everything downstream of e is linear in it and is the training step of fmhip.h as
- * it stands.  Choosing which `other` row to pair with a preferred one (negative sampling) is the caller's job.
+ * it stands.  Choosing which `other` row to pair with a preferred one (negative sampling) is the caller's job
+ * here; fmhip_bpr.h draws it on the device over a block of contexts and a block of candidates.
  *
  * Same library and conventions as fmhip.h (plain C, int status, fmhip_last_error, never throws), which this header includes.
  *

@@ -11,9 +11,10 @@
 //     sparkfm::FMLearn      S/fm/FMLearn.scala:10-12         the plug-in point: learn(fm, dataset): FMModel
 //     sparkfm::HipSGD       (build-defined; SparkFM ships ALS only) one learn = one epoch of mini-batch SGD on the GPU
 //     sparkfm::HipALS       S/fm/lib/ALS.scala:15-75,202-208 the reference's own learner in fp64 on the GPU
+//     sparkfm::HipBPR       (build-defined) BPR over a contexts and a candidates block, negatives drawn on the device (include/fmhip_bpr.h)
 //     sparkfm::FM           S/fm/FM.scala:25-33, S/fm/impl/FactorizationMachines.scala:30-51   the fit loop
 //
-// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC), include/fmhip_ranking.h (ranking evaluation), include/fmhip_weights.h (per-row example weights), include/fmhip_relational.h (relational data) include/fmhip_mcmc.h (the MCMC learner) and include/fmhip_mcmc_task.h (its tasks) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
+// Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC), include/fmhip_ranking.h (ranking evaluation), include/fmhip_weights.h (per-row example weights), include/fmhip_relational.h (relational data) include/fmhip_mcmc.h (the MCMC learner), include/fmhip_mcmc_task.h (its tasks) and include/fmhip_bpr.h (the BPR trainer) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
 // here a non-zero status of the C ABI becomes sparkfm::Error carrying fmhip_last_error().  Parameters live on the host as in
 // the reference (public, mutable: `fm.w0`, `fm.w`, `fm.v` with v[f + i*k] = breeze's column-major DenseMatrix(k, n+1)); every
 // call that needs them on the device uploads them first, as jvm/HipSGD.scala does (the fit loop calls `learn` once per
@@ -40,6 +41,7 @@
 #include "fmhip_mcmc.h"
 #include "fmhip_mcmc_task.h"
 #include "fmhip_mcmc_groups.h"
+#include "fmhip_bpr.h"
 
 namespace sparkfm {
 
@@ -407,6 +409,8 @@ class FMLearn {
     virtual FMModel &learn(FMModel &fm, DataSet &dataset) = 0;
     // relational data: a learner that does not train on it says so
     virtual FMModel &learn(FMModel &, RelationalData &) { throw Error(FMHIP_ERR_UNSUPPORTED, "this learner does not train on relational data"); }
+    // a learner that trains on more than the fit loop's dataset says how wide the model must be (HipBPR: the larger of its two blocks')
+    virtual int64_t dimension() { return 0; }
 };
 
 // One learn = one epoch of mini-batch SGD over the dataset's batches (ascending order) — fmhip_sgd_epoch.
@@ -668,6 +672,104 @@ class HipMCMC : public FMLearn {
     State pending_state_;
 };
 
+// BPR on implicit feedback (include/fmhip_bpr.h): the contexts (users) once, the candidates (items) once — both one-batch DataSets
+// with disjoint feature ids, BORROWED — and per context the candidate rows it interacted with.  The negatives are drawn on the
+// device afresh for every epoch and the step is the relational one: no joined row is ever built.  n_pairs = n_neg * interactions;
+// the training order is context-ascending, rows ascending and distinct inside a context (the Python mirror's shuffle=False).
+// One learn = one epoch (fmhip_bpr_epoch): resample at t = the epochs done, then every batch of batch_pairs pairs.  loss:
+// FMHIP_LOSS_LOGISTIC is BPR, FMHIP_LOSS_SQUARED the squared pair loss; the model's pairing flag is neither read nor set.
+class HipBPR : public FMLearn {
+  public:
+    double eta, reg0, regw, regv;
+    int loss, optimizer;
+    double adagrad_eps, adagrad_init;
+    fmhip_stats last_stats{};
+    fmhip_bpr_sample_stats sample_stats{};
+    HipBPR(DataSet &contexts, DataSet &candidates, const std::vector<std::vector<int32_t>> &positives, int32_t n_neg = 1, int64_t batch_pairs = 0,
+           uint64_t seed = 0, double eta_ = 0.05, double reg0_ = 0.0, double regw_ = 0.0, double regv_ = 0.0, int loss_ = FMHIP_LOSS_LOGISTIC,
+           int optimizer_ = FMHIP_OPT_SGD, double adagrad_eps_ = 1e-10, double adagrad_init_ = 0.1)
+        : eta(eta_), reg0(reg0_), regw(regw_), regv(regv_), loss(loss_), optimizer(optimizer_), adagrad_eps(adagrad_eps_), adagrad_init(adagrad_init_),
+          contexts_(contexts), candidates_(candidates), n_neg_(n_neg), batch_pairs_(batch_pairs), seed_(seed) {
+        if ((int64_t)positives.size() != contexts.size()) throw Error(FMHIP_ERR_INVALID, "positives must hold one list per context");
+        for (size_t u = 0; u < positives.size(); ++u) {
+            std::vector<int32_t> rows = positives[u];
+            std::sort(rows.begin(), rows.end());
+            rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+            for (int32_t c : rows) {
+                inter_ctx_.push_back((int32_t)u);
+                inter_cand_.push_back(c);
+            }
+        }
+    }
+    HipBPR(const HipBPR &) = delete;
+    HipBPR &operator=(const HipBPR &) = delete;
+    ~HipBPR() { (void)fmhip_bpr_destroy(h_); }
+
+    int64_t dimension() override { return std::max(contexts_.dimension(), candidates_.dimension()); }
+    int64_t n_pairs() const { return (int64_t)inter_ctx_.size() * n_neg_; }
+    // the handle borrows the blocks' device copies: made again when either was unpersisted since (FM's fit loop unpersists its dataset)
+    fmhip_bpr_t handle() {
+        const fmhip_dataset_t c = contexts_.handle(), i = candidates_.handle();
+        if (h_ && (c != for_ctx_ || i != for_cand_)) close();
+        if (!h_) {
+            check(fmhip_bpr_create(contexts_.device(), c, i, (int64_t)inter_ctx_.size(), inter_ctx_.data(), inter_cand_.data(), n_neg_, batch_pairs_,
+                                   seed_, &h_));
+            for_ctx_ = c;
+            for_cand_ = i;
+        }
+        return h_;
+    }
+    void close() {
+        check(fmhip_bpr_destroy(h_));
+        h_ = nullptr;
+    }
+    FMModel &learn(FMModel &fm) {
+        const fmhip_bpr_t h = handle();
+        check(fmhip_model_set_loss(fm.upload(), loss));
+        check(fmhip_model_set_optimizer(fm.upload(), optimizer, adagrad_eps, adagrad_init));
+        check(fmhip_bpr_epoch(fm.upload(), h, epoch_, eta, reg0, regw, regv, nullptr, &last_stats));
+        ++epoch_;
+        fm.download();
+        return fm;
+    }
+    FMModel &learn(FMModel &fm, DataSet &) override { return learn(fm); }       // (the fit loop's dataset is not read)
+    using FMLearn::learn;
+    FMModel fit(int32_t numFactor, int epochs, uint64_t seed = 0) {
+        FMModel fm(dimension(), numFactor, 0.0, 0.01, seed, contexts_.device());
+        for (int i = 0; i < epochs; ++i) learn(fm);
+        return fm;
+    }
+    const fmhip_bpr_sample_stats &resample(int64_t t) {
+        check(fmhip_bpr_resample(handle(), t, &sample_stats));
+        return sample_stats;
+    }
+    std::vector<int32_t> negatives() {
+        std::vector<int32_t> out((size_t)n_pairs());
+        check(fmhip_bpr_negatives(handle(), out.data()));
+        return out;
+    }
+    double computePairLogLoss(FMModel &fm) {
+        double ll = 0.0;
+        check(fmhip_bpr_pair_logloss(fm.upload(), handle(), &ll, nullptr, nullptr));
+        return ll;
+    }
+    double computePairAccuracy(FMModel &fm) {
+        double ll = 0.0, conc = 0.0;
+        check(fmhip_bpr_pair_logloss(fm.upload(), handle(), &ll, &conc, nullptr));
+        return conc;
+    }
+
+  private:
+    DataSet &contexts_, &candidates_;
+    std::vector<int32_t> inter_ctx_, inter_cand_;
+    int32_t n_neg_;
+    int64_t batch_pairs_;
+    uint64_t seed_;
+    int64_t epoch_ = 0;
+    fmhip_bpr_t h_ = nullptr;
+    fmhip_dataset_t for_ctx_ = nullptr, for_cand_ = nullptr;
+};
+
 // FM(dataset, numFactor, maxIteration).learnWith(learner) — S/fm/FM.scala:25-33 and the fit loop of
 // S/fm/impl/FactorizationMachines.scala:30-51: cache; new FMModel(dimension, numFactor); maxIteration x { computeRMSE (logged);
 // fm = fml.learn(fm, dataset) }; unpersist
@@ -704,7 +806,7 @@ class FM {
     template <class Data, class Init>
     FMModel fit(Data &data, FMLearn &fml, Init init) {
         Data &ds = data.cache();                                                 // :36
-        FMModel fm(ds.dimension(), numFactor_, 0.0, 0.01, seed_, ds.device());   // :39
+        FMModel fm(std::max<int64_t>(ds.dimension(), fml.dimension()), numFactor_, 0.0, 0.01, seed_, ds.device());   // :39 (+ the learner's own width)
         init(fm);
         for (int i = 1; i <= maxIteration_; ++i) {                               // :42
             rmse_history.push_back(fm.computeRMSE(ds));                          // :43 (logged and discarded in the reference)

@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_bpr.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -40,7 +40,7 @@ SYMBOLS_EXPERIMENTAL = (
     "fmhip_dataset_partition_rows", "fmhip_step_forward_pass",
     "fmhip_comm_create_external", "fmhip_stream_wait", "fmhip_device_read", "fmhip_device_write",
     "fmhip_comm_profile_begin", "fmhip_comm_profile_end", "fmhip_comm_emulate", "fmhip_comm_emulate_load", "fmhip_comm_emulate_ranks",
-    "fmhip_model_get_optimizer_state", "fmhip_model_set_optimizer_state",
+    "fmhip_model_get_optimizer_state", "fmhip_model_set_optimizer_state", "fmhip_bpr_debug_inverse",
 )
 # ... and include/fmhip_topk.h — top-K recommendation over (contexts x candidates)
 SYMBOLS_TOPK = ("fmhip_topk", "fmhip_pair_scores")
@@ -67,6 +67,9 @@ MCMC_REGRESSION, MCMC_CLASSIFICATION = 0, 1
 # ... and include/fmhip_mcmc_groups.h — its attribute groups: a lambda and a mu per feature group
 SYMBOLS_MCMC_GROUPS = ("fmhip_mcmc_set_groups", "fmhip_mcmc_group_info", "fmhip_mcmc_get_group_state", "fmhip_mcmc_set_group_state")
 MCMC_MAX_GROUPS = 4096     # FMHIP_MCMC_MAX_GROUPS
+# ... and include/fmhip_bpr.h — the BPR trainer: negatives drawn on the device over a contexts and a candidates block
+SYMBOLS_BPR = ("fmhip_bpr_create", "fmhip_bpr_destroy", "fmhip_bpr_info", "fmhip_bpr_resample", "fmhip_bpr_negatives", "fmhip_bpr_step",
+               "fmhip_bpr_epoch", "fmhip_bpr_pair_logloss")
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -287,6 +290,14 @@ class McmcStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BprSampleStats(C.Structure):
+    """fmhip_bpr_sample_stats (include/fmhip_bpr.h)."""
+    _fields_ = [("attempts", C.c_int64), ("forced", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DatasetOpts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("hot_block", C.c_int32), ("batch_rows", C.c_int64), ("row_block_rows", C.c_int64)]
 
@@ -455,8 +466,17 @@ def load():
     L.fmhip_mcmc_group_info.argtypes = [vp, P(C.c_int32), vp]
     L.fmhip_mcmc_get_group_state.argtypes = [vp, P(dbl), vp, vp, P(i64)]
     L.fmhip_mcmc_set_group_state.argtypes = [vp, dbl, vp, vp]
+    L.fmhip_bpr_create.argtypes = [C.c_int, vp, vp, i64, vp, vp, i32, i64, C.c_uint64, P(vp)]
+    L.fmhip_bpr_destroy.argtypes = [vp]
+    L.fmhip_bpr_info.argtypes = [vp, P(i64), P(i64), P(i64), P(i64), P(i32)]
+    L.fmhip_bpr_resample.argtypes = [vp, i64, P(BprSampleStats)]
+    L.fmhip_bpr_negatives.argtypes = [vp, vp]
+    L.fmhip_bpr_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, P(Stats)]
+    L.fmhip_bpr_epoch.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, vp, P(Stats)]
+    L.fmhip_bpr_pair_logloss.argtypes = [vp, vp, P(dbl), P(dbl), P(Stats)]
+    L.fmhip_bpr_debug_inverse.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
-                 + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS):
+                 + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_BPR):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

@@ -1,0 +1,224 @@
+"""HipBPR — BPR on implicit feedback over a block of contexts and a block of candidates (include/fmhip_bpr.h).
+
+``HipSGD.run(loss="logistic", pairs=True)`` trains BPR on a flat ``DataSet.from_pairs(preferred, other)`` whose `other` rows the
+caller has to choose, join and rebuild every epoch.  ``HipBPR`` takes what ``FMModel.recommend`` takes — the users once, the items
+once — and the observed interactions as one array of candidate rows per context (the format of ``exclude=``); the negatives are
+drawn on the device afresh for every epoch and the step is the relational one, so nothing joined is ever built:
+
+    bpr = HipBPR.run(users, items, positives, n_neg=1, eta=0.05, regv=0.01)
+    fm = bpr.fit(k=16, epochs=20)                          # or FM(users, 16, maxIteration=20).learnWith(bpr)
+    fm.computeRankingMetrics(users, items, held_out, exclude=positives)
+"""
+import ctypes as C
+import operator
+
+import numpy as np
+
+from . import _ffi
+from .dataset import DataSet
+from .learn import FMLearn
+from .model import FMModel
+
+
+class HipBPR(FMLearn):
+    """One ``learn`` = one epoch: the negatives redrawn at t = the epochs done, then every batch.
+
+    `contexts`, `candidates`: single-batch training ``DataSet``s (batch_rows=0, not scoring-only, unweighted; labels unused) with
+    disjoint feature ids.  `positives`: one integer array of candidate rows per context (sorted and de-duplicated here).  There are
+    n_pairs = n_neg * (number of interactions) pairs; pair p belongs to interaction p // n_neg of the TRAINING ORDER, fixed here:
+    context-ascending (rows ascending inside a context), or with shuffle=True a ``PCG64([seed])`` permutation of that.
+    `batch_pairs`: pairs per mini-batch (0: one batch).  `seed` also keys the sampler.  `loss`: "logistic" (BPR) or "squared" (the
+    squared pair loss); `optimizer` and the AdaGrad settings as ``HipSGD``.  The model's pairing flag is neither read nor set."""
+
+    def __init__(self, contexts, candidates, positives, n_neg=1, batch_pairs=0, seed=0, shuffle=True, eta=0.05, reg0=0.0, regw=0.0,
+                 regv=0.0, loss="logistic", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1):
+        for what, d in (("contexts", contexts), ("candidates", candidates)):
+            if not isinstance(d, DataSet):
+                raise TypeError("%s must be a DataSet, not %s" % (what, type(d).__name__))
+            if d.scoring:
+                raise ValueError("%s is a scoring-only DataSet: the trainer needs its transposes (make it without scoring=True)" % what)
+            if d.weights is not None:
+                raise ValueError("%s carries example weights: the BPR trainer takes unweighted blocks" % what)
+            if 0 < d.batch_rows < d.size:
+                raise ValueError("%s has more than one batch: make it with batch_rows=0" % what)
+        if contexts.device != candidates.device:
+            raise ValueError("contexts on device %d, candidates on device %d" % (contexts.device, candidates.device))
+        self.n_neg = operator.index(n_neg)
+        if self.n_neg < 1:
+            raise ValueError("n_neg must be >= 1, not %d" % self.n_neg)
+        if candidates.size < 2:
+            raise ValueError("candidates has %d rows: a pair needs at least 2" % candidates.size)
+        self.seed = operator.index(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2^64), not %r" % (seed,))
+        if not isinstance(shuffle, bool):
+            raise ValueError("shuffle must be True or False, not %r" % (shuffle,))
+        self.contexts, self.candidates = contexts, candidates
+        ptr, rows = _ffi.row_lists(positives, contexts.size, candidates.size, "positives")
+        n = int(ptr[-1])
+        if n < 1:
+            raise ValueError("positives holds no interaction")
+        full = np.flatnonzero(np.diff(ptr) >= candidates.size)
+        if len(full):
+            raise ValueError("context %d has all %d candidate rows as positives: no negative exists for it" % (full[0], candidates.size))
+        if 2 * n * self.n_neg >= 2 ** 31:
+            raise ValueError("n_neg * interactions = %d pairs: 2 * n_pairs must stay below 2^31" % (n * self.n_neg))
+        self.positives_ptr, self.positives_rows = ptr, rows[:n].copy()
+        ictx = np.repeat(np.arange(contexts.size, dtype=np.int32), np.diff(ptr))
+        icand = self.positives_rows
+        if shuffle:
+            perm = np.random.Generator(np.random.PCG64([self.seed])).permutation(n)
+            ictx, icand = ictx[perm], icand[perm]
+        self.inter_ctx, self.inter_cand = np.ascontiguousarray(ictx, np.int32), np.ascontiguousarray(icand, np.int32)
+        self.n_pairs = n * self.n_neg
+        bp = operator.index(batch_pairs)
+        self.batch_pairs = bp if 0 < bp <= self.n_pairs else self.n_pairs
+        self.shuffle = shuffle
+        self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
+        self.loss, self.optimizer = loss, optimizer
+        self._loss_code, self._opt_code = _ffi.loss_code(loss), _ffi.optimizer_code(optimizer)
+        self.adagrad_eps, self.adagrad_init = _ffi.adagrad_settings(adagrad_eps, adagrad_init)
+        self.device = contexts.device
+        self._h, self._for = None, None
+        self._epoch = 0
+        self.last_stats = None
+        self.sample_stats = None
+
+    @classmethod
+    def run(cls, contexts, candidates, positives, **kw):
+        return cls(contexts, candidates, positives, **kw)
+
+    # -- what the fit loop reads ------------------------------------------------------------
+    @property
+    def dimension(self):
+        """The larger of the two blocks' dimensions: what a model that trains on them must hold."""
+        return max(self.contexts.dimension, self.candidates.dimension)
+
+    @property
+    def n_batches(self):
+        return (self.n_pairs + self.batch_pairs - 1) // self.batch_pairs
+
+    @property
+    def handle(self):
+        """The trainer's handle.  It borrows the two blocks' device copies: when either has been unpersisted since (``learnWith``
+        unpersists its dataset argument), the handle is made again over the fresh copies — the draw is then the one at t = 0."""
+        blocks = (self.contexts.cache()._h, self.candidates.cache()._h)
+        if self._h is not None and (self._for[0] is not blocks[0] or self._for[1] is not blocks[1]):
+            self.close()
+        if self._h is None:
+            h = C.c_void_p()
+            _ffi.check(_ffi.load().fmhip_bpr_create(self.device, blocks[0], blocks[1], len(self.inter_ctx), _ffi.ptr(self.inter_ctx),
+                                                    _ffi.ptr(self.inter_cand), self.n_neg, self.batch_pairs, self.seed, C.byref(h)))
+            self._h, self._for = h, blocks
+        return self._h
+
+    def info(self):
+        v = [C.c_int64() for _ in range(4)]
+        m = C.c_int32()
+        _ffi.check(_ffi.load().fmhip_bpr_info(self.handle, *[C.byref(x) for x in v], C.byref(m)))
+        return dict(zip(("n_pairs", "dimension", "batch_pairs", "n_batches", "n_neg"), [int(x.value) for x in v] + [int(m.value)]))
+
+    def close(self):
+        """Frees the handle (the blocks stay cached: they are the caller's)."""
+        if self._h is not None:
+            _ffi.load().fmhip_bpr_destroy(self._h)
+            self._h, self._for = None, None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- the draw ---------------------------------------------------------------------------
+    def resample(self, t):
+        """Redraws every pair's negative at epoch `t` (fmhip_bpr_resample) -> ``sample_stats``: attempts, forced."""
+        st = _ffi.BprSampleStats()
+        _ffi.check(_ffi.load().fmhip_bpr_resample(self.handle, operator.index(t), C.byref(st)))
+        self.sample_stats = st.as_dict()
+        return self.sample_stats
+
+    def negatives(self):
+        """int32 [n_pairs]: the current draw (the draw at t = 0 until the first resample or learn)."""
+        out = np.empty(self.n_pairs, np.int32)
+        _ffi.check(_ffi.load().fmhip_bpr_negatives(self.handle, _ffi.ptr(out)))
+        return out
+
+    def pairs(self):
+        """(ctx, pos, neg) row arrays [n_pairs], in training order."""
+        return np.repeat(self.inter_ctx, self.n_neg), np.repeat(self.inter_cand, self.n_neg), self.negatives()
+
+    def expand(self):
+        """The flat ``DataSet.from_pairs`` of the current draw: row 2p = context ++ positive (label 1), row 2p+1 = context ++
+        negative (label 0), batched by 2 * batch_pairs rows.  For tests and for comparison with the flat route."""
+        ctx, pos, neg = self.pairs()
+        n = 2 * self.n_pairs
+        u = np.repeat(ctx.astype(np.int64), 2)
+        i = np.empty(n, np.int64)
+        i[0::2], i[1::2] = pos, neg
+        srcs = [(self.contexts, u), (self.candidates, i)]
+        lens = [blk.row_ptr[mp + 1] - blk.row_ptr[mp] for blk, mp in srcs]
+        row_ptr = np.zeros(n + 1, np.int64)
+        np.cumsum(lens[0] + lens[1], out=row_ptr[1:])
+        col, val = np.empty(row_ptr[-1], np.int32), np.empty(row_ptr[-1], np.float64)
+        at = row_ptr[:-1].copy()
+        for (blk, mp), ln in zip(srcs, lens):
+            within = np.arange(ln.sum(), dtype=np.int64) - np.repeat(np.cumsum(ln) - ln, ln)
+            src, dst = np.repeat(blk.row_ptr[mp], ln) + within, np.repeat(at, ln) + within
+            col[dst], val[dst] = blk.col[src], blk.val[src]
+            at += ln
+        y = np.zeros(n)
+        y[0::2] = 1.0
+        return DataSet(row_ptr, col, val, y, name="bpr.flat", batch_rows=2 * self.batch_pairs, device=self.device)
+
+    # -- training ---------------------------------------------------------------------------
+    def _set_rule(self, fm):
+        """The model's loss and optimizer (never its pairing flag: the calls are pairwise by construction)."""
+        L = _ffi.load()
+        _ffi.check(L.fmhip_model_set_loss(fm.handle, self._loss_code))
+        _ffi.check(L.fmhip_model_set_optimizer(fm.handle, self._opt_code, self.adagrad_eps, self.adagrad_init))
+
+    def learn(self, fm, dataset=None):
+        """One epoch (fmhip_bpr_epoch): resample at t = the epochs done, then every batch in order.  `dataset` is not read."""
+        st = _ffi.Stats()
+        self._set_rule(fm)
+        _ffi.check(_ffi.load().fmhip_bpr_epoch(fm.handle, self.handle, self._epoch, self.eta, self.reg0, self.regw, self.regv, None,
+                                               C.byref(st)))
+        fm._device_updated()
+        self._epoch += 1
+        self.last_stats = st.as_dict()
+        return fm
+
+    def step(self, fm, batch, want_stats=True):
+        """A single mini-batch step on the current draw (fmhip_bpr_step)."""
+        st = _ffi.Stats()
+        self._set_rule(fm)
+        _ffi.check(_ffi.load().fmhip_bpr_step(fm.handle, self.handle, operator.index(batch), self.eta, self.reg0, self.regw, self.regv,
+                                              C.byref(st) if want_stats else None))
+        fm._device_updated()
+        if want_stats:
+            self.last_stats = st.as_dict()
+        return st.as_dict() if want_stats else None
+
+    def fit(self, k, epochs, seed=0, init=None):
+        """A model of the trainer's `dimension` with `k` factors, trained for `epochs` epochs.  `init` = (w0, w, v)."""
+        fm = FMModel(self.dimension, k, seed=seed, device=self.device)
+        if init is not None:
+            fm.w0, fm.w, fm.v = init
+        for _ in range(operator.index(epochs)):
+            fm = self.learn(fm)
+        return fm
+
+    # -- scores of the current pairs -------------------------------------------------------------
+    def _pair_score(self, fm):
+        ll, conc = C.c_double(), C.c_double()
+        _ffi.check(_ffi.load().fmhip_bpr_pair_logloss(fm.handle, self.handle, C.byref(ll), C.byref(conc), None))
+        return ll.value, conc.value
+
+    def computePairLogLoss(self, fm):
+        """Mean -log sigmoid(yhat(u, i+) - yhat(u, i-)) over the current pairs (fmhip_bpr_pair_logloss)."""
+        return self._pair_score(fm)[0]
+
+    def computePairAccuracy(self, fm):
+        """Share of the current pairs whose positive the model scores higher (a tie counts one half)."""
+        return self._pair_score(fm)[1]

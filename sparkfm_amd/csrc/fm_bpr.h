@@ -1,0 +1,38 @@
+// fm_bpr.h — launchers of the BPR trainer's device work (fm_bpr.hip; internal to libfmhip.so): the negative sampler and the
+// inverse map of the candidates relation, rebuilt on the device after every resample.  The rule: include/fmhip_bpr.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace fmhip {
+
+// One thread per pair p: the context of interaction p / n_neg, a row of [0, M) outside the context's positives
+// (rng::negative_row, mcmc_rng.h) into map[2p + 1] — the candidates relation's mapping; map[2p] (the positive) is not touched.
+struct BprSampleArgs {
+    uint64_t seed;
+    uint32_t t;
+    int32_t n_pairs, n_neg, M;
+    const int32_t *ictx;       // [n_inter] the interactions' contexts, in training order
+    const int64_t *pptr;       // [n_ctx + 1]
+    const int32_t *prow;       // the contexts' positives, ascending and distinct inside a list
+    int32_t *map;              // [2 * n_pairs]
+    unsigned long long *part;  // [bpr_sample_blocks][2] per-block {attempts, forced pairs}
+    unsigned long long *total; // [2] their sums (a second, one-block launch)
+};
+int bpr_sample_blocks(int64_t n_pairs);
+hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s);
+
+// The inverse map of ONE batch (fmhip::host::RelationInverse::append_batch, array for array) from the batch's slice of the mapping:
+// one radix sort of (block row, batch-local row) words over the bits the two need, the lists read off the sorted words, the work
+// list at the cut by scans.  Every output array has the capacity its worst case needs: trow / tj / wt / wbeg / wdst `rows`, tptr
+// rows + 1, lt / lfirst / lcount rows / cut + 1; counts[4] = {n_touched, n_work, n_long, n_part}.
+struct BprInverseArgs {
+    const int32_t *map;        // the batch's `rows` entries, all in [0, block_rows)
+    int32_t rows, block_rows, cut;
+    int32_t *trow, *tptr, *tj, *wt, *wbeg, *wdst, *lt, *lfirst, *lcount, *counts;
+};
+// bytes of workspace a batch of up to `rows` rows needs (0 on success in *bytes)
+hipError_t bpr_inverse_workspace(int32_t rows, int32_t block_rows, size_t *bytes);
+hipError_t launch_bpr_inverse(const BprInverseArgs &a, void *workspace, size_t bytes, hipStream_t s);
+
+}  // namespace fmhip

@@ -1,0 +1,258 @@
+// fm_bpr.hip — the BPR trainer's device work (fm_bpr.h): k_bpr_sample draws a negative row per pair, and the k_bpr_inv_* kernels
+// around one rocPRIM radix sort and two scans rebuild the candidates relation's inverse map of a batch.  Integer arithmetic only;
+// every address has one writer and nothing depends on the launch shape.
+#include "fm_bpr.h"
+#include "mcmc_rng.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+namespace fmhip {
+namespace {
+
+constexpr int kT = 256;
+using u64 = unsigned long long;
+
+inline unsigned blocks_of(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
+
+__global__ __launch_bounds__(kT) void k_bpr_sample(BprSampleArgs a) {
+    u64 att = 0, forced = 0;
+    for (int64_t p = (int64_t)blockIdx.x * kT + threadIdx.x; p < a.n_pairs; p += (int64_t)gridDim.x * kT) {
+        const int32_t u = a.ictx[p / a.n_neg];
+        const int64_t lo = a.pptr[u];
+        int at = 0, f = 0;
+        a.map[2 * p + 1] = rng::negative_row(a.seed, (uint32_t)p, a.t, (uint32_t)a.M, a.prow + lo, (int32_t)(a.pptr[u + 1] - lo), &at, &f);
+        att += (u64)at;
+        forced += (u64)f;
+    }
+    __shared__ u64 sh[2][kT / 64];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        att += __shfl_xor(att, m, 64);
+        forced += __shfl_xor(forced, m, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sh[0][threadIdx.x >> 6] = att;
+        sh[1][threadIdx.x >> 6] = forced;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        u64 s = 0;
+        for (int w = 0; w < kT / 64; ++w) s += sh[threadIdx.x][w];
+        a.part[2 * (size_t)blockIdx.x + threadIdx.x] = s;
+    }
+}
+
+// one block: the per-block partials' sums (integers: any order gives the same)
+__global__ __launch_bounds__(kT) void k_bpr_sample_total(const u64 *part, int n_blocks, u64 *total) {
+    u64 s[2] = {0, 0};
+    for (int b = threadIdx.x; b < n_blocks; b += kT) {
+        s[0] += part[2 * (size_t)b];
+        s[1] += part[2 * (size_t)b + 1];
+    }
+    __shared__ u64 sh[2][kT / 64];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        s[0] += __shfl_xor(s[0], m, 64);
+        s[1] += __shfl_xor(s[1], m, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sh[0][threadIdx.x >> 6] = s[0];
+        sh[1][threadIdx.x >> 6] = s[1];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        u64 v = 0;
+        for (int w = 0; w < kT / 64; ++w) v += sh[threadIdx.x][w];
+        total[threadIdx.x] = v;
+    }
+}
+
+// ---- the inverse map --------------------------------------------------------------------------------------------------------------
+
+// bits that hold every value of [0, n): at least 1
+inline int bits_for(int64_t n) {
+    int b = 1;
+    while (((int64_t)1 << b) < n) ++b;
+    return b;
+}
+
+// per touched list: work items, partial rows, long lists
+struct Tri { int32_t w, p, l; };
+struct TriPlus {
+    __host__ __device__ Tri operator()(const Tri &x, const Tri &y) const { return Tri{x.w + y.w, x.p + y.p, x.l + y.l}; }
+};
+
+__global__ __launch_bounds__(kT) void k_bpr_inv_keys(const int32_t *map, int32_t rows, int rbits, u64 *key) {
+    const int64_t i64 = (int64_t)blockIdx.x * kT + threadIdx.x;      // (64-bit: the grid's last block may reach past 2^31)
+    const int32_t i = (int32_t)i64;
+    if (i64 < rows) key[i] = ((u64)(uint32_t)map[i] << rbits) | (u64)(uint32_t)i;
+}
+
+// sorted words -> trow, and the flag of every position that starts a list
+__global__ __launch_bounds__(kT) void k_bpr_inv_heads(const u64 *key, int32_t rows, int rbits, int32_t *trow, int32_t *head) {
+    const int64_t i64 = (int64_t)blockIdx.x * kT + threadIdx.x;
+    if (i64 >= rows) return;
+    const int32_t i = (int32_t)i64;
+    const u64 w = key[i];
+    trow[i] = (int32_t)(w & (((u64)1 << rbits) - 1));
+    head[i] = i == 0 || (key[i - 1] >> rbits) != (w >> rbits) ? 1 : 0;
+}
+
+// tinc: the inclusive scan of the flags.  A head writes its list's block row and start; the last position closes tptr and counts the lists
+__global__ __launch_bounds__(kT) void k_bpr_inv_touch(const u64 *key, const int32_t *head, const int32_t *tinc, int32_t rows, int rbits, int32_t *tj,
+                                                      int32_t *tptr, int32_t *counts) {
+    const int64_t i64 = (int64_t)blockIdx.x * kT + threadIdx.x;
+    if (i64 >= rows) return;
+    const int32_t i = (int32_t)i64;
+    const int32_t t = tinc[i] - 1;
+    if (head[i]) {
+        tj[t] = (int32_t)(key[i] >> rbits);
+        tptr[t] = i;
+    }
+    if (i == rows - 1) {
+        tptr[t + 1] = rows;
+        counts[0] = t + 1;
+    }
+}
+
+// per list (threads past the last list: zeros): what it adds to the work list
+__global__ __launch_bounds__(kT) void k_bpr_inv_count(const int32_t *tptr, const int32_t *counts, int32_t rows, int32_t cut, Tri *tri) {
+    const int64_t t64 = (int64_t)blockIdx.x * kT + threadIdx.x;
+    if (t64 >= rows) return;
+    const int32_t t = (int32_t)t64;
+    Tri v{0, 0, 0};
+    if (t < counts[0]) {
+        const int32_t len = tptr[t + 1] - tptr[t];
+        if (len <= cut) v.w = 1;
+        else v = Tri{(len + cut - 1) / cut, (len + cut - 1) / cut, 1};
+    }
+    tri[t] = v;
+}
+
+// trix: the exclusive scan of tri.  A list of up to `cut` rows is one item that writes its block row; a longer one is cut into
+// chunks that write partial rows, plus one entry of the second pass (RelationInverse::append_batch)
+__global__ __launch_bounds__(kT) void k_bpr_inv_fill(BprInverseArgs a, const Tri *tri, const Tri *trix) {
+    const int64_t t64 = (int64_t)blockIdx.x * kT + threadIdx.x;
+    const int32_t n_t = a.counts[0];
+    if (t64 >= a.rows || t64 >= n_t) return;
+    const int32_t t = (int32_t)t64;
+    const Tri own = tri[t], at = trix[t];
+    const int32_t beg = a.tptr[t];
+    if (own.l == 0) {
+        a.wt[at.w] = t;
+        a.wbeg[at.w] = beg;
+        a.wdst[at.w] = a.tj[t];
+    } else {
+        a.lt[at.l] = t;
+        a.lfirst[at.l] = at.p;
+        a.lcount[at.l] = own.p;
+        for (int32_t c = 0; c < own.w; ++c) {
+            a.wt[at.w + c] = t;
+            a.wbeg[at.w + c] = beg + c * a.cut;
+            a.wdst[at.w + c] = -1 - (at.p + c);
+        }
+    }
+    if (t == n_t - 1) {
+        a.counts[1] = at.w + own.w;
+        a.counts[2] = at.l + own.l;
+        a.counts[3] = at.p + own.p;
+    }
+}
+
+struct InvLayout {
+    size_t key = 0, sorted = 0, head = 0, tinc = 0, tri = 0, trix = 0, tmp = 0, tmp_bytes = 0, total = 0;
+};
+
+#define BPR_TRY(expr)                    \
+    do {                                 \
+        hipError_t _e = (expr);          \
+        if (_e != hipSuccess) return _e; \
+    } while (0)
+
+hipError_t inv_layout(int32_t rows, int32_t block_rows, InvLayout *L) {
+    if (rows < 1 || block_rows < 1) return hipErrorInvalidValue;
+    const size_t N = (size_t)rows;
+    const int end_bit = bits_for(rows) + bits_for(block_rows);
+    size_t t = 0, tb = 0;
+    BPR_TRY(rocprim::radix_sort_keys(nullptr, t, (u64 *)nullptr, (u64 *)nullptr, N, 0u, (unsigned)end_bit, (hipStream_t) nullptr));
+    tb = t > tb ? t : tb;
+    BPR_TRY(rocprim::inclusive_scan(nullptr, t, (int32_t *)nullptr, (int32_t *)nullptr, N, rocprim::plus<int32_t>(), (hipStream_t) nullptr));
+    tb = t > tb ? t : tb;
+    BPR_TRY(rocprim::exclusive_scan(nullptr, t, (Tri *)nullptr, (Tri *)nullptr, Tri{0, 0, 0}, N, TriPlus(), (hipStream_t) nullptr));
+    tb = t > tb ? t : tb;
+    size_t off = 0;
+    const auto take = [&off](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    L->key = take(N * sizeof(u64));
+    L->sorted = take(N * sizeof(u64));
+    L->head = take(N * sizeof(int32_t));
+    L->tinc = take(N * sizeof(int32_t));
+    L->tri = take(N * sizeof(Tri));
+    L->trix = take(N * sizeof(Tri));
+    L->tmp = take(tb);
+    L->tmp_bytes = tb;
+    L->total = off;
+    return hipSuccess;
+}
+
+}  // namespace
+
+int bpr_sample_blocks(int64_t n_pairs) {
+    int64_t blocks = (n_pairs + kT - 1) / kT;
+    if (blocks > 4096) blocks = 4096;       // pairs grid-strided
+    if (blocks < 1) blocks = 1;
+    return (int)blocks;
+}
+
+hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s) {
+    const int blocks = bpr_sample_blocks(a.n_pairs);
+    hipLaunchKernelGGL(k_bpr_sample, dim3((unsigned)blocks), dim3(kT), 0, s, a);
+    BPR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_bpr_sample_total, dim3(1), dim3(kT), 0, s, a.part, blocks, a.total);
+    return hipGetLastError();
+}
+
+hipError_t bpr_inverse_workspace(int32_t rows, int32_t block_rows, size_t *bytes) {
+    InvLayout L;
+    BPR_TRY(inv_layout(rows, block_rows, &L));
+    *bytes = L.total;
+    return hipSuccess;
+}
+
+hipError_t launch_bpr_inverse(const BprInverseArgs &a, void *workspace, size_t bytes, hipStream_t s) {
+    InvLayout L;
+    BPR_TRY(inv_layout(a.rows, a.block_rows, &L));
+    if (!workspace || bytes < L.total || a.cut < 1) return hipErrorInvalidValue;
+    char *base = static_cast<char *>(workspace);
+    u64 *key = reinterpret_cast<u64 *>(base + L.key), *sorted = reinterpret_cast<u64 *>(base + L.sorted);
+    int32_t *head = reinterpret_cast<int32_t *>(base + L.head), *tinc = reinterpret_cast<int32_t *>(base + L.tinc);
+    Tri *tri = reinterpret_cast<Tri *>(base + L.tri), *trix = reinterpret_cast<Tri *>(base + L.trix);
+    void *tmp = base + L.tmp;
+    const size_t N = (size_t)a.rows;
+    const int rbits = bits_for(a.rows), end_bit = rbits + bits_for(a.block_rows);
+    const dim3 g(blocks_of(a.rows)), b(kT);
+    hipLaunchKernelGGL(k_bpr_inv_keys, g, b, 0, s, a.map, a.rows, rbits, key);
+    BPR_TRY(hipGetLastError());
+    size_t t = L.tmp_bytes;
+    BPR_TRY(rocprim::radix_sort_keys(tmp, t, key, sorted, N, 0u, (unsigned)end_bit, s));
+    hipLaunchKernelGGL(k_bpr_inv_heads, g, b, 0, s, sorted, a.rows, rbits, a.trow, head);
+    BPR_TRY(hipGetLastError());
+    t = L.tmp_bytes;
+    BPR_TRY(rocprim::inclusive_scan(tmp, t, head, tinc, N, rocprim::plus<int32_t>(), s));
+    hipLaunchKernelGGL(k_bpr_inv_touch, g, b, 0, s, sorted, head, tinc, a.rows, rbits, a.tj, a.tptr, a.counts);
+    BPR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_bpr_inv_count, g, b, 0, s, a.tptr, a.counts, a.rows, a.cut, tri);
+    BPR_TRY(hipGetLastError());
+    t = L.tmp_bytes;
+    BPR_TRY(rocprim::exclusive_scan(tmp, t, tri, trix, Tri{0, 0, 0}, N, TriPlus(), s));
+    hipLaunchKernelGGL(k_bpr_inv_fill, g, b, 0, s, a, tri, trix);
+    return hipGetLastError();
+}
+
+#undef BPR_TRY
+
+}  // namespace fmhip

@@ -29,6 +29,8 @@ struct RelFinishArgs {
     int32_t n_rows;
     int32_t pack_k;                // >= 0: packed rows (FwdArgs::pack_k)
     int32_t loss;                  // Loss (fm_kernels.h)
+    int32_t q_only;                // 1 (training form only; the BPR trainer): P = Q_r as it is and yhat beside it — no residual, no e, no
+                                   // statistics: launch_pair_finish (fm_pairing.h) follows and forms the pairs' from them
 };
 
 // grid of launch_rel_finish = the number of per-block statistic partials it writes (<= kMaxFwdBlocks)

@@ -61,6 +61,12 @@ __global__ __launch_bounds__(kBlock) void k_rel_finish(RelFinishArgs a) {
         float z = 0.f;
         const bool t = a.y[r] > 0.f;
         const float e = logistic ? pair_sigma_residual(yh, t, z) : yh - a.y[r];
+        if (!RESID && a.q_only) {       // the pairs' finish follows: the q row as it is, the prediction beside it
+#pragma unroll
+            for (int jj = 0; jj < J; ++jj) p_store(p + jj * LPN, Q[jj]);
+            if (l == 0) a.yhat[r] = yh;
+            continue;
+        }
         if (!RESID) {
 #pragma unroll
             for (int jj = 0; jj < J; ++jj) {
@@ -79,6 +85,7 @@ __global__ __launch_bounds__(kBlock) void k_rel_finish(RelFinishArgs a) {
             if (RESID && logistic) stl += fmaxf(t ? -yh : yh, 0.f) + log1pf(z);       // the row's log-loss, as row_finish forms it
         }
     }
+    if (!RESID && a.q_only) return;     // (uniform: the statistics are the pairs' finish's)
     double v[4] = {st1, st2, stbad, stl};
     const int where[4] = {0, 1, 2, 3};
     pair_block_sums<4>(a.bsum, v, where);

@@ -1,0 +1,322 @@
+// fmhip_bpr.hip — the BPR trainer (include/fmhip_bpr.h): the handle (an owned relational dataset of 2 n_pairs rows over the two
+// borrowed blocks), the resample
+//     k_bpr_sample (the candidates mapping's odd entries) -> per batch the inverse map on the device (fm_bpr.hip) -> the counts back
+// and the training calls, which are the relational step in its pairs mode (rel_step, fmhip_relational.hip).  The kernels are in
+// fm_bpr.hip; the host arithmetic (the positives' lists, the sampler's twin) in fmhip_host.cpp.
+#include "fmhip_internal.h"
+#include "fm_bpr.h"
+#include "fm_relational.h"
+
+#include <algorithm>
+#include <memory>
+#include <new>
+#include <vector>
+
+using namespace fmhip;
+using namespace fmhip::host;
+
+namespace {
+
+// the capacity of a batch's slices of the candidates relation's arrays: RelationInverse's offsets, at the worst case of `rows` rows
+// (a list is at least one row and a chunk at least one, so work items <= rows; a long list is more than the cut)
+int64_t long_cap(int64_t rows) { return rows / kRelSumCut + 1; }
+
+int check_block(int device, fmhip_dataset_t d, const char *what) {
+    if (!d) return fail(FMHIP_ERR_INVALID, "the %s block is NULL", what);
+    if (d->device != device) return fail(FMHIP_ERR_INVALID, "the %s block is on device %d, not %d", what, d->device, device);
+    if (d->scoring_only)
+        return fail(FMHIP_ERR_UNSUPPORTED, "the %s block was created with fmhip_rows_create (scoring only): it has no transposes to train on", what);
+    if (d->weighted)
+        return fail(FMHIP_ERR_UNSUPPORTED, "the %s block carries example weights (fmhip_dataset_create_weighted): the BPR trainer takes unweighted blocks", what);
+    if (d->batches.size() != 1)
+        return fail(FMHIP_ERR_INVALID, "the %s block has %zu batches — create it with batch_rows = 0 (one batch of all its %lld rows)", what,
+                    d->batches.size(), (long long)d->n_rows);
+    return FMHIP_OK;
+}
+
+int check_bpr(fmhip_model_t m, fmhip_bpr_t h) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    return check_rel_model(m, h->R);
+}
+
+// the sampler at epoch t, the inverse map of every batch, the batches' counts (one synchronisation); the handle's own stream
+int resample(fmhip_bpr_t h, int64_t t, fmhip_bpr_sample_stats *stats) {
+    if (t < 0 || t > 0xffffffffll) return fail(FMHIP_ERR_INVALID, "t = %lld: an epoch is in [0, 2^32)", (long long)t);
+    TRY(set_device(h->device));
+    fmhip_relational_t R = h->R;
+    fmhip_relational::Relation &rel = *R->rels[1];
+    // the mapping and the inverse map are read by the steps queued so far
+    if (R->busy_set) HIP_TRY(hipStreamWaitEvent(h->stream, R->busy, 0));
+    BprSampleArgs sa{};
+    sa.seed = h->seed;
+    sa.t = (uint32_t)t;
+    sa.n_pairs = (int32_t)h->n_pairs;
+    sa.n_neg = h->n_neg;
+    sa.M = (int32_t)h->M;
+    sa.ictx = h->ictx.p;
+    sa.pptr = h->pptr.p;
+    sa.prow = h->prow.p;
+    sa.map = rel.map.p;
+    sa.part = h->spart.p;
+    sa.total = h->stotal.p;
+    HIP_TRY(launch_bpr_sample(sa, h->stream));
+    const size_t nb = R->batches.size();
+    for (size_t b = 0; b < nb; ++b) {
+        const RelationInverse::Batch &ib = rel.batches[b];
+        BprInverseArgs ia{};
+        ia.map = rel.map.p + R->batches[b].row0;
+        ia.rows = (int32_t)R->batches[b].rows;
+        ia.block_rows = (int32_t)h->M;
+        ia.cut = kRelSumCut;
+        ia.trow = rel.trow.p + ib.row_off;
+        ia.tptr = rel.tptr.p + ib.tptr_off;
+        ia.tj = rel.tj.p + ib.t_off;
+        ia.wt = rel.wt.p + ib.w_off;
+        ia.wbeg = rel.wbeg.p + ib.w_off;
+        ia.wdst = rel.wdst.p + ib.w_off;
+        ia.lt = rel.lt.p + ib.l_off;
+        ia.lfirst = rel.lfirst.p + ib.l_off;
+        ia.lcount = rel.lcount.p + ib.l_off;
+        ia.counts = h->counts.p + 4 * b;
+        HIP_TRY(launch_bpr_inverse(ia, h->work.p, h->work.n, h->stream));
+    }
+    std::vector<int32_t> counts(4 * nb);
+    unsigned long long total[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counts.data(), h->counts.p, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(total, h->stotal.p, sizeof total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    int32_t max_part = 0;
+    for (size_t b = 0; b < nb; ++b) {
+        RelationInverse::Batch &ib = rel.batches[b];
+        const int32_t *c = counts.data() + 4 * b;
+        const int64_t rows = R->batches[b].rows;
+        // (what the slices and the step's partial rows are sized for)
+        if (c[0] < 1 || c[0] > rows || c[1] < c[0] || c[1] > rows || c[2] < 0 || c[2] >= long_cap(rows) || c[3] < 0 || c[3] > 2 * long_cap(rows))
+            return fail(FMHIP_ERR_HIP, "the inverse map of batch %zu came back with counts {%d, %d, %d, %d} for %lld rows", b, c[0], c[1], c[2], c[3],
+                        (long long)rows);
+        ib.n_touched = c[0];
+        ib.n_work = c[1];
+        ib.n_long = c[2];
+        ib.n_part = c[3];
+        max_part = std::max(max_part, c[3]);
+    }
+    rel.max_part = max_part;      // (the step's workspace grows to it: ensure_rel_workspace)
+    if (stats) {
+        stats->attempts = (int64_t)total[0];
+        stats->forced = (int64_t)total[1];
+    }
+    return FMHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmhip_bpr_create(int device, fmhip_dataset_t contexts, fmhip_dataset_t candidates, int64_t n_inter, const int32_t *inter_ctx,
+                     const int32_t *inter_cand, int32_t n_neg, int64_t batch_pairs, uint64_t seed, fmhip_bpr_t *out) {
+    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    // ---- the host checks (no HIP call before they have passed)
+    if (n_neg < 1) return fail(FMHIP_ERR_INVALID, "n_neg = %d: every interaction needs at least one negative", (int)n_neg);
+    TRY(check_block(device, contexts, "contexts"));
+    TRY(check_block(device, candidates, "candidates"));
+    const int64_t n_ctx = contexts->n_rows, M = candidates->n_rows;
+    if (M < 2) return fail(FMHIP_ERR_INVALID, "the candidates block has %lld rows: a pair needs at least 2 candidate rows", (long long)M);
+    if (n_inter < 1) return fail(FMHIP_ERR_INVALID, "n_inter = %lld: the trainer needs at least one interaction", (long long)n_inter);
+    if (!inter_ctx || !inter_cand) return fail(FMHIP_ERR_INVALID, "inter_ctx or inter_cand is NULL");
+    if (2 * (n_inter * (int64_t)n_neg) >= ((int64_t)1 << 31) || n_inter >= ((int64_t)1 << 31))
+        return fail(FMHIP_ERR_INVALID, "n_pairs = n_neg * n_inter = %d * %lld: the 2 * n_pairs rows must number less than 2^31", (int)n_neg,
+                    (long long)n_inter);
+    for (int64_t i = 0; i < n_inter; ++i) {
+        if (inter_ctx[i] < 0 || inter_ctx[i] >= n_ctx)
+            return fail(FMHIP_ERR_INVALID, "interaction %lld names context row %d, outside the contexts block's rows [0, %lld)", (long long)i,
+                        (int)inter_ctx[i], (long long)n_ctx);
+        if (inter_cand[i] < 0 || inter_cand[i] >= M)
+            return fail(FMHIP_ERR_INVALID, "interaction %lld names candidate row %d, outside the candidates block's rows [0, %lld)", (long long)i,
+                        (int)inter_cand[i], (long long)M);
+    }
+    std::vector<int64_t> pptr;
+    std::vector<int32_t> prow;
+    bpr_positive_lists(n_ctx, n_inter, inter_ctx, inter_cand, pptr, prow);
+    for (int64_t u = 0; u < n_ctx; ++u)
+        if (pptr[(size_t)u + 1] - pptr[(size_t)u] >= M)
+            return fail(FMHIP_ERR_INVALID, "context %lld has all %lld candidate rows as positives: no negative exists for it", (long long)u, (long long)M);
+    {
+        std::vector<int32_t> feats[2];
+        part_features(contexts, feats[0]);
+        part_features(candidates, feats[1]);
+        const int32_t *fp[2] = {feats[0].data(), feats[1].data()};
+        const int64_t fn[2] = {(int64_t)feats[0].size(), (int64_t)feats[1].size()};
+        const SharedFeature sh = first_shared_feature(2, fp, fn, std::max(contexts->dimension, candidates->dimension));
+        if (sh.feature >= 0)
+            return fail(FMHIP_ERR_INVALID, "feature %d occurs in the contexts block and in the candidates block: the blocks' feature sets must be "
+                                           "disjoint (every block's backward stores its gradient rows)", (int)sh.feature);
+    }
+    // ---- the relational dataset it stands for (the negatives' entries hold the positive until the first draw)
+    const int64_t n_pairs = n_inter * n_neg, N = 2 * n_pairs;
+    if (batch_pairs <= 0 || batch_pairs > n_pairs) batch_pairs = n_pairs;
+    std::unique_ptr<fmhip_bpr> H(new (std::nothrow) fmhip_bpr());
+    if (!H) return fail(FMHIP_ERR_NOMEM, "out of host memory");
+    H->device = device;
+    H->n_inter = n_inter;
+    H->n_pairs = n_pairs;
+    H->batch_pairs = batch_pairs;
+    H->n_ctx = n_ctx;
+    H->M = M;
+    H->n_neg = n_neg;
+    H->seed = seed;
+    {
+        std::vector<double> y((size_t)N);
+        std::vector<int32_t> mc((size_t)N), mi((size_t)N);
+        for (int64_t p = 0; p < n_pairs; ++p) {
+            const int64_t i = p / n_neg;
+            y[(size_t)(2 * p)] = 1.0;
+            y[(size_t)(2 * p + 1)] = 0.0;
+            mc[(size_t)(2 * p)] = mc[(size_t)(2 * p + 1)] = inter_ctx[i];
+            mi[(size_t)(2 * p)] = mi[(size_t)(2 * p + 1)] = inter_cand[i];
+        }
+        const fmhip_dataset_t blocks[2] = {contexts, candidates};
+        const int32_t *maps[2] = {mc.data(), mi.data()};
+        TRY(fmhip_relational_create(device, N, y.data(), 2, blocks, maps, nullptr, 2 * batch_pairs, &H->R));
+    }
+    TRY(set_device(device));
+    fmhip_relational_t R = H->R;
+    fmhip_relational::Relation &rel = *R->rels[1];
+    // the candidates relation's inverse map: buffers at their worst case, O(rows + rows / cut) in all, filled by the device
+    const size_t nb = R->batches.size();
+    int64_t l_total = 0;
+    for (size_t b = 0; b < nb; ++b) {
+        RelationInverse::Batch &ib = rel.batches[b];
+        ib = RelationInverse::Batch{};
+        ib.row_off = ib.t_off = ib.w_off = R->batches[b].row0;
+        ib.tptr_off = R->batches[b].row0 + (int64_t)b;
+        ib.l_off = l_total;
+        l_total += long_cap(R->batches[b].rows);
+    }
+    TRY(rel.trow.alloc((size_t)N)); TRY(rel.tj.alloc((size_t)N)); TRY(rel.tptr.alloc((size_t)N + nb));
+    TRY(rel.wt.alloc((size_t)N)); TRY(rel.wbeg.alloc((size_t)N)); TRY(rel.wdst.alloc((size_t)N));
+    TRY(rel.lt.alloc((size_t)l_total)); TRY(rel.lfirst.alloc((size_t)l_total)); TRY(rel.lcount.alloc((size_t)l_total));
+    TRY(H->counts.alloc(4 * nb));
+    TRY(H->ictx.alloc((size_t)n_inter));
+    HIP_TRY(hipMemcpy(H->ictx.p, inter_ctx, (size_t)n_inter * sizeof(int32_t), hipMemcpyHostToDevice));
+    TRY(H->pptr.alloc(pptr.size()));
+    HIP_TRY(hipMemcpy(H->pptr.p, pptr.data(), pptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    TRY(H->prow.alloc(std::max<size_t>(prow.size(), 1)));
+    if (!prow.empty()) HIP_TRY(hipMemcpy(H->prow.p, prow.data(), prow.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    TRY(H->spart.alloc(2 * (size_t)bpr_sample_blocks(n_pairs)));
+    TRY(H->stotal.alloc(2));
+    size_t work = 0;
+    HIP_TRY(bpr_inverse_workspace((int32_t)R->max_rows, (int32_t)M, &work));
+    TRY(H->work.alloc(work));
+    HIP_TRY(hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking));
+    TRY(resample(H.get(), 0, nullptr));
+    *out = H.release();
+    return FMHIP_OK;
+}
+
+int fmhip_bpr_destroy(fmhip_bpr_t h) {
+    if (!h) return FMHIP_OK;
+    (void)hipSetDevice(h->device);
+    std::unique_ptr<fmhip_bpr>(h).reset();
+    return FMHIP_OK;
+}
+
+int fmhip_bpr_info(fmhip_bpr_t h, int64_t *n_pairs, int64_t *dimension, int64_t *batch_pairs, int64_t *n_batches, int32_t *n_neg) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (n_pairs) *n_pairs = h->n_pairs;
+    if (dimension) *dimension = h->R->dimension;
+    if (batch_pairs) *batch_pairs = h->batch_pairs;
+    if (n_batches) *n_batches = (int64_t)h->R->batches.size();
+    if (n_neg) *n_neg = h->n_neg;
+    return FMHIP_OK;
+}
+
+int fmhip_bpr_resample(fmhip_bpr_t h, int64_t t, fmhip_bpr_sample_stats *stats) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    return resample(h, t, stats);
+}
+
+int fmhip_bpr_negatives(fmhip_bpr_t h, int32_t *out) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    TRY(set_device(h->device));
+    std::vector<int32_t> map((size_t)(2 * h->n_pairs));
+    HIP_TRY(hipMemcpy(map.data(), h->R->rels[1]->map.p, map.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int64_t p = 0; p < h->n_pairs; ++p) out[p] = map[(size_t)(2 * p + 1)];
+    return FMHIP_OK;
+}
+
+int fmhip_bpr_step(fmhip_model_t m, fmhip_bpr_t h, int64_t batch, double eta, double reg0, double regw, double regv, fmhip_stats *stats) {
+    WriteLock lock(m);
+    TRY(check_bpr(m, h));
+    if (batch < 0 || batch >= (int64_t)h->R->batches.size())
+        return fail(FMHIP_ERR_INVALID, "batch %lld out of range [0, %zu)", (long long)batch, h->R->batches.size());
+    TRY(rel_step(m, h->R, batch, Sgd{eta, reg0, regw, regv}, nullptr, true));
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        TRY(read_scal(m, stats));
+        stats->nnz = m->last_nnz;
+        stats->steps = 1;
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_bpr_epoch(fmhip_model_t m, fmhip_bpr_t h, int64_t t, double eta, double reg0, double regw, double regv, const int64_t *order,
+                    fmhip_stats *stats) {
+    WriteLock lock(m);
+    TRY(check_bpr(m, h));
+    const int64_t nb = (int64_t)h->R->batches.size();
+    if (order)
+        for (int64_t j = 0; j < nb; ++j)
+            if (order[j] < 0 || order[j] >= nb) return fail(FMHIP_ERR_INVALID, "batch %lld out of range [0, %lld)", (long long)order[j], (long long)nb);
+    TRY(resample(h, t, nullptr));
+    HIP_TRY(hipMemsetAsync(m->acc.p, 0, 4 * sizeof(double), m->stream));
+    const Sgd sgd{eta, reg0, regw, regv};
+    int64_t nnz = 0;
+    for (int64_t j = 0; j < nb; ++j) {
+        TRY(rel_step(m, h->R, order ? order[j] : j, sgd, m->acc.p, true));
+        nnz += m->last_nnz;
+    }
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        TRY(read_acc(m, stats));
+        stats->nnz = nnz;
+        stats->steps = nb;
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_bpr_pair_logloss(fmhip_model_t m, fmhip_bpr_t h, double *logloss, double *concordance, fmhip_stats *stats) {
+    ReadLock lock(m);
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (!logloss) return fail(FMHIP_ERR_INVALID, "logloss is NULL");
+    return rel_pair_score(m, h->R, logloss, concordance, stats);
+}
+
+int fmhip_bpr_debug_inverse(struct fmhip_bpr *h, int64_t batch, int32_t *trow, int32_t *tptr, int32_t *tj, int32_t *wt, int32_t *wbeg,
+                            int32_t *wdst, int32_t *lt, int32_t *lfirst, int32_t *lcount, int32_t *counts) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (batch < 0 || batch >= (int64_t)h->R->batches.size())
+        return fail(FMHIP_ERR_INVALID, "batch %lld out of range [0, %zu)", (long long)batch, h->R->batches.size());
+    if (!trow || !tptr || !tj || !wt || !wbeg || !wdst || !lt || !lfirst || !lcount || !counts) return fail(FMHIP_ERR_INVALID, "an out array is NULL");
+    TRY(set_device(h->device));
+    const fmhip_relational::Relation &rel = *h->R->rels[1];
+    const RelationInverse::Batch &ib = rel.batches[(size_t)batch];
+    const auto back = [](int32_t *dst, const int32_t *src, int64_t n) {
+        return n > 0 ? hipMemcpy(dst, src, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(back(trow, rel.trow.p + ib.row_off, h->R->batches[(size_t)batch].rows));
+    HIP_TRY(back(tptr, rel.tptr.p + ib.tptr_off, (int64_t)ib.n_touched + 1));
+    HIP_TRY(back(tj, rel.tj.p + ib.t_off, ib.n_touched));
+    HIP_TRY(back(wt, rel.wt.p + ib.w_off, ib.n_work));
+    HIP_TRY(back(wbeg, rel.wbeg.p + ib.w_off, ib.n_work));
+    HIP_TRY(back(wdst, rel.wdst.p + ib.w_off, ib.n_work));
+    HIP_TRY(back(lt, rel.lt.p + ib.l_off, ib.n_long));
+    HIP_TRY(back(lfirst, rel.lfirst.p + ib.l_off, ib.n_long));
+    HIP_TRY(back(lcount, rel.lcount.p + ib.l_off, ib.n_long));
+    HIP_TRY(back(counts, h->counts.p + 4 * batch, 4));
+    return FMHIP_OK;
+}
+
+}  // extern "C"

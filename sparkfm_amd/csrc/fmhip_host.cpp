@@ -726,6 +726,39 @@ void RelationInverse::append_batch(const int32_t *map, int64_t rows, int64_t blo
     batches.push_back(b);
 }
 
+// ---- the BPR trainer (include/fmhip_bpr.h) ------------------------------------------------------------------------------
+
+void bpr_positive_lists(int64_t n_ctx, int64_t n_inter, const int32_t *inter_ctx, const int32_t *inter_cand, std::vector<int64_t> &ptr,
+                        std::vector<int32_t> &rows) {
+    // counting sort by context, every list sorted, its repeats dropped, the lists closed up
+    std::vector<int64_t> at((size_t)n_ctx + 1, 0);
+    for (int64_t i = 0; i < n_inter; ++i) ++at[(size_t)inter_ctx[i] + 1];
+    for (int64_t u = 0; u < n_ctx; ++u) at[(size_t)u + 1] += at[(size_t)u];
+    std::vector<int32_t> all((size_t)n_inter);
+    {
+        std::vector<int64_t> cur(at.begin(), at.end() - 1);
+        for (int64_t i = 0; i < n_inter; ++i) all[(size_t)cur[(size_t)inter_ctx[i]]++] = inter_cand[i];
+    }
+    ptr.assign((size_t)n_ctx + 1, 0);
+    rows.clear();
+    rows.reserve((size_t)n_inter);
+    for (int64_t u = 0; u < n_ctx; ++u) {
+        auto lo = all.begin() + at[(size_t)u], hi = all.begin() + at[(size_t)u + 1];
+        std::sort(lo, hi);
+        hi = std::unique(lo, hi);
+        rows.insert(rows.end(), lo, hi);
+        ptr[(size_t)u + 1] = (int64_t)rows.size();
+    }
+}
+
+int32_t bpr_negative(uint64_t seed, uint32_t p, uint32_t t, int32_t M, const int32_t *list, int32_t len, int *attempts, int *forced) {
+    int a = 0, f = 0;
+    const int32_t c = rng::negative_row(seed, p, t, (uint32_t)M, list, len, &a, &f);
+    if (attempts) *attempts = a;
+    if (forced) *forced = f;
+    return c;
+}
+
 // ---- the MCMC learner's draws -------------------------------------------------------------------------------------------
 
 double mcmc_uniform(uint64_t seed, uint32_t index, uint32_t group, uint32_t t, uint32_t stream) { return rng::uniform(seed, index, group, t, stream); }

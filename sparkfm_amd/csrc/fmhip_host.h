@@ -183,6 +183,15 @@ struct RelationInverse {
     void append_batch(const int32_t *map, int64_t rows, int64_t block_rows, int32_t cut, std::vector<int32_t> &count);
 };
 
+// ---- the BPR trainer (fmhip_bpr_create, include/fmhip_bpr.h) ---------------------------------------------------------------------
+// The contexts' positives from the interactions (any order, repeats allowed; every entry inside its block: checked by the caller):
+// ptr[n_ctx + 1], rows = the lists one after the other, each ascending and distinct — what _ffi.row_lists builds in Python.
+void bpr_positive_lists(int64_t n_ctx, int64_t n_inter, const int32_t *inter_ctx, const int32_t *inter_cand, std::vector<int64_t> &ptr,
+                        std::vector<int32_t> &rows);
+// The negative row of pair p at epoch t: the host twin of k_bpr_sample (rng::negative_row, mcmc_rng.h — the same integer code, so
+// the two agree bit for bit).  list: the context's positives (ascending, distinct, len < M).  attempts / forced: nullable
+int32_t bpr_negative(uint64_t seed, uint32_t p, uint32_t t, int32_t M, const int32_t *list, int32_t len, int *attempts, int *forced = nullptr);
+
 // ---- the MCMC learner's draws (fmhip_mcmc_epoch, include/fmhip_mcmc.h; the generator: mcmc_rng.h) ------------------------------
 // Counters are (index, group, t, stream); t = the epochs the handle has completed.
 double mcmc_uniform(uint64_t seed, uint32_t index, uint32_t group, uint32_t t, uint32_t stream);

@@ -6,6 +6,7 @@
 #include "../../include/fmhip_experimental.h"   // (includes fmhip.h: the library implements both surfaces)
 #include "../../include/fmhip_pairing.h"        // (enum fmhip_pairing: the model carries the switch)
 #include "../../include/fmhip_relational.h"     // (fmhip_relational_t: the handle's state is declared below)
+#include "../../include/fmhip_bpr.h"            // (fmhip_bpr_t: likewise)
 #include "fm_kernels.h"
 #include "fmhip_host.h"   // the pure host arithmetic (shards, relabelling, batch metadata, band plan, ALS levels, the dp plan's cuts and shares)
 
@@ -300,6 +301,28 @@ struct fmhip_relational {
     }
 };
 
+// A BPR trainer (include/fmhip_bpr.h): an OWNED relational dataset of 2 n_pairs rows over the two borrowed blocks — relation 0 the
+// contexts (its inverse map built once on the host), relation 1 the candidates, whose mapping's odd entries the sampler rewrites
+// and whose inverse map the device rebuilds (buffers at their worst case, the batches' counts read back once per resample) —
+// the interactions' contexts and the contexts' positives on the device, and a stream of its own for the resample.
+struct fmhip_bpr {
+    template <typename T> using DevBuf = fmhip::host::DevBuf<T>;
+    int device = 0;
+    fmhip_relational_t R = nullptr;
+    int64_t n_inter = 0, n_pairs = 0, batch_pairs = 0, n_ctx = 0, M = 0;
+    int32_t n_neg = 0;
+    uint64_t seed = 0;
+    DevBuf<int32_t> ictx, prow, counts;        // counts: [n_batches][4]
+    DevBuf<int64_t> pptr;
+    DevBuf<unsigned long long> spart, stotal;  // the sampler's per-block partials and their sums
+    DevBuf<char> work;                         // the inverse build's workspace, for the largest batch
+    hipStream_t stream = nullptr;
+    ~fmhip_bpr() {
+        if (R) (void)fmhip_relational_destroy(R);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
 struct fmhip_model {
     template <typename T> using DevBuf = fmhip::host::DevBuf<T>;
     using ProfRec = fmhip::host::ProfRec;
@@ -455,6 +478,14 @@ int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t 
 // none)?  Under AdaGrad only without decay (`r`: the rule to judge by — the model's own, or the one a plan agreed)
 bool lazy_decay_ok(fmhip_model_t m, const Sgd &s, const TrainRule &r);
 int read_scal(fmhip_model_t m, fmhip_stats *st);
+// ---- fmhip_relational.hip
+void part_features(fmhip_dataset_t d, std::vector<int32_t> &out);     // a part's features: its transposes' columns and the hot block's ids
+int check_rel_model(fmhip_model_t m, fmhip_relational_t R);           // device and dimension; sets the device
+// one relational step of batch b, asynchronous on the model's stream; acc (nullable): the epoch's fp64 accumulators.  pairs (the
+// BPR trainer): rows 2p / 2p+1 are one example — the finish leaves Q_r and yhat_r, launch_pair_finish forms the residuals
+int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs = false);
+// ---- fmhip_score.hip: fmhip_pair_logloss over the rows of a relational dataset without a plain part (the caller holds the model's lock shared)
+int rel_pair_score(fmhip_model_t m, fmhip_relational_t R, double *logloss, double *concordance, fmhip_stats *stats);
 // the four leading numbers of a statistics block {sum e, sum e^2, rows, rows with a non-finite prediction} (the packed gradient's
 // fp32 head, an fp64 accumulator) into *st; nnz, steps and what a fifth slot means are the caller's
 template <typename T>

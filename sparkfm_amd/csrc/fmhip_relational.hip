@@ -3,9 +3,11 @@
 //     fold_scales -> kFwdQ forward of every block (whole) -> kFwdQ forward of the plain part's batch -> k_rel_finish
 //     -> per relation: k_rel_gather_sum, then the existing backward + fixups over the block's CSC with (P_b, e_b) for (P, e)
 //     -> the plain part's backward with P as it is -> the step's statistics (launch_reduce_blocks) -> the dense launch_apply
+// The BPR trainer (fmhip_bpr.hip) runs the same step in its pairs mode: the finish leaves Q_r and yhat_r, launch_pair_finish forms e.
 // The scoring calls are in fmhip_score.hip (they work in a ScorePass); the kernels in fm_relational.hip; the host arithmetic
 // (mapping check, disjointness of the parts' features, the inverse map's counting sort) in fmhip_host.cpp.
 #include "fmhip_internal.h"
+#include "fm_pairing.h"
 #include "fm_relational.h"
 
 #include <algorithm>
@@ -34,22 +36,6 @@ const char *part_name(int p, int m, char (&buf)[32]) {
     return buf;
 }
 
-// a part's features: the columns of its batches' transposes and the dense hot block's ids
-void part_features(fmhip_dataset_t d, std::vector<int32_t> &out) {
-    out = d->h_cfeat;
-    for (int32_t id : d->hot_ids)
-        if (id >= 0) out.push_back(id);
-}
-
-int check_model(fmhip_model_t m, fmhip_relational_t R) {
-    if (!m || !R) return fail(FMHIP_ERR_INVALID, "model or relational dataset is NULL");
-    if (m->device != R->device) return fail(FMHIP_ERR_INVALID, "model on device %d, relational dataset on device %d", m->device, R->device);
-    if (R->dimension > m->n)
-        return fail(FMHIP_ERR_SHAPE, "relational dataset has feature index %lld but the model has num_attribute = %lld", (long long)R->dimension,
-                    (long long)m->n);
-    return set_device(m->device);
-}
-
 int check_rel_batch(fmhip_relational_t R, int64_t batch) {
     if (batch < 0 || batch >= (int64_t)R->batches.size())
         return fail(FMHIP_ERR_INVALID, "batch %lld out of range [0, %zu)", (long long)batch, R->batches.size());
@@ -76,8 +62,29 @@ int ensure_rel_workspace(fmhip_model_t m, fmhip_relational_t R) {
     return FMHIP_OK;
 }
 
+}  // namespace
+
+namespace fmhip {
+namespace host {
+
+// a part's features: the columns of its batches' transposes and the dense hot block's ids
+void part_features(fmhip_dataset_t d, std::vector<int32_t> &out) {
+    out = d->h_cfeat;
+    for (int32_t id : d->hot_ids)
+        if (id >= 0) out.push_back(id);
+}
+
+int check_rel_model(fmhip_model_t m, fmhip_relational_t R) {
+    if (!m || !R) return fail(FMHIP_ERR_INVALID, "model or relational dataset is NULL");
+    if (m->device != R->device) return fail(FMHIP_ERR_INVALID, "model on device %d, relational dataset on device %d", m->device, R->device);
+    if (R->dimension > m->n)
+        return fail(FMHIP_ERR_SHAPE, "relational dataset has feature index %lld but the model has num_attribute = %lld", (long long)R->dimension,
+                    (long long)m->n);
+    return set_device(m->device);
+}
+
 // one relational step of batch b, asynchronous on the model's stream; acc (nullable): the epoch's fp64 accumulators
-int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc) {
+int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs) {
     const fmhip_relational::Batch &B = R->batches[(size_t)b];
     TRY(fold_scales(m));                     // the dense update only: the tables are at scale 1 from here on
     TRY(ensure_rel_workspace(m, R));
@@ -110,12 +117,28 @@ int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, d
     fa.yplain = m->yhat.p;
     fa.y = R->y.p + B.row0;
     fa.e = m->e.p;
-    fa.yhat = nullptr;
+    fa.yhat = pairs ? m->yhat.p : nullptr;
     fa.bsum = m->bsum.p;
     fa.n_rows = (int32_t)B.rows;
     fa.pack_k = m->pack_k();
     fa.loss = m->rule.loss;
+    fa.q_only = pairs ? 1 : 0;
     HIP_TRY(launch_rel_finish(m->Kp, fa, false, m->stream, &m->fwd_parts));
+    if (pairs) {
+        // the BPR trainer: the finish left Q_r in P and yhat_r beside it, as the flat paired step's kFwdQ forward does; the pairs'
+        // finish (fm_pairing.hip) turns them into P_r = Q_r e_r, e and the statistics partials (its own block count)
+        PairArgs pa{};
+        pa.P = m->P.p;
+        pa.yhat = m->yhat.p;
+        pa.y = R->y.p + B.row0;          // (batches are even: 8-byte aligned)
+        pa.e = m->e.p;
+        pa.bsum = m->bsum.p;
+        pa.n_pairs = (int32_t)(B.rows / 2);
+        pa.pack_k = m->pack_k();
+        pa.loss = m->rule.loss;
+        pa.c = nullptr;
+        HIP_TRY(launch_pair_finish(m->Kp, pa, m->stream, &m->fwd_parts));
+    }
     m->grad_dirty = true;
     m->last_nnz = nnz;
     m->last_rows = B.rows;
@@ -162,8 +185,13 @@ int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, d
     return FMHIP_OK;
 }
 
+}  // namespace host
+}  // namespace fmhip
+
+namespace {
+
 int check_train_rel(fmhip_model_t m, fmhip_relational_t R) {
-    TRY(check_model(m, R));
+    TRY(check_rel_model(m, R));
     if (const char *why = refusal(Path::kRelational, m->rule)) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
     return FMHIP_OK;
 }

@@ -735,7 +735,9 @@ struct RelScoreBufs {       // (declared before the pass: freed after it has dra
     std::vector<std::unique_ptr<DevBuf<float>>> Q, yq;
 };
 
-int rel_score_pass(fmhip_model_t m, fmhip_relational_t R, double *yhat, fmhip_stats *st, double *logloss) {
+// pair_sums (the BPR trainer; no plain part, even batches): the rows 2j / 2j+1 are scored as pairs — k_pair_score's partials over the
+// predictions the finish left, as fmhip_pair_logloss — and [0] = the concordant pairs, [1] = the sum of the pairs' log-losses
+int rel_score_pass(fmhip_model_t m, fmhip_relational_t R, double *yhat, fmhip_stats *st, double *logloss, double *pair_sums = nullptr) {
     if (!m || !R) return fail(FMHIP_ERR_INVALID, "model or relational dataset is NULL");
     if (m->device != R->device) return fail(FMHIP_ERR_INVALID, "model on device %d, relational dataset on device %d", m->device, R->device);
     if (R->dimension > m->n)
@@ -780,7 +782,8 @@ int rel_score_pass(fmhip_model_t m, fmhip_relational_t R, double *yhat, fmhip_st
         fa.n_rows = (int32_t)B.rows;
         int parts = 0;
         HIP_TRY(launch_rel_finish(m->Kp, fa, true, cx.s, &parts));
-        HIP_TRY(launch_reduce_blocks(cx.bsum.p, parts, (int32_t)B.rows, nullptr, cx.acc.p, cx.s, logloss != nullptr));
+        if (pair_sums) HIP_TRY(launch_pair_score(cx.yhat.p, R->y.p + B.row0, (int32_t)(B.rows / 2), cx.bsum.p, cx.s, &parts));
+        HIP_TRY(launch_reduce_blocks(cx.bsum.p, parts, (int32_t)B.rows, nullptr, cx.acc.p, cx.s, logloss != nullptr || pair_sums != nullptr));
         if (yhat) TRY(pass.copy_back(cx.yhat.p, B.rows, 1, 1, hbuf, yhat + B.row0));
     }
     double h[5];
@@ -789,10 +792,34 @@ int rel_score_pass(fmhip_model_t m, fmhip_relational_t R, double *yhat, fmhip_st
     s.nnz = R->block_nnz + (R->plain ? R->plain->nnz : 0);
     if (st) *st = s;
     if (logloss) *logloss = h[4];
+    if (pair_sums) {
+        pair_sums[0] = h[0];
+        pair_sums[1] = h[4];
+    }
     return FMHIP_OK;
 }
 
 }  // namespace
+
+namespace fmhip {
+namespace host {
+
+int rel_pair_score(fmhip_model_t m, fmhip_relational_t R, double *logloss, double *concordance, fmhip_stats *stats) {
+    fmhip_stats st;
+    double sums[2] = {0.0, 0.0};
+    TRY(rel_score_pass(m, R, nullptr, &st, nullptr, sums));
+    const double pairs = (double)(R->n_rows / 2);
+    *logloss = pairs > 0 ? sums[1] / pairs : 0.0;
+    if (concordance) *concordance = pairs > 0 ? sums[0] / pairs : 0.0;
+    if (stats) {
+        *stats = st;
+        stats->sum_e = 0.0;        // e_2j = -e_2j+1
+    }
+    return FMHIP_OK;
+}
+
+}  // namespace host
+}  // namespace fmhip
 
 extern "C" {
 

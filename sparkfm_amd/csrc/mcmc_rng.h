@@ -3,7 +3,8 @@
 // numbers: as easy as 1, 2, 3", SC 2011), the two variates derived from one block of it, and the probit link's truncated
 // normal (include/fmhip_mcmc_task.h), a bounded rejection loop over blocks of a stream of its own.  Integer arithmetic only up
 // to u53; log / cos / sqrt are the caller's libm (host) or the device's (kernel), so host and device normals agree to a
-// few ulp, not bit for bit.  No HIP header: g++ compiles it for the sanitizer harnesses.
+// few ulp, not bit for bit.  Also here: the BPR trainer's negative rows (include/fmhip_bpr.h; fm_bpr.hip), integer arithmetic
+// throughout, so those agree bit for bit.  No HIP header: g++ compiles it for the sanitizer harnesses.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -18,7 +19,7 @@ namespace fmhip {
 namespace rng {
 
 // the streams of a counter (index, group, t, stream): what a draw is for
-enum { kStreamCoord = 0, kStreamW0 = 1, kStreamAlpha = 2, kStreamLambda = 3, kStreamMu = 4, kStreamTarget = 5 };
+enum { kStreamCoord = 0, kStreamW0 = 1, kStreamAlpha = 2, kStreamLambda = 3, kStreamMu = 4, kStreamTarget = 5, kStreamNegative = 6 };
 
 struct Block { uint32_t x[4]; };
 
@@ -104,6 +105,42 @@ FMHIP_RNG_FN double truncated_normal_mean(double a) {
 
 // Phi(x) = erfc(-x / sqrt 2) / 2: the probability a probit score stands for
 FMHIP_RNG_FN double normal_cdf(double x) { return 0.5 * erfc(-x / 1.4142135623730951); }
+
+// ---- the BPR trainer's negative rows (include/fmhip_bpr.h) ------------------------------------------------------------------------
+constexpr int kNegMaxAttempts = 64;
+
+// is row c in the ascending list?
+FMHIP_RNG_FN bool row_listed(const int32_t *list, int32_t len, int32_t c) {
+    int32_t lo = 0, hi = len;
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (list[mid] < c) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < len && list[lo] == c;
+}
+
+// A row of [0, M) outside `list` (ascending, distinct, fewer than M entries: the caller has checked) for pair p at epoch t, by
+// rejection: attempt a = 0 .. 63 takes word a & 3 of the block of counter (p, a >> 2, t, kStreamNegative), c = (word * M) >> 32,
+// accepted if c is not listed.  All 64 rejected: from the last c on, c = (c + 1) mod M until c is not listed (at most len steps);
+// *forced = 1.  *attempts: the attempts made (1 .. 64).  Integer arithmetic only: host and device agree bit for bit.
+FMHIP_RNG_FN int32_t negative_row(uint64_t seed, uint32_t p, uint32_t t, uint32_t M, const int32_t *list, int32_t len, int *attempts, int *forced) {
+    int32_t c = 0;
+    Block b{};
+    for (int a = 0; a < kNegMaxAttempts; ++a) {
+        if ((a & 3) == 0) b = block_of(seed, p, (uint32_t)(a >> 2), t, kStreamNegative);
+        c = (int32_t)(((uint64_t)b.x[a & 3] * M) >> 32);
+        if (!row_listed(list, len, c)) {
+            *attempts = a + 1;
+            *forced = 0;
+            return c;
+        }
+    }
+    for (int32_t i = 0; i <= len && row_listed(list, len, c); ++i) c = (uint32_t)(c + 1) == M ? 0 : c + 1;
+    *attempts = kNegMaxAttempts;
+    *forced = 1;
+    return c;
+}
 
 }  // namespace rng
 }  // namespace fmhip

@@ -43,12 +43,13 @@ class FactorizationMachines:
     def learnWith(self, fml, init=None):
         """S/fm/impl/FactorizationMachines.scala:30-51: cache; new FMModel(dimension, numFactor);
         maxIteration x { computeRMSE (logged); fm = fml.learn(fm, dataset) }; unpersist.
-        `init` = (w0, w, v) injects parameters (the reference's own init is unseeded, quirk Q2)."""
+        `init` = (w0, w, v) injects parameters (the reference's own init is unseeded, quirk Q2).  A learner that trains on more
+        than `dataset` says so through a `dimension` of its own (``HipBPR``: the larger of its two blocks'): the model holds both."""
         ds = self.dataset
         if self.relations:
             ds = RelationalData(ds.y, self.relations, plain=ds if ds.nnz else None, batch_rows=ds.batch_rows, name=ds.name, device=ds.device)
         ds = ds.cache()                                               # :36
-        fm = FMModel(ds.dimension, self.numFactor, seed=self.seed, device=ds.device)   # :39
+        fm = FMModel(max(ds.dimension, getattr(fml, "dimension", 0)), self.numFactor, seed=self.seed, device=ds.device)   # :39
         if init is not None:
             fm.w0, fm.w, fm.v = init
         for i in range(1, self.maxIteration + 1):                     # :42
