@@ -42,7 +42,8 @@
  *    model, a prior that is not finite and > 0 (mu_0: finite; reg0: finite and >= 0).
  *  - determinism: bit-identical run to run for a given seed; the draws do not depend on the walk the sweep takes.
  * Classification (the probit link) and clipping to the label range: fmhip_mcmc_task.h, over this handle.
- * libFM's attribute groups (a lambda and a mu per feature group): fmhip_mcmc_groups.h.  Not here: relational / weighted data.
+ * libFM's attribute groups (a lambda and a mu per feature group): fmhip_mcmc_groups.h.  Relational data, swept by blocks:
+ * fmhip_mcmc_relational.h.  Not here: weighted data.
  */
 #ifndef FMHIP_MCMC_H
 #define FMHIP_MCMC_H

@@ -41,6 +41,7 @@
 #include "fmhip_mcmc.h"
 #include "fmhip_mcmc_task.h"
 #include "fmhip_mcmc_groups.h"
+#include "fmhip_mcmc_relational.h"
 #include "fmhip_bpr.h"
 
 namespace sparkfm {
@@ -198,6 +199,7 @@ class RelationalData {
         return nb;
     }
     const std::vector<double> &labels() const { return y_; }
+    int32_t n_parts() const { return (int32_t)relations_.size() + (plain_ ? 1 : 0); }     // the relations, then the plain part
     fmhip_relational_t handle() { return cache().h_; }
     int device() const { return device_; }
 
@@ -481,6 +483,10 @@ class HipALS : public FMLearn {
 // setGroups (include/fmhip_mcmc_groups.h; before the first learn): one attribute-group id per feature — at least the model's
 // num_attribute of them — and lambda and mu are sampled per (parameter group, attribute group): State's lambda and mu then hold
 // (k + 1) * G values, [g * G + a], and groupCounts() the trained features of every group.
+// learn(fm, RelationalData) (include/fmhip_mcmc_relational.h) sweeps a one-batch relational train set BY BLOCKS, never expanded — the
+// random numbers of the flat run on the expanded rows.  setTest(RelationalData *) gives it a relational test set (normally the
+// train set's blocks under other mappings; the DataSet of the constructor serves as well); setPartGroups() makes every part —
+// relation 0, 1, ..., the plain part — an attribute group (a group table is not taken with relational data).
 class HipMCMC : public FMLearn {
   public:
     struct State {
@@ -522,6 +528,15 @@ class HipMCMC : public FMLearn {
         n_groups_ = n_groups != 0 ? n_groups : most + 1;
         grouped_ = true;
     }
+    void setPartGroups() {                          // relational data: a part is an attribute group
+        if (h_) throw Error(FMHIP_ERR_INVALID, "the attribute groups are set before the first learn");
+        part_groups_ = true;
+    }
+    void setTest(RelationalData *test) {            // a relational test set, in the DataSet's place
+        if (h_) throw Error(FMHIP_ERR_INVALID, "the test set is given before the first learn");
+        rel_test_ = test;
+        test_ = nullptr;
+    }
     int32_t numGroups() const { return n_groups_; }
     HipMCMC(const HipMCMC &) = delete;
     HipMCMC &operator=(const HipMCMC &) = delete;
@@ -557,6 +572,44 @@ class HipMCMC : public FMLearn {
             classification_ = to.task == FMHIP_MCMC_CLASSIFICATION;
             m_ = m;
             d_ = d;
+            r_ = nullptr;
+            k_ = fm.num_factor;
+            if (pending_) {
+                pending_ = false;
+                setState(pending_state_.alpha, pending_state_.lambda, pending_state_.mu);
+            }
+        }
+        check(fmhip_mcmc_epoch(h_, &last_stats));
+        fm.download();
+        if (burn_in > 0 && last_stats.iterations == burn_in) check(fmhip_mcmc_reset_average(h_));
+        return fm;
+    }
+    FMModel &learn(FMModel &fm, RelationalData &dataset) override {
+        fmhip_model_t m = fm.upload();
+        fmhip_relational_t r = dataset.handle();
+        if (h_ && (m != m_ || r != r_)) close();
+        if (!h_) {
+            if (grouped_ && !part_groups_)
+                throw Error(FMHIP_ERR_UNSUPPORTED, "relational data takes no group table: setPartGroups() makes every part an attribute group");
+            fmhip_mcmc_task_opts to = task_opts;
+            if (clip_to_labels) {
+                if (dataset.labels().empty()) throw Error(FMHIP_ERR_INVALID, "clip_to_labels needs a train set with rows");
+                const auto range = std::minmax_element(dataset.labels().begin(), dataset.labels().end());
+                to.clip = 1;
+                to.clip_lo = *range.first;
+                to.clip_hi = *range.second;
+            }
+            check(fmhip_mcmc_create_relational(m, r, rel_test_ ? rel_test_->handle() : nullptr, test_ ? test_->handle() : nullptr, &opts, &to,
+                                               part_groups_ ? 1 : 0, &h_));
+            if (part_groups_) {
+                grouped_ = true;
+                n_groups_ = dataset.n_parts();
+            }
+            n_train_ = dataset.size();
+            classification_ = to.task == FMHIP_MCMC_CLASSIFICATION;
+            m_ = m;
+            r_ = r;
+            d_ = nullptr;
             k_ = fm.num_factor;
             if (pending_) {
                 pending_ = false;
@@ -619,14 +672,14 @@ class HipMCMC : public FMLearn {
         double sum = 0.0;
         for (size_t r = 0; r < p.size(); ++r) {
             const double q = std::min(std::max(p[r], 1e-15), 1.0 - 1e-15);
-            sum -= test_->labels()[r] > 0 ? std::log(q) : std::log1p(-q);
+            sum -= test_labels()[r] > 0 ? std::log(q) : std::log1p(-q);
         }
         return p.empty() ? 0.0 : sum / (double)p.size();
     }
     double computeAccuracy() {                      // the share of test rows whose averaged probability is on the label's side of 1/2
         const std::vector<double> p = probabilities("computeAccuracy");
         size_t hits = 0;
-        for (size_t r = 0; r < p.size(); ++r) hits += (p[r] > 0.5) == (test_->labels()[r] > 0);
+        for (size_t r = 0; r < p.size(); ++r) hits += (p[r] > 0.5) == (test_labels()[r] > 0);
         return p.empty() ? 0.0 : (double)hits / (double)p.size();
     }
     double computeRMSE() {                          // of the averaged prediction against the test labels (regression)
@@ -635,12 +688,14 @@ class HipMCMC : public FMLearn {
             throw Error(FMHIP_ERR_INVALID, "a classification run's predictions are probabilities: score them with computeLogLoss or computeAccuracy");
         const std::vector<double> mean = predictions();
         double sse = 0.0;
-        for (size_t r = 0; r < mean.size(); ++r) sse += (mean[r] - test_->labels()[r]) * (mean[r] - test_->labels()[r]);
+        for (size_t r = 0; r < mean.size(); ++r) sse += (mean[r] - test_labels()[r]) * (mean[r] - test_labels()[r]);
         return mean.empty() ? 0.0 : std::sqrt(sse / (double)mean.size());
     }
     void close() {
         check(fmhip_mcmc_destroy(h_));
         h_ = nullptr;
+        d_ = nullptr;                               // (the next learn makes a handle for whatever it is given, flat or relational)
+        r_ = nullptr;
     }
 
   private:
@@ -649,9 +704,10 @@ class HipMCMC : public FMLearn {
         return h_;
     }
     size_t test_rows() const {
-        if (!test_) throw Error(FMHIP_ERR_INVALID, "HipMCMC was made without a test set");
-        return (size_t)test_->size();
+        if (!test_ && !rel_test_) throw Error(FMHIP_ERR_INVALID, "HipMCMC was made without a test set");
+        return (size_t)(rel_test_ ? rel_test_->size() : test_->size());
     }
+    const std::vector<double> &test_labels() const { return rel_test_ ? rel_test_->labels() : test_->labels(); }
     std::vector<double> probabilities(const char *what) {
         need();
         if (!classification_) throw Error(FMHIP_ERR_INVALID, std::string(what) + " scores a classification run's probabilities (see computeRMSE)");
@@ -659,6 +715,9 @@ class HipMCMC : public FMLearn {
     }
     size_t state_size() const { return ((size_t)k_ + 1) * (size_t)n_groups_; }
     DataSet *test_;
+    RelationalData *rel_test_ = nullptr;
+    bool part_groups_ = false;
+    fmhip_relational_t r_ = nullptr;
     std::vector<int32_t> groups_;
     int32_t n_groups_ = 1;
     bool grouped_ = false;

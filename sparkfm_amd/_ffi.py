@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_bpr.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_mcmc_relational.h, include/fmhip_bpr.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -67,6 +67,8 @@ MCMC_REGRESSION, MCMC_CLASSIFICATION = 0, 1
 # ... and include/fmhip_mcmc_groups.h — its attribute groups: a lambda and a mu per feature group
 SYMBOLS_MCMC_GROUPS = ("fmhip_mcmc_set_groups", "fmhip_mcmc_group_info", "fmhip_mcmc_get_group_state", "fmhip_mcmc_set_group_state")
 MCMC_MAX_GROUPS = 4096     # FMHIP_MCMC_MAX_GROUPS
+# ... and include/fmhip_mcmc_relational.h — its block-structure sweep over relational data
+SYMBOLS_MCMC_RELATIONAL = ("fmhip_mcmc_create_relational",)
 # ... and include/fmhip_bpr.h — the BPR trainer: negatives drawn on the device over a contexts and a candidates block
 SYMBOLS_BPR = ("fmhip_bpr_create", "fmhip_bpr_destroy", "fmhip_bpr_info", "fmhip_bpr_resample", "fmhip_bpr_negatives", "fmhip_bpr_step",
                "fmhip_bpr_epoch", "fmhip_bpr_pair_logloss")
@@ -466,6 +468,7 @@ def load():
     L.fmhip_mcmc_group_info.argtypes = [vp, P(C.c_int32), vp]
     L.fmhip_mcmc_get_group_state.argtypes = [vp, P(dbl), vp, vp, P(i64)]
     L.fmhip_mcmc_set_group_state.argtypes = [vp, dbl, vp, vp]
+    L.fmhip_mcmc_create_relational.argtypes = [vp, vp, vp, vp, P(McmcOpts), P(McmcTaskOpts), C.c_int32, P(vp)]
     L.fmhip_bpr_create.argtypes = [C.c_int, vp, vp, i64, vp, vp, i32, i64, C.c_uint64, P(vp)]
     L.fmhip_bpr_destroy.argtypes = [vp]
     L.fmhip_bpr_info.argtypes = [vp, P(i64), P(i64), P(i64), P(i64), P(i32)]
@@ -476,7 +479,7 @@ def load():
     L.fmhip_bpr_pair_logloss.argtypes = [vp, vp, P(dbl), P(dbl), P(Stats)]
     L.fmhip_bpr_debug_inverse.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
-                 + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_BPR):
+                 + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

@@ -831,3 +831,352 @@ hipError_t launch_mcmc_accumulate(const AlsArgs &t, double *sum, hipStream_t s, 
 }
 
 }  // namespace fmhip
+
+// ==== the block-structure sweep (include/fmhip_mcmc_relational.h; launchers: mcmc_blocks.h) =====================================
+// The same conditional on the same columns, with a block column's sums taken over the BLOCK's rows from per-row caches instead of
+// over the data rows that reference them.  Per part and parameter group: k_block_gather (+ _long) builds the caches by a segmented
+// sum over the handle's inverse map, k_block_level / k_block_cols_wg walk the block's columns, k_block_scatter takes the steps back
+// to e and Q_f.  Every operation's order is written down in the public header; no fused multiply-add anywhere.
+#include "mcmc_blocks.h"
+#include "fm_relational.h"
+
+namespace fmhip {
+namespace {
+
+// yhat_r, e_r and Q_f[r] of every data row from the blocks' yhat_p and q_p; PROBIT: k_mcmc_probit_targets' draw around yhat_r
+template <bool PROBIT>
+__global__ __launch_bounds__(256) void k_block_combine(BlockCombine c, McmcProbit p, uint64_t seed, uint32_t t) {
+#pragma clang fp contract(off)
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < c.n_rows; r += (int64_t)gridDim.x * 256) {
+        const double w0 = *c.w0;
+        int64_t j[kBlockPartsMax];
+        double yhat = w0;
+        for (int b = 0; b < c.n_parts; ++b) {
+            j[b] = c.map[b] ? (int64_t)c.map[b][r] : r;
+            yhat += c.yhat[b][j[b]] - w0;
+        }
+        for (int f = 0; f < c.k; ++f) {
+            double run = c.q[0][f * c.J[0] + j[0]], cross = 0.0;
+            for (int b = 1; b < c.n_parts; ++b) {
+                const double qb = c.q[b][f * c.J[b] + j[b]];
+                cross += run * qb;
+                run += qb;
+            }
+            yhat += cross;
+            if (c.Q) c.Q[f * c.n_rows + r] = run;
+        }
+        if (PROBIT) {
+            const double s = p.labels[r] > 0.0 ? 1.0 : -1.0;
+            double target = s;
+            if (p.mode != kProbitStart) {
+                const double lo = -s * yhat;
+                const double z = p.mode == kProbitSample ? rng::truncated_normal(seed, (uint32_t)r, t, lo, nullptr) : rng::truncated_normal_mean(lo);
+                target = yhat + s * z;
+            }
+            p.ystar[r] = target;
+            c.e[r] = yhat - target;
+        } else {
+            c.e[r] = yhat - c.y[r];
+        }
+    }
+}
+
+// k_mcmc_sums' quantity 1 + g over ONE part's trained columns
+__global__ __launch_bounds__(kSumsBlock) void k_block_theta_sums(AlsArgs a, const int32_t *trained, const double *hyp, double *out, int P) {
+#pragma clang fp contract(off)
+    __shared__ double sh[2][kSumsBlock / 64];
+    const int g = (int)blockIdx.x / P, chunk = (int)blockIdx.x % P, tid = threadIdx.x;
+    const double mu = hyp[2 + a.k + g];
+    const int64_t lo = (int64_t)a.n_cols * chunk / P, hi = (int64_t)a.n_cols * (chunk + 1) / P;
+    double s0 = 0.0, s1 = 0.0;
+    for (int64_t s = lo + tid; s < hi; s += kSumsBlock) {
+        if (!trained[s]) continue;
+        const int64_t i = a.cfeat[s];
+        const double th = g == 0 ? a.w[i] : a.v[(g - 1) + i * a.k];
+        const double d = th - mu;
+        s0 += th;
+        s1 += d * d;
+    }
+    block_sum2<kSumsBlock>(s0, s1, sh);
+    if (tid == 0) {
+        out[2 * (int64_t)blockIdx.x] = s0;
+        out[2 * (int64_t)blockIdx.x + 1] = s1;
+    }
+}
+
+// The cache build: work item w = one list of the inverse map (or one chunk of kRelSumCut rows of a longer list), a thread each, the
+// rows ascending.  One writer per address: a block row's caches (or a partial row), and qrest[r] of the rows it reads.
+template <bool FACTOR>
+__global__ __launch_bounds__(256) void k_block_gather(BlockPart b, const double *e, const double *Qf, const double *qp) {
+#pragma clang fp contract(off)
+    const int w = (int)blockIdx.x * 256 + threadIdx.x;
+    if (w >= b.n_work) return;
+    const int t = b.wt[w], beg = b.wbeg[w];
+    const int end = beg + kRelSumCut < b.tptr[t + 1] ? beg + kRelSumCut : b.tptr[t + 1];
+    double E = 0.0, A = 0.0, B = 0.0, Cc = 0.0;
+    const double qj = FACTOR ? qp[b.tj[t]] : 0.0;
+    for (int pos = beg; pos < end; ++pos) {
+        const int r = b.trow[pos];
+        const double er = e[r];
+        E += er;
+        if (FACTOR) {
+            const double qr = Qf[r] - qj;
+            b.qrest[r] = qr;
+            A += qr;
+            B += qr * qr;
+            Cc += er * qr;
+        }
+    }
+    const int dst = b.wdst[w];
+    if (dst >= 0) {
+        b.cache[dst] = E;
+        if (FACTOR) {
+            b.cache[b.J + dst] = A;
+            b.cache[2 * b.J + dst] = B;
+            b.cache[3 * b.J + dst] = Cc;
+        }
+    } else {
+        double *part = b.part + 4 * (int64_t)(-1 - dst);
+        part[0] = E;
+        part[1] = A;
+        part[2] = B;
+        part[3] = Cc;
+    }
+}
+
+// ... and the long lists: their chunks' sums added in chunk order
+__global__ __launch_bounds__(256) void k_block_gather_long(BlockPart b) {
+#pragma clang fp contract(off)
+    const int l = (int)blockIdx.x * 256 + threadIdx.x;
+    if (l >= b.n_long) return;
+    const int64_t j = b.tj[b.lt[l]];
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int c = 0; c < b.lcount[l]; ++c) {
+        const double *part = b.part + 4 * (int64_t)(b.lfirst[l] + c);
+        for (int x = 0; x < 4; ++x) s[x] += part[x];
+    }
+    for (int x = 0; x < 4; ++x) b.cache[x * b.J + j] = s[x];
+}
+
+// sum h^2 and sum e*h of block column [c0, c1) from the caches: this thread's share (entries tid, tid + stride, ...)
+template <bool FACTOR>
+__device__ __forceinline__ void block_col_sums(const BlockPart &b, const double *qp, int c0, int c1, double th, int tid, int stride, double &shs,
+                                               double &seh) {
+#pragma clang fp contract(off)
+    const double *E = b.cache, *A = b.cache + b.J, *B = b.cache + 2 * b.J, *Cc = b.cache + 3 * b.J;
+    for (int p = c0 + tid; p < c1; p += stride) {
+        const uint32_t j = b.a.crow[p] & 0x7fffffffu;
+        const double x = b.a.cval[p];
+        if (FACTOR) {
+            const double u = qp[j] - x * th;
+            shs += (x * x) * ((b.n[j] * (u * u) + (2.0 * u) * A[j]) + B[j]);
+            seh += x * (u * E[j] + Cc[j]);
+        } else {
+            shs += (x * x) * b.n[j];
+            seh += x * E[j];
+        }
+    }
+}
+
+// the step d = theta' - theta of block column [c0, c1) into the caches (a column's block rows are distinct: one writer each)
+template <bool FACTOR>
+__device__ __forceinline__ void block_col_update(const BlockPart &b, double *qp, int c0, int c1, double th, double d, int tid, int stride) {
+#pragma clang fp contract(off)
+    double *E = b.cache, *A = b.cache + b.J, *B = b.cache + 2 * b.J, *Cc = b.cache + 3 * b.J, *S1 = b.cache + 4 * b.J, *S2 = b.cache + 5 * b.J;
+    for (int p = c0 + tid; p < c1; p += stride) {
+        const uint32_t j = b.a.crow[p] & 0x7fffffffu;
+        const double xd = b.a.cval[p] * d;
+        if (FACTOR) {
+            const double u = qp[j] - b.a.cval[p] * th;
+            E[j] += xd * (b.n[j] * u + A[j]);
+            Cc[j] += xd * (u * A[j] + B[j]);
+            S1[j] += xd * u;
+            S2[j] += xd;
+            qp[j] += xd;
+        } else {
+            E[j] += b.n[j] * xd;
+            S2[j] += xd;                                          // (the w pass's D)
+        }
+    }
+}
+
+// The columns of one LEVEL of the block's schedule, a wave each (k_als_level's shape: they share no block row)
+template <bool FACTOR>
+__global__ __launch_bounds__(kLevelBlock) void k_block_level(BlockPart b, const int32_t *cols, int n, int f, int long_col, McmcDev m) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int jc = (int)blockIdx.x * (kLevelBlock / 64) + (int)(threadIdx.x >> 6);
+    if (jc >= n) return;
+    const int s = cols[jc];
+    if (!b.trained[s]) return;
+    const int c0 = b.a.cptr[s], c1 = b.a.cptr[s + 1];
+    if (c1 - c0 >= long_col) return;                               // the 1024-thread workgroup walk behind this launch
+    const int64_t i = b.a.cfeat[s];
+    double *par = FACTOR ? b.a.v + f + i * b.a.k : b.a.w + i;
+    double *qp = b.a.q + (FACTOR ? (int64_t)f * b.J : 0);
+    const int g = FACTOR ? 1 + f : 0;
+    const double th = *par;
+    double shs = 0.0, seh = 0.0;
+    block_col_sums<FACTOR>(b, qp, c0, c1, th, lane, 64, shs, seh);
+    shs = wave_sum(shs);
+    seh = wave_sum(seh);
+    const double tn = group_draw(b.a, g, 0.0, m).at(i)(th, seh, shs, noise_at((int64_t)g * b.a.n_cols + s, m));
+    if (is_updatable(tn, th)) block_col_update<FACTOR>(b, qp, c0, c1, th, tn - th, lane, 64);
+    if (lane == 0) *par = tn;
+}
+
+// The columns [s_lo, s_hi) in order by ONE workgroup (k_als_cols_wg's shape): a dense conflict graph, or one long column
+template <int kAlsBlock, bool FACTOR>
+__global__ __launch_bounds__(kAlsBlock) void k_block_cols_wg(BlockPart b, int s_lo, int s_hi, int f, McmcDev m) {
+#pragma clang fp contract(off)
+    __shared__ double sh[2][kAlsBlock / 64];
+    const int tid = threadIdx.x;
+    const int g = FACTOR ? 1 + f : 0;
+    double *qp = b.a.q + (FACTOR ? (int64_t)f * b.J : 0);
+    const auto draw = group_draw(b.a, g, 0.0, m);
+    for (int s = s_lo; s < s_hi; ++s) {
+        if (!b.trained[s]) continue;
+        const int64_t i = b.a.cfeat[s];
+        const int c0 = b.a.cptr[s], c1 = b.a.cptr[s + 1];
+        double *par = FACTOR ? b.a.v + f + i * b.a.k : b.a.w + i;
+        const double th = *par;
+        const double zn = noise_at((int64_t)g * b.a.n_cols + s, m);
+        double shs = 0.0, seh = 0.0;
+        block_col_sums<FACTOR>(b, qp, c0, c1, th, tid, kAlsBlock, shs, seh);
+        block_sum2<kAlsBlock>(shs, seh, sh);
+        const double tn = draw.at(i)(th, seh, shs, zn);
+        if (is_updatable(tn, th)) block_col_update<FACTOR>(b, qp, c0, c1, th, tn - th, tid, kAlsBlock);
+        __syncthreads();
+        if (tid == 0) *par = tn;
+        __syncthreads();
+    }
+}
+
+// the part's steps back to the data rows
+template <bool FACTOR>
+__global__ __launch_bounds__(256) void k_block_scatter(BlockPart b, double *e, double *Qf) {
+#pragma clang fp contract(off)
+    const double *S1 = b.cache + 4 * b.J, *S2 = b.cache + 5 * b.J;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < b.n_rows; r += (int64_t)gridDim.x * 256) {
+        const int64_t j = b.map[r];
+        if (FACTOR) {
+            e[r] += S1[j] + S2[j] * b.qrest[r];
+            Qf[r] += S2[j];
+        } else {
+            e[r] += S2[j];
+        }
+    }
+}
+
+template <bool FACTOR>
+hipError_t block_pass(const BlockPart &b, const BlockPlan &plan, int f, double *e, double *Q, const McmcDev &m, hipStream_t s) {
+    const int n_cols = b.a.n_cols;
+    double *Qf = FACTOR ? Q + (int64_t)f * b.n_rows : nullptr;
+    const double *qp = FACTOR ? b.a.q + (int64_t)f * b.J : nullptr;
+    hipError_t err = hipMemsetAsync(b.cache, 0, (size_t)kBlockCaches * (size_t)b.J * sizeof(double), s);      // rows nobody references: exact zeros
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL((k_block_gather<FACTOR>), dim3((unsigned)((b.n_work + 255) / 256)), dim3(256), 0, s, b, e, Qf, qp);
+    if (b.n_long > 0) hipLaunchKernelGGL(k_block_gather_long, dim3((unsigned)((b.n_long + 255) / 256)), dim3(256), 0, s, b);
+    int long_col = kAlsLongColumn;
+    if (const char *ev = getenv("FMHIP_ALS_LONG")) long_col = atoi(ev) > 0 ? atoi(ev) : long_col;
+    const bool have = plan.h_lev_ptr && plan.h_lev_cols && b.a.lev_cols && plan.n_levels > 0;
+    bool levels = have && (int64_t)plan.n_levels * 16 <= n_cols;
+    if (const char *ev = getenv("FMHIP_ALS_LEVELS")) levels = have && atoi(ev) != 0;
+    if (levels) {
+        for (int l = 0; l < plan.n_levels; ++l) {
+            const int n = plan.h_lev_ptr[l + 1] - plan.h_lev_ptr[l];
+            if (n < 1) continue;
+            hipLaunchKernelGGL((k_block_level<FACTOR>), dim3((unsigned)((n + kLevelBlock / 64 - 1) / (kLevelBlock / 64))), dim3(kLevelBlock), 0, s, b,
+                               b.a.lev_cols + plan.h_lev_ptr[l], n, f, long_col, m);
+            for (int j = plan.h_lev_ptr[l]; j < plan.h_lev_ptr[l + 1]; ++j) {      // the level's long columns share no row with its others
+                const int c = plan.h_lev_cols[j];
+                if (plan.h_cptr[c + 1] - plan.h_cptr[c] >= long_col && plan.h_trained[c])
+                    hipLaunchKernelGGL((k_block_cols_wg<1024, FACTOR>), dim3(1), dim3(1024), 0, s, b, c, c + 1, f, m);
+            }
+        }
+    } else if (n_cols > 0) {
+        const bool wide_wg = (int64_t)plan.h_cptr[n_cols] / n_cols >= 512;
+        if (wide_wg) hipLaunchKernelGGL((k_block_cols_wg<1024, FACTOR>), dim3(1), dim3(1024), 0, s, b, 0, n_cols, f, m);
+        else hipLaunchKernelGGL((k_block_cols_wg<256, FACTOR>), dim3(1), dim3(256), 0, s, b, 0, n_cols, f, m);
+    }
+    hipLaunchKernelGGL((k_block_scatter<FACTOR>), dim3(row_blocks(b.n_rows)), dim3(256), 0, s, b, e, Qf);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_block_noise(const AlsArgs &a, double *z, uint64_t seed, uint32_t t, hipStream_t s) {
+    int64_t nb = ((int64_t)(a.k + 1) * a.n_cols + 1 + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    hipLaunchKernelGGL(k_mcmc_noise, dim3((unsigned)nb), dim3(256), 0, s, a, z, seed, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_forward(const AlsArgs &a, bool with_q, hipStream_t s) {
+    if (a.n_rows < 1) return hipSuccess;
+    hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a);
+    int64_t qb = (a.n_rows * a.k + 255) / 256;
+    if (qb > 4096) qb = 4096;
+    if (with_q && a.k > 0) hipLaunchKernelGGL(k_als_q_all, dim3((unsigned)(qb < 1 ? 1 : qb)), dim3(256), 0, s, a, a.q);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_combine(const BlockCombine &c, const McmcProbit *probit, uint64_t seed, uint32_t t, hipStream_t s) {
+    if (c.n_rows < 1) return hipSuccess;
+    if (probit) hipLaunchKernelGGL(k_block_combine<true>, dim3(row_blocks(c.n_rows)), dim3(256), 0, s, c, *probit, seed, t);
+    else hipLaunchKernelGGL(k_block_combine<false>, dim3(row_blocks(c.n_rows)), dim3(256), 0, s, c, McmcProbit{}, seed, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_sse(const AlsArgs &rows, double *sums, hipStream_t s) {
+    hipLaunchKernelGGL(k_mcmc_sums, dim3((unsigned)kMcmcSumParts), dim3(kSumsBlock), 0, s, rows, McmcDev{}, sums, kMcmcSumParts);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_theta_sums(const AlsArgs &a, const int32_t *trained, const double *hyp, double *out, hipStream_t s) {
+    hipLaunchKernelGGL(k_block_theta_sums, dim3((unsigned)((a.k + 1) * kMcmcSumParts)), dim3(kSumsBlock), 0, s, a, trained, hyp, out, kMcmcSumParts);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_bias(const AlsArgs &rows, const McmcDev &m, hipStream_t s) {
+    hipLaunchKernelGGL((k_als_w0<1024, McmcDev>), dim3(1), dim3(1024), 0, s, rows, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_pass(const BlockPart &b, const BlockPlan &plan, int g, double *e, double *Q, const McmcDev &m, hipStream_t s) {
+    return g == 0 ? block_pass<false>(b, plan, 0, e, Q, m, s) : block_pass<true>(b, plan, g - 1, e, Q, m, s);
+}
+
+hipError_t launch_plain_pass(const AlsArgs &a, int g, const McmcDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
+                             const int32_t *h_lev_cols, int n_levels, hipStream_t s) {
+    if (a.n_cols < 1) return hipSuccess;
+    int long_col = kAlsLongColumn;
+    if (const char *ev = getenv("FMHIP_ALS_LONG")) long_col = atoi(ev) > 0 ? atoi(ev) : long_col;
+    const bool have = h_lev_ptr && h_lev_cols && a.lev_cols && n_levels > 0;
+    bool levels = have && (int64_t)n_levels * 16 <= a.n_cols;
+    if (const char *ev = getenv("FMHIP_ALS_LEVELS")) levels = have && atoi(ev) != 0;
+    if (levels)
+        return g == 0 ? level_pass<false>(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, 0, long_col, s, m)
+                      : level_pass<true>(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, g - 1, long_col, s, m);
+    int64_t short_nnz = 0, n_short = 0;
+    for (int c = 0; c < a.n_cols; ++c) {
+        const int len = h_cptr[c + 1] - h_cptr[c];
+        if (len < long_col) { short_nnz += len; ++n_short; }
+    }
+    const bool wide_wg = n_short > 0 && short_nnz / n_short >= 512;
+    return g == 0 ? sweep_pass<false>(a, h_cfeat, h_cptr, 0, long_col, wide_wg, s, m) : sweep_pass<true>(a, h_cfeat, h_cptr, g - 1, long_col, wide_wg, s, m);
+}
+
+hipError_t launch_block_accumulate(double *last, double *sum, int64_t n_rows, const McmcLink &link, hipStream_t s) {
+    if (n_rows < 1) return hipSuccess;
+    const dim3 grid(row_blocks(n_rows)), block(256);
+    if (link.kind == kLinkProbit)
+        hipLaunchKernelGGL(k_mcmc_accumulate_link<LinkProbit>, grid, block, 0, s, last, sum, n_rows, LinkProbit{});
+    else if (link.kind == kLinkClamp)
+        hipLaunchKernelGGL(k_mcmc_accumulate_link<LinkClamp>, grid, block, 0, s, last, sum, n_rows, LinkClamp{link.lo, link.hi});
+    else
+        hipLaunchKernelGGL(k_mcmc_accumulate, grid, block, 0, s, last, sum, n_rows);
+    return hipGetLastError();
+}
+
+}  // namespace fmhip

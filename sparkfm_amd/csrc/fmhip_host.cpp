@@ -853,5 +853,51 @@ const char *mcmc_bad_task(int32_t task, int32_t clip, double clip_lo, double cli
     return nullptr;
 }
 
+// ---- ... its block-structure sweep (include/fmhip_mcmc_relational.h) ------------------------------------------------------
+
+McmcPartOrder mcmc_part_order(int n_parts, const int32_t *const *feat, const int64_t *n_feat) {
+    McmcPartOrder out;
+    std::vector<int32_t> lo((size_t)n_parts, INT32_MAX), hi((size_t)n_parts, -1);
+    for (int p = 0; p < n_parts; ++p)
+        for (int64_t x = 0; x < n_feat[p]; ++x) {
+            lo[(size_t)p] = std::min(lo[(size_t)p], feat[p][x]);
+            hi[(size_t)p] = std::max(hi[(size_t)p], feat[p][x]);
+        }
+    out.order.resize((size_t)n_parts);
+    for (int p = 0; p < n_parts; ++p) out.order[(size_t)p] = p;
+    // (a part without features sorts last: nothing of it is walked)
+    std::stable_sort(out.order.begin(), out.order.end(), [&](int x, int y) { return lo[(size_t)x] < lo[(size_t)y]; });
+    for (int x = 0; x + 1 < n_parts; ++x) {
+        const int a = out.order[(size_t)x], b = out.order[(size_t)x + 1];
+        if (hi[(size_t)b] < 0) break;
+        if (lo[(size_t)b] <= hi[(size_t)a]) {
+            out.a = a;
+            out.b = b;
+            out.feature = lo[(size_t)b];
+            break;
+        }
+    }
+    return out;
+}
+
+void mcmc_block_counts(const int32_t *map, int64_t n_rows, int64_t block_rows, std::vector<double> &n) {
+    n.assign((size_t)block_rows, 0.0);
+    for (int64_t r = 0; r < n_rows; ++r) n[(size_t)map[r]] += 1.0;
+}
+
+int64_t mcmc_block_trained(const int32_t *cfeat, const int32_t *cptr, const uint32_t *crow, int64_t n_cols, int64_t num_attribute, const double *n,
+                           std::vector<int32_t> &trained) {
+    trained.assign((size_t)n_cols, 0);
+    int64_t count = 0;
+    for (int64_t s = 0; s < n_cols; ++s) {
+        if (cfeat[s] >= num_attribute) continue;
+        bool used = false;
+        for (int32_t p = cptr[s]; p < cptr[s + 1] && !used; ++p) used = !n || n[crow[p] & 0x7fffffffu] > 0.0;
+        trained[(size_t)s] = used ? 1 : 0;
+        count += used;
+    }
+    return count;
+}
+
 }  // namespace host
 }  // namespace fmhip

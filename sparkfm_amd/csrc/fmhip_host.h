@@ -236,6 +236,22 @@ double mcmc_truncated_mean(double a);
 // nullptr, or why (task, clip, [clip_lo, clip_hi]) is refused: an unknown task, a clip with the classification task, a clip
 // range that is not finite with lo < hi
 const char *mcmc_bad_task(int32_t task, int32_t clip, double clip_lo, double clip_hi);
+// ---- ... and its block-structure sweep over relational data (include/fmhip_mcmc_relational.h) ----
+// The order the parts are walked in: by ascending id range.  feat[p]: part p's feature ids (any order, repeats allowed; a part
+// without features keeps its place).  The flat sweep walks ascending ids, so the ranges must not interleave: a = -1, or the two
+// parts (a's range starts lower) and the lowest feature of b that lies inside a's range
+struct McmcPartOrder {
+    std::vector<int> order;
+    int a = -1, b = -1;
+    int32_t feature = -1;
+};
+McmcPartOrder mcmc_part_order(int n_parts, const int32_t *const *feat, const int64_t *n_feat);
+// n[j] = the data rows that map to block row j (map: n_rows entries in [0, block_rows), checked by the caller)
+void mcmc_block_counts(const int32_t *map, int64_t n_rows, int64_t block_rows, std::vector<double> &n);
+// trained[s] = 1 when column s is in T — its id below num_attribute (quirk Q1) and an entry in a block row with n[j] > 0 (crow:
+// the CSC row words, bit 31 a flag; n = NULL: the plain part, every row counts) -> |T| of the part
+int64_t mcmc_block_trained(const int32_t *cfeat, const int32_t *cptr, const uint32_t *crow, int64_t n_cols, int64_t num_attribute, const double *n,
+                           std::vector<int32_t> &trained);
 
 }  // namespace host
 }  // namespace fmhip

@@ -290,6 +290,7 @@ struct fmhip_relational {
     std::vector<std::unique_ptr<Relation>> rels;
     fmhip_dataset_t plain = nullptr;
     DevBuf<float> y;
+    DevBuf<double> y64;                                                 // the labels as given (the MCMC learner's residuals are fp64)
     std::vector<Batch> batches;
     // A step is queued, not run, when its call returns, and the workspace above is the HANDLE's: `busy` is recorded behind every
     // step on the stream it ran on, and a step on ANOTHER stream (another model) waits for it before it touches the workspace

@@ -11,10 +11,11 @@
 // A handle with attribute groups (include/fmhip_mcmc_groups.h, G > 1) keeps lambda and mu as [(k + 1) x G], takes the groups' sums
 // from k_mcmc_group_sums over the plan fmhip_mcmc_set_groups made (fmhip_host.cpp: mcmc_group_plan) — added here in chunk order,
 // inside the same single sync — and walks with McmcGroupDev.  G = 1, set or not, is the sequence above, launch for launch.
+// A handle over relational data (include/fmhip_mcmc_relational.h) is made and stepped in fmhip_mcmc_relational.hip; the struct both
+// share is fmhip_mcmc_handle.h's, and every call here but the epoch and set_groups serves it as it serves a flat handle.
 // The kernels are in als_kernels.hip, the generator in mcmc_rng.h.
 #include "fmhip_internal.h"
-#include "als_kernels.h"
-#include "../../include/fmhip_mcmc_groups.h"
+#include "fmhip_mcmc_handle.h"
 
 #include <algorithm>
 #include <cmath>
@@ -24,30 +25,6 @@
 
 using namespace fmhip;
 using namespace fmhip::host;
-
-struct fmhip_mcmc {
-    fmhip_model_t m = nullptr;
-    fmhip_dataset_t train = nullptr, test = nullptr;
-    fmhip_mcmc_opts opts{};
-    int32_t task = FMHIP_MCMC_REGRESSION;
-    McmcLink link;                          // what a draw's test prediction becomes before it joins the sum
-    McmcPriors priors;
-    int32_t k = 0;
-    int64_t n_trained = 0;                  // |T|: the column slots with id < num_attribute
-    double alpha = 1.0;
-    std::vector<double> lambda, mu;         // [(k + 1) * G], row-major: [g * G + a]
-    int32_t G = 1;                          // attribute groups (include/fmhip_mcmc_groups.h); 1: none, the epoch fmhip_mcmc.h describes
-    McmcGroupPlan plan;                     // G > 1: the chunks of the grouped sums
-    int64_t plan_cols = 0;                  // ... and the column slots they were made over
-    DevBuf<int32_t> d_group, d_order, d_chunk_ptr, d_chunk_group;      // group: [num_attribute + 1]
-    DevBuf<double> gsums;                   // k_mcmc_group_sums' partials [n_chunks * (k + 1) * 2]
-    std::vector<double> h_gsums;
-    int64_t iterations = 0, draws = 0;
-    DevBuf<double> z, hyp, sums;            // the epoch's noise; {alpha, lambda, mu}; k_mcmc_sums' partials
-    DevBuf<double> ystar;                   // classification: the latent targets the last epoch trained on [train rows]
-    DevBuf<double> test_sum, test_last, test_zero;     // [test rows]: the running sum, the last draw's predictions, zeros
-    std::vector<double> h_sums, h_hyp;
-};
 
 namespace {
 
@@ -146,6 +123,13 @@ int get_state(fmhip_mcmc_t s, double *alpha, double *lambda, double *mu, int64_t
     return FMHIP_OK;
 }
 
+// the rows of the handle's test set, flat or relational (-1: none)
+int64_t test_rows(fmhip_mcmc_t s) {
+    if (s->test) return s->test->n_rows;
+    if (s->rel && s->rel->test) return s->rel->test->n_rows;
+    return -1;
+}
+
 int set_state(fmhip_mcmc_t s, double alpha, const double *lambda, const double *mu) {
     if (!(std::isfinite(alpha) && alpha > 0.0)) return fail(FMHIP_ERR_INVALID, "alpha must be finite and > 0");
     const int G = s->G;
@@ -199,6 +183,7 @@ int fmhip_mcmc_destroy(fmhip_mcmc_t s) {
 
 int fmhip_mcmc_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats) {
     if (!s) return fail(FMHIP_ERR_INVALID, "the MCMC handle is NULL");
+    if (s->rel) return mcmc_relational_epoch(s, stats);
     fmhip_model_t m = s->m;
     fmhip_dataset_t d = s->train;
     WriteLock lock(m);
@@ -320,6 +305,9 @@ int fmhip_mcmc_set_groups(fmhip_mcmc_t s, const int32_t *group, int64_t n, int32
     if (!s) return fail(FMHIP_ERR_INVALID, "the MCMC handle is NULL");
     fmhip_model_t m = s->m;
     WriteLock lock(m);
+    if (s->rel)
+        return fail(FMHIP_ERR_UNSUPPORTED, "a handle over relational data takes no group table: its attribute groups are its parts "
+                                           "(fmhip_mcmc_create_relational with part_groups = 1)");
     if (s->iterations > 0)
         return fail(FMHIP_ERR_INVALID, "the attribute groups are set before the handle's first epoch: this one has completed %lld", (long long)s->iterations);
     if (n != m->n) return fail(FMHIP_ERR_INVALID, "the group table holds n = %lld ids but the model has num_attribute = %lld", (long long)n, (long long)m->n);
@@ -394,7 +382,7 @@ int fmhip_mcmc_reset_average(fmhip_mcmc_t s) {
     if (!s) return fail(FMHIP_ERR_INVALID, "the MCMC handle is NULL");
     WriteLock lock(s->m);
     TRY(set_device(s->m->device));
-    if (s->test) {
+    if (test_rows(s) >= 0) {
         HIP_TRY(hipMemsetAsync(s->test_sum.p, 0, s->test_sum.n * sizeof(double), s->m->stream));
         HIP_TRY(hipStreamSynchronize(s->m->stream));
     }
@@ -404,10 +392,10 @@ int fmhip_mcmc_reset_average(fmhip_mcmc_t s) {
 
 int fmhip_mcmc_predictions(fmhip_mcmc_t s, double *mean, double *last, int64_t *draws) {
     if (!s) return fail(FMHIP_ERR_INVALID, "the MCMC handle is NULL");
-    if (!s->test) return fail(FMHIP_ERR_INVALID, "the MCMC handle was created without a test set");
+    if (test_rows(s) < 0) return fail(FMHIP_ERR_INVALID, "the MCMC handle was created without a test set");
     ReadLock lock(s->m);
     TRY(set_device(s->m->device));
-    const size_t n = (size_t)s->test->n_rows;
+    const size_t n = (size_t)test_rows(s);
     if (mean && n) HIP_TRY(hipMemcpy(mean, s->test_sum.p, n * sizeof(double), hipMemcpyDeviceToHost));
     if (last && n) HIP_TRY(hipMemcpy(last, s->test_last.p, n * sizeof(double), hipMemcpyDeviceToHost));
     if (mean)
@@ -420,9 +408,10 @@ int fmhip_mcmc_latent_targets(fmhip_mcmc_t s, double *out) {
     if (!s || !out) return fail(FMHIP_ERR_INVALID, "the MCMC handle or out is NULL");
     ReadLock lock(s->m);
     TRY(set_device(s->m->device));
-    const size_t n = (size_t)s->train->n_rows;
+    const size_t n = (size_t)(s->rel ? s->rel->train->n_rows : s->train->n_rows);
     const bool drawn = s->task == FMHIP_MCMC_CLASSIFICATION && s->iterations > 0;
-    if (n) HIP_TRY(hipMemcpy(out, drawn ? s->ystar.p : s->train->y64.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    const double *labels = s->rel ? s->rel->train->y64.p : s->train->y64.p;
+    if (n) HIP_TRY(hipMemcpy(out, drawn ? s->ystar.p : labels, n * sizeof(double), hipMemcpyDeviceToHost));
     return FMHIP_OK;
 }
 

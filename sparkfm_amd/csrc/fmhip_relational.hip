@@ -284,6 +284,8 @@ int fmhip_relational_create(int device, int64_t n_rows, const double *y, int32_t
         std::vector<float> yf((size_t)n_rows);
         for (int64_t r = 0; r < n_rows; ++r) yf[(size_t)r] = (float)y[r];
         TRY(upload(R->y, yf));
+        TRY(R->y64.alloc((size_t)n_rows));
+        HIP_TRY(hipMemcpy(R->y64.p, y, (size_t)n_rows * sizeof(double), hipMemcpyHostToDevice));
     }
     std::vector<int32_t> count;
     for (int i = 0; i < n_relations; ++i) {

@@ -118,6 +118,8 @@ class HipMCMC(FMLearn):
     alpha_0 = beta_0 = alpha_lambda = beta_lambda = gamma_0 = 1, mu_0 = 0.  The handle is made on the first ``learn`` for a
     (model, dataset) pair and remade when either changes; ``close()`` frees it.  Needs a single-batch DataSet like ``HipALS``.
 
+    This class takes flat rows; a ``RelationalData`` is swept by blocks, never expanded, by its subclass ``HipBlockMCMC``.
+
     `task` (include/fmhip_mcmc_task.h): "regression", or "classification" — binary labels [y > 0] by the probit link: every epoch
     trains on latent targets drawn from truncated normals (``latent_targets()``), alpha stays 1, and ``predictions()`` /
     ``last_predictions()`` are PROBABILITIES Phi(yhat), scored by ``computeLogLoss()``, ``computeAccuracy()`` and ``computeAUC()``
@@ -134,19 +136,22 @@ class HipMCMC(FMLearn):
     PRIORS = ("reg0", "init_lambda", "alpha_0", "beta_0", "alpha_lambda", "beta_lambda", "gamma_0", "mu_0")
 
     TASKS = {"regression": _ffi.MCMC_REGRESSION, "classification": _ffi.MCMC_CLASSIFICATION}
+    RELATIONAL = False          # HipBlockMCMC: the train set is a RelationalData, `test` may be one, groups may be "parts"
 
     def __init__(self, seed=0, test=None, burn_in=0, sample=True, task="regression", clip=None, groups=None, **priors):
         import math
         import operator
         self.groups, self.n_groups = None, 1
-        if groups is not None:
+        if self.RELATIONAL and isinstance(groups, str) and groups == "parts":
+            self.groups = "parts"       # (n_groups: the train set's parts, known when the handle is made)
+        elif groups is not None:
             from .metadata import Metadata
             if isinstance(groups, Metadata):
                 table, n_groups = groups.attrGroup, groups.numAttrGroups
             else:
                 table = np.asarray(groups)
                 if table.ndim != 1 or (len(table) and not np.issubdtype(table.dtype, np.integer)):
-                    raise TypeError("groups must be a Metadata or a 1-d integer array (one group id per feature)")
+                    raise TypeError("groups must be a Metadata, a 1-d integer array (one group id per feature) or, with HipBlockMCMC, 'parts'")
                 if len(table) and table.min() < 0:
                     raise ValueError("feature %d has group id %d: ids are >= 0" % (int(np.argmin(table)), int(table.min())))
                 n_groups = int(table.max()) + 1 if len(table) else 1
@@ -178,7 +183,7 @@ class HipMCMC(FMLearn):
         if not isinstance(sample, bool):
             raise ValueError("sample must be True or False, not %r" % (sample,))
         self.sample = sample
-        if isinstance(test, RelationalData):
+        if isinstance(test, RelationalData) and not self.RELATIONAL:
             test.handle             # raises: this call takes flat rows
         if test is not None and getattr(test, "scoring", False):
             raise ValueError("the test set must keep its fp64 rows: make it without scoring=True")
@@ -204,12 +209,18 @@ class HipMCMC(FMLearn):
 
     def _handle(self, fm, dataset):
         L = _ffi.load()
-        mh, dh = fm.handle, dataset.handle
+        relational = self.RELATIONAL
+        if relational and self.groups is not None and not isinstance(self.groups, str):
+            raise ValueError("a RelationalData train set takes no group table: groups='parts' makes every part (relation 0, 1, ..., the plain part) "
+                             "an attribute group — what relational.meta() names over expand()")
+        mh, dh = fm.handle, dataset.rel_handle if relational else dataset.handle
         if self._h is not None and self._for != (mh.value, dh.value):
             self.close()
         if self._h is None:
             n = fm.num_attribute
-            if self.groups is not None and len(self.groups) < n:
+            if relational:
+                self.n_groups = len(dataset._parts()) if self.groups is not None else 1
+            elif self.groups is not None and len(self.groups) < n:
                 raise ValueError("groups holds %d ids but the model has num_attribute = %d" % (len(self.groups), n))
             opts = _ffi.McmcOpts(self.seed, 1 if self.sample else 0, *[self.priors[n] for n in self.PRIORS])
             h = C.c_void_p()
@@ -220,10 +231,16 @@ class HipMCMC(FMLearn):
                     raise ValueError("clip='labels' needs a train set with rows")
                 clip = (float(y.min()), float(y.max()))
             task = _ffi.McmcTaskOpts(self.TASKS[self.task], 0 if clip is None else 1, *(clip or (0.0, 0.0)))
-            _ffi.check(L.fmhip_mcmc_create_task(mh, dh, None if self.test is None else self.test.handle, C.byref(opts), C.byref(task), C.byref(h)))
+            if relational:
+                rel_test = isinstance(self.test, RelationalData)
+                _ffi.check(L.fmhip_mcmc_create_relational(mh, dh, self.test.rel_handle if rel_test else None,
+                                                          None if self.test is None or rel_test else self.test.handle, C.byref(opts), C.byref(task),
+                                                          0 if self.groups is None else 1, C.byref(h)))
+            else:
+                _ffi.check(L.fmhip_mcmc_create_task(mh, dh, None if self.test is None else self.test.handle, C.byref(opts), C.byref(task), C.byref(h)))
             self._h, self._for, self._k, self._n_train = h, (mh.value, dh.value), fm.num_factor, dataset.size
             self._keep = (fm, dataset)      # the handle borrows both
-            if self.groups is not None:
+            if self.groups is not None and not relational:
                 table = np.ascontiguousarray(self.groups[:n])
                 rc = L.fmhip_mcmc_set_groups(h, _ffi.ptr(table), n, self.n_groups)
                 if rc != 0:
@@ -235,7 +252,9 @@ class HipMCMC(FMLearn):
         return self._h
 
     def learn(self, fm, dataset):
-        if isinstance(dataset, RelationalData):
+        if isinstance(dataset, RelationalData) != self.RELATIONAL:
+            if self.RELATIONAL:
+                raise TypeError("HipBlockMCMC sweeps the blocks of a RelationalData, not flat rows: HipMCMC takes a %s" % type(dataset).__name__)
             dataset.handle          # raises: this call takes flat rows
         L = _ffi.load()
         h = self._handle(fm, dataset)
@@ -358,3 +377,20 @@ class HipMCMC(FMLearn):
             self.close()
         except Exception:
             pass
+
+
+class HipBlockMCMC(HipMCMC):
+    """``HipMCMC`` over a ``RelationalData`` (single batch), swept BY BLOCKS (include/fmhip_mcmc_relational.h; Rendle, "Scaling
+    Factorization Machines to Relational Data") — ``expand()`` is never built: a block column costs one entry per block row instead of
+    one per data row that references it, its sums taken from per-block-row caches.  Same seed, same random numbers as ``HipMCMC`` on
+    ``expand()``; the two differ by rounding.
+
+        mcmc = HipBlockMCMC.run(test=held_out, burn_in=15, groups="parts")
+        fm = FM(ratings, k, maxIteration=40).withRelation([users, items]).learnWith(mcmc)
+
+    Everything is ``HipMCMC``'s — tasks, clip, priors, state, predictions, scores — except: `test` is a ``RelationalData`` (normally the
+    train set's blocks under ``Relation.remap``) or a flat DataSet; `groups` is None or "parts" — every part (relation 0, 1, ..., the plain
+    part) is an attribute group, as ``relational.meta()`` names them over ``expand()``, and ``state`` is (k + 1, parts); a table is not
+    taken.  The parts' feature-id ranges must not interleave (the block sweep walks part after part, the flat one ascending ids)."""
+
+    RELATIONAL = True

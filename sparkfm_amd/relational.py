@@ -64,8 +64,8 @@ class Relation:
 class RelationalData:
     """N labels, m >= 1 relations, an optional plain part (a ``DataSet`` or ``Features`` of the same N rows), ``batch_rows``.
     Feature ids are global and the parts' feature sets must be pairwise disjoint.  ``cache()`` moves it to the device
-    (fmhip_relational_create); ``HipSGD.learn`` / ``step`` and ``FMModel.predict`` / ``computeRMSE`` / ``computeLogLoss`` /
-    ``computeAccuracy`` take it; every other call needs the flat rows: ``expand()``."""
+    (fmhip_relational_create); ``HipSGD.learn`` / ``step``, ``HipBlockMCMC.learn`` (and its ``test=``) and ``FMModel.predict`` /
+    ``computeRMSE`` / ``computeLogLoss`` / ``computeAccuracy`` take it; every other call needs the flat rows: ``expand()``."""
 
     def __init__(self, y, relations, plain=None, batch_rows=0, name="relational", device=0):
         if isinstance(relations, Relation):
@@ -161,7 +161,7 @@ class RelationalData:
 
     @property
     def handle(self):
-        raise TypeError("this call takes a flat DataSet, not a RelationalData (which HipSGD.learn / step and FMModel.predict / computeRMSE / "
+        raise TypeError("this call takes a flat DataSet, not a RelationalData (which HipSGD.learn / step, HipBlockMCMC.learn and FMModel.predict / computeRMSE / "
                         "computeLogLoss / computeAccuracy take): pass relational.expand()")
 
     def info(self):
