@@ -30,7 +30,10 @@ int fmhip_ablation_mask(void);
 typedef enum fmhip_tune_key {
     /* forward kernel: 60 = LDS w-tile (default: the linear weights of the 6144 lowest feature ids are staged in LDS), 0 = plain
      * global-memory gathers, 20 = LDS V-tile (rows of the lowest-id features of V staged in LDS); the tiles only help when ids
-     * are frequency-ranked (hot = low id), results are the same either way */
+     * are frequency-ranked (hot = low id), results are the same either way.  61 = the w-tile kernel without the issue priority that
+     * its row walk of up to 32 (padded) factors raises while it issues a step's requests (look-ahead stream loads, w lookup,
+     * V-row gathers; dropped for the arithmetic): the A/B switch of profiles/fwd_phase.md.  The other kernels raise none and
+     * ignore bit 0 (1 = 0, 21 = 20); bit-identical either way (only WHEN a wave issues its loads changes) */
     FMHIP_TUNE_FORWARD_KERNEL = 0,
     /* backward kernel: 1 = pipelined buffer-load walk (default), 0 = plain walk */
     FMHIP_TUNE_BACKWARD_KERNEL = 1,

@@ -76,6 +76,8 @@ SYMBOLS_BPR = ("fmhip_bpr_create", "fmhip_bpr_destroy", "fmhip_bpr_info", "fmhip
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
 TUNE = {name[5:]: value for name, value in list(globals().items()) if name.startswith("TUNE_")}
+# values of FORWARD_KERNEL: the kernel, plus FWD_NO_ISSUE_PRIO for the w-tile kernel's instance without the raised issue priority
+FWD_WTILE, FWD_VTILE, FWD_PLAIN, FWD_NO_ISSUE_PRIO, FWD_DEFAULT = 60, 20, 0, 1, 60
 UNIQUE_ID_BYTES = 128
 # enum fmhip_loss (include/fmhip.h): the loss a model trains under (fmhip_model_set_loss)
 LOSS_SQUARED, LOSS_LOGISTIC = 0, 1

@@ -19,5 +19,9 @@ constexpr int kHotT = 16;          // slots of one page of the dense hot block (
 constexpr int kHotPages = 8;
 static_assert(kHotPages * kHotT <= 128, "a slot mask holds 128 bits");
 typedef unsigned __int128 slotmask_t;      // one bit per slot of the dense hot block
+// The priority a wave of the forward's row walk issues a step's requests at (s_setprio; fm_forward.hip, forward_rows: 1 gains half
+// as much at C3, 3 no more than 2: profiles/fwd_phase.md), and the bit of tuning key 0 (FMHIP_TUNE_FORWARD_KERNEL) that turns it off
+constexpr int kFwdIssuePrio = 2;
+constexpr int kFwdNoIssuePrio = 1;
 
 }  // namespace fmhip

@@ -31,11 +31,16 @@
 #ifndef FMHIP_EXP_NO_HOT
 #define FMHIP_EXP_NO_HOT 0
 #endif
+// phase probe (same results, but no kernel anyone should train with): FMHIP_EXP_PHASE_PROBE = n delays waves 2-3 of every workgroup
+// once by n x 64 cycles before their first row, 1000 + n every other workgroup instead (profiles/fwd_phase.md section 0)
+#ifndef FMHIP_EXP_PHASE_PROBE
+#define FMHIP_EXP_PHASE_PROBE 0
+#endif
 // ... none of which may reach a library anyone trains with: a build that sets one must say so (FMHIP_ABLATION_BUILD, which
 // tools/build_variant.sh passes for A/B variants), and fmhip_ablation_mask() reports it at run time (tests/test_host_cpu.py
 // asserts the shipped library's mask is 0)
 #define FMHIP_FWD_ABLATIONS ((FMHIP_EXP_NO_STREAM ? 1 : 0) | (FMHIP_EXP_NO_MATH ? 2 : 0) | (FMHIP_EXP_NO_W ? 4 : 0) | (FMHIP_EXP_NO_GATHER ? 8 : 0) | \
-                             (FMHIP_EXP_L1_GATHER ? 16 : 0) | (FMHIP_EXP_NO_HOT ? 32 : 0))
+                             (FMHIP_EXP_L1_GATHER ? 16 : 0) | (FMHIP_EXP_NO_HOT ? 32 : 0) | (FMHIP_EXP_PHASE_PROBE ? 64 : 0))
 #if FMHIP_FWD_ABLATIONS && !defined(FMHIP_ABLATION_BUILD)
 #error "a result-changing FMHIP_EXP_* ablation is set without FMHIP_ABLATION_BUILD: timing-only variants are built by tools/build_variant.sh"
 #endif
@@ -46,7 +51,7 @@ int forward_ablations() { return FMHIP_FWD_ABLATIONS; }
 
 namespace fmhip {
 
-std::atomic<int> g_tune[kTuneCount] = {60, 1, 0, 0, 2, 1, 0, 1, 0, 1, 0, 1, 4};   // forward: w-tile kernel; backward: pipelined; tile rows: auto; row blocks: off; backward placement: band-affine; hot block: on; row order: on; forced flat loads: off; lazy decay: on; fused update: off; merged finish: on; hot pages: 4 of up to kHotPages (pages 5-8 measured: no gain, profiles/r03_experiments.md)
+std::atomic<int> g_tune[kTuneCount] = {60, 1, 0, 0, 2, 1, 0, 1, 0, 1, 0, 1, 4};   // forward: w-tile kernel, issue priority raised (61 = not); backward: pipelined; tile rows: auto; row blocks: off; backward placement: band-affine; hot block: on; row order: on; forced flat loads: off; lazy decay: on; fused update: off; merged finish: on; hot pages: 4 of up to kHotPages (pages 5-8 measured: no gain, profiles/r03_experiments.md)
 
 int padded_factors(int k) {
     int kp = 32;   // a row is at least one 128-B line: the cost of a gather is per line, not per byte
@@ -224,7 +229,9 @@ __device__ __forceinline__ void slot_entries(const int *sc, int c, int c0, int (
 // BUF: V fits a 32-bit buffer view (< 4 GiB): a row's address is ONE 32-bit shift-add per entry (the
 // descriptor lives in scalar registers) instead of a 64-bit multiply-add pair, and the dead entries of a
 // partial step fetch nothing (out-of-range offset).  Wider tables take flat 64-bit addresses.
-template <int LPN, int J, int CH, bool MASKED, bool BUF>
+// PRIO: the caller raised the wave's issue priority for the step's requests (forward_rows, PH = 1); it drops once the gathers of
+// the step's first chunk — at Kp <= 64 the whole step — are out.
+template <int LPN, int J, int CH, bool MASKED, bool BUF, bool PRIO = false>
 __device__ __forceinline__ void fwd_step(const float *V, __amdgpu_buffer_rsrc_t vr, const int *sc, int c, float x, int cnt, int l, float4 (&q)[J],
                                          float4 (&s)[J]) {
     constexpr int KP = 4 * LPN * J;
@@ -249,6 +256,10 @@ __device__ __forceinline__ void fwd_step(const float *V, __amdgpu_buffer_rsrc_t 
                     for (int jj = 0; jj < J; ++jj) t[j][jj] = vp[jj * LPN];
                 }
             }
+        }
+        if (PRIO && c0 == 0) {
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_setprio(0);
         }
         if (FMHIP_FWD_LDS_SHARE) __builtin_amdgcn_sched_barrier(0);
         int xi[CH];
@@ -495,7 +506,15 @@ __device__ __forceinline__ float w_lookup(const FwdArgs &a, __amdgpu_buffer_rsrc
 // frequency-ranked ids) feature ids are read from the LDS tile `wt` — a 64-lane gather of w costs ~2 TA
 // cycles per distinct line touched, as much per nonzero as the whole 128-B V-row gather
 // (profiles/r01_experiments.md §13); lanes whose id is in the tile drop out of the global gather.
-template <int LPN, int J, int MODE, bool PACKED, bool HOT, bool WT, bool BUF>
+//
+// PH = 1 (unless bit 0 of tuning key 0, FMHIP_TUNE_FORWARD_KERNEL, is set; the look-ahead walk only): the wave's issue priority is up
+// from the top of a step until its gathers are out — the look-ahead stream requests, the w lookup and the gathers' address
+// arithmetic then win the vector ALU from other waves' FMAs, and the wave's requests reach the texture path sooner — and down
+// for the accumulation, the hand-off and the row finish.  One raise and one drop per step; WHEN a wave issues changes, never what
+// it sums or in which order: the bits are those of PH = 0.  Measured (profiles/fwd_phase.md): the w-tile kernel at Kp = 32 gains
+// 2.5-3 us per launch at C3; packed rows lose 1 us at C2, the plain kernel on unpacked rows 1.4 us, Kp = 64 does not move — so
+// only k_forward_wt at Kp = 32 has a PH = 1 instance (launch_wt).
+template <int LPN, int J, int MODE, bool PACKED, bool HOT, bool WT, bool BUF, int PH = 0>
 __device__ __forceinline__ void forward_rows(const FwdArgs &a, const float *wt, const float *vh, const float *wh, bool hot_plain) {
     __shared__ __attribute__((aligned(16))) int stage[FMHIP_FWD_LDS_SHARE ? 2 * kBlock : 4];   // slot_share
     constexpr int SLOTS = kBlock / LPN;
@@ -511,6 +530,13 @@ __device__ __forceinline__ void forward_rows(const FwdArgs &a, const float *wt, 
     const float *valb = a.val + a.nz0;
     float st1 = 0.f, st2 = 0.f, stbad = 0.f, stl = 0.f;   // this thread's share of {sum e, sum e^2, nonfinite, log-loss}
     if (BUF && FMHIP_FWD_AHEAD) {
+#if FMHIP_EXP_PHASE_PROBE
+        {
+            const bool late = FMHIP_EXP_PHASE_PROBE >= 1000 ? (((blockIdx.x >> 3) ^ (blockIdx.x >> 8)) & 1) != 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) >= 2;
+            if (late)
+                for (int i = 0; i < FMHIP_EXP_PHASE_PROBE % 1000; ++i) __builtin_amdgcn_s_sleep(1);
+        }
+#endif
         // Through a buffer view one loop serves full and partial steps — a dead entry is id -1 with value 0: its row offset
         // lies past the end of V (a multiple of the row size below 2^32), the gather fetches nothing and returns 0, and 0 * 0
         // adds exactly nothing — and the entries of the row's NEXT step are requested before this step's gathers, so the
@@ -542,6 +568,7 @@ __device__ __forceinline__ void forward_rows(const FwdArgs &a, const float *wt, 
             for (uint32_t base = p0; base < p1; base += LPN) {
                 const int c = live_n ? c_n : -1;
                 const float x = live_n ? x_n : 0.f;
+                if constexpr (PH == 1) __builtin_amdgcn_s_setprio(kFwdIssuePrio);
                 const uint32_t pos = base + LPN + l;
                 if (PACKED) {
                     // unconditional loads (a dead lane reads a harmless word), the dead-lane select left to the consumer
@@ -559,7 +586,7 @@ __device__ __forceinline__ void forward_rows(const FwdArgs &a, const float *wt, 
                 }
                 float wv = 0.f;
                 if (!PACKED && !FMHIP_EXP_NO_W && c >= 0) wv = w_lookup<WT, BUF>(a, wr, wt, T, c);
-                fwd_step<LPN, J, CH, false, BUF>(a.V, vr, slot_publish<LPN>(stage, c, x, l), c, x, LPN, l, q, s);
+                fwd_step<LPN, J, CH, false, BUF, PH == 1>(a.V, vr, slot_publish<LPN>(stage, c, x, l), c, x, LPN, l, q, s);
                 if (!PACKED) lin = fmaf(wv, x, lin);
             }
             row_finish<LPN, J, MODE, PACKED>(a, r, l, q, s, lin, w0, st1, st2, stbad, stl);
@@ -636,7 +663,7 @@ __global__ __launch_bounds__(kBlock, (LPN * J <= 8 && HOT ? FMHIP_FWD_PLAIN_WGS 
 #ifndef FMHIP_FWD_WGS
 #define FMHIP_FWD_WGS 5       // waves per SIMD the compiler budgets registers for (Kp = 32); 6 was measured: r04_experiments.md section 18
 #endif
-template <int LPN, int J, int MODE, bool HOT, bool BUF>
+template <int LPN, int J, int MODE, bool HOT, bool BUF, int PH = 0>
 __global__ __launch_bounds__(kBlock, (LPN * J <= 8 ? FMHIP_FWD_WGS : 1)) void k_forward_wt(FwdArgs a) {
     constexpr int KP = 4 * LPN * J;
     extern __shared__ __attribute__((aligned(16))) float wt[];
@@ -646,7 +673,7 @@ __global__ __launch_bounds__(kBlock, (LPN * J <= 8 ? FMHIP_FWD_WGS : 1)) void k_
     bool hot_plain = false;
     if (HOT) hot_plain = hot_stage<KP>(a, vh, wh);
     else __syncthreads();
-    forward_rows<LPN, J, MODE, false, HOT, true, BUF>(a, wt, vh, wh, hot_plain);
+    forward_rows<LPN, J, MODE, false, HOT, true, BUF, PH>(a, wt, vh, wh, hot_plain);
 }
 
 // Pass B of the two-pass forward (kFwdPartB): a row has a handful of cold entries — the features at or above the top cut, a few per
@@ -719,6 +746,16 @@ __global__ __launch_bounds__(kBlock) void k_rescale(float *V, float *w, int64_t 
     }
 }
 
+// FwdArgs::phase (tuning key 0's bit 0, inverted) -> the PH instance of the row walk: only the w-tile kernel of Kp = 32 rows through a
+// buffer view has one (forward_rows); every other launch is the kernel as it was before the priority raise existed.
+template <int LPN, int J, int MODE, bool HOT, bool BUF>
+void launch_wt(const FwdArgs &a, dim3 g, dim3 b, size_t lds, hipStream_t s) {
+    if constexpr (LPN * J <= 8 && BUF) {
+        if (a.phase == 1) { hipLaunchKernelGGL((k_forward_wt<LPN, J, MODE, HOT, BUF, 1>), g, b, lds, s, a); return; }
+    }
+    hipLaunchKernelGGL((k_forward_wt<LPN, J, MODE, HOT, BUF, 0>), g, b, lds, s, a);
+}
+
 // The one place that decides which forward kernel runs and how large its grid is (the number of
 // per-block statistic partials the launch writes): packed rows carry w in the row, so only the plain
 // kernel handles them; the LDS V-tile kernel needs V to fit a 32-bit buffer view and has no hot-block
@@ -752,7 +789,7 @@ hipError_t fwd_launch(const FwdArgs &a, hipStream_t s, int *n_partials) {
     if constexpr (!plain_only) {
     if (pl.var == 60) {
         const size_t lds_bytes = (size_t)a.wt_rows * sizeof(float);
-#define FMHIP_WT(HOT_, BUF_) hipLaunchKernelGGL((k_forward_wt<LPN, J, MODE, HOT_, BUF_>), g, b, lds_bytes, s, a)
+#define FMHIP_WT(HOT_, BUF_) launch_wt<LPN, J, MODE, HOT_, BUF_>(a, g, b, lds_bytes, s)
         if (a.hot_T) { if (buf) FMHIP_WT(true, true); else FMHIP_WT(true, false); }
         else { if (buf) FMHIP_WT(false, true); else FMHIP_WT(false, false); }
 #undef FMHIP_WT
@@ -813,11 +850,11 @@ hipError_t fwd_launch_pass(const FwdArgs &a0, hipStream_t s, int *n_partials) {
             if (pl.var == 60) {
                 const size_t lds_bytes = (size_t)a.wt_rows * sizeof(float);
                 if (a.hot_T) {
-                    if (buf) hipLaunchKernelGGL((k_forward_wt<LPN, J, MODE, true, true>), g, b, lds_bytes, s, a);
-                    else hipLaunchKernelGGL((k_forward_wt<LPN, J, MODE, true, false>), g, b, lds_bytes, s, a);
+                    if (buf) launch_wt<LPN, J, MODE, true, true>(a, g, b, lds_bytes, s);
+                    else launch_wt<LPN, J, MODE, true, false>(a, g, b, lds_bytes, s);
                 } else {
-                    if (buf) hipLaunchKernelGGL((k_forward_wt<LPN, J, MODE, false, true>), g, b, lds_bytes, s, a);
-                    else hipLaunchKernelGGL((k_forward_wt<LPN, J, MODE, false, false>), g, b, lds_bytes, s, a);
+                    if (buf) launch_wt<LPN, J, MODE, false, true>(a, g, b, lds_bytes, s);
+                    else launch_wt<LPN, J, MODE, false, false>(a, g, b, lds_bytes, s);
                 }
                 return hipGetLastError();
             }

@@ -77,7 +77,8 @@ struct FwdArgs {
     // host-side launch choices (the model's tuning keys 0 and 6; the kernels never read them)
     int32_t variant;   // 60 = LDS w-tile kernel, 20 = LDS V-tile kernel, 0 = plain
     int32_t occ_cap;   // cap on the w-tile kernel's resident workgroups per CU (0 = all that fit)
-    int32_t loss;      // Loss: the residual the row finish forms (host side: launch_forward picks the kernel instance by it)
+    int32_t phase;     // bit 0 of the model's tuning key 0 inverted: 1 = the w-tile kernel's walk with raised issue priority where it has an instance (fm_forward.hip, launch_wt), 0 = the plain walk
+    int32_t loss;     // Loss: the residual the row finish forms (host side: launch_forward picks the kernel instance by it)
 };
 
 // Fused update (single-GPU step, nothing to exchange): a finished gradient row is applied to its parameter row on

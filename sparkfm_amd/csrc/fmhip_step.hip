@@ -151,7 +151,9 @@ FwdArgs fwd_args(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm) {
         if (m->tv(kTuneTile) > 0) t = m->tv(kTuneTile);
         a.tile_rows = (int32_t)std::min<int64_t>(t, m->n1);
         a.wt_rows = (int32_t)std::min<int64_t>(m->tv(kTuneTile) > 0 ? m->tv(kTuneTile) : 6144, m->n1);   // 24 KiB
-        a.variant = m->tv(kTuneFwd);
+        // key 0 = the kernel (60 / 20 / 0), plus 1 for the w-tile kernel's instance without the raised issue priority (fm_forward.hip, launch_wt)
+        a.variant = m->tv(kTuneFwd) & ~kFwdNoIssuePrio;
+        a.phase = (m->tv(kTuneFwd) & kFwdNoIssuePrio) ? 0 : 1;
         a.occ_cap = m->tv(kTuneFwdOcc);
     }
     return a;
