@@ -205,6 +205,13 @@ struct fmhip_bpr;
 int fmhip_bpr_debug_inverse(struct fmhip_bpr *h, int64_t batch, int32_t *trow, int32_t *tptr, int32_t *tj, int32_t *wt, int32_t *wbeg,
                             int32_t *wdst, int32_t *lt, int32_t *lfirst, int32_t *lcount, int32_t *counts);
 
+/* ---- the adaptive sampler's candidates (tests) ---------------------------------------------- */
+/* What the adaptive sampler (include/fmhip_bpr_adaptive.h) sees for the pairs [p0, p1) at epoch t under the model as it stands: the
+ * sampler's kernel in its record mode.  rows / scores: (p1 - p0) * n_cand entries, candidate c of pair p at (p - p0) * n_cand + c —
+ * its row and its score yq_i + <q_u, q_i>.  The mapping, the inverse map and the sample statistics are left alone.  Folds the
+ * model's scales (as a training call does) and synchronises. */
+int fmhip_bpr_debug_adaptive(fmhip_model_t m, struct fmhip_bpr *h, int64_t t, int64_t p0, int64_t p1, int32_t *rows, float *scores);
+
 #ifdef __cplusplus
 }
 #endif

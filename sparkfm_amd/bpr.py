@@ -28,10 +28,13 @@ class HipBPR(FMLearn):
     n_pairs = n_neg * (number of interactions) pairs; pair p belongs to interaction p // n_neg of the TRAINING ORDER, fixed here:
     context-ascending (rows ascending inside a context), or with shuffle=True a ``PCG64([seed])`` permutation of that.
     `batch_pairs`: pairs per mini-batch (0: one batch).  `seed` also keys the sampler.  `loss`: "logistic" (BPR) or "squared" (the
-    squared pair loss); `optimizer` and the AdaGrad settings as ``HipSGD``.  The model's pairing flag is neither read nor set."""
+    squared pair loss); `optimizer` and the AdaGrad settings as ``HipSGD``.  The model's pairing flag is neither read nor set.
+    `n_candidates` (1 .. 64): above 1 every epoch draws that many candidates per pair and trains on the one the model scores
+    highest at the epoch's start (include/fmhip_bpr_adaptive.h) — once per epoch, so with several batches the later ones see
+    choices made before the earlier batches' updates; 1 is the uniform sampler, bit for bit what it was."""
 
     def __init__(self, contexts, candidates, positives, n_neg=1, batch_pairs=0, seed=0, shuffle=True, eta=0.05, reg0=0.0, regw=0.0,
-                 regv=0.0, loss="logistic", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1):
+                 regv=0.0, loss="logistic", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1, n_candidates=1):
         for what, d in (("contexts", contexts), ("candidates", candidates)):
             if not isinstance(d, DataSet):
                 raise TypeError("%s must be a DataSet, not %s" % (what, type(d).__name__))
@@ -48,6 +51,11 @@ class HipBPR(FMLearn):
             raise ValueError("n_neg must be >= 1, not %d" % self.n_neg)
         if candidates.size < 2:
             raise ValueError("candidates has %d rows: a pair needs at least 2" % candidates.size)
+        if isinstance(n_candidates, bool):
+            raise TypeError("n_candidates must be an integer, not %r" % (n_candidates,))
+        self._n_candidates = operator.index(n_candidates)
+        if not 1 <= self._n_candidates <= _ffi.BPR_MAX_CANDIDATES:
+            raise ValueError("n_candidates must be in [1, %d], not %d" % (_ffi.BPR_MAX_CANDIDATES, self._n_candidates))
         self.seed = operator.index(seed)
         if not 0 <= self.seed < 2 ** 64:
             raise ValueError("seed must be in [0, 2^64), not %r" % (seed,))
@@ -110,7 +118,14 @@ class HipBPR(FMLearn):
             _ffi.check(_ffi.load().fmhip_bpr_create(self.device, blocks[0], blocks[1], len(self.inter_ctx), _ffi.ptr(self.inter_ctx),
                                                     _ffi.ptr(self.inter_cand), self.n_neg, self.batch_pairs, self.seed, C.byref(h)))
             self._h, self._for = h, blocks
+            if self._n_candidates > 1:
+                _ffi.check(_ffi.load().fmhip_bpr_set_candidates(h, self._n_candidates))
         return self._h
+
+    @property
+    def n_candidates(self):
+        """Candidates drawn per pair and epoch (include/fmhip_bpr_adaptive.h); 1: the uniform sampler."""
+        return self._n_candidates
 
     def info(self):
         v = [C.c_int64() for _ in range(4)]
@@ -131,12 +146,32 @@ class HipBPR(FMLearn):
             pass
 
     # -- the draw ---------------------------------------------------------------------------
-    def resample(self, t):
-        """Redraws every pair's negative at epoch `t` (fmhip_bpr_resample) -> ``sample_stats``: attempts, forced."""
-        st = _ffi.BprSampleStats()
-        _ffi.check(_ffi.load().fmhip_bpr_resample(self.handle, operator.index(t), C.byref(st)))
+    def resample(self, t, fm=None):
+        """Redraws every pair's negative at epoch `t` -> ``sample_stats``.  Without a model the draw is uniform (fmhip_bpr_resample:
+        attempts, forced).  With `fm` it is the best of `n_candidates` candidates under the model as it stands
+        (fmhip_bpr_resample_adaptive: attempts, forced, replaced — the pairs whose kept candidate is not the uniform draw)."""
+        if fm is None:
+            if self._n_candidates > 1:
+                raise ValueError("n_candidates = %d: the adaptive draw needs a model — resample(t, fm)" % self._n_candidates)
+            st = _ffi.BprSampleStats()
+            _ffi.check(_ffi.load().fmhip_bpr_resample(self.handle, operator.index(t), C.byref(st)))
+        else:
+            st = _ffi.BprAdaptiveStats()
+            _ffi.check(_ffi.load().fmhip_bpr_resample_adaptive(fm.handle, self.handle, operator.index(t), C.byref(st)))
         self.sample_stats = st.as_dict()
         return self.sample_stats
+
+    def candidate_draws(self, fm, t, p0=0, p1=None):
+        """(rows int32, scores float32), each [p1 - p0, n_candidates]: what the adaptive sampler sees for the pairs [p0, p1) at epoch
+        `t` under `fm` — every candidate's row and its score yq_i + <q_u, q_i> (fmhip_bpr_debug_adaptive).  Changes no draw."""
+        p0 = operator.index(p0)
+        p1 = self.n_pairs if p1 is None else operator.index(p1)
+        if not 0 <= p0 < p1 <= self.n_pairs:
+            raise ValueError("pairs [%d, %d) must be a non-empty range inside [0, %d)" % (p0, p1, self.n_pairs))
+        rows = np.empty((p1 - p0, self._n_candidates), np.int32)
+        scores = np.empty((p1 - p0, self._n_candidates), np.float32)
+        _ffi.check(_ffi.load().fmhip_bpr_debug_adaptive(fm.handle, self.handle, operator.index(t), p0, p1, _ffi.ptr(rows), _ffi.ptr(scores)))
+        return rows, scores
 
     def negatives(self):
         """int32 [n_pairs]: the current draw (the draw at t = 0 until the first resample or learn)."""
@@ -179,7 +214,8 @@ class HipBPR(FMLearn):
         _ffi.check(L.fmhip_model_set_optimizer(fm.handle, self._opt_code, self.adagrad_eps, self.adagrad_init))
 
     def learn(self, fm, dataset=None):
-        """One epoch (fmhip_bpr_epoch): resample at t = the epochs done, then every batch in order.  `dataset` is not read."""
+        """One epoch (fmhip_bpr_epoch): resample at t = the epochs done (adaptively under `fm` when n_candidates > 1), then every
+        batch in order.  `dataset` is not read."""
         st = _ffi.Stats()
         self._set_rule(fm)
         _ffi.check(_ffi.load().fmhip_bpr_epoch(fm.handle, self.handle, self._epoch, self.eta, self.reg0, self.regw, self.regv, None,

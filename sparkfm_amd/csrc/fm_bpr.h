@@ -22,6 +22,28 @@ struct BprSampleArgs {
 int bpr_sample_blocks(int64_t n_pairs);
 hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s);
 
+// The adaptive sampler (k_bpr_sample_adaptive; the rule: include/fmhip_bpr_adaptive.h).  A group of G = Kp / 4 lanes (8 .. 64) per
+// pair: lane l keeps floats 4l .. 4l+3 of the context's q row in registers, the group's lanes draw the pair's n_cand candidate
+// rows side by side (lane l candidates l, l + G, ...; rng::negative_row with group0 = c << 4), then candidate by candidate the
+// group gathers the row's q slice, multiplies and sums over the group by an xor-shuffle tree — an order Kp alone fixes — and lane 0
+// writes the first strict maximum into map[2p + 1].  Qu / Qi / yqi are what the kFwdQ forwards of the two blocks left (rel.Q,
+// rel.yq); floats k .. Kp-1 of the context's slice (the packed slot and the padding) are cleared in registers, so the score does
+// not rest on what the tables hold there.  Record mode (rec_rows set): pairs [p0, p1) only, every candidate's row and score out,
+// the mapping left alone.
+struct BprAdaptiveArgs {
+    BprSampleArgs s;           // part: [bpr_adaptive_blocks][3] {attempts, forced, replaced pairs}; total: [3]
+    int32_t n_cand;            // 1 .. kBprMaxCand
+    int32_t k;                 // the model's factors: floats [k, Kp) of a q row are no factors
+    const float *Qu, *Qi;      // [n_ctx][Kp], [M][Kp]
+    const float *yqi;          // [M]
+    int32_t p0, p1;            // record mode: the pairs written
+    int32_t *rec_rows;         // [(p1 - p0) * n_cand] or nullptr
+    float *rec_scores;         // [(p1 - p0) * n_cand]
+};
+constexpr int kBprMaxCand = 64;
+int bpr_adaptive_blocks(int Kp, int64_t n_pairs);
+hipError_t launch_bpr_sample_adaptive(int Kp, const BprAdaptiveArgs &a, hipStream_t s);
+
 // The inverse map of ONE batch (fmhip::host::RelationInverse::append_batch, array for array) from the batch's slice of the mapping:
 // one radix sort of (block row, batch-local row) words over the bits the two need, the lists read off the sorted words, the work
 // list at the cut by scans.  Every output array has the capacity its worst case needs: trow / tj / wt / wbeg / wdst `rows`, tptr

@@ -1,6 +1,8 @@
 // fm_bpr.hip — the BPR trainer's device work (fm_bpr.h): k_bpr_sample draws a negative row per pair, and the k_bpr_inv_* kernels
 // around one rocPRIM radix sort and two scans rebuild the candidates relation's inverse map of a batch.  Integer arithmetic only;
-// every address has one writer and nothing depends on the launch shape.
+// every address has one writer and nothing depends on the launch shape.  k_bpr_sample_adaptive (include/fmhip_bpr_adaptive.h) draws
+// several candidates per pair with the same integer code and keeps the one the model scores highest: the one place with fp32 in it,
+// a dot product whose summation order the row width alone fixes.
 #include "fm_bpr.h"
 #include "mcmc_rng.h"
 
@@ -66,6 +68,143 @@ __global__ __launch_bounds__(kT) void k_bpr_sample_total(const u64 *part, int n_
         for (int w = 0; w < kT / 64; ++w) v += sh[threadIdx.x][w];
         total[threadIdx.x] = v;
     }
+}
+
+// ---- the adaptive sampler (fm_bpr.h: BprAdaptiveArgs) -----------------------------------------------------------------------------
+
+__device__ __forceinline__ float f4dot(float4 a, float4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); }
+
+constexpr int kCandChunk = 4;       // candidate rows a group has in flight before it reduces: the gathers' latency overlaps
+
+// G lanes per pair, kT / G pairs per block and pass.  The trip count is the block's (`base` is uniform), and a group whose pair lies
+// past the end works on the last pair again and writes nothing: no lane leaves before the block's last shuffle.  A score is
+// yq_i + (the lanes' 4-term fmaf chains summed by the xor tree over G): the same in every lane of the group, whatever the grid.
+template <int G, bool RECORD>
+__global__ __launch_bounds__(kT) void k_bpr_sample_adaptive(BprAdaptiveArgs a) {
+    constexpr int KP = 4 * G, GPB = kT / G;
+    const int l = threadIdx.x & (G - 1), grp = threadIdx.x / G;
+    const int64_t first = RECORD ? a.p0 : 0, end = RECORD ? a.p1 : a.s.n_pairs;
+    const int C = a.n_cand;
+    u64 att = 0, forced = 0, repl = 0;
+    for (int64_t base = first + (int64_t)blockIdx.x * GPB; base < end; base += (int64_t)gridDim.x * GPB) {
+        const bool live = base + grp < end;
+        const int64_t p = live ? base + grp : end - 1;
+        const int32_t u = a.s.ictx[p / a.s.n_neg];
+        const int64_t lo = a.s.pptr[u];
+        const int32_t len = (int32_t)(a.s.pptr[u + 1] - lo);
+        float4 qu = reinterpret_cast<const float4 *>(a.Qu + (size_t)u * KP)[l];
+        if (4 * l + 0 >= a.k) qu.x = 0.f;      // the packed slot and the padding are no factors
+        if (4 * l + 1 >= a.k) qu.y = 0.f;
+        if (4 * l + 2 >= a.k) qu.z = 0.f;
+        if (4 * l + 3 >= a.k) qu.w = 0.f;
+        int32_t keep = 0, keep_c = 0;
+        float best = 0.f;
+        for (int c0 = 0; c0 < C; c0 += G) {
+            // the group's lanes draw candidates c0 .. c0 + G - 1 side by side
+            int32_t mine = 0;
+            if (c0 + l < C) {
+                int at = 0, f = 0;
+                mine = rng::negative_row(a.s.seed, (uint32_t)p, a.s.t, (uint32_t)a.s.M, a.s.prow + lo, len, &at, &f, (uint32_t)(c0 + l) << 4);
+                if (live) {
+                    att += (u64)at;
+                    forced += (u64)f;
+                }
+            }
+            const int n = C - c0 < G ? C - c0 : G;
+            for (int j0 = 0; j0 < n; j0 += kCandChunk) {
+                int32_t row[kCandChunk];
+                float4 qi[kCandChunk];
+                float yq[kCandChunk], d[kCandChunk];
+#pragma unroll
+                for (int jj = 0; jj < kCandChunk; ++jj) {
+                    const int j = j0 + jj < n ? j0 + jj : n - 1;       // (past the last candidate: the last one again, not compared)
+                    row[jj] = __shfl(mine, j, G);
+                    qi[jj] = reinterpret_cast<const float4 *>(a.Qi + (size_t)row[jj] * KP)[l];
+                    yq[jj] = a.yqi[row[jj]];
+                }
+#pragma unroll
+                for (int jj = 0; jj < kCandChunk; ++jj) d[jj] = f4dot(qu, qi[jj]);
+#pragma unroll
+                for (int m = G >> 1; m >= 1; m >>= 1)
+#pragma unroll
+                    for (int jj = 0; jj < kCandChunk; ++jj) d[jj] += __shfl_xor(d[jj], m, G);
+#pragma unroll
+                for (int jj = 0; jj < kCandChunk; ++jj) {
+                    const int c = c0 + j0 + jj;
+                    if (j0 + jj >= n) break;
+                    const float s = yq[jj] + d[jj];
+                    if (RECORD && live && l == 0) {
+                        const size_t at = (size_t)(p - a.p0) * (size_t)C + (size_t)c;
+                        a.rec_rows[at] = row[jj];
+                        a.rec_scores[at] = s;
+                    }
+                    if (c == 0 || s > best) {      // candidate 0 is the incumbent; a NaN is never greater
+                        best = s;
+                        keep = row[jj];
+                        keep_c = c;
+                    }
+                }
+            }
+        }
+        if (!RECORD && live && l == 0) {
+            a.s.map[2 * p + 1] = keep;
+            repl += keep_c != 0 ? 1u : 0u;
+        }
+    }
+    if (RECORD) return;
+    __shared__ u64 sh[3][kT / 64];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        att += __shfl_xor(att, m, 64);
+        forced += __shfl_xor(forced, m, 64);
+        repl += __shfl_xor(repl, m, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sh[0][threadIdx.x >> 6] = att;
+        sh[1][threadIdx.x >> 6] = forced;
+        sh[2][threadIdx.x >> 6] = repl;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        u64 s = 0;
+        for (int w = 0; w < kT / 64; ++w) s += sh[threadIdx.x][w];
+        a.s.part[3 * (size_t)blockIdx.x + threadIdx.x] = s;
+    }
+}
+
+// one block: the sums of the per-block {attempts, forced, replaced}
+__global__ __launch_bounds__(kT) void k_bpr_adaptive_total(const u64 *part, int n_blocks, u64 *total) {
+    u64 s[3] = {0, 0, 0};
+    for (int b = threadIdx.x; b < n_blocks; b += kT)
+        for (int i = 0; i < 3; ++i) s[i] += part[3 * (size_t)b + i];
+    __shared__ u64 sh[3][kT / 64];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+        for (int i = 0; i < 3; ++i) s[i] += __shfl_xor(s[i], m, 64);
+    if ((threadIdx.x & 63) == 0)
+        for (int i = 0; i < 3; ++i) sh[i][threadIdx.x >> 6] = s[i];
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        u64 v = 0;
+        for (int w = 0; w < kT / 64; ++w) v += sh[threadIdx.x][w];
+        total[threadIdx.x] = v;
+    }
+}
+
+template <int G>
+hipError_t launch_adaptive(const BprAdaptiveArgs &a, hipStream_t s) {
+    const bool record = a.rec_rows != nullptr;
+    const int64_t n = record ? (int64_t)a.p1 - a.p0 : a.s.n_pairs;
+    const int blocks = bpr_adaptive_blocks(4 * G, n);
+    if (record) {
+        hipLaunchKernelGGL((k_bpr_sample_adaptive<G, true>), dim3((unsigned)blocks), dim3(kT), 0, s, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((k_bpr_sample_adaptive<G, false>), dim3((unsigned)blocks), dim3(kT), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_bpr_adaptive_total, dim3(1), dim3(kT), 0, s, a.s.part, blocks, a.s.total);
+    return hipGetLastError();
 }
 
 // ---- the inverse map --------------------------------------------------------------------------------------------------------------
@@ -214,6 +353,26 @@ hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s) {
     BPR_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_bpr_sample_total, dim3(1), dim3(kT), 0, s, a.part, blocks, a.total);
     return hipGetLastError();
+}
+
+int bpr_adaptive_blocks(int Kp, int64_t n_pairs) {
+    const int64_t per_block = kT / (Kp / 4);      // a group of Kp / 4 lanes per pair
+    int64_t blocks = (n_pairs + per_block - 1) / per_block;
+    if (blocks > 4096) blocks = 4096;       // pairs grid-strided
+    if (blocks < 1) blocks = 1;
+    return (int)blocks;
+}
+
+hipError_t launch_bpr_sample_adaptive(int Kp, const BprAdaptiveArgs &a, hipStream_t s) {
+    if (a.n_cand < 1 || a.n_cand > kBprMaxCand || a.k < 0 || a.k > Kp) return hipErrorInvalidValue;
+    if (a.rec_rows && (!a.rec_scores || a.p0 < 0 || a.p1 > a.s.n_pairs || a.p0 >= a.p1)) return hipErrorInvalidValue;
+    switch (Kp) {
+        case 32: return launch_adaptive<8>(a, s);
+        case 64: return launch_adaptive<16>(a, s);
+        case 128: return launch_adaptive<32>(a, s);
+        case 256: return launch_adaptive<64>(a, s);
+        default: return hipErrorInvalidValue;      // (padded_factors: a power of two in [32, 256])
+    }
 }
 
 hipError_t bpr_inverse_workspace(int32_t rows, int32_t block_rows, size_t *bytes) {

@@ -1,9 +1,11 @@
 // fmhip_bpr.hip — the BPR trainer (include/fmhip_bpr.h): the handle (an owned relational dataset of 2 n_pairs rows over the two
 // borrowed blocks), the resample
 //     k_bpr_sample (the candidates mapping's odd entries) -> per batch the inverse map on the device (fm_bpr.hip) -> the counts back
-// and the training calls, which are the relational step in its pairs mode (rel_step, fmhip_relational.hip).  The kernels are in
+// (adaptive, include/fmhip_bpr_adaptive.h: the two blocks' kFwdQ forwards on the model's stream first, then k_bpr_sample_adaptive in
+// k_bpr_sample's place) and the training calls, which are the relational step in its pairs mode (rel_step, fmhip_relational.hip).  The kernels are in
 // fm_bpr.hip; the host arithmetic (the positives' lists, the sampler's twin) in fmhip_host.cpp.
 #include "fmhip_internal.h"
+#include "../../include/fmhip_bpr_adaptive.h"
 #include "fm_bpr.h"
 #include "fm_relational.h"
 
@@ -39,14 +41,7 @@ int check_bpr(fmhip_model_t m, fmhip_bpr_t h) {
     return check_rel_model(m, h->R);
 }
 
-// the sampler at epoch t, the inverse map of every batch, the batches' counts (one synchronisation); the handle's own stream
-int resample(fmhip_bpr_t h, int64_t t, fmhip_bpr_sample_stats *stats) {
-    if (t < 0 || t > 0xffffffffll) return fail(FMHIP_ERR_INVALID, "t = %lld: an epoch is in [0, 2^32)", (long long)t);
-    TRY(set_device(h->device));
-    fmhip_relational_t R = h->R;
-    fmhip_relational::Relation &rel = *R->rels[1];
-    // the mapping and the inverse map are read by the steps queued so far
-    if (R->busy_set) HIP_TRY(hipStreamWaitEvent(h->stream, R->busy, 0));
+BprSampleArgs sample_args(fmhip_bpr_t h, int64_t t) {
     BprSampleArgs sa{};
     sa.seed = h->seed;
     sa.t = (uint32_t)t;
@@ -56,10 +51,62 @@ int resample(fmhip_bpr_t h, int64_t t, fmhip_bpr_sample_stats *stats) {
     sa.ictx = h->ictx.p;
     sa.pptr = h->pptr.p;
     sa.prow = h->prow.p;
-    sa.map = rel.map.p;
+    sa.map = h->R->rels[1]->map.p;
     sa.part = h->spart.p;
     sa.total = h->stotal.p;
-    HIP_TRY(launch_bpr_sample(sa, h->stream));
+    return sa;
+}
+
+int check_epoch_index(int64_t t) {
+    if (t < 0 || t > 0xffffffffll) return fail(FMHIP_ERR_INVALID, "t = %lld: an epoch is in [0, 2^32)", (long long)t);
+    return FMHIP_OK;
+}
+
+// What the adaptive sampler reads, queued: the two blocks' kFwdQ forwards on the model's stream (rel_block_forwards), the handle's
+// stream behind them by an event — and behind the steps queued so far, which read the mapping.  -> the sampler's arguments
+int adaptive_args(fmhip_model_t m, fmhip_bpr_t h, int64_t t, BprAdaptiveArgs *out) {
+    fmhip_relational_t R = h->R;
+    TRY(rel_block_forwards(m, R));
+    if (!h->fwd_done) HIP_TRY(hipEventCreateWithFlags(&h->fwd_done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->fwd_done, m->stream));
+    HIP_TRY(hipStreamWaitEvent(h->stream, h->fwd_done, 0));
+    if (R->busy_set) HIP_TRY(hipStreamWaitEvent(h->stream, R->busy, 0));
+    TRY(h->apart.ensure(3 * (size_t)bpr_adaptive_blocks(m->Kp, h->n_pairs)));
+    TRY(h->atotal.ensure(3));
+    BprAdaptiveArgs aa{};
+    aa.s = sample_args(h, t);
+    aa.s.part = h->apart.p;
+    aa.s.total = h->atotal.p;
+    aa.n_cand = h->n_cand;
+    aa.k = m->k;
+    aa.Qu = R->rels[0]->Q.p;
+    aa.Qi = R->rels[1]->Q.p;
+    aa.yqi = R->rels[1]->yq.p;
+    *out = aa;
+    return FMHIP_OK;
+}
+
+// the sampler at epoch t, the inverse map of every batch, the batches' counts (one synchronisation); the handle's own stream.
+// m given: the adaptive sampler under that model (the caller has checked the two against each other and holds the model's lock),
+// else the uniform one.  total: {attempts, forced} or, adaptive, {attempts, forced, replaced}
+int resample(fmhip_bpr_t h, int64_t t, unsigned long long *total_out, fmhip_model_t m = nullptr) {
+    TRY(check_epoch_index(t));
+    TRY(set_device(h->device));
+    fmhip_relational_t R = h->R;
+    fmhip_relational::Relation &rel = *R->rels[1];
+    const int n_total = m ? 3 : 2;
+    const unsigned long long *d_total = nullptr;
+    if (m) {
+        BprAdaptiveArgs aa{};
+        TRY(adaptive_args(m, h, t, &aa));
+        HIP_TRY(launch_bpr_sample_adaptive(m->Kp, aa, h->stream));
+        d_total = h->atotal.p;
+    } else {
+        // the mapping and the inverse map are read by the steps queued so far
+        if (R->busy_set) HIP_TRY(hipStreamWaitEvent(h->stream, R->busy, 0));
+        HIP_TRY(launch_bpr_sample(sample_args(h, t), h->stream));
+        d_total = h->stotal.p;
+    }
     const size_t nb = R->batches.size();
     for (size_t b = 0; b < nb; ++b) {
         const RelationInverse::Batch &ib = rel.batches[b];
@@ -81,9 +128,9 @@ int resample(fmhip_bpr_t h, int64_t t, fmhip_bpr_sample_stats *stats) {
         HIP_TRY(launch_bpr_inverse(ia, h->work.p, h->work.n, h->stream));
     }
     std::vector<int32_t> counts(4 * nb);
-    unsigned long long total[2] = {0, 0};
+    unsigned long long total[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(counts.data(), h->counts.p, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(total, h->stotal.p, sizeof total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(total, d_total, (size_t)n_total * sizeof total[0], hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     int32_t max_part = 0;
     for (size_t b = 0; b < nb; ++b) {
@@ -101,10 +148,8 @@ int resample(fmhip_bpr_t h, int64_t t, fmhip_bpr_sample_stats *stats) {
         max_part = std::max(max_part, c[3]);
     }
     rel.max_part = max_part;      // (the step's workspace grows to it: ensure_rel_workspace)
-    if (stats) {
-        stats->attempts = (int64_t)total[0];
-        stats->forced = (int64_t)total[1];
-    }
+    if (total_out)
+        for (int i = 0; i < 3; ++i) total_out[i] = total[i];
     return FMHIP_OK;
 }
 
@@ -233,7 +278,64 @@ int fmhip_bpr_info(fmhip_bpr_t h, int64_t *n_pairs, int64_t *dimension, int64_t 
 
 int fmhip_bpr_resample(fmhip_bpr_t h, int64_t t, fmhip_bpr_sample_stats *stats) {
     if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
-    return resample(h, t, stats);
+    unsigned long long total[3];
+    TRY(resample(h, t, total));
+    if (stats) {
+        stats->attempts = (int64_t)total[0];
+        stats->forced = (int64_t)total[1];
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_bpr_set_candidates(fmhip_bpr_t h, int32_t n_cand) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (n_cand < 1 || n_cand > FMHIP_BPR_MAX_CANDIDATES)
+        return fail(FMHIP_ERR_INVALID, "n_cand = %d: a pair has 1 .. %d candidates", (int)n_cand, FMHIP_BPR_MAX_CANDIDATES);
+    h->n_cand = n_cand;
+    return FMHIP_OK;
+}
+
+int fmhip_bpr_get_candidates(fmhip_bpr_t h, int32_t *n_cand) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (!n_cand) return fail(FMHIP_ERR_INVALID, "n_cand is NULL");
+    *n_cand = h->n_cand;
+    return FMHIP_OK;
+}
+
+int fmhip_bpr_resample_adaptive(fmhip_model_t m, fmhip_bpr_t h, int64_t t, fmhip_bpr_adaptive_stats *stats) {
+    WriteLock lock(m);
+    TRY(check_bpr(m, h));
+    unsigned long long total[3];
+    TRY(resample(h, t, total, m));
+    if (stats) {
+        stats->attempts = (int64_t)total[0];
+        stats->forced = (int64_t)total[1];
+        stats->replaced = (int64_t)total[2];
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_bpr_debug_adaptive(fmhip_model_t m, struct fmhip_bpr *h, int64_t t, int64_t p0, int64_t p1, int32_t *rows, float *scores) {
+    WriteLock lock(m);
+    TRY(check_bpr(m, h));
+    TRY(check_epoch_index(t));
+    if (p0 < 0 || p1 > h->n_pairs || p0 >= p1)
+        return fail(FMHIP_ERR_INVALID, "pairs [%lld, %lld): a non-empty range inside [0, %lld)", (long long)p0, (long long)p1, (long long)h->n_pairs);
+    if (!rows || !scores) return fail(FMHIP_ERR_INVALID, "an out array is NULL");
+    const size_t n = (size_t)(p1 - p0) * (size_t)h->n_cand;
+    TRY(h->rec_rows.ensure(n));
+    TRY(h->rec_scores.ensure(n));
+    BprAdaptiveArgs aa{};
+    TRY(adaptive_args(m, h, t, &aa));
+    aa.p0 = (int32_t)p0;
+    aa.p1 = (int32_t)p1;
+    aa.rec_rows = h->rec_rows.p;
+    aa.rec_scores = h->rec_scores.p;
+    HIP_TRY(launch_bpr_sample_adaptive(m->Kp, aa, h->stream));
+    HIP_TRY(hipMemcpyAsync(rows, h->rec_rows.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(scores, h->rec_scores.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return FMHIP_OK;
 }
 
 int fmhip_bpr_negatives(fmhip_bpr_t h, int32_t *out) {
@@ -269,7 +371,7 @@ int fmhip_bpr_epoch(fmhip_model_t m, fmhip_bpr_t h, int64_t t, double eta, doubl
     if (order)
         for (int64_t j = 0; j < nb; ++j)
             if (order[j] < 0 || order[j] >= nb) return fail(FMHIP_ERR_INVALID, "batch %lld out of range [0, %lld)", (long long)order[j], (long long)nb);
-    TRY(resample(h, t, nullptr));
+    TRY(resample(h, t, nullptr, h->n_cand > 1 ? m : nullptr));
     HIP_TRY(hipMemsetAsync(m->acc.p, 0, 4 * sizeof(double), m->stream));
     const Sgd sgd{eta, reg0, regw, regv};
     int64_t nnz = 0;

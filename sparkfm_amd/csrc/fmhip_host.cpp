@@ -751,12 +751,16 @@ void bpr_positive_lists(int64_t n_ctx, int64_t n_inter, const int32_t *inter_ctx
     }
 }
 
-int32_t bpr_negative(uint64_t seed, uint32_t p, uint32_t t, int32_t M, const int32_t *list, int32_t len, int *attempts, int *forced) {
+int32_t bpr_candidate(uint64_t seed, uint32_t p, uint32_t c, uint32_t t, int32_t M, const int32_t *list, int32_t len, int *attempts, int *forced) {
     int a = 0, f = 0;
-    const int32_t c = rng::negative_row(seed, p, t, (uint32_t)M, list, len, &a, &f);
+    const int32_t row = rng::negative_row(seed, p, t, (uint32_t)M, list, len, &a, &f, c << 4);
     if (attempts) *attempts = a;
     if (forced) *forced = f;
-    return c;
+    return row;
+}
+
+int32_t bpr_negative(uint64_t seed, uint32_t p, uint32_t t, int32_t M, const int32_t *list, int32_t len, int *attempts, int *forced) {
+    return bpr_candidate(seed, p, 0, t, M, list, len, attempts, forced);
 }
 
 // ---- the MCMC learner's draws -------------------------------------------------------------------------------------------

@@ -191,6 +191,10 @@ void bpr_positive_lists(int64_t n_ctx, int64_t n_inter, const int32_t *inter_ctx
 // The negative row of pair p at epoch t: the host twin of k_bpr_sample (rng::negative_row, mcmc_rng.h — the same integer code, so
 // the two agree bit for bit).  list: the context's positives (ascending, distinct, len < M).  attempts / forced: nullable
 int32_t bpr_negative(uint64_t seed, uint32_t p, uint32_t t, int32_t M, const int32_t *list, int32_t len, int *attempts, int *forced = nullptr);
+// Candidate c = 0 .. 63 of the adaptive sampler (include/fmhip_bpr_adaptive.h): the same rule with the counter's group word
+// offset by c << 4 — the host twin of k_bpr_sample_adaptive's draws.  bpr_negative is its c = 0 case.
+int32_t bpr_candidate(uint64_t seed, uint32_t p, uint32_t c, uint32_t t, int32_t M, const int32_t *list, int32_t len, int *attempts,
+                      int *forced = nullptr);
 
 // ---- the MCMC learner's draws (fmhip_mcmc_epoch, include/fmhip_mcmc.h; the generator: mcmc_rng.h) ------------------------------
 // Counters are (index, group, t, stream); t = the epochs the handle has completed.

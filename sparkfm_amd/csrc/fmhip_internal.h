@@ -318,7 +318,15 @@ struct fmhip_bpr {
     DevBuf<unsigned long long> spart, stotal;  // the sampler's per-block partials and their sums
     DevBuf<char> work;                         // the inverse build's workspace, for the largest batch
     hipStream_t stream = nullptr;
+    // the adaptive sampler (include/fmhip_bpr_adaptive.h): candidates per pair, its {attempts, forced, replaced} partials and sums,
+    // the debug call's record buffers, and the event that puts the sampler (own stream) behind the blocks' forwards (the model's)
+    int32_t n_cand = 1;
+    DevBuf<unsigned long long> apart, atotal;
+    DevBuf<int32_t> rec_rows;
+    DevBuf<float> rec_scores;
+    hipEvent_t fwd_done = nullptr;
     ~fmhip_bpr() {
+        if (fwd_done) (void)hipEventDestroy(fwd_done);
         if (R) (void)fmhip_relational_destroy(R);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -485,6 +493,9 @@ int check_rel_model(fmhip_model_t m, fmhip_relational_t R);           // device 
 // one relational step of batch b, asynchronous on the model's stream; acc (nullable): the epoch's fp64 accumulators.  pairs (the
 // BPR trainer): rows 2p / 2p+1 are one example — the finish leaves Q_r and yhat_r, launch_pair_finish forms the residuals
 int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs = false);
+// the beginning of a step alone (the BPR trainer's adaptive sampler reads what it leaves): scales folded, workspace sized, every
+// block's kFwdQ forward into its relation's Q / yq, asynchronous on the model's stream
+int rel_block_forwards(fmhip_model_t m, fmhip_relational_t R);
 // ---- fmhip_score.hip: fmhip_pair_logloss over the rows of a relational dataset without a plain part (the caller holds the model's lock shared)
 int rel_pair_score(fmhip_model_t m, fmhip_relational_t R, double *logloss, double *concordance, fmhip_stats *stats);
 // the four leading numbers of a statistics block {sum e, sum e^2, rows, rows with a non-finite prediction} (the packed gradient's

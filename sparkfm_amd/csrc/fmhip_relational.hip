@@ -83,6 +83,20 @@ int check_rel_model(fmhip_model_t m, fmhip_relational_t R) {
     return set_device(m->device);
 }
 
+// what a step begins with, on its own: the scales folded, the handle's workspace sized, then every block's kFwdQ forward into the
+// relation's Q / yq on the model's stream (behind the last step that used the workspace)
+int rel_block_forwards(fmhip_model_t m, fmhip_relational_t R) {
+    TRY(fold_scales(m));
+    TRY(ensure_rel_workspace(m, R));
+    if (R->busy_set && R->busy_stream != m->stream) HIP_TRY(hipStreamWaitEvent(m->stream, R->busy, 0));
+    for (auto &relp : R->rels) {
+        fmhip_relational::Relation &rel = *relp;
+        const FwdArgs a = fwd_args_out(m, rel.block, rel.block->batches[0], rel.Q.p, nullptr, nullptr, rel.yq.p, kLossSquared);
+        HIP_TRY(launch_forward(m->Kp, kFwdQ, a, m->stream, nullptr));
+    }
+    return FMHIP_OK;
+}
+
 // one relational step of batch b, asynchronous on the model's stream; acc (nullable): the epoch's fp64 accumulators
 int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs) {
     const fmhip_relational::Batch &B = R->batches[(size_t)b];

@@ -124,11 +124,14 @@ FMHIP_RNG_FN bool row_listed(const int32_t *list, int32_t len, int32_t c) {
 // rejection: attempt a = 0 .. 63 takes word a & 3 of the block of counter (p, a >> 2, t, kStreamNegative), c = (word * M) >> 32,
 // accepted if c is not listed.  All 64 rejected: from the last c on, c = (c + 1) mod M until c is not listed (at most len steps);
 // *forced = 1.  *attempts: the attempts made (1 .. 64).  Integer arithmetic only: host and device agree bit for bit.
-FMHIP_RNG_FN int32_t negative_row(uint64_t seed, uint32_t p, uint32_t t, uint32_t M, const int32_t *list, int32_t len, int *attempts, int *forced) {
+// group0 is added to the counter's group word: candidate c of the adaptive sampler (include/fmhip_bpr_adaptive.h) draws with
+// group0 = c << 4, so its 16 blocks are its own and candidate 0 is the uniform sampler's draw.
+FMHIP_RNG_FN int32_t negative_row(uint64_t seed, uint32_t p, uint32_t t, uint32_t M, const int32_t *list, int32_t len, int *attempts, int *forced,
+                                  uint32_t group0 = 0) {
     int32_t c = 0;
     Block b{};
     for (int a = 0; a < kNegMaxAttempts; ++a) {
-        if ((a & 3) == 0) b = block_of(seed, p, (uint32_t)(a >> 2), t, kStreamNegative);
+        if ((a & 3) == 0) b = block_of(seed, p, group0 | (uint32_t)(a >> 2), t, kStreamNegative);
         c = (int32_t)(((uint64_t)b.x[a & 3] * M) >> 32);
         if (!row_listed(list, len, c)) {
             *attempts = a + 1;
