@@ -49,14 +49,11 @@ struct McmcDev {
 };
 
 // ... and what a handle with attribute groups (include/fmhip_mcmc_groups.h, G = n_groups > 1) takes in McmcDev's place — a type of
-// its own, so that the instantiations the ALS epoch and an ungrouped handle run keep their arguments and their code:
+// its own, so that the instantiations the ALS epoch and an ungrouped handle run keep their arguments and their code; z, sample and
+// zi are McmcDev's, so what does not depend on the groups (the noise, the bias step) takes it as one:
 // hyp = {alpha, lambda[(k + 1) * G], mu[(k + 1) * G]}, [g * G + a]; group[i] = feature i's attribute group, num_attribute + 1
 // entries (the walks read a column's id a step ahead of the test that skips quirk Q1's slot)
-struct McmcGroupDev {
-    const double *hyp;
-    const double *z;
-    int32_t sample;
-    int64_t zi;
+struct McmcGroupDev : McmcDev {
     const int32_t *group;
     int32_t n_groups;
 };
@@ -89,34 +86,40 @@ constexpr int kAlsMaxParts = 512;       // workgroups of a chip-wide column step
 // (FMHIP_ALS_LONG in the environment overrides it: a test / measurement knob)
 constexpr int kAlsLongColumn = 8192;
 
-// h_cfeat / h_cptr: HOST copies of cfeat / cptr (the sweep's launch plan follows the column lengths)
-// h_lev_ptr / n_levels: the level schedule's offsets into a.lev_cols (NULL / 0: none); h_lev_cols: host copy of a.lev_cols.  Taken when the levels hold at least
-// 16 columns on average (FMHIP_ALS_LEVELS=0 / 1 in the environment: never / always — a test and measurement knob).
-hipError_t launch_als_epoch(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
-                            const int32_t *h_lev_cols, int n_levels, hipStream_t s);
+// A dataset's compressed columns as the HOST sees them — what a walk's launch plan follows (fmhip_api.hip: als_plan makes it from
+// a dataset): copies of cfeat / cptr, and the level schedule's offsets into a.lev_cols (NULL / 0: none) with a copy of a.lev_cols.
+// The levels are taken when they hold at least 16 columns on average (FMHIP_ALS_LEVELS=0 / 1 in the environment: never / always —
+// a test and measurement knob).
+struct ColumnPlan {
+    const int32_t *h_cfeat, *h_cptr, *h_lev_ptr, *h_lev_cols;
+    int32_t n_levels;
+};
+
+hipError_t launch_als_epoch(const AlsArgs &a, const ColumnPlan &plan, hipStream_t s);
 
 // ---- the MCMC epoch: the ALS column walk with the Gaussian conditional's draw in computeTheta's place --------------------
 constexpr int kMcmcSumParts = 64;       // workgroups (= partial sums the host adds in order) per reduced quantity
-// The launches in front of the epoch's one host sync: the epoch's noise into z (= m.z; m.sample only; counter (id, group, t, stream)
-// under `seed`), the residuals e = yhat - y, and the sums the hyper-parameter draws need — sums[2 * (q * kMcmcSumParts + c)], + 1:
-// quantity q = 0 {sum e^2, -}, q = 1 + g {sum theta, sum (theta - m.hyp's mu_g)^2} over group g's trained parameters
-// probit (nullable): the residual pass is k_mcmc_probit_targets' — a.y must be probit->ystar — with counter (row, attempt, t, 5)
+// The epoch's noise of a's columns into z [(k + 1) * a.n_cols + 1] (a.n_cols = 0: the bias's alone); counter (id, group, t, stream)
+// under `seed`
+hipError_t launch_mcmc_noise(const AlsArgs &a, double *z, uint64_t seed, uint32_t t, hipStream_t s);
+// The launches in front of the epoch's one host sync: the noise (m.sample only; z = m.z), the residuals e = yhat - y, and the sums
+// the hyper-parameter draws need — sums[2 * (q * kMcmcSumParts + c)], + 1: quantity q = 0 {sum e^2, -}, q = 1 + g {sum theta,
+// sum (theta - m.hyp's mu_g)^2} over group g's trained parameters.
+// probit (nullable): the residual pass is k_mcmc_probit_targets' — a.y must be probit->ystar — with counter (row, attempt, t, 5).
+// groups (nullable): a handle with attribute groups — m IS its McmcGroupDev; sums[] holds quantity 0 only and the groups' sums are
+// k_mcmc_group_sums' (a workgroup per chunk of the plan, every partial reduced in a fixed order, no atomics), which the host adds
+// in chunk order.
 hipError_t launch_mcmc_begin(const AlsArgs &a, const McmcDev &m, double *z, uint64_t seed, uint32_t t, double *sums, hipStream_t s,
-                             const McmcProbit *probit = nullptr);
+                             const McmcProbit *probit = nullptr, const McmcGroupSums *groups = nullptr);
 // ... and behind it, with the new m.hyp on the device: the bias draw, the residuals again, q, the sweeps — launch_als_epoch's
-// plan (the same environment knobs), every step a draw
-hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
-                              const int32_t *h_lev_cols, int n_levels, hipStream_t s);
-// The same two for a handle with attribute groups.  Begin: sums[] holds quantity 0 only (kMcmcSumParts pairs); the groups' sums are
-// k_mcmc_group_sums' — a workgroup per chunk of the plan, every partial reduced in a fixed order, no atomics — which the host adds
-// in chunk order.  Sweeps: every step looks its lambda and mu up by the column's group.
-hipError_t launch_mcmc_group_begin(const AlsArgs &a, const McmcGroupDev &m, const McmcGroupSums &plan, double *z, uint64_t seed, uint32_t t, double *sums,
-                                   hipStream_t s, const McmcProbit *probit = nullptr);
-hipError_t launch_mcmc_group_sweeps(const AlsArgs &a, const McmcGroupDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
-                                    const int32_t *h_lev_cols, int n_levels, hipStream_t s);
-// The test rows' predictions under the parameters t.w0 / t.w / t.v into t.e (the last draw's), and sum[r] += t.e[r]: t holds the
-// test set's k, n_rows, row_ptr, col, val and, as y, n_rows zeros (k_als_residual's e = yhat - 0 is the prediction exactly).
-// link: what the prediction becomes first, in t.e too (kLinkNone: the launch this always was)
+// plan (the same environment knobs), every step a draw; with attribute groups every step looks its lambda and mu up by the
+// column's group
+hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcDev &m, const ColumnPlan &plan, hipStream_t s);
+hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcGroupDev &m, const ColumnPlan &plan, hipStream_t s);
+// last <- link(last), sum += last.  link: what a draw's test prediction becomes first (kLinkNone: itself)
+hipError_t launch_mcmc_accumulate_link(double *last, double *sum, int64_t n_rows, const McmcLink &link, hipStream_t s);
+// The test rows' predictions under the parameters t.w0 / t.w / t.v into t.e (the last draw's), then the call above over t.e: t
+// holds the test set's k, n_rows, row_ptr, col, val and, as y, n_rows zeros (k_als_residual's e = yhat - 0 is the prediction exactly).
 hipError_t launch_mcmc_accumulate(const AlsArgs &t, double *sum, hipStream_t s, const McmcLink &link = McmcLink{});
 
 }  // namespace fmhip

@@ -6,7 +6,9 @@
 // workgroup; the parallelism is inside a column (its entries are spread over the 1024 threads,
 // sums are tree-reduced in a fixed order).  All arithmetic is fp64 without fma contraction — the
 // reference runs on the JVM, which never fuses — so an epoch tracks the fp64 oracle to ~1e-13.
-// Three shapes of the sweep:
+// Four shapes of the sweep, chosen per epoch in this order (walk_choice, epoch_tail):
+//  * k_als_level — the level schedule, when the dataset has one and its levels are wide (one-hot fields): the columns of a
+//    level share no row, so they take a wave each side by side, a launch per level and parameter group.
 //  * k_als_sweep_lds — residuals e and the factor's q live in LDS (n_rows * 16 B <= 160,000 B: BASELINE config 1's
 //    10,000 rows fill it exactly); ONE wave walks the columns (a column of ~100 entries is two wave-iterations: no
 //    workgroup barrier per feature, wave sums by DPP row reductions), the next column's entries are prefetched
@@ -17,17 +19,26 @@
 //    workgroup sums its slice (sum h^2, sum e*h), the second launch adds the partials in a fixed tree (every workgroup
 //    the same bits), forms theta* and updates its slice of e and q.  The dependency between consecutive columns is the
 //    launch boundary — no device-side grid barrier to get wrong.  A column of 10^5 entries costs a CPU core ~0.2 ms per
-//    step and this path two launches.
+//    step and this path two launches.  (A level's long columns take it too, behind the level's launch.)
 // Every factor's q comes from one up-front pass over the feature-sorted rows (k_als_q_all), the per-row order of the
 // reference's transposed pass.
+// The MCMC learner (include/fmhip_mcmc.h) walks the same columns with the Gaussian conditional's draw in computeTheta's place:
+// every walk takes a parameter pack that is empty for ALS and holds the epoch's McmcDev / McmcGroupDev for MCMC, so the ALS
+// kernels keep their arguments and their code.  Its own kernels — the noise, the probit targets, the hyper-parameter sums, the
+// test rows' accumulation — sit beside the walks' in the first section.
+// The second section is the block-structure sweep over relational data (include/fmhip_mcmc_relational.h; launchers: mcmc_blocks.h):
+// the same conditional on a block's columns with the sums taken over the BLOCK's rows from per-row caches.  It shares this file's
+// anonymous-namespace device functions (the draw, the sums, the probit residual), the walk choice and — for the plain part — the
+// per-group pass.
 #include "als_kernels.h"
+#include "fm_relational.h"
+#include "mcmc_blocks.h"
 #include "mcmc_rng.h"
 
 #include <cstdlib>
 
 namespace fmhip {
 namespace {
-
 
 // S/fm/lib/ALS.scala:190-192
 __device__ __forceinline__ bool is_updatable(double nv, double ov) { return !isnan(nv) && !isinf(nv) && nv != ov; }
@@ -92,21 +103,17 @@ __device__ __forceinline__ DrawMcmcGroups group_draw(const AlsArgs &a, int g, do
 }
 
 // the noise of entry idx of m.z (k_mcmc_noise filled it before the epoch's first dependent launch); of a long column's own step
+// (a McmcGroupDev is a McmcDev here and in the bias step)
 __device__ __forceinline__ double noise_at(int64_t) { return 0.0; }
 __device__ __forceinline__ double noise_at(int64_t idx, const McmcDev &m) { return m.z[idx]; }
-__device__ __forceinline__ double noise_at(int64_t idx, const McmcGroupDev &m) { return m.z[idx]; }
 __device__ __forceinline__ double noise_own() { return 0.0; }
 __device__ __forceinline__ double noise_own(const McmcDev &m) { return m.z[m.zi]; }
-__device__ __forceinline__ double noise_own(const McmcGroupDev &m) { return m.z[m.zi]; }
 
 // the bias step: computeTheta(w0, reg0, sum e, size) / the conditional with h = 1, lambda = reg0, mu = 0 (its noise sits behind
-// the coordinates')
+// the coordinates'; the bias has no group: alpha is hyp[0] in both layouts)
 __device__ __forceinline__ double bias_step(const AlsArgs &a, double w0, double se) { return compute_theta(w0, a.reg0, se, (double)a.n_rows); }
 __device__ __forceinline__ double bias_step(const AlsArgs &a, double w0, double se, const McmcDev &m) {
     return DrawMcmc{m.hyp[0], a.reg0, 0.0, m.sample != 0}(w0, se, (double)a.n_rows, m.z[(int64_t)(a.k + 1) * a.n_cols]);
-}
-__device__ __forceinline__ double bias_step(const AlsArgs &a, double w0, double se, const McmcGroupDev &m) {
-    return bias_step(a, w0, se, McmcDev{m.hyp, m.z, m.sample, m.zi});      // (the bias has no group: alpha is hyp[0] in both layouts)
 }
 
 // FMModel.predict's exact order of operations (S/fm/FMModel.scala:34-63) for row r: sequential sums in stored order
@@ -144,20 +151,23 @@ __global__ __launch_bounds__(256) void k_als_residual(AlsArgs a) {
 // s = +1 / -1 is that of the label's class [y > 0].  p.mode kProbitStart (the handle's first epoch): y* = s; kProbitSample:
 // y* = yhat + s z, z the row's own truncated normal (z > -s yhat; counter (row, attempt, t, kStreamTarget): no schedule enters it);
 // kProbitMean: z is that draw's expectation.  A wave waits for the lane with the most attempts — 64 at the most, by construction.
+// probit_residual: row r's target around the forward yhat into p.ystar -> its residual (the block sweep's combine calls it too)
+__device__ __forceinline__ double probit_residual(const McmcProbit &p, int64_t r, double yhat, uint64_t seed, uint32_t t) {
+#pragma clang fp contract(off)
+    const double s = p.labels[r] > 0.0 ? 1.0 : -1.0;
+    double target = s;
+    if (p.mode != kProbitStart) {
+        const double lo = -s * yhat;
+        const double z = p.mode == kProbitSample ? rng::truncated_normal(seed, (uint32_t)r, t, lo, nullptr) : rng::truncated_normal_mean(lo);
+        target = yhat + s * z;
+    }
+    p.ystar[r] = target;
+    return yhat - target;
+}
+
 __global__ __launch_bounds__(256) void k_mcmc_probit_targets(AlsArgs a, McmcProbit p, uint64_t seed, uint32_t t) {
 #pragma clang fp contract(off)
-    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < a.n_rows; r += (int64_t)gridDim.x * 256) {
-        const double yhat = row_predict(a, r);
-        const double s = p.labels[r] > 0.0 ? 1.0 : -1.0;
-        double target = s;
-        if (p.mode != kProbitStart) {
-            const double lo = -s * yhat;
-            const double z = p.mode == kProbitSample ? rng::truncated_normal(seed, (uint32_t)r, t, lo, nullptr) : rng::truncated_normal_mean(lo);
-            target = yhat + s * z;
-        }
-        p.ystar[r] = target;
-        a.e[r] = yhat - target;
-    }
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < a.n_rows; r += (int64_t)gridDim.x * 256) a.e[r] = probit_residual(p, r, row_predict(a, r), seed, t);
 }
 
 // The MCMC learner's averaged prediction.  The test rows' predictions under the draw the epoch left are k_als_residual's own —
@@ -223,6 +233,23 @@ __global__ __launch_bounds__(256) void k_mcmc_noise(AlsArgs a, double *z, uint64
 // out[2 * (quantity * P + chunk)], + 1 — the host adds a quantity's P partials in order.  All groups at epoch start: nothing
 // writes w, or column f of V, before that group's own sweep (the argument that lets k_als_q_all run up front).
 constexpr int kSumsBlock = 256;
+
+// this thread's share of {sum theta, sum (theta - mu)^2} of parameter group g over chunk `chunk` of P of the column slots: the
+// slots lo + tid, lo + tid + kSumsBlock, ... that trained(s) keeps
+template <class Trained>
+__device__ __forceinline__ void theta_sums(const AlsArgs &a, int g, double mu, int chunk, int P, int tid, Trained trained, double &s0, double &s1) {
+#pragma clang fp contract(off)
+    const int64_t lo = (int64_t)a.n_cols * chunk / P, hi = (int64_t)a.n_cols * (chunk + 1) / P;
+    for (int64_t s = lo + tid; s < hi; s += kSumsBlock) {
+        if (!trained(s)) continue;
+        const int64_t i = a.cfeat[s];
+        const double th = g == 0 ? a.w[i] : a.v[(g - 1) + i * a.k];
+        const double d = th - mu;
+        s0 += th;
+        s1 += d * d;
+    }
+}
+
 __global__ __launch_bounds__(kSumsBlock) void k_mcmc_sums(AlsArgs a, McmcDev m, double *out, int P) {
 #pragma clang fp contract(off)
     __shared__ double sh[2][kSumsBlock / 64];
@@ -235,17 +262,8 @@ __global__ __launch_bounds__(kSumsBlock) void k_mcmc_sums(AlsArgs a, McmcDev m, 
             s0 += e * e;
         }
     } else {
-        const int g = quantity - 1;
-        const double mu = m.hyp[2 + a.k + g];
-        const int64_t lo = (int64_t)a.n_cols * chunk / P, hi = (int64_t)a.n_cols * (chunk + 1) / P;
-        for (int64_t s = lo + tid; s < hi; s += kSumsBlock) {
-            const int64_t i = a.cfeat[s];
-            if (i >= a.num_attribute) continue;                    // quirk Q1: slot n is never trained
-            const double th = g == 0 ? a.w[i] : a.v[(g - 1) + i * a.k];
-            const double d = th - mu;
-            s0 += th;
-            s1 += d * d;
-        }
+        const int g = quantity - 1;                                // (quirk Q1: slot n is never trained)
+        theta_sums(a, g, m.hyp[2 + a.k + g], chunk, P, tid, [&](int64_t s) { return a.cfeat[s] < a.num_attribute; }, s0, s1);
     }
     block_sum2<kSumsBlock>(s0, s1, sh);
     if (tid == 0) {
@@ -637,9 +655,7 @@ __global__ __launch_bounds__(kLdsSweepThreads) void k_als_sweep_lds(AlsArgs a, c
     }
 }
 
-}  // namespace
-
-namespace {
+// ---- the launch plan ----------------------------------------------------------------------------------------
 
 // one chip-wide closed-form step of a long column (two launches; see k_als_col_sums)
 template <class Dev>
@@ -654,55 +670,92 @@ void long_column_step(const AlsArgs &a, double *q, int c0, int c1, int64_t i, in
     int G = (c1 - c0 + 2047) / 2048;
     if (G > kAlsMaxParts) G = kAlsMaxParts;
     const int64_t zi = (int64_t)(FACTOR ? 1 + f : 0) * a.n_cols + slot;
-    (void)zi;
     hipLaunchKernelGGL((k_als_col_sums<FACTOR>), dim3((unsigned)G), dim3(kColBlock), 0, s, a, q, c0, c1, i, f);
     hipLaunchKernelGGL((k_als_col_update<FACTOR, M...>), dim3((unsigned)G), dim3(kColBlock), 0, s, a, q, c0, c1, i, f, own_noise(m, zi)...);
 }
 
+// How a dataset's columns are walked, decided once per launch_* call from the host's view of them and the two environment knobs:
+// columns of at least long_col entries take the chip-wide step (FMHIP_ALS_LONG overrides kAlsLongColumn); `levels`: the level
+// schedule — a launch per level and pass, every column of the level on a wave of its own — pays when the levels are wide (one-hot
+// fields: two levels of thousands of columns), while a dense conflict graph (config 1: every column shares rows with most others)
+// has about as many levels as columns and keeps the sequential walks (FMHIP_ALS_LEVELS=0 / 1: never / always);
+// wide_wg: the sequential walk's workgroup has 1024 threads, not 256 (a barrier over 4 waves is ~3x cheaper than over 16), when
+// the columns it walks average at least 512 entries.  The two walks take that mean differently and both rules are kept as they
+// were measured: the flat walk over its SHORT columns only (the long ones leave it for the chip-wide step), the block walk over
+// all of the block's columns (it walks every one of them itself).
+struct WalkChoice {
+    int long_col;
+    bool levels, wide_wg;
+};
+
+WalkChoice walk_choice(const AlsArgs &a, const ColumnPlan &plan, bool block_walk) {
+    WalkChoice c{kAlsLongColumn, false, false};
+    if (const char *ev = getenv("FMHIP_ALS_LONG")) c.long_col = atoi(ev) > 0 ? atoi(ev) : c.long_col;
+    const bool have = plan.h_lev_ptr && plan.h_lev_cols && a.lev_cols && plan.n_levels > 0;
+    c.levels = have && (int64_t)plan.n_levels * 16 <= a.n_cols;
+    if (const char *ev = getenv("FMHIP_ALS_LEVELS")) c.levels = have && atoi(ev) != 0;
+    if (c.levels || a.n_cols < 1) return c;
+    if (block_walk) {
+        c.wide_wg = (int64_t)plan.h_cptr[a.n_cols] / a.n_cols >= 512;
+    } else {
+        int64_t short_nnz = 0, n_short = 0;
+        for (int col = 0; col < a.n_cols; ++col) {
+            const int len = plan.h_cptr[col + 1] - plan.h_cptr[col];
+            if (len < c.long_col) { short_nnz += len; ++n_short; }
+        }
+        c.wide_wg = n_short > 0 && short_nnz / n_short >= 512;
+    }
+    return c;
+}
+
+// e and q in global memory, following the column lengths: a run of short columns is one launch of one workgroup, a long column two
+// chip-wide launches
 template <bool FACTOR, class... M>
-hipError_t sweep_pass(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, int f, int long_col, bool wide_wg, hipStream_t s, const M &...m) {
+hipError_t sweep_pass(const AlsArgs &a, const ColumnPlan &plan, const WalkChoice &c, int f, hipStream_t s, const M &...m) {
+    const int32_t *h_cfeat = plan.h_cfeat, *h_cptr = plan.h_cptr;
     double *q = a.q + (FACTOR ? (int64_t)f * a.n_rows : 0);
     int s0 = 0;
     while (s0 < a.n_cols) {
         const int len = h_cptr[s0 + 1] - h_cptr[s0];
-        if (len >= long_col) {
+        if (len >= c.long_col) {
             if (h_cfeat[s0] < a.num_attribute) long_column_step<FACTOR>(a, q, h_cptr[s0], h_cptr[s0 + 1], (int64_t)h_cfeat[s0], f, s0, s, m...);
             ++s0;
             continue;
         }
         int s1 = s0 + 1;
-        while (s1 < a.n_cols && h_cptr[s1 + 1] - h_cptr[s1] < long_col) ++s1;
-        if (wide_wg) hipLaunchKernelGGL((k_als_cols_wg<1024, FACTOR, M...>), dim3(1), dim3(1024), 0, s, a, q, s0, s1, f, m...);
+        while (s1 < a.n_cols && h_cptr[s1 + 1] - h_cptr[s1] < c.long_col) ++s1;
+        if (c.wide_wg) hipLaunchKernelGGL((k_als_cols_wg<1024, FACTOR, M...>), dim3(1), dim3(1024), 0, s, a, q, s0, s1, f, m...);
         else hipLaunchKernelGGL((k_als_cols_wg<256, FACTOR, M...>), dim3(1), dim3(256), 0, s, a, q, s0, s1, f, m...);
         s0 = s1;
     }
     return hipGetLastError();
 }
 
-}  // namespace
-
-namespace {
 template <bool FACTOR, class... M>
-hipError_t level_pass(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr, const int32_t *h_lev_cols,
-                      int n_levels, int f, int long_col, hipStream_t s, const M &...m) {
+hipError_t level_pass(const AlsArgs &a, const ColumnPlan &plan, const WalkChoice &c, int f, hipStream_t s, const M &...m) {
+    const int32_t *h_cfeat = plan.h_cfeat, *h_cptr = plan.h_cptr, *h_lev_ptr = plan.h_lev_ptr;
     double *q = a.q + (FACTOR ? (int64_t)f * a.n_rows : 0);
-    for (int l = 0; l < n_levels; ++l) {
+    for (int l = 0; l < plan.n_levels; ++l) {
         const int n = h_lev_ptr[l + 1] - h_lev_ptr[l];
         if (n < 1) continue;
         hipLaunchKernelGGL((k_als_level<FACTOR, M...>), dim3((unsigned)((n + kLevelBlock / 64 - 1) / (kLevelBlock / 64))), dim3(kLevelBlock), 0, s, a, q,
-                           a.lev_cols + h_lev_ptr[l], n, f, long_col, m...);
+                           a.lev_cols + h_lev_ptr[l], n, f, c.long_col, m...);
         // the level's long columns share no row with its other columns either: their chip-wide steps follow, in any order
         for (int j = h_lev_ptr[l]; j < h_lev_ptr[l + 1]; ++j) {
-            const int c = h_lev_cols[j];
-            if (h_cptr[c + 1] - h_cptr[c] >= long_col && h_cfeat[c] < a.num_attribute)
-                long_column_step<FACTOR>(a, q, h_cptr[c], h_cptr[c + 1], (int64_t)h_cfeat[c], f, c, s, m...);
+            const int col = plan.h_lev_cols[j];
+            if (h_cptr[col + 1] - h_cptr[col] >= c.long_col && h_cfeat[col] < a.num_attribute)
+                long_column_step<FACTOR>(a, q, h_cptr[col], h_cptr[col + 1], (int64_t)h_cfeat[col], f, col, s, m...);
         }
     }
     return hipGetLastError();
 }
-}  // namespace
 
-namespace {
+// The pass of ONE parameter group (0: w; 1 + f: factor f) over e and q in global memory: the level walk or the sweep walk
+template <class... M>
+hipError_t group_pass(const AlsArgs &a, int g, const ColumnPlan &plan, const WalkChoice &c, hipStream_t s, const M &...m) {
+    if (c.levels) return g == 0 ? level_pass<false>(a, plan, c, 0, s, m...) : level_pass<true>(a, plan, c, g - 1, s, m...);
+    return g == 0 ? sweep_pass<false>(a, plan, c, 0, s, m...) : sweep_pass<true>(a, plan, c, g - 1, s, m...);
+}
 
 unsigned row_blocks(int64_t n_rows) {
     int64_t blocks = (n_rows + 255) / 256;
@@ -713,8 +766,7 @@ unsigned row_blocks(int64_t n_rows) {
 // Everything of an epoch behind its first residual pass (which the caller has launched): the bias step, the residuals
 // again, every factor's q, the sweeps.  With an McmcDev every closed-form step is the Gaussian conditional's draw.
 template <class... M>
-hipError_t epoch_tail(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
-                      const int32_t *h_lev_cols, int n_levels, hipStream_t s, const M &...m) {
+hipError_t epoch_tail(const AlsArgs &a, const ColumnPlan &plan, hipStream_t s, const M &...m) {
     const unsigned blocks = row_blocks(a.n_rows);
     // precomputeTermE (:17) with the old bias feeds the bias step (:19-27); the residuals the sweeps start from are
     // evaluated after `fm.w0 = w0` (see k_als_w0)
@@ -726,121 +778,76 @@ hipError_t epoch_tail(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h
     if (qb > 4096) qb = 4096;
     hipLaunchKernelGGL(k_als_q_all, dim3((unsigned)(qb < 1 ? 1 : qb)), dim3(256), 0, s, a, a.q);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    int long_col = kAlsLongColumn;
-    if (const char *ev = getenv("FMHIP_ALS_LONG")) long_col = atoi(ev) > 0 ? atoi(ev) : long_col;
-    {
-        // level schedule: a launch per level and pass, every column of the level on a wave of its own — pays when the
-        // levels are wide (one-hot fields: two levels of thousands of columns); a dense conflict graph (config 1: every
-        // column shares rows with most others) has about as many levels as columns and keeps the sequential walks below.
-        // A level's columns long enough for the chip-wide step take it, behind the level's launch.
-        const bool have = h_lev_ptr && h_lev_cols && a.lev_cols && n_levels > 0;
-        bool levels = have && (int64_t)n_levels * 16 <= a.n_cols;
-        if (const char *ev = getenv("FMHIP_ALS_LEVELS")) levels = have && atoi(ev) != 0;
-        if (levels) {
-            if ((e = level_pass<false>(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, 0, long_col, s, m...)) != hipSuccess) return e;
-            for (int f = 0; f < a.k; ++f)
-                if ((e = level_pass<true>(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, f, long_col, s, m...)) != hipSuccess) return e;
-            return hipSuccess;
-        }
-    }
-    if ((size_t)a.n_rows * 2 * sizeof(double) <= kAlsLdsBytes && !getenv("FMHIP_ALS_NO_LDS")) {
+    const WalkChoice c = walk_choice(a, plan, false);
+    if (!c.levels && (size_t)a.n_rows * 2 * sizeof(double) <= kAlsLdsBytes && !getenv("FMHIP_ALS_NO_LDS")) {
         // e and q fit the LDS of one CU: the one-wave column walk
         e = hipFuncSetAttribute((const void *)k_als_sweep_lds<M...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAlsLdsBytes);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_als_sweep_lds<M...>, dim3(1), dim3(kLdsSweepThreads), (size_t)a.n_rows * 2 * sizeof(double), s, a, a.q, m...);
         return hipGetLastError();
     }
-    // e and q in global memory: one pass per parameter group following the column lengths — a run of short columns is one
-    // launch of one workgroup, a long column two chip-wide launches
-    // the short columns' mean length decides their workgroup size (a barrier over 4 waves is ~3x cheaper than over 16)
-    int64_t short_nnz = 0, n_short = 0;
-    for (int c = 0; c < a.n_cols; ++c) {
-        const int len = h_cptr[c + 1] - h_cptr[c];
-        if (len < long_col) { short_nnz += len; ++n_short; }
-    }
-    const bool wide_wg = n_short > 0 && short_nnz / n_short >= 512;
-    if ((e = sweep_pass<false>(a, h_cfeat, h_cptr, 0, long_col, wide_wg, s, m...)) != hipSuccess) return e;
-    for (int f = 0; f < a.k; ++f)
-        if ((e = sweep_pass<true>(a, h_cfeat, h_cptr, f, long_col, wide_wg, s, m...)) != hipSuccess) return e;
+    for (int g = 0; g <= a.k; ++g)
+        if ((e = group_pass(a, g, plan, c, s, m...)) != hipSuccess) return e;
     return hipSuccess;
 }
 
 }  // namespace
 
-hipError_t launch_als_epoch(const AlsArgs &a, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
-                            const int32_t *h_lev_cols, int n_levels, hipStream_t s) {
+hipError_t launch_als_epoch(const AlsArgs &a, const ColumnPlan &plan, hipStream_t s) {
     hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a);
-    return epoch_tail(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, s);
+    return epoch_tail(a, plan, s);
+}
+
+hipError_t launch_mcmc_noise(const AlsArgs &a, double *z, uint64_t seed, uint32_t t, hipStream_t s) {
+    int64_t nb = ((int64_t)(a.k + 1) * a.n_cols + 1 + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    hipLaunchKernelGGL(k_mcmc_noise, dim3((unsigned)nb), dim3(256), 0, s, a, z, seed, t);
+    return hipGetLastError();
 }
 
 hipError_t launch_mcmc_begin(const AlsArgs &a, const McmcDev &m, double *z, uint64_t seed, uint32_t t, double *sums, hipStream_t s,
-                             const McmcProbit *probit) {
+                             const McmcProbit *probit, const McmcGroupSums *groups) {
     if (m.sample) {
-        int64_t nb = ((int64_t)(a.k + 1) * a.n_cols + 1 + 255) / 256;
-        if (nb > 4096) nb = 4096;
-        hipLaunchKernelGGL(k_mcmc_noise, dim3((unsigned)nb), dim3(256), 0, s, a, z, seed, t);
+        const hipError_t e = launch_mcmc_noise(a, z, seed, t, s);
+        if (e != hipSuccess) return e;
     }
     if (probit)
         hipLaunchKernelGGL(k_mcmc_probit_targets, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a, *probit, seed, t);
     else
         hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_mcmc_sums, dim3((unsigned)((a.k + 2) * kMcmcSumParts)), dim3(kSumsBlock), 0, s, a, m, sums, kMcmcSumParts);
+    // with groups quantity 0 (sum e^2) stays where it is: k_mcmc_sums' first kMcmcSumParts workgroups, which read nothing of the state
+    hipLaunchKernelGGL(k_mcmc_sums, dim3((unsigned)((groups ? 1 : a.k + 2) * kMcmcSumParts)), dim3(kSumsBlock), 0, s, a, m, sums, kMcmcSumParts);
+    if (groups && m.sample && groups->n_chunks > 0)
+        hipLaunchKernelGGL(k_mcmc_group_sums, dim3((unsigned)groups->n_chunks), dim3(kGroupSumsBlock), 0, s, a, static_cast<const McmcGroupDev &>(m), *groups);
     return hipGetLastError();
 }
 
-hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
-                              const int32_t *h_lev_cols, int n_levels, hipStream_t s) {
-    return epoch_tail(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, s, m);
-}
+hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcDev &m, const ColumnPlan &plan, hipStream_t s) { return epoch_tail(a, plan, s, m); }
+hipError_t launch_mcmc_sweeps(const AlsArgs &a, const McmcGroupDev &m, const ColumnPlan &plan, hipStream_t s) { return epoch_tail(a, plan, s, m); }
 
-hipError_t launch_mcmc_group_begin(const AlsArgs &a, const McmcGroupDev &m, const McmcGroupSums &plan, double *z, uint64_t seed, uint32_t t, double *sums,
-                                   hipStream_t s, const McmcProbit *probit) {
-    const McmcDev flat{m.hyp, m.z, m.sample, m.zi};
-    if (m.sample) {
-        int64_t nb = ((int64_t)(a.k + 1) * a.n_cols + 1 + 255) / 256;
-        if (nb > 4096) nb = 4096;
-        hipLaunchKernelGGL(k_mcmc_noise, dim3((unsigned)nb), dim3(256), 0, s, a, z, seed, t);
-    }
-    if (probit)
-        hipLaunchKernelGGL(k_mcmc_probit_targets, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a, *probit, seed, t);
+hipError_t launch_mcmc_accumulate_link(double *last, double *sum, int64_t n_rows, const McmcLink &link, hipStream_t s) {
+    if (n_rows < 1) return hipSuccess;
+    const dim3 grid(row_blocks(n_rows)), block(256);
+    if (link.kind == kLinkProbit)
+        hipLaunchKernelGGL(k_mcmc_accumulate_link<LinkProbit>, grid, block, 0, s, last, sum, n_rows, LinkProbit{});
+    else if (link.kind == kLinkClamp)
+        hipLaunchKernelGGL(k_mcmc_accumulate_link<LinkClamp>, grid, block, 0, s, last, sum, n_rows, LinkClamp{link.lo, link.hi});
     else
-        hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(a.n_rows)), dim3(256), 0, s, a);
-    // quantity 0 (sum e^2) stays where it is: k_mcmc_sums' first kMcmcSumParts workgroups, which read nothing of the state
-    hipLaunchKernelGGL(k_mcmc_sums, dim3((unsigned)kMcmcSumParts), dim3(kSumsBlock), 0, s, a, flat, sums, kMcmcSumParts);
-    if (m.sample && plan.n_chunks > 0)
-        hipLaunchKernelGGL(k_mcmc_group_sums, dim3((unsigned)plan.n_chunks), dim3(kGroupSumsBlock), 0, s, a, m, plan);
+        hipLaunchKernelGGL(k_mcmc_accumulate, grid, block, 0, s, last, sum, n_rows);
     return hipGetLastError();
-}
-
-hipError_t launch_mcmc_group_sweeps(const AlsArgs &a, const McmcGroupDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
-                                    const int32_t *h_lev_cols, int n_levels, hipStream_t s) {
-    return epoch_tail(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, s, m);
 }
 
 hipError_t launch_mcmc_accumulate(const AlsArgs &t, double *sum, hipStream_t s, const McmcLink &link) {
     if (t.n_rows < 1) return hipSuccess;
     hipLaunchKernelGGL(k_als_residual, dim3(row_blocks(t.n_rows)), dim3(256), 0, s, t);
-    const dim3 grid(row_blocks(t.n_rows)), block(256);
-    if (link.kind == kLinkProbit)
-        hipLaunchKernelGGL(k_mcmc_accumulate_link<LinkProbit>, grid, block, 0, s, t.e, sum, t.n_rows, LinkProbit{});
-    else if (link.kind == kLinkClamp)
-        hipLaunchKernelGGL(k_mcmc_accumulate_link<LinkClamp>, grid, block, 0, s, t.e, sum, t.n_rows, LinkClamp{link.lo, link.hi});
-    else
-        hipLaunchKernelGGL(k_mcmc_accumulate, grid, block, 0, s, t.e, sum, t.n_rows);
-    return hipGetLastError();
+    return launch_mcmc_accumulate_link(t.e, sum, t.n_rows, link, s);
 }
-
-}  // namespace fmhip
 
 // ==== the block-structure sweep (include/fmhip_mcmc_relational.h; launchers: mcmc_blocks.h) =====================================
 // The same conditional on the same columns, with a block column's sums taken over the BLOCK's rows from per-row caches instead of
 // over the data rows that reference them.  Per part and parameter group: k_block_gather (+ _long) builds the caches by a segmented
 // sum over the handle's inverse map, k_block_level / k_block_cols_wg walk the block's columns, k_block_scatter takes the steps back
 // to e and Q_f.  Every operation's order is written down in the public header; no fused multiply-add anywhere.
-#include "mcmc_blocks.h"
-#include "fm_relational.h"
-
-namespace fmhip {
 namespace {
 
 // yhat_r, e_r and Q_f[r] of every data row from the blocks' yhat_p and q_p; PROBIT: k_mcmc_probit_targets' draw around yhat_r
@@ -865,19 +872,7 @@ __global__ __launch_bounds__(256) void k_block_combine(BlockCombine c, McmcProbi
             yhat += cross;
             if (c.Q) c.Q[f * c.n_rows + r] = run;
         }
-        if (PROBIT) {
-            const double s = p.labels[r] > 0.0 ? 1.0 : -1.0;
-            double target = s;
-            if (p.mode != kProbitStart) {
-                const double lo = -s * yhat;
-                const double z = p.mode == kProbitSample ? rng::truncated_normal(seed, (uint32_t)r, t, lo, nullptr) : rng::truncated_normal_mean(lo);
-                target = yhat + s * z;
-            }
-            p.ystar[r] = target;
-            c.e[r] = yhat - target;
-        } else {
-            c.e[r] = yhat - c.y[r];
-        }
+        c.e[r] = PROBIT ? probit_residual(p, r, yhat, seed, t) : yhat - c.y[r];
     }
 }
 
@@ -886,17 +881,8 @@ __global__ __launch_bounds__(kSumsBlock) void k_block_theta_sums(AlsArgs a, cons
 #pragma clang fp contract(off)
     __shared__ double sh[2][kSumsBlock / 64];
     const int g = (int)blockIdx.x / P, chunk = (int)blockIdx.x % P, tid = threadIdx.x;
-    const double mu = hyp[2 + a.k + g];
-    const int64_t lo = (int64_t)a.n_cols * chunk / P, hi = (int64_t)a.n_cols * (chunk + 1) / P;
     double s0 = 0.0, s1 = 0.0;
-    for (int64_t s = lo + tid; s < hi; s += kSumsBlock) {
-        if (!trained[s]) continue;
-        const int64_t i = a.cfeat[s];
-        const double th = g == 0 ? a.w[i] : a.v[(g - 1) + i * a.k];
-        const double d = th - mu;
-        s0 += th;
-        s1 += d * d;
-    }
+    theta_sums(a, g, hyp[2 + a.k + g], chunk, P, tid, [&](int64_t s) { return trained[s] != 0; }, s0, s1);
     block_sum2<kSumsBlock>(s0, s1, sh);
     if (tid == 0) {
         out[2 * (int64_t)blockIdx.x] = s0;
@@ -1069,7 +1055,7 @@ __global__ __launch_bounds__(256) void k_block_scatter(BlockPart b, double *e, d
 }
 
 template <bool FACTOR>
-hipError_t block_pass(const BlockPart &b, const BlockPlan &plan, int f, double *e, double *Q, const McmcDev &m, hipStream_t s) {
+hipError_t block_pass(const BlockPart &b, const BlockPlan &plan, const WalkChoice &c, int f, double *e, double *Q, const McmcDev &m, hipStream_t s) {
     const int n_cols = b.a.n_cols;
     double *Qf = FACTOR ? Q + (int64_t)f * b.n_rows : nullptr;
     const double *qp = FACTOR ? b.a.q + (int64_t)f * b.J : nullptr;
@@ -1077,26 +1063,20 @@ hipError_t block_pass(const BlockPart &b, const BlockPlan &plan, int f, double *
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL((k_block_gather<FACTOR>), dim3((unsigned)((b.n_work + 255) / 256)), dim3(256), 0, s, b, e, Qf, qp);
     if (b.n_long > 0) hipLaunchKernelGGL(k_block_gather_long, dim3((unsigned)((b.n_long + 255) / 256)), dim3(256), 0, s, b);
-    int long_col = kAlsLongColumn;
-    if (const char *ev = getenv("FMHIP_ALS_LONG")) long_col = atoi(ev) > 0 ? atoi(ev) : long_col;
-    const bool have = plan.h_lev_ptr && plan.h_lev_cols && b.a.lev_cols && plan.n_levels > 0;
-    bool levels = have && (int64_t)plan.n_levels * 16 <= n_cols;
-    if (const char *ev = getenv("FMHIP_ALS_LEVELS")) levels = have && atoi(ev) != 0;
-    if (levels) {
+    if (c.levels) {
         for (int l = 0; l < plan.n_levels; ++l) {
             const int n = plan.h_lev_ptr[l + 1] - plan.h_lev_ptr[l];
             if (n < 1) continue;
             hipLaunchKernelGGL((k_block_level<FACTOR>), dim3((unsigned)((n + kLevelBlock / 64 - 1) / (kLevelBlock / 64))), dim3(kLevelBlock), 0, s, b,
-                               b.a.lev_cols + plan.h_lev_ptr[l], n, f, long_col, m);
+                               b.a.lev_cols + plan.h_lev_ptr[l], n, f, c.long_col, m);
             for (int j = plan.h_lev_ptr[l]; j < plan.h_lev_ptr[l + 1]; ++j) {      // the level's long columns share no row with its others
-                const int c = plan.h_lev_cols[j];
-                if (plan.h_cptr[c + 1] - plan.h_cptr[c] >= long_col && plan.h_trained[c])
-                    hipLaunchKernelGGL((k_block_cols_wg<1024, FACTOR>), dim3(1), dim3(1024), 0, s, b, c, c + 1, f, m);
+                const int col = plan.h_lev_cols[j];
+                if (plan.h_cptr[col + 1] - plan.h_cptr[col] >= c.long_col && plan.h_trained[col])
+                    hipLaunchKernelGGL((k_block_cols_wg<1024, FACTOR>), dim3(1), dim3(1024), 0, s, b, col, col + 1, f, m);
             }
         }
     } else if (n_cols > 0) {
-        const bool wide_wg = (int64_t)plan.h_cptr[n_cols] / n_cols >= 512;
-        if (wide_wg) hipLaunchKernelGGL((k_block_cols_wg<1024, FACTOR>), dim3(1), dim3(1024), 0, s, b, 0, n_cols, f, m);
+        if (c.wide_wg) hipLaunchKernelGGL((k_block_cols_wg<1024, FACTOR>), dim3(1), dim3(1024), 0, s, b, 0, n_cols, f, m);
         else hipLaunchKernelGGL((k_block_cols_wg<256, FACTOR>), dim3(1), dim3(256), 0, s, b, 0, n_cols, f, m);
     }
     hipLaunchKernelGGL((k_block_scatter<FACTOR>), dim3(row_blocks(b.n_rows)), dim3(256), 0, s, b, e, Qf);
@@ -1104,13 +1084,6 @@ hipError_t block_pass(const BlockPart &b, const BlockPlan &plan, int f, double *
 }
 
 }  // namespace
-
-hipError_t launch_block_noise(const AlsArgs &a, double *z, uint64_t seed, uint32_t t, hipStream_t s) {
-    int64_t nb = ((int64_t)(a.k + 1) * a.n_cols + 1 + 255) / 256;
-    if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(k_mcmc_noise, dim3((unsigned)nb), dim3(256), 0, s, a, z, seed, t);
-    return hipGetLastError();
-}
 
 hipError_t launch_block_forward(const AlsArgs &a, bool with_q, hipStream_t s) {
     if (a.n_rows < 1) return hipSuccess;
@@ -1128,7 +1101,7 @@ hipError_t launch_block_combine(const BlockCombine &c, const McmcProbit *probit,
     return hipGetLastError();
 }
 
-hipError_t launch_block_sse(const AlsArgs &rows, double *sums, hipStream_t s) {
+hipError_t launch_block_sse(const AlsArgs &rows, double *sums, hipStream_t s) {      // k_mcmc_sums' quantity 0: it reads nothing of McmcDev
     hipLaunchKernelGGL(k_mcmc_sums, dim3((unsigned)kMcmcSumParts), dim3(kSumsBlock), 0, s, rows, McmcDev{}, sums, kMcmcSumParts);
     return hipGetLastError();
 }
@@ -1144,39 +1117,13 @@ hipError_t launch_block_bias(const AlsArgs &rows, const McmcDev &m, hipStream_t 
 }
 
 hipError_t launch_block_pass(const BlockPart &b, const BlockPlan &plan, int g, double *e, double *Q, const McmcDev &m, hipStream_t s) {
-    return g == 0 ? block_pass<false>(b, plan, 0, e, Q, m, s) : block_pass<true>(b, plan, g - 1, e, Q, m, s);
+    const WalkChoice c = walk_choice(b.a, plan, true);
+    return g == 0 ? block_pass<false>(b, plan, c, 0, e, Q, m, s) : block_pass<true>(b, plan, c, g - 1, e, Q, m, s);
 }
 
-hipError_t launch_plain_pass(const AlsArgs &a, int g, const McmcDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
-                             const int32_t *h_lev_cols, int n_levels, hipStream_t s) {
+hipError_t launch_plain_pass(const AlsArgs &a, int g, const McmcDev &m, const ColumnPlan &plan, hipStream_t s) {
     if (a.n_cols < 1) return hipSuccess;
-    int long_col = kAlsLongColumn;
-    if (const char *ev = getenv("FMHIP_ALS_LONG")) long_col = atoi(ev) > 0 ? atoi(ev) : long_col;
-    const bool have = h_lev_ptr && h_lev_cols && a.lev_cols && n_levels > 0;
-    bool levels = have && (int64_t)n_levels * 16 <= a.n_cols;
-    if (const char *ev = getenv("FMHIP_ALS_LEVELS")) levels = have && atoi(ev) != 0;
-    if (levels)
-        return g == 0 ? level_pass<false>(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, 0, long_col, s, m)
-                      : level_pass<true>(a, h_cfeat, h_cptr, h_lev_ptr, h_lev_cols, n_levels, g - 1, long_col, s, m);
-    int64_t short_nnz = 0, n_short = 0;
-    for (int c = 0; c < a.n_cols; ++c) {
-        const int len = h_cptr[c + 1] - h_cptr[c];
-        if (len < long_col) { short_nnz += len; ++n_short; }
-    }
-    const bool wide_wg = n_short > 0 && short_nnz / n_short >= 512;
-    return g == 0 ? sweep_pass<false>(a, h_cfeat, h_cptr, 0, long_col, wide_wg, s, m) : sweep_pass<true>(a, h_cfeat, h_cptr, g - 1, long_col, wide_wg, s, m);
-}
-
-hipError_t launch_block_accumulate(double *last, double *sum, int64_t n_rows, const McmcLink &link, hipStream_t s) {
-    if (n_rows < 1) return hipSuccess;
-    const dim3 grid(row_blocks(n_rows)), block(256);
-    if (link.kind == kLinkProbit)
-        hipLaunchKernelGGL(k_mcmc_accumulate_link<LinkProbit>, grid, block, 0, s, last, sum, n_rows, LinkProbit{});
-    else if (link.kind == kLinkClamp)
-        hipLaunchKernelGGL(k_mcmc_accumulate_link<LinkClamp>, grid, block, 0, s, last, sum, n_rows, LinkClamp{link.lo, link.hi});
-    else
-        hipLaunchKernelGGL(k_mcmc_accumulate, grid, block, 0, s, last, sum, n_rows);
-    return hipGetLastError();
+    return group_pass(a, g, plan, walk_choice(a, plan, false), s, m);
 }
 
 }  // namespace fmhip

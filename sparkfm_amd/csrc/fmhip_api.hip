@@ -138,6 +138,38 @@ int als_check(fmhip_model_t m, fmhip_dataset_t d) {
     return FMHIP_OK;
 }
 
+// the walk's arguments over dataset d with the model's fp64 device parameters: the dataset's and the parameters' fields, and the
+// chip-wide column step's partials (the model's, whatever dataset is walked); y, the regularisers, e and q are the caller's
+AlsArgs als_args(fmhip_model_t m, fmhip_dataset_t d) {
+    AlsArgs a{};
+    a.k = m->k;
+    a.num_attribute = m->n;
+    a.n_rows = d->n_rows;
+    a.nnz = d->nnz;
+    a.row_ptr = d->row_ptr.p;
+    a.col = d->col.p;
+    a.val = d->val64.p;
+    a.scol = d->scol.p;
+    a.sval = d->sval64.p;
+    a.n_cols = d->n_rows > 0 ? d->batches[0].n_cols : 0;
+    a.cfeat = d->cfeat.p;
+    a.cptr = d->cptr.p;
+    a.crow = d->crow.p;
+    a.cval = d->cval64.p;
+    a.w0 = m->als_w0.p;
+    a.w = m->als_w.p;
+    a.v = m->als_v.p;
+    a.part = m->als_part.p;
+    a.lev_cols = d->als_lev_cols.p;
+    return a;
+}
+
+// the host's view of d's columns, which the walk's launch plan follows
+ColumnPlan als_plan(fmhip_dataset_t d) {
+    const int n_levels = d->als_lev_ptr.empty() ? 0 : (int)d->als_lev_ptr.size() - 1;
+    return ColumnPlan{d->h_cfeat.data(), d->h_cptr.data(), n_levels ? d->als_lev_ptr.data() : nullptr, d->h_als_lev_cols.data(), n_levels};
+}
+
 // the fp64 masters onto the device and the walk's arguments (the workspace is the model's); *a is meaningful when d has rows
 int als_begin(fmhip_model_t m, fmhip_dataset_t d, double reg0, double regw, double regv, AlsArgs *out) {
     TRY(als_check(m, d));
@@ -162,32 +194,13 @@ int als_begin(fmhip_model_t m, fmhip_dataset_t d, double reg0, double regw, doub
     HIP_TRY(hipMemcpyAsync(m->als_v.p, m->h_v.data(), nv * sizeof(double), hipMemcpyHostToDevice, m->stream));
     AlsArgs a{};
     if (d->n_rows > 0) {
-        const BatchMeta &bm = d->batches[0];
-        a.k = m->k;
-        a.num_attribute = m->n;
-        a.n_rows = d->n_rows;
-        a.nnz = d->nnz;
-        a.row_ptr = d->row_ptr.p;
-        a.col = d->col.p;
-        a.val = d->val64.p;
-        a.scol = d->scol.p;
-        a.sval = d->sval64.p;
+        a = als_args(m, d);
         a.y = d->y64.p;
-        a.n_cols = bm.n_cols;
-        a.cfeat = d->cfeat.p;
-        a.cptr = d->cptr.p;
-        a.crow = d->crow.p;
-        a.cval = d->cval64.p;
-        a.w0 = m->als_w0.p;
-        a.w = m->als_w.p;
-        a.v = m->als_v.p;
         a.reg0 = reg0;
         a.regw = regw;
         a.regv = regv;
         a.e = m->als_e.p;
         a.q = m->als_q.p;
-        a.part = m->als_part.p;
-        a.lev_cols = d->als_lev_cols.p;
     }
     *out = a;
     return FMHIP_OK;
@@ -565,11 +578,7 @@ int fmhip_als_epoch(fmhip_model_t m, fmhip_dataset_t d, double reg0, double regw
     WriteLock lock(m);
     AlsArgs a{};
     TRY(als_begin(m, d, reg0, regw, regv, &a));
-    if (d->n_rows > 0) {
-        const int n_levels = d->als_lev_ptr.empty() ? 0 : (int)d->als_lev_ptr.size() - 1;
-        HIP_TRY(launch_als_epoch(a, d->h_cfeat.data(), d->h_cptr.data(), n_levels ? d->als_lev_ptr.data() : nullptr, d->h_als_lev_cols.data(), n_levels,
-                                 m->stream));
-    }
+    if (d->n_rows > 0) HIP_TRY(launch_als_epoch(a, als_plan(d), m->stream));
     return als_end(m);
 }
 

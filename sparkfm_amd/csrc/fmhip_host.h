@@ -216,6 +216,25 @@ double mcmc_draw_alpha(uint64_t seed, uint32_t t, const McmcPriors &p, int64_t n
 // mu ~ N((sum_theta + gamma_0 mu_0) / (m + gamma_0), 1 / ((m + gamma_0) lambda)) = mean + z / sqrt((m + gamma_0) lambda)
 void mcmc_draw_group(uint64_t seed, uint32_t t, uint32_t g, const McmcPriors &p, int64_t m, double sum_theta, double sum_dev2, double mu_old,
                      double *lambda, double *mu);
+// One epoch's hyper-parameter draws, for every kind of handle: alpha (unless probit: the link keeps what the state holds), then
+// lambda and mu of every (parameter group g < k1, attribute group a < G) at [g * G + a], stream id g + (a << 16).
+// count_of(a) = m_a; partials_of(g, a, add) calls add(sum theta, sum (theta - mu_old)^2) once per partial pair of (g, a), in the
+// order they are to be added (none: the draw from the prior).
+template <class CountOf, class PartialsOf>
+void mcmc_draw_state(uint64_t seed, uint32_t t, const McmcPriors &p, bool probit, int64_t n_rows, double sse, int k1, int G, CountOf count_of,
+                     PartialsOf partials_of, double *alpha, double *lambda, double *mu) {
+    if (!probit) *alpha = mcmc_draw_alpha(seed, t, p, n_rows, sse);
+    for (int g = 0; g < k1; ++g)
+        for (int a = 0; a < G; ++a) {
+            double sum_theta = 0.0, sum_dev2 = 0.0;
+            partials_of(g, a, [&](double theta, double dev2) {
+                sum_theta += theta;
+                sum_dev2 += dev2;
+            });
+            const size_t at = (size_t)g * (size_t)G + (size_t)a;
+            mcmc_draw_group(seed, t, (uint32_t)g + ((uint32_t)a << 16), p, count_of(a), sum_theta, sum_dev2, mu[at], &lambda[at], &mu[at]);
+        }
+}
 // ---- ... its attribute groups (include/fmhip_mcmc_groups.h) ----
 constexpr int kMcmcMaxGroups = 4096;        // FMHIP_MCMC_MAX_GROUPS
 constexpr int kMcmcGroupChunk = 512;        // column slots per chunk of k_mcmc_group_sums (a workgroup each)

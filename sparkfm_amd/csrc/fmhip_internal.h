@@ -22,6 +22,7 @@
 
 namespace fmhip {
 struct AlsArgs;     // als_kernels.h
+struct ColumnPlan;
 namespace host {
 
 // records the calling thread's error message (fmhip_last_error) and returns `code`
@@ -422,8 +423,12 @@ struct ReadLock {
 int partition_rows_locked(fmhip_dataset_t d, int64_t cut_feature);      // fmhip_dataset_partition_rows with d->part_mu held by the caller
 // ---- fmhip_api.hip: the column walk's epoch in pieces (fmhip_als_epoch; fmhip_mcmc_epoch in fmhip_mcmc.hip).  The caller holds
 // the model's lock.  als_check: every refusal of (m, d), the model untouched; als_begin: als_check, the fp64 masters onto the
-// device, the walk's arguments (meaningful when d has rows); als_end: the parameters back into the masters and the fp32 copy
+// device, the walk's arguments (meaningful when d has rows); als_end: the parameters back into the masters and the fp32 copy;
+// als_args: the dataset and parameter fields of the walk's arguments (als_begin's, before y, the regularisers, e and q);
+// als_plan: the host's view of d's columns
 int als_check(fmhip_model_t m, fmhip_dataset_t d);
+AlsArgs als_args(fmhip_model_t m, fmhip_dataset_t d);
+ColumnPlan als_plan(fmhip_dataset_t d);
 int als_begin(fmhip_model_t m, fmhip_dataset_t d, double reg0, double regw, double regv, AlsArgs *out);
 int als_end(fmhip_model_t m);
 // ---- fmhip_step.hip

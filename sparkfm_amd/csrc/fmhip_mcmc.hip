@@ -10,9 +10,11 @@
 // the test rows' accumulation takes Phi of the score (a regression handle with a clip: the clamp).
 // A handle with attribute groups (include/fmhip_mcmc_groups.h, G > 1) keeps lambda and mu as [(k + 1) x G], takes the groups' sums
 // from k_mcmc_group_sums over the plan fmhip_mcmc_set_groups made (fmhip_host.cpp: mcmc_group_plan) — added here in chunk order,
-// inside the same single sync — and walks with McmcGroupDev.  G = 1, set or not, is the sequence above, launch for launch.
+// inside the same single sync — and walks with McmcGroupDev.  G = 1, set or not, is the sequence above, launch for launch: the epoch
+// is ONE sequence over the walk's value, and its draws are fmhip_host.h's mcmc_draw_state, which the relational epoch calls too.
 // A handle over relational data (include/fmhip_mcmc_relational.h) is made and stepped in fmhip_mcmc_relational.hip; the struct both
-// share is fmhip_mcmc_handle.h's, and every call here but the epoch and set_groups serves it as it serves a flat handle.
+// share is fmhip_mcmc_handle.h's, with what the two creators and the two epochs have in common (the settings, the test buffers, the
+// flat test set's accumulation, the epoch's end), and every call here but the epoch and set_groups serves it as it serves a flat handle.
 // The kernels are in als_kernels.hip, the generator in mcmc_rng.h.
 #include "fmhip_internal.h"
 #include "fmhip_mcmc_handle.h"
@@ -37,47 +39,24 @@ int upload_state(fmhip_mcmc_t s) {
     return FMHIP_OK;
 }
 
-int check_test(fmhip_model_t m, fmhip_dataset_t test) {
-    if (test->device != m->device) return fail(FMHIP_ERR_INVALID, "model on device %d, test set on device %d", m->device, test->device);
-    if (test->dimension > m->n)
-        return fail(FMHIP_ERR_INVALID, "the test set has feature index %lld but the model has num_attribute = %lld", (long long)test->dimension,
-                    (long long)m->n);
-    if (test->batches.size() > 1 || (test->nnz > 0 && !test->val64.p))
-        return fail(FMHIP_ERR_UNSUPPORTED, "the MCMC learner predicts its test rows in fp64: create the test set with fmhip_dataset_create and "
-                                           "batch_rows <= 0 (single batch; fmhip_rows_create keeps no fp64 rows)");
-    return FMHIP_OK;
-}
-
 // fmhip_mcmc_create (task_opts NULL) and fmhip_mcmc_create_task
 int create(fmhip_model_t m, fmhip_dataset_t train, fmhip_dataset_t test, const fmhip_mcmc_opts *opts, const fmhip_mcmc_task_opts *task_opts,
            fmhip_mcmc_t *out) {
     if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
     *out = nullptr;
     fmhip_mcmc_opts o;
-    fmhip_mcmc_opts_default(&o);
-    if (opts) o = *opts;
-    const McmcPriors pri{o.alpha_0, o.beta_0, o.alpha_lambda, o.beta_lambda, o.gamma_0, o.mu_0};
-    if (const char *bad = mcmc_bad_setting(pri, o.reg0, o.init_lambda))
-        return fail(FMHIP_ERR_INVALID, "%s must be finite and > 0 (mu_0: finite; reg0: finite and >= 0)", bad);
-    fmhip_mcmc_task_opts to{FMHIP_MCMC_REGRESSION, 0, 0.0, 0.0};
-    if (task_opts) to = *task_opts;
-    if (const char *bad = mcmc_bad_task(to.task, to.clip, to.clip_lo, to.clip_hi)) return fail(FMHIP_ERR_INVALID, "%s", bad);
+    fmhip_mcmc_task_opts to;
+    TRY(mcmc_settings(opts, task_opts, &o, &to));
     if (!m || !train) return fail(FMHIP_ERR_INVALID, "model or train set is NULL");
     ReadLock lock(m);
     TRY(als_check(m, train));
-    if (test) TRY(check_test(m, test));
+    if (test) TRY(mcmc_check_test(m, test));
     fmhip_mcmc *s = new (std::nothrow) fmhip_mcmc;
     if (!s) return fail(FMHIP_ERR_NOMEM, "out of host memory");
     std::unique_ptr<fmhip_mcmc> guard(s);
-    s->m = m;
+    mcmc_fill(s, m, o, to);
     s->train = train;
     s->test = test;
-    s->opts = o;
-    s->priors = pri;
-    s->task = to.task;
-    if (to.task == FMHIP_MCMC_CLASSIFICATION) s->link.kind = kLinkProbit;
-    else if (to.clip) s->link = McmcLink{kLinkClamp, to.clip_lo, to.clip_hi};
-    s->k = m->k;
     const size_t k1 = (size_t)m->k + 1;
     s->lambda.assign(k1, o.init_lambda);
     s->mu.assign(k1, 0.0);
@@ -91,15 +70,7 @@ int create(fmhip_model_t m, fmhip_dataset_t train, fmhip_dataset_t test, const f
     TRY(s->sums.alloc(s->h_sums.size()));
     HIP_TRY(hipMemset(s->z.p, 0, nz * sizeof(double)));
     if (s->task == FMHIP_MCMC_CLASSIFICATION) TRY(s->ystar.alloc((size_t)std::max<int64_t>(train->n_rows, 1)));
-    if (test) {
-        const size_t nt = (size_t)std::max<int64_t>(test->n_rows, 1);
-        TRY(s->test_sum.alloc(nt));
-        TRY(s->test_last.alloc(nt));
-        TRY(s->test_zero.alloc(nt));
-        HIP_TRY(hipMemset(s->test_sum.p, 0, nt * sizeof(double)));
-        HIP_TRY(hipMemset(s->test_last.p, 0, nt * sizeof(double)));
-        HIP_TRY(hipMemset(s->test_zero.p, 0, nt * sizeof(double)));
-    }
+    if (test) TRY(mcmc_alloc_test(s, test->n_rows));
     *out = guard.release();
     return FMHIP_OK;
 }
@@ -150,6 +121,82 @@ int set_state(fmhip_mcmc_t s, double alpha, const double *lambda, const double *
 
 }  // namespace
 
+namespace fmhip {
+namespace host {
+
+int mcmc_settings(const fmhip_mcmc_opts *opts, const fmhip_mcmc_task_opts *task_opts, fmhip_mcmc_opts *o, fmhip_mcmc_task_opts *to) {
+    fmhip_mcmc_opts_default(o);
+    if (opts) *o = *opts;
+    const McmcPriors pri{o->alpha_0, o->beta_0, o->alpha_lambda, o->beta_lambda, o->gamma_0, o->mu_0};
+    if (const char *bad = mcmc_bad_setting(pri, o->reg0, o->init_lambda))
+        return fail(FMHIP_ERR_INVALID, "%s must be finite and > 0 (mu_0: finite; reg0: finite and >= 0)", bad);
+    fmhip_mcmc_task_opts_default(to);
+    if (task_opts) *to = *task_opts;
+    if (const char *bad = mcmc_bad_task(to->task, to->clip, to->clip_lo, to->clip_hi)) return fail(FMHIP_ERR_INVALID, "%s", bad);
+    return FMHIP_OK;
+}
+
+int mcmc_check_test(fmhip_model_t m, fmhip_dataset_t test) {
+    if (test->device != m->device) return fail(FMHIP_ERR_INVALID, "model on device %d, test set on device %d", m->device, test->device);
+    if (test->dimension > m->n)
+        return fail(FMHIP_ERR_INVALID, "the test set has feature index %lld but the model has num_attribute = %lld", (long long)test->dimension,
+                    (long long)m->n);
+    if (test->batches.size() > 1 || (test->nnz > 0 && !test->val64.p))
+        return fail(FMHIP_ERR_UNSUPPORTED, "the MCMC learner predicts its test rows in fp64: create the test set with fmhip_dataset_create and "
+                                           "batch_rows <= 0 (single batch; fmhip_rows_create keeps no fp64 rows)");
+    return FMHIP_OK;
+}
+
+void mcmc_fill(fmhip_mcmc_t s, fmhip_model_t m, const fmhip_mcmc_opts &o, const fmhip_mcmc_task_opts &to) {
+    s->m = m;
+    s->opts = o;
+    s->priors = McmcPriors{o.alpha_0, o.beta_0, o.alpha_lambda, o.beta_lambda, o.gamma_0, o.mu_0};
+    s->task = to.task;
+    if (to.task == FMHIP_MCMC_CLASSIFICATION) s->link.kind = kLinkProbit;
+    else if (to.clip) s->link = McmcLink{kLinkClamp, to.clip_lo, to.clip_hi};
+    s->k = m->k;
+}
+
+int mcmc_alloc_test(fmhip_mcmc_t s, int64_t n_rows) {
+    const size_t nt = (size_t)std::max<int64_t>(n_rows, 1);
+    for (DevBuf<double> *b : {&s->test_sum, &s->test_last, &s->test_zero}) {
+        TRY(b->alloc(nt));
+        HIP_TRY(hipMemset(b->p, 0, nt * sizeof(double)));
+    }
+    return FMHIP_OK;
+}
+
+int mcmc_accumulate_flat_test(fmhip_mcmc_t s) {
+    AlsArgs ta{};
+    ta.k = s->k;
+    ta.n_rows = s->test->n_rows;
+    ta.row_ptr = s->test->row_ptr.p;
+    ta.col = s->test->col.p;
+    ta.val = s->test->val64.p;
+    ta.w0 = s->m->als_w0.p;
+    ta.w = s->m->als_w.p;
+    ta.v = s->m->als_v.p;
+    ta.y = s->test_zero.p;
+    ta.e = s->test_last.p;
+    HIP_TRY(launch_mcmc_accumulate(ta, s->test_sum.p, s->m->stream, s->link));
+    return FMHIP_OK;
+}
+
+int mcmc_finish_epoch(fmhip_mcmc_t s, double train_rmse, fmhip_mcmc_stats *stats) {
+    TRY(als_end(s->m));
+    ++s->iterations;
+    ++s->draws;
+    if (stats) {
+        stats->alpha = s->alpha;
+        stats->train_rmse = train_rmse;
+        stats->iterations = s->iterations;
+    }
+    return FMHIP_OK;
+}
+
+}  // namespace host
+}  // namespace fmhip
+
 extern "C" {
 
 int fmhip_mcmc_opts_default(fmhip_mcmc_opts *opts) {
@@ -190,93 +237,49 @@ int fmhip_mcmc_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats) {
     if (m->k != s->k) return fail(FMHIP_ERR_INVALID, "the model's k changed under the MCMC handle");
     AlsArgs a{};
     TRY(als_begin(m, d, s->opts.reg0, 0.0, 0.0, &a));       // (what the handle was created for may have changed: checked again)
-    const int k1 = s->k + 1, P = kMcmcSumParts;
+    const int k1 = s->k + 1, P = kMcmcSumParts, G = s->G;
     const bool probit = s->task == FMHIP_MCMC_CLASSIFICATION;
     const uint32_t t = (uint32_t)s->iterations;
     double sse = 0.0;
-    if (d->n_rows > 0 && s->G > 1) {
-        const int G = s->G, n_chunks = (int)s->plan.chunk_group.size();
-        if (a.n_cols != s->plan_cols)
-            return fail(FMHIP_ERR_INVALID, "the train set's columns changed under the MCMC handle (%d, the groups were set over %lld)", a.n_cols,
-                        (long long)s->plan_cols);
-        const McmcGroupDev dev{s->hyp.p, s->z.p, s->opts.sample ? 1 : 0, 0, s->d_group.p, G};
-        const McmcGroupSums sums{s->d_order.p, s->d_chunk_ptr.p, s->d_chunk_group.p, n_chunks, s->gsums.p};
-        TRY(upload_state(s));                                // the means the sums are taken around
-        const McmcProbit targets{d->y64.p, s->ystar.p, s->iterations == 0 ? kProbitStart : dev.sample ? kProbitSample : kProbitMean};
-        if (probit) a.y = s->ystar.p;
-        HIP_TRY(launch_mcmc_group_begin(a, dev, sums, s->z.p, s->opts.seed, t, s->sums.p, m->stream, probit ? &targets : nullptr));
-        HIP_TRY(hipMemcpyAsync(s->h_sums.data(), s->sums.p, 2 * (size_t)P * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-        if (dev.sample && n_chunks > 0)
-            HIP_TRY(hipMemcpyAsync(s->h_gsums.data(), s->gsums.p, s->h_gsums.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-        HIP_TRY(hipStreamSynchronize(m->stream));            // still the epoch's one host sync
-        for (int c = 0; c < P; ++c) sse += s->h_sums[2 * (size_t)c];
-        if (dev.sample) {
-            if (!probit) s->alpha = mcmc_draw_alpha(s->opts.seed, t, s->priors, d->n_rows, sse);
-            for (int g = 0; g < k1; ++g)
-                for (int ag = 0; ag < G; ++ag) {
-                    double sum_theta = 0.0, sum_dev2 = 0.0;      // a (g, a)'s partials in chunk order; none: a draw from the prior
-                    for (int c = s->plan.group_chunks[(size_t)ag]; c < s->plan.group_chunks[(size_t)ag + 1]; ++c) {
-                        sum_theta += s->h_gsums[2 * ((size_t)c * k1 + g)];
-                        sum_dev2 += s->h_gsums[2 * ((size_t)c * k1 + g) + 1];
-                    }
-                    const size_t at = (size_t)g * G + ag;
-                    mcmc_draw_group(s->opts.seed, t, (uint32_t)g + ((uint32_t)ag << 16), s->priors, s->plan.counts[(size_t)ag], sum_theta, sum_dev2, s->mu[at],
-                                    &s->lambda[at], &s->mu[at]);
-                }
-            TRY(upload_state(s));
-        }
-        const int n_levels = d->als_lev_ptr.empty() ? 0 : (int)d->als_lev_ptr.size() - 1;
-        HIP_TRY(launch_mcmc_group_sweeps(a, dev, d->h_cfeat.data(), d->h_cptr.data(), n_levels ? d->als_lev_ptr.data() : nullptr, d->h_als_lev_cols.data(),
-                                         n_levels, m->stream));
-    } else if (d->n_rows > 0) {
-        const McmcDev dev{s->hyp.p, s->z.p, s->opts.sample ? 1 : 0, 0};
+    // The epoch's launches for the walk's value `dev`: a McmcDev, or with attribute groups a McmcGroupDev and the plan of its
+    // sums — which then come from k_mcmc_group_sums' chunks, not from k_mcmc_sums' quantities 1 + g.  Nothing else differs.
+    const auto run = [&](const auto &dev, const McmcGroupSums *groups) -> int {
         TRY(upload_state(s));                                // the means the sums are taken around
         const McmcProbit targets{d->y64.p, s->ystar.p, s->iterations == 0 ? kProbitStart : dev.sample ? kProbitSample : kProbitMean};
         if (probit) a.y = s->ystar.p;                        // the whole epoch trains on the latent targets
-        HIP_TRY(launch_mcmc_begin(a, dev, s->z.p, s->opts.seed, t, s->sums.p, m->stream, probit ? &targets : nullptr));
-        HIP_TRY(hipMemcpyAsync(s->h_sums.data(), s->sums.p, s->h_sums.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-        HIP_TRY(hipStreamSynchronize(m->stream));
+        HIP_TRY(launch_mcmc_begin(a, dev, s->z.p, s->opts.seed, t, s->sums.p, m->stream, probit ? &targets : nullptr, groups));
+        HIP_TRY(hipMemcpyAsync(s->h_sums.data(), s->sums.p, (groups ? 2 * (size_t)P : s->h_sums.size()) * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        if (groups && dev.sample && groups->n_chunks > 0)
+            HIP_TRY(hipMemcpyAsync(s->h_gsums.data(), s->gsums.p, s->h_gsums.size() * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));            // the epoch's one host sync
         for (int c = 0; c < P; ++c) sse += s->h_sums[2 * (size_t)c];
         if (dev.sample) {
-            if (!probit) s->alpha = mcmc_draw_alpha(s->opts.seed, t, s->priors, d->n_rows, sse);   // (the probit link: alpha stays what the state holds)
-            for (int g = 0; g < k1; ++g) {
-                double sum_theta = 0.0, sum_dev2 = 0.0;
-                for (int c = 0; c < P; ++c) {
-                    sum_theta += s->h_sums[2 * ((size_t)(1 + g) * P + c)];
-                    sum_dev2 += s->h_sums[2 * ((size_t)(1 + g) * P + c) + 1];
-                }
-                mcmc_draw_group(s->opts.seed, t, (uint32_t)g, s->priors, s->n_trained, sum_theta, sum_dev2, s->mu[(size_t)g], &s->lambda[(size_t)g],
-                                &s->mu[(size_t)g]);
-            }
+            const auto count_of = [&](int ag) { return groups ? s->plan.counts[(size_t)ag] : s->n_trained; };
+            const auto partials_of = [&](int g, int ag, auto add) {
+                if (groups)      // the group's chunks in order; none: a draw from the prior
+                    for (int c = s->plan.group_chunks[(size_t)ag]; c < s->plan.group_chunks[(size_t)ag + 1]; ++c)
+                        add(s->h_gsums[2 * ((size_t)c * k1 + g)], s->h_gsums[2 * ((size_t)c * k1 + g) + 1]);
+                else
+                    for (int c = 0; c < P; ++c) add(s->h_sums[2 * ((size_t)(1 + g) * P + c)], s->h_sums[2 * ((size_t)(1 + g) * P + c) + 1]);
+            };
+            mcmc_draw_state(s->opts.seed, t, s->priors, probit, d->n_rows, sse, k1, G, count_of, partials_of, &s->alpha, s->lambda.data(), s->mu.data());
             TRY(upload_state(s));
         }
-        const int n_levels = d->als_lev_ptr.empty() ? 0 : (int)d->als_lev_ptr.size() - 1;
-        HIP_TRY(launch_mcmc_sweeps(a, dev, d->h_cfeat.data(), d->h_cptr.data(), n_levels ? d->als_lev_ptr.data() : nullptr, d->h_als_lev_cols.data(),
-                                   n_levels, m->stream));
+        HIP_TRY(launch_mcmc_sweeps(a, dev, als_plan(d), m->stream));
+        return FMHIP_OK;
+    };
+    const McmcDev flat{s->hyp.p, s->z.p, s->opts.sample ? 1 : 0, 0};
+    if (d->n_rows > 0 && G > 1) {
+        if (a.n_cols != s->plan_cols)
+            return fail(FMHIP_ERR_INVALID, "the train set's columns changed under the MCMC handle (%d, the groups were set over %lld)", a.n_cols,
+                        (long long)s->plan_cols);
+        const McmcGroupSums sums{s->d_order.p, s->d_chunk_ptr.p, s->d_chunk_group.p, (int)s->plan.chunk_group.size(), s->gsums.p};
+        TRY(run(McmcGroupDev{flat, s->d_group.p, G}, &sums));
+    } else if (d->n_rows > 0) {
+        TRY(run(flat, nullptr));
     }
-    if (s->test) {
-        AlsArgs ta{};
-        ta.k = s->k;
-        ta.n_rows = s->test->n_rows;
-        ta.row_ptr = s->test->row_ptr.p;
-        ta.col = s->test->col.p;
-        ta.val = s->test->val64.p;
-        ta.w0 = m->als_w0.p;
-        ta.w = m->als_w.p;
-        ta.v = m->als_v.p;
-        ta.y = s->test_zero.p;
-        ta.e = s->test_last.p;
-        HIP_TRY(launch_mcmc_accumulate(ta, s->test_sum.p, m->stream, s->link));
-    }
-    TRY(als_end(m));
-    ++s->iterations;
-    ++s->draws;
-    if (stats) {
-        stats->alpha = s->alpha;
-        stats->train_rmse = d->n_rows > 0 ? std::sqrt(sse / (double)d->n_rows) : 0.0;
-        stats->iterations = s->iterations;
-    }
-    return FMHIP_OK;
+    if (s->test) TRY(mcmc_accumulate_flat_test(s));
+    return mcmc_finish_epoch(s, d->n_rows > 0 ? std::sqrt(sse / (double)d->n_rows) : 0.0, stats);
 }
 
 int fmhip_mcmc_get_state(fmhip_mcmc_t s, double *alpha, double *lambda, double *mu, int64_t *iterations) {

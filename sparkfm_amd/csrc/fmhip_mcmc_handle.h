@@ -66,5 +66,18 @@ namespace fmhip {
 namespace host {
 // fmhip_mcmc_epoch of a relational handle (the caller holds no lock)
 int mcmc_relational_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats);
+// ---- what the two creators and the two epochs share (fmhip_mcmc.hip) ----
+// the settings a handle is made with: the defaults where opts / task_opts is NULL, refused when one is out of range
+int mcmc_settings(const fmhip_mcmc_opts *opts, const fmhip_mcmc_task_opts *task_opts, fmhip_mcmc_opts *o, fmhip_mcmc_task_opts *to);
+// every reason a flat test set is refused
+int mcmc_check_test(fmhip_model_t m, fmhip_dataset_t test);
+// the fields every handle has: the model, the settings, the priors, the task with its link, k
+void mcmc_fill(fmhip_mcmc_t s, fmhip_model_t m, const fmhip_mcmc_opts &o, const fmhip_mcmc_task_opts &to);
+// test_sum, test_last, test_zero: max(n_rows, 1) zeros each
+int mcmc_alloc_test(fmhip_mcmc_t s, int64_t n_rows);
+// the flat test set's rows under the draw the epoch left: into test_last, through the link, onto test_sum
+int mcmc_accumulate_flat_test(fmhip_mcmc_t s);
+// the epoch's end: the parameters back into the model, the counters, the stats (nullable)
+int mcmc_finish_epoch(fmhip_mcmc_t s, double train_rmse, fmhip_mcmc_stats *stats);
 }  // namespace host
 }  // namespace fmhip

@@ -66,31 +66,6 @@ int check_relational(fmhip_model_t m, fmhip_relational_t R, const char *set) {
     return FMHIP_OK;
 }
 
-// the walk's arguments over dataset d with the model's fp64 device parameters (als_begin's, without the workspace)
-AlsArgs part_args(fmhip_model_t m, fmhip_dataset_t d) {
-    AlsArgs a{};
-    a.k = m->k;
-    a.num_attribute = m->n;
-    a.n_rows = d->n_rows;
-    a.nnz = d->nnz;
-    a.row_ptr = d->row_ptr.p;
-    a.col = d->col.p;
-    a.val = d->val64.p;
-    a.scol = d->scol.p;
-    a.sval = d->sval64.p;
-    a.n_cols = d->n_rows > 0 ? d->batches[0].n_cols : 0;
-    a.cfeat = d->cfeat.p;
-    a.cptr = d->cptr.p;
-    a.crow = d->crow.p;
-    a.cval = d->cval64.p;
-    a.w0 = m->als_w0.p;
-    a.w = m->als_w.p;
-    a.v = m->als_v.p;
-    a.part = m->als_part.p;
-    a.lev_cols = d->als_lev_cols.p;
-    return a;
-}
-
 // per part {alpha, lambda[k + 1], mu[k + 1]}: McmcDev's layout, so that every walk takes the flat handle's step
 int upload_state(fmhip_mcmc_t s) {
     McmcRelational &X = *s->rel;
@@ -156,7 +131,7 @@ int mcmc_relational_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats) {
     std::vector<AlsArgs> fwd((size_t)NP);
     for (int p = 0; p < NP; ++p) {
         McmcRelational::Part &part = *X.parts[(size_t)p];
-        AlsArgs a = part_args(m, part.d);
+        AlsArgs a = als_args(m, part.d);
         a.reg0 = s->opts.reg0;
         a.y = X.zeros.p;
         a.e = part.yhat.p;
@@ -171,8 +146,8 @@ int mcmc_relational_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats) {
     rows.reg0 = s->opts.reg0;
     TRY(upload_state(s));                                // the means the sums are taken around
     if (sample) {
-        for (int p = 0; p < NP; ++p) HIP_TRY(launch_block_noise(fwd[(size_t)p], X.parts[(size_t)p]->z.p, s->opts.seed, t, m->stream));
-        HIP_TRY(launch_block_noise(rows, X.zbias.p, s->opts.seed, t, m->stream));
+        for (int p = 0; p < NP; ++p) HIP_TRY(launch_mcmc_noise(fwd[(size_t)p], X.parts[(size_t)p]->z.p, s->opts.seed, t, m->stream));
+        HIP_TRY(launch_mcmc_noise(rows, X.zbias.p, s->opts.seed, t, m->stream));
     }
     const McmcProbit targets{R->y64.p, s->ystar.p, s->iterations == 0 ? kProbitStart : sample ? kProbitSample : kProbitMean};
     const double *y = probit ? s->ystar.p : R->y64.p;    // the whole epoch trains on the latent targets
@@ -189,28 +164,17 @@ int mcmc_relational_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats) {
     double sse = 0.0;
     for (int c = 0; c < P; ++c) sse += s->h_sums[2 * (size_t)c];
     if (sample) {
-        if (!probit) s->alpha = mcmc_draw_alpha(s->opts.seed, t, s->priors, N, sse);
-        const int G = s->G;
-        for (int g = 0; g < k1; ++g) {
-            double sum_theta = 0.0, sum_dev2 = 0.0;      // every part's chunks in order, the parts in walk order
-            for (int x = 0; x < NP; ++x) {
-                const int p = X.part_groups ? x : X.order[(size_t)x];
-                const McmcRelational::Part &part = *X.parts[(size_t)p];
-                if (X.part_groups) sum_theta = sum_dev2 = 0.0;
-                for (int c = 0; c < P; ++c) {
-                    sum_theta += part.h_sums[2 * ((size_t)g * P + c)];
-                    sum_dev2 += part.h_sums[2 * ((size_t)g * P + c) + 1];
-                }
-                if (X.part_groups) {
-                    const size_t at = (size_t)g * G + p;
-                    mcmc_draw_group(s->opts.seed, t, (uint32_t)g + ((uint32_t)p << 16), s->priors, part.n_trained, sum_theta, sum_dev2, s->mu[at], &s->lambda[at],
-                                    &s->mu[at]);
-                }
-            }
-            if (!X.part_groups)
-                mcmc_draw_group(s->opts.seed, t, (uint32_t)g, s->priors, s->n_trained, sum_theta, sum_dev2, s->mu[(size_t)g], &s->lambda[(size_t)g],
-                                &s->mu[(size_t)g]);
-        }
+        // a (g, a)'s partials: every part's chunks in order, the parts in walk order — with part_groups part a's own
+        const auto count_of = [&](int ag) { return X.part_groups ? X.parts[(size_t)ag]->n_trained : s->n_trained; };
+        const auto partials_of = [&](int g, int ag, auto add) {
+            const auto of_part = [&](const McmcRelational::Part &part) {
+                for (int c = 0; c < P; ++c) add(part.h_sums[2 * ((size_t)g * P + c)], part.h_sums[2 * ((size_t)g * P + c) + 1]);
+            };
+            if (X.part_groups) of_part(*X.parts[(size_t)ag]);
+            else
+                for (int x = 0; x < NP; ++x) of_part(*X.parts[(size_t)X.order[(size_t)x]]);
+        };
+        mcmc_draw_state(s->opts.seed, t, s->priors, probit, N, sse, k1, s->G, count_of, partials_of, &s->alpha, s->lambda.data(), s->mu.data());
         TRY(upload_state(s));
     }
     // ---- behind the sync: the bias, the residuals again, the sweeps
@@ -222,13 +186,11 @@ int mcmc_relational_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats) {
             McmcRelational::Part &part = *X.parts[(size_t)p];
             fmhip_dataset_t d = part.d;
             const McmcDev dev{X.hyp.p + (size_t)p * stride, part.z.p, sample ? 1 : 0, 0};
-            const int n_levels = d->als_lev_ptr.empty() ? 0 : (int)d->als_lev_ptr.size() - 1;
             if (part.rel < 0) {
                 AlsArgs a = fwd[(size_t)p];
                 a.e = X.e.p;
                 a.q = X.Q.p;
-                HIP_TRY(launch_plain_pass(a, g, dev, d->h_cfeat.data(), d->h_cptr.data(), n_levels ? d->als_lev_ptr.data() : nullptr,
-                                          d->h_als_lev_cols.data(), n_levels, m->stream));
+                HIP_TRY(launch_plain_pass(a, g, dev, als_plan(d), m->stream));
                 continue;
             }
             const fmhip_relational::Relation &rel = *R->rels[(size_t)part.rel];
@@ -254,45 +216,25 @@ int mcmc_relational_epoch(fmhip_mcmc_t s, fmhip_mcmc_stats *stats) {
             b.cache = part.cache.p;
             b.part = part.part.p;
             b.qrest = X.qrest.p;
-            const BlockPlan plan{d->h_cptr.data(), part.h_trained.data(), n_levels ? d->als_lev_ptr.data() : nullptr, d->h_als_lev_cols.data(), n_levels};
-            HIP_TRY(launch_block_pass(b, plan, g, X.e.p, X.Q.p, dev, m->stream));
+            HIP_TRY(launch_block_pass(b, BlockPlan{als_plan(d), part.h_trained.data()}, g, X.e.p, X.Q.p, dev, m->stream));
         }
     // ---- the test rows under the draw the epoch left
     if (X.test) {
         fmhip_relational_t T = X.test;
         std::vector<AlsArgs> tf((size_t)n_parts(T));
         for (size_t p = 0; p < tf.size(); ++p) {
-            AlsArgs a = part_args(m, part_data(T, (int)p));
+            AlsArgs a = als_args(m, part_data(T, (int)p));
             a.y = X.test_zeros.p;
             a.e = X.test_parts[p]->yhat.p;
             a.q = X.test_parts[p]->q.p;
             tf[p] = a;
         }
         TRY(residuals(s, T, tf, X.test_zeros.p, s->test_last.p, nullptr, nullptr, t));
-        HIP_TRY(launch_block_accumulate(s->test_last.p, s->test_sum.p, T->n_rows, s->link, m->stream));
+        HIP_TRY(launch_mcmc_accumulate_link(s->test_last.p, s->test_sum.p, T->n_rows, s->link, m->stream));
     } else if (s->test) {
-        AlsArgs ta{};
-        ta.k = s->k;
-        ta.n_rows = s->test->n_rows;
-        ta.row_ptr = s->test->row_ptr.p;
-        ta.col = s->test->col.p;
-        ta.val = s->test->val64.p;
-        ta.w0 = m->als_w0.p;
-        ta.w = m->als_w.p;
-        ta.v = m->als_v.p;
-        ta.y = s->test_zero.p;
-        ta.e = s->test_last.p;
-        HIP_TRY(launch_mcmc_accumulate(ta, s->test_sum.p, m->stream, s->link));
+        TRY(mcmc_accumulate_flat_test(s));
     }
-    TRY(als_end(m));
-    ++s->iterations;
-    ++s->draws;
-    if (stats) {
-        stats->alpha = s->alpha;
-        stats->train_rmse = std::sqrt(sse / (double)N);
-        stats->iterations = s->iterations;
-    }
-    return FMHIP_OK;
+    return mcmc_finish_epoch(s, std::sqrt(sse / (double)N), stats);
 }
 
 }  // namespace host
@@ -305,29 +247,15 @@ int fmhip_mcmc_create_relational(fmhip_model_t m, fmhip_relational_t train, fmhi
     if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
     *out = nullptr;
     fmhip_mcmc_opts o;
-    fmhip_mcmc_opts_default(&o);
-    if (opts) o = *opts;
-    const McmcPriors pri{o.alpha_0, o.beta_0, o.alpha_lambda, o.beta_lambda, o.gamma_0, o.mu_0};
-    if (const char *bad = mcmc_bad_setting(pri, o.reg0, o.init_lambda))
-        return fail(FMHIP_ERR_INVALID, "%s must be finite and > 0 (mu_0: finite; reg0: finite and >= 0)", bad);
-    fmhip_mcmc_task_opts to{FMHIP_MCMC_REGRESSION, 0, 0.0, 0.0};
-    if (task_opts) to = *task_opts;
-    if (const char *bad = mcmc_bad_task(to.task, to.clip, to.clip_lo, to.clip_hi)) return fail(FMHIP_ERR_INVALID, "%s", bad);
+    fmhip_mcmc_task_opts to;
+    TRY(mcmc_settings(opts, task_opts, &o, &to));
     if (!m || !train) return fail(FMHIP_ERR_INVALID, "model or train set is NULL");
     if (test_relational && test_flat) return fail(FMHIP_ERR_INVALID, "a relational test set and a flat one were both given: at most one of the two");
     ReadLock lock(m);
     fmhip_relational_t R = train;
     TRY(check_relational(m, R, "the train set"));
     if (test_relational) TRY(check_relational(m, test_relational, "the test set"));
-    if (test_flat) {
-        if (test_flat->device != m->device) return fail(FMHIP_ERR_INVALID, "model on device %d, test set on device %d", m->device, test_flat->device);
-        if (test_flat->dimension > m->n)
-            return fail(FMHIP_ERR_INVALID, "the test set has feature index %lld but the model has num_attribute = %lld", (long long)test_flat->dimension,
-                        (long long)m->n);
-        if (test_flat->batches.size() > 1 || (test_flat->nnz > 0 && !test_flat->val64.p))
-            return fail(FMHIP_ERR_UNSUPPORTED, "the MCMC learner predicts its test rows in fp64: create the test set with fmhip_dataset_create and "
-                                               "batch_rows <= 0 (single batch; fmhip_rows_create keeps no fp64 rows)");
-    }
+    if (test_flat) TRY(mcmc_check_test(m, test_flat));
     const int NP = n_parts(R);
     if (part_groups && NP > FMHIP_MCMC_MAX_GROUPS) return fail(FMHIP_ERR_UNSUPPORTED, "%d parts are above FMHIP_MCMC_MAX_GROUPS", NP);
     McmcPartOrder po;
@@ -351,14 +279,8 @@ int fmhip_mcmc_create_relational(fmhip_model_t m, fmhip_relational_t train, fmhi
     s->rel.reset(new (std::nothrow) McmcRelational);
     if (!s->rel) return fail(FMHIP_ERR_NOMEM, "out of host memory");
     McmcRelational &X = *s->rel;
-    s->m = m;
+    mcmc_fill(s, m, o, to);
     s->test = test_flat;
-    s->opts = o;
-    s->priors = pri;
-    s->task = to.task;
-    if (to.task == FMHIP_MCMC_CLASSIFICATION) s->link.kind = kLinkProbit;
-    else if (to.clip) s->link = McmcLink{kLinkClamp, to.clip_lo, to.clip_hi};
-    s->k = m->k;
     X.train = R;
     X.test = test_relational;
     X.order = po.order;
@@ -415,12 +337,7 @@ int fmhip_mcmc_create_relational(fmhip_model_t m, fmhip_relational_t train, fmhi
     TRY(zeros(X.zeros, max_rows));
     TRY(zeros(X.zbias, 1));
     if (s->task == FMHIP_MCMC_CLASSIFICATION) TRY(s->ystar.alloc(N));
-    if (test_relational || test_flat) {
-        const size_t nt = (size_t)std::max<int64_t>(test_relational ? test_relational->n_rows : test_flat->n_rows, 1);
-        TRY(zeros(s->test_sum, nt));
-        TRY(zeros(s->test_last, nt));
-        TRY(zeros(s->test_zero, nt));
-    }
+    if (test_relational || test_flat) TRY(mcmc_alloc_test(s, test_relational ? test_relational->n_rows : test_flat->n_rows));
     if (test_relational) {
         size_t rows = (size_t)test_relational->n_rows;
         for (int p = 0; p < n_parts(test_relational); ++p) {

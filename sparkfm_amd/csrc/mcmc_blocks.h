@@ -1,6 +1,7 @@
 // mcmc_blocks.h — launchers of the MCMC learner's block-structure sweep (include/fmhip_mcmc_relational.h; internal to libfmhip.so).
-// The kernels sit in als_kernels.hip beside the flat column walk, whose step (DrawMcmc), sums (wave_sum, block_sum2) and per-group
-// passes (level_pass / sweep_pass: the plain part) they share; the existing instantiations keep their arguments and their code.
+// The kernels sit in als_kernels.hip beside the flat column walk, whose step (DrawMcmc), sums (wave_sum, block_sum2, theta_sums),
+// walk choice and per-group pass (group_pass: the plain part) they share; the existing instantiations keep their arguments and
+// their code.  The parts' noise and the test rows' accumulation are als_kernels.h's launch_mcmc_noise / launch_mcmc_accumulate_link.
 #pragma once
 #include "als_kernels.h"
 
@@ -42,14 +43,11 @@ struct BlockCombine {
     double *Q;                           // [k][n_rows] out, nullable
 };
 
-// The host's view of a block's columns: what the walk's launch plan follows
-struct BlockPlan {
-    const int32_t *h_cptr, *h_trained, *h_lev_ptr, *h_lev_cols;
-    int32_t n_levels;
+// The host's view of a block's columns: what the walk's launch plan follows, and a copy of BlockPart.trained
+struct BlockPlan : ColumnPlan {
+    const int32_t *h_trained;
 };
 
-// the epoch's noise of one part's columns (z: [(k + 1) * a.n_cols + 1]; a.n_cols = 0: the bias's alone)
-hipError_t launch_block_noise(const AlsArgs &a, double *z, uint64_t seed, uint32_t t, hipStream_t s);
 // yhat_p of every block row (a.e) and, with_q, q_p (a.q: it depends on v alone, so the pass behind the bias step leaves it out)
 hipError_t launch_block_forward(const AlsArgs &a, bool with_q, hipStream_t s);
 hipError_t launch_block_combine(const BlockCombine &c, const McmcProbit *probit, uint64_t seed, uint32_t t, hipStream_t s);
@@ -62,9 +60,6 @@ hipError_t launch_block_bias(const AlsArgs &rows, const McmcDev &m, hipStream_t 
 // One part's pass of parameter group g (0: w; 1 + f: factor f): cache build, the column walk, the scatter into e and Q_f
 hipError_t launch_block_pass(const BlockPart &b, const BlockPlan &plan, int g, double *e, double *Q, const McmcDev &m, hipStream_t s);
 // ... and the plain part's: the flat walk's per-group pass over e and Q_f directly (a.e = e, a.q = Q)
-hipError_t launch_plain_pass(const AlsArgs &a, int g, const McmcDev &m, const int32_t *h_cfeat, const int32_t *h_cptr, const int32_t *h_lev_ptr,
-                             const int32_t *h_lev_cols, int n_levels, hipStream_t s);
-// last <- link(last), sum += last
-hipError_t launch_block_accumulate(double *last, double *sum, int64_t n_rows, const McmcLink &link, hipStream_t s);
+hipError_t launch_plain_pass(const AlsArgs &a, int g, const McmcDev &m, const ColumnPlan &plan, hipStream_t s);
 
 }  // namespace fmhip

@@ -1,9 +1,14 @@
 // host_mcmc_groups_harness.cpp — the host plan of the MCMC learner's grouped hyper-parameter sums (sparkfm_amd/csrc/fmhip_host.cpp:
 // mcmc_group_plan, mcmc_bad_group) as a stand-alone program, built with -fsanitize=address,undefined:
 //   host_mcmc_groups_harness check <seed>    random shapes and the edge cases -> "checks ok"
+//   host_mcmc_groups_harness draw <seed>     the epoch's hyper-parameter draws (fmhip_host.h: mcmc_draw_state) -> "draws ok"
 // Every shape is checked for: the chunks cover every trained slot exactly once; they sit in group order; no chunk crosses a group
 // or holds more than the chunk size; a group's slots keep their ascending order (the plan is stable); m_a is right; quirk Q1's
 // slot (id = num_attribute) is in no chunk whatever group it was given.
+// draw: mcmc_draw_state for k + 1 = 3 over the three shapes its callers give it — one group with 4 partials (the flat handle), three
+// groups with 0, 1 and 5 partials (the grouped handle; the empty group draws from the prior), and two parts' 4 partials each added
+// as one run (the relational handle) — against mcmc_draw_alpha / mcmc_draw_group called one at a time on sums added sequentially in
+// that order, stream id g + (a << 16): exact equality.  The probit form leaves alpha as it was.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -70,8 +75,72 @@ static void check_plan(const char *what, const std::vector<int32_t> &cfeat, int6
     for (size_t s = 0; s < cfeat.size(); ++s) CHECK(seen[s] == (cfeat[s] < num_attribute ? 1 : 0), "%s: slot %zu planned %d times", what, s, seen[s]);
 }
 
+static double rnd_double() { return (double)rnd() / 2147483648.0 * 4.0 - 2.0; }
+
+// partials[g][a]: the (sum theta, sum dev^2) pairs of (g, a) in the order they are added
+static void check_draw(const char *what, uint64_t seed, uint32_t t, int G, const std::vector<int> &n_partials, const std::vector<int64_t> &counts) {
+    const int k1 = 3;
+    McmcPriors pri;
+    pri.alpha_0 = 1.5; pri.beta_0 = 0.5; pri.alpha_lambda = 2.0; pri.beta_lambda = 0.25; pri.gamma_0 = 3.0; pri.mu_0 = -0.5;
+    std::vector<std::vector<double>> partials((size_t)k1 * (size_t)G);
+    for (int g = 0; g < k1; ++g)
+        for (int a = 0; a < G; ++a)
+            for (int c = 0; c < n_partials[(size_t)a]; ++c) {
+                partials[(size_t)g * G + a].push_back(rnd_double());
+                partials[(size_t)g * G + a].push_back(rnd_double() * rnd_double() + 4.0);      // a sum of squares: positive
+            }
+    std::vector<double> lambda0((size_t)k1 * (size_t)G), mu0((size_t)k1 * (size_t)G);
+    for (size_t i = 0; i < lambda0.size(); ++i) {
+        lambda0[i] = 0.5 + (double)(rnd() % 100) / 10.0;
+        mu0[i] = rnd_double();
+    }
+    const int64_t n_rows = 1 + rnd() % 1000;
+    const double sse = 0.25 + (double)(rnd() % 1000);
+    const auto count_of = [&](int a) { return counts[(size_t)a]; };
+    const auto partials_of = [&](int g, int a, auto add) {
+        const std::vector<double> &v = partials[(size_t)g * G + a];
+        for (size_t c = 0; c < v.size(); c += 2) add(v[c], v[c + 1]);
+    };
+    for (int probit = 0; probit < 2; ++probit) {
+        double alpha = 7.25;
+        std::vector<double> lambda = lambda0, mu = mu0;
+        mcmc_draw_state(seed, t, pri, probit != 0, n_rows, sse, k1, G, count_of, partials_of, &alpha, lambda.data(), mu.data());
+        const double want_alpha = probit ? 7.25 : mcmc_draw_alpha(seed, t, pri, n_rows, sse);
+        CHECK(alpha == want_alpha, "%s, probit %d: alpha = %.17g, want %.17g", what, probit, alpha, want_alpha);
+        for (int g = 0; g < k1; ++g)
+            for (int a = 0; a < G; ++a) {
+                const size_t at = (size_t)g * G + a;
+                double sum_theta = 0.0, sum_dev2 = 0.0;
+                for (size_t c = 0; c < partials[at].size(); c += 2) {
+                    sum_theta += partials[at][c];
+                    sum_dev2 += partials[at][c + 1];
+                }
+                double want_lambda = lambda0[at], want_mu = mu0[at];
+                mcmc_draw_group(seed, t, (uint32_t)g + ((uint32_t)a << 16), pri, counts[(size_t)a], sum_theta, sum_dev2, mu0[at], &want_lambda, &want_mu);
+                CHECK(lambda[at] == want_lambda && mu[at] == want_mu, "%s, probit %d, (g, a) = (%d, %d): lambda %.17g mu %.17g, want %.17g %.17g", what, probit, g,
+                      a, lambda[at], mu[at], want_lambda, want_mu);
+                CHECK(want_lambda != lambda0[at] && want_mu != mu0[at], "%s: (%d, %d) was not drawn", what, g, a);
+            }
+    }
+}
+
+static int draws(uint64_t seed) {
+    for (uint32_t t = 0; t < 3; ++t) {
+        check_draw("one group, 4 partials", seed, t, 1, {4}, {11});
+        check_draw("three groups, 0 / 1 / 5 partials", seed, t, 3, {0, 1, 5}, {0, 300, 2100});
+        check_draw("two parts of 4 partials as one run", seed, t, 1, {2 * 4}, {64});
+    }
+    if (fails) {
+        fprintf(stderr, "%d checks failed\n", fails);
+        return 1;
+    }
+    printf("draws ok\n");
+    return 0;
+}
+
 int main(int argc, char **argv) {
     rng_state = argc > 2 ? strtoull(argv[2], nullptr, 10) : 1u;
+    if (argc > 1 && !strcmp(argv[1], "draw")) return draws(rng_state);
     // ---- the edge cases
     {
         const int64_t n = 10;

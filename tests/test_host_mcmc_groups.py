@@ -1,6 +1,7 @@
 """The MCMC learner's attribute groups, host surface (no GPU): the header against the binding, the refusals that need no device,
-Metadata's arithmetic, HipMCMC's validation of `groups`, and the host plan of the grouped sums (csrc/fmhip_host.cpp: mcmc_group_plan,
-driven by tests/host_mcmc_groups_harness.cpp — a stand-alone program built with AddressSanitizer and UBSan)."""
+Metadata's arithmetic, HipMCMC's validation of `groups`, and the host plan of the grouped sums (csrc/fmhip_host.cpp: mcmc_group_plan)
+and the epoch's hyper-parameter draws (csrc/fmhip_host.h: mcmc_draw_state), both driven by tests/host_mcmc_groups_harness.cpp — a
+stand-alone program built with AddressSanitizer and UBSan."""
 import ctypes as C
 import os
 import re
@@ -149,3 +150,12 @@ def test_the_chunk_plan_under_the_sanitizers(harness):
     a group or exceed the chunk size, keep a group's slots ascending; m_a is right."""
     for seed in (20261019, 5):
         assert "checks ok" in harness("check", seed)
+
+
+def test_the_state_draw_is_the_single_draws_in_the_documented_order(harness):
+    """mcmc_draw_state — the one hyper-parameter draw of the flat, the grouped and the relational epoch — for k + 1 = 3 over one group
+    with 4 partials, three groups with 0, 1 and 5 partials (the empty group: the draw from the prior) and two parts' 4 partials each as
+    one run: alpha, lambda and mu EQUAL mcmc_draw_alpha / mcmc_draw_group called one at a time on sums added sequentially in that order
+    with stream id g + (a << 16); the probit form leaves alpha untouched."""
+    for seed in (20261020, 7):
+        assert "draws ok" in harness("draw", seed)
