@@ -4,6 +4,7 @@
 // several candidates per pair with the same integer code and keeps the one the model scores highest: the one place with fp32 in it,
 // a dot product whose summation order the row width alone fixes.
 #include "fm_bpr.h"
+#include "fm_device.h"      // f4dot; grid_blocks (fm_kernels.h)
 #include "mcmc_rng.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -17,6 +18,26 @@ using u64 = unsigned long long;
 
 inline unsigned blocks_of(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
 
+// the block's sums of N counters: an xor-shuffle inside every wave, one LDS word per wave, thread i < N adds counter i's words
+// in wave order and writes out[i]
+template <int N>
+__device__ __forceinline__ void block_sums_u64(u64 (&v)[N], u64 *out) {
+    __shared__ u64 sh[N][kT / 64];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], m, 64);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int i = 0; i < N; ++i) sh[i][threadIdx.x >> 6] = v[i];
+    __syncthreads();
+    if (threadIdx.x < N) {
+        u64 s = 0;
+        for (int w = 0; w < kT / 64; ++w) s += sh[threadIdx.x][w];
+        out[threadIdx.x] = s;
+    }
+}
+
 __global__ __launch_bounds__(kT) void k_bpr_sample(BprSampleArgs a) {
     u64 att = 0, forced = 0;
     for (int64_t p = (int64_t)blockIdx.x * kT + threadIdx.x; p < a.n_pairs; p += (int64_t)gridDim.x * kT) {
@@ -27,52 +48,21 @@ __global__ __launch_bounds__(kT) void k_bpr_sample(BprSampleArgs a) {
         att += (u64)at;
         forced += (u64)f;
     }
-    __shared__ u64 sh[2][kT / 64];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        att += __shfl_xor(att, m, 64);
-        forced += __shfl_xor(forced, m, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        sh[0][threadIdx.x >> 6] = att;
-        sh[1][threadIdx.x >> 6] = forced;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        u64 s = 0;
-        for (int w = 0; w < kT / 64; ++w) s += sh[threadIdx.x][w];
-        a.part[2 * (size_t)blockIdx.x + threadIdx.x] = s;
-    }
+    u64 v[2] = {att, forced};
+    block_sums_u64<2>(v, a.part + 2 * (size_t)blockIdx.x);
 }
 
-// one block: the per-block partials' sums (integers: any order gives the same)
-__global__ __launch_bounds__(kT) void k_bpr_sample_total(const u64 *part, int n_blocks, u64 *total) {
-    u64 s[2] = {0, 0};
-    for (int b = threadIdx.x; b < n_blocks; b += kT) {
-        s[0] += part[2 * (size_t)b];
-        s[1] += part[2 * (size_t)b + 1];
-    }
-    __shared__ u64 sh[2][kT / 64];
+// one block: the sums of the per-block partials of N counters each (integers: any order gives the same)
+template <int N>
+__global__ __launch_bounds__(kT) void k_bpr_total(const u64 *part, int n_blocks, u64 *total) {
+    u64 s[N] = {};
+    for (int b = threadIdx.x; b < n_blocks; b += kT)
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        s[0] += __shfl_xor(s[0], m, 64);
-        s[1] += __shfl_xor(s[1], m, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        sh[0][threadIdx.x >> 6] = s[0];
-        sh[1][threadIdx.x >> 6] = s[1];
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        u64 v = 0;
-        for (int w = 0; w < kT / 64; ++w) v += sh[threadIdx.x][w];
-        total[threadIdx.x] = v;
-    }
+        for (int i = 0; i < N; ++i) s[i] += part[N * (size_t)b + i];
+    block_sums_u64<N>(s, total);
 }
 
 // ---- the adaptive sampler (fm_bpr.h: BprAdaptiveArgs) -----------------------------------------------------------------------------
-
-__device__ __forceinline__ float f4dot(float4 a, float4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); }
 
 constexpr int kCandChunk = 4;       // candidate rows a group has in flight before it reduces: the gathers' latency overlaps
 
@@ -152,43 +142,8 @@ __global__ __launch_bounds__(kT) void k_bpr_sample_adaptive(BprAdaptiveArgs a) {
         }
     }
     if (RECORD) return;
-    __shared__ u64 sh[3][kT / 64];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        att += __shfl_xor(att, m, 64);
-        forced += __shfl_xor(forced, m, 64);
-        repl += __shfl_xor(repl, m, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        sh[0][threadIdx.x >> 6] = att;
-        sh[1][threadIdx.x >> 6] = forced;
-        sh[2][threadIdx.x >> 6] = repl;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        u64 s = 0;
-        for (int w = 0; w < kT / 64; ++w) s += sh[threadIdx.x][w];
-        a.s.part[3 * (size_t)blockIdx.x + threadIdx.x] = s;
-    }
-}
-
-// one block: the sums of the per-block {attempts, forced, replaced}
-__global__ __launch_bounds__(kT) void k_bpr_adaptive_total(const u64 *part, int n_blocks, u64 *total) {
-    u64 s[3] = {0, 0, 0};
-    for (int b = threadIdx.x; b < n_blocks; b += kT)
-        for (int i = 0; i < 3; ++i) s[i] += part[3 * (size_t)b + i];
-    __shared__ u64 sh[3][kT / 64];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-        for (int i = 0; i < 3; ++i) s[i] += __shfl_xor(s[i], m, 64);
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < 3; ++i) sh[i][threadIdx.x >> 6] = s[i];
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        u64 v = 0;
-        for (int w = 0; w < kT / 64; ++w) v += sh[threadIdx.x][w];
-        total[threadIdx.x] = v;
-    }
+    u64 v[3] = {att, forced, repl};
+    block_sums_u64<3>(v, a.s.part + 3 * (size_t)blockIdx.x);
 }
 
 template <int G>
@@ -203,7 +158,7 @@ hipError_t launch_adaptive(const BprAdaptiveArgs &a, hipStream_t s) {
     hipLaunchKernelGGL((k_bpr_sample_adaptive<G, false>), dim3((unsigned)blocks), dim3(kT), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_bpr_adaptive_total, dim3(1), dim3(kT), 0, s, a.s.part, blocks, a.s.total);
+    hipLaunchKernelGGL(k_bpr_total<3>, dim3(1), dim3(kT), 0, s, a.s.part, blocks, a.s.total);
     return hipGetLastError();
 }
 
@@ -340,28 +295,17 @@ hipError_t inv_layout(int32_t rows, int32_t block_rows, InvLayout *L) {
 
 }  // namespace
 
-int bpr_sample_blocks(int64_t n_pairs) {
-    int64_t blocks = (n_pairs + kT - 1) / kT;
-    if (blocks > 4096) blocks = 4096;       // pairs grid-strided
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
+int bpr_sample_blocks(int64_t n_pairs) { return grid_blocks(n_pairs, kT, 4096); }
 
 hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s) {
     const int blocks = bpr_sample_blocks(a.n_pairs);
     hipLaunchKernelGGL(k_bpr_sample, dim3((unsigned)blocks), dim3(kT), 0, s, a);
     BPR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bpr_sample_total, dim3(1), dim3(kT), 0, s, a.part, blocks, a.total);
+    hipLaunchKernelGGL(k_bpr_total<2>, dim3(1), dim3(kT), 0, s, a.part, blocks, a.total);
     return hipGetLastError();
 }
 
-int bpr_adaptive_blocks(int Kp, int64_t n_pairs) {
-    const int64_t per_block = kT / (Kp / 4);      // a group of Kp / 4 lanes per pair
-    int64_t blocks = (n_pairs + per_block - 1) / per_block;
-    if (blocks > 4096) blocks = 4096;       // pairs grid-strided
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
+int bpr_adaptive_blocks(int Kp, int64_t n_pairs) { return grid_blocks(n_pairs, kT / (Kp / 4), 4096); }      // a group of Kp / 4 lanes per pair
 
 hipError_t launch_bpr_sample_adaptive(int Kp, const BprAdaptiveArgs &a, hipStream_t s) {
     if (a.n_cand < 1 || a.n_cand > kBprMaxCand || a.k < 0 || a.k > Kp) return hipErrorInvalidValue;

@@ -50,6 +50,7 @@ __device__ __forceinline__ float4 f4mul(float4 a, float s) { return make_float4(
 __device__ __forceinline__ void f4fma(float4 &acc, float4 a, float s) {
     acc.x = fmaf(a.x, s, acc.x); acc.y = fmaf(a.y, s, acc.y); acc.z = fmaf(a.z, s, acc.z); acc.w = fmaf(a.w, s, acc.w);
 }
+__device__ __forceinline__ float f4dot(float4 a, float4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); }
 __device__ __forceinline__ void f4add(float4 &acc, float4 a) { acc.x += a.x; acc.y += a.y; acc.z += a.z; acc.w += a.w; }
 __device__ __forceinline__ void f4sqacc(float4 &acc, float4 a) {
     acc.x = fmaf(a.x, a.x, acc.x); acc.y = fmaf(a.y, a.y, acc.y); acc.z = fmaf(a.z, a.z, acc.z); acc.w = fmaf(a.w, a.w, acc.w);
@@ -378,49 +379,6 @@ __device__ __forceinline__ void reduce_blocks_body(const double *bsum, int32_t n
             const float rows = (float)n_rows, invb = rows > 0.f ? 1.0f / rows : 0.f, b0 = *w0;
             *w0 = b0 - eta * fmaf(reg0, b0, (float)t1 * invb);
         }
-    }
-}
-
-// ------------------------------------------------------------------ the finishes behind a q-mode forward
-// (k_pair_finish, fm_pairing.hip; k_weight_finish, fm_weights.hip)
-// sigma(d) - t, t in {0, 1}, without overflow — the form of row_finish (fm_forward.hip) applied to the pair's margin: z = exp(-|d|)
-// <= 1, and 1 - sigma(d) = sigma(-d) is formed directly, so a saturated margin on the right side gives a tiny residual rather
-// than a difference of two numbers near 1.  z is handed back for the log-loss, log1p(z) + max(t ? -d : d, 0).
-__device__ __forceinline__ float pair_sigma_residual(float d, bool t, float &z) {
-    z = expf(-fabsf(d));
-    const float inv = 1.f / (1.f + z);
-    const bool pos = d >= 0.f;
-    return t ? -(pos ? z * inv : inv) : (pos ? inv : z * inv);
-}
-
-// The residual of a weighted row (fm_weights.h): c * e, and +0 for a row of weight 0 whatever its e — a non-finite one included —
-// so that such a row adds exactly nothing anywhere (its sign bit too: e rides in the P row's bits, kEInP).
-__device__ __forceinline__ float weighted_residual(float c, float e) { return c > 0.f ? c * e : 0.f; }
-
-// block partial of N sums (fixed order), to bsum[blockIdx.x][4] (the slots past N: 0)
-template <int N>
-__device__ __forceinline__ void pair_block_sums(double *bsum, double (&v)[N], const int (&slot)[N]) {
-    static_assert(N <= 4, "a partial has four slots");
-    __shared__ double sh[N][kBlock / 64];
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v[i] += __shfl_xor(v[i], m, 64);
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int i = 0; i < N; ++i) sh[i][wv] = v[i];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double o[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            double t = 0.0;
-#pragma unroll
-            for (int w = 0; w < kBlock / 64; ++w) t += sh[i][w];
-            o[slot[i]] = t;
-        }
-        *reinterpret_cast<double4 *>(bsum + (size_t)blockIdx.x * 4) = make_double4(o[0], o[1], o[2], o[3]);
     }
 }
 

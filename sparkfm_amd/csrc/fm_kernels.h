@@ -24,6 +24,11 @@ inline int tune_default(int key) { return g_tune[key].load(std::memory_order_rel
 
 // padded factor count: 4 * LPN * J with LPN = lanes per row-slot (<= 16), J float4 per lane
 int padded_factors(int k);
+// grid of a kernel that strides its grid over `items`, per_block of them per workgroup and pass: what covers them in one pass, in [1, cap]
+inline int grid_blocks(int64_t items, int64_t per_block, int cap) {
+    const int64_t blocks = (items + per_block - 1) / per_block;
+    return (int)(blocks > cap ? cap : (blocks < 1 ? 1 : blocks));
+}
 // grid of k_forward for a batch (also the number of per-block statistic partials it writes)
 constexpr int kMaxFwdBlocks = 16384;
 int forward_blocks(int Kp, int64_t n_rows);

@@ -18,21 +18,19 @@ struct PairArgs {
     const float *yhat;   // [2 * n_pairs] the rows' predictions
     const float *y;      // [2 * n_pairs] the batch's labels (an even row0: 8-byte aligned)
     float *e;            // [2 * n_pairs] out
-    double *bsum;        // [pair_finish_blocks][4] per-block {sum e = 0 exactly, sum e^2, rows with a non-finite yhat, 0}
+    double *bsum;        // [slot_blocks(Kp, n_pairs)][4] per-block {sum e = 0 exactly, sum e^2, rows with a non-finite yhat, 0}
     int32_t n_pairs;
     int32_t pack_k;      // >= 0: packed rows (FwdArgs::pack_k)
     int32_t loss;        // Loss (fm_kernels.h)
     const float *c;      // weighted dataset (fm_weights.h): [2 * n_pairs] the batch's row weights, pair j's = c[2j]; NULL: none
 };
 
-// grid of launch_pair_finish = the number of per-block statistic partials it writes (<= kMaxFwdBlocks)
-int pair_finish_blocks(int Kp, int64_t n_pairs);
+// n_partials: the launch's grid (slot_blocks, fm_finish.h) = the number of per-block statistic partials it writes (<= kMaxFwdBlocks)
 hipError_t launch_pair_finish(int Kp, const PairArgs &a, hipStream_t s, int *n_partials);
 
 // Scoring of held-out pairs (fmhip_pair_logloss): per-block partials in the layout launch_reduce_blocks(with_logloss) sums,
 //     {concordance (1, or 0.5 at d == 0), sum e^2 over both rows with e = +-(sigma(d) - [dy > 0]), rows with a non-finite yhat, log-loss}
 // the log-loss of a pair being softplus(-d) if dy > 0, else softplus(d).
-int pair_score_blocks(int64_t n_pairs);
 hipError_t launch_pair_score(const float *yhat, const float *y, int32_t n_pairs, double *bsum, hipStream_t s, int *n_partials);
 
 }  // namespace fmhip

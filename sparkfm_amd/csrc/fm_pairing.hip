@@ -1,7 +1,7 @@
 // fm_pairing.hip — pairwise ranking (BPR / RankNet): the residual of a PAIR of rows, formed after the kFwdQ forward has left
 // every row's sv*q in P and its prediction beside it (k_pair_finish), and the scoring of held-out pairs (k_pair_score).
-// Formulas and buffers: fm_pairing.h.  Lane geometry: fm_device.h.
-#include "fm_device.h"
+// Formulas and buffers: fm_pairing.h.  Lane geometry: fm_device.h; what the finishes share: fm_finish.h.
+#include "fm_finish.h"
 #include "fm_pairing.h"
 
 namespace fmhip {
@@ -17,13 +17,12 @@ namespace {
 template <int LPN, int J, bool PACKED, bool WEIGHTED>
 __global__ __launch_bounds__(kBlock) void k_pair_finish(PairArgs a) {
     constexpr int KP = 4 * LPN * J;
-    constexpr int SLOTS = kBlock / LPN;
-    const int l = threadIdx.x & (LPN - 1);
-    const int slot = threadIdx.x / LPN;
-    const int kl = PACKED ? (a.pack_k >> 2) & (LPN - 1) : 0, kj = PACKED ? (a.pack_k >> 2) / LPN : 0, kc = a.pack_k & 3;
+    const SlotLoop<LPN> sl;
+    const int l = sl.l;
+    const PackPos<LPN, PACKED> k(a.pack_k);
     const bool logistic = a.loss == kLossLogistic;
     float st2 = 0.f, stbad = 0.f;
-    for (int j = blockIdx.x * SLOTS + slot; j < a.n_pairs; j += gridDim.x * SLOTS) {
+    for (int j = sl.first; j < a.n_pairs; j += sl.stride) {
         float4 *p0 = reinterpret_cast<float4 *>(a.P + (size_t)(2 * j) * KP) + l, *p1 = p0 + KP / 4;
         float4 r0[J], r1[J];
 #pragma unroll
@@ -35,16 +34,9 @@ __global__ __launch_bounds__(kBlock) void k_pair_finish(PairArgs a) {
         if (WEIGHTED) g = weighted_residual(a.c[2 * j], g);
         const float e0 = g, e1 = -g;
 #pragma unroll
-        for (int jj = 0; jj < J; ++jj) {
-            float4 o0 = f4mul(r0[jj], e0), o1 = f4mul(r1[jj], e1);
-            if (PACKED && jj == kj && l == kl) { f4set(o0, kc, e0); f4set(o1, kc, e1); }   // slot k of the P row carries e
-            if (!PACKED && kEInP && jj == 0 && l < 8) {                                    // no spare slot: e rides in the LSBs (fm_device.h)
-                o0 = embed_bits4(o0, __float_as_uint(e0) >> (4 * l));
-                o1 = embed_bits4(o1, __float_as_uint(e1) >> (4 * l));
-            }
-            p_store(p0 + jj * LPN, o0);
-            p_store(p1 + jj * LPN, o1);
-        }
+        for (int jj = 0; jj < J; ++jj) { r0[jj] = f4mul(r0[jj], e0); r1[jj] = f4mul(r1[jj], e1); }
+        store_e_row<LPN, J, PACKED>(p0, r0, e0, l, k);
+        store_e_row<LPN, J, PACKED>(p1, r1, e1, l, k);
         if (l == 0) {
             reinterpret_cast<float2 *>(a.e)[j] = make_float2(e0, e1);
             st2 = fmaf(e0, e0, st2);
@@ -82,47 +74,22 @@ __global__ __launch_bounds__(kBlock) void k_pair_score(const float *yhat, const 
 
 }  // namespace
 
-int pair_finish_blocks(int Kp, int64_t n_pairs) {
-    const int lpn = Kp <= 64 ? 8 : 16;      // the forward's slot width (launch_forward)
-    const int slots = kBlock / lpn;
-    int64_t blocks = (n_pairs + slots - 1) / slots;
-    if (blocks > 8192) blocks = 8192;       // as k_apply: enough workgroups to fill the chip many times over, pairs grid-strided
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
-
 hipError_t launch_pair_finish(int Kp, const PairArgs &a, hipStream_t s, int *n_partials) {
-    const int blocks = pair_finish_blocks(Kp, a.n_pairs);
+    const int blocks = slot_blocks(Kp, a.n_pairs);
     if (n_partials) *n_partials = blocks;
     const dim3 g((unsigned)blocks), b(kBlock);
-#define FMHIP_PF(LPN_, J_)                                                                      \
-    do {                                                                                        \
-        if (a.c) {                                                                                      \
-            if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<LPN_, J_, true, true>), g, b, 0, s, a);  \
-            else hipLaunchKernelGGL((k_pair_finish<LPN_, J_, false, true>), g, b, 0, s, a);               \
-        } else if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<LPN_, J_, true, false>), g, b, 0, s, a); \
-        else hipLaunchKernelGGL((k_pair_finish<LPN_, J_, false, false>), g, b, 0, s, a);                \
-    } while (0)
-    switch (Kp) {
-        case 32: FMHIP_PF(8, 1); break;
-        case 64: FMHIP_PF(8, 2); break;
-        case 128: FMHIP_PF(16, 2); break;
-        case 256: FMHIP_PF(16, 4); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef FMHIP_PF
-    return hipGetLastError();
-}
-
-int pair_score_blocks(int64_t n_pairs) {
-    int64_t blocks = (n_pairs + kBlock - 1) / kBlock;
-    if (blocks > 1024) blocks = 1024;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
+    return for_slot_shape(Kp, [&](auto lpn, auto j) {
+        constexpr int L = decltype(lpn)::value, JJ = decltype(j)::value;
+        if (a.c) {
+            if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<L, JJ, true, true>), g, b, 0, s, a);
+            else hipLaunchKernelGGL((k_pair_finish<L, JJ, false, true>), g, b, 0, s, a);
+        } else if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<L, JJ, true, false>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((k_pair_finish<L, JJ, false, false>), g, b, 0, s, a);
+    });
 }
 
 hipError_t launch_pair_score(const float *yhat, const float *y, int32_t n_pairs, double *bsum, hipStream_t s, int *n_partials) {
-    const int blocks = pair_score_blocks(n_pairs);
+    const int blocks = grid_blocks(n_pairs, kBlock, 1024);
     if (n_partials) *n_partials = blocks;
     hipLaunchKernelGGL(k_pair_score, dim3((unsigned)blocks), dim3(kBlock), 0, s, yhat, y, n_pairs, bsum);
     return hipGetLastError();

@@ -25,7 +25,7 @@ struct RelFinishArgs {
     const float *y;                // [n_rows] the batch's labels
     float *e;                      // [n_rows] out: the residuals (nullable in residual mode)
     float *yhat;                   // [n_rows] out, nullable: the predictions
-    double *bsum;                  // [rel_finish_blocks][4] per-block {sum e, sum e^2, rows with a non-finite yhat, sum of log-losses (residual mode, logistic) else 0}
+    double *bsum;                  // [slot_blocks(Kp, n_rows)][4] per-block {sum e, sum e^2, rows with a non-finite yhat, sum of log-losses (residual mode, logistic) else 0}
     int32_t n_rows;
     int32_t pack_k;                // >= 0: packed rows (FwdArgs::pack_k)
     int32_t loss;                  // Loss (fm_kernels.h)
@@ -33,8 +33,7 @@ struct RelFinishArgs {
                                    // statistics: launch_pair_finish (fm_pairing.h) follows and forms the pairs' from them
 };
 
-// grid of launch_rel_finish = the number of per-block statistic partials it writes (<= kMaxFwdBlocks)
-int rel_finish_blocks(int Kp, int64_t n_rows);
+// n_partials: the launch's grid (slot_blocks, fm_finish.h) = the number of per-block statistic partials it writes (<= kMaxFwdBlocks)
 // residual_only: the scoring form — P is read (plain part) and never written
 hipError_t launch_rel_finish(int Kp, const RelFinishArgs &a, bool residual_only, hipStream_t s, int *n_partials);
 

@@ -1,17 +1,14 @@
 // fm_relational.hip — relational data (block-structure FM): the finish that combines the blocks' q-mode passes into a data row's
-// prediction, residual and P row (k_rel_finish, a sibling of k_weight_finish), and the deterministic segmented sum that turns
+// prediction, residual and P row (k_rel_finish: a row per slot), and the deterministic segmented sum that turns
 // the batch's P rows into a block's P_b / e_b (k_rel_gather_sum, k_rel_gather_long).  The rule and the buffers: fm_relational.h.
-// Lane geometry: fm_device.h.
-#include "fm_device.h"
-#include "fm_kernels.h"
+// Lane geometry: fm_device.h; what the finishes share: fm_finish.h.
+#include "fm_finish.h"
 #include "fm_relational.h"
 
 namespace fmhip {
 namespace {
 
-__device__ __forceinline__ float f4dot(float4 a, float4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); }
-
-// One slot of LPN lanes per data row (k_weight_finish's geometry): lane l holds floats 4*(l + jj*LPN) .. +3 of a row.  Per relation
+// One slot of LPN lanes per data row: lane l holds floats 4*(l + jj*LPN) .. +3 of a row.  Per relation
 // the slot gathers ONE contiguous q row (16 B per lane) and one prediction.  The cross term is accumulated as <q_b, Q so far>
 // BEFORE q_b joins Q — the sum over b < b' term by term, not (|Q|^2 - sum |q_b|^2) / 2, which cancels.  The plain part's q row is
 // the row's own P row, where its kFwdQ pass left it.  RESID: the scoring form (nothing written to P; the logistic residual also
@@ -19,14 +16,13 @@ __device__ __forceinline__ float f4dot(float4 a, float4 b) { return fmaf(a.x, b.
 template <int LPN, int J, bool PACKED, bool RESID>
 __global__ __launch_bounds__(kBlock) void k_rel_finish(RelFinishArgs a) {
     constexpr int KP = 4 * LPN * J;
-    constexpr int SLOTS = kBlock / LPN;
-    const int l = threadIdx.x & (LPN - 1);
-    const int slot = threadIdx.x / LPN;
-    const int kl = PACKED ? (a.pack_k >> 2) & (LPN - 1) : 0, kj = PACKED ? (a.pack_k >> 2) / LPN : 0, kc = a.pack_k & 3;
+    const SlotLoop<LPN> sl;
+    const int l = sl.l;
+    const PackPos<LPN, PACKED> k(a.pack_k);
     const bool logistic = a.loss == kLossLogistic;
     const float w0 = *a.w0;
     float st1 = 0.f, st2 = 0.f, stbad = 0.f, stl = 0.f;
-    for (int r = blockIdx.x * SLOTS + slot; r < a.n_rows; r += gridDim.x * SLOTS) {
+    for (int r = sl.first; r < a.n_rows; r += sl.stride) {
         float4 Q[J];
 #pragma unroll
         for (int jj = 0; jj < J; ++jj) Q[jj] = f4zero();
@@ -69,12 +65,8 @@ __global__ __launch_bounds__(kBlock) void k_rel_finish(RelFinishArgs a) {
         }
         if (!RESID) {
 #pragma unroll
-            for (int jj = 0; jj < J; ++jj) {
-                float4 o = f4mul(Q[jj], e);
-                if (PACKED && jj == kj && l == kl) f4set(o, kc, e);                                            // slot k of the P row carries e
-                if (!PACKED && kEInP && jj == 0 && l < 8) o = embed_bits4(o, __float_as_uint(e) >> (4 * l));   // no spare slot: e rides in the LSBs (fm_device.h)
-                p_store(p + jj * LPN, o);
-            }
+            for (int jj = 0; jj < J; ++jj) Q[jj] = f4mul(Q[jj], e);
+            store_e_row<LPN, J, PACKED>(p, Q, e, l, k);
         }
         if (l == 0) {
             if (a.e) a.e[r] = e;
@@ -89,22 +81,6 @@ __global__ __launch_bounds__(kBlock) void k_rel_finish(RelFinishArgs a) {
     double v[4] = {st1, st2, stbad, stl};
     const int where[4] = {0, 1, 2, 3};
     pair_block_sums<4>(a.bsum, v, where);
-}
-
-// a finished sum into row `row` of a table in the P row format: e in the packed slot, or embedded in the row's low bits
-template <int LPN, int J, bool PACKED>
-__device__ __forceinline__ void rel_store_row(float *table, float *etab, int32_t row, int l, float4 (&acc)[J], float es, int32_t pack_k) {
-    constexpr int KP = 4 * LPN * J;
-    const int kl = PACKED ? (pack_k >> 2) & (LPN - 1) : 0, kj = PACKED ? (pack_k >> 2) / LPN : 0, kc = pack_k & 3;
-    float4 *dst = reinterpret_cast<float4 *>(table + (size_t)row * KP) + l;
-#pragma unroll
-    for (int jj = 0; jj < J; ++jj) {
-        float4 o = acc[jj];
-        if (PACKED && jj == kj && l == kl) f4set(o, kc, es);
-        if (!PACKED && kEInP && jj == 0 && l < 8) o = embed_bits4(o, __float_as_uint(es) >> (4 * l));
-        p_store(dst + jj * LPN, o);
-    }
-    if (l == 0) etab[row] = es;
 }
 
 // rows [beg, end) of `list` (row ids into `table`), added in list order; four rows' loads in flight, added in order
@@ -147,10 +123,10 @@ __device__ __forceinline__ void rel_sum_rows(const float *table, const float *et
 template <int LPN, int J, bool PACKED>
 __global__ __launch_bounds__(kBlock) void k_rel_gather_sum(RelGatherArgs a) {
     constexpr int KP = 4 * LPN * J;
-    constexpr int SLOTS = kBlock / LPN;
-    const int l = threadIdx.x & (LPN - 1);
-    const int slot = threadIdx.x / LPN;
-    for (int w = blockIdx.x * SLOTS + slot; w < a.n_work; w += gridDim.x * SLOTS) {
+    const SlotLoop<LPN> sl;
+    const int l = sl.l;
+    const PackPos<LPN, PACKED> k(a.pack_k);
+    for (int w = sl.first; w < a.n_work; w += sl.stride) {
         const int32_t t = a.wt[w], beg = a.wbeg[w], dst = a.wdst[w];
         const int32_t end = min(beg + kRelSumCut, a.tptr[t + 1]);
         float4 acc[J];
@@ -158,8 +134,9 @@ __global__ __launch_bounds__(kBlock) void k_rel_gather_sum(RelGatherArgs a) {
         for (int jj = 0; jj < J; ++jj) acc[jj] = f4zero();
         float es = 0.f;
         rel_sum_rows<LPN, J>(a.P, a.e, a.trow, beg, end, l, acc, es);
-        if (dst >= 0) {
-            rel_store_row<LPN, J, PACKED>(a.Pb, a.eb, dst, l, acc, es, a.pack_k);
+        if (dst >= 0) {     // a finished sum: a row of P_b in the P row format, e_b beside it
+            store_e_row<LPN, J, PACKED>(reinterpret_cast<float4 *>(a.Pb + (size_t)dst * KP) + l, acc, es, l, k);
+            if (l == 0) a.eb[dst] = es;
         } else {
             float4 *o = reinterpret_cast<float4 *>(a.part + (size_t)(-1 - dst) * KP) + l;
 #pragma unroll
@@ -172,76 +149,49 @@ __global__ __launch_bounds__(kBlock) void k_rel_gather_sum(RelGatherArgs a) {
 // One slot per long list: its chunks' partial rows, added in chunk order, into the block row.
 template <int LPN, int J, bool PACKED>
 __global__ __launch_bounds__(kBlock) void k_rel_gather_long(RelGatherArgs a) {
-    constexpr int SLOTS = kBlock / LPN;
-    const int l = threadIdx.x & (LPN - 1);
-    const int slot = threadIdx.x / LPN;
-    for (int i = blockIdx.x * SLOTS + slot; i < a.n_long; i += gridDim.x * SLOTS) {
-        const int32_t first = a.lfirst[i];
+    constexpr int KP = 4 * LPN * J;
+    const SlotLoop<LPN> sl;
+    const int l = sl.l;
+    const PackPos<LPN, PACKED> k(a.pack_k);
+    for (int i = sl.first; i < a.n_long; i += sl.stride) {
+        const int32_t first = a.lfirst[i], dst = a.tj[a.lt[i]];
         float4 acc[J];
 #pragma unroll
         for (int jj = 0; jj < J; ++jj) acc[jj] = f4zero();
         float es = 0.f;
         rel_sum_rows<LPN, J>(a.part, a.part_e, nullptr, first, first + a.lcount[i], l, acc, es);
-        rel_store_row<LPN, J, PACKED>(a.Pb, a.eb, a.tj[a.lt[i]], l, acc, es, a.pack_k);
+        store_e_row<LPN, J, PACKED>(reinterpret_cast<float4 *>(a.Pb + (size_t)dst * KP) + l, acc, es, l, k);
+        if (l == 0) a.eb[dst] = es;
     }
-}
-
-int slot_blocks(int Kp, int64_t items) {
-    const int lpn = Kp <= 64 ? 8 : 16;      // the forward's slot width (launch_forward)
-    const int slots = kBlock / lpn;
-    int64_t blocks = (items + slots - 1) / slots;
-    if (blocks > 8192) blocks = 8192;       // as k_weight_finish: enough workgroups to fill the chip many times over, items grid-strided
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
 }
 
 }  // namespace
 
-int rel_finish_blocks(int Kp, int64_t n_rows) { return slot_blocks(Kp, n_rows); }
-
 hipError_t launch_rel_finish(int Kp, const RelFinishArgs &a, bool residual_only, hipStream_t s, int *n_partials) {
-    const int blocks = rel_finish_blocks(Kp, a.n_rows);
+    const int blocks = slot_blocks(Kp, a.n_rows);
     if (n_partials) *n_partials = blocks;
     const dim3 g((unsigned)blocks), b(kBlock);
-#define FMHIP_RF(LPN_, J_)                                                                                          \
-    do {                                                                                                            \
-        if (residual_only) hipLaunchKernelGGL((k_rel_finish<LPN_, J_, false, true>), g, b, 0, s, a);                \
-        else if (a.pack_k >= 0) hipLaunchKernelGGL((k_rel_finish<LPN_, J_, true, false>), g, b, 0, s, a);           \
-        else hipLaunchKernelGGL((k_rel_finish<LPN_, J_, false, false>), g, b, 0, s, a);                             \
-    } while (0)
-    switch (Kp) {       // the instances of launch_weight_finish
-        case 32: FMHIP_RF(8, 1); break;
-        case 64: FMHIP_RF(8, 2); break;
-        case 128: FMHIP_RF(16, 2); break;
-        case 256: FMHIP_RF(16, 4); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef FMHIP_RF
-    return hipGetLastError();
+    return for_slot_shape(Kp, [&](auto lpn, auto j) {
+        constexpr int L = decltype(lpn)::value, JJ = decltype(j)::value;
+        if (residual_only) hipLaunchKernelGGL((k_rel_finish<L, JJ, false, true>), g, b, 0, s, a);
+        else if (a.pack_k >= 0) hipLaunchKernelGGL((k_rel_finish<L, JJ, true, false>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((k_rel_finish<L, JJ, false, false>), g, b, 0, s, a);
+    });
 }
 
 hipError_t launch_rel_gather_sum(int Kp, const RelGatherArgs &a, hipStream_t s) {
     if (a.n_work <= 0) return hipSuccess;
     const dim3 g((unsigned)slot_blocks(Kp, a.n_work)), gl((unsigned)slot_blocks(Kp, a.n_long)), b(kBlock);
-#define FMHIP_RG(LPN_, J_)                                                                                          \
-    do {                                                                                                            \
-        if (a.pack_k >= 0) {                                                                                        \
-            hipLaunchKernelGGL((k_rel_gather_sum<LPN_, J_, true>), g, b, 0, s, a);                                  \
-            if (a.n_long > 0) hipLaunchKernelGGL((k_rel_gather_long<LPN_, J_, true>), gl, b, 0, s, a);              \
-        } else {                                                                                                    \
-            hipLaunchKernelGGL((k_rel_gather_sum<LPN_, J_, false>), g, b, 0, s, a);                                 \
-            if (a.n_long > 0) hipLaunchKernelGGL((k_rel_gather_long<LPN_, J_, false>), gl, b, 0, s, a);             \
-        }                                                                                                           \
-    } while (0)
-    switch (Kp) {
-        case 32: FMHIP_RG(8, 1); break;
-        case 64: FMHIP_RG(8, 2); break;
-        case 128: FMHIP_RG(16, 2); break;
-        case 256: FMHIP_RG(16, 4); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef FMHIP_RG
-    return hipGetLastError();
+    return for_slot_shape(Kp, [&](auto lpn, auto j) {
+        constexpr int L = decltype(lpn)::value, JJ = decltype(j)::value;
+        if (a.pack_k >= 0) {
+            hipLaunchKernelGGL((k_rel_gather_sum<L, JJ, true>), g, b, 0, s, a);
+            if (a.n_long > 0) hipLaunchKernelGGL((k_rel_gather_long<L, JJ, true>), gl, b, 0, s, a);
+        } else {
+            hipLaunchKernelGGL((k_rel_gather_sum<L, JJ, false>), g, b, 0, s, a);
+            if (a.n_long > 0) hipLaunchKernelGGL((k_rel_gather_long<L, JJ, false>), gl, b, 0, s, a);
+        }
+    });
 }
 
 }  // namespace fmhip

@@ -21,14 +21,13 @@ struct WeightArgs {
     const float *y;      // [n_rows] the batch's labels
     const float *c;      // [n_rows] the batch's weights (finite, >= 0: validated when the dataset was built)
     float *e;            // [n_rows] out: c_r * e_r(loss); +0 for a row of weight 0
-    double *bsum;        // [weight_finish_blocks][4] per-block {sum e, sum e^2, rows with a non-finite yhat, 0}
+    double *bsum;        // [slot_blocks(Kp, n_rows)][4] per-block {sum e, sum e^2, rows with a non-finite yhat, 0}
     int32_t n_rows;
     int32_t pack_k;      // >= 0: packed rows (FwdArgs::pack_k)
     int32_t loss;        // Loss (fm_kernels.h)
 };
 
-// grid of launch_weight_finish = the number of per-block statistic partials it writes (<= kMaxFwdBlocks)
-int weight_finish_blocks(int Kp, int64_t n_rows);
+// n_partials: the launch's grid (slot_blocks, fm_finish.h) = the number of per-block statistic partials it writes (<= kMaxFwdBlocks)
 hipError_t launch_weight_finish(int Kp, const WeightArgs &a, hipStream_t s, int *n_partials);
 
 // Weighted scores (fmhip_weighted_scores) behind a residual-mode forward that left the predictions in yhat: per-block partials in

@@ -1,8 +1,7 @@
 // fm_weights.hip — per-row example weights: the residual of a WEIGHTED row, formed after the kFwdQ forward has left the row's
-// sv*q in P and its prediction beside it (k_weight_finish, the row-per-slot sibling of k_pair_finish), and the weighted scores
-// of a dataset (k_weighted_score).  The rule and the buffers: fm_weights.h.  Lane geometry: fm_device.h.
-#include "fm_device.h"
-#include "fm_kernels.h"
+// sv*q in P and its prediction beside it (k_weight_finish: a row per slot), and the weighted scores of a dataset
+// (k_weighted_score).  The rule and the buffers: fm_weights.h.  Lane geometry: fm_device.h; what the finishes share: fm_finish.h.
+#include "fm_finish.h"
 #include "fm_weights.h"
 
 namespace fmhip {
@@ -14,13 +13,12 @@ namespace {
 template <int LPN, int J, bool PACKED>
 __global__ __launch_bounds__(kBlock) void k_weight_finish(WeightArgs a) {
     constexpr int KP = 4 * LPN * J;
-    constexpr int SLOTS = kBlock / LPN;
-    const int l = threadIdx.x & (LPN - 1);
-    const int slot = threadIdx.x / LPN;
-    const int kl = PACKED ? (a.pack_k >> 2) & (LPN - 1) : 0, kj = PACKED ? (a.pack_k >> 2) / LPN : 0, kc = a.pack_k & 3;
+    const SlotLoop<LPN> sl;
+    const int l = sl.l;
+    const PackPos<LPN, PACKED> k(a.pack_k);
     const bool logistic = a.loss == kLossLogistic;
     float st1 = 0.f, st2 = 0.f, stbad = 0.f;
-    for (int r = blockIdx.x * SLOTS + slot; r < a.n_rows; r += gridDim.x * SLOTS) {
+    for (int r = sl.first; r < a.n_rows; r += sl.stride) {
         float4 *p = reinterpret_cast<float4 *>(a.P + (size_t)r * KP) + l;
         float4 q[J];
 #pragma unroll
@@ -30,12 +28,8 @@ __global__ __launch_bounds__(kBlock) void k_weight_finish(WeightArgs a) {
         // the loss's residual as row_finish (fm_forward.hip) forms it, then the weight
         const float e = weighted_residual(a.c[r], logistic ? pair_sigma_residual(yh, a.y[r] > 0.f, z) : yh - a.y[r]);
 #pragma unroll
-        for (int jj = 0; jj < J; ++jj) {
-            float4 o = f4mul(q[jj], e);
-            if (PACKED && jj == kj && l == kl) f4set(o, kc, e);                                            // slot k of the P row carries e
-            if (!PACKED && kEInP && jj == 0 && l < 8) o = embed_bits4(o, __float_as_uint(e) >> (4 * l));   // no spare slot: e rides in the LSBs (fm_device.h)
-            p_store(p + jj * LPN, o);
-        }
+        for (int jj = 0; jj < J; ++jj) q[jj] = f4mul(q[jj], e);
+        store_e_row<LPN, J, PACKED>(p, q, e, l, k);
         if (l == 0) {
             a.e[r] = e;
             st1 += e;
@@ -68,41 +62,18 @@ __global__ __launch_bounds__(kBlock) void k_weighted_score(const float *yhat, co
 
 }  // namespace
 
-int weight_finish_blocks(int Kp, int64_t n_rows) {
-    const int lpn = Kp <= 64 ? 8 : 16;      // the forward's slot width (launch_forward)
-    const int slots = kBlock / lpn;
-    int64_t blocks = (n_rows + slots - 1) / slots;
-    if (blocks > 8192) blocks = 8192;       // as k_pair_finish: enough workgroups to fill the chip many times over, rows grid-strided
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
-
 hipError_t launch_weight_finish(int Kp, const WeightArgs &a, hipStream_t s, int *n_partials) {
-    const int blocks = weight_finish_blocks(Kp, a.n_rows);
+    const int blocks = slot_blocks(Kp, a.n_rows);
     if (n_partials) *n_partials = blocks;
     const dim3 g((unsigned)blocks), b(kBlock);
-#define FMHIP_WF(LPN_, J_)                                                                        \
-    do {                                                                                          \
-        if (a.pack_k >= 0) hipLaunchKernelGGL((k_weight_finish<LPN_, J_, true>), g, b, 0, s, a);  \
-        else hipLaunchKernelGGL((k_weight_finish<LPN_, J_, false>), g, b, 0, s, a);               \
-    } while (0)
-    switch (Kp) {       // the instances of launch_pair_finish
-        case 32: FMHIP_WF(8, 1); break;
-        case 64: FMHIP_WF(8, 2); break;
-        case 128: FMHIP_WF(16, 2); break;
-        case 256: FMHIP_WF(16, 4); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef FMHIP_WF
-    return hipGetLastError();
+    return for_slot_shape(Kp, [&](auto lpn, auto j) {
+        constexpr int L = decltype(lpn)::value, JJ = decltype(j)::value;
+        if (a.pack_k >= 0) hipLaunchKernelGGL((k_weight_finish<L, JJ, true>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((k_weight_finish<L, JJ, false>), g, b, 0, s, a);
+    });
 }
 
-int weighted_score_blocks(int64_t n_rows) {
-    int64_t blocks = (n_rows + kBlock - 1) / kBlock;
-    if (blocks > 1024) blocks = 1024;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
+int weighted_score_blocks(int64_t n_rows) { return grid_blocks(n_rows, kBlock, 1024); }
 
 hipError_t launch_weighted_score(const float *yhat, const float *y, const float *c, int32_t n_rows, double *bsum, hipStream_t s, int *n_partials) {
     const int blocks = weighted_score_blocks(n_rows);

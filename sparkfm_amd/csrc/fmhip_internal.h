@@ -8,6 +8,8 @@
 #include "../../include/fmhip_relational.h"     // (fmhip_relational_t: the handle's state is declared below)
 #include "../../include/fmhip_bpr.h"            // (fmhip_bpr_t: likewise)
 #include "fm_kernels.h"
+#include "fm_pairing.h"      // (PairArgs, RelFinishArgs: the builders the step and the scoring pass share are declared below)
+#include "fm_relational.h"
 #include "fmhip_host.h"   // the pure host arithmetic (shards, relabelling, batch metadata, band plan, ALS levels, the dp plan's cuts and shares)
 
 #include <cmath>
@@ -443,6 +445,8 @@ int check_even_batches(fmhip_dataset_t d);                // pairs (rows 2j, 2j+
 int check_batch(fmhip_dataset_t d, int64_t batch);
 // the pieces of one mini-batch step, all asynchronous on m->stream
 int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b);
+// the pairs' finish over the model's workspace (P, yhat -> P, e, bsum): `rows` rows whose labels start at y and whose weights at c (NULL: none)
+PairArgs pair_args(fmhip_model_t m, const float *y, const float *c, int64_t rows);
 // the step size and the regularisation of one SGD step (the C entry points take them one by one)
 struct Sgd {
     double eta, reg0, regw, regv;
@@ -501,6 +505,18 @@ int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, d
 // the beginning of a step alone (the BPR trainer's adaptive sampler reads what it leaves): scales folded, workspace sized, every
 // block's kFwdQ forward into its relation's Q / yq, asynchronous on the model's stream
 int rel_block_forwards(fmhip_model_t m, fmhip_relational_t R);
+// Where a relational finish works: per relation the block's q rows and predictions, and the data rows' P / e / yhat / partials — the
+// handle's and the model's workspace in a step, buffers of its own in a scoring pass.  yhat holds the plain part's predictions on
+// the way in and, where the finish writes them, the rows' on the way out (a row's is read before it is written)
+struct RelBufs {
+    float *Q[FMHIP_RELATIONS_MAX], *yq[FMHIP_RELATIONS_MAX];
+    float *P, *e, *yhat;
+    double *bsum;
+};
+// every block's kFwdQ forward, over the whole block, into w.Q / w.yq on stream s
+int rel_q_forwards(fmhip_model_t m, fmhip_relational_t R, const RelBufs &w, hipStream_t s);
+// the finish of the data rows B over w, in its scoring form's layout: the predictions written, no q_only
+RelFinishArgs rel_finish_args(fmhip_model_t m, fmhip_relational_t R, const RelBufs &w, const fmhip_relational::Batch &B, int loss);
 // ---- fmhip_score.hip: fmhip_pair_logloss over the rows of a relational dataset without a plain part (the caller holds the model's lock shared)
 int rel_pair_score(fmhip_model_t m, fmhip_relational_t R, double *logloss, double *concordance, fmhip_stats *stats);
 // the four leading numbers of a statistics block {sum e, sum e^2, rows, rows with a non-finite prediction} (the packed gradient's

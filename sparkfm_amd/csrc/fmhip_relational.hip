@@ -7,8 +7,6 @@
 // The scoring calls are in fmhip_score.hip (they work in a ScorePass); the kernels in fm_relational.hip; the host arithmetic
 // (mapping check, disjointness of the parts' features, the inverse map's counting sort) in fmhip_host.cpp.
 #include "fmhip_internal.h"
-#include "fm_pairing.h"
-#include "fm_relational.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -83,40 +81,68 @@ int check_rel_model(fmhip_model_t m, fmhip_relational_t R) {
     return set_device(m->device);
 }
 
+int rel_q_forwards(fmhip_model_t m, fmhip_relational_t R, const RelBufs &w, hipStream_t s) {
+    for (size_t i = 0; i < R->rels.size(); ++i) {
+        fmhip_dataset_t blk = R->rels[i]->block;
+        const FwdArgs a = fwd_args_out(m, blk, blk->batches[0], w.Q[i], nullptr, nullptr, w.yq[i], kLossSquared);
+        HIP_TRY(launch_forward(m->Kp, kFwdQ, a, s, nullptr));
+    }
+    return FMHIP_OK;
+}
+
+RelFinishArgs rel_finish_args(fmhip_model_t m, fmhip_relational_t R, const RelBufs &w, const fmhip_relational::Batch &B, int loss) {
+    RelFinishArgs fa{};
+    fa.m = (int32_t)R->rels.size();
+    for (int i = 0; i < fa.m; ++i) {
+        fa.Q[i] = w.Q[i];
+        fa.yq[i] = w.yq[i];
+        fa.map[i] = R->rels[(size_t)i]->map.p + B.row0;
+    }
+    fa.has_plain = R->plain ? 1 : 0;
+    fa.w0 = m->w0.p;
+    fa.P = w.P;
+    fa.yplain = w.yhat;
+    fa.y = R->y.p + B.row0;
+    fa.e = w.e;
+    fa.yhat = w.yhat;
+    fa.bsum = w.bsum;
+    fa.n_rows = (int32_t)B.rows;
+    fa.pack_k = m->pack_k();
+    fa.loss = loss;
+    return fa;
+}
+
+// a step's buffers: the handle's Q / yq per relation (ensure_rel_workspace has sized them), the model's workspace
+static RelBufs rel_step_bufs(fmhip_model_t m, fmhip_relational_t R) {
+    RelBufs w{};
+    for (size_t i = 0; i < R->rels.size(); ++i) {
+        w.Q[i] = R->rels[i]->Q.p;
+        w.yq[i] = R->rels[i]->yq.p;
+    }
+    w.P = m->P.p;
+    w.e = m->e.p;
+    w.yhat = m->yhat.p;
+    w.bsum = m->bsum.p;
+    return w;
+}
+
 // what a step begins with, on its own: the scales folded, the handle's workspace sized, then every block's kFwdQ forward into the
 // relation's Q / yq on the model's stream (behind the last step that used the workspace)
 int rel_block_forwards(fmhip_model_t m, fmhip_relational_t R) {
-    TRY(fold_scales(m));
+    TRY(fold_scales(m));                     // the dense update only: the tables are at scale 1 from here on
     TRY(ensure_rel_workspace(m, R));
+    // the workspace is the handle's: behind the last step that used it, if that one was queued on another stream (another model)
     if (R->busy_set && R->busy_stream != m->stream) HIP_TRY(hipStreamWaitEvent(m->stream, R->busy, 0));
-    for (auto &relp : R->rels) {
-        fmhip_relational::Relation &rel = *relp;
-        const FwdArgs a = fwd_args_out(m, rel.block, rel.block->batches[0], rel.Q.p, nullptr, nullptr, rel.yq.p, kLossSquared);
-        HIP_TRY(launch_forward(m->Kp, kFwdQ, a, m->stream, nullptr));
-    }
-    return FMHIP_OK;
+    return rel_q_forwards(m, R, rel_step_bufs(m, R), m->stream);
 }
 
 // one relational step of batch b, asynchronous on the model's stream; acc (nullable): the epoch's fp64 accumulators
 int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs) {
     const fmhip_relational::Batch &B = R->batches[(size_t)b];
-    TRY(fold_scales(m));                     // the dense update only: the tables are at scale 1 from here on
-    TRY(ensure_rel_workspace(m, R));
-    // the workspace is the handle's: behind the last step that used it, if that one was queued on another stream (another model)
-    if (R->busy_set && R->busy_stream != m->stream) HIP_TRY(hipStreamWaitEvent(m->stream, R->busy, 0));
-    if (m->grad_dirty) {
+    TRY(rel_block_forwards(m, R));           // every block's q-mode pass, over the whole block
+    if (m->grad_dirty) {                     // (the forwards do not touch the gradient)
         HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
         m->grad_dirty = false;
-    }
-    RelFinishArgs fa{};
-    fa.m = (int32_t)R->rels.size();
-    for (int i = 0; i < fa.m; ++i) {         // every block's q-mode pass, over the whole block
-        fmhip_relational::Relation &rel = *R->rels[(size_t)i];
-        const FwdArgs a = fwd_args_out(m, rel.block, rel.block->batches[0], rel.Q.p, nullptr, nullptr, rel.yq.p, kLossSquared);
-        HIP_TRY(launch_forward(m->Kp, kFwdQ, a, m->stream, nullptr));
-        fa.Q[i] = rel.Q.p;
-        fa.yq[i] = rel.yq.p;
-        fa.map[i] = rel.map.p + B.row0;
     }
     int64_t nnz = R->block_nnz;
     if (R->plain) {
@@ -125,33 +151,14 @@ int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, d
         HIP_TRY(launch_forward(m->Kp, kFwdQ, a, m->stream, nullptr));
         nnz += bm.nnz_total;
     }
-    fa.has_plain = R->plain ? 1 : 0;
-    fa.w0 = m->w0.p;
-    fa.P = m->P.p;
-    fa.yplain = m->yhat.p;
-    fa.y = R->y.p + B.row0;
-    fa.e = m->e.p;
-    fa.yhat = pairs ? m->yhat.p : nullptr;
-    fa.bsum = m->bsum.p;
-    fa.n_rows = (int32_t)B.rows;
-    fa.pack_k = m->pack_k();
-    fa.loss = m->rule.loss;
+    RelFinishArgs fa = rel_finish_args(m, R, rel_step_bufs(m, R), B, m->rule.loss);
+    if (!pairs) fa.yhat = nullptr;           // (only the pairs' finish reads the rows' predictions)
     fa.q_only = pairs ? 1 : 0;
     HIP_TRY(launch_rel_finish(m->Kp, fa, false, m->stream, &m->fwd_parts));
     if (pairs) {
         // the BPR trainer: the finish left Q_r in P and yhat_r beside it, as the flat paired step's kFwdQ forward does; the pairs'
         // finish (fm_pairing.hip) turns them into P_r = Q_r e_r, e and the statistics partials (its own block count)
-        PairArgs pa{};
-        pa.P = m->P.p;
-        pa.yhat = m->yhat.p;
-        pa.y = R->y.p + B.row0;          // (batches are even: 8-byte aligned)
-        pa.e = m->e.p;
-        pa.bsum = m->bsum.p;
-        pa.n_pairs = (int32_t)(B.rows / 2);
-        pa.pack_k = m->pack_k();
-        pa.loss = m->rule.loss;
-        pa.c = nullptr;
-        HIP_TRY(launch_pair_finish(m->Kp, pa, m->stream, &m->fwd_parts));
+        HIP_TRY(launch_pair_finish(m->Kp, pair_args(m, R->y.p + B.row0, nullptr, B.rows), m->stream, &m->fwd_parts));
     }
     m->grad_dirty = true;
     m->last_nnz = nnz;

@@ -738,38 +738,26 @@ struct RelScoreBufs {       // (declared before the pass: freed after it has dra
 // pair_sums (the BPR trainer; no plain part, even batches): the rows 2j / 2j+1 are scored as pairs — k_pair_score's partials over the
 // predictions the finish left, as fmhip_pair_logloss — and [0] = the concordant pairs, [1] = the sum of the pairs' log-losses
 int rel_score_pass(fmhip_model_t m, fmhip_relational_t R, double *yhat, fmhip_stats *st, double *logloss, double *pair_sums = nullptr) {
-    if (!m || !R) return fail(FMHIP_ERR_INVALID, "model or relational dataset is NULL");
-    if (m->device != R->device) return fail(FMHIP_ERR_INVALID, "model on device %d, relational dataset on device %d", m->device, R->device);
-    if (R->dimension > m->n)
-        return fail(FMHIP_ERR_SHAPE, "relational dataset has feature index %lld but the model has num_attribute = %lld", (long long)R->dimension,
-                    (long long)m->n);
-    TRY(set_device(m->device));
+    TRY(check_rel_model(m, R));
     RelScoreBufs bufs;
     ScorePass pass(m);
     TRY(pass.begin({R->max_rows, R->max_rows, R->plain ? R->max_rows : -1, true}));
     ScoreCtx &cx = pass.cx();
-    RelFinishArgs fa{};
-    fa.m = (int32_t)R->rels.size();
-    for (int i = 0; i < fa.m; ++i) {
-        fmhip_dataset_t blk = R->rels[(size_t)i]->block;
+    RelBufs w{};
+    for (size_t i = 0; i < R->rels.size(); ++i) {
+        fmhip_dataset_t blk = R->rels[i]->block;
         bufs.Q.emplace_back(new DevBuf<float>());
         bufs.yq.emplace_back(new DevBuf<float>());
         TRY(bufs.Q.back()->alloc((size_t)blk->n_rows * m->Kp));
         TRY(bufs.yq.back()->alloc((size_t)blk->n_rows));
-        const FwdArgs a = fwd_args_out(m, blk, blk->batches[0], bufs.Q.back()->p, nullptr, nullptr, bufs.yq.back()->p, kLossSquared);
-        HIP_TRY(launch_forward(m->Kp, kFwdQ, a, cx.s, nullptr));
-        fa.Q[i] = bufs.Q.back()->p;
-        fa.yq[i] = bufs.yq.back()->p;
+        w.Q[i] = bufs.Q.back()->p;
+        w.yq[i] = bufs.yq.back()->p;
     }
-    fa.has_plain = R->plain ? 1 : 0;
-    fa.w0 = m->w0.p;
-    fa.P = R->plain ? cx.P.p : nullptr;
-    fa.yplain = cx.yhat.p;              // (read per row before the row's prediction is written over it)
-    fa.e = cx.e.p;
-    fa.yhat = cx.yhat.p;
-    fa.bsum = cx.bsum.p;
-    fa.pack_k = m->pack_k();
-    fa.loss = logloss ? kLossLogistic : kLossSquared;
+    w.P = R->plain ? cx.P.p : nullptr;
+    w.e = cx.e.p;
+    w.yhat = cx.yhat.p;
+    w.bsum = cx.bsum.p;
+    TRY(rel_q_forwards(m, R, w, cx.s));
     std::vector<float> hbuf;
     for (size_t b = 0; b < R->batches.size(); ++b) {
         const fmhip_relational::Batch &B = R->batches[b];
@@ -777,9 +765,7 @@ int rel_score_pass(fmhip_model_t m, fmhip_relational_t R, double *yhat, fmhip_st
             const FwdArgs a = fwd_args_out(m, R->plain, R->plain->batches[b], cx.P.p, nullptr, nullptr, cx.yhat.p, kLossSquared);
             HIP_TRY(launch_forward(m->Kp, kFwdQ, a, cx.s, nullptr));
         }
-        for (int i = 0; i < fa.m; ++i) fa.map[i] = R->rels[(size_t)i]->map.p + B.row0;
-        fa.y = R->y.p + B.row0;
-        fa.n_rows = (int32_t)B.rows;
+        const RelFinishArgs fa = rel_finish_args(m, R, w, B, logloss ? kLossLogistic : kLossSquared);
         int parts = 0;
         HIP_TRY(launch_rel_finish(m->Kp, fa, true, cx.s, &parts));
         if (pair_sums) HIP_TRY(launch_pair_score(cx.yhat.p, R->y.p + B.row0, (int32_t)(B.rows / 2), cx.bsum.p, cx.s, &parts));

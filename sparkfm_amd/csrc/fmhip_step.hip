@@ -5,7 +5,6 @@
 // the fixup launch, inside the column walk) and the lazily decayed tables' bookkeeping.  Everything here is asynchronous on the
 // model's stream; the arithmetic lives in fm_forward.hip / fm_backward.hip / fm_apply.hip.
 #include "fmhip_internal.h"
-#include "fm_pairing.h"
 #include "fm_weights.h"
 
 #include <algorithm>
@@ -246,6 +245,20 @@ static ApplyArgs apply_args(fmhip_model_t m, const Sgd &s, const float *rows) {
     return a;
 }
 
+PairArgs pair_args(fmhip_model_t m, const float *y, const float *c, int64_t rows) {
+    PairArgs pa{};
+    pa.P = m->P.p;
+    pa.yhat = m->yhat.p;
+    pa.y = y;                // (batches are even: 8-byte aligned)
+    pa.e = m->e.p;
+    pa.bsum = m->bsum.p;
+    pa.n_pairs = (int32_t)(rows / 2);
+    pa.pack_k = m->pack_k();
+    pa.loss = m->rule.loss;
+    pa.c = c;
+    return pa;
+}
+
 // forward of one batch: P = e*q, e, per-block statistics partials
 int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
     const BatchMeta &bm = d->batches[(size_t)b];
@@ -266,16 +279,7 @@ int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
         const FwdArgs a = fwd_args_out(m, d, bm, m->P.p, nullptr, nullptr, m->yhat.p, kLossSquared);
         HIP_TRY(launch_forward(m->Kp, kFwdQ, a, m->stream, nullptr));
         if (m->rule.paired()) {
-            PairArgs pa{};
-            pa.P = m->P.p;
-            pa.yhat = m->yhat.p;
-            pa.y = d->y.p + bm.row0;
-            pa.e = m->e.p;
-            pa.bsum = m->bsum.p;
-            pa.n_pairs = (int32_t)(bm.rows / 2);
-            pa.pack_k = m->pack_k();
-            pa.loss = m->rule.loss;
-            pa.c = d->weighted ? d->c.p + bm.row0 : nullptr;
+            const PairArgs pa = pair_args(m, d->y.p + bm.row0, d->weighted ? d->c.p + bm.row0 : nullptr, bm.rows);
             HIP_TRY(launch_pair_finish(m->Kp, pa, m->stream, &m->fwd_parts));
         } else {
             WeightArgs wa{};
