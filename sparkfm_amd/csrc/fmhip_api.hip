@@ -555,7 +555,7 @@ int fmhip_batch_grad(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, double *
     HIP_TRY(hipMemcpyAsync(hV.data(), m->V.p, hV.size() * sizeof(float), hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
-    m->grad_dirty = false;
+    m->step.grad_consumed();
     const float *sc = hG.data(), *Gw = sc + kGradHead, *Gb = Gw + m->n1p, *GV = sc + m->head_floats();
     for (int64_t i = 0; i < m->n1; ++i) {
         if (gw) gw[i] = table_w(m, GV, Gw, i);
@@ -597,7 +597,7 @@ int fmhip_grad_bind(fmhip_model_t m, void *device_ptr) {
     if (device_ptr && (reinterpret_cast<uintptr_t>(device_ptr) & 15u))
         return fail(FMHIP_ERR_INVALID, "gradient buffer must be 16-byte aligned");
     m->grad = device_ptr ? static_cast<float *>(device_ptr) : m->grad_own.p;
-    m->grad_dirty = false;
+    m->step.grad_consumed();      // (taken as clean: the buffer itself is not touched)
     return FMHIP_OK;
 }
 
@@ -635,25 +635,11 @@ int fmhip_step_backward(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, int64
     TRY(check_train(m, d));
     TRY(check_batch(d, batch));
     if (feat_lo < 0 || feat_hi < feat_lo) return fail(FMHIP_ERR_INVALID, "bad feature interval [%lld, %lld)", (long long)feat_lo, (long long)feat_hi);
-    // intervals tile [0, n+1) in DESCENDING order (a range straddling two intervals is walked with the upper one, whose
-    // partials the lower one's fixup then reads) or, from feature 0 up, in ASCENDING order (the mirror rule); the first call
-    // after the forward says which: it ends at n+1 or starts at 0
-    if (m->bw_next_hi < 0) return fail(FMHIP_ERR_INVALID, "fmhip_step_backward without fmhip_step_forward");
-    if (finish && feat_lo != 0) return fail(FMHIP_ERR_INVALID, "finish = 1 belongs to the interval that starts at feature 0");
-    if (m->bw_next_hi == INT64_MAX) m->bw_up = feat_hi < m->n1 && feat_lo == 0;
-    if (m->bw_up) {
-        const int64_t want = m->bw_next_hi == INT64_MAX ? 0 : m->bw_next_hi;
-        if (feat_lo != want)
-            return fail(FMHIP_ERR_INVALID, "feature intervals must tile [0, n+1) in ascending order (expected lo = %lld, got %lld)", (long long)want, (long long)feat_lo);
-        TRY(step_backward(m, d, batch, feat_lo, feat_hi, finish != 0, nullptr, nullptr, kOwnUpper));
-        m->bw_next_hi = feat_hi >= m->n1 ? -1 : feat_hi;
-        return FMHIP_OK;
-    }
-    if (m->bw_next_hi == INT64_MAX ? feat_hi < m->n1 : feat_hi != m->bw_next_hi)
-        return fail(FMHIP_ERR_INVALID, "feature intervals must tile [0, n+1) in descending order (expected hi = %lld, got %lld), or start at feature 0 and ascend",
-                    (long long)(m->bw_next_hi == INT64_MAX ? m->n1 : m->bw_next_hi), (long long)feat_hi);
-    TRY(step_backward(m, d, batch, feat_lo, feat_hi, finish != 0, nullptr, nullptr));
-    m->bw_next_hi = feat_lo == 0 ? -1 : feat_lo;
+    // (the tiling rule — descending, or ascending from feature 0 — is bw_window_step's, fmhip_host.h)
+    const BwVerdict v = bw_window_step(m->step.bw, m->n1, feat_lo, feat_hi, finish != 0);
+    if (v.refusal != BwRefusal::kNone) return fail(FMHIP_ERR_INVALID, "%s", bw_refusal_text(v).c_str());
+    TRY(step_backward(m, d, batch, feat_lo, feat_hi, finish != 0, nullptr, nullptr, v.own));
+    m->step.backward_walked(v.next);
     return FMHIP_OK;
 }
 
@@ -678,7 +664,7 @@ int fmhip_step_stats(fmhip_model_t m, fmhip_stats *stats) {
     TRY(set_device(m->device));
     memset(stats, 0, sizeof *stats);
     TRY(read_scal(m, stats));
-    stats->nnz = m->last_nnz;
+    stats->nnz = m->step.last_nnz;
     stats->steps = 1;
     return FMHIP_OK;
 }

@@ -357,7 +357,7 @@ int fmhip_bpr_step(fmhip_model_t m, fmhip_bpr_t h, int64_t batch, double eta, do
     if (stats) {
         memset(stats, 0, sizeof *stats);
         TRY(read_scal(m, stats));
-        stats->nnz = m->last_nnz;
+        stats->nnz = m->step.last_nnz;
         stats->steps = 1;
     }
     return FMHIP_OK;
@@ -377,7 +377,7 @@ int fmhip_bpr_epoch(fmhip_model_t m, fmhip_bpr_t h, int64_t t, double eta, doubl
     int64_t nnz = 0;
     for (int64_t j = 0; j < nb; ++j) {
         TRY(rel_step(m, h->R, order ? order[j] : j, sgd, m->acc.p, true));
-        nnz += m->last_nnz;
+        nnz += m->step.last_nnz;
     }
     if (stats) {
         memset(stats, 0, sizeof *stats);

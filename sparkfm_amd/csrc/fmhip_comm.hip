@@ -464,14 +464,6 @@ int exchange_row_count(fmhip_model_t m, fmhip_comm_t c, float *slot, float rows,
     return collective(c, slot, 1, FMHIP_COLL_SUM_F32, c->cs);
 }
 
-// the dense and pipelined modes' step on a rank that has run out of rows: it contributes zeros (row count 0 included)
-int zero_contribution(fmhip_model_t m) {
-    HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
-    m->grad_dirty = true;
-    m->last_nnz = m->last_rows = 0;
-    return FMHIP_OK;
-}
-
 // Update every interval as its slice arrives (identical on all ranks: replicas stay bit-identical).  The compute stream waits
 // for the slices of the intervals `first` down to 0 in turn (wait = false: the collectives ran on the compute stream itself).
 // Each group of apply_groups is updated behind the wait for its lowest interval: apply(lo, hi, last), last = the group that
@@ -674,29 +666,22 @@ int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
     const bool foreign = c->msg_kp != m->Kp;
     if (foreign && live) return fail(FMHIP_ERR_INVALID, "the touched-rows exchange was planned for rows of %d floats, this model has %d", c->msg_kp, m->Kp);
     if (const char *why = touched_refusal(m, c, sgd)) return fail(FMHIP_ERR_UNSUPPORTED, "%s", why);
-    const bool packed_dirty = m->grad_dirty;     // this step neither writes nor cleans the model's packed gradient
     const int64_t t = position >= 0 ? position : c->t_cursor;
     if (t >= (int64_t)c->tsteps.size())
         return fail(FMHIP_ERR_INVALID, "position %lld outside the planned schedule of %zu steps", (long long)t, c->tsteps.size());
     const auto &ts = c->tsteps[(size_t)t];
     const CompactLayout L(ts.n_u, c->msg_kp);
     const GradView view{c->cg, c->cg + L.gw, c->cg + L.gb, c->cg + L.gv, ts.cdst, ts.hot_pos};
+    // the compact buffer is this step's target: the step neither writes nor cleans the model's packed gradient — a pending
+    // memset of it (8.9 GB at C5's width) would be wasted, and a gradient pending in it stays pending
+    const StepState::ViewScope target(m->step, &view);
     // one interval (no cuts): nothing can overlap, so both collectives run on the compute stream itself — no event hops
     // between the streams, which cost a one-rank step ~40 us of idle time (profiles/r04_experiments.md)
     const bool serial = c->cuts.empty();
     TRY(exchange_row_count(m, c, c->rows_dev, live ? (float)d->batches[(size_t)batch].rows : 0.f, !serial));
-    if (live) {
-        // the packed gradient is not written by this step: a pending memset of it (8.9 GB at C5's width) would be wasted
-        m->grad_dirty = false;
-        const int rc = step_forward(m, d, batch);
-        m->grad_dirty = packed_dirty;
-        TRY(rc);
-    } else {
-        // out of rows: the rows of the compact buffer are clean after every update; the scalars in front of them keep the
-        // last step's (already exchanged) sums and must not travel again
-        HIP_TRY(hipMemsetAsync(c->cg, 0, (size_t)kGradHead * sizeof(float), m->stream));
-        m->last_nnz = m->last_rows = 0;
-    }
+    // out of rows: the rows of the compact buffer are clean after every update; the scalars in front of them keep the
+    // last step's (already exchanged) sums and must not travel again
+    TRY(live ? step_forward(m, d, batch) : zero_contribution(m, true));
     CommProf *pr = next_prof(c);
     // intervals of feature ids [edge[i], edge[i+1]) = rows [pe[i], pe[i+1]) of the compact buffer, from the top down
     const CompactEdges ce = compact_edges(c->cuts, m->n1, ts.cut_pos, ts.n_u);
@@ -704,14 +689,7 @@ int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
     const int n_int = (int)edge.size() - 1;
     for (int i = n_int - 1; i >= 0; --i) {
         const bool last = i == 0;
-        if (live) {
-            m->view = &view;
-            m->grad_dirty = false;
-            const int rc = step_backward(m, d, batch, edge[(size_t)i], n_int == 1 ? INT64_MAX : edge[(size_t)i + 1], last, nullptr);
-            m->view = nullptr;
-            m->grad_dirty = packed_dirty;
-            TRY(rc);
-        }
+        if (live) TRY(step_backward(m, d, batch, edge[(size_t)i], n_int == 1 ? INT64_MAX : edge[(size_t)i + 1], last, nullptr));
         if (serial) {
             int pi;
             TRY(span_begin(pr, true, m->stream, pi));
@@ -727,7 +705,7 @@ int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
             TRY(reduce_regions(m, c, reg.data(), 3, c->ev_ready[i], c->ev_done[i], pr));
         }
     }
-    m->bw_next_hi = -1;
+    m->step.backward_over();
     if (pr) HIP_TRY(hipEventRecord(pr->wait_a, m->stream));
     TRY(apply_as_arrived(m, c, pe, ts.n_u, n_int - 1, !serial, [&](int64_t plo, int64_t phi, bool last) -> int {
         if (foreign) {
@@ -736,15 +714,17 @@ int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
             if (last) HIP_TRY(hipMemsetAsync(c->cg, 0, L.total * sizeof(float), m->stream));
             return FMHIP_OK;
         }
-        if (last)       // the step's global sums where fmhip_step_stats / fmhip_dp_epoch read them
+        // the step's global sums where fmhip_step_stats / fmhip_dp_epoch read them: the packed gradient's head — unless a gradient
+        // is pending there (fmhip_step_compute before this step): its head is that gradient's sum e and row count, which the
+        // fmhip_step_apply to come steps w0 by and divides by
+        if (last && !m->step.grad_dirty)
             HIP_TRY(hipMemcpyAsync(m->scal(), c->cg, (size_t)kScalars * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
         int ai;
         TRY(span_begin(pr, false, m->stream, ai));
-        TRY(step_apply_rows(m, sgd, ts.uni, (int32_t)(phi - plo), c->rows_dev, &view, plo, last));
+        TRY(step_apply_rows(m, sgd, ts.uni, (int32_t)(phi - plo), c->rows_dev, plo, last));
         return span_end(pr, false, m->stream, ai);
     }));
     if (pr) HIP_TRY(hipEventRecord(pr->wait_b, m->stream));
-    m->grad_dirty = packed_dirty;
     c->t_cursor = (t + 1) % (int64_t)c->tsteps.size();
     return FMHIP_OK;
 }
@@ -752,7 +732,7 @@ int dp_step_touched(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
 int dp_step_dense(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t c, const Sgd &sgd) {
     const bool live = batch >= 0;
     TRY(exchange_row_count(m, c, c->rows_dev, live ? (float)d->batches[(size_t)batch].rows : 0.f, true));
-    TRY(live ? step_forward(m, d, batch) : zero_contribution(m));
+    TRY(live ? step_forward(m, d, batch) : zero_contribution(m, false));
     CommProf *pr = next_prof(c);
     // intervals [edge[i], edge[i+1]) from the top down; the lowest one carries the statistics scalars
     const std::vector<int64_t> edge = interval_edges(c->cuts, m->n1, 0);
@@ -769,7 +749,7 @@ int dp_step_dense(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_
             TRY(reduce_regions(m, c, reg.data(), 3, c->ev_ready[i], c->ev_done[i], pr));
         }
     }
-    m->bw_next_hi = -1;
+    m->step.backward_over();
     if (pr) HIP_TRY(hipEventRecord(pr->wait_a, m->stream));
     TRY(apply_as_arrived(m, c, edge, m->n1, n_int - 1, true, [&](int64_t lo, int64_t hi, bool last) -> int {
         int ai;
@@ -844,7 +824,7 @@ int dp_run_pipelined(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const i
             TRY(step_apply_interval(m, sgd, edge[(size_t)T], edge[(size_t)T + 1], c->rows_dev + ((t - 1) & 1), true));
         }
         TRY(exchange_row_count(m, c, rows_t, live ? (float)d->batches[(size_t)b].rows : 0.f, true));
-        TRY(live ? step_forward_pass(m, d, b, 1) : zero_contribution(m));
+        TRY(live ? step_forward_pass(m, d, b, 1) : zero_contribution(m, false));
         // the order of the intervals: the second-coldest first (little work, many bytes: the wire starts early), down to feature
         // 0, the coldest last (it travels beside the next position's pass A).  Who walks a straddling range: whoever comes first
         for (int o = 0; o < n_int; ++o) {
@@ -856,7 +836,7 @@ int dp_run_pipelined(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const i
             const auto reg = slice_regions(m->GV(), m->Gw(), m->Gb(), m->grad, lo, hi, (size_t)m->Kp, head);
             TRY(reduce_regions(m, c, reg.data(), 3, c->ev_ready[i], c->ev_done[i], pr));
         }
-        m->bw_next_hi = -1;
+        m->step.backward_over();
         if (pr) HIP_TRY(hipEventRecord(pr->wait_a, m->stream));
         // every interval but the top one is updated as its slice arrives; the step closes with the top one's update
         TRY(apply_as_arrived(m, c, edge, m->n1, T - 1, true, [&](int64_t lo, int64_t hi, bool) -> int {
@@ -899,16 +879,9 @@ int dp_step_sharded(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
                                            "slack allows (%d), or a caller-owned gradient buffer (fmhip_grad_bind) with n+1 not a multiple of world",
                     (long long)top, W, (long long)m->n1, fmhip_model::kSlackRows);
     TRY(exchange_row_count(m, c, c->rows_dev, live ? (float)d->batches[(size_t)batch].rows : 0.f, true));
-    if (live) {
-        TRY(step_forward(m, d, batch));
-    } else {
-        // out of rows: contribute zeros.  After a sharded step every row of G is clean (own share: the update; the other
-        // shares: the zeroing); only the statistics scalars in front keep the last step's sums
-        if (m->grad_dirty) HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
-        else HIP_TRY(hipMemsetAsync(m->grad, 0, (size_t)kGradHead * sizeof(float), m->stream));
-        m->grad_dirty = true;
-        m->last_nnz = m->last_rows = 0;
-    }
+    // out of rows: contribute zeros.  After a sharded step every row of G is clean (own share: the update; the other
+    // shares: the zeroing); only the statistics scalars in front keep the last step's sums
+    TRY(live ? step_forward(m, d, batch) : zero_contribution(m, true));
     CommProf *pr = next_prof(c);
     const std::vector<int64_t> edge = interval_edges(c->cuts, m->n1, W);      // (the plan rounds already; a plan made for another world may not have)
     const int n_int = (int)edge.size() - 1;
@@ -947,12 +920,12 @@ int dp_step_sharded(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_com
         if (c->profiling) c->prof_bytes += (int64_t)(gv_bytes + head_bytes);
     }
     HIP_TRY(hipEventRecord(c->ev_gathered, c->cs));
-    m->bw_next_hi = -1;
+    m->step.backward_over();
     // the next forward reads V and the next backward writes G: everything queued on the comm stream must have landed
     if (pr) HIP_TRY(hipEventRecord(pr->wait_a, m->stream));
     HIP_TRY(hipStreamWaitEvent(m->stream, c->ev_gathered, 0));
     if (pr) HIP_TRY(hipEventRecord(pr->wait_b, m->stream));
-    m->grad_dirty = false;
+    m->step.grad_consumed();
     return FMHIP_OK;
 }
 
@@ -1488,7 +1461,7 @@ static int dp_epoch(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, const Sg
     if (stats) {
         memset(stats, 0, sizeof *stats);
         TRY(read_scal(m, stats));      // all-reduced: the global batch's sums
-        stats->nnz = m->last_nnz;
+        stats->nnz = m->step.last_nnz;
         stats->steps = steps;
     }
     return FMHIP_OK;

@@ -3,6 +3,7 @@
 #include "fmhip_host.h"
 #include "mcmc_rng.h"
 
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <math.h>
@@ -616,6 +617,39 @@ std::vector<ApplyGroup> apply_groups(const std::vector<int64_t> &edges, int64_t 
         pend_hi = -1;
     }
     return g;
+}
+
+// ---- the split step's backward window -----------------------------------------------------------------------------------
+BwVerdict bw_window_step(BwWindow w, int64_t n1, int64_t lo, int64_t hi, bool finish) {
+    auto refuse = [&](BwRefusal why, int64_t want, int64_t got) { return BwVerdict{why, want, got, 0, w}; };
+    if (w.closed()) return refuse(BwRefusal::kClosed, 0, 0);
+    if (finish && lo != 0) return refuse(BwRefusal::kFinishAboveZero, 0, 0);
+    const bool fresh = w.next == INT64_MAX;
+    if (fresh ? hi < n1 && lo == 0 : w.up) {
+        const int64_t want = fresh ? 0 : w.next;
+        if (lo != want) return refuse(BwRefusal::kNotAscending, want, lo);
+        return BwVerdict{BwRefusal::kNone, 0, 0, kOwnUpper, BwWindow{hi >= n1 ? -1 : hi, true}};
+    }
+    if (fresh ? hi < n1 : hi != w.next) return refuse(BwRefusal::kNotDescending, fresh ? n1 : w.next, hi);
+    return BwVerdict{BwRefusal::kNone, 0, 0, kOwnLower, BwWindow{lo == 0 ? -1 : lo, false}};
+}
+
+std::string bw_refusal_text(const BwVerdict &v) {
+    char buf[200] = "";
+    switch (v.refusal) {
+        case BwRefusal::kNone: break;
+        case BwRefusal::kClosed: return "fmhip_step_backward without fmhip_step_forward";
+        case BwRefusal::kFinishAboveZero: return "finish = 1 belongs to the interval that starts at feature 0";
+        case BwRefusal::kNotAscending:
+            snprintf(buf, sizeof buf, "feature intervals must tile [0, n+1) in ascending order (expected lo = %lld, got %lld)", (long long)v.want,
+                     (long long)v.got);
+            break;
+        case BwRefusal::kNotDescending:
+            snprintf(buf, sizeof buf, "feature intervals must tile [0, n+1) in descending order (expected hi = %lld, got %lld), or start at feature 0 and ascend",
+                     (long long)v.want, (long long)v.got);
+            break;
+    }
+    return buf;
 }
 
 // HitRate / Recall / Precision / NDCG at k, MRR and MAP of the ranks fmhip_rank returns (include/fmhip_ranking.h states each).

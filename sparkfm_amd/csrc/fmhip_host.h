@@ -1,7 +1,7 @@
 // fmhip_host.h — the library's PURE HOST ARITHMETIC: everything libfmhip.so computes on the host that needs no GPU and no
 // HIP header — row shards, feature relabelling, the host passes of the dataset build (validation, the dense hot block's choice and
 // split, the forward row order, the ALS row sort, the own bitmaps, the example weights' check), a batch's range / fixup metadata, the band-affine plan of the
-// backward's ranges, the ALS sweep's level schedule, the data-parallel plan's cuts, interval edges, equal shares and update groups.  fmhip_dataset.hip /
+// backward's ranges, the ALS sweep's level schedule, the data-parallel plan's cuts, interval edges, equal shares and update groups, the split step's backward window.  fmhip_dataset.hip /
 // fmhip_comm.hip call these; tests/host_arith_harness.cpp compiles fmhip_host.cpp with g++ -fsanitize=address,undefined and
 // drives them over random shapes (the sanitizers cannot run on the GPU pool, the index arithmetic can run
 // here).  Not installed, not part of the ABI.
@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include <memory>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -146,6 +147,34 @@ CompactEdges compact_edges(const std::vector<int64_t> &cuts, int64_t n1, const i
 // launch, in that order: the rows [lo, hi) and the interval `at` whose arrival it waits for
 struct ApplyGroup { int at; int64_t lo, hi; };
 std::vector<ApplyGroup> apply_groups(const std::vector<int64_t> &edges, int64_t total_rows, int first_interval);
+
+// ---- the split step's backward window (fmhip_step_backward; StepState, fmhip_internal.h) -------------------------------
+// Which of the two ranges that straddle a feature interval's edges a step_backward call walks: a straddling range belongs to
+// whichever of its two intervals is walked FIRST (the other one's fixup then finds its partials).  Descending calls own their
+// lower edge, ascending calls their upper one; a schedule that mixes the orders says so per call.
+enum { kOwnLower = 1, kOwnUpper = 2 };
+// The caller's intervals tile [0, n1) in DESCENDING order (a range straddling two intervals is walked with the upper one, whose
+// partials the lower one's fixup then reads) or, from feature 0 up, in ASCENDING order (the mirror rule); the first call after
+// the forward says which: it ends at n1 (or beyond) or starts at 0.  next: -1 = closed (no forward, or the tiling is complete),
+// INT64_MAX = open and no interval walked yet, else the edge the next interval must end at (up: start at)
+struct BwWindow {
+    int64_t next = -1;
+    bool up = false;
+    static BwWindow opened() { return BwWindow{INT64_MAX, false}; }
+    bool closed() const { return next < 0; }
+    bool operator==(const BwWindow &o) const { return next == o.next && up == o.up; }
+};
+enum class BwRefusal { kNone, kClosed, kFinishAboveZero, kNotAscending, kNotDescending };
+// the interval [lo, hi) (0 <= lo <= hi, checked by the caller; finish: it carries the step's statistics) against window w: accepted
+// (refusal kNone) with the straddling ranges it owns and the window after it, or refused — `next` is then w itself
+struct BwVerdict {
+    BwRefusal refusal;
+    int64_t want, got;      // kNotAscending / kNotDescending: the edge the window expected and the caller's
+    int own;
+    BwWindow next;
+};
+BwVerdict bw_window_step(BwWindow w, int64_t n1, int64_t lo, int64_t hi, bool finish);
+std::string bw_refusal_text(const BwVerdict &v);      // fmhip_step_backward's error message for a refusal
 
 // ---- ranking metrics of given ranks (fmhip_rank_metrics, include/fmhip_ranking.h) ------------------------------------
 // ranks[rel_ptr[c] .. rel_ptr[c+1]) are the 0-based ranks of context c's relevant rows; the metrics are cut at k >= 1 and

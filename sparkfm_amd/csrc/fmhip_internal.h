@@ -107,6 +107,49 @@ struct GradView {
     const int32_t *hot_pos;    // per slot of the dense hot block: its row (-1 = unused slot)
 };
 
+// What a mini-batch step carries from one of its pieces to the next (forward -> backward intervals -> [exchange] -> update), and
+// the ONLY place that writes it: every route moves it through the transitions below ("The step's state").
+struct StepState {
+    // where this step's gradient rows go: the model's packed gradient (nullptr), or a compact view for the length of a ViewScope
+    const GradView *view = nullptr;
+    bool grad_dirty = false;      // the PACKED gradient holds a gradient that has not been applied/zeroed
+    bool hot_pending = false;     // the dense hot block's gradient of the current step is still to be formed
+    BwWindow bw;                  // the feature intervals fmhip_step_backward may still walk
+    int64_t last_nnz = 0, last_rows = 0;
+    int fwd_parts = 0;            // per-block statistic partials the last forward launch wrote
+
+    // The touched-rows exchange sets its compact buffer as the step's target ONCE: under it no transition cleans or dirties the
+    // packed gradient — a gradient pending from fmhip_step_compute is still there, and still to be applied, afterwards
+    struct ViewScope {
+        StepState &s;
+        ViewScope(StepState &s_, const GradView *v) : s(s_) { s.view = v; }
+        ~ViewScope() { s.view = nullptr; }
+        ViewScope(const ViewScope &) = delete;
+    };
+    // forward begins: must the target be zeroed first?  Never a view (its rows are clean after every update) — and the packed
+    // gradient is not written by such a step: a pending memset of it (8.9 GB at C5's width) would be wasted
+    bool must_zero() const { return !view && grad_dirty; }
+    // the target holds this step's contribution (a forward's rows to come, or a rank's zeros): what fmhip_step_stats reports
+    void written(int64_t nnz, int64_t rows) {
+        if (!view) grad_dirty = true;
+        last_nnz = nnz;
+        last_rows = rows;
+    }
+    // forward done: + the backward window opens and the hot block is armed (hot: the dataset has one)
+    void forward_done(int64_t nnz, int64_t rows, bool hot) {
+        written(nnz, rows);
+        bw = BwWindow::opened();
+        hot_pending = hot;
+    }
+    // the relational step arms the block per part (each part's whole-batch backward consumes it) and leaves it disarmed
+    void arm_hot(bool hot) { hot_pending = hot; }
+    void hot_formed() { hot_pending = false; }
+    void backward_walked(const BwWindow &next) { bw = next; }     // fmhip_step_backward: one accepted interval
+    void backward_over() { bw = BwWindow{}; }                     // an exchange mode walked its own intervals
+    // the target's gradient is applied — or the packed buffer zeroed, or a fresh one bound (no view is set in those calls)
+    void grad_consumed() { if (!view) grad_dirty = false; }
+};
+
 // How a model trains, as ONE value: the residual every training path forms (enum fmhip_loss), whether rows 2j / 2j+1 of a
 // batch are one example with the loss applied to their difference (enum fmhip_pairing; fm_pairing.h — the training forward
 // then runs in two launches and keeps the rows' predictions in yhat), and the update rule with its settings (enum
@@ -357,15 +400,11 @@ struct fmhip_model {
     DevBuf<float> V, w, w0;
     DevBuf<float> grad_own;
     float *grad = nullptr;        // packed gradient in use (own or bound)
-    const fmhip::host::GradView *view = nullptr;   // set around a backward that writes elsewhere (see GradView)
-    bool grad_dirty = false;      // holds a gradient that has not been applied/zeroed
+    fmhip::host::StepState step;  // what the pieces of a mini-batch step hand on to each other
     DevBuf<float> P, e, part, pieces, hot_part;
     DevBuf<float> part_sl;        // two-pass forward: pass A's {sum_f s_f, linear term} per row
-    bool hot_pending = false;   // the dense hot block's gradient of the current step is still to be formed
     DevBuf<double> acc;           // {sum e, sum e^2, rows, nonfinite}
     DevBuf<double> bsum;          // k_forward's per-block statistic partials
-    int64_t last_nnz = 0, last_rows = 0;
-    int fwd_parts = 0;            // per-block statistic partials the last forward launch wrote
     // lazy weight decay (fm_apply.hip): the device tables hold U with V = sv*U, w = sw*(stored w); both are
     // exactly 1 unless rows-only updates with decay are pending.  Tracked in fp64 on the host, so the
     // scale itself accumulates no fp32 rounding from step to step.
@@ -376,8 +415,6 @@ struct fmhip_model {
     // w_i's), Nw [n1p] (unpacked rows only), N0 [1] — one more copy of the model (8.6 GB at 2^25 x 64); the tables stay at
     // scale 1 (sv = sw = 1) while it is set
     DevBuf<float> NV, Nw, N0;
-    int64_t bw_next_hi = -1;      // feature-chunked backward: the next interval must end here (-1: none pending)
-    bool bw_up = false;           // ... ascending intervals instead (the next one must START here)
     // fp64 master copy of the parameters (reference layout): exact round trip of what the caller set,
     // and the state the fp64 ALS learner trains; stale once an fp32 SGD step has run
     std::vector<double> h_w, h_v;
@@ -461,10 +498,6 @@ struct FusedPlan {
     double sv_out = 1.0, sw_out = 1.0;    // the tables' scales after the step
     FusedUpd upd{};
 };
-// Which of the two ranges that straddle a feature interval's edges a step_backward call walks: a straddling range belongs to
-// whichever of its two intervals is walked FIRST (the other one's fixup then finds its partials).  Descending calls own their
-// lower edge, ascending calls their upper one; a schedule that mixes the orders says so per call.
-enum { kOwnLower = 1, kOwnUpper = 2 };
 // the training forward in two passes (pass 0 = A: features below the dataset's split cut; pass 1 = B: the others + the row's finish)
 int step_forward_pass(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int pass);
 // src (the relational step): the backward reads these P rows / residuals — a block's P_b / e_b — instead of the model's
@@ -476,22 +509,28 @@ int step_compute(fmhip_model_t m, fmhip_dataset_t d, int64_t b, double *acc, con
 // can this step's update run inside the fixup launch / the column walk?  (fills *p; false: a launch of its own, step_apply)
 bool plan_fused(fmhip_model_t m, fmhip_dataset_t d, int64_t b, const Sgd &s, FusedPlan *p);
 int finish_fused(fmhip_model_t m, const FusedPlan &p);      // what step_apply leaves behind, for a step planned fused
+// forward begins: the step's target zeroed if it is the packed gradient and holds an old one
+int begin_forward(fmhip_model_t m);
+// This rank has run out of rows: its contribution to the step's exchange is zeros (row count 0 included).  rows_clean: the
+// exchange leaves every gradient ROW of the target zero behind it, so a clean target needs only the statistics head in front of
+// them cleared — which keeps the last step's (already exchanged) sums.  A compact view is always such a target
+int zero_contribution(fmhip_model_t m, bool rows_clean);
 int fold_scales(fmhip_model_t m);                           // lazily decayed tables back to scale 1
 int read_acc(fmhip_model_t m, fmhip_stats *st);             // the fp64 epoch accumulators (synchronises)
 int step_apply(fmhip_model_t m, const Sgd &s, fmhip_dataset_t d = nullptr, int64_t b = -1);
 int step_apply_interval(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, const float *rows, bool last);
 // The sharded update of the feature interval [lo, hi) on stream `s` (one launch): V rows [vlo, vhi) (this rank's share) get
 // the dense update, every linear weight of the interval is stepped, the G_V rows of [lo, hi_r) outside the share are zeroed
-// (hi_r >= hi: the top interval's equal shares reach into the slack rows).  `last`: also steps w0 and closes the step.
+// (hi_r >= hi: the top interval's equal shares reach into the slack rows).  `last`: also steps w0 and closes the step — but for
+// the gradient, which stays the step's until the caller's all-gathers have landed (dp_step_sharded).
 int step_apply_shard(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, int64_t hi_r, int64_t vlo, int64_t vhi, const float *rows,
                      bool last, hipStream_t stream);
 // the rows-only (lazy-decay) update of the feature rows listed on the device (ids < 0 are skipped), |B| from `rows`
 // (device float): the touched-rows exchange of the data-parallel step applies the union of all ranks' rows with it
-// view given: the gradient rows are read from (and zeroed in) its compact arrays, row j belonging to feature feat[j]
+// the step's target a compact view (StepState): the gradient rows are read from (and zeroed in) its arrays, row j belonging to feature feat[j]
 // off / last: the rows [off, off + n_feat) of the list (and of a compact view) only — the touched-rows exchange updates a
 // feature interval as soon as its slice has arrived; the step's bookkeeping (w0, the tables' scale) moves with the LAST slice
-int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t n_feat, const float *rows, const GradView *view = nullptr,
-                    int64_t off = 0, bool last = true);
+int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t n_feat, const float *rows, int64_t off = 0, bool last = true);
 // can the update of this step leave rows without a gradient alone (weight decay rides in the tables' scale, or there is
 // none)?  Under AdaGrad only without decay (`r`: the rule to judge by — the model's own, or the one a plan agreed)
 bool lazy_decay_ok(fmhip_model_t m, const Sgd &s, const TrainRule &r);

@@ -140,10 +140,7 @@ int rel_block_forwards(fmhip_model_t m, fmhip_relational_t R) {
 int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs) {
     const fmhip_relational::Batch &B = R->batches[(size_t)b];
     TRY(rel_block_forwards(m, R));           // every block's q-mode pass, over the whole block
-    if (m->grad_dirty) {                     // (the forwards do not touch the gradient)
-        HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
-        m->grad_dirty = false;
-    }
+    TRY(begin_forward(m));                   // (the forwards do not touch the gradient)
     int64_t nnz = R->block_nnz;
     if (R->plain) {
         const BatchMeta &bm = R->plain->batches[(size_t)b];
@@ -154,15 +151,13 @@ int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, d
     RelFinishArgs fa = rel_finish_args(m, R, rel_step_bufs(m, R), B, m->rule.loss);
     if (!pairs) fa.yhat = nullptr;           // (only the pairs' finish reads the rows' predictions)
     fa.q_only = pairs ? 1 : 0;
-    HIP_TRY(launch_rel_finish(m->Kp, fa, false, m->stream, &m->fwd_parts));
+    HIP_TRY(launch_rel_finish(m->Kp, fa, false, m->stream, &m->step.fwd_parts));
     if (pairs) {
         // the BPR trainer: the finish left Q_r in P and yhat_r beside it, as the flat paired step's kFwdQ forward does; the pairs'
         // finish (fm_pairing.hip) turns them into P_r = Q_r e_r, e and the statistics partials (its own block count)
-        HIP_TRY(launch_pair_finish(m->Kp, pair_args(m, R->y.p + B.row0, nullptr, B.rows), m->stream, &m->fwd_parts));
+        HIP_TRY(launch_pair_finish(m->Kp, pair_args(m, R->y.p + B.row0, nullptr, B.rows), m->stream, &m->step.fwd_parts));
     }
-    m->grad_dirty = true;
-    m->last_nnz = nnz;
-    m->last_rows = B.rows;
+    m->step.written(nnz, B.rows);            // (no backward window: the parts' whole-batch backwards below are the step's own)
     for (auto &relp : R->rels) {
         fmhip_relational::Relation &rel = *relp;
         const RelationInverse::Batch &ib = rel.batches[(size_t)b];
@@ -190,15 +185,15 @@ int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, d
         ga.pack_k = m->pack_k();
         HIP_TRY(launch_rel_gather_sum(m->Kp, ga, m->stream));
         const BwdSource src{rel.Pb.p, rel.eb.p};
-        m->hot_pending = rel.block->hot_T > 0;
+        m->step.arm_hot(rel.block->hot_T > 0);
         TRY(step_backward(m, rel.block, 0, 0, INT64_MAX, false, nullptr, nullptr, kOwnLower, &src));
     }
     if (R->plain) {                          // the plain part: P as the finish left it (the paired path's second half)
-        m->hot_pending = R->plain->hot_T > 0;
+        m->step.arm_hot(R->plain->hot_T > 0);
         TRY(step_backward(m, R->plain, b, 0, INT64_MAX, false, nullptr));
     }
-    m->hot_pending = false;
-    HIP_TRY(launch_reduce_blocks(m->bsum.p, m->fwd_parts, (int32_t)B.rows, m->scal(), acc, m->stream));
+    m->step.arm_hot(false);
+    HIP_TRY(launch_reduce_blocks(m->bsum.p, m->step.fwd_parts, (int32_t)B.rows, m->scal(), acc, m->stream));
     TRY(step_apply(m, sgd));                 // the dense update (SGD or AdaGrad), which also closes the step
     HIP_TRY(hipEventRecord(R->busy, m->stream));
     R->busy_stream = m->stream;
@@ -358,7 +353,7 @@ int fmhip_relational_sgd_step(fmhip_model_t m, fmhip_relational_t r, int64_t bat
         // (the update zeroes the gradient rows it applies, not the head's statistics)
         memset(stats, 0, sizeof *stats);
         TRY(read_scal(m, stats));
-        stats->nnz = m->last_nnz;
+        stats->nnz = m->step.last_nnz;
         stats->steps = 1;
     }
     return FMHIP_OK;
@@ -376,7 +371,7 @@ int fmhip_relational_sgd_epoch(fmhip_model_t m, fmhip_relational_t r, double eta
     int64_t nnz = 0;
     for (int64_t j = 0; j < nb; ++j) {
         TRY(rel_step(m, r, order ? order[j] : j, sgd, m->acc.p));
-        nnz += m->last_nnz;
+        nnz += m->step.last_nnz;
     }
     if (stats) {
         memset(stats, 0, sizeof *stats);

@@ -201,11 +201,11 @@ BwdArgs bwd_args(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
     a.GV = m->GV();
     a.Gw = m->Gw();
     a.Gb = m->Gb();
-    if (m->view) {     // the rows go to a compact buffer (touched-rows exchange): column s -> row view->cdst[s]
-        a.GV = m->view->GV;
-        a.Gw = m->view->Gw;
-        a.Gb = m->view->Gb;
-        a.cdst = m->view->cdst;
+    if (const GradView *view = m->step.view) {     // the rows go to a compact buffer (touched-rows exchange): column s -> row view->cdst[s]
+        a.GV = view->GV;
+        a.Gw = view->Gw;
+        a.Gb = view->Gb;
+        a.cdst = view->cdst;
     }
     a.part = m->part.p;
     return a;
@@ -259,18 +259,30 @@ PairArgs pair_args(fmhip_model_t m, const float *y, const float *c, int64_t rows
     return pa;
 }
 
+int begin_forward(fmhip_model_t m) {
+    if (!m->step.must_zero()) return FMHIP_OK;
+    HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
+    m->step.grad_consumed();
+    return FMHIP_OK;
+}
+
+int zero_contribution(fmhip_model_t m, bool rows_clean) {
+    const GradView *view = m->step.view;
+    const bool head_only = view || (rows_clean && !m->step.grad_dirty);
+    HIP_TRY(hipMemsetAsync(view ? view->scal : m->grad, 0, (head_only ? (size_t)kGradHead : m->grad_floats()) * sizeof(float), m->stream));
+    m->step.written(0, 0);
+    return FMHIP_OK;
+}
+
 // forward of one batch: P = e*q, e, per-block statistics partials
 int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
     const BatchMeta &bm = d->batches[(size_t)b];
     TRY(ensure_workspace(m, d));
-    if (m->grad_dirty) {
-        HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
-        m->grad_dirty = false;
-    }
+    TRY(begin_forward(m));
     if (m->rule.paired() || d->weighted) {
         // two launches: the q-mode forward — every existing kernel choice (hot pages, packed rows, row order, address mode) as it
         // is, P = sv*q and the predictions beside it — then the pairs' finish (fm_pairing.hip): P rows times +-g, e, the statistics
-        // partials (its own block count: the backward's finish sums m->fwd_parts of them)
+        // partials (its own block count: the backward's finish sums m->step.fwd_parts of them)
         // (check_train has refused datasets whose batches would cut a pair)
         // A weighted dataset (fm_weights.h) trains the same way: its pairs through the same finish with the weights beside the
         // labels, its single rows through a finish of their own (fm_weights.hip)
@@ -280,7 +292,7 @@ int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
         HIP_TRY(launch_forward(m->Kp, kFwdQ, a, m->stream, nullptr));
         if (m->rule.paired()) {
             const PairArgs pa = pair_args(m, d->y.p + bm.row0, d->weighted ? d->c.p + bm.row0 : nullptr, bm.rows);
-            HIP_TRY(launch_pair_finish(m->Kp, pa, m->stream, &m->fwd_parts));
+            HIP_TRY(launch_pair_finish(m->Kp, pa, m->stream, &m->step.fwd_parts));
         } else {
             WeightArgs wa{};
             wa.P = m->P.p;
@@ -292,17 +304,13 @@ int step_forward(fmhip_model_t m, fmhip_dataset_t d, int64_t b) {
             wa.n_rows = (int32_t)bm.rows;
             wa.pack_k = m->pack_k();
             wa.loss = m->rule.loss;
-            HIP_TRY(launch_weight_finish(m->Kp, wa, m->stream, &m->fwd_parts));
+            HIP_TRY(launch_weight_finish(m->Kp, wa, m->stream, &m->step.fwd_parts));
         }
     } else {
         ProfScope ps(m, FMHIP_K_FORWARD, bm.nnz_total, bm.rows);
-        HIP_TRY(launch_forward(m->Kp, kFwdTrain, fwd_args(m, d, bm), m->stream, &m->fwd_parts));
+        HIP_TRY(launch_forward(m->Kp, kFwdTrain, fwd_args(m, d, bm), m->stream, &m->step.fwd_parts));
     }
-    m->grad_dirty = true;
-    m->last_nnz = bm.nnz_total;
-    m->last_rows = bm.rows;
-    m->bw_next_hi = INT64_MAX;
-    m->hot_pending = d->hot_T > 0;
+    m->step.forward_done(bm.nnz_total, bm.rows, d->hot_T > 0);
     return FMHIP_OK;
 }
 
@@ -331,19 +339,12 @@ int step_forward_pass(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int pass) {
         HIP_TRY(launch_forward(m->Kp, kFwdPartA, a, m->stream, nullptr));
         return FMHIP_OK;
     }
-    if (m->grad_dirty) {
-        HIP_TRY(hipMemsetAsync(m->grad, 0, m->grad_floats() * sizeof(float), m->stream));
-        m->grad_dirty = false;
-    }
+    TRY(begin_forward(m));
     {
         ProfScope ps(m, FMHIP_K_FORWARD, 0, bm.rows);
-        HIP_TRY(launch_forward(m->Kp, kFwdPartB, a, m->stream, &m->fwd_parts));
+        HIP_TRY(launch_forward(m->Kp, kFwdPartB, a, m->stream, &m->step.fwd_parts));
     }
-    m->grad_dirty = true;
-    m->last_nnz = bm.nnz_total;
-    m->last_rows = bm.rows;
-    m->bw_next_hi = INT64_MAX;
-    m->hot_pending = d->hot_T > 0;
+    m->step.forward_done(bm.nnz_total, bm.rows, d->hot_T > 0);
     return FMHIP_OK;
 }
 
@@ -351,14 +352,14 @@ int step_forward_pass(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int pass) {
 // the first backward call of a step forms them and every later interval finds them complete): the
 // work rides in that call's backward and fixup launches
 void hot_attach(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm, BwdArgs &ba) {
-    if (!m->hot_pending) return;
+    if (!m->step.hot_pending) return;
     HotArgs &h = ba.hot;
     h.P = m->P.p;
     h.e = m->e.p;
     h.xhot = d->xhot.p + (size_t)bm.row0 * kHotT;
     h.page_stride = std::max<int64_t>(d->n_rows, 1) * kHotT;
     h.pages = d->hot_pages;
-    h.hot_ids = m->view ? m->view->hot_pos : d->d_hot_ids.p;
+    h.hot_ids = m->step.view ? m->step.view->hot_pos : d->d_hot_ids.p;
     h.part = m->hot_part.p;
     h.GV = ba.GV;
     h.Gw = ba.Gw;
@@ -368,11 +369,47 @@ void hot_attach(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm, BwdArgs
     h.nblk = hot_blocks(m->Kp, bm.rows);
     h.upd = ba.upd;
     ba.hot_blocks = h.nblk;
-    m->hot_pending = false;
+    m->step.hot_formed();
 }
 
-// backward + fixup of the columns whose feature id lies in [feat_lo, feat_hi) into the packed
-// gradient.  The CSC stream is sorted by feature, so the interval is a contiguous run of entries;
+// ba, built for the whole batch, clipped to the columns whose feature id lies in [feat_lo, feat_hi): the range window, the band
+// plan's runs inside it, the cut columns its fixup assembles (host searches over the dataset's host copies) -> its stored entries
+static int64_t clip_to_interval(fmhip_dataset_t d, const BatchMeta &bm, int64_t b, int64_t feat_lo, int64_t feat_hi, int own, bool banded,
+                                BwdArgs &ba) {
+    const int32_t *hf = d->h_cfeat.data() + bm.col_off, *hp = d->h_cptr.data() + bm.col_off + b;
+    const int32_t *hs = d->h_split.data() + bm.split_off;
+    const int32_t s_lo = (int32_t)(std::lower_bound(hf, hf + bm.n_cols, (int32_t)std::min<int64_t>(feat_lo, INT32_MAX)) - hf);
+    const int32_t s_hi = (int32_t)(std::lower_bound(hf, hf + bm.n_cols, (int32_t)std::min<int64_t>(feat_hi, INT32_MAX)) - hf);
+    const int32_t e_lo = hp[s_lo], e_hi = hp[s_hi];            // entry interval of the columns
+    // lower edge owned: from the range holding entry e_lo; else from the first range that starts at or after it (the range
+    // holding entry e_lo - 1 goes with the interval below).  Upper edge likewise.
+    ba.rho_lo = (own & kOwnLower) ? e_lo / kRangeLen : (e_lo + kRangeLen - 1) / kRangeLen;
+    ba.rho_hi = s_hi >= bm.n_cols ? bm.n_ranges : ((own & kOwnUpper) ? (e_hi + kRangeLen - 1) / kRangeLen : e_hi / kRangeLen);
+    if (ba.rho_hi < ba.rho_lo) ba.rho_hi = ba.rho_lo;                  // (an interval inside one range that a neighbour owns)
+    if (banded) {
+        // every run of the plan holds ascending range ids: the part of it inside [rho_lo, rho_hi) is one sub-run
+        for (int x = 0; x < kXcds; ++x)
+            for (int sg = 0; sg < kXSegs; ++sg) {
+                const int32_t *r0 = d->h_xlist.data() + bm.xoff[x] + bm.xseg[x][sg], *r1 = d->h_xlist.data() + bm.xoff[x] + bm.xseg[x][sg + 1];
+                const int32_t *lo = std::lower_bound(r0, r1, ba.rho_lo), *hi = std::lower_bound(r0, r1, ba.rho_hi);
+                ba.xseg_off[x][sg] = (int32_t)(lo - d->h_xlist.data());
+                ba.xseg_len[x][sg] = (int32_t)(hi - lo);
+            }
+    }
+    const int32_t sp_lo = (int32_t)(std::lower_bound(hs, hs + bm.n_split, s_lo) - hs);
+    const int32_t sp_hi = (int32_t)(std::lower_bound(hs, hs + bm.n_split, s_hi) - hs);
+    ba.split_seg += sp_lo;
+    ba.n_split = sp_hi - sp_lo;
+    const int32_t *hss = d->h_split_short.data() + bm.split_short_off;
+    const int32_t q_lo = (int32_t)(std::lower_bound(hss, hss + bm.n_split_short, s_lo) - hss);
+    const int32_t q_hi = (int32_t)(std::lower_bound(hss, hss + bm.n_split_short, s_hi) - hss);
+    ba.split_short += q_lo;
+    ba.n_split_short = q_hi - q_lo;
+    return (int64_t)e_hi - e_lo;
+}
+
+// backward + fixup of the columns whose feature id lies in [feat_lo, feat_hi) into the step's target (the packed gradient, or
+// the compact view the step set).  The CSC stream is sorted by feature, so the interval is a contiguous run of entries;
 // the range holding its first entry is walked by THIS call in full (the entries of lower features
 // in it produce G rows / head partials that the call covering them consumes later), the range
 // holding the first entry of feat_hi is left to the call that covers feat_hi.  `finish` adds the
@@ -406,89 +443,43 @@ int step_backward(fmhip_model_t m, fmhip_dataset_t d, int64_t b, int64_t feat_lo
         ba.no_wave_sum = 1;
         ba.xcd_chunk = 0;
     }
-    if (whole) {   // the common case needs no host-side searches
-        if (banded)
-            for (int x = 0; x < kXcds; ++x) {     // one run per XCD: its list in walk order (no window to clip the plan's runs to)
-                ba.xseg_off[x][0] = (int32_t)bm.woff[x];
-                ba.xseg_len[x][0] = bm.xlen[x];
-            }
-        if (finish) {
-            ba.red_bsum = m->bsum.p;
-            ba.red_nblocks = m->fwd_parts;
-            ba.red_rows = (int32_t)bm.rows;
-            ba.red_scal = m->view ? m->view->scal : m->scal();
-            ba.red_acc = acc;
+    int64_t nnz_part = bm.nnz_total;
+    if (!whole) {
+        nnz_part = clip_to_interval(d, bm, b, feat_lo, feat_hi, own, banded, ba);
+    } else if (banded) {   // the common case needs no host-side searches
+        for (int x = 0; x < kXcds; ++x) {     // one run per XCD: its list in walk order (no window to clip the plan's runs to)
+            ba.xseg_off[x][0] = (int32_t)bm.woff[x];
+            ba.xseg_len[x][0] = bm.xlen[x];
         }
-        {
-            ProfScope ps(m, FMHIP_K_BACKWARD, bm.nnz_total, bm.rows);
-            HIP_TRY(launch_backward(m->Kp, ba, m->stream));
-        }
-        if (fused && fused->mode == 2) {
-            // merged finish: the fixup launch also updates the parameters (its own rows from registers, the rest in
-            // extra workgroups beside it); the column walk above stored its gradient rows as usual
-            ApplyArgs &f = ba.fin;
-            f = apply_args(m, fused->sgd, m->scal() + 2);
-            f.do_w0 = 0;                                   // the statistics block steps w0 (red_w0)
-            f.invb_val = fused->upd.invb;
-            f.use_invb_val = 1;
-            int64_t blocks = (m->n1 * (m->Kp / 4) + 255) / 256;
-            ba.fin_blocks = (int32_t)std::min<int64_t>(std::max<int64_t>(blocks, 1), FMHIP_FIN_BLOCKS);
-            ba.fin_own = d->own_bits.p + bm.own_off;
-            ba.fin_own_bits = (int32_t)std::min<int64_t>(d->own_words * 32, INT32_MAX);
-        }
-        {
-            ProfScope ps(m, FMHIP_K_FIXUP, bm.nnz_total, bm.rows);
-            HIP_TRY(launch_fixup(m->Kp, ba, m->stream));
-            HIP_TRY(launch_fixup2(m->Kp, ba, m->stream));
-        }
-        return FMHIP_OK;
-    }
-    const int32_t *hf = d->h_cfeat.data() + bm.col_off, *hp = d->h_cptr.data() + bm.col_off + b;
-    const int32_t *hs = d->h_split.data() + bm.split_off;
-    const int32_t s_lo = (int32_t)(std::lower_bound(hf, hf + bm.n_cols, (int32_t)std::min<int64_t>(feat_lo, INT32_MAX)) - hf);
-    const int32_t s_hi = (int32_t)(std::lower_bound(hf, hf + bm.n_cols, (int32_t)std::min<int64_t>(feat_hi, INT32_MAX)) - hf);
-    const int32_t e_lo = hp[s_lo], e_hi = hp[s_hi];            // entry interval of the columns
-    // lower edge owned: from the range holding entry e_lo; else from the first range that starts at or after it (the range
-    // holding entry e_lo - 1 goes with the interval below).  Upper edge likewise.
-    ba.rho_lo = (own & kOwnLower) ? e_lo / kRangeLen : (e_lo + kRangeLen - 1) / kRangeLen;
-    ba.rho_hi = s_hi >= bm.n_cols ? bm.n_ranges : ((own & kOwnUpper) ? (e_hi + kRangeLen - 1) / kRangeLen : e_hi / kRangeLen);
-    if (ba.rho_hi < ba.rho_lo) ba.rho_hi = ba.rho_lo;                  // (an interval inside one range that a neighbour owns)
-    if (banded) {
-        // every run of the plan holds ascending range ids: the part of it inside [rho_lo, rho_hi) is one sub-run
-        for (int x = 0; x < kXcds; ++x)
-            for (int sg = 0; sg < kXSegs; ++sg) {
-                const int32_t *r0 = d->h_xlist.data() + bm.xoff[x] + bm.xseg[x][sg], *r1 = d->h_xlist.data() + bm.xoff[x] + bm.xseg[x][sg + 1];
-                const int32_t *lo = std::lower_bound(r0, r1, ba.rho_lo), *hi = std::lower_bound(r0, r1, ba.rho_hi);
-                ba.xseg_off[x][sg] = (int32_t)(lo - d->h_xlist.data());
-                ba.xseg_len[x][sg] = (int32_t)(hi - lo);
-            }
-    }
-    const int32_t sp_lo = (int32_t)(std::lower_bound(hs, hs + bm.n_split, s_lo) - hs);
-    const int32_t sp_hi = (int32_t)(std::lower_bound(hs, hs + bm.n_split, s_hi) - hs);
-    ba.split_seg += sp_lo;
-    ba.n_split = sp_hi - sp_lo;
-    {
-        const int32_t *hss = d->h_split_short.data() + bm.split_short_off;
-        const int32_t q_lo = (int32_t)(std::lower_bound(hss, hss + bm.n_split_short, s_lo) - hss);
-        const int32_t q_hi = (int32_t)(std::lower_bound(hss, hss + bm.n_split_short, s_hi) - hss);
-        ba.split_short += q_lo;
-        ba.n_split_short = q_hi - q_lo;
     }
     if (finish) {
         ba.red_bsum = m->bsum.p;
-        ba.red_nblocks = m->fwd_parts;
+        ba.red_nblocks = m->step.fwd_parts;
         ba.red_rows = (int32_t)bm.rows;
-        ba.red_scal = m->view ? m->view->scal : m->scal();
+        ba.red_scal = m->step.view ? m->step.view->scal : m->scal();
         ba.red_acc = acc;
     }
-    const int64_t nnz_part = (int64_t)e_hi - e_lo;
     {
         ProfScope ps(m, FMHIP_K_BACKWARD, nnz_part, bm.rows);
         HIP_TRY(launch_backward(m->Kp, ba, m->stream));
     }
+    if (whole && fused && fused->mode == 2) {
+        // merged finish: the fixup launch also updates the parameters (its own rows from registers, the rest in
+        // extra workgroups beside it); the column walk above stored its gradient rows as usual
+        ApplyArgs &f = ba.fin;
+        f = apply_args(m, fused->sgd, m->scal() + 2);
+        f.do_w0 = 0;                                   // the statistics block steps w0 (red_w0)
+        f.invb_val = fused->upd.invb;
+        f.use_invb_val = 1;
+        int64_t blocks = (m->n1 * (m->Kp / 4) + 255) / 256;
+        ba.fin_blocks = (int32_t)std::min<int64_t>(std::max<int64_t>(blocks, 1), FMHIP_FIN_BLOCKS);
+        ba.fin_own = d->own_bits.p + bm.own_off;
+        ba.fin_own_bits = (int32_t)std::min<int64_t>(d->own_words * 32, INT32_MAX);
+    }
     {
         ProfScope ps(m, FMHIP_K_FIXUP, nnz_part, bm.rows);
         HIP_TRY(launch_fixup(m->Kp, ba, m->stream));
+        if (whole) HIP_TRY(launch_fixup2(m->Kp, ba, m->stream));
     }
     return FMHIP_OK;
 }
@@ -555,13 +546,14 @@ int fold_scales(fmhip_model_t m) {
     return FMHIP_OK;
 }
 
-// the end of a step's update: the tables' new scales, the gradient clean, the fp64 copy stale, the next profiling step
-static int close_step(fmhip_model_t m, double sv_out, double sw_out) {
+// the end of a step's update: the tables' new scales, the gradient consumed (unless it stays the step's a little longer: the
+// sharded exchange), the fp64 copy stale, the next profiling step
+static int close_step(fmhip_model_t m, double sv_out, double sw_out, bool grad_consumed = true) {
     m->sv = sv_out;
     m->sw = sw_out;
     // fp32 tables lose nothing to a small scale until their values approach the denormal range; fold long before
     if (m->sv < 0x1p-24 || m->sw < 0x1p-24) TRY(fold_scales(m));
-    m->grad_dirty = false;
+    if (grad_consumed) m->step.grad_consumed();
     m->host64_fresh = false;
     ++m->prof_step;
     return FMHIP_OK;
@@ -592,7 +584,7 @@ int step_apply(fmhip_model_t m, const Sgd &s, fmhip_dataset_t d, int64_t b) {
     a.eta_w = (float)(s.eta / sw_out);
     a.do_w0 = 1;
     {
-        ProfScope ps(m, FMHIP_K_APPLY, m->last_nnz, m->last_rows);
+        ProfScope ps(m, FMHIP_K_APPLY, m->step.last_nnz, m->step.last_rows);
         HIP_TRY(launch_apply(m->Kp, a, m->stream));
     }
     return close_step(m, sv_out, sw_out);
@@ -607,7 +599,7 @@ int step_apply_interval(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, c
     a.row_hi = hi;
     a.do_w0 = last ? 1 : 0;
     if (hi > lo || last) {
-        ProfScope ps(m, FMHIP_K_APPLY, m->last_nnz, m->last_rows);
+        ProfScope ps(m, FMHIP_K_APPLY, m->step.last_nnz, m->step.last_rows);
         HIP_TRY(launch_apply(m->Kp, a, m->stream));
     }
     return last ? close_step(m, 1.0, 1.0) : FMHIP_OK;      // every interval folded the pending scale
@@ -624,18 +616,12 @@ int step_apply_shard(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, int6
     a.z_hi = std::max(hi_r, hi);
     a.do_w0 = last ? 1 : 0;
     HIP_TRY(launch_apply_shard(m->Kp, a, stream));
-    if (last) {
-        // every share folded the pending scale; the all-gather spreads the folded rows.  The gradient is left dirty: the
-        // caller's all-gathers still follow (dp_step_sharded clears it after the last one)
-        m->sv = m->sw = 1.0;
-        m->host64_fresh = false;
-        ++m->prof_step;
-    }
-    return FMHIP_OK;
+    // every share folded the pending scale; the all-gather spreads the folded rows.  The gradient is left dirty: the
+    // caller's all-gathers still follow (dp_step_sharded clears it after the last one)
+    return last ? close_step(m, 1.0, 1.0, false) : FMHIP_OK;
 }
 
-int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t n_feat, const float *rows, const GradView *view, int64_t off,
-                    bool last) {
+int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t n_feat, const float *rows, int64_t off, bool last) {
     // (judged as SGD: the touched-rows exchange refuses AdaGrad with decay up front, by the plan's optimizer, on every rank alike —
     // a rank whose optimizer changed since the plan must not stop halfway through the step's collectives)
     if (!lazy_decay_ok(m, s, TrainRule{}))
@@ -649,7 +635,7 @@ int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t 
     a.n_feat = n_feat;
     a.eta_v = (float)(s.eta / sv_out);
     a.eta_w = (float)(s.eta / sw_out);
-    if (view) {
+    if (const GradView *view = m->step.view) {
         a.GV = view->GV + (size_t)off * m->Kp;
         a.Gw = view->Gw + off;
         a.Gb = view->Gb + off;
@@ -658,7 +644,7 @@ int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t 
     }
     a.do_w0 = last ? 1 : 0;
     if (n_feat > 0 || last) {
-        ProfScope ps(m, FMHIP_K_APPLY, m->last_nnz, m->last_rows);
+        ProfScope ps(m, FMHIP_K_APPLY, m->step.last_nnz, m->step.last_rows);
         HIP_TRY(launch_apply(m->Kp, a, m->stream));
     }
     return last ? close_step(m, sv_out, sw_out) : FMHIP_OK;

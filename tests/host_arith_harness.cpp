@@ -6,7 +6,7 @@
 // watch the index arithmetic.  VERDICT r4 next #6; the sanitizers cannot run on the GPU pool.
 //
 // Covered: shard_bounds; feature_counts / rank_from_counts / relabel_columns; finish_batch_meta, plan_bands, als_levels; choose_cuts,
-// interval_edges, shard_share, compact_edges, apply_groups; and the host passes of the dataset build — validate_rows,
+// interval_edges, shard_share, compact_edges, apply_groups; bw_window_step (`host_arith_harness window`: exhaustive); and the host passes of the dataset build — validate_rows,
 // choose_hot_block, split_hot_rows, forward_row_order, sort_rows_by_feature (each for float and double values, with 1 and with
 // 4 threads, which must agree) and own_bitmaps.
 //
@@ -773,7 +773,90 @@ static void check_own_bitmaps(Rng &r) {
         for (size_t f = 0; f < words * 32; ++f) CHECK((own[b * words + f / 32] >> (f & 31) & 1u) == (f <= (size_t)dim && want[b][f] ? 1u : 0u));
 }
 
+// ---- the split step's backward window (bw_window_step: fmhip_step_backward's tiling rule) -------------------------------
+// The intervals [e[j], e[j+1]) of one cut of [0, n1), walked in EVERY order: `used` marks the calls accepted so far (depth of
+// them), which by the rule are the top `depth` intervals (descending) or the bottom ones (ascending, up).  Every interval still
+// unused is offered as the next call: only the one that continues the order may be accepted, with its own flags; any other is
+// refused with the window as it was.  After the last interval the window is closed and refuses everything.
+struct WindowWalk {
+    int64_t n1;
+    std::vector<int64_t> e;
+    int k() const { return (int)e.size() - 1; }
+    int64_t calls = 0;
+
+    BwVerdict call(BwWindow w, int j, bool finish, bool open_top) {
+        ++calls;
+        return bw_window_step(w, n1, e[(size_t)j], open_top ? INT64_MAX : e[(size_t)j + 1], finish);
+    }
+    void walk(BwWindow w, int depth, bool up, unsigned used) {
+        if (depth == k()) {
+            CHECK(w.closed());
+            for (int j = 0; j < k(); ++j)
+                for (int finish = 0; finish < 2; ++finish) {
+                    const BwVerdict v = call(w, j, finish != 0, false);
+                    CHECK(v.refusal == BwRefusal::kClosed && v.next == w);
+                }
+            CHECK(bw_refusal_text(call(w, 0, false, false)) == "fmhip_step_backward without fmhip_step_forward");
+            return;
+        }
+        CHECK(!w.closed());
+        for (int j = 0; j < k(); ++j) {
+            if (used >> j & 1u) continue;
+            // the first call says which way: the top interval descends (a single interval is both, and descends), the bottom one ascends
+            const bool down_ok = (depth == 0 || !up) && j == k() - 1 - depth, up_ok = (depth == 0 ? k() > 1 : up) && j == depth;
+            for (int open_top = 0; open_top < (j == k() - 1 ? 2 : 1); ++open_top) {      // hi beyond n1 is n1
+                const BwVerdict v = call(w, j, false, open_top != 0);
+                if (down_ok || up_ok) {
+                    CHECK(v.refusal == BwRefusal::kNone && v.own == (down_ok ? kOwnLower : kOwnUpper));
+                    CHECK(v.next.closed() == (depth + 1 == k()));
+                    if (!open_top) walk(v.next, depth + 1, up_ok, used | 1u << j);
+                } else {
+                    CHECK(v.refusal == (depth > 0 && up ? BwRefusal::kNotAscending : BwRefusal::kNotDescending) && v.next == w);
+                    CHECK(v.got == (depth > 0 && up ? e[(size_t)j] : open_top ? INT64_MAX : e[(size_t)j + 1]));
+                    CHECK(v.want == (depth == 0 ? n1 : up ? e[(size_t)depth] : e[(size_t)(k() - depth)]));
+                }
+                // finish belongs to the interval that starts at feature 0, and changes nothing else
+                const BwVerdict f = call(w, j, true, open_top != 0);
+                if (j > 0) CHECK(f.refusal == BwRefusal::kFinishAboveZero && f.next == w);
+                else CHECK(f.refusal == v.refusal && f.own == v.own && f.next == v.next);
+            }
+        }
+    }
+};
+
+static void check_backward_window() {
+    int64_t calls = 0;
+    for (int64_t n1 : {1, 2, 7, 300})
+        for (int64_t a = 1; a <= n1; ++a)              // cuts 0 < a < b < c < n1 (a cut at n1: none, and none above it)
+            for (int64_t b = a < n1 ? a + 1 : n1; b <= n1; ++b)
+                for (int64_t c = b < n1 ? b + 1 : n1; c <= n1; ++c) {
+                    WindowWalk ww{n1, {0}};
+                    for (int64_t x : {a, b, c})
+                        if (x < n1) ww.e.push_back(x);
+                    ww.e.push_back(n1);
+                    ww.walk(BwWindow::opened(), 0, false, 0u);
+                    // no forward, no window
+                    CHECK(ww.call(BwWindow{}, ww.k() - 1, false, false).refusal == BwRefusal::kClosed);
+                    calls += ww.calls;
+                }
+    // the refusals' texts, byte for byte
+    BwVerdict v = bw_window_step(BwWindow::opened(), 300, 90, 180, false);
+    CHECK(bw_refusal_text(v) == "feature intervals must tile [0, n+1) in descending order (expected hi = 300, got 180), or start at feature 0 and ascend");
+    v = bw_window_step(BwWindow{180, false}, 300, 0, 90, true);
+    CHECK(bw_refusal_text(v) == "feature intervals must tile [0, n+1) in descending order (expected hi = 180, got 90), or start at feature 0 and ascend");
+    v = bw_window_step(BwWindow{90, true}, 300, 180, 300, false);
+    CHECK(bw_refusal_text(v) == "feature intervals must tile [0, n+1) in ascending order (expected lo = 90, got 180)");
+    v = bw_window_step(BwWindow::opened(), 300, 180, 300, true);
+    CHECK(bw_refusal_text(v) == "finish = 1 belongs to the interval that starts at feature 0");
+    CHECK(bw_refusal_text(bw_window_step(BwWindow::opened(), 300, 0, 300, true)).empty());
+    printf("host_arith_harness: backward window: %lld calls: checks ok\n", (long long)calls);
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "window")) {      // exhaustive and unseeded: a run of its own
+        check_backward_window();
+        return 0;
+    }
     g_seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
     const int cases = argc > 2 ? atoi(argv[2]) : 40;
     Rng r(g_seed);

@@ -607,6 +607,12 @@ def test_host_arithmetic_under_the_sanitizers(tmp_path):
     for seed in (20261005, 7, 99):
         r = subprocess.run([exe, str(seed), "25"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=600)
         assert r.returncode == 0 and b"checks ok" in r.stdout, (seed, r.stderr.decode()[-3000:])
+    # fmhip_step_backward's tiling rule (bw_window_step), exhaustively: n+1 in {1, 2, 7, 300}, every cut of [0, n+1) into 1 to 4
+    # intervals, every order of them — descending accepted with kOwnLower, ascending with kOwnUpper, the window closed after the
+    # last interval, any other order refused at its first wrong call with the window unchanged, finish above feature 0 refused,
+    # a closed window refusing everything, hi = INT64_MAX taken as n+1; the refusals' texts byte for byte
+    r = subprocess.run([exe, "window"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=600)
+    assert r.returncode == 0 and b"backward window" in r.stdout and b"checks ok" in r.stdout, r.stderr.decode()[-3000:]
     # the library itself links this translation unit (not a copy): the build lists it and the host entry points answer the same
     from sparkfm_amd import _build
     assert "fmhip_host.cpp" in _build.HIP_SOURCES
