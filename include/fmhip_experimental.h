@@ -212,6 +212,13 @@ int fmhip_bpr_debug_inverse(struct fmhip_bpr *h, int64_t batch, int32_t *trow, i
  * model's scales (as a training call does) and synchronises. */
 int fmhip_bpr_debug_adaptive(fmhip_model_t m, struct fmhip_bpr *h, int64_t t, int64_t p0, int64_t p1, int32_t *rows, float *scores);
 
+/* ---- the WARP sampler's candidates (tests) -------------------------------------------------- */
+/* What the WARP sampler (include/fmhip_warp.h) sees for the pairs [p0, p1) at epoch t under the model as it stands: its kernel in
+ * its record mode, which looks at every candidate.  rows / scores as fmhip_bpr_debug_adaptive; pos_scores: p1 - p0 entries, the
+ * positive's score s+ of pair p at p - p0.  The mapping, the weights, the trial counts, the inverse map and the sample statistics
+ * are left alone; the switch need not be on.  Folds the model's scales and synchronises. */
+int fmhip_warp_debug(fmhip_model_t m, struct fmhip_bpr *h, int64_t t, int64_t p0, int64_t p1, int32_t *rows, float *scores, float *pos_scores);
+
 #ifdef __cplusplus
 }
 #endif

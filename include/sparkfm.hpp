@@ -11,7 +11,7 @@
 //     sparkfm::FMLearn      S/fm/FMLearn.scala:10-12         the plug-in point: learn(fm, dataset): FMModel
 //     sparkfm::HipSGD       (build-defined; SparkFM ships ALS only) one learn = one epoch of mini-batch SGD on the GPU
 //     sparkfm::HipALS       S/fm/lib/ALS.scala:15-75,202-208 the reference's own learner in fp64 on the GPU
-//     sparkfm::HipBPR       (build-defined) BPR over a contexts and a candidates block, negatives drawn on the device (include/fmhip_bpr.h; n_candidates: include/fmhip_bpr_adaptive.h)
+//     sparkfm::HipBPR       (build-defined) BPR over a contexts and a candidates block, negatives drawn on the device (include/fmhip_bpr.h; n_candidates: include/fmhip_bpr_adaptive.h; sampler: include/fmhip_warp.h)
 //     sparkfm::FM           S/fm/FM.scala:25-33, S/fm/impl/FactorizationMachines.scala:30-51   the fit loop
 //
 // Nothing but include/fmhip.h (the product header), include/fmhip_topk.h (top-K recommendation), include/fmhip_pairing.h (pairwise ranking), include/fmhip_metrics.h (ROC AUC), include/fmhip_ranking.h (ranking evaluation), include/fmhip_weights.h (per-row example weights), include/fmhip_relational.h (relational data) include/fmhip_mcmc.h (the MCMC learner), include/fmhip_mcmc_task.h (its tasks) and include/fmhip_bpr.h (the BPR trainer) is used.  The reference throws JVM exceptions (S/DataCollection.scala:36);
@@ -44,6 +44,7 @@
 #include "fmhip_mcmc_relational.h"
 #include "fmhip_bpr.h"
 #include "fmhip_bpr_adaptive.h"
+#include "fmhip_warp.h"
 
 namespace sparkfm {
 
@@ -740,19 +741,28 @@ class HipMCMC : public FMLearn {
 // FMHIP_LOSS_LOGISTIC is BPR, FMHIP_LOSS_SQUARED the squared pair loss; the model's pairing flag is neither read nor set.
 // n_candidates (1 .. 64; include/fmhip_bpr_adaptive.h): above 1 every epoch draws that many candidates per pair and trains on the
 // one the model scores highest at the epoch's start (once per epoch: later batches see slightly stale choices); 1: uniform.
+// sampler: kAuto is that; kWarp (include/fmhip_warp.h) keeps per pair the first of the n_candidates candidates that violates
+// `margin` (>= 0) against the positive and trains a hinge weighted by the rank estimated from the trials — `loss` is then not set.
 class HipBPR : public FMLearn {
   public:
+    enum Sampler { kAuto = 0, kWarp = 1 };
     double eta, reg0, regw, regv;
     int loss, optimizer;
     double adagrad_eps, adagrad_init;
     fmhip_stats last_stats{};
     fmhip_bpr_sample_stats sample_stats{};
     fmhip_bpr_adaptive_stats adaptive_stats{};
+    fmhip_warp_stats warp_stats{};
     HipBPR(DataSet &contexts, DataSet &candidates, const std::vector<std::vector<int32_t>> &positives, int32_t n_neg = 1, int64_t batch_pairs = 0,
            uint64_t seed = 0, double eta_ = 0.05, double reg0_ = 0.0, double regw_ = 0.0, double regv_ = 0.0, int loss_ = FMHIP_LOSS_LOGISTIC,
-           int optimizer_ = FMHIP_OPT_SGD, double adagrad_eps_ = 1e-10, double adagrad_init_ = 0.1, int32_t n_candidates = 1)
+           int optimizer_ = FMHIP_OPT_SGD, double adagrad_eps_ = 1e-10, double adagrad_init_ = 0.1, int32_t n_candidates = 1,
+           int sampler = kAuto, double margin = 1.0)
         : eta(eta_), reg0(reg0_), regw(regw_), regv(regv_), loss(loss_), optimizer(optimizer_), adagrad_eps(adagrad_eps_), adagrad_init(adagrad_init_),
-          contexts_(contexts), candidates_(candidates), n_neg_(n_neg), batch_pairs_(batch_pairs), seed_(seed), n_candidates_(n_candidates) {
+          contexts_(contexts), candidates_(candidates), n_neg_(n_neg), batch_pairs_(batch_pairs), seed_(seed), n_candidates_(n_candidates),
+          sampler_(sampler), margin_(margin) {
+        if (sampler != kAuto && sampler != kWarp) throw Error(FMHIP_ERR_INVALID, "sampler must be HipBPR::kAuto or HipBPR::kWarp");
+        if (!(margin >= 0.0) || !(margin <= 3.4028234663852886e38)) throw Error(FMHIP_ERR_INVALID, "margin must be a finite number >= 0");
+        if (sampler == kWarp && loss_ != FMHIP_LOSS_LOGISTIC) throw Error(FMHIP_ERR_INVALID, "sampler = kWarp trains its own hinge: leave loss at its default");
         if (n_candidates < 1 || n_candidates > FMHIP_BPR_MAX_CANDIDATES) throw Error(FMHIP_ERR_INVALID, "n_candidates must be in [1, 64]");
         if ((int64_t)positives.size() != contexts.size()) throw Error(FMHIP_ERR_INVALID, "positives must hold one list per context");
         for (size_t u = 0; u < positives.size(); ++u) {
@@ -772,6 +782,8 @@ class HipBPR : public FMLearn {
     int64_t dimension() override { return std::max(contexts_.dimension(), candidates_.dimension()); }
     int64_t n_pairs() const { return (int64_t)inter_ctx_.size() * n_neg_; }
     int32_t n_candidates() const { return n_candidates_; }
+    bool warp() const { return sampler_ == kWarp; }
+    double margin() const { return margin_; }
     // the handle borrows the blocks' device copies: made again when either was unpersisted since (FM's fit loop unpersists its dataset)
     fmhip_bpr_t handle() {
         const fmhip_dataset_t c = contexts_.handle(), i = candidates_.handle();
@@ -780,6 +792,7 @@ class HipBPR : public FMLearn {
             check(fmhip_bpr_create(contexts_.device(), c, i, (int64_t)inter_ctx_.size(), inter_ctx_.data(), inter_cand_.data(), n_neg_, batch_pairs_,
                                    seed_, &h_));
             if (n_candidates_ > 1) check(fmhip_bpr_set_candidates(h_, n_candidates_));
+            if (warp()) check(fmhip_warp_set(h_, 1, margin_));
             for_ctx_ = c;
             for_cand_ = i;
         }
@@ -791,7 +804,7 @@ class HipBPR : public FMLearn {
     }
     FMModel &learn(FMModel &fm) {
         const fmhip_bpr_t h = handle();
-        check(fmhip_model_set_loss(fm.upload(), loss));
+        if (!warp()) check(fmhip_model_set_loss(fm.upload(), loss));      // (WARP's hinge: the model's loss is left as it is)
         check(fmhip_model_set_optimizer(fm.upload(), optimizer, adagrad_eps, adagrad_init));
         check(fmhip_bpr_epoch(fm.upload(), h, epoch_, eta, reg0, regw, regv, nullptr, &last_stats));
         ++epoch_;
@@ -806,15 +819,33 @@ class HipBPR : public FMLearn {
         return fm;
     }
     const fmhip_bpr_sample_stats &resample(int64_t t) {
+        if (warp()) throw Error(FMHIP_ERR_INVALID, "sampler = kWarp: the WARP draw needs a model — resampleWarp(t, fm)");
         if (n_candidates_ > 1) throw Error(FMHIP_ERR_INVALID, "n_candidates > 1: the adaptive draw needs a model — resample(t, fm)");
         check(fmhip_bpr_resample(handle(), t, &sample_stats));
         return sample_stats;
     }
     // the best of n_candidates candidates under the model as it stands (fmhip_bpr_resample_adaptive)
     const fmhip_bpr_adaptive_stats &resample(int64_t t, FMModel &fm) {
+        if (warp()) throw Error(FMHIP_ERR_INVALID, "sampler = kWarp: the draw is resampleWarp(t, fm)");
         const fmhip_bpr_t h = handle();
         check(fmhip_bpr_resample_adaptive(fm.upload(), h, t, &adaptive_stats));
         return adaptive_stats;
+    }
+    // the WARP draw under the model as it stands (fmhip_warp_resample), and what it left per pair
+    const fmhip_warp_stats &resampleWarp(int64_t t, FMModel &fm) {
+        const fmhip_bpr_t h = handle();
+        check(fmhip_warp_resample(fm.upload(), h, t, &warp_stats));
+        return warp_stats;
+    }
+    std::vector<float> pairWeights() {
+        std::vector<float> out((size_t)n_pairs());
+        check(fmhip_warp_weights(handle(), out.data()));
+        return out;
+    }
+    std::vector<int32_t> trials() {
+        std::vector<int32_t> out((size_t)n_pairs());
+        check(fmhip_warp_trials(handle(), out.data()));
+        return out;
     }
     std::vector<int32_t> negatives() {
         std::vector<int32_t> out((size_t)n_pairs());
@@ -839,6 +870,8 @@ class HipBPR : public FMLearn {
     int64_t batch_pairs_;
     uint64_t seed_;
     int32_t n_candidates_;
+    int sampler_;
+    double margin_;
     int64_t epoch_ = 0;
     fmhip_bpr_t h_ = nullptr;
     fmhip_dataset_t for_ctx_ = nullptr, for_cand_ = nullptr;

@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_mcmc_relational.h, include/fmhip_bpr.h, include/fmhip_bpr_adaptive.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_mcmc_relational.h, include/fmhip_bpr.h, include/fmhip_bpr_adaptive.h, include/fmhip_warp.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -41,6 +41,7 @@ SYMBOLS_EXPERIMENTAL = (
     "fmhip_comm_create_external", "fmhip_stream_wait", "fmhip_device_read", "fmhip_device_write",
     "fmhip_comm_profile_begin", "fmhip_comm_profile_end", "fmhip_comm_emulate", "fmhip_comm_emulate_load", "fmhip_comm_emulate_ranks",
     "fmhip_model_get_optimizer_state", "fmhip_model_set_optimizer_state", "fmhip_bpr_debug_inverse", "fmhip_bpr_debug_adaptive",
+    "fmhip_warp_debug",
 )
 # ... and include/fmhip_topk.h — top-K recommendation over (contexts x candidates)
 SYMBOLS_TOPK = ("fmhip_topk", "fmhip_pair_scores")
@@ -75,6 +76,8 @@ SYMBOLS_BPR = ("fmhip_bpr_create", "fmhip_bpr_destroy", "fmhip_bpr_info", "fmhip
 # ... and include/fmhip_bpr_adaptive.h — its adaptive negatives: C candidates per pair, the model's best kept
 SYMBOLS_BPR_ADAPTIVE = ("fmhip_bpr_set_candidates", "fmhip_bpr_get_candidates", "fmhip_bpr_resample_adaptive")
 BPR_MAX_CANDIDATES = 64    # FMHIP_BPR_MAX_CANDIDATES
+# ... and include/fmhip_warp.h — WARP: the first candidate that violates the margin, a hinge weighted by the estimated rank
+SYMBOLS_WARP = ("fmhip_warp_set", "fmhip_warp_get", "fmhip_warp_resample", "fmhip_warp_weights", "fmhip_warp_trials")
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -313,6 +316,14 @@ class BprAdaptiveStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class WarpStats(C.Structure):
+    """fmhip_warp_stats (include/fmhip_warp.h)."""
+    _fields_ = [("pairs", C.c_int64), ("violated", C.c_int64), ("trials", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DatasetOpts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("hot_block", C.c_int32), ("batch_rows", C.c_int64), ("row_block_rows", C.c_int64)]
 
@@ -495,8 +506,15 @@ def load():
     L.fmhip_bpr_get_candidates.argtypes = [vp, P(i32)]
     L.fmhip_bpr_resample_adaptive.argtypes = [vp, vp, i64, P(BprAdaptiveStats)]
     L.fmhip_bpr_debug_adaptive.argtypes = [vp, vp, i64, i64, i64, vp, vp]
+    L.fmhip_warp_set.argtypes = [vp, C.c_int, dbl]
+    L.fmhip_warp_get.argtypes = [vp, P(C.c_int), P(dbl)]
+    L.fmhip_warp_resample.argtypes = [vp, vp, i64, P(WarpStats)]
+    L.fmhip_warp_weights.argtypes = [vp, vp]
+    L.fmhip_warp_trials.argtypes = [vp, vp]
+    L.fmhip_warp_debug.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
-                 + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE):
+                 + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
+                 + SYMBOLS_WARP):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

@@ -31,10 +31,16 @@ class HipBPR(FMLearn):
     squared pair loss); `optimizer` and the AdaGrad settings as ``HipSGD``.  The model's pairing flag is neither read nor set.
     `n_candidates` (1 .. 64): above 1 every epoch draws that many candidates per pair and trains on the one the model scores
     highest at the epoch's start (include/fmhip_bpr_adaptive.h) — once per epoch, so with several batches the later ones see
-    choices made before the earlier batches' updates; 1 is the uniform sampler, bit for bit what it was."""
+    choices made before the earlier batches' updates; 1 is the uniform sampler, bit for bit what it was.
+    `sampler`: "auto" (that: uniform at n_candidates = 1, the best of n_candidates above) or "warp" (include/fmhip_warp.h): every
+    epoch keeps per pair the FIRST of its n_candidates candidates whose score is above the positive's minus `margin` (>= 0), and
+    the step trains a hinge at that margin weighted by the rank estimated from how many candidates that took; pairs without a
+    violator get weight 0.  With "warp" `loss` stays at its default — the hinge takes its place and the model's loss is not set."""
+
+    SAMPLERS = ("auto", "warp")
 
     def __init__(self, contexts, candidates, positives, n_neg=1, batch_pairs=0, seed=0, shuffle=True, eta=0.05, reg0=0.0, regw=0.0,
-                 regv=0.0, loss="logistic", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1, n_candidates=1):
+                 regv=0.0, loss="logistic", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1, n_candidates=1, sampler="auto", margin=1.0):
         for what, d in (("contexts", contexts), ("candidates", candidates)):
             if not isinstance(d, DataSet):
                 raise TypeError("%s must be a DataSet, not %s" % (what, type(d).__name__))
@@ -56,6 +62,15 @@ class HipBPR(FMLearn):
         self._n_candidates = operator.index(n_candidates)
         if not 1 <= self._n_candidates <= _ffi.BPR_MAX_CANDIDATES:
             raise ValueError("n_candidates must be in [1, %d], not %d" % (_ffi.BPR_MAX_CANDIDATES, self._n_candidates))
+        if sampler not in self.SAMPLERS:
+            raise ValueError("sampler must be one of %s, not %r" % (", ".join(repr(s) for s in self.SAMPLERS), sampler))
+        self._sampler = sampler
+        if isinstance(margin, bool) or not isinstance(margin, (int, float, np.integer, np.floating)) \
+                or not 0 <= float(margin) <= float(np.finfo(np.float32).max):      # (the device's margin is fp32; a NaN fails both)
+            raise ValueError("margin must be a finite number >= 0, not %r" % (margin,))
+        self._margin = float(margin)
+        if sampler == "warp" and loss != "logistic":
+            raise ValueError("sampler='warp' trains its own hinge: leave loss at its default, not %r" % (loss,))
         self.seed = operator.index(seed)
         if not 0 <= self.seed < 2 ** 64:
             raise ValueError("seed must be in [0, 2^64), not %r" % (seed,))
@@ -120,12 +135,27 @@ class HipBPR(FMLearn):
             self._h, self._for = h, blocks
             if self._n_candidates > 1:
                 _ffi.check(_ffi.load().fmhip_bpr_set_candidates(h, self._n_candidates))
+            if self.warp:
+                _ffi.check(_ffi.load().fmhip_warp_set(h, 1, self._margin))
         return self._h
 
     @property
     def n_candidates(self):
         """Candidates drawn per pair and epoch (include/fmhip_bpr_adaptive.h); 1: the uniform sampler."""
         return self._n_candidates
+
+    @property
+    def sampler(self):
+        return self._sampler
+
+    @property
+    def margin(self):
+        """The WARP margin (read only with sampler="warp")."""
+        return self._margin
+
+    @property
+    def warp(self):
+        return self._sampler == "warp"
 
     def info(self):
         v = [C.c_int64() for _ in range(4)]
@@ -149,8 +179,14 @@ class HipBPR(FMLearn):
     def resample(self, t, fm=None):
         """Redraws every pair's negative at epoch `t` -> ``sample_stats``.  Without a model the draw is uniform (fmhip_bpr_resample:
         attempts, forced).  With `fm` it is the best of `n_candidates` candidates under the model as it stands
-        (fmhip_bpr_resample_adaptive: attempts, forced, replaced — the pairs whose kept candidate is not the uniform draw)."""
-        if fm is None:
+        (fmhip_bpr_resample_adaptive: attempts, forced, replaced — the pairs whose kept candidate is not the uniform draw).
+        With sampler="warp" it is the WARP draw under `fm` (fmhip_warp_resample: pairs, violated, trials), and a model is required."""
+        if self.warp:
+            if fm is None:
+                raise ValueError("sampler='warp': the WARP draw needs a model — resample(t, fm)")
+            st = _ffi.WarpStats()
+            _ffi.check(_ffi.load().fmhip_warp_resample(fm.handle, self.handle, operator.index(t), C.byref(st)))
+        elif fm is None:
             if self._n_candidates > 1:
                 raise ValueError("n_candidates = %d: the adaptive draw needs a model — resample(t, fm)" % self._n_candidates)
             st = _ffi.BprSampleStats()
@@ -164,14 +200,50 @@ class HipBPR(FMLearn):
     def candidate_draws(self, fm, t, p0=0, p1=None):
         """(rows int32, scores float32), each [p1 - p0, n_candidates]: what the adaptive sampler sees for the pairs [p0, p1) at epoch
         `t` under `fm` — every candidate's row and its score yq_i + <q_u, q_i> (fmhip_bpr_debug_adaptive).  Changes no draw."""
-        p0 = operator.index(p0)
-        p1 = self.n_pairs if p1 is None else operator.index(p1)
-        if not 0 <= p0 < p1 <= self.n_pairs:
-            raise ValueError("pairs [%d, %d) must be a non-empty range inside [0, %d)" % (p0, p1, self.n_pairs))
+        if self.warp:
+            raise ValueError("sampler='warp': candidate_draws is the adaptive sampler's record — use warp_draws(fm, t)")
+        p0, p1 = self._pair_range(p0, p1)
         rows = np.empty((p1 - p0, self._n_candidates), np.int32)
         scores = np.empty((p1 - p0, self._n_candidates), np.float32)
         _ffi.check(_ffi.load().fmhip_bpr_debug_adaptive(fm.handle, self.handle, operator.index(t), p0, p1, _ffi.ptr(rows), _ffi.ptr(scores)))
         return rows, scores
+
+    def _pair_range(self, p0, p1):
+        p0 = operator.index(p0)
+        p1 = self.n_pairs if p1 is None else operator.index(p1)
+        if not 0 <= p0 < p1 <= self.n_pairs:
+            raise ValueError("pairs [%d, %d) must be a non-empty range inside [0, %d)" % (p0, p1, self.n_pairs))
+        return p0, p1
+
+    def _need_warp(self, what):
+        if not self.warp:
+            raise ValueError("%s belongs to sampler='warp', not %r" % (what, self._sampler))
+
+    def warp_draws(self, fm, t, p0=0, p1=None):
+        """(rows int32 [p1 - p0, n_candidates], scores float32 of the same shape, pos_scores float32 [p1 - p0]): what the WARP
+        sampler sees for the pairs [p0, p1) at epoch `t` under `fm` — every candidate's row and score and the positive's score s+
+        (fmhip_warp_debug).  Changes no draw."""
+        self._need_warp("warp_draws")
+        p0, p1 = self._pair_range(p0, p1)
+        rows = np.empty((p1 - p0, self._n_candidates), np.int32)
+        scores = np.empty((p1 - p0, self._n_candidates), np.float32)
+        pos = np.empty(p1 - p0, np.float32)
+        _ffi.check(_ffi.load().fmhip_warp_debug(fm.handle, self.handle, operator.index(t), p0, p1, _ffi.ptr(rows), _ffi.ptr(scores), _ffi.ptr(pos)))
+        return rows, scores, pos
+
+    def pair_weights(self):
+        """float32 [n_pairs]: the standing WARP draw's pair weights c_p = W[N_p] (0 where no candidate violated)."""
+        self._need_warp("pair_weights")
+        out = np.empty(self.n_pairs, np.float32)
+        _ffi.check(_ffi.load().fmhip_warp_weights(self.handle, _ffi.ptr(out)))
+        return out
+
+    def trials(self):
+        """int32 [n_pairs]: the standing WARP draw's N_p — 1 + the index of the first violating candidate, 0 for none."""
+        self._need_warp("trials")
+        out = np.empty(self.n_pairs, np.int32)
+        _ffi.check(_ffi.load().fmhip_warp_trials(self.handle, _ffi.ptr(out)))
+        return out
 
     def negatives(self):
         """int32 [n_pairs]: the current draw (the draw at t = 0 until the first resample or learn)."""
@@ -210,7 +282,8 @@ class HipBPR(FMLearn):
     def _set_rule(self, fm):
         """The model's loss and optimizer (never its pairing flag: the calls are pairwise by construction)."""
         L = _ffi.load()
-        _ffi.check(L.fmhip_model_set_loss(fm.handle, self._loss_code))
+        if not self.warp:      # (WARP trains its own hinge: the model's loss is left as it is)
+            _ffi.check(L.fmhip_model_set_loss(fm.handle, self._loss_code))
         _ffi.check(L.fmhip_model_set_optimizer(fm.handle, self._opt_code, self.adagrad_eps, self.adagrad_init))
 
     def learn(self, fm, dataset=None):

@@ -44,6 +44,21 @@ constexpr int kBprMaxCand = 64;
 int bpr_adaptive_blocks(int Kp, int64_t n_pairs);
 hipError_t launch_bpr_sample_adaptive(int Kp, const BprAdaptiveArgs &a, hipStream_t s);
 
+// The WARP sampler (k_bpr_sample_warp; the rule: include/fmhip_warp.h): the adaptive sampler's groups, draws and scores, with the
+// pair's positive (map[2p]) gathered and scored first by the same code; the kept row is the FIRST candidate whose score is
+// strictly above thr = s+ - margin, N = 1 + its index (0: none, candidate 0's row kept).  Lane 0 writes map[2p + 1], the pair's
+// weight W[N] to c[2p] and c[2p + 1], and N to trials[p].  A group stops scoring at the end of the chunk that holds its first
+// violator.  Record mode: pairs [p0, p1), every candidate's row and score and s+ out, nothing else written, no early stop.
+struct BprWarpArgs {
+    BprAdaptiveArgs a;         // a.s.part: [bpr_adaptive_blocks][2] {violated pairs, sum of N over them}; a.s.total: [2]
+    float margin;
+    const float *W;            // [n_cand + 1] W[0] = 0, W[n] the weight of a pair whose first violator is candidate n - 1
+    float *c;                  // [2 * n_pairs] the pairs' weights, a valid PairArgs::c (fm_pairing.h)
+    int32_t *trials;           // [n_pairs] N
+    float *rec_pos;            // record mode: [p1 - p0] s+
+};
+hipError_t launch_bpr_sample_warp(int Kp, const BprWarpArgs &a, hipStream_t s);
+
 // The inverse map of ONE batch (fmhip::host::RelationInverse::append_batch, array for array) from the batch's slice of the mapping:
 // one radix sort of (block row, batch-local row) words over the bits the two need, the lists read off the sorted words, the work
 // list at the cut by scans.  Every output array has the capacity its worst case needs: trow / tj / wt / wbeg / wdst `rows`, tptr

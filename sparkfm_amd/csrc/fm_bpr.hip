@@ -2,7 +2,8 @@
 // around one rocPRIM radix sort and two scans rebuild the candidates relation's inverse map of a batch.  Integer arithmetic only;
 // every address has one writer and nothing depends on the launch shape.  k_bpr_sample_adaptive (include/fmhip_bpr_adaptive.h) draws
 // several candidates per pair with the same integer code and keeps the one the model scores highest: the one place with fp32 in it,
-// a dot product whose summation order the row width alone fixes.
+// a dot product whose summation order the row width alone fixes.  k_bpr_sample_warp (include/fmhip_warp.h) scores the same candidates
+// the same way and keeps the first one that violates the margin against the pair's positive, with the pair's rank weight beside it.
 #include "fm_bpr.h"
 #include "fm_device.h"      // f4dot; grid_blocks (fm_kernels.h)
 #include "mcmc_rng.h"
@@ -162,6 +163,117 @@ hipError_t launch_adaptive(const BprAdaptiveArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---- the WARP sampler (fm_bpr.h: BprWarpArgs) ---------------------------------------------------------------------------------------
+
+// The adaptive kernel's lane layout, draws and score order.  The positive's row is gathered and scored first, by the code that
+// scores a candidate; a candidate violates iff its score is strictly above thr (false for a NaN on either side).  Every lane of a
+// group holds the same scores, so `n_first` and the early exit are uniform over the group: a group that leaves the candidate loops
+// leaves whole, and the width-G shuffles of the groups still in them read only their own lanes.
+template <int G, bool RECORD>
+__global__ __launch_bounds__(kT) void k_bpr_sample_warp(BprWarpArgs w) {
+    constexpr int KP = 4 * G, GPB = kT / G;
+    const BprAdaptiveArgs &a = w.a;
+    const int l = threadIdx.x & (G - 1), grp = threadIdx.x / G;
+    const int64_t first = RECORD ? a.p0 : 0, end = RECORD ? a.p1 : a.s.n_pairs;
+    const int C = a.n_cand;
+    u64 violated = 0, trials = 0;
+    for (int64_t base = first + (int64_t)blockIdx.x * GPB; base < end; base += (int64_t)gridDim.x * GPB) {
+        const bool live = base + grp < end;
+        const int64_t p = live ? base + grp : end - 1;
+        const int32_t u = a.s.ictx[p / a.s.n_neg];
+        const int64_t lo = a.s.pptr[u];
+        const int32_t len = (int32_t)(a.s.pptr[u + 1] - lo);
+        float4 qu = reinterpret_cast<const float4 *>(a.Qu + (size_t)u * KP)[l];
+        if (4 * l + 0 >= a.k) qu.x = 0.f;      // the packed slot and the padding are no factors
+        if (4 * l + 1 >= a.k) qu.y = 0.f;
+        if (4 * l + 2 >= a.k) qu.z = 0.f;
+        if (4 * l + 3 >= a.k) qu.w = 0.f;
+        float thr;
+        {
+            const int32_t ipos = a.s.map[2 * p];      // (the positive: no sampler writes the even entries)
+            const float4 qp = reinterpret_cast<const float4 *>(a.Qi + (size_t)ipos * KP)[l];
+            const float yp = a.yqi[ipos];
+            float dp = f4dot(qu, qp);
+#pragma unroll
+            for (int m = G >> 1; m >= 1; m >>= 1) dp += __shfl_xor(dp, m, G);
+            const float spos = yp + dp;
+            if (RECORD && live && l == 0) w.rec_pos[p - a.p0] = spos;
+            thr = spos - w.margin;
+        }
+        int32_t keep = 0, n_first = 0;
+        for (int c0 = 0; c0 < C && (RECORD || n_first == 0); c0 += G) {
+            // the group's lanes draw candidates c0 .. c0 + G - 1 side by side
+            int32_t mine = 0;
+            if (c0 + l < C) {
+                int at = 0, f = 0;
+                mine = rng::negative_row(a.s.seed, (uint32_t)p, a.s.t, (uint32_t)a.s.M, a.s.prow + lo, len, &at, &f, (uint32_t)(c0 + l) << 4);
+            }
+            const int n = C - c0 < G ? C - c0 : G;
+            for (int j0 = 0; j0 < n && (RECORD || n_first == 0); j0 += kCandChunk) {
+                int32_t row[kCandChunk];
+                float4 qi[kCandChunk];
+                float yq[kCandChunk], d[kCandChunk];
+#pragma unroll
+                for (int jj = 0; jj < kCandChunk; ++jj) {
+                    const int j = j0 + jj < n ? j0 + jj : n - 1;       // (past the last candidate: the last one again, not compared)
+                    row[jj] = __shfl(mine, j, G);
+                    qi[jj] = reinterpret_cast<const float4 *>(a.Qi + (size_t)row[jj] * KP)[l];
+                    yq[jj] = a.yqi[row[jj]];
+                }
+#pragma unroll
+                for (int jj = 0; jj < kCandChunk; ++jj) d[jj] = f4dot(qu, qi[jj]);
+#pragma unroll
+                for (int m = G >> 1; m >= 1; m >>= 1)
+#pragma unroll
+                    for (int jj = 0; jj < kCandChunk; ++jj) d[jj] += __shfl_xor(d[jj], m, G);
+#pragma unroll
+                for (int jj = 0; jj < kCandChunk; ++jj) {
+                    const int c = c0 + j0 + jj;
+                    if (j0 + jj >= n) break;
+                    const float s = yq[jj] + d[jj];
+                    if (RECORD && live && l == 0) {
+                        const size_t at = (size_t)(p - a.p0) * (size_t)C + (size_t)c;
+                        a.rec_rows[at] = row[jj];
+                        a.rec_scores[at] = s;
+                    }
+                    if (c == 0) keep = row[jj];                        // no violator: candidate 0's row
+                    if (n_first == 0 && s > thr) {                     // the first violator; a NaN is never greater
+                        n_first = c + 1;
+                        keep = row[jj];
+                    }
+                }
+            }
+        }
+        if (!RECORD && live && l == 0) {
+            a.s.map[2 * p + 1] = keep;
+            const float cw = w.W[n_first];
+            reinterpret_cast<float2 *>(w.c)[p] = make_float2(cw, cw);
+            w.trials[p] = n_first;
+            violated += n_first != 0 ? 1u : 0u;
+            trials += (u64)n_first;
+        }
+    }
+    if (RECORD) return;
+    u64 v[2] = {violated, trials};
+    block_sums_u64<2>(v, a.s.part + 2 * (size_t)blockIdx.x);
+}
+
+template <int G>
+hipError_t launch_warp(const BprWarpArgs &w, hipStream_t s) {
+    const bool record = w.a.rec_rows != nullptr;
+    const int64_t n = record ? (int64_t)w.a.p1 - w.a.p0 : w.a.s.n_pairs;
+    const int blocks = bpr_adaptive_blocks(4 * G, n);
+    if (record) {
+        hipLaunchKernelGGL((k_bpr_sample_warp<G, true>), dim3((unsigned)blocks), dim3(kT), 0, s, w);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((k_bpr_sample_warp<G, false>), dim3((unsigned)blocks), dim3(kT), 0, s, w);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_bpr_total<2>, dim3(1), dim3(kT), 0, s, w.a.s.part, blocks, w.a.s.total);
+    return hipGetLastError();
+}
+
 // ---- the inverse map --------------------------------------------------------------------------------------------------------------
 
 // bits that hold every value of [0, n): at least 1
@@ -315,6 +427,21 @@ hipError_t launch_bpr_sample_adaptive(int Kp, const BprAdaptiveArgs &a, hipStrea
         case 64: return launch_adaptive<16>(a, s);
         case 128: return launch_adaptive<32>(a, s);
         case 256: return launch_adaptive<64>(a, s);
+        default: return hipErrorInvalidValue;      // (padded_factors: a power of two in [32, 256])
+    }
+}
+
+hipError_t launch_bpr_sample_warp(int Kp, const BprWarpArgs &w, hipStream_t s) {
+    const BprAdaptiveArgs &a = w.a;
+    if (a.n_cand < 1 || a.n_cand > kBprMaxCand || a.k < 0 || a.k > Kp || !(w.margin >= 0.f)) return hipErrorInvalidValue;
+    if (a.rec_rows) {
+        if (!a.rec_scores || !w.rec_pos || a.p0 < 0 || a.p1 > a.s.n_pairs || a.p0 >= a.p1) return hipErrorInvalidValue;
+    } else if (!w.W || !w.c || !w.trials) return hipErrorInvalidValue;
+    switch (Kp) {
+        case 32: return launch_warp<8>(w, s);
+        case 64: return launch_warp<16>(w, s);
+        case 128: return launch_warp<32>(w, s);
+        case 256: return launch_warp<64>(w, s);
         default: return hipErrorInvalidValue;      // (padded_factors: a power of two in [32, 256])
     }
 }

@@ -23,7 +23,12 @@ struct PairArgs {
     int32_t pack_k;      // >= 0: packed rows (FwdArgs::pack_k)
     int32_t loss;        // Loss (fm_kernels.h)
     const float *c;      // weighted dataset (fm_weights.h): [2 * n_pairs] the batch's row weights, pair j's = c[2j]; NULL: none
+    float margin;        // loss == kPairLossHinge: m
 };
+
+// A third value of PairArgs::loss, internal to the library (fmhip_model_set_loss does not know it): the WARP step's hinge
+// (include/fmhip_warp.h), g = (d < margin) ? -1 : 0 times the pair's weight c[2j] — c is then required.  A NaN d gives g = 0.
+constexpr int32_t kPairLossHinge = 2;
 
 // n_partials: the launch's grid (slot_blocks, fm_finish.h) = the number of per-block statistic partials it writes (<= kMaxFwdBlocks)
 hipError_t launch_pair_finish(int Kp, const PairArgs &a, hipStream_t s, int *n_partials);

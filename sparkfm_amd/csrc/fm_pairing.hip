@@ -14,7 +14,9 @@ namespace {
 // a sum over rows in any other order is not.
 // WEIGHTED (a weighted dataset, fm_weights.h): the pair's residual is c_2j * g — row 2j's weight; row 2j+1's is not read — so the
 // rows' residuals still sum to exactly zero.  The unweighted instances do not see the pointer.
-template <int LPN, int J, bool PACKED, bool WEIGHTED>
+// HINGE (the WARP step, fm_pairing.h: kPairLossHinge; always WEIGHTED): g = -1 where d < margin, else 0 — also for a NaN d, which
+// the non-finite count still sees — times the pair's weight.  The other instances do not see the margin.
+template <int LPN, int J, bool PACKED, bool WEIGHTED, bool HINGE = false>
 __global__ __launch_bounds__(kBlock) void k_pair_finish(PairArgs a) {
     constexpr int KP = 4 * LPN * J;
     const SlotLoop<LPN> sl;
@@ -30,7 +32,9 @@ __global__ __launch_bounds__(kBlock) void k_pair_finish(PairArgs a) {
         const float2 yh = reinterpret_cast<const float2 *>(a.yhat)[j], yy = reinterpret_cast<const float2 *>(a.y)[j];
         const float d = yh.x - yh.y, dy = yy.x - yy.y;
         float z;
-        float g = logistic ? pair_sigma_residual(d, dy > 0.f, z) : d - dy;
+        float g;
+        if (HINGE) g = d < a.margin ? -1.f : 0.f;
+        else g = logistic ? pair_sigma_residual(d, dy > 0.f, z) : d - dy;
         if (WEIGHTED) g = weighted_residual(a.c[2 * j], g);
         const float e0 = g, e1 = -g;
 #pragma unroll
@@ -75,12 +79,16 @@ __global__ __launch_bounds__(kBlock) void k_pair_score(const float *yhat, const 
 }  // namespace
 
 hipError_t launch_pair_finish(int Kp, const PairArgs &a, hipStream_t s, int *n_partials) {
+    if (a.loss == kPairLossHinge && (!a.c || !(a.margin >= 0.f))) return hipErrorInvalidValue;
     const int blocks = slot_blocks(Kp, a.n_pairs);
     if (n_partials) *n_partials = blocks;
     const dim3 g((unsigned)blocks), b(kBlock);
     return for_slot_shape(Kp, [&](auto lpn, auto j) {
         constexpr int L = decltype(lpn)::value, JJ = decltype(j)::value;
-        if (a.c) {
+        if (a.loss == kPairLossHinge) {
+            if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<L, JJ, true, true, true>), g, b, 0, s, a);
+            else hipLaunchKernelGGL((k_pair_finish<L, JJ, false, true, true>), g, b, 0, s, a);
+        } else if (a.c) {
             if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<L, JJ, true, true>), g, b, 0, s, a);
             else hipLaunchKernelGGL((k_pair_finish<L, JJ, false, true>), g, b, 0, s, a);
         } else if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<L, JJ, true, false>), g, b, 0, s, a);

@@ -2,14 +2,17 @@
 // borrowed blocks), the resample
 //     k_bpr_sample (the candidates mapping's odd entries) -> per batch the inverse map on the device (fm_bpr.hip) -> the counts back
 // (adaptive, include/fmhip_bpr_adaptive.h: the two blocks' kFwdQ forwards on the model's stream first, then k_bpr_sample_adaptive in
-// k_bpr_sample's place) and the training calls, which are the relational step in its pairs mode (rel_step, fmhip_relational.hip).  The kernels are in
+// k_bpr_sample's place; WARP, include/fmhip_warp.h: the same with k_bpr_sample_warp, which also leaves the pairs' weights for the
+// step's hinge) and the training calls, which are the relational step in its pairs mode (rel_step, fmhip_relational.hip).  The kernels are in
 // fm_bpr.hip; the host arithmetic (the positives' lists, the sampler's twin) in fmhip_host.cpp.
 #include "fmhip_internal.h"
 #include "../../include/fmhip_bpr_adaptive.h"
+#include "../../include/fmhip_warp.h"
 #include "fm_bpr.h"
 #include "fm_relational.h"
 
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <new>
 #include <vector>
@@ -86,17 +89,53 @@ int adaptive_args(fmhip_model_t m, fmhip_bpr_t h, int64_t t, BprAdaptiveArgs *ou
     return FMHIP_OK;
 }
 
+// What the WARP sampler reads and writes, queued as adaptive_args queues it: the weight table (made on the host when the candidate
+// count has changed, uploaded on the handle's stream), the pairs' weights and trial counts, the {violated, trials} partials
+int warp_args(fmhip_model_t m, fmhip_bpr_t h, int64_t t, BprWarpArgs *out) {
+    BprWarpArgs wa{};
+    TRY(adaptive_args(m, h, t, &wa.a));
+    TRY(h->wpart.ensure(2 * (size_t)bpr_adaptive_blocks(m->Kp, h->n_pairs)));
+    TRY(h->wtotal.ensure(2));
+    TRY(h->wc.ensure(2 * (size_t)h->n_pairs));
+    TRY(h->wtrials.ensure((size_t)h->n_pairs));
+    TRY(h->wtab.ensure((size_t)kBprMaxCand + 1));
+    if (h->wtab_cand != h->n_cand) {
+        h->h_wtab.assign((size_t)h->n_cand + 1, 0.f);
+        warp_weight_table(h->M, h->n_cand, h->h_wtab.data());
+        h->wtab_cand = h->n_cand;
+    }
+    HIP_TRY(hipMemcpyAsync(h->wtab.p, h->h_wtab.data(), h->h_wtab.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    wa.a.s.part = h->wpart.p;
+    wa.a.s.total = h->wtotal.p;
+    wa.margin = (float)h->warp_margin;
+    wa.W = h->wtab.p;
+    wa.c = h->wc.p;
+    wa.trials = h->wtrials.p;
+    *out = wa;
+    return FMHIP_OK;
+}
+
+enum Sampler { kUniform, kAdaptive, kWarp };
+
 // the sampler at epoch t, the inverse map of every batch, the batches' counts (one synchronisation); the handle's own stream.
-// m given: the adaptive sampler under that model (the caller has checked the two against each other and holds the model's lock),
-// else the uniform one.  total: {attempts, forced} or, adaptive, {attempts, forced, replaced}
-int resample(fmhip_bpr_t h, int64_t t, unsigned long long *total_out, fmhip_model_t m = nullptr) {
+// m given: the adaptive sampler — or, warp, the WARP sampler — under that model (the caller has checked the two against each other
+// and holds the model's lock), else the uniform one.  total: {attempts, forced}; adaptive, {attempts, forced, replaced}; WARP,
+// {violated, trials}
+int resample(fmhip_bpr_t h, int64_t t, unsigned long long *total_out, fmhip_model_t m = nullptr, bool warp = false) {
     TRY(check_epoch_index(t));
     TRY(set_device(h->device));
     fmhip_relational_t R = h->R;
     fmhip_relational::Relation &rel = *R->rels[1];
-    const int n_total = m ? 3 : 2;
+    const Sampler which = !m ? kUniform : warp ? kWarp : kAdaptive;
+    const int n_total = which == kAdaptive ? 3 : 2;
     const unsigned long long *d_total = nullptr;
-    if (m) {
+    if (which == kWarp) {
+        h->warp_drawn = false;                // (until this draw has come back whole)
+        BprWarpArgs wa{};
+        TRY(warp_args(m, h, t, &wa));
+        HIP_TRY(launch_bpr_sample_warp(m->Kp, wa, h->stream));
+        d_total = h->wtotal.p;
+    } else if (m) {
         BprAdaptiveArgs aa{};
         TRY(adaptive_args(m, h, t, &aa));
         HIP_TRY(launch_bpr_sample_adaptive(m->Kp, aa, h->stream));
@@ -148,8 +187,26 @@ int resample(fmhip_bpr_t h, int64_t t, unsigned long long *total_out, fmhip_mode
         max_part = std::max(max_part, c[3]);
     }
     rel.max_part = max_part;      // (the step's workspace grows to it: ensure_rel_workspace)
+    if (which == kWarp) h->warp_drawn = true;
     if (total_out)
         for (int i = 0; i < 3; ++i) total_out[i] = total[i];
+    return FMHIP_OK;
+}
+
+// a handle whose WARP switch is on takes its draws from fmhip_warp_resample alone
+int refuse_under_warp(fmhip_bpr_t h, const char *call) {
+    if (h->warp) return fail(FMHIP_ERR_INVALID, "%s: WARP is on for this trainer (fmhip_warp_set) — its draw is fmhip_warp_resample", call);
+    return FMHIP_OK;
+}
+
+// the hinge a step of this handle trains: the standing WARP draw's weights and the margin; WARP off: none (*out = nullptr)
+int step_hinge(fmhip_bpr_t h, PairHinge *store, const PairHinge **out) {
+    *out = nullptr;
+    if (!h->warp) return FMHIP_OK;
+    if (!h->warp_drawn)
+        return fail(FMHIP_ERR_INVALID, "WARP is on and no WARP draw stands since fmhip_warp_set: call fmhip_warp_resample (or fmhip_bpr_epoch) first");
+    *store = PairHinge{h->wc.p, (float)h->warp_margin};
+    *out = store;
     return FMHIP_OK;
 }
 
@@ -278,6 +335,7 @@ int fmhip_bpr_info(fmhip_bpr_t h, int64_t *n_pairs, int64_t *dimension, int64_t 
 
 int fmhip_bpr_resample(fmhip_bpr_t h, int64_t t, fmhip_bpr_sample_stats *stats) {
     if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    TRY(refuse_under_warp(h, "fmhip_bpr_resample"));
     unsigned long long total[3];
     TRY(resample(h, t, total));
     if (stats) {
@@ -305,6 +363,7 @@ int fmhip_bpr_get_candidates(fmhip_bpr_t h, int32_t *n_cand) {
 int fmhip_bpr_resample_adaptive(fmhip_model_t m, fmhip_bpr_t h, int64_t t, fmhip_bpr_adaptive_stats *stats) {
     WriteLock lock(m);
     TRY(check_bpr(m, h));
+    TRY(refuse_under_warp(h, "fmhip_bpr_resample_adaptive"));
     unsigned long long total[3];
     TRY(resample(h, t, total, m));
     if (stats) {
@@ -338,6 +397,86 @@ int fmhip_bpr_debug_adaptive(fmhip_model_t m, struct fmhip_bpr *h, int64_t t, in
     return FMHIP_OK;
 }
 
+// ---- WARP (include/fmhip_warp.h) ----------------------------------------------------------------------------------------------------
+
+int fmhip_warp_set(fmhip_bpr_t h, int enabled, double margin) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (!(margin >= 0.0) || !std::isfinite(margin) || !std::isfinite((float)margin))
+        return fail(FMHIP_ERR_INVALID, "margin = %g: the WARP margin is a finite number >= 0", margin);
+    h->warp = enabled != 0;
+    h->warp_margin = margin;
+    h->warp_drawn = false;
+    return FMHIP_OK;
+}
+
+int fmhip_warp_get(fmhip_bpr_t h, int *enabled, double *margin) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (enabled) *enabled = h->warp ? 1 : 0;
+    if (margin) *margin = h->warp_margin;
+    return FMHIP_OK;
+}
+
+int fmhip_warp_resample(fmhip_model_t m, fmhip_bpr_t h, int64_t t, fmhip_warp_stats *stats) {
+    WriteLock lock(m);
+    TRY(check_bpr(m, h));
+    if (!h->warp) return fail(FMHIP_ERR_INVALID, "WARP is off for this trainer: turn it on with fmhip_warp_set");
+    unsigned long long total[3];
+    TRY(resample(h, t, total, m, true));
+    if (stats) {
+        stats->pairs = h->n_pairs;
+        stats->violated = (int64_t)total[0];
+        stats->trials = (int64_t)total[1];
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_warp_weights(fmhip_bpr_t h, float *out) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    if (!h->warp_drawn) return fail(FMHIP_ERR_INVALID, "no WARP draw stands: call fmhip_warp_resample first");
+    TRY(set_device(h->device));
+    std::vector<float> c((size_t)(2 * h->n_pairs));
+    HIP_TRY(hipMemcpy(c.data(), h->wc.p, c.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int64_t p = 0; p < h->n_pairs; ++p) out[p] = c[(size_t)(2 * p)];
+    return FMHIP_OK;
+}
+
+int fmhip_warp_trials(fmhip_bpr_t h, int32_t *out) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    if (!h->warp_drawn) return fail(FMHIP_ERR_INVALID, "no WARP draw stands: call fmhip_warp_resample first");
+    TRY(set_device(h->device));
+    HIP_TRY(hipMemcpy(out, h->wtrials.p, (size_t)h->n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return FMHIP_OK;
+}
+
+int fmhip_warp_debug(fmhip_model_t m, struct fmhip_bpr *h, int64_t t, int64_t p0, int64_t p1, int32_t *rows, float *scores, float *pos_scores) {
+    WriteLock lock(m);
+    TRY(check_bpr(m, h));
+    TRY(check_epoch_index(t));
+    if (p0 < 0 || p1 > h->n_pairs || p0 >= p1)
+        return fail(FMHIP_ERR_INVALID, "pairs [%lld, %lld): a non-empty range inside [0, %lld)", (long long)p0, (long long)p1, (long long)h->n_pairs);
+    if (!rows || !scores || !pos_scores) return fail(FMHIP_ERR_INVALID, "an out array is NULL");
+    const size_t np = (size_t)(p1 - p0), n = np * (size_t)h->n_cand;
+    TRY(h->rec_rows.ensure(n));
+    TRY(h->rec_scores.ensure(n));
+    TRY(h->rec_pos.ensure(np));
+    BprWarpArgs wa{};
+    TRY(adaptive_args(m, h, t, &wa.a));
+    wa.a.p0 = (int32_t)p0;
+    wa.a.p1 = (int32_t)p1;
+    wa.a.rec_rows = h->rec_rows.p;
+    wa.a.rec_scores = h->rec_scores.p;
+    wa.rec_pos = h->rec_pos.p;
+    wa.margin = (float)h->warp_margin;
+    HIP_TRY(launch_bpr_sample_warp(m->Kp, wa, h->stream));
+    HIP_TRY(hipMemcpyAsync(rows, h->rec_rows.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(scores, h->rec_scores.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(pos_scores, h->rec_pos.p, np * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return FMHIP_OK;
+}
+
 int fmhip_bpr_negatives(fmhip_bpr_t h, int32_t *out) {
     if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
     if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
@@ -353,7 +492,10 @@ int fmhip_bpr_step(fmhip_model_t m, fmhip_bpr_t h, int64_t batch, double eta, do
     TRY(check_bpr(m, h));
     if (batch < 0 || batch >= (int64_t)h->R->batches.size())
         return fail(FMHIP_ERR_INVALID, "batch %lld out of range [0, %zu)", (long long)batch, h->R->batches.size());
-    TRY(rel_step(m, h->R, batch, Sgd{eta, reg0, regw, regv}, nullptr, true));
+    PairHinge hinge_store{};
+    const PairHinge *hinge = nullptr;
+    TRY(step_hinge(h, &hinge_store, &hinge));
+    TRY(rel_step(m, h->R, batch, Sgd{eta, reg0, regw, regv}, nullptr, true, hinge));
     if (stats) {
         memset(stats, 0, sizeof *stats);
         TRY(read_scal(m, stats));
@@ -371,12 +513,16 @@ int fmhip_bpr_epoch(fmhip_model_t m, fmhip_bpr_t h, int64_t t, double eta, doubl
     if (order)
         for (int64_t j = 0; j < nb; ++j)
             if (order[j] < 0 || order[j] >= nb) return fail(FMHIP_ERR_INVALID, "batch %lld out of range [0, %lld)", (long long)order[j], (long long)nb);
-    TRY(resample(h, t, nullptr, h->n_cand > 1 ? m : nullptr));
+    if (h->warp) TRY(resample(h, t, nullptr, m, true));
+    else TRY(resample(h, t, nullptr, h->n_cand > 1 ? m : nullptr));
+    PairHinge hinge_store{};
+    const PairHinge *hinge = nullptr;
+    TRY(step_hinge(h, &hinge_store, &hinge));
     HIP_TRY(hipMemsetAsync(m->acc.p, 0, 4 * sizeof(double), m->stream));
     const Sgd sgd{eta, reg0, regw, regv};
     int64_t nnz = 0;
     for (int64_t j = 0; j < nb; ++j) {
-        TRY(rel_step(m, h->R, order ? order[j] : j, sgd, m->acc.p, true));
+        TRY(rel_step(m, h->R, order ? order[j] : j, sgd, m->acc.p, true, hinge));
         nnz += m->step.last_nnz;
     }
     if (stats) {

@@ -797,6 +797,24 @@ int32_t bpr_negative(uint64_t seed, uint32_t p, uint32_t t, int32_t M, const int
     return bpr_candidate(seed, p, 0, t, M, list, len, attempts, forced);
 }
 
+void warp_weight_table(int64_t M, int C, float *out) {
+    out[0] = 0.f;
+    double h = 0.0;
+    int64_t j = 0;
+    for (int n = C; n >= 1; --n) {      // (M - 1) / n grows as n falls: the sum runs on from where it stood
+        const int64_t r = std::max<int64_t>(1, (M - 1) / n);
+        while (j < r) h += 1.0 / (double)++j;
+        out[n] = (float)h;
+    }
+}
+
+int warp_first_violator(const float *scores, int C, float s_pos, float margin) {
+    const float thr = s_pos - margin;
+    for (int c = 0; c < C; ++c)
+        if (scores[c] > thr) return c + 1;
+    return 0;
+}
+
 // ---- the MCMC learner's draws -------------------------------------------------------------------------------------------
 
 double mcmc_uniform(uint64_t seed, uint32_t index, uint32_t group, uint32_t t, uint32_t stream) { return rng::uniform(seed, index, group, t, stream); }

@@ -225,6 +225,13 @@ int32_t bpr_negative(uint64_t seed, uint32_t p, uint32_t t, int32_t M, const int
 int32_t bpr_candidate(uint64_t seed, uint32_t p, uint32_t c, uint32_t t, int32_t M, const int32_t *list, int32_t len, int *attempts,
                       int *forced = nullptr);
 
+// WARP (include/fmhip_warp.h).  The weight table: out[0] = 0 and, for n = 1 .. C, out[n] = (float)H(max(1, (M - 1) / n)) with
+// H(r) = sum_{j = 1 .. r} 1 / j in fp64, j ascending — one pass over j = 1 .. M - 1 for all n.  out: C + 1 floats; M >= 2, C >= 1.
+void warp_weight_table(int64_t M, int C, float *out);
+// N of a pair: 1 + the lowest c in [0, C) with scores[c] > s_pos - margin (one fp32 subtraction; a strict test, so a tie and a NaN
+// on either side are no violation), 0 when there is none — the host twin of k_bpr_sample_warp's choice.
+int warp_first_violator(const float *scores, int C, float s_pos, float margin);
+
 // ---- the MCMC learner's draws (fmhip_mcmc_epoch, include/fmhip_mcmc.h; the generator: mcmc_rng.h) ------------------------------
 // Counters are (index, group, t, stream); t = the epochs the handle has completed.
 double mcmc_uniform(uint64_t seed, uint32_t index, uint32_t group, uint32_t t, uint32_t stream);

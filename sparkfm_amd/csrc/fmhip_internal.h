@@ -371,6 +371,16 @@ struct fmhip_bpr {
     DevBuf<int32_t> rec_rows;
     DevBuf<float> rec_scores;
     hipEvent_t fwd_done = nullptr;
+    // WARP (include/fmhip_warp.h): the switch and the margin, whether a WARP draw stands since the switch was last set, the pairs'
+    // weights (a PairArgs::c over all 2 n_pairs rows) and trial counts, the weight table W[0 .. wtab_cand] on both sides, the
+    // sampler's {violated, trials} partials and sums, the debug call's s+ record
+    bool warp = false, warp_drawn = false;
+    double warp_margin = 1.0;
+    DevBuf<float> wc, wtab, rec_pos;
+    DevBuf<int32_t> wtrials;
+    std::vector<float> h_wtab;
+    int32_t wtab_cand = 0;
+    DevBuf<unsigned long long> wpart, wtotal;
     ~fmhip_bpr() {
         if (fwd_done) (void)hipEventDestroy(fwd_done);
         if (R) (void)fmhip_relational_destroy(R);
@@ -540,7 +550,13 @@ void part_features(fmhip_dataset_t d, std::vector<int32_t> &out);     // a part'
 int check_rel_model(fmhip_model_t m, fmhip_relational_t R);           // device and dimension; sets the device
 // one relational step of batch b, asynchronous on the model's stream; acc (nullable): the epoch's fp64 accumulators.  pairs (the
 // BPR trainer): rows 2p / 2p+1 are one example — the finish leaves Q_r and yhat_r, launch_pair_finish forms the residuals
-int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs = false);
+// hinge (pairs only; the WARP step, include/fmhip_warp.h): the pairs' finish takes the weights' slice c + the batch's first row and
+// the hinge residual at this margin in place of the model's loss; nullptr: the model's loss, unweighted
+struct PairHinge {
+    const float *c;      // [2 * n_pairs] over the whole dataset
+    float margin;
+};
+int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs = false, const PairHinge *hinge = nullptr);
 // the beginning of a step alone (the BPR trainer's adaptive sampler reads what it leaves): scales folded, workspace sized, every
 // block's kFwdQ forward into its relation's Q / yq, asynchronous on the model's stream
 int rel_block_forwards(fmhip_model_t m, fmhip_relational_t R);

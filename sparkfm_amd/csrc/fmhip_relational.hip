@@ -137,7 +137,7 @@ int rel_block_forwards(fmhip_model_t m, fmhip_relational_t R) {
 }
 
 // one relational step of batch b, asynchronous on the model's stream; acc (nullable): the epoch's fp64 accumulators
-int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs) {
+int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs, const PairHinge *hinge) {
     const fmhip_relational::Batch &B = R->batches[(size_t)b];
     TRY(rel_block_forwards(m, R));           // every block's q-mode pass, over the whole block
     TRY(begin_forward(m));                   // (the forwards do not touch the gradient)
@@ -155,7 +155,13 @@ int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, d
     if (pairs) {
         // the BPR trainer: the finish left Q_r in P and yhat_r beside it, as the flat paired step's kFwdQ forward does; the pairs'
         // finish (fm_pairing.hip) turns them into P_r = Q_r e_r, e and the statistics partials (its own block count)
-        HIP_TRY(launch_pair_finish(m->Kp, pair_args(m, R->y.p + B.row0, nullptr, B.rows), m->stream, &m->step.fwd_parts));
+        PairArgs pa = pair_args(m, R->y.p + B.row0, nullptr, B.rows);
+        if (hinge) {                         // the WARP step: the sampler's weights, the hinge in the model's loss's place
+            pa.c = hinge->c + B.row0;
+            pa.loss = kPairLossHinge;
+            pa.margin = hinge->margin;
+        }
+        HIP_TRY(launch_pair_finish(m->Kp, pa, m->stream, &m->step.fwd_parts));
     }
     m->step.written(nnz, B.rows);            // (no backward window: the parts' whole-batch backwards below are the step's own)
     for (auto &relp : R->rels) {
