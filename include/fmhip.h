@@ -207,7 +207,10 @@ int fmhip_term_q(fmhip_model_t m, fmhip_dataset_t d, double *q /* n_rows*k */);
  * e_r = yhat_r - y_r, or sigma(yhat_r) - [y_r > 0] for a model set to FMHIP_LOSS_LOGISTIC (fmhip_model_set_loss); a model set to
  * FMHIP_PAIRING_ADJACENT (fmhip_pairing.h) trains on pairs of rows: e_2j = -e_2j+1 = the loss's residual of the pair's difference.
  * A model set to FMHIP_OPT_ADAGRAD (fmhip_model_set_optimizer) takes per-coordinate steps instead, each theta with its accumulator n:
- *   g_hat  = g_theta / |batch| + reg_theta * theta,   n <- n + g_hat^2,   theta <- theta - eta * g_hat / (sqrt(n) + eps)      */
+ *   g_hat  = g_theta / |batch| + reg_theta * theta,   n <- n + g_hat^2,   theta <- theta - eta * g_hat / (sqrt(n) + eps)
+ * A model put under FTRL-Proximal (fmhip_model_set_ftrl, fmhip_ftrl.h) takes the third rule: per-coordinate steps with L1 and L2 in a
+ * closed form, eta its alpha and reg_theta its L2 — a parameter whose gradient is zero does not move, most of a wide model ends
+ * exactly zero (the rule is written out in that header).                                                                         */
 int fmhip_sgd_step(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, double eta, double reg0, double regw,
                    double regv, fmhip_stats *stats /* nullable: skips the host sync */);
 /* one pass over all batches; order[n_batches] = batch visiting order (NULL = ascending) */

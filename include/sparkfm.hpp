@@ -45,6 +45,7 @@
 #include "fmhip_bpr.h"
 #include "fmhip_bpr_adaptive.h"
 #include "fmhip_warp.h"
+#include "fmhip_ftrl.h"
 
 namespace sparkfm {
 
@@ -284,6 +285,16 @@ class FMModel {
         check(fmhip_weighted_scores(upload(), dataset.handle(), &r));
         return r;
     }
+    // Exact sparsity counts of the model as uploaded (fmhip_model_nonzeros, include/fmhip_ftrl.h): nonzero w, nonzero v, and the
+    // features whose w and whole v row are zero — what FTRL-Proximal's L1 (HipFTRL) leaves behind
+    struct Nonzeros {
+        int64_t w_nonzero = 0, v_nonzero = 0, features_all_zero = 0;
+    };
+    Nonzeros nonzeros() {
+        Nonzeros z;
+        check(fmhip_model_nonzeros(upload(), &z.w_nonzero, &z.v_nonzero, &z.features_all_zero));
+        return z;
+    }
     // Pairwise ranking score of the pairs (rows 2j, 2j+1) of `dataset` (fmhip_pair_logloss): the mean of -log sigmoid(+-d) over the
     // pairs' margins d = predict(row 2j) - predict(row 2j+1), the sign by which row carries the larger label ...
     double computePairLogLoss(DataSet &dataset) {
@@ -456,6 +467,46 @@ class HipSGD : public FMLearn {
         check(fmhip_relational_sgd_epoch(fm.upload(), dataset.handle(), eta, reg0, regw, regv, nullptr, &last_stats));
         fm.download();
         return fm;
+    }
+};
+
+// HipSGD under FTRL-Proximal with L1 (include/fmhip_ftrl.h): per-coordinate rates like AdaGrad's plus an L1 term that leaves most of a
+// wide model exactly zero (FMModel::nonzeros).  alpha: the step size; beta: added to sqrt(n) in every rate; l1w, l1v: the L1 of the
+// linear weights and of the factors (w0 has none); l2_0, l2w, l2v: the L2 of the rule's closed form — no decay: a parameter whose
+// gradient is zero keeps every bit; ftrl_init: what the accumulators start at.  The rule is put on the model before every epoch (the
+// same settings keep its state; the model's upload before each call writes its own values back, which keeps it too).
+class HipFTRL : public FMLearn {
+  public:
+    double alpha, beta, l1w, l1v, l2_0, l2w, l2v, ftrl_init;
+    int loss;
+    bool pairs;
+    fmhip_stats last_stats{};
+    explicit HipFTRL(double alpha_ = 0.1, double beta_ = 1.0, double l1w_ = 0.0, double l1v_ = 0.0, double l2_0_ = 0.0, double l2w_ = 0.0,
+                     double l2v_ = 0.0, double ftrl_init_ = 0.0, int loss_ = FMHIP_LOSS_SQUARED, bool pairs_ = false)
+        : alpha(alpha_), beta(beta_), l1w(l1w_), l1v(l1v_), l2_0(l2_0_), l2w(l2w_), l2v(l2v_), ftrl_init(ftrl_init_), loss(loss_),
+          pairs(pairs_) {}
+    static HipFTRL run(double alpha = 0.1, double beta = 1.0, double l1w = 0.0, double l1v = 0.0, double l2_0 = 0.0, double l2w = 0.0,
+                       double l2v = 0.0, double ftrl_init = 0.0, int loss = FMHIP_LOSS_SQUARED, bool pairs = false) {
+        return HipFTRL(alpha, beta, l1w, l1v, l2_0, l2w, l2v, ftrl_init, loss, pairs);
+    }
+    FMModel &learn(FMModel &fm, DataSet &dataset) override {
+        check(fmhip_sgd_epoch(set_rule(fm), dataset.handle(), alpha, l2_0, l2w, l2v, nullptr, &last_stats));
+        fm.download();
+        return fm;
+    }
+    FMModel &learn(FMModel &fm, RelationalData &dataset) override {
+        check(fmhip_relational_sgd_epoch(set_rule(fm), dataset.handle(), alpha, l2_0, l2w, l2v, nullptr, &last_stats));
+        fm.download();
+        return fm;
+    }
+
+  private:
+    fmhip_model_t set_rule(FMModel &fm) {
+        fmhip_model_t m = fm.upload();
+        check(fmhip_model_set_loss(m, loss));
+        check(fmhip_model_set_pairing(m, pairs ? FMHIP_PAIRING_ADJACENT : FMHIP_PAIRING_NONE));
+        check(fmhip_model_set_ftrl(m, beta, ftrl_init, l1w, l1v));
+        return m;
     }
 };
 

@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_mcmc_relational.h, include/fmhip_bpr.h, include/fmhip_bpr_adaptive.h, include/fmhip_warp.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_mcmc_relational.h, include/fmhip_bpr.h, include/fmhip_bpr_adaptive.h, include/fmhip_warp.h, include/fmhip_ftrl.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -78,6 +78,9 @@ SYMBOLS_BPR_ADAPTIVE = ("fmhip_bpr_set_candidates", "fmhip_bpr_get_candidates", 
 BPR_MAX_CANDIDATES = 64    # FMHIP_BPR_MAX_CANDIDATES
 # ... and include/fmhip_warp.h — WARP: the first candidate that violates the margin, a hinge weighted by the estimated rank
 SYMBOLS_WARP = ("fmhip_warp_set", "fmhip_warp_get", "fmhip_warp_resample", "fmhip_warp_weights", "fmhip_warp_trials")
+# ... and include/fmhip_ftrl.h — FTRL-Proximal with L1: the third update rule, its state, the model's exact sparsity counts
+SYMBOLS_FTRL = ("fmhip_model_set_ftrl", "fmhip_model_get_ftrl_state", "fmhip_model_set_ftrl_state", "fmhip_model_nonzeros")
+OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
  TUNE_ROW_ORDER, TUNE_FLAT_ADDRESS, TUNE_LAZY_DECAY, TUNE_FUSED_UPDATE, TUNE_MERGED_FINISH, TUNE_HOT_PAGES) = range(13)
@@ -162,6 +165,47 @@ class TrainRule:
             raise ValueError("this engine trains on single rows only")
         if self.opt_code != OPT_SGD:
             raise ValueError("this engine trains with plain SGD only")
+
+
+def ftrl_settings(beta, init, l1w, l1v):
+    """(beta, initial accumulator, l1w, l1v) as floats; ValueError unless all are finite and >= 0 and beta + sqrt(init) > 0 (as the
+    C ABI, which checks the sum in fp32)."""
+    import math
+    import struct
+    out = []
+    for name, x in (("beta", beta), ("ftrl_init", init), ("l1w", l1w), ("l1v", l1v)):
+        x = float(x)
+        if not (math.isfinite(x) and x >= 0.0):
+            raise ValueError("%s must be finite and >= 0, not %r" % (name, x))
+        out.append(x)
+    f32 = lambda x: struct.unpack("f", struct.pack("f", x))[0]
+    if not f32(out[0]) + math.sqrt(f32(out[1])) > 0.0:
+        raise ValueError("beta + sqrt(ftrl_init) must be > 0 (the first step would divide by zero), not beta %r, ftrl_init %r" % (out[0], out[1]))
+    return tuple(out)
+
+
+class FtrlRule(TrainRule):
+    """A TrainRule whose update rule is FTRL-Proximal (include/fmhip_ftrl.h): loss and pairing as TrainRule's, the rule's four
+    settings validated here (ValueError); `set_on` puts it on a model through fmhip_model_set_ftrl (the same settings again keep
+    the model's zeta and n)."""
+
+    def __init__(self, loss="squared", pairs=False, beta=1.0, ftrl_init=0.0, l1w=0.0, l1v=0.0):
+        super().__init__(loss=loss, pairs=pairs)
+        self.optimizer, self.opt_code = "ftrl", OPT_FTRL
+        self.beta, self.ftrl_init, self.l1w, self.l1v = ftrl_settings(beta, ftrl_init, l1w, l1v)
+
+    def publish(self, learner):
+        """The keywords as the learner's public attributes (.loss, .pairs, .beta, .ftrl_init, .l1w, .l1v) -> self."""
+        for name in ("loss", "pairs", "beta", "ftrl_init", "l1w", "l1v"):
+            setattr(learner, name, getattr(self, name))
+        return self
+
+    def set_on(self, handle):
+        """fmhip_model_set_loss, _set_pairing, _set_ftrl."""
+        L = load()
+        check(L.fmhip_model_set_loss(handle, self.loss_code))
+        check(L.fmhip_model_set_pairing(handle, self.pairing_code))
+        check(L.fmhip_model_set_ftrl(handle, self.beta, self.ftrl_init, self.l1w, self.l1v))
 
 
 class Stats(C.Structure):
@@ -512,9 +556,13 @@ def load():
     L.fmhip_warp_weights.argtypes = [vp, vp]
     L.fmhip_warp_trials.argtypes = [vp, vp]
     L.fmhip_warp_debug.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
+    L.fmhip_model_set_ftrl.argtypes = [vp, dbl, dbl, dbl, dbl]
+    L.fmhip_model_get_ftrl_state.argtypes = [vp, P(dbl), vp, vp, P(dbl), vp, vp]
+    L.fmhip_model_set_ftrl_state.argtypes = [vp, dbl, vp, vp, dbl, vp, vp]
+    L.fmhip_model_nonzeros.argtypes = [vp, P(i64), P(i64), P(i64)]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

@@ -7,23 +7,24 @@ namespace {
 
 // (apply_piece / apply_w0 live in fm_device.h: k_fixup's merged finish uses them too)
 
-// ADA: the AdaGrad form (fm_device.h), its own instance — the SGD instances carry none of its registers
-template <int KP, bool ADA>
+// RULE: the update rule (enum ApplyRule; fm_device.h), each its own instance — the SGD instances carry none of the others' registers
+template <int KP, int RULE>
 __global__ __launch_bounds__(kBlock) void k_apply(ApplyArgs a) {
     constexpr int LPR = KP / 4;  // lanes per feature row (<= 64, divides the wave)
     const float invb = apply_invb(a);
     const int64_t total = (a.row_hi - a.row_lo) * LPR;
     for (int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * kBlock)
-        apply_piece<KP, false, ADA>(a, a.row_lo + idx / LPR, (int)(idx % LPR), invb);
-    if (a.do_w0) apply_w0<ADA>(a, invb);
+        apply_piece<KP, false, RULE>(a, a.row_lo + idx / LPR, (int)(idx % LPR), invb);
+    if (a.do_w0) apply_w0<RULE>(a, invb);
 }
 
 // The same update restricted to the rows a batch touched (its distinct features + the dense hot
 // block's); every other row has a zero gradient and its decay rides in the tables' scale (see above).
 // Matters when the model is far wider than a batch (Criteo-like widths: 2^25 rows of V, 8.6 GB,
 // against ~2 M touched).
-// (ADA: the accumulator rows are indexed by the feature id i, like the parameter rows; the gradient by gr)
-template <int KP, bool ADA>
+// (AdaGrad, FTRL: the state rows are indexed by the feature id i, like the parameter rows; the gradient by gr.  FTRL: a listed row
+// whose gradient is zero — a hot-block row the batch did not touch — keeps its bits, as every unlisted row does)
+template <int KP, int RULE>
 __global__ __launch_bounds__(kBlock) void k_apply_rows(ApplyArgs a) {
     constexpr int LPR = KP / 4;
     const float invb = apply_invb(a);
@@ -31,9 +32,9 @@ __global__ __launch_bounds__(kBlock) void k_apply_rows(ApplyArgs a) {
     for (int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * kBlock) {
         const int64_t j = idx / LPR;
         const int32_t i = j < a.n_feat ? a.feat[j] : a.hot_ids[j - a.n_feat];
-        if (i >= 0) apply_piece<KP, true, ADA>(a, i, (int)(idx % LPR), invb, a.g_compact ? j : (int64_t)i);
+        if (i >= 0) apply_piece<KP, true, RULE>(a, i, (int)(idx % LPR), invb, a.g_compact ? j : (int64_t)i);
     }
-    if (a.do_w0) apply_w0<ADA>(a, invb);
+    if (a.do_w0) apply_w0<RULE>(a, invb);
 }
 
 // Sharded update (fmhip_comm.hip, FMHIP_EXCHANGE_SHARDED): one launch per feature interval [w_lo, z_hi), queued on the
@@ -107,7 +108,120 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(const float *V, const fl
     }
 }
 
+// ------------------------------------------------------------------ FTRL-Proximal: state derivation, exact sparsity counts
+// zeta = -theta * (beta + sqrt(n)): the proximal centre at the current parameters (with l1 = l2 = 0 the closed form of ftrl_step gives
+// theta back), over the whole padded tables — a padded slot holds theta = 0 and gets zeta = -0.
+// oV / ow / ow0 (all or none): the parameters BEFORE they were replaced — a parameter whose bits did not change keeps its zeta (it
+// still agrees with it: writing a model's own values back, or one of its three parts, costs the others no state)
+__device__ __forceinline__ float ftrl_centre(float theta, float n, float beta, float zeta, bool keep) {
+    return keep ? zeta : -theta * (beta + sqrtf(n));
+}
+__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+
+__global__ __launch_bounds__(kBlock) void k_ftrl_init(const float *V, const float *w, const float *w0, const float *NV, const float *Nw,
+                                                     const float *N0, float *ZV, float *Zw, float *Z0, const float *oV, const float *ow,
+                                                     const float *ow0, int64_t n1p, int32_t lpr, float beta) {
+    const int64_t total = n1p * lpr;
+    for (int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * kBlock) {
+        const float4 t = reinterpret_cast<const float4 *>(V)[idx], n = reinterpret_cast<const float4 *>(NV)[idx];
+        float4 z = f4zero(), o = t;
+        if (oV) {
+            z = reinterpret_cast<const float4 *>(ZV)[idx];
+            o = reinterpret_cast<const float4 *>(oV)[idx];
+        }
+        z.x = ftrl_centre(t.x, n.x, beta, z.x, oV && same_bits(t.x, o.x));
+        z.y = ftrl_centre(t.y, n.y, beta, z.y, oV && same_bits(t.y, o.y));
+        z.z = ftrl_centre(t.z, n.z, beta, z.z, oV && same_bits(t.z, o.z));
+        z.w = ftrl_centre(t.w, n.w, beta, z.w, oV && same_bits(t.w, o.w));
+        reinterpret_cast<float4 *>(ZV)[idx] = z;
+        // (total >= n1p: every entry of the vector is covered)
+        if (Zw && idx < n1p) Zw[idx] = ftrl_centre(w[idx], Nw[idx], beta, ow ? Zw[idx] : 0.f, ow && same_bits(w[idx], ow[idx]));
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *Z0 = ftrl_centre(*w0, *N0, beta, ow0 ? *Z0 : 0.f, ow0 && same_bits(*w0, *ow0));
+}
+
+// Exact integer counts over the real entries (i < n1, f < k; packed rows: slot pack_k is w_i, else the vector beside the table).
+// LPR lanes hold one row (they share a wave); the row's "anything alive" is summed over them by a butterfly.  Every thread keeps its
+// own counts, a block sums them in a fixed order and writes ONE partial triple; no atomics — the host adds the blocks in index order.
+template <int KP>
+__global__ __launch_bounds__(kBlock) void k_count_nonzeros(const float *V, const float *w, int64_t n1, int32_t k, int32_t pack_k,
+                                                          int64_t *part) {
+    constexpr int LPR = KP / 4;
+    static_assert(LPR <= 64 && 64 % LPR == 0 && kBlock % 64 == 0, "a row's lanes share a wave");
+    const int64_t total = n1 * LPR;      // a multiple of LPR, and so is the stride: a row's lanes take the same trips
+    int64_t cw = 0, cv = 0, cz = 0;
+    for (int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * kBlock) {
+        const int64_t i = idx / LPR;
+        const int c = (int)(idx % LPR);
+        const float4 t = reinterpret_cast<const float4 *>(V)[idx];
+        const float e[4] = {t.x, t.y, t.z, t.w};
+        int alive = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int f = 4 * c + j;
+            const int nz = e[j] != 0.f;
+            if (f < k) { cv += nz; alive += nz; }
+            else if (f == pack_k) { cw += nz; alive += nz; }
+        }
+        if (pack_k < 0 && c == 0) {
+            const int nz = w[i] != 0.f;
+            cw += nz;
+            alive += nz;
+        }
+#pragma unroll
+        for (int mask = LPR / 2; mask >= 1; mask >>= 1) alive += __shfl_xor(alive, mask, LPR);
+        if (c == 0) cz += alive == 0;
+    }
+#pragma unroll
+    for (int mask = 32; mask >= 1; mask >>= 1) {
+        cw += __shfl_xor(cw, mask, 64);
+        cv += __shfl_xor(cv, mask, 64);
+        cz += __shfl_xor(cz, mask, 64);
+    }
+    __shared__ int64_t sh[3][kBlock / 64];
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sh[0][wv] = cw; sh[1][wv] = cv; sh[2][wv] = cz; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t t0 = 0, t1 = 0, t2 = 0;
+        for (int j = 0; j < kBlock / 64; ++j) { t0 += sh[0][j]; t1 += sh[1][j]; t2 += sh[2][j]; }
+        part[3 * (int64_t)blockIdx.x + 0] = t0;
+        part[3 * (int64_t)blockIdx.x + 1] = t1;
+        part[3 * (int64_t)blockIdx.x + 2] = t2;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_ftrl_init(int Kp, const float *V, const float *w, const float *w0, const float *NV, const float *Nw, const float *N0,
+                            float *ZV, float *Zw, float *Z0, const float *oV, const float *ow, const float *ow0, int64_t n1p, float beta,
+                            hipStream_t s) {
+    if (Kp % 4 != 0 || (Zw && (!w || !Nw))) return hipErrorInvalidValue;
+    if ((oV != nullptr) != (ow0 != nullptr) || (oV && Zw && !ow)) return hipErrorInvalidValue;
+    int64_t blocks = (n1p * (Kp / 4) + kBlock - 1) / kBlock;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(k_ftrl_init, dim3((unsigned)blocks), dim3(kBlock), 0, s, V, w, w0, NV, Nw, N0, ZV, Zw, Z0, oV, Zw ? ow : nullptr, ow0,
+                       n1p, Kp / 4, beta);
+    return hipGetLastError();
+}
+
+hipError_t launch_count_nonzeros(int Kp, const float *V, const float *w, int64_t n1, int32_t k, int32_t pack_k, int64_t *part,
+                                 int *n_blocks, hipStream_t s) {
+    int64_t blocks = (n1 * (Kp / 4) + kBlock - 1) / kBlock;
+    if (blocks > kCountBlocks) blocks = kCountBlocks;
+    if (blocks < 1) blocks = 1;
+    *n_blocks = (int)blocks;
+    dim3 g((unsigned)blocks), b(kBlock);
+    switch (Kp) {
+        case 32: hipLaunchKernelGGL((k_count_nonzeros<32>), g, b, 0, s, V, w, n1, k, pack_k, part); break;
+        case 64: hipLaunchKernelGGL((k_count_nonzeros<64>), g, b, 0, s, V, w, n1, k, pack_k, part); break;
+        case 128: hipLaunchKernelGGL((k_count_nonzeros<128>), g, b, 0, s, V, w, n1, k, pack_k, part); break;
+        case 256: hipLaunchKernelGGL((k_count_nonzeros<256>), g, b, 0, s, V, w, n1, k, pack_k, part); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
 
 hipError_t launch_gather_rows(int Kp, const float *V, const float *w, const int32_t *ids, int64_t n, float *out_v, float *out_w,
                               hipStream_t s) {
@@ -149,13 +263,17 @@ hipError_t launch_apply(int Kp, const ApplyArgs &a, hipStream_t s) {
     if (blocks > 8192) blocks = 8192;
     if (blocks < 1) blocks = 1;
     dim3 g((unsigned)blocks), b(kBlock);
-    const bool ada = a.NV != nullptr;
+    // the rule is stated by the caller; its state must be there (a missing table is an error, never another rule's instance)
+    if (a.rule != kRuleSgd && a.rule != kRuleAdaGrad && a.rule != kRuleFtrl) return hipErrorInvalidValue;
+    if (a.rule != kRuleSgd && (!a.NV || !a.N0 || (a.pack_k < 0 && !a.Nw))) return hipErrorInvalidValue;
+    if (a.rule == kRuleFtrl && (!a.ZV || !a.Z0 || (a.pack_k < 0 && !a.Zw))) return hipErrorInvalidValue;
+#define FMHIP_AP_RULE(KP_, RULE_)                                                      \
+    if (rows_only) hipLaunchKernelGGL((k_apply_rows<KP_, RULE_>), g, b, 0, s, a);      \
+    else hipLaunchKernelGGL((k_apply<KP_, RULE_>), g, b, 0, s, a)
 #define FMHIP_AP(KP_)                                                                  \
-    if (ada) {                                                                         \
-        if (rows_only) hipLaunchKernelGGL((k_apply_rows<KP_, true>), g, b, 0, s, a);   \
-        else hipLaunchKernelGGL((k_apply<KP_, true>), g, b, 0, s, a);                  \
-    } else if (rows_only) hipLaunchKernelGGL((k_apply_rows<KP_, false>), g, b, 0, s, a); \
-    else hipLaunchKernelGGL((k_apply<KP_, false>), g, b, 0, s, a)
+    if (a.rule == kRuleFtrl) { FMHIP_AP_RULE(KP_, kRuleFtrl); }                        \
+    else if (a.rule == kRuleAdaGrad) { FMHIP_AP_RULE(KP_, kRuleAdaGrad); }             \
+    else { FMHIP_AP_RULE(KP_, kRuleSgd); }
     switch (Kp) {
         case 32: FMHIP_AP(32); break;
         case 64: FMHIP_AP(64); break;
@@ -164,6 +282,7 @@ hipError_t launch_apply(int Kp, const ApplyArgs &a, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
 #undef FMHIP_AP
+#undef FMHIP_AP_RULE
     return hipGetLastError();
 }
 

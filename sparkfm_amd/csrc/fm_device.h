@@ -216,7 +216,7 @@ __device__ __forceinline__ uint32_t slot_bcast(uint32_t v, int src) { return (ui
 // (row_finish) and the next dense pass (below) folds it back in.  With no decay and sv = 1 both passes
 // perform the same operations on the same values (bit-identical; tested).
 //
-// AdaGrad (ADA; torch.optim.Adagrad with lr = eta, weight_decay = reg): per scalar parameter theta with its accumulator n,
+// AdaGrad (RULE == kRuleAdaGrad; torch.optim.Adagrad with lr = eta, weight_decay = reg): per scalar parameter theta with its accumulator n,
 //     g_hat = g/|B| + reg*theta  (the SGD form's fmaf),   n <- n + g_hat^2,   theta <- theta - eta*g_hat / (sqrt(n) + eps)
 // correctly rounded sqrtf and IEEE division; one writer per element, fixed order.  The tables are at scale 1 (no lazy
 // decay under AdaGrad), so the rows-only form is the dense one restricted to the listed rows — exact when reg = 0, where an
@@ -226,17 +226,83 @@ __device__ __forceinline__ void adagrad_step(float &th, float &n, float gh, floa
     th = th - eta * gh / (sqrtf(n) + eps);
 }
 
-// one float4 of one feature row; ROWS = the rows-only (lazy) form; ADA = the AdaGrad form
+// FTRL-Proximal (RULE == kRuleFtrl; McMahan et al., "Ad click prediction: a view from the trenches") with L1 and L2 in its closed
+// form: per scalar parameter theta, zeta (the rule's z pre-multiplied by the step size, so that no state depends on eta) and n (the
+// sum of squared gradients); g is the plain mean gradient, nothing folded in:
+//     n' = n + g^2,  r = sqrt(n'),  r0 = sqrt(n),  s = g^2 / (r + r0)   (= r - r0 without the cancellation; 0 where g^2 underflows at n = 0)
+//     zeta' = zeta + eta*g - s*theta
+//     theta' = |zeta'| <= eta*l1 ? +0 : -(zeta' - sign(zeta')*eta*l1) / (beta + r + eta*l2)
+// A coordinate with g == 0 keeps theta, zeta and n EXACTLY (a select, no branch), whatever l1 and l2 are: the rows-only form is the
+// dense one restricted to the listed rows under any regularisation — what AdaGrad with decay cannot offer.  Correctly rounded sqrtf
+// and IEEE division, no contraction beyond the fmaf written out; every instance shares this one instruction sequence.
+// tau = eta*l1, el2 = eta*l2 (formed once per launch, the same products everywhere)
+__device__ __forceinline__ void ftrl_step(float &th, float &z, float &n, float g, float eta, float tau, float beta, float el2) {
+#pragma clang fp contract(off)
+    const float n1 = fmaf(g, g, n);
+    const float r = sqrtf(n1), r0 = sqrtf(n);
+    const float rs = r + r0;
+    const float s = rs > 0.f ? g * g / rs : 0.f;
+    const float z1 = fmaf(eta, g, z) - s * th;
+    const float t1 = fabsf(z1) <= tau ? 0.f : -(z1 - copysignf(tau, z1)) / ((beta + r) + el2);
+    const bool moves = g != 0.f;
+    th = moves ? t1 : th;
+    z = moves ? z1 : z;
+    n = moves ? n1 : n;
+}
+
+// one float4 of one feature row; ROWS = the rows-only (lazy) form; RULE = the update rule (enum ApplyRule): each rule is an
+// instance of its own — the SGD instances carry none of the others' registers
 // gr: the row of the gradient arrays that belongs to parameter row i (the packed gradient: gr == i; the compact
 // gradient of the touched-rows exchange: the position of feature i in the step's union)
-template <int KP, bool ROWS, bool ADA = false>
+template <int KP, bool ROWS, int RULE = kRuleSgd>
 __device__ __forceinline__ void apply_piece(const ApplyArgs &a, int64_t i, int c, float invb, int64_t gr) {
     constexpr int LPR = KP / 4;
     float4 *V4 = reinterpret_cast<float4 *>(a.V) + i * LPR + c;
     float4 *G4 = reinterpret_cast<float4 *>(a.GV) + gr * LPR + c;
     const float b = a.Gb[gr];
     float4 g = *G4, u = *V4;
-    if constexpr (ADA) {
+    if constexpr (RULE == kRuleFtrl) {
+        float4 *N4 = reinterpret_cast<float4 *>(a.NV) + i * LPR + c;   // same lanes, same float4 as the V row
+        float4 *Z4 = reinterpret_cast<float4 *>(a.ZV) + i * LPR + c;
+        float4 n = *N4, z = *Z4;
+        const float tau_v = a.eta * a.l1v, el2_v = a.eta * a.regv, tau_w = a.eta * a.l1w, el2_w = a.eta * a.regw;
+        const bool has_w = a.pack_k >= 0 && c == (a.pack_k >> 2);
+        float wt = 0.f, wz = 0.f, wn = 0.f, wg = 0.f;
+        if (has_w) {   // packed rows: component pack_k & 3 is the linear weight with its zeta and its accumulator
+            wt = f4pick(u, a.pack_k & 3);
+            wz = f4pick(z, a.pack_k & 3);
+            wn = f4pick(n, a.pack_k & 3);
+            wg = f4pick(g, a.pack_k & 3) * invb;
+        }
+        // (padded factor slots: g == 0, they never move)
+        ftrl_step(u.x, z.x, n.x, (g.x - u.x * b) * invb, a.eta, tau_v, a.beta, el2_v);
+        ftrl_step(u.y, z.y, n.y, (g.y - u.y * b) * invb, a.eta, tau_v, a.beta, el2_v);
+        ftrl_step(u.z, z.z, n.z, (g.z - u.z * b) * invb, a.eta, tau_v, a.beta, el2_v);
+        ftrl_step(u.w, z.w, n.w, (g.w - u.w * b) * invb, a.eta, tau_v, a.beta, el2_v);
+        if (has_w) {
+            ftrl_step(wt, wz, wn, wg, a.eta, tau_w, a.beta, el2_w);
+            f4set(u, a.pack_k & 3, wt);
+            f4set(z, a.pack_k & 3, wz);
+            f4set(n, a.pack_k & 3, wn);
+        }
+        *V4 = u;
+        *Z4 = z;
+        *N4 = n;
+        *G4 = f4zero();
+        if (c == 0) {
+            if (a.pack_k < 0) {   // (packed rows: the w table is not read)
+                float wi = a.w[i], zi = a.Zw[i], ni = a.Nw[i];
+                ftrl_step(wi, zi, ni, a.Gw[gr] * invb, a.eta, tau_w, a.beta, el2_w);
+                a.w[i] = wi;
+                a.Zw[i] = zi;
+                a.Nw[i] = ni;
+            }
+            a.Gw[gr] = 0.f;
+            a.Gb[gr] = 0.f;
+        }
+        return;
+    }
+    if constexpr (RULE == kRuleAdaGrad) {
         float4 *N4 = reinterpret_cast<float4 *>(a.NV) + i * LPR + c;   // same lanes, same float4 as the V row
         float4 n = *N4;
         const bool has_w = a.pack_k >= 0 && c == (a.pack_k >> 2);
@@ -300,9 +366,9 @@ __device__ __forceinline__ void apply_piece(const ApplyArgs &a, int64_t i, int c
         a.Gb[gr] = 0.f;  // same wave already holds its copy of b (all lanes of a row share a wave)
     }
 }
-template <int KP, bool ROWS, bool ADA = false>
+template <int KP, bool ROWS, int RULE = kRuleSgd>
 __device__ __forceinline__ void apply_piece(const ApplyArgs &a, int64_t i, int c, float invb) {
-    apply_piece<KP, ROWS, ADA>(a, i, c, invb, i);
+    apply_piece<KP, ROWS, RULE>(a, i, c, invb, i);
 }
 
 // 1/|B|: from the step's row count on the device, or given by the host
@@ -312,11 +378,17 @@ __device__ __forceinline__ float apply_invb(const ApplyArgs &a) {
     return rows > 0.f ? 1.0f / rows : 0.f;
 }
 
-template <bool ADA = false>
+template <int RULE = kRuleSgd>
 __device__ __forceinline__ void apply_w0(const ApplyArgs &a, float invb) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const float w0 = *a.w0;
-        if constexpr (ADA) {
+        if constexpr (RULE == kRuleFtrl) {   // (no L1 on the bias)
+            float t = w0, z = *a.Z0, n = *a.N0;
+            ftrl_step(t, z, n, a.scal[0] * invb, a.eta, 0.f, a.beta, a.eta * a.reg0);
+            *a.w0 = t;
+            *a.Z0 = z;
+            *a.N0 = n;
+        } else if constexpr (RULE == kRuleAdaGrad) {
             float t = w0, n = *a.N0;
             adagrad_step(t, n, fmaf(a.reg0, w0, a.scal[0] * invb), a.eta, a.eps);
             *a.w0 = t;

@@ -136,12 +136,21 @@ struct ApplyArgs {
     // k_apply_shard (sharded update of one feature interval): V rows [row_lo, row_hi) = this rank's share are updated,
     // the linear weights of [w_lo, w_hi) = the whole interval are stepped, the G_V rows of [w_lo, z_hi) outside the share zeroed
     int64_t w_lo, w_hi, z_hi;
-    // AdaGrad (NV != NULL: launch_apply picks the AdaGrad instances): the per-coordinate accumulators, shaped like the
+    // the update rule (enum ApplyRule): launch_apply picks the rule's instances by this field alone
+    int32_t rule;
+    // AdaGrad and FTRL-Proximal: the per-coordinate accumulators, shaped like the
     // parameters — NV like V (packed rows: slot pack_k holds w_i's), Nw like w (unpacked rows only), N0 like w0.  The tables
-    // are at scale 1 under AdaGrad (sv_in = sw_in = 1; the host asserts it)
+    // are at scale 1 under both (sv_in = sw_in = 1; the host asserts it)
     float *NV, *Nw, *N0;
     float eps;
+    // FTRL-Proximal (fm_device.h: ftrl_step): zeta = eta*z per parameter, shaped like the accumulators; eta is the rule's alpha, reg*
+    // the L2 of its closed form, l1w / l1v the L1 of the linear weights / the factors (w0 has none)
+    float *ZV, *Zw, *Z0;
+    float beta, l1w, l1v;
 };
+
+// the rules of the parameter update: the values of enum fmhip_optimizer (fmhip.h) and FMHIP_OPT_FTRL (fmhip_ftrl.h)
+enum ApplyRule { kRuleSgd = 0, kRuleAdaGrad = 1, kRuleFtrl = 2 };
 
 struct BwdArgs {
     const uint32_t *crow;      // batch CSC: bit31 = first entry of its column, low bits = batch-local row
@@ -225,6 +234,17 @@ hipError_t launch_fixup(int Kp, const BwdArgs &a, hipStream_t s);
 hipError_t launch_fixup2(int Kp, const BwdArgs &a, hipStream_t s);   // sums the pieces of multi-piece features
 hipError_t launch_apply(int Kp, const ApplyArgs &a, hipStream_t s);
 hipError_t launch_apply_shard(int Kp, const ApplyArgs &a, hipStream_t s);        // see ApplyArgs::w_lo
+// FTRL-Proximal: zeta = -theta * (beta + sqrt(n)) over whole tables (ZV / NV like V [n1p][Kp]; Zw / Nw like w [n1p], NULL with packed
+// rows; Z0 / N0 like w0) — the proximal centre at the current parameters.  oV, ow, ow0 (all NULL, or the tables' contents before
+// the parameters were replaced): a parameter whose bits did not change keeps its zeta
+hipError_t launch_ftrl_init(int Kp, const float *V, const float *w, const float *w0, const float *NV, const float *Nw, const float *N0,
+                            float *ZV, float *Zw, float *Z0, const float *oV, const float *ow, const float *ow0, int64_t n1p, float beta,
+                            hipStream_t s);
+constexpr int kCountBlocks = 1024;      // most blocks of launch_count_nonzeros
+// exact counts over the real entries (i < n1, f < k; packed rows: slot pack_k counted as w_i): part[3*b + {0, 1, 2}] = block b's
+// nonzero w, nonzero v, features whose w and whole V row are zero; *n_blocks blocks wrote (<= kCountBlocks); the caller sums in order
+hipError_t launch_count_nonzeros(int Kp, const float *V, const float *w, int64_t n1, int32_t k, int32_t pack_k, int64_t *part,
+                                 int *n_blocks, hipStream_t s);
 // scal[0..3] = {sum e, sum e^2, n_rows, nonfinite} (optional); acc (optional, 4 doubles) += the same;
 // with_logloss: acc holds 5 doubles and acc[4] += the sum of the partials' fourth slot (the log-loss)
 hipError_t launch_reduce_blocks(const double *bsum, int32_t nblocks, int32_t n_rows, float *scal, double *acc,

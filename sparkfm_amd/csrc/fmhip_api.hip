@@ -80,6 +80,33 @@ void table_pack(const fmhip_model *m, const FT *w, const FT *v, float fill, std:
     }
 }
 
+// An FTRL model's parameters were replaced (set_params, init_normal, ALS through set_params_impl): zeta = -theta (beta + sqrt(n)) from
+// the new theta and the current n, on the model's stream — theta and zeta never disagree.  `old` (set_params): the tables before the
+// call — a parameter whose fp32 bits did not change keeps its zeta (a model's own values written back, as a host mirror that uploads
+// before every call does, lose no state).  Any other model: nothing
+struct FtrlBefore {
+    DevBuf<float> V, w, w0;
+    int take(fmhip_model_t m) {      // the tables as they are, queued on the model's stream
+        if (!m->rule.ftrl()) return FMHIP_OK;
+        TRY(fold_scales(m));         // (FTRL tables are at scale 1 already; a no-op that states it)
+        TRY(V.alloc((size_t)m->n1p * m->Kp));
+        TRY(w.alloc((size_t)m->n1p));
+        TRY(w0.alloc(1));
+        HIP_TRY(hipMemcpyAsync(V.p, m->V.p, V.n * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+        HIP_TRY(hipMemcpyAsync(w.p, m->w.p, w.n * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+        HIP_TRY(hipMemcpyAsync(w0.p, m->w0.p, sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+        return FMHIP_OK;
+    }
+};
+
+int ftrl_rederive(fmhip_model_t m, const FtrlBefore *old = nullptr) {
+    if (!m->rule.ftrl()) return FMHIP_OK;
+    HIP_TRY(launch_ftrl_init(m->Kp, m->V.p, m->w.p, m->w0.p, m->NV.p, m->Nw.p, m->N0.p, m->ZV.p, m->Zw.p, m->Z0.p, old ? old->V.p : nullptr,
+                             old ? old->w.p : nullptr, old ? old->w0.p : nullptr, m->n1p, (float)m->rule.ftrl_beta, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));      // (`old` is freed by the caller)
+    return FMHIP_OK;
+}
+
 template <typename FT>
 int set_params_impl(fmhip_model_t m, FT w0, const FT *w, const FT *v) {
     if (!m || !w || !v) return fail(FMHIP_ERR_INVALID, "NULL argument");
@@ -91,10 +118,13 @@ int set_params_impl(fmhip_model_t m, FT w0, const FT *w, const FT *v) {
     m->h_w.assign(w, w + m->n1);
     m->h_v.assign(v, v + m->n1 * m->k);
     m->host64_fresh = true;
+    FtrlBefore before;
+    TRY(before.take(m));
     m->sv = m->sw = 1.0;
     HIP_TRY(hipMemcpyAsync(m->V.p, hV.data(), hV.size() * sizeof(float), hipMemcpyHostToDevice, m->stream));
     HIP_TRY(hipMemcpyAsync(m->w.p, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice, m->stream));
     HIP_TRY(hipMemcpyAsync(m->w0.p, &hw0, sizeof(float), hipMemcpyHostToDevice, m->stream));
+    TRY(ftrl_rederive(m, &before));
     HIP_TRY(hipStreamSynchronize(m->stream));
     return FMHIP_OK;
 }
@@ -354,9 +384,25 @@ int fmhip_model_set_pairing(fmhip_model_t m, int pairing) {
     return FMHIP_OK;
 }
 
+// back to plain SGD: the accumulators (AdaGrad's or FTRL's) and FTRL's zeta are freed, the rule's settings cleared
+static int drop_optimizer_state(fmhip_model_t m) {
+    if (m->rule.adagrad() || m->rule.ftrl()) HIP_TRY(hipStreamSynchronize(m->stream));    // no queued update may still use them
+    m->NV.release();
+    m->Nw.release();
+    m->N0.release();
+    m->ZV.release();
+    m->Zw.release();
+    m->Z0.release();
+    m->rule.opt = FMHIP_OPT_SGD;
+    m->rule.ada_eps = m->rule.ada_init = 0.0;
+    m->rule.ftrl_beta = m->rule.ftrl_init = m->rule.ftrl_l1w = m->rule.ftrl_l1v = 0.0;
+    return FMHIP_OK;
+}
+
 int fmhip_model_set_optimizer(fmhip_model_t m, int optimizer, double eps, double initial_accumulator) {
     if (optimizer != FMHIP_OPT_SGD && optimizer != FMHIP_OPT_ADAGRAD)
-        return fail(FMHIP_ERR_INVALID, "optimizer %d: FMHIP_OPT_SGD (0) or FMHIP_OPT_ADAGRAD (1)", optimizer);
+        return fail(FMHIP_ERR_INVALID, "optimizer %d: FMHIP_OPT_SGD (0) or FMHIP_OPT_ADAGRAD (1) (FTRL-Proximal has settings of its own: "
+                                       "fmhip_model_set_ftrl, fmhip_ftrl.h)", optimizer);
     if (optimizer == FMHIP_OPT_ADAGRAD && !(std::isfinite(eps) && eps > 0.0))
         return fail(FMHIP_ERR_INVALID, "AdaGrad eps must be finite and > 0 (got %g)", eps);
     if (optimizer == FMHIP_OPT_ADAGRAD && !(std::isfinite(initial_accumulator) && initial_accumulator >= 0.0))
@@ -364,15 +410,8 @@ int fmhip_model_set_optimizer(fmhip_model_t m, int optimizer, double eps, double
     WriteLock lock(m);
     if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
     TRY(set_device(m->device));
-    if (optimizer == FMHIP_OPT_SGD) {
-        if (m->rule.adagrad()) HIP_TRY(hipStreamSynchronize(m->stream));    // no queued update may still use them
-        m->NV.release();
-        m->Nw.release();
-        m->N0.release();
-        m->rule.opt = FMHIP_OPT_SGD;
-        m->rule.ada_eps = m->rule.ada_init = 0.0;
-        return FMHIP_OK;
-    }
+    if (m->rule.ftrl()) TRY(drop_optimizer_state(m));      // an FTRL model: its state goes first, whatever comes next
+    if (optimizer == FMHIP_OPT_SGD) return drop_optimizer_state(m);
     TrainRule want = m->rule;
     want.opt = FMHIP_OPT_ADAGRAD;
     want.ada_eps = eps;
@@ -431,11 +470,130 @@ int fmhip_model_set_optimizer_state(fmhip_model_t m, double n0, const double *nw
     return FMHIP_OK;
 }
 
+// ---- FTRL-Proximal (include/fmhip_ftrl.h)
+
+static_assert((int)FMHIP_OPT_SGD == (int)kRuleSgd && (int)FMHIP_OPT_ADAGRAD == (int)kRuleAdaGrad && (int)FMHIP_OPT_FTRL == (int)kRuleFtrl,
+              "fmhip.h / fmhip_ftrl.h and fm_kernels.h disagree on the update rules");
+
+int fmhip_model_set_ftrl(fmhip_model_t m, double beta, double initial_accumulator, double l1w, double l1v) {
+    auto ok = [](double x) { return std::isfinite(x) && x >= 0.0; };
+    if (!ok(beta)) return fail(FMHIP_ERR_INVALID, "FTRL beta must be finite and >= 0 (got %g)", beta);
+    if (!ok(initial_accumulator)) return fail(FMHIP_ERR_INVALID, "FTRL initial_accumulator must be finite and >= 0 (got %g)", initial_accumulator);
+    if (!ok(l1w)) return fail(FMHIP_ERR_INVALID, "FTRL l1w must be finite and >= 0 (got %g)", l1w);
+    if (!ok(l1v)) return fail(FMHIP_ERR_INVALID, "FTRL l1v must be finite and >= 0 (got %g)", l1v);
+    // (in the fp32 the kernels divide in)
+    if (!((float)beta + std::sqrt((float)initial_accumulator) > 0.f))
+        return fail(FMHIP_ERR_INVALID, "FTRL needs beta + sqrt(initial_accumulator) > 0 (got beta %g, initial_accumulator %g): the first "
+                                       "step would divide by zero", beta, initial_accumulator);
+    WriteLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    TRY(set_device(m->device));
+    TrainRule want = m->rule;
+    want.opt = FMHIP_OPT_FTRL;
+    want.ada_eps = want.ada_init = 0.0;
+    want.ftrl_beta = beta;
+    want.ftrl_init = initial_accumulator;
+    want.ftrl_l1w = l1w;
+    want.ftrl_l1v = l1v;
+    if (m->rule == want) return FMHIP_OK;
+    TRY(fold_scales(m));          // the FTRL kernels work on tables at scale 1
+    TRY(drop_optimizer_state(m));  // (SGD until the state is in place; AdaGrad's accumulators are not FTRL's)
+    TRY(m->NV.ensure((size_t)m->n1p * m->Kp));
+    TRY(m->ZV.ensure((size_t)m->n1p * m->Kp));
+    if (m->pack_k() < 0) {
+        TRY(m->Nw.ensure((size_t)m->n1p));
+        TRY(m->Zw.ensure((size_t)m->n1p));
+    }
+    TRY(m->N0.ensure(1));
+    TRY(m->Z0.ensure(1));
+    const float init = (float)initial_accumulator;
+    uint32_t bits;
+    memcpy(&bits, &init, sizeof bits);
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->NV.p), (int)bits, m->NV.n, m->stream));
+    if (m->Nw.p) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->Nw.p), (int)bits, m->Nw.n, m->stream));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->N0.p), (int)bits, 1, m->stream));
+    m->rule = want;
+    const int rc = ftrl_rederive(m);
+    if (rc != FMHIP_OK) {
+        (void)drop_optimizer_state(m);
+        return rc;
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_model_get_ftrl_state(fmhip_model_t m, double *z0, double *zw, double *zv, double *n0, double *nw, double *nv) {
+    ReadLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    if (!m->rule.ftrl()) return fail(FMHIP_ERR_INVALID, "the model has no FTRL state (fmhip_model_set_ftrl)");
+    TRY(set_device(m->device));
+    std::vector<float> hT((size_t)m->n1p * m->Kp), hw(m->Nw.p ? (size_t)m->n1p : 0);
+    float h0 = 0.f;
+    for (int pass = 0; pass < 2; ++pass) {      // zeta, then n
+        const float *T = pass ? m->NV.p : m->ZV.p, *wv = pass ? m->Nw.p : m->Zw.p, *s0 = pass ? m->N0.p : m->Z0.p;
+        HIP_TRY(hipMemcpyAsync(hT.data(), T, hT.size() * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+        if (wv) HIP_TRY(hipMemcpyAsync(hw.data(), wv, hw.size() * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipMemcpyAsync(&h0, s0, sizeof(float), hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));
+        if (double *o0 = pass ? n0 : z0) *o0 = h0;
+        table_unpack(m, hT.data(), hw.data(), m->n1, 1.0, 1.0, pass ? nw : zw, pass ? nv : zv);     // (the state carries no scale)
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_model_set_ftrl_state(fmhip_model_t m, double z0, const double *zw, const double *zv, double n0, const double *nw, const double *nv) {
+    if (!std::isfinite(z0)) return fail(FMHIP_ERR_INVALID, "z0 is not finite");
+    if (!(std::isfinite(n0) && n0 >= 0.0)) return fail(FMHIP_ERR_INVALID, "n0 is negative or not finite");
+    WriteLock lock(m);
+    if (!m || !zw || !zv || !nw || !nv) return fail(FMHIP_ERR_INVALID, "NULL argument");
+    if (!m->rule.ftrl()) return fail(FMHIP_ERR_INVALID, "the model has no FTRL state (fmhip_model_set_ftrl)");
+    for (int64_t i = 0; i < m->n1; ++i) {
+        if (!std::isfinite(zw[i])) return fail(FMHIP_ERR_INVALID, "zw[%lld] is not finite", (long long)i);
+        if (!(std::isfinite(nw[i]) && nw[i] >= 0.0)) return fail(FMHIP_ERR_INVALID, "nw[%lld] is negative or not finite", (long long)i);
+    }
+    for (int64_t j = 0; j < m->n1 * m->k; ++j) {
+        if (!std::isfinite(zv[j])) return fail(FMHIP_ERR_INVALID, "zv[%lld] is not finite", (long long)j);
+        if (!(std::isfinite(nv[j]) && nv[j] >= 0.0)) return fail(FMHIP_ERR_INVALID, "nv[%lld] is negative or not finite", (long long)j);
+    }
+    TRY(set_device(m->device));
+    std::vector<float> hT, hw;
+    for (int pass = 0; pass < 2; ++pass) {      // zeta, then n; padding: what fmhip_model_set_ftrl leaves there (theta = 0: zeta = -0)
+        float *T = pass ? m->NV.p : m->ZV.p, *wv = pass ? m->Nw.p : m->Zw.p, *s0 = pass ? m->N0.p : m->Z0.p;
+        table_pack(m, pass ? nw : zw, pass ? nv : zv, pass ? (float)m->rule.ftrl_init : -0.f, hT, wv ? &hw : nullptr);
+        const float h0 = (float)(pass ? n0 : z0);
+        HIP_TRY(hipMemcpyAsync(T, hT.data(), hT.size() * sizeof(float), hipMemcpyHostToDevice, m->stream));
+        if (wv) HIP_TRY(hipMemcpyAsync(wv, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice, m->stream));
+        HIP_TRY(hipMemcpyAsync(s0, &h0, sizeof(float), hipMemcpyHostToDevice, m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_model_nonzeros(fmhip_model_t m, int64_t *w_nonzero, int64_t *v_nonzero, int64_t *features_all_zero) {
+    ReadLock lock(m);
+    if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
+    TRY(set_device(m->device));
+    DevBuf<int64_t> part;       // (a workspace of this call: readers run side by side)
+    TRY(part.alloc(3 * (size_t)kCountBlocks));
+    int nb = 0;
+    HIP_TRY(launch_count_nonzeros(m->Kp, m->V.p, m->w.p, m->n1, m->k, m->pack_k(), part.p, &nb, m->stream));
+    std::vector<int64_t> h(3 * (size_t)nb);
+    HIP_TRY(hipMemcpyAsync(h.data(), part.p, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    int64_t t[3] = {0, 0, 0};
+    for (int b = 0; b < nb; ++b)
+        for (int j = 0; j < 3; ++j) t[j] += h[3 * (size_t)b + j];
+    if (w_nonzero) *w_nonzero = t[0];
+    if (v_nonzero) *v_nonzero = t[1];
+    if (features_all_zero) *features_all_zero = t[2];
+    return FMHIP_OK;
+}
+
 int fmhip_model_init_normal(fmhip_model_t m, uint64_t seed, double mean, double stdev) {
     WriteLock lock(m);
     if (!m) return fail(FMHIP_ERR_INVALID, "model is NULL");
     TRY(set_device(m->device));
     HIP_TRY(launch_init_normal(m->Kp, m->V.p, m->w.p, m->w0.p, m->n1, m->n1p, m->k, seed, (float)mean, (float)stdev, m->stream));
+    TRY(ftrl_rederive(m));
     HIP_TRY(hipStreamSynchronize(m->stream));
     m->sv = m->sw = 1.0;
     m->host64_fresh = false;     // the device holds the parameters; the fp64 masters are refreshed on demand

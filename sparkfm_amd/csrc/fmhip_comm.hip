@@ -115,7 +115,12 @@ int need_rccl() {
     } while (0)
 
 constexpr int kMaxCuts = 7;      // == FMHIP_DP_MAX_CUTS
-constexpr int kCtrlWords = kMaxCuts + 2;      // int64 words of the communicator's scratch: the cuts' broadcast, the plan's agreement vector
+// The plan's second agreement vector, by named slots: a value the ranks must hold alike takes two (put_agree), the sharded
+// exchange's refusal one.  AdaGrad fills opt, eps, init; FTRL-Proximal opt, beta, init, l1w, l1v
+enum OptSlot { kOptRule = 0, kOptEps = 2, kOptInit = 4, kOptBeta = 6, kOptL1w = 8, kOptL1v = 10, kOptShardRefused = 12, kOptSlots = 13 };
+// int64 words of the communicator's scratch: the cuts' broadcast, the plan's agreement vectors
+constexpr int kCtrlWords = kOptSlots > kMaxCuts + 2 ? kOptSlots : kMaxCuts + 2;
+static_assert(kCtrlWords >= kOptSlots && kCtrlWords >= kMaxCuts + 2, "the communicator's scratch holds every control vector");
 static_assert(kMaxCuts == FMHIP_DP_MAX_CUTS, "fmhip.h and fmhip_comm.hip disagree on the number of cuts");
 
 // Stand-in for a collective's duration on the comm stream (fmhip_comm_emulate): one wave spins on the
@@ -941,6 +946,11 @@ int local_checks(fmhip_model_t m, fmhip_dataset_t d, int64_t batch, fmhip_comm_t
         };
         if (r.loss != p.loss) return changed("loss", p.loss, r.loss);
         if (r.pairing != p.pairing) return changed("pairing", p.pairing, r.pairing);
+        if (p.ftrl() || r.ftrl())
+            return fail(FMHIP_ERR_INVALID, "the plan was agreed for optimizer %d (beta %g, initial accumulator %g, l1w %g, l1v %g), this model now "
+                                           "trains under optimizer %d (beta %g, initial accumulator %g, l1w %g, l1v %g) (fmhip_model_set_ftrl, "
+                                           "fmhip_model_set_optimizer): call fmhip_dp_plan again (every rank)", p.opt, p.ftrl_beta, p.ftrl_init,
+                        p.ftrl_l1w, p.ftrl_l1v, r.opt, r.ftrl_beta, r.ftrl_init, r.ftrl_l1w, r.ftrl_l1v);
         return fail(FMHIP_ERR_INVALID, "the plan was agreed for optimizer %d (eps %g, initial accumulator %g), this model now trains under "
                                        "optimizer %d (eps %g, initial accumulator %g) (fmhip_model_set_optimizer): call fmhip_dp_plan again "
                                        "(every rank)", p.opt, p.ada_eps, p.ada_init, r.opt, r.ada_eps, r.ada_init);
@@ -1301,7 +1311,7 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     constexpr int kAgree = 9;
     static_assert(kAgree <= kCtrlWords, "the plan's agreement vector travels in the communicator's scratch (kCtrlWords int64)");
     const TrainRule &rule = m->rule;
-    int64_t agree[kAgree] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size(), 0, 0, rule.adagrad(), d->weighted};
+    int64_t agree[kAgree] = {0, d->rb_rows != 0, 1, 0, (int64_t)d->batches.size(), 0, 0, rule.adagrad() || rule.ftrl(), d->weighted};
     put_agree(agree + 5, rule.loss + 2 * rule.pairing);
     for (const auto &bm : d->batches) {
         agree[0] = std::max<int64_t>(agree[0], bm.rows);
@@ -1313,21 +1323,29 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     TRY(control_i64(m, c, agree, kAgree, false));
     if (agree[7]) {
         // the optimizer and the bit patterns of its settings (>= 0, so non-negative int64 whose negation exists)
-        int64_t eb, ib;
-        memcpy(&eb, &rule.ada_eps, sizeof eb);
-        memcpy(&ib, &rule.ada_init, sizeof ib);
-        constexpr int kOpt = 7;
-        static_assert(kOpt <= kMaxCuts + 1, "the optimizer's agreement vector travels in the communicator's scratch (kMaxCuts + 1 int64)");
-        int64_t o[kOpt] = {0, 0, 0, 0, 0, 0, c->exchange == FMHIP_EXCHANGE_SHARDED && refusal(Path::kSharded, rule)};
-        put_agree(o, rule.opt);
-        put_agree(o + 2, eb);
-        put_agree(o + 4, ib);
-        TRY(control_i64(m, c, o, kOpt, false));
-        if (!agreed(o) || !agreed(o + 2) || !agreed(o + 4))
-            return fail(FMHIP_ERR_INVALID, "the ranks' models train under different optimizers or optimizer settings (fmhip_model_set_optimizer): "
-                                           "set the same optimizer, eps and initial accumulator on every rank");
+        auto bits = [](double x) {
+            int64_t b;
+            memcpy(&b, &x, sizeof b);
+            return b;
+        };
+        static_assert(kOptSlots <= kCtrlWords, "the optimizer's agreement vector travels in the communicator's scratch (kCtrlWords int64)");
+        int64_t o[kOptSlots] = {};
+        o[kOptShardRefused] = c->exchange == FMHIP_EXCHANGE_SHARDED && refusal(Path::kSharded, rule);
+        put_agree(o + kOptRule, rule.opt);
+        put_agree(o + kOptEps, bits(rule.ada_eps));
+        put_agree(o + kOptInit, bits(rule.ftrl() ? rule.ftrl_init : rule.ada_init));
+        put_agree(o + kOptBeta, bits(rule.ftrl_beta));
+        put_agree(o + kOptL1w, bits(rule.ftrl_l1w));
+        put_agree(o + kOptL1v, bits(rule.ftrl_l1v));
+        TRY(control_i64(m, c, o, kOptSlots, false));
+        if (!agreed(o + kOptRule) || !agreed(o + kOptEps) || !agreed(o + kOptInit))
+            return fail(FMHIP_ERR_INVALID, "the ranks' models train under different optimizers or optimizer settings (fmhip_model_set_optimizer, "
+                                           "fmhip_model_set_ftrl): set the same optimizer, eps and initial accumulator on every rank");
+        if (!agreed(o + kOptBeta) || !agreed(o + kOptL1w) || !agreed(o + kOptL1v))
+            return fail(FMHIP_ERR_INVALID, "the ranks' models train under different FTRL settings (fmhip_model_set_ftrl): set the same beta, "
+                                           "l1w and l1v on every rank");
         // (agreed above: every rank holds the optimizer of the rank that raised the slot, so every rank refuses here or none does)
-        if (o[6]) return fail(FMHIP_ERR_UNSUPPORTED, "%s", refusal(Path::kSharded, rule));
+        if (o[kOptShardRefused]) return fail(FMHIP_ERR_UNSUPPORTED, "%s", refusal(Path::kSharded, rule));
     }
     if (!agreed(agree + 5))
         return fail(FMHIP_ERR_INVALID, "the ranks' models train under different losses (fmhip_model_set_loss) or pairings (fmhip_model_set_pairing): "

@@ -7,6 +7,7 @@
 #include "../../include/fmhip_pairing.h"        // (enum fmhip_pairing: the model carries the switch)
 #include "../../include/fmhip_relational.h"     // (fmhip_relational_t: the handle's state is declared below)
 #include "../../include/fmhip_bpr.h"            // (fmhip_bpr_t: likewise)
+#include "../../include/fmhip_ftrl.h"           // (FMHIP_OPT_FTRL: the third value a model's rule reports)
 #include "fm_kernels.h"
 #include "fm_pairing.h"      // (PairArgs, RelFinishArgs: the builders the step and the scoring pass share are declared below)
 #include "fm_relational.h"
@@ -160,11 +161,16 @@ struct TrainRule {
     int pairing = FMHIP_PAIRING_NONE;
     int opt = FMHIP_OPT_SGD;
     double ada_eps = 0.0, ada_init = 0.0;
+    // FMHIP_OPT_FTRL (fmhip_ftrl.h; set by fmhip_model_set_ftrl only): beta, the accumulators' initial value, the L1 of w and of V
+    double ftrl_beta = 0.0, ftrl_init = 0.0, ftrl_l1w = 0.0, ftrl_l1v = 0.0;
     bool adagrad() const { return opt == FMHIP_OPT_ADAGRAD; }
+    bool ftrl() const { return opt == FMHIP_OPT_FTRL; }
     bool paired() const { return pairing != FMHIP_PAIRING_NONE; }
     // the settings by bit pattern (what the ranks agree on is their bits, and -0.0 or a NaN must not compare by value)
     bool same_optimizer(const TrainRule &o) const {
-        return opt == o.opt && memcmp(&ada_eps, &o.ada_eps, sizeof ada_eps) == 0 && memcmp(&ada_init, &o.ada_init, sizeof ada_init) == 0;
+        auto same = [](const double &a, const double &b) { return memcmp(&a, &b, sizeof a) == 0; };
+        return opt == o.opt && same(ada_eps, o.ada_eps) && same(ada_init, o.ada_init) && same(ftrl_beta, o.ftrl_beta) &&
+               same(ftrl_init, o.ftrl_init) && same(ftrl_l1w, o.ftrl_l1w) && same(ftrl_l1v, o.ftrl_l1v);
     }
     bool operator==(const TrainRule &o) const { return loss == o.loss && pairing == o.pairing && same_optimizer(o); }
 };
@@ -194,10 +200,13 @@ inline const char *refusal(Path p, const TrainRule &r, bool weighted = false) {
     }
     switch (p) {
         case Path::kSharded:
+            if (r.ftrl())
+                return "the sharded exchange does not support FTRL-Proximal (each rank's zeta and accumulators would hold its own "
+                       "share only): use the dense, pipelined or touched exchange";
             return !r.adagrad() ? nullptr
                                 : "the sharded exchange does not support AdaGrad (each rank's accumulators would hold its own share "
                                   "only): use the dense, pipelined or touched exchange";
-        case Path::kTouchedDecay:
+        case Path::kTouchedDecay:      // (FTRL: accepted — its L2 is no decay, a row without a gradient does not move)
             return !r.adagrad() ? nullptr
                                 : "the touched-rows exchange under AdaGrad needs regw = regv = 0 (with decay every row moves: use the "
                                   "dense or pipelined exchange)";
@@ -425,6 +434,8 @@ struct fmhip_model {
     // w_i's), Nw [n1p] (unpacked rows only), N0 [1] — one more copy of the model (8.6 GB at 2^25 x 64); the tables stay at
     // scale 1 (sv = sw = 1) while it is set
     DevBuf<float> NV, Nw, N0;
+    // FTRL-Proximal: zeta = eta*z per parameter, shaped like the accumulators (which it shares: NV, Nw, N0 hold its n)
+    DevBuf<float> ZV, Zw, Z0;
     // fp64 master copy of the parameters (reference layout): exact round trip of what the caller set,
     // and the state the fp64 ALS learner trains; stale once an fp32 SGD step has run
     std::vector<double> h_w, h_v;
@@ -542,7 +553,7 @@ int step_apply_shard(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, int6
 // feature interval as soon as its slice has arrived; the step's bookkeeping (w0, the tables' scale) moves with the LAST slice
 int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t n_feat, const float *rows, int64_t off = 0, bool last = true);
 // can the update of this step leave rows without a gradient alone (weight decay rides in the tables' scale, or there is
-// none)?  Under AdaGrad only without decay (`r`: the rule to judge by — the model's own, or the one a plan agreed)
+// none)?  Under AdaGrad only without decay; under FTRL always (its L2 is no decay: zero gradient, nothing moves) (`r`: the rule to judge by — the model's own, or the one a plan agreed)
 bool lazy_decay_ok(fmhip_model_t m, const Sgd &s, const TrainRule &r);
 int read_scal(fmhip_model_t m, fmhip_stats *st);
 // ---- fmhip_relational.hip

@@ -234,6 +234,7 @@ static ApplyArgs apply_args(fmhip_model_t m, const Sgd &s, const float *rows) {
     a.eta_v = a.eta_w = a.eta;
     a.sv_in = (float)m->sv;
     a.sw_in = (float)m->sw;
+    a.rule = m->rule.opt;
     if (m->rule.adagrad()) {
         // set_optimizer folded the scale and AdaGrad never takes the lazy-decay path: the AdaGrad kernels assume scale 1
         assert(m->sv == 1.0 && m->sw == 1.0);
@@ -241,6 +242,19 @@ static ApplyArgs apply_args(fmhip_model_t m, const Sgd &s, const float *rows) {
         a.Nw = m->Nw.p;
         a.N0 = m->N0.p;
         a.eps = (float)m->rule.ada_eps;
+    }
+    if (m->rule.ftrl()) {
+        // set_ftrl folded the scale and no FTRL step moves it (its L2 is no decay): the FTRL kernels assume scale 1
+        assert(m->sv == 1.0 && m->sw == 1.0);
+        a.NV = m->NV.p;
+        a.Nw = m->Nw.p;
+        a.N0 = m->N0.p;
+        a.ZV = m->ZV.p;
+        a.Zw = m->Zw.p;
+        a.Z0 = m->Z0.p;
+        a.beta = (float)m->rule.ftrl_beta;
+        a.l1w = (float)m->rule.ftrl_l1w;
+        a.l1v = (float)m->rule.ftrl_l1v;
     }
     return a;
 }
@@ -492,7 +506,9 @@ int step_compute(fmhip_model_t m, fmhip_dataset_t d, int64_t b, double *acc, con
 
 // can weight decay ride in the tables' scale for this step?  (no decay at all: trivially)
 // AdaGrad: only then — with decay every row moves (its accumulator too), which no scale can express: the dense pass
+// FTRL-Proximal: always — its L2 sits in the closed form, and a row whose gradient is zero keeps its value, zeta and n exactly
 bool lazy_decay_ok(fmhip_model_t m, const Sgd &s, const TrainRule &r) {
+    if (r.ftrl()) return true;
     if (s.regw == 0.0 && s.regv == 0.0) return true;
     if (r.adagrad()) return false;
     const double dv = s.dv(), dw = s.dw();
@@ -507,9 +523,9 @@ static bool few_rows(fmhip_model_t m, fmhip_dataset_t d, const BatchMeta &bm) {
 
 // Can this step apply its gradient rows inside the backward (no exchange, no separate update launch)?  It is the
 // rows-only update, so weight decay must be expressible through the tables' scale (lazy decay, fm_apply.hip).
-// Both forms are SGD's: under AdaGrad the update is a launch of its own (k_apply / k_apply_rows).
+// Both forms are SGD's: under AdaGrad and FTRL-Proximal the update is a launch of its own (k_apply / k_apply_rows).
 bool plan_fused(fmhip_model_t m, fmhip_dataset_t d, int64_t b, const Sgd &s, FusedPlan *p) {
-    if (m->rule.adagrad()) return false;
+    if (m->rule.adagrad() || m->rule.ftrl()) return false;
     const bool lazy_ok = lazy_decay_ok(m, s, m->rule);
     const BatchMeta &bm0 = d->batches[(size_t)b];
     p->sgd = s;
@@ -577,8 +593,10 @@ int step_apply(fmhip_model_t m, const Sgd &s, fmhip_dataset_t d, int64_t b) {
         a.n_feat = bm.n_cols;
         a.hot_ids = d->d_hot_ids.p;
         a.n_hot = d->hot_pages * kHotT;
-        sv_out = m->sv * s.dv();
-        sw_out = m->sw * s.dw();
+        if (!m->rule.ftrl()) {      // (FTRL: nothing decays, the tables stay at scale 1)
+            sv_out = m->sv * s.dv();
+            sw_out = m->sw * s.dw();
+        }
     }
     a.eta_v = (float)(s.eta / sv_out);
     a.eta_w = (float)(s.eta / sw_out);
@@ -624,10 +642,12 @@ int step_apply_shard(fmhip_model_t m, const Sgd &s, int64_t lo, int64_t hi, int6
 int step_apply_rows(fmhip_model_t m, const Sgd &s, const int32_t *feat, int32_t n_feat, const float *rows, int64_t off, bool last) {
     // (judged as SGD: the touched-rows exchange refuses AdaGrad with decay up front, by the plan's optimizer, on every rank alike —
     // a rank whose optimizer changed since the plan must not stop halfway through the step's collectives)
-    if (!lazy_decay_ok(m, s, TrainRule{}))
+    // FTRL-Proximal is judged by its own rule: never refused for decay (a model that left FTRL since the plan is stopped by the
+    // step's local checks and contributes zeros; what it reaches here with is its own rule again)
+    if (!m->rule.ftrl() && !lazy_decay_ok(m, s, TrainRule{}))
         return fail(FMHIP_ERR_UNSUPPORTED, "a rows-only update needs weight decay that fits the tables' scale (0.5 <= 1 - eta*reg <= 1)");
     // every slice of a step starts from the scale the step began with (m->sv / m->sw move with the LAST slice only)
-    const bool ada = m->rule.adagrad();      // (its tables stay at scale 1)
+    const bool ada = m->rule.adagrad() || m->rule.ftrl();      // (their tables stay at scale 1)
     const double sv_out = ada ? 1.0 : m->sv * s.dv(), sw_out = ada ? 1.0 : m->sw * s.dw();
     ApplyArgs a = apply_args(m, s, rows);
     a.rows_only = 1;

@@ -576,6 +576,27 @@ class HipDataParallelSGD(FMLearn):
         return fm
 
 
+class HipDataParallelFTRL(HipDataParallelSGD):
+    """``HipDataParallelSGD`` under FTRL-Proximal with L1 (``HipFTRL``'s keywords; include/fmhip_ftrl.h).  `plan` agrees the rule's
+    settings over the ranks.  exchange: "dense", "pipelined" or "touched" — the touched-rows exchange is exact with l1, l2 > 0 (a row no
+    rank's batch touched does not move under this rule); "sharded" is refused on every rank (every rank's state would hold its own
+    share only).  Equal state on every rank is the caller's job, as equal parameters are: start every replica from the same model."""
+
+    def __init__(self, comm, alpha=0.1, beta=1.0, l1w=0.0, l1v=0.0, l2_0=0.0, l2w=0.0, l2v=0.0, ftrl_init=0.0, loss="squared", pairs=False,
+                 upper_fractions=(0.05, 0.15, 0.3, 0.55), exchange="dense"):
+        import math
+        for name, x in (("alpha", alpha), ("l2_0", l2_0), ("l2w", l2w), ("l2v", l2v)):
+            if not (math.isfinite(float(x)) and float(x) >= 0.0):
+                raise ValueError("%s must be finite and >= 0, not %r" % (name, x))
+        rule = _ffi.FtrlRule(loss, pairs, beta, ftrl_init, l1w, l1v)      # (validated before the communicator is touched)
+        super().__init__(comm, eta=alpha, reg0=l2_0, regw=l2w, regv=l2v, upper_fractions=upper_fractions, exchange=exchange, loss=loss,
+                         pairs=pairs)
+        del self.adagrad_eps, self.adagrad_init
+        self.alpha, self.l2_0, self.l2w, self.l2v = self.eta, self.reg0, self.regw, self.regv
+        self.rule = rule.publish(self)
+        self.optimizer = "ftrl"
+
+
 def shard_rows(rows, rank, world):
     """Contiguous row shard [lo, hi) of `rank`.  `rows` = the CSR row_ptr array: balanced by stored
     nonzeros (fmhip_shard_rows) — the right split for skewed real data; `rows` = a row

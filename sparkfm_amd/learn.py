@@ -85,6 +85,39 @@ class HipSGD(FMLearn):
         return st.as_dict() if want_stats else None
 
 
+class HipFTRL(HipSGD):
+    """``HipSGD`` under FTRL-Proximal with L1 (include/fmhip_ftrl.h; McMahan et al., the `ftrl` optimizer of xLearn and alphaFM):
+    per-coordinate rates like AdaGrad's plus an L1 term that leaves most of a wide model EXACTLY zero (``FMModel.nonzeros()``).
+
+        fm = FM(train, 4, maxIteration=20).learnWith(HipFTRL.run(loss="logistic", alpha=0.1, beta=0.05, l1w=1.0, l2w=1e-4, l2v=1e-4))
+
+    `alpha`: the step size (the training calls' eta).  `beta`: added to sqrt(n) in every rate.  `l1w`, `l1v`: the L1 of the linear
+    weights and of the factors (w0 has none).  `l2_0`, `l2w`, `l2v`: the L2 of the rule's closed form (the calls' reg0 / regw /
+    regv — not a decay: a parameter whose gradient is zero keeps every bit, so a batch that touches few rows of a wide model
+    updates those rows only, whatever the regularisation).  `ftrl_init`: what the accumulators n start at.  Per parameter, with g
+    the batch's mean gradient:  n' = n + g^2;  zeta' = zeta + alpha g - (sqrt(n') - sqrt(n)) theta;
+    theta' = 0 if |zeta'| <= alpha l1 else -(zeta' - sign(zeta') alpha l1) / (beta + sqrt(n') + alpha l2).
+    With l1 = l2 = 0 that is AdaGrad with eps = beta.  Note that an L1 on V beyond its initial scale zeroes EVERY factor row — the
+    gradient of v_i vanishes where all of V is zero — so l1v is for models whose factors have grown; l1w is the usual knob.
+    `loss`, `pairs`, `shuffle_seed`: as ``HipSGD``.  ``learn`` / ``step`` are inherited and take a ``DataSet`` (weighted too) or a
+    ``RelationalData``; both put the rule on the model first (the same settings again keep its state; changed ones restart it)."""
+
+    def __init__(self, alpha=0.1, beta=1.0, l1w=0.0, l1v=0.0, l2_0=0.0, l2w=0.0, l2v=0.0, ftrl_init=0.0, loss="squared", pairs=False,
+                 shuffle_seed=None):
+        import math
+        for name, x in (("alpha", alpha), ("l2_0", l2_0), ("l2w", l2w), ("l2v", l2v)):
+            if not (math.isfinite(float(x)) and float(x) >= 0.0):
+                raise ValueError("%s must be finite and >= 0, not %r" % (name, x))
+        self.alpha = self.eta = float(alpha)
+        self.l2_0, self.l2w, self.l2v = float(l2_0), float(l2w), float(l2v)
+        self.reg0, self.regw, self.regv = self.l2_0, self.l2w, self.l2v
+        self.rule = _ffi.FtrlRule(loss, pairs, beta, ftrl_init, l1w, l1v).publish(self)
+        self.optimizer = "ftrl"
+        self.shuffle_seed = shuffle_seed
+        self._epoch = 0
+        self.last_stats = None
+
+
 class HipALS(FMLearn):
     """The reference's own learner on the GPU: one ``learn`` = one ``ALS.learn`` pass
     (S/fm/lib/ALS.scala:15-75) in fp64, using the MODEL's regularisers ``fm.reg0/regw/regv`` as the

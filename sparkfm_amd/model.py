@@ -382,3 +382,37 @@ class FMModel(Model):
         _ffi.check(_ffi.load().fmhip_batch_grad(self.handle, dataset.handle, batch, _ffi.ptr(gv), _ffi.ptr(gw),
                                                 C.byref(g0), C.byref(st)))
         return gv.reshape((self.num_factor, n1), order="F"), gw, g0.value, st.as_dict()
+
+    # -- FTRL-Proximal (include/fmhip_ftrl.h) --------------------------------------------
+    def nonzeros(self):
+        """Exact counts over the model on the device (fmhip_model_nonzeros): dict of w_nonzero (of w_total = num_attribute + 1),
+        v_nonzero (of v_total = w_total * num_factor) and features_all_zero — features whose w and whole V row are zero."""
+        w, v, z = C.c_int64(), C.c_int64(), C.c_int64()
+        _ffi.check(_ffi.load().fmhip_model_nonzeros(self.handle, C.byref(w), C.byref(v), C.byref(z)))
+        n1 = self.num_attribute + 1
+        return dict(w_nonzero=int(w.value), v_nonzero=int(v.value), features_all_zero=int(z.value), w_total=n1,
+                    v_total=n1 * self.num_factor)
+
+    def ftrl_state(self):
+        """The FTRL state of a model under that rule (``HipFTRL``; fmhip_model_get_ftrl_state), for checkpoints: dict of z0, zw
+        (n1), zv (k, n1), n0, nw, nv — zeta and n of w0, w and v, shaped like them."""
+        n1, k = self.num_attribute + 1, self.num_factor
+        z0, n0 = C.c_double(), C.c_double()
+        zw, nw, zv, nv = np.empty(n1), np.empty(n1), np.empty(k * n1), np.empty(k * n1)
+        _ffi.check(_ffi.load().fmhip_model_get_ftrl_state(self.handle, C.byref(z0), _ffi.ptr(zw), _ffi.ptr(zv), C.byref(n0),
+                                                          _ffi.ptr(nw), _ffi.ptr(nv)))
+        return dict(z0=z0.value, zw=zw, zv=zv.reshape((k, n1), order="F"), n0=n0.value, nw=nw, nv=nv.reshape((k, n1), order="F"))
+
+    def set_ftrl_state(self, state):
+        """Writes a state read by ``ftrl_state`` back (fmhip_model_set_ftrl_state).  The model must be under FTRL with the settings
+        the state was trained with (``_ffi.FtrlRule(...).set_on(fm.handle)``, or a first ``HipFTRL`` step): parameters and state
+        restored into a fresh model continue the run bit for bit."""
+        n1, k = self.num_attribute + 1, self.num_factor
+        flat = {}
+        for name, shape in (("zw", (n1,)), ("nw", (n1,)), ("zv", (k, n1)), ("nv", (k, n1))):
+            a = np.asarray(state[name], np.float64)
+            if a.shape != shape:
+                raise ValueError("%s must have shape %r, not %r" % (name, shape, a.shape))
+            flat[name] = np.ascontiguousarray(a.reshape(-1, order="F"))
+        _ffi.check(_ffi.load().fmhip_model_set_ftrl_state(self.handle, float(state["z0"]), _ffi.ptr(flat["zw"]), _ffi.ptr(flat["zv"]),
+                                                          float(state["n0"]), _ffi.ptr(flat["nw"]), _ffi.ptr(flat["nv"])))
