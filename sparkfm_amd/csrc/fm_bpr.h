@@ -22,14 +22,16 @@ struct BprSampleArgs {
 int bpr_sample_blocks(int64_t n_pairs);
 hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s);
 
-// The adaptive sampler (k_bpr_sample_adaptive; the rule: include/fmhip_bpr_adaptive.h).  A group of G = Kp / 4 lanes (8 .. 64) per
-// pair: lane l keeps floats 4l .. 4l+3 of the context's q row in registers, the group's lanes draw the pair's n_cand candidate
-// rows side by side (lane l candidates l, l + G, ...; rng::negative_row with group0 = c << 4), then candidate by candidate the
-// group gathers the row's q slice, multiplies and sums over the group by an xor-shuffle tree — an order Kp alone fixes — and lane 0
-// writes the first strict maximum into map[2p + 1].  Qu / Qi / yqi are what the kFwdQ forwards of the two blocks left (rel.Q,
-// rel.yq); floats k .. Kp-1 of the context's slice (the packed slot and the padding) are cleared in registers, so the score does
-// not rest on what the tables hold there.  Record mode (rec_rows set): pairs [p0, p1) only, every candidate's row and score out,
-// the mapping left alone.
+// The scored samplers' candidate walk (k_bpr_sample_walk).  A group of G = Kp / 4 lanes (8 .. 64) per pair: lane l keeps floats
+// 4l .. 4l+3 of the context's q row in registers, the group's lanes draw the pair's n_cand candidate rows side by side (lane l
+// candidates l, l + G, ...; rng::negative_row with group0 = c << 4), then candidate by candidate the group gathers the row's q
+// slice, multiplies and sums over the group by an xor-shuffle tree — an order Kp alone fixes — and hands row and score to the
+// sampler's choice rule, whose lane 0 writes the kept row into map[2p + 1].  Qu / Qi / yqi are what the kFwdQ forwards of the two
+// blocks left (rel.Q, rel.yq); floats k .. Kp-1 of the context's slice (the packed slot and the padding) are cleared in registers,
+// so the score does not rest on what the tables hold there.  Record mode (rec_rows set): pairs [p0, p1) only, every candidate's row
+// and score out, nothing else written, no early stop.
+//
+// Best of C (the rule: include/fmhip_bpr_adaptive.h) adds nothing to the walk's arguments: it keeps the first strict maximum.
 struct BprAdaptiveArgs {
     BprSampleArgs s;           // part: [bpr_adaptive_blocks][3] {attempts, forced, replaced pairs}; total: [3]
     int32_t n_cand;            // 1 .. kBprMaxCand
@@ -44,11 +46,10 @@ constexpr int kBprMaxCand = 64;
 int bpr_adaptive_blocks(int Kp, int64_t n_pairs);
 hipError_t launch_bpr_sample_adaptive(int Kp, const BprAdaptiveArgs &a, hipStream_t s);
 
-// The WARP sampler (k_bpr_sample_warp; the rule: include/fmhip_warp.h): the adaptive sampler's groups, draws and scores, with the
-// pair's positive (map[2p]) gathered and scored first by the same code; the kept row is the FIRST candidate whose score is
-// strictly above thr = s+ - margin, N = 1 + its index (0: none, candidate 0's row kept).  Lane 0 writes map[2p + 1], the pair's
-// weight W[N] to c[2p] and c[2p + 1], and N to trials[p].  A group stops scoring at the end of the chunk that holds its first
-// violator.  Record mode: pairs [p0, p1), every candidate's row and score and s+ out, nothing else written, no early stop.
+// WARP (the rule: include/fmhip_warp.h) adds the pair's positive (map[2p]), gathered and scored before the walk by the walk's
+// code; the kept row is the FIRST candidate whose score is strictly above thr = s+ - margin, N = 1 + its index (0: none,
+// candidate 0's row kept).  Lane 0 also writes the pair's weight W[N] to c[2p] and c[2p + 1], and N to trials[p].  A group stops
+// scoring at the end of the chunk that holds its first violator.  Record mode: s+ out as well.
 struct BprWarpArgs {
     BprAdaptiveArgs a;         // a.s.part: [bpr_adaptive_blocks][2] {violated pairs, sum of N over them}; a.s.total: [2]
     float margin;

@@ -1,9 +1,10 @@
 // fm_bpr.hip — the BPR trainer's device work (fm_bpr.h): k_bpr_sample draws a negative row per pair, and the k_bpr_inv_* kernels
 // around one rocPRIM radix sort and two scans rebuild the candidates relation's inverse map of a batch.  Integer arithmetic only;
-// every address has one writer and nothing depends on the launch shape.  k_bpr_sample_adaptive (include/fmhip_bpr_adaptive.h) draws
-// several candidates per pair with the same integer code and keeps the one the model scores highest: the one place with fp32 in it,
-// a dot product whose summation order the row width alone fixes.  k_bpr_sample_warp (include/fmhip_warp.h) scores the same candidates
-// the same way and keeps the first one that violates the margin against the pair's positive, with the pair's rank weight beside it.
+// every address has one writer and nothing depends on the launch shape.  k_bpr_sample_walk draws several candidates per pair with
+// the same integer code and scores them under the model: the one place with fp32 in it, a dot product whose summation order the row
+// width alone fixes.  What a score does to the pair's choice is the walk's rule: BestOfC (include/fmhip_bpr_adaptive.h) keeps the
+// candidate the model scores highest, FirstViolator (include/fmhip_warp.h) the first one that violates the margin against the pair's
+// positive, with the pair's rank weight beside it.
 #include "fm_bpr.h"
 #include "fm_device.h"      // f4dot; grid_blocks (fm_kernels.h)
 #include "mcmc_rng.h"
@@ -63,20 +64,112 @@ __global__ __launch_bounds__(kT) void k_bpr_total(const u64 *part, int n_blocks,
     block_sums_u64<N>(s, total);
 }
 
-// ---- the adaptive sampler (fm_bpr.h: BprAdaptiveArgs) -----------------------------------------------------------------------------
+// ---- the scored samplers: one candidate walk (fm_bpr.h: BprAdaptiveArgs), a choice rule per sampler --------------------------------
 
 constexpr int kCandChunk = 4;       // candidate rows a group has in flight before it reduces: the gathers' latency overlaps
 
+// The scores of N rows of Qi, lane l of a group of G holding floats 4l .. 4l+3 of each and of the context's slice: yq_i + (the lanes'
+// 4-term fmaf chains summed by the xor tree over G) — an order G alone fixes, the same in every lane of the group.
+template <int G, int N>
+__device__ __forceinline__ void group_scores(const float4 &qu, const float4 (&qi)[N], const float (&yq)[N], float (&s)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) s[i] = f4dot(qu, qi[i]);
+#pragma unroll
+    for (int m = G >> 1; m >= 1; m >>= 1)
+#pragma unroll
+        for (int i = 0; i < N; ++i) s[i] += __shfl_xor(s[i], m, G);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        s[i] = yq[i] + s[i];
+        // (the sums are formed here, so the yq loads are issued beside the gathers: left free, the compiler sinks each load into
+        // its candidate's branch of the caller, and a chunk pays four load latencies in a row)
+        asm volatile("" : "+v"(s[i]));
+    }
+}
+
+// A choice rule is the state of one pair's walk and what the walk calls on it: begin (before the first draw), drawn (per draw of a
+// pair that exists, with the draw's {attempts, forced}), done (asked at the loop heads: may the group stop?), see (per candidate, in
+// order, with its row and score) and finish (lane 0 of a pair that exists, not in record mode: the outputs and the pair's share of
+// the N counters).
+
+// Best of C: the first strict maximum.
+struct BestOfC {
+    using Args = BprAdaptiveArgs;
+    static constexpr int N = 3;      // {attempts, forced, replaced pairs}
+    static __host__ __device__ const BprAdaptiveArgs &walk_args(const Args &a) { return a; }
+    static bool valid(const Args &, bool) { return true; }
+    int32_t keep = 0, keep_c = 0;
+    float best = 0.f;
+    template <int G, bool RECORD>
+    __device__ __forceinline__ void begin(const Args &, int64_t, const float4 &, int, bool) {}
+    __device__ __forceinline__ void drawn(u64 (&v)[N], int at, int f) const {
+        v[0] += (u64)at;
+        v[1] += (u64)f;
+    }
+    static constexpr __device__ bool done() { return false; }
+    __device__ __forceinline__ void see(int c, int32_t row, float s) {
+        if (c == 0 || s > best) {      // candidate 0 is the incumbent; a NaN is never greater
+            best = s;
+            keep = row;
+            keep_c = c;
+        }
+    }
+    __device__ __forceinline__ void finish(const Args &a, int64_t p, u64 (&v)[N]) const {
+        a.s.map[2 * p + 1] = keep;
+        v[2] += keep_c != 0 ? 1u : 0u;
+    }
+};
+
+// The first violator (WARP): the positive's row is scored first, by the code that scores a candidate; a candidate violates iff its
+// score is strictly above thr (false for a NaN on either side).  Every lane of a group holds the same scores, so `n_first` and the
+// early exit are uniform over the group: a group that leaves the candidate loops leaves whole, and the width-G shuffles of the
+// groups still in them read only their own lanes.
+struct FirstViolator {
+    using Args = BprWarpArgs;
+    static constexpr int N = 2;      // {violated pairs, sum of their trials}
+    static __host__ __device__ const BprAdaptiveArgs &walk_args(const Args &w) { return w.a; }
+    static bool valid(const Args &w, bool record) { return w.margin >= 0.f && (record ? w.rec_pos != nullptr : w.W && w.c && w.trials); }
+    float thr = 0.f;
+    int32_t keep = 0, n_first = 0;
+    template <int G, bool RECORD>
+    __device__ __forceinline__ void begin(const Args &w, int64_t p, const float4 &qu, int l, bool writes) {
+        const int32_t ipos = w.a.s.map[2 * p];      // (the positive: no sampler writes the even entries)
+        const float4 qp[1] = {reinterpret_cast<const float4 *>(w.a.Qi + (size_t)ipos * (4 * G))[l]};
+        const float yp[1] = {w.a.yqi[ipos]};
+        float spos[1];
+        group_scores<G, 1>(qu, qp, yp, spos);
+        if (RECORD && writes) w.rec_pos[p - w.a.p0] = spos[0];
+        thr = spos[0] - w.margin;
+    }
+    __device__ __forceinline__ void drawn(u64 (&)[N], int, int) const {}
+    __device__ __forceinline__ bool done() const { return n_first != 0; }
+    __device__ __forceinline__ void see(int c, int32_t row, float s) {
+        if (c == 0) keep = row;                        // no violator: candidate 0's row
+        if (n_first == 0 && s > thr) {                 // the first violator; a NaN is never greater
+            n_first = c + 1;
+            keep = row;
+        }
+    }
+    __device__ __forceinline__ void finish(const Args &w, int64_t p, u64 (&v)[N]) const {
+        w.a.s.map[2 * p + 1] = keep;
+        const float cw = w.W[n_first];
+        reinterpret_cast<float2 *>(w.c)[p] = make_float2(cw, cw);
+        w.trials[p] = n_first;
+        v[0] += n_first != 0 ? 1u : 0u;
+        v[1] += (u64)n_first;
+    }
+};
+
 // G lanes per pair, kT / G pairs per block and pass.  The trip count is the block's (`base` is uniform), and a group whose pair lies
-// past the end works on the last pair again and writes nothing: no lane leaves before the block's last shuffle.  A score is
-// yq_i + (the lanes' 4-term fmaf chains summed by the xor tree over G): the same in every lane of the group, whatever the grid.
-template <int G, bool RECORD>
-__global__ __launch_bounds__(kT) void k_bpr_sample_adaptive(BprAdaptiveArgs a) {
+// past the end works on the last pair again and writes nothing: no lane leaves before the block's last shuffle.
+template <int G, class Rule, bool RECORD>
+__global__ __launch_bounds__(kT) void k_bpr_sample_walk(typename Rule::Args ra) {
     constexpr int KP = 4 * G, GPB = kT / G;
+    const BprAdaptiveArgs &a = Rule::walk_args(ra);
     const int l = threadIdx.x & (G - 1), grp = threadIdx.x / G;
     const int64_t first = RECORD ? a.p0 : 0, end = RECORD ? a.p1 : a.s.n_pairs;
     const int C = a.n_cand;
-    u64 att = 0, forced = 0, repl = 0;
+    u64 v[Rule::N] = {};
     for (int64_t base = first + (int64_t)blockIdx.x * GPB; base < end; base += (int64_t)gridDim.x * GPB) {
         const bool live = base + grp < end;
         const int64_t p = live ? base + grp : end - 1;
@@ -88,24 +181,21 @@ __global__ __launch_bounds__(kT) void k_bpr_sample_adaptive(BprAdaptiveArgs a) {
         if (4 * l + 1 >= a.k) qu.y = 0.f;
         if (4 * l + 2 >= a.k) qu.z = 0.f;
         if (4 * l + 3 >= a.k) qu.w = 0.f;
-        int32_t keep = 0, keep_c = 0;
-        float best = 0.f;
-        for (int c0 = 0; c0 < C; c0 += G) {
+        Rule r;
+        r.template begin<G, RECORD>(ra, p, qu, l, live && l == 0);
+        for (int c0 = 0; c0 < C && (RECORD || !r.done()); c0 += G) {
             // the group's lanes draw candidates c0 .. c0 + G - 1 side by side
             int32_t mine = 0;
             if (c0 + l < C) {
                 int at = 0, f = 0;
                 mine = rng::negative_row(a.s.seed, (uint32_t)p, a.s.t, (uint32_t)a.s.M, a.s.prow + lo, len, &at, &f, (uint32_t)(c0 + l) << 4);
-                if (live) {
-                    att += (u64)at;
-                    forced += (u64)f;
-                }
+                if (live) r.drawn(v, at, f);
             }
             const int n = C - c0 < G ? C - c0 : G;
-            for (int j0 = 0; j0 < n; j0 += kCandChunk) {
+            for (int j0 = 0; j0 < n && (RECORD || !r.done()); j0 += kCandChunk) {
                 int32_t row[kCandChunk];
                 float4 qi[kCandChunk];
-                float yq[kCandChunk], d[kCandChunk];
+                float yq[kCandChunk], s[kCandChunk];
 #pragma unroll
                 for (int jj = 0; jj < kCandChunk; ++jj) {
                     const int j = j0 + jj < n ? j0 + jj : n - 1;       // (past the last candidate: the last one again, not compared)
@@ -113,165 +203,57 @@ __global__ __launch_bounds__(kT) void k_bpr_sample_adaptive(BprAdaptiveArgs a) {
                     qi[jj] = reinterpret_cast<const float4 *>(a.Qi + (size_t)row[jj] * KP)[l];
                     yq[jj] = a.yqi[row[jj]];
                 }
-#pragma unroll
-                for (int jj = 0; jj < kCandChunk; ++jj) d[jj] = f4dot(qu, qi[jj]);
-#pragma unroll
-                for (int m = G >> 1; m >= 1; m >>= 1)
-#pragma unroll
-                    for (int jj = 0; jj < kCandChunk; ++jj) d[jj] += __shfl_xor(d[jj], m, G);
+                group_scores<G, kCandChunk>(qu, qi, yq, s);
 #pragma unroll
                 for (int jj = 0; jj < kCandChunk; ++jj) {
                     const int c = c0 + j0 + jj;
                     if (j0 + jj >= n) break;
-                    const float s = yq[jj] + d[jj];
                     if (RECORD && live && l == 0) {
                         const size_t at = (size_t)(p - a.p0) * (size_t)C + (size_t)c;
                         a.rec_rows[at] = row[jj];
-                        a.rec_scores[at] = s;
+                        a.rec_scores[at] = s[jj];
                     }
-                    if (c == 0 || s > best) {      // candidate 0 is the incumbent; a NaN is never greater
-                        best = s;
-                        keep = row[jj];
-                        keep_c = c;
-                    }
+                    r.see(c, row[jj], s[jj]);
                 }
             }
         }
-        if (!RECORD && live && l == 0) {
-            a.s.map[2 * p + 1] = keep;
-            repl += keep_c != 0 ? 1u : 0u;
-        }
+        if (!RECORD && live && l == 0) r.finish(ra, p, v);
     }
     if (RECORD) return;
-    u64 v[3] = {att, forced, repl};
-    block_sums_u64<3>(v, a.s.part + 3 * (size_t)blockIdx.x);
+    block_sums_u64<Rule::N>(v, a.s.part + Rule::N * (size_t)blockIdx.x);
 }
 
-template <int G>
-hipError_t launch_adaptive(const BprAdaptiveArgs &a, hipStream_t s) {
+// record mode (rec_rows set): the walk alone; else the walk and the one-block sum of its partials
+template <int G, class Rule>
+hipError_t launch_walk(const typename Rule::Args &ra, hipStream_t s) {
+    const BprAdaptiveArgs &a = Rule::walk_args(ra);
     const bool record = a.rec_rows != nullptr;
     const int64_t n = record ? (int64_t)a.p1 - a.p0 : a.s.n_pairs;
     const int blocks = bpr_adaptive_blocks(4 * G, n);
     if (record) {
-        hipLaunchKernelGGL((k_bpr_sample_adaptive<G, true>), dim3((unsigned)blocks), dim3(kT), 0, s, a);
+        hipLaunchKernelGGL((k_bpr_sample_walk<G, Rule, true>), dim3((unsigned)blocks), dim3(kT), 0, s, ra);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((k_bpr_sample_adaptive<G, false>), dim3((unsigned)blocks), dim3(kT), 0, s, a);
+    hipLaunchKernelGGL((k_bpr_sample_walk<G, Rule, false>), dim3((unsigned)blocks), dim3(kT), 0, s, ra);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_bpr_total<3>, dim3(1), dim3(kT), 0, s, a.s.part, blocks, a.s.total);
+    hipLaunchKernelGGL(k_bpr_total<Rule::N>, dim3(1), dim3(kT), 0, s, a.s.part, blocks, a.s.total);
     return hipGetLastError();
 }
 
-// ---- the WARP sampler (fm_bpr.h: BprWarpArgs) ---------------------------------------------------------------------------------------
-
-// The adaptive kernel's lane layout, draws and score order.  The positive's row is gathered and scored first, by the code that
-// scores a candidate; a candidate violates iff its score is strictly above thr (false for a NaN on either side).  Every lane of a
-// group holds the same scores, so `n_first` and the early exit are uniform over the group: a group that leaves the candidate loops
-// leaves whole, and the width-G shuffles of the groups still in them read only their own lanes.
-template <int G, bool RECORD>
-__global__ __launch_bounds__(kT) void k_bpr_sample_warp(BprWarpArgs w) {
-    constexpr int KP = 4 * G, GPB = kT / G;
-    const BprAdaptiveArgs &a = w.a;
-    const int l = threadIdx.x & (G - 1), grp = threadIdx.x / G;
-    const int64_t first = RECORD ? a.p0 : 0, end = RECORD ? a.p1 : a.s.n_pairs;
-    const int C = a.n_cand;
-    u64 violated = 0, trials = 0;
-    for (int64_t base = first + (int64_t)blockIdx.x * GPB; base < end; base += (int64_t)gridDim.x * GPB) {
-        const bool live = base + grp < end;
-        const int64_t p = live ? base + grp : end - 1;
-        const int32_t u = a.s.ictx[p / a.s.n_neg];
-        const int64_t lo = a.s.pptr[u];
-        const int32_t len = (int32_t)(a.s.pptr[u + 1] - lo);
-        float4 qu = reinterpret_cast<const float4 *>(a.Qu + (size_t)u * KP)[l];
-        if (4 * l + 0 >= a.k) qu.x = 0.f;      // the packed slot and the padding are no factors
-        if (4 * l + 1 >= a.k) qu.y = 0.f;
-        if (4 * l + 2 >= a.k) qu.z = 0.f;
-        if (4 * l + 3 >= a.k) qu.w = 0.f;
-        float thr;
-        {
-            const int32_t ipos = a.s.map[2 * p];      // (the positive: no sampler writes the even entries)
-            const float4 qp = reinterpret_cast<const float4 *>(a.Qi + (size_t)ipos * KP)[l];
-            const float yp = a.yqi[ipos];
-            float dp = f4dot(qu, qp);
-#pragma unroll
-            for (int m = G >> 1; m >= 1; m >>= 1) dp += __shfl_xor(dp, m, G);
-            const float spos = yp + dp;
-            if (RECORD && live && l == 0) w.rec_pos[p - a.p0] = spos;
-            thr = spos - w.margin;
-        }
-        int32_t keep = 0, n_first = 0;
-        for (int c0 = 0; c0 < C && (RECORD || n_first == 0); c0 += G) {
-            // the group's lanes draw candidates c0 .. c0 + G - 1 side by side
-            int32_t mine = 0;
-            if (c0 + l < C) {
-                int at = 0, f = 0;
-                mine = rng::negative_row(a.s.seed, (uint32_t)p, a.s.t, (uint32_t)a.s.M, a.s.prow + lo, len, &at, &f, (uint32_t)(c0 + l) << 4);
-            }
-            const int n = C - c0 < G ? C - c0 : G;
-            for (int j0 = 0; j0 < n && (RECORD || n_first == 0); j0 += kCandChunk) {
-                int32_t row[kCandChunk];
-                float4 qi[kCandChunk];
-                float yq[kCandChunk], d[kCandChunk];
-#pragma unroll
-                for (int jj = 0; jj < kCandChunk; ++jj) {
-                    const int j = j0 + jj < n ? j0 + jj : n - 1;       // (past the last candidate: the last one again, not compared)
-                    row[jj] = __shfl(mine, j, G);
-                    qi[jj] = reinterpret_cast<const float4 *>(a.Qi + (size_t)row[jj] * KP)[l];
-                    yq[jj] = a.yqi[row[jj]];
-                }
-#pragma unroll
-                for (int jj = 0; jj < kCandChunk; ++jj) d[jj] = f4dot(qu, qi[jj]);
-#pragma unroll
-                for (int m = G >> 1; m >= 1; m >>= 1)
-#pragma unroll
-                    for (int jj = 0; jj < kCandChunk; ++jj) d[jj] += __shfl_xor(d[jj], m, G);
-#pragma unroll
-                for (int jj = 0; jj < kCandChunk; ++jj) {
-                    const int c = c0 + j0 + jj;
-                    if (j0 + jj >= n) break;
-                    const float s = yq[jj] + d[jj];
-                    if (RECORD && live && l == 0) {
-                        const size_t at = (size_t)(p - a.p0) * (size_t)C + (size_t)c;
-                        a.rec_rows[at] = row[jj];
-                        a.rec_scores[at] = s;
-                    }
-                    if (c == 0) keep = row[jj];                        // no violator: candidate 0's row
-                    if (n_first == 0 && s > thr) {                     // the first violator; a NaN is never greater
-                        n_first = c + 1;
-                        keep = row[jj];
-                    }
-                }
-            }
-        }
-        if (!RECORD && live && l == 0) {
-            a.s.map[2 * p + 1] = keep;
-            const float cw = w.W[n_first];
-            reinterpret_cast<float2 *>(w.c)[p] = make_float2(cw, cw);
-            w.trials[p] = n_first;
-            violated += n_first != 0 ? 1u : 0u;
-            trials += (u64)n_first;
-        }
+template <class Rule>
+hipError_t launch_scored(int Kp, const typename Rule::Args &ra, hipStream_t s) {
+    const BprAdaptiveArgs &a = Rule::walk_args(ra);
+    const bool record = a.rec_rows != nullptr;
+    if (a.n_cand < 1 || a.n_cand > kBprMaxCand || a.k < 0 || a.k > Kp || !Rule::valid(ra, record)) return hipErrorInvalidValue;
+    if (record && (!a.rec_scores || a.p0 < 0 || a.p1 > a.s.n_pairs || a.p0 >= a.p1)) return hipErrorInvalidValue;
+    switch (Kp) {
+        case 32: return launch_walk<8, Rule>(ra, s);
+        case 64: return launch_walk<16, Rule>(ra, s);
+        case 128: return launch_walk<32, Rule>(ra, s);
+        case 256: return launch_walk<64, Rule>(ra, s);
+        default: return hipErrorInvalidValue;      // (padded_factors: a power of two in [32, 256])
     }
-    if (RECORD) return;
-    u64 v[2] = {violated, trials};
-    block_sums_u64<2>(v, a.s.part + 2 * (size_t)blockIdx.x);
-}
-
-template <int G>
-hipError_t launch_warp(const BprWarpArgs &w, hipStream_t s) {
-    const bool record = w.a.rec_rows != nullptr;
-    const int64_t n = record ? (int64_t)w.a.p1 - w.a.p0 : w.a.s.n_pairs;
-    const int blocks = bpr_adaptive_blocks(4 * G, n);
-    if (record) {
-        hipLaunchKernelGGL((k_bpr_sample_warp<G, true>), dim3((unsigned)blocks), dim3(kT), 0, s, w);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((k_bpr_sample_warp<G, false>), dim3((unsigned)blocks), dim3(kT), 0, s, w);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_bpr_total<2>, dim3(1), dim3(kT), 0, s, w.a.s.part, blocks, w.a.s.total);
-    return hipGetLastError();
 }
 
 // ---- the inverse map --------------------------------------------------------------------------------------------------------------
@@ -419,32 +401,8 @@ hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s) {
 
 int bpr_adaptive_blocks(int Kp, int64_t n_pairs) { return grid_blocks(n_pairs, kT / (Kp / 4), 4096); }      // a group of Kp / 4 lanes per pair
 
-hipError_t launch_bpr_sample_adaptive(int Kp, const BprAdaptiveArgs &a, hipStream_t s) {
-    if (a.n_cand < 1 || a.n_cand > kBprMaxCand || a.k < 0 || a.k > Kp) return hipErrorInvalidValue;
-    if (a.rec_rows && (!a.rec_scores || a.p0 < 0 || a.p1 > a.s.n_pairs || a.p0 >= a.p1)) return hipErrorInvalidValue;
-    switch (Kp) {
-        case 32: return launch_adaptive<8>(a, s);
-        case 64: return launch_adaptive<16>(a, s);
-        case 128: return launch_adaptive<32>(a, s);
-        case 256: return launch_adaptive<64>(a, s);
-        default: return hipErrorInvalidValue;      // (padded_factors: a power of two in [32, 256])
-    }
-}
-
-hipError_t launch_bpr_sample_warp(int Kp, const BprWarpArgs &w, hipStream_t s) {
-    const BprAdaptiveArgs &a = w.a;
-    if (a.n_cand < 1 || a.n_cand > kBprMaxCand || a.k < 0 || a.k > Kp || !(w.margin >= 0.f)) return hipErrorInvalidValue;
-    if (a.rec_rows) {
-        if (!a.rec_scores || !w.rec_pos || a.p0 < 0 || a.p1 > a.s.n_pairs || a.p0 >= a.p1) return hipErrorInvalidValue;
-    } else if (!w.W || !w.c || !w.trials) return hipErrorInvalidValue;
-    switch (Kp) {
-        case 32: return launch_warp<8>(w, s);
-        case 64: return launch_warp<16>(w, s);
-        case 128: return launch_warp<32>(w, s);
-        case 256: return launch_warp<64>(w, s);
-        default: return hipErrorInvalidValue;      // (padded_factors: a power of two in [32, 256])
-    }
-}
+hipError_t launch_bpr_sample_adaptive(int Kp, const BprAdaptiveArgs &a, hipStream_t s) { return launch_scored<BestOfC>(Kp, a, s); }
+hipError_t launch_bpr_sample_warp(int Kp, const BprWarpArgs &w, hipStream_t s) { return launch_scored<FirstViolator>(Kp, w, s); }
 
 hipError_t bpr_inverse_workspace(int32_t rows, int32_t block_rows, size_t *bytes) {
     InvLayout L;

@@ -1,10 +1,11 @@
 // fmhip_bpr.hip — the BPR trainer (include/fmhip_bpr.h): the handle (an owned relational dataset of 2 n_pairs rows over the two
 // borrowed blocks), the resample
 //     k_bpr_sample (the candidates mapping's odd entries) -> per batch the inverse map on the device (fm_bpr.hip) -> the counts back
-// (adaptive, include/fmhip_bpr_adaptive.h: the two blocks' kFwdQ forwards on the model's stream first, then k_bpr_sample_adaptive in
-// k_bpr_sample's place; WARP, include/fmhip_warp.h: the same with k_bpr_sample_warp, which also leaves the pairs' weights for the
-// step's hinge) and the training calls, which are the relational step in its pairs mode (rel_step, fmhip_relational.hip).  The kernels are in
-// fm_bpr.hip; the host arithmetic (the positives' lists, the sampler's twin) in fmhip_host.cpp.
+// (the scored samplers: the two blocks' kFwdQ forwards on the model's stream first, then k_bpr_sample_walk in k_bpr_sample's place —
+// under the best-of-C rule, include/fmhip_bpr_adaptive.h, or under WARP's, include/fmhip_warp.h, which also leaves the pairs' weights
+// for the step's hinge) and the training calls, which are the relational step in its pairs mode (rel_step, fmhip_relational.hip).
+// Every draw goes through resample(), every record call through record_scores().  The kernels are in fm_bpr.hip; the host arithmetic
+// (the positives' lists, the sampler's twin) in fmhip_host.cpp.
 #include "fmhip_internal.h"
 #include "../../include/fmhip_bpr_adaptive.h"
 #include "../../include/fmhip_warp.h"
@@ -55,47 +56,54 @@ BprSampleArgs sample_args(fmhip_bpr_t h, int64_t t) {
     sa.pptr = h->pptr.p;
     sa.prow = h->prow.p;
     sa.map = h->R->rels[1]->map.p;
-    sa.part = h->spart.p;
-    sa.total = h->stotal.p;
+    sa.part = h->part.p;
+    sa.total = h->total.p;
     return sa;
 }
+
+// The samplers, and per sampler the counters its kernel sums, in the order of its public stats struct: uniform {attempts, forced}
+// (fmhip_bpr_sample_stats), best of C {attempts, forced, replaced} (fmhip_bpr_adaptive_stats), WARP {violated, trials}
+// (fmhip_warp_stats, behind `pairs`)
+enum Sampler { kUniform, kBestOfC, kWarp };
+constexpr int kCounters[] = {2, 3, 2};
+
+// the sampler an epoch draws with
+Sampler epoch_sampler(fmhip_bpr_t h) { return h->warp ? kWarp : h->n_cand > 1 ? kBestOfC : kUniform; }
 
 int check_epoch_index(int64_t t) {
     if (t < 0 || t > 0xffffffffll) return fail(FMHIP_ERR_INVALID, "t = %lld: an epoch is in [0, 2^32)", (long long)t);
     return FMHIP_OK;
 }
 
-// What the adaptive sampler reads, queued: the two blocks' kFwdQ forwards on the model's stream (rel_block_forwards), the handle's
-// stream behind them by an event — and behind the steps queued so far, which read the mapping.  -> the sampler's arguments
-int adaptive_args(fmhip_model_t m, fmhip_bpr_t h, int64_t t, BprAdaptiveArgs *out) {
+// What a scored sampler's walk reads, queued: the two blocks' kFwdQ forwards on the model's stream (rel_block_forwards), the
+// handle's stream behind them by an event — and behind the steps queued so far, which read the mapping.  -> the walk's arguments
+// (wa->a) and WARP's margin; the partials sized for `which`
+int scored_args(fmhip_model_t m, fmhip_bpr_t h, int64_t t, Sampler which, BprWarpArgs *wa) {
     fmhip_relational_t R = h->R;
     TRY(rel_block_forwards(m, R));
     if (!h->fwd_done) HIP_TRY(hipEventCreateWithFlags(&h->fwd_done, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(h->fwd_done, m->stream));
     HIP_TRY(hipStreamWaitEvent(h->stream, h->fwd_done, 0));
     if (R->busy_set) HIP_TRY(hipStreamWaitEvent(h->stream, R->busy, 0));
-    TRY(h->apart.ensure(3 * (size_t)bpr_adaptive_blocks(m->Kp, h->n_pairs)));
-    TRY(h->atotal.ensure(3));
-    BprAdaptiveArgs aa{};
-    aa.s = sample_args(h, t);
-    aa.s.part = h->apart.p;
-    aa.s.total = h->atotal.p;
-    aa.n_cand = h->n_cand;
-    aa.k = m->k;
-    aa.Qu = R->rels[0]->Q.p;
-    aa.Qi = R->rels[1]->Q.p;
-    aa.yqi = R->rels[1]->yq.p;
-    *out = aa;
+    TRY(h->part.ensure((size_t)kCounters[which] * (size_t)bpr_adaptive_blocks(m->Kp, h->n_pairs)));
+    *wa = BprWarpArgs{};
+    wa->a.s = sample_args(h, t);
+    wa->a.n_cand = h->n_cand;
+    wa->a.k = m->k;
+    wa->a.Qu = R->rels[0]->Q.p;
+    wa->a.Qi = R->rels[1]->Q.p;
+    wa->a.yqi = R->rels[1]->yq.p;
+    wa->margin = (float)h->warp_margin;
     return FMHIP_OK;
 }
 
-// What the WARP sampler reads and writes, queued as adaptive_args queues it: the weight table (made on the host when the candidate
-// count has changed, uploaded on the handle's stream), the pairs' weights and trial counts, the {violated, trials} partials
-int warp_args(fmhip_model_t m, fmhip_bpr_t h, int64_t t, BprWarpArgs *out) {
-    BprWarpArgs wa{};
-    TRY(adaptive_args(m, h, t, &wa.a));
-    TRY(h->wpart.ensure(2 * (size_t)bpr_adaptive_blocks(m->Kp, h->n_pairs)));
-    TRY(h->wtotal.ensure(2));
+hipError_t launch_scored(Sampler which, int Kp, const BprWarpArgs &wa, hipStream_t s) {
+    return which == kWarp ? launch_bpr_sample_warp(Kp, wa, s) : launch_bpr_sample_adaptive(Kp, wa.a, s);
+}
+
+// What a WARP draw reads and writes on top of scored_args, queued behind it: the weight table (made on the host when the candidate
+// count has changed, uploaded on the handle's stream), the pairs' weights and trial counts
+int warp_outputs(fmhip_bpr_t h, BprWarpArgs *wa) {
     TRY(h->wc.ensure(2 * (size_t)h->n_pairs));
     TRY(h->wtrials.ensure((size_t)h->n_pairs));
     TRY(h->wtab.ensure((size_t)kBprMaxCand + 1));
@@ -105,46 +113,30 @@ int warp_args(fmhip_model_t m, fmhip_bpr_t h, int64_t t, BprWarpArgs *out) {
         h->wtab_cand = h->n_cand;
     }
     HIP_TRY(hipMemcpyAsync(h->wtab.p, h->h_wtab.data(), h->h_wtab.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    wa.a.s.part = h->wpart.p;
-    wa.a.s.total = h->wtotal.p;
-    wa.margin = (float)h->warp_margin;
-    wa.W = h->wtab.p;
-    wa.c = h->wc.p;
-    wa.trials = h->wtrials.p;
-    *out = wa;
+    wa->W = h->wtab.p;
+    wa->c = h->wc.p;
+    wa->trials = h->wtrials.p;
     return FMHIP_OK;
 }
 
-enum Sampler { kUniform, kAdaptive, kWarp };
-
-// the sampler at epoch t, the inverse map of every batch, the batches' counts (one synchronisation); the handle's own stream.
-// m given: the adaptive sampler — or, warp, the WARP sampler — under that model (the caller has checked the two against each other
-// and holds the model's lock), else the uniform one.  total: {attempts, forced}; adaptive, {attempts, forced, replaced}; WARP,
-// {violated, trials}
-int resample(fmhip_bpr_t h, int64_t t, unsigned long long *total_out, fmhip_model_t m = nullptr, bool warp = false) {
+// sampler `which` at epoch t, the inverse map of every batch, the batches' counts (one synchronisation); the handle's own stream.
+// A scored sampler draws under model m (the caller has checked the two against each other and holds the model's lock); the uniform
+// one takes none.  total_out: the sampler's kCounters[which] counters
+int resample(fmhip_bpr_t h, int64_t t, Sampler which, fmhip_model_t m, int64_t *total_out) {
     TRY(check_epoch_index(t));
     TRY(set_device(h->device));
     fmhip_relational_t R = h->R;
     fmhip_relational::Relation &rel = *R->rels[1];
-    const Sampler which = !m ? kUniform : warp ? kWarp : kAdaptive;
-    const int n_total = which == kAdaptive ? 3 : 2;
-    const unsigned long long *d_total = nullptr;
-    if (which == kWarp) {
-        h->warp_drawn = false;                // (until this draw has come back whole)
-        BprWarpArgs wa{};
-        TRY(warp_args(m, h, t, &wa));
-        HIP_TRY(launch_bpr_sample_warp(m->Kp, wa, h->stream));
-        d_total = h->wtotal.p;
-    } else if (m) {
-        BprAdaptiveArgs aa{};
-        TRY(adaptive_args(m, h, t, &aa));
-        HIP_TRY(launch_bpr_sample_adaptive(m->Kp, aa, h->stream));
-        d_total = h->atotal.p;
-    } else {
+    if (which == kWarp) h->warp_drawn = false;      // (until this draw has come back whole)
+    if (which == kUniform) {
         // the mapping and the inverse map are read by the steps queued so far
         if (R->busy_set) HIP_TRY(hipStreamWaitEvent(h->stream, R->busy, 0));
         HIP_TRY(launch_bpr_sample(sample_args(h, t), h->stream));
-        d_total = h->stotal.p;
+    } else {
+        BprWarpArgs wa{};
+        TRY(scored_args(m, h, t, which, &wa));
+        if (which == kWarp) TRY(warp_outputs(h, &wa));
+        HIP_TRY(launch_scored(which, m->Kp, wa, h->stream));
     }
     const size_t nb = R->batches.size();
     for (size_t b = 0; b < nb; ++b) {
@@ -169,7 +161,7 @@ int resample(fmhip_bpr_t h, int64_t t, unsigned long long *total_out, fmhip_mode
     std::vector<int32_t> counts(4 * nb);
     unsigned long long total[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(counts.data(), h->counts.p, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(total, d_total, (size_t)n_total * sizeof total[0], hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(total, h->total.p, (size_t)kCounters[which] * sizeof total[0], hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     int32_t max_part = 0;
     for (size_t b = 0; b < nb; ++b) {
@@ -189,7 +181,34 @@ int resample(fmhip_bpr_t h, int64_t t, unsigned long long *total_out, fmhip_mode
     rel.max_part = max_part;      // (the step's workspace grows to it: ensure_rel_workspace)
     if (which == kWarp) h->warp_drawn = true;
     if (total_out)
-        for (int i = 0; i < 3; ++i) total_out[i] = total[i];
+        for (int i = 0; i < kCounters[which]; ++i) total_out[i] = (int64_t)total[i];
+    return FMHIP_OK;
+}
+
+// Record mode of a scored sampler's walk for pairs [p0, p1) at epoch t, the mapping left alone: every candidate's row and score
+// and, WARP, the positives' scores
+int record_scores(fmhip_model_t m, fmhip_bpr_t h, int64_t t, int64_t p0, int64_t p1, Sampler which, int32_t *rows, float *scores, float *pos_scores) {
+    TRY(check_bpr(m, h));
+    TRY(check_epoch_index(t));
+    if (p0 < 0 || p1 > h->n_pairs || p0 >= p1)
+        return fail(FMHIP_ERR_INVALID, "pairs [%lld, %lld): a non-empty range inside [0, %lld)", (long long)p0, (long long)p1, (long long)h->n_pairs);
+    if (!rows || !scores || (which == kWarp && !pos_scores)) return fail(FMHIP_ERR_INVALID, "an out array is NULL");
+    const size_t np = (size_t)(p1 - p0), n = np * (size_t)h->n_cand;
+    TRY(h->rec_rows.ensure(n));
+    TRY(h->rec_scores.ensure(n));
+    if (which == kWarp) TRY(h->rec_pos.ensure(np));
+    BprWarpArgs wa{};
+    TRY(scored_args(m, h, t, which, &wa));
+    wa.a.p0 = (int32_t)p0;
+    wa.a.p1 = (int32_t)p1;
+    wa.a.rec_rows = h->rec_rows.p;
+    wa.a.rec_scores = h->rec_scores.p;
+    wa.rec_pos = h->rec_pos.p;
+    HIP_TRY(launch_scored(which, m->Kp, wa, h->stream));
+    HIP_TRY(hipMemcpyAsync(rows, h->rec_rows.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(scores, h->rec_scores.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (which == kWarp) HIP_TRY(hipMemcpyAsync(pos_scores, h->rec_pos.p, np * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return FMHIP_OK;
 }
 
@@ -305,13 +324,13 @@ int fmhip_bpr_create(int device, fmhip_dataset_t contexts, fmhip_dataset_t candi
     HIP_TRY(hipMemcpy(H->pptr.p, pptr.data(), pptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     TRY(H->prow.alloc(std::max<size_t>(prow.size(), 1)));
     if (!prow.empty()) HIP_TRY(hipMemcpy(H->prow.p, prow.data(), prow.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    TRY(H->spart.alloc(2 * (size_t)bpr_sample_blocks(n_pairs)));
-    TRY(H->stotal.alloc(2));
+    TRY(H->part.alloc(2 * (size_t)bpr_sample_blocks(n_pairs)));      // (the uniform sampler's need; the scored ones grow it)
+    TRY(H->total.alloc(3));
     size_t work = 0;
     HIP_TRY(bpr_inverse_workspace((int32_t)R->max_rows, (int32_t)M, &work));
     TRY(H->work.alloc(work));
     HIP_TRY(hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking));
-    TRY(resample(H.get(), 0, nullptr));
+    TRY(resample(H.get(), 0, kUniform, nullptr, nullptr));
     *out = H.release();
     return FMHIP_OK;
 }
@@ -336,11 +355,11 @@ int fmhip_bpr_info(fmhip_bpr_t h, int64_t *n_pairs, int64_t *dimension, int64_t 
 int fmhip_bpr_resample(fmhip_bpr_t h, int64_t t, fmhip_bpr_sample_stats *stats) {
     if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
     TRY(refuse_under_warp(h, "fmhip_bpr_resample"));
-    unsigned long long total[3];
-    TRY(resample(h, t, total));
+    int64_t total[3];
+    TRY(resample(h, t, kUniform, nullptr, total));
     if (stats) {
-        stats->attempts = (int64_t)total[0];
-        stats->forced = (int64_t)total[1];
+        stats->attempts = total[0];
+        stats->forced = total[1];
     }
     return FMHIP_OK;
 }
@@ -364,37 +383,19 @@ int fmhip_bpr_resample_adaptive(fmhip_model_t m, fmhip_bpr_t h, int64_t t, fmhip
     WriteLock lock(m);
     TRY(check_bpr(m, h));
     TRY(refuse_under_warp(h, "fmhip_bpr_resample_adaptive"));
-    unsigned long long total[3];
-    TRY(resample(h, t, total, m));
+    int64_t total[3];
+    TRY(resample(h, t, kBestOfC, m, total));
     if (stats) {
-        stats->attempts = (int64_t)total[0];
-        stats->forced = (int64_t)total[1];
-        stats->replaced = (int64_t)total[2];
+        stats->attempts = total[0];
+        stats->forced = total[1];
+        stats->replaced = total[2];
     }
     return FMHIP_OK;
 }
 
 int fmhip_bpr_debug_adaptive(fmhip_model_t m, struct fmhip_bpr *h, int64_t t, int64_t p0, int64_t p1, int32_t *rows, float *scores) {
     WriteLock lock(m);
-    TRY(check_bpr(m, h));
-    TRY(check_epoch_index(t));
-    if (p0 < 0 || p1 > h->n_pairs || p0 >= p1)
-        return fail(FMHIP_ERR_INVALID, "pairs [%lld, %lld): a non-empty range inside [0, %lld)", (long long)p0, (long long)p1, (long long)h->n_pairs);
-    if (!rows || !scores) return fail(FMHIP_ERR_INVALID, "an out array is NULL");
-    const size_t n = (size_t)(p1 - p0) * (size_t)h->n_cand;
-    TRY(h->rec_rows.ensure(n));
-    TRY(h->rec_scores.ensure(n));
-    BprAdaptiveArgs aa{};
-    TRY(adaptive_args(m, h, t, &aa));
-    aa.p0 = (int32_t)p0;
-    aa.p1 = (int32_t)p1;
-    aa.rec_rows = h->rec_rows.p;
-    aa.rec_scores = h->rec_scores.p;
-    HIP_TRY(launch_bpr_sample_adaptive(m->Kp, aa, h->stream));
-    HIP_TRY(hipMemcpyAsync(rows, h->rec_rows.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(scores, h->rec_scores.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return FMHIP_OK;
+    return record_scores(m, h, t, p0, p1, kBestOfC, rows, scores, nullptr);
 }
 
 // ---- WARP (include/fmhip_warp.h) ----------------------------------------------------------------------------------------------------
@@ -420,12 +421,12 @@ int fmhip_warp_resample(fmhip_model_t m, fmhip_bpr_t h, int64_t t, fmhip_warp_st
     WriteLock lock(m);
     TRY(check_bpr(m, h));
     if (!h->warp) return fail(FMHIP_ERR_INVALID, "WARP is off for this trainer: turn it on with fmhip_warp_set");
-    unsigned long long total[3];
-    TRY(resample(h, t, total, m, true));
+    int64_t total[3];
+    TRY(resample(h, t, kWarp, m, total));
     if (stats) {
         stats->pairs = h->n_pairs;
-        stats->violated = (int64_t)total[0];
-        stats->trials = (int64_t)total[1];
+        stats->violated = total[0];
+        stats->trials = total[1];
     }
     return FMHIP_OK;
 }
@@ -452,29 +453,7 @@ int fmhip_warp_trials(fmhip_bpr_t h, int32_t *out) {
 
 int fmhip_warp_debug(fmhip_model_t m, struct fmhip_bpr *h, int64_t t, int64_t p0, int64_t p1, int32_t *rows, float *scores, float *pos_scores) {
     WriteLock lock(m);
-    TRY(check_bpr(m, h));
-    TRY(check_epoch_index(t));
-    if (p0 < 0 || p1 > h->n_pairs || p0 >= p1)
-        return fail(FMHIP_ERR_INVALID, "pairs [%lld, %lld): a non-empty range inside [0, %lld)", (long long)p0, (long long)p1, (long long)h->n_pairs);
-    if (!rows || !scores || !pos_scores) return fail(FMHIP_ERR_INVALID, "an out array is NULL");
-    const size_t np = (size_t)(p1 - p0), n = np * (size_t)h->n_cand;
-    TRY(h->rec_rows.ensure(n));
-    TRY(h->rec_scores.ensure(n));
-    TRY(h->rec_pos.ensure(np));
-    BprWarpArgs wa{};
-    TRY(adaptive_args(m, h, t, &wa.a));
-    wa.a.p0 = (int32_t)p0;
-    wa.a.p1 = (int32_t)p1;
-    wa.a.rec_rows = h->rec_rows.p;
-    wa.a.rec_scores = h->rec_scores.p;
-    wa.rec_pos = h->rec_pos.p;
-    wa.margin = (float)h->warp_margin;
-    HIP_TRY(launch_bpr_sample_warp(m->Kp, wa, h->stream));
-    HIP_TRY(hipMemcpyAsync(rows, h->rec_rows.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(scores, h->rec_scores.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(pos_scores, h->rec_pos.p, np * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return FMHIP_OK;
+    return record_scores(m, h, t, p0, p1, kWarp, rows, scores, pos_scores);
 }
 
 int fmhip_bpr_negatives(fmhip_bpr_t h, int32_t *out) {
@@ -513,8 +492,7 @@ int fmhip_bpr_epoch(fmhip_model_t m, fmhip_bpr_t h, int64_t t, double eta, doubl
     if (order)
         for (int64_t j = 0; j < nb; ++j)
             if (order[j] < 0 || order[j] >= nb) return fail(FMHIP_ERR_INVALID, "batch %lld out of range [0, %lld)", (long long)order[j], (long long)nb);
-    if (h->warp) TRY(resample(h, t, nullptr, m, true));
-    else TRY(resample(h, t, nullptr, h->n_cand > 1 ? m : nullptr));
+    TRY(resample(h, t, epoch_sampler(h), m, nullptr));
     PairHinge hinge_store{};
     const PairHinge *hinge = nullptr;
     TRY(step_hinge(h, &hinge_store, &hinge));

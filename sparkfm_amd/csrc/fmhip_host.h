@@ -221,7 +221,7 @@ void bpr_positive_lists(int64_t n_ctx, int64_t n_inter, const int32_t *inter_ctx
 // the two agree bit for bit).  list: the context's positives (ascending, distinct, len < M).  attempts / forced: nullable
 int32_t bpr_negative(uint64_t seed, uint32_t p, uint32_t t, int32_t M, const int32_t *list, int32_t len, int *attempts, int *forced = nullptr);
 // Candidate c = 0 .. 63 of the adaptive sampler (include/fmhip_bpr_adaptive.h): the same rule with the counter's group word
-// offset by c << 4 — the host twin of k_bpr_sample_adaptive's draws.  bpr_negative is its c = 0 case.
+// offset by c << 4 — the host twin of k_bpr_sample_walk's draws.  bpr_negative is its c = 0 case.
 int32_t bpr_candidate(uint64_t seed, uint32_t p, uint32_t c, uint32_t t, int32_t M, const int32_t *list, int32_t len, int *attempts,
                       int *forced = nullptr);
 
@@ -229,7 +229,7 @@ int32_t bpr_candidate(uint64_t seed, uint32_t p, uint32_t c, uint32_t t, int32_t
 // H(r) = sum_{j = 1 .. r} 1 / j in fp64, j ascending — one pass over j = 1 .. M - 1 for all n.  out: C + 1 floats; M >= 2, C >= 1.
 void warp_weight_table(int64_t M, int C, float *out);
 // N of a pair: 1 + the lowest c in [0, C) with scores[c] > s_pos - margin (one fp32 subtraction; a strict test, so a tie and a NaN
-// on either side are no violation), 0 when there is none — the host twin of k_bpr_sample_warp's choice.
+// on either side are no violation), 0 when there is none — the host twin of the walk's FirstViolator rule.
 int warp_first_violator(const float *scores, int C, float s_pos, float margin);
 
 // ---- the MCMC learner's draws (fmhip_mcmc_epoch, include/fmhip_mcmc.h; the generator: mcmc_rng.h) ------------------------------

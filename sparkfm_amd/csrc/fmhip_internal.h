@@ -370,26 +370,26 @@ struct fmhip_bpr {
     uint64_t seed = 0;
     DevBuf<int32_t> ictx, prow, counts;        // counts: [n_batches][4]
     DevBuf<int64_t> pptr;
-    DevBuf<unsigned long long> spart, stotal;  // the sampler's per-block partials and their sums
+    // the per-block partials and their sums [3] of the sampler that runs: a resample grows `part` to its sampler's need and ends in a
+    // synchronise, so no two draws hold it at once
+    DevBuf<unsigned long long> part, total;
     DevBuf<char> work;                         // the inverse build's workspace, for the largest batch
     hipStream_t stream = nullptr;
-    // the adaptive sampler (include/fmhip_bpr_adaptive.h): candidates per pair, its {attempts, forced, replaced} partials and sums,
-    // the debug call's record buffers, and the event that puts the sampler (own stream) behind the blocks' forwards (the model's)
+    // the adaptive sampler (include/fmhip_bpr_adaptive.h): candidates per pair, the debug call's record buffers, and the event that
+    // puts the sampler (own stream) behind the blocks' forwards (the model's)
     int32_t n_cand = 1;
-    DevBuf<unsigned long long> apart, atotal;
     DevBuf<int32_t> rec_rows;
     DevBuf<float> rec_scores;
     hipEvent_t fwd_done = nullptr;
     // WARP (include/fmhip_warp.h): the switch and the margin, whether a WARP draw stands since the switch was last set, the pairs'
     // weights (a PairArgs::c over all 2 n_pairs rows) and trial counts, the weight table W[0 .. wtab_cand] on both sides, the
-    // sampler's {violated, trials} partials and sums, the debug call's s+ record
+    // debug call's s+ record
     bool warp = false, warp_drawn = false;
     double warp_margin = 1.0;
     DevBuf<float> wc, wtab, rec_pos;
     DevBuf<int32_t> wtrials;
     std::vector<float> h_wtab;
     int32_t wtab_cand = 0;
-    DevBuf<unsigned long long> wpart, wtotal;
     ~fmhip_bpr() {
         if (fwd_done) (void)hipEventDestroy(fwd_done);
         if (R) (void)fmhip_relational_destroy(R);

@@ -7,7 +7,10 @@ left every bit where it was — tools/grad_hash.py does the same for the single-
 600 rows in 3 batches of 200 (the last workgroup of every finish has empty slots), 300 features.  Per case and k one line: the
 flat routes hash batch 2's gradient (gv, gw) and print g0 and sse, the relational and BPR routes — which have no gradient call —
 hash the parameters after one step of batch 2 and print that step's sum e and sse; then every route hashes the parameters after
-two epochs.  The adaptive BPR case adds the statistics of one more draw under the trained model."""
+two epochs.  The adaptive BPR case adds the statistics of one more draw under the trained model.  The lines of the scored samplers
+(best of C at C = 9, WARP at C = 4 and 9, margin 0.1) hash the parameters after two epochs and, under that model at t = 2, what the
+record call returns for all pairs (rows, scores, WARP: the positives' scores) and what a draw leaves (negatives, WARP: trials and
+pair weights), with the draw's statistics."""
 import hashlib
 import os
 import sys
@@ -70,6 +73,21 @@ def stepped_case(name, k, step, learn, extra=lambda fm: ""):
     fm.close()
 
 
+def sampler_case(name, k, cand, kw):
+    """Two epochs, then under the trained model at t = 2: the record call's arrays for all pairs, and what a draw leaves."""
+    bpr = HipBPR.run(users.block, items.block, positives, n_neg=1, batch_pairs=BATCH // 2, seed=3, eta=ETA, n_candidates=cand, **REGS, **kw)
+    fm = model(k)
+    for _ in range(2):
+        bpr.learn(fm)
+    record = bpr.warp_draws(fm, 2) if bpr.warp else bpr.candidate_draws(fm, 2)
+    st = bpr.resample(2, fm)
+    left = [bpr.negatives()] + ([bpr.trials(), bpr.pair_weights()] if bpr.warp else [])
+    print("%-22s k=%-3d after 2 epochs %s | record at t=2 %s | draw at t=2 %s %s" % (
+        name, k, params(fm), sha(*record), sha(*left), " ".join("%s=%d" % kv for kv in sorted(st.items()))))
+    bpr.close()
+    fm.close()
+
+
 rng = np.random.default_rng(5)
 rp, col, val = rows_of(rng, ROWS, 0, N1, 1, 12)
 y = rng.normal(0, 1, ROWS)
@@ -103,3 +121,7 @@ for k in KS:
         stepped_case(name, k, lambda fm: bpr.step(fm, 2), bpr.learn,
                      (lambda fm: " | draw at t=2 " + " ".join("%s=%d" % kv for kv in sorted(bpr.resample(2, fm).items()))) if cand > 1 else (lambda fm: ""))
         bpr.close()
+    # the scored samplers' walk: C = 9 is a second pass of the 8-lane group at k = 8, ending inside a chunk
+    for name, cand, kw in (("BPR best-of-C C=9", 9, {}), ("BPR WARP C=4", 4, dict(sampler="warp", margin=0.1)),
+                           ("BPR WARP C=9", 9, dict(sampler="warp", margin=0.1))):
+        sampler_case(name, k, cand, kw)
