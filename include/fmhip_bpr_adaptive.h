@@ -15,7 +15,7 @@
  *
  * SCORING.  The score of candidate row i for context row u is
  *     s = yq_i[i] + <q_u[u], q_i[i]>                                     (fp32)
- * with q and yq what one forward over each block leaves under the model AS IT STANDS WHEN THE RESAMPLE IS CALLED (the relational
+ * with q and yq what one forward over each block leaves under the model AS IT STANDS WHEN THE DRAW IS MADE (the relational
  * step's: yhat(u, i) = yq_u + yq_i - w0 + <q_u, q_i>).  yq_u[u] - w0 is the same for all candidates of a pair and is left out.  The
  * dot product is summed in an order the model's padded factor count alone fixes — never the launch shape — so the same model bits,
  * seed and t give the same rows run to run and device to device.
@@ -24,9 +24,10 @@
  * is strictly greater than the incumbent's.  Ties keep the earlier candidate; a NaN score never replaces the incumbent (and a NaN
  * incumbent is never replaced).
  *
- * STALENESS.  The resample stays once per epoch (one synchronisation per epoch, for the inverse map): the negatives are the hardest
- * against the model at the epoch's START.  With one batch per epoch (batch_pairs = 0) that is exact dynamic negative sampling; with
- * several batches the later ones train on choices made before the earlier batches' updates.  There is no per-batch resample.
+ * WHEN.  fmhip_bpr_resample_adaptive draws every pair at once: the negatives are the hardest against the model at the moment of the
+ * call, and a handle in its default redraw mode makes that call once per epoch — with one batch per epoch (batch_pairs = 0) exact
+ * dynamic negative sampling, with several the later batches train on choices made before the earlier batches' updates.  The
+ * per-batch redraw (fmhip_redraw.h) draws each batch's pairs under the model as it stands at that batch's step.
  *
  * WHICH CALLS ARE ADAPTIVE.  fmhip_bpr_resample_adaptive always; fmhip_bpr_epoch when the handle's n_cand > 1 (with n_cand = 1 it
  * runs exactly what it ran before this header existed).  fmhip_bpr_resample, which takes no model, and the draw inside

@@ -16,7 +16,7 @@
  *     s = yq_i[i] + <q_u[u], q_i[i]>                                     (fp32)
  * and the positive's score s+ is the same expression at the pair's positive row, formed by the same code in the same order — a
  * lane's 4-term fused chain, then an xor tree over the Kp / 4 lanes of a row — with floats >= k of the context's slice cleared.
- * q and yq are what one forward over each block leaves under the model AS IT STANDS WHEN THE RESAMPLE IS CALLED.
+ * q and yq are what one forward over each block leaves under the model AS IT STANDS WHEN THE DRAW IS MADE.
  *
  * CHOOSING.  thr = s+ - (float)m, one fp32 subtraction.  Candidate c VIOLATES iff s_c > thr: a strict test, so a tie is no violation
  * and a NaN on either side never violates.  N = 1 + the lowest violating c, or 0 when none of the C violates.  The pair's negative
@@ -29,8 +29,9 @@
  *
  * THE STEP minimises (1 / |B|) sum_p c_p max(0, m - (yhat+_p - yhat-_p)) over a batch, |B| its ROW count as for every pair rule:
  *     d = yhat_2p - yhat_2p+1,   g = (d < (float)m) ? -1 : 0,   g <- c_p g,   e_2p = g,   e_2p+1 = -g
- * The hinge is judged AT THE STEP on the current model: a pair an earlier batch already fixed gives no gradient, so the staleness
- * between the once-per-epoch resample and the later batches is harmless by construction.  A NaN d gives g = 0 and is counted in the
+ * The hinge is judged AT THE STEP on the current model: a pair an earlier batch already fixed gives no gradient, whenever its draw
+ * was made.  The weights c_p and the kept rows are the draw's: once per epoch by default, or under the model of the batch's own
+ * step with the per-batch redraw (fmhip_redraw.h).  A NaN d gives g = 0 and is counted in the
  * statistics' non-finite slot.  The statistics are the pair rule's: sum_e exactly 0, sse = 2 sum g^2.  SGD and AdaGrad as the
  * model is set (fmhip_model_set_optimizer); the model's loss (fmhip_model_set_loss) is neither read nor changed while WARP is on.
  *

@@ -45,6 +45,7 @@
 #include "fmhip_bpr.h"
 #include "fmhip_bpr_adaptive.h"
 #include "fmhip_warp.h"
+#include "fmhip_redraw.h"
 #include "fmhip_ftrl.h"
 
 namespace sparkfm {
@@ -797,6 +798,7 @@ class HipMCMC : public FMLearn {
 class HipBPR : public FMLearn {
   public:
     enum Sampler { kAuto = 0, kWarp = 1 };
+    enum Redraw { kEpoch = FMHIP_REDRAW_EPOCH, kBatch = FMHIP_REDRAW_BATCH };      // include/fmhip_redraw.h
     double eta, reg0, regw, regv;
     int loss, optimizer;
     double adagrad_eps, adagrad_init;
@@ -804,14 +806,16 @@ class HipBPR : public FMLearn {
     fmhip_bpr_sample_stats sample_stats{};
     fmhip_bpr_adaptive_stats adaptive_stats{};
     fmhip_warp_stats warp_stats{};
+    fmhip_redraw_stats redraw_stats{};      // kBatch: the sampler's counters summed over the last epoch's batches; step(fm, batch, t): that draw's
     HipBPR(DataSet &contexts, DataSet &candidates, const std::vector<std::vector<int32_t>> &positives, int32_t n_neg = 1, int64_t batch_pairs = 0,
            uint64_t seed = 0, double eta_ = 0.05, double reg0_ = 0.0, double regw_ = 0.0, double regv_ = 0.0, int loss_ = FMHIP_LOSS_LOGISTIC,
            int optimizer_ = FMHIP_OPT_SGD, double adagrad_eps_ = 1e-10, double adagrad_init_ = 0.1, int32_t n_candidates = 1,
-           int sampler = kAuto, double margin = 1.0)
+           int sampler = kAuto, double margin = 1.0, int redraw = kEpoch)
         : eta(eta_), reg0(reg0_), regw(regw_), regv(regv_), loss(loss_), optimizer(optimizer_), adagrad_eps(adagrad_eps_), adagrad_init(adagrad_init_),
           contexts_(contexts), candidates_(candidates), n_neg_(n_neg), batch_pairs_(batch_pairs), seed_(seed), n_candidates_(n_candidates),
-          sampler_(sampler), margin_(margin) {
+          sampler_(sampler), margin_(margin), redraw_(redraw) {
         if (sampler != kAuto && sampler != kWarp) throw Error(FMHIP_ERR_INVALID, "sampler must be HipBPR::kAuto or HipBPR::kWarp");
+        if (redraw != kEpoch && redraw != kBatch) throw Error(FMHIP_ERR_INVALID, "redraw must be HipBPR::kEpoch or HipBPR::kBatch");
         if (!(margin >= 0.0) || !(margin <= 3.4028234663852886e38)) throw Error(FMHIP_ERR_INVALID, "margin must be a finite number >= 0");
         if (sampler == kWarp && loss_ != FMHIP_LOSS_LOGISTIC) throw Error(FMHIP_ERR_INVALID, "sampler = kWarp trains its own hinge: leave loss at its default");
         if (n_candidates < 1 || n_candidates > FMHIP_BPR_MAX_CANDIDATES) throw Error(FMHIP_ERR_INVALID, "n_candidates must be in [1, 64]");
@@ -835,6 +839,7 @@ class HipBPR : public FMLearn {
     int32_t n_candidates() const { return n_candidates_; }
     bool warp() const { return sampler_ == kWarp; }
     double margin() const { return margin_; }
+    int redraw() const { return redraw_; }
     // the handle borrows the blocks' device copies: made again when either was unpersisted since (FM's fit loop unpersists its dataset)
     fmhip_bpr_t handle() {
         const fmhip_dataset_t c = contexts_.handle(), i = candidates_.handle();
@@ -844,6 +849,7 @@ class HipBPR : public FMLearn {
                                    seed_, &h_));
             if (n_candidates_ > 1) check(fmhip_bpr_set_candidates(h_, n_candidates_));
             if (warp()) check(fmhip_warp_set(h_, 1, margin_));
+            if (redraw_ != kEpoch) check(fmhip_redraw_set(h_, redraw_));
             for_ctx_ = c;
             for_cand_ = i;
         }
@@ -858,9 +864,19 @@ class HipBPR : public FMLearn {
         if (!warp()) check(fmhip_model_set_loss(fm.upload(), loss));      // (WARP's hinge: the model's loss is left as it is)
         check(fmhip_model_set_optimizer(fm.upload(), optimizer, adagrad_eps, adagrad_init));
         check(fmhip_bpr_epoch(fm.upload(), h, epoch_, eta, reg0, regw, regv, nullptr, &last_stats));
+        if (redraw_ == kBatch) check(fmhip_redraw_epoch_stats(h, &redraw_stats));
         ++epoch_;
         fm.download();
         return fm;
+    }
+    // one mini-batch step whose pairs are first redrawn at epoch t under the model as it stands (fmhip_redraw_step; either mode)
+    const fmhip_stats &step(FMModel &fm, int64_t batch, int64_t t) {
+        const fmhip_bpr_t h = handle();
+        if (!warp()) check(fmhip_model_set_loss(fm.upload(), loss));
+        check(fmhip_model_set_optimizer(fm.upload(), optimizer, adagrad_eps, adagrad_init));
+        check(fmhip_redraw_step(fm.upload(), h, t, batch, eta, reg0, regw, regv, &last_stats, &redraw_stats));
+        fm.download();
+        return last_stats;
     }
     FMModel &learn(FMModel &fm, DataSet &) override { return learn(fm); }       // (the fit loop's dataset is not read)
     using FMLearn::learn;
@@ -923,6 +939,7 @@ class HipBPR : public FMLearn {
     int32_t n_candidates_;
     int sampler_;
     double margin_;
+    int redraw_;
     int64_t epoch_ = 0;
     fmhip_bpr_t h_ = nullptr;
     fmhip_dataset_t for_ctx_ = nullptr, for_cand_ = nullptr;

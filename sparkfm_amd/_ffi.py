@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_mcmc_relational.h, include/fmhip_bpr.h, include/fmhip_bpr_adaptive.h, include/fmhip_warp.h, include/fmhip_ftrl.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_mcmc_relational.h, include/fmhip_bpr.h, include/fmhip_bpr_adaptive.h, include/fmhip_warp.h, include/fmhip_ftrl.h, include/fmhip_redraw.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -78,6 +78,10 @@ SYMBOLS_BPR_ADAPTIVE = ("fmhip_bpr_set_candidates", "fmhip_bpr_get_candidates", 
 BPR_MAX_CANDIDATES = 64    # FMHIP_BPR_MAX_CANDIDATES
 # ... and include/fmhip_warp.h — WARP: the first candidate that violates the margin, a hinge weighted by the estimated rank
 SYMBOLS_WARP = ("fmhip_warp_set", "fmhip_warp_get", "fmhip_warp_resample", "fmhip_warp_weights", "fmhip_warp_trials")
+# ... and include/fmhip_redraw.h — when the BPR trainer redraws: once per epoch, or before every batch under the current model
+SYMBOLS_REDRAW = ("fmhip_redraw_set", "fmhip_redraw_get", "fmhip_redraw_step", "fmhip_redraw_epoch_stats")
+REDRAW_EPOCH, REDRAW_BATCH = 0, 1      # FMHIP_REDRAW_EPOCH, FMHIP_REDRAW_BATCH
+REDRAWS = {"epoch": REDRAW_EPOCH, "batch": REDRAW_BATCH}
 # ... and include/fmhip_ftrl.h — FTRL-Proximal with L1: the third update rule, its state, the model's exact sparsity counts
 SYMBOLS_FTRL = ("fmhip_model_set_ftrl", "fmhip_model_get_ftrl_state", "fmhip_model_set_ftrl_state", "fmhip_model_nonzeros")
 OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
@@ -368,6 +372,15 @@ class WarpStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RedrawStats(C.Structure):
+    """fmhip_redraw_stats (include/fmhip_redraw.h)."""
+    _fields_ = [("pairs", C.c_int64), ("attempts", C.c_int64), ("forced", C.c_int64), ("replaced", C.c_int64), ("violated", C.c_int64),
+                ("trials", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DatasetOpts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("hot_block", C.c_int32), ("batch_rows", C.c_int64), ("row_block_rows", C.c_int64)]
 
@@ -556,13 +569,17 @@ def load():
     L.fmhip_warp_weights.argtypes = [vp, vp]
     L.fmhip_warp_trials.argtypes = [vp, vp]
     L.fmhip_warp_debug.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
+    L.fmhip_redraw_set.argtypes = [vp, C.c_int]
+    L.fmhip_redraw_get.argtypes = [vp, P(C.c_int)]
+    L.fmhip_redraw_step.argtypes = [vp, vp, i64, i64, dbl, dbl, dbl, dbl, P(Stats), P(RedrawStats)]
+    L.fmhip_redraw_epoch_stats.argtypes = [vp, P(RedrawStats)]
     L.fmhip_model_set_ftrl.argtypes = [vp, dbl, dbl, dbl, dbl]
     L.fmhip_model_get_ftrl_state.argtypes = [vp, P(dbl), vp, vp, P(dbl), vp, vp]
     L.fmhip_model_set_ftrl_state.argtypes = [vp, dbl, vp, vp, dbl, vp, vp]
     L.fmhip_model_nonzeros.argtypes = [vp, P(i64), P(i64), P(i64)]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP + SYMBOLS_FTRL):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

@@ -21,7 +21,8 @@ from .model import FMModel
 
 
 class HipBPR(FMLearn):
-    """One ``learn`` = one epoch: the negatives redrawn at t = the epochs done, then every batch.
+    """One ``learn`` = one epoch at t = the epochs done: the negatives redrawn, then every batch (redraw="epoch"), or every batch's
+    negatives redrawn right before its step under the model as it then stands (redraw="batch", include/fmhip_redraw.h).
 
     `contexts`, `candidates`: single-batch training ``DataSet``s (batch_rows=0, not scoring-only, unweighted; labels unused) with
     disjoint feature ids.  `positives`: one integer array of candidate rows per context (sorted and de-duplicated here).  There are
@@ -30,17 +31,23 @@ class HipBPR(FMLearn):
     `batch_pairs`: pairs per mini-batch (0: one batch).  `seed` also keys the sampler.  `loss`: "logistic" (BPR) or "squared" (the
     squared pair loss); `optimizer` and the AdaGrad settings as ``HipSGD``.  The model's pairing flag is neither read nor set.
     `n_candidates` (1 .. 64): above 1 every epoch draws that many candidates per pair and trains on the one the model scores
-    highest at the epoch's start (include/fmhip_bpr_adaptive.h) — once per epoch, so with several batches the later ones see
-    choices made before the earlier batches' updates; 1 is the uniform sampler, bit for bit what it was.
+    highest (include/fmhip_bpr_adaptive.h) — at the epoch's start under redraw="epoch", at the batch's own step under
+    redraw="batch"; 1 is the uniform sampler, bit for bit what it was.
     `sampler`: "auto" (that: uniform at n_candidates = 1, the best of n_candidates above) or "warp" (include/fmhip_warp.h): every
     epoch keeps per pair the FIRST of its n_candidates candidates whose score is above the positive's minus `margin` (>= 0), and
     the step trains a hinge at that margin weighted by the rank estimated from how many candidates that took; pairs without a
-    violator get weight 0.  With "warp" `loss` stays at its default — the hinge takes its place and the model's loss is not set."""
+    violator get weight 0.  With "warp" `loss` stays at its default — the hinge takes its place and the model's loss is not set.
+    `redraw`: "epoch" (one draw of every pair per ``learn``, one synchronisation for it) or "batch" (include/fmhip_redraw.h): batch
+    b's pairs are drawn between batch b's forwards and the rest of its step, the candidate rows being those of the per-epoch draw
+    and the scores — hence the choice, and WARP's weights — the current model's; an epoch still synchronises once, at its end.  A
+    uniform sampler trains the same bits in both modes."""
 
     SAMPLERS = ("auto", "warp")
+    REDRAWS = ("epoch", "batch")
 
     def __init__(self, contexts, candidates, positives, n_neg=1, batch_pairs=0, seed=0, shuffle=True, eta=0.05, reg0=0.0, regw=0.0,
-                 regv=0.0, loss="logistic", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1, n_candidates=1, sampler="auto", margin=1.0):
+                 regv=0.0, loss="logistic", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1, n_candidates=1, sampler="auto", margin=1.0,
+                 redraw="epoch"):
         for what, d in (("contexts", contexts), ("candidates", candidates)):
             if not isinstance(d, DataSet):
                 raise TypeError("%s must be a DataSet, not %s" % (what, type(d).__name__))
@@ -65,6 +72,9 @@ class HipBPR(FMLearn):
         if sampler not in self.SAMPLERS:
             raise ValueError("sampler must be one of %s, not %r" % (", ".join(repr(s) for s in self.SAMPLERS), sampler))
         self._sampler = sampler
+        if not isinstance(redraw, str) or redraw not in self.REDRAWS:
+            raise ValueError("redraw must be one of %s, not %r" % (", ".join(repr(s) for s in self.REDRAWS), redraw))
+        self._redraw = redraw
         if isinstance(margin, bool) or not isinstance(margin, (int, float, np.integer, np.floating)) \
                 or not 0 <= float(margin) <= float(np.finfo(np.float32).max):      # (the device's margin is fp32; a NaN fails both)
             raise ValueError("margin must be a finite number >= 0, not %r" % (margin,))
@@ -137,6 +147,8 @@ class HipBPR(FMLearn):
                 _ffi.check(_ffi.load().fmhip_bpr_set_candidates(h, self._n_candidates))
             if self.warp:
                 _ffi.check(_ffi.load().fmhip_warp_set(h, 1, self._margin))
+            if self._redraw != "epoch":
+                _ffi.check(_ffi.load().fmhip_redraw_set(h, _ffi.REDRAWS[self._redraw]))
         return self._h
 
     @property
@@ -147,6 +159,11 @@ class HipBPR(FMLearn):
     @property
     def sampler(self):
         return self._sampler
+
+    @property
+    def redraw(self):
+        """"epoch" or "batch": when ``learn`` redraws the negatives (include/fmhip_redraw.h)."""
+        return self._redraw
 
     @property
     def margin(self):
@@ -287,23 +304,40 @@ class HipBPR(FMLearn):
         _ffi.check(L.fmhip_model_set_optimizer(fm.handle, self._opt_code, self.adagrad_eps, self.adagrad_init))
 
     def learn(self, fm, dataset=None):
-        """One epoch (fmhip_bpr_epoch): resample at t = the epochs done (adaptively under `fm` when n_candidates > 1), then every
-        batch in order.  `dataset` is not read."""
+        """One epoch (fmhip_bpr_epoch) at t = the epochs done.  redraw="epoch": resample (adaptively under `fm` when n_candidates > 1),
+        then every batch in order.  redraw="batch": per batch in order its draw under `fm` as it stands, then its step;
+        ``sample_stats`` then holds the sampler's counters summed over the batches (fmhip_redraw_epoch_stats).  `dataset` is not read."""
         st = _ffi.Stats()
         self._set_rule(fm)
         _ffi.check(_ffi.load().fmhip_bpr_epoch(fm.handle, self.handle, self._epoch, self.eta, self.reg0, self.regw, self.regv, None,
                                                C.byref(st)))
+        if self._redraw == "batch":
+            dr = _ffi.RedrawStats()
+            _ffi.check(_ffi.load().fmhip_redraw_epoch_stats(self.handle, C.byref(dr)))
+            self.sample_stats = dr.as_dict()
         fm._device_updated()
         self._epoch += 1
         self.last_stats = st.as_dict()
         return fm
 
-    def step(self, fm, batch, want_stats=True):
-        """A single mini-batch step on the current draw (fmhip_bpr_step)."""
+    def step(self, fm, batch, t=None, want_stats=True):
+        """A single mini-batch step.  Without `t`: on the current draw (fmhip_bpr_step).  With `t`: the batch's pairs are first
+        redrawn at epoch `t` under `fm` as it stands, by the trainer's sampler, and the batch's inverse map rebuilt
+        (fmhip_redraw_step; either redraw mode); with want_stats ``sample_stats`` holds that draw's counters."""
+        if isinstance(t, bool):
+            raise TypeError("t must be an epoch index, not %r (want_stats is a keyword)" % (t,))
         st = _ffi.Stats()
         self._set_rule(fm)
-        _ffi.check(_ffi.load().fmhip_bpr_step(fm.handle, self.handle, operator.index(batch), self.eta, self.reg0, self.regw, self.regv,
-                                              C.byref(st) if want_stats else None))
+        if t is None:
+            _ffi.check(_ffi.load().fmhip_bpr_step(fm.handle, self.handle, operator.index(batch), self.eta, self.reg0, self.regw, self.regv,
+                                                  C.byref(st) if want_stats else None))
+        else:
+            dr = _ffi.RedrawStats()
+            _ffi.check(_ffi.load().fmhip_redraw_step(fm.handle, self.handle, operator.index(t), operator.index(batch), self.eta, self.reg0,
+                                                     self.regw, self.regv, C.byref(st) if want_stats else None,
+                                                     C.byref(dr) if want_stats else None))
+            if want_stats:
+                self.sample_stats = dr.as_dict()
         fm._device_updated()
         if want_stats:
             self.last_stats = st.as_dict()

@@ -6,18 +6,20 @@
 
 namespace fmhip {
 
-// One thread per pair p: the context of interaction p / n_neg, a row of [0, M) outside the context's positives
-// (rng::negative_row, mcmc_rng.h) into map[2p + 1] — the candidates relation's mapping; map[2p] (the positive) is not touched.
+// One thread per pair p of [p0, p1): the context of interaction p / n_neg, a row of [0, M) outside the context's positives
+// (rng::negative_row, mcmc_rng.h) into map[2p + 1] — the candidates relation's mapping; map[2p] (the positive) is not touched, and
+// nothing of a pair outside the range.  A whole-set draw passes [0, n_pairs); the grid and the partials are sized by the range.
 struct BprSampleArgs {
     uint64_t seed;
     uint32_t t;
     int32_t n_pairs, n_neg, M;
+    int32_t p0, p1;            // the pairs drawn (a scored sampler's record mode: the pairs written)
     const int32_t *ictx;       // [n_inter] the interactions' contexts, in training order
     const int64_t *pptr;       // [n_ctx + 1]
     const int32_t *prow;       // the contexts' positives, ascending and distinct inside a list
     int32_t *map;              // [2 * n_pairs]
-    unsigned long long *part;  // [bpr_sample_blocks][2] per-block {attempts, forced pairs}
-    unsigned long long *total; // [2] their sums (a second, one-block launch)
+    unsigned long long *part;  // [bpr_sample_blocks(p1 - p0)][2] per-block {attempts, forced pairs}
+    unsigned long long *total; // [2] their sums (a second, one-block launch): the caller's slot, one per draw in flight
 };
 int bpr_sample_blocks(int64_t n_pairs);
 hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s);
@@ -28,8 +30,8 @@ hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s);
 // slice, multiplies and sums over the group by an xor-shuffle tree — an order Kp alone fixes — and hands row and score to the
 // sampler's choice rule, whose lane 0 writes the kept row into map[2p + 1].  Qu / Qi / yqi are what the kFwdQ forwards of the two
 // blocks left (rel.Q, rel.yq); floats k .. Kp-1 of the context's slice (the packed slot and the padding) are cleared in registers,
-// so the score does not rest on what the tables hold there.  Record mode (rec_rows set): pairs [p0, p1) only, every candidate's row
-// and score out, nothing else written, no early stop.
+// so the score does not rest on what the tables hold there.  Both modes walk the pairs [s.p0, s.p1) and touch nothing of a pair
+// outside them.  Record mode (rec_rows set): every candidate's row and score out, nothing else written, no early stop.
 //
 // Best of C (the rule: include/fmhip_bpr_adaptive.h) adds nothing to the walk's arguments: it keeps the first strict maximum.
 struct BprAdaptiveArgs {
@@ -38,9 +40,8 @@ struct BprAdaptiveArgs {
     int32_t k;                 // the model's factors: floats [k, Kp) of a q row are no factors
     const float *Qu, *Qi;      // [n_ctx][Kp], [M][Kp]
     const float *yqi;          // [M]
-    int32_t p0, p1;            // record mode: the pairs written
-    int32_t *rec_rows;         // [(p1 - p0) * n_cand] or nullptr
-    float *rec_scores;         // [(p1 - p0) * n_cand]
+    int32_t *rec_rows;         // [(s.p1 - s.p0) * n_cand] or nullptr
+    float *rec_scores;         // [(s.p1 - s.p0) * n_cand]
 };
 constexpr int kBprMaxCand = 64;
 int bpr_adaptive_blocks(int Kp, int64_t n_pairs);
@@ -56,7 +57,7 @@ struct BprWarpArgs {
     const float *W;            // [n_cand + 1] W[0] = 0, W[n] the weight of a pair whose first violator is candidate n - 1
     float *c;                  // [2 * n_pairs] the pairs' weights, a valid PairArgs::c (fm_pairing.h)
     int32_t *trials;           // [n_pairs] N
-    float *rec_pos;            // record mode: [p1 - p0] s+
+    float *rec_pos;            // record mode: [a.s.p1 - a.s.p0] s+
 };
 hipError_t launch_bpr_sample_warp(int Kp, const BprWarpArgs &a, hipStream_t s);
 

@@ -42,7 +42,7 @@ __device__ __forceinline__ void block_sums_u64(u64 (&v)[N], u64 *out) {
 
 __global__ __launch_bounds__(kT) void k_bpr_sample(BprSampleArgs a) {
     u64 att = 0, forced = 0;
-    for (int64_t p = (int64_t)blockIdx.x * kT + threadIdx.x; p < a.n_pairs; p += (int64_t)gridDim.x * kT) {
+    for (int64_t p = a.p0 + (int64_t)blockIdx.x * kT + threadIdx.x; p < a.p1; p += (int64_t)gridDim.x * kT) {
         const int32_t u = a.ictx[p / a.n_neg];
         const int64_t lo = a.pptr[u];
         int at = 0, f = 0;
@@ -138,7 +138,7 @@ struct FirstViolator {
         const float yp[1] = {w.a.yqi[ipos]};
         float spos[1];
         group_scores<G, 1>(qu, qp, yp, spos);
-        if (RECORD && writes) w.rec_pos[p - w.a.p0] = spos[0];
+        if (RECORD && writes) w.rec_pos[p - w.a.s.p0] = spos[0];
         thr = spos[0] - w.margin;
     }
     __device__ __forceinline__ void drawn(u64 (&)[N], int, int) const {}
@@ -160,14 +160,15 @@ struct FirstViolator {
     }
 };
 
-// G lanes per pair, kT / G pairs per block and pass.  The trip count is the block's (`base` is uniform), and a group whose pair lies
-// past the end works on the last pair again and writes nothing: no lane leaves before the block's last shuffle.
+// G lanes per pair, kT / G pairs per block and pass, over the pairs [s.p0, s.p1) in either mode.  The trip count is the block's
+// (`base` is uniform), and a group whose pair lies past the end works on the range's last pair again and writes nothing: no lane
+// leaves before the block's last shuffle.
 template <int G, class Rule, bool RECORD>
 __global__ __launch_bounds__(kT) void k_bpr_sample_walk(typename Rule::Args ra) {
     constexpr int KP = 4 * G, GPB = kT / G;
     const BprAdaptiveArgs &a = Rule::walk_args(ra);
     const int l = threadIdx.x & (G - 1), grp = threadIdx.x / G;
-    const int64_t first = RECORD ? a.p0 : 0, end = RECORD ? a.p1 : a.s.n_pairs;
+    const int64_t first = a.s.p0, end = a.s.p1;
     const int C = a.n_cand;
     u64 v[Rule::N] = {};
     for (int64_t base = first + (int64_t)blockIdx.x * GPB; base < end; base += (int64_t)gridDim.x * GPB) {
@@ -209,7 +210,7 @@ __global__ __launch_bounds__(kT) void k_bpr_sample_walk(typename Rule::Args ra) 
                     const int c = c0 + j0 + jj;
                     if (j0 + jj >= n) break;
                     if (RECORD && live && l == 0) {
-                        const size_t at = (size_t)(p - a.p0) * (size_t)C + (size_t)c;
+                        const size_t at = (size_t)(p - first) * (size_t)C + (size_t)c;
                         a.rec_rows[at] = row[jj];
                         a.rec_scores[at] = s[jj];
                     }
@@ -228,8 +229,7 @@ template <int G, class Rule>
 hipError_t launch_walk(const typename Rule::Args &ra, hipStream_t s) {
     const BprAdaptiveArgs &a = Rule::walk_args(ra);
     const bool record = a.rec_rows != nullptr;
-    const int64_t n = record ? (int64_t)a.p1 - a.p0 : a.s.n_pairs;
-    const int blocks = bpr_adaptive_blocks(4 * G, n);
+    const int blocks = bpr_adaptive_blocks(4 * G, (int64_t)a.s.p1 - a.s.p0);
     if (record) {
         hipLaunchKernelGGL((k_bpr_sample_walk<G, Rule, true>), dim3((unsigned)blocks), dim3(kT), 0, s, ra);
         return hipGetLastError();
@@ -246,7 +246,7 @@ hipError_t launch_scored(int Kp, const typename Rule::Args &ra, hipStream_t s) {
     const BprAdaptiveArgs &a = Rule::walk_args(ra);
     const bool record = a.rec_rows != nullptr;
     if (a.n_cand < 1 || a.n_cand > kBprMaxCand || a.k < 0 || a.k > Kp || !Rule::valid(ra, record)) return hipErrorInvalidValue;
-    if (record && (!a.rec_scores || a.p0 < 0 || a.p1 > a.s.n_pairs || a.p0 >= a.p1)) return hipErrorInvalidValue;
+    if (a.s.p0 < 0 || a.s.p1 > a.s.n_pairs || a.s.p0 >= a.s.p1 || (record && !a.rec_scores)) return hipErrorInvalidValue;
     switch (Kp) {
         case 32: return launch_walk<8, Rule>(ra, s);
         case 64: return launch_walk<16, Rule>(ra, s);
@@ -392,7 +392,8 @@ hipError_t inv_layout(int32_t rows, int32_t block_rows, InvLayout *L) {
 int bpr_sample_blocks(int64_t n_pairs) { return grid_blocks(n_pairs, kT, 4096); }
 
 hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s) {
-    const int blocks = bpr_sample_blocks(a.n_pairs);
+    if (a.p0 < 0 || a.p1 > a.n_pairs || a.p0 >= a.p1) return hipErrorInvalidValue;
+    const int blocks = bpr_sample_blocks((int64_t)a.p1 - a.p0);
     hipLaunchKernelGGL(k_bpr_sample, dim3((unsigned)blocks), dim3(kT), 0, s, a);
     BPR_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_bpr_total<2>, dim3(1), dim3(kT), 0, s, a.part, blocks, a.total);

@@ -51,8 +51,15 @@ struct RelGatherArgs {
     float *part;                   // [n_part][Kp] chunk sums of the long lists
     float *part_e;                 // [n_part]
     int32_t pack_k;
+    // Device-counted form (the BPR trainer's per-batch redraw, include/fmhip_redraw.h): counts = the batch's {n_touched, n_work,
+    // n_long, n_part} where the inverse build left them, read by the kernels in n_work's and n_long's place, each clamped to the
+    // capacity of the slices the host knows (cap_work, cap_long; cap_part partial rows), so that no count indexes outside a slice.
+    // nullptr: n_work and n_long by value, as above
+    const int32_t *counts;
+    int32_t cap_work, cap_long, cap_part;
 };
-// two launches: every work item (a slot each, ascending rows, fp32), then the long lists' chunk sums in chunk order
+// two launches: every work item (a slot each, ascending rows, fp32), then the long lists' chunk sums in chunk order.  With counts
+// set both kernels are always launched, on the grids of cap_work and cap_long: a zero count leaves at the loop's head
 hipError_t launch_rel_gather_sum(int Kp, const RelGatherArgs &a, hipStream_t s);
 
 }  // namespace fmhip

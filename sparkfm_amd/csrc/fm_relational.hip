@@ -119,14 +119,16 @@ __device__ __forceinline__ void rel_sum_rows(const float *table, const float *et
 
 // One slot per work item (fmhip::host::RelationInverse): up to kRelSumCut listed P rows and their e, summed in ascending row order
 // in fp32.  A whole list writes its block row of P_b / e_b; a chunk of a long list writes a partial row.  What an item sums and
-// where it writes is fixed by the data (every address has one writer), and the result is the same bits for any grid.
+// where it writes is fixed by the data (every address has one writer), and the result is the same bits for any grid — so the
+// number of items may as well be read from the device (RelGatherArgs::counts) under a grid sized for the worst case.
 template <int LPN, int J, bool PACKED>
 __global__ __launch_bounds__(kBlock) void k_rel_gather_sum(RelGatherArgs a) {
     constexpr int KP = 4 * LPN * J;
     const SlotLoop<LPN> sl;
     const int l = sl.l;
     const PackPos<LPN, PACKED> k(a.pack_k);
-    for (int w = sl.first; w < a.n_work; w += sl.stride) {
+    const int n_work = a.counts ? min(a.counts[1], a.cap_work) : a.n_work;
+    for (int w = sl.first; w < n_work; w += sl.stride) {
         const int32_t t = a.wt[w], beg = a.wbeg[w], dst = a.wdst[w];
         const int32_t end = min(beg + kRelSumCut, a.tptr[t + 1]);
         float4 acc[J];
@@ -138,6 +140,7 @@ __global__ __launch_bounds__(kBlock) void k_rel_gather_sum(RelGatherArgs a) {
             store_e_row<LPN, J, PACKED>(reinterpret_cast<float4 *>(a.Pb + (size_t)dst * KP) + l, acc, es, l, k);
             if (l == 0) a.eb[dst] = es;
         } else {
+            if (a.counts && -1 - dst >= a.cap_part) continue;      // (device counts: no partial row outside the slice)
             float4 *o = reinterpret_cast<float4 *>(a.part + (size_t)(-1 - dst) * KP) + l;
 #pragma unroll
             for (int jj = 0; jj < J; ++jj) o[jj * LPN] = acc[jj];
@@ -153,8 +156,10 @@ __global__ __launch_bounds__(kBlock) void k_rel_gather_long(RelGatherArgs a) {
     const SlotLoop<LPN> sl;
     const int l = sl.l;
     const PackPos<LPN, PACKED> k(a.pack_k);
-    for (int i = sl.first; i < a.n_long; i += sl.stride) {
+    const int n_long = a.counts ? min(a.counts[2], a.cap_long) : a.n_long;
+    for (int i = sl.first; i < n_long; i += sl.stride) {
         const int32_t first = a.lfirst[i], dst = a.tj[a.lt[i]];
+        if (a.counts && (first < 0 || a.lcount[i] < 0 || first + a.lcount[i] > a.cap_part)) continue;
         float4 acc[J];
 #pragma unroll
         for (int jj = 0; jj < J; ++jj) acc[jj] = f4zero();
@@ -180,16 +185,19 @@ hipError_t launch_rel_finish(int Kp, const RelFinishArgs &a, bool residual_only,
 }
 
 hipError_t launch_rel_gather_sum(int Kp, const RelGatherArgs &a, hipStream_t s) {
-    if (a.n_work <= 0) return hipSuccess;
-    const dim3 g((unsigned)slot_blocks(Kp, a.n_work)), gl((unsigned)slot_blocks(Kp, a.n_long)), b(kBlock);
+    const bool dev = a.counts != nullptr;
+    if (dev && (a.cap_work < 1 || a.cap_long < 1 || a.cap_part < 1)) return hipErrorInvalidValue;
+    const int32_t n_work = dev ? a.cap_work : a.n_work, n_long = dev ? a.cap_long : a.n_long;
+    if (n_work <= 0) return hipSuccess;
+    const dim3 g((unsigned)slot_blocks(Kp, n_work)), gl((unsigned)slot_blocks(Kp, n_long)), b(kBlock);
     return for_slot_shape(Kp, [&](auto lpn, auto j) {
         constexpr int L = decltype(lpn)::value, JJ = decltype(j)::value;
         if (a.pack_k >= 0) {
             hipLaunchKernelGGL((k_rel_gather_sum<L, JJ, true>), g, b, 0, s, a);
-            if (a.n_long > 0) hipLaunchKernelGGL((k_rel_gather_long<L, JJ, true>), gl, b, 0, s, a);
+            if (n_long > 0) hipLaunchKernelGGL((k_rel_gather_long<L, JJ, true>), gl, b, 0, s, a);
         } else {
             hipLaunchKernelGGL((k_rel_gather_sum<L, JJ, false>), g, b, 0, s, a);
-            if (a.n_long > 0) hipLaunchKernelGGL((k_rel_gather_long<L, JJ, false>), gl, b, 0, s, a);
+            if (n_long > 0) hipLaunchKernelGGL((k_rel_gather_long<L, JJ, false>), gl, b, 0, s, a);
         }
     });
 }

@@ -4,11 +4,15 @@
 // (the scored samplers: the two blocks' kFwdQ forwards on the model's stream first, then k_bpr_sample_walk in k_bpr_sample's place —
 // under the best-of-C rule, include/fmhip_bpr_adaptive.h, or under WARP's, include/fmhip_warp.h, which also leaves the pairs' weights
 // for the step's hinge) and the training calls, which are the relational step in its pairs mode (rel_step, fmhip_relational.hip).
-// Every draw goes through resample(), every record call through record_scores().  The kernels are in fm_bpr.hip; the host arithmetic
+// A draw is queue_draw() — the sampler over a range of batches, then their inverse maps — and the counts come back by queue_fetch()
+// / accept_counts(): resample() is the first over every batch on the handle's stream followed by the second; the per-batch redraw
+// (include/fmhip_redraw.h; redraw_batch) queues one batch's draw between its step's forwards and the rest of the step on the
+// model's stream and fetches once per epoch.  Every record call goes through record_scores().  The kernels are in fm_bpr.hip; the host arithmetic
 // (the positives' lists, the sampler's twin) in fmhip_host.cpp.
 #include "fmhip_internal.h"
 #include "../../include/fmhip_bpr_adaptive.h"
 #include "../../include/fmhip_warp.h"
+#include "../../include/fmhip_redraw.h"
 #include "fm_bpr.h"
 #include "fm_relational.h"
 
@@ -22,10 +26,6 @@ using namespace fmhip;
 using namespace fmhip::host;
 
 namespace {
-
-// the capacity of a batch's slices of the candidates relation's arrays: RelationInverse's offsets, at the worst case of `rows` rows
-// (a list is at least one row and a chunk at least one, so work items <= rows; a long list is more than the cut)
-int64_t long_cap(int64_t rows) { return rows / kRelSumCut + 1; }
 
 int check_block(int device, fmhip_dataset_t d, const char *what) {
     if (!d) return fail(FMHIP_ERR_INVALID, "the %s block is NULL", what);
@@ -45,19 +45,29 @@ int check_bpr(fmhip_model_t m, fmhip_bpr_t h) {
     return check_rel_model(m, h->R);
 }
 
-BprSampleArgs sample_args(fmhip_bpr_t h, int64_t t) {
+// the pairs of the batches [b0, b1): a batch holds 2 * batch_pairs rows, rows 2p and 2p + 1 one pair
+void pair_range(fmhip_bpr_t h, size_t b0, size_t b1, int64_t *p0, int64_t *p1) {
+    const fmhip_relational::Batch &first = h->R->batches[b0], &last = h->R->batches[b1 - 1];
+    *p0 = first.row0 / 2;
+    *p1 = (last.row0 + last.rows) / 2;
+}
+
+// a draw of the pairs [p0, p1) at epoch t whose counters' sums go to slot `slot` of h->total
+BprSampleArgs sample_args(fmhip_bpr_t h, int64_t t, int64_t p0, int64_t p1, size_t slot) {
     BprSampleArgs sa{};
     sa.seed = h->seed;
     sa.t = (uint32_t)t;
     sa.n_pairs = (int32_t)h->n_pairs;
     sa.n_neg = h->n_neg;
     sa.M = (int32_t)h->M;
+    sa.p0 = (int32_t)p0;
+    sa.p1 = (int32_t)p1;
     sa.ictx = h->ictx.p;
     sa.pptr = h->pptr.p;
     sa.prow = h->prow.p;
     sa.map = h->R->rels[1]->map.p;
     sa.part = h->part.p;
-    sa.total = h->total.p;
+    sa.total = h->total.p + 3 * slot;
     return sa;
 }
 
@@ -75,19 +85,13 @@ int check_epoch_index(int64_t t) {
     return FMHIP_OK;
 }
 
-// What a scored sampler's walk reads, queued: the two blocks' kFwdQ forwards on the model's stream (rel_block_forwards), the
-// handle's stream behind them by an event — and behind the steps queued so far, which read the mapping.  -> the walk's arguments
-// (wa->a) and WARP's margin; the partials sized for `which`
-int scored_args(fmhip_model_t m, fmhip_bpr_t h, int64_t t, Sampler which, BprWarpArgs *wa) {
+// a scored sampler's walk over the pairs [p0, p1) under m, its arguments alone (nothing queued): the partials sized for `which`
+// over the whole set, -> wa->a and WARP's margin
+int walk_args(fmhip_model_t m, fmhip_bpr_t h, int64_t t, Sampler which, int64_t p0, int64_t p1, size_t slot, BprWarpArgs *wa) {
     fmhip_relational_t R = h->R;
-    TRY(rel_block_forwards(m, R));
-    if (!h->fwd_done) HIP_TRY(hipEventCreateWithFlags(&h->fwd_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->fwd_done, m->stream));
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->fwd_done, 0));
-    if (R->busy_set) HIP_TRY(hipStreamWaitEvent(h->stream, R->busy, 0));
     TRY(h->part.ensure((size_t)kCounters[which] * (size_t)bpr_adaptive_blocks(m->Kp, h->n_pairs)));
     *wa = BprWarpArgs{};
-    wa->a.s = sample_args(h, t);
+    wa->a.s = sample_args(h, t, p0, p1, slot);
     wa->a.n_cand = h->n_cand;
     wa->a.k = m->k;
     wa->a.Qu = R->rels[0]->Q.p;
@@ -97,13 +101,26 @@ int scored_args(fmhip_model_t m, fmhip_bpr_t h, int64_t t, Sampler which, BprWar
     return FMHIP_OK;
 }
 
+// What a scored sampler's walk on the handle's own stream reads, queued: the two blocks' kFwdQ forwards on the model's stream
+// (rel_block_forwards), the handle's stream behind them by an event — and behind the steps queued so far, which read the
+// mapping.  -> walk_args
+int scored_args(fmhip_model_t m, fmhip_bpr_t h, int64_t t, Sampler which, int64_t p0, int64_t p1, size_t slot, BprWarpArgs *wa) {
+    fmhip_relational_t R = h->R;
+    TRY(rel_block_forwards(m, R));
+    if (!h->fwd_done) HIP_TRY(hipEventCreateWithFlags(&h->fwd_done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->fwd_done, m->stream));
+    HIP_TRY(hipStreamWaitEvent(h->stream, h->fwd_done, 0));
+    if (R->busy_set) HIP_TRY(hipStreamWaitEvent(h->stream, R->busy, 0));
+    return walk_args(m, h, t, which, p0, p1, slot, wa);
+}
+
 hipError_t launch_scored(Sampler which, int Kp, const BprWarpArgs &wa, hipStream_t s) {
     return which == kWarp ? launch_bpr_sample_warp(Kp, wa, s) : launch_bpr_sample_adaptive(Kp, wa.a, s);
 }
 
-// What a WARP draw reads and writes on top of scored_args, queued behind it: the weight table (made on the host when the candidate
-// count has changed, uploaded on the handle's stream), the pairs' weights and trial counts
-int warp_outputs(fmhip_bpr_t h, BprWarpArgs *wa) {
+// What a WARP draw reads on top of the walk's arguments, queued on stream s: the weight table (made on the host when the candidate
+// count has changed, uploaded), and the room for what it writes: the pairs' weights and trial counts
+int warp_table(fmhip_bpr_t h, hipStream_t s) {
     TRY(h->wc.ensure(2 * (size_t)h->n_pairs));
     TRY(h->wtrials.ensure((size_t)h->n_pairs));
     TRY(h->wtab.ensure((size_t)kBprMaxCand + 1));
@@ -112,34 +129,54 @@ int warp_outputs(fmhip_bpr_t h, BprWarpArgs *wa) {
         warp_weight_table(h->M, h->n_cand, h->h_wtab.data());
         h->wtab_cand = h->n_cand;
     }
-    HIP_TRY(hipMemcpyAsync(h->wtab.p, h->h_wtab.data(), h->h_wtab.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    wa->W = h->wtab.p;
-    wa->c = h->wc.p;
-    wa->trials = h->wtrials.p;
+    HIP_TRY(hipMemcpyAsync(h->wtab.p, h->h_wtab.data(), h->h_wtab.size() * sizeof(float), hipMemcpyHostToDevice, s));
     return FMHIP_OK;
 }
 
-// sampler `which` at epoch t, the inverse map of every batch, the batches' counts (one synchronisation); the handle's own stream.
-// A scored sampler draws under model m (the caller has checked the two against each other and holds the model's lock); the uniform
-// one takes none.  total_out: the sampler's kCounters[which] counters
-int resample(fmhip_bpr_t h, int64_t t, Sampler which, fmhip_model_t m, int64_t *total_out) {
-    TRY(check_epoch_index(t));
-    TRY(set_device(h->device));
+void warp_outputs(fmhip_bpr_t h, BprWarpArgs *wa) {
+    wa->W = h->wtab.p;
+    wa->c = h->wc.p;
+    wa->trials = h->wtrials.p;
+}
+
+// the WARP draws that stand: batches [b0, b1) drawn (or, `have` false, every batch dropped); all of them: a draw of the whole set
+void warp_mark(fmhip_bpr_t h, size_t b0, size_t b1, bool have) {
+    const size_t nb = h->R->batches.size();
+    if (!have) {
+        h->warp_have.assign(nb, 0);
+        h->warp_drawn = false;
+        return;
+    }
+    h->warp_have.resize(nb, 0);
+    for (size_t b = b0; b < b1; ++b) h->warp_have[b] = 1;
+    h->warp_drawn = std::find(h->warp_have.begin(), h->warp_have.end(), (char)0) == h->warp_have.end();
+}
+
+// Queues on stream s: sampler `which` at epoch t over the pairs of the batches [b0, b1) (one launch; its counters into slot b0 of
+// h->total), then the inverse map of each of those batches, the counts left on the device.  own_stream: s is the handle's stream
+// — a scored sampler's forwards are queued on the model's and s put behind them and behind the steps queued so far; else s is the
+// model's stream, on which the caller has queued rel_block_forwards for this model state (and, WARP, warp_table).  A scored
+// sampler draws under m (the caller has checked the two against each other and holds the model's lock); the uniform one reads none
+int queue_draw(fmhip_bpr_t h, int64_t t, Sampler which, fmhip_model_t m, size_t b0, size_t b1, hipStream_t s, bool own_stream) {
     fmhip_relational_t R = h->R;
     fmhip_relational::Relation &rel = *R->rels[1];
-    if (which == kWarp) h->warp_drawn = false;      // (until this draw has come back whole)
+    int64_t p0 = 0, p1 = 0;
+    pair_range(h, b0, b1, &p0, &p1);
     if (which == kUniform) {
         // the mapping and the inverse map are read by the steps queued so far
-        if (R->busy_set) HIP_TRY(hipStreamWaitEvent(h->stream, R->busy, 0));
-        HIP_TRY(launch_bpr_sample(sample_args(h, t), h->stream));
+        if (own_stream && R->busy_set) HIP_TRY(hipStreamWaitEvent(s, R->busy, 0));
+        HIP_TRY(launch_bpr_sample(sample_args(h, t, p0, p1, b0), s));
     } else {
         BprWarpArgs wa{};
-        TRY(scored_args(m, h, t, which, &wa));
-        if (which == kWarp) TRY(warp_outputs(h, &wa));
-        HIP_TRY(launch_scored(which, m->Kp, wa, h->stream));
+        if (own_stream) TRY(scored_args(m, h, t, which, p0, p1, b0, &wa));
+        else TRY(walk_args(m, h, t, which, p0, p1, b0, &wa));
+        if (which == kWarp) {
+            if (own_stream) TRY(warp_table(h, s));
+            warp_outputs(h, &wa);
+        }
+        HIP_TRY(launch_scored(which, m->Kp, wa, s));
     }
-    const size_t nb = R->batches.size();
-    for (size_t b = 0; b < nb; ++b) {
+    for (size_t b = b0; b < b1; ++b) {
         const RelationInverse::Batch &ib = rel.batches[b];
         BprInverseArgs ia{};
         ia.map = rel.map.p + R->batches[b].row0;
@@ -156,32 +193,114 @@ int resample(fmhip_bpr_t h, int64_t t, Sampler which, fmhip_model_t m, int64_t *
         ia.lfirst = rel.lfirst.p + ib.l_off;
         ia.lcount = rel.lcount.p + ib.l_off;
         ia.counts = h->counts.p + 4 * b;
-        HIP_TRY(launch_bpr_inverse(ia, h->work.p, h->work.n, h->stream));
+        HIP_TRY(launch_bpr_inverse(ia, h->work.p, h->work.n, s));
+        h->stale[b] = 1;
     }
-    std::vector<int32_t> counts(4 * nb);
-    unsigned long long total[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(counts.data(), h->counts.p, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(total, h->total.p, (size_t)kCounters[which] * sizeof total[0], hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    int32_t max_part = 0;
+    h->any_stale = true;
+    return FMHIP_OK;
+}
+
+// every batch's counts and every slot of the samplers' counters, on their way back on stream s: good once s has been synchronised
+struct Fetched {
+    std::vector<int32_t> counts;
+    std::vector<unsigned long long> total;
+};
+
+int queue_fetch(fmhip_bpr_t h, hipStream_t s, Fetched *f) {
+    const size_t nb = h->R->batches.size();
+    f->counts.assign(4 * nb, 0);
+    f->total.assign(3 * nb, 0);
+    HIP_TRY(hipMemcpyAsync(f->counts.data(), h->counts.p, f->counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(f->total.data(), h->total.p, f->total.size() * sizeof f->total[0], hipMemcpyDeviceToHost, s));
+    return FMHIP_OK;
+}
+
+// the fetched counts checked against what the slices and the step's partial rows are sized for, then the host's copy refreshed
+int accept_counts(fmhip_bpr_t h, const Fetched &f) {
+    fmhip_relational_t R = h->R;
+    fmhip_relational::Relation &rel = *R->rels[1];
+    const size_t nb = R->batches.size();
     for (size_t b = 0; b < nb; ++b) {
-        RelationInverse::Batch &ib = rel.batches[b];
-        const int32_t *c = counts.data() + 4 * b;
+        const int32_t *c = f.counts.data() + 4 * b;
         const int64_t rows = R->batches[b].rows;
-        // (what the slices and the step's partial rows are sized for)
-        if (c[0] < 1 || c[0] > rows || c[1] < c[0] || c[1] > rows || c[2] < 0 || c[2] >= long_cap(rows) || c[3] < 0 || c[3] > 2 * long_cap(rows))
+        if (c[0] < 1 || c[0] > rows || c[1] < c[0] || c[1] > rows || c[2] < 0 || c[2] >= rel_long_cap(rows) || c[3] < 0 || c[3] > 2 * rel_long_cap(rows))
             return fail(FMHIP_ERR_HIP, "the inverse map of batch %zu came back with counts {%d, %d, %d, %d} for %lld rows", b, c[0], c[1], c[2], c[3],
                         (long long)rows);
+    }
+    for (size_t b = 0; b < nb; ++b) {
+        RelationInverse::Batch &ib = rel.batches[b];
+        const int32_t *c = f.counts.data() + 4 * b;
         ib.n_touched = c[0];
         ib.n_work = c[1];
         ib.n_long = c[2];
         ib.n_part = c[3];
-        max_part = std::max(max_part, c[3]);
+        h->stale[b] = 0;
     }
-    rel.max_part = max_part;      // (the step's workspace grows to it: ensure_rel_workspace)
-    if (which == kWarp) h->warp_drawn = true;
+    h->any_stale = false;
+    return FMHIP_OK;
+}
+
+// the host's counts, for a call that reads them — and the draw itself, for a call that reads the mapping or WARP's outputs from
+// the host: when a per-batch draw has been queued and not fetched since, one fetch (one synchronisation, the handle's stream
+// behind the steps queued so far, hence behind every draw)
+int fresh_counts(fmhip_bpr_t h) {
+    if (!h->any_stale) return FMHIP_OK;
+    TRY(set_device(h->device));
+    if (h->R->busy_set) HIP_TRY(hipStreamWaitEvent(h->stream, h->R->busy, 0));
+    Fetched f;
+    TRY(queue_fetch(h, h->stream, &f));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return accept_counts(h, f);
+}
+
+// sampler `which` at epoch t over the whole set, the inverse map of every batch, the batches' counts (one synchronisation); the
+// handle's own stream.  total_out: the sampler's kCounters[which] counters
+int resample(fmhip_bpr_t h, int64_t t, Sampler which, fmhip_model_t m, int64_t *total_out) {
+    TRY(check_epoch_index(t));
+    TRY(set_device(h->device));
+    if (which == kWarp) warp_mark(h, 0, 0, false);      // (until this draw has come back whole)
+    const size_t nb = h->R->batches.size();
+    TRY(queue_draw(h, t, which, m, 0, nb, h->stream, true));
+    Fetched f;
+    TRY(queue_fetch(h, h->stream, &f));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    TRY(accept_counts(h, f));
+    if (which == kWarp) warp_mark(h, 0, nb, true);
     if (total_out)
-        for (int i = 0; i < kCounters[which]; ++i) total_out[i] = (int64_t)total[i];
+        for (int i = 0; i < kCounters[which]; ++i) total_out[i] = (int64_t)f.total[(size_t)i];
+    return FMHIP_OK;
+}
+
+// a sampler's counters of one draw over `pairs` pairs, added to the public six {pairs, attempts, forced, replaced, violated, trials}
+void add_draw(Sampler which, const unsigned long long *tot, int64_t pairs, int64_t (&out)[6]) {
+    out[0] += pairs;
+    const int at = which == kWarp ? 4 : 1;
+    for (int i = 0; i < kCounters[which]; ++i) out[at + i] += (int64_t)tot[i];
+}
+
+void put_draw(const int64_t (&v)[6], fmhip_redraw_stats *out) {
+    out->pairs = v[0];
+    out->attempts = v[1];
+    out->forced = v[2];
+    out->replaced = v[3];
+    out->violated = v[4];
+    out->trials = v[5];
+}
+
+// One batch of the per-batch redraw (include/fmhip_redraw.h), queued on the model's stream: the blocks' forwards under the model
+// as it stands, the draw of the batch's pairs, the batch's inverse map, the rest of the step with the counts read on the device.
+// WARP: the caller has queued warp_table on the model's stream
+int redraw_batch(fmhip_model_t m, fmhip_bpr_t h, int64_t t, Sampler which, int64_t b, const Sgd &sgd, double *acc) {
+    fmhip_relational_t R = h->R;
+    TRY(rel_block_forwards(m, R));
+    TRY(queue_draw(h, t, which, m, (size_t)b, (size_t)b + 1, m->stream, false));
+    const PairHinge hinge{h->wc.p, (float)h->warp_margin};
+    const int32_t *dev_counts[2] = {nullptr, h->counts.p + 4 * b};
+    RelStepQueued queued;
+    queued.forwards = true;
+    queued.dev_counts = dev_counts;
+    TRY(rel_step(m, R, b, sgd, acc, true, which == kWarp ? &hinge : nullptr, queued));
+    if (which == kWarp) warp_mark(h, (size_t)b, (size_t)b + 1, true);
     return FMHIP_OK;
 }
 
@@ -198,9 +317,7 @@ int record_scores(fmhip_model_t m, fmhip_bpr_t h, int64_t t, int64_t p0, int64_t
     TRY(h->rec_scores.ensure(n));
     if (which == kWarp) TRY(h->rec_pos.ensure(np));
     BprWarpArgs wa{};
-    TRY(scored_args(m, h, t, which, &wa));
-    wa.a.p0 = (int32_t)p0;
-    wa.a.p1 = (int32_t)p1;
+    TRY(scored_args(m, h, t, which, p0, p1, 0, &wa));
     wa.a.rec_rows = h->rec_rows.p;
     wa.a.rec_scores = h->rec_scores.p;
     wa.rec_pos = h->rec_pos.p;
@@ -226,6 +343,47 @@ int step_hinge(fmhip_bpr_t h, PairHinge *store, const PairHinge **out) {
         return fail(FMHIP_ERR_INVALID, "WARP is on and no WARP draw stands since fmhip_warp_set: call fmhip_warp_resample (or fmhip_bpr_epoch) first");
     *store = PairHinge{h->wc.p, (float)h->warp_margin};
     *out = store;
+    return FMHIP_OK;
+}
+
+// fmhip_bpr_epoch in the per-batch mode: every batch's forwards, draw, inverse map and step in stream order on the model's stream,
+// then ONE synchronisation — the statistics' copy when the caller wants them, the stream's otherwise — that also brings back every
+// batch's counts and the sampler's counters per batch (the caller holds the model's lock and has checked m, h and the order)
+int redraw_epoch(fmhip_model_t m, fmhip_bpr_t h, int64_t t, const Sgd &sgd, const int64_t *order, fmhip_stats *stats) {
+    TRY(check_epoch_index(t));
+    const Sampler which = epoch_sampler(h);
+    const int64_t nb = (int64_t)h->R->batches.size();
+    h->have_epoch_draw = false;
+    if (which == kWarp) {
+        warp_mark(h, 0, 0, false);
+        TRY(warp_table(h, m->stream));
+    }
+    HIP_TRY(hipMemsetAsync(h->total.p, 0, 3 * (size_t)nb * sizeof(unsigned long long), m->stream));      // (a batch the order leaves out)
+    HIP_TRY(hipMemsetAsync(m->acc.p, 0, 4 * sizeof(double), m->stream));
+    int64_t nnz = 0;
+    std::vector<char> visited((size_t)nb, 0);
+    for (int64_t j = 0; j < nb; ++j) {
+        const int64_t b = order ? order[j] : j;
+        TRY(redraw_batch(m, h, t, which, b, sgd, m->acc.p));
+        visited[(size_t)b] = 1;
+        nnz += m->step.last_nnz;
+    }
+    Fetched f;
+    TRY(queue_fetch(h, m->stream, &f));
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        TRY(read_acc(m, stats));      // (synchronises the model's stream: the fetch has landed)
+        stats->nnz = nnz;
+        stats->steps = nb;
+    } else {
+        HIP_TRY(hipStreamSynchronize(m->stream));
+    }
+    TRY(accept_counts(h, f));
+    int64_t sum[6] = {0, 0, 0, 0, 0, 0};
+    for (int64_t b = 0; b < nb; ++b)
+        if (visited[(size_t)b]) add_draw(which, f.total.data() + 3 * b, h->R->batches[(size_t)b].rows / 2, sum);
+    memcpy(h->epoch_draw, sum, sizeof sum);
+    h->have_epoch_draw = true;
     return FMHIP_OK;
 }
 
@@ -312,8 +470,12 @@ int fmhip_bpr_create(int device, fmhip_dataset_t contexts, fmhip_dataset_t candi
         ib.row_off = ib.t_off = ib.w_off = R->batches[b].row0;
         ib.tptr_off = R->batches[b].row0 + (int64_t)b;
         ib.l_off = l_total;
-        l_total += long_cap(R->batches[b].rows);
+        l_total += rel_long_cap(R->batches[b].rows);
     }
+    // the partial rows of the long lists, at their worst case too (a few KB per 1000 rows): whatever a draw gives fits, so the step
+    // never waits for a count to size its workspace
+    rel.max_part = (int32_t)(2 * rel_long_cap(R->max_rows));
+    H->stale.assign(nb, 0);
     TRY(rel.trow.alloc((size_t)N)); TRY(rel.tj.alloc((size_t)N)); TRY(rel.tptr.alloc((size_t)N + nb));
     TRY(rel.wt.alloc((size_t)N)); TRY(rel.wbeg.alloc((size_t)N)); TRY(rel.wdst.alloc((size_t)N));
     TRY(rel.lt.alloc((size_t)l_total)); TRY(rel.lfirst.alloc((size_t)l_total)); TRY(rel.lcount.alloc((size_t)l_total));
@@ -325,7 +487,7 @@ int fmhip_bpr_create(int device, fmhip_dataset_t contexts, fmhip_dataset_t candi
     TRY(H->prow.alloc(std::max<size_t>(prow.size(), 1)));
     if (!prow.empty()) HIP_TRY(hipMemcpy(H->prow.p, prow.data(), prow.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     TRY(H->part.alloc(2 * (size_t)bpr_sample_blocks(n_pairs)));      // (the uniform sampler's need; the scored ones grow it)
-    TRY(H->total.alloc(3));
+    TRY(H->total.alloc(3 * nb));
     size_t work = 0;
     HIP_TRY(bpr_inverse_workspace((int32_t)R->max_rows, (int32_t)M, &work));
     TRY(H->work.alloc(work));
@@ -406,7 +568,7 @@ int fmhip_warp_set(fmhip_bpr_t h, int enabled, double margin) {
         return fail(FMHIP_ERR_INVALID, "margin = %g: the WARP margin is a finite number >= 0", margin);
     h->warp = enabled != 0;
     h->warp_margin = margin;
-    h->warp_drawn = false;
+    warp_mark(h, 0, 0, false);
     return FMHIP_OK;
 }
 
@@ -436,6 +598,7 @@ int fmhip_warp_weights(fmhip_bpr_t h, float *out) {
     if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
     if (!h->warp_drawn) return fail(FMHIP_ERR_INVALID, "no WARP draw stands: call fmhip_warp_resample first");
     TRY(set_device(h->device));
+    TRY(fresh_counts(h));      // (behind the per-batch draws queued so far)
     std::vector<float> c((size_t)(2 * h->n_pairs));
     HIP_TRY(hipMemcpy(c.data(), h->wc.p, c.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (int64_t p = 0; p < h->n_pairs; ++p) out[p] = c[(size_t)(2 * p)];
@@ -447,6 +610,7 @@ int fmhip_warp_trials(fmhip_bpr_t h, int32_t *out) {
     if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
     if (!h->warp_drawn) return fail(FMHIP_ERR_INVALID, "no WARP draw stands: call fmhip_warp_resample first");
     TRY(set_device(h->device));
+    TRY(fresh_counts(h));
     HIP_TRY(hipMemcpy(out, h->wtrials.p, (size_t)h->n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
     return FMHIP_OK;
 }
@@ -460,6 +624,7 @@ int fmhip_bpr_negatives(fmhip_bpr_t h, int32_t *out) {
     if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
     if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
     TRY(set_device(h->device));
+    TRY(fresh_counts(h));      // (a per-batch draw queued without a synchronisation writes the mapping: behind it)
     std::vector<int32_t> map((size_t)(2 * h->n_pairs));
     HIP_TRY(hipMemcpy(map.data(), h->R->rels[1]->map.p, map.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int64_t p = 0; p < h->n_pairs; ++p) out[p] = map[(size_t)(2 * p + 1)];
@@ -474,6 +639,7 @@ int fmhip_bpr_step(fmhip_model_t m, fmhip_bpr_t h, int64_t batch, double eta, do
     PairHinge hinge_store{};
     const PairHinge *hinge = nullptr;
     TRY(step_hinge(h, &hinge_store, &hinge));
+    TRY(fresh_counts(h));      // (the step sizes its gather from the host's counts)
     TRY(rel_step(m, h->R, batch, Sgd{eta, reg0, regw, regv}, nullptr, true, hinge));
     if (stats) {
         memset(stats, 0, sizeof *stats);
@@ -492,6 +658,7 @@ int fmhip_bpr_epoch(fmhip_model_t m, fmhip_bpr_t h, int64_t t, double eta, doubl
     if (order)
         for (int64_t j = 0; j < nb; ++j)
             if (order[j] < 0 || order[j] >= nb) return fail(FMHIP_ERR_INVALID, "batch %lld out of range [0, %lld)", (long long)order[j], (long long)nb);
+    if (h->redraw == FMHIP_REDRAW_BATCH) return redraw_epoch(m, h, t, Sgd{eta, reg0, regw, regv}, order, stats);
     TRY(resample(h, t, epoch_sampler(h), m, nullptr));
     PairHinge hinge_store{};
     const PairHinge *hinge = nullptr;
@@ -512,6 +679,63 @@ int fmhip_bpr_epoch(fmhip_model_t m, fmhip_bpr_t h, int64_t t, double eta, doubl
     return FMHIP_OK;
 }
 
+// ---- the redraw mode (include/fmhip_redraw.h) -------------------------------------------------------------------------------------------
+
+int fmhip_redraw_set(fmhip_bpr_t h, int mode) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (mode != FMHIP_REDRAW_EPOCH && mode != FMHIP_REDRAW_BATCH)
+        return fail(FMHIP_ERR_INVALID, "mode = %d: the redraw mode is FMHIP_REDRAW_EPOCH (%d) or FMHIP_REDRAW_BATCH (%d)", mode, FMHIP_REDRAW_EPOCH,
+                    FMHIP_REDRAW_BATCH);
+    h->redraw = mode;
+    return FMHIP_OK;
+}
+
+int fmhip_redraw_get(fmhip_bpr_t h, int *mode) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (!mode) return fail(FMHIP_ERR_INVALID, "mode is NULL");
+    *mode = h->redraw;
+    return FMHIP_OK;
+}
+
+int fmhip_redraw_step(fmhip_model_t m, fmhip_bpr_t h, int64_t t, int64_t batch, double eta, double reg0, double regw, double regv,
+                      fmhip_stats *stats, fmhip_redraw_stats *draw) {
+    WriteLock lock(m);
+    TRY(check_bpr(m, h));
+    if (batch < 0 || batch >= (int64_t)h->R->batches.size())
+        return fail(FMHIP_ERR_INVALID, "batch %lld out of range [0, %zu)", (long long)batch, h->R->batches.size());
+    TRY(check_epoch_index(t));
+    const Sampler which = epoch_sampler(h);
+    if (which == kWarp) TRY(warp_table(h, m->stream));
+    TRY(redraw_batch(m, h, t, which, batch, Sgd{eta, reg0, regw, regv}, nullptr));
+    if (!stats && !draw) return FMHIP_OK;
+    Fetched f;
+    TRY(queue_fetch(h, m->stream, &f));
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        TRY(read_scal(m, stats));      // (synchronises the model's stream: the fetch has landed)
+        stats->nnz = m->step.last_nnz;
+        stats->steps = 1;
+    } else {
+        HIP_TRY(hipStreamSynchronize(m->stream));
+    }
+    TRY(accept_counts(h, f));
+    if (draw) {
+        int64_t v[6] = {0, 0, 0, 0, 0, 0};
+        add_draw(which, f.total.data() + 3 * batch, h->R->batches[(size_t)batch].rows / 2, v);
+        put_draw(v, draw);
+    }
+    return FMHIP_OK;
+}
+
+int fmhip_redraw_epoch_stats(fmhip_bpr_t h, fmhip_redraw_stats *out) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    if (!h->have_epoch_draw)
+        return fail(FMHIP_ERR_INVALID, "no per-batch epoch has run: fmhip_redraw_set(h, FMHIP_REDRAW_BATCH), then fmhip_bpr_epoch");
+    put_draw(h->epoch_draw, out);
+    return FMHIP_OK;
+}
+
 int fmhip_bpr_pair_logloss(fmhip_model_t m, fmhip_bpr_t h, double *logloss, double *concordance, fmhip_stats *stats) {
     ReadLock lock(m);
     if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
@@ -526,6 +750,7 @@ int fmhip_bpr_debug_inverse(struct fmhip_bpr *h, int64_t batch, int32_t *trow, i
         return fail(FMHIP_ERR_INVALID, "batch %lld out of range [0, %zu)", (long long)batch, h->R->batches.size());
     if (!trow || !tptr || !tj || !wt || !wbeg || !wdst || !lt || !lfirst || !lcount || !counts) return fail(FMHIP_ERR_INVALID, "an out array is NULL");
     TRY(set_device(h->device));
+    TRY(fresh_counts(h));
     const fmhip_relational::Relation &rel = *h->R->rels[1];
     const RelationInverse::Batch &ib = rel.batches[(size_t)batch];
     const auto back = [](int32_t *dst, const int32_t *src, int64_t n) {

@@ -360,7 +360,9 @@ struct fmhip_relational {
 // A BPR trainer (include/fmhip_bpr.h): an OWNED relational dataset of 2 n_pairs rows over the two borrowed blocks — relation 0 the
 // contexts (its inverse map built once on the host), relation 1 the candidates, whose mapping's odd entries the sampler rewrites
 // and whose inverse map the device rebuilds (buffers at their worst case, the batches' counts read back once per resample) —
-// the interactions' contexts and the contexts' positives on the device, and a stream of its own for the resample.
+// the interactions' contexts and the contexts' positives on the device, and a stream of its own for the resample.  Under the
+// per-batch redraw (include/fmhip_redraw.h) a batch's draw, inverse map and step are queued on the model's stream and the step reads
+// the counts from the device: the host's copy (R->rels[1]->batches) is then stale until the next fetch.
 struct fmhip_bpr {
     template <typename T> using DevBuf = fmhip::host::DevBuf<T>;
     int device = 0;
@@ -372,7 +374,14 @@ struct fmhip_bpr {
     DevBuf<int64_t> pptr;
     // the per-block partials and their sums [3] of the sampler that runs: a resample grows `part` to its sampler's need and ends in a
     // synchronise, so no two draws hold it at once
-    DevBuf<unsigned long long> part, total;
+    DevBuf<unsigned long long> part, total;   // total: [n_batches][3], a slot per batch (a whole-set draw sums into slot 0)
+    // the redraw mode (FMHIP_REDRAW_*), the batches whose host counts are older than the device's, and the sampler's counters
+    // summed over the last per-batch epoch {pairs, attempts, forced, replaced, violated, trials}
+    int redraw = 0;
+    std::vector<char> stale;
+    bool any_stale = false;
+    bool have_epoch_draw = false;
+    int64_t epoch_draw[6] = {0, 0, 0, 0, 0, 0};
     DevBuf<char> work;                         // the inverse build's workspace, for the largest batch
     hipStream_t stream = nullptr;
     // the adaptive sampler (include/fmhip_bpr_adaptive.h): candidates per pair, the debug call's record buffers, and the event that
@@ -385,6 +394,7 @@ struct fmhip_bpr {
     // weights (a PairArgs::c over all 2 n_pairs rows) and trial counts, the weight table W[0 .. wtab_cand] on both sides, the
     // debug call's s+ record
     bool warp = false, warp_drawn = false;
+    std::vector<char> warp_have;               // per batch: a WARP draw stands since the switch was last set (all: warp_drawn)
     double warp_margin = 1.0;
     DevBuf<float> wc, wtab, rec_pos;
     DevBuf<int32_t> wtrials;
@@ -567,7 +577,19 @@ struct PairHinge {
     const float *c;      // [2 * n_pairs] over the whole dataset
     float margin;
 };
-int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs = false, const PairHinge *hinge = nullptr);
+// queued (the per-batch redraw): rel_block_forwards has been queued for this model state by the caller — the step does not repeat it.
+// dev_counts (nullable; one entry per relation, each nullable): the batch's inverse-map counts {n_touched, n_work, n_long, n_part}
+// of that relation ON THE DEVICE — its gather reads n_work and n_long there, clamped to the slices' capacity, on worst-case grids,
+// and the host's copy of the counts is not read
+struct RelStepQueued {
+    bool forwards = false;
+    const int32_t *const *dev_counts = nullptr;
+};
+int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs = false, const PairHinge *hinge = nullptr,
+             const RelStepQueued &queued = RelStepQueued());
+// the capacity of the long lists' slices of a batch of `rows` rows (a long list has more than the cut's rows); its partial rows
+// number at most twice that
+inline int64_t rel_long_cap(int64_t rows) { return rows / FMHIP_RELATIONAL_SUM_CUT + 1; }
 // the beginning of a step alone (the BPR trainer's adaptive sampler reads what it leaves): scales folded, workspace sized, every
 // block's kFwdQ forward into its relation's Q / yq, asynchronous on the model's stream
 int rel_block_forwards(fmhip_model_t m, fmhip_relational_t R);

@@ -137,9 +137,10 @@ int rel_block_forwards(fmhip_model_t m, fmhip_relational_t R) {
 }
 
 // one relational step of batch b, asynchronous on the model's stream; acc (nullable): the epoch's fp64 accumulators
-int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs, const PairHinge *hinge) {
+int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, double *acc, bool pairs, const PairHinge *hinge,
+             const RelStepQueued &queued) {
     const fmhip_relational::Batch &B = R->batches[(size_t)b];
-    TRY(rel_block_forwards(m, R));           // every block's q-mode pass, over the whole block
+    if (!queued.forwards) TRY(rel_block_forwards(m, R));      // every block's q-mode pass, over the whole block
     TRY(begin_forward(m));                   // (the forwards do not touch the gradient)
     int64_t nnz = R->block_nnz;
     if (R->plain) {
@@ -164,8 +165,8 @@ int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, d
         HIP_TRY(launch_pair_finish(m->Kp, pa, m->stream, &m->step.fwd_parts));
     }
     m->step.written(nnz, B.rows);            // (no backward window: the parts' whole-batch backwards below are the step's own)
-    for (auto &relp : R->rels) {
-        fmhip_relational::Relation &rel = *relp;
+    for (size_t ri = 0; ri < R->rels.size(); ++ri) {
+        fmhip_relational::Relation &rel = *R->rels[ri];
         const RelationInverse::Batch &ib = rel.batches[(size_t)b];
         const size_t J = (size_t)rel.block->n_rows;
         HIP_TRY(hipMemsetAsync(rel.Pb.p, 0, J * m->Kp * sizeof(float), m->stream));      // block rows nobody references: exact zeros
@@ -189,6 +190,13 @@ int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, d
         ga.part = rel.part.p;
         ga.part_e = rel.part_e.p;
         ga.pack_k = m->pack_k();
+        if (queued.dev_counts && queued.dev_counts[ri]) {      // the counts where the inverse build left them: no host copy read
+            ga.counts = queued.dev_counts[ri];
+            ga.n_work = ga.n_long = 0;
+            ga.cap_work = (int32_t)B.rows;
+            ga.cap_long = (int32_t)rel_long_cap(B.rows);
+            ga.cap_part = 2 * ga.cap_long;
+        }
         HIP_TRY(launch_rel_gather_sum(m->Kp, ga, m->stream));
         const BwdSource src{rel.Pb.p, rel.eb.p};
         m->step.arm_hot(rel.block->hot_T > 0);
