@@ -116,10 +116,14 @@ def make_problem(seed, n_rows, k, blocks, maps, plain, n1, loss="squared", scale
                 maps=[np.asarray(m, np.int32) for m in maps], plain=plain)
 
 
-def base_problem(seed, k, loss="squared", n_rows=400, plain=True, hot_refs=150):
+def base_problem(seed, k, loss="squared", n_rows=400, plain=True, hot_refs=150, hot=False):
     """The issue's base problem: a user block (J = 37, 0-6 nonzeros, ids [0, 100)), an item block (J = 90, 1-8 nonzeros, ids
     [100, 220)), a plain part (0-3 nonzeros, ids [220, 300)).  Item row 3 is referenced by `hot_refs` rows; user rows 30.. and item
-    rows 80.. by nobody; item row 5 is empty (and referenced)."""
+    rows 80.. by nobody; item row 5 is empty (and referenced).
+    hot (default off: every other case keeps its data): dense features on top, from a generator of their own — six "demographic"
+    features (ids 94..99) in the user block, five of them in 15-60 % of its rows and id 99 in the seven rows nobody references and
+    in no other (19 % of the block: its gradient is exactly zero); three features (ids 297..299) in 20-50 % of the plain part's rows.
+    Built with hot_block=4 (the user block) and in several batches (the plain part) both hold a dense hot block: `hot_layouts`."""
     rng = np.random.default_rng(seed)
     users = random_block(rng, 37, 0, 6, 0, 100)
     items = random_block(rng, 90, 1, 8, 100, 220, empty=(5,))
@@ -129,12 +133,58 @@ def base_problem(seed, k, loss="squared", n_rows=400, plain=True, hot_refs=150):
     mi[rng.choice(n_rows, size=min(hot_refs, n_rows), replace=False)] = 3
     mi[:2] = 5
     pl = random_block(rng, n_rows, 0, 3, 220, 300) if plain else None
+    if hot:
+        hrng = np.random.default_rng(seed + 7000)
+        users = with_dense_features(hrng, users, [94, 95, 96, 97, 98], hrng.uniform(0.15, 0.60, 5))
+        users = with_dense_features(hrng, users, [DEMO_UNREFERENCED], [1.0], rows=range(30, 37), only=True)
+        if plain:
+            pl = with_dense_features(hrng, pl, list(PLAIN_HOT), hrng.uniform(0.20, 0.50, 3))
     return make_problem(seed, n_rows, k, [users, items], [mu, mi], pl, 300, loss)
 
 
-def build(fmhip, p, batch_rows=0):
-    """-> (RelationalData, FMModel at the problem's parameters)."""
+DEMO = (94, 95, 96, 97, 98, 99)         # base_problem(hot=True): the user block's dense features ...
+DEMO_UNREFERENCED = 99                  # ... the one that only rows nobody references hold
+PLAIN_HOT = (297, 298, 299)             # ... and the plain part's
+
+
+def with_dense_features(rng, block, ids, shares, rows=None, only=False):
+    """The block with feature ids[i] added to a share shares[i] of `rows` (default: all) where the row does not hold it yet;
+    only: and removed from every other row."""
+    n = len(block["row_ptr"]) - 1
+    rows = set(range(n) if rows is None else rows)
+    rp, col, val = [0], [], []
+    for j in range(n):
+        c, x = block["col"][block["row_ptr"][j]:block["row_ptr"][j + 1]].tolist(), block["val"][block["row_ptr"][j]:block["row_ptr"][j + 1]].tolist()
+        for f, share in zip(ids, shares):
+            draw = rng.random() < share
+            if j in rows and draw and f not in c:
+                c.append(int(f))
+                x.append(float(rng.uniform(0.1, 1.0)))
+            if only and j not in rows and f in c:
+                x.pop(c.index(f))
+                c.remove(f)
+        col += c
+        val += x
+        rp.append(len(col))
+    return dict(row_ptr=np.asarray(rp, np.int64), col=np.asarray(col, np.int32), val=np.asarray(val, np.float64))
+
+
+def hot_layouts(p, batch_rows, hot_block=4):
+    """What ds.layout() must report for the user block (built single-batch with hot_block by name) and for the plain part (in batches
+    of batch_rows) of base_problem(hot=True), by the library's rule as layout_cases.expected_layout restates it."""
+    import layout_cases as lc
+    return (lc.expected_layout(dict(p["blocks"][0], n1=p["n1"]), dict(batch_rows=0, hot_block=hot_block)),
+            lc.expected_layout(dict(p["plain"], n1=p["n1"]), dict(batch_rows=batch_rows)))
+
+
+def build(fmhip, p, batch_rows=0, hot_block=None):
+    """-> (RelationalData, FMModel at the problem's parameters).  hot_block: relation 0's block is a DataSet built with a dense hot
+    block asked for by name (a single-batch dataset gets none by default)."""
     rels = [fmhip.Relation((b["row_ptr"], b["col"], b["val"]), m) for b, m in zip(p["blocks"], p["maps"])]
+    if hot_block:
+        b = p["blocks"][0]
+        rels[0] = fmhip.Relation(fmhip.DataSet(b["row_ptr"], b["col"], b["val"], np.zeros(len(b["row_ptr"]) - 1), batch_rows=0, hot_block=hot_block),
+                                 p["maps"][0])
     pl = None if p.get("plain") is None else fmhip.Features(p["plain"]["row_ptr"], p["plain"]["col"], p["plain"]["val"])
     rd = fmhip.RelationalData(p["y"], rels, plain=pl, batch_rows=batch_rows)
     fm = fmhip.FMModel(p["n1"] - 1, p["k"])

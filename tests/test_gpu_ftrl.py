@@ -486,6 +486,49 @@ def test_relational_step_vs_the_flat_step(fmhip, k, loss):
     fm.close()
 
 
+@pytest.mark.parametrize("loss", ["squared", "logistic"])
+@pytest.mark.parametrize("k", [8, 32, 100])
+def test_relational_step_with_hot_block_parts_vs_the_flat_step(fmhip, k, loss):
+    """test_relational_step_vs_the_flat_step on relational_ref.base_problem(hot=True): the user block built with a dense hot block
+    by name, the plain part in four batches with one of its own (asserted) — every batch's step against the twin and against the
+    flat step on expand(), the same tolerances and caps; two runs bit-identical."""
+    p = rref.base_problem(700 + k, k, loss, hot=True)
+    a, br = rref.flat(p), 100
+    assert len(fref.cancelling_features(a["row_ptr"], a["col"], a["n1"])) == 0
+    l1w, l1v = fref.choose_l1(a, loss)
+    rule = fref.Rule(loss, False, BETA, l1w, l1v)
+    s0 = fref.State(a["w0"], a["w"], a["v"], INIT, BETA)
+    kw = dict(alpha=ETA, beta=BETA, l1w=l1w, l1v=l1v, l2_0=L2[0], l2w=L2[1], l2v=L2[2], ftrl_init=INIT, loss=loss)
+    want_u, want_p = rref.hot_layouts(p, br)
+    for b in range(4):
+        s1 = fref.step(s0.copy(), a["row_ptr"], a["col"], a["val"], a["y"], b * br, (b + 1) * br, ETA, *L2, rule)
+        outs = []
+        for _ in range(2):
+            rd, fm = rref.build(fmhip, p, br, hot_block=4)
+            fmhip.HipFTRL(**kw).step(fm, rd, b)
+            outs.append(bits(fm))
+            got_u, got_p = rd.relations[0].block.layout(), rd.plain.layout()
+            assert got_u["hot_pages"] == want_u["hot_pages"] >= 1 and sorted(got_u["hot_ids_all"]) == want_u["hot_ids_all"]
+            assert got_p["hot_pages"] == want_p["hot_pages"] >= 1 and sorted(got_p["hot_ids_all"]) == want_p["hot_ids_all"]
+            if len(outs) == 1:
+                check_step(fm, s0, s1, ETA, rule)
+                fl = rd.expand().cache()
+                fm2 = fmhip.FMModel(p["n1"] - 1, k)
+                fm2.w0, fm2.w, fm2.v = p["w0"], p["w"], p["v"]
+                fmhip.HipFTRL(**kw).step(fm2, fl, b)
+                check_step(fm2, s0, s1, ETA, rule)
+                tol = fref.tolerances(s0, s1)
+                near = fref.near_threshold(s0, s1, ETA, rule)
+                assert (np.abs(fm.v - fm2.v) <= 2 * tol["v"])[~near["v"]].all() and (np.abs(fm.w - fm2.w) <= 2 * tol["w"])[~near["w"]].all()
+                fl.unpersist()
+                fm2.close()
+            rd.unpersist()
+            for part in rd._parts():
+                part.unpersist()
+            fm.close()
+        assert same(outs[0], outs[1]), b
+
+
 # ---- 8. the sparsity counts ---------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("k", [8, 32])

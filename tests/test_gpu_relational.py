@@ -48,9 +48,9 @@ def close(rd, fm):
     fm.close()
 
 
-def one_step(fmhip, p, loss, regs=REGS, batch_rows=0, batch=0, **kw):
-    """One relational step of `batch` on the device and by the twin -> (fm, rd, s0, s1, stats, e)."""
-    rd, fm = rref.build(fmhip, p, batch_rows)
+def one_step(fmhip, p, loss, regs=REGS, batch_rows=0, batch=0, hot_block=None, **kw):
+    """One relational step of `batch` on the device and by the twin -> (fm, rd, s0, s1, stats, e).  hot_block: relational_ref.build's."""
+    rd, fm = rref.build(fmhip, p, batch_rows, hot_block)
     n = len(p["y"])
     br = batch_rows if 0 < batch_rows <= n else n
     r0, r1 = batch * br, min(n, (batch + 1) * br)
@@ -213,6 +213,82 @@ def test_segmented_sum_edges(fmhip, case, k, loss):
         outs.append(params(fm) + (st["sse"], st["sum_e"]))
         close(rd, fm)
     assert same(outs[0], outs[1])
+
+
+# ---- 4b. parts with a dense hot block ---------------------------------------------------------------------------------------
+
+HOT_BATCH = 100
+
+
+def assert_hot_parts(rd, p):
+    """base_problem(hot=True) built with hot_block=4 and in batches: the user block and the plain part both report the hot block the
+    library's rule gives them (relational_ref.hot_layouts), with the dense features in it."""
+    want_u, want_p = rref.hot_layouts(p, HOT_BATCH)
+    got_u, got_p = rd.relations[0].block.layout(), rd.plain.layout()
+    for got, want, dense in ((got_u, want_u, rref.DEMO), (got_p, want_p, rref.PLAIN_HOT)):
+        assert got["hot_pages"] == want["hot_pages"] >= 1 and sorted(got["hot_ids"]) == want["hot_ids"] and sorted(got["hot_ids_all"]) == want["hot_ids_all"]
+        assert set(dense) <= set(got["hot_ids_all"]) and len(set(dense) & set(got["hot_ids"])) >= 2
+        assert got["nnz_sparse_backward"] == want["nnz_sparse_backward"]
+    assert rref.DEMO_UNREFERENCED in got_u["hot_ids"] and rd.plain.n_batches == 4
+    assert rd.relations[1].block.layout()["hot_pages"] == 0          # the item block: single-batch, not asked for by name
+
+
+@pytest.mark.parametrize("loss", ["squared", "logistic"])
+@pytest.mark.parametrize("k", [8, 32, 100])
+@pytest.mark.parametrize("optimizer", ["sgd", "adagrad"])
+def test_hot_block_parts_one_step_vs_twin_and_flat(fmhip, optimizer, k, loss):
+    """base_problem(hot=True): six dense "demographic" features in the user block (built with hot_block=4: the block product reads
+    the block's gathered Pb / eb), three in the plain part (four batches of 100 rows).  One step of every batch against the
+    relational twin and the device's own flat step on expand() against the same twin, at check_step's bounds (test_gpu_weights.py /
+    test_gpu_adagrad.py); the statistics; two runs bit-identical."""
+    p = rref.base_problem(700 + k, k, loss, hot=True)
+    kw = dict(optimizer="adagrad", adagrad_init=0.1) if optimizer == "adagrad" else {}
+    for b in range(4):
+        outs = []
+        for _ in range(2):
+            fm, rd, s0, s1, st, e = one_step(fmhip, p, loss, batch_rows=HOT_BATCH, batch=b, hot_block=4, **kw)
+            outs.append(params(fm) + (get_state(fm) if kw else ()) + (st["sse"], st["sum_e"]))
+            if len(outs) == 2:
+                break
+            assert_hot_parts(rd, p)
+            check_stats(st, e)
+            fl = rd.expand().cache()
+            fm2 = fmhip.FMModel(p["n1"] - 1, k)
+            fm2.w0, fm2.w, fm2.v = p["w0"], p["w"], p["v"]
+            fmhip.HipSGD(eta=ETA, reg0=REGS[0], regw=REGS[1], regv=REGS[2], loss=loss, **kw).step(fm2, fl, b)
+            for model in (fm, fm2):
+                if kw:
+                    check_adagrad_step(model, s0, s1, 0.1, ETA)
+                else:
+                    check_step(model, s0, s1)
+            fl.unpersist()
+            fm2.close()
+            close(rd, fm)
+        close(rd, fm)
+        assert same(outs[0], outs[1]), b
+
+
+@pytest.mark.parametrize("k", [8, 32, 100])
+@pytest.mark.parametrize("optimizer", ["sgd", "adagrad"])
+def test_unreferenced_block_rows_leave_a_hot_feature_untouched(fmhip, optimizer, k):
+    """Feature 99 sits in page 0 of the user block's hot block and only in block rows no data row references: the block product
+    reads exact zeros from Pb / eb there, so its gradient is exactly zero as the twin's is — without decay its v row, its w and (AdaGrad)
+    its accumulators keep every bit, while the other dense features move."""
+    p = rref.base_problem(700 + k, k, "squared", hot=True)
+    f = rref.DEMO_UNREFERENCED
+    assert not np.isin(np.flatnonzero(rref.dense(p["blocks"][0]["row_ptr"], p["blocks"][0]["col"], p["blocks"][0]["val"], p["n1"])[:, f]), p["maps"][0]).any()
+    kw = dict(optimizer="adagrad", adagrad_init=0.1) if optimizer == "adagrad" else {}
+    for b in range(4):
+        fm, rd, s0, s1, st, e = one_step(fmhip, p, "squared", regs=(0.0, 0.0, 0.0), batch_rows=HOT_BATCH, batch=b, hot_block=4, **kw)
+        assert_hot_parts(rd, p)
+        assert s1.w[f] == s0.w[f] and np.array_equal(s1.v[:, f], s0.v[:, f])             # the twin: an exactly zero gradient
+        assert fm.w[f] == np.float32(p["w"][f]) and np.array_equal(fm.v[:, f], p["v"][:, f].astype(np.float32))
+        moved = [g for g in rref.DEMO if g != f]
+        assert (fm.v[:, moved] != p["v"][:, moved].astype(np.float32)).any(axis=0).all()
+        if kw:
+            n0, nw, nv = get_state(fm)
+            assert nw[f] == np.float32(0.1) and (nv[:, f] == np.float32(0.1)).all() and (nv[:, moved] > np.float32(0.1)).any(axis=0).all()
+        close(rd, fm)
 
 
 def test_two_models_take_turns_on_one_handle(fmhip):
