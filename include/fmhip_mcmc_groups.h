@@ -24,7 +24,7 @@
  * slots in a stable order by group, cut into chunks that never straddle a group); the host adds a (g, a)'s partials in chunk order:
  * the result does not depend on the CU count or the launch schedule, and an epoch still has one host sync.
  * Not here: groups for fmhip_als_epoch (sample = 0 through this handle is per-group-regularised ALS), relational / weighted /
- * multi-batch data, per-group regularisation of the SGD learners.
+ * multi-batch data.  (The fp32 SGD path has its own regulariser per feature group, fixed or learned on a validation set: fmhip_sgda.h.)
  */
 #ifndef FMHIP_MCMC_GROUPS_H
 #define FMHIP_MCMC_GROUPS_H

@@ -8,7 +8,7 @@ from .dataset import DataSet, Features  # noqa: F401
 from .relational import Relation, RelationalData  # noqa: F401
 from .metadata import Metadata  # noqa: F401
 from .model import FMModel, Model  # noqa: F401
-from .learn import FMLearn, HipALS, HipBlockMCMC, HipFTRL, HipMCMC, HipSGD  # noqa: F401
+from .learn import FMLearn, HipALS, HipBlockMCMC, HipFTRL, HipMCMC, HipSGD, HipSGDA  # noqa: F401
 from .distributed import HipDataParallelFTRL  # noqa: F401
 from .bpr import HipBPR  # noqa: F401
 from .fm import FM, FactorizationMachines, Task  # noqa: F401
@@ -16,5 +16,5 @@ from .datacollection import DataCollection  # noqa: F401
 from .feature_order import FeatureOrder  # noqa: F401
 from . import fmutils as FMUtils  # noqa: F401
 
-__all__ = ["DataSet", "Features", "FMModel", "Model", "FMLearn", "HipSGD", "HipFTRL", "HipDataParallelFTRL", "HipALS", "HipMCMC", "HipBlockMCMC", "HipBPR", "FM", "FactorizationMachines", "Task",
+__all__ = ["DataSet", "Features", "FMModel", "Model", "FMLearn", "HipSGD", "HipSGDA", "HipFTRL", "HipDataParallelFTRL", "HipALS", "HipMCMC", "HipBlockMCMC", "HipBPR", "FM", "FactorizationMachines", "Task",
            "DataCollection", "FMUtils", "FeatureOrder", "Relation", "RelationalData", "Metadata"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_mcmc_relational.h, include/fmhip_bpr.h, include/fmhip_bpr_adaptive.h, include/fmhip_warp.h, include/fmhip_ftrl.h, include/fmhip_redraw.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_mcmc_relational.h, include/fmhip_bpr.h, include/fmhip_bpr_adaptive.h, include/fmhip_warp.h, include/fmhip_ftrl.h, include/fmhip_redraw.h, include/fmhip_sgda.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -84,6 +84,10 @@ REDRAW_EPOCH, REDRAW_BATCH = 0, 1      # FMHIP_REDRAW_EPOCH, FMHIP_REDRAW_BATCH
 REDRAWS = {"epoch": REDRAW_EPOCH, "batch": REDRAW_BATCH}
 # ... and include/fmhip_ftrl.h — FTRL-Proximal with L1: the third update rule, its state, the model's exact sparsity counts
 SYMBOLS_FTRL = ("fmhip_model_set_ftrl", "fmhip_model_get_ftrl_state", "fmhip_model_set_ftrl_state", "fmhip_model_nonzeros")
+# ... and include/fmhip_sgda.h — SGDA: SGD whose per-group regularisers take gradient steps on a validation set
+SYMBOLS_SGDA = ("fmhip_sgda_create", "fmhip_sgda_destroy", "fmhip_sgda_step", "fmhip_sgda_epoch", "fmhip_sgda_get_lambda",
+                "fmhip_sgda_set_lambda", "fmhip_sgda_last_sums", "fmhip_sgda_info")
+SGDA_MAX_GROUPS = 4096     # FMHIP_SGDA_MAX_GROUPS
 OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
@@ -577,9 +581,17 @@ def load():
     L.fmhip_model_get_ftrl_state.argtypes = [vp, P(dbl), vp, vp, P(dbl), vp, vp]
     L.fmhip_model_set_ftrl_state.argtypes = [vp, dbl, vp, vp, dbl, vp, vp]
     L.fmhip_model_nonzeros.argtypes = [vp, P(i64), P(i64), P(i64)]
+    L.fmhip_sgda_create.argtypes = [vp, vp, i64, i32, dbl, dbl, P(vp)]
+    L.fmhip_sgda_destroy.argtypes = [vp]
+    L.fmhip_sgda_step.argtypes = [vp, vp, i64, vp, i64, dbl, dbl, dbl, P(Stats), P(Stats)]
+    L.fmhip_sgda_epoch.argtypes = [vp, vp, vp, dbl, dbl, dbl, vp, P(Stats), P(Stats)]
+    L.fmhip_sgda_get_lambda.argtypes = [vp, vp, vp]
+    L.fmhip_sgda_set_lambda.argtypes = [vp, vp, vp]
+    L.fmhip_sgda_last_sums.argtypes = [vp, vp, vp]
+    L.fmhip_sgda_info.argtypes = [vp, P(i32), vp, P(i64)]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

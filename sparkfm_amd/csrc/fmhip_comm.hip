@@ -1285,6 +1285,9 @@ int fmhip_dp_plan(fmhip_model_t m, fmhip_dataset_t d, fmhip_comm_t c, int n_frac
     WriteLock lock(m);       // the step changes the model; the communicator is used by the thread that owns its model
     TRY(check_comm(m, c));
     TRY(check_train(m, d));
+    if (m->sgda_handles > 0)
+        return fail(FMHIP_ERR_UNSUPPORTED, "this model has a live SGDA handle (include/fmhip_sgda.h): its per-group regularisers do not travel through the "
+                                           "data-parallel exchanges — destroy the handle first");
     if (n_fractions < 0 || n_fractions > kMaxCuts || (n_fractions > 0 && !upper_fractions))
         return fail(FMHIP_ERR_INVALID, "n_fractions must be 0..%d with an array of as many fractions", kMaxCuts);
     int64_t cuts[kMaxCuts + 1] = {};

@@ -898,6 +898,12 @@ void mcmc_group_plan(const int32_t *cfeat, int64_t n_cols, int64_t num_attribute
         if (cfeat[s] < num_attribute) plan->order[(size_t)at[(size_t)group[cfeat[s]]]++] = (int32_t)s;
 }
 
+void sgda_group_plan(const int32_t *group, int64_t n, int32_t n_groups, int chunk_rows, McmcGroupPlan *plan) {
+    std::vector<int32_t> ids((size_t)n);
+    std::iota(ids.begin(), ids.end(), 0);       // every row is a slot of its own, all of them trained
+    mcmc_group_plan(ids.data(), n, n, group, n_groups, chunk_rows, plan);
+}
+
 double mcmc_truncated_normal(uint64_t seed, uint32_t row, uint32_t t, double a, int *attempts) { return rng::truncated_normal(seed, row, t, a, attempts); }
 double mcmc_truncated_mean(double a) { return rng::truncated_normal_mean(a); }
 

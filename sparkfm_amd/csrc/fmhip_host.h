@@ -287,6 +287,12 @@ struct McmcGroupPlan {
 };
 void mcmc_group_plan(const int32_t *cfeat, int64_t n_cols, int64_t num_attribute, const int32_t *group, int32_t n_groups, int chunk_slots,
                      McmcGroupPlan *plan);
+// ---- the SGDA learner's plan (include/fmhip_sgda.h): the same construction over ALL n feature rows (row i is its own slot) —
+// order holds feature ids, ascending inside a group; counts[a] = the features of group a; an empty group has no chunk.
+// group: n ids, each in [0, n_groups) (checked by the caller: mcmc_bad_group)
+constexpr int kSgdaMaxGroups = 4096;        // FMHIP_SGDA_MAX_GROUPS
+constexpr int kSgdaChunk = 128;             // feature rows per chunk of k_sgda_lambda_partials (a workgroup each: 100 k rows give 782, three per CU)
+void sgda_group_plan(const int32_t *group, int64_t n, int32_t n_groups, int chunk_rows, McmcGroupPlan *plan);
 // ---- ... and its tasks (include/fmhip_mcmc_task.h) ----
 // the probit link's latent draw of a row: z ~ N(0,1) given z > a, counter (row, attempt, t, stream 5); attempts: nullable
 double mcmc_truncated_normal(uint64_t seed, uint32_t row, uint32_t t, double a, int *attempts);

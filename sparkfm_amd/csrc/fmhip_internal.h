@@ -439,6 +439,7 @@ struct fmhip_model {
     // scale itself accumulates no fp32 rounding from step to step.
     double sv = 1.0, sw = 1.0;
     fmhip::host::TrainRule rule;  // how the model trains (the three fmhip_model_set_* calls)
+    int sgda_handles = 0;         // live SGDA handles (include/fmhip_sgda.h) over this model: fmhip_dp_plan refuses it while there is one
     DevBuf<float> yhat;           // paired or weighted training forward: [max_rows] predictions between its two launches
     // AdaGrad: per-coordinate accumulators shaped like the parameters — NV [n1p][Kp] like V (packed rows: slot pack_k holds
     // w_i's), Nw [n1p] (unpacked rows only), N0 [1] — one more copy of the model (8.6 GB at 2^25 x 64); the tables stay at

@@ -118,6 +118,191 @@ class HipFTRL(HipSGD):
         self.last_stats = None
 
 
+class HipSGDA(HipSGD):
+    """``HipSGD`` whose regularisers are learned while it trains (include/fmhip_sgda.h; libFM's ``-method sgda -validation``; Rendle,
+    "Learning recommender systems with adaptive regularization"): a lambda_w per feature group and a lambda_v per (factor, feature
+    group), each stepped after every train batch along the gradient of a held-out batch's loss.  Nothing to grid-search.
+
+        sgda = HipSGDA.run(validation=val, groups=Metadata.fromFields((n_users, n_items)), eta=0.05)
+        fm = FM(train, k, maxIteration=E).learnWith(sgda)
+        sgda.state["lambda_w"], sgda.last_validation_stats
+
+    `validation`: a DataSet made like the train set (it needs its transposes: not ``scoring=True``); step t of the run takes its batch
+    t mod n_batches.  `groups`: None (one group), a ``Metadata`` or an int array with one group id per feature ROW — the model has
+    num_attribute + 1 rows (quirk Q1's spare slot); an array or Metadata exactly one entry short is padded with its last id.
+    `eta_lambda`: the regularisers' step size relative to eta (None: eta, libFM's choice); lambda <- max(0, lambda + eta_lambda eta S).
+    `init_lambda`: where every lambda starts.  ``validation=None`` with ``eta_lambda=0`` is SGD with a FIXED regulariser per group, and
+    `init_lambda` may then also be a pair ``(lambda_w[G], lambda_v[k][G])``.  `reg0` regularises w0 as in ``HipSGD``.
+    `loss`, `shuffle_seed`: as ``HipSGD``.  Plain SGD on single, unweighted rows of a ``DataSet`` only: no AdaGrad / FTRL, no pairs,
+    no ``RelationalData`` (FmhipError, FMHIP_ERR_UNSUPPORTED).  The handle is made by the first ``learn`` / ``step`` for a model and
+    remade when the model changes; ``close()`` frees it."""
+
+    def __init__(self, validation=None, groups=None, eta=0.05, eta_lambda=None, init_lambda=0.0, reg0=0.0, loss="squared", shuffle_seed=None):
+        import math
+        super().__init__(eta=eta, reg0=reg0, shuffle_seed=shuffle_seed, loss=loss)
+        self.eta_lambda = self.eta if eta_lambda is None else float(eta_lambda)
+        if not (math.isfinite(self.eta_lambda) and self.eta_lambda >= 0.0):
+            raise ValueError("eta_lambda must be finite and >= 0, not %r" % (eta_lambda,))
+        if validation is None and self.eta_lambda != 0.0:
+            raise ValueError("eta_lambda = %r needs a validation set: pass validation=, or eta_lambda=0 for fixed per-group regularisation" % self.eta_lambda)
+        if validation is not None and getattr(validation, "scoring", False):
+            raise ValueError("the validation set must keep its transposes: make it without scoring=True")
+        self.validation = validation
+        self.groups, self.n_groups = None, 1
+        if groups is not None:
+            from .metadata import Metadata
+            if isinstance(groups, Metadata):
+                table, n_groups = groups.attrGroup, groups.numAttrGroups
+            else:
+                table = np.asarray(groups)
+                if table.ndim != 1 or (len(table) and not np.issubdtype(table.dtype, np.integer)):
+                    raise TypeError("groups must be a Metadata or a 1-d integer array (one group id per feature row)")
+                if len(table) and table.min() < 0:
+                    raise ValueError("feature %d has group id %d: ids are >= 0" % (int(np.argmin(table)), int(table.min())))
+                n_groups = int(table.max()) + 1 if len(table) else 1
+            if n_groups > _ffi.SGDA_MAX_GROUPS:
+                raise ValueError("%d feature groups: at most %d (FMHIP_SGDA_MAX_GROUPS)" % (n_groups, _ffi.SGDA_MAX_GROUPS))
+            self.groups, self.n_groups = np.ascontiguousarray(table, np.int32), int(n_groups)
+        self._init_pair = None
+        if isinstance(init_lambda, (tuple, list)):
+            if validation is not None or self.eta_lambda != 0.0:
+                raise ValueError("a (lambda_w, lambda_v) pair as init_lambda goes with validation=None and eta_lambda=0 (fixed regularisation)")
+            lw, lv = init_lambda
+            self._init_pair = (np.array(lw, np.float64), np.array(lv, np.float64))
+            self.init_lambda = 0.0
+        else:
+            self.init_lambda = float(init_lambda)
+            if not (math.isfinite(self.init_lambda) and self.init_lambda >= 0.0):
+                raise ValueError("init_lambda must be finite and >= 0, not %r" % (init_lambda,))
+        self._h = None
+        self._for = None            # the model handle's value the SGDA handle was made for
+        self._keep = None
+        self.last_validation_stats = None
+
+    def _handle(self, fm):
+        L = _ffi.load()
+        if self._h is not None and self._for != fm.handle.value:
+            self.close()
+        if self._h is None:
+            n1 = fm.num_attribute + 1
+            if self.groups is None:
+                table = np.zeros(n1, np.int32)
+            elif len(self.groups) == n1 - 1:
+                table = np.ascontiguousarray(np.append(self.groups, self.groups[-1] if n1 > 1 else 0), np.int32)
+            elif len(self.groups) == n1:
+                table = self.groups
+            else:
+                raise ValueError("groups holds %d ids but the model has num_attribute + 1 = %d feature rows" % (len(self.groups), n1))
+            self.rule.set_on(fm.handle)
+            h = C.c_void_p()
+            _ffi.check(L.fmhip_sgda_create(fm.handle, _ffi.ptr(table), n1, self.n_groups, self.init_lambda, self.init_lambda, C.byref(h)))
+            self._h, self._for, self._k, self._keep = h, fm.handle.value, fm.num_factor, fm
+            if self._init_pair is not None:
+                try:
+                    self.set_state(*self._init_pair)
+                except Exception:
+                    self.close()
+                    raise
+        return self._h
+
+    def _data(self, dataset):
+        if isinstance(dataset, RelationalData):
+            raise _ffi.FmhipError(-5, "SGDA does not take relational data yet: expand() it and train on the flat rows, or use HipSGD")
+        return dataset.handle
+
+    def _metric(self, st, fm=None):
+        """A validation stats block -> its dict plus `rmse` over its rows (squared loss: the validation loss, for free) and, for an
+        epoch under the logistic loss, `logloss`: one scoring pass over the validation set after the epoch (the training forward
+        sums residuals, not log-likelihoods)."""
+        d = st.as_dict()
+        d["rmse"] = float(np.sqrt(d["sse"] / d["rows"])) if d["rows"] > 0 else float("nan")
+        if fm is not None and self.loss == "logistic":
+            d["logloss"] = fm.computeLogLoss(self.validation)
+        return d
+
+    def learn(self, fm, dataset):
+        L = _ffi.load()
+        dh = self._data(dataset)
+        self.rule.set_on(fm.handle)
+        h = self._handle(fm)
+        order = self.batch_order(dataset.n_batches)
+        st, sv = _ffi.Stats(), _ffi.Stats()
+        val = self.validation
+        _ffi.check(L.fmhip_sgda_epoch(h, dh, None if val is None else val.handle, self.eta, self.eta_lambda, self.reg0, _ffi.ptr(order),
+                                      C.byref(st), C.byref(sv)))
+        fm._device_updated()
+        self._epoch += 1
+        self.last_stats = st.as_dict()
+        self.last_validation_stats = None if val is None else self._metric(sv, fm)
+        return fm
+
+    def step(self, fm, dataset, batch, val_batch=None, want_stats=True):
+        """A single step (fmhip_sgda_step): train batch `batch`, validation batch `val_batch` (None: the handle's step counter mod the
+        validation set's batches).  -> (train stats, validation stats) dicts, or None."""
+        L = _ffi.load()
+        dh = self._data(dataset)
+        self.rule.set_on(fm.handle)
+        h = self._handle(fm)
+        val = self.validation
+        if val is not None and val_batch is None:
+            val_batch = self.state["steps"] % max(val.n_batches, 1)
+        st, sv = _ffi.Stats(), _ffi.Stats()
+        _ffi.check(L.fmhip_sgda_step(h, dh, batch, None if val is None else val.handle, 0 if val_batch is None else int(val_batch), self.eta,
+                                     self.eta_lambda, self.reg0, C.byref(st) if want_stats else None,
+                                     C.byref(sv) if want_stats and val is not None else None))
+        fm._device_updated()
+        if not want_stats:
+            return None
+        return st.as_dict(), (None if val is None else self._metric(sv))
+
+    def _need(self):
+        if self._h is None:
+            raise RuntimeError("HipSGDA has no handle yet: it is made by the first learn(fm, dataset) or step")
+        return self._h
+
+    @property
+    def state(self):
+        """dict of lambda_w (G,), lambda_v (k, G) and steps (the steps taken: the validation batches' counter)."""
+        h = self._need()
+        lw, lv, steps = np.empty(self.n_groups), np.empty((self._k, self.n_groups)), C.c_int64()
+        _ffi.check(_ffi.load().fmhip_sgda_get_lambda(h, _ffi.ptr(lw), _ffi.ptr(lv)))
+        _ffi.check(_ffi.load().fmhip_sgda_info(h, None, None, C.byref(steps)))
+        return dict(lambda_w=lw, lambda_v=lv, steps=int(steps.value))
+
+    def set_state(self, lambda_w, lambda_v):
+        """lambda_w (G,) and lambda_v (k, G), finite and >= 0 (the library refuses anything else and keeps what it had)."""
+        lw, lv = np.ascontiguousarray(lambda_w, np.float64), np.ascontiguousarray(lambda_v, np.float64)
+        self._need()
+        if lw.shape != (self.n_groups,) or lv.shape != (self._k, self.n_groups):
+            raise ValueError("lambda_w must have shape (%d,) and lambda_v (%d, %d)" % (self.n_groups, self._k, self.n_groups))
+        _ffi.check(_ffi.load().fmhip_sgda_set_lambda(self._h, _ffi.ptr(lw), _ffi.ptr(lv)))
+
+    def last_sums(self):
+        """(S_w (G,), S_v (k, G)) of the last step that had a validation batch, fp64: d(validation loss)/d lambda = -eta S."""
+        h = self._need()
+        sw, sv = np.empty(self.n_groups), np.empty((self._k, self.n_groups))
+        _ffi.check(_ffi.load().fmhip_sgda_last_sums(h, _ffi.ptr(sw), _ffi.ptr(sv)))
+        return sw, sv
+
+    @property
+    def group_counts(self):
+        """int64 [G]: the feature rows of every group."""
+        counts = np.empty(self.n_groups, np.int64)
+        _ffi.check(_ffi.load().fmhip_sgda_info(self._need(), None, _ffi.ptr(counts), None))
+        return counts
+
+    def close(self):
+        if self._h is not None:
+            _ffi.load().fmhip_sgda_destroy(self._h)
+        self._h, self._for, self._keep = None, None, None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HipALS(FMLearn):
     """The reference's own learner on the GPU: one ``learn`` = one ``ALS.learn`` pass
     (S/fm/lib/ALS.scala:15-75) in fp64, using the MODEL's regularisers ``fm.reg0/regw/regv`` as the
