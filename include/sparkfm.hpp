@@ -46,6 +46,7 @@
 #include "fmhip_bpr_adaptive.h"
 #include "fmhip_warp.h"
 #include "fmhip_redraw.h"
+#include "fmhip_proposal.h"
 #include "fmhip_ftrl.h"
 
 namespace sparkfm {
@@ -795,9 +796,12 @@ class HipMCMC : public FMLearn {
 // one the model scores highest at the epoch's start (once per epoch: later batches see slightly stale choices); 1: uniform.
 // sampler: kAuto is that; kWarp (include/fmhip_warp.h) keeps per pair the first of the n_candidates candidates that violates
 // `margin` (>= 0) against the positive and trains a hinge weighted by the rank estimated from the trials — `loss` is then not set.
+// negatives (include/fmhip_proposal.h): kUniform, or kPopularity — candidate row i drawn in proportion to (n_i + smooth)^power, n_i
+// the contexts that list row i; setProposal takes any M weights.
 class HipBPR : public FMLearn {
   public:
     enum Sampler { kAuto = 0, kWarp = 1 };
+    enum Negatives { kUniform = 0, kPopularity = 1 };
     enum Redraw { kEpoch = FMHIP_REDRAW_EPOCH, kBatch = FMHIP_REDRAW_BATCH };      // include/fmhip_redraw.h
     double eta, reg0, regw, regv;
     int loss, optimizer;
@@ -810,7 +814,7 @@ class HipBPR : public FMLearn {
     HipBPR(DataSet &contexts, DataSet &candidates, const std::vector<std::vector<int32_t>> &positives, int32_t n_neg = 1, int64_t batch_pairs = 0,
            uint64_t seed = 0, double eta_ = 0.05, double reg0_ = 0.0, double regw_ = 0.0, double regv_ = 0.0, int loss_ = FMHIP_LOSS_LOGISTIC,
            int optimizer_ = FMHIP_OPT_SGD, double adagrad_eps_ = 1e-10, double adagrad_init_ = 0.1, int32_t n_candidates = 1,
-           int sampler = kAuto, double margin = 1.0, int redraw = kEpoch)
+           int sampler = kAuto, double margin = 1.0, int redraw = kEpoch, int negatives = kUniform, double power = 0.75, double smooth = 1.0)
         : eta(eta_), reg0(reg0_), regw(regw_), regv(regv_), loss(loss_), optimizer(optimizer_), adagrad_eps(adagrad_eps_), adagrad_init(adagrad_init_),
           contexts_(contexts), candidates_(candidates), n_neg_(n_neg), batch_pairs_(batch_pairs), seed_(seed), n_candidates_(n_candidates),
           sampler_(sampler), margin_(margin), redraw_(redraw) {
@@ -829,6 +833,15 @@ class HipBPR : public FMLearn {
                 inter_cand_.push_back(c);
             }
         }
+        if (negatives != kUniform && negatives != kPopularity) throw Error(FMHIP_ERR_INVALID, "negatives must be HipBPR::kUniform or HipBPR::kPopularity");
+        if (negatives == kPopularity) {
+            if (!(smooth > 0.0) || !std::isfinite(smooth) || !std::isfinite(power)) throw Error(FMHIP_ERR_INVALID, "smooth must be > 0, power finite");
+            std::vector<double> n((size_t)candidates.size(), 0.0);
+            for (int32_t c : inter_cand_)
+                if (c >= 0 && (size_t)c < n.size()) n[(size_t)c] += 1.0;
+            for (double &x : n) x = std::pow(x + smooth, power);
+            proposal_ = n;
+        }
     }
     HipBPR(const HipBPR &) = delete;
     HipBPR &operator=(const HipBPR &) = delete;
@@ -840,6 +853,15 @@ class HipBPR : public FMLearn {
     bool warp() const { return sampler_ == kWarp; }
     double margin() const { return margin_; }
     int redraw() const { return redraw_; }
+    const std::vector<double> &proposal() const { return proposal_; }      // empty: uniform
+    // the proposal from the next draw on (fmhip_proposal_set): one weight per candidate row, or an empty vector for uniform
+    void setProposal(const std::vector<double> &weights) {
+        if (!weights.empty() && (int64_t)weights.size() != candidates_.size()) throw Error(FMHIP_ERR_INVALID, "the proposal takes one weight per candidate row");
+        for (double w : weights)
+            if (!(w > 0.0) || !std::isfinite(w)) throw Error(FMHIP_ERR_INVALID, "a proposal weight is finite and > 0");
+        if (h_) check(fmhip_proposal_set(h_, weights.empty() ? nullptr : weights.data()));
+        proposal_ = weights;
+    }
     // the handle borrows the blocks' device copies: made again when either was unpersisted since (FM's fit loop unpersists its dataset)
     fmhip_bpr_t handle() {
         const fmhip_dataset_t c = contexts_.handle(), i = candidates_.handle();
@@ -850,6 +872,7 @@ class HipBPR : public FMLearn {
             if (n_candidates_ > 1) check(fmhip_bpr_set_candidates(h_, n_candidates_));
             if (warp()) check(fmhip_warp_set(h_, 1, margin_));
             if (redraw_ != kEpoch) check(fmhip_redraw_set(h_, redraw_));
+            if (!proposal_.empty()) check(fmhip_proposal_set(h_, proposal_.data()));
             for_ctx_ = c;
             for_cand_ = i;
         }
@@ -940,6 +963,7 @@ class HipBPR : public FMLearn {
     int sampler_;
     double margin_;
     int redraw_;
+    std::vector<double> proposal_;
     int64_t epoch_ = 0;
     fmhip_bpr_t h_ = nullptr;
     fmhip_dataset_t for_ctx_ = nullptr, for_cand_ = nullptr;

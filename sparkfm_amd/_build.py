@@ -25,7 +25,7 @@ HIP_DEPS = ["fm_kernels.h", "fm_weights.h", "fm_relational.h", "fm_bpr.h", "fm_t
             os.path.join("..", "..", "include", "fmhip_mcmc_relational.h"), os.path.join("..", "..", "include", "fmhip_bpr.h"),
             os.path.join("..", "..", "include", "fmhip_bpr_adaptive.h"), os.path.join("..", "..", "include", "fmhip_warp.h"),
             os.path.join("..", "..", "include", "fmhip_ftrl.h"), os.path.join("..", "..", "include", "fmhip_redraw.h"),
-            os.path.join("..", "..", "include", "fmhip_sgda.h")]
+            os.path.join("..", "..", "include", "fmhip_sgda.h"), os.path.join("..", "..", "include", "fmhip_proposal.h")]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result"]
 
 

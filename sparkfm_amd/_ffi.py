@@ -88,6 +88,8 @@ SYMBOLS_FTRL = ("fmhip_model_set_ftrl", "fmhip_model_get_ftrl_state", "fmhip_mod
 SYMBOLS_SGDA = ("fmhip_sgda_create", "fmhip_sgda_destroy", "fmhip_sgda_step", "fmhip_sgda_epoch", "fmhip_sgda_get_lambda",
                 "fmhip_sgda_set_lambda", "fmhip_sgda_last_sums", "fmhip_sgda_info")
 SGDA_MAX_GROUPS = 4096     # FMHIP_SGDA_MAX_GROUPS
+# ... and include/fmhip_proposal.h — what the BPR trainer draws candidate rows from: uniform, or an alias table of M weights
+SYMBOLS_PROPOSAL = ("fmhip_proposal_set", "fmhip_proposal_get", "fmhip_proposal_table")
 OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
@@ -589,9 +591,12 @@ def load():
     L.fmhip_sgda_set_lambda.argtypes = [vp, vp, vp]
     L.fmhip_sgda_last_sums.argtypes = [vp, vp, vp]
     L.fmhip_sgda_info.argtypes = [vp, P(i32), vp, P(i64)]
+    L.fmhip_proposal_set.argtypes = [vp, vp]
+    L.fmhip_proposal_get.argtypes = [vp, P(C.c_int)]
+    L.fmhip_proposal_table.argtypes = [vp, vp, vp]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

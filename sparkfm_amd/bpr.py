@@ -40,14 +40,20 @@ class HipBPR(FMLearn):
     `redraw`: "epoch" (one draw of every pair per ``learn``, one synchronisation for it) or "batch" (include/fmhip_redraw.h): batch
     b's pairs are drawn between batch b's forwards and the rest of its step, the candidate rows being those of the per-epoch draw
     and the scores — hence the choice, and WARP's weights — the current model's; an epoch still synchronises once, at its end.  A
-    uniform sampler trains the same bits in both modes."""
+    uniform sampler trains the same bits in both modes.
+    `negatives`: the proposal every candidate row is drawn from (include/fmhip_proposal.h) — "uniform" (the default: bit for bit what
+    it was), "popularity" (row i in proportion to (n_i + smooth) ** power, n_i the number of contexts whose positives list row i;
+    power = 0.75 is word2vec's noise distribution; `smooth` > 0 keeps every row drawable) or an array of M finite weights > 0.  It
+    composes with every sampler and both redraws: the n_candidates candidates of the best-of and WARP rules come from it too.
+    WARP's rank estimate stays (M - 1) // N.  A fresh handle holds the uniform draw at t = 0 until its first resample or learn."""
 
     SAMPLERS = ("auto", "warp")
     REDRAWS = ("epoch", "batch")
+    NEGATIVES = ("uniform", "popularity")
 
     def __init__(self, contexts, candidates, positives, n_neg=1, batch_pairs=0, seed=0, shuffle=True, eta=0.05, reg0=0.0, regw=0.0,
                  regv=0.0, loss="logistic", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1, n_candidates=1, sampler="auto", margin=1.0,
-                 redraw="epoch"):
+                 redraw="epoch", negatives="uniform", power=0.75, smooth=1.0):
         for what, d in (("contexts", contexts), ("candidates", candidates)):
             if not isinstance(d, DataSet):
                 raise TypeError("%s must be a DataSet, not %s" % (what, type(d).__name__))
@@ -116,6 +122,40 @@ class HipBPR(FMLearn):
         self._epoch = 0
         self.last_stats = None
         self.sample_stats = None
+        self._proposal = None
+        if isinstance(negatives, str):
+            if negatives not in self.NEGATIVES:
+                raise ValueError("negatives must be one of %s, or an array of %d weights, not %r"
+                                 % (", ".join(repr(s) for s in self.NEGATIVES), candidates.size, negatives))
+            if negatives == "popularity":
+                self._proposal = self._checked_weights(self.popularity_weights(power, smooth))
+        else:
+            self._proposal = self._checked_weights(negatives)
+
+    def popularity_weights(self, power=0.75, smooth=1.0):
+        """float64 [M]: (n_i + smooth) ** power, n_i the number of contexts whose positives list row i."""
+        for what, x in (("power", power), ("smooth", smooth)):
+            if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
+                raise ValueError("%s must be a finite number, not %r" % (what, x))
+        if not smooth > 0:
+            raise ValueError("smooth must be > 0 (every row needs a positive weight), not %r" % (smooth,))
+        counts = np.bincount(self.positives_rows, minlength=self.candidates.size).astype(np.float64)
+        return (counts + float(smooth)) ** float(power)
+
+    def _checked_weights(self, weights):
+        """A copy of `weights` as float64 [M], every entry finite and > 0; ValueError otherwise."""
+        if weights is None or isinstance(weights, (str, bytes)):
+            raise ValueError("negatives must be 'uniform', 'popularity' or an array of %d weights, not %r" % (self.candidates.size, weights))
+        w = np.array(weights, np.float64)
+        if w.shape != (self.candidates.size,):
+            raise ValueError("the proposal takes one weight per candidate row: shape (%d,), not %r" % (self.candidates.size, w.shape))
+        bad = np.flatnonzero(~(np.isfinite(w) & (w > 0)))
+        if len(bad):
+            raise ValueError("weights[%d] = %r: a proposal weight is finite and > 0" % (bad[0], float(w[bad[0]])))
+        if not np.isfinite(sum(w.tolist())):
+            raise ValueError("the sum of the weights is not finite")
+        w.setflags(write=False)
+        return w
 
     @classmethod
     def run(cls, contexts, candidates, positives, **kw):
@@ -149,7 +189,31 @@ class HipBPR(FMLearn):
                 _ffi.check(_ffi.load().fmhip_warp_set(h, 1, self._margin))
             if self._redraw != "epoch":
                 _ffi.check(_ffi.load().fmhip_redraw_set(h, _ffi.REDRAWS[self._redraw]))
+            if self._proposal is not None:
+                _ffi.check(_ffi.load().fmhip_proposal_set(h, _ffi.ptr(self._proposal)))
         return self._h
+
+    @property
+    def proposal(self):
+        """None under the uniform proposal, else the float64 [M] weights the candidate rows are drawn in proportion to."""
+        return self._proposal
+
+    def set_proposal(self, weights):
+        """The proposal from the next draw on (fmhip_proposal_set): None for uniform, or M finite weights > 0.  The standing draw is
+        left as it is.  A refusal leaves the proposal that was in force."""
+        w = None if weights is None else self._checked_weights(weights)
+        if self._h is not None:
+            _ffi.check(_ffi.load().fmhip_proposal_set(self._h, _ffi.ptr(w)))
+        self._proposal = w
+
+    def proposal_table(self):
+        """(thresh uint32 [M], alias int32 [M]): the alias table the device draws from (fmhip_proposal_table); the proposal must
+        be a weighted one."""
+        if self._proposal is None:
+            raise ValueError("the proposal is uniform: it has no table")
+        thresh, alias = np.empty(self.candidates.size, np.uint32), np.empty(self.candidates.size, np.int32)
+        _ffi.check(_ffi.load().fmhip_proposal_table(self.handle, _ffi.ptr(thresh), _ffi.ptr(alias)))
+        return thresh, alias
 
     @property
     def n_candidates(self):

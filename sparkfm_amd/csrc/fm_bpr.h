@@ -4,11 +4,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mcmc_rng.h"
+
 namespace fmhip {
 
 // One thread per pair p of [p0, p1): the context of interaction p / n_neg, a row of [0, M) outside the context's positives
 // (rng::negative_row, mcmc_rng.h) into map[2p + 1] — the candidates relation's mapping; map[2p] (the positive) is not touched, and
 // nothing of a pair outside the range.  A whole-set draw passes [0, n_pairs); the grid and the partials are sized by the range.
+// With `tab` set the row comes from the weighted proposal instead (rng::proposal_row): the kernels take the proposal as a
+// compile-time parameter, and the uniform instantiations are the code they were.  The scored samplers' walk draws the same way.
 struct BprSampleArgs {
     uint64_t seed;
     uint32_t t;
@@ -20,6 +24,7 @@ struct BprSampleArgs {
     int32_t *map;              // [2 * n_pairs]
     unsigned long long *part;  // [bpr_sample_blocks(p1 - p0)][2] per-block {attempts, forced pairs}
     unsigned long long *total; // [2] their sums (a second, one-block launch): the caller's slot, one per draw in flight
+    const rng::AliasEntry *tab; // [M] the weighted proposal's alias table (include/fmhip_proposal.h), every alias in [0, M); nullptr: uniform
 };
 int bpr_sample_blocks(int64_t n_pairs);
 hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s);

@@ -4,7 +4,8 @@
 // the same integer code and scores them under the model: the one place with fp32 in it, a dot product whose summation order the row
 // width alone fixes.  What a score does to the pair's choice is the walk's rule: BestOfC (include/fmhip_bpr_adaptive.h) keeps the
 // candidate the model scores highest, FirstViolator (include/fmhip_warp.h) the first one that violates the margin against the pair's
-// positive, with the pair's rank weight beside it.
+// positive, with the pair's rank weight beside it.  Where a candidate row comes from is the proposal (include/fmhip_proposal.h), a
+// compile-time parameter of both samplers: uniform, or an alias table read with one 8-byte load per attempt.
 #include "fm_bpr.h"
 #include "fm_device.h"      // f4dot; grid_blocks (fm_kernels.h)
 #include "mcmc_rng.h"
@@ -40,13 +41,22 @@ __device__ __forceinline__ void block_sums_u64(u64 (&v)[N], u64 *out) {
     }
 }
 
+// One draw of pair p under the proposal: uniform (rng::negative_row) or WEIGHTED (rng::proposal_row: per attempt one dependent
+// 8-byte load of the alias table in front of row_listed's binary search).  group0: the candidate's group offset, c << 4.
+template <bool WEIGHTED>
+__device__ __forceinline__ int32_t draw_row(const BprSampleArgs &s, int64_t p, const int32_t *list, int32_t len, int *at, int *f, uint32_t group0) {
+    if constexpr (WEIGHTED) return rng::proposal_row(s.seed, (uint32_t)p, s.t, (uint32_t)s.M, s.tab, list, len, at, f, group0);
+    else return rng::negative_row(s.seed, (uint32_t)p, s.t, (uint32_t)s.M, list, len, at, f, group0);
+}
+
+template <bool WEIGHTED>
 __global__ __launch_bounds__(kT) void k_bpr_sample(BprSampleArgs a) {
     u64 att = 0, forced = 0;
     for (int64_t p = a.p0 + (int64_t)blockIdx.x * kT + threadIdx.x; p < a.p1; p += (int64_t)gridDim.x * kT) {
         const int32_t u = a.ictx[p / a.n_neg];
         const int64_t lo = a.pptr[u];
         int at = 0, f = 0;
-        a.map[2 * p + 1] = rng::negative_row(a.seed, (uint32_t)p, a.t, (uint32_t)a.M, a.prow + lo, (int32_t)(a.pptr[u + 1] - lo), &at, &f);
+        a.map[2 * p + 1] = draw_row<WEIGHTED>(a, p, a.prow + lo, (int32_t)(a.pptr[u + 1] - lo), &at, &f, 0u);
         att += (u64)at;
         forced += (u64)f;
     }
@@ -163,7 +173,7 @@ struct FirstViolator {
 // G lanes per pair, kT / G pairs per block and pass, over the pairs [s.p0, s.p1) in either mode.  The trip count is the block's
 // (`base` is uniform), and a group whose pair lies past the end works on the range's last pair again and writes nothing: no lane
 // leaves before the block's last shuffle.
-template <int G, class Rule, bool RECORD>
+template <int G, class Rule, bool RECORD, bool WEIGHTED>
 __global__ __launch_bounds__(kT) void k_bpr_sample_walk(typename Rule::Args ra) {
     constexpr int KP = 4 * G, GPB = kT / G;
     const BprAdaptiveArgs &a = Rule::walk_args(ra);
@@ -189,7 +199,7 @@ __global__ __launch_bounds__(kT) void k_bpr_sample_walk(typename Rule::Args ra) 
             int32_t mine = 0;
             if (c0 + l < C) {
                 int at = 0, f = 0;
-                mine = rng::negative_row(a.s.seed, (uint32_t)p, a.s.t, (uint32_t)a.s.M, a.s.prow + lo, len, &at, &f, (uint32_t)(c0 + l) << 4);
+                mine = draw_row<WEIGHTED>(a.s, p, a.s.prow + lo, len, &at, &f, (uint32_t)(c0 + l) << 4);
                 if (live) r.drawn(v, at, f);
             }
             const int n = C - c0 < G ? C - c0 : G;
@@ -225,20 +235,26 @@ __global__ __launch_bounds__(kT) void k_bpr_sample_walk(typename Rule::Args ra) 
 }
 
 // record mode (rec_rows set): the walk alone; else the walk and the one-block sum of its partials
-template <int G, class Rule>
-hipError_t launch_walk(const typename Rule::Args &ra, hipStream_t s) {
+template <int G, class Rule, bool WEIGHTED>
+hipError_t launch_walk_under(const typename Rule::Args &ra, hipStream_t s) {
     const BprAdaptiveArgs &a = Rule::walk_args(ra);
     const bool record = a.rec_rows != nullptr;
     const int blocks = bpr_adaptive_blocks(4 * G, (int64_t)a.s.p1 - a.s.p0);
     if (record) {
-        hipLaunchKernelGGL((k_bpr_sample_walk<G, Rule, true>), dim3((unsigned)blocks), dim3(kT), 0, s, ra);
+        hipLaunchKernelGGL((k_bpr_sample_walk<G, Rule, true, WEIGHTED>), dim3((unsigned)blocks), dim3(kT), 0, s, ra);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((k_bpr_sample_walk<G, Rule, false>), dim3((unsigned)blocks), dim3(kT), 0, s, ra);
+    hipLaunchKernelGGL((k_bpr_sample_walk<G, Rule, false, WEIGHTED>), dim3((unsigned)blocks), dim3(kT), 0, s, ra);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_bpr_total<Rule::N>, dim3(1), dim3(kT), 0, s, a.s.part, blocks, a.s.total);
     return hipGetLastError();
+}
+
+// the proposal picks the instantiation: a table, the weighted one
+template <int G, class Rule>
+hipError_t launch_walk(const typename Rule::Args &ra, hipStream_t s) {
+    return Rule::walk_args(ra).s.tab ? launch_walk_under<G, Rule, true>(ra, s) : launch_walk_under<G, Rule, false>(ra, s);
 }
 
 template <class Rule>
@@ -394,7 +410,8 @@ int bpr_sample_blocks(int64_t n_pairs) { return grid_blocks(n_pairs, kT, 4096); 
 hipError_t launch_bpr_sample(const BprSampleArgs &a, hipStream_t s) {
     if (a.p0 < 0 || a.p1 > a.n_pairs || a.p0 >= a.p1) return hipErrorInvalidValue;
     const int blocks = bpr_sample_blocks((int64_t)a.p1 - a.p0);
-    hipLaunchKernelGGL(k_bpr_sample, dim3((unsigned)blocks), dim3(kT), 0, s, a);
+    if (a.tab) hipLaunchKernelGGL(k_bpr_sample<true>, dim3((unsigned)blocks), dim3(kT), 0, s, a);
+    else hipLaunchKernelGGL(k_bpr_sample<false>, dim3((unsigned)blocks), dim3(kT), 0, s, a);
     BPR_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_bpr_total<2>, dim3(1), dim3(kT), 0, s, a.part, blocks, a.total);
     return hipGetLastError();

@@ -13,6 +13,7 @@
 #include "../../include/fmhip_bpr_adaptive.h"
 #include "../../include/fmhip_warp.h"
 #include "../../include/fmhip_redraw.h"
+#include "../../include/fmhip_proposal.h"
 #include "fm_bpr.h"
 #include "fm_relational.h"
 
@@ -68,6 +69,7 @@ BprSampleArgs sample_args(fmhip_bpr_t h, int64_t t, int64_t p0, int64_t p1, size
     sa.map = h->R->rels[1]->map.p;
     sa.part = h->part.p;
     sa.total = h->total.p + 3 * slot;
+    sa.tab = h->h_ptab.empty() ? nullptr : h->ptab.p;      // (the proposal, include/fmhip_proposal.h: every sampler's draws read it here)
     return sa;
 }
 
@@ -733,6 +735,47 @@ int fmhip_redraw_epoch_stats(fmhip_bpr_t h, fmhip_redraw_stats *out) {
     if (!h->have_epoch_draw)
         return fail(FMHIP_ERR_INVALID, "no per-batch epoch has run: fmhip_redraw_set(h, FMHIP_REDRAW_BATCH), then fmhip_bpr_epoch");
     put_draw(h->epoch_draw, out);
+    return FMHIP_OK;
+}
+
+// ---- the proposal (include/fmhip_proposal.h) --------------------------------------------------------------------------------------------
+
+int fmhip_proposal_set(fmhip_bpr_t h, const double *weights) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    std::vector<rng::AliasEntry> tab;
+    if (weights) {
+        tab.resize((size_t)h->M);
+        const int64_t bad = bpr_alias_table(h->M, weights, tab.data());
+        if (bad == -2) return fail(FMHIP_ERR_INVALID, "the sum of the %lld weights is not finite", (long long)h->M);
+        if (bad >= 0) return fail(FMHIP_ERR_INVALID, "weights[%lld] = %g: a proposal weight is finite and > 0", (long long)bad, weights[bad]);
+    }
+    // the draws queued so far read the table that stands: behind them (the per-batch ones are on the model's stream, in front of
+    // the step that records R->busy)
+    TRY(set_device(h->device));
+    if (h->R->busy_set) HIP_TRY(hipEventSynchronize(h->R->busy));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!tab.empty()) {
+        TRY(h->ptab.ensure(tab.size()));
+        HIP_TRY(hipMemcpy(h->ptab.p, tab.data(), tab.size() * sizeof tab[0], hipMemcpyHostToDevice));
+    }
+    h->h_ptab.swap(tab);
+    return FMHIP_OK;
+}
+
+int fmhip_proposal_get(fmhip_bpr_t h, int *weighted) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (!weighted) return fail(FMHIP_ERR_INVALID, "weighted is NULL");
+    *weighted = h->h_ptab.empty() ? 0 : 1;
+    return FMHIP_OK;
+}
+
+int fmhip_proposal_table(fmhip_bpr_t h, uint32_t *thresh, int32_t *alias) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (h->h_ptab.empty()) return fail(FMHIP_ERR_INVALID, "the proposal is uniform: it has no table (fmhip_proposal_set)");
+    for (size_t i = 0; i < h->h_ptab.size(); ++i) {
+        if (thresh) thresh[i] = h->h_ptab[i].thresh;
+        if (alias) alias[i] = h->h_ptab[i].alias;
+    }
     return FMHIP_OK;
 }
 

@@ -797,6 +797,40 @@ int32_t bpr_negative(uint64_t seed, uint32_t p, uint32_t t, int32_t M, const int
     return bpr_candidate(seed, p, 0, t, M, list, len, attempts, forced);
 }
 
+int64_t bpr_alias_table(int64_t M, const double *weights, rng::AliasEntry *out) {
+    for (int64_t i = 0; i < M; ++i)
+        if (!(weights[i] > 0.0) || !std::isfinite(weights[i])) return i;
+    double sum = 0.0;
+    for (int64_t i = 0; i < M; ++i) sum += weights[i];
+    if (!std::isfinite(sum)) return -2;
+    std::vector<double> q((size_t)M);
+    std::vector<int32_t> small, large;
+    for (int64_t i = 0; i < M; ++i) {
+        q[(size_t)i] = weights[i] / sum * (double)M;
+        (q[(size_t)i] < 1.0 ? small : large).push_back((int32_t)i);
+    }
+    for (int64_t i = 0; i < M; ++i) out[i] = rng::AliasEntry{0xffffffffu, (int32_t)i};
+    while (!small.empty() && !large.empty()) {
+        const int32_t l = small.back(), g = large.back();
+        small.pop_back();
+        large.pop_back();
+        const double scaled = floor(q[(size_t)l] * 4294967296.0);
+        out[l] = rng::AliasEntry{scaled >= 4294967295.0 ? 0xffffffffu : (uint32_t)scaled, g};
+        q[(size_t)g] = (q[(size_t)g] + q[(size_t)l]) - 1.0;
+        (q[(size_t)g] < 1.0 ? small : large).push_back(g);
+    }
+    return -1;
+}
+
+int32_t bpr_proposal_candidate(uint64_t seed, uint32_t p, uint32_t c, uint32_t t, int32_t M, const rng::AliasEntry *tab, const int32_t *list,
+                               int32_t len, int *attempts, int *forced) {
+    int a = 0, f = 0;
+    const int32_t row = rng::proposal_row(seed, p, t, (uint32_t)M, tab, list, len, &a, &f, c << 4);
+    if (attempts) *attempts = a;
+    if (forced) *forced = f;
+    return row;
+}
+
 void warp_weight_table(int64_t M, int C, float *out) {
     out[0] = 0.f;
     double h = 0.0;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "fm_constants.h"
+#include "mcmc_rng.h"      // rng::AliasEntry
 
 namespace fmhip {
 namespace host {
@@ -224,6 +225,18 @@ int32_t bpr_negative(uint64_t seed, uint32_t p, uint32_t t, int32_t M, const int
 // offset by c << 4 — the host twin of k_bpr_sample_walk's draws.  bpr_negative is its c = 0 case.
 int32_t bpr_candidate(uint64_t seed, uint32_t p, uint32_t c, uint32_t t, int32_t M, const int32_t *list, int32_t len, int *attempts,
                       int *forced = nullptr);
+
+// The weighted proposal (include/fmhip_proposal.h).  The alias table of M weights by Vose's method in fp64, in a stated order so
+// that a Python twin gives the same entries: S = the sum of the weights, index ascending; q_i = w_i / S * M; the small list holds
+// the i with q_i < 1 and the large list the others, both index-ascending, both used as stacks (the last entry is taken first).
+// While neither is empty: l = small's last, g = large's last, both taken off; bucket l = {floor(q_l * 2^32) clamped to
+// 2^32 - 1, g}; q_g = (q_g + q_l) - 1; g goes onto small if q_g < 1, else back onto large.  What is left on either list keeps
+// its own row: {2^32 - 1, itself}.  -> -1, or the first row whose weight is not finite and > 0, or -2 when S overflows (out is
+// then not written).
+int64_t bpr_alias_table(int64_t M, const double *weights, rng::AliasEntry *out);
+// Candidate c of pair p under the table: the host twin of the weighted kernels' draws (rng::proposal_row, group0 = c << 4)
+int32_t bpr_proposal_candidate(uint64_t seed, uint32_t p, uint32_t c, uint32_t t, int32_t M, const rng::AliasEntry *tab, const int32_t *list,
+                               int32_t len, int *attempts, int *forced = nullptr);
 
 // WARP (include/fmhip_warp.h).  The weight table: out[0] = 0 and, for n = 1 .. C, out[n] = (float)H(max(1, (M - 1) / n)) with
 // H(r) = sum_{j = 1 .. r} 1 / j in fp64, j ascending — one pass over j = 1 .. M - 1 for all n.  out: C + 1 floats; M >= 2, C >= 1.

@@ -400,6 +400,9 @@ struct fmhip_bpr {
     DevBuf<int32_t> wtrials;
     std::vector<float> h_wtab;
     int32_t wtab_cand = 0;
+    // the proposal (include/fmhip_proposal.h): uniform while h_ptab is empty, else the alias table of M entries on both sides
+    DevBuf<fmhip::rng::AliasEntry> ptab;
+    std::vector<fmhip::rng::AliasEntry> h_ptab;
     ~fmhip_bpr() {
         if (fwd_done) (void)hipEventDestroy(fwd_done);
         if (R) (void)fmhip_relational_destroy(R);

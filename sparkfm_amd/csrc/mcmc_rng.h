@@ -4,7 +4,8 @@
 // normal (include/fmhip_mcmc_task.h), a bounded rejection loop over blocks of a stream of its own.  Integer arithmetic only up
 // to u53; log / cos / sqrt are the caller's libm (host) or the device's (kernel), so host and device normals agree to a
 // few ulp, not bit for bit.  Also here: the BPR trainer's negative rows (include/fmhip_bpr.h; fm_bpr.hip), integer arithmetic
-// throughout, so those agree bit for bit.  No HIP header: g++ compiles it for the sanitizer harnesses.
+// throughout, so those agree bit for bit — under the uniform proposal and under a weighted one (include/fmhip_proposal.h: an alias
+// table the host builds).  No HIP header: g++ compiles it for the sanitizer harnesses.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -109,6 +110,9 @@ FMHIP_RNG_FN double normal_cdf(double x) { return 0.5 * erfc(-x / 1.414213562373
 // ---- the BPR trainer's negative rows (include/fmhip_bpr.h) ------------------------------------------------------------------------
 constexpr int kNegMaxAttempts = 64;
 
+// the block of words a negative's attempts share: counter (p, group, t, kStreamNegative) — the samplers' one site
+FMHIP_RNG_FN Block negative_block(uint64_t seed, uint32_t p, uint32_t group, uint32_t t) { return block_of(seed, p, group, t, kStreamNegative); }
+
 // is row c in the ascending list?
 FMHIP_RNG_FN bool row_listed(const int32_t *list, int32_t len, int32_t c) {
     int32_t lo = 0, hi = len;
@@ -131,7 +135,7 @@ FMHIP_RNG_FN int32_t negative_row(uint64_t seed, uint32_t p, uint32_t t, uint32_
     int32_t c = 0;
     Block b{};
     for (int a = 0; a < kNegMaxAttempts; ++a) {
-        if ((a & 3) == 0) b = block_of(seed, p, group0 | (uint32_t)(a >> 2), t, kStreamNegative);
+        if ((a & 3) == 0) b = negative_block(seed, p, group0 | (uint32_t)(a >> 2), t);
         c = (int32_t)(((uint64_t)b.x[a & 3] * M) >> 32);
         if (!row_listed(list, len, c)) {
             *attempts = a + 1;
@@ -141,6 +145,42 @@ FMHIP_RNG_FN int32_t negative_row(uint64_t seed, uint32_t p, uint32_t t, uint32_
     }
     for (int32_t i = 0; i <= len && row_listed(list, len, c); ++i) c = (uint32_t)(c + 1) == M ? 0 : c + 1;
     *attempts = kNegMaxAttempts;
+    *forced = 1;
+    return c;
+}
+
+// ---- ... drawn from a weighted proposal (include/fmhip_proposal.h) ------------------------------------------------------------------
+constexpr int kPropMaxAttempts = 32;
+
+// one bucket of the alias table (Walker / Vose): 8 bytes, read with one load.  A bucket that is never redirected has alias = its
+// own index, so both sides of the comparison give it and no threshold of 2^32 is needed.
+struct alignas(8) AliasEntry {
+    uint32_t thresh;      // floor(p * 2^32), at most 2^32 - 1: the bucket keeps its own row when the second word is below it
+    int32_t alias;        // the row it gives otherwise, in [0, M)
+};
+
+// negative_row's sibling under a weighted proposal: attempt a = 0 .. 31 takes the words x0 = x[2 (a & 1)], x1 = x[2 (a & 1) + 1] of
+// the block of counter (p, group0 | (a >> 1), t, kStreamNegative) — two attempts a block, 16 blocks a candidate, the c << 4 spacing
+// of the walk — j = (x0 * M) >> 32, c = x1 < tab[j].thresh ? j : tab[j].alias, accepted if c is not listed.  All 32 rejected: the
+// forced walk of negative_row from the last c on; *forced = 1.  *attempts: 1 .. 32.  tab: M entries, every alias in [0, M).
+FMHIP_RNG_FN int32_t proposal_row(uint64_t seed, uint32_t p, uint32_t t, uint32_t M, const AliasEntry *tab, const int32_t *list, int32_t len,
+                                  int *attempts, int *forced, uint32_t group0 = 0) {
+    int32_t c = 0;
+    Block b{};
+    for (int a = 0; a < kPropMaxAttempts; ++a) {
+        if ((a & 1) == 0) b = negative_block(seed, p, group0 | (uint32_t)(a >> 1), t);
+        const uint32_t x0 = (a & 1) ? b.x[2] : b.x[0], x1 = (a & 1) ? b.x[3] : b.x[1];
+        const uint32_t j = (uint32_t)(((uint64_t)x0 * M) >> 32);
+        const AliasEntry e = tab[j];
+        c = x1 < e.thresh ? (int32_t)j : e.alias;
+        if (!row_listed(list, len, c)) {
+            *attempts = a + 1;
+            *forced = 0;
+            return c;
+        }
+    }
+    for (int32_t i = 0; i <= len && row_listed(list, len, c); ++i) c = (uint32_t)(c + 1) == M ? 0 : c + 1;
+    *attempts = kPropMaxAttempts;
     *forced = 1;
     return c;
 }
