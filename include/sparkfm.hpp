@@ -47,6 +47,7 @@
 #include "fmhip_warp.h"
 #include "fmhip_redraw.h"
 #include "fmhip_proposal.h"
+#include "fmhip_softmax.h"
 #include "fmhip_ftrl.h"
 
 namespace sparkfm {
@@ -798,10 +799,14 @@ class HipMCMC : public FMLearn {
 // `margin` (>= 0) against the positive and trains a hinge weighted by the rank estimated from the trials — `loss` is then not set.
 // negatives (include/fmhip_proposal.h): kUniform, or kPopularity — candidate row i drawn in proportion to (n_i + smooth)^power, n_i
 // the contexts that list row i; setProposal takes any M weights.
+// loss = HipBPR::kSoftmax (include/fmhip_softmax.h): the n_neg negatives of an interaction compete in one sampled-softmax loss; the
+// trainer's own rule — the model's loss is not set; not with kWarp; batch_pairs a multiple of n_neg.  logq: the proposal's
+// log-probabilities are subtracted from the logits (ignored under kUniform).
 class HipBPR : public FMLearn {
   public:
     enum Sampler { kAuto = 0, kWarp = 1 };
     enum Negatives { kUniform = 0, kPopularity = 1 };
+    enum { kSoftmax = -1 };      // a value of `loss` beside FMHIP_LOSS_SQUARED / FMHIP_LOSS_LOGISTIC, handled here: never passed to the model
     enum Redraw { kEpoch = FMHIP_REDRAW_EPOCH, kBatch = FMHIP_REDRAW_BATCH };      // include/fmhip_redraw.h
     double eta, reg0, regw, regv;
     int loss, optimizer;
@@ -814,13 +819,15 @@ class HipBPR : public FMLearn {
     HipBPR(DataSet &contexts, DataSet &candidates, const std::vector<std::vector<int32_t>> &positives, int32_t n_neg = 1, int64_t batch_pairs = 0,
            uint64_t seed = 0, double eta_ = 0.05, double reg0_ = 0.0, double regw_ = 0.0, double regv_ = 0.0, int loss_ = FMHIP_LOSS_LOGISTIC,
            int optimizer_ = FMHIP_OPT_SGD, double adagrad_eps_ = 1e-10, double adagrad_init_ = 0.1, int32_t n_candidates = 1,
-           int sampler = kAuto, double margin = 1.0, int redraw = kEpoch, int negatives = kUniform, double power = 0.75, double smooth = 1.0)
+           int sampler = kAuto, double margin = 1.0, int redraw = kEpoch, int negatives = kUniform, double power = 0.75, double smooth = 1.0,
+           bool logq = false)
         : eta(eta_), reg0(reg0_), regw(regw_), regv(regv_), loss(loss_), optimizer(optimizer_), adagrad_eps(adagrad_eps_), adagrad_init(adagrad_init_),
           contexts_(contexts), candidates_(candidates), n_neg_(n_neg), batch_pairs_(batch_pairs), seed_(seed), n_candidates_(n_candidates),
-          sampler_(sampler), margin_(margin), redraw_(redraw) {
+          sampler_(sampler), margin_(margin), redraw_(redraw), logq_(logq) {
         if (sampler != kAuto && sampler != kWarp) throw Error(FMHIP_ERR_INVALID, "sampler must be HipBPR::kAuto or HipBPR::kWarp");
         if (redraw != kEpoch && redraw != kBatch) throw Error(FMHIP_ERR_INVALID, "redraw must be HipBPR::kEpoch or HipBPR::kBatch");
         if (!(margin >= 0.0) || !(margin <= 3.4028234663852886e38)) throw Error(FMHIP_ERR_INVALID, "margin must be a finite number >= 0");
+        if (sampler == kWarp && loss_ == kSoftmax) throw Error(FMHIP_ERR_INVALID, "sampler = kWarp and loss = kSoftmax each train their own rule: choose one");
         if (sampler == kWarp && loss_ != FMHIP_LOSS_LOGISTIC) throw Error(FMHIP_ERR_INVALID, "sampler = kWarp trains its own hinge: leave loss at its default");
         if (n_candidates < 1 || n_candidates > FMHIP_BPR_MAX_CANDIDATES) throw Error(FMHIP_ERR_INVALID, "n_candidates must be in [1, 64]");
         if ((int64_t)positives.size() != contexts.size()) throw Error(FMHIP_ERR_INVALID, "positives must hold one list per context");
@@ -833,6 +840,9 @@ class HipBPR : public FMLearn {
                 inter_cand_.push_back(c);
             }
         }
+        if (softmax() && batch_pairs > 0 && batch_pairs < n_pairs() && batch_pairs % n_neg != 0)
+            throw Error(FMHIP_ERR_INVALID, "loss = kSoftmax: batch_pairs = " + std::to_string(batch_pairs) + " is no multiple of n_neg = " +
+                                               std::to_string(n_neg) + " — a batch would split an interaction's negatives");
         if (negatives != kUniform && negatives != kPopularity) throw Error(FMHIP_ERR_INVALID, "negatives must be HipBPR::kUniform or HipBPR::kPopularity");
         if (negatives == kPopularity) {
             if (!(smooth > 0.0) || !std::isfinite(smooth) || !std::isfinite(power)) throw Error(FMHIP_ERR_INVALID, "smooth must be > 0, power finite");
@@ -851,6 +861,8 @@ class HipBPR : public FMLearn {
     int64_t n_pairs() const { return (int64_t)inter_ctx_.size() * n_neg_; }
     int32_t n_candidates() const { return n_candidates_; }
     bool warp() const { return sampler_ == kWarp; }
+    bool softmax() const { return loss == kSoftmax; }
+    bool ownRule() const { return warp() || softmax(); }      // the step's rule is the trainer's: the model's loss is left as it is
     double margin() const { return margin_; }
     int redraw() const { return redraw_; }
     const std::vector<double> &proposal() const { return proposal_; }      // empty: uniform
@@ -873,6 +885,7 @@ class HipBPR : public FMLearn {
             if (warp()) check(fmhip_warp_set(h_, 1, margin_));
             if (redraw_ != kEpoch) check(fmhip_redraw_set(h_, redraw_));
             if (!proposal_.empty()) check(fmhip_proposal_set(h_, proposal_.data()));
+            if (softmax()) check(fmhip_softmax_set(h_, 1, logq_ ? 1 : 0));
             for_ctx_ = c;
             for_cand_ = i;
         }
@@ -884,7 +897,7 @@ class HipBPR : public FMLearn {
     }
     FMModel &learn(FMModel &fm) {
         const fmhip_bpr_t h = handle();
-        if (!warp()) check(fmhip_model_set_loss(fm.upload(), loss));      // (WARP's hinge: the model's loss is left as it is)
+        if (!ownRule()) check(fmhip_model_set_loss(fm.upload(), loss));
         check(fmhip_model_set_optimizer(fm.upload(), optimizer, adagrad_eps, adagrad_init));
         check(fmhip_bpr_epoch(fm.upload(), h, epoch_, eta, reg0, regw, regv, nullptr, &last_stats));
         if (redraw_ == kBatch) check(fmhip_redraw_epoch_stats(h, &redraw_stats));
@@ -895,7 +908,7 @@ class HipBPR : public FMLearn {
     // one mini-batch step whose pairs are first redrawn at epoch t under the model as it stands (fmhip_redraw_step; either mode)
     const fmhip_stats &step(FMModel &fm, int64_t batch, int64_t t) {
         const fmhip_bpr_t h = handle();
-        if (!warp()) check(fmhip_model_set_loss(fm.upload(), loss));
+        if (!ownRule()) check(fmhip_model_set_loss(fm.upload(), loss));
         check(fmhip_model_set_optimizer(fm.upload(), optimizer, adagrad_eps, adagrad_init));
         check(fmhip_redraw_step(fm.upload(), h, t, batch, eta, reg0, regw, regv, &last_stats, &redraw_stats));
         fm.download();
@@ -942,6 +955,29 @@ class HipBPR : public FMLearn {
         check(fmhip_bpr_negatives(handle(), out.data()));
         return out;
     }
+    // the sampled softmax (include/fmhip_softmax.h): the pairs' probabilities of each batch's last step, the log-Q table (empty
+    // unless the correction is in force), the mean loss and the share of interactions whose positive is on top
+    std::vector<float> softmaxProbs() {
+        std::vector<float> out((size_t)n_pairs());
+        check(fmhip_softmax_probs(handle(), out.data()));
+        return out;
+    }
+    std::vector<float> logq() {
+        if (!softmax() || !logq_ || proposal_.empty()) return {};
+        std::vector<float> out((size_t)candidates_.size());
+        check(fmhip_softmax_logq(handle(), out.data()));
+        return out;
+    }
+    double computeSoftmaxLoss(FMModel &fm) {
+        double loss_ = 0.0;
+        check(fmhip_softmax_loss(fm.upload(), handle(), &loss_, nullptr, nullptr));
+        return loss_;
+    }
+    double computeTop1(FMModel &fm) {
+        double top = 0.0;
+        check(fmhip_softmax_loss(fm.upload(), handle(), nullptr, &top, nullptr));
+        return top;
+    }
     double computePairLogLoss(FMModel &fm) {
         double ll = 0.0;
         check(fmhip_bpr_pair_logloss(fm.upload(), handle(), &ll, nullptr, nullptr));
@@ -963,6 +999,7 @@ class HipBPR : public FMLearn {
     int sampler_;
     double margin_;
     int redraw_;
+    bool logq_;
     std::vector<double> proposal_;
     int64_t epoch_ = 0;
     fmhip_bpr_t h_ = nullptr;

@@ -14,8 +14,8 @@ SYNTH = os.path.join(LIBDIR, "libfmsynth.so")
 
 HIP_SOURCES = ["fm_forward.hip", "fm_backward.hip", "fm_apply.hip", "als_kernels.hip", "csc_build.hip", "fmhip_api.hip", "fmhip_score.hip",
                "fmhip_dataset.hip", "fmhip_step.hip", "fmhip_comm.hip", "fmhip_host.cpp", "fm_topk.hip", "fm_pairing.hip", "fm_auc.hip", "fm_rank.hip", "fm_weights.hip",
-               "fm_relational.hip", "fmhip_relational.hip", "fmhip_mcmc.hip", "fmhip_mcmc_relational.hip", "fm_bpr.hip", "fmhip_bpr.hip", "fm_sgda.hip", "fmhip_sgda.hip"]
-HIP_DEPS = ["fm_kernels.h", "fm_weights.h", "fm_relational.h", "fm_bpr.h", "fm_topk.h", "fm_pair_tiles.h", "fm_rank.h", "fm_pairing.h", "fm_auc.h", "fm_score_key.h", "fm_constants.h", "fm_device.h", "fm_finish.h", "als_kernels.h", "csc_build.h", "fmhip_internal.h", "fmhip_host.h", "mcmc_rng.h", "mcmc_blocks.h", "fmhip_mcmc_handle.h", "fm_sgda.h",
+               "fm_relational.hip", "fmhip_relational.hip", "fmhip_mcmc.hip", "fmhip_mcmc_relational.hip", "fm_bpr.hip", "fmhip_bpr.hip", "fm_sgda.hip", "fmhip_sgda.hip", "fm_softmax.hip"]
+HIP_DEPS = ["fm_kernels.h", "fm_weights.h", "fm_relational.h", "fm_bpr.h", "fm_topk.h", "fm_pair_tiles.h", "fm_rank.h", "fm_pairing.h", "fm_auc.h", "fm_score_key.h", "fm_constants.h", "fm_device.h", "fm_finish.h", "als_kernels.h", "csc_build.h", "fmhip_internal.h", "fmhip_host.h", "mcmc_rng.h", "mcmc_blocks.h", "fmhip_mcmc_handle.h", "fm_sgda.h", "fm_softmax.h",
             os.path.join("..", "..", "include", "fmhip.h"), os.path.join("..", "..", "include", "fmhip_experimental.h"),
             os.path.join("..", "..", "include", "fmhip_topk.h"), os.path.join("..", "..", "include", "fmhip_pairing.h"),
             os.path.join("..", "..", "include", "fmhip_metrics.h"), os.path.join("..", "..", "include", "fmhip_ranking.h"),
@@ -25,7 +25,8 @@ HIP_DEPS = ["fm_kernels.h", "fm_weights.h", "fm_relational.h", "fm_bpr.h", "fm_t
             os.path.join("..", "..", "include", "fmhip_mcmc_relational.h"), os.path.join("..", "..", "include", "fmhip_bpr.h"),
             os.path.join("..", "..", "include", "fmhip_bpr_adaptive.h"), os.path.join("..", "..", "include", "fmhip_warp.h"),
             os.path.join("..", "..", "include", "fmhip_ftrl.h"), os.path.join("..", "..", "include", "fmhip_redraw.h"),
-            os.path.join("..", "..", "include", "fmhip_sgda.h"), os.path.join("..", "..", "include", "fmhip_proposal.h")]
+            os.path.join("..", "..", "include", "fmhip_sgda.h"), os.path.join("..", "..", "include", "fmhip_proposal.h"),
+            os.path.join("..", "..", "include", "fmhip_softmax.h")]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result"]
 
 

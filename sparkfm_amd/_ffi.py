@@ -90,6 +90,8 @@ SYMBOLS_SGDA = ("fmhip_sgda_create", "fmhip_sgda_destroy", "fmhip_sgda_step", "f
 SGDA_MAX_GROUPS = 4096     # FMHIP_SGDA_MAX_GROUPS
 # ... and include/fmhip_proposal.h — what the BPR trainer draws candidate rows from: uniform, or an alias table of M weights
 SYMBOLS_PROPOSAL = ("fmhip_proposal_set", "fmhip_proposal_get", "fmhip_proposal_table")
+# ... and include/fmhip_softmax.h — the sampled softmax over an interaction's n_neg negatives, with the proposal's log-Q correction
+SYMBOLS_SOFTMAX = ("fmhip_softmax_set", "fmhip_softmax_get", "fmhip_softmax_loss", "fmhip_softmax_probs", "fmhip_softmax_logq")
 OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
@@ -594,9 +596,14 @@ def load():
     L.fmhip_proposal_set.argtypes = [vp, vp]
     L.fmhip_proposal_get.argtypes = [vp, P(C.c_int)]
     L.fmhip_proposal_table.argtypes = [vp, vp, vp]
+    L.fmhip_softmax_set.argtypes = [vp, C.c_int, C.c_int]
+    L.fmhip_softmax_get.argtypes = [vp, P(C.c_int), P(C.c_int)]
+    L.fmhip_softmax_loss.argtypes = [vp, vp, P(dbl), P(dbl), P(Stats)]
+    L.fmhip_softmax_probs.argtypes = [vp, vp]
+    L.fmhip_softmax_logq.argtypes = [vp, vp]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

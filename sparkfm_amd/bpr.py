@@ -45,7 +45,12 @@ class HipBPR(FMLearn):
     it was), "popularity" (row i in proportion to (n_i + smooth) ** power, n_i the number of contexts whose positives list row i;
     power = 0.75 is word2vec's noise distribution; `smooth` > 0 keeps every row drawable) or an array of M finite weights > 0.  It
     composes with every sampler and both redraws: the n_candidates candidates of the best-of and WARP rules come from it too.
-    WARP's rank estimate stays (M - 1) // N.  A fresh handle holds the uniform draw at t = 0 until its first resample or learn."""
+    WARP's rank estimate stays (M - 1) // N.  A fresh handle holds the uniform draw at t = 0 until its first resample or learn.
+    `loss="softmax"` (include/fmhip_softmax.h): the n_neg negatives of an interaction compete in one sampled-softmax loss,
+    -log softmax(s+ | s+, s-_1 .. s-_n), instead of forming n_neg independent pairs; at n_neg = 1 it is logistic BPR.  The trainer
+    handles it itself — the model's loss is neither read nor set.  It composes with n_candidates, both redraws and `negatives`, not
+    with sampler="warp"; `batch_pairs` must be a multiple of n_neg.  `logq=True` subtracts the proposal's log-probabilities from the
+    logits (the log-Q correction of a sampled softmax); it is ignored under the uniform proposal."""
 
     SAMPLERS = ("auto", "warp")
     REDRAWS = ("epoch", "batch")
@@ -53,7 +58,7 @@ class HipBPR(FMLearn):
 
     def __init__(self, contexts, candidates, positives, n_neg=1, batch_pairs=0, seed=0, shuffle=True, eta=0.05, reg0=0.0, regw=0.0,
                  regv=0.0, loss="logistic", optimizer="sgd", adagrad_eps=1e-10, adagrad_init=0.1, n_candidates=1, sampler="auto", margin=1.0,
-                 redraw="epoch", negatives="uniform", power=0.75, smooth=1.0):
+                 redraw="epoch", negatives="uniform", power=0.75, smooth=1.0, logq=False):
         for what, d in (("contexts", contexts), ("candidates", candidates)):
             if not isinstance(d, DataSet):
                 raise TypeError("%s must be a DataSet, not %s" % (what, type(d).__name__))
@@ -85,6 +90,12 @@ class HipBPR(FMLearn):
                 or not 0 <= float(margin) <= float(np.finfo(np.float32).max):      # (the device's margin is fp32; a NaN fails both)
             raise ValueError("margin must be a finite number >= 0, not %r" % (margin,))
         self._margin = float(margin)
+        self._softmax = isinstance(loss, str) and loss == "softmax"
+        if not isinstance(logq, (bool, np.bool_)):
+            raise ValueError("logq must be True or False, not %r" % (logq,))
+        self._logq = bool(logq)
+        if sampler == "warp" and self._softmax:
+            raise ValueError("sampler='warp' trains its own hinge and loss='softmax' its own rule: choose one of them")
         if sampler == "warp" and loss != "logistic":
             raise ValueError("sampler='warp' trains its own hinge: leave loss at its default, not %r" % (loss,))
         self.seed = operator.index(seed)
@@ -112,10 +123,14 @@ class HipBPR(FMLearn):
         self.n_pairs = n * self.n_neg
         bp = operator.index(batch_pairs)
         self.batch_pairs = bp if 0 < bp <= self.n_pairs else self.n_pairs
+        if self._softmax and self.batch_pairs < self.n_pairs and self.batch_pairs % self.n_neg:
+            raise ValueError("loss='softmax': batch_pairs = %d is no multiple of n_neg = %d — a batch would split an interaction's negatives"
+                             % (self.batch_pairs, self.n_neg))
         self.shuffle = shuffle
         self.eta, self.reg0, self.regw, self.regv = float(eta), float(reg0), float(regw), float(regv)
         self.loss, self.optimizer = loss, optimizer
-        self._loss_code, self._opt_code = _ffi.loss_code(loss), _ffi.optimizer_code(optimizer)
+        self._loss_code = None if self._softmax else _ffi.loss_code(loss)      # (the softmax is the trainer's own rule, not a model loss)
+        self._opt_code = _ffi.optimizer_code(optimizer)
         self.adagrad_eps, self.adagrad_init = _ffi.adagrad_settings(adagrad_eps, adagrad_init)
         self.device = contexts.device
         self._h, self._for = None, None
@@ -191,6 +206,8 @@ class HipBPR(FMLearn):
                 _ffi.check(_ffi.load().fmhip_redraw_set(h, _ffi.REDRAWS[self._redraw]))
             if self._proposal is not None:
                 _ffi.check(_ffi.load().fmhip_proposal_set(h, _ffi.ptr(self._proposal)))
+            if self._softmax:
+                _ffi.check(_ffi.load().fmhip_softmax_set(h, 1, int(self._logq)))
         return self._h
 
     @property
@@ -363,7 +380,7 @@ class HipBPR(FMLearn):
     def _set_rule(self, fm):
         """The model's loss and optimizer (never its pairing flag: the calls are pairwise by construction)."""
         L = _ffi.load()
-        if not self.warp:      # (WARP trains its own hinge: the model's loss is left as it is)
+        if not self.warp and not self._softmax:      # (WARP and the softmax train their own rule: the model's loss is left as it is)
             _ffi.check(L.fmhip_model_set_loss(fm.handle, self._loss_code))
         _ffi.check(L.fmhip_model_set_optimizer(fm.handle, self._opt_code, self.adagrad_eps, self.adagrad_init))
 
@@ -421,6 +438,44 @@ class HipBPR(FMLearn):
         ll, conc = C.c_double(), C.c_double()
         _ffi.check(_ffi.load().fmhip_bpr_pair_logloss(fm.handle, self.handle, C.byref(ll), C.byref(conc), None))
         return ll.value, conc.value
+
+    @property
+    def softmax(self):
+        """True with loss="softmax"."""
+        return self._softmax
+
+    @property
+    def logq(self):
+        """None unless the log-Q correction is in force (loss="softmax", logq=True, a weighted proposal), else the float32 [M]
+        table log(w_i / sum w) the logits are corrected by (fmhip_softmax_logq)."""
+        if not (self._softmax and self._logq and self._proposal is not None):
+            return None
+        out = np.empty(self.candidates.size, np.float32)
+        _ffi.check(_ffi.load().fmhip_softmax_logq(self.handle, _ffi.ptr(out)))
+        return out
+
+    def softmax_probs(self):
+        """float32 [n_pairs]: the softmax probability of every pair's negative as the last step of its batch left it
+        (fmhip_softmax_probs); every batch must have had a step."""
+        if not self._softmax:
+            raise ValueError("softmax_probs belongs to loss='softmax', not %r" % (self.loss,))
+        out = np.empty(self.n_pairs, np.float32)
+        _ffi.check(_ffi.load().fmhip_softmax_probs(self.handle, _ffi.ptr(out)))
+        return out
+
+    def _softmax_score(self, fm):
+        loss, top1 = C.c_double(), C.c_double()
+        _ffi.check(_ffi.load().fmhip_softmax_loss(fm.handle, self.handle, C.byref(loss), C.byref(top1), None))
+        return loss.value, top1.value
+
+    def computeSoftmaxLoss(self, fm):
+        """Mean over the interactions of -log softmax(s+ | s+, the interaction's n_neg current negatives) (fmhip_softmax_loss),
+        log-Q corrected when the correction is in force."""
+        return self._softmax_score(fm)[0]
+
+    def computeTop1(self, fm):
+        """Share of the interactions whose positive scores strictly above all of its n_neg current negatives."""
+        return self._softmax_score(fm)[1]
 
     def computePairLogLoss(self, fm):
         """Mean -log sigmoid(yhat(u, i+) - yhat(u, i-)) over the current pairs (fmhip_bpr_pair_logloss)."""

@@ -23,12 +23,17 @@ struct PairArgs {
     int32_t pack_k;      // >= 0: packed rows (FwdArgs::pack_k)
     int32_t loss;        // Loss (fm_kernels.h)
     const float *c;      // weighted dataset (fm_weights.h): [2 * n_pairs] the batch's row weights, pair j's = c[2j]; NULL: none
+                         // (kPairLossHinge, kPairLossGiven: the pairs' weights / probabilities in the same layout)
     float margin;        // loss == kPairLossHinge: m
 };
 
 // A third value of PairArgs::loss, internal to the library (fmhip_model_set_loss does not know it): the WARP step's hinge
 // (include/fmhip_warp.h), g = (d < margin) ? -1 : 0 times the pair's weight c[2j] — c is then required.  A NaN d gives g = 0.
 constexpr int32_t kPairLossHinge = 2;
+// A fourth, as internal: the residual is GIVEN, g = -c[2j] (0 where c[2j] is not > 0, the pair's P rows then exact zeros) — the
+// sampled softmax's step (include/fmhip_softmax.h), whose pre-pass (fm_softmax.h) leaves the pairs' probabilities in c.  c is
+// required; y and the margin are not read.
+constexpr int32_t kPairLossGiven = 3;
 
 // n_partials: the launch's grid (slot_blocks, fm_finish.h) = the number of per-block statistic partials it writes (<= kMaxFwdBlocks)
 hipError_t launch_pair_finish(int Kp, const PairArgs &a, hipStream_t s, int *n_partials);

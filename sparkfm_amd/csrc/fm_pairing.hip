@@ -16,7 +16,10 @@ namespace {
 // rows' residuals still sum to exactly zero.  The unweighted instances do not see the pointer.
 // HINGE (the WARP step, fm_pairing.h: kPairLossHinge; always WEIGHTED): g = -1 where d < margin, else 0 — also for a NaN d, which
 // the non-finite count still sees — times the pair's weight.  The other instances do not see the margin.
-template <int LPN, int J, bool PACKED, bool WEIGHTED, bool HINGE = false>
+// GIVEN (the sampled softmax's step, fm_pairing.h: kPairLossGiven): g = -c[2j], formed by the pre-pass (fm_softmax.hip); a pair
+// whose c is not > 0 gets e = 0 and P rows of exact zeros whatever its q rows hold, so an interaction the pre-pass zeroed for a
+// non-finite margin adds nothing anywhere.  The other instances are what they were.
+template <int LPN, int J, bool PACKED, bool WEIGHTED, bool HINGE = false, bool GIVEN = false>
 __global__ __launch_bounds__(kBlock) void k_pair_finish(PairArgs a) {
     constexpr int KP = 4 * LPN * J;
     const SlotLoop<LPN> sl;
@@ -33,12 +36,17 @@ __global__ __launch_bounds__(kBlock) void k_pair_finish(PairArgs a) {
         const float d = yh.x - yh.y, dy = yy.x - yy.y;
         float z;
         float g;
-        if (HINGE) g = d < a.margin ? -1.f : 0.f;
+        if (GIVEN) g = a.c[2 * j] > 0.f ? -a.c[2 * j] : 0.f;
+        else if (HINGE) g = d < a.margin ? -1.f : 0.f;
         else g = logistic ? pair_sigma_residual(d, dy > 0.f, z) : d - dy;
         if (WEIGHTED) g = weighted_residual(a.c[2 * j], g);
         const float e0 = g, e1 = -g;
 #pragma unroll
         for (int jj = 0; jj < J; ++jj) { r0[jj] = f4mul(r0[jj], e0); r1[jj] = f4mul(r1[jj], e1); }
+        if (GIVEN && g == 0.f) {
+#pragma unroll
+            for (int jj = 0; jj < J; ++jj) r0[jj] = r1[jj] = f4zero();
+        }
         store_e_row<LPN, J, PACKED>(p0, r0, e0, l, k);
         store_e_row<LPN, J, PACKED>(p1, r1, e1, l, k);
         if (l == 0) {
@@ -80,12 +88,16 @@ __global__ __launch_bounds__(kBlock) void k_pair_score(const float *yhat, const 
 
 hipError_t launch_pair_finish(int Kp, const PairArgs &a, hipStream_t s, int *n_partials) {
     if (a.loss == kPairLossHinge && (!a.c || !(a.margin >= 0.f))) return hipErrorInvalidValue;
+    if (a.loss == kPairLossGiven && !a.c) return hipErrorInvalidValue;
     const int blocks = slot_blocks(Kp, a.n_pairs);
     if (n_partials) *n_partials = blocks;
     const dim3 g((unsigned)blocks), b(kBlock);
     return for_slot_shape(Kp, [&](auto lpn, auto j) {
         constexpr int L = decltype(lpn)::value, JJ = decltype(j)::value;
-        if (a.loss == kPairLossHinge) {
+        if (a.loss == kPairLossGiven) {
+            if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<L, JJ, true, false, false, true>), g, b, 0, s, a);
+            else hipLaunchKernelGGL((k_pair_finish<L, JJ, false, false, false, true>), g, b, 0, s, a);
+        } else if (a.loss == kPairLossHinge) {
             if (a.pack_k >= 0) hipLaunchKernelGGL((k_pair_finish<L, JJ, true, true, true>), g, b, 0, s, a);
             else hipLaunchKernelGGL((k_pair_finish<L, JJ, false, true, true>), g, b, 0, s, a);
         } else if (a.c) {

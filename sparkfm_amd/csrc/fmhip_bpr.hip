@@ -14,6 +14,7 @@
 #include "../../include/fmhip_warp.h"
 #include "../../include/fmhip_redraw.h"
 #include "../../include/fmhip_proposal.h"
+#include "../../include/fmhip_softmax.h"
 #include "fm_bpr.h"
 #include "fm_relational.h"
 
@@ -289,6 +290,59 @@ void put_draw(const int64_t (&v)[6], fmhip_redraw_stats *out) {
     out->trials = v[5];
 }
 
+// ---- the sampled softmax (include/fmhip_softmax.h) ----
+// the correction is in force: switch and request on, a weighted proposal
+bool logq_in_force(fmhip_bpr_t h) { return h->softmax && h->sm_logq && !h->h_pw.empty(); }
+
+// the log-Q table on both sides as the switch and the proposal now stand (the caller has waited for the steps queued so far)
+int refresh_logq(fmhip_bpr_t h) {
+    h->h_lq.clear();
+    if (!logq_in_force(h)) return FMHIP_OK;
+    h->h_lq.resize((size_t)h->M);
+    bpr_log_proposal(h->M, h->h_pw.data(), h->h_lq.data());
+    TRY(h->lq.ensure(h->h_lq.size()));
+    HIP_TRY(hipMemcpy(h->lq.p, h->h_lq.data(), h->h_lq.size() * sizeof(float), hipMemcpyHostToDevice));
+    return FMHIP_OK;
+}
+
+// every draw and step queued so far has finished (the per-batch ones are on the model's stream, in front of the step that records R->busy)
+int wait_queued(fmhip_bpr_t h) {
+    TRY(set_device(h->device));
+    if (h->R->busy_set) HIP_TRY(hipEventSynchronize(h->R->busy));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return FMHIP_OK;
+}
+
+// a batch splits an interaction: its pairs are no multiple of n_neg (one batch never does)
+bool splits_interactions(fmhip_bpr_t h) { return h->R->batches.size() > 1 && h->batch_pairs % h->n_neg != 0; }
+
+// batch b has had a softmax step: its probabilities stand
+void softmax_mark(fmhip_bpr_t h, int64_t b) {
+    if (!h->softmax) return;
+    h->sm_have.resize(h->R->batches.size(), 0);
+    h->sm_have[(size_t)b] = 1;
+}
+
+// What a step of this handle trains in the model's loss's place: the softmax rule (its buffers sized here), or — `warp_drawn`: the
+// caller vouches for the WARP draw — the WARP hinge on the standing weights; neither switch on: the model's loss (*out = nullptr)
+int step_rule(fmhip_bpr_t h, bool warp_drawn, PairHinge *store, const PairHinge **out) {
+    *out = nullptr;
+    if (h->softmax) {
+        TRY(h->sm_pi.ensure(2 * (size_t)h->n_pairs));
+        TRY(h->sm_bsum.ensure(4 * (size_t)softmax_blocks(h->n_neg, h->R->max_rows / (2 * (int64_t)h->n_neg))));
+        *store = PairHinge{};
+        store->softmax_n = h->n_neg;
+        store->pi = h->sm_pi.p;
+        store->lq = logq_in_force(h) ? h->lq.p : nullptr;
+        store->sm_bsum = h->sm_bsum.p;
+        *out = store;
+    } else if (h->warp && warp_drawn) {
+        *store = PairHinge{h->wc.p, (float)h->warp_margin};
+        *out = store;
+    }
+    return FMHIP_OK;
+}
+
 // One batch of the per-batch redraw (include/fmhip_redraw.h), queued on the model's stream: the blocks' forwards under the model
 // as it stands, the draw of the batch's pairs, the batch's inverse map, the rest of the step with the counts read on the device.
 // WARP: the caller has queued warp_table on the model's stream
@@ -296,13 +350,16 @@ int redraw_batch(fmhip_model_t m, fmhip_bpr_t h, int64_t t, Sampler which, int64
     fmhip_relational_t R = h->R;
     TRY(rel_block_forwards(m, R));
     TRY(queue_draw(h, t, which, m, (size_t)b, (size_t)b + 1, m->stream, false));
-    const PairHinge hinge{h->wc.p, (float)h->warp_margin};
+    PairHinge rule_store{};
+    const PairHinge *rule = nullptr;
+    TRY(step_rule(h, which == kWarp, &rule_store, &rule));
     const int32_t *dev_counts[2] = {nullptr, h->counts.p + 4 * b};
     RelStepQueued queued;
     queued.forwards = true;
     queued.dev_counts = dev_counts;
-    TRY(rel_step(m, R, b, sgd, acc, true, which == kWarp ? &hinge : nullptr, queued));
+    TRY(rel_step(m, R, b, sgd, acc, true, rule, queued));
     if (which == kWarp) warp_mark(h, (size_t)b, (size_t)b + 1, true);
+    softmax_mark(h, b);
     return FMHIP_OK;
 }
 
@@ -337,15 +394,11 @@ int refuse_under_warp(fmhip_bpr_t h, const char *call) {
     return FMHIP_OK;
 }
 
-// the hinge a step of this handle trains: the standing WARP draw's weights and the margin; WARP off: none (*out = nullptr)
+// the rule a step on the STANDING draw trains (step_rule); WARP on without a standing WARP draw: refused
 int step_hinge(fmhip_bpr_t h, PairHinge *store, const PairHinge **out) {
-    *out = nullptr;
-    if (!h->warp) return FMHIP_OK;
-    if (!h->warp_drawn)
+    if (h->warp && !h->warp_drawn)
         return fail(FMHIP_ERR_INVALID, "WARP is on and no WARP draw stands since fmhip_warp_set: call fmhip_warp_resample (or fmhip_bpr_epoch) first");
-    *store = PairHinge{h->wc.p, (float)h->warp_margin};
-    *out = store;
-    return FMHIP_OK;
+    return step_rule(h, true, store, out);
 }
 
 // fmhip_bpr_epoch in the per-batch mode: every batch's forwards, draw, inverse map and step in stream order on the model's stream,
@@ -568,6 +621,8 @@ int fmhip_warp_set(fmhip_bpr_t h, int enabled, double margin) {
     if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
     if (!(margin >= 0.0) || !std::isfinite(margin) || !std::isfinite((float)margin))
         return fail(FMHIP_ERR_INVALID, "margin = %g: the WARP margin is a finite number >= 0", margin);
+    if (enabled && h->softmax)
+        return fail(FMHIP_ERR_INVALID, "fmhip_warp_set: the softmax switch is on for this trainer (fmhip_softmax_set) — WARP trains its own hinge; turn the softmax off first");
     h->warp = enabled != 0;
     h->warp_margin = margin;
     warp_mark(h, 0, 0, false);
@@ -643,6 +698,7 @@ int fmhip_bpr_step(fmhip_model_t m, fmhip_bpr_t h, int64_t batch, double eta, do
     TRY(step_hinge(h, &hinge_store, &hinge));
     TRY(fresh_counts(h));      // (the step sizes its gather from the host's counts)
     TRY(rel_step(m, h->R, batch, Sgd{eta, reg0, regw, regv}, nullptr, true, hinge));
+    softmax_mark(h, batch);
     if (stats) {
         memset(stats, 0, sizeof *stats);
         TRY(read_scal(m, stats));
@@ -670,6 +726,7 @@ int fmhip_bpr_epoch(fmhip_model_t m, fmhip_bpr_t h, int64_t t, double eta, doubl
     int64_t nnz = 0;
     for (int64_t j = 0; j < nb; ++j) {
         TRY(rel_step(m, h->R, order ? order[j] : j, sgd, m->acc.p, true, hinge));
+        softmax_mark(h, order ? order[j] : j);
         nnz += m->step.last_nnz;
     }
     if (stats) {
@@ -751,15 +808,15 @@ int fmhip_proposal_set(fmhip_bpr_t h, const double *weights) {
     }
     // the draws queued so far read the table that stands: behind them (the per-batch ones are on the model's stream, in front of
     // the step that records R->busy)
-    TRY(set_device(h->device));
-    if (h->R->busy_set) HIP_TRY(hipEventSynchronize(h->R->busy));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    TRY(wait_queued(h));
     if (!tab.empty()) {
         TRY(h->ptab.ensure(tab.size()));
         HIP_TRY(hipMemcpy(h->ptab.p, tab.data(), tab.size() * sizeof tab[0], hipMemcpyHostToDevice));
     }
     h->h_ptab.swap(tab);
-    return FMHIP_OK;
+    if (weights) h->h_pw.assign(weights, weights + h->M);
+    else h->h_pw.clear();
+    return refresh_logq(h);      // (the softmax's log-Q table follows the proposal, include/fmhip_softmax.h)
 }
 
 int fmhip_proposal_get(fmhip_bpr_t h, int *weighted) {
@@ -776,6 +833,64 @@ int fmhip_proposal_table(fmhip_bpr_t h, uint32_t *thresh, int32_t *alias) {
         if (thresh) thresh[i] = h->h_ptab[i].thresh;
         if (alias) alias[i] = h->h_ptab[i].alias;
     }
+    return FMHIP_OK;
+}
+
+// ---- the sampled softmax (include/fmhip_softmax.h) -------------------------------------------------------------------------------------
+
+int fmhip_softmax_set(fmhip_bpr_t h, int enabled, int logq) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (enabled && h->warp)
+        return fail(FMHIP_ERR_INVALID, "fmhip_softmax_set: WARP is on for this trainer (fmhip_warp_set) — its hinge is the step's rule; turn WARP off first");
+    if (enabled && splits_interactions(h))
+        return fail(FMHIP_ERR_INVALID, "fmhip_softmax_set: batch_pairs = %lld is no multiple of n_neg = %d — a batch would split an interaction's negatives",
+                    (long long)h->batch_pairs, (int)h->n_neg);
+    TRY(wait_queued(h));      // (the steps queued so far read the table and the probabilities that stand)
+    h->softmax = enabled != 0;
+    h->sm_logq = logq != 0;
+    h->sm_have.assign(h->R->batches.size(), 0);
+    return refresh_logq(h);
+}
+
+int fmhip_softmax_get(fmhip_bpr_t h, int *enabled, int *logq) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (enabled) *enabled = h->softmax ? 1 : 0;
+    if (logq) *logq = h->sm_logq ? 1 : 0;
+    return FMHIP_OK;
+}
+
+int fmhip_softmax_loss(fmhip_model_t m, fmhip_bpr_t h, double *loss, double *top1, fmhip_stats *stats) {
+    ReadLock lock(m);
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (splits_interactions(h))
+        return fail(FMHIP_ERR_INVALID, "fmhip_softmax_loss: batch_pairs = %lld is no multiple of n_neg = %d — a batch splits an interaction's negatives",
+                    (long long)h->batch_pairs, (int)h->n_neg);
+    double sums[2] = {0.0, 0.0};
+    TRY(rel_softmax_score(m, h->R, h->n_neg, logq_in_force(h) ? h->lq.p : nullptr, sums, stats));
+    const double inter = (double)h->n_inter;
+    if (top1) *top1 = sums[0] / inter;
+    if (loss) *loss = sums[1] / inter;
+    return FMHIP_OK;
+}
+
+int fmhip_softmax_probs(fmhip_bpr_t h, float *out) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    if (!h->softmax || h->sm_have.empty() || std::find(h->sm_have.begin(), h->sm_have.end(), (char)0) != h->sm_have.end())
+        return fail(FMHIP_ERR_INVALID, "fmhip_softmax_probs: no softmax probabilities stand — every batch needs a step since fmhip_softmax_set(h, 1, ..)");
+    TRY(wait_queued(h));
+    std::vector<float> c((size_t)(2 * h->n_pairs));
+    HIP_TRY(hipMemcpy(c.data(), h->sm_pi.p, c.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int64_t p = 0; p < h->n_pairs; ++p) out[p] = c[(size_t)(2 * p)];
+    return FMHIP_OK;
+}
+
+int fmhip_softmax_logq(fmhip_bpr_t h, float *out) {
+    if (!h) return fail(FMHIP_ERR_INVALID, "the BPR trainer is NULL");
+    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
+    if (!logq_in_force(h))
+        return fail(FMHIP_ERR_INVALID, "fmhip_softmax_logq: the log-Q correction is not in force (it needs the softmax switch, logq and a weighted proposal)");
+    std::copy(h->h_lq.begin(), h->h_lq.end(), out);
     return FMHIP_OK;
 }
 

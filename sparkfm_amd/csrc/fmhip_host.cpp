@@ -822,6 +822,15 @@ int64_t bpr_alias_table(int64_t M, const double *weights, rng::AliasEntry *out) 
     return -1;
 }
 
+void bpr_log_proposal(int64_t M, const double *weights, float *out) {
+    double sum = 0.0;
+    for (int64_t i = 0; i < M; ++i) sum += weights[i];
+    for (int64_t i = 0; i < M; ++i) {
+        const double r = weights[i] / sum;
+        out[i] = (float)(r > 0.0 ? log(r) : log(weights[i]) - log(sum));      // (a quotient that underflows: still finite)
+    }
+}
+
 int32_t bpr_proposal_candidate(uint64_t seed, uint32_t p, uint32_t c, uint32_t t, int32_t M, const rng::AliasEntry *tab, const int32_t *list,
                                int32_t len, int *attempts, int *forced) {
     int a = 0, f = 0;

@@ -234,6 +234,9 @@ int32_t bpr_candidate(uint64_t seed, uint32_t p, uint32_t c, uint32_t t, int32_t
 // its own row: {2^32 - 1, itself}.  -> -1, or the first row whose weight is not finite and > 0, or -2 when S overflows (out is
 // then not written).
 int64_t bpr_alias_table(int64_t M, const double *weights, rng::AliasEntry *out);
+// The sampled softmax's log-Q table (include/fmhip_softmax.h): out[i] = (float)log(w_i / S) in fp64, S as above.  weights: M doubles
+// that bpr_alias_table has accepted (finite, > 0, a finite sum), so every out[i] is finite and <= 0.
+void bpr_log_proposal(int64_t M, const double *weights, float *out);
 // Candidate c of pair p under the table: the host twin of the weighted kernels' draws (rng::proposal_row, group0 = c << 4)
 int32_t bpr_proposal_candidate(uint64_t seed, uint32_t p, uint32_t c, uint32_t t, int32_t M, const rng::AliasEntry *tab, const int32_t *list,
                                int32_t len, int *attempts, int *forced = nullptr);

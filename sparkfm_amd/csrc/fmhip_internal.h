@@ -11,6 +11,7 @@
 #include "fm_kernels.h"
 #include "fm_pairing.h"      // (PairArgs, RelFinishArgs: the builders the step and the scoring pass share are declared below)
 #include "fm_relational.h"
+#include "fm_softmax.h"      // (SoftmaxArgs: the pre-pass the BPR trainer's softmax step and its scoring pass share)
 #include "fmhip_host.h"   // the pure host arithmetic (shards, relabelling, batch metadata, band plan, ALS levels, the dp plan's cuts and shares)
 
 #include <cmath>
@@ -403,6 +404,15 @@ struct fmhip_bpr {
     // the proposal (include/fmhip_proposal.h): uniform while h_ptab is empty, else the alias table of M entries on both sides
     DevBuf<fmhip::rng::AliasEntry> ptab;
     std::vector<fmhip::rng::AliasEntry> h_ptab;
+    // the sampled softmax (include/fmhip_softmax.h): the switch and the log-Q request, the pairs' probabilities of each batch's
+    // last step (a PairArgs::c over all 2 n_pairs rows) and which batches have had one since the switch was set, the pre-pass's
+    // partials, the proposal's weights as given and — while the correction is in force — log(w_i / sum w) on both sides
+    bool softmax = false, sm_logq = false;
+    DevBuf<float> sm_pi, lq;
+    DevBuf<double> sm_bsum;
+    std::vector<char> sm_have;
+    std::vector<double> h_pw;
+    std::vector<float> h_lq;
     ~fmhip_bpr() {
         if (fwd_done) (void)hipEventDestroy(fwd_done);
         if (R) (void)fmhip_relational_destroy(R);
@@ -577,9 +587,16 @@ int check_rel_model(fmhip_model_t m, fmhip_relational_t R);           // device 
 // BPR trainer): rows 2p / 2p+1 are one example — the finish leaves Q_r and yhat_r, launch_pair_finish forms the residuals
 // hinge (pairs only; the WARP step, include/fmhip_warp.h): the pairs' finish takes the weights' slice c + the batch's first row and
 // the hinge residual at this margin in place of the model's loss; nullptr: the model's loss, unweighted
+// softmax_n > 0 (the sampled softmax's step, include/fmhip_softmax.h) in the hinge's place: between the two finishes the pre-pass
+// (fm_softmax.h) writes the probabilities of the batch's pairs into pi's slice — interactions of softmax_n adjacent pairs, the
+// log-Q table lq (nullable) read through relation 1's mapping, its partials into sm_bsum — and the pairs' finish takes them as given
 struct PairHinge {
     const float *c;      // [2 * n_pairs] over the whole dataset
     float margin;
+    int32_t softmax_n = 0;
+    float *pi = nullptr;         // [2 * n_pairs] over the whole dataset
+    const float *lq = nullptr;
+    double *sm_bsum = nullptr;   // [softmax_blocks of the largest batch][4]
 };
 // queued (the per-batch redraw): rel_block_forwards has been queued for this model state by the caller — the step does not repeat it.
 // dev_counts (nullable; one entry per relation, each nullable): the batch's inverse-map counts {n_touched, n_work, n_long, n_part}
@@ -611,6 +628,9 @@ int rel_q_forwards(fmhip_model_t m, fmhip_relational_t R, const RelBufs &w, hipS
 RelFinishArgs rel_finish_args(fmhip_model_t m, fmhip_relational_t R, const RelBufs &w, const fmhip_relational::Batch &B, int loss);
 // ---- fmhip_score.hip: fmhip_pair_logloss over the rows of a relational dataset without a plain part (the caller holds the model's lock shared)
 int rel_pair_score(fmhip_model_t m, fmhip_relational_t R, double *logloss, double *concordance, fmhip_stats *stats);
+// ... and fmhip_softmax_loss: the rows as interactions of n adjacent pairs (every batch whole ones), lq (nullable) the log-Q table
+// read through relation 1's mapping -> sums[0] = the interactions whose positive is on top, sums[1] = the sum of their losses
+int rel_softmax_score(fmhip_model_t m, fmhip_relational_t R, int32_t n, const float *lq, double *sums, fmhip_stats *stats);
 // the four leading numbers of a statistics block {sum e, sum e^2, rows, rows with a non-finite prediction} (the packed gradient's
 // fp32 head, an fp64 accumulator) into *st; nnz, steps and what a fifth slot means are the caller's
 template <typename T>

@@ -157,7 +157,19 @@ int rel_step(fmhip_model_t m, fmhip_relational_t R, int64_t b, const Sgd &sgd, d
         // the BPR trainer: the finish left Q_r in P and yhat_r beside it, as the flat paired step's kFwdQ forward does; the pairs'
         // finish (fm_pairing.hip) turns them into P_r = Q_r e_r, e and the statistics partials (its own block count)
         PairArgs pa = pair_args(m, R->y.p + B.row0, nullptr, B.rows);
-        if (hinge) {                         // the WARP step: the sampler's weights, the hinge in the model's loss's place
+        if (hinge && hinge->softmax_n > 0) {  // the softmax step: the pre-pass over yhat, then the probabilities taken as given
+            SoftmaxArgs sa{};
+            sa.yhat = m->yhat.p;
+            sa.map = R->rels[1]->map.p + B.row0;
+            sa.lq = hinge->lq;
+            sa.pi = hinge->pi + B.row0;
+            sa.bsum = hinge->sm_bsum;
+            sa.n = hinge->softmax_n;
+            sa.n_inter = (int32_t)(B.rows / (2 * (int64_t)hinge->softmax_n));
+            HIP_TRY(launch_softmax_pre(sa, m->stream, nullptr));
+            pa.c = sa.pi;
+            pa.loss = kPairLossGiven;
+        } else if (hinge) {                  // the WARP step: the sampler's weights, the hinge in the model's loss's place
             pa.c = hinge->c + B.row0;
             pa.loss = kPairLossHinge;
             pa.margin = hinge->margin;

@@ -737,7 +737,11 @@ struct RelScoreBufs {       // (declared before the pass: freed after it has dra
 
 // pair_sums (the BPR trainer; no plain part, even batches): the rows 2j / 2j+1 are scored as pairs — k_pair_score's partials over the
 // predictions the finish left, as fmhip_pair_logloss — and [0] = the concordant pairs, [1] = the sum of the pairs' log-losses
-int rel_score_pass(fmhip_model_t m, fmhip_relational_t R, double *yhat, fmhip_stats *st, double *logloss, double *pair_sums = nullptr) {
+// softmax_n > 0 (with pair_sums; include/fmhip_softmax.h): the pairs as interactions of softmax_n — the softmax pre-pass in its
+// scoring form (fm_softmax.h; lq nullable) in k_pair_score's place, [0] = the interactions with the positive on top, [1] = the
+// sum of the interactions' losses
+int rel_score_pass(fmhip_model_t m, fmhip_relational_t R, double *yhat, fmhip_stats *st, double *logloss, double *pair_sums = nullptr,
+                   int32_t softmax_n = 0, const float *lq = nullptr) {
     TRY(check_rel_model(m, R));
     RelScoreBufs bufs;
     ScorePass pass(m);
@@ -768,7 +772,16 @@ int rel_score_pass(fmhip_model_t m, fmhip_relational_t R, double *yhat, fmhip_st
         const RelFinishArgs fa = rel_finish_args(m, R, w, B, logloss ? kLossLogistic : kLossSquared);
         int parts = 0;
         HIP_TRY(launch_rel_finish(m->Kp, fa, true, cx.s, &parts));
-        if (pair_sums) HIP_TRY(launch_pair_score(cx.yhat.p, R->y.p + B.row0, (int32_t)(B.rows / 2), cx.bsum.p, cx.s, &parts));
+        if (pair_sums && softmax_n > 0) {
+            SoftmaxArgs sa{};
+            sa.yhat = cx.yhat.p;
+            sa.map = R->rels[1]->map.p + B.row0;
+            sa.lq = lq;
+            sa.bsum = cx.bsum.p;
+            sa.n = softmax_n;
+            sa.n_inter = (int32_t)(B.rows / (2 * (int64_t)softmax_n));
+            HIP_TRY(launch_softmax_pre(sa, cx.s, &parts));
+        } else if (pair_sums) HIP_TRY(launch_pair_score(cx.yhat.p, R->y.p + B.row0, (int32_t)(B.rows / 2), cx.bsum.p, cx.s, &parts));
         HIP_TRY(launch_reduce_blocks(cx.bsum.p, parts, (int32_t)B.rows, nullptr, cx.acc.p, cx.s, logloss != nullptr || pair_sums != nullptr));
         if (yhat) TRY(pass.copy_back(cx.yhat.p, B.rows, 1, 1, hbuf, yhat + B.row0));
     }
@@ -800,6 +813,16 @@ int rel_pair_score(fmhip_model_t m, fmhip_relational_t R, double *logloss, doubl
     if (stats) {
         *stats = st;
         stats->sum_e = 0.0;        // e_2j = -e_2j+1
+    }
+    return FMHIP_OK;
+}
+
+int rel_softmax_score(fmhip_model_t m, fmhip_relational_t R, int32_t n, const float *lq, double *sums, fmhip_stats *stats) {
+    fmhip_stats st;
+    TRY(rel_score_pass(m, R, nullptr, &st, nullptr, sums, n, lq));
+    if (stats) {
+        *stats = st;
+        stats->sum_e = 0.0;        // e_2p = -e_2p+1
     }
     return FMHIP_OK;
 }
