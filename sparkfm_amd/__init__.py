@@ -11,10 +11,12 @@ from .model import FMModel, Model  # noqa: F401
 from .learn import FMLearn, HipALS, HipBlockMCMC, HipFTRL, HipMCMC, HipSGD, HipSGDA  # noqa: F401
 from .distributed import HipDataParallelFTRL  # noqa: F401
 from .bpr import HipBPR  # noqa: F401
+from .ffm import FFM, FFMDataSet, FFMModel, HipFFM  # noqa: F401
 from .fm import FM, FactorizationMachines, Task  # noqa: F401
 from .datacollection import DataCollection  # noqa: F401
 from .feature_order import FeatureOrder  # noqa: F401
 from . import fmutils as FMUtils  # noqa: F401
 
 __all__ = ["DataSet", "Features", "FMModel", "Model", "FMLearn", "HipSGD", "HipSGDA", "HipFTRL", "HipDataParallelFTRL", "HipALS", "HipMCMC", "HipBlockMCMC", "HipBPR", "FM", "FactorizationMachines", "Task",
-           "DataCollection", "FMUtils", "FeatureOrder", "Relation", "RelationalData", "Metadata"]
+           "DataCollection", "FMUtils", "FeatureOrder", "Relation", "RelationalData", "Metadata",
+           "FFM", "FFMDataSet", "FFMModel", "HipFFM"]

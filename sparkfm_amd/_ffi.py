@@ -1,4 +1,4 @@
-"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_mcmc_relational.h, include/fmhip_bpr.h, include/fmhip_bpr_adaptive.h, include/fmhip_warp.h, include/fmhip_ftrl.h, include/fmhip_redraw.h, include/fmhip_sgda.h) a JNI shim would bind.
+"""ctypes binding of libfmhip.so — the same C ABI (include/fmhip.h, include/fmhip_experimental.h, include/fmhip_topk.h, include/fmhip_pairing.h, include/fmhip_metrics.h, include/fmhip_ranking.h, include/fmhip_weights.h, include/fmhip_relational.h, include/fmhip_mcmc.h, include/fmhip_mcmc_task.h, include/fmhip_mcmc_groups.h, include/fmhip_mcmc_relational.h, include/fmhip_bpr.h, include/fmhip_bpr_adaptive.h, include/fmhip_warp.h, include/fmhip_ftrl.h, include/fmhip_redraw.h, include/fmhip_sgda.h, include/fmhip_ffm.h) a JNI shim would bind.
 
 There is NO CPU fallback: if the HIP library is missing this module raises, loudly.
 """
@@ -92,6 +92,12 @@ SGDA_MAX_GROUPS = 4096     # FMHIP_SGDA_MAX_GROUPS
 SYMBOLS_PROPOSAL = ("fmhip_proposal_set", "fmhip_proposal_get", "fmhip_proposal_table")
 # ... and include/fmhip_softmax.h — the sampled softmax over an interaction's n_neg negatives, with the proposal's log-Q correction
 SYMBOLS_SOFTMAX = ("fmhip_softmax_set", "fmhip_softmax_get", "fmhip_softmax_loss", "fmhip_softmax_probs", "fmhip_softmax_logq")
+# ... and include/fmhip_ffm.h — the field-aware FM: a model, a dataset and kernels of their own
+SYMBOLS_FFM = ("fmhip_ffm_model_create", "fmhip_ffm_model_destroy", "fmhip_ffm_model_info", "fmhip_ffm_model_set_params",
+               "fmhip_ffm_model_get_params", "fmhip_ffm_model_set_rule", "fmhip_ffm_model_set_linear", "fmhip_ffm_model_get_accumulators",
+               "fmhip_ffm_model_set_accumulators", "fmhip_ffm_dataset_create", "fmhip_ffm_dataset_destroy", "fmhip_ffm_dataset_info",
+               "fmhip_ffm_predict", "fmhip_ffm_step", "fmhip_ffm_epoch")
+FFM_MAX_FIELDS, FFM_MAX_FACTORS, FFM_MAX_ROW = 64, 16, 64      # FMHIP_FFM_MAX_FIELDS, FMHIP_FFM_MAX_FACTORS, FMHIP_FFM_MAX_ROW
 OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
@@ -601,9 +607,24 @@ def load():
     L.fmhip_softmax_loss.argtypes = [vp, vp, P(dbl), P(dbl), P(Stats)]
     L.fmhip_softmax_probs.argtypes = [vp, vp]
     L.fmhip_softmax_logq.argtypes = [vp, vp]
+    L.fmhip_ffm_model_create.argtypes = [C.c_int, i64, i32, i32, vp, P(vp)]
+    L.fmhip_ffm_model_destroy.argtypes = [vp]
+    L.fmhip_ffm_model_info.argtypes = [vp, P(i64), P(i32), P(i32), P(i32)]
+    L.fmhip_ffm_model_set_params.argtypes = [vp, dbl, vp, vp]
+    L.fmhip_ffm_model_get_params.argtypes = [vp, P(dbl), vp, vp]
+    L.fmhip_ffm_model_set_rule.argtypes = [vp, C.c_int, C.c_int, dbl, dbl]
+    L.fmhip_ffm_model_set_linear.argtypes = [vp, C.c_int]
+    L.fmhip_ffm_model_get_accumulators.argtypes = [vp, P(dbl), vp, vp]
+    L.fmhip_ffm_model_set_accumulators.argtypes = [vp, dbl, vp, vp]
+    L.fmhip_ffm_dataset_create.argtypes = [C.c_int, i64, vp, vp, vp, vp, vp, i64, P(vp)]
+    L.fmhip_ffm_dataset_destroy.argtypes = [vp]
+    L.fmhip_ffm_dataset_info.argtypes = [vp, P(i64), P(i64), P(i64), P(i32), P(i32), P(i64), P(i64)]
+    L.fmhip_ffm_predict.argtypes = [vp, vp, vp]
+    L.fmhip_ffm_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, P(Stats)]
+    L.fmhip_ffm_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, vp, P(Stats)]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

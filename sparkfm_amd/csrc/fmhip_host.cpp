@@ -1004,5 +1004,120 @@ int64_t mcmc_block_trained(const int32_t *cfeat, const int32_t *cptr, const uint
     return count;
 }
 
+// ---- field-aware FM (include/fmhip_ffm.h) ----
+
+FfmCheck ffm_validate(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const int32_t *field, const double *val) {
+    FfmCheck c;
+    auto bad = [&](int kind, int64_t row, int64_t entry) {
+        c.kind = kind;
+        c.row = row;
+        c.entry = entry;
+        return c;
+    };
+    if (n_rows > 0 && row_ptr[0] != 0) return bad(kFfmBadRowPtr, 0, -1);
+    int32_t seen[kFfmMaxRow];
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const int64_t lo = row_ptr[r], hi = row_ptr[r + 1];
+        if (hi < lo) return bad(kFfmBadRowPtr, r, -1);
+        if (hi - lo > kFfmMaxRow) return bad(kFfmRowTooLong, r, -1);
+        for (int64_t p = lo; p < hi; ++p)
+            if (col[p] < 0) return bad(kFfmBadFeature, r, p);
+        for (int64_t p = lo; p < hi; ++p)
+            if (field[p] < 0 || field[p] >= kFfmMaxFields) return bad(kFfmBadField, r, p);
+        for (int64_t p = lo; p < hi; ++p)
+            if (!std::isfinite((float)val[p])) return bad(kFfmBadValue, r, p);
+        const int len = (int)(hi - lo);
+        for (int j = 0; j < len; ++j) {
+            for (int t = 0; t < j; ++t)
+                if (seen[t] == col[lo + j]) return bad(kFfmDupFeature, r, lo + j);
+            seen[j] = col[lo + j];
+            c.dim = std::max(c.dim, col[lo + j]);
+            c.fields = std::max(c.fields, field[lo + j] + 1);
+        }
+        c.max_len = std::max(c.max_len, (int32_t)len);
+    }
+    return c;
+}
+
+void ffm_build(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const int32_t *field, const double *val, int64_t batch_rows, int chunk,
+               FfmLayout *out) {
+    FfmLayout &L = *out;
+    L = FfmLayout();
+    const int64_t nnz = n_rows > 0 ? row_ptr[n_rows] : 0;
+    L.col.resize((size_t)nnz);
+    L.field.resize((size_t)nnz);
+    L.run.assign((size_t)nnz, 0);
+    L.val.resize((size_t)nnz);
+    L.occ_row.resize((size_t)nnz);
+    L.occ_pos.resize((size_t)nnz);
+    // rows: the stable sort by (field, feature), then the run heads
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const int64_t lo = row_ptr[r];
+        const int len = (int)(row_ptr[r + 1] - lo);
+        int idx[kFfmMaxRow];
+        for (int j = 0; j < len; ++j) idx[j] = j;
+        std::stable_sort(idx, idx + len, [&](int x, int y) {
+            return field[lo + x] != field[lo + y] ? field[lo + x] < field[lo + y] : col[lo + x] < col[lo + y];
+        });
+        for (int j = 0; j < len; ++j) {
+            L.col[(size_t)(lo + j)] = col[lo + idx[j]];
+            L.field[(size_t)(lo + j)] = (uint8_t)field[lo + idx[j]];
+            L.val[(size_t)(lo + j)] = (float)val[lo + idx[j]];
+        }
+        for (int j = 0; j < len;) {
+            int e = j + 1;
+            while (e < len && L.field[(size_t)(lo + e)] == L.field[(size_t)(lo + j)]) ++e;
+            L.run[(size_t)(lo + j)] = (uint8_t)(e - j);
+            j = e;
+        }
+    }
+    // batches: the transpose by a sort of (feature, entry) keys — ascending entries of one feature are ascending rows — and the cuts
+    if (batch_rows <= 0 || batch_rows > n_rows) batch_rows = n_rows;
+    std::vector<uint64_t> keys;
+    for (int64_t row0 = 0; row0 < n_rows; row0 += batch_rows) {
+        FfmBatch b;
+        b.row0 = row0;
+        b.rows = std::min(batch_rows, n_rows - row0);
+        b.nnz0 = row_ptr[row0];
+        b.nnz = (int32_t)(row_ptr[row0 + b.rows] - b.nnz0);
+        b.col_off = (int64_t)L.cfeat.size();
+        b.cptr_off = (int64_t)L.cptr.size();
+        b.chunk_off = (int64_t)L.chunk_col.size();
+        keys.resize((size_t)b.nnz);
+        for (int32_t p = 0; p < b.nnz; ++p) keys[(size_t)p] = ((uint64_t)(uint32_t)L.col[(size_t)(b.nnz0 + p)] << 32) | (uint32_t)p;
+        std::sort(keys.begin(), keys.end());
+        int64_t r = row0;
+        std::vector<int32_t> row_of((size_t)b.nnz);
+        for (int32_t p = 0; p < b.nnz; ++p) {
+            while (row_ptr[r + 1] <= b.nnz0 + p) ++r;
+            row_of[(size_t)p] = (int32_t)(r - row0);
+        }
+        for (int64_t q = row0; q < row0 + b.rows; ++q) b.max_len = std::max(b.max_len, (int32_t)(row_ptr[q + 1] - row_ptr[q]));
+        for (int32_t o = 0; o < b.nnz; ++o) {
+            const int32_t feat = (int32_t)(keys[(size_t)o] >> 32), p = (int32_t)(keys[(size_t)o] & 0xffffffffu);
+            if (o == 0 || feat != L.cfeat.back()) {
+                if (b.n_cols > 0) b.n_chunks += (o - L.cptr.back() + chunk - 1) / chunk;
+                L.cfeat.push_back(feat);
+                L.cptr.push_back(o);
+                L.chunk0.push_back(b.n_chunks);
+                ++b.n_cols;
+            }
+            L.occ_row[(size_t)(b.nnz0 + o)] = row_of[(size_t)p];
+            L.occ_pos[(size_t)(b.nnz0 + o)] = (uint8_t)(b.nnz0 + p - row_ptr[row0 + row_of[(size_t)p]]);
+        }
+        if (b.n_cols > 0) b.n_chunks += (b.nnz - L.cptr.back() + chunk - 1) / chunk;
+        L.cptr.push_back(b.nnz);
+        L.chunk0.push_back(b.n_chunks);
+        for (int32_t c = 0; c < b.n_cols; ++c) {
+            const int32_t n = L.chunk0[(size_t)(b.cptr_off + c + 1)] - L.chunk0[(size_t)(b.cptr_off + c)];
+            L.chunk_col.insert(L.chunk_col.end(), (size_t)n, c);
+        }
+        L.max_rows = std::max(L.max_rows, b.rows);
+        L.max_cols = std::max(L.max_cols, b.n_cols);
+        L.max_chunks = std::max(L.max_chunks, b.n_chunks);
+        L.batches.push_back(b);
+    }
+}
+
 }  // namespace host
 }  // namespace fmhip

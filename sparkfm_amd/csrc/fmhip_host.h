@@ -334,5 +334,48 @@ void mcmc_block_counts(const int32_t *map, int64_t n_rows, int64_t block_rows, s
 int64_t mcmc_block_trained(const int32_t *cfeat, const int32_t *cptr, const uint32_t *crow, int64_t n_cols, int64_t num_attribute, const double *n,
                            std::vector<int32_t> &trained);
 
+// ---- field-aware FM (include/fmhip_ffm.h): the dataset build ----
+constexpr int kFfmMaxFields = 64;           // FMHIP_FFM_MAX_FIELDS (a wave's touched-fields mask is one 64-bit word)
+constexpr int kFfmMaxFactors = 16;          // FMHIP_FFM_MAX_FACTORS
+constexpr int kFfmMaxRow = 64;              // FMHIP_FFM_MAX_ROW: entries per data row (a lane each)
+constexpr int kFfmChunk = 256;              // occurrences per chunk of a column's list (a wave of k_ffm_backward each)
+// the first offence in row order, and inside a row in this order of kinds; entry: its index in col / field / val (kFfmBadRowPtr,
+// kFfmRowTooLong: -1).  dim = the largest feature id, fields = the largest field id + 1, max_len = the longest row (of valid
+// data: not meaningful beside an offence)
+enum FfmBad { kFfmOk = 0, kFfmBadRowPtr, kFfmRowTooLong, kFfmBadFeature, kFfmBadField, kFfmBadValue, kFfmDupFeature };
+struct FfmCheck {
+    int kind = kFfmOk;
+    int64_t row = -1, entry = -1;
+    int32_t dim = 0, fields = 0, max_len = 0;
+};
+// row_ptr[0] == 0 and never decreasing, rows of at most kFfmMaxRow entries, feature ids >= 0, field ids in [0, kFfmMaxFields), values
+// finite as the fp32 they are stored as, no feature id twice in a row
+FfmCheck ffm_validate(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const int32_t *field, const double *val);
+// One mini-batch of the layout: rows [row0, row0 + rows), entries [nnz0, nnz0 + nnz) of the entry arrays AND of the occurrence arrays;
+// n_cols features present: cfeat[col_off ..] ascending, cptr / chunk0 [cptr_off .. cptr_off + n_cols] (cptr: batch-local occurrence
+// offsets; chunk0: batch-local chunk offsets); n_chunks chunks: chunk_col[chunk_off ..] = the chunk's batch-local column
+struct FfmBatch {
+    int64_t row0 = 0, rows = 0, nnz0 = 0, col_off = 0, cptr_off = 0, chunk_off = 0;
+    int32_t nnz = 0, n_cols = 0, n_chunks = 0, max_len = 0;
+};
+// The device layout of an FFM dataset, built once on the host (validated input: ffm_validate).
+//   rows: every row's entries stably sorted by (field, feature) under the caller's row_ptr; run[p] = the length of the same-field
+//         run entry p heads, 0 for an entry that heads none
+//   per batch the transpose: for every feature present its occurrences (batch-local row, position in the sorted row) in ascending
+//         row order, each column's list cut into chunks of `chunk` occurrences (chunk j of column c: occurrences
+//         [cptr[c] + chunk * (j - chunk0[c]), min(.. + chunk, cptr[c + 1])))
+struct FfmLayout {
+    std::vector<int32_t> col;
+    std::vector<uint8_t> field, run;
+    std::vector<float> val;
+    std::vector<FfmBatch> batches;
+    std::vector<int32_t> cfeat, cptr, chunk0, chunk_col, occ_row;
+    std::vector<uint8_t> occ_pos;
+    int64_t max_rows = 0;
+    int32_t max_cols = 0, max_chunks = 0;
+};
+void ffm_build(int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const int32_t *field, const double *val, int64_t batch_rows, int chunk,
+               FfmLayout *out);
+
 }  // namespace host
 }  // namespace fmhip

@@ -37,6 +37,28 @@ def loadLibFMFile(path, numFeatures=-1, **dataset_kw):
                    **dataset_kw)
 
 
+def loadLibFFMFile(path, **dataset_kw):
+    """libffm's text format, `label field:feature:value field:feature:value ...`: lines trimmed, empty lines and lines starting with
+    '#' skipped, items split on single spaces, ids kept as written (0-based) -> FFMDataSet (its keywords: batch_rows, normalize, device)."""
+    from .ffm import FFMDataSet
+    ys, rows = [], []
+    with open(path) as fh:
+        for line in fh:
+            line = line.strip()
+            if not line or line.startswith("#"):
+                continue
+            items = line.split(" ")
+            ys.append(float(items[0]))
+            row = []
+            for item in items[1:]:
+                if not item:
+                    continue
+                f, i, v = item.split(":")
+                row.append((int(f), int(i), float(v)))
+            rows.append(row)
+    return FFMDataSet.from_rows(rows, np.asarray(ys, np.float64), **dataset_kw)
+
+
 def minimizeString(v):
     """S/fm/FMUtils.scala:71-74: java.text.DecimalFormat("#") for integral values, "#.###" otherwise
     (HALF_EVEN, no trailing zeros, and — DecimalFormat semantics — no leading zero: 0.5 -> ".5")."""
