@@ -98,6 +98,12 @@ SYMBOLS_FFM = ("fmhip_ffm_model_create", "fmhip_ffm_model_destroy", "fmhip_ffm_m
                "fmhip_ffm_model_set_accumulators", "fmhip_ffm_dataset_create", "fmhip_ffm_dataset_destroy", "fmhip_ffm_dataset_info",
                "fmhip_ffm_predict", "fmhip_ffm_step", "fmhip_ffm_epoch")
 FFM_MAX_FIELDS, FFM_MAX_FACTORS, FFM_MAX_ROW = 64, 16, 64      # FMHIP_FFM_MAX_FIELDS, FMHIP_FFM_MAX_FACTORS, FMHIP_FFM_MAX_ROW
+# ... and include/fmhip_fwfm.h — the field-weighted FM: a model and kernels of its own over the FFM's dataset handle
+SYMBOLS_FWFM = ("fmhip_fwfm_model_create", "fmhip_fwfm_model_destroy", "fmhip_fwfm_model_info", "fmhip_fwfm_model_set_params",
+                "fmhip_fwfm_model_get_params", "fmhip_fwfm_model_set_rule", "fmhip_fwfm_model_set_linear", "fmhip_fwfm_model_set_field_weights",
+                "fmhip_fwfm_model_get_accumulators", "fmhip_fwfm_model_set_accumulators", "fmhip_fwfm_predict", "fmhip_fwfm_step",
+                "fmhip_fwfm_epoch")
+FWFM_MAX_FIELDS, FWFM_MAX_FACTORS = 64, 32      # FMHIP_FWFM_MAX_FIELDS, FMHIP_FWFM_MAX_FACTORS
 OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
@@ -622,9 +628,22 @@ def load():
     L.fmhip_ffm_predict.argtypes = [vp, vp, vp]
     L.fmhip_ffm_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, P(Stats)]
     L.fmhip_ffm_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, vp, P(Stats)]
+    L.fmhip_fwfm_model_create.argtypes = [C.c_int, i64, i32, i32, vp, P(vp)]
+    L.fmhip_fwfm_model_destroy.argtypes = [vp]
+    L.fmhip_fwfm_model_info.argtypes = [vp, P(i64), P(i32), P(i32), P(i32)]
+    L.fmhip_fwfm_model_set_params.argtypes = [vp, dbl, vp, vp, vp]
+    L.fmhip_fwfm_model_get_params.argtypes = [vp, P(dbl), vp, vp, vp]
+    L.fmhip_fwfm_model_set_rule.argtypes = [vp, C.c_int, C.c_int, dbl, dbl]
+    L.fmhip_fwfm_model_set_linear.argtypes = [vp, C.c_int]
+    L.fmhip_fwfm_model_set_field_weights.argtypes = [vp, C.c_int]
+    L.fmhip_fwfm_model_get_accumulators.argtypes = [vp, P(dbl), vp, vp, vp]
+    L.fmhip_fwfm_model_set_accumulators.argtypes = [vp, dbl, vp, vp, vp]
+    L.fmhip_fwfm_predict.argtypes = [vp, vp, vp]
+    L.fmhip_fwfm_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl, P(Stats)]
+    L.fmhip_fwfm_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, dbl, vp, P(Stats)]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM + SYMBOLS_FWFM):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

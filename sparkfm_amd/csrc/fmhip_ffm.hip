@@ -2,6 +2,7 @@
 // sequence of a step — fm_ffm.hip's three kernels.  The dataset's layout is built on the host (fmhip_host.cpp: ffm_validate, ffm_build).
 #include "../../include/fmhip_ffm.h"
 #include "fm_ffm.h"
+#include "fmhip_ffm_dataset.h"
 #include "fmhip_internal.h"
 
 #include <algorithm>
@@ -32,19 +33,6 @@ struct fmhip_ffm_model {
     DevBuf<float> yhat, e, part;
     DevBuf<double> bsum, stats, acc;
     size_t vfloats() const { return (size_t)n1 * F * Kp; }
-};
-
-struct fmhip_ffm_dataset {
-    template <typename T> using DevBuf = fmhip::host::DevBuf<T>;
-    int device = 0;
-    int64_t n_rows = 0, nnz = 0, batch_rows = 0, max_rows = 0;
-    int32_t dim = 0, fields = 0, max_len = 0, max_chunks = 0;
-    bool labels = false;
-    std::vector<FfmBatch> batches;
-    DevBuf<int64_t> row_ptr;
-    DevBuf<int32_t> col, cfeat, cptr, chunk0, chunk_col, occ_row;
-    DevBuf<uint8_t> fld, run, occ_pos;
-    DevBuf<float> val, y;
 };
 
 namespace {

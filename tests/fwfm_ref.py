@@ -1,0 +1,110 @@
+"""The fp64 twin of the field-weighted FM (include/fmhip_fwfm.h), from the naive pairwise definition: a double loop over a < b, nothing
+clever.  Rows are lists of (field, feature, value), as ffm_ref's."""
+import numpy as np
+
+from ffm_ref import P_BATCH, P_EPOCHS, P_ETA, P_K, P_REGV, planted, random_rows  # noqa: F401
+
+
+class State:
+    def __init__(self, w0, w, v, r, init=None):
+        self.w0, self.w, self.v, self.r = float(w0), np.array(w, np.float64), np.array(v, np.float64), np.array(r, np.float64)
+        if init is not None:          # AdaGrad's accumulators
+            self.n0, self.nw, self.nv, self.nr = float(init), np.full_like(self.w, init), np.full_like(self.v, init), np.full_like(self.r, init)
+
+
+def predict_row(s, row):
+    """(yhat, sum of |terms|) of one row."""
+    yh, mag = s.w0, abs(s.w0)
+    for f, i, x in row:
+        yh += s.w[i] * x
+        mag += abs(s.w[i] * x)
+    for a in range(len(row)):
+        for b in range(a + 1, len(row)):
+            (fa, ia, xa), (fb, ib, xb) = row[a], row[b]
+            t = xa * xb * s.r[fa, fb] * float(s.v[ia] @ s.v[ib])
+            yh += t
+            mag += abs(t)
+    return yh, mag
+
+
+def predict(s, rows):
+    out = np.array([predict_row(s, r) for r in rows], np.float64).reshape(-1, 2)
+    return out[:, 0], out[:, 1]
+
+
+def logloss(s, rows, y):
+    yh = predict(s, rows)[0]
+    return float(np.mean(np.maximum(yh, 0.0) - (y > 0) * yh + np.log1p(np.exp(-np.abs(yh)))))
+
+
+def touched(rows, n1):
+    """[n1] bool: the features a batch holds."""
+    t = np.zeros(n1, bool)
+    for row in rows:
+        for _, i, _ in row:
+            t[i] = True
+    return t
+
+
+def step(s, rows, y, eta, reg0, regw, regv, regr=0.0, loss="squared", optimizer="sgd", eps=1e-10, linear=True, field_weights=True):
+    """One mini-batch step in place -> touched(rows)."""
+    B = len(rows)
+    yh, y = predict(s, rows)[0], np.asarray(y, np.float64)
+    e = yh - y if loss == "squared" else 1.0 / (1.0 + np.exp(-yh)) - (y > 0)
+    gv, gw, gr = np.zeros_like(s.v), np.zeros_like(s.w), np.zeros_like(s.r)
+    for r, row in enumerate(rows):
+        for a, (fa, ia, xa) in enumerate(row):
+            gw[ia] += e[r] * xa / B
+            for b in range(a + 1, len(row)):
+                fb, ib, xb = row[b]
+                gv[ia] += e[r] * xa * xb * s.r[fa, fb] * s.v[ib] / B
+                gv[ib] += e[r] * xa * xb * s.r[fa, fb] * s.v[ia] / B
+                d = e[r] * xa * xb * float(s.v[ia] @ s.v[ib]) / B
+                gr[fa, fb] += d          # one parameter for the symmetric pair
+                if fa != fb:
+                    gr[fb, fa] += d
+    g0 = e.sum() / B
+    t = touched(rows, len(s.w))
+
+    def upd(theta, n, g, mask):
+        if optimizer == "sgd":
+            return np.where(mask, theta - eta * g, theta), n
+        n2 = n + g * g
+        return np.where(mask, theta - eta * g / (np.sqrt(n2) + eps), theta), np.where(mask, n2, n)
+
+    ada = optimizer == "adagrad"
+    nv, nw, n0, nr = (s.nv, s.nw, s.n0, s.nr) if ada else (None,) * 4
+    s.v, nv = upd(s.v, nv, gv + regv * s.v, t[:, None])
+    if linear:
+        s.w, nw = upd(s.w, nw, gw + regw * s.w, t)
+        w0, n0 = upd(s.w0, n0, g0 + reg0 * s.w0, True)
+        s.w0 = float(w0)
+    if field_weights:
+        s.r, nr = upd(s.r, nr, gr + regr * s.r, True)
+    if ada:
+        s.nv, s.nw, s.n0, s.nr = nv, nw, float(n0), nr
+    return t
+
+
+def epoch(s, rows, y, batch_rows, order=None, **kw):
+    n = len(rows)
+    br = n if batch_rows <= 0 else batch_rows
+    starts = list(range(0, n, br))
+    for j in (range(len(starts)) if order is None else order):
+        lo = starts[j]
+        step(s, rows[lo:lo + br], y[lo:lo + br], **kw)
+    return s
+
+
+def planted_init(t, F):
+    v = np.random.default_rng(t["seed"] + 1).random((t["n1"], P_K)) / np.sqrt(P_K)
+    return State(0.0, np.zeros(t["n1"]), v, np.ones((F, F)), init=1.0)
+
+
+def run_planted(t, F, field_weights=True, epochs=P_EPOCHS):
+    """Trains the twin on ffm_ref.planted() -> (state, train log-loss, test log-loss); field_weights=False: the plain FM (r = 1, frozen)."""
+    (xtr, ytr), (xte, yte) = t["train"], t["test"]
+    s = planted_init(t, F)
+    for _ in range(epochs):
+        epoch(s, xtr, ytr, P_BATCH, eta=P_ETA, reg0=0.0, regw=0.0, regv=P_REGV, loss="logistic", optimizer="adagrad", field_weights=field_weights)
+    return s, logloss(s, xtr, ytr), logloss(s, xte, yte)
