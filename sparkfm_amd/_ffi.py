@@ -104,6 +104,13 @@ SYMBOLS_FWFM = ("fmhip_fwfm_model_create", "fmhip_fwfm_model_destroy", "fmhip_fw
                 "fmhip_fwfm_model_get_accumulators", "fmhip_fwfm_model_set_accumulators", "fmhip_fwfm_predict", "fmhip_fwfm_step",
                 "fmhip_fwfm_epoch")
 FWFM_MAX_FIELDS, FWFM_MAX_FACTORS = 64, 32      # FMHIP_FWFM_MAX_FIELDS, FMHIP_FWFM_MAX_FACTORS
+# ... and include/fmhip_fmfm.h — the field-matrixed FM: a k x k matrix per pair of fields, over the same dataset handle
+SYMBOLS_FMFM = ("fmhip_fmfm_model_create", "fmhip_fmfm_model_destroy", "fmhip_fmfm_model_info", "fmhip_fmfm_model_set_params",
+                "fmhip_fmfm_model_get_params", "fmhip_fmfm_model_set_rule", "fmhip_fmfm_model_set_linear", "fmhip_fmfm_model_set_field_matrices",
+                "fmhip_fmfm_model_get_accumulators", "fmhip_fmfm_model_set_accumulators", "fmhip_fmfm_predict", "fmhip_fmfm_step",
+                "fmhip_fmfm_epoch")
+FMFM_MAX_FIELDS, FMFM_MAX_FACTORS, FMFM_MAX_WIDTH = 64, 16, 768      # FMHIP_FMFM_MAX_FIELDS, FMHIP_FMFM_MAX_FACTORS, FMHIP_FMFM_MAX_WIDTH
+FMFM_FORWARD_ROWS, FMFM_GRAD_ROWS = 128, 256      # csrc/fm_fmfm.h's kFmfmRowsPerBlock, kFmfmGradRows: rows per forward workgroup, per gradient split
 OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
@@ -641,9 +648,22 @@ def load():
     L.fmhip_fwfm_predict.argtypes = [vp, vp, vp]
     L.fmhip_fwfm_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl, P(Stats)]
     L.fmhip_fwfm_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, dbl, vp, P(Stats)]
+    L.fmhip_fmfm_model_create.argtypes = [C.c_int, i64, i32, i32, vp, P(vp)]
+    L.fmhip_fmfm_model_destroy.argtypes = [vp]
+    L.fmhip_fmfm_model_info.argtypes = [vp, P(i64), P(i32), P(i32), P(i32)]
+    L.fmhip_fmfm_model_set_params.argtypes = [vp, dbl, vp, vp, vp]
+    L.fmhip_fmfm_model_get_params.argtypes = [vp, P(dbl), vp, vp, vp]
+    L.fmhip_fmfm_model_set_rule.argtypes = [vp, C.c_int, C.c_int, dbl, dbl]
+    L.fmhip_fmfm_model_set_linear.argtypes = [vp, C.c_int]
+    L.fmhip_fmfm_model_set_field_matrices.argtypes = [vp, C.c_int]
+    L.fmhip_fmfm_model_get_accumulators.argtypes = [vp, P(dbl), vp, vp, vp]
+    L.fmhip_fmfm_model_set_accumulators.argtypes = [vp, dbl, vp, vp, vp]
+    L.fmhip_fmfm_predict.argtypes = [vp, vp, vp]
+    L.fmhip_fmfm_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl, P(Stats)]
+    L.fmhip_fmfm_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, dbl, vp, P(Stats)]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM + SYMBOLS_FWFM):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM + SYMBOLS_FWFM + SYMBOLS_FMFM):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int
