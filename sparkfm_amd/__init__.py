@@ -15,6 +15,7 @@ from .ffm import FFM, FFMDataSet, FFMModel, HipFFM  # noqa: F401
 from .fwfm import FwFM, FwFMModel, HipFwFM  # noqa: F401
 from .fmfm import FmFM, FmFMModel, HipFmFM  # noqa: F401
 from .deepfm import DeepFM, DeepFMModel, HipDeepFM  # noqa: F401
+from .dcn import DCN, DCNModel, HipDCN  # noqa: F401
 from .fm import FM, FactorizationMachines, Task  # noqa: F401
 from .datacollection import DataCollection  # noqa: F401
 from .feature_order import FeatureOrder  # noqa: F401
@@ -23,4 +24,4 @@ from . import fmutils as FMUtils  # noqa: F401
 __all__ = ["DataSet", "Features", "FMModel", "Model", "FMLearn", "HipSGD", "HipSGDA", "HipFTRL", "HipDataParallelFTRL", "HipALS", "HipMCMC", "HipBlockMCMC", "HipBPR", "FM", "FactorizationMachines", "Task",
            "DataCollection", "FMUtils", "FeatureOrder", "Relation", "RelationalData", "Metadata",
            "FFM", "FFMDataSet", "FFMModel", "HipFFM", "FwFM", "FwFMModel", "HipFwFM", "FmFM", "FmFMModel", "HipFmFM",
-           "DeepFM", "DeepFMModel", "HipDeepFM"]
+           "DeepFM", "DeepFMModel", "HipDeepFM", "DCN", "DCNModel", "HipDCN"]

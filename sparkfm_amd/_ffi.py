@@ -119,6 +119,13 @@ SYMBOLS_DEEPFM = ("fmhip_deepfm_model_create", "fmhip_deepfm_model_destroy", "fm
 # FMHIP_DEEPFM_MAX_FIELDS, _FACTORS, _WIDTH, _LAYERS, _UNITS
 DEEPFM_MAX_FIELDS, DEEPFM_MAX_FACTORS, DEEPFM_MAX_WIDTH, DEEPFM_MAX_LAYERS, DEEPFM_MAX_UNITS = 64, 16, 768, 3, 256
 DEEPFM_FORWARD_ROWS, DEEPFM_GRAD_ROWS = 128, 512      # csrc/fm_deepfm.h's kDeepRowsPerBlock, kDeepGradRows
+# ... and include/fmhip_dcn.h — DCN-V2: a low-rank cross network over the field sums, over the same dataset handle
+SYMBOLS_DCN = ("fmhip_dcn_model_create", "fmhip_dcn_model_destroy", "fmhip_dcn_model_info", "fmhip_dcn_model_set_params",
+               "fmhip_dcn_model_get_params", "fmhip_dcn_model_set_rule", "fmhip_dcn_model_set_linear", "fmhip_dcn_model_set_cross",
+               "fmhip_dcn_model_get_accumulators", "fmhip_dcn_model_set_accumulators", "fmhip_dcn_predict", "fmhip_dcn_step", "fmhip_dcn_epoch")
+# FMHIP_DCN_MAX_FIELDS, _FACTORS, _WIDTH, _LAYERS, _RANK
+DCN_MAX_FIELDS, DCN_MAX_FACTORS, DCN_MAX_WIDTH, DCN_MAX_LAYERS, DCN_MAX_RANK = 64, 16, 768, 3, 256
+DCN_FORWARD_ROWS, DCN_GRAD_ROWS = 128, 512      # csrc/fm_dcn.h's kDcnRowsPerBlock, kDcnGradRows
 OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
@@ -682,9 +689,22 @@ def load():
     L.fmhip_deepfm_predict.argtypes = [vp, vp, vp]
     L.fmhip_deepfm_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl, P(Stats)]
     L.fmhip_deepfm_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, dbl, vp, P(Stats)]
+    L.fmhip_dcn_model_create.argtypes = [C.c_int, i64, i32, i32, i32, i32, vp, P(vp)]
+    L.fmhip_dcn_model_destroy.argtypes = [vp]
+    L.fmhip_dcn_model_info.argtypes = [vp, P(i64), P(i32), P(i32), P(i32), P(i32), P(i32)]
+    L.fmhip_dcn_model_set_params.argtypes = [vp, dbl, vp, vp, P(vp), P(vp), P(vp), vp]
+    L.fmhip_dcn_model_get_params.argtypes = [vp, P(dbl), vp, vp, P(vp), P(vp), P(vp), vp]
+    L.fmhip_dcn_model_set_rule.argtypes = [vp, C.c_int, C.c_int, dbl, dbl]
+    L.fmhip_dcn_model_set_linear.argtypes = [vp, C.c_int]
+    L.fmhip_dcn_model_set_cross.argtypes = [vp, C.c_int]
+    L.fmhip_dcn_model_get_accumulators.argtypes = [vp, P(dbl), vp, vp, P(vp), P(vp), P(vp), vp]
+    L.fmhip_dcn_model_set_accumulators.argtypes = [vp, dbl, vp, vp, P(vp), P(vp), P(vp), vp]
+    L.fmhip_dcn_predict.argtypes = [vp, vp, vp]
+    L.fmhip_dcn_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl, P(Stats)]
+    L.fmhip_dcn_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, dbl, vp, P(Stats)]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM + SYMBOLS_FWFM + SYMBOLS_FMFM + SYMBOLS_DEEPFM):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM + SYMBOLS_FWFM + SYMBOLS_FMFM + SYMBOLS_DEEPFM + SYMBOLS_DCN):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int
