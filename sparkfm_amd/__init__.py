@@ -16,6 +16,7 @@ from .fwfm import FwFM, FwFMModel, HipFwFM  # noqa: F401
 from .fmfm import FmFM, FmFMModel, HipFmFM  # noqa: F401
 from .deepfm import DeepFM, DeepFMModel, HipDeepFM  # noqa: F401
 from .dcn import DCN, DCNModel, HipDCN  # noqa: F401
+from .autoint import AutoInt, AutoIntModel, HipAutoInt  # noqa: F401
 from .fm import FM, FactorizationMachines, Task  # noqa: F401
 from .datacollection import DataCollection  # noqa: F401
 from .feature_order import FeatureOrder  # noqa: F401
@@ -24,4 +25,5 @@ from . import fmutils as FMUtils  # noqa: F401
 __all__ = ["DataSet", "Features", "FMModel", "Model", "FMLearn", "HipSGD", "HipSGDA", "HipFTRL", "HipDataParallelFTRL", "HipALS", "HipMCMC", "HipBlockMCMC", "HipBPR", "FM", "FactorizationMachines", "Task",
            "DataCollection", "FMUtils", "FeatureOrder", "Relation", "RelationalData", "Metadata",
            "FFM", "FFMDataSet", "FFMModel", "HipFFM", "FwFM", "FwFMModel", "HipFwFM", "FmFM", "FmFMModel", "HipFmFM",
-           "DeepFM", "DeepFMModel", "HipDeepFM", "DCN", "DCNModel", "HipDCN"]
+           "DeepFM", "DeepFMModel", "HipDeepFM", "DCN", "DCNModel", "HipDCN",
+           "AutoInt", "AutoIntModel", "HipAutoInt"]

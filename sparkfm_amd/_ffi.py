@@ -126,6 +126,14 @@ SYMBOLS_DCN = ("fmhip_dcn_model_create", "fmhip_dcn_model_destroy", "fmhip_dcn_m
 # FMHIP_DCN_MAX_FIELDS, _FACTORS, _WIDTH, _LAYERS, _RANK
 DCN_MAX_FIELDS, DCN_MAX_FACTORS, DCN_MAX_WIDTH, DCN_MAX_LAYERS, DCN_MAX_RANK = 64, 16, 768, 3, 256
 DCN_FORWARD_ROWS, DCN_GRAD_ROWS = 128, 512      # csrc/fm_dcn.h's kDcnRowsPerBlock, kDcnGradRows
+# ... and include/fmhip_autoint.h — AutoInt: multi-head self-attention over the field sums, over the same dataset handle
+SYMBOLS_AUTOINT = ("fmhip_autoint_model_create", "fmhip_autoint_model_destroy", "fmhip_autoint_model_info", "fmhip_autoint_model_set_params",
+                   "fmhip_autoint_model_get_params", "fmhip_autoint_model_set_rule", "fmhip_autoint_model_set_linear", "fmhip_autoint_model_set_attention",
+                   "fmhip_autoint_model_get_accumulators", "fmhip_autoint_model_set_accumulators", "fmhip_autoint_predict", "fmhip_autoint_step",
+                   "fmhip_autoint_epoch")
+# FMHIP_AUTOINT_MAX_FIELDS, _FACTORS, _LAYERS, _HEADS, _HEAD_DIM, _WIDTH
+AUTOINT_MAX_FIELDS, AUTOINT_MAX_FACTORS, AUTOINT_MAX_LAYERS, AUTOINT_MAX_HEADS, AUTOINT_MAX_HEAD_DIM, AUTOINT_MAX_WIDTH = 64, 16, 3, 4, 32, 64
+AUTOINT_FORWARD_ROWS = 128      # csrc/fm_autoint.h's kAutoIntRowsPerBlock
 OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
@@ -702,9 +710,22 @@ def load():
     L.fmhip_dcn_predict.argtypes = [vp, vp, vp]
     L.fmhip_dcn_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl, P(Stats)]
     L.fmhip_dcn_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, dbl, vp, P(Stats)]
+    L.fmhip_autoint_model_create.argtypes = [C.c_int, i64, i32, i32, i32, i32, i32, vp, P(vp)]
+    L.fmhip_autoint_model_destroy.argtypes = [vp]
+    L.fmhip_autoint_model_info.argtypes = [vp, P(i64), P(i32), P(i32), P(i32), P(i32), P(i32), P(i32)]
+    L.fmhip_autoint_model_set_params.argtypes = [vp, dbl, vp, vp, P(vp), vp]
+    L.fmhip_autoint_model_get_params.argtypes = [vp, P(dbl), vp, vp, P(vp), vp]
+    L.fmhip_autoint_model_set_rule.argtypes = [vp, C.c_int, C.c_int, dbl, dbl]
+    L.fmhip_autoint_model_set_linear.argtypes = [vp, C.c_int]
+    L.fmhip_autoint_model_set_attention.argtypes = [vp, C.c_int]
+    L.fmhip_autoint_model_get_accumulators.argtypes = [vp, P(dbl), vp, vp, P(vp), vp]
+    L.fmhip_autoint_model_set_accumulators.argtypes = [vp, dbl, vp, vp, P(vp), vp]
+    L.fmhip_autoint_predict.argtypes = [vp, vp, vp]
+    L.fmhip_autoint_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl, P(Stats)]
+    L.fmhip_autoint_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, dbl, vp, P(Stats)]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM + SYMBOLS_FWFM + SYMBOLS_FMFM + SYMBOLS_DEEPFM + SYMBOLS_DCN):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM + SYMBOLS_FWFM + SYMBOLS_FMFM + SYMBOLS_DEEPFM + SYMBOLS_DCN + SYMBOLS_AUTOINT):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int
