@@ -1,17 +1,10 @@
 // fmhip_deepfm.hip — the C ABI of DeepFM (include/fmhip_deepfm.h): the model handle, the refusals, and the launch sequence of a step —
 // fm_deepfm.hip's forward (the MLP forwards and backwards for a tile of rows), its weight gradients, fm_fwfm.hip's backward and update
 // for v, w, w0 and the statistics, then the dense part's own update.  The data handle is the FFM's (fmhip_ffm_dataset.h), read and
-// never changed.
+// never changed; what the handle shares with the other field models is fmhip_field_model.h's.
 #include "../../include/fmhip_deepfm.h"
 #include "fm_deepfm.h"
-#include "fmhip_ffm_dataset.h"
-#include "fmhip_internal.h"
-
-#include <algorithm>
-#include <cmath>
-#include <mutex>
-#include <new>
-#include <vector>
+#include "fmhip_field_model.h"
 
 using namespace fmhip;
 using namespace fmhip::host;
@@ -19,226 +12,90 @@ using namespace fmhip::host;
 static_assert(FMHIP_DEEPFM_MAX_FIELDS == kFfmMaxFields, "fmhip_deepfm.h and fmhip_host.h disagree on the fields");
 static_assert(FMHIP_DEEPFM_MAX_WIDTH == kDeepMaxWidth, "fmhip_deepfm.h and fm_deepfm.h disagree on the width");
 static_assert(FMHIP_DEEPFM_MAX_LAYERS == kDeepMaxLayers && FMHIP_DEEPFM_MAX_UNITS == kDeepMaxUnits, "fmhip_deepfm.h and fm_deepfm.h disagree on the layers");
+static_assert(kDeepMaxLayers == kFieldMaxLayers, "fm_deepfm.h and fmhip_field_layout.h disagree on the layers");
 static_assert(kFwfmChunkLen == kFfmChunk, "fm_fwfm.h and fmhip_host.h disagree on the chunk length");
 
-struct fmhip_deepfm_model {
-    template <typename T> using DevBuf = fmhip::host::DevBuf<T>;
-    std::mutex mu;
-    int device = 0;
-    int64_t n = 0, n1 = 0;
-    int32_t F = 0, k = 0, Kp = 0, Pp = 0, L = 0;
-    int32_t width[kDeepMaxLayers + 1] = {};          // width[0] = Pp on the device (F k for the caller), width[l] = n_l
-    int32_t woff[kDeepMaxLayers] = {}, boff[kDeepMaxLayers] = {}, uoff = 0, total = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    DevBuf<float> V, w, w0, D, NV, Nw, N0, ND;
-    int loss = FMHIP_LOSS_SQUARED, opt = FMHIP_OPT_SGD, linear = 1, train_d = 1;
-    double eps = 0.0, init = 0.0;
-    // workspace, grown to the largest dataset the model has been paired with
-    DevBuf<float> yhat, e, dz, part, sw, hw[kDeepMaxLayers], dw[kDeepMaxLayers], gpart;
-    DevBuf<double> bsum, stats, acc;
-    size_t vfloats() const { return (size_t)n1 * Kp; }
-    int rows_in(int l) const { return l == 1 ? F * k : width[l - 1]; }          // the caller's n_{l-1}
-    size_t dev_row(int l, int i) const { return l == 1 ? (size_t)(i / k) * Kp + i % k : (size_t)i; }          // ... and its row on the device
+struct fmhip_deepfm_model : FieldCore {
+    DeepfmSlots s;          // the widths, and where W_l, b_l and u sit in D
+    DevBuf<float> D, ND;
+    DevBuf<float> sw, hw[kDeepMaxLayers], dw[kDeepMaxLayers], gpart;          // workspace
 };
 
 namespace {
 
-// the table codec: the caller's v[i k + d] <-> the device's [i][Kp] fp32 (pad slots: `pad`)
-std::vector<float> pack_table(const fmhip_deepfm_model *m, const double *v, float pad) {
-    std::vector<float> t(m->vfloats(), pad);
-    for (size_t j = 0; j < (size_t)m->n1; ++j)
-        for (int d = 0; d < m->k; ++d) t[j * m->Kp + d] = (float)v[j * m->k + d];
-    return t;
-}
+constexpr FieldNames kNames{"DeepFM", "DEEPFM", "deepfm", "regd"};
 
-// the caller's W_l, b_l, u <-> the device's one array (fm_deepfm.h); the rows of W_1 no caller's row maps to: `pad`
-std::vector<float> pack_dense(const fmhip_deepfm_model *m, const double *const *W, const double *const *b, const double *u, float pad) {
-    std::vector<float> t((size_t)m->total, pad);
-    for (int l = 1; l <= m->L; ++l) {
-        const int nl = m->width[l];
-        for (int i = 0; i < m->rows_in(l); ++i)
-            for (int j = 0; j < nl; ++j) t[m->woff[l - 1] + m->dev_row(l, i) * nl + j] = (float)W[l - 1][(size_t)i * nl + j];
-        for (int j = 0; j < nl; ++j) t[m->boff[l - 1] + j] = (float)b[l - 1][j];
-    }
-    for (int j = 0; j < m->width[m->L]; ++j) t[m->uoff + j] = (float)u[j];
-    return t;
-}
-
-int write_floats(fmhip_deepfm_model *m, float *dev, const std::vector<float> &t) {
-    HIP_TRY(hipMemcpyAsync(dev, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    return FMHIP_OK;
-}
-
-int write_vector(fmhip_deepfm_model *m, float *dev, const double *src, size_t n) { return write_floats(m, dev, std::vector<float>(src, src + n)); }
-
-// n floats of the device as doubles; stride > width: the first `width` of every `stride` (the factor table)
-int read_vector(fmhip_deepfm_model *m, const float *dev, size_t n, double *out, int width = 1, int stride = 1) {
-    std::vector<float> t(n);
-    HIP_TRY(hipMemcpyAsync(t.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    for (size_t j = 0; j < n / stride; ++j)
-        for (int d = 0; d < width; ++d) out[j * width + d] = t[j * stride + d];
-    return FMHIP_OK;
-}
-
-int read_dense(fmhip_deepfm_model *m, const float *dev, double *const *W, double *const *b, double *u) {
-    if (!W && !b && !u) return FMHIP_OK;
-    std::vector<float> t((size_t)m->total);
-    HIP_TRY(hipMemcpyAsync(t.data(), dev, t.size() * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    for (int l = 1; l <= m->L; ++l) {
-        const int nl = m->width[l];
-        if (W && W[l - 1])
-            for (int i = 0; i < m->rows_in(l); ++i)
-                for (int j = 0; j < nl; ++j) W[l - 1][(size_t)i * nl + j] = t[m->woff[l - 1] + m->dev_row(l, i) * nl + j];
-        if (b && b[l - 1])
-            for (int j = 0; j < nl; ++j) b[l - 1][j] = t[m->boff[l - 1] + j];
-    }
-    if (u)
-        for (int j = 0; j < m->width[m->L]; ++j) u[j] = t[m->uoff + j];
-    return FMHIP_OK;
+// the caller's arrays by (slot map array, layer): W_l, b_l, u
+template <typename T>
+auto arrays(T *const *W, T *const *b, T *u) {
+    return [=](int a, int l) -> T * { return a == 0 ? (W ? W[l] : nullptr) : (a == 1 ? (b ? b[l] : nullptr) : u); };
 }
 
 int check_dense_pointers(const fmhip_deepfm_model *m, const double *const *W, const double *const *b, const double *u) {
     if (!W || !b || !u) return fail(FMHIP_ERR_INVALID, "NULL argument");
-    for (int l = 0; l < m->L; ++l)
-        if (!W[l] || !b[l]) return fail(FMHIP_ERR_INVALID, "layer %d: NULL argument", l + 1);
-    return FMHIP_OK;
+    const int l = first_null_layer(m->s, arrays(W, b, u));
+    return l < 0 ? FMHIP_OK : fail(FMHIP_ERR_INVALID, "layer %d: NULL argument", l + 1);
 }
 
 // every refusal of (m, d) that needs no launch, then the device and the workspace
 int pair_up(fmhip_deepfm_model_t m, fmhip_ffm_dataset_t d, bool train) {
-    if (!d) return fail(FMHIP_ERR_INVALID, "the FFM dataset handle is NULL");
-    if (d->device != m->device) return fail(FMHIP_ERR_INVALID, "the dataset lives on device %d, the model on device %d", d->device, m->device);
-    if (d->nnz > 0 && d->dim > m->n)
-        return fail(FMHIP_ERR_INVALID, "the dataset holds feature id %d, above the model's num_attribute = %lld", d->dim, (long long)m->n);
-    if (d->fields > m->F) return fail(FMHIP_ERR_INVALID, "the dataset holds field id %d, outside the model's [0, %d)", d->fields - 1, m->F);
-    if (train && !d->labels) return fail(FMHIP_ERR_INVALID, "the dataset was created without labels (y = NULL): it can be scored, not trained on");
-    TRY(set_device(m->device));
-    TRY(m->yhat.ensure((size_t)std::max<int64_t>(train ? d->max_rows : d->n_rows, 1)));
+    TRY(pair_refusals(*m, d, train));
+    const size_t rows = (size_t)std::max<int64_t>(d->max_rows, 1);
+    TRY(pair_workspace(*m, d, train, (size_t)deepfm_forward_blocks(rows)));
     if (train) {
-        int32_t max_nnz = 1;
-        for (const FfmBatch &b : d->batches) max_nnz = std::max(max_nnz, b.nnz);
-        const size_t rows = (size_t)std::max<int64_t>(d->max_rows, 1);
-        TRY(m->e.ensure(rows));
-        TRY(m->dz.ensure((size_t)max_nnz * m->Kp));
-        TRY(m->bsum.ensure((size_t)deepfm_forward_blocks(rows) * 4));
-        TRY(m->part.ensure((size_t)std::max(d->max_chunks, 1) * (m->Kp + kFwfmPartTail)));
-        TRY(m->sw.ensure(rows * m->Pp));
-        for (int l = 0; l < m->L; ++l) {
-            TRY(m->hw[l].ensure(rows * m->width[l + 1]));
-            TRY(m->dw[l].ensure(rows * m->width[l + 1]));
+        TRY(m->sw.ensure(rows * m->s.Pp));
+        for (int l = 0; l < m->s.L; ++l) {
+            TRY(m->hw[l].ensure(rows * m->s.width[l + 1]));
+            TRY(m->dw[l].ensure(rows * m->s.width[l + 1]));
         }
-        TRY(m->gpart.ensure((size_t)deepfm_grad_splits(rows) * m->total));
+        TRY(m->gpart.ensure((size_t)deepfm_grad_splits(rows) * m->s.total()));
     }
     return FMHIP_OK;
 }
 
 DeepfmArgs batch_args(fmhip_deepfm_model_t m, fmhip_ffm_dataset_t d, const FfmBatch &b) {
+    const DeepfmSlots &s = m->s;
     DeepfmArgs q{};
-    FwfmArgs &a = q.b;
-    a.V = m->V.p;
-    a.w = m->w.p;
-    a.w0 = m->w0.p;
-    a.NV = m->NV.p;
-    a.Nw = m->Nw.p;
-    a.N0 = m->N0.p;
-    a.Nr = m->ND.p;               // (the FwFM's update launch wants the pointers; with train_r = 0 it reads neither)
-    a.rpart = m->gpart.p;
-    a.F = m->F;
-    a.Fp = (m->F + 15) / 16 * 16;
-    a.Kp = m->Kp;
-    a.row_ptr = d->row_ptr.p + b.row0;
-    a.col = d->col.p;
-    a.fld = d->fld.p;
-    a.run = d->run.p;
-    a.val = d->val.p;
-    a.y = d->labels ? d->y.p + b.row0 : nullptr;
-    a.nnz0 = b.nnz0;
-    a.rows = (int32_t)b.rows;
-    a.cfeat = d->cfeat.p + b.col_off;
-    a.cptr = d->cptr.p + b.cptr_off;
-    a.chunk0 = d->chunk0.p + b.cptr_off;
-    a.chunk_col = d->chunk_col.p + b.chunk_off;
-    a.occ_row = d->occ_row.p + b.nnz0;
-    a.occ_pos = d->occ_pos.p + b.nnz0;
-    a.n_cols = b.n_cols;
-    a.n_chunks = b.n_chunks;
-    a.yhat = m->yhat.p;
-    a.e = m->e.p;
-    a.dz = m->dz.p;
-    a.bsum = m->bsum.p;
-    a.n_blocks = deepfm_forward_blocks(b.rows);
-    a.part = m->part.p;
-    a.stats = m->stats.p;
-    a.loss = m->loss;
-    a.linear = m->linear;
-    a.train_r = 0;
-    a.eps = (float)m->eps;
-    a.invb = b.rows > 0 ? 1.0f / (float)b.rows : 0.f;
+    q.b = fwfm_args(*m, d, b, deepfm_forward_blocks(b.rows));
+    q.b.Nr = m->ND.p;               // (the FwFM's update launch wants the pointers; with train_r = 0 it reads neither)
+    q.b.rpart = m->gpart.p;
     q.D = m->D.p;
     q.ND = m->ND.p;
     q.k = m->k;
-    q.Pp = m->Pp;
-    q.L = m->L;
-    for (int l = 0; l <= m->L; ++l) q.n[l] = m->width[l];
-    for (int l = 0; l < m->L; ++l) {
-        q.woff[l] = m->woff[l];
-        q.boff[l] = m->boff[l];
+    q.Pp = s.Pp;
+    q.L = s.L;
+    for (int l = 0; l <= s.L; ++l) q.n[l] = s.width[l];
+    for (int l = 0; l < s.L; ++l) {
+        q.woff[l] = s.woff[l];
+        q.boff[l] = s.boff[l];
         q.hw[l] = m->hw[l].p;
         q.dw[l] = m->dw[l].p;
     }
-    q.uoff = m->uoff;
-    q.total = m->total;
+    q.uoff = s.uoff;
+    q.total = s.n_total;
     q.sw = m->sw.p;
     q.gpart = m->gpart.p;
     q.n_splits = deepfm_grad_splits(b.rows);
-    q.train_d = m->train_d;
+    q.train_d = m->train;
     return q;
 }
 
-bool rate_ok(double x) { return std::isfinite(x) && x >= 0.0; }
-
-int check_rates(double eta, double reg0, double regw, double regv, double regd) {
-    if (!std::isfinite(eta) || !rate_ok(reg0) || !rate_ok(regw) || !rate_ok(regv) || !rate_ok(regd))
-        return fail(FMHIP_ERR_INVALID, "eta = %g, reg0 = %g, regw = %g, regv = %g, regd = %g: the step size is finite, a regulariser finite and >= 0", eta, reg0,
-                    regw, regv, regd);
-    return FMHIP_OK;
+hipError_t forward(fmhip_deepfm_model_t m, fmhip_ffm_dataset_t d, const FfmBatch &b, float *yhat) {
+    DeepfmArgs a = batch_args(m, d, b);
+    a.b.yhat = yhat;
+    return launch_deepfm_forward(a, false, m->stream);
 }
 
-struct Rates {
-    double eta, reg0, regw, regv, regd;
-};
-
-// one step, asynchronous on the model's stream; acc: the epoch's running sums on the device (nullable)
-int deepfm_step(fmhip_deepfm_model_t m, fmhip_ffm_dataset_t d, int64_t b, const Rates &q, double *acc, bool acc_reset = false) {
+int one_step(fmhip_deepfm_model_t m, fmhip_ffm_dataset_t d, int64_t b, const Rates &q, double *acc, bool acc_reset) {
     DeepfmArgs a = batch_args(m, d, d->batches[(size_t)b]);
-    a.b.eta = (float)q.eta;
-    a.b.reg0 = (float)q.reg0;
-    a.b.regw = (float)q.regw;
-    a.b.regv = (float)q.regv;
-    a.regd = (float)q.regd;
-    a.b.acc = acc;
-    a.b.acc_reset = acc_reset;
+    set_rates(a.b, q, acc, acc_reset);
+    a.regd = (float)q.regx;
     const bool ada = m->opt == FMHIP_OPT_ADAGRAD;
     HIP_TRY(launch_deepfm_forward(a, true, m->stream));
-    if (m->train_d) HIP_TRY(launch_deepfm_wgrad(a, m->stream));
+    if (m->train) HIP_TRY(launch_deepfm_wgrad(a, m->stream));
     HIP_TRY(launch_fwfm_backward(a.b, ada, m->stream));
     HIP_TRY(launch_fwfm_update(a.b, ada, m->stream));
-    if (m->train_d) HIP_TRY(launch_deepfm_dupdate(a, ada, m->stream));
-    return FMHIP_OK;
-}
-
-int read_stats(fmhip_deepfm_model_t m, const double *dev, int64_t nnz, int64_t steps, fmhip_stats *st) {
-    double h[4];
-    HIP_TRY(hipMemcpyAsync(h, dev, sizeof h, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    memset(st, 0, sizeof *st);
-    fill_stats(st, h);
-    st->nnz = nnz;
-    st->steps = steps;
+    if (m->train) HIP_TRY(launch_deepfm_dupdate(a, ada, m->stream));
     return FMHIP_OK;
 }
 
@@ -248,16 +105,8 @@ extern "C" {
 
 int fmhip_deepfm_model_create(int device, int64_t num_attribute, int32_t num_fields, int32_t num_factor, int32_t n_layers, const int32_t *widths,
                               void *stream, fmhip_deepfm_model_t *out) {
-    if (!out) return fail(FMHIP_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (num_attribute < 0) return fail(FMHIP_ERR_INVALID, "num_attribute = %lld: a model has at least feature 0", (long long)num_attribute);
-    if (num_fields < 1) return fail(FMHIP_ERR_INVALID, "num_fields = %d: a model has at least one field", num_fields);
-    if (num_fields > FMHIP_DEEPFM_MAX_FIELDS)
-        return fail(FMHIP_ERR_UNSUPPORTED, "num_fields = %d is above FMHIP_DEEPFM_MAX_FIELDS = %d", num_fields, FMHIP_DEEPFM_MAX_FIELDS);
-    if (num_factor < 1) return fail(FMHIP_ERR_INVALID, "num_factor = %d: a model has at least one factor", num_factor);
-    if (num_factor > FMHIP_DEEPFM_MAX_FACTORS)
-        return fail(FMHIP_ERR_UNSUPPORTED, "num_factor = %d is above FMHIP_DEEPFM_MAX_FACTORS = %d", num_factor, FMHIP_DEEPFM_MAX_FACTORS);
-    const int32_t Kp = num_factor <= 4 ? 4 : (num_factor <= 8 ? 8 : 16);
+    TRY(check_field_shape(kNames, out, num_attribute, num_fields, num_factor, FMHIP_DEEPFM_MAX_FACTORS));
+    const int32_t Kp = field_kp(num_factor);
     if (num_fields * Kp > FMHIP_DEEPFM_MAX_WIDTH)
         return fail(FMHIP_ERR_UNSUPPORTED, "num_fields = %d at num_factor = %d (padded to %d): F·Kp = %d is above %d", num_fields, num_factor, Kp, num_fields * Kp,
                     FMHIP_DEEPFM_MAX_WIDTH);
@@ -269,82 +118,29 @@ int fmhip_deepfm_model_create(int device, int64_t num_attribute, int32_t num_fie
         if (widths[l] > FMHIP_DEEPFM_MAX_UNITS)
             return fail(FMHIP_ERR_UNSUPPORTED, "widths[%d] = %d is above FMHIP_DEEPFM_MAX_UNITS = %d", l, widths[l], FMHIP_DEEPFM_MAX_UNITS);
     }
-    if (num_attribute >= INT32_MAX) return fail(FMHIP_ERR_UNSUPPORTED, "num_attribute = %lld: feature ids are 32-bit", (long long)num_attribute);
+    TRY(check_feature_ids(num_attribute));
     TRY(set_device(device));
     fmhip_deepfm_model *m = new (std::nothrow) fmhip_deepfm_model();
     if (!m) return fail(FMHIP_ERR_NOMEM, "out of host memory");
-    m->device = device;
-    m->n = num_attribute;
-    m->n1 = num_attribute + 1;
-    m->F = num_fields;
-    m->k = num_factor;
-    m->Kp = Kp;
-    m->Pp = (num_fields * Kp + 15) / 16 * 16;
-    m->L = n_layers;
-    m->width[0] = m->Pp;
-    int32_t at = 0;
-    for (int l = 1; l <= n_layers; ++l) {
-        m->width[l] = widths[l - 1];
-        m->woff[l - 1] = at;
-        at += m->width[l - 1] * m->width[l];
-    }
-    m->uoff = at;
-    at += m->width[n_layers];
-    for (int l = 1; l <= n_layers; ++l) {
-        m->boff[l - 1] = at;
-        at += m->width[l];
-    }
-    m->total = at;
-    if (stream) {
-        m->stream = reinterpret_cast<hipStream_t>(stream);
-    } else {
-        hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            delete m;
-            return fail(FMHIP_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-        }
-        m->own_stream = true;
-    }
-    int rc;
-    if ((rc = m->V.alloc(m->vfloats())) || (rc = m->w.alloc((size_t)m->n1)) || (rc = m->w0.alloc(1)) || (rc = m->D.alloc((size_t)m->total)) ||
-        (rc = m->stats.alloc(4)) || (rc = m->acc.alloc(4))) {
-        fmhip_deepfm_model_destroy(m);
+    set_shape(*m, device, num_attribute, num_fields, num_factor);
+    m->s = DeepfmSlots(num_fields, num_factor, n_layers, widths);
+    if (int rc = open_model(*m, kNames, stream, m->D, m->s.total(), nullptr)) {
+        destroy_model(m);
         return rc;
-    }
-    hipError_t e = hipMemset(m->V.p, 0, m->V.n * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(m->w.p, 0, m->w.n * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(m->w0.p, 0, sizeof(float));
-    if (e == hipSuccess) e = hipMemset(m->D.p, 0, m->D.n * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(m->stats.p, 0, 4 * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(m->acc.p, 0, 4 * sizeof(double));
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        fmhip_deepfm_model_destroy(m);
-        return fail(FMHIP_ERR_HIP, "setting up the DeepFM model failed: %s", hipGetErrorString(e));
     }
     *out = m;
     return FMHIP_OK;
 }
 
-int fmhip_deepfm_model_destroy(fmhip_deepfm_model_t m) {
-    if (!m) return FMHIP_OK;
-    (void)hipSetDevice(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    if (m->own_stream && m->stream) (void)hipStreamDestroy(m->stream);
-    delete m;
-    return FMHIP_OK;
-}
+int fmhip_deepfm_model_destroy(fmhip_deepfm_model_t m) { return destroy_model(m); }
 
 int fmhip_deepfm_model_info(fmhip_deepfm_model_t m, int64_t *num_attribute, int32_t *num_fields, int32_t *num_factor, int32_t *padded_factors,
                             int32_t *n_layers, int32_t *widths) {
     if (!m) return fail(FMHIP_ERR_INVALID, "the DeepFM model handle is NULL");
-    if (num_attribute) *num_attribute = m->n;
-    if (num_fields) *num_fields = m->F;
-    if (num_factor) *num_factor = m->k;
-    if (padded_factors) *padded_factors = m->Kp;
-    if (n_layers) *n_layers = m->L;
+    model_info(*m, num_attribute, num_fields, num_factor, padded_factors);
+    if (n_layers) *n_layers = m->s.L;
     if (widths)
-        for (int l = 0; l < m->L; ++l) widths[l] = m->width[l + 1];
+        for (int l = 0; l < m->s.L; ++l) widths[l] = m->s.width[l + 1];
     return FMHIP_OK;
 }
 
@@ -353,87 +149,32 @@ int fmhip_deepfm_model_set_params(fmhip_deepfm_model_t m, double w0, const doubl
     if (!m) return fail(FMHIP_ERR_INVALID, "the DeepFM model handle is NULL");
     if (!w || !v) return fail(FMHIP_ERR_INVALID, "NULL argument");
     TRY(check_dense_pointers(m, W, b, u));
-    std::lock_guard<std::mutex> lock(m->mu);
-    TRY(set_device(m->device));
-    TRY(write_floats(m, m->V.p, pack_table(m, v, 0.f)));
-    TRY(write_vector(m, m->w.p, w, (size_t)m->n1));
-    TRY(write_floats(m, m->D.p, pack_dense(m, W, b, u, 0.f)));
-    return write_vector(m, m->w0.p, &w0, 1);
+    return set_params(*m, w0, w, v, m->D.p, m->s, arrays(W, b, u));
 }
 
 int fmhip_deepfm_model_get_params(fmhip_deepfm_model_t m, double *w0, double *w, double *v, double *const *W, double *const *b, double *u) {
     if (!m) return fail(FMHIP_ERR_INVALID, "the DeepFM model handle is NULL");
-    std::lock_guard<std::mutex> lock(m->mu);
-    TRY(set_device(m->device));
-    if (w0) TRY(read_vector(m, m->w0.p, 1, w0));
-    if (w) TRY(read_vector(m, m->w.p, (size_t)m->n1, w));
-    if (v) TRY(read_vector(m, m->V.p, m->vfloats(), v, m->k, m->Kp));
-    return read_dense(m, m->D.p, W, b, u);
+    return get_params(*m, w0, w, v, m->D.p, m->s, W || b || u, arrays(W, b, u));
 }
 
 int fmhip_deepfm_model_set_rule(fmhip_deepfm_model_t m, int loss, int optimizer, double eps, double init) {
     if (!m) return fail(FMHIP_ERR_INVALID, "the DeepFM model handle is NULL");
-    if (loss != FMHIP_LOSS_SQUARED && loss != FMHIP_LOSS_LOGISTIC) return fail(FMHIP_ERR_INVALID, "loss = %d: FMHIP_LOSS_SQUARED or FMHIP_LOSS_LOGISTIC", loss);
-    if (optimizer != FMHIP_OPT_SGD && optimizer != FMHIP_OPT_ADAGRAD)
-        return fail(FMHIP_ERR_INVALID, "optimizer = %d: FMHIP_OPT_SGD or FMHIP_OPT_ADAGRAD", optimizer);
-    if (optimizer == FMHIP_OPT_ADAGRAD) {
-        if (!(std::isfinite(eps) && eps > 0.0)) return fail(FMHIP_ERR_INVALID, "eps = %g: AdaGrad's eps is finite and > 0", eps);
-        if (!rate_ok(init)) return fail(FMHIP_ERR_INVALID, "init = %g: AdaGrad's initial accumulator is finite and >= 0", init);
-    }
-    std::lock_guard<std::mutex> lock(m->mu);
-    TRY(set_device(m->device));
-    m->loss = loss;
-    if (optimizer == FMHIP_OPT_SGD) {
-        HIP_TRY(hipStreamSynchronize(m->stream));
-        m->NV.release();
-        m->Nw.release();
-        m->N0.release();
-        m->ND.release();
-        m->opt = FMHIP_OPT_SGD;
-        return FMHIP_OK;
-    }
-    if (m->opt == FMHIP_OPT_ADAGRAD && memcmp(&m->eps, &eps, sizeof eps) == 0 && memcmp(&m->init, &init, sizeof init) == 0) return FMHIP_OK;
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    TRY(m->NV.alloc(m->vfloats()));
-    TRY(m->Nw.alloc((size_t)m->n1));
-    TRY(m->N0.alloc(1));
-    TRY(m->ND.alloc((size_t)m->total));
-    const std::vector<float> fill(std::max({m->vfloats(), (size_t)m->n1, (size_t)m->total}), (float)init);
-    HIP_TRY(hipMemcpy(m->NV.p, fill.data(), m->vfloats() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->Nw.p, fill.data(), (size_t)m->n1 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->N0.p, fill.data(), sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->ND.p, fill.data(), (size_t)m->total * sizeof(float), hipMemcpyHostToDevice));
-    m->opt = FMHIP_OPT_ADAGRAD;
-    m->eps = eps;
-    m->init = init;
-    return FMHIP_OK;
+    return set_rule(*m, loss, optimizer, eps, init, m->ND, m->s.total());
 }
 
 int fmhip_deepfm_model_set_linear(fmhip_deepfm_model_t m, int linear) {
     if (!m) return fail(FMHIP_ERR_INVALID, "the DeepFM model handle is NULL");
-    if (linear != 0 && linear != 1) return fail(FMHIP_ERR_INVALID, "linear = %d: 0 or 1", linear);
-    std::lock_guard<std::mutex> lock(m->mu);
-    m->linear = linear;
-    return FMHIP_OK;
+    return set_flag(*m, &FieldCore::linear, "linear", linear);
 }
 
 int fmhip_deepfm_model_set_deep(fmhip_deepfm_model_t m, int train) {
     if (!m) return fail(FMHIP_ERR_INVALID, "the DeepFM model handle is NULL");
-    if (train != 0 && train != 1) return fail(FMHIP_ERR_INVALID, "train = %d: 0 or 1", train);
-    std::lock_guard<std::mutex> lock(m->mu);
-    m->train_d = train;
-    return FMHIP_OK;
+    return set_flag(*m, &FieldCore::train, "train", train);
 }
 
 int fmhip_deepfm_model_get_accumulators(fmhip_deepfm_model_t m, double *n0, double *nw, double *nv, double *const *nW, double *const *nb, double *nu) {
     if (!m) return fail(FMHIP_ERR_INVALID, "the DeepFM model handle is NULL");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (m->opt != FMHIP_OPT_ADAGRAD) return fail(FMHIP_ERR_INVALID, "the model is under SGD: it has no accumulators (fmhip_deepfm_model_set_rule)");
-    TRY(set_device(m->device));
-    if (n0) TRY(read_vector(m, m->N0.p, 1, n0));
-    if (nw) TRY(read_vector(m, m->Nw.p, (size_t)m->n1, nw));
-    if (nv) TRY(read_vector(m, m->NV.p, m->vfloats(), nv, m->k, m->Kp));
-    return read_dense(m, m->ND.p, nW, nb, nu);
+    return get_accumulators(*m, kNames, n0, nw, nv, m->ND.p, m->s, nW || nb || nu, arrays(nW, nb, nu));
 }
 
 int fmhip_deepfm_model_set_accumulators(fmhip_deepfm_model_t m, double n0, const double *nw, const double *nv, const double *const *nW,
@@ -441,75 +182,24 @@ int fmhip_deepfm_model_set_accumulators(fmhip_deepfm_model_t m, double n0, const
     if (!m) return fail(FMHIP_ERR_INVALID, "the DeepFM model handle is NULL");
     if (!nw || !nv) return fail(FMHIP_ERR_INVALID, "NULL argument");
     TRY(check_dense_pointers(m, nW, nb, nu));
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (m->opt != FMHIP_OPT_ADAGRAD) return fail(FMHIP_ERR_INVALID, "the model is under SGD: it has no accumulators (fmhip_deepfm_model_set_rule)");
-    if (!rate_ok(n0)) return fail(FMHIP_ERR_INVALID, "n0 = %g: an accumulator is finite and >= 0", n0);
-    for (int64_t i = 0; i < m->n1; ++i)
-        if (!rate_ok(nw[i])) return fail(FMHIP_ERR_INVALID, "nw[%lld] = %g: an accumulator is finite and >= 0", (long long)i, nw[i]);
-    for (size_t j = 0; j < (size_t)m->n1 * m->k; ++j)
-        if (!rate_ok(nv[j])) return fail(FMHIP_ERR_INVALID, "nv[%zu] = %g: an accumulator is finite and >= 0", j, nv[j]);
-    for (int l = 1; l <= m->L; ++l) {
-        for (size_t j = 0; j < (size_t)m->rows_in(l) * m->width[l]; ++j)
-            if (!rate_ok(nW[l - 1][j])) return fail(FMHIP_ERR_INVALID, "nW[%d][%zu] = %g: an accumulator is finite and >= 0", l - 1, j, nW[l - 1][j]);
-        for (int j = 0; j < m->width[l]; ++j)
-            if (!rate_ok(nb[l - 1][j])) return fail(FMHIP_ERR_INVALID, "nb[%d][%d] = %g: an accumulator is finite and >= 0", l - 1, j, nb[l - 1][j]);
-    }
-    for (int j = 0; j < m->width[m->L]; ++j)
-        if (!rate_ok(nu[j])) return fail(FMHIP_ERR_INVALID, "nu[%d] = %g: an accumulator is finite and >= 0", j, nu[j]);
-    TRY(set_device(m->device));
-    TRY(write_floats(m, m->NV.p, pack_table(m, nv, (float)m->init)));
-    TRY(write_vector(m, m->Nw.p, nw, (size_t)m->n1));
-    TRY(write_floats(m, m->ND.p, pack_dense(m, nW, nb, nu, (float)m->init)));
-    return write_vector(m, m->N0.p, &n0, 1);
+    return set_accumulators(*m, kNames, n0, nw, nv, m->ND.p, m->s, arrays(nW, nb, nu));
 }
 
 int fmhip_deepfm_predict(fmhip_deepfm_model_t m, fmhip_ffm_dataset_t d, double *yhat) {
     if (!m) return fail(FMHIP_ERR_INVALID, "the DeepFM model handle is NULL");
-    if (!d) return fail(FMHIP_ERR_INVALID, "the FFM dataset handle is NULL");
-    if (!yhat) return fail(FMHIP_ERR_INVALID, "yhat is NULL");
-    std::lock_guard<std::mutex> lock(m->mu);
-    TRY(pair_up(m, d, false));
-    for (const FfmBatch &b : d->batches) {
-        DeepfmArgs a = batch_args(m, d, b);
-        a.b.yhat = m->yhat.p + b.row0;
-        HIP_TRY(launch_deepfm_forward(a, false, m->stream));
-    }
-    std::vector<float> h((size_t)d->n_rows);
-    if (d->n_rows > 0) HIP_TRY(hipMemcpyAsync(h.data(), m->yhat.p, h.size() * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    std::copy(h.begin(), h.end(), yhat);
-    return FMHIP_OK;
+    return predict(m, d, yhat, pair_up, forward);
 }
 
 int fmhip_deepfm_step(fmhip_deepfm_model_t m, fmhip_ffm_dataset_t d, int64_t batch, double eta, double reg0, double regw, double regv, double regd,
                       fmhip_stats *stats) {
     if (!m) return fail(FMHIP_ERR_INVALID, "the DeepFM model handle is NULL");
-    if (!d) return fail(FMHIP_ERR_INVALID, "the FFM dataset handle is NULL");
-    TRY(check_rates(eta, reg0, regw, regv, regd));
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (batch < 0 || batch >= (int64_t)d->batches.size())
-        return fail(FMHIP_ERR_INVALID, "batch = %lld: the dataset has %zu batches", (long long)batch, d->batches.size());
-    TRY(pair_up(m, d, true));
-    TRY(deepfm_step(m, d, batch, Rates{eta, reg0, regw, regv, regd}, nullptr));
-    if (stats) TRY(read_stats(m, m->stats.p, d->batches[(size_t)batch].nnz, 1, stats));
-    return FMHIP_OK;
+    return step(m, kNames, d, batch, Rates{eta, reg0, regw, regv, regd}, stats, pair_up, one_step);
 }
 
 int fmhip_deepfm_epoch(fmhip_deepfm_model_t m, fmhip_ffm_dataset_t d, double eta, double reg0, double regw, double regv, double regd,
                        const int64_t *order, fmhip_stats *stats) {
     if (!m) return fail(FMHIP_ERR_INVALID, "the DeepFM model handle is NULL");
-    if (!d) return fail(FMHIP_ERR_INVALID, "the FFM dataset handle is NULL");
-    TRY(check_rates(eta, reg0, regw, regv, regd));
-    std::lock_guard<std::mutex> lock(m->mu);
-    const int64_t nb = (int64_t)d->batches.size();
-    if (order)
-        for (int64_t j = 0; j < nb; ++j)
-            if (order[j] < 0 || order[j] >= nb) return fail(FMHIP_ERR_INVALID, "order[%lld] = %lld: the dataset has %lld batches", (long long)j, (long long)order[j], (long long)nb);
-    TRY(pair_up(m, d, true));
-    // the epoch's sums: the first step's update launch overwrites them, the others add
-    for (int64_t j = 0; j < nb; ++j) TRY(deepfm_step(m, d, order ? order[j] : j, Rates{eta, reg0, regw, regv, regd}, m->acc.p, j == 0));
-    if (stats) TRY(read_stats(m, m->acc.p, d->nnz, nb, stats));
-    return FMHIP_OK;
+    return epoch(m, kNames, d, Rates{eta, reg0, regw, regv, regd}, order, stats, pair_up, one_step);
 }
 
 }  // extern "C"

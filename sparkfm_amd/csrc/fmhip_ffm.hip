@@ -2,14 +2,7 @@
 // sequence of a step — fm_ffm.hip's three kernels.  The dataset's layout is built on the host (fmhip_host.cpp: ffm_validate, ffm_build).
 #include "../../include/fmhip_ffm.h"
 #include "fm_ffm.h"
-#include "fmhip_ffm_dataset.h"
-#include "fmhip_internal.h"
-
-#include <algorithm>
-#include <cmath>
-#include <mutex>
-#include <new>
-#include <vector>
+#include "fmhip_field_model.h"
 
 using namespace fmhip;
 using namespace fmhip::host;
@@ -45,38 +38,9 @@ int upload(DevBuf<T> &buf, const std::vector<T> &h) {
 }
 
 // the table codec: the caller's v[((i F) + f) k + d] <-> the device's [i][f][Kp] fp32 (pad slots: `pad`)
-std::vector<float> pack_table(const fmhip_ffm_model *m, const double *v, float pad) {
-    std::vector<float> t(m->vfloats(), pad);
-    const size_t vecs = (size_t)m->n1 * m->F;
-    for (size_t j = 0; j < vecs; ++j)
-        for (int d = 0; d < m->k; ++d) t[j * m->Kp + d] = (float)v[j * m->k + d];
-    return t;
-}
+std::vector<float> pack_vectors(const fmhip_ffm_model *m, const double *v, float pad) { return pack_table((size_t)m->n1 * m->F, m->k, m->Kp, v, pad); }
 
-int read_table(fmhip_ffm_model *m, const float *dev, double *v) {
-    std::vector<float> t(m->vfloats());
-    HIP_TRY(hipMemcpyAsync(t.data(), dev, t.size() * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    const size_t vecs = (size_t)m->n1 * m->F;
-    for (size_t j = 0; j < vecs; ++j)
-        for (int d = 0; d < m->k; ++d) v[j * m->k + d] = t[j * m->Kp + d];
-    return FMHIP_OK;
-}
-
-int read_vector(fmhip_ffm_model *m, const float *dev, size_t n, double *out) {
-    std::vector<float> t(n);
-    HIP_TRY(hipMemcpyAsync(t.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    std::copy(t.begin(), t.end(), out);
-    return FMHIP_OK;
-}
-
-int write_vector(fmhip_ffm_model *m, float *dev, const double *src, size_t n) {
-    std::vector<float> t(src, src + n);
-    HIP_TRY(hipMemcpyAsync(dev, t.data(), n * sizeof(float), hipMemcpyHostToDevice, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    return FMHIP_OK;
-}
+int read_table(fmhip_ffm_model *m, const float *dev, double *v) { return read_vector(m->stream, dev, m->vfloats(), v, m->k, m->Kp); }
 
 // every refusal of (m, d) that needs no launch, then the device and the workspace
 int pair_up(fmhip_ffm_model_t m, fmhip_ffm_dataset_t d, bool train) {
@@ -136,8 +100,6 @@ FfmArgs batch_args(fmhip_ffm_model_t m, fmhip_ffm_dataset_t d, const FfmBatch &b
     return a;
 }
 
-bool rate_ok(double x) { return std::isfinite(x) && x >= 0.0; }
-
 int check_rates(double eta, double reg0, double regw, double regv) {
     if (!std::isfinite(eta) || !rate_ok(reg0) || !rate_ok(regw) || !rate_ok(regv))
         return fail(FMHIP_ERR_INVALID, "eta = %g, reg0 = %g, regw = %g, regv = %g: the step size is finite, a regulariser finite and >= 0", eta, reg0, regw, regv);
@@ -156,17 +118,6 @@ int ffm_step(fmhip_ffm_model_t m, fmhip_ffm_dataset_t d, int64_t b, double eta, 
     HIP_TRY(launch_ffm_forward(a, true, m->stream));
     HIP_TRY(launch_ffm_backward(a, m->stream));
     HIP_TRY(launch_ffm_update(a, m->opt == FMHIP_OPT_ADAGRAD, m->stream));
-    return FMHIP_OK;
-}
-
-int read_stats(fmhip_ffm_model_t m, const double *dev, int64_t nnz, int64_t steps, fmhip_stats *st) {
-    double h[4];
-    HIP_TRY(hipMemcpyAsync(h, dev, sizeof h, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    memset(st, 0, sizeof *st);
-    fill_stats(st, h);
-    st->nnz = nnz;
-    st->steps = steps;
     return FMHIP_OK;
 }
 
@@ -193,17 +144,11 @@ int fmhip_ffm_model_create(int device, int64_t num_attribute, int32_t num_fields
     m->F = num_fields;
     m->k = num_factor;
     m->Kp = num_factor <= 4 ? 4 : (num_factor <= 8 ? 8 : 16);
-    if (stream) {
-        m->stream = reinterpret_cast<hipStream_t>(stream);
-    } else {
-        hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            delete m;
-            return fail(FMHIP_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-        }
-        m->own_stream = true;
+    int rc = open_stream(m, stream);
+    if (rc) {
+        delete m;
+        return rc;
     }
-    int rc;
     hipError_t e = hipSuccess;
     if ((rc = m->V.alloc(m->vfloats())) || (rc = m->w.alloc((size_t)m->n1)) || (rc = m->w0.alloc(1)) || (rc = m->stats.alloc(4)) || (rc = m->acc.alloc(4))) {
         fmhip_ffm_model_destroy(m);
@@ -223,14 +168,7 @@ int fmhip_ffm_model_create(int device, int64_t num_attribute, int32_t num_fields
     return FMHIP_OK;
 }
 
-int fmhip_ffm_model_destroy(fmhip_ffm_model_t m) {
-    if (!m) return FMHIP_OK;
-    (void)hipSetDevice(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    if (m->own_stream && m->stream) (void)hipStreamDestroy(m->stream);
-    delete m;
-    return FMHIP_OK;
-}
+int fmhip_ffm_model_destroy(fmhip_ffm_model_t m) { return destroy_model(m); }
 
 int fmhip_ffm_model_info(fmhip_ffm_model_t m, int64_t *num_attribute, int32_t *num_fields, int32_t *num_factor, int32_t *padded_factors) {
     if (!m) return fail(FMHIP_ERR_INVALID, "the FFM model handle is NULL");
@@ -246,19 +184,17 @@ int fmhip_ffm_model_set_params(fmhip_ffm_model_t m, double w0, const double *w, 
     if (!w || !v) return fail(FMHIP_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> lock(m->mu);
     TRY(set_device(m->device));
-    const std::vector<float> t = pack_table(m, v, 0.f);
-    HIP_TRY(hipMemcpyAsync(m->V.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    TRY(write_vector(m, m->w.p, w, (size_t)m->n1));
-    return write_vector(m, m->w0.p, &w0, 1);
+    TRY(write_floats(m->stream, m->V.p, pack_vectors(m, v, 0.f)));
+    TRY(write_vector(m->stream, m->w.p, w, (size_t)m->n1));
+    return write_vector(m->stream, m->w0.p, &w0, 1);
 }
 
 int fmhip_ffm_model_get_params(fmhip_ffm_model_t m, double *w0, double *w, double *v) {
     if (!m) return fail(FMHIP_ERR_INVALID, "the FFM model handle is NULL");
     std::lock_guard<std::mutex> lock(m->mu);
     TRY(set_device(m->device));
-    if (w0) TRY(read_vector(m, m->w0.p, 1, w0));
-    if (w) TRY(read_vector(m, m->w.p, (size_t)m->n1, w));
+    if (w0) TRY(read_vector(m->stream, m->w0.p, 1, w0));
+    if (w) TRY(read_vector(m->stream, m->w.p, (size_t)m->n1, w));
     if (v) TRY(read_table(m, m->V.p, v));
     return FMHIP_OK;
 }
@@ -311,8 +247,8 @@ int fmhip_ffm_model_get_accumulators(fmhip_ffm_model_t m, double *n0, double *nw
     std::lock_guard<std::mutex> lock(m->mu);
     if (m->opt != FMHIP_OPT_ADAGRAD) return fail(FMHIP_ERR_INVALID, "the model is under SGD: it has no accumulators (fmhip_ffm_model_set_rule)");
     TRY(set_device(m->device));
-    if (n0) TRY(read_vector(m, m->N0.p, 1, n0));
-    if (nw) TRY(read_vector(m, m->Nw.p, (size_t)m->n1, nw));
+    if (n0) TRY(read_vector(m->stream, m->N0.p, 1, n0));
+    if (nw) TRY(read_vector(m->stream, m->Nw.p, (size_t)m->n1, nw));
     if (nv) TRY(read_table(m, m->NV.p, nv));
     return FMHIP_OK;
 }
@@ -329,11 +265,9 @@ int fmhip_ffm_model_set_accumulators(fmhip_ffm_model_t m, double n0, const doubl
     for (size_t j = 0; j < nvals; ++j)
         if (!rate_ok(nv[j])) return fail(FMHIP_ERR_INVALID, "nv[%zu] = %g: an accumulator is finite and >= 0", j, nv[j]);
     TRY(set_device(m->device));
-    const std::vector<float> t = pack_table(m, nv, (float)m->init);
-    HIP_TRY(hipMemcpyAsync(m->NV.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    TRY(write_vector(m, m->Nw.p, nw, (size_t)m->n1));
-    return write_vector(m, m->N0.p, &n0, 1);
+    TRY(write_floats(m->stream, m->NV.p, pack_vectors(m, nv, (float)m->init)));
+    TRY(write_vector(m->stream, m->Nw.p, nw, (size_t)m->n1));
+    return write_vector(m->stream, m->N0.p, &n0, 1);
 }
 
 int fmhip_ffm_dataset_create(int device, int64_t n_rows, const int64_t *row_ptr, const int32_t *col, const int32_t *field, const double *val,
@@ -448,7 +382,7 @@ int fmhip_ffm_step(fmhip_ffm_model_t m, fmhip_ffm_dataset_t d, int64_t batch, do
         return fail(FMHIP_ERR_INVALID, "batch = %lld: the dataset has %zu batches", (long long)batch, d->batches.size());
     TRY(pair_up(m, d, true));
     TRY(ffm_step(m, d, batch, eta, reg0, regw, regv, nullptr));
-    if (stats) TRY(read_stats(m, m->stats.p, d->batches[(size_t)batch].nnz, 1, stats));
+    if (stats) TRY(read_stats(m->stream, m->stats.p, d->batches[(size_t)batch].nnz, 1, stats));
     return FMHIP_OK;
 }
 
@@ -459,13 +393,11 @@ int fmhip_ffm_epoch(fmhip_ffm_model_t m, fmhip_ffm_dataset_t d, double eta, doub
     TRY(check_rates(eta, reg0, regw, regv));
     std::lock_guard<std::mutex> lock(m->mu);
     const int64_t nb = (int64_t)d->batches.size();
-    if (order)
-        for (int64_t j = 0; j < nb; ++j)
-            if (order[j] < 0 || order[j] >= nb) return fail(FMHIP_ERR_INVALID, "order[%lld] = %lld: the dataset has %lld batches", (long long)j, (long long)order[j], (long long)nb);
+    TRY(check_order(order, nb));
     TRY(pair_up(m, d, true));
     // the epoch's sums: the first step's update launch overwrites them, the others add
     for (int64_t j = 0; j < nb; ++j) TRY(ffm_step(m, d, order ? order[j] : j, eta, reg0, regw, regv, m->acc.p, j == 0));
-    if (stats) TRY(read_stats(m, m->acc.p, d->nnz, nb, stats));
+    if (stats) TRY(read_stats(m->stream, m->acc.p, d->nnz, nb, stats));
     return FMHIP_OK;
 }
 

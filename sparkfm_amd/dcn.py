@@ -11,7 +11,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi, metrics
+from . import _ffi
+from ._fieldmodel import FieldLearner, FieldModel, pointers as _pointers
 
 
 def dcn_init(seed, num_attribute, num_fields, num_factor, cross_layers, rank, init_std=0.01):
@@ -25,31 +26,15 @@ def dcn_init(seed, num_attribute, num_fields, num_factor, cross_layers, rank, in
     return v, cross, rng.uniform(-aP, aP, P)
 
 
-def _pointers(arrays):
-    return (C.c_void_p * len(arrays))(*[_ffi.ptr(x) for x in arrays])
-
-
-class DCNModel:
+class DCNModel(FieldModel):
     """w0, w [n + 1], v [n + 1, k], the cross layers [(V_l [F k, r], U_l [r, F k], c_l [F k])] and u [F k] on the device
     (fmhip_dcn_model_t).  A new model is all zero, and an all-zero v has an all-zero gradient: DCN.learnWith draws v and the cross part."""
 
+    _prefix, _info_tail = "fmhip_dcn", 2
+
     def __init__(self, num_attribute, num_fields, num_factor, cross_layers=2, rank=64, device=0, stream=None):
-        self.num_attribute, self.num_fields, self.num_factor, self.device = int(num_attribute), int(num_fields), int(num_factor), int(device)
         self.cross_layers, self.rank = int(cross_layers), int(rank)
-        h = C.c_void_p()
-        _ffi.check(_ffi.load().fmhip_dcn_model_create(self.device, self.num_attribute, self.num_fields, self.num_factor, self.cross_layers, self.rank,
-                                                      stream, C.byref(h)))
-        self._h = h
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def padded_factors(self):
-        kp = C.c_int32()
-        _ffi.check(_ffi.load().fmhip_dcn_model_info(self._h, None, None, None, C.byref(kp), None, None))
-        return kp.value
+        self._create(num_attribute, num_fields, num_factor, device, stream, self.cross_layers, self.rank)
 
     def _zeros(self):
         """(w, v, [V_l], [U_l], [c_l], u) of zeros."""
@@ -100,96 +85,16 @@ class DCNModel:
         _ffi.check(_ffi.load().fmhip_dcn_model_set_accumulators(self._h, float(n0), _ffi.ptr(nw), _ffi.ptr(nv), _pointers(Vs), _pointers(Us),
                                                                 _pointers(cs), _ffi.ptr(nu)))
 
-    def predict(self, dataset):
-        """The margins yhat of the rows (fmhip_dcn_predict), float64."""
-        yh = np.zeros(dataset.size)
-        _ffi.check(_ffi.load().fmhip_dcn_predict(self._h, dataset.handle, _ffi.ptr(yh)))
-        return yh
 
-    def computeRMSE(self, dataset):
-        return float(np.sqrt(np.mean((self.predict(dataset) - dataset.y) ** 2))) if dataset.size else 0.0
-
-    def computeLogLoss(self, dataset):
-        """Mean log-loss of sigmoid(predict) against t = [y > 0]: max(yhat, 0) - t yhat + log1p(exp(-|yhat|))."""
-        if not dataset.size:
-            return 0.0
-        yh, t = self.predict(dataset), dataset.y > 0
-        return float(np.mean(np.maximum(yh, 0.0) - t * yh + np.log1p(np.exp(-np.abs(yh)))))
-
-    def computeAUC(self, dataset):
-        """ROC AUC of the predictions against t = [y > 0], exact, ties one half (sparkfm_amd.metrics.auc)."""
-        return metrics.auc(self.predict(dataset), dataset.y, device=self.device)["auc"]
-
-    def computeAccuracy(self, dataset):
-        if not dataset.size:
-            return 0.0
-        return float(((self.predict(dataset) >= 0) == (dataset.y > 0)).mean())
-
-    def close(self):
-        if self._h is not None:
-            _ffi.load().fmhip_dcn_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class HipDCN:
+class HipDCN(FieldLearner):
     """The DCN-V2 learner: mini-batch SGD or AdaGrad; v and w of the features a batch holds move, the cross part and w0 every batch.
     cross=False never steps V_l, U_l, c_l and u; linear=False never steps w0 and w."""
 
+    _prefix, _flag, _reg = "fmhip_dcn", "cross", "regd"
+
     def __init__(self, loss="logistic", optimizer="adagrad", eta=0.1, reg0=0.0, regw=0.0, regv=1e-5, regd=0.0, linear=True, cross=True,
                  maxIteration=10, adagrad_eps=1e-10, adagrad_init=1.0):
-        self.loss_code, self.opt_code = _ffi.loss_code(loss), _ffi.optimizer_code(optimizer)
-        self.adagrad_eps, self.adagrad_init = _ffi.adagrad_settings(adagrad_eps, adagrad_init)
-        for name, x in (("eta", eta), ("reg0", reg0), ("regw", regw), ("regv", regv), ("regd", regd)):
-            if not (np.isfinite(x) and x >= 0):
-                raise ValueError("%s must be finite and >= 0, not %r" % (name, x))
-        for name, x in (("linear", linear), ("cross", cross)):
-            if not isinstance(x, bool):
-                raise ValueError("%s must be True or False, not %r" % (name, x))
-        self.loss, self.optimizer, self.linear, self.cross = loss, optimizer, linear, cross
-        self.eta, self.rates = float(eta), (float(reg0), float(regw), float(regv), float(regd))
-        self.maxIteration = int(maxIteration)
-        self.last_stats = None
-
-    @classmethod
-    def run(cls, **kw):
-        return cls(**kw)
-
-    def _set_rule(self, model):
-        L = _ffi.load()
-        _ffi.check(L.fmhip_dcn_model_set_rule(model.handle, self.loss_code, self.opt_code, self.adagrad_eps, self.adagrad_init))
-        _ffi.check(L.fmhip_dcn_model_set_linear(model.handle, int(self.linear)))
-        _ffi.check(L.fmhip_dcn_model_set_cross(model.handle, int(self.cross)))
-
-    def step(self, model, dataset, batch, stats=True):
-        """One mini-batch step (fmhip_dcn_step) -> the batch's statistics (None with stats=False: no host synchronisation)."""
-        self._set_rule(model)
-        st = _ffi.Stats()
-        _ffi.check(_ffi.load().fmhip_dcn_step(model.handle, dataset.handle, int(batch), self.eta, *self.rates, C.byref(st) if stats else None))
-        self.last_stats = st.as_dict() if stats else None
-        return self.last_stats
-
-    def learn(self, model, dataset, order=None):
-        """One epoch (fmhip_dcn_epoch) over the batches in `order` (None: ascending) -> model."""
-        self._set_rule(model)
-        st = _ffi.Stats()
-        o = None if order is None else np.ascontiguousarray(order, np.int64)
-        if o is not None and o.shape != (dataset.n_batches,):
-            raise ValueError("order must hold one id per batch (%d)" % dataset.n_batches)
-        _ffi.check(_ffi.load().fmhip_dcn_epoch(model.handle, dataset.handle, self.eta, *self.rates, _ffi.ptr(o), C.byref(st)))
-        self.last_stats = st.as_dict()
-        return model
-
-    def fit(self, model, dataset):
-        """maxIteration epochs over the batches in ascending order."""
-        for _ in range(self.maxIteration):
-            self.learn(model, dataset)
-        return model
+        self._setup(loss, optimizer, eta, reg0, regw, regv, regd, linear, cross, maxIteration, adagrad_eps, adagrad_init)
 
 
 class DCN:

@@ -10,7 +10,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi, metrics
+from . import _ffi
+from ._fieldmodel import FieldLearner, FieldModel
 
 
 class FFMDataSet:
@@ -95,24 +96,13 @@ class FFMDataSet:
             pass
 
 
-class FFMModel:
+class FFMModel(FieldModel):
     """w0, w [n + 1] and v [n + 1, F, k] on the device (fmhip_ffm_model_t).  New parameters are zero; FFM.learnWith draws libffm's init."""
 
+    _prefix = "fmhip_ffm"
+
     def __init__(self, num_attribute, num_fields, num_factor, device=0, stream=None):
-        self.num_attribute, self.num_fields, self.num_factor, self.device = int(num_attribute), int(num_fields), int(num_factor), int(device)
-        h = C.c_void_p()
-        _ffi.check(_ffi.load().fmhip_ffm_model_create(self.device, self.num_attribute, self.num_fields, self.num_factor, stream, C.byref(h)))
-        self._h = h
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def padded_factors(self):
-        kp = C.c_int32()
-        _ffi.check(_ffi.load().fmhip_ffm_model_info(self._h, None, None, None, C.byref(kp)))
-        return kp.value
+        self._create(num_attribute, num_fields, num_factor, device, stream)
 
     def _shape(self):
         return (self.num_attribute + 1, self.num_fields, self.num_factor)
@@ -144,46 +134,12 @@ class FFMModel:
             raise ValueError("nw must have shape %r and nv shape %r" % ((self.num_attribute + 1,), self._shape()))
         _ffi.check(_ffi.load().fmhip_ffm_model_set_accumulators(self._h, float(n0), _ffi.ptr(nw), _ffi.ptr(nv)))
 
-    def predict(self, dataset):
-        """The margins yhat of the rows (fmhip_ffm_predict), float64."""
-        yh = np.zeros(dataset.size)
-        _ffi.check(_ffi.load().fmhip_ffm_predict(self._h, dataset.handle, _ffi.ptr(yh)))
-        return yh
 
-    def computeRMSE(self, dataset):
-        return float(np.sqrt(np.mean((self.predict(dataset) - dataset.y) ** 2))) if dataset.size else 0.0
-
-    def computeLogLoss(self, dataset):
-        """Mean log-loss of sigmoid(predict) against t = [y > 0]: max(yhat, 0) - t yhat + log1p(exp(-|yhat|))."""
-        if not dataset.size:
-            return 0.0
-        yh, t = self.predict(dataset), dataset.y > 0
-        return float(np.mean(np.maximum(yh, 0.0) - t * yh + np.log1p(np.exp(-np.abs(yh)))))
-
-    def computeAUC(self, dataset):
-        """ROC AUC of the predictions against t = [y > 0], exact, ties one half (sparkfm_amd.metrics.auc)."""
-        return metrics.auc(self.predict(dataset), dataset.y, device=self.device)["auc"]
-
-    def computeAccuracy(self, dataset):
-        if not dataset.size:
-            return 0.0
-        return float(((self.predict(dataset) >= 0) == (dataset.y > 0)).mean())
-
-    def close(self):
-        if self._h is not None:
-            _ffi.load().fmhip_ffm_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class HipFFM:
+class HipFFM(FieldLearner):
     """The FFM learner: mini-batch SGD or AdaGrad with libffm's lazy regularisation (only what a batch touches moves).
     linear=False is libffm's model: w0 and w are left as they are (0 from FFM.learnWith) and never stepped."""
+
+    _prefix = "fmhip_ffm"          # (no array of its own: no _flag, three regularisers)
 
     def __init__(self, loss="logistic", optimizer="adagrad", eta=0.2, regv=2e-5, regw=0.0, reg0=0.0, linear=True, maxIteration=10, seed=0,
                  adagrad_eps=1e-10, adagrad_init=1.0):
@@ -196,43 +152,9 @@ class HipFFM:
             raise ValueError("linear must be True or False, not %r" % (linear,))
         self.loss, self.optimizer, self.linear = loss, optimizer, linear
         self.eta, self.regv, self.regw, self.reg0 = float(eta), float(regv), float(regw), float(reg0)
+        self.rates = (self.reg0, self.regw, self.regv)
         self.maxIteration, self.seed = int(maxIteration), int(seed)
         self.last_stats = None
-
-    @classmethod
-    def run(cls, **kw):
-        return cls(**kw)
-
-    def _set_rule(self, model):
-        L = _ffi.load()
-        _ffi.check(L.fmhip_ffm_model_set_rule(model.handle, self.loss_code, self.opt_code, self.adagrad_eps, self.adagrad_init))
-        _ffi.check(L.fmhip_ffm_model_set_linear(model.handle, int(self.linear)))
-
-    def step(self, model, dataset, batch, stats=True):
-        """One mini-batch step (fmhip_ffm_step) -> the batch's statistics (None with stats=False: no host synchronisation)."""
-        self._set_rule(model)
-        st = _ffi.Stats()
-        _ffi.check(_ffi.load().fmhip_ffm_step(model.handle, dataset.handle, int(batch), self.eta, self.reg0, self.regw, self.regv,
-                                             C.byref(st) if stats else None))
-        self.last_stats = st.as_dict() if stats else None
-        return self.last_stats
-
-    def learn(self, model, dataset, order=None):
-        """One epoch (fmhip_ffm_epoch) over the batches in `order` (None: ascending) -> model."""
-        self._set_rule(model)
-        st = _ffi.Stats()
-        o = None if order is None else np.ascontiguousarray(order, np.int64)
-        if o is not None and o.shape != (dataset.n_batches,):
-            raise ValueError("order must hold one id per batch (%d)" % dataset.n_batches)
-        _ffi.check(_ffi.load().fmhip_ffm_epoch(model.handle, dataset.handle, self.eta, self.reg0, self.regw, self.regv, _ffi.ptr(o), C.byref(st)))
-        self.last_stats = st.as_dict()
-        return model
-
-    def fit(self, model, dataset):
-        """maxIteration epochs over the batches in ascending order."""
-        for _ in range(self.maxIteration):
-            self.learn(model, dataset)
-        return model
 
 
 def libffm_init(seed, num_attribute, num_fields, num_factor):

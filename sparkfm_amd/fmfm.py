@@ -11,7 +11,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi, metrics
+from . import _ffi
+from ._fieldmodel import FieldLearner, FieldModel
 
 
 def identity_matrices(num_fields, num_factor):
@@ -22,25 +23,14 @@ def identity_matrices(num_fields, num_factor):
     return m
 
 
-class FmFMModel:
+class FmFMModel(FieldModel):
     """w0, w [n + 1], v [n + 1, k] and the field matrices m [F, F, k, k] on the device (fmhip_fmfm_model_t).  A new model has
     v = w = w0 = 0 and m[f][g] = I for f != g; FmFM.learnWith draws v."""
 
+    _prefix = "fmhip_fmfm"
+
     def __init__(self, num_attribute, num_fields, num_factor, device=0, stream=None):
-        self.num_attribute, self.num_fields, self.num_factor, self.device = int(num_attribute), int(num_fields), int(num_factor), int(device)
-        h = C.c_void_p()
-        _ffi.check(_ffi.load().fmhip_fmfm_model_create(self.device, self.num_attribute, self.num_fields, self.num_factor, stream, C.byref(h)))
-        self._h = h
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def padded_factors(self):
-        kp = C.c_int32()
-        _ffi.check(_ffi.load().fmhip_fmfm_model_info(self._h, None, None, None, C.byref(kp)))
-        return kp.value
+        self._create(num_attribute, num_fields, num_factor, device, stream)
 
     def _zeros(self):
         return (np.zeros(self.num_attribute + 1), np.zeros((self.num_attribute + 1, self.num_factor)),
@@ -78,96 +68,17 @@ class FmFMModel:
         nw, nv, nm = self._checked(("nw", "nv", "nm"), (nw, nv, nm))
         _ffi.check(_ffi.load().fmhip_fmfm_model_set_accumulators(self._h, float(n0), _ffi.ptr(nw), _ffi.ptr(nv), _ffi.ptr(nm)))
 
-    def predict(self, dataset):
-        """The margins yhat of the rows (fmhip_fmfm_predict), float64."""
-        yh = np.zeros(dataset.size)
-        _ffi.check(_ffi.load().fmhip_fmfm_predict(self._h, dataset.handle, _ffi.ptr(yh)))
-        return yh
 
-    def computeRMSE(self, dataset):
-        return float(np.sqrt(np.mean((self.predict(dataset) - dataset.y) ** 2))) if dataset.size else 0.0
-
-    def computeLogLoss(self, dataset):
-        """Mean log-loss of sigmoid(predict) against t = [y > 0]: max(yhat, 0) - t yhat + log1p(exp(-|yhat|))."""
-        if not dataset.size:
-            return 0.0
-        yh, t = self.predict(dataset), dataset.y > 0
-        return float(np.mean(np.maximum(yh, 0.0) - t * yh + np.log1p(np.exp(-np.abs(yh)))))
-
-    def computeAUC(self, dataset):
-        """ROC AUC of the predictions against t = [y > 0], exact, ties one half (sparkfm_amd.metrics.auc)."""
-        return metrics.auc(self.predict(dataset), dataset.y, device=self.device)["auc"]
-
-    def computeAccuracy(self, dataset):
-        if not dataset.size:
-            return 0.0
-        return float(((self.predict(dataset) >= 0) == (dataset.y > 0)).mean())
-
-    def close(self):
-        if self._h is not None:
-            _ffi.load().fmhip_fmfm_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class HipFmFM:
+class HipFmFM(FieldLearner):
     """The FmFM learner: mini-batch SGD or AdaGrad; v and w of the features a batch holds move, the field matrices and w0 every batch.
     field_matrices=False never steps m (with m = I: the plain FM on rows of one entry per field); linear=False never steps w0 and w."""
 
+    _prefix, _flag, _reg = "fmhip_fmfm", "field_matrices", "regm"
+
     def __init__(self, loss="logistic", optimizer="adagrad", eta=0.1, reg0=0.0, regw=0.0, regv=1e-5, regm=0.0, linear=True, field_matrices=True,
                  maxIteration=10, seed=0, adagrad_eps=1e-10, adagrad_init=1.0):
-        self.loss_code, self.opt_code = _ffi.loss_code(loss), _ffi.optimizer_code(optimizer)
-        self.adagrad_eps, self.adagrad_init = _ffi.adagrad_settings(adagrad_eps, adagrad_init)
-        for name, x in (("eta", eta), ("reg0", reg0), ("regw", regw), ("regv", regv), ("regm", regm)):
-            if not (np.isfinite(x) and x >= 0):
-                raise ValueError("%s must be finite and >= 0, not %r" % (name, x))
-        for name, x in (("linear", linear), ("field_matrices", field_matrices)):
-            if not isinstance(x, bool):
-                raise ValueError("%s must be True or False, not %r" % (name, x))
-        self.loss, self.optimizer, self.linear, self.field_matrices = loss, optimizer, linear, field_matrices
-        self.eta, self.rates = float(eta), (float(reg0), float(regw), float(regv), float(regm))
-        self.maxIteration, self.seed = int(maxIteration), int(seed)
-        self.last_stats = None
-
-    @classmethod
-    def run(cls, **kw):
-        return cls(**kw)
-
-    def _set_rule(self, model):
-        L = _ffi.load()
-        _ffi.check(L.fmhip_fmfm_model_set_rule(model.handle, self.loss_code, self.opt_code, self.adagrad_eps, self.adagrad_init))
-        _ffi.check(L.fmhip_fmfm_model_set_linear(model.handle, int(self.linear)))
-        _ffi.check(L.fmhip_fmfm_model_set_field_matrices(model.handle, int(self.field_matrices)))
-
-    def step(self, model, dataset, batch, stats=True):
-        """One mini-batch step (fmhip_fmfm_step) -> the batch's statistics (None with stats=False: no host synchronisation)."""
-        self._set_rule(model)
-        st = _ffi.Stats()
-        _ffi.check(_ffi.load().fmhip_fmfm_step(model.handle, dataset.handle, int(batch), self.eta, *self.rates, C.byref(st) if stats else None))
-        self.last_stats = st.as_dict() if stats else None
-        return self.last_stats
-
-    def learn(self, model, dataset, order=None):
-        """One epoch (fmhip_fmfm_epoch) over the batches in `order` (None: ascending) -> model."""
-        self._set_rule(model)
-        st = _ffi.Stats()
-        o = None if order is None else np.ascontiguousarray(order, np.int64)
-        if o is not None and o.shape != (dataset.n_batches,):
-            raise ValueError("order must hold one id per batch (%d)" % dataset.n_batches)
-        _ffi.check(_ffi.load().fmhip_fmfm_epoch(model.handle, dataset.handle, self.eta, *self.rates, _ffi.ptr(o), C.byref(st)))
-        self.last_stats = st.as_dict()
-        return model
-
-    def fit(self, model, dataset):
-        """maxIteration epochs over the batches in ascending order."""
-        for _ in range(self.maxIteration):
-            self.learn(model, dataset)
-        return model
+        self._setup(loss, optimizer, eta, reg0, regw, regv, regm, linear, field_matrices, maxIteration, adagrad_eps, adagrad_init)
+        self.seed = int(seed)
 
 
 class FmFM:
