@@ -17,6 +17,7 @@ from .fmfm import FmFM, FmFMModel, HipFmFM  # noqa: F401
 from .deepfm import DeepFM, DeepFMModel, HipDeepFM  # noqa: F401
 from .dcn import DCN, DCNModel, HipDCN  # noqa: F401
 from .autoint import AutoInt, AutoIntModel, HipAutoInt  # noqa: F401
+from .cin import CIN, CINModel, HipCIN  # noqa: F401
 from .fm import FM, FactorizationMachines, Task  # noqa: F401
 from .datacollection import DataCollection  # noqa: F401
 from .feature_order import FeatureOrder  # noqa: F401
@@ -26,4 +27,4 @@ __all__ = ["DataSet", "Features", "FMModel", "Model", "FMLearn", "HipSGD", "HipS
            "DataCollection", "FMUtils", "FeatureOrder", "Relation", "RelationalData", "Metadata",
            "FFM", "FFMDataSet", "FFMModel", "HipFFM", "FwFM", "FwFMModel", "HipFwFM", "FmFM", "FmFMModel", "HipFmFM",
            "DeepFM", "DeepFMModel", "HipDeepFM", "DCN", "DCNModel", "HipDCN",
-           "AutoInt", "AutoIntModel", "HipAutoInt"]
+           "AutoInt", "AutoIntModel", "HipAutoInt", "CIN", "CINModel", "HipCIN"]

@@ -134,6 +134,13 @@ SYMBOLS_AUTOINT = ("fmhip_autoint_model_create", "fmhip_autoint_model_destroy", 
 # FMHIP_AUTOINT_MAX_FIELDS, _FACTORS, _LAYERS, _HEADS, _HEAD_DIM, _WIDTH
 AUTOINT_MAX_FIELDS, AUTOINT_MAX_FACTORS, AUTOINT_MAX_LAYERS, AUTOINT_MAX_HEADS, AUTOINT_MAX_HEAD_DIM, AUTOINT_MAX_WIDTH = 64, 16, 3, 4, 32, 64
 AUTOINT_FORWARD_ROWS = 128      # csrc/fm_autoint.h's kAutoIntRowsPerBlock
+# ... and include/fmhip_cin.h — xDeepFM's CIN: vector-wise feature maps over the field sums, over the same dataset handle
+SYMBOLS_CIN = ("fmhip_cin_model_create", "fmhip_cin_model_destroy", "fmhip_cin_model_info", "fmhip_cin_model_set_params",
+               "fmhip_cin_model_get_params", "fmhip_cin_model_set_rule", "fmhip_cin_model_set_linear", "fmhip_cin_model_set_cin",
+               "fmhip_cin_model_get_accumulators", "fmhip_cin_model_set_accumulators", "fmhip_cin_predict", "fmhip_cin_step", "fmhip_cin_epoch")
+# FMHIP_CIN_MAX_FIELDS, _FACTORS, _LAYERS, _MAPS
+CIN_MAX_FIELDS, CIN_MAX_FACTORS, CIN_MAX_LAYERS, CIN_MAX_MAPS = 64, 16, 3, 128
+CIN_FORWARD_ROWS, CIN_GRAD_ROWS = 128, 512      # csrc/fm_cin.h's kCinRowsPerBlock, kCinGradRows
 OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
@@ -723,9 +730,22 @@ def load():
     L.fmhip_autoint_predict.argtypes = [vp, vp, vp]
     L.fmhip_autoint_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl, P(Stats)]
     L.fmhip_autoint_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, dbl, vp, P(Stats)]
+    L.fmhip_cin_model_create.argtypes = [C.c_int, i64, i32, i32, i32, P(i32), vp, P(vp)]
+    L.fmhip_cin_model_destroy.argtypes = [vp]
+    L.fmhip_cin_model_info.argtypes = [vp, P(i64), P(i32), P(i32), P(i32), P(i32), P(i32)]
+    L.fmhip_cin_model_set_params.argtypes = [vp, dbl, vp, vp, P(vp), vp]
+    L.fmhip_cin_model_get_params.argtypes = [vp, P(dbl), vp, vp, P(vp), vp]
+    L.fmhip_cin_model_set_rule.argtypes = [vp, C.c_int, C.c_int, dbl, dbl]
+    L.fmhip_cin_model_set_linear.argtypes = [vp, C.c_int]
+    L.fmhip_cin_model_set_cin.argtypes = [vp, C.c_int]
+    L.fmhip_cin_model_get_accumulators.argtypes = [vp, P(dbl), vp, vp, P(vp), vp]
+    L.fmhip_cin_model_set_accumulators.argtypes = [vp, dbl, vp, vp, P(vp), vp]
+    L.fmhip_cin_predict.argtypes = [vp, vp, vp]
+    L.fmhip_cin_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl, P(Stats)]
+    L.fmhip_cin_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, dbl, vp, P(Stats)]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM + SYMBOLS_FWFM + SYMBOLS_FMFM + SYMBOLS_DEEPFM + SYMBOLS_DCN + SYMBOLS_AUTOINT):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM + SYMBOLS_FWFM + SYMBOLS_FMFM + SYMBOLS_DEEPFM + SYMBOLS_DCN + SYMBOLS_AUTOINT + SYMBOLS_CIN):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

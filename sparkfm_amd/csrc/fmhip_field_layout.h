@@ -157,6 +157,41 @@ struct AutoIntSlots {
     }
 };
 
+// CIN (fm_cin.h): W_l [H_l][hp_l][Fp] at woff[l - 1] (hp_1 = Fp = F rounded up to 16, hp_l = H_{l-1} above), field j of a row at
+// position pos(j) — the MFMA order, its own inverse —, then u [H_1 + .. + H_L] at uoff.  Arrays: 0 = W [H_l][H_{l-1}][F] (per layer),
+// 1 = u
+struct CinSlots {
+    static constexpr int kLayered = 1;          // the leading arrays that come one per layer
+    int32_t F = 0, k = 0, Fp = 0, L = 0;
+    int32_t H[kFieldMaxLayers + 1] = {};          // H[0] = F, H[l] = H_l
+    int32_t woff[kFieldMaxLayers] = {}, uoff = 0, n_total = 0;
+    CinSlots() = default;
+    CinSlots(int32_t fields, int32_t factors, int32_t n_layers, const int32_t *maps) : F(fields), k(factors), Fp(round16(fields)), L(n_layers) {
+        H[0] = F;
+        int32_t at = 0;
+        for (int l = 1; l <= L; ++l) {
+            H[l] = maps[l - 1];
+            woff[l - 1] = at;
+            at += H[l] * stored(l) * Fp;
+        }
+        uoff = at;
+        for (int l = 1; l <= L; ++l) at += H[l];
+        n_total = at;
+    }
+    size_t total() const { return (size_t)n_total; }
+    int stored(int l) const { return l == 1 ? Fp : H[l - 1]; }          // the device's H_{l-1}
+    static int pos(int j) { return (j & ~15) + 4 * (j & 3) + ((j >> 2) & 3); }
+    static const char *name(int a) { return a == 0 ? "W" : "u"; }
+    template <class Fn> void each(Fn f) const {
+        for (int l = 1; l <= L; ++l)
+            for (int h = 0; h < H[l]; ++h)
+                for (int i = 0; i < H[l - 1]; ++i)
+                    for (int j = 0; j < F; ++j)
+                        f(0, l - 1, ((size_t)h * H[l - 1] + i) * F + j, woff[l - 1] + ((size_t)h * stored(l) + i) * Fp + pos(j));
+        for (int i = 0; i < n_total - uoff; ++i) f(1, 0, (size_t)i, (size_t)uoff + i);
+    }
+};
+
 // the caller's arrays -> the device's one array; src(array, layer): the array's doubles.  The elements no slot maps to: `pad`
 template <class Map, class Src>
 std::vector<float> pack_slots(const Map &m, Src src, float pad) {
