@@ -192,6 +192,24 @@ struct CinSlots {
     }
 };
 
+// AFM (fm_afm.h): W [t][Kp] (the caller's row of k floats at the head of the device's row of Kp: a lane of the forward reads Kp / 4
+// consecutive floats of it), then b [t], h [t] and p [Kp].  Arrays: 0 = W [t][k], 1 = b, 2 = h, 3 = p
+struct AfmSlots {
+    static constexpr int kLayered = 0;          // the leading arrays that come one per layer
+    int32_t F = 0, k = 0, Kp = 0, t = 0;
+    AfmSlots() = default;
+    AfmSlots(int32_t fields, int32_t factors, int32_t attention) : F(fields), k(factors), Kp(field_kp(factors)), t(attention) {}
+    size_t total() const { return (size_t)t * Kp + 2 * (size_t)t + Kp; }
+    static const char *name(int a) { return a == 0 ? "W" : (a == 1 ? "b" : (a == 2 ? "h" : "p")); }
+    template <class Fn> void each(Fn f) const {
+        for (int n = 0; n < t; ++n)
+            for (int d = 0; d < k; ++d) f(0, 0, (size_t)n * k + d, (size_t)n * Kp + d);
+        for (int n = 0; n < t; ++n) f(1, 0, (size_t)n, (size_t)t * Kp + n);
+        for (int n = 0; n < t; ++n) f(2, 0, (size_t)n, (size_t)t * Kp + t + n);
+        for (int d = 0; d < k; ++d) f(3, 0, (size_t)d, (size_t)t * Kp + 2 * (size_t)t + d);
+    }
+};
+
 // the caller's arrays -> the device's one array; src(array, layer): the array's doubles.  The elements no slot maps to: `pad`
 template <class Map, class Src>
 std::vector<float> pack_slots(const Map &m, Src src, float pad) {
