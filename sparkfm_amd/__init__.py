@@ -19,6 +19,7 @@ from .dcn import DCN, DCNModel, HipDCN  # noqa: F401
 from .autoint import AutoInt, AutoIntModel, HipAutoInt  # noqa: F401
 from .cin import CIN, CINModel, HipCIN  # noqa: F401
 from .afm import AFM, AFMModel, HipAFM  # noqa: F401
+from .pnn import PNN, PNNModel, HipPNN  # noqa: F401
 from .fm import FM, FactorizationMachines, Task  # noqa: F401
 from .datacollection import DataCollection  # noqa: F401
 from .feature_order import FeatureOrder  # noqa: F401
@@ -28,4 +29,5 @@ __all__ = ["DataSet", "Features", "FMModel", "Model", "FMLearn", "HipSGD", "HipS
            "DataCollection", "FMUtils", "FeatureOrder", "Relation", "RelationalData", "Metadata",
            "FFM", "FFMDataSet", "FFMModel", "HipFFM", "FwFM", "FwFMModel", "HipFwFM", "FmFM", "FmFMModel", "HipFmFM",
            "DeepFM", "DeepFMModel", "HipDeepFM", "DCN", "DCNModel", "HipDCN",
-           "AutoInt", "AutoIntModel", "HipAutoInt", "CIN", "CINModel", "HipCIN", "AFM", "AFMModel", "HipAFM"]
+           "AutoInt", "AutoIntModel", "HipAutoInt", "CIN", "CINModel", "HipCIN", "AFM", "AFMModel", "HipAFM",
+           "PNN", "PNNModel", "HipPNN"]

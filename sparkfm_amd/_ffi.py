@@ -147,6 +147,13 @@ SYMBOLS_AFM = ("fmhip_afm_model_create", "fmhip_afm_model_destroy", "fmhip_afm_m
                "fmhip_afm_model_get_accumulators", "fmhip_afm_model_set_accumulators", "fmhip_afm_predict", "fmhip_afm_step", "fmhip_afm_epoch")
 AFM_MAX_FIELDS, AFM_MAX_FACTORS, AFM_MAX_ATTENTION = 64, 16, 64      # FMHIP_AFM_MAX_FIELDS, _FACTORS, _ATTENTION
 AFM_FORWARD_ROWS = 128      # csrc/fm_afm.h's kAfmRowsPerBlock
+# ... and include/fmhip_pnn.h — the product-based neural network: an MLP over the field sums and their pairwise inner products
+SYMBOLS_PNN = ("fmhip_pnn_model_create", "fmhip_pnn_model_destroy", "fmhip_pnn_model_info", "fmhip_pnn_model_set_params",
+               "fmhip_pnn_model_get_params", "fmhip_pnn_model_set_rule", "fmhip_pnn_model_set_linear", "fmhip_pnn_model_set_deep",
+               "fmhip_pnn_model_get_accumulators", "fmhip_pnn_model_set_accumulators", "fmhip_pnn_predict", "fmhip_pnn_step", "fmhip_pnn_epoch")
+# FMHIP_PNN_MAX_FIELDS, _FACTORS, _LAYERS, _UNITS, _WIDTH
+PNN_MAX_FIELDS, PNN_MAX_FACTORS, PNN_MAX_LAYERS, PNN_MAX_UNITS, PNN_MAX_WIDTH = 64, 16, 3, 256, 1408
+PNN_FORWARD_ROWS = 128      # csrc/fm_pnn.h's kPnnRowsPerBlock
 OPT_FTRL = 2               # FMHIP_OPT_FTRL: reported, never accepted by fmhip_model_set_optimizer (not in OPTIMIZERS)
 # enum fmhip_tune_key (include/fmhip_experimental.h); TUNE maps the names without their prefix
 (TUNE_FORWARD_KERNEL, TUNE_BACKWARD_KERNEL, TUNE_TILE_ROWS, TUNE_ROW_BLOCK, TUNE_XCD_PLACEMENT, TUNE_HOT_BLOCK, TUNE_FORWARD_OCCUPANCY,
@@ -762,9 +769,22 @@ def load():
     L.fmhip_afm_predict.argtypes = [vp, vp, vp]
     L.fmhip_afm_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl, P(Stats)]
     L.fmhip_afm_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, dbl, vp, P(Stats)]
+    L.fmhip_pnn_model_create.argtypes = [C.c_int, i64, i32, i32, i32, P(i32), vp, P(vp)]
+    L.fmhip_pnn_model_destroy.argtypes = [vp]
+    L.fmhip_pnn_model_info.argtypes = [vp, P(i64), P(i32), P(i32), P(i32), P(i32), P(i32)]
+    L.fmhip_pnn_model_set_params.argtypes = [vp, dbl, vp, vp, P(vp), P(vp), vp]
+    L.fmhip_pnn_model_get_params.argtypes = [vp, P(dbl), vp, vp, P(vp), P(vp), vp]
+    L.fmhip_pnn_model_set_rule.argtypes = [vp, C.c_int, C.c_int, dbl, dbl]
+    L.fmhip_pnn_model_set_linear.argtypes = [vp, C.c_int]
+    L.fmhip_pnn_model_set_deep.argtypes = [vp, C.c_int]
+    L.fmhip_pnn_model_get_accumulators.argtypes = [vp, P(dbl), vp, vp, P(vp), P(vp), vp]
+    L.fmhip_pnn_model_set_accumulators.argtypes = [vp, dbl, vp, vp, P(vp), P(vp), vp]
+    L.fmhip_pnn_predict.argtypes = [vp, vp, vp]
+    L.fmhip_pnn_step.argtypes = [vp, vp, i64, dbl, dbl, dbl, dbl, dbl, P(Stats)]
+    L.fmhip_pnn_epoch.argtypes = [vp, vp, dbl, dbl, dbl, dbl, dbl, vp, P(Stats)]
     for name in (SYMBOLS + SYMBOLS_EXPERIMENTAL + SYMBOLS_TOPK + SYMBOLS_PAIRING + SYMBOLS_METRICS + SYMBOLS_RANKING + SYMBOLS_WEIGHTS
                  + SYMBOLS_RELATIONAL + SYMBOLS_MCMC + SYMBOLS_MCMC_TASK + SYMBOLS_MCMC_GROUPS + SYMBOLS_MCMC_RELATIONAL + SYMBOLS_BPR + SYMBOLS_BPR_ADAPTIVE
-                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM + SYMBOLS_FWFM + SYMBOLS_FMFM + SYMBOLS_DEEPFM + SYMBOLS_DCN + SYMBOLS_AUTOINT + SYMBOLS_CIN + SYMBOLS_AFM):
+                 + SYMBOLS_WARP + SYMBOLS_FTRL + SYMBOLS_REDRAW + SYMBOLS_SGDA + SYMBOLS_PROPOSAL + SYMBOLS_SOFTMAX + SYMBOLS_FFM + SYMBOLS_FWFM + SYMBOLS_FMFM + SYMBOLS_DEEPFM + SYMBOLS_DCN + SYMBOLS_AUTOINT + SYMBOLS_CIN + SYMBOLS_AFM + SYMBOLS_PNN):
         fn = getattr(L, name)
         if name not in ("fmhip_version", "fmhip_last_error"):
             fn.restype = C.c_int

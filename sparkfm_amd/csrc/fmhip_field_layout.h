@@ -210,6 +210,65 @@ struct AfmSlots {
     }
 };
 
+// PNN (fm_pnn.h): DeepFM's order — W_l at woff[l - 1], then u, then the b_l — with a taller W_1: the caller's n_0 = F k + G rows
+// ([s | g], G = F (F - 1) / 2 pairs i < j, ascending in i, then in j) sit in n0p rows on the device: row f k + d at f Kp + d, the
+// pair (i, j) in its Gram tile (i / 16, j / 16) at the tile's first row + (i % 16) 16 + j % 16.  The tiles on and above the diagonal
+// follow one another behind the Pp field rows in ascending (mt, nt); a tile keeps its first ns slices of 16 rows — those that hold a
+// pair: 16 off the diagonal, min(F - 16 mt, 16) - 1 on it.  Arrays: 0 = W, 1 = b (per layer), 2 = u
+struct PnnSlots {
+    static constexpr int kLayered = 2;          // the leading arrays that come one per layer
+    int32_t F = 0, k = 0, Kp = 0, Pp = 0, G = 0, L = 0;
+    int32_t width[kFieldMaxLayers + 1] = {};          // width[0] = n0p on the device (F k + G for the caller), width[l] = n_l
+    int32_t woff[kFieldMaxLayers] = {}, boff[kFieldMaxLayers] = {}, uoff = 0, n_total = 0;
+    int32_t tile_off[4][4] = {};          // [mt][nt]: the tile's first row of W_1
+    PnnSlots() = default;
+    PnnSlots(int32_t fields, int32_t factors, int32_t n_layers, const int32_t *widths)
+        : F(fields), k(factors), Kp(field_kp(factors)), Pp(round16(fields * Kp)), G(fields * (fields - 1) / 2), L(n_layers) {
+        int32_t at = Pp;
+        for (int m = 0; m < (F + 15) / 16 && m < 4; ++m)
+            for (int n = m; n < (F + 15) / 16 && n < 4; ++n) {
+                tile_off[m][n] = at;
+                at += 16 * slices(m, n);
+            }
+        width[0] = at;
+        at = 0;
+        for (int l = 1; l <= L; ++l) {
+            width[l] = widths[l - 1];
+            woff[l - 1] = at;
+            at += width[l - 1] * width[l];
+        }
+        uoff = at;
+        at += width[L];
+        for (int l = 1; l <= L; ++l) {
+            boff[l - 1] = at;
+            at += width[l];
+        }
+        n_total = at;
+    }
+    size_t total() const { return (size_t)n_total; }
+    int slices(int m, int n) const { return m != n ? 16 : (F - 16 * m < 16 ? F - 16 * m : 16) - 1; }
+    int rows_in(int l) const { return l == 1 ? F * k + G : width[l - 1]; }          // the caller's n_{l-1}
+    size_t pair_row(int i, int j) const { return (size_t)tile_off[i / 16][j / 16] + (i % 16) * 16 + j % 16; }
+    static const char *name(int a) { return a == 0 ? "W" : (a == 1 ? "b" : "u"); }
+    template <class Fn> void each(Fn f) const {
+        for (int l = 1; l <= L; ++l) {
+            const int nl = width[l];
+            int pi = 0, pj = 0;          // the pair of the caller's row, walked with it
+            for (int i = 0; i < rows_in(l); ++i) {
+                size_t row = (size_t)i;
+                if (l == 1 && i < F * k) row = (size_t)(i / k) * Kp + i % k;
+                else if (l == 1) {
+                    if (++pj >= F) pj = ++pi + 1;
+                    row = pair_row(pi, pj);
+                }
+                for (int j = 0; j < nl; ++j) f(0, l - 1, (size_t)i * nl + j, woff[l - 1] + row * nl + j);
+            }
+            for (int j = 0; j < nl; ++j) f(1, l - 1, (size_t)j, (size_t)boff[l - 1] + j);
+        }
+        for (int j = 0; j < width[L]; ++j) f(2, 0, (size_t)j, (size_t)uoff + j);
+    }
+};
+
 // the caller's arrays -> the device's one array; src(array, layer): the array's doubles.  The elements no slot maps to: `pad`
 template <class Map, class Src>
 std::vector<float> pack_slots(const Map &m, Src src, float pad) {

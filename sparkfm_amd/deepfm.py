@@ -63,12 +63,12 @@ class DeepFMModel(FieldModel):
     def get_params(self):
         """(w0, w, v, layers, u), layers a list of (W_l, b_l)."""
         w0, (w, v, Ws, bs, u) = C.c_double(), self._zeros()
-        _ffi.check(_ffi.load().fmhip_deepfm_model_get_params(self._h, C.byref(w0), _ffi.ptr(w), _ffi.ptr(v), _pointers(Ws), _pointers(bs), _ffi.ptr(u)))
+        self._call("model_get_params", self._h, C.byref(w0), _ffi.ptr(w), _ffi.ptr(v), _pointers(Ws), _pointers(bs), _ffi.ptr(u))
         return w0.value, w, v, list(zip(Ws, bs)), u
 
     def set_params(self, w0, w, v, layers, u):
         w, v, Ws, bs, u = self._checked("", w, v, layers, u)
-        _ffi.check(_ffi.load().fmhip_deepfm_model_set_params(self._h, float(w0), _ffi.ptr(w), _ffi.ptr(v), _pointers(Ws), _pointers(bs), _ffi.ptr(u)))
+        self._call("model_set_params", self._h, float(w0), _ffi.ptr(w), _ffi.ptr(v), _pointers(Ws), _pointers(bs), _ffi.ptr(u))
 
     w0 = property(lambda self: self.get_params()[0])
     w = property(lambda self: self.get_params()[1])
@@ -79,12 +79,12 @@ class DeepFMModel(FieldModel):
     def adagrad_state(self):
         """(n0, nw, nv, [(nW_l, nb_l)], nu): AdaGrad's accumulators, shaped like the parameters (a model under SGD raises)."""
         n0, (nw, nv, Ws, bs, nu) = C.c_double(), self._zeros()
-        _ffi.check(_ffi.load().fmhip_deepfm_model_get_accumulators(self._h, C.byref(n0), _ffi.ptr(nw), _ffi.ptr(nv), _pointers(Ws), _pointers(bs), _ffi.ptr(nu)))
+        self._call("model_get_accumulators", self._h, C.byref(n0), _ffi.ptr(nw), _ffi.ptr(nv), _pointers(Ws), _pointers(bs), _ffi.ptr(nu))
         return n0.value, nw, nv, list(zip(Ws, bs)), nu
 
     def set_adagrad_state(self, n0, nw, nv, nlayers, nu):
         nw, nv, Ws, bs, nu = self._checked("n", nw, nv, nlayers, nu)
-        _ffi.check(_ffi.load().fmhip_deepfm_model_set_accumulators(self._h, float(n0), _ffi.ptr(nw), _ffi.ptr(nv), _pointers(Ws), _pointers(bs), _ffi.ptr(nu)))
+        self._call("model_set_accumulators", self._h, float(n0), _ffi.ptr(nw), _ffi.ptr(nv), _pointers(Ws), _pointers(bs), _ffi.ptr(nu))
 
 
 class HipDeepFM(FieldLearner):
